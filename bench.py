@@ -8,12 +8,22 @@ clustering -> rochade_refine -> k/phi filter, kernels K1..K4) over one batch of 
 2048 frames on 8 GPUs) and the only collective is the RCCL gather of the result slabs to rank 0
 (one collective per step; a second pass with --grouped-gather steps per collective is reported beside it).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  value = pixels of all ranks through the chain per second
 (Mpix/s), inputs resident in HBM, over the K timed steps (wall clock between two fences);
+ms_per_step = the same wall clock over K.
+
+A plain run does only that: render the frames, settle, W warm-up steps, the K timed steps
+(no profiling events among them), the completeness check of the last step's results
+(gather_check), --dump-outputs, the line.  --dump-outputs DIR writes the last timed step's
+results as rank 0 receives them (dump_outputs below).  Everything else below -- per-step
+events, roofline, per-kernel breakdown, oracle checks, CPU baseline, the pipelined and
+grouped-gather passes, the extra configurations and legs -- runs with --full only, as
+described:
+
 ms_per_step_median = median of the K per-step device times (events between the steps).
 roofline = K1 (the dominant kernel): algorithmic bytes per launch / average launch duration from
 hipEvents recorded on the launch stream inside the timed region (every 5th step: the events
@@ -109,7 +119,49 @@ def parse_args(argv=None):
                          "device; halved until it fits a quarter of the host memory this process may still take)")
     ap.add_argument("--pmc-traffic", type=float, default=None,
                     help="HBM bytes per K1 launch from a separate rocprofv3 --pmc run (profiles/)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-step events, roofline, per-kernel breakdown, oracle checks, CPU baseline, "
+                         "the pipelined / grouped-gather passes and the extra configurations and legs (the --no-* options and "
+                         "--extra-pipeline / --grouped-gather select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (rank 0: every rank's frames) as DIR/*.npy, float32 / float64, "
+                         "at most 64 MB (a seeded sample of whole frames beyond that)")
     return ap.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0xA9121D  # which frames a dump over the budget keeps (the renderer's seed base: fixed, like the frames)
+
+
+def dump_outputs(out_dir, gathered, frames_per_rank):
+    """The last timed step's results as a caller of the timed path receives them (rank 0: every rank's slab and frame table)
+    -> out_dir/saddles.npy  float32 [n, 5]: x, y, k, theta, phi of every saddle, frame after frame (global frame order)
+       out_dir/frames.npy   float64 [f, 4]: global frame index, saddle count, status word, clusters of every frame dumped
+    The slab offsets are layout, not results, and are left out.  Over DUMP_BUDGET_BYTES, a seeded sample of whole frames
+    (the same frames for the same arguments) is written.  Returns a summary for the result line."""
+    import numpy as np
+    from aprilgrid_rs_amd import sharding
+    gs, gt = gathered
+    lists, rows = [], []
+    for r in range(len(gt)):
+        t = gt[r].cpu().numpy()
+        for j, s in enumerate(sharding.unpack_frames(gs[r], gt[r])):
+            lists.append(np.zeros((0, 5), np.float32) if s is None else s)
+            rows.append((r * frames_per_rank + j, t[j, 0], t[j, 2], t[j, 3]))
+    nbytes = [l.nbytes + 32 for l in lists]
+    keep = list(range(len(lists)))
+    if sum(nbytes) > DUMP_BUDGET_BYTES:
+        keep, used = [], 0
+        for i in np.random.default_rng(DUMP_SAMPLE_SEED).permutation(len(lists)):
+            if used + nbytes[i] <= DUMP_BUDGET_BYTES:
+                keep.append(int(i))
+                used += nbytes[i]
+        keep.sort()
+    os.makedirs(out_dir, exist_ok=True)
+    saddles = np.concatenate([lists[i] for i in keep]) if keep else np.zeros((0, 5), np.float32)
+    np.save(os.path.join(out_dir, "saddles.npy"), np.ascontiguousarray(saddles, np.float32))
+    np.save(os.path.join(out_dir, "frames.npy"), np.array([rows[i] for i in keep], np.float64).reshape(-1, 4))
+    return {"dir": out_dir, "frames": len(keep), "of_frames": len(lists), "saddles": int(len(saddles))}
 
 
 def make_workload(first_frame, n_frames, width, height, fmt, unique, noise, device):
@@ -840,14 +892,16 @@ def main(argv=None):
     saddles_per_frame = float(tb[:, 0].mean())
     clusters_per_frame = float(tb[:, 3].mean())
 
-    # timed region: hipEvents (on the launch stream) around K1 only -- 2 records per step -- and one
+    # timed region (--full): hipEvents (on the launch stream) around K1 only -- 2 records per step -- and one
     # event between the steps (strictly serial: the chain launches on the current stream)
     # (an event pair costs the stream two ~5 us gaps around the kernel: K1 of every 5th step is timed)
-    for d in pipe.dets:
-        d.set_option("profile_stride", 5 if args.steps >= 20 else 1)
-        d.profile_enable(1)
-        d.profile_reset()
-    serial = pipe.depth == 1
+    # A plain run times the steps alone.
+    if args.full:
+        for d in pipe.dets:
+            d.set_option("profile_stride", 5 if args.steps >= 20 else 1)
+            d.profile_enable(1)
+            d.profile_reset()
+    serial = pipe.depth == 1 and args.full
     evs = [rt.event() for _ in range(args.steps + 1)] if serial else []
     fence()
     t0 = time.perf_counter()
@@ -861,7 +915,7 @@ def main(argv=None):
     dt = time.perf_counter() - t0
     per_step = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)] if serial else []
     k1_ms, k1_n = 0.0, 0
-    for d in pipe.dets:
+    for d in pipe.dets if args.full else []:
         ms, n = d.profile_read()["k_blur_hessian"]
         k1_ms, k1_n = k1_ms + ms, k1_n + n
         d.profile_enable(0)
@@ -884,7 +938,7 @@ def main(argv=None):
         assert all(a.tobytes() == b.tobytes() for a, b in zip(mine, own)), "rank 0's gathered slab differs from its own results"
         gather_check = {"ranks": world, "frames": world * F, "saddles": tot,
                         "through_collective": bool(pipe.gather.multi), "backend": rt.backend if pipe.gather.multi else None}
-        if world > 1 and not args.no_verify:
+        if world > 1 and args.full and not args.no_verify:
             # first frame of every other rank, re-rendered here from its seed, against the oracle
             from aprilgrid_rs_amd import synth
             for r in range(1, world):
@@ -892,13 +946,14 @@ def main(argv=None):
                                            pure_noise=args.noise)
                 verify_against_oracle(sharding.unpack_frames(gs[r], gt[r])[:1], host_view(fr, args.format), "rank %d" % r)
             gather_check["oracle_checked_remote_frames"] = world - 1
+        dumped = dump_outputs(args.dump_outputs, gathered, F) if args.dump_outputs else None
 
-    # separate, untimed pass for the per-kernel breakdown: one detector, strictly serial, events
+    # --full: separate, untimed pass for the per-kernel breakdown: one detector, strictly serial, events
     # around every launch (each kernel alone on the GPU)
     det = pipe.dets[0]
-    out_s, out_t = sharding.alloc_result_buffers(F, dev, slab)
+    out_s, out_t = sharding.alloc_result_buffers(F, dev, slab) if args.full else (None, None)
     prof = {}
-    names = list(det.profile_read().keys())
+    names = list(det.profile_read().keys()) if args.full else []
     for k, name in enumerate(names):  # one kernel per pass, every 5th batch: everything else stays back to back
         det.set_option("profile_kernel", k)
         det.set_option("profile_stride", 5 if args.steps >= 20 else 1)
@@ -908,15 +963,16 @@ def main(argv=None):
             det.saddles_batch_enqueue_to(frames, out_s, out_t)
         fence()
         prof[name] = det.profile_read()[name]
-    prof = {k: v for k, v in prof.items() if v[1]}  # the launches this batch size takes (256 frames: K1, k_verify_seeds, k_sparse_frame)
-    det.profile_enable(0)
-    det.set_option("profile_kernel", 0)
-    det.set_option("profile_stride", 1)
+    if args.full:
+        prof = {k: v for k, v in prof.items() if v[1]}  # the launches this batch size takes (256 frames: K1, k_verify_seeds, k_sparse_frame)
+        det.profile_enable(0)
+        det.set_option("profile_kernel", 0)
+        det.set_option("profile_stride", 1)
     rows_per_seg = det.get_option("k1_rows_per_segment")
 
-    # N = 1: the same K steps again with several batches in flight (reported as "pipelined")
+    # N = 1, --full: the same K steps again with several batches in flight (reported as "pipelined")
     pipelined = None
-    if world == 1 and args.extra_pipeline > 1 and args.pipeline == 1:
+    if args.full and world == 1 and args.extra_pipeline > 1 and args.pipeline == 1:
         pipe2 = sharding.ChainPipeline(A.TagFamily.T36H11, F, dev, depth=args.extra_pipeline, dst=0, slab_records=slab)
         t_settle = time.perf_counter()  # same untimed settle as the main pass: fresh workspaces, clocks
         while True:
@@ -946,10 +1002,10 @@ def main(argv=None):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
 
-    # N > 1: the same K steps again with the slabs of --grouped-gather consecutive steps per collective (every rank
+    # N > 1, --full: the same K steps again with the slabs of --grouped-gather consecutive steps per collective (every rank
     # walks the same sequence; reported beside `value`, which stays on one collective per step)
     grouped = None
-    if world > 1 and args.grouped_gather > 1 and args.gather_steps == 1 and args.gather_every <= 1 and args.pipeline == 1:
+    if args.full and world > 1 and args.grouped_gather > 1 and args.gather_steps == 1 and args.gather_every <= 1 and args.pipeline == 1:
         pipe_g = sharding.ChainPipeline(A.TagFamily.T36H11, F, dev, depth=1, dst=0, slab_records=slab,
                                         detector_cls=rt.detector_cls, steps_per_gather=args.grouped_gather)
 
@@ -981,44 +1037,45 @@ def main(argv=None):
         total_px = px_per_step_rank * world * args.steps
         ms_per_step = 1e3 * dt / args.steps
         mpix = total_px / dt / 1e6
-        in_b = IN_BYTES[args.format]
-        k1_alone_ms = prof["k_blur_hessian"][0] / max(prof["k_blur_hessian"][1], 1)
-        if serial and k1_n:  # the blur kernel's figure of the breakdown is the one measured inside the timed region
-            prof["k_blur_hessian"] = (k1_ms, k1_n)
-        chain_ms = sum(v[0] / max(v[1], 1) for v in prof.values())
-        traffic, traffic_src = args.pmc_traffic, "--pmc-traffic" if args.pmc_traffic else None
-        if traffic is None and world == 1:
-            traffic, traffic_src = recorded_traffic("%dx%dx%d_%s%s" % (F, W, H, args.format, "_noise" if args.noise else ""))
-        a_mat = in_b + 12  # SURVEY.md 8(d) A_mat: input + blur write + response write + response re-read
-        # the bytes THIS design is built to move per pixel (the response plane is never materialised): input +
-        # blur write + mask write (K1) + mask re-read (K2) + 0.125 for the sparse stages' algorithmic gathers and
-        # lists (about 970 nine-row windows and 5 800 3x3 re-tests per megapixel frame): 5.375 B/px for L8
-        a_design = in_b + 4 + 0.125 + 0.125 + 0.125
-        a_min = 2 * in_b  # SURVEY.md 8(d) A_min: the input read twice, nothing dense written
-        roof = k1_roofline(px_per_step_rank, in_b, k1_ms, k1_n, traffic, traffic_src)
-        # the same kernel alone on the GPU (serial pass below the timed region): with
-        # --pipeline > 1 the timed launches share the chip with another step's sparse kernels
-        if world == 1:  # the same box's plain copy rate, measured now: K1's HBM traffic against it
-            copy_gbps = box_copy_gbps(torch, dev)
-            roof["copy_GBps_this_box"] = round(copy_gbps, 1)
-            if traffic:
-                roof["traffic_frac_of_copy_this_box"] = round(traffic / (roof["avg_launch_ms"] * 1e-3) / 1e9 / copy_gbps, 4)
-        # the CHAIN against the roofline -- bytes the design moves (and A_min beside it) over the
-        # whole step as timed (first launch of K1 to the end of the last kernel, ms_per_step), against 8 TB/s
-        step_s = ms_per_step * 1e-3  # every rank runs its own 256 frames in this time
-        roof["chain_design_bytes_per_px"] = a_design
-        roof["chain_GBps"] = round(px_per_step_rank * a_design / step_s / 1e9, 1)
-        roof["chain_frac"] = round(px_per_step_rank * a_design / step_s / 1e9 / HBM_PEAK_GBPS, 4)
-        roof["a_min_bytes_per_px"] = a_min
-        roof["a_min_frac"] = round(px_per_step_rank * a_min / step_s / 1e9 / HBM_PEAK_GBPS, 4)
-        if pipelined:  # the same over the step with several batches in flight (reported beside, never `value`)
-            pipelined["chain_frac"] = round(px_per_step_rank * a_design / (pipelined["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
-            roof["chain_frac_in_flight"] = pipelined["chain_frac"]
-        roof["chain_note"] = ("chain_frac = design bytes per GPU / ms_per_step / 8 TB/s (what the whole step achieves); frac = the blur "
-                              "kernel alone; a_min_frac = the fused lower bound of SURVEY.md 8(d) over the same step time")
-        if not serial:  # batches in flight: the timed launches shared the chip; the serial pass gives the kernel alone
-            roof["alone_avg_launch_ms"] = round(k1_alone_ms, 5)
-            roof["alone_frac"] = round(roof["bytes_per_launch"] / (k1_alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
+        if args.full:  # roofline and breakdown figures
+            in_b = IN_BYTES[args.format]
+            k1_alone_ms = prof["k_blur_hessian"][0] / max(prof["k_blur_hessian"][1], 1)
+            if serial and k1_n:  # the blur kernel's figure of the breakdown is the one measured inside the timed region
+                prof["k_blur_hessian"] = (k1_ms, k1_n)
+            chain_ms = sum(v[0] / max(v[1], 1) for v in prof.values())
+            traffic, traffic_src = args.pmc_traffic, "--pmc-traffic" if args.pmc_traffic else None
+            if traffic is None and world == 1:
+                traffic, traffic_src = recorded_traffic("%dx%dx%d_%s%s" % (F, W, H, args.format, "_noise" if args.noise else ""))
+            a_mat = in_b + 12  # SURVEY.md 8(d) A_mat: input + blur write + response write + response re-read
+            # the bytes THIS design is built to move per pixel (the response plane is never materialised): input +
+            # blur write + mask write (K1) + mask re-read (K2) + 0.125 for the sparse stages' algorithmic gathers and
+            # lists (about 970 nine-row windows and 5 800 3x3 re-tests per megapixel frame): 5.375 B/px for L8
+            a_design = in_b + 4 + 0.125 + 0.125 + 0.125
+            a_min = 2 * in_b  # SURVEY.md 8(d) A_min: the input read twice, nothing dense written
+            roof = k1_roofline(px_per_step_rank, in_b, k1_ms, k1_n, traffic, traffic_src)
+            # the same kernel alone on the GPU (serial pass below the timed region): with
+            # --pipeline > 1 the timed launches share the chip with another step's sparse kernels
+            if world == 1:  # the same box's plain copy rate, measured now: K1's HBM traffic against it
+                copy_gbps = box_copy_gbps(torch, dev)
+                roof["copy_GBps_this_box"] = round(copy_gbps, 1)
+                if traffic:
+                    roof["traffic_frac_of_copy_this_box"] = round(traffic / (roof["avg_launch_ms"] * 1e-3) / 1e9 / copy_gbps, 4)
+            # the CHAIN against the roofline -- bytes the design moves (and A_min beside it) over the
+            # whole step as timed (first launch of K1 to the end of the last kernel, ms_per_step), against 8 TB/s
+            step_s = ms_per_step * 1e-3  # every rank runs its own 256 frames in this time
+            roof["chain_design_bytes_per_px"] = a_design
+            roof["chain_GBps"] = round(px_per_step_rank * a_design / step_s / 1e9, 1)
+            roof["chain_frac"] = round(px_per_step_rank * a_design / step_s / 1e9 / HBM_PEAK_GBPS, 4)
+            roof["a_min_bytes_per_px"] = a_min
+            roof["a_min_frac"] = round(px_per_step_rank * a_min / step_s / 1e9 / HBM_PEAK_GBPS, 4)
+            if pipelined:  # the same over the step with several batches in flight (reported beside, never `value`)
+                pipelined["chain_frac"] = round(px_per_step_rank * a_design / (pipelined["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
+                roof["chain_frac_in_flight"] = pipelined["chain_frac"]
+            roof["chain_note"] = ("chain_frac = design bytes per GPU / ms_per_step / 8 TB/s (what the whole step achieves); frac = the blur "
+                                  "kernel alone; a_min_frac = the fused lower bound of SURVEY.md 8(d) over the same step time")
+            if not serial:  # batches in flight: the timed launches shared the chip; the serial pass gives the kernel alone
+                roof["alone_avg_launch_ms"] = round(k1_alone_ms, 5)
+                roof["alone_frac"] = round(roof["bytes_per_launch"] / (k1_alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
         result = {
             "metric": ("STUB -- NOT A MEASUREMENT (CPU oracle behind the enqueue call, control-flow test) -- " if stub else "")
                       + "Mpix/s through the saddle chain (blur->threshold->gradient->saddle), frames resident in HBM",
@@ -1048,8 +1105,11 @@ def main(argv=None):
                 "batches_in_flight": pipe.depth,
                 "k1_rows_per_segment": rows_per_seg,
             },
-            "roofline": roof,
-            "chain": {
+            "gather_check": gather_check,
+        }
+        if args.full:
+            result["roofline"] = roof
+            result["chain"] = {
                 "a_mat_bytes_per_px": a_mat,
                 "kernel_ms_per_step": {k: round(v[0] / max(v[1], 1), 5) for k, v in prof.items()},
                 "sparse_path": {1: "k_verify_seeds + k_flood_refine + k_rare (three launches)",
@@ -1069,9 +1129,7 @@ def main(argv=None):
                         "to back on the stream): the blur kernel inside the timed region (= roofline.avg_launch_ms), the "
                         "others in untimed passes of their own; each figure includes the ~2 us the pair itself costs; the "
                         "kernels' durations by rocprofv3 --kernel-trace --stats are under profiles/",
-            },
-            "gather_check": gather_check,
-        }
+            }
         if per_step:
             result["ms_per_step_median"] = round(statistics.median(per_step), 4)
             result["ms_per_step_min"] = round(min(per_step), 4)
@@ -1079,7 +1137,9 @@ def main(argv=None):
             result["pipelined"] = pipelined
         if grouped:
             result["grouped_gather"] = grouped
-        if world == 1:
+        if dumped:
+            result["dumped_outputs"] = dumped
+        if args.full and world == 1:
             host = host_view(frames[:uniq], args.format)
             if not args.no_verify:
                 result["verified_frames"] = verify_against_oracle(own[:uniq], host, "main workload",
@@ -1090,7 +1150,7 @@ def main(argv=None):
                 result["cpu_baseline"]["host_cores_shown"] = os.cpu_count()
     pipe.close()
     del pipe
-    if world == 1 and rank == 0 and not args.no_extra:
+    if args.full and world == 1 and rank == 0 and not args.no_extra:
         del frames, out_s, out_t
         torch.cuda.empty_cache()
         st = max(10, args.steps // 2)

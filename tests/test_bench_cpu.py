@@ -30,7 +30,7 @@ def test_plain_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update({"AGX_BENCH_STUB": "1", "OMP_NUM_THREADS": "1"})
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--frames", "2",
-           "--width", "192", "--height", "128", "--settle-ms", "30", "--no-extra", "--no-cpu-baseline"]
+           "--width", "192", "--height", "128", "--settle-ms", "30", "--full", "--no-extra", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd="/tmp")  # (from any directory)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -84,7 +84,7 @@ def test_bench_two_rank_control_flow_under_gloo():
     env = {**os.environ, "AGX_BENCH_STUB": "1", "PYTHONPATH": ROOT, "OMP_NUM_THREADS": "1"}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--frames", "2", "--width", "192", "--height", "128", "--settle-ms", "30", "--no-extra", "--no-cpu-baseline"]
+           "--frames", "2", "--width", "192", "--height", "128", "--settle-ms", "30", "--full", "--no-extra", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -108,7 +108,7 @@ def _launch(world, extra, timeout=900):
     s.close()
     env = {**os.environ, "AGX_BENCH_STUB": "1", "PYTHONPATH": ROOT, "OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1"}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world)] + extra
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--full"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=timeout, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -185,3 +185,51 @@ def test_the_stream_of_the_end_to_end_leg_is_sized_from_the_memory_the_process_m
     avail = bench.host_memory_available()
     total = next(int(l.split()[1]) * 1024 for l in open("/proc/meminfo") if l.startswith("MemTotal:"))
     assert avail is not None and 0 < avail <= total
+
+
+def test_a_plain_run_reports_the_headline_only_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` (stub backend): the line carries the headline fields, --steps sets the timed steps,
+    none of the --full figures are computed, and --dump-outputs writes the last step's results identically in two runs."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update({"AGX_BENCH_STUB": "1", "OMP_NUM_THREADS": "1"})
+    outs = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", "3",
+               "--width", "192", "--height", "128", "--settle-ms", "0", "--dump-outputs", str(tmp_path / run)]
+        r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in out, k
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["higher_is_better"] is True
+        for k in ("roofline", "chain", "ms_per_step_median", "pipelined", "verified_frames", "cpu_baseline", "extra_configs",
+                  "host_boundary", "detect_end_to_end"):
+            assert k not in out, k
+        assert out["dumped_outputs"]["frames"] == 3
+        saddles, frames = np.load(tmp_path / run / "saddles.npy"), np.load(tmp_path / run / "frames.npy")
+        assert saddles.dtype == np.float32 and saddles.shape[1] == 5 and frames.dtype == np.float64 and frames.shape == (3, 4)
+        assert list(frames[:, 0]) == [0, 1, 2] and frames[:, 1].sum() == len(saddles) > 0
+        outs.append((saddles, frames))
+    assert all(np.array_equal(x.view(np.uint8), y.view(np.uint8)) for x, y in zip(*outs))
+
+
+def test_a_dump_over_the_budget_keeps_a_seeded_sample_of_whole_frames(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import torch
+    import bench
+    from aprilgrid_rs_amd import sharding
+    n, per = 6, 10
+    flat, saddles, table = sharding.alloc_packed(n, "cpu", slab_records=per)
+    saddles[: n * per] = torch.arange(n * per * 5, dtype=torch.float32).view(-1, 5)
+    table[:, 0], table[:, 1], table[:, 2], table[:, 3] = per, torch.arange(n) * per, 0, 1
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 3 * (per * 20 + 32))
+    got = [bench.dump_outputs(str(tmp_path / d), ([saddles], [table]), n) for d in ("a", "b")]
+    assert got[0]["frames"] == 3 and got[0]["of_frames"] == n and got[0]["saddles"] == 3 * per
+    f = np.load(tmp_path / "a" / "frames.npy")
+    assert np.array_equal(f, np.load(tmp_path / "b" / "frames.npy")) and list(f[:, 0]) == sorted(f[:, 0])
+    s = np.load(tmp_path / "a" / "saddles.npy")
+    want = np.concatenate([saddles[int(i) * per:(int(i) + 1) * per].numpy() for i in f[:, 0]])
+    assert np.array_equal(s, want)

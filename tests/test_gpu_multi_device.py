@@ -327,7 +327,7 @@ def test_bench_sends_its_slabs_through_nccl_with_a_world_of_one(tmp_path):
     from tests.util import ROOT
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29547")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--collective-world-1", "--steps", "4", "--warmup", "1",
-                        "--frames", "64", "--settle-ms", "0", "--no-extra", "--no-cpu-baseline", "--extra-pipeline", "0"],
+                        "--frames", "64", "--settle-ms", "0", "--full", "--no-extra", "--no-cpu-baseline", "--extra-pipeline", "0"],
                        capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -34,4 +34,4 @@ for k, v in agg.items():
 PY
 done
 cat $OUT/traffic.txt
-python3 bench.py --steps 20 --warmup 3 > $OUT/bench.json 2>/dev/null; cat $OUT/bench.json | cut -c1-400
+python3 bench.py --steps 20 --warmup 3 --full > $OUT/bench.json 2>/dev/null; cat $OUT/bench.json | cut -c1-400

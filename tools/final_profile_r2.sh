@@ -42,4 +42,4 @@ pmc L8
 pmc RGB8 --format RGB8 --unique 64
 pmc 4K --width 3840 --height 2160 --frames 32 --unique 8
 cat $OUT/traffic.txt
-python3 bench.py --steps 50 --warmup 3 > $OUT/bench.json 2>/dev/null; cut -c1-300 $OUT/bench.json
+python3 bench.py --steps 50 --warmup 3 --full > $OUT/bench.json 2>/dev/null; cut -c1-300 $OUT/bench.json

@@ -62,5 +62,5 @@ print("  per batch: %.1f us of wall time (%d batches)" % (tot / 1e3 / n1, n1))
 PY
 cat $OUT/pipeline3_overlap.txt
 rm -rf $D
-python3 bench.py --steps 50 --warmup 3 > $OUT/bench.json 2>/dev/null; cut -c1-300 $OUT/bench.json
+python3 bench.py --steps 50 --warmup 3 --full > $OUT/bench.json 2>/dev/null; cut -c1-300 $OUT/bench.json
 python3 tools/kernel_resources.py > $OUT/kernel_resources.txt 2>/dev/null

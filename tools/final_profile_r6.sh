@@ -89,7 +89,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tail_$TAG -- python
 S=$(find /tmp/tail_$TAG -name "*kernel_stats.csv" | head -1); (head -1 $S; grep "agx::" $S) > $OUT/device_tail_kernel_stats.csv; cut -c1-130 $OUT/device_tail_kernel_stats.csv
 echo "== the driver's command"
 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2>/dev/null; cut -c1-200 $OUT/bench_driver_command.json
-python3 bench.py --steps 50 --warmup 3 > $OUT/bench.json 2>/dev/null; cut -c1-300 $OUT/bench.json
+python3 bench.py --steps 50 --warmup 3 --full > $OUT/bench.json 2>/dev/null; cut -c1-300 $OUT/bench.json
 python3 tools/kernel_resources.py > $OUT/kernel_resources.txt 2>/dev/null
 echo "== one rank through RCCL's gather, a collective per step (stdout must be the JSON line alone)"
 python3 bench.py --gpus 1 --steps 20 --warmup 5 --collective-world-1 --no-extra --no-cpu-baseline > $OUT/bench_collective_world_1.json 2>/dev/null; wc -l $OUT/bench_collective_world_1.json

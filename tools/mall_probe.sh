@@ -1,6 +1,7 @@
 set -e
-mkdir -p gpurun_out/mall
+OUT=${1:?usage: tools/mall_probe.sh <output directory>}
+mkdir -p "$OUT"
 for f in 16 32 48 64 128 256; do
-  python bench.py --frames $f --steps 60 --warmup 5 --no-extra --no-cpu-baseline --no-verify > gpurun_out/mall/f$f.json 2> gpurun_out/mall/f$f.err
+  python bench.py --frames $f --steps 60 --warmup 5 --full --no-extra --no-cpu-baseline --no-verify > "$OUT/f$f.json" 2> "$OUT/f$f.err"
   echo done $f
 done
