@@ -59,6 +59,10 @@ SYMBOLS = {
     "agx_debug_cgroup_cpu_quota": (C.c_int, [C.c_char_p, C.c_char_p]),
     "agx_detect_batch": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, _P, C.c_uint32,
                                    _P, _P, C.c_int]),
+    "agx_detect_batch_enqueue": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_uint32]),
+    "agx_detect_batch_enqueue_to": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, _P, C.c_uint32,
+                                              _P, _P]),
+    "agx_detect_batch_fetch": (C.c_int, [_P, _P, _P, _P, C.c_int]),
     "agx_group_create": (C.c_int, [C.c_int, C.POINTER(Params), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "agx_group_destroy": (None, [_P]),
     "agx_group_size": (C.c_int, [_P]),

@@ -392,7 +392,7 @@ static int detect_batch_device_tail(agx_detector *det, const void *frames, const
             luma_row = (size_t)width;
             luma_frame = (size_t)width * (size_t)height;
         }
-        rc = agx_internal_enqueue_tail(det, d_luma, luma_row, luma_frame, std::max(cap_per_frame, 1u));
+        rc = agx_internal_enqueue_tail(det, d_luma, luma_row, luma_frame, std::max(cap_per_frame, 1u), 0);
         if (rc) break;
         const agx_tag *tags = nullptr;
         const uint32_t *table = nullptr;
@@ -705,4 +705,246 @@ static int detect_batch_impl(agx_detector *det, const void *frames, const void *
     if (rc) return rc;
     if (nomem.load()) return AGX_ERR_NOMEM;
     return first_bad.load();
+}
+
+// ---- agx_detect_batch_enqueue / _enqueue_to / agx_detect_batch_fetch: detect over a batch resident in device memory ---------
+// The enqueue puts the chain, to_luma8 (L16 / RGB8: k_luma8) and, where this process may use it, the device tail on the
+// detector's stream and returns without waiting.  The fetch waits, takes the device tail's tags, and runs the host tail on the
+// pool for the frames the kernel handed back -- every frame without the device tail -- from the chain's compact saddle lists and
+// the u8 luma of those frames only, copied down from the device.  No frame ever exists in host memory as the caller's pixels.
+int agx::detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                             size_t frame_stride_bytes, int format, uint32_t cap_per_frame, bool to_device, agx_tag *d_tags,
+                             uint32_t *d_counts, int *d_status)
+{
+    // option "device_tail" -1 (default) or 1: the device tail wherever this process may use it (no batch-size rule: with the frames
+    // on the device there is no upload for the host tail to hide behind); 0, or a tail this process may not use: the host tail
+    const int tail_mode = agx_internal_device_tail(det);
+    bool on_device = tail_mode != 0;
+    if (on_device) {
+        const int prc = agx_internal_tail_prepare(det);
+        if (prc && tail_mode == 1) return prc;
+        if (prc) on_device = false;
+    }
+    int rc = agx_saddles_batch_enqueue(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format);
+    if (rc) return rc;
+    const uint8_t *d_luma = static_cast<const uint8_t *>(d_frames);  // detector.rs:507: L8 frames are their own u8 luma
+    size_t luma_row = row_stride_bytes, luma_frame = frame_stride_bytes;
+    if (format != AGX_L8) {
+        rc = agx_internal_chunk_luma8(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, 0, 1,
+                                      (size_t)n_frames, nullptr, &d_luma);
+        luma_row = (size_t)width;
+        luma_frame = (size_t)width * (size_t)height;
+    }
+    if (!rc && on_device) rc = agx_internal_enqueue_tail(det, d_luma, luma_row, luma_frame, std::max(cap_per_frame, 1u), to_device ? 1 : 0);
+    if (!rc && to_device) {
+        if (on_device) {
+            rc = agx_internal_publish_tags(det, cap_per_frame, d_tags, d_counts, d_status);
+        } else {  // every frame is the fetch's: until then count 0, AGX_ERR_STATE
+            hipStream_t st = static_cast<hipStream_t>(agx_internal_stream(det));
+            if (hipMemsetD32Async(d_counts, 0, (size_t)n_frames, st) != hipSuccess ||
+                hipMemsetD32Async(d_status, AGX_ERR_STATE, (size_t)n_frames, st) != hipSuccess)
+                rc = AGX_ERR_HIP;
+        }
+    }
+    if (rc) {
+        agx_internal_abandon_batch(det);  // (nothing half-enqueued is left to be fetched)
+        return rc;
+    }
+    DetectPending &p = *agx_internal_detect_pending(det);
+    p.kind = to_device ? 2 : 1;
+    p.device_tail = on_device;
+    p.n_frames = n_frames;
+    p.width = width;
+    p.height = height;
+    p.cap = cap_per_frame;
+    p.d_luma = d_luma;
+    p.luma_row = luma_row;
+    p.luma_frame = luma_frame;
+    p.d_tags = d_tags;
+    p.d_counts = d_counts;
+    p.d_status = d_status;
+    return AGX_OK;
+}
+
+int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads)
+{
+    DetectPending &pend = *agx_internal_detect_pending(det);
+    const DetectPending b = pend;
+    if ((b.kind == 1 && !counts) || (out && b.cap && !counts)) return AGX_ERR_ARG;  // (the batch stays in flight)
+    if (b.kind == 1 && !out && b.cap) return AGX_ERR_ARG;
+    pend.kind = 0;  // resolved by this call, whatever happens below
+    const int n = b.n_frames, W = b.width, H = b.height;
+    const uint32_t cap = b.cap;
+    const bool to_dev = b.kind == 2;
+    const size_t plane = (size_t)W * (size_t)H;
+    hipStream_t stream = static_cast<hipStream_t>(agx_internal_stream(det));
+    const FamilyInfo *fam = static_cast<const FamilyInfo *>(agx_internal_family(det));
+    const int max_boards = agx_internal_max_boards(det);
+    if (n_threads <= 0) n_threads = agx_host_parallelism();
+    // every frame's result as the host knows it (the device arrays of _enqueue_to get the same), the frames the host tail takes,
+    // and (_enqueue_to) their tag rows until they are copied to the caller's device arrays
+    std::vector<uint32_t> cnt;
+    std::vector<int> st;
+    std::vector<int> host_frames;
+    std::vector<std::vector<agx_tag>> rows;
+    std::mutex m;
+    std::condition_variable cv;
+    int outstanding[2] = {0, 0};  // host tails of the frames in luma slot r not finished yet (guarded by m)
+    std::atomic<bool> nomem{false};
+    WorkerPool *pool = nullptr;
+    int rc = AGX_OK, n_fallback = 0, n_uncertain = 0;
+    try {
+        do {
+            if (hipSetDevice(agx_internal_device(det)) != hipSuccess) { rc = AGX_ERR_HIP; break; }
+            pool = static_cast<WorkerPool *>(agx_internal_pool(det, n_threads));
+            if (!pool) { rc = AGX_ERR_ARG; break; }
+            cnt.assign((size_t)n, 0u);
+            st.assign((size_t)n, AGX_OK);
+            std::vector<char> back((size_t)n, b.device_tail ? 0 : 1);  // 1 handed back, 2 handed back as uncertain
+            if (b.device_tail) {
+                const uint32_t *table = nullptr;
+                const agx_tag *tags = nullptr;
+                uint32_t tag_stride = 0;
+                std::vector<uint32_t> dtab;
+                if (to_dev) {  // the 16-byte table entry per frame, not the rows: those are in the caller's arrays already
+                    dtab.resize((size_t)n * 4);
+                    if (hipMemcpyAsync(dtab.data(), agx_internal_device_tail_table(det), dtab.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                       stream) != hipSuccess ||
+                        hipStreamSynchronize(stream) != hipSuccess) { rc = AGX_ERR_HIP; break; }
+                    table = dtab.data();
+                } else {
+                    rc = agx_internal_fetch_tail(det, &tags, &table, &tag_stride);  // waits for the device
+                    if (rc) break;
+                }
+                for (int f = 0; f < n; ++f) {
+                    const uint32_t ts = table[4 * f + 1], nt = table[4 * f];
+                    if (ts != TAIL_OK) {
+                        back[(size_t)f] = (ts & TAIL_UNCERTAIN) ? 2 : 1;
+                        continue;
+                    }
+                    cnt[(size_t)f] = nt;
+                    if (nt > cap) st[(size_t)f] = AGX_ERR_CAPACITY;  // (the kernel hands such frames back; never truncated either way)
+                    else if (!to_dev && nt) std::memcpy(out + (size_t)f * cap, tags + (size_t)f * tag_stride, (size_t)nt * sizeof(agx_tag));
+                }
+            }
+            if (std::none_of(back.begin(), back.end(), [](char c) { return c != 0; })) break;
+            // the saddle lists of the frames handed back (and the status of frames whose chain overflowed)
+            std::vector<uint32_t> ns((size_t)n), offs((size_t)n);
+            std::vector<int> fst((size_t)n);
+            const agx_saddle *records = nullptr;
+            rc = agx_internal_fetch_compact(det, &records, ns.data(), offs.data(), fst.data());
+            if (rc) break;
+            for (int f = 0; f < n; ++f) {
+                if (!back[(size_t)f]) continue;
+                if (fst[(size_t)f] != AGX_OK) {  // reported, never truncated (_enqueue_to: k_publish_tags has said so already)
+                    cnt[(size_t)f] = 0;
+                    st[(size_t)f] = fst[(size_t)f];
+                    continue;
+                }
+                if (b.device_tail) {
+                    ++n_fallback;
+                    n_uncertain += back[(size_t)f] == 2;
+                }
+                host_frames.push_back(f);
+            }
+            const int n_host = (int)host_frames.size();
+            if (!n_host) break;
+            if (to_dev) rows.resize((size_t)n_host);
+            // their u8 luma, copied down a group at a time into one of two pinned slots while the previous group's tails run
+            const int G = std::min(n_host, std::max(8, std::min(32, 2 * pool->size())));
+            const int n_slots = n_host > G ? 2 : 1;
+            uint8_t *h_luma = agx_internal_fetch_luma(det, (size_t)n_slots * (size_t)G * plane);
+            if (!h_luma) { rc = AGX_ERR_HIP; break; }
+            for (int c0 = 0, ci = 0; c0 < n_host && !rc; c0 += G, ++ci) {
+                const int nc = std::min(G, n_host - c0), r = ci % n_slots;
+                {
+                    std::unique_lock<std::mutex> lk(m);
+                    cv.wait(lk, [&] { return outstanding[r] == 0; });
+                }
+                uint8_t *slot = h_luma + (size_t)r * (size_t)G * plane;
+                bool ok = true;
+                for (int i = 0; i < nc && ok; ++i)
+                    ok = hipMemcpy2DAsync(slot + (size_t)i * plane, (size_t)W, b.d_luma + (size_t)host_frames[(size_t)(c0 + i)] * b.luma_frame,
+                                          b.luma_row, (size_t)W, (size_t)H, hipMemcpyDeviceToHost, stream) == hipSuccess;
+                if (!ok || hipStreamSynchronize(stream) != hipSuccess) { rc = AGX_ERR_HIP; break; }
+                {
+                    std::lock_guard<std::mutex> lk(m);
+                    outstanding[r] = nc;
+                }
+                int submitted = 0;
+                try {
+                    for (int i = 0; i < nc; ++i, ++submitted) {
+                        const int k = c0 + i, f = host_frames[(size_t)k];
+                        const uint8_t *g = slot + (size_t)i * plane;
+                        const agx_saddle *sp = records + offs[(size_t)f];
+                        const uint32_t n_s = ns[(size_t)f];
+                        pool->submit([=, &cnt, &st, &rows, &nomem, &m, &cv, &outstanding] {
+                            try {  // nothing unwinds out of a worker thread: host memory exhaustion becomes the frame's status
+                                const std::vector<agx_tag> &tg = detect_tail_scratch(*fam, max_boards, sp, n_s, g, W, H, (size_t)W);
+                                cnt[(size_t)f] = (uint32_t)tg.size();
+                                if (tg.size() > cap) st[(size_t)f] = AGX_ERR_CAPACITY;
+                                else if (to_dev) rows[(size_t)k].assign(tg.begin(), tg.end());
+                                else if (!tg.empty()) std::memcpy(out + (size_t)f * cap, tg.data(), tg.size() * sizeof(agx_tag));
+                            } catch (...) {
+                                cnt[(size_t)f] = 0;
+                                st[(size_t)f] = AGX_ERR_NOMEM;
+                                nomem.store(true);
+                            }
+                            bool last;
+                            {
+                                std::lock_guard<std::mutex> lk(m);
+                                last = --outstanding[r] == 0;
+                            }
+                            if (last) cv.notify_all();
+                        });
+                    }
+                } catch (...) {  // a task could not be queued: the slot's counter must not wait for tails that will never run
+                    std::lock_guard<std::mutex> lk(m);
+                    outstanding[r] -= nc - submitted;
+                    throw;
+                }
+            }
+        } while (false);
+    } catch (...) {
+        rc = AGX_ERR_NOMEM;
+    }
+    if (pool) (void)pool->wait();  // every tail (they read the luma slots and the compact list, and write cnt / st / rows)
+    if (!rc && nomem.load()) rc = AGX_ERR_NOMEM;
+    if (!rc && to_dev) {
+        // the host tail's frames into the caller's device arrays, on the detector's stream: rows, count, status (all frames at once
+        // where the host tail took every frame)
+        bool ok = true;
+        for (size_t k = 0; k < host_frames.size() && ok; ++k) {
+            const int f = host_frames[k];
+            if (st[(size_t)f] == AGX_OK && cnt[(size_t)f])
+                ok = hipMemcpyAsync(b.d_tags + (size_t)f * cap, rows[k].data(), (size_t)cnt[(size_t)f] * sizeof(agx_tag), hipMemcpyHostToDevice,
+                                    stream) == hipSuccess;
+            if (ok && b.device_tail)
+                ok = hipMemcpyAsync(b.d_counts + f, &cnt[(size_t)f], sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess &&
+                     hipMemcpyAsync(b.d_status + f, &st[(size_t)f], sizeof(int), hipMemcpyHostToDevice, stream) == hipSuccess;
+        }
+        if (ok && !b.device_tail)
+            ok = hipMemcpyAsync(b.d_counts, cnt.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess &&
+                 hipMemcpyAsync(b.d_status, st.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream) == hipSuccess;
+        // the caller's host arrays as well, if it passed any: the rows from the device arrays, counts and status as known here
+        if (ok && out && cap)
+            ok = hipMemcpyAsync(out, b.d_tags, (size_t)n * cap * sizeof(agx_tag), hipMemcpyDeviceToHost, stream) == hipSuccess;
+        if (!ok || hipStreamSynchronize(stream) != hipSuccess) rc = AGX_ERR_HIP;
+    }
+    agx_internal_abandon_batch(det);  // (waits for the stream; nothing of the batch is left to be fetched)
+    agx_internal_tail_stats(det, b.device_tail ? n : 0, n_fallback, n_uncertain);
+    if (rc) {  // the call failed as a whole: no frame's result is valid (as agx_detect_batch)
+        if (counts)
+            for (int f = 0; f < n; ++f) counts[f] = 0;
+        if (frame_status)
+            for (int f = 0; f < n; ++f) frame_status[f] = rc;
+        return rc;
+    }
+    int first_bad = AGX_OK;
+    for (int f = 0; f < n; ++f) {
+        if (counts) counts[f] = cnt[(size_t)f];
+        if (frame_status) frame_status[f] = st[(size_t)f];
+        if (first_bad == AGX_OK) first_bad = st[(size_t)f];
+    }
+    return first_bad;
 }

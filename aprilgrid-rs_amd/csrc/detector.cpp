@@ -77,7 +77,8 @@ struct agx_detector {
         bool host = false;     // pinned host memory (mapped when dev != nullptr)
         void *dev = nullptr;   // device address of the payload of a mapped host buffer
     };
-    enum { SB_STAGE, SB_LUMA_D, SB_LUMA_H, SB_CODES, SB_TAGS, SB_TAIL_TABLE, SB_COUNT };
+    // (SB_DTAGS .. SB_FETCH_LUMA: agx_detect_batch_enqueue_to's device tail results, agx_detect_batch_fetch's luma planes)
+    enum { SB_STAGE, SB_LUMA_D, SB_LUMA_H, SB_CODES, SB_TAGS, SB_TAIL_TABLE, SB_DTAGS, SB_DTABLE, SB_FETCH_LUMA, SB_COUNT };
     SideBuf side[SB_COUNT];
     // staging for the single-frame host API
     uint8_t *d_stage = nullptr;
@@ -135,6 +136,13 @@ struct agx_detector {
     size_t tail_frames = 0;
     uint32_t tail_tag_cap = 0;
     int last_tail_frames = 0, last_tail_fallbacks = 0, last_tail_uncertain = 0;  // of the last agx_detect_batch call
+    agx_tag *d_tail_tags = nullptr;     // agx_detect_batch_enqueue_to: device [dtail_frames][dtail_tag_cap]
+    uint32_t *d_tail_table = nullptr;   //                                device [dtail_frames][4]
+    size_t dtail_frames = 0;
+    uint32_t dtail_tag_cap = 0;
+    uint8_t *h_fetch_luma = nullptr;    // agx_detect_batch_fetch: pinned luma planes of the frames the host tail takes
+    size_t fetch_luma_bytes = 0;
+    agx::DetectPending detect;          // agx_detect_batch_enqueue / _to: the batch agx_detect_batch_fetch resolves
 
     std::string last_error;
 };
@@ -643,13 +651,14 @@ __attribute__((visibility("hidden"))) int agx_internal_upload_streams(agx_detect
 // device, then *records = the batch's compact list in the detector's pinned host mirror (valid until the next enqueue;
 // frame f's list = counts[f] records from offsets[f]) and status[f] = AGX_OK / AGX_ERR_CAPACITY (a device-side list of
 // the frame overflowed: its count is 0).  Returns AGX_OK, or the HIP / state error of the fetch.
+static int saddles_fetch_impl(agx_detector *det, agx_saddle *out, uint32_t cap_per_frame, uint32_t *counts, int *frame_status);
 __attribute__((visibility("hidden"))) int agx_internal_fetch_compact(agx_detector *det, const agx_saddle **records, uint32_t *counts,
                                                                      uint32_t *offsets, int *status)
 {
     const int n = det->enqueued ? det->args.n_frames : 0;
     // cap 0: counts and status only (a frame with any saddles reads "capacity" against cap 0: the real status is
     // derived from the counters below, with no limit on the list's length)
-    int rc = agx_saddles_batch_fetch(det, nullptr, 0, counts, status);
+    int rc = saddles_fetch_impl(det, nullptr, 0, counts, status);
     if (rc != AGX_OK && rc != AGX_ERR_CAPACITY) return rc;
     for (int f = 0; f < n; ++f) {
         const FrameCounters &c = det->h_ctr[f];
@@ -703,7 +712,7 @@ __attribute__((visibility("hidden"))) int agx_internal_tail_prepare(agx_detector
 }
 __attribute__((visibility("hidden"))) int agx_internal_tail_debug(const agx_detector *) { return tuning_env("AGX_TAIL_DEBUG", 0); }  // (read at create)
 __attribute__((visibility("hidden"))) int agx_internal_enqueue_tail(agx_detector *det, const void *d_luma, size_t luma_row_stride,
-                                                                    size_t luma_frame_stride, uint32_t tag_cap)
+                                                                    size_t luma_frame_stride, uint32_t tag_cap, int to_device)
 {
     if (!det->enqueued || det->external_out) return AGX_ERR_STATE;
     const ChainArgs &a = det->args;
@@ -713,7 +722,24 @@ __attribute__((visibility("hidden"))) int agx_internal_enqueue_tail(agx_detector
         const int rc = agx_internal_tail_prepare(det);
         if (rc) return rc;
     }
-    if ((size_t)a.n_frames > det->tail_frames || tag_cap > det->tail_tag_cap) {
+    if (to_device && ((size_t)a.n_frames > det->dtail_frames || tag_cap > det->dtail_tag_cap)) {  // (device memory: the same layout)
+        if (hipStreamSynchronize(det->stream) != hipSuccess) return AGX_ERR_HIP;
+        const size_t F = std::max((size_t)a.n_frames, det->dtail_frames), cap = std::max(tag_cap, det->dtail_tag_cap);
+        det->dtail_frames = 0;
+        det->dtail_tag_cap = 0;
+        det->d_tail_tags = static_cast<agx_tag *>(side_alloc(det, agx_detector::SB_DTAGS, F * cap * sizeof(agx_tag), 0));
+        det->d_tail_table = static_cast<uint32_t *>(side_alloc(det, agx_detector::SB_DTABLE, F * 4 * sizeof(uint32_t), 0));
+        if (!det->d_tail_tags || !det->d_tail_table) {
+            side_free(det, agx_detector::SB_DTAGS);
+            side_free(det, agx_detector::SB_DTABLE);
+            det->d_tail_tags = nullptr;
+            det->d_tail_table = nullptr;
+            return AGX_ERR_HIP;
+        }
+        det->dtail_frames = F;
+        det->dtail_tag_cap = (uint32_t)cap;
+    }
+    if (!to_device && ((size_t)a.n_frames > det->tail_frames || tag_cap > det->tail_tag_cap)) {
         if (hipStreamSynchronize(det->stream) != hipSuccess) return AGX_ERR_HIP;
         const size_t F = std::max((size_t)a.n_frames, det->tail_frames), cap = std::max(tag_cap, det->tail_tag_cap);
         det->tail_frames = 0;  // (nothing usable until both tables exist)
@@ -747,16 +773,36 @@ __attribute__((visibility("hidden"))) int agx_internal_enqueue_tail(agx_detector
     t.n_codes = det->fam.n_codes;
     t.codes = det->d_codes;
     t.max_boards = det->params.max_num_of_boards;
-    t.tags = det->h_tags_dev;
-    t.table = det->h_tail_table_dev;
+    t.tags = to_device ? det->d_tail_tags : det->h_tags_dev;
+    t.table = to_device ? det->d_tail_table : det->h_tail_table_dev;
     t.tag_cap = tag_cap;  // this call's: a frame with more tags is handed back (TAIL_CAPACITY), whatever the table could hold
-    t.tag_stride = det->tail_tag_cap;
+    t.tag_stride = to_device ? det->dtail_tag_cap : det->tail_tag_cap;
     t.debug_band = (float)det->tail_debug_band_mdeg * 1e-3f;
     t.debug = tuning_env("AGX_TAIL_DEBUG", 0);
     t.debug_frame = tuning_env("AGX_TAIL_DEBUG_FRAME", 0);
     if (launch_board_tail(t, det->stream) != 0) return AGX_ERR_HIP;
     return AGX_OK;
 }
+__attribute__((visibility("hidden"))) int agx_internal_publish_tags(agx_detector *det, uint32_t cap_per_frame, agx_tag *d_tags,
+                                                                    uint32_t *d_counts, int *d_status)
+{
+    if (!det->enqueued || !det->d_tail_table) return AGX_ERR_STATE;
+    const int e = launch_publish_tags(det->d_tail_table, det->d_tail_tags, det->dtail_tag_cap, det->args.ctr, det->args.n_frames,
+                                      cap_per_frame, d_tags, d_counts, d_status, det->stream);
+    return e == 0 ? AGX_OK : AGX_ERR_HIP;
+}
+__attribute__((visibility("hidden"))) const uint32_t *agx_internal_device_tail_table(agx_detector *det) { return det->d_tail_table; }
+__attribute__((visibility("hidden"))) uint8_t *agx_internal_fetch_luma(agx_detector *det, size_t bytes)
+{
+    if (bytes > det->fetch_luma_bytes) {
+        det->fetch_luma_bytes = 0;
+        det->h_fetch_luma = static_cast<uint8_t *>(side_alloc(det, agx_detector::SB_FETCH_LUMA, bytes, 1));
+        if (!det->h_fetch_luma) return nullptr;
+        det->fetch_luma_bytes = bytes;
+    }
+    return det->h_fetch_luma;
+}
+__attribute__((visibility("hidden"))) agx::DetectPending *agx_internal_detect_pending(agx_detector *det) { return &det->detect; }
 __attribute__((visibility("hidden"))) int agx_internal_fetch_tail(agx_detector *det, const agx_tag **tags, const uint32_t **table, uint32_t *tag_cap)
 {
     if (hipStreamSynchronize(det->stream) != hipSuccess) return AGX_ERR_HIP;
@@ -1052,6 +1098,7 @@ static int batch_enqueue_impl(agx_detector *det, const void *d_frames, int n_fra
     // of 4, odd-width L16): the blur kernel gathers bytes instead of loading dwords
     const bool byte_rows = ((row_stride_bytes | (uintptr_t)d_frames | (n_frames > 1 ? frame_stride_bytes : 0)) & 3) != 0;
     if (n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
+    det->detect.kind = 0;  // (this batch replaces whatever was in flight, an agx_detect_batch_enqueue's included)
     HIP_TRY(det, hipSetDevice(det->device));
     int rc = ensure_workspace(det, n_frames, width, height);
     if (rc) return rc;
@@ -1132,6 +1179,16 @@ int agx_saddles_batch_fetch(agx_detector *det, agx_saddle *out, uint32_t cap_per
                             int *frame_status)
 {
     return agx_guard(det, [&]() -> int {
+    if (det && det->enqueued && det->detect.kind)
+        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_detect_batch_enqueue's: fetch it with agx_detect_batch_fetch");
+    return saddles_fetch_impl(det, out, cap_per_frame, counts, frame_status);
+    });
+}
+
+// agx_saddles_batch_fetch without the pairing rule (agx_internal_fetch_compact reads the chain's results of a detect batch too)
+static int saddles_fetch_impl(agx_detector *det, agx_saddle *out, uint32_t cap_per_frame, uint32_t *counts, int *frame_status)
+{
+    return agx_guard(det, [&]() -> int {
     if (!det || !counts || (!out && cap_per_frame)) return fail(det, AGX_ERR_ARG, "null output");
     if (!det->enqueued) return fail(det, AGX_ERR_STATE, "no batch enqueued");
     if (det->external_out) return fail(det, AGX_ERR_STATE, "last batch wrote to caller-owned device buffers");
@@ -1209,6 +1266,52 @@ int agx_saddles_batch_fetch(agx_detector *det, agx_saddle *out, uint32_t cap_per
                         (size_t)c.n_out * sizeof(agx_saddle));
     }
     return first_bad;
+    });
+}
+
+// detect over a batch in device memory, stream-ordered (csrc/detect_batch.cpp: the chain, k_luma8, the device tail, the fetch)
+static int detect_enqueue_checked(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                                  size_t frame_stride_bytes, int format, uint32_t cap_per_frame, bool to_device, agx_tag *d_tags,
+                                  uint32_t *d_counts, int *d_status)
+{
+    if (!det) return AGX_ERR_ARG;
+    if (format != AGX_L8 && format != AGX_L16 && format != AGX_RGB8)  // (the decode needs to_luma8: agx_detect_planes for the rest)
+        return fail(det, AGX_ERR_FORMAT, "format must be AGX_L8, AGX_L16 or AGX_RGB8");
+    if (to_device && (!d_counts || !d_status || (!d_tags && cap_per_frame) || (((uintptr_t)d_tags | (uintptr_t)d_counts | (uintptr_t)d_status) & 3)))
+        return fail(det, AGX_ERR_ARG, "null or misaligned output buffers");
+    return detect_enqueue_impl(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, cap_per_frame, to_device,
+                               d_tags, d_counts, d_status);
+}
+
+int agx_detect_batch_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                             size_t frame_stride_bytes, int format, uint32_t cap_per_frame)
+{
+    return agx_guard(det, [&]() -> int {
+    return detect_enqueue_checked(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, cap_per_frame,
+                                  false, nullptr, nullptr, nullptr);
+    });
+}
+
+int agx_detect_batch_enqueue_to(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                                size_t frame_stride_bytes, int format, agx_tag *d_tags, uint32_t cap_per_frame, uint32_t *d_counts,
+                                int *d_status)
+{
+    return agx_guard(det, [&]() -> int {
+    return detect_enqueue_checked(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, cap_per_frame,
+                                  true, d_tags, d_counts, d_status);
+    });
+}
+
+int agx_detect_batch_fetch(agx_detector *det, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    if (!det->detect.kind || !det->enqueued) return fail(det, AGX_ERR_STATE, "no agx_detect_batch_enqueue batch in flight");
+    det->last_error.clear();
+    const int rc = detect_fetch_impl(det, out, counts, frame_status, n_threads);
+    if (rc == AGX_ERR_NOMEM) det->last_error = "out of host memory or threads";
+    else if (rc != AGX_OK && rc != AGX_ERR_CAPACITY && det->last_error.empty()) det->last_error = agx_status_string(rc);
+    return rc;
     });
 }
 

@@ -32,9 +32,19 @@ int agx_internal_fetch_compact(agx_detector *det, const agx_saddle **records, ui
 int agx_internal_device_tail(agx_detector *det);
 int agx_internal_tail_prepare(agx_detector *det);  // one-time set-up on the handle's device (code list, kernel attributes): all or nothing
 int agx_internal_tail_debug(const agx_detector *det);  // AGX_TAIL_DEBUG as read when the handle was created
-int agx_internal_enqueue_tail(agx_detector *det, const void *d_luma, size_t luma_row_stride, size_t luma_frame_stride, uint32_t tag_cap);
+// to_device != 0 (agx_detect_batch_enqueue_to): tags and table go to a pair of device buffers instead, read by
+// agx_internal_publish_tags and agx_internal_device_tail_table
+int agx_internal_enqueue_tail(agx_detector *det, const void *d_luma, size_t luma_row_stride, size_t luma_frame_stride, uint32_t tag_cap,
+                              int to_device);
 int agx_internal_fetch_tail(agx_detector *det, const agx_tag **tags, const uint32_t **table, uint32_t *tag_cap);
 void agx_internal_tail_stats(agx_detector *det, int frames, int fallbacks, int uncertain);
+// agx_detect_batch_enqueue_to: the device tail's results of the batch (device buffers) into the caller's layout, behind the
+// tail on the detector's stream (tail_kernels.hip, k_publish_tags); the device address of the tail's frame table [n][4]
+int agx_internal_publish_tags(agx_detector *det, uint32_t cap_per_frame, agx_tag *d_tags, uint32_t *d_counts, int *d_status);
+const uint32_t *agx_internal_device_tail_table(agx_detector *det);
+// agx_detect_batch_fetch: pinned host memory of at least `bytes` for the u8 luma of the frames the host tail takes (grown on
+// demand, guarded like every side buffer)
+uint8_t *agx_internal_fetch_luma(agx_detector *det, size_t bytes);
 }
 namespace agx {
 void destroy_worker_pool(void *pool);
@@ -42,4 +52,23 @@ void *create_worker_pool(int n_threads);
 struct TailWorkers;  // host_tail.hpp
 TailWorkers *create_tail_workers(int n_threads);  // nullptr for n_threads <= 1
 void destroy_tail_workers(TailWorkers *w);
+
+// agx_detect_batch_enqueue / _enqueue_to: what agx_detect_batch_fetch needs of the batch in flight.  Any enqueue of the chain
+// (either pair, agx_detect_batch, agx_detect) resets it: one batch in flight per handle, the last one enqueued.
+struct DetectPending {
+    int kind = 0;              // 0 none, 1 results to host arrays (agx_detect_batch_enqueue), 2 to the caller's device arrays
+    bool device_tail = false;  // the device tail runs behind the chain; else the fetch runs the host tail on every frame
+    int n_frames = 0, width = 0, height = 0;
+    uint32_t cap = 0;
+    const uint8_t *d_luma = nullptr;  // the batch's u8 luma on the device: the L8 frames themselves or the k_luma8 planes
+    size_t luma_row = 0, luma_frame = 0;
+    agx_tag *d_tags = nullptr;  // kind 2: [n_frames][cap]
+    uint32_t *d_counts = nullptr;
+    int *d_status = nullptr;
+};
+int detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                        size_t frame_stride_bytes, int format, uint32_t cap_per_frame, bool to_device, agx_tag *d_tags,
+                        uint32_t *d_counts, int *d_status);
+int detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads);
 }
+extern "C" agx::DetectPending *agx_internal_detect_pending(agx_detector *det);

@@ -48,6 +48,11 @@ struct TailArgs {
 
 // Enqueue the device tail of the batch on `stream`; hipError_t.
 int launch_board_tail(const TailArgs &t, void *stream);
+// agx_detect_batch_enqueue_to: the tail's rows and frame table (device memory, rows tag_stride apart) into the caller's layout,
+// one wave per frame: d_tags[f][cap] (a frame's rows only), d_counts[f], d_status[f] (agx_status; AGX_ERR_STATE for a frame
+// handed back to the host tail, which agx_detect_batch_fetch fills in); ctr = the chain's counters of the batch.  hipError_t.
+int launch_publish_tags(const uint32_t *table, const agx_tag *tags, uint32_t tag_stride, const FrameCounters *ctr, int n_frames,
+                        uint32_t cap, agx_tag *d_tags, uint32_t *d_counts, int *d_status, void *stream);
 int init_tail_kernels();  // per-device kernel attributes (current device); hipError_t
 
 }  // namespace agx

@@ -1444,7 +1444,51 @@ __global__ void __launch_bounds__(64 * TW) k_board_tail(TailArgs a)
     }
 }
 
+// agx_detect_batch_enqueue_to: frame f's entry of the tail's table (count, status) and its rows into the caller's arrays, as
+// agx_detect_batch_fetch reports them: TAIL_OK -> its rows, AGX_OK (more tags than cap: AGX_ERR_CAPACITY with the true count
+// and no row); a list of the chain that overflowed -> AGX_ERR_CAPACITY, count 0; handed back -> count 0, AGX_ERR_STATE until the
+// fetch has run the host tail.  Nothing beyond the frame's own count of rows is written.
+__global__ void __launch_bounds__(256) k_publish_tags(const uint32_t *table, const agx_tag *tags, uint32_t tag_stride,
+                                                      const FrameCounters *ctr, int n_frames, uint32_t cap, agx_tag *d_tags,
+                                                      uint32_t *d_counts, int *d_status)
+{
+    const int f = (int)(blockIdx.x * 4 + (threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
+    if (f >= n_frames) return;
+    const uint32_t nt = table[4 * f], st = table[4 * f + 1];
+    uint32_t count = 0, rows = 0;
+    int status;
+    if (ctr[f].flags & (FLAG_CAND_OVERFLOW | FLAG_ROOT_OVERFLOW | FLAG_OUT_OVERFLOW)) {
+        status = AGX_ERR_CAPACITY;
+    } else if (st != TAIL_OK) {
+        status = AGX_ERR_STATE;
+    } else if (nt > cap) {
+        status = AGX_ERR_CAPACITY;
+        count = nt;
+    } else {
+        status = AGX_OK;
+        count = nt;
+        rows = nt < tag_stride ? nt : tag_stride;  // (TAIL_OK: nt <= the tail's tag_cap <= tag_stride)
+    }
+    const uint32_t words = rows * (uint32_t)(sizeof(agx_tag) / 4);
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(tags + (size_t)f * tag_stride);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(d_tags + (size_t)f * cap);
+    for (uint32_t i = (uint32_t)lane; i < words; i += 64u) dst[i] = src[i];
+    if (lane == 0) {
+        d_counts[f] = count;
+        d_status[f] = status;
+    }
+}
+
 }  // namespace
+
+int launch_publish_tags(const uint32_t *table, const agx_tag *tags, uint32_t tag_stride, const FrameCounters *ctr, int n_frames,
+                        uint32_t cap, agx_tag *d_tags, uint32_t *d_counts, int *d_status, void *stream)
+{
+    if (n_frames <= 0) return (int)hipSuccess;
+    hipLaunchKernelGGL(k_publish_tags, dim3((unsigned)((n_frames + 3) / 4)), dim3(256), 0, (hipStream_t)stream, table, tags, tag_stride,
+                       ctr, n_frames, cap, d_tags, d_counts, d_status);
+    return (int)hipGetLastError();
+}
 
 int init_tail_kernels()
 {

@@ -108,6 +108,7 @@ class TagDetector:
         self.detector_params = optional_detector_params or DetectorParams.default_params()
         self.device = device
         self._batch = None
+        self._detect = None  # detect_batch_enqueue's batch: (n, cap, frames kept alive, device outputs or None)
 
     new = classmethod(lambda cls, tag_family, optional_detector_params=None, device=0:
                       cls(tag_family, optional_detector_params, device))
@@ -327,6 +328,7 @@ class TagDetector:
         self._check(self._lib.agx_saddles_batch_enqueue(self._h, frames.data_ptr(), n, w, h, w * bpp, w * h * bpp,
                                                         fmt))
         self._batch = (n, frames)  # keep the tensor alive until fetched
+        self._detect = None
 
     def saddles_batch_enqueue_to(self, frames, out_saddles, frame_table):
         """Device-resident results: out_saddles float32 [capacity, 5] and frame_table int32
@@ -340,6 +342,7 @@ class TagDetector:
             self._h, frames.data_ptr(), n, w, h, w * bpp, w * h * bpp, fmt, out_saddles.data_ptr(),
             out_saddles.shape[0], frame_table.data_ptr()))
         self._batch = None
+        self._detect = None
 
     def saddles_batch_enqueue_ptr(self, dptr, n, w, h, row_stride, frame_stride, fmt, follow_torch_stream=True):
         """agx_saddles_batch_enqueue on a raw device address (any row / frame stride: a view cut out of a larger allocation).
@@ -351,6 +354,7 @@ class TagDetector:
         self._check(self._lib.agx_saddles_batch_enqueue(self._h, C.c_void_p(dptr), n, w, h, row_stride, frame_stride,
                                                         fmt))
         self._batch = (n, None)
+        self._detect = None
 
     def saddles_batch_fetch(self, cap_per_frame=None, raise_on_overflow=True):
         """-> (list of SADDLE_DTYPE arrays, one per frame; per-frame status array).  cap_per_frame None:
@@ -385,6 +389,87 @@ class TagDetector:
         if st not in (_ffi.AGX_OK, _ffi.AGX_ERR_CAPACITY):
             self._check(st)
         return st
+
+    def detect_batch_enqueue(self, frames, cap=1024, out=None):
+        """detect() over a batch resident on this detector's GPU: frames as saddles_batch_enqueue ([N,H,W] uint8 / int16 /
+        uint16 or [N,H,W,3] uint8, contiguous; float32 planes are refused), stream-ordered behind torch's current stream.
+        Returns immediately; detect_batch_fetch waits.  out=(tags, counts, status): device-resident results instead --
+        tags int32 [N, cap, 9] (id, then the 8 corner floats as bits: split_device_tags), counts int32 [N], status int32 [N],
+        final once detect_batch_fetch has returned (a frame handed back to the host tail reads count 0 / AGX_ERR_STATE until then)."""
+        fmt, bpp = self._tensor_format(frames)
+        if fmt == _ffi.AGX_LF32:
+            raise AgxError(_ffi.AGX_ERR_FORMAT, "detect_batch takes L8 / L16 / RGB8 frames")
+        n, h, w = frames.shape[:3]
+        self._follow_torch_stream(frames)
+        self._enqueue_detect(frames.data_ptr(), n, w, h, w * bpp, w * h * bpp, fmt, cap, out, keep=frames)
+
+    def detect_batch_enqueue_ptr(self, dptr, n, w, h, row_stride, frame_stride, fmt, cap=1024, out=None, follow_torch_stream=True):
+        """detect_batch_enqueue on a raw device address with any row / frame stride (as saddles_batch_enqueue_ptr); the caller
+        keeps the memory alive until detect_batch_fetch."""
+        if follow_torch_stream:
+            self._follow_torch_stream()
+        self._enqueue_detect(dptr, n, w, h, row_stride, frame_stride, fmt, cap, out, keep=None)
+
+    def _enqueue_detect(self, dptr, n, w, h, row_stride, frame_stride, fmt, cap, out, keep):
+        self._batch = None  # (one batch in flight per handle: this one replaces a saddle batch)
+        self._detect = None
+        if out is None:
+            self._check(self._lib.agx_detect_batch_enqueue(self._h, C.c_void_p(dptr), n, w, h, row_stride, frame_stride, fmt, cap))
+        else:
+            import torch
+            tags, counts, status = out
+            for t, shape in ((tags, (n, cap, 9)), (counts, (n,)), (status, (n,))):
+                if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == torch.int32 and tuple(t.shape) == shape):
+                    raise AgxError(_ffi.AGX_ERR_ARG, "out tensors must be contiguous int32 CUDA tensors [n, cap, 9], [n], [n]")
+                if t.device.index != self.device:
+                    raise AgxError(_ffi.AGX_ERR_ARG, "out tensor on device %s, the detector on %d" % (t.device.index, self.device))
+            self._check(self._lib.agx_detect_batch_enqueue_to(self._h, C.c_void_p(dptr), n, w, h, row_stride, frame_stride, fmt,
+                                                              tags.data_ptr(), cap, counts.data_ptr(), status.data_ptr()))
+        self._detect = (n, cap, keep, out)  # (frames and outputs stay alive until fetched)
+
+    def detect_batch_fetch_raw(self, n_threads=0):
+        """agx_detect_batch_fetch -> (rc, out [N, cap] TAG_DTYPE, counts uint32 [N], status int32 [N]) as detect_batch_raw; after
+        detect_batch_enqueue(out=...) -> (rc, tags, counts, status), the device tensors.  Nothing is raised for a frame status."""
+        if self._detect is None:
+            raise AgxError(_ffi.AGX_ERR_STATE, "no detect batch enqueued")
+        n, cap, _, dev_out = self._detect
+        self._detect = None
+        if dev_out is not None:
+            rc = self._lib.agx_detect_batch_fetch(self._h, None, None, None, n_threads)
+            if rc not in (_ffi.AGX_OK, _ffi.AGX_ERR_CAPACITY):
+                self._check(rc)
+            return (rc,) + tuple(dev_out)
+        out = np.zeros((n, cap), self.TAG_DTYPE)
+        counts = np.zeros(n, np.uint32)
+        status = np.full(n, _ffi.AGX_ERR_STATE, np.int32)
+        rc = self._lib.agx_detect_batch_fetch(self._h, out.ctypes.data, counts.ctypes.data, status.ctypes.data, n_threads)
+        if rc not in (_ffi.AGX_OK, _ffi.AGX_ERR_CAPACITY):
+            self._check(rc)
+        return rc, out, counts, status
+
+    def detect_batch_fetch(self, n_threads=0, raise_on_overflow=True):
+        """Wait for detect_batch_enqueue's batch -> what detect_batch returns (list of {tag_id: 4x2 corners}; with
+        raise_on_overflow=False (results, status)).  After detect_batch_enqueue(out=...) the results stay on the device:
+        -> (tags, counts, status), the tensors passed as out (raise_on_overflow as above)."""
+        rc, out, counts, status = self.detect_batch_fetch_raw(n_threads)
+        if rc != _ffi.AGX_OK and raise_on_overflow:
+            self._check(rc)
+        if not isinstance(out, np.ndarray):
+            return out, counts, status
+        res = [None if status[i] != 0 else {int(t["id"]): t["xy"].reshape(4, 2).copy() for t in out[i, : counts[i]]}
+               for i in range(len(counts))]
+        return res if raise_on_overflow else (res, status)
+
+    def detect_batch_device(self, frames, n_threads=0, cap=1024, raise_on_overflow=True):
+        """detect_batch for frames resident on the GPU only (a torch tensor): detect_batch_enqueue + detect_batch_fetch."""
+        self.detect_batch_enqueue(frames, cap)
+        return self.detect_batch_fetch(n_threads, raise_on_overflow)
+
+    @staticmethod
+    def split_device_tags(tags):
+        """tags int32 [..., cap, 9] of detect_batch_enqueue(out=...) -> (ids int32 [..., cap], corners float32 [..., cap, 4, 2])."""
+        import torch
+        return tags[..., 0], tags[..., 1:].contiguous().view(torch.float32).reshape(*tags.shape[:-1], 4, 2)
 
     # ---- measurement / parity hooks ------------------------------------------------------
     def profile_enable(self, level=2):

@@ -133,6 +133,13 @@ extern "C" {
     pub fn agx_detect_batch(det: *mut agx_detector, frames: *const c_void, d_frames: *const c_void, n_frames: c_int, width: c_int,
                             height: c_int, row_stride_bytes: usize, frame_stride_bytes: usize, format: c_int, out: *mut agx_tag,
                             cap_per_frame: u32, counts: *mut u32, frame_status: *mut c_int, n_threads: c_int) -> c_int;
+    pub fn agx_detect_batch_enqueue(det: *mut agx_detector, d_frames: *const c_void, n_frames: c_int, width: c_int, height: c_int,
+                                    row_stride_bytes: usize, frame_stride_bytes: usize, format: c_int, cap_per_frame: u32) -> c_int;
+    pub fn agx_detect_batch_enqueue_to(det: *mut agx_detector, d_frames: *const c_void, n_frames: c_int, width: c_int, height: c_int,
+                                       row_stride_bytes: usize, frame_stride_bytes: usize, format: c_int, d_tags: *mut agx_tag,
+                                       cap_per_frame: u32, d_counts: *mut u32, d_status: *mut c_int) -> c_int;
+    pub fn agx_detect_batch_fetch(det: *mut agx_detector, out: *mut agx_tag, counts: *mut u32, frame_status: *mut c_int,
+                                  n_threads: c_int) -> c_int;
     pub fn agx_host_parallelism() -> c_int;
     pub fn agx_luma8(pixels: *const c_void, width: c_int, height: c_int, row_stride_bytes: usize, format: c_int, out: *mut u8) -> c_int;
 

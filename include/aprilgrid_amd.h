@@ -272,6 +272,30 @@ int agx_detect_batch(agx_detector *det, const void *frames, const void *d_frames
                      int height, size_t row_stride_bytes, size_t frame_stride_bytes, int format, agx_tag *out,
                      uint32_t cap_per_frame, uint32_t *counts, int *frame_status, int n_threads);
 
+/* detect (src/detector.rs:505-540) over a batch resident in DEVICE memory; layout and formats as
+ * agx_saddles_batch_enqueue (AGX_L8 / AGX_L16 / AGX_RGB8; AGX_LF32 is AGX_ERR_FORMAT).  Enqueues the chain, to_luma8 (non-L8,
+ * on the device) and the device tail on the detector's stream and returns without waiting; the frames must stay in place until
+ * agx_detect_batch_fetch has returned.  The device tail runs where option "device_tail" is -1 or 1 and this process may use it
+ * (no batch-size rule); with 0, or where it is refused, the fetch runs the host tail on every frame from the compact saddle lists
+ * and the u8 luma planes copied down.  Same tags, counts and statuses as agx_detect_batch on the same pixels, either way.
+ * One batch in flight per handle, as for agx_saddles_batch_enqueue: any later enqueue (either pair, agx_detect_batch, agx_detect)
+ * replaces it; agx_saddles_batch_fetch of it, or agx_detect_batch_fetch of a saddle batch, is AGX_ERR_STATE. */
+int agx_detect_batch_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height,
+                             size_t row_stride_bytes, size_t frame_stride_bytes, int format, uint32_t cap_per_frame);
+/* The same, results also in CALLER-OWNED DEVICE memory (4-byte aligned): d_tags [n_frames][cap_per_frame] agx_tag (may be NULL
+ * for cap 0), d_counts [n_frames] uint32, d_status [n_frames] int (agx_status per frame, as agx_detect_batch's frame_status).
+ * Only a frame's own count of rows is written; more tags than cap_per_frame is AGX_ERR_CAPACITY with the true count and no row.
+ * A frame the device tail hands back to the host tail reads count 0 and AGX_ERR_STATE until agx_detect_batch_fetch has written
+ * its rows, count and status (on the detector's stream, before it returns); without the device tail that is every frame. */
+int agx_detect_batch_enqueue_to(agx_detector *det, const void *d_frames, int n_frames, int width, int height,
+                                size_t row_stride_bytes, size_t frame_stride_bytes, int format, agx_tag *d_tags,
+                                uint32_t cap_per_frame, uint32_t *d_counts, int *d_status);
+/* Wait; resolve the frames the kernel handed back on n_threads host threads (0 = agx_host_parallelism()); out / counts /
+ * frame_status as agx_detect_batch (out sized n_frames * the enqueue's cap; frame_status may be NULL).  After _enqueue_to the
+ * host arrays may be NULL; the device arrays are final when this returns.  Returns the first non-OK frame status, else AGX_OK;
+ * AGX_ERR_STATE with nothing in flight.  The batch is resolved by this call: a second fetch is AGX_ERR_STATE. */
+int agx_detect_batch_fetch(agx_detector *det, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads);
+
 /* ---- detector groups: several GPUs of one node driven from ONE process ----------------- */
 
 /* The reference's detect(&self) is stateless, so a batch shards by frame:
@@ -364,8 +388,9 @@ enum { AGX_DBG_BLUR = 0, AGX_DBG_RESP = 1, AGX_DBG_MIN = 2, AGX_DBG_CENTERS = 3,
        AGX_DBG_REDZONES = 8, /* 6 x uint32: guarded buffers, damaged guard bytes, first damaged buffer, its byte
                                offset from the payload start (int32), device address of buffer 0 (lo, hi: for the
                                check of the check).  Buffers = the chain's workspace, then the staging buffer, the luma
-                               planes and the device tail's code list, tag rows and frame table (mapped pinned host memory)
-                               as far as they exist.  Needs no enqueued batch.  Guard bytes exist only in handles created with
+                               planes and the device tail's code list, tag rows and frame table (mapped pinned host memory), then
+                               agx_detect_batch_enqueue_to's device-memory tag rows and frame table and agx_detect_batch_fetch's
+                               pinned luma planes, as far as they exist.  Needs no enqueued batch.  Guard bytes exist only in handles created with
                                AGX_REDZONE_BYTES=<n> in the environment (memory-safety tests of the kernels) */
        AGX_DBG_TAIL_TABLE_ADDR = 11 /* 2 x uint64: host address and payload bytes of the device tail's frame table (the check
                                        of the check for a buffer in mapped host memory).  Needs no enqueued batch */ };
