@@ -10,6 +10,11 @@ AGX_OK = 0
 AGX_ERR_ARG, AGX_ERR_FORMAT, AGX_ERR_CAPACITY, AGX_ERR_HIP = -1, -2, -3, -4
 AGX_ERR_NO_DEVICE, AGX_ERR_FAMILY, AGX_ERR_STATE, AGX_ERR_NOMEM = -5, -6, -7, -8
 AGX_L8, AGX_L16, AGX_RGB8, AGX_LF32 = 0, 1, 2, 3
+AGX_LA8, AGX_RGBA8, AGX_BGR8, AGX_BGRA8, AGX_RGB8P, AGX_LA16, AGX_RGB16, AGX_RGBA16 = 4, 5, 6, 7, 8, 9, 10, 11
+# agx_format -> (bytes between adjacent pixels of a row, rows per frame as a multiple of the height, numpy dtype of a channel)
+FORMAT_LAYOUT = {AGX_L8: (1, 1, "u1"), AGX_L16: (2, 1, "u2"), AGX_RGB8: (3, 1, "u1"), AGX_LF32: (4, 1, "f4"),
+                 AGX_LA8: (2, 1, "u1"), AGX_RGBA8: (4, 1, "u1"), AGX_BGR8: (3, 1, "u1"), AGX_BGRA8: (4, 1, "u1"),
+                 AGX_RGB8P: (1, 3, "u1"), AGX_LA16: (4, 1, "u2"), AGX_RGB16: (6, 1, "u2"), AGX_RGBA16: (8, 1, "u2")}
 AGX_GATHER_RCCL, AGX_GATHER_PEER = 0, 1
 AGX_DBG_BLUR, AGX_DBG_RESP, AGX_DBG_MIN, AGX_DBG_CENTERS, AGX_DBG_REFINED = 0, 1, 2, 3, 4
 AGX_N_KERNELS = 5

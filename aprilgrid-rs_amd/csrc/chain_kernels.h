@@ -161,8 +161,13 @@ int launch_debug_resp(const ChainArgs &a, int frame, float *dst, void *stream);
 int launch_publish(const ChainArgs &a, uint32_t h_out_records, uint32_t *h_table_dev, float *h_out_dev, void *stream);
 // Zero n_records counter records on `stream` (used instead of a memset while the stream is being captured).
 int launch_clear_counters(FrameCounters *ctr, size_t n_records, void *stream);
-// u8 luma (to_luma8) of n_frames L16 (format 1) / RGB8 (format 2) frames in device memory: rows `pitch`
-// bytes apart, frames `frame_stride` bytes apart -> tight [n_frames][H][W]
+// k_front_luma: the integer luma plane of n_frames frames of one of the layouts AGX_LA8 .. AGX_RGBA16 (format 4 .. 11) in device
+// memory -> tight [n_frames][H][W] u8 (8-bit layouts; 16-bit layouts with out8 != 0: to_luma8) or u16 (16-bit layouts, out8 == 0).
+// Rows `row_stride` bytes apart, frames `frame_stride`; the planes of AGX_RGB8P are H * row_stride bytes apart.
+int launch_front_luma(const void *src, size_t row_stride, size_t frame_stride, int n_frames, int format, void *dst, int out8, int W,
+                      int H, void *stream);
+// u8 luma (to_luma8) of n_frames L16 (format 1) / RGB8 (format 2) frames in device memory, or of a layout of
+// launch_front_luma (by that kernel): rows `pitch` bytes apart, frames `frame_stride` bytes apart -> tight [n_frames][H][W]
 int launch_luma8(const void *src, size_t pitch, size_t frame_stride, int n_frames, int format, uint8_t *dst, int W, int H,
                  void *stream);
 

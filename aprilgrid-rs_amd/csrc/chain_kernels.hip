@@ -3076,8 +3076,187 @@ __global__ void __launch_bounds__(256) k_luma8(const uint8_t *src, size_t pitch,
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Front end of the other integer layouts (agx_format 4 .. 11: LA8, RGBA8, BGR8, BGRA8, planar RGB8, LA16, RGB16, RGBA16):
+// the frame's integer luma plane, tight [n][H][W] u8 (8-bit layouts) or u16 (16-bit layouts), which the unchanged L8 / L16
+// chain then reads -- to_luma32f of an integer colour image is its integer luma / 255 (/ 65535), so the chain's result is
+// that of the image crate by construction.  The arithmetic is luma8()'s (host_tail.cpp): alpha dropped,
+// (2126 r + 7152 g + 722 b) / 10000 in u32 (at most 655 350 000 for 16-bit channels); the division is written as one and
+// left to the compiler's exact reciprocal sequence.  OUT8: a 16-bit layout narrowed to to_luma8, (luma16 + 128) / 257.
+//
+// A streaming kernel: a lane owns 4 adjacent pixels of a row, which it loads as 1 .. 2 dword vectors (8 .. 32 bytes; three
+// dwords from three planes for the planar layout) and stores as one dword (u8) or two (u16), so a wave reads and writes whole
+// 128-byte lines; the four rows of a lane are loaded before the first is converted.  Grid = (256-column block, 16-row block,
+// frame): no index arithmetic beyond adds and one multiply per row.  `vec` = 0 (a base, stride or width that is not a
+// multiple of 4) takes the per-pixel path with the same pixel-to-lane mapping.
+constexpr int FL_LA8 = 4, FL_RGBA8 = 5, FL_BGR8 = 6, FL_BGRA8 = 7, FL_RGB8P = 8, FL_LA16 = 9, FL_RGB16 = 10, FL_RGBA16 = 11;
+constexpr int FL_ROWS = 4;  // rows per lane; a workgroup of 4 waves covers 16 rows x 256 columns
+
+// vectors of dwords that are only dword-aligned in memory (a row may start at any multiple of 4)
+typedef uint32_t fl_u32x2 __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint32_t fl_u32x3 __attribute__((ext_vector_type(3), aligned(4)));
+typedef uint32_t fl_u32x4 __attribute__((ext_vector_type(4), aligned(4)));
+
+template <int LAYOUT>
+struct FrontLayout {
+    static constexpr bool in16 = LAYOUT >= FL_LA16;
+    // bytes between horizontally adjacent pixels
+    static constexpr int bpp = LAYOUT == FL_LA8 ? 2 : LAYOUT == FL_BGR8 ? 3 : LAYOUT == FL_RGB8P ? 1 : LAYOUT == FL_RGB16 ? 6
+                             : LAYOUT == FL_RGBA16 ? 8 : 4;
+    static constexpr int dwords = LAYOUT == FL_RGB8P ? 3 : bpp;  // per lane: 4 pixels
+};
+
+__device__ __forceinline__ uint32_t fl_weighted(uint32_t r, uint32_t g, uint32_t b) { return (2126u * r + 7152u * g + 722u * b) / 10000u; }
+
+// the lane's 4 pixels of one row: p = the first of them (plane 0), plane = bytes between the planes of the planar layout
+template <int LAYOUT>
+__device__ __forceinline__ void fl_load4(const uint8_t *p, size_t plane, uint32_t (&d)[8])
+{
+    if (LAYOUT == FL_LA8) {
+        const fl_u32x2 v = *reinterpret_cast<const fl_u32x2 *>(p);
+        d[0] = v.x, d[1] = v.y;
+    } else if (LAYOUT == FL_BGR8) {
+        const fl_u32x3 v = *reinterpret_cast<const fl_u32x3 *>(p);
+        d[0] = v.x, d[1] = v.y, d[2] = v.z;
+    } else if (LAYOUT == FL_RGB8P) {
+        d[0] = *reinterpret_cast<const uint32_t *>(p);
+        d[1] = *reinterpret_cast<const uint32_t *>(p + plane);
+        d[2] = *reinterpret_cast<const uint32_t *>(p + 2 * plane);
+    } else {
+        const fl_u32x4 v = *reinterpret_cast<const fl_u32x4 *>(p);
+        d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
+        if (LAYOUT == FL_RGB16) {
+            const fl_u32x2 w = *reinterpret_cast<const fl_u32x2 *>(p + 16);
+            d[4] = w.x, d[5] = w.y;
+        } else if (LAYOUT == FL_RGBA16) {
+            const fl_u32x4 w = *reinterpret_cast<const fl_u32x4 *>(p + 16);
+            d[4] = w.x, d[5] = w.y, d[6] = w.z, d[7] = w.w;
+        }
+    }
+}
+
+// integer luma of pixel i (0 .. 3) of the dwords fl_load4 read (little endian)
+template <int LAYOUT>
+__device__ __forceinline__ uint32_t fl_luma_of(const uint32_t (&d)[8], int i)
+{
+    auto byte = [&](int k) { return (d[k >> 2] >> (8 * (k & 3))) & 0xffu; };
+    auto half = [&](int k) { return (d[k >> 1] >> (16 * (k & 1))) & 0xffffu; };
+    switch (LAYOUT) {
+    case FL_LA8: return byte(2 * i);
+    case FL_RGBA8: return fl_weighted(byte(4 * i), byte(4 * i + 1), byte(4 * i + 2));
+    case FL_BGRA8: return fl_weighted(byte(4 * i + 2), byte(4 * i + 1), byte(4 * i));
+    case FL_BGR8: return fl_weighted(byte(3 * i + 2), byte(3 * i + 1), byte(3 * i));
+    case FL_RGB8P: return fl_weighted(byte(i), byte(4 + i), byte(8 + i));
+    case FL_LA16: return half(2 * i);
+    case FL_RGB16: return fl_weighted(half(3 * i), half(3 * i + 1), half(3 * i + 2));
+    default: return fl_weighted(half(4 * i), half(4 * i + 1), half(4 * i + 2));  // FL_RGBA16
+    }
+}
+
+// the same of one pixel at p, read channel by channel (16-bit channels are 2-byte aligned: the host checks)
+template <int LAYOUT>
+__device__ __forceinline__ uint32_t fl_luma_scalar(const uint8_t *p, size_t plane)
+{
+    const uint16_t *q = reinterpret_cast<const uint16_t *>(p);
+    switch (LAYOUT) {
+    case FL_LA8: return p[0];
+    case FL_RGBA8: return fl_weighted(p[0], p[1], p[2]);
+    case FL_BGRA8:
+    case FL_BGR8: return fl_weighted(p[2], p[1], p[0]);
+    case FL_RGB8P: return fl_weighted(p[0], p[plane], p[2 * plane]);
+    case FL_LA16: return q[0];
+    default: return fl_weighted(q[0], q[1], q[2]);  // FL_RGB16, FL_RGBA16
+    }
+}
+
+template <int LAYOUT, bool OUT8>
+__global__ void __launch_bounds__(256) k_front_luma(const uint8_t *__restrict__ src, long long frame_stride, int row_stride,
+                                                    uint8_t *__restrict__ dst, int W, int H, int vec)
+{
+    using L = FrontLayout<LAYOUT>;
+    constexpr bool WIDE = L::in16 && !OUT8;  // u16 out
+    const int x0 = ((int)blockIdx.x * 64 + (int)threadIdx.x) * 4;
+    if (x0 >= W) return;
+    // rows y0, y0 + 4, ..: a wave (one threadIdx.y, said to the compiler) reads one row per load
+    const int y0 = (int)blockIdx.y * (4 * FL_ROWS) + __builtin_amdgcn_readfirstlane((int)threadIdx.y);
+    const size_t plane = (size_t)H * (size_t)row_stride;
+    const uint8_t *in = src + (size_t)blockIdx.z * (size_t)frame_stride + (size_t)x0 * L::bpp;
+    uint8_t *out = dst + ((size_t)blockIdx.z * (size_t)H * (size_t)W + (size_t)x0) * (WIDE ? 2 : 1);
+    const size_t out_row = (size_t)W * (WIDE ? 2 : 1);
+    auto narrow = [](uint32_t l) { return (L::in16 && OUT8) ? (l + 128u) / 257u : l; };
+    if (vec) {  // (wave-uniform) W % 4 == 0: the lane's 4 pixels are all inside the row
+        uint32_t d[FL_ROWS][8];
+#pragma unroll
+        for (int j = 0; j < FL_ROWS; ++j)  // (rows past the last one: the last one again, not stored)
+            fl_load4<LAYOUT>(in + (size_t)min(y0 + 4 * j, H - 1) * (size_t)row_stride, plane, d[j]);
+#pragma unroll
+        for (int j = 0; j < FL_ROWS; ++j) {
+            const int y = y0 + 4 * j;
+            if (y >= H) continue;
+            uint32_t l[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) l[i] = narrow(fl_luma_of<LAYOUT>(d[j], i));
+            uint8_t *o = out + (size_t)y * out_row;
+            if (WIDE) *reinterpret_cast<uint2 *>(o) = make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16));
+            else *reinterpret_cast<uint32_t *>(o) = l[0] | (l[1] << 8) | (l[2] << 16) | (l[3] << 24);
+        }
+    } else {
+        for (int j = 0; j < FL_ROWS; ++j) {
+            const int y = y0 + 4 * j;
+            if (y >= H) break;
+            const uint8_t *r = in + (size_t)y * (size_t)row_stride;
+            uint8_t *o = out + (size_t)y * out_row;
+            for (int i = 0; i < 4 && x0 + i < W; ++i) {
+                const uint32_t l = narrow(fl_luma_scalar<LAYOUT>(r + i * L::bpp, plane));
+                if (WIDE) reinterpret_cast<uint16_t *>(o)[i] = (uint16_t)l;
+                else o[i] = (uint8_t)l;
+            }
+        }
+    }
+}
+
+int launch_front_luma(const void *src, size_t row_stride, size_t frame_stride, int n_frames, int format, void *dst, int out8, int W,
+                      int H, void *stream)
+{
+    if (n_frames <= 0 || n_frames > 65535 || W < 1 || H < 1 || row_stride > 0x7fffffffu) return (int)hipErrorInvalidValue;
+    const bool wide = format >= FL_LA16 && !out8;
+    const bool vec = (((uintptr_t)src | row_stride | (n_frames > 1 ? frame_stride : 0) | (size_t)W) & 3) == 0 &&
+                     ((uintptr_t)dst & (wide ? 7 : 3)) == 0;
+    const dim3 grid((unsigned)((W + 255) / 256), (unsigned)((H + 4 * FL_ROWS - 1) / (4 * FL_ROWS)), (unsigned)n_frames), block(64, 4);
+    if (grid.y > 65535u) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const uint8_t *s = (const uint8_t *)src;
+    uint8_t *d = (uint8_t *)dst;
+    const long long fs = (long long)frame_stride;
+    const int rs = (int)row_stride, v = vec ? 1 : 0;
+#define AGX_FRONT(LAYOUT, OUT8) hipLaunchKernelGGL((k_front_luma<LAYOUT, OUT8>), grid, block, 0, st, s, fs, rs, d, W, H, v)
+    switch (format) {
+    case FL_LA8: AGX_FRONT(FL_LA8, false); break;
+    case FL_RGBA8: AGX_FRONT(FL_RGBA8, false); break;
+    case FL_BGR8: AGX_FRONT(FL_BGR8, false); break;
+    case FL_BGRA8: AGX_FRONT(FL_BGRA8, false); break;
+    case FL_RGB8P: AGX_FRONT(FL_RGB8P, false); break;
+    case FL_LA16:
+        if (out8) AGX_FRONT(FL_LA16, true);
+        else AGX_FRONT(FL_LA16, false);
+        break;
+    case FL_RGB16:
+        if (out8) AGX_FRONT(FL_RGB16, true);
+        else AGX_FRONT(FL_RGB16, false);
+        break;
+    case FL_RGBA16:
+        if (out8) AGX_FRONT(FL_RGBA16, true);
+        else AGX_FRONT(FL_RGBA16, false);
+        break;
+    default: return (int)hipErrorInvalidValue;
+    }
+#undef AGX_FRONT
+    return hipGetLastError();
+}
+
 int launch_luma8(const void *src, size_t pitch, size_t frame_stride, int n_frames, int format, uint8_t *dst, int W, int H, void *stream)
 {
+    if (format >= FL_LA8 && format <= FL_RGBA16) return launch_front_luma(src, pitch, frame_stride, n_frames, format, dst, 1, W, H, stream);
     const size_t n = (size_t)W * (size_t)H * (size_t)n_frames;
     const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 16384);
     if (format == 1)

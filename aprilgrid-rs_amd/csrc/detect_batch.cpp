@@ -519,13 +519,14 @@ static int detect_batch_impl(agx_detector *det, const void *frames, const void *
                              uint32_t cap_per_frame, uint32_t *counts, int *frame_status, int n_threads)
 {
     if (!det || !frames || !counts || n_frames <= 0 || (!out && cap_per_frame)) return AGX_ERR_ARG;
-    if (format != AGX_L8 && format != AGX_L16 && format != AGX_RGB8) return AGX_ERR_FORMAT;  // the tail derives to_luma8 itself
+    const size_t bpp = (size_t)format_px_bytes(format);
+    if (!bpp || format == AGX_LF32) return AGX_ERR_FORMAT;  // the tail derives to_luma8 itself: every integer format
     if (width < 2 || height < 2) return AGX_ERR_ARG;
-    const size_t bpp = format == AGX_L8 ? 1 : (format == AGX_L16 ? 2 : 3);
-    if (row_stride_bytes < (size_t)width * bpp || (n_frames > 1 && frame_stride_bytes < row_stride_bytes * (size_t)height)) return AGX_ERR_ARG;
+    const size_t frame_bytes = row_stride_bytes * format_rows(format, height);
+    if (row_stride_bytes < (size_t)width * bpp || (n_frames > 1 && frame_stride_bytes < frame_bytes)) return AGX_ERR_ARG;
     // one frame: the stride between frames means nothing to the caller (0 is a natural value), but the staging
     // and the upload below are sized by it -- use the frame's own extent
-    if (n_frames == 1 && frame_stride_bytes < row_stride_bytes * (size_t)height) frame_stride_bytes = row_stride_bytes * (size_t)height;
+    if (n_frames == 1 && frame_stride_bytes < frame_bytes) frame_stride_bytes = frame_bytes;
     // 0 = every CPU this process may keep busy: its affinity mask or its cgroup quota, whichever is smaller (threads beyond a
     // quota are not merely idle: the quota is spent sooner and EVERY thread of the process, the one driving the device
     // included, is frozen for the rest of the scheduler period -- profiles/r5_host_cpu_quota_and_tail_scaling.txt)

@@ -77,8 +77,9 @@ struct agx_detector {
         bool host = false;     // pinned host memory (mapped when dev != nullptr)
         void *dev = nullptr;   // device address of the payload of a mapped host buffer
     };
-    // (SB_DTAGS .. SB_FETCH_LUMA: agx_detect_batch_enqueue_to's device tail results, agx_detect_batch_fetch's luma planes)
-    enum { SB_STAGE, SB_LUMA_D, SB_LUMA_H, SB_CODES, SB_TAGS, SB_TAIL_TABLE, SB_DTAGS, SB_DTABLE, SB_FETCH_LUMA, SB_COUNT };
+    // (SB_DTAGS .. SB_FETCH_LUMA: agx_detect_batch_enqueue_to's device tail results, agx_detect_batch_fetch's luma planes;
+    // SB_FRONT: the front-end kernel's integer luma plane of a batch in one of the layouts AGX_LA8 .. AGX_RGBA16)
+    enum { SB_STAGE, SB_LUMA_D, SB_LUMA_H, SB_CODES, SB_TAGS, SB_TAIL_TABLE, SB_DTAGS, SB_DTABLE, SB_FETCH_LUMA, SB_FRONT, SB_COUNT };
     SideBuf side[SB_COUNT];
     // staging for the single-frame host API
     uint8_t *d_stage = nullptr;
@@ -86,6 +87,15 @@ struct agx_detector {
     // agx_detect on L16 / RGB8: the u8 luma of the staged frame, computed on the device
     uint8_t *d_luma = nullptr, *h_luma = nullptr;
     size_t luma_bytes = 0;
+    // AGX_LA8 .. AGX_RGBA16: k_front_luma's plane of the batch, tight [n][H][W] u8 / u16 -- what the chain reads instead of the
+    // frames; front_src / front_format / front_frames name the batch it holds, so that to_luma8 is derived from it instead of
+    // from the frames again (an 8-bit layout: it IS that plane).  They are valid only from batch_enqueue_impl to the next
+    // enqueue on the handle, which resets them first (format -1: none): whoever asks for the luma of a batch does so right
+    // behind that batch's enqueue, on the same stream
+    uint8_t *d_front = nullptr;
+    size_t front_bytes = 0;
+    const void *front_src = nullptr;
+    int front_format = -1, front_frames = 0;
     // pinned host mirrors
     FrameCounters *h_ctr = nullptr;
     size_t h_ctr_frames = 0;
@@ -573,9 +583,9 @@ int frame_status_of(const FrameCounters &c, uint32_t cap_per_frame)
     return AGX_OK;
 }
 
-bool valid_format(int f) { return f == AGX_L8 || f == AGX_L16 || f == AGX_RGB8 || f == AGX_LF32; }
-int bytes_per_px(int f) { return f == AGX_L8 ? 1 : (f == AGX_L16 ? 2 : (f == AGX_RGB8 ? 3 : 4)); }
-const char *kFormatMsg = "format must be AGX_L8, AGX_L16, AGX_RGB8 or AGX_LF32";
+bool valid_format(int f) { return format_px_bytes(f) != 0; }
+int bytes_per_px(int f) { return format_px_bytes(f); }
+const char *kFormatMsg = "format must be one of AGX_L8 .. AGX_RGBA16 (agx_format)";
 
 }  // namespace
 
@@ -611,6 +621,15 @@ __attribute__((visibility("hidden"))) int agx_internal_chunk_luma8(agx_detector 
 {
     const size_t plane = (size_t)width * (size_t)height, one = plane * chunk_capacity_frames;
     if (slot < 0 || slot >= n_slots) return AGX_ERR_ARG;
+    // a layout of the front-end kernel whose plane the chain of these very frames has just read (the batch enqueued last):
+    // 8-bit: that plane IS their to_luma8; 16-bit: k_luma8 narrows it (2 bytes per pixel to read instead of the frames' 4 .. 8)
+    const bool same_batch = format_front(format) && det->enqueued && det->front_format == format && det->front_src == d_frames &&
+                            det->front_frames == n_frames;
+    const bool front = same_batch && !format_16bit(format), front16 = same_batch && format_16bit(format);
+    if (front && !h_out) {
+        if (d_out) *d_out = det->d_front;
+        return AGX_OK;
+    }
     if ((size_t)n_slots * one > det->luma_bytes) {
         if (hipStreamSynchronize(det->stream) != hipSuccess) return AGX_ERR_HIP;
         det->luma_bytes = 0;
@@ -620,7 +639,10 @@ __attribute__((visibility("hidden"))) int agx_internal_chunk_luma8(agx_detector 
         det->luma_bytes = (size_t)n_slots * one;
     }
     uint8_t *d = det->d_luma + (size_t)slot * one, *h = det->h_luma + (size_t)slot * one;
-    if (launch_luma8(d_frames, row_stride, frame_stride, n_frames, format, d, width, height, det->stream) != 0) return AGX_ERR_HIP;
+    if (front) d = det->d_front;
+    else if (front16) {
+        if (launch_luma8(det->d_front, (size_t)width * 2, plane * 2, n_frames, AGX_L16, d, width, height, det->stream) != 0) return AGX_ERR_HIP;
+    } else if (launch_luma8(d_frames, row_stride, frame_stride, n_frames, format, d, width, height, det->stream) != 0) return AGX_ERR_HIP;
     if (d_out) *d_out = d;  // (the device tail reads it there; no copy to the host unless asked for)
     if (!h_out) return AGX_OK;
     if (hipMemcpyAsync(h, d, plane * (size_t)n_frames, hipMemcpyDeviceToHost, det->stream) != hipSuccess) return AGX_ERR_HIP;
@@ -1088,20 +1110,45 @@ static int batch_enqueue_impl(agx_detector *det, const void *d_frames, int n_fra
     if ((long long)width * height >= (1ll << 30) || width > 65000) return fail(det, AGX_ERR_ARG, "frame too large (>= 2^30 px or wider than 65000)");
     const size_t px_bytes = (size_t)bytes_per_px(format);
     if (row_stride_bytes < (size_t)width * px_bytes || row_stride_bytes > 0x7fffffffu ||
-        (n_frames > 1 && frame_stride_bytes < row_stride_bytes * (size_t)height))
+        (n_frames > 1 && frame_stride_bytes < row_stride_bytes * format_rows(format, height)))
         return fail(det, AGX_ERR_ARG, "strides must cover a row / a frame");
-    if (format == AGX_L16 && ((row_stride_bytes | frame_stride_bytes | (uintptr_t)d_frames) & 1))
+    if (format_16bit(format) && ((row_stride_bytes | frame_stride_bytes | (uintptr_t)d_frames) & 1))
         return fail(det, AGX_ERR_ARG, "16-bit pixels must be 2-byte aligned");
     if (format == AGX_LF32 && ((row_stride_bytes | frame_stride_bytes | (uintptr_t)d_frames) & 3))
         return fail(det, AGX_ERR_ARG, "f32 pixels must be 4-byte aligned");
-    // rows that are not 4-byte aligned (tightly packed L8 / RGB8 of a width that is not a multiple
-    // of 4, odd-width L16): the blur kernel gathers bytes instead of loading dwords
-    const bool byte_rows = ((row_stride_bytes | (uintptr_t)d_frames | (n_frames > 1 ? frame_stride_bytes : 0)) & 3) != 0;
     if (n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
+    if (format_front(format) && height > 16 * 65535)  // (k_front_luma's grid: 16 rows per workgroup, 65535 workgroups)
+        return fail(det, AGX_ERR_ARG, "frames of this format may have at most 1048560 rows");
     det->detect.kind = 0;  // (this batch replaces whatever was in flight, an agx_detect_batch_enqueue's included)
+    det->front_format = -1;
     HIP_TRY(det, hipSetDevice(det->device));
     int rc = ensure_workspace(det, n_frames, width, height);
     if (rc) return rc;
+    if (format_front(format)) {
+        // AGX_LA8 .. AGX_RGBA16: the front-end kernel writes the batch's integer luma plane (tight u8 / u16) and the L8 / L16
+        // chain reads that: to_luma32f of an integer image is its integer luma / 255 (/ 65535)
+        const size_t out_px = format_16bit(format) ? 2 : 1, need = (size_t)n_frames * (size_t)width * (size_t)height * out_px;
+        if (need > det->front_bytes) {
+            HIP_TRY(det, hipStreamSynchronize(det->stream));
+            det->front_bytes = 0;
+            det->d_front = static_cast<uint8_t *>(side_alloc(det, agx_detector::SB_FRONT, need, 0));
+            if (!det->d_front) return fail(det, AGX_ERR_HIP, "hipMalloc: front-end luma plane");
+            det->front_bytes = need;
+        }
+        hipError_t e = (hipError_t)launch_front_luma(d_frames, row_stride_bytes, frame_stride_bytes, n_frames, format, det->d_front, 0,
+                                                     width, height, det->stream);
+        if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_front_luma: ") + hipGetErrorString(e));
+        det->front_src = d_frames;
+        det->front_format = format;
+        det->front_frames = n_frames;
+        d_frames = det->d_front;
+        row_stride_bytes = (size_t)width * out_px;
+        frame_stride_bytes = row_stride_bytes * (size_t)height;
+        format = out_px == 2 ? AGX_L16 : AGX_L8;
+    }
+    // rows that are not 4-byte aligned (tightly packed L8 / RGB8 of a width that is not a multiple
+    // of 4, odd-width L16): the blur kernel gathers bytes instead of loading dwords
+    const bool byte_rows = ((row_stride_bytes | (uintptr_t)d_frames | (n_frames > 1 ? frame_stride_bytes : 0)) & 3) != 0;
     ChainArgs &a = det->args;
     a.frames = (const uint8_t *)d_frames;
     a.frame_stride = (long long)frame_stride_bytes;
@@ -1275,8 +1322,8 @@ static int detect_enqueue_checked(agx_detector *det, const void *d_frames, int n
                                   uint32_t *d_counts, int *d_status)
 {
     if (!det) return AGX_ERR_ARG;
-    if (format != AGX_L8 && format != AGX_L16 && format != AGX_RGB8)  // (the decode needs to_luma8: agx_detect_planes for the rest)
-        return fail(det, AGX_ERR_FORMAT, "format must be AGX_L8, AGX_L16 or AGX_RGB8");
+    if (!valid_format(format) || format == AGX_LF32)  // (the decode needs to_luma8: agx_detect_planes for an f32 plane)
+        return fail(det, AGX_ERR_FORMAT, "format must be an integer agx_format (AGX_LF32: agx_detect_planes)");
     if (to_device && (!d_counts || !d_status || (!d_tags && cap_per_frame) || (((uintptr_t)d_tags | (uintptr_t)d_counts | (uintptr_t)d_status) & 3)))
         return fail(det, AGX_ERR_ARG, "null or misaligned output buffers");
     return detect_enqueue_impl(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, cap_per_frame, to_device,
@@ -1330,7 +1377,8 @@ int refined_saddle_points_impl(agx_detector *det, const void *pixels, int width,
     if (row_stride_bytes < row_bytes) return fail(det, AGX_ERR_ARG, "row stride smaller than a row");
     HIP_TRY(det, hipSetDevice(det->device));
     const size_t pitch = (row_bytes + 3) & ~(size_t)3;
-    const size_t need = pitch * (size_t)height;
+    const size_t rows = format_rows(format, height);  // (the planar layout: three planes, one under the other)
+    const size_t need = pitch * rows;
     if (need > det->stage_bytes) {
         HIP_TRY(det, hipStreamSynchronize(det->stream));
         det->stage_bytes = 0;
@@ -1338,7 +1386,7 @@ int refined_saddle_points_impl(agx_detector *det, const void *pixels, int width,
         if (!det->d_stage) return fail(det, AGX_ERR_HIP, "hipMalloc: staging buffer");
         det->stage_bytes = need;
     }
-    HIP_TRY(det, hipMemcpy2DAsync(det->d_stage, pitch, pixels, row_stride_bytes, row_bytes, (size_t)height,
+    HIP_TRY(det, hipMemcpy2DAsync(det->d_stage, pitch, pixels, row_stride_bytes, row_bytes, rows,
                                   hipMemcpyHostToDevice, det->stream));
     int rc = agx_saddles_batch_enqueue(det, det->d_stage, 1, width, height, pitch, need, format);
     if (rc) return rc;

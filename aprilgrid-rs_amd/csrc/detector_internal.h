@@ -47,6 +47,23 @@ const uint32_t *agx_internal_device_tail_table(agx_detector *det);
 uint8_t *agx_internal_fetch_luma(agx_detector *det, size_t bytes);
 }
 namespace agx {
+// agx_format: bytes between horizontally adjacent pixels (0: not a format), the rows a frame of `height` spans (the planar
+// layout: three planes), the layouts the front-end kernel converts (k_front_luma) and which of those have 16-bit channels
+inline int format_px_bytes(int f)
+{
+    switch (f) {
+    case AGX_L8: case AGX_RGB8P: return 1;
+    case AGX_L16: case AGX_LA8: return 2;
+    case AGX_RGB8: case AGX_BGR8: return 3;
+    case AGX_LF32: case AGX_RGBA8: case AGX_BGRA8: case AGX_LA16: return 4;
+    case AGX_RGB16: return 6;
+    case AGX_RGBA16: return 8;
+    default: return 0;
+    }
+}
+inline size_t format_rows(int f, int height) { return (size_t)height * (f == AGX_RGB8P ? 3u : 1u); }
+inline bool format_front(int f) { return f >= AGX_LA8 && f <= AGX_RGBA16; }
+inline bool format_16bit(int f) { return f == AGX_L16 || f == AGX_LA16 || f == AGX_RGB16 || f == AGX_RGBA16; }
 void destroy_worker_pool(void *pool);
 void *create_worker_pool(int n_threads);
 struct TailWorkers;  // host_tail.hpp

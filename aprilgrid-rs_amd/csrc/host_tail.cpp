@@ -1367,6 +1367,41 @@ int luma8(const void *pixels, int width, int height, size_t row_stride, int form
             for (int x = 0; x < width; ++x)
                 o[x] = (uint8_t)((2126u * row[3 * x] + 7152u * row[3 * x + 1] + 722u * row[3 * x + 2]) / 10000u);
             break;
+        // the layouts of the front-end kernel (chain_kernels.hip, k_front_luma), by the same integer expressions
+        case AGX_LA8:
+            for (int x = 0; x < width; ++x) o[x] = row[2 * x];
+            break;
+        case AGX_RGBA8:
+            for (int x = 0; x < width; ++x)
+                o[x] = (uint8_t)((2126u * row[4 * x] + 7152u * row[4 * x + 1] + 722u * row[4 * x + 2]) / 10000u);
+            break;
+        case AGX_BGR8:
+        case AGX_BGRA8: {
+            const int n = format == AGX_BGR8 ? 3 : 4;
+            for (int x = 0; x < width; ++x)
+                o[x] = (uint8_t)((2126u * row[n * x + 2] + 7152u * row[n * x + 1] + 722u * row[n * x]) / 10000u);
+            break;
+        }
+        case AGX_RGB8P: {
+            const uint8_t *g = row + (size_t)height * row_stride, *b = g + (size_t)height * row_stride;
+            for (int x = 0; x < width; ++x) o[x] = (uint8_t)((2126u * row[x] + 7152u * g[x] + 722u * b[x]) / 10000u);
+            break;
+        }
+        case AGX_LA16: {
+            const uint16_t *r16 = (const uint16_t *)row;
+            for (int x = 0; x < width; ++x) o[x] = (uint8_t)(((uint32_t)r16[2 * x] + 128u) / 257u);
+            break;
+        }
+        case AGX_RGB16:
+        case AGX_RGBA16: {
+            const uint16_t *r16 = (const uint16_t *)row;
+            const int n = format == AGX_RGB16 ? 3 : 4;
+            for (int x = 0; x < width; ++x) {
+                const uint32_t l16 = (2126u * r16[n * x] + 7152u * r16[n * x + 1] + 722u * r16[n * x + 2]) / 10000u;
+                o[x] = (uint8_t)((l16 + 128u) / 257u);
+            }
+            break;
+        }
         default: return AGX_ERR_FORMAT;
         }
     }

@@ -9,7 +9,9 @@ Same names, argument meaning and error behaviour as the reference where Python a
   TagDetector.detect                  src/detector.rs:505-540
   TagDetector.detect_kornia           src/detector.rs:478-503
 An image is a numpy array standing for the DynamicImage variants the reference is fed:
-HxW uint8 (ImageLuma8), HxW uint16 (ImageLuma16), HxWx3 uint8 (ImageRgb8).
+HxW uint8 (ImageLuma8), HxW uint16 (ImageLuma16), HxWx3 uint8 (ImageRgb8); HxWx2 / HxWx4 uint8 (ImageLumaA8, ImageRgba8),
+HxWx2 / HxWx3 / HxWx4 uint16 (ImageLumaA16, ImageRgb16, ImageRgba16).  BGR / BGRA order and channel-first planes (3xHxW uint8)
+are named with format=: the shape cannot tell them from RGB / RGBA or a three-row HxWx? image.
 """
 import ctypes as C
 import enum
@@ -72,8 +74,35 @@ class DetectorParams:
                            self.max_num_of_boards)
 
 
-def _image_args(img):
+def _check_layout(shape, itemsize, kind, fmt):
+    """format= override: the array / tensor [..., H, W(, C)] (or [..., 3, H, W] for the planar layout) must be what `fmt` says;
+    -> (H, W, bytes per pixel of a row)."""
+    if fmt not in _ffi.FORMAT_LAYOUT:
+        raise AgxError(_ffi.AGX_ERR_FORMAT, "unknown format %r" % (fmt,))
+    bpp, planes, dt = _ffi.FORMAT_LAYOUT[fmt]
+    ch = bpp // int(dt[1])
+    want_kind = {"u": "iu", "f": "f"}[dt[0]]  # (torch spells 16-bit pixels int16 where it has no uint16)
+    ok = itemsize == int(dt[1]) and kind in want_kind
+    if planes == 3:
+        ok = ok and len(shape) >= 3 and shape[-3] == 3
+    elif ch == 1:
+        ok = ok and len(shape) >= 2
+        shape = tuple(shape) + (1,)
+    else:
+        ok = ok and len(shape) >= 3 and shape[-1] == ch
+        shape = tuple(shape)
+    if not ok:
+        raise AgxError(_ffi.AGX_ERR_FORMAT, "array %s of %d-byte elements is not format %d" % (tuple(shape), itemsize, fmt))
+    return (shape[-2], shape[-1], bpp) if planes == 3 else (shape[-3], shape[-2], bpp)
+
+
+def _image_args(img, format=None):
     a = np.ascontiguousarray(img)
+    if format is not None:
+        h, w, bpp = _check_layout(a.shape, a.dtype.itemsize, a.dtype.kind, format)
+        if format == _ffi.AGX_RGB8P:  # the three planes one under the other, as the library reads them
+            a = a.reshape(3 * h, w)
+        return a, format, w * bpp
     if a.ndim == 3 and a.shape[2] == 1:
         a = a[:, :, 0]
         a = np.ascontiguousarray(a)
@@ -85,8 +114,17 @@ def _image_args(img):
         return a, _ffi.AGX_RGB8, a.shape[1] * 3
     if a.ndim == 2 and a.dtype == np.float32:  # the caller's own to_luma32f plane (any DynamicImage variant)
         return a, _ffi.AGX_LF32, a.shape[1] * 4
-    raise AgxError(_ffi.AGX_ERR_FORMAT, "image must be HxW uint8/uint16/float32 or HxWx3 uint8, got %s %s"
+    if a.ndim == 3 and a.dtype == np.uint8 and a.shape[2] in (2, 4):
+        return a, (_ffi.AGX_LA8 if a.shape[2] == 2 else _ffi.AGX_RGBA8), a.shape[1] * a.shape[2]
+    if a.ndim == 3 and a.dtype == np.uint16 and a.shape[2] in (2, 3, 4):
+        return a, {2: _ffi.AGX_LA16, 3: _ffi.AGX_RGB16, 4: _ffi.AGX_RGBA16}[a.shape[2]], a.shape[1] * a.shape[2] * 2
+    raise AgxError(_ffi.AGX_ERR_FORMAT, "image must be HxW uint8/uint16/float32 or HxWx{2,3,4} uint8/uint16, got %s %s"
                    % (a.shape, a.dtype))
+
+
+def _image_hw(a, fmt):
+    """(H, W) of the array _image_args returned (the planar layout is a [3H, W] array)."""
+    return (a.shape[0] // 3, a.shape[1]) if fmt == _ffi.AGX_RGB8P else a.shape[:2]
 
 
 class TagDetector:
@@ -129,10 +167,11 @@ class TagDetector:
             raise AgxError(st, self._lib.agx_last_error(self._h).decode())
 
     # ---- reference API -------------------------------------------------------------------
-    def refined_saddle_points(self, img, as_array=False, cap=16384):
-        """-> Vec<Saddle> (list of Saddle) or, with as_array=True, a SADDLE_DTYPE array."""
-        a, fmt, stride = _image_args(img)
-        h, w = a.shape[:2]
+    def refined_saddle_points(self, img, as_array=False, cap=16384, format=None):
+        """-> Vec<Saddle> (list of Saddle) or, with as_array=True, a SADDLE_DTYPE array.  format: the agx_format of `img`
+        instead of the one its shape and dtype suggest (BGR / BGRA order, 3xHxW planes)."""
+        a, fmt, stride = _image_args(img, format)
+        h, w = _image_hw(a, fmt)
         # the library writes into a buffer this handle keeps (plain f32 rows: allocating and slicing a structured array per call
         # cost 12 us of a 116 us call); the caller gets its own copy
         buf = self._saddle_buf
@@ -154,10 +193,10 @@ class TagDetector:
         return [Saddle((float(s["x"]), float(s["y"])), float(s["k"]), float(s["theta"]), float(s["phi"]))
                 for s in res]
 
-    def detect(self, img, cap=4096):
-        """-> HashMap<u32, [(f32,f32);4]> as {tag_id: 4x2 float32 array}."""
-        a, fmt, stride = _image_args(img)
-        h, w = a.shape[:2]
+    def detect(self, img, cap=4096, format=None):
+        """-> HashMap<u32, [(f32,f32);4]> as {tag_id: 4x2 float32 array}.  format: as refined_saddle_points."""
+        a, fmt, stride = _image_args(img, format)
+        h, w = _image_hw(a, fmt)
         out = (_ffi.TagC * cap)()
         n = C.c_uint32(0)
         self._check(self._lib.agx_detect(self._h, a.ctypes.data, w, h, stride, fmt, out, cap, C.byref(n)))
@@ -178,16 +217,18 @@ class TagDetector:
 
     TAG_DTYPE = np.dtype([("id", "u4"), ("xy", "f4", (8,))])
 
-    def detect_batch_raw(self, frames, n_threads=0, cap=1024, device_frames=None, out=None, counts=None, status=None):
+    def detect_batch_raw(self, frames, n_threads=0, cap=1024, device_frames=None, out=None, counts=None, status=None, format=None):
         """agx_detect_batch as a C / Rust caller uses it: frames = numpy [N,H,W] uint8 / uint16 or [N,H,W,3] uint8 in
         host memory (optionally also resident on the GPU as the torch tensor device_frames); the tags go into the
         caller's arrays out [N, cap] of TAG_DTYPE, counts [N] uint32, status [N] int32 (allocated when None).
         -> (rc, out, counts, status); nothing is raised for a capacity status."""
         a = np.ascontiguousarray(frames)
-        _, fmt, stride = _image_args(a[0])
+        img0, fmt, stride = _image_args(a[0], format)
         if fmt == _ffi.AGX_LF32:
-            raise AgxError(_ffi.AGX_ERR_FORMAT, "detect_batch takes L8 / L16 / RGB8 frames")
-        n, h, w = a.shape[:3]
+            raise AgxError(_ffi.AGX_ERR_FORMAT, "detect_batch takes frames of integer pixels")
+        n = a.shape[0]
+        h, w = _image_hw(img0, fmt)
+        frame_stride = stride * h * _ffi.FORMAT_LAYOUT[fmt][1]
         if out is None:
             out = np.zeros((n, cap), self.TAG_DTYPE)
         if counts is None:
@@ -208,11 +249,11 @@ class TagDetector:
                 raise AgxError(_ffi.AGX_ERR_ARG, "device_frames %s / %d-byte elements differ from frames %s / %d-byte elements"
                                % (tuple(t.shape), t.element_size(), tuple(a.shape), a.dtype.itemsize))
             dptr = t.data_ptr()
-        rc = self._lib.agx_detect_batch(self._h, a.ctypes.data, dptr, n, w, h, stride, stride * h, fmt,
+        rc = self._lib.agx_detect_batch(self._h, a.ctypes.data, dptr, n, w, h, stride, frame_stride, fmt,
                                         out.ctypes.data, cap, counts.ctypes.data, status.ctypes.data, n_threads)
         return rc, out, counts, status
 
-    def detect_batch(self, frames, n_threads=0, cap=1024, device_frames=None, raise_on_overflow=True):
+    def detect_batch(self, frames, n_threads=0, cap=1024, device_frames=None, raise_on_overflow=True, format=None):
         """detect() over a batch: frames = numpy [N,H,W] uint8 / uint16 or [N,H,W,3] uint8 in host
         memory (optionally also resident on the GPU as the torch tensor device_frames).  The chain
         runs on the device chunk by chunk while n_threads host threads (0 = agx_host_parallelism(): the
@@ -221,7 +262,7 @@ class TagDetector:
         over the detector's saddle capacity) raises by default; raise_on_overflow=False returns
         (results, status) instead: status[i] != 0 marks such a frame (its entry is None), every other
         frame keeps its result."""
-        rc, out, counts, status = self.detect_batch_raw(frames, n_threads, cap, device_frames)
+        rc, out, counts, status = self.detect_batch_raw(frames, n_threads, cap, device_frames, format=format)
         n = len(counts)
         if rc != _ffi.AGX_OK and (raise_on_overflow or rc != _ffi.AGX_ERR_CAPACITY):
             self._check(rc)
@@ -265,9 +306,9 @@ class TagDetector:
         return {int(out[i].id): np.array(out[i].xy, np.float32).reshape(4, 2) for i in range(n.value)}
 
     @staticmethod
-    def luma8(img):
-        a, fmt, stride = _image_args(img)
-        h, w = a.shape[:2]
+    def luma8(img, format=None):
+        a, fmt, stride = _image_args(img, format)
+        h, w = _image_hw(a, fmt)
         out = np.empty((h, w), np.uint8)
         st = _ffi.lib().agx_luma8(a.ctypes.data, w, h, stride, fmt, out.ctypes.data)
         if st != _ffi.AGX_OK:
@@ -305,41 +346,64 @@ class TagDetector:
             self.set_stream(s)
 
     @staticmethod
-    def _tensor_format(frames):
+    def _tensor_format(frames, format=None):
+        """-> (agx_format, bytes per pixel of a row); format: the caller's word instead of what the shape suggests."""
         import torch
         if not frames.is_cuda or not frames.is_contiguous():
             raise AgxError(_ffi.AGX_ERR_ARG, "frames must be a contiguous device tensor")
+        if format is not None:
+            kind = "f" if frames.dtype.is_floating_point else "i"
+            return format, _check_layout(tuple(frames.shape[1:]), frames.element_size(), kind, format)[2]
+        sixteen = (torch.int16, getattr(torch, "uint16", torch.int16))
         if frames.dim() == 3 and frames.dtype == torch.uint8:
             return _ffi.AGX_L8, 1
-        if frames.dim() == 3 and frames.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)):
+        if frames.dim() == 3 and frames.dtype in sixteen:
             return _ffi.AGX_L16, 2
         if frames.dim() == 4 and frames.shape[3] == 3 and frames.dtype == torch.uint8:
             return _ffi.AGX_RGB8, 3
         if frames.dim() == 3 and frames.dtype == torch.float32:
             return _ffi.AGX_LF32, 4
+        if frames.dim() == 4 and frames.dtype == torch.uint8 and frames.shape[3] in (2, 4):
+            if frames.shape[1] == 3:  # [N,3,H,2|4]: three planes of a narrow image, or a 3-row LA8 / RGBA8 image?
+                raise AgxError(_ffi.AGX_ERR_FORMAT, "frame tensor %s is ambiguous (channel-first or channel-last): name it with format="
+                               % (tuple(frames.shape),))
+            return (_ffi.AGX_LA8, 2) if frames.shape[3] == 2 else (_ffi.AGX_RGBA8, 4)
+        if frames.dim() == 4 and frames.dtype == torch.uint8 and frames.shape[1] == 3:  # channel-first (shape[3] != 3 here)
+            return _ffi.AGX_RGB8P, 1
+        if frames.dim() == 4 and frames.dtype in sixteen and frames.shape[3] in (2, 3, 4):
+            return {2: (_ffi.AGX_LA16, 4), 3: (_ffi.AGX_RGB16, 6), 4: (_ffi.AGX_RGBA16, 8)}[int(frames.shape[3])]
         raise AgxError(_ffi.AGX_ERR_FORMAT, "unsupported frame tensor %s %s" % (tuple(frames.shape), frames.dtype))
 
-    def saddles_batch_enqueue(self, frames):
-        """frames: a torch tensor on this detector's GPU -- [N,H,W] uint8 (L8), [N,H,W] int16/uint16
-        (L16) or [N,H,W,3] uint8 (RGB8), contiguous.  Returns immediately; see saddles_batch_fetch."""
-        fmt, bpp = self._tensor_format(frames)
+    @staticmethod
+    def _tensor_geometry(frames, fmt, bpp):
+        """-> (n, w, h, row stride, frame stride) of a contiguous batch tensor in format fmt."""
+        planes = _ffi.FORMAT_LAYOUT[fmt][1]
+        n = frames.shape[0]
+        h, w = (frames.shape[2], frames.shape[3]) if planes == 3 else (frames.shape[1], frames.shape[2])
+        return n, w, h, w * bpp, w * h * bpp * planes
+
+    def saddles_batch_enqueue(self, frames, format=None):
+        """frames: a torch tensor on this detector's GPU, contiguous -- [N,H,W] uint8 (L8), [N,H,W] int16/uint16 (L16),
+        [N,H,W,3] uint8 (RGB8), [N,H,W,2] / [N,H,W,4] uint8 (LA8 / RGBA8), [N,3,H,W] uint8 with W > 4 (planar RGB8: what torch
+        image decoders return; W = 3 reads as RGB8 as ever, W = 2 or 4 is ambiguous and must be named), [N,H,W,2|3|4] int16/uint16 (LA16 / RGB16 / RGBA16).  format: the agx_format instead of the one
+        the shape suggests (AGX_BGR8 / AGX_BGRA8 can only be named).  Returns immediately; see saddles_batch_fetch."""
+        fmt, bpp = self._tensor_format(frames, format)
         self._follow_torch_stream(frames)
-        n, h, w = frames.shape[:3]
-        self._check(self._lib.agx_saddles_batch_enqueue(self._h, frames.data_ptr(), n, w, h, w * bpp, w * h * bpp,
-                                                        fmt))
+        n, w, h, rs, fs = self._tensor_geometry(frames, fmt, bpp)
+        self._check(self._lib.agx_saddles_batch_enqueue(self._h, frames.data_ptr(), n, w, h, rs, fs, fmt))
         self._batch = (n, frames)  # keep the tensor alive until fetched
         self._detect = None
 
-    def saddles_batch_enqueue_to(self, frames, out_saddles, frame_table):
+    def saddles_batch_enqueue_to(self, frames, out_saddles, frame_table, format=None):
         """Device-resident results: out_saddles float32 [capacity, 5] and frame_table int32
         [n_frames, 4] (count, offset, status, clusters) are torch tensors on the same GPU."""
-        fmt, bpp = self._tensor_format(frames)
+        fmt, bpp = self._tensor_format(frames, format)
         self._follow_torch_stream(frames)
-        n, h, w = frames.shape[:3]
+        n, w, h, rs, fs = self._tensor_geometry(frames, fmt, bpp)
         assert out_saddles.is_cuda and out_saddles.is_contiguous() and out_saddles.shape[1] == 5
         assert frame_table.is_cuda and frame_table.is_contiguous() and tuple(frame_table.shape) == (n, 4)
         self._check(self._lib.agx_saddles_batch_enqueue_to(
-            self._h, frames.data_ptr(), n, w, h, w * bpp, w * h * bpp, fmt, out_saddles.data_ptr(),
+            self._h, frames.data_ptr(), n, w, h, rs, fs, fmt, out_saddles.data_ptr(),
             out_saddles.shape[0], frame_table.data_ptr()))
         self._batch = None
         self._detect = None
@@ -390,18 +454,18 @@ class TagDetector:
             self._check(st)
         return st
 
-    def detect_batch_enqueue(self, frames, cap=1024, out=None):
-        """detect() over a batch resident on this detector's GPU: frames as saddles_batch_enqueue ([N,H,W] uint8 / int16 /
-        uint16 or [N,H,W,3] uint8, contiguous; float32 planes are refused), stream-ordered behind torch's current stream.
+    def detect_batch_enqueue(self, frames, cap=1024, out=None, format=None):
+        """detect() over a batch resident on this detector's GPU: frames and format= as saddles_batch_enqueue (every integer
+        layout, contiguous; float32 planes are refused), stream-ordered behind torch's current stream.
         Returns immediately; detect_batch_fetch waits.  out=(tags, counts, status): device-resident results instead --
         tags int32 [N, cap, 9] (id, then the 8 corner floats as bits: split_device_tags), counts int32 [N], status int32 [N],
         final once detect_batch_fetch has returned (a frame handed back to the host tail reads count 0 / AGX_ERR_STATE until then)."""
-        fmt, bpp = self._tensor_format(frames)
+        fmt, bpp = self._tensor_format(frames, format)
         if fmt == _ffi.AGX_LF32:
-            raise AgxError(_ffi.AGX_ERR_FORMAT, "detect_batch takes L8 / L16 / RGB8 frames")
-        n, h, w = frames.shape[:3]
+            raise AgxError(_ffi.AGX_ERR_FORMAT, "detect_batch takes frames of integer pixels")
+        n, w, h, rs, fs = self._tensor_geometry(frames, fmt, bpp)
         self._follow_torch_stream(frames)
-        self._enqueue_detect(frames.data_ptr(), n, w, h, w * bpp, w * h * bpp, fmt, cap, out, keep=frames)
+        self._enqueue_detect(frames.data_ptr(), n, w, h, rs, fs, fmt, cap, out, keep=frames)
 
     def detect_batch_enqueue_ptr(self, dptr, n, w, h, row_stride, frame_stride, fmt, cap=1024, out=None, follow_torch_stream=True):
         """detect_batch_enqueue on a raw device address with any row / frame stride (as saddles_batch_enqueue_ptr); the caller
@@ -460,9 +524,9 @@ class TagDetector:
                for i in range(len(counts))]
         return res if raise_on_overflow else (res, status)
 
-    def detect_batch_device(self, frames, n_threads=0, cap=1024, raise_on_overflow=True):
+    def detect_batch_device(self, frames, n_threads=0, cap=1024, raise_on_overflow=True, format=None):
         """detect_batch for frames resident on the GPU only (a torch tensor): detect_batch_enqueue + detect_batch_fetch."""
-        self.detect_batch_enqueue(frames, cap)
+        self.detect_batch_enqueue(frames, cap, format=format)
         return self.detect_batch_fetch(n_threads, raise_on_overflow)
 
     @staticmethod
@@ -576,17 +640,17 @@ class DetectorGroup:
         if st != _ffi.AGX_OK:
             raise AgxError(st, self._lib.agx_group_last_error(self._g).decode())
 
-    def saddles_enqueue(self, frames_per_rank, records_per_frame=0):
-        """frames_per_rank: one contiguous device tensor per rank ([F,H,W] u8 / int16 or [F,H,W,3] u8,
+    def saddles_enqueue(self, frames_per_rank, records_per_frame=0, format=None):
+        """frames_per_rank: one contiguous device tensor per rank (shapes and format= as TagDetector.saddles_batch_enqueue,
         same shape everywhere), rank r's on devices[r]; the caller has made sure they are ready
         (e.g. torch.cuda.synchronize): the ranks run on their detectors' own streams."""
         assert len(frames_per_rank) == len(self.devices)
-        fmt, bpp = TagDetector._tensor_format(frames_per_rank[0])
-        n, h, w = frames_per_rank[0].shape[:3]
+        fmt, bpp = TagDetector._tensor_format(frames_per_rank[0], format)
+        n, w, h, rs, fs = TagDetector._tensor_geometry(frames_per_rank[0], fmt, bpp)
         for t in frames_per_rank:
             assert tuple(t.shape) == tuple(frames_per_rank[0].shape) and t.is_contiguous() and t.is_cuda
         ptrs = (C.c_void_p * len(frames_per_rank))(*[t.data_ptr() for t in frames_per_rank])
-        self._check(self._lib.agx_group_saddles_enqueue(self._g, ptrs, n, w, h, w * bpp, w * h * bpp, fmt,
+        self._check(self._lib.agx_group_saddles_enqueue(self._g, ptrs, n, w, h, rs, fs, fmt,
                                                         records_per_frame))
         self._keep = list(frames_per_rank)
         self._frames_per_rank = n

@@ -81,6 +81,14 @@ pub const AGX_L8: c_int = 0;
 pub const AGX_L16: c_int = 1;
 pub const AGX_RGB8: c_int = 2;
 pub const AGX_LF32: c_int = 3;
+pub const AGX_LA8: c_int = 4;
+pub const AGX_RGBA8: c_int = 5;
+pub const AGX_BGR8: c_int = 6;
+pub const AGX_BGRA8: c_int = 7;
+pub const AGX_RGB8P: c_int = 8;
+pub const AGX_LA16: c_int = 9;
+pub const AGX_RGB16: c_int = 10;
+pub const AGX_RGBA16: c_int = 11;
 // per-frame status bits of the device frame table
 pub const AGX_FRAME_CANDIDATE_OVERFLOW: c_int = 1;
 pub const AGX_FRAME_CLUSTER_OVERFLOW: c_int = 2;

@@ -163,7 +163,14 @@ impl TagDetector {
             ImageLuma8(b) => (native(b.as_raw().as_ptr() as *const c_void, b.width() as usize, ffi::AGX_L8), b.width(), b.height()),
             ImageLuma16(b) => (native(b.as_raw().as_ptr() as *const c_void, 2 * b.width() as usize, ffi::AGX_L16), b.width(), b.height()),
             ImageRgb8(b) => (native(b.as_raw().as_ptr() as *const c_void, 3 * b.width() as usize, ffi::AGX_RGB8), b.width(), b.height()),
-            // La8, Rgba8, Rgb16, Rgba16, La16, Rgb32F, Rgba32F: exactly the planes the reference computes
+            // the other integer variants: no copy either, the library's front-end kernel writes their integer luma plane
+            // and the L8 / L16 chain reads that (alpha dropped; (2126 R + 7152 G + 722 B) / 10000, the image crate's own)
+            ImageLumaA8(b) => (native(b.as_raw().as_ptr() as *const c_void, 2 * b.width() as usize, ffi::AGX_LA8), b.width(), b.height()),
+            ImageRgba8(b) => (native(b.as_raw().as_ptr() as *const c_void, 4 * b.width() as usize, ffi::AGX_RGBA8), b.width(), b.height()),
+            ImageLumaA16(b) => (native(b.as_raw().as_ptr() as *const c_void, 4 * b.width() as usize, ffi::AGX_LA16), b.width(), b.height()),
+            ImageRgb16(b) => (native(b.as_raw().as_ptr() as *const c_void, 6 * b.width() as usize, ffi::AGX_RGB16), b.width(), b.height()),
+            ImageRgba16(b) => (native(b.as_raw().as_ptr() as *const c_void, 8 * b.width() as usize, ffi::AGX_RGBA16), b.width(), b.height()),
+            // Rgb32F, Rgba32F (and variants a later image crate adds): exactly the planes the reference computes
             other => (Input::Planes { luma32f: other.to_luma32f(), luma8: other.to_luma8() }, other.width(), other.height()),
         }
     }
@@ -217,14 +224,15 @@ impl TagDetector {
         Self::tags_to_map(&out[..n as usize])
     }
 
-    /// reference src/detector.rs:478-503: `kornia::image::Image<u8, N>`, N = 1 (u8c1) or 3 (u8c3, HWC interleaved); any
-    /// other N panics with the reference's message.  The tensor's storage is handed over as it is (the reference
+    /// reference src/detector.rs:478-503: `kornia::image::Image<u8, N>`, N = 1 (u8c1) or 3 (u8c3, HWC interleaved), and
+    /// beyond the reference N = 4 (u8c4 as R,G,B,A: `AGX_RGBA8`); any other N panics with the reference's message.  The tensor's storage is handed over as it is (the reference
     /// clones it into a GrayImage / RgbImage first).
     #[cfg(feature = "kornia")]
     pub fn detect_kornia<const N: usize>(&self, img: &kornia::image::Image<u8, N>) -> HashMap<u32, [(f32, f32); 4]> {
         let fmt = match img.num_channels() {
             1 => ffi::AGX_L8,
             3 => ffi::AGX_RGB8,
+            4 => ffi::AGX_RGBA8,
             _ => panic!("Only support u8c1 and u8c3"),
         };
         let (w, h) = (img.width(), img.height());

@@ -58,13 +58,29 @@ typedef enum agx_family {
 /* The three DynamicImage variants the reference's tests, benches and detect_kornia feed the
  * path (src/detector.rs:409,507,478-503): ImageLuma8, ImageLuma16, ImageRgb8 (HWC) -- their luma
  * conversion (image crate to_luma32f) is fused into the blur kernel -- and, for every other
- * variant (La8, Rgba8, Rgb16, Rgba16, Rgb32F ...), the caller's own img.to_luma32f() plane. */
+ * variant, the caller's own img.to_luma32f() plane (AGX_LF32).
+ * AGX_LA8 .. AGX_RGBA16: the other integer variants (ImageLumaA8, ImageRgba8, ImageLumaA16, ImageRgb16, ImageRgba16) and the
+ * layouts GPU producers hand over (BGR / BGRA of OpenCV-style decoders, channel-first planes of tensor image decoders).  A
+ * front-end kernel writes the frame's integer luma plane -- alpha is ignored; colour is (2126 R + 7152 G + 722 B) / 10000 in
+ * unsigned 32-bit arithmetic, the image crate's to_luma8 (8-bit) / its 16-bit counterpart -- and the L8 / L16 chain runs on
+ * that plane: to_luma32f of an integer colour image is that integer luma / 255 (/ 65535).  to_luma8 of the 16-bit ones is
+ * (luma16 + 128) / 257, as for AGX_L16.  Every entry point that takes a format takes them, batches and single frames alike.
+ * The f32 colour variants (Rgb32F, Rgba32F) stay with agx_detect_planes: nothing in this project records their arithmetic. */
 typedef enum agx_format {
     AGX_L8 = 0,   /* 1 byte / pixel                                    */
     AGX_L16 = 1,  /* 2 bytes / pixel, native endian                    */
     AGX_RGB8 = 2, /* 3 bytes / pixel, interleaved R,G,B (kornia Image<u8,3>) */
-    AGX_LF32 = 3  /* 4 bytes / pixel: row-major f32 luma in [0,1] = DynamicImage::to_luma32f
+    AGX_LF32 = 3, /* 4 bytes / pixel: row-major f32 luma in [0,1] = DynamicImage::to_luma32f
                      (src/detector.rs:409) as the caller computed it; taken as is */
+    AGX_LA8 = 4,   /* 2 bytes / pixel: L,A                              */
+    AGX_RGBA8 = 5, /* 4 bytes / pixel: R,G,B,A                          */
+    AGX_BGR8 = 6,  /* 3 bytes / pixel: B,G,R                            */
+    AGX_BGRA8 = 7, /* 4 bytes / pixel: B,G,R,A                          */
+    AGX_RGB8P = 8, /* 1 byte / pixel in three planes R,G,B: plane c of a frame starts c * height * row_stride_bytes behind
+                      the frame's start (a frame spans 3 * height rows; channel-first [N,3,H,W] tensors) */
+    AGX_LA16 = 9,  /* 4 bytes / pixel: L,A as u16; the 16-bit layouts are native endian and 2-byte aligned, as AGX_L16 */
+    AGX_RGB16 = 10, /* 6 bytes / pixel: R,G,B as u16                    */
+    AGX_RGBA16 = 11 /* 8 bytes / pixel: R,G,B,A as u16                  */
 } agx_format;
 
 /* detector::DetectorParams -- src/detector.rs:25-41 */
@@ -258,7 +274,7 @@ int agx_host_parallelism(void);
 int agx_debug_cgroup_cpu_quota(const char *cgroup_root, const char *proc_self_cgroup);
 
 /* TagDetector::detect (src/detector.rs:505-540) over a batch of equally sized frames in HOST memory
- * (frame i at frames + i*frame_stride_bytes; formats AGX_L8 / AGX_L16 / AGX_RGB8).  With the device tail (option
+ * (frame i at frames + i*frame_stride_bytes; every agx_format but AGX_LF32).  With the device tail (option
  * "device_tail", the default where available) the saddle chain and the board search + decode of a chunk of up to 1024
  * frames run on the device while n_threads host threads (0 = agx_host_parallelism(); the pool lives as long as the
  * detector) upload the next chunk and take the frames the kernel hands back.  With the host tail the saddle
@@ -273,8 +289,8 @@ int agx_detect_batch(agx_detector *det, const void *frames, const void *d_frames
                      uint32_t cap_per_frame, uint32_t *counts, int *frame_status, int n_threads);
 
 /* detect (src/detector.rs:505-540) over a batch resident in DEVICE memory; layout and formats as
- * agx_saddles_batch_enqueue (AGX_L8 / AGX_L16 / AGX_RGB8; AGX_LF32 is AGX_ERR_FORMAT).  Enqueues the chain, to_luma8 (non-L8,
- * on the device) and the device tail on the detector's stream and returns without waiting; the frames must stay in place until
+ * agx_saddles_batch_enqueue (every agx_format but AGX_LF32, which is AGX_ERR_FORMAT).  Enqueues the chain, to_luma8 (non-L8,
+ * on the device; for AGX_LA8 .. AGX_RGB8P the front-end kernel's plane is that plane) and the device tail on the detector's stream and returns without waiting; the frames must stay in place until
  * agx_detect_batch_fetch has returned.  The device tail runs where option "device_tail" is -1 or 1 and this process may use it
  * (no batch-size rule); with 0, or where it is refused, the fetch runs the host tail on every frame from the compact saddle lists
  * and the u8 luma planes copied down.  Same tags, counts and statuses as agx_detect_batch on the same pixels, either way.
@@ -350,7 +366,7 @@ int agx_detect_tail_threads(int family, const agx_params *params, const agx_sadd
                             const uint8_t *luma8, int width, int height, size_t row_stride_bytes, agx_tag *out,
                             uint32_t cap, uint32_t *n_out, int n_threads);
 
-/* to_luma8 (src/detector.rs:507) of a host image into a tightly packed host plane. */
+/* to_luma8 (src/detector.rs:507) of a host image (any agx_format but AGX_LF32) into a tightly packed host plane. */
 int agx_luma8(const void *pixels, int width, int height, size_t row_stride_bytes, int format,
               uint8_t *out);
 
@@ -389,8 +405,8 @@ enum { AGX_DBG_BLUR = 0, AGX_DBG_RESP = 1, AGX_DBG_MIN = 2, AGX_DBG_CENTERS = 3,
                                offset from the payload start (int32), device address of buffer 0 (lo, hi: for the
                                check of the check).  Buffers = the chain's workspace, then the staging buffer, the luma
                                planes and the device tail's code list, tag rows and frame table (mapped pinned host memory), then
-                               agx_detect_batch_enqueue_to's device-memory tag rows and frame table and agx_detect_batch_fetch's
-                               pinned luma planes, as far as they exist.  Needs no enqueued batch.  Guard bytes exist only in handles created with
+                               agx_detect_batch_enqueue_to's device-memory tag rows and frame table, agx_detect_batch_fetch's
+                               pinned luma planes and the front-end kernel's luma plane (AGX_LA8 .. AGX_RGBA16), as far as they exist.  Needs no enqueued batch.  Guard bytes exist only in handles created with
                                AGX_REDZONE_BYTES=<n> in the environment (memory-safety tests of the kernels) */
        AGX_DBG_TAIL_TABLE_ADDR = 11 /* 2 x uint64: host address and payload bytes of the device tail's frame table (the check
                                        of the check for a buffer in mapped host memory).  Needs no enqueued batch */ };
