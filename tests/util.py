@@ -50,11 +50,11 @@ def check_saddles(gpu, ref, what=""):
             assert np.max(np.abs(gpu[f] - ref[f])) <= ANGLE_TOL_DEG, (what, f)
 
 
-def check_frame(det, O, img, frame=0, what="", params=None):
-    """Compare every intermediate product of `frame` of the detector's last batch with the oracle:
-    blur plane, the response recomputed from it (separate kernel), per-frame min, cluster table,
-    unfiltered refine output -- and, when the detector runs with store_response, the response
-    the blur kernel itself evaluated in registers."""
+def check_planes_and_tables(det, O, img, frame=0, what="", params=None):
+    """Planes and integer tables of `frame` of the detector's last batch against the oracle: blur plane, the response
+    recomputed from it (separate kernel), per-frame min, cluster count, first pixels and sizes, no overflow flag -- and, when
+    the detector runs with store_response, the response the blur kernel itself evaluated in registers.
+    -> (oracle saddles, oracle debug products, the detector's cluster table)."""
     h, w = img.shape[:2]
     ref, d = O.refined_saddle_points(img, params=params, debug=True)
     assert bits_equal(det.debug_fetch(frame, "blur", (h, w)), d["blur"]), what + ": blur plane"
@@ -66,12 +66,29 @@ def check_frame(det, O, img, frame=0, what="", params=None):
     assert len(c) == len(d["centers"]), what + ": cluster count %d vs %d" % (len(c), len(d["centers"]))
     assert np.array_equal(c["first_index"], d["first_index"]), what + ": cluster first pixels"
     assert np.array_equal(c["size"], d["sizes"]), what + ": cluster sizes"
-    assert bits_equal(c["cx"], d["centers"][:, 0]) and bits_equal(c["cy"], d["centers"][:, 1]), what + ": centroids"
+    flags = det.debug_fetch(frame, "counters")["flags"]
+    assert not (flags & 7), what + ": overflow flags %d" % flags
+    return ref, d, c
+
+
+def check_centroids(c, d, what="", rows=None):
+    """Centroids of the detector's cluster table c against the oracle's, bit for bit (rows: only these clusters)."""
+    rows = slice(None) if rows is None else rows
+    assert bits_equal(c["cx"][rows], d["centers"][rows, 0]) and bits_equal(c["cy"][rows], d["centers"][rows, 1]), what + ": centroids"
+
+
+def check_frame(det, O, img, frame=0, what="", params=None):
+    """Compare every intermediate product of `frame` of the detector's last batch with the oracle:
+    blur plane, the response recomputed from it (separate kernel), per-frame min, cluster table,
+    unfiltered refine output -- and, when the detector runs with store_response, the response
+    the blur kernel itself evaluated in registers."""
+    h, w = img.shape[:2]
+    ref, d, c = check_planes_and_tables(det, O, img, frame, what, params)
+    check_centroids(c, d, what)
     check_saddles(det.debug_fetch(frame, "refined"), d["refined"], what + " (unfiltered)")
     # informational flags: AGX_FRAME_CENTROID_INEXACT (8) only where a coordinate sum can reach 2^24 (a cluster
     # refined twice -- a race between k_refine's workgroups that round 2 fixed -- used to raise it spuriously)
     flags = det.debug_fetch(frame, "counters")["flags"]
-    assert not (flags & 7), what + ": overflow flags %d" % flags
     if len(d["sizes"]) == 0 or float(d["sizes"].max()) * max(h, w) < 2.0 ** 24:
         assert not (flags & 8), what + ": AGX_FRAME_CENTROID_INEXACT set without cause"
     return ref
