@@ -117,8 +117,8 @@ private:
     bool stop_ = false, failed_ = false;
 };
 
-void destroy_worker_pool(void *p) { delete static_cast<WorkerPool *>(p); }
-void *create_worker_pool(int n_threads) { return new WorkerPool(n_threads); }
+void destroy_worker_pool(WorkerPool *p) { delete p; }
+WorkerPool *create_worker_pool(int n_threads) { return new WorkerPool(n_threads); }
 
 // Workers of one frame's board search (option "tail_threads"): n - 1 pool threads plus the caller.
 class PoolTailWorkers : public TailWorkers {
@@ -146,6 +146,179 @@ private:
 };
 TailWorkers *create_tail_workers(int n_threads) { return n_threads > 1 ? new PoolTailWorkers(std::min(n_threads, 64)) : nullptr; }
 void destroy_tail_workers(TailWorkers *w) { delete w; }
+
+// ---- what agx_detect_batch and the enqueue / fetch pair need of the handle beyond its fields -----------------------------------
+// The detector's worker pool: created on first use, replaced when n_threads changes (throws where threads cannot be created:
+// the entry points catch)
+static WorkerPool *worker_pool(agx_detector *det, int n_threads)
+{
+    if (n_threads < 1) return nullptr;
+    if (det->pool && det->pool_threads != n_threads) {
+        destroy_worker_pool(det->pool);
+        det->pool = nullptr;
+    }
+    if (!det->pool) {
+        det->pool_threads = 0;
+        det->pool = create_worker_pool(n_threads);
+        det->pool_threads = n_threads;
+    }
+    return det->pool;
+}
+// The upload streams, one per staging slot (created on first use, all of them or none: a failure half way destroys what
+// exists, so that a later call starts over instead of finding a half-initialised set); nullptr on failure
+static const hipStream_t *upload_streams(agx_detector *det)
+{
+    if (!det->upload_streams_ready) {
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < AGX_UPLOAD_STREAMS && e == hipSuccess; ++i)
+            e = hipStreamCreateWithFlags(&det->upload_streams[i], hipStreamNonBlocking);
+        if (e != hipSuccess) {
+            for (int i = 0; i < AGX_UPLOAD_STREAMS; ++i) {
+                if (det->upload_streams[i]) (void)hipStreamDestroy(det->upload_streams[i]);
+                det->upload_streams[i] = nullptr;
+            }
+            return nullptr;
+        }
+        det->upload_streams_ready = true;
+    }
+    return det->upload_streams;
+}
+// u8 luma of a chunk of L16 / colour frames (device pointers), computed on the device behind whatever is on the detector's
+// stream: *d_out = where it is on the device (the device tail reads it there) and, with h_out, copied into pinned host memory:
+// [n_frames][H][W] at *h_out (valid after the stream has been waited for -- the chunk's fetch does).  The staging is a ring
+// of n_slots chunks of chunk_capacity_frames; the caller reuses a slot when the host tails that read it are done.
+static int chunk_luma8(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride, size_t frame_stride,
+                       int format, int slot, int n_slots, size_t chunk_capacity_frames, const uint8_t **h_out, const uint8_t **d_out)
+{
+    const size_t plane = (size_t)width * (size_t)height, one = plane * chunk_capacity_frames;
+    if (slot < 0 || slot >= n_slots) return AGX_ERR_ARG;
+    // a layout of the front-end kernel whose plane the chain of these very frames has just read (the batch enqueued last):
+    // 8-bit: that plane IS their to_luma8; 16-bit: k_luma8 narrows it (2 bytes per pixel to read instead of the frames' 4 .. 8)
+    const bool same_batch = format_front(format) && det->enqueued && det->front_format == format && det->front_src == d_frames &&
+                            det->front_frames == n_frames;
+    const bool front = same_batch && !format_16bit(format), front16 = same_batch && format_16bit(format);
+    uint8_t *d_front = det->side[SB_FRONT].ptr<uint8_t>();
+    if (front && !h_out) {
+        if (d_out) *d_out = d_front;
+        return AGX_OK;
+    }
+    if (!side_ensure_pair(det, SB_LUMA_D, (size_t)n_slots * one, 0, SB_LUMA_H, (size_t)n_slots * one, 1)) return AGX_ERR_HIP;
+    uint8_t *d = det->side[SB_LUMA_D].ptr<uint8_t>() + (size_t)slot * one, *h = det->side[SB_LUMA_H].ptr<uint8_t>() + (size_t)slot * one;
+    if (front) d = d_front;
+    else if (front16) {
+        if (launch_luma8(d_front, (size_t)width * 2, plane * 2, n_frames, AGX_L16, d, width, height, det->stream) != 0) return AGX_ERR_HIP;
+    } else if (launch_luma8(d_frames, row_stride, frame_stride, n_frames, format, d, width, height, det->stream) != 0) return AGX_ERR_HIP;
+    if (d_out) *d_out = d;
+    if (!h_out) return AGX_OK;
+    if (hipMemcpyAsync(h, d, plane * (size_t)n_frames, hipMemcpyDeviceToHost, det->stream) != hipSuccess) return AGX_ERR_HIP;
+    *h_out = h;
+    return AGX_OK;
+}
+// Option "device_tail": the board search + decode of the batch that was just enqueued, behind it on the detector's stream.
+// The device evaluates angle_degree's atan2f by glibc's routine (libm_f32.h): offered only where this process's atan2f IS that
+// routine -- checked once per process on 2^20 operand pairs (more in tests/test_abi_cpu.py)
+uint64_t libm_check_once()
+{
+    // (AGX_DEBUG_LIBM_MISMATCH=1: tests of the refusal path pretend that one input differs)
+    static const uint64_t mismatches = libm_atan2f_mismatches(1u << 20, 1) + (uint64_t)(tuning_env("AGX_DEBUG_LIBM_MISMATCH", 0) != 0);
+    return mismatches;
+}
+// 0: the host tail; 1: the device tail (asked for); 2: the device tail is available and the call may choose by its size
+static int device_tail_mode(const agx_detector *det)
+{
+    if (det->device_tail < 0) return libm_check_once() == 0 ? 2 : 0;
+    return det->device_tail;
+}
+static void set_tail_stats(agx_detector *det, int frames, int fallbacks, int uncertain)
+{
+    det->last_tail_frames = frames;
+    det->last_tail_fallbacks = fallbacks;
+    det->last_tail_uncertain = uncertain;
+}
+// One-time set-up of the device tail on this handle's device: the family's code list in device memory and the kernel's
+// attributes (155 KB of LDS).  All or nothing: a failure leaves nothing behind, and a later call starts over.
+static int tail_prepare(agx_detector *det)
+{
+    if (det->tail_ready) return AGX_OK;
+    if (hipSetDevice(det->device) != hipSuccess) return AGX_ERR_HIP;  // (the kernel's attributes are set on the current device)
+    const size_t bytes = (size_t)det->fam.n_codes * sizeof(uint64_t);
+    void *d_codes = side_ensure(det, SB_CODES, bytes, 0);
+    if (!d_codes || hipMemcpy(d_codes, det->fam.codes, bytes, hipMemcpyHostToDevice) != hipSuccess || init_tail_kernels() != 0) {
+        side_free(det, SB_CODES);
+        return AGX_ERR_HIP;
+    }
+    det->tail_ready = true;
+    return AGX_OK;
+}
+// d_luma = the frames' u8 luma in device memory (L8 frames: the frames themselves).  The results: tags[f * stride ..] (stride
+// = the pair's tag capacity, >= this call's tag_cap), table[4 f] = count, table[4 f + 1] = TAIL_* status (+ 2: the frame's 100 MHz
+// ticks, + 3: saddles | seeds << 16) -- in mapped pinned host memory (fetch_tail waits for them) or, to_device
+// (agx_detect_batch_enqueue_to), in a pair of device buffers that publish_tags and the fetch read.  Either pair grows to the
+// largest frame count and the largest capacity seen.
+static int enqueue_tail(agx_detector *det, const void *d_luma, size_t luma_row_stride, size_t luma_frame_stride, uint32_t tag_cap, bool to_device)
+{
+    if (!det->enqueued || det->external_out) return AGX_ERR_STATE;
+    const ChainArgs &a = det->args;
+    if (tag_cap == 0 || luma_row_stride > 0x7fffffffu) return AGX_ERR_ARG;
+    if (tag_cap > 128u) tag_cap = 128u;  // (the kernel's own list of distinct ids; frames beyond it take the host tail)
+    if (const int rc = tail_prepare(det)) return rc;
+    size_t &frames = to_device ? det->dtail_frames : det->tail_frames;
+    uint32_t &stride = to_device ? det->dtail_tag_cap : det->tail_tag_cap;
+    const int sb_tags = to_device ? SB_DTAGS : SB_TAGS, sb_table = to_device ? SB_DTABLE : SB_TAIL_TABLE;
+    const SideBuf &tags = det->side[sb_tags], &table = det->side[sb_table];
+    if ((size_t)a.n_frames > frames || tag_cap > stride) {
+        const size_t F = std::max((size_t)a.n_frames, frames);
+        const uint32_t cap = std::max(tag_cap, stride);
+        frames = 0;  // (nothing usable until both tables exist)
+        stride = 0;
+        const int kind = to_device ? 0 : 2;
+        if (!side_ensure_pair(det, sb_tags, F * cap * sizeof(agx_tag), kind, sb_table, F * 4 * sizeof(uint32_t), kind)) return AGX_ERR_HIP;
+        frames = F;
+        stride = cap;
+    }
+    TailArgs t{};
+    t.saddles = a.out;
+    t.ctr = a.ctr;
+    t.n_frames = a.n_frames;
+    t.luma = static_cast<const uint8_t *>(d_luma);
+    t.luma_frame_stride = (long long)luma_frame_stride;
+    t.luma_row_stride = (int)luma_row_stride;
+    t.W = a.W;
+    t.H = a.H;
+    t.edge = det->fam.edge;
+    t.border = det->fam.border;
+    t.hamming = det->fam.hamming;
+    t.n_codes = det->fam.n_codes;
+    t.codes = det->side[SB_CODES].ptr<uint64_t>();
+    t.max_boards = det->params.max_num_of_boards;
+    t.tags = to_device ? tags.ptr<agx_tag>() : tags.dev<agx_tag>();
+    t.table = to_device ? table.ptr<uint32_t>() : table.dev<uint32_t>();
+    t.tag_cap = tag_cap;  // this call's: a frame with more tags is handed back (TAIL_CAPACITY), whatever the table could hold
+    t.tag_stride = stride;
+    t.debug_band = (float)det->tail_debug_band_mdeg * 1e-3f;
+    t.debug = tuning_env("AGX_TAIL_DEBUG", 0);
+    t.debug_frame = tuning_env("AGX_TAIL_DEBUG_FRAME", 0);
+    if (launch_board_tail(t, det->stream) != 0) return AGX_ERR_HIP;
+    return AGX_OK;
+}
+// agx_detect_batch_enqueue_to: the device tail's results of the batch (device buffers) into the caller's layout, behind the
+// tail on the detector's stream (tail_kernels.hip, k_publish_tags)
+static int publish_tags(agx_detector *det, uint32_t cap_per_frame, agx_tag *d_tags, uint32_t *d_counts, int *d_status)
+{
+    if (!det->enqueued || !det->dtail_frames) return AGX_ERR_STATE;
+    const int e = launch_publish_tags(det->side[SB_DTABLE].ptr<uint32_t>(), det->side[SB_DTAGS].ptr<agx_tag>(), det->dtail_tag_cap, det->args.ctr,
+                                      det->args.n_frames, cap_per_frame, d_tags, d_counts, d_status, det->stream);
+    return e == 0 ? AGX_OK : AGX_ERR_HIP;
+}
+// Waits for the device; then the tail's results in mapped pinned host memory, rows *tag_stride apart
+static int fetch_tail(agx_detector *det, const agx_tag **tags, const uint32_t **table, uint32_t *tag_stride)
+{
+    if (hipStreamSynchronize(det->stream) != hipSuccess) return AGX_ERR_HIP;
+    *tags = det->side[SB_TAGS].ptr<agx_tag>();
+    *table = det->side[SB_TAIL_TABLE].ptr<uint32_t>();
+    *tag_stride = det->tail_tag_cap;
+    return AGX_OK;
+}
 
 }  // namespace agx
 
@@ -268,9 +441,9 @@ static int detect_batch_device_tail(agx_detector *det, const void *frames, const
                                     size_t row_stride_bytes, size_t frame_stride_bytes, int format, agx_tag *out,
                                     uint32_t cap_per_frame, uint32_t *counts, int *frame_status, WorkerPool *pool)
 {
-    const FamilyInfo *fam = static_cast<const FamilyInfo *>(agx_internal_family(det));
-    const int max_boards = agx_internal_max_boards(det);
-    const int device = agx_internal_device(det);
+    const FamilyInfo *fam = &det->fam;
+    const int max_boards = det->params.max_num_of_boards;
+    const int device = det->device;
     constexpr int S = AGX_UPLOAD_STREAMS;
     // A frame's search occupies a workgroup of eight waves for two to five milliseconds (frames whose first seed does not
     // find the whole board cost twice the others), one workgroup per CU: a launch takes what its slowest frame takes, and
@@ -280,11 +453,11 @@ static int detect_batch_device_tail(agx_detector *det, const void *frames, const
     const int n_chunks = (n_frames + chunk - 1) / chunk;
     const size_t chunk_bytes = (size_t)chunk * frame_stride_bytes;
     uint8_t *d_stage = nullptr;
-    hipStream_t up[S] = {nullptr, nullptr, nullptr};
+    const hipStream_t *up = nullptr;
     if (!d_frames) {
-        d_stage = static_cast<uint8_t *>(agx_internal_stage(det, (size_t)std::min(S, n_chunks) * chunk_bytes));
-        if (!d_stage) return AGX_ERR_HIP;
-        if (agx_internal_upload_streams(det, (void **)up) != 0) return AGX_ERR_HIP;
+        d_stage = static_cast<uint8_t *>(side_ensure(det, SB_STAGE, (size_t)std::min(S, n_chunks) * chunk_bytes, 0));
+        up = upload_streams(det);
+        if (!d_stage || !up) return AGX_ERR_HIP;
     }
     std::mutex m;
     std::condition_variable cv;
@@ -365,7 +538,7 @@ static int detect_batch_device_tail(agx_detector *det, const void *frames, const
     parts_left.assign((size_t)n_chunks, P);
     chunk_failed.assign((size_t)n_chunks, 0);
     if (!d_frames) release_chunks(std::min(S, n_chunks));
-    const int tail_debug = agx_internal_tail_debug(det);  // AGX_TAIL_DEBUG as the handle read it when it was created
+    const int tail_debug = tuning_env("AGX_TAIL_DEBUG", 0);  // (as read when the handle was created)
     std::vector<uint32_t> ns, offs;
     std::vector<int> fst;
     for (int ci = 0; ci < n_chunks; ++ci) {
@@ -386,18 +559,17 @@ static int detect_batch_device_tail(agx_detector *det, const void *frames, const
         const uint8_t *d_luma = static_cast<const uint8_t *>(d_chunk);  // detector.rs:507: L8 frames are their own u8 luma
         size_t luma_row = row_stride_bytes, luma_frame = frame_stride_bytes;
         if (format != AGX_L8) {
-            rc = agx_internal_chunk_luma8(det, d_chunk, nf, width, height, row_stride_bytes, frame_stride_bytes, format, 0, 1, (size_t)chunk,
-                                          nullptr, &d_luma);
+            rc = chunk_luma8(det, d_chunk, nf, width, height, row_stride_bytes, frame_stride_bytes, format, 0, 1, (size_t)chunk, nullptr, &d_luma);
             if (rc) break;
             luma_row = (size_t)width;
             luma_frame = (size_t)width * (size_t)height;
         }
-        rc = agx_internal_enqueue_tail(det, d_luma, luma_row, luma_frame, std::max(cap_per_frame, 1u), 0);
+        rc = enqueue_tail(det, d_luma, luma_row, luma_frame, std::max(cap_per_frame, 1u), false);
         if (rc) break;
         const agx_tag *tags = nullptr;
         const uint32_t *table = nullptr;
         uint32_t tag_cap = 0;
-        rc = agx_internal_fetch_tail(det, &tags, &table, &tag_cap);  // waits for the device
+        rc = fetch_tail(det, &tags, &table, &tag_cap);  // waits for the device
         if (rc) break;
         bool any_back = false;
         if (tail_debug) {
@@ -445,7 +617,7 @@ static int detect_batch_device_tail(agx_detector *det, const void *frames, const
             offs.resize((size_t)nf);
             fst.resize((size_t)nf);
             const agx_saddle *records = nullptr;
-            rc = agx_internal_fetch_compact(det, &records, ns.data(), offs.data(), fst.data());
+            rc = fetch_compact(det, &records, ns.data(), offs.data(), fst.data());
             pending_batch = false;
             if (rc) break;
             for (int f = 0; f < nf; ++f) {
@@ -493,7 +665,7 @@ static int detect_batch_device_tail(agx_detector *det, const void *frames, const
                 });
             }
         } else {
-            agx_internal_abandon_batch(det);  // (the stream is idle: the batch is done with)
+            abandon_batch(det);  // (the stream is idle: the batch is done with)
             pending_batch = false;
         }
         // chain, luma and tail have read the staging slot: the chunk S ahead may go up
@@ -507,8 +679,8 @@ static int detect_batch_device_tail(agx_detector *det, const void *frames, const
         stop_uploads = true;
     }
     (void)pool->wait();
-    if (pending_batch) agx_internal_abandon_batch(det);
-    agx_internal_tail_stats(det, n_frames, n_fallback, n_uncertain);
+    if (pending_batch) abandon_batch(det);
+    set_tail_stats(det, n_frames, n_fallback, n_uncertain);
     if (rc) return rc;
     if (nomem.load()) return AGX_ERR_NOMEM;
     return first_bad.load();
@@ -531,27 +703,27 @@ static int detect_batch_impl(agx_detector *det, const void *frames, const void *
     // quota are not merely idle: the quota is spent sooner and EVERY thread of the process, the one driving the device
     // included, is frozen for the rest of the scheduler period -- profiles/r5_host_cpu_quota_and_tail_scaling.txt)
     if (n_threads <= 0) n_threads = agx_host_parallelism();
-    WorkerPool *pool = static_cast<WorkerPool *>(agx_internal_pool(det, n_threads));
+    WorkerPool *pool = worker_pool(det, n_threads);
     if (!pool) return AGX_ERR_ARG;
-    const FamilyInfo *fam = static_cast<const FamilyInfo *>(agx_internal_family(det));
-    const int max_boards = agx_internal_max_boards(det);
-    if (hipSetDevice(agx_internal_device(det)) != hipSuccess) return AGX_ERR_HIP;
-    const int device = agx_internal_device(det);
+    const FamilyInfo *fam = &det->fam;
+    const int max_boards = det->params.max_num_of_boards;
+    if (hipSetDevice(det->device) != hipSuccess) return AGX_ERR_HIP;
+    const int device = det->device;
     // The device tail costs a launch whose length is its slowest frame's (1.5 .. 3.5 ms) whatever the batch; the host tail costs
     // ~0.9 ms per frame and thread.  Measured on 16 threads the two meet at ~60 frames (1: 1.0 / 1.7 ms, 16: 2.1 / 3.6,
     // 48: 4.3 / 4.4, 64: 4.6 / 4.7, 96: 6.8 / 5.3, 128: 8.9 / 6.0, 256: 15.7 / 8.5): left to choose, a call of fewer than four
     // frames per host thread keeps the host tail.
-    const int tail_mode = agx_internal_device_tail(det);
+    const int tail_mode = device_tail_mode(det);
     bool on_device = tail_mode == 1 || (tail_mode == 2 && n_frames >= 4 * pool->size());
     if (on_device) {  // the one-time set-up (code list, 155 KB of LDS for the kernel): asked for -> its failure is the call's;
-        const int prc = agx_internal_tail_prepare(det);  // left to choose -> the host tail, which needs nothing from the device
+        const int prc = tail_prepare(det);  // left to choose -> the host tail, which needs nothing from the device
         if (prc && tail_mode == 1) return prc;
         if (prc) on_device = false;
     }
     if (on_device)
         return detect_batch_device_tail(det, frames, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, out,
                                         cap_per_frame, counts, frame_status, pool);
-    agx_internal_tail_stats(det, 0, 0, 0);  // ("last_device_tail_frames" 0: this call's tails run on the host)
+    set_tail_stats(det, 0, 0, 0);  // ("last_device_tail_frames" 0: this call's tails run on the host)
 
     // Chunks of about one frame per worker (8 .. 64): the chain of a chunk takes 0.1 ms on the device, a frame's board
     // search about a millisecond on a host thread, so small chunks cost nothing and the workers start after the first 8 .. 64 frames
@@ -567,11 +739,11 @@ static int detect_batch_impl(agx_detector *det, const void *frames, const void *
     const int n_chunks = (n_frames + chunk - 1) / chunk;
     const size_t chunk_bytes = (size_t)chunk * frame_stride_bytes;
     uint8_t *d_stage = nullptr;
-    hipStream_t up[S] = {nullptr, nullptr, nullptr};
+    const hipStream_t *up = nullptr;
     if (!d_frames) {
-        d_stage = static_cast<uint8_t *>(agx_internal_stage(det, (size_t)std::min(S, n_chunks) * chunk_bytes));
-        if (!d_stage) return AGX_ERR_HIP;
-        if (agx_internal_upload_streams(det, (void **)up) != 0) return AGX_ERR_HIP;
+        d_stage = static_cast<uint8_t *>(side_ensure(det, SB_STAGE, (size_t)std::min(S, n_chunks) * chunk_bytes, 0));
+        up = upload_streams(det);
+        if (!d_stage || !up) return AGX_ERR_HIP;
     }
     struct Slot {  // one chunk's results while its tails run
         std::vector<agx_saddle> saddles;  // compact
@@ -624,8 +796,7 @@ static int detect_batch_impl(agx_detector *det, const void *frames, const void *
         // the device behind the chain (the frames are there) and come back with the saddles
         const uint8_t *h_luma = nullptr;
         if (format != AGX_L8) {
-            rc = agx_internal_chunk_luma8(det, d_chunk, nf, width, height, row_stride_bytes, frame_stride_bytes, format, r, R,
-                                          (size_t)chunk, &h_luma, nullptr);
+            rc = chunk_luma8(det, d_chunk, nf, width, height, row_stride_bytes, frame_stride_bytes, format, r, R, (size_t)chunk, &h_luma, nullptr);
             if (rc) break;
         }
         Slot &sl = slots[(size_t)r];
@@ -633,7 +804,7 @@ static int detect_batch_impl(agx_detector *det, const void *frames, const void *
         sl.offs.resize((size_t)nf);
         sl.fst.resize((size_t)nf);
         const agx_saddle *records = nullptr;
-        rc = agx_internal_fetch_compact(det, &records, sl.ns.data(), sl.offs.data(), sl.fst.data());  // waits for the device
+        rc = fetch_compact(det, &records, sl.ns.data(), sl.offs.data(), sl.fst.data());  // waits for the device
         pending_batch = false;
         if (rc) break;
         // chain and luma have read the staging slot: the chunk S ahead may go up (ahead of every queued tail)
@@ -702,7 +873,7 @@ static int detect_batch_impl(agx_detector *det, const void *frames, const void *
         rc = AGX_ERR_NOMEM;  // host memory exhausted on this thread
     }
     (void)pool->wait();  // every tail and every upload still queued (an upload may be reading the caller's frames)
-    if (pending_batch) agx_internal_abandon_batch(det);  // an error between enqueue and fetch: no stale batch is left to be fetched later
+    if (pending_batch) abandon_batch(det);  // an error between enqueue and fetch: no stale batch is left to be fetched later
     if (rc) return rc;
     if (nomem.load()) return AGX_ERR_NOMEM;
     return first_bad.load();
@@ -719,10 +890,10 @@ int agx::detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_fram
 {
     // option "device_tail" -1 (default) or 1: the device tail wherever this process may use it (no batch-size rule: with the frames
     // on the device there is no upload for the host tail to hide behind); 0, or a tail this process may not use: the host tail
-    const int tail_mode = agx_internal_device_tail(det);
+    const int tail_mode = device_tail_mode(det);
     bool on_device = tail_mode != 0;
     if (on_device) {
-        const int prc = agx_internal_tail_prepare(det);
+        const int prc = tail_prepare(det);
         if (prc && tail_mode == 1) return prc;
         if (prc) on_device = false;
     }
@@ -731,27 +902,25 @@ int agx::detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_fram
     const uint8_t *d_luma = static_cast<const uint8_t *>(d_frames);  // detector.rs:507: L8 frames are their own u8 luma
     size_t luma_row = row_stride_bytes, luma_frame = frame_stride_bytes;
     if (format != AGX_L8) {
-        rc = agx_internal_chunk_luma8(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, 0, 1,
-                                      (size_t)n_frames, nullptr, &d_luma);
+        rc = chunk_luma8(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, 0, 1, (size_t)n_frames, nullptr, &d_luma);
         luma_row = (size_t)width;
         luma_frame = (size_t)width * (size_t)height;
     }
-    if (!rc && on_device) rc = agx_internal_enqueue_tail(det, d_luma, luma_row, luma_frame, std::max(cap_per_frame, 1u), to_device ? 1 : 0);
+    if (!rc && on_device) rc = enqueue_tail(det, d_luma, luma_row, luma_frame, std::max(cap_per_frame, 1u), to_device);
     if (!rc && to_device) {
         if (on_device) {
-            rc = agx_internal_publish_tags(det, cap_per_frame, d_tags, d_counts, d_status);
+            rc = publish_tags(det, cap_per_frame, d_tags, d_counts, d_status);
         } else {  // every frame is the fetch's: until then count 0, AGX_ERR_STATE
-            hipStream_t st = static_cast<hipStream_t>(agx_internal_stream(det));
-            if (hipMemsetD32Async(d_counts, 0, (size_t)n_frames, st) != hipSuccess ||
-                hipMemsetD32Async(d_status, AGX_ERR_STATE, (size_t)n_frames, st) != hipSuccess)
+            if (hipMemsetD32Async(d_counts, 0, (size_t)n_frames, det->stream) != hipSuccess ||
+                hipMemsetD32Async(d_status, AGX_ERR_STATE, (size_t)n_frames, det->stream) != hipSuccess)
                 rc = AGX_ERR_HIP;
         }
     }
     if (rc) {
-        agx_internal_abandon_batch(det);  // (nothing half-enqueued is left to be fetched)
+        abandon_batch(det);  // (nothing half-enqueued is left to be fetched)
         return rc;
     }
-    DetectPending &p = *agx_internal_detect_pending(det);
+    DetectPending &p = det->detect;
     p.kind = to_device ? 2 : 1;
     p.device_tail = on_device;
     p.n_frames = n_frames;
@@ -769,7 +938,7 @@ int agx::detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_fram
 
 int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads)
 {
-    DetectPending &pend = *agx_internal_detect_pending(det);
+    DetectPending &pend = det->detect;
     const DetectPending b = pend;
     if ((b.kind == 1 && !counts) || (out && b.cap && !counts)) return AGX_ERR_ARG;  // (the batch stays in flight)
     if (b.kind == 1 && !out && b.cap) return AGX_ERR_ARG;
@@ -778,9 +947,9 @@ int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, in
     const uint32_t cap = b.cap;
     const bool to_dev = b.kind == 2;
     const size_t plane = (size_t)W * (size_t)H;
-    hipStream_t stream = static_cast<hipStream_t>(agx_internal_stream(det));
-    const FamilyInfo *fam = static_cast<const FamilyInfo *>(agx_internal_family(det));
-    const int max_boards = agx_internal_max_boards(det);
+    hipStream_t stream = det->stream;
+    const FamilyInfo *fam = &det->fam;
+    const int max_boards = det->params.max_num_of_boards;
     if (n_threads <= 0) n_threads = agx_host_parallelism();
     // every frame's result as the host knows it (the device arrays of _enqueue_to get the same), the frames the host tail takes,
     // and (_enqueue_to) their tag rows until they are copied to the caller's device arrays
@@ -796,8 +965,8 @@ int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, in
     int rc = AGX_OK, n_fallback = 0, n_uncertain = 0;
     try {
         do {
-            if (hipSetDevice(agx_internal_device(det)) != hipSuccess) { rc = AGX_ERR_HIP; break; }
-            pool = static_cast<WorkerPool *>(agx_internal_pool(det, n_threads));
+            if (hipSetDevice(det->device) != hipSuccess) { rc = AGX_ERR_HIP; break; }
+            pool = worker_pool(det, n_threads);
             if (!pool) { rc = AGX_ERR_ARG; break; }
             cnt.assign((size_t)n, 0u);
             st.assign((size_t)n, AGX_OK);
@@ -809,12 +978,11 @@ int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, in
                 std::vector<uint32_t> dtab;
                 if (to_dev) {  // the 16-byte table entry per frame, not the rows: those are in the caller's arrays already
                     dtab.resize((size_t)n * 4);
-                    if (hipMemcpyAsync(dtab.data(), agx_internal_device_tail_table(det), dtab.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                       stream) != hipSuccess ||
+                    if (hipMemcpyAsync(dtab.data(), det->side[SB_DTABLE].payload, dtab.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
                         hipStreamSynchronize(stream) != hipSuccess) { rc = AGX_ERR_HIP; break; }
                     table = dtab.data();
                 } else {
-                    rc = agx_internal_fetch_tail(det, &tags, &table, &tag_stride);  // waits for the device
+                    rc = fetch_tail(det, &tags, &table, &tag_stride);  // waits for the device
                     if (rc) break;
                 }
                 for (int f = 0; f < n; ++f) {
@@ -833,7 +1001,7 @@ int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, in
             std::vector<uint32_t> ns((size_t)n), offs((size_t)n);
             std::vector<int> fst((size_t)n);
             const agx_saddle *records = nullptr;
-            rc = agx_internal_fetch_compact(det, &records, ns.data(), offs.data(), fst.data());
+            rc = fetch_compact(det, &records, ns.data(), offs.data(), fst.data());
             if (rc) break;
             for (int f = 0; f < n; ++f) {
                 if (!back[(size_t)f]) continue;
@@ -854,7 +1022,8 @@ int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, in
             // their u8 luma, copied down a group at a time into one of two pinned slots while the previous group's tails run
             const int G = std::min(n_host, std::max(8, std::min(32, 2 * pool->size())));
             const int n_slots = n_host > G ? 2 : 1;
-            uint8_t *h_luma = agx_internal_fetch_luma(det, (size_t)n_slots * (size_t)G * plane);
+            // (pinned, guarded like every side buffer; fetch_compact has waited for the stream, so side_ensure's own wait costs nothing)
+            uint8_t *h_luma = static_cast<uint8_t *>(side_ensure(det, SB_FETCH_LUMA, (size_t)n_slots * (size_t)G * plane, 1));
             if (!h_luma) { rc = AGX_ERR_HIP; break; }
             for (int c0 = 0, ci = 0; c0 < n_host && !rc; c0 += G, ++ci) {
                 const int nc = std::min(G, n_host - c0), r = ci % n_slots;
@@ -932,8 +1101,8 @@ int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, in
             ok = hipMemcpyAsync(out, b.d_tags, (size_t)n * cap * sizeof(agx_tag), hipMemcpyDeviceToHost, stream) == hipSuccess;
         if (!ok || hipStreamSynchronize(stream) != hipSuccess) rc = AGX_ERR_HIP;
     }
-    agx_internal_abandon_batch(det);  // (waits for the stream; nothing of the batch is left to be fetched)
-    agx_internal_tail_stats(det, b.device_tail ? n : 0, n_fallback, n_uncertain);
+    abandon_batch(det);  // (waits for the stream; nothing of the batch is left to be fetched)
+    set_tail_stats(det, b.device_tail ? n : 0, n_fallback, n_uncertain);
     if (rc) {  // the call failed as a whole: no frame's result is valid (as agx_detect_batch)
         if (counts)
             for (int f = 0; f < n; ++f) counts[f] = 0;

@@ -22,150 +22,17 @@
 
 using namespace agx;
 
-namespace {
-
-const char *kKernelNames[K_COUNT] = {"k_blur_hessian", "k_verify_seeds", "k_flood_refine", "k_rare_emit", "k_sparse_frame"};
-
-struct EventPair {
-    hipEvent_t a, b;
-    int kernel;
-};
-
-}  // namespace
-
-struct agx_detector {
-    int family = AGX_T36H11;
-    FamilyInfo fam{};
-    agx_params params{};
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    RefineConsts rc{};
-    float blur_w[7]{};
-    uint32_t lim_cand = 0, lim_roots = 0, lim_out = 0;
-    int force_generic = 0;
-    int k1_rows = 0;
-    int sparse_path = 0;  // option "sparse_path": 0 = by batch size, 1 = K2 + K3 + K4 (three launches), 2 = k_sparse_frame (one)
-    bool last_sparse_frame = false;  // the last batch ran K1 + K_SPARSE
-    int last_sparse_path = 1;        // 1 three launches, 2 k_sparse_frame alone, 3 k_verify_seeds + k_sparse_frame
-    int n_cus = 0;                   // compute units of the device (hipDeviceProp_t::multiProcessorCount)
-    int dbg = 0;
-    float *d_dbg_resp = nullptr;  // lazily allocated plane for agx_debug_fetch(AGX_DBG_RESP_RECOMPUTED)
-    long long dbg_resp_plane = 0;
-    int store_resp = 0;           // option "store_response": K1's parity-test instantiation
-    float *d_resp_store = nullptr;  // [n_frames][H][W] planes it writes
-    size_t resp_store_floats = 0;
-    bool resp_stored = false;     // the last batch ran with store_response
-    int ws_W = 0, ws_H = 0;       // geometry the mask plane was last zeroed for
-
-    // workspace (device)
-    ChainArgs args{};
-    size_t cap_frames = 0;        // frames the dense planes hold
-    long long cap_plane = 0;      // pixels per frame the dense planes hold
-    uint32_t alloc_cand = 0, alloc_roots = 0, alloc_out = 0;
-    std::vector<void *> device_allocs;
-    // AGX_REDZONE_BYTES (environment, read when the handle is created; tests only): every workspace
-    // buffer gets this many guard bytes in front and behind, filled with 0xA5; agx_debug_fetch
-    // (AGX_DBG_REDZONES) reports the guard bytes that no longer hold the pattern
-    size_t redzone = 0;
-    std::vector<size_t> alloc_bytes;  // payload bytes per entry of device_allocs
-    // Buffers outside the chain's workspace (staging, luma planes, the device tail's code list and result tables): the same
-    // guard bytes around each, device memory or mapped pinned host memory; AGX_DBG_REDZONES counts them after the workspace's
-    struct SideBuf {
-        void *base = nullptr;  // start of the front guard (what hipMalloc / hipHostMalloc returned)
-        size_t bytes = 0;      // payload
-        bool host = false;     // pinned host memory (mapped when dev != nullptr)
-        void *dev = nullptr;   // device address of the payload of a mapped host buffer
-    };
-    // (SB_DTAGS .. SB_FETCH_LUMA: agx_detect_batch_enqueue_to's device tail results, agx_detect_batch_fetch's luma planes;
-    // SB_FRONT: the front-end kernel's integer luma plane of a batch in one of the layouts AGX_LA8 .. AGX_RGBA16)
-    enum { SB_STAGE, SB_LUMA_D, SB_LUMA_H, SB_CODES, SB_TAGS, SB_TAIL_TABLE, SB_DTAGS, SB_DTABLE, SB_FETCH_LUMA, SB_FRONT, SB_COUNT };
-    SideBuf side[SB_COUNT];
-    // staging for the single-frame host API
-    uint8_t *d_stage = nullptr;
-    size_t stage_bytes = 0;
-    // agx_detect on L16 / RGB8: the u8 luma of the staged frame, computed on the device
-    uint8_t *d_luma = nullptr, *h_luma = nullptr;
-    size_t luma_bytes = 0;
-    // AGX_LA8 .. AGX_RGBA16: k_front_luma's plane of the batch, tight [n][H][W] u8 / u16 -- what the chain reads instead of the
-    // frames; front_src / front_format / front_frames name the batch it holds, so that to_luma8 is derived from it instead of
-    // from the frames again (an 8-bit layout: it IS that plane).  They are valid only from batch_enqueue_impl to the next
-    // enqueue on the handle, which resets them first (format -1: none): whoever asks for the luma of a batch does so right
-    // behind that batch's enqueue, on the same stream
-    uint8_t *d_front = nullptr;
-    size_t front_bytes = 0;
-    const void *front_src = nullptr;
-    int front_format = -1, front_frames = 0;
-    // pinned host mirrors
-    FrameCounters *h_ctr = nullptr;
-    size_t h_ctr_frames = 0;
-    uint32_t *h_total = nullptr;
-    float *h_out = nullptr;
-    size_t h_out_records = 0;
-    float *d_out_internal = nullptr;  // workspace copy of args.out
-    float *h_out_dev = nullptr;       // device address of h_out (mapped pinned memory): a single frame's list is written there directly
-    bool out_in_host = false;         // last batch's compact output went straight to h_out
-    uint32_t *h_table = nullptr, *h_table_dev = nullptr;  // mapped pinned [frames + 1][4]: per frame count, offset, status, clusters (k_publish / the single frame's k_rare)
-    size_t h_table_rows = 0;
-    size_t mask_words = 0;
-    bool external_out = false;       // last batch wrote into caller-owned device memory
-
-    // two counter sets used alternately: the last kernel of a batch clears the other set, so only a
-    // batch that finds its set not known to be clear pays a memset
-    FrameCounters *d_ctr[2] = {nullptr, nullptr};
-    size_t ctr_cleared[2] = {0, 0};  // records of the set known to be zero (0 = in use / unknown)
-    int ctr_cur = 0;
-
-    bool enqueued = false;
-    int profiling = 0;  // 0 off, 1 = K1 only, 2 = every kernel
-    int prof_stride = 1;        // level 1: time the selected kernel of every prof_stride-th batch only
-    int prof_kernel = K_BLUR_HESSIAN;  // level 1: which kernel (option "profile_kernel", default the blur kernel)
-    uint64_t prof_batches = 0;  // batches enqueued while profiling
-    std::vector<EventPair> pending_events;
-    std::vector<hipEvent_t> free_events;
-    double prof_ms[K_COUNT]{};
-    uint64_t prof_launches[K_COUNT]{};
-
-    // agx_detect_batch: the next chunk's upload runs on a stream of its own under the current chunk's chain and fetch
-    hipStream_t upload_streams[AGX_UPLOAD_STREAMS] = {nullptr, nullptr, nullptr};  // agx_detect_batch: one per staging slot, all or none
-    bool upload_streams_ready = false;
-    TailWorkers *tail_workers = nullptr;  // option "tail_threads" > 1: one frame's board search on several threads
-    int tail_threads = 1;
-    void *pool = nullptr;  // agx_detect_batch: worker threads of the host tail
-    int pool_threads = 0;
-    std::vector<agx_saddle> scratch_saddles;  // host staging of agx_detect / agx_detect_planes (reused)
-
-    // option "device_tail": agx_detect_batch's board search + decode on the device (tail_kernels.hip); frames the kernel
-    // hands back (TAIL_UNCERTAIN / TAIL_CAPACITY) take the host tail
-    int device_tail = -1;  // -1: by the batch's size, where this process's atan2f is the routine the kernel restates; 0 off; 1 on
-    bool tail_ready = false;        // code list on the device and the kernel's attributes set for this device: all or nothing
-    int tail_debug_band_mdeg = 0;   // option "tail_debug_band" (tests of the hand-back path), thousandths of a degree
-    uint64_t *d_codes = nullptr;                                     // the family's code list
-    agx_tag *h_tags = nullptr, *h_tags_dev = nullptr;                // mapped pinned [tail_frames][tail_tag_cap]
-    uint32_t *h_tail_table = nullptr, *h_tail_table_dev = nullptr;   // mapped pinned [tail_frames][4]: count, status, ticks, saddles | seeds << 16
-    size_t tail_frames = 0;
-    uint32_t tail_tag_cap = 0;
-    int last_tail_frames = 0, last_tail_fallbacks = 0, last_tail_uncertain = 0;  // of the last agx_detect_batch call
-    agx_tag *d_tail_tags = nullptr;     // agx_detect_batch_enqueue_to: device [dtail_frames][dtail_tag_cap]
-    uint32_t *d_tail_table = nullptr;   //                                device [dtail_frames][4]
-    size_t dtail_frames = 0;
-    uint32_t dtail_tag_cap = 0;
-    uint8_t *h_fetch_luma = nullptr;    // agx_detect_batch_fetch: pinned luma planes of the frames the host tail takes
-    size_t fetch_luma_bytes = 0;
-    agx::DetectPending detect;          // agx_detect_batch_enqueue / _to: the batch agx_detect_batch_fetch resolves
-
-    std::string last_error;
-};
-
-namespace {
-
-thread_local std::string g_create_error;  // reason of this thread's last failed agx_detector_create (det == NULL)
-
-int fail(agx_detector *d, int status, const std::string &msg)
+int agx::fail(agx_detector *d, int status, const std::string &msg)
 {
     if (d) d->last_error = msg;
     return status;
 }
+
+namespace {
+
+const char *kKernelNames[K_COUNT] = {"k_blur_hessian", "k_verify_seeds", "k_flood_refine", "k_rare_emit", "k_sparse_frame"};
+
+thread_local std::string g_create_error;  // reason of this thread's last failed agx_detector_create (det == NULL)
 
 // Nothing unwinds across the C boundary (include/aprilgrid_amd.h, "Conventions"): every entry point runs its body through
 // agx_guard.  A failed host allocation or thread creation becomes AGX_ERR_NOMEM, anything else AGX_ERR_STATE; the message
@@ -290,20 +157,24 @@ int dev_alloc(agx_detector *d, T *&ptr, size_t count)
     return AGX_OK;
 }
 
-// A buffer outside the workspace, with the handle's guard bytes around it.  kind: 0 device, 1 pinned host, 2 pinned host
-// mapped into the device (b.dev = its device address).  The old buffer is freed first; on failure the slot is empty.
-void side_free(agx_detector *d, int which)
+}  // namespace
+
+// The side buffers (detector_internal.h): guard bytes around each, like the workspace's
+void agx::side_free(agx_detector *d, int which)
 {
-    agx_detector::SideBuf &b = d->side[which];
+    SideBuf &b = d->side[which];
     if (b.base) (void)(b.host ? hipHostFree(b.base) : hipFree(b.base));
-    b = agx_detector::SideBuf();
+    b = SideBuf();
 }
-void *side_alloc(agx_detector *d, int which, size_t bytes, int kind)
+void *agx::side_ensure(agx_detector *d, int which, size_t bytes, int kind)
 {
+    SideBuf &b = d->side[which];
+    if (b.base && b.bytes >= bytes) return b.payload;
+    const bool idle = hipSetDevice(d->device) == hipSuccess && hipStreamSynchronize(d->stream) == hipSuccess;
     side_free(d, which);
-    agx_detector::SideBuf &b = d->side[which];
+    if (!idle) return nullptr;
     const size_t rz = d->redzone, payload = std::max<size_t>(bytes, 1);
-    void *p = nullptr;
+    void *p = nullptr, *dp = nullptr;
     if (kind == 0) {
         if (hipMalloc(&p, payload + 2 * rz) != hipSuccess) return nullptr;
         if (rz && (hipMemset(p, 0xA5, rz) != hipSuccess || hipMemset((char *)p + rz + payload, 0xA5, rz) != hipSuccess)) {
@@ -316,20 +187,27 @@ void *side_alloc(agx_detector *d, int which, size_t bytes, int kind)
             std::memset(p, 0xA5, rz);
             std::memset((char *)p + rz + payload, 0xA5, rz);
         }
-        if (kind == 2) {
-            void *dp = nullptr;
-            if (hipHostGetDevicePointer(&dp, p, 0) != hipSuccess) {
-                (void)hipHostFree(p);
-                return nullptr;
-            }
-            b.dev = (char *)dp + rz;
+        if (kind == 2 && hipHostGetDevicePointer(&dp, p, 0) != hipSuccess) {
+            (void)hipHostFree(p);
+            return nullptr;
         }
     }
     b.base = p;
+    b.payload = (char *)p + rz;
+    b.mapped = dp ? (char *)dp + rz : nullptr;
     b.bytes = payload;
     b.host = kind != 0;
-    return (char *)p + rz;
+    return b.payload;
 }
+bool agx::side_ensure_pair(agx_detector *d, int a, size_t bytes_a, int kind_a, int b, size_t bytes_b, int kind_b)
+{
+    if (side_ensure(d, a, bytes_a, kind_a) && side_ensure(d, b, bytes_b, kind_b)) return true;
+    side_free(d, a);
+    side_free(d, b);
+    return false;
+}
+
+namespace {
 
 void free_workspace(agx_detector *d)
 {
@@ -583,8 +461,18 @@ int frame_status_of(const FrameCounters &c, uint32_t cap_per_frame)
     return AGX_OK;
 }
 
-bool valid_format(int f) { return format_px_bytes(f) != 0; }
-int bytes_per_px(int f) { return format_px_bytes(f); }
+// A row of the frame table (count, offset, flags, clusters) as the counter record the fetch works with; false where one of
+// the frame's lists overflowed (the full record is then fetched, for the sizes in the error message)
+bool counters_of_row(const uint32_t *row, FrameCounters &c)
+{
+    std::memset(&c, 0, sizeof c);
+    c.n_out = row[0];
+    c.out_offset = row[1];
+    c.flags = row[2];
+    c.n_clusters = row[3];
+    return !(row[2] & (FLAG_CAND_OVERFLOW | FLAG_ROOT_OVERFLOW | FLAG_OUT_OVERFLOW));
+}
+
 const char *kFormatMsg = "format must be one of AGX_L8 .. AGX_RGBA16 (agx_format)";
 
 }  // namespace
@@ -592,267 +480,6 @@ const char *kFormatMsg = "format must be one of AGX_L8 .. AGX_RGBA16 (agx_format
 extern "C" {
 
 int agx_abi_version(void) { return AGX_ABI_VERSION; }
-
-__attribute__((visibility("hidden"))) void *agx_internal_stream(agx_detector *det) { return det ? (void *)det->stream : nullptr; }
-__attribute__((visibility("hidden"))) int agx_internal_device(const agx_detector *det) { return det ? det->device : -1; }
-__attribute__((visibility("hidden"))) void *agx_internal_pool(agx_detector *det, int n_threads)
-{
-    if (!det || n_threads < 1) return nullptr;
-    if (det->pool && det->pool_threads != n_threads) {
-        destroy_worker_pool(det->pool);
-        det->pool = nullptr;
-    }
-    if (!det->pool) {
-        det->pool_threads = 0;
-        det->pool = create_worker_pool(n_threads);  // (throws where threads cannot be created: agx_detect_batch catches)
-        det->pool_threads = n_threads;
-    }
-    return det->pool;
-}
-// agx_detect_batch: u8 luma of a chunk of L16 / RGB8 frames (device pointers), computed on the device
-// behind whatever is on the detector's stream and copied into pinned host memory: [n_frames][H][W] at
-// *h_out (valid after the stream has been waited for -- the chunk's fetch does).  The staging is a ring of
-// n_slots chunks; the caller reuses a slot when the host tails that read it are done.
-__attribute__((visibility("hidden"))) int agx_internal_chunk_luma8(agx_detector *det, const void *d_frames, int n_frames,
-                                                                   int width, int height, size_t row_stride,
-                                                                   size_t frame_stride, int format, int slot, int n_slots,
-                                                                   size_t chunk_capacity_frames, const uint8_t **h_out,
-                                                                   const uint8_t **d_out)
-{
-    const size_t plane = (size_t)width * (size_t)height, one = plane * chunk_capacity_frames;
-    if (slot < 0 || slot >= n_slots) return AGX_ERR_ARG;
-    // a layout of the front-end kernel whose plane the chain of these very frames has just read (the batch enqueued last):
-    // 8-bit: that plane IS their to_luma8; 16-bit: k_luma8 narrows it (2 bytes per pixel to read instead of the frames' 4 .. 8)
-    const bool same_batch = format_front(format) && det->enqueued && det->front_format == format && det->front_src == d_frames &&
-                            det->front_frames == n_frames;
-    const bool front = same_batch && !format_16bit(format), front16 = same_batch && format_16bit(format);
-    if (front && !h_out) {
-        if (d_out) *d_out = det->d_front;
-        return AGX_OK;
-    }
-    if ((size_t)n_slots * one > det->luma_bytes) {
-        if (hipStreamSynchronize(det->stream) != hipSuccess) return AGX_ERR_HIP;
-        det->luma_bytes = 0;
-        det->d_luma = static_cast<uint8_t *>(side_alloc(det, agx_detector::SB_LUMA_D, (size_t)n_slots * one, 0));
-        det->h_luma = static_cast<uint8_t *>(side_alloc(det, agx_detector::SB_LUMA_H, (size_t)n_slots * one, 1));
-        if (!det->d_luma || !det->h_luma) return AGX_ERR_HIP;
-        det->luma_bytes = (size_t)n_slots * one;
-    }
-    uint8_t *d = det->d_luma + (size_t)slot * one, *h = det->h_luma + (size_t)slot * one;
-    if (front) d = det->d_front;
-    else if (front16) {
-        if (launch_luma8(det->d_front, (size_t)width * 2, plane * 2, n_frames, AGX_L16, d, width, height, det->stream) != 0) return AGX_ERR_HIP;
-    } else if (launch_luma8(d_frames, row_stride, frame_stride, n_frames, format, d, width, height, det->stream) != 0) return AGX_ERR_HIP;
-    if (d_out) *d_out = d;  // (the device tail reads it there; no copy to the host unless asked for)
-    if (!h_out) return AGX_OK;
-    if (hipMemcpyAsync(h, d, plane * (size_t)n_frames, hipMemcpyDeviceToHost, det->stream) != hipSuccess) return AGX_ERR_HIP;
-    *h_out = h;
-    return AGX_OK;
-}
-// agx_detect_batch: the upload streams, one per staging slot (created on first use, all of them or none: a failure
-// half way destroys what exists, so that a later call starts over instead of finding a half-initialised set); hipError_t
-__attribute__((visibility("hidden"))) int agx_internal_upload_streams(agx_detector *det, void **streams)
-{
-    if (!det->upload_streams_ready) {
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < AGX_UPLOAD_STREAMS && e == hipSuccess; ++i)
-            e = hipStreamCreateWithFlags(&det->upload_streams[i], hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            for (int i = 0; i < AGX_UPLOAD_STREAMS; ++i) {
-                if (det->upload_streams[i]) (void)hipStreamDestroy(det->upload_streams[i]);
-                det->upload_streams[i] = nullptr;
-            }
-            return (int)e;
-        }
-        det->upload_streams_ready = true;
-    }
-    for (int i = 0; i < AGX_UPLOAD_STREAMS; ++i) streams[i] = det->upload_streams[i];
-    return 0;
-}
-// agx_detect_batch: the last batch's results without the [frame][cap] layout of agx_saddles_batch_fetch: waits for the
-// device, then *records = the batch's compact list in the detector's pinned host mirror (valid until the next enqueue;
-// frame f's list = counts[f] records from offsets[f]) and status[f] = AGX_OK / AGX_ERR_CAPACITY (a device-side list of
-// the frame overflowed: its count is 0).  Returns AGX_OK, or the HIP / state error of the fetch.
-static int saddles_fetch_impl(agx_detector *det, agx_saddle *out, uint32_t cap_per_frame, uint32_t *counts, int *frame_status);
-__attribute__((visibility("hidden"))) int agx_internal_fetch_compact(agx_detector *det, const agx_saddle **records, uint32_t *counts,
-                                                                     uint32_t *offsets, int *status)
-{
-    const int n = det->enqueued ? det->args.n_frames : 0;
-    // cap 0: counts and status only (a frame with any saddles reads "capacity" against cap 0: the real status is
-    // derived from the counters below, with no limit on the list's length)
-    int rc = saddles_fetch_impl(det, nullptr, 0, counts, status);
-    if (rc != AGX_OK && rc != AGX_ERR_CAPACITY) return rc;
-    for (int f = 0; f < n; ++f) {
-        const FrameCounters &c = det->h_ctr[f];
-        status[f] = frame_status_of(c, 0xffffffffu);
-        counts[f] = status[f] == AGX_OK ? c.n_out : 0;
-        offsets[f] = c.out_offset;
-    }
-    *records = reinterpret_cast<const agx_saddle *>(det->h_out);
-    det->last_error.clear();
-    return AGX_OK;
-}
-// agx_detect_batch with option "device_tail": the board search + decode of the batch that was just enqueued, behind it on
-// the detector's stream.  d_luma = the frames' u8 luma in device memory (L8 frames: the frames themselves).  Results go to
-// mapped pinned host memory; agx_internal_fetch_tail waits for them.
-// the device evaluates angle_degree's atan2f by glibc's routine (libm_f32.h): offered only where this process's atan2f IS that
-// routine -- checked once per process on 2^20 operand pairs (more in tests/test_abi_cpu.py)
-static uint64_t libm_check_once()
-{
-    // (AGX_DEBUG_LIBM_MISMATCH=1: tests of the refusal path pretend that one input differs)
-    static const uint64_t mismatches = libm_atan2f_mismatches(1u << 20, 1) + (uint64_t)(tuning_env("AGX_DEBUG_LIBM_MISMATCH", 0) != 0);
-    return mismatches;
-}
-// 0: the host tail; 1: the device tail (asked for); 2: the device tail is available and the call may choose by its size
-__attribute__((visibility("hidden"))) int agx_internal_device_tail(agx_detector *det)
-{
-    if (det->device_tail < 0) return libm_check_once() == 0 ? 2 : 0;
-    return det->device_tail;
-}
-__attribute__((visibility("hidden"))) void agx_internal_tail_stats(agx_detector *det, int frames, int fallbacks, int uncertain)
-{
-    det->last_tail_frames = frames;
-    det->last_tail_fallbacks = fallbacks;
-    det->last_tail_uncertain = uncertain;
-}
-// One-time set-up of the device tail on this handle's device: the family's code list in device memory and the kernel's
-// attributes (155 KB of LDS).  All or nothing: a failure leaves nothing behind, and a later call starts over.
-__attribute__((visibility("hidden"))) int agx_internal_tail_prepare(agx_detector *det)
-{
-    if (det->tail_ready) return AGX_OK;
-    if (hipSetDevice(det->device) != hipSuccess) return AGX_ERR_HIP;
-    det->d_codes = static_cast<uint64_t *>(side_alloc(det, agx_detector::SB_CODES, (size_t)det->fam.n_codes * sizeof(uint64_t), 0));
-    if (!det->d_codes ||
-        hipMemcpy(det->d_codes, det->fam.codes, (size_t)det->fam.n_codes * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
-        init_tail_kernels() != 0) {
-        side_free(det, agx_detector::SB_CODES);
-        det->d_codes = nullptr;
-        return AGX_ERR_HIP;
-    }
-    det->tail_ready = true;
-    return AGX_OK;
-}
-__attribute__((visibility("hidden"))) int agx_internal_tail_debug(const agx_detector *) { return tuning_env("AGX_TAIL_DEBUG", 0); }  // (read at create)
-__attribute__((visibility("hidden"))) int agx_internal_enqueue_tail(agx_detector *det, const void *d_luma, size_t luma_row_stride,
-                                                                    size_t luma_frame_stride, uint32_t tag_cap, int to_device)
-{
-    if (!det->enqueued || det->external_out) return AGX_ERR_STATE;
-    const ChainArgs &a = det->args;
-    if (tag_cap == 0 || luma_row_stride > 0x7fffffffu) return AGX_ERR_ARG;
-    if (tag_cap > 128u) tag_cap = 128u;  // (the kernel's own list of distinct ids; frames beyond it take the host tail)
-    if (!det->tail_ready) {
-        const int rc = agx_internal_tail_prepare(det);
-        if (rc) return rc;
-    }
-    if (to_device && ((size_t)a.n_frames > det->dtail_frames || tag_cap > det->dtail_tag_cap)) {  // (device memory: the same layout)
-        if (hipStreamSynchronize(det->stream) != hipSuccess) return AGX_ERR_HIP;
-        const size_t F = std::max((size_t)a.n_frames, det->dtail_frames), cap = std::max(tag_cap, det->dtail_tag_cap);
-        det->dtail_frames = 0;
-        det->dtail_tag_cap = 0;
-        det->d_tail_tags = static_cast<agx_tag *>(side_alloc(det, agx_detector::SB_DTAGS, F * cap * sizeof(agx_tag), 0));
-        det->d_tail_table = static_cast<uint32_t *>(side_alloc(det, agx_detector::SB_DTABLE, F * 4 * sizeof(uint32_t), 0));
-        if (!det->d_tail_tags || !det->d_tail_table) {
-            side_free(det, agx_detector::SB_DTAGS);
-            side_free(det, agx_detector::SB_DTABLE);
-            det->d_tail_tags = nullptr;
-            det->d_tail_table = nullptr;
-            return AGX_ERR_HIP;
-        }
-        det->dtail_frames = F;
-        det->dtail_tag_cap = (uint32_t)cap;
-    }
-    if (!to_device && ((size_t)a.n_frames > det->tail_frames || tag_cap > det->tail_tag_cap)) {
-        if (hipStreamSynchronize(det->stream) != hipSuccess) return AGX_ERR_HIP;
-        const size_t F = std::max((size_t)a.n_frames, det->tail_frames), cap = std::max(tag_cap, det->tail_tag_cap);
-        det->tail_frames = 0;  // (nothing usable until both tables exist)
-        det->tail_tag_cap = 0;
-        det->h_tags = static_cast<agx_tag *>(side_alloc(det, agx_detector::SB_TAGS, F * cap * sizeof(agx_tag), 2));
-        det->h_tail_table = static_cast<uint32_t *>(side_alloc(det, agx_detector::SB_TAIL_TABLE, F * 4 * sizeof(uint32_t), 2));
-        if (!det->h_tags || !det->h_tail_table) {
-            side_free(det, agx_detector::SB_TAGS);
-            side_free(det, agx_detector::SB_TAIL_TABLE);
-            det->h_tags = det->h_tags_dev = nullptr;
-            det->h_tail_table = det->h_tail_table_dev = nullptr;
-            return AGX_ERR_HIP;
-        }
-        det->h_tags_dev = static_cast<agx_tag *>(det->side[agx_detector::SB_TAGS].dev);
-        det->h_tail_table_dev = static_cast<uint32_t *>(det->side[agx_detector::SB_TAIL_TABLE].dev);
-        det->tail_frames = F;
-        det->tail_tag_cap = (uint32_t)cap;
-    }
-    TailArgs t{};
-    t.saddles = a.out;
-    t.ctr = a.ctr;
-    t.n_frames = a.n_frames;
-    t.luma = static_cast<const uint8_t *>(d_luma);
-    t.luma_frame_stride = (long long)luma_frame_stride;
-    t.luma_row_stride = (int)luma_row_stride;
-    t.W = a.W;
-    t.H = a.H;
-    t.edge = det->fam.edge;
-    t.border = det->fam.border;
-    t.hamming = det->fam.hamming;
-    t.n_codes = det->fam.n_codes;
-    t.codes = det->d_codes;
-    t.max_boards = det->params.max_num_of_boards;
-    t.tags = to_device ? det->d_tail_tags : det->h_tags_dev;
-    t.table = to_device ? det->d_tail_table : det->h_tail_table_dev;
-    t.tag_cap = tag_cap;  // this call's: a frame with more tags is handed back (TAIL_CAPACITY), whatever the table could hold
-    t.tag_stride = to_device ? det->dtail_tag_cap : det->tail_tag_cap;
-    t.debug_band = (float)det->tail_debug_band_mdeg * 1e-3f;
-    t.debug = tuning_env("AGX_TAIL_DEBUG", 0);
-    t.debug_frame = tuning_env("AGX_TAIL_DEBUG_FRAME", 0);
-    if (launch_board_tail(t, det->stream) != 0) return AGX_ERR_HIP;
-    return AGX_OK;
-}
-__attribute__((visibility("hidden"))) int agx_internal_publish_tags(agx_detector *det, uint32_t cap_per_frame, agx_tag *d_tags,
-                                                                    uint32_t *d_counts, int *d_status)
-{
-    if (!det->enqueued || !det->d_tail_table) return AGX_ERR_STATE;
-    const int e = launch_publish_tags(det->d_tail_table, det->d_tail_tags, det->dtail_tag_cap, det->args.ctr, det->args.n_frames,
-                                      cap_per_frame, d_tags, d_counts, d_status, det->stream);
-    return e == 0 ? AGX_OK : AGX_ERR_HIP;
-}
-__attribute__((visibility("hidden"))) const uint32_t *agx_internal_device_tail_table(agx_detector *det) { return det->d_tail_table; }
-__attribute__((visibility("hidden"))) uint8_t *agx_internal_fetch_luma(agx_detector *det, size_t bytes)
-{
-    if (bytes > det->fetch_luma_bytes) {
-        det->fetch_luma_bytes = 0;
-        det->h_fetch_luma = static_cast<uint8_t *>(side_alloc(det, agx_detector::SB_FETCH_LUMA, bytes, 1));
-        if (!det->h_fetch_luma) return nullptr;
-        det->fetch_luma_bytes = bytes;
-    }
-    return det->h_fetch_luma;
-}
-__attribute__((visibility("hidden"))) agx::DetectPending *agx_internal_detect_pending(agx_detector *det) { return &det->detect; }
-__attribute__((visibility("hidden"))) int agx_internal_fetch_tail(agx_detector *det, const agx_tag **tags, const uint32_t **table, uint32_t *tag_cap)
-{
-    if (hipStreamSynchronize(det->stream) != hipSuccess) return AGX_ERR_HIP;
-    *tags = det->h_tags;
-    *table = det->h_tail_table;
-    *tag_cap = det->tail_tag_cap;
-    return AGX_OK;
-}
-__attribute__((visibility("hidden"))) void agx_internal_abandon_batch(agx_detector *det)
-{
-    if (!det) return;
-    (void)hipStreamSynchronize(det->stream);
-    harvest_events(det);
-    det->enqueued = false;
-}
-__attribute__((visibility("hidden"))) const void *agx_internal_family(const agx_detector *det) { return &det->fam; }
-__attribute__((visibility("hidden"))) int agx_internal_max_boards(const agx_detector *det) { return det->params.max_num_of_boards; }
-__attribute__((visibility("hidden"))) void *agx_internal_stage(agx_detector *det, size_t bytes)
-{
-    if (bytes > det->stage_bytes) {
-        if (hipSetDevice(det->device) != hipSuccess || hipStreamSynchronize(det->stream) != hipSuccess) return nullptr;
-        det->stage_bytes = 0;
-        det->d_stage = static_cast<uint8_t *>(side_alloc(det, agx_detector::SB_STAGE, bytes, 0));
-        if (!det->d_stage) return nullptr;
-        det->stage_bytes = bytes;
-    }
-    return det->d_stage;
-}
 
 const char *agx_status_string(int status)
 {
@@ -976,10 +603,8 @@ void agx_detector_destroy(agx_detector *det)
     free_workspace(det);
     if (det->pool) destroy_worker_pool(det->pool);
     if (det->tail_workers) destroy_tail_workers(det->tail_workers);
-    for (int i = 0; i < agx_detector::SB_COUNT; ++i) side_free(det, i);  // staging, luma planes, the device tail's buffers
+    for (int i = 0; i < SB_COUNT; ++i) side_free(det, i);
     if (det->h_table) (void)hipHostFree(det->h_table);
-    if (det->d_dbg_resp) (void)hipFree(det->d_dbg_resp);
-    if (det->d_resp_store) (void)hipFree(det->d_resp_store);
     for (int i = 0; i < AGX_UPLOAD_STREAMS; ++i)
         if (det->upload_streams[i]) (void)hipStreamDestroy(det->upload_streams[i]);
     if (det->own_stream) (void)hipStreamDestroy(det->own_stream);
@@ -1105,10 +730,10 @@ static int batch_enqueue_impl(agx_detector *det, const void *d_frames, int n_fra
                               uint32_t saddle_capacity, void *d_frame_table)
 {
     if (!det || !d_frames || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null frames or n_frames <= 0");
-    if (!valid_format(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
+    if (!format_px_bytes(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
     if (width < 2 || height < 2) return fail(det, AGX_ERR_ARG, "width and height must be >= 2");
     if ((long long)width * height >= (1ll << 30) || width > 65000) return fail(det, AGX_ERR_ARG, "frame too large (>= 2^30 px or wider than 65000)");
-    const size_t px_bytes = (size_t)bytes_per_px(format);
+    const size_t px_bytes = (size_t)format_px_bytes(format);
     if (row_stride_bytes < (size_t)width * px_bytes || row_stride_bytes > 0x7fffffffu ||
         (n_frames > 1 && frame_stride_bytes < row_stride_bytes * format_rows(format, height)))
         return fail(det, AGX_ERR_ARG, "strides must cover a row / a frame");
@@ -1128,20 +753,15 @@ static int batch_enqueue_impl(agx_detector *det, const void *d_frames, int n_fra
         // AGX_LA8 .. AGX_RGBA16: the front-end kernel writes the batch's integer luma plane (tight u8 / u16) and the L8 / L16
         // chain reads that: to_luma32f of an integer image is its integer luma / 255 (/ 65535)
         const size_t out_px = format_16bit(format) ? 2 : 1, need = (size_t)n_frames * (size_t)width * (size_t)height * out_px;
-        if (need > det->front_bytes) {
-            HIP_TRY(det, hipStreamSynchronize(det->stream));
-            det->front_bytes = 0;
-            det->d_front = static_cast<uint8_t *>(side_alloc(det, agx_detector::SB_FRONT, need, 0));
-            if (!det->d_front) return fail(det, AGX_ERR_HIP, "hipMalloc: front-end luma plane");
-            det->front_bytes = need;
-        }
-        hipError_t e = (hipError_t)launch_front_luma(d_frames, row_stride_bytes, frame_stride_bytes, n_frames, format, det->d_front, 0,
+        void *d_front = side_ensure(det, SB_FRONT, need, 0);
+        if (!d_front) return fail(det, AGX_ERR_HIP, "hipMalloc: front-end luma plane");
+        hipError_t e = (hipError_t)launch_front_luma(d_frames, row_stride_bytes, frame_stride_bytes, n_frames, format, d_front, 0,
                                                      width, height, det->stream);
         if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_front_luma: ") + hipGetErrorString(e));
         det->front_src = d_frames;
         det->front_format = format;
         det->front_frames = n_frames;
-        d_frames = det->d_front;
+        d_frames = d_front;
         row_stride_bytes = (size_t)width * out_px;
         frame_stride_bytes = row_stride_bytes * (size_t)height;
         format = out_px == 2 ? AGX_L16 : AGX_L8;
@@ -1184,17 +804,10 @@ static int batch_enqueue_impl(agx_detector *det, const void *d_frames, int n_fra
     a.resp_dbg = nullptr;
     det->resp_stored = false;
     if (det->store_resp) {  // parity tests: K1 also stores the response it evaluates in registers
-        const size_t need = (size_t)n_frames * (size_t)a.plane;
-        if (need > det->resp_store_floats) {
-            HIP_TRY(det, hipStreamSynchronize(det->stream));
-            if (det->d_resp_store) (void)hipFree(det->d_resp_store);
-            det->d_resp_store = nullptr;
-            det->resp_store_floats = 0;
-            HIP_TRY(det, hipMalloc((void **)&det->d_resp_store, need * sizeof(float)));
-            det->resp_store_floats = need;
-        }
-        HIP_TRY(det, hipMemsetAsync(det->d_resp_store, 0, need * sizeof(float), det->stream));  // the border ring is 0
-        a.resp_dbg = det->d_resp_store;
+        const size_t need = (size_t)n_frames * (size_t)a.plane * sizeof(float);
+        a.resp_dbg = static_cast<float *>(side_ensure(det, SB_RESP_STORE, need, 0));
+        if (!a.resp_dbg) return fail(det, AGX_ERR_HIP, "hipMalloc: response planes");
+        HIP_TRY(det, hipMemsetAsync(a.resp_dbg, 0, need, det->stream));  // the border ring is 0
         det->resp_stored = true;
     }
     if (!plan_k1(a, det->k1_rows)) return fail(det, AGX_ERR_ARG, "unsupported frame geometry");
@@ -1222,17 +835,7 @@ int agx_saddles_batch_enqueue_to(agx_detector *det, const void *d_frames, int n_
     });
 }
 
-int agx_saddles_batch_fetch(agx_detector *det, agx_saddle *out, uint32_t cap_per_frame, uint32_t *counts,
-                            int *frame_status)
-{
-    return agx_guard(det, [&]() -> int {
-    if (det && det->enqueued && det->detect.kind)
-        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_detect_batch_enqueue's: fetch it with agx_detect_batch_fetch");
-    return saddles_fetch_impl(det, out, cap_per_frame, counts, frame_status);
-    });
-}
-
-// agx_saddles_batch_fetch without the pairing rule (agx_internal_fetch_compact reads the chain's results of a detect batch too)
+// agx_saddles_batch_fetch without the pairing rule (agx::fetch_compact reads the chain's results of a detect batch too)
 static int saddles_fetch_impl(agx_detector *det, agx_saddle *out, uint32_t cap_per_frame, uint32_t *counts, int *frame_status)
 {
     return agx_guard(det, [&]() -> int {
@@ -1245,17 +848,8 @@ static int saddles_fetch_impl(agx_detector *det, agx_saddle *out, uint32_t cap_p
     bool have_counters = false;
     if (det->out_in_host) {  // one frame: list and table row are in host memory when the stream is through -- no copy at all
         HIP_TRY(det, hipStreamSynchronize(det->stream));
-        const uint32_t *row = det->h_table;
-        if (!(row[2] & (FLAG_CAND_OVERFLOW | FLAG_ROOT_OVERFLOW | FLAG_OUT_OVERFLOW))) {
-            FrameCounters &c = det->h_ctr[0];
-            std::memset(&c, 0, sizeof c);
-            c.n_out = row[0];
-            c.out_offset = row[1];
-            c.flags = row[2];
-            c.n_clusters = row[3];
-            *det->h_total = row[0] + row[1];
-            have_counters = true;
-        }  // else: the full record below (sizes of the overflowing lists for the error message)
+        have_counters = counters_of_row(det->h_table, det->h_ctr[0]);  // (false: the full record below)
+        *det->h_total = det->h_table[0] + det->h_table[1];
     }
     bool out_fetched = det->out_in_host;
     if (!have_counters && !det->out_in_host && det->h_table_dev && det->h_out_dev && F + 1 <= det->h_table_rows) {
@@ -1264,16 +858,8 @@ static int saddles_fetch_impl(agx_detector *det, agx_saddle *out, uint32_t cap_p
         if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_publish: ") + hipGetErrorString(e));
         HIP_TRY(det, hipStreamSynchronize(det->stream));
         bool bad = false;
-        for (size_t f = 0; f < F; ++f) {
-            const uint32_t *row = det->h_table + 4 * f;
-            FrameCounters &c = det->h_ctr[f];
-            std::memset(&c, 0, sizeof c);
-            c.n_out = row[0];
-            c.out_offset = row[1];
-            c.flags = row[2];
-            c.n_clusters = row[3];
-            bad = bad || (row[2] & (FLAG_CAND_OVERFLOW | FLAG_ROOT_OVERFLOW | FLAG_OUT_OVERFLOW));
-        }
+        for (size_t f = 0; f < F; ++f)
+            if (!counters_of_row(det->h_table + 4 * f, det->h_ctr[f])) bad = true;
         *det->h_total = det->h_table[4 * F];
         have_counters = !bad;  // (an overflowing frame: the full records below, for the sizes in the error message)
         out_fetched = true;
@@ -1316,13 +902,23 @@ static int saddles_fetch_impl(agx_detector *det, agx_saddle *out, uint32_t cap_p
     });
 }
 
+int agx_saddles_batch_fetch(agx_detector *det, agx_saddle *out, uint32_t cap_per_frame, uint32_t *counts,
+                            int *frame_status)
+{
+    return agx_guard(det, [&]() -> int {
+    if (det && det->enqueued && det->detect.kind)
+        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_detect_batch_enqueue's: fetch it with agx_detect_batch_fetch");
+    return saddles_fetch_impl(det, out, cap_per_frame, counts, frame_status);
+    });
+}
+
 // detect over a batch in device memory, stream-ordered (csrc/detect_batch.cpp: the chain, k_luma8, the device tail, the fetch)
 static int detect_enqueue_checked(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
                                   size_t frame_stride_bytes, int format, uint32_t cap_per_frame, bool to_device, agx_tag *d_tags,
                                   uint32_t *d_counts, int *d_status)
 {
     if (!det) return AGX_ERR_ARG;
-    if (!valid_format(format) || format == AGX_LF32)  // (the decode needs to_luma8: agx_detect_planes for an f32 plane)
+    if (!format_px_bytes(format) || format == AGX_LF32)  // (the decode needs to_luma8: agx_detect_planes for an f32 plane)
         return fail(det, AGX_ERR_FORMAT, "format must be an integer agx_format (AGX_LF32: agx_detect_planes)");
     if (to_device && (!d_counts || !d_status || (!d_tags && cap_per_frame) || (((uintptr_t)d_tags | (uintptr_t)d_counts | (uintptr_t)d_status) & 3)))
         return fail(det, AGX_ERR_ARG, "null or misaligned output buffers");
@@ -1364,45 +960,70 @@ int agx_detect_batch_fetch(agx_detector *det, agx_tag *out, uint32_t *counts, in
 
 }  // extern "C"
 
+int agx::fetch_compact(agx_detector *det, const agx_saddle **records, uint32_t *counts, uint32_t *offsets, int *status)
+{
+    const int n = det->enqueued ? det->args.n_frames : 0;
+    // cap 0: counts and status only (a frame with any saddles reads "capacity" against cap 0: the real status is
+    // derived from the counters below, with no limit on the list's length)
+    int rc = saddles_fetch_impl(det, nullptr, 0, counts, status);
+    if (rc != AGX_OK && rc != AGX_ERR_CAPACITY) return rc;
+    for (int f = 0; f < n; ++f) {
+        const FrameCounters &c = det->h_ctr[f];
+        status[f] = frame_status_of(c, 0xffffffffu);
+        counts[f] = status[f] == AGX_OK ? c.n_out : 0;
+        offsets[f] = c.out_offset;
+    }
+    *records = reinterpret_cast<const agx_saddle *>(det->h_out);
+    det->last_error.clear();
+    return AGX_OK;
+}
+
+void agx::abandon_batch(agx_detector *det)
+{
+    (void)hipStreamSynchronize(det->stream);
+    harvest_events(det);
+    det->enqueued = false;
+}
+
 namespace {
+// The single frame of the last agx_refined_saddle_points call again, into a larger buffer (its
+// list is still in the pinned host mirror).
+int refetch_single(agx_detector *det, agx_saddle *out, uint32_t cap, uint32_t *n_out)
+{
+    const FrameCounters &c = det->h_ctr[0];
+    *n_out = c.n_out;
+    if (c.n_out > cap) return AGX_ERR_CAPACITY;
+    if (c.n_out) std::memcpy(out, det->h_out + (size_t)c.out_offset * 5, (size_t)c.n_out * sizeof(agx_saddle));
+    det->last_error.clear();
+    return AGX_OK;
+}
+
 // agx_refined_saddle_points; with want_luma8 (L16 / RGB8 only) the u8 luma of the frame is computed on the
-// device behind the chain and is in det->h_luma (tight [H][W]) when this returns.
+// device behind the chain and is in SB_LUMA_H (tight [H][W]) when this returns.
 int refined_saddle_points_impl(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes,
                                int format, agx_saddle *out, uint32_t cap, uint32_t *n_out, bool want_luma8)
 {
     if (!det || !pixels || !n_out) return fail(det, AGX_ERR_ARG, "null argument");
-    if (!valid_format(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
+    if (!format_px_bytes(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
     if (width < 2 || height < 2) return fail(det, AGX_ERR_ARG, "width and height must be >= 2");
-    const size_t row_bytes = (size_t)width * bytes_per_px(format);
+    const size_t row_bytes = (size_t)width * format_px_bytes(format);
     if (row_stride_bytes < row_bytes) return fail(det, AGX_ERR_ARG, "row stride smaller than a row");
     HIP_TRY(det, hipSetDevice(det->device));
     const size_t pitch = (row_bytes + 3) & ~(size_t)3;
     const size_t rows = format_rows(format, height);  // (the planar layout: three planes, one under the other)
     const size_t need = pitch * rows;
-    if (need > det->stage_bytes) {
-        HIP_TRY(det, hipStreamSynchronize(det->stream));
-        det->stage_bytes = 0;
-        det->d_stage = static_cast<uint8_t *>(side_alloc(det, agx_detector::SB_STAGE, need, 0));
-        if (!det->d_stage) return fail(det, AGX_ERR_HIP, "hipMalloc: staging buffer");
-        det->stage_bytes = need;
-    }
-    HIP_TRY(det, hipMemcpy2DAsync(det->d_stage, pitch, pixels, row_stride_bytes, row_bytes, rows,
-                                  hipMemcpyHostToDevice, det->stream));
-    int rc = agx_saddles_batch_enqueue(det, det->d_stage, 1, width, height, pitch, need, format);
+    void *d_stage = side_ensure(det, SB_STAGE, need, 0);
+    if (!d_stage) return fail(det, AGX_ERR_HIP, "hipMalloc: staging buffer");
+    HIP_TRY(det, hipMemcpy2DAsync(d_stage, pitch, pixels, row_stride_bytes, row_bytes, rows, hipMemcpyHostToDevice, det->stream));
+    int rc = agx_saddles_batch_enqueue(det, d_stage, 1, width, height, pitch, need, format);
     if (rc) return rc;
     if (want_luma8) {  // stream-ordered behind the chain; the fetch below waits for the stream
         const size_t lb = (size_t)width * (size_t)height;
-        if (lb > det->luma_bytes) {
-            HIP_TRY(det, hipStreamSynchronize(det->stream));
-            det->luma_bytes = 0;
-            det->d_luma = static_cast<uint8_t *>(side_alloc(det, agx_detector::SB_LUMA_D, lb, 0));
-            det->h_luma = static_cast<uint8_t *>(side_alloc(det, agx_detector::SB_LUMA_H, lb, 1));
-            if (!det->d_luma || !det->h_luma) return fail(det, AGX_ERR_HIP, "hipMalloc / hipHostMalloc: luma planes");
-            det->luma_bytes = lb;
-        }
-        hipError_t e = (hipError_t)launch_luma8(det->d_stage, pitch, need, 1, format, det->d_luma, width, height, det->stream);
+        if (!side_ensure_pair(det, SB_LUMA_D, lb, 0, SB_LUMA_H, lb, 1)) return fail(det, AGX_ERR_HIP, "hipMalloc / hipHostMalloc: luma planes");
+        uint8_t *d_luma = det->side[SB_LUMA_D].ptr<uint8_t>();
+        hipError_t e = (hipError_t)launch_luma8(d_stage, pitch, need, 1, format, d_luma, width, height, det->stream);
         if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_luma8: ") + hipGetErrorString(e));
-        HIP_TRY(det, hipMemcpyAsync(det->h_luma, det->d_luma, lb, hipMemcpyDeviceToHost, det->stream));
+        HIP_TRY(det, hipMemcpyAsync(det->side[SB_LUMA_H].payload, d_luma, lb, hipMemcpyDeviceToHost, det->stream));
     }
     // one frame: the pinned host mirror of the batch fetch holds the list; a too-small `cap` reports
     // the needed size
@@ -1410,13 +1031,9 @@ int refined_saddle_points_impl(agx_detector *det, const void *pixels, int width,
     int st = AGX_OK;
     rc = agx_saddles_batch_fetch(det, nullptr, 0, &count, &st);  // cap 0: counts and status only
     if (rc && rc != AGX_ERR_CAPACITY) return rc;
-    const FrameCounters &c = det->h_ctr[0];
-    if (c.flags & (FLAG_CAND_OVERFLOW | FLAG_ROOT_OVERFLOW | FLAG_OUT_OVERFLOW)) return AGX_ERR_CAPACITY;  // last_error set by fetch
-    *n_out = c.n_out;
-    if (c.n_out > cap) return fail(det, AGX_ERR_CAPACITY, "output capacity too small");
-    if (c.n_out) std::memcpy(out, det->h_out + (size_t)c.out_offset * 5, (size_t)c.n_out * sizeof(agx_saddle));
-    det->last_error.clear();
-    return AGX_OK;
+    if (frame_status_of(det->h_ctr[0], 0xffffffffu) != AGX_OK) return AGX_ERR_CAPACITY;  // a list overflowed: last_error set by fetch
+    rc = refetch_single(det, out, cap, n_out);
+    return rc == AGX_ERR_CAPACITY ? fail(det, rc, "output capacity too small") : rc;
 }
 }  // namespace
 
@@ -1428,18 +1045,6 @@ int agx_refined_saddle_points(agx_detector *det, const void *pixels, int width, 
     return agx_guard(det, [&]() -> int {
     return refined_saddle_points_impl(det, pixels, width, height, row_stride_bytes, format, out, cap, n_out, false);
     });
-}
-
-// The single frame of the last agx_refined_saddle_points call again, into a larger buffer (its
-// list is still in the pinned host mirror).
-static int refetch_single(agx_detector *det, agx_saddle *out, uint32_t cap, uint32_t *n_out)
-{
-    const FrameCounters &c = det->h_ctr[0];
-    *n_out = c.n_out;
-    if (c.n_out > cap) return AGX_ERR_CAPACITY;
-    if (c.n_out) std::memcpy(out, det->h_out + (size_t)c.out_offset * 5, (size_t)c.n_out * sizeof(agx_saddle));
-    det->last_error.clear();
-    return AGX_OK;
 }
 
 int agx_debug_angle_pairs(const float *vectors, size_t n, float *exact, float *approx, uint8_t *has_approx)
@@ -1543,7 +1148,7 @@ int agx_detect(agx_detector *det, const void *pixels, int width, int height, siz
 {
     return agx_guard(det, [&]() -> int {
     if (!det || !pixels || !n_out) return fail(det, AGX_ERR_ARG, "null argument");
-    if (!valid_format(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
+    if (!format_px_bytes(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
     if (width < 2 || height < 2) return fail(det, AGX_ERR_ARG, "width and height must be >= 2");
     if (format == AGX_LF32) return fail(det, AGX_ERR_FORMAT, "an f32 luma plane carries no u8 luma for the decode: use agx_detect_planes");
     // detector.rs:507-508: u8 luma for the decode, saddle chain on the device.  L8 is its own luma; for
@@ -1560,7 +1165,7 @@ int agx_detect(agx_detector *det, const void *pixels, int width, int height, siz
         rc = refetch_single(det, saddles.data(), (uint32_t)saddles.size(), &ns);
     }
     if (rc) return rc;
-    const uint8_t *grey = device_luma ? det->h_luma : (const uint8_t *)pixels;
+    const uint8_t *grey = device_luma ? det->side[SB_LUMA_H].ptr<uint8_t>() : (const uint8_t *)pixels;
     const size_t grey_stride = device_luma ? (size_t)width : row_stride_bytes;
     return agx_detect_from_saddles(det, saddles.data(), ns, grey, width, height, grey_stride, out, cap, n_out);
     });
@@ -1677,7 +1282,7 @@ int fetch_redzones(agx_detector *det, void *host_out, size_t cap_bytes, size_t *
     };
     for (size_t i = 0; i < det->device_allocs.size(); ++i)
         if (int rc = check(det->device_allocs[i], det->alloc_bytes[i], false)) return rc;
-    for (const agx_detector::SideBuf &b : det->side)
+    for (const SideBuf &b : det->side)
         if (b.base)
             if (int rc = check(b.base, b.bytes, b.host)) return rc;
     std::memcpy(host_out, v, sizeof v);
@@ -1693,8 +1298,9 @@ int agx_debug_fetch(agx_detector *det, int frame, int what, void *host_out, size
     if (what == AGX_DBG_TAIL_TABLE_ADDR) {  // tests of the guard check: {host address, payload bytes} of the device tail's frame table
         *n_items = 2;
         if (cap_bytes < 2 * sizeof(uint64_t)) return AGX_ERR_CAPACITY;
-        if (!det->h_tail_table) return fail(det, AGX_ERR_STATE, "no device tail has run on this handle");
-        const uint64_t v[2] = {(uint64_t)(uintptr_t)det->h_tail_table, (uint64_t)det->side[agx_detector::SB_TAIL_TABLE].bytes};
+        const SideBuf &table = det->side[SB_TAIL_TABLE];
+        if (!table.base) return fail(det, AGX_ERR_STATE, "no device tail has run on this handle");
+        const uint64_t v[2] = {(uint64_t)(uintptr_t)table.payload, (uint64_t)table.bytes};
         std::memcpy(host_out, v, sizeof v);
         return AGX_OK;
     }
@@ -1719,24 +1325,19 @@ int agx_debug_fetch(agx_detector *det, int frame, int what, void *host_out, size
         if (cap_bytes < plane * sizeof(float)) return AGX_ERR_CAPACITY;
         if (!det->resp_stored)
             return fail(det, AGX_ERR_STATE, "AGX_DBG_RESP needs option store_response=1 before the batch is enqueued");
-        HIP_TRY(det, hipMemcpy(host_out, det->d_resp_store + (size_t)frame * plane, plane * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(det, hipMemcpy(host_out, det->side[SB_RESP_STORE].ptr<float>() + (size_t)frame * plane, plane * sizeof(float), hipMemcpyDeviceToHost));
         return AGX_OK;
     }
     case AGX_DBG_RESP_RECOMPUTED: {
         // cross-check: the response recomputed from the stored blur plane by a separate kernel
         *n_items = plane;
         if (cap_bytes < plane * sizeof(float)) return AGX_ERR_CAPACITY;
-        if (det->dbg_resp_plane < (long long)plane) {
-            if (det->d_dbg_resp) (void)hipFree(det->d_dbg_resp);
-            det->d_dbg_resp = nullptr;
-            det->dbg_resp_plane = 0;
-            HIP_TRY(det, hipMalloc((void **)&det->d_dbg_resp, plane * sizeof(float)));
-            det->dbg_resp_plane = (long long)plane;
-        }
-        hipError_t e = (hipError_t)launch_debug_resp(a, frame, det->d_dbg_resp, det->stream);
+        float *d_resp = static_cast<float *>(side_ensure(det, SB_DBG_RESP, plane * sizeof(float), 0));
+        if (!d_resp) return fail(det, AGX_ERR_HIP, "hipMalloc: response plane");
+        hipError_t e = (hipError_t)launch_debug_resp(a, frame, d_resp, det->stream);
         if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_debug_resp: ") + hipGetErrorString(e));
         HIP_TRY(det, hipStreamSynchronize(det->stream));
-        HIP_TRY(det, hipMemcpy(host_out, det->d_dbg_resp, plane * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(det, hipMemcpy(host_out, d_resp, plane * sizeof(float), hipMemcpyDeviceToHost));
         return AGX_OK;
     }
     case AGX_DBG_COUNTERS: {
@@ -1750,9 +1351,9 @@ int agx_debug_fetch(agx_detector *det, int frame, int what, void *host_out, size
     case 9: {  // AGX_DBG_LUMA8: the u8 luma the device computed for the last agx_detect on an L16 / RGB8 image
         const size_t lb = (size_t)a.W * (size_t)a.H;
         *n_items = lb;
-        if (!det->h_luma || det->luma_bytes < lb) return fail(det, AGX_ERR_STATE, "no device luma: agx_detect on an L16 / RGB8 image first");
+        if (det->side[SB_LUMA_H].bytes < lb) return fail(det, AGX_ERR_STATE, "no device luma: agx_detect on an L16 / RGB8 image first");
         if (cap_bytes < lb) return AGX_ERR_CAPACITY;
-        std::memcpy(host_out, det->h_luma, lb);
+        std::memcpy(host_out, det->side[SB_LUMA_H].payload, lb);
         return AGX_OK;
     }
     case 10: {  // wave timeline (debug_ablation & 4096): `frame` selects the kernel (1 = verify, 2 = flood, 3 = refine);

@@ -1,51 +1,17 @@
-// detector_internal.h -- library-internal accessors of a detector handle (not part of the ABI).
+// detector_internal.h -- the detector handle as the library's own files see it (detector.cpp, detect_batch.cpp, group.cpp);
+// not part of the ABI.
 #pragma once
-#include "../../include/aprilgrid_amd.h"
+#include <hip/hip_runtime_api.h>
 
-extern "C" {
-// hipStream_t the detector's kernels are enqueued on (its own stream, or the caller's after
-// agx_detector_set_stream) and its device ordinal.
-void *agx_internal_stream(agx_detector *det);
-int agx_internal_device(const agx_detector *det);
-// agx_detect_batch: the detector's worker pool (created on first use, resized when n_threads
-// changes), its family table (agx::FamilyInfo), max_num_of_boards and a device staging buffer of
-// at least `bytes` (grown on demand).
-void *agx_internal_pool(agx_detector *det, int n_threads);
-const void *agx_internal_family(const agx_detector *det);
-int agx_internal_max_boards(const agx_detector *det);
-void *agx_internal_stage(agx_detector *det, size_t bytes);
-// Wait for whatever is enqueued and forget it (an error path between enqueue and fetch).
-void agx_internal_abandon_batch(agx_detector *det);
+#include <string>
+#include <vector>
+
+#include "../../include/aprilgrid_amd.h"
+#include "chain_kernels.h"
+#include "host_tail.hpp"
+
 #define AGX_UPLOAD_STREAMS 3
-int agx_internal_upload_streams(agx_detector *det, void **streams /* [AGX_UPLOAD_STREAMS] */);  // hipError_t
-// u8 luma of a chunk of L16 / RGB8 device frames, computed on the device and copied to pinned host
-// memory behind the detector's stream ([n_frames][H][W] at *h_out once the stream has been waited for);
-// the staging is a ring of n_slots chunks of chunk_capacity_frames
-int agx_internal_chunk_luma8(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride,
-                             size_t frame_stride, int format, int slot, int n_slots, size_t chunk_capacity_frames,
-                             const uint8_t **h_out, const uint8_t **d_out);  // (h_out null: no copy to the host; d_out: where it is on the device)
-// the last batch's compact list in the detector's pinned host mirror (valid until the next enqueue) + per-frame
-// counts / offsets / status; waits for the device
-int agx_internal_fetch_compact(agx_detector *det, const agx_saddle **records, uint32_t *counts, uint32_t *offsets, int *status);
-// option "device_tail": board search + decode of the enqueued batch on the device (tail_kernels.hip); the results in mapped
-// pinned host memory after agx_internal_fetch_tail: tags[f * *tag_cap ..] (the rows' stride, >= the cap that was enqueued), table[4 f] = count, table[4 f + 1] = agx::TAIL_* status (+ 2: the frame's 100 MHz ticks, + 3: saddles | seeds << 16)
-int agx_internal_device_tail(agx_detector *det);
-int agx_internal_tail_prepare(agx_detector *det);  // one-time set-up on the handle's device (code list, kernel attributes): all or nothing
-int agx_internal_tail_debug(const agx_detector *det);  // AGX_TAIL_DEBUG as read when the handle was created
-// to_device != 0 (agx_detect_batch_enqueue_to): tags and table go to a pair of device buffers instead, read by
-// agx_internal_publish_tags and agx_internal_device_tail_table
-int agx_internal_enqueue_tail(agx_detector *det, const void *d_luma, size_t luma_row_stride, size_t luma_frame_stride, uint32_t tag_cap,
-                              int to_device);
-int agx_internal_fetch_tail(agx_detector *det, const agx_tag **tags, const uint32_t **table, uint32_t *tag_cap);
-void agx_internal_tail_stats(agx_detector *det, int frames, int fallbacks, int uncertain);
-// agx_detect_batch_enqueue_to: the device tail's results of the batch (device buffers) into the caller's layout, behind the
-// tail on the detector's stream (tail_kernels.hip, k_publish_tags); the device address of the tail's frame table [n][4]
-int agx_internal_publish_tags(agx_detector *det, uint32_t cap_per_frame, agx_tag *d_tags, uint32_t *d_counts, int *d_status);
-const uint32_t *agx_internal_device_tail_table(agx_detector *det);
-// agx_detect_batch_fetch: pinned host memory of at least `bytes` for the u8 luma of the frames the host tail takes (grown on
-// demand, guarded like every side buffer)
-uint8_t *agx_internal_fetch_luma(agx_detector *det, size_t bytes);
-}
+
 namespace agx {
 // agx_format: bytes between horizontally adjacent pixels (0: not a format), the rows a frame of `height` spans (the planar
 // layout: three planes), the layouts the front-end kernel converts (k_front_luma) and which of those have 16-bit channels
@@ -64,9 +30,10 @@ inline int format_px_bytes(int f)
 inline size_t format_rows(int f, int height) { return (size_t)height * (f == AGX_RGB8P ? 3u : 1u); }
 inline bool format_front(int f) { return f >= AGX_LA8 && f <= AGX_RGBA16; }
 inline bool format_16bit(int f) { return f == AGX_L16 || f == AGX_LA16 || f == AGX_RGB16 || f == AGX_RGBA16; }
-void destroy_worker_pool(void *pool);
-void *create_worker_pool(int n_threads);
-struct TailWorkers;  // host_tail.hpp
+
+class WorkerPool;  // detect_batch.cpp
+WorkerPool *create_worker_pool(int n_threads);
+void destroy_worker_pool(WorkerPool *pool);
 TailWorkers *create_tail_workers(int n_threads);  // nullptr for n_threads <= 1
 void destroy_tail_workers(TailWorkers *w);
 
@@ -83,9 +50,159 @@ struct DetectPending {
     uint32_t *d_counts = nullptr;
     int *d_status = nullptr;
 };
+
+struct EventPair {
+    hipEvent_t a, b;
+    int kernel;
+};
+
+// A buffer outside the chain's workspace, device memory or pinned host memory, with the handle's guard bytes in front and
+// behind.  The slot is the only record of it: who needs the buffer asks the slot (side_ensure below grows it).
+struct SideBuf {
+    void *base = nullptr;     // start of the front guard (what hipMalloc / hipHostMalloc returned)
+    void *payload = nullptr;  // base + guard
+    void *mapped = nullptr;   // device address of the payload of a mapped host buffer
+    size_t bytes = 0;         // payload
+    bool host = false;        // pinned host memory
+    template <class T> T *ptr() const { return static_cast<T *>(payload); }  // null while the slot is empty
+    template <class T> T *dev() const { return static_cast<T *>(mapped); }
+};
+enum {
+    SB_STAGE,       // staging of host frames (agx_detect, agx_detect_batch)
+    SB_LUMA_D,      // u8 luma of L16 / colour frames, computed on the device ...
+    SB_LUMA_H,      // ... and its pinned host copy
+    SB_CODES,       // the device tail: the family's code list
+    SB_TAGS,        // mapped pinned [tail_frames][tail_tag_cap] agx_tag
+    SB_TAIL_TABLE,  // mapped pinned [tail_frames][4]: count, status, ticks, saddles | seeds << 16
+    SB_DTAGS,       // agx_detect_batch_enqueue_to: the same pair in device memory, [dtail_frames][dtail_tag_cap] ...
+    SB_DTABLE,      // ... and [dtail_frames][4]
+    SB_FETCH_LUMA,  // agx_detect_batch_fetch: pinned luma planes of the frames the host tail takes
+    SB_FRONT,       // k_front_luma's integer luma plane of a batch in one of the layouts AGX_LA8 .. AGX_RGBA16
+    SB_RESP_STORE,  // option "store_response": the [n_frames][H][W] planes K1's parity-test instantiation writes
+    SB_DBG_RESP,    // agx_debug_fetch(AGX_DBG_RESP_RECOMPUTED): one plane
+    SB_COUNT
+};
+}  // namespace agx
+
+struct agx_detector {
+    int family = AGX_T36H11;
+    agx::FamilyInfo fam{};
+    agx_params params{};
+    int device = 0;
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;  // what the kernels are enqueued on: own_stream, or the caller's after agx_detector_set_stream
+    agx::RefineConsts rc{};
+    float blur_w[7]{};
+    uint32_t lim_cand = 0, lim_roots = 0, lim_out = 0;
+    int force_generic = 0;
+    int k1_rows = 0;
+    int sparse_path = 0;  // option "sparse_path": 0 = by batch size, 1 = K2 + K3 + K4 (three launches), 2 = k_sparse_frame (one)
+    bool last_sparse_frame = false;  // the last batch ran K1 + K_SPARSE
+    int last_sparse_path = 1;        // 1 three launches, 2 k_sparse_frame alone, 3 k_verify_seeds + k_sparse_frame
+    int n_cus = 0;                   // compute units of the device (hipDeviceProp_t::multiProcessorCount)
+    int dbg = 0;
+    int store_resp = 0;           // option "store_response": K1's parity-test instantiation (writes SB_RESP_STORE)
+    bool resp_stored = false;     // the last batch ran with store_response
+    int ws_W = 0, ws_H = 0;       // geometry the mask plane was last zeroed for
+
+    // workspace (device)
+    agx::ChainArgs args{};
+    size_t cap_frames = 0;        // frames the dense planes hold
+    long long cap_plane = 0;      // pixels per frame the dense planes hold
+    uint32_t alloc_cand = 0, alloc_roots = 0, alloc_out = 0;
+    std::vector<void *> device_allocs;
+    // AGX_REDZONE_BYTES (environment, read when the handle is created; tests only): every workspace
+    // buffer gets this many guard bytes in front and behind, filled with 0xA5; agx_debug_fetch
+    // (AGX_DBG_REDZONES) reports the guard bytes that no longer hold the pattern
+    size_t redzone = 0;
+    std::vector<size_t> alloc_bytes;  // payload bytes per entry of device_allocs
+    // the buffers outside the workspace: the same guard bytes around each; AGX_DBG_REDZONES counts the ones that exist after the
+    // workspace's, in this order
+    agx::SideBuf side[agx::SB_COUNT];
+    // SB_FRONT holds the plane the chain reads instead of the frames; front_src / front_format / front_frames name the batch it
+    // holds, so that to_luma8 is derived from it instead of from the frames again (an 8-bit layout: it IS that plane).  They are
+    // valid only from batch_enqueue_impl to the next enqueue on the handle, which resets them first (format -1: none): whoever
+    // asks for the luma of a batch does so right behind that batch's enqueue, on the same stream
+    const void *front_src = nullptr;
+    int front_format = -1, front_frames = 0;
+    // pinned host mirrors
+    agx::FrameCounters *h_ctr = nullptr;
+    size_t h_ctr_frames = 0;
+    uint32_t *h_total = nullptr;
+    float *h_out = nullptr;
+    size_t h_out_records = 0;
+    float *d_out_internal = nullptr;  // workspace copy of args.out
+    float *h_out_dev = nullptr;       // device address of h_out (mapped pinned memory): a single frame's list is written there directly
+    bool out_in_host = false;         // last batch's compact output went straight to h_out
+    uint32_t *h_table = nullptr, *h_table_dev = nullptr;  // mapped pinned [frames + 1][4]: per frame count, offset, status, clusters (k_publish / the single frame's k_rare)
+    size_t h_table_rows = 0;
+    size_t mask_words = 0;
+    bool external_out = false;       // last batch wrote into caller-owned device memory
+
+    // two counter sets used alternately: the last kernel of a batch clears the other set, so only a
+    // batch that finds its set not known to be clear pays a memset
+    agx::FrameCounters *d_ctr[2] = {nullptr, nullptr};
+    size_t ctr_cleared[2] = {0, 0};  // records of the set known to be zero (0 = in use / unknown)
+    int ctr_cur = 0;
+
+    bool enqueued = false;
+    int profiling = 0;  // 0 off, 1 = K1 only, 2 = every kernel
+    int prof_stride = 1;        // level 1: time the selected kernel of every prof_stride-th batch only
+    int prof_kernel = agx::K_BLUR_HESSIAN;  // level 1: which kernel (option "profile_kernel", default the blur kernel)
+    uint64_t prof_batches = 0;  // batches enqueued while profiling
+    std::vector<agx::EventPair> pending_events;
+    std::vector<hipEvent_t> free_events;
+    double prof_ms[agx::K_COUNT]{};
+    uint64_t prof_launches[agx::K_COUNT]{};
+
+    // agx_detect_batch: the next chunk's upload runs on a stream of its own under the current chunk's chain and fetch
+    hipStream_t upload_streams[AGX_UPLOAD_STREAMS] = {nullptr, nullptr, nullptr};  // one per staging slot, all or none
+    bool upload_streams_ready = false;
+    agx::TailWorkers *tail_workers = nullptr;  // option "tail_threads" > 1: one frame's board search on several threads
+    int tail_threads = 1;
+    agx::WorkerPool *pool = nullptr;  // agx_detect_batch: worker threads of the host tail
+    int pool_threads = 0;
+    std::vector<agx_saddle> scratch_saddles;  // host staging of agx_detect / agx_detect_planes (reused)
+
+    // option "device_tail": agx_detect_batch's board search + decode on the device (tail_kernels.hip); frames the kernel
+    // hands back (TAIL_UNCERTAIN / TAIL_CAPACITY) take the host tail
+    int device_tail = -1;  // -1: by the batch's size, where this process's atan2f is the routine the kernel restates; 0 off; 1 on
+    bool tail_ready = false;        // code list on the device and the kernel's attributes set for this device: all or nothing
+    int tail_debug_band_mdeg = 0;   // option "tail_debug_band" (tests of the hand-back path), thousandths of a degree
+    size_t tail_frames = 0, dtail_frames = 0;      // layout of SB_TAGS + SB_TAIL_TABLE and of SB_DTAGS + SB_DTABLE: rows ...
+    uint32_t tail_tag_cap = 0, dtail_tag_cap = 0;  // ... and tags per row (0: the pair does not exist)
+    int last_tail_frames = 0, last_tail_fallbacks = 0, last_tail_uncertain = 0;  // of the last agx_detect_batch call
+    agx::DetectPending detect;          // agx_detect_batch_enqueue / _to: the batch agx_detect_batch_fetch resolves
+
+    std::string last_error;
+};
+
+namespace agx {
+int fail(agx_detector *d, int status, const std::string &msg);  // sets agx_last_error, returns status
+// The payload of slot `which`, at least `bytes` long, or nullptr (the slot is then empty).  kind: 0 device, 1 pinned host,
+// 2 pinned host mapped into the device (dev() = its device address).  A slot that is large enough is returned as it is;
+// otherwise the handle's stream is waited for first -- work in flight may still read the buffer about to be freed -- and the
+// slot is freed and allocated again: whatever pointed into it is void.
+// DetectPending::d_luma and args.frames point into SB_LUMA_D / SB_FRONT from an agx_detect_batch_enqueue to its fetch.  Those
+// two slots are grown only behind an enqueue of the chain (batch_enqueue_impl; chunk_luma8 and agx_detect, which follow their
+// own enqueue), and every such enqueue resets `detect` and front_format first; the fetch itself grows SB_FETCH_LUMA only.
+void *side_ensure(agx_detector *d, int which, size_t bytes, int kind);
+// Two slots that are only of use together (SB_LUMA_D + SB_LUMA_H, SB_TAGS + SB_TAIL_TABLE, SB_DTAGS + SB_DTABLE): both as
+// asked for, or both empty
+bool side_ensure_pair(agx_detector *d, int a, size_t bytes_a, int kind_a, int b, size_t bytes_b, int kind_b);
+void side_free(agx_detector *d, int which);
+// the last batch's compact list in the detector's pinned host mirror (valid until the next enqueue; frame f's list =
+// counts[f] records from offsets[f]) + per-frame status (AGX_ERR_CAPACITY: a device-side list of the frame overflowed, its
+// count is 0); waits for the device
+int fetch_compact(agx_detector *det, const agx_saddle **records, uint32_t *counts, uint32_t *offsets, int *status);
+// Wait for whatever is enqueued and forget it (an error path between enqueue and fetch).
+void abandon_batch(agx_detector *det);
+// disagreements between this process's atan2f and the routine the device tail restates (libm_f32.h), checked once per process
+// on 2^20 operand pairs: the device tail is offered only where there are none
+uint64_t libm_check_once();
+// detect over a batch in device memory, stream-ordered (detect_batch.cpp)
 int detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
                         size_t frame_stride_bytes, int format, uint32_t cap_per_frame, bool to_device, agx_tag *d_tags,
                         uint32_t *d_counts, int *d_status);
 int detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads);
-}
-extern "C" agx::DetectPending *agx_internal_detect_pending(agx_detector *det);
+}  // namespace agx

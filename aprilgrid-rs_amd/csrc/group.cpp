@@ -326,7 +326,7 @@ int agx_group_saddles_enqueue(agx_group *g, const void *const *d_frames, int fra
         if (rc) return gfail(g, rc, std::string("rank ") + std::to_string(r) + ": " + agx_last_error(g->dets[r]));
     }
     // the one exchange step: gather the slabs on the root device, stream-ordered behind the chains
-    hipStream_t root = (hipStream_t)agx_internal_stream(g->dets[0]);
+    hipStream_t root = g->dets[0]->stream;
     GHIP(g, hipSetDevice(g->devices[0]));
     if (g->n == 1 && g->rccl_bound) {
         // A group of one under AGX_GROUP_RCCL_SELF=1 (test switch): the root's own slabs take the library's path -- a send
@@ -349,7 +349,7 @@ int agx_group_saddles_enqueue(agx_group *g, const void *const *d_frames, int fra
     if (g->n > 1 && g->rccl_bound) {
         int e = g->rccl.GroupStart();
         for (int r = 1; r < g->n && e == 0; ++r) {
-            hipStream_t st = (hipStream_t)agx_internal_stream(g->dets[r]);
+            hipStream_t st = g->dets[r]->stream;
             e = g->rccl.Send(g->d_table[r], tab_bytes, kNcclUint8, 0, g->comms[r], st);
             if (e == 0) e = g->rccl.Send(g->d_saddles[r], sad_bytes, kNcclUint8, 0, g->comms[r], st);
             if (e == 0) e = g->rccl.Recv((char *)g->d_all_table + (size_t)r * tab_bytes, tab_bytes, kNcclUint8, r, g->comms[0], root);
@@ -360,7 +360,7 @@ int agx_group_saddles_enqueue(agx_group *g, const void *const *d_frames, int fra
             return gfail(g, AGX_ERR_HIP, std::string("RCCL gather: ") + (g->rccl.GetErrorString ? g->rccl.GetErrorString(e ? e : e2) : "error"));
     } else {
         for (int r = 1; r < g->n; ++r) {
-            hipStream_t st = (hipStream_t)agx_internal_stream(g->dets[r]);
+            hipStream_t st = g->dets[r]->stream;
             GHIP(g, hipSetDevice(g->devices[r]));
             GHIP(g, hipMemcpyPeerAsync((char *)g->d_all_table + (size_t)r * tab_bytes, g->devices[0], g->d_table[r], g->devices[r], tab_bytes, st));
             GHIP(g, hipMemcpyPeerAsync((char *)g->d_all_saddles + (size_t)r * sad_bytes, g->devices[0], g->d_saddles[r], g->devices[r], sad_bytes, st));
@@ -381,7 +381,7 @@ int agx_group_saddles_fetch(agx_group *g, agx_saddle *out, uint32_t cap_per_fram
     if (!g->enqueued) return gfail(g, AGX_ERR_STATE, "no batch enqueued");
     const size_t F = (size_t)g->frames_per_rank;
     const size_t sad_bytes = (size_t)g->slab_records * 5 * sizeof(float), tab_bytes = F * 4 * sizeof(uint32_t);
-    hipStream_t root = (hipStream_t)agx_internal_stream(g->dets[0]);
+    hipStream_t root = g->dets[0]->stream;
     GHIP(g, hipSetDevice(g->devices[0]));
     GHIP(g, hipMemcpyAsync(g->h_table, g->d_all_table, (size_t)g->n * tab_bytes, hipMemcpyDeviceToHost, root));
     GHIP(g, hipMemcpyAsync(g->h_saddles, g->d_all_saddles, (size_t)g->n * sad_bytes, hipMemcpyDeviceToHost, root));

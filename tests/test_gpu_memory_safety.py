@@ -271,3 +271,91 @@ def test_a_write_into_a_tail_buffers_guard_is_seen():
     r = d.debug_fetch(0, "redzones")
     assert r["damaged_bytes"] == 2 and r["first_buffer"] == r["buffers"] - 1 and r["first_offset"] == int(addr[1]) + 5, r
     d.close()
+
+
+def test_side_buffers_regrow_under_guards():
+    """Every buffer outside the chain's workspace -- staging, code list, tag rows and frame table (host and device pair), luma
+    planes, the front-end plane, the stored and the recomputed response -- is created on one guarded handle, grown by a larger
+    batch and a larger plane, and used again at the first size.  After every call: no guard byte damaged, no buffer gone, the
+    tags those of a handle on the host tail, and K1's stored response equal to the recomputed one on the interior.  The shapes
+    are the smallest that give tags and saddles: what grows a buffer does not depend on its size."""
+    import torch
+    import aprilgrid_rs_amd as A
+    synth = synth_module()
+    d = _guarded_detector()
+    d.set_option("device_tail", 1)
+    plain = _guarded_detector()  # the same calls without store_response: what the two response buffers add to the count
+    plain.set_option("device_tail", 1)
+    host = A.TagDetector("t36h11", None, device=0)
+    host.set_option("device_tail", 0)
+    cap = 128
+    seen = {id(d): 0, id(plain): 0}
+    cases = {}
+
+    def intact(det, what):
+        r = det.debug_fetch(0, "redzones")
+        assert r["damaged_bytes"] == 0, "%s: %s" % (what, r)
+        assert r["buffers"] >= seen[id(det)], "%s: a buffer is gone: %s, %d before" % (what, r, seen[id(det)])
+        seen[id(det)] = r["buffers"]
+        return r["buffers"]
+
+    def case(n, w, h):
+        """The frames of a shape in every layout, and the comparison handle's tags of them (computed once)."""
+        if (n, w, h) not in cases:
+            dev = synth.render_batch(300, n, w, h, device="cuda")[0]
+            l8 = dev.cpu().numpy()
+            rgba = np.ascontiguousarray(np.stack([l8, l8, l8, np.full_like(l8, 255)], axis=-1))
+            layouts = {"L8": l8, "L16": l8.astype(np.uint16) * 257, "RGBA8": rgba}
+            ref = {}
+            for name, frames in layouts.items():
+                rc, out, cnt, st = host.detect_batch_raw(frames, n_threads=2, cap=cap)
+                assert rc == 0 and (st == 0).all() and cnt.min() > 0, (name, rc, st, cnt)
+                ref[name] = (out, cnt)
+            cases[(n, w, h)] = (dev, layouts, ref)
+        return cases[(n, w, h)]
+
+    def same_tags(out, cnt, ref, what):
+        assert np.array_equal(np.asarray(cnt, np.uint32), ref[1]), what
+        for f in range(len(cnt)):
+            assert out[f, : cnt[f]].tobytes() == ref[0][f, : cnt[f]].tobytes(), "%s frame %d" % (what, f)
+
+    def calls(det, n, w, h, with_response):
+        dev, layouts, ref = case(n, w, h)
+        what = "%d frames of %d x %d" % (n, w, h)
+        for name, frames in layouts.items():  # L8: stage, codes, tags, table; L16: the luma pair; RGBA8: the front plane
+            rc, out, cnt, st = det.detect_batch_raw(frames, n_threads=2, cap=cap)
+            assert rc == 0 and (st == 0).all() and det.get_option("last_device_tail_frames") == n, (what, name, rc, st)
+            same_tags(out, cnt, ref[name], "%s %s" % (what, name))
+            intact(det, "%s %s" % (what, name))
+        dev_out = (torch.zeros((n, cap, 9), dtype=torch.int32, device="cuda"), torch.zeros(n, dtype=torch.int32, device="cuda"),
+                   torch.full((n,), -1, dtype=torch.int32, device="cuda"))
+        det.detect_batch_enqueue(dev, cap=cap, out=dev_out)  # the device pair of tag rows and frame table
+        tags, cnt, st = det.detect_batch_fetch(n_threads=2)
+        assert (st.cpu().numpy() == 0).all(), (what, st)
+        same_tags(tags.cpu().numpy().view(np.uint32).reshape(n, cap, 9), cnt.cpu().numpy(), (ref["L8"][0].view(np.uint32).reshape(n, cap, 9), ref["L8"][1]),
+                  what + " enqueue_to")
+        intact(det, what + " enqueue_to")
+        if not with_response:
+            return
+        det.set_option("store_response", 1)
+        det.saddles_batch_enqueue(dev)
+        res, st = det.saddles_batch_fetch()
+        assert (st == 0).all() and min(len(r) for r in res) > 0, (what, st)
+        for f in (0, n - 1):
+            stored = det.debug_fetch(f, "resp", (h, w))
+            intact(det, what + " stored response")
+            again = det.debug_fetch(f, "resp_recomputed", (h, w))
+            intact(det, what + " recomputed response")
+            assert np.array_equal(stored[1:h - 1, 1:w - 1].view(np.uint32), again[1:h - 1, 1:w - 1].view(np.uint32)), "%s frame %d: response" % (what, f)
+        det.set_option("store_response", 0)
+
+    calls(d, 4, 320, 240, True)
+    first = seen[id(d)]
+    for n, w, h in ((9, 320, 240), (9, 352, 264)):  # more frames, then a larger plane as well
+        calls(d, n, w, h, True)
+        calls(plain, n, w, h, False)
+    assert seen[id(d)] >= seen[id(plain)] + 2, (seen[id(d)], seen[id(plain)])  # SB_RESP_STORE and SB_DBG_RESP are counted
+    calls(d, 4, 320, 240, True)  # the first size again, in the buffers grown since
+    assert seen[id(d)] >= first
+    for det in (d, plain, host):
+        det.close()
