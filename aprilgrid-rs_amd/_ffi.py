@@ -75,6 +75,9 @@ SYMBOLS = {
     "agx_group_saddles_enqueue": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int,
                                             C.c_uint32]),
     "agx_group_saddles_fetch": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
+    "agx_group_detect_enqueue": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int,
+                                           C.c_uint32, C.c_uint32]),
+    "agx_group_detect_fetch": (C.c_int, [_P, _P, _P, _P, C.c_int]),
     "agx_group_last_error": (C.c_char_p, [_P]),
     "agx_detect_from_saddles": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_int, C.c_int, C.c_size_t, _P, C.c_uint32,
                                           C.POINTER(C.c_uint32)]),

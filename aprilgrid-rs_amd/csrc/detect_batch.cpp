@@ -310,6 +310,14 @@ static int publish_tags(agx_detector *det, uint32_t cap_per_frame, agx_tag *d_ta
                                       det->args.n_frames, cap_per_frame, d_tags, d_counts, d_status, det->stream);
     return e == 0 ? AGX_OK : AGX_ERR_HIP;
 }
+// agx_group_detect_enqueue: the same results packed -- frame table + slab in the group's device buffers (k_pack_scan, k_pack_tags)
+static int pack_tags(agx_detector *det, uint32_t cap_per_frame, uint32_t *d_table, agx_tag *d_slab, uint32_t slab_records)
+{
+    if (!det->enqueued || !det->dtail_frames) return AGX_ERR_STATE;
+    const int e = launch_pack_tags(det->side[SB_DTABLE].ptr<uint32_t>(), det->side[SB_DTAGS].ptr<agx_tag>(), det->dtail_tag_cap, det->args.ctr,
+                                   det->args.n_frames, cap_per_frame, d_table, d_slab, slab_records, det->stream);
+    return e == 0 ? AGX_OK : AGX_ERR_HIP;
+}
 // Waits for the device; then the tail's results in mapped pinned host memory, rows *tag_stride apart
 static int fetch_tail(agx_detector *det, const agx_tag **tags, const uint32_t **table, uint32_t *tag_stride)
 {
@@ -885,9 +893,10 @@ static int detect_batch_impl(agx_detector *det, const void *frames, const void *
 // pool for the frames the kernel handed back -- every frame without the device tail -- from the chain's compact saddle lists and
 // the u8 luma of those frames only, copied down from the device.  No frame ever exists in host memory as the caller's pixels.
 int agx::detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
-                             size_t frame_stride_bytes, int format, uint32_t cap_per_frame, bool to_device, agx_tag *d_tags,
-                             uint32_t *d_counts, int *d_status)
+                             size_t frame_stride_bytes, int format, uint32_t cap_per_frame, int kind, agx_tag *d_tags,
+                             uint32_t *d_counts, int *d_status, uint32_t slab_records)
 {
+    const bool to_device = kind != 1;  // the tail's rows and table stay in device memory (SB_DTAGS + SB_DTABLE)
     // option "device_tail" -1 (default) or 1: the device tail wherever this process may use it (no batch-size rule: with the frames
     // on the device there is no upload for the host tail to hide behind); 0, or a tail this process may not use: the host tail
     const int tail_mode = device_tail_mode(det);
@@ -907,7 +916,11 @@ int agx::detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_fram
         luma_frame = (size_t)width * (size_t)height;
     }
     if (!rc && on_device) rc = enqueue_tail(det, d_luma, luma_row, luma_frame, std::max(cap_per_frame, 1u), to_device);
-    if (!rc && to_device) {
+    if (!rc && kind == 3) {
+        // a group's batch: d_counts = the packed frame table [n_frames][4], d_tags = the slab (group.cpp owns both).  Without
+        // the device tail no pack kernel runs: the group fills the table with "handed back" itself
+        if (on_device) rc = pack_tags(det, cap_per_frame, d_counts, d_tags, slab_records);
+    } else if (!rc && to_device) {
         if (on_device) {
             rc = publish_tags(det, cap_per_frame, d_tags, d_counts, d_status);
         } else {  // every frame is the fetch's: until then count 0, AGX_ERR_STATE
@@ -921,7 +934,7 @@ int agx::detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_fram
         return rc;
     }
     DetectPending &p = det->detect;
-    p.kind = to_device ? 2 : 1;
+    p.kind = kind;
     p.device_tail = on_device;
     p.n_frames = n_frames;
     p.width = width;
@@ -936,66 +949,28 @@ int agx::detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_fram
     return AGX_OK;
 }
 
-int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads)
+// The host tail of the frames `back` marks (1 handed back, 2 handed back as uncertain; without the device tail: every frame) of
+// the batch `b` in flight on `det`, on the pool: from the chain's compact saddle lists and those frames' u8 luma, copied down
+// from the device a group at a time.  cnt / st [n] get those frames' counts and statuses (a list of the chain overflowed: 0,
+// AGX_ERR_CAPACITY -- reported, never truncated); their rows go to out + f * cap or, with `rows` (results bound for device
+// arrays), into (*rows)[k] for host_frames[k].  Every tail has finished when this returns, whatever it returns.
+static int resolve_on_host(agx_detector *det, const DetectPending &b, const std::vector<char> &back, WorkerPool *pool, agx_tag *out,
+                           std::vector<uint32_t> &cnt, std::vector<int> &st, std::vector<int> &host_frames,
+                           std::vector<std::vector<agx_tag>> *rows, int &n_fallback, int &n_uncertain)
 {
-    DetectPending &pend = det->detect;
-    const DetectPending b = pend;
-    if ((b.kind == 1 && !counts) || (out && b.cap && !counts)) return AGX_ERR_ARG;  // (the batch stays in flight)
-    if (b.kind == 1 && !out && b.cap) return AGX_ERR_ARG;
-    pend.kind = 0;  // resolved by this call, whatever happens below
     const int n = b.n_frames, W = b.width, H = b.height;
     const uint32_t cap = b.cap;
-    const bool to_dev = b.kind == 2;
     const size_t plane = (size_t)W * (size_t)H;
     hipStream_t stream = det->stream;
     const FamilyInfo *fam = &det->fam;
     const int max_boards = det->params.max_num_of_boards;
-    if (n_threads <= 0) n_threads = agx_host_parallelism();
-    // every frame's result as the host knows it (the device arrays of _enqueue_to get the same), the frames the host tail takes,
-    // and (_enqueue_to) their tag rows until they are copied to the caller's device arrays
-    std::vector<uint32_t> cnt;
-    std::vector<int> st;
-    std::vector<int> host_frames;
-    std::vector<std::vector<agx_tag>> rows;
     std::mutex m;
     std::condition_variable cv;
     int outstanding[2] = {0, 0};  // host tails of the frames in luma slot r not finished yet (guarded by m)
     std::atomic<bool> nomem{false};
-    WorkerPool *pool = nullptr;
-    int rc = AGX_OK, n_fallback = 0, n_uncertain = 0;
+    int rc = AGX_OK;
     try {
         do {
-            if (hipSetDevice(det->device) != hipSuccess) { rc = AGX_ERR_HIP; break; }
-            pool = worker_pool(det, n_threads);
-            if (!pool) { rc = AGX_ERR_ARG; break; }
-            cnt.assign((size_t)n, 0u);
-            st.assign((size_t)n, AGX_OK);
-            std::vector<char> back((size_t)n, b.device_tail ? 0 : 1);  // 1 handed back, 2 handed back as uncertain
-            if (b.device_tail) {
-                const uint32_t *table = nullptr;
-                const agx_tag *tags = nullptr;
-                uint32_t tag_stride = 0;
-                std::vector<uint32_t> dtab;
-                if (to_dev) {  // the 16-byte table entry per frame, not the rows: those are in the caller's arrays already
-                    dtab.resize((size_t)n * 4);
-                    if (hipMemcpyAsync(dtab.data(), det->side[SB_DTABLE].payload, dtab.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-                        hipStreamSynchronize(stream) != hipSuccess) { rc = AGX_ERR_HIP; break; }
-                    table = dtab.data();
-                } else {
-                    rc = fetch_tail(det, &tags, &table, &tag_stride);  // waits for the device
-                    if (rc) break;
-                }
-                for (int f = 0; f < n; ++f) {
-                    const uint32_t ts = table[4 * f + 1], nt = table[4 * f];
-                    if (ts != TAIL_OK) {
-                        back[(size_t)f] = (ts & TAIL_UNCERTAIN) ? 2 : 1;
-                        continue;
-                    }
-                    cnt[(size_t)f] = nt;
-                    if (nt > cap) st[(size_t)f] = AGX_ERR_CAPACITY;  // (the kernel hands such frames back; never truncated either way)
-                    else if (!to_dev && nt) std::memcpy(out + (size_t)f * cap, tags + (size_t)f * tag_stride, (size_t)nt * sizeof(agx_tag));
-                }
-            }
             if (std::none_of(back.begin(), back.end(), [](char c) { return c != 0; })) break;
             // the saddle lists of the frames handed back (and the status of frames whose chain overflowed)
             std::vector<uint32_t> ns((size_t)n), offs((size_t)n);
@@ -1018,7 +993,7 @@ int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, in
             }
             const int n_host = (int)host_frames.size();
             if (!n_host) break;
-            if (to_dev) rows.resize((size_t)n_host);
+            if (rows) rows->resize((size_t)n_host);
             // their u8 luma, copied down a group at a time into one of two pinned slots while the previous group's tails run
             const int G = std::min(n_host, std::max(8, std::min(32, 2 * pool->size())));
             const int n_slots = n_host > G ? 2 : 1;
@@ -1048,12 +1023,12 @@ int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, in
                         const uint8_t *g = slot + (size_t)i * plane;
                         const agx_saddle *sp = records + offs[(size_t)f];
                         const uint32_t n_s = ns[(size_t)f];
-                        pool->submit([=, &cnt, &st, &rows, &nomem, &m, &cv, &outstanding] {
+                        pool->submit([=, &cnt, &st, &nomem, &m, &cv, &outstanding] {
                             try {  // nothing unwinds out of a worker thread: host memory exhaustion becomes the frame's status
                                 const std::vector<agx_tag> &tg = detect_tail_scratch(*fam, max_boards, sp, n_s, g, W, H, (size_t)W);
                                 cnt[(size_t)f] = (uint32_t)tg.size();
                                 if (tg.size() > cap) st[(size_t)f] = AGX_ERR_CAPACITY;
-                                else if (to_dev) rows[(size_t)k].assign(tg.begin(), tg.end());
+                                else if (rows) (*rows)[(size_t)k].assign(tg.begin(), tg.end());
                                 else if (!tg.empty()) std::memcpy(out + (size_t)f * cap, tg.data(), tg.size() * sizeof(agx_tag));
                             } catch (...) {
                                 cnt[(size_t)f] = 0;
@@ -1078,8 +1053,68 @@ int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, in
     } catch (...) {
         rc = AGX_ERR_NOMEM;
     }
-    if (pool) (void)pool->wait();  // every tail (they read the luma slots and the compact list, and write cnt / st / rows)
+    (void)pool->wait();  // every tail (they read the luma slots and the compact list, and write cnt / st / rows)
     if (!rc && nomem.load()) rc = AGX_ERR_NOMEM;
+    return rc;
+}
+
+int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads)
+{
+    DetectPending &pend = det->detect;
+    const DetectPending b = pend;
+    if ((b.kind == 1 && !counts) || (out && b.cap && !counts)) return AGX_ERR_ARG;  // (the batch stays in flight)
+    if (b.kind == 1 && !out && b.cap) return AGX_ERR_ARG;
+    pend.kind = 0;  // resolved by this call, whatever happens below
+    const int n = b.n_frames;
+    const uint32_t cap = b.cap;
+    const bool to_dev = b.kind == 2;
+    hipStream_t stream = det->stream;
+    if (n_threads <= 0) n_threads = agx_host_parallelism();
+    // every frame's result as the host knows it (the device arrays of _enqueue_to get the same), the frames the host tail takes,
+    // and (_enqueue_to) their tag rows until they are copied to the caller's device arrays
+    std::vector<uint32_t> cnt;
+    std::vector<int> st;
+    std::vector<int> host_frames;
+    std::vector<std::vector<agx_tag>> rows;
+    int rc = AGX_OK, n_fallback = 0, n_uncertain = 0;
+    try {
+        do {
+            if (hipSetDevice(det->device) != hipSuccess) { rc = AGX_ERR_HIP; break; }
+            WorkerPool *pool = worker_pool(det, n_threads);
+            if (!pool) { rc = AGX_ERR_ARG; break; }
+            cnt.assign((size_t)n, 0u);
+            st.assign((size_t)n, AGX_OK);
+            std::vector<char> back((size_t)n, b.device_tail ? 0 : 1);  // 1 handed back, 2 handed back as uncertain
+            if (b.device_tail) {
+                const uint32_t *table = nullptr;
+                const agx_tag *tags = nullptr;
+                uint32_t tag_stride = 0;
+                std::vector<uint32_t> dtab;
+                if (to_dev) {  // the 16-byte table entry per frame, not the rows: those are in the caller's arrays already
+                    dtab.resize((size_t)n * 4);
+                    if (hipMemcpyAsync(dtab.data(), det->side[SB_DTABLE].payload, dtab.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                        hipStreamSynchronize(stream) != hipSuccess) { rc = AGX_ERR_HIP; break; }
+                    table = dtab.data();
+                } else {
+                    rc = fetch_tail(det, &tags, &table, &tag_stride);  // waits for the device
+                    if (rc) break;
+                }
+                for (int f = 0; f < n; ++f) {
+                    const uint32_t ts = table[4 * f + 1], nt = table[4 * f];
+                    if (ts != TAIL_OK) {
+                        back[(size_t)f] = (ts & TAIL_UNCERTAIN) ? 2 : 1;
+                        continue;
+                    }
+                    cnt[(size_t)f] = nt;
+                    if (nt > cap) st[(size_t)f] = AGX_ERR_CAPACITY;  // (the kernel hands such frames back; never truncated either way)
+                    else if (!to_dev && nt) std::memcpy(out + (size_t)f * cap, tags + (size_t)f * tag_stride, (size_t)nt * sizeof(agx_tag));
+                }
+            }
+            rc = resolve_on_host(det, b, back, pool, out, cnt, st, host_frames, to_dev ? &rows : nullptr, n_fallback, n_uncertain);
+        } while (false);
+    } catch (...) {
+        rc = AGX_ERR_NOMEM;
+    }
     if (!rc && to_dev) {
         // the host tail's frames into the caller's device arrays, on the detector's stream: rows, count, status (all frames at once
         // where the host tail took every frame)
@@ -1117,4 +1152,39 @@ int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, in
         if (first_bad == AGX_OK) first_bad = st[(size_t)f];
     }
     return first_bad;
+}
+
+// agx_group_detect_fetch, rank by rank: the group has read this rank's packed frame table; back[f] != 0 marks the frames the
+// host tail takes (1, or 2: handed back as uncertain; without the device tail every frame).  Only THEIR rows (out + f * cap),
+// counts and statuses are written: the other frames' are the group's, from the gathered table and slab.  Resolves the batch.
+int agx::group_detect_fetch_impl(agx_detector *det, const char *back_in, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads)
+{
+    DetectPending &pend = det->detect;
+    const DetectPending b = pend;
+    if (b.kind != 3 || !det->enqueued) return AGX_ERR_STATE;  // (something else was enqueued on the borrowed detector since)
+    pend.kind = 0;
+    const int n = b.n_frames;
+    if (n_threads <= 0) n_threads = agx_host_parallelism();
+    std::vector<uint32_t> cnt;
+    std::vector<int> st, host_frames;
+    int rc = AGX_OK, n_fallback = 0, n_uncertain = 0;
+    try {
+        const std::vector<char> back(back_in, back_in + n);
+        cnt.assign((size_t)n, 0u);
+        st.assign((size_t)n, AGX_OK);
+        if (std::any_of(back.begin(), back.end(), [](char c) { return c != 0; })) {
+            WorkerPool *pool = hipSetDevice(det->device) == hipSuccess ? worker_pool(det, n_threads) : nullptr;
+            rc = pool ? resolve_on_host(det, b, back, pool, out, cnt, st, host_frames, nullptr, n_fallback, n_uncertain) : AGX_ERR_HIP;
+        }
+        for (int f = 0; f < n && !rc; ++f)
+            if (back[(size_t)f]) {
+                counts[f] = cnt[(size_t)f];
+                frame_status[f] = st[(size_t)f];
+            }
+    } catch (...) {
+        rc = AGX_ERR_NOMEM;
+    }
+    abandon_batch(det);
+    set_tail_stats(det, b.device_tail ? n : 0, n_fallback, n_uncertain);
+    return rc;
 }

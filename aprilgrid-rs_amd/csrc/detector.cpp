@@ -914,16 +914,17 @@ int agx_saddles_batch_fetch(agx_detector *det, agx_saddle *out, uint32_t cap_per
 
 // detect over a batch in device memory, stream-ordered (csrc/detect_batch.cpp: the chain, k_luma8, the device tail, the fetch)
 static int detect_enqueue_checked(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
-                                  size_t frame_stride_bytes, int format, uint32_t cap_per_frame, bool to_device, agx_tag *d_tags,
-                                  uint32_t *d_counts, int *d_status)
+                                  size_t frame_stride_bytes, int format, uint32_t cap_per_frame, int kind, agx_tag *d_tags,
+                                  uint32_t *d_counts, int *d_status, uint32_t slab_records = 0)
 {
+    const bool to_device = kind == 2;
     if (!det) return AGX_ERR_ARG;
     if (!format_px_bytes(format) || format == AGX_LF32)  // (the decode needs to_luma8: agx_detect_planes for an f32 plane)
         return fail(det, AGX_ERR_FORMAT, "format must be an integer agx_format (AGX_LF32: agx_detect_planes)");
     if (to_device && (!d_counts || !d_status || (!d_tags && cap_per_frame) || (((uintptr_t)d_tags | (uintptr_t)d_counts | (uintptr_t)d_status) & 3)))
         return fail(det, AGX_ERR_ARG, "null or misaligned output buffers");
-    return detect_enqueue_impl(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, cap_per_frame, to_device,
-                               d_tags, d_counts, d_status);
+    return detect_enqueue_impl(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, cap_per_frame, kind,
+                               d_tags, d_counts, d_status, slab_records);
 }
 
 int agx_detect_batch_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
@@ -931,7 +932,7 @@ int agx_detect_batch_enqueue(agx_detector *det, const void *d_frames, int n_fram
 {
     return agx_guard(det, [&]() -> int {
     return detect_enqueue_checked(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, cap_per_frame,
-                                  false, nullptr, nullptr, nullptr);
+                                  1, nullptr, nullptr, nullptr);
     });
 }
 
@@ -941,7 +942,7 @@ int agx_detect_batch_enqueue_to(agx_detector *det, const void *d_frames, int n_f
 {
     return agx_guard(det, [&]() -> int {
     return detect_enqueue_checked(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, cap_per_frame,
-                                  true, d_tags, d_counts, d_status);
+                                  2, d_tags, d_counts, d_status);
     });
 }
 
@@ -950,6 +951,7 @@ int agx_detect_batch_fetch(agx_detector *det, agx_tag *out, uint32_t *counts, in
     return agx_guard(det, [&]() -> int {
     if (!det) return AGX_ERR_ARG;
     if (!det->detect.kind || !det->enqueued) return fail(det, AGX_ERR_STATE, "no agx_detect_batch_enqueue batch in flight");
+    if (det->detect.kind == 3) return fail(det, AGX_ERR_STATE, "the batch in flight is a group's: fetch it with agx_group_detect_fetch");
     det->last_error.clear();
     const int rc = detect_fetch_impl(det, out, counts, frame_status, n_threads);
     if (rc == AGX_ERR_NOMEM) det->last_error = "out of host memory or threads";
@@ -959,6 +961,28 @@ int agx_detect_batch_fetch(agx_detector *det, agx_tag *out, uint32_t *counts, in
 }
 
 }  // extern "C"
+
+int agx::group_detect_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                              size_t frame_stride_bytes, int format, uint32_t cap_per_frame, uint32_t *d_table, agx_tag *d_slab,
+                              uint32_t slab_records)
+{
+    return agx_guard(det, [&]() -> int {
+    return detect_enqueue_checked(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, cap_per_frame,
+                                  3, d_slab, d_table, nullptr, slab_records);
+    });
+}
+
+int agx::group_detect_fetch(agx_detector *det, const char *back, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads)
+{
+    return agx_guard(det, [&]() -> int {
+    det->last_error.clear();
+    const int rc = group_detect_fetch_impl(det, back, out, counts, frame_status, n_threads);
+    if (rc == AGX_ERR_NOMEM) det->last_error = "out of host memory or threads";
+    else if (rc == AGX_ERR_STATE) det->last_error = "the group's batch is no longer the one in flight on this detector";
+    else if (rc != AGX_OK && det->last_error.empty()) det->last_error = agx_status_string(rc);
+    return rc;
+    });
+}
 
 int agx::fetch_compact(agx_detector *det, const agx_saddle **records, uint32_t *counts, uint32_t *offsets, int *status)
 {

@@ -40,14 +40,15 @@ void destroy_tail_workers(TailWorkers *w);
 // agx_detect_batch_enqueue / _enqueue_to: what agx_detect_batch_fetch needs of the batch in flight.  Any enqueue of the chain
 // (either pair, agx_detect_batch, agx_detect) resets it: one batch in flight per handle, the last one enqueued.
 struct DetectPending {
-    int kind = 0;              // 0 none, 1 results to host arrays (agx_detect_batch_enqueue), 2 to the caller's device arrays
+    int kind = 0;              // 0 none, 1 results to host arrays (agx_detect_batch_enqueue), 2 to the caller's device arrays,
+                               // 3 owned by a group (agx_group_detect_enqueue): only agx_group_detect_fetch resolves it
     bool device_tail = false;  // the device tail runs behind the chain; else the fetch runs the host tail on every frame
     int n_frames = 0, width = 0, height = 0;
     uint32_t cap = 0;
     const uint8_t *d_luma = nullptr;  // the batch's u8 luma on the device: the L8 frames themselves or the k_luma8 planes
     size_t luma_row = 0, luma_frame = 0;
-    agx_tag *d_tags = nullptr;  // kind 2: [n_frames][cap]
-    uint32_t *d_counts = nullptr;
+    agx_tag *d_tags = nullptr;  // kind 2: [n_frames][cap]; kind 3: the group's tag slab of this rank
+    uint32_t *d_counts = nullptr;  // kind 3: the group's packed frame table [n_frames][4]
     int *d_status = nullptr;
 };
 
@@ -201,8 +202,16 @@ void abandon_batch(agx_detector *det);
 // on 2^20 operand pairs: the device tail is offered only where there are none
 uint64_t libm_check_once();
 // detect over a batch in device memory, stream-ordered (detect_batch.cpp)
+// kind: DetectPending::kind (1, 2 or 3; 3: d_counts = the packed frame table, d_tags = the slab of slab_records records)
 int detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
-                        size_t frame_stride_bytes, int format, uint32_t cap_per_frame, bool to_device, agx_tag *d_tags,
-                        uint32_t *d_counts, int *d_status);
+                        size_t frame_stride_bytes, int format, uint32_t cap_per_frame, int kind, agx_tag *d_tags,
+                        uint32_t *d_counts, int *d_status, uint32_t slab_records);
 int detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads);
+int group_detect_fetch_impl(agx_detector *det, const char *back, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads);
+// What group.cpp calls for rank r's share of a detect batch (detector.cpp: the entry points' argument checks and guard around
+// the two functions above).  After the enqueue det->detect.device_tail says whether the pack kernel ran.
+int group_detect_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                         size_t frame_stride_bytes, int format, uint32_t cap_per_frame, uint32_t *d_table, agx_tag *d_slab,
+                         uint32_t slab_records);
+int group_detect_fetch(agx_detector *det, const char *back, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads);
 }  // namespace agx

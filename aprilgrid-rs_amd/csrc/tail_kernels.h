@@ -53,6 +53,20 @@ int launch_board_tail(const TailArgs &t, void *stream);
 // handed back to the host tail, which agx_detect_batch_fetch fills in); ctr = the chain's counters of the batch.  hipError_t.
 int launch_publish_tags(const uint32_t *table, const agx_tag *tags, uint32_t tag_stride, const FrameCounters *ctr, int n_frames,
                         uint32_t cap, agx_tag *d_tags, uint32_t *d_counts, int *d_status, void *stream);
+// agx_group_detect_enqueue: flags word of a packed frame table entry {count, offset, status, flags}
+enum : uint32_t {
+    PACK_HANDED_BACK = 1u,  // the device tail handed the frame back: count 0, AGX_ERR_STATE until the fetch has run the host tail
+    PACK_UNCERTAIN = 2u,    // ... because of an angle inside its guard band (TAIL_UNCERTAIN)
+    PACK_SLAB_FULL = 4u     // the frame's rows would cross the end of the slab: AGX_ERR_CAPACITY, the true count, no row
+};
+// The same inputs as launch_publish_tags, packed instead of laid out per frame: d_table[f] = {count, offset, status, flags}
+// (16 bytes; status = the agx_status k_publish_tags reports), the rows of the AGX_OK frames back to back in frame order in
+// d_slab[slab_records] -- offset = the exclusive prefix sum over the frames before f of the rows they hold (a frame that is not
+// AGX_OK holds none).  A frame whose rows would end beyond slab_records is PACK_SLAB_FULL and still counts in the sum, so every
+// frame behind it is too: the first overflow closes the slab, and a frame's offset depends only on the frames before it.
+// d_table must be 16-byte aligned; n_frames <= 65535.  hipError_t.
+int launch_pack_tags(const uint32_t *table, const agx_tag *tags, uint32_t tag_stride, const FrameCounters *ctr, int n_frames,
+                     uint32_t cap, uint32_t *d_table, agx_tag *d_slab, uint32_t slab_records, void *stream);
 int init_tail_kernels();  // per-device kernel attributes (current device); hipError_t
 
 }  // namespace agx

@@ -1479,7 +1479,96 @@ __global__ void __launch_bounds__(256) k_publish_tags(const uint32_t *table, con
     }
 }
 
+// agx_group_detect_enqueue: the same per-frame rule as k_publish_tags, but the rows of the AGX_OK frames go back to back into a
+// slab, in frame order, so that the gather moves tags and not [F][cap] rows.  Two launches: k_pack_scan, ONE workgroup of 16
+// waves, writes the frame table {count, offset, status, flags} -- offset = exclusive prefix sum of the rows the frames before
+// hold, in chunks of 1024 frames with a running carry: a wave scan by __shfl_up, the 16 wave totals through LDS --; then
+// k_pack_tags copies a frame's rows per wave, as k_publish_tags does.  (One launch with the scan redone by every workgroup
+// reads F / 2 table entries per workgroup on average: nothing at F = 256, 2^29 entry reads at the F = 65 535 a batch may have.)
+// A frame whose rows would end beyond slab_records is PACK_SLAB_FULL: AGX_ERR_CAPACITY, its true count, no row.  It still counts
+// in the sum, so the offsets of all frames behind it lie beyond the slab too: the first overflow closes the slab, and what a
+// frame reports depends only on the frames before it.
+__global__ void __launch_bounds__(1024) k_pack_scan(const uint32_t *table, const FrameCounters *ctr, int n_frames, uint32_t cap,
+                                                    uint32_t tag_stride, uint32_t slab_records, uint4 *d_table)
+{
+    __shared__ uint32_t wave_sum[16];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // rows of the chunks before this one.  A frame holds at most min(cap, tag_stride) rows and tag_stride <= 128 (enqueue_tail
+    // clamps the tail's tag capacity), so 65 535 frames sum to < 2^23: neither carry nor off + rows can wrap
+    uint32_t carry = 0;
+    for (int base = 0; base < n_frames; base += 1024) {
+        const int f = base + tid;
+        uint32_t count = 0, rows = 0, flags = 0;
+        int status = AGX_OK;
+        if (f < n_frames) {
+            const uint32_t nt = table[4 * f], st = table[4 * f + 1];
+            if (ctr[f].flags & (FLAG_CAND_OVERFLOW | FLAG_ROOT_OVERFLOW | FLAG_OUT_OVERFLOW)) {
+                status = AGX_ERR_CAPACITY;
+            } else if (st != TAIL_OK) {
+                status = AGX_ERR_STATE;
+                flags = PACK_HANDED_BACK | ((st & TAIL_UNCERTAIN) ? PACK_UNCERTAIN : 0u);
+            } else if (nt > cap || nt > tag_stride) {  // (TAIL_OK: nt <= the tail's tag_cap <= tag_stride; were it not, no row is
+                status = AGX_ERR_CAPACITY;             // reported rather than rows that were never stored)
+                count = nt;
+            } else {
+                count = nt;
+                rows = nt;
+            }
+        }
+        uint32_t incl = rows;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t v = __shfl_up(incl, (unsigned)d, 64);
+            if (lane >= d) incl += v;
+        }
+        if (lane == 63) wave_sum[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (int w = 0; w < 16; ++w) {
+            const uint32_t s = wave_sum[w];
+            total += s;
+            if (w < wave) before += s;
+        }
+        const uint32_t off = carry + before + incl - rows;
+        if (f < n_frames) {
+            if (status == AGX_OK && off + rows > slab_records) {
+                status = AGX_ERR_CAPACITY;
+                flags = PACK_SLAB_FULL;
+            }
+            d_table[f] = make_uint4(count, off, (uint32_t)status, flags);
+        }
+        carry += total;
+        __syncthreads();  // (before the next chunk's totals overwrite wave_sum)
+    }
+}
+
+__global__ void __launch_bounds__(256) k_pack_tags(const uint4 *d_table, const agx_tag *tags, uint32_t tag_stride, int n_frames,
+                                                   uint32_t slab_records, agx_tag *d_slab)
+{
+    const int f = (int)(blockIdx.x * 4 + (threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
+    if (f >= n_frames) return;
+    const uint4 e = d_table[f];  // {count, offset, status, flags}
+    if (e.z != (uint32_t)AGX_OK || e.x > tag_stride || (unsigned long long)e.y + e.x > slab_records) return;  // (never true of an AGX_OK entry: the scan's rules, held again before the stores)
+    const uint32_t words = e.x * (uint32_t)(sizeof(agx_tag) / 4);
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(tags + (size_t)f * tag_stride);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(d_slab + e.y);
+    for (uint32_t i = (uint32_t)lane; i < words; i += 64u) dst[i] = src[i];
+}
+
 }  // namespace
+
+int launch_pack_tags(const uint32_t *table, const agx_tag *tags, uint32_t tag_stride, const FrameCounters *ctr, int n_frames,
+                     uint32_t cap, uint32_t *d_table, agx_tag *d_slab, uint32_t slab_records, void *stream)
+{
+    if (n_frames <= 0) return (int)hipSuccess;
+    if (n_frames > 65535 || ((uintptr_t)d_table & 15)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(1024), 0, (hipStream_t)stream, table, ctr, n_frames, cap, tag_stride, slab_records,
+                       reinterpret_cast<uint4 *>(d_table));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_pack_tags, dim3((unsigned)((n_frames + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const uint4 *>(d_table), tags, tag_stride, n_frames, slab_records, d_slab);
+    return (int)hipGetLastError();
+}
 
 int launch_publish_tags(const uint32_t *table, const agx_tag *tags, uint32_t tag_stride, const FrameCounters *ctr, int n_frames,
                         uint32_t cap, agx_tag *d_tags, uint32_t *d_counts, int *d_status, void *stream)

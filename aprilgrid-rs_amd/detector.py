@@ -621,6 +621,7 @@ class DetectorGroup:
         self.devices = list(devices)
         self._keep = None
         self._frames_per_rank = 0
+        self._detect = None
 
     def close(self):
         if getattr(self, "_g", None) and self._g.value:
@@ -669,3 +670,46 @@ class DetectorGroup:
         # a frame whose list is merely longer than cap_per_frame reports its length (status -3): fetch again with room
         self.last_counts = counts
         return [out[i, : counts[i]].copy() if status[i] == 0 else out[i, :0].copy() for i in range(n)], status
+
+    def detect_enqueue(self, frames_per_rank, cap=1024, tags_per_frame=0, format=None):
+        """detect() over one contiguous device tensor per rank (as saddles_enqueue; every integer layout, float32 planes are
+        refused): every rank's chain, device tail and tag packing, then the gather of the packed tag slabs to devices[0].
+        Returns immediately; detect_fetch waits.  tags_per_frame: average tags per frame a rank's slab holds (0 = 128)."""
+        assert len(frames_per_rank) == len(self.devices)
+        fmt, bpp = TagDetector._tensor_format(frames_per_rank[0], format)
+        if fmt == _ffi.AGX_LF32:
+            raise AgxError(_ffi.AGX_ERR_FORMAT, "detect takes frames of integer pixels")
+        n, w, h, rs, fs = TagDetector._tensor_geometry(frames_per_rank[0], fmt, bpp)
+        for t in frames_per_rank:
+            assert tuple(t.shape) == tuple(frames_per_rank[0].shape) and t.is_contiguous() and t.is_cuda
+        ptrs = (C.c_void_p * len(frames_per_rank))(*[t.data_ptr() for t in frames_per_rank])
+        self._detect = None
+        self._check(self._lib.agx_group_detect_enqueue(self._g, ptrs, n, w, h, rs, fs, fmt, cap, tags_per_frame))
+        self._keep = list(frames_per_rank)
+        self._frames_per_rank = n
+        self._detect = (n * len(self.devices), cap)
+
+    def detect_fetch_raw(self, n_threads=0):
+        """agx_group_detect_fetch -> (rc, out [N, cap] TAG_DTYPE, counts uint32 [N], status int32 [N]), global frame r*F + f, as
+        TagDetector.detect_batch_fetch_raw.  Nothing is raised for a frame status."""
+        if self._detect is None:
+            raise AgxError(_ffi.AGX_ERR_STATE, "no detect batch enqueued")
+        n, cap = self._detect
+        self._detect = None
+        out = np.zeros((n, cap), TagDetector.TAG_DTYPE)
+        counts = np.zeros(n, np.uint32)
+        status = np.full(n, _ffi.AGX_ERR_STATE, np.int32)
+        rc = self._lib.agx_group_detect_fetch(self._g, out.ctypes.data, counts.ctypes.data, status.ctypes.data, n_threads)
+        self._keep = None
+        if rc not in (_ffi.AGX_OK, _ffi.AGX_ERR_CAPACITY):
+            self._check(rc)
+        return rc, out, counts, status
+
+    def detect_fetch(self, n_threads=0, raise_on_overflow=True):
+        """-> (list of {tag_id: 4x2 corners} per global frame r*F + f, None for a frame that is not AGX_OK; status array)."""
+        rc, out, counts, status = self.detect_fetch_raw(n_threads)
+        if rc != _ffi.AGX_OK and raise_on_overflow:
+            self._check(rc)
+        res = [None if status[i] != 0 else {int(t["id"]): t["xy"].reshape(4, 2).copy() for t in out[i, : counts[i]]}
+               for i in range(len(counts))]
+        return res, status

@@ -177,6 +177,11 @@ extern "C" {
                                      records_per_frame: u32) -> c_int;
     pub fn agx_group_saddles_fetch(group: *mut agx_group, out: *mut agx_saddle, cap_per_frame: u32, counts: *mut u32,
                                    frame_status: *mut c_int) -> c_int;
+    pub fn agx_group_detect_enqueue(group: *mut agx_group, d_frames: *const *const c_void, frames_per_rank: c_int, width: c_int,
+                                    height: c_int, row_stride_bytes: usize, frame_stride_bytes: usize, format: c_int,
+                                    cap_per_frame: u32, tags_per_frame: u32) -> c_int;
+    pub fn agx_group_detect_fetch(group: *mut agx_group, out: *mut agx_tag, counts: *mut u32, frame_status: *mut c_int,
+                                  n_threads: c_int) -> c_int;
     pub fn agx_group_last_error(group: *const agx_group) -> *const c_char;
 
     pub fn agx_profile_enable(det: *mut agx_detector, on: c_int) -> c_int;

@@ -344,6 +344,32 @@ int agx_group_saddles_enqueue(agx_group *group, const void *const *d_frames, int
  * frame_status (sized n_devices*frames_per_rank, as agx_saddles_batch_fetch). */
 int agx_group_saddles_fetch(agx_group *group, agx_saddle *out, uint32_t cap_per_frame, uint32_t *counts,
                             int *frame_status);
+/* detect (src/detector.rs:505-540) over n_devices * frames_per_rank frames, rank r's resident on ITS device at
+ * d_frames[r]; layout and formats as agx_detect_batch_enqueue (every agx_format but AGX_LF32, which is
+ * AGX_ERR_FORMAT).  Enqueues every rank's chain, to_luma8, device tail (where option "device_tail" of the rank's
+ * detector and this process allow it, as agx_detect_batch_enqueue) and the pack kernel -- frame table + the frames'
+ * tag records back to back, in frame order -- and then the gather of the per-rank tables and tag slabs to the root
+ * device, and returns without waiting; the frames must stay in place until agx_group_detect_fetch has returned.
+ * tags_per_frame: average tag records per frame the per-rank slab holds (0 = 128).  AGX_ERR_ARG for more than
+ * 65535 frames per rank, or a slab (frames_per_rank * tags_per_frame records of 36 bytes) of 2^31 bytes or more.
+ * One batch per group is in
+ * flight, of either kind: a later enqueue replaces it; fetching it with the other kind's fetch, or with a borrowed
+ * detector's own agx_detect_batch_fetch / agx_saddles_batch_fetch, is AGX_ERR_STATE. */
+int agx_group_detect_enqueue(agx_group *group, const void *const *d_frames, int frames_per_rank, int width,
+                             int height, size_t row_stride_bytes, size_t frame_stride_bytes, int format,
+                             uint32_t cap_per_frame, uint32_t tags_per_frame);
+/* Wait for the gather; then the frames the device tails handed back (without the device tail: every frame) take the
+ * host tail on their own rank's device data, the ranks in turn, each on n_threads host threads (0 =
+ * agx_host_parallelism()).  Frame f of rank r is global frame r*frames_per_rank + f of out ([n][cap_per_frame] of
+ * the enqueue), counts and frame_status (may be NULL); per frame as agx_detect_batch_fetch -- and AGX_ERR_CAPACITY
+ * with the true count and no row for a frame that found its rank's slab full (agx_group_last_error names the rank,
+ * the frame and the slab; tags_per_frame = the largest count always fits).  Nothing is ever truncated.  Returns the
+ * first non-OK frame status, else AGX_OK.  The batch is resolved by this call: a second fetch, or a fetch with
+ * nothing enqueued, is AGX_ERR_STATE (a NULL group or NULL counts is AGX_ERR_ARG whatever is in flight; the state is
+ * checked next, and only then a NULL out against the cap_per_frame of the batch in flight: AGX_ERR_ARG, the batch
+ * stays in flight).  Afterwards options "last_device_tail_frames" / "_fallbacks" / "_uncertain" of
+ * agx_group_detector(group, r) describe rank r's share of the batch. */
+int agx_group_detect_fetch(agx_group *group, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads);
 /* group == NULL: the reason of this thread's last failed agx_group_create. */
 const char *agx_group_last_error(const agx_group *group);
 
