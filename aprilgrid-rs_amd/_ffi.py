@@ -16,6 +16,9 @@ FORMAT_LAYOUT = {AGX_L8: (1, 1, "u1"), AGX_L16: (2, 1, "u2"), AGX_RGB8: (3, 1, "
                  AGX_LA8: (2, 1, "u1"), AGX_RGBA8: (4, 1, "u1"), AGX_BGR8: (3, 1, "u1"), AGX_BGRA8: (4, 1, "u1"),
                  AGX_RGB8P: (1, 3, "u1"), AGX_LA16: (4, 1, "u2"), AGX_RGB16: (6, 1, "u2"), AGX_RGBA16: (8, 1, "u2")}
 AGX_GATHER_RCCL, AGX_GATHER_PEER = 0, 1
+# rochade_refine of caller-given points (src/detector.rs:194-361): the status of a point, and which plane is refined on
+AGX_POINT_REFINED, AGX_POINT_OUTSIDE, AGX_POINT_NOT_SADDLE, AGX_POINT_MOVED = 0, 1, 2, 3
+AGX_REFINE_BLURRED, AGX_REFINE_PLANE = 0, 1
 AGX_DBG_BLUR, AGX_DBG_RESP, AGX_DBG_MIN, AGX_DBG_CENTERS, AGX_DBG_REFINED = 0, 1, 2, 3, 4
 AGX_N_KERNELS = 5
 
@@ -28,6 +31,13 @@ class Params(C.Structure):
 class SaddleC(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("k", C.c_float), ("theta", C.c_float),
                 ("phi", C.c_float)]
+
+
+class PointC(C.Structure):  # agx_point: one (f32, f32) of initial_corners
+    _fields_ = [("x", C.c_float), ("y", C.c_float)]
+
+
+POINT_DTYPE = [("x", "f4"), ("y", "f4")]  # numpy dtype of agx_point
 
 
 class TagC(C.Structure):
@@ -68,6 +78,11 @@ SYMBOLS = {
     "agx_detect_batch_enqueue_to": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, _P, C.c_uint32,
                                               _P, _P]),
     "agx_detect_batch_fetch": (C.c_int, [_P, _P, _P, _P, C.c_int]),
+    "agx_refine_points_enqueue": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _P, C.c_uint32,
+                                            _P, _P, _P]),
+    "agx_refine_points_fetch": (C.c_int, [_P, _P, _P]),
+    "agx_rochade_refine": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, _P, C.c_uint32, _P, _P,
+                                     C.POINTER(C.c_uint32)]),
     "agx_group_create": (C.c_int, [C.c_int, C.POINTER(Params), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "agx_group_destroy": (None, [_P]),
     "agx_group_size": (C.c_int, [_P]),

@@ -145,6 +145,23 @@ bool plan_k1(ChainArgs &a, int override_rows_per_seg);
 // Enqueue one kernel of the chain on `stream` (hipStream_t as void*).  Returns hipError_t.
 int launch_kernel(int which, const ChainArgs &a, const RefineConsts &rc, void *stream);
 
+// k_refine_points (agx_refine_points_enqueue): rochade_refine (detector.rs:194-361, half_size_patch = 2) of caller-given points
+// on the f32 plane(s) `img` -- the chain's blur planes, or a caller's own.  All pointers are device pointers.
+struct RefinePointsArgs {
+    const float *img;        // frame f's plane at img + f * frame_stride
+    long long frame_stride;  // floats
+    long long pitch;         // floats between rows (>= W)
+    int W, H;
+    int padded;              // at least 3 readable floats behind the last plane (the aligned 16-byte window loads may be used)
+    const float *points;     // [n_frames][points_per_frame] (x, y)
+    uint32_t points_per_frame;
+    const uint32_t *counts;  // [n_frames] points of frame f (capped at points_per_frame), or null: points_per_frame each
+    float *out;              // [n_frames][points_per_frame][5]: x, y, k, theta, phi; five zeros for a rejected point
+    uint32_t *status;        // [n_frames][points_per_frame]: AGX_POINT_*
+};
+// grid (ceil(points_per_frame / 64), n_frames <= 65535), one point per lane; hipError_t
+int launch_refine_points(const RefinePointsArgs &p, const RefineConsts &rc, int n_frames, void *stream);
+
 size_t k5_lds_bytes(const ChainArgs &a);
 
 constexpr size_t WAVE_TIMES_STRIDE = (size_t)1 << 20;  // records per kernel (debug_ablation & 4096)

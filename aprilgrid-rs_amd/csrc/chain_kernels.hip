@@ -29,6 +29,8 @@
 //                       where a component leaves the flood windows, the generic clustering fallback
 //                       (mask -> candidate list -> lock-free union-find -> sums) and its refinement;
 //                       the large-list sort (> 1024 refined records per frame)
+//   k_refine_points     rochade_refine (detector.rs:194-361) of caller-given points, one point per lane, on the
+//                       chain's blur planes or a caller's f32 plane (agx_refine_points_enqueue); not part of the chain
 #include <hip/hip_runtime.h>
 
 #include <map>
@@ -3309,6 +3311,153 @@ int launch_clear_counters(FrameCounters *ctr, size_t n_records, void *stream)
     const size_t n_words = n_records * (sizeof(FrameCounters) / 4);
     const unsigned grid = (unsigned)std::min<size_t>((n_words + 255) / 256, 1024);
     hipLaunchKernelGGL(k_clear_counters, dim3(grid), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<uint32_t *>(ctr), n_words);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// k_refine_points: rochade_refine (detector.rs:194-361, half_size_patch = 2) of CALLER-GIVEN points, one point per
+// lane -- agx_refine_points_enqueue.  The arithmetic is refine_values' from initial_x, initial_y on, restated here
+// so that the chain's kernels compile as they did (tests/test_gpu_refine_points.py holds the two copies together,
+// bit for bit): the 9 x 9 window in two load batches, the 25 running sums in the reference's tap order, the six
+// parameter sums, the 2 x 2 LU with row pivoting, sqrtf / acosf / atan2f.  What differs is around it: the plane has
+// a row pitch (a caller's plane need not be tight, nor 16-byte aligned: VEC = false), every point writes its own
+// slot -- record and status, in input order -- and a point is refused BEFORE anything is converted to int or read:
+// NaN, infinities and coordinates beyond the int range (undefined in the reference: `as i32`, unchecked indexing)
+// are AGX_POINT_OUTSIDE like every point whose window leaves the image.
+// ------------------------------------------------------------------------------------------
+enum : uint32_t { POINT_REFINED = 0u, POINT_OUTSIDE = 1u, POINT_NOT_SADDLE = 2u, POINT_MOVED = 3u };  // AGX_POINT_*
+
+template <bool VEC>
+__device__ __forceinline__ uint32_t refine_point(const RefineConsts &rc, const float *img, size_t pitch, int W, int H, float initial_x,
+                                                 float initial_y, float (&rec)[5])
+{
+    const float rxf = roundf(initial_x), ryf = roundf(initial_y);
+    // :266-274, decided in float: NaN fails every comparison, and what passes converts to int exactly
+    if (!(rxf >= 4.0f && ryf >= 4.0f && rxf <= 1073741824.0f && ryf <= 1073741824.0f)) return POINT_OUTSIDE;
+    const int round_x = (int)rxf, round_y = (int)ryf;
+    if (round_y + 4 >= H || round_x + 4 >= W) return POINT_OUTSIDE;
+    const int wx0 = round_x - 4;
+    const int al = VEC ? (wx0 & 3) : 0;
+    const float *win = img + (size_t)(round_y - 4) * pitch + (wx0 - al);
+    float conv[25];
+#pragma unroll
+    for (int q = 0; q < 25; ++q) conv[q] = 0.0f;
+    float prm[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    constexpr int NQ = VEC ? 3 : 9;  // loads per row: 3 x 16 bytes, or 9 floats
+    typedef float rowload_t __attribute__((ext_vector_type(VEC ? 4 : 1)));
+    rowload_t raw[5][NQ];
+    auto fetch = [&](int first, int n) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k)
+            if (k < n) {
+#pragma unroll
+                for (int e = 0; e < NQ; ++e)
+                    raw[k][e] = *reinterpret_cast<const rowload_t *>(win + (size_t)(first + k) * pitch + (VEC ? 4 * e : e));
+            }
+        asm volatile("" ::: "memory");  // every load of the batch is issued before the first one is waited for
+    };
+    fetch(0, 5);
+#pragma unroll
+    for (int wr = 0; wr < 9; ++wr) {
+        if (wr == 5) fetch(5, 4);
+        float v[9];
+        const int k = wr < 5 ? wr : wr - 5;
+        if (VEC) {
+            // three aligned 16-byte loads cover the 9 floats; shift by the misalignment
+            const rowload_t q0 = raw[k][0], q1 = raw[k][1 % NQ], q2 = raw[k][2 % NQ];
+            const bool s1 = (al & 1) != 0, s2 = (al & 2) != 0;
+            constexpr int L = VEC ? 4 : 1;
+            const float u0 = s1 ? q0[1 % L] : q0[0], u1 = s1 ? q0[2 % L] : q0[1 % L], u2 = s1 ? q0[3 % L] : q0[2 % L], u3 = s1 ? q1[0] : q0[3 % L];
+            const float u4 = s1 ? q1[1 % L] : q1[0], u5 = s1 ? q1[2 % L] : q1[1 % L], u6 = s1 ? q1[3 % L] : q1[2 % L], u7 = s1 ? q2[0] : q1[3 % L];
+            const float u8 = s1 ? q2[1 % L] : q2[0], u9 = s1 ? q2[2 % L] : q2[1 % L], u10 = s1 ? q2[3 % L] : q2[2 % L];
+            v[0] = s2 ? u2 : u0; v[1] = s2 ? u3 : u1; v[2] = s2 ? u4 : u2; v[3] = s2 ? u5 : u3; v[4] = s2 ? u6 : u4;
+            v[5] = s2 ? u7 : u5; v[6] = s2 ? u8 : u6; v[7] = s2 ? u9 : u7; v[8] = s2 ? u10 : u8;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 9; ++e) v[e] = raw[k][e % NQ][0];
+        }
+#pragma unroll
+        for (int r = 0; r < 5; ++r) {
+            const int pr = wr - r;
+            if (pr < 0 || pr > 4) continue;
+#pragma unroll
+            for (int c = 0; c < 5; ++c)
+#pragma unroll
+                for (int pc = 0; pc < 5; ++pc) conv[r * 5 + c] = conv[r * 5 + c] + v[c + pc] * rc.cone[pr * 5 + pc];
+        }
+        if (wr >= 4) {
+            const int r = wr - 4;
+#pragma unroll
+            for (int c = 0; c < 5; ++c)
+#pragma unroll
+                for (int j = 0; j < 6; ++j) prm[j] = prm[j] + rc.pmat[(r * 5 + c) * 6 + j] * conv[r * 5 + c];
+        }
+    }
+    const float a1 = prm[0], a2 = prm[1], a3 = prm[2], a4 = prm[3], a5 = prm[4];
+    const float fxx = 2.0f * a1, fyy = 2.0f * a3, fxy = a2;
+    const float d = fxx * fyy - fxy * fxy;
+    if (!(d < 0.0f)) return POINT_NOT_SADDLE;  // :331-339
+    // find_xy(2a1, a2, a4, a2, 2a3, a5), math_util.rs:5-12: 2x2 LU with row pivoting
+    float x0, y0;
+    {
+        const float A0 = 2.0f * a1, B0 = a2, R0 = -a4;
+        const float A1 = a2, B1 = 2.0f * a3, R1 = -a5;
+        float pa, pb, pr_, qa, qb, qr;
+        if (fabsf(A1) > fabsf(A0)) {
+            pa = A1; pb = B1; pr_ = R1; qa = A0; qb = B0; qr = R0;
+        } else {
+            pa = A0; pb = B0; pr_ = R0; qa = A1; qb = B1; qr = R1;
+        }
+        const float l = qa / pa;
+        const float u22 = qb - l * pb;
+        const float y2 = qr - l * pr_;
+        y0 = y2 / u22;
+        x0 = (pr_ - pb * y0) / pa;
+    }
+    if (!(fabsf(x0) <= 1.0f && fabsf(y0) <= 1.0f)) return POINT_MOVED;  // :342-347
+    const float c5 = (a1 + a3) / 2.0f;
+    const float c4 = (a1 - a3) / 2.0f;
+    const float c3 = a2 / 2.0f;
+    const float k = sqrtf(c4 * c4 + c3 * c3);
+    if (!(fabsf(c5) < k)) return POINT_MOVED;
+    const float PI_F = 3.14159274101257324219f;
+    const float phi = acosf(-c5 / k) / 2.0f / PI_F * 180.0f;
+    const float theta = atan2f(c3, c4) / 2.0f / PI_F * 180.0f;
+    rec[0] = rxf + x0;
+    rec[1] = ryf + y0;
+    rec[2] = k;
+    rec[3] = theta;
+    rec[4] = phi;
+    return POINT_REFINED;
+}
+
+// grid (ceil(points_per_frame / 64), n_frames): point i of frame f reads points[f * ppf + i] and writes record and status
+// [f * ppf + i]; slots at or beyond the frame's count are left alone.
+template <bool VEC>
+__global__ void __launch_bounds__(64) k_refine_points(RefinePointsArgs p, RefineConsts rc)
+{
+    const uint32_t f = blockIdx.y, i = blockIdx.x * 64u + threadIdx.x;
+    uint32_t n = p.points_per_frame;
+    if (p.counts) n = min(p.counts[f], n);
+    if (i >= n) return;
+    const size_t slot = (size_t)f * p.points_per_frame + i;
+    const float x = p.points[2 * slot], y = p.points[2 * slot + 1];
+    float rec[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    const uint32_t st = refine_point<VEC>(rc, p.img + (size_t)f * (size_t)p.frame_stride, (size_t)p.pitch, p.W, p.H, x, y, rec);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) p.out[slot * 5 + q] = st == POINT_REFINED ? rec[q] : 0.0f;
+    p.status[slot] = st;
+}
+
+int launch_refine_points(const RefinePointsArgs &p, const RefineConsts &rc, int n_frames, void *stream)
+{
+    if (n_frames <= 0 || n_frames > 65535 || !p.points_per_frame) return (int)hipErrorInvalidValue;
+    const dim3 grid((p.points_per_frame + 63u) / 64u, (unsigned)n_frames), block(64);
+    // the aligned 16-byte window loads: rows, frames and the plane itself on the 16-byte grid, and (they reach up to three
+    // floats past a window) a plane known to have that much room behind it -- the chain's blur plane, never a caller's
+    const bool vec = p.padded && (p.pitch & 3) == 0 && (p.frame_stride & 3) == 0 && ((uintptr_t)p.img & 15) == 0;
+    if (vec) hipLaunchKernelGGL((k_refine_points<true>), grid, block, 0, (hipStream_t)stream, p, rc);
+    else hipLaunchKernelGGL((k_refine_points<false>), grid, block, 0, (hipStream_t)stream, p, rc);
     return hipGetLastError();
 }
 

@@ -454,6 +454,31 @@ int enqueue_chain(agx_detector *d)
     return AGX_OK;
 }
 
+// The front of the chain alone -- K1 and whatever ran before it -- for agx_refine_points_enqueue on the frames' blur planes.
+// K1 publishes the frames' minima into a counter set that nothing clears afterwards (k_rare / k_sparse_frame do not run):
+// neither set is known to be clear then, and the next batch of any kind clears its own.
+int enqueue_blur_only(agx_detector *d)
+{
+    ChainArgs &a = d->args;
+    const int p = d->ctr_cur ^ 1;
+    const size_t need = (size_t)a.n_frames + 1;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(d->stream, &cap);
+    if (cap == hipStreamCaptureStatusActive) {  // (as enqueue_chain: a replayed graph clears its own set every time)
+        HIP_TRY(d, (hipError_t)launch_clear_counters(d->d_ctr[p], need, d->stream));
+    } else if (d->ctr_cleared[p] < need) {
+        HIP_TRY(d, hipMemsetAsync(d->d_ctr[p], 0, need * sizeof(FrameCounters), d->stream));
+    }
+    d->ctr_cleared[0] = d->ctr_cleared[1] = 0;
+    a.ctr = d->d_ctr[p];
+    a.ctr_next = d->d_ctr[p ^ 1];
+    a.total_out = &a.ctr[a.n_frames].min_key_inv;
+    hipError_t e = (hipError_t)launch_kernel(K_BLUR_HESSIAN, a, d->rc, d->stream);
+    if (e != hipSuccess) return fail(d, AGX_ERR_HIP, std::string("launch ") + kKernelNames[K_BLUR_HESSIAN] + ": " + hipGetErrorString(e));
+    d->ctr_cur = p;
+    return AGX_OK;
+}
+
 int frame_status_of(const FrameCounters &c, uint32_t cap_per_frame)
 {
     if (c.flags & (FLAG_CAND_OVERFLOW | FLAG_ROOT_OVERFLOW | FLAG_OUT_OVERFLOW)) return AGX_ERR_CAPACITY;
@@ -727,7 +752,7 @@ int agx_detector_sync(agx_detector *det)
 
 static int batch_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, int width, int height,
                               size_t row_stride_bytes, size_t frame_stride_bytes, int format, void *d_saddles,
-                              uint32_t saddle_capacity, void *d_frame_table)
+                              uint32_t saddle_capacity, void *d_frame_table, bool blur_only = false)
 {
     if (!det || !d_frames || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null frames or n_frames <= 0");
     if (!format_px_bytes(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
@@ -745,6 +770,7 @@ static int batch_enqueue_impl(agx_detector *det, const void *d_frames, int n_fra
     if (format_front(format) && height > 16 * 65535)  // (k_front_luma's grid: 16 rows per workgroup, 65535 workgroups)
         return fail(det, AGX_ERR_ARG, "frames of this format may have at most 1048560 rows");
     det->detect.kind = 0;  // (this batch replaces whatever was in flight, an agx_detect_batch_enqueue's included)
+    det->refine.kind = 0;  // (... and an agx_refine_points_enqueue's)
     det->front_format = -1;
     HIP_TRY(det, hipSetDevice(det->device));
     int rc = ensure_workspace(det, n_frames, width, height);
@@ -811,6 +837,10 @@ static int batch_enqueue_impl(agx_detector *det, const void *d_frames, int n_fra
         det->resp_stored = true;
     }
     if (!plan_k1(a, det->k1_rows)) return fail(det, AGX_ERR_ARG, "unsupported frame geometry");
+    if (blur_only) {  // agx_refine_points_enqueue: nothing of the chain will be there to be fetched
+        det->enqueued = false;
+        return enqueue_blur_only(det);
+    }
     return enqueue_chain(det);
 }
 
@@ -906,6 +936,8 @@ int agx_saddles_batch_fetch(agx_detector *det, agx_saddle *out, uint32_t cap_per
                             int *frame_status)
 {
     return agx_guard(det, [&]() -> int {
+    if (det && det->refine.kind)
+        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_refine_points_enqueue's: fetch it with agx_refine_points_fetch");
     if (det && det->enqueued && det->detect.kind)
         return fail(det, AGX_ERR_STATE, "the batch in flight is agx_detect_batch_enqueue's: fetch it with agx_detect_batch_fetch");
     return saddles_fetch_impl(det, out, cap_per_frame, counts, frame_status);
@@ -950,6 +982,8 @@ int agx_detect_batch_fetch(agx_detector *det, agx_tag *out, uint32_t *counts, in
 {
     return agx_guard(det, [&]() -> int {
     if (!det) return AGX_ERR_ARG;
+    if (det->refine.kind)
+        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_refine_points_enqueue's: fetch it with agx_refine_points_fetch");
     if (!det->detect.kind || !det->enqueued) return fail(det, AGX_ERR_STATE, "no agx_detect_batch_enqueue batch in flight");
     if (det->detect.kind == 3) return fail(det, AGX_ERR_STATE, "the batch in flight is a group's: fetch it with agx_group_detect_fetch");
     det->last_error.clear();
@@ -957,6 +991,175 @@ int agx_detect_batch_fetch(agx_detector *det, agx_tag *out, uint32_t *counts, in
     if (rc == AGX_ERR_NOMEM) det->last_error = "out of host memory or threads";
     else if (rc != AGX_OK && rc != AGX_ERR_CAPACITY && det->last_error.empty()) det->last_error = agx_status_string(rc);
     return rc;
+    });
+}
+
+}  // extern "C"
+
+// ---- rochade_refine of caller-given points (src/detector.rs:194-361) ---------------------------------------------------------
+static int refine_points_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, int width, int height,
+                                      size_t row_stride_bytes, size_t frame_stride_bytes, int format, int image,
+                                      const void *d_points, uint32_t points_per_frame, const uint32_t *d_counts,
+                                      agx_saddle *d_out, uint32_t *d_status)
+{
+    if (!det) return AGX_ERR_ARG;
+    if (!d_frames || !d_points || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null frames, null points or n_frames <= 0");
+    if (!points_per_frame) return fail(det, AGX_ERR_ARG, "points_per_frame must be > 0");
+    if ((d_out == nullptr) != (d_status == nullptr)) return fail(det, AGX_ERR_ARG, "d_out and d_status: both or neither");
+    if (image != AGX_REFINE_BLURRED && image != AGX_REFINE_PLANE) return fail(det, AGX_ERR_ARG, "image must be AGX_REFINE_BLURRED or AGX_REFINE_PLANE");
+    if ((((uintptr_t)d_points | (uintptr_t)d_counts | (uintptr_t)d_out | (uintptr_t)d_status) & 3))
+        return fail(det, AGX_ERR_ARG, "points, counts and result buffers must be 4-byte aligned");
+    if (!format_px_bytes(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
+    if (image == AGX_REFINE_PLANE && format != AGX_LF32) return fail(det, AGX_ERR_FORMAT, "AGX_REFINE_PLANE takes an AGX_LF32 plane");
+    if (width < 1 || height < 1) return fail(det, AGX_ERR_ARG, "width and height must be >= 1");
+    if ((long long)width * height >= (1ll << 30) || width > 65000) return fail(det, AGX_ERR_ARG, "frame too large (>= 2^30 px or wider than 65000)");
+    if (n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
+    const size_t slots = (size_t)n_frames * points_per_frame;
+    if (slots >= ((size_t)1 << 31)) return fail(det, AGX_ERR_ARG, "at most 2^31 - 1 points per batch");
+    const size_t px_bytes = (size_t)format_px_bytes(format);
+    if (row_stride_bytes < (size_t)width * px_bytes || row_stride_bytes > 0x7fffffffu ||
+        (n_frames > 1 && frame_stride_bytes < row_stride_bytes * format_rows(format, height)))
+        return fail(det, AGX_ERR_ARG, "strides must cover a row / a frame");
+    if (format == AGX_LF32 && ((row_stride_bytes | (n_frames > 1 ? frame_stride_bytes : 0) | (uintptr_t)d_frames) & 3))
+        return fail(det, AGX_ERR_ARG, "f32 pixels must be 4-byte aligned");
+    HIP_TRY(det, hipSetDevice(det->device));
+    // this batch replaces whatever was in flight
+    det->detect.kind = 0;
+    det->refine.kind = 0;
+    det->front_format = -1;
+    det->enqueued = false;
+    RefinePointsArgs p{};
+    p.W = width;
+    p.H = height;
+    const bool any_window = width >= 9 && height >= 9;  // (a smaller frame is valid input: all its points are AGX_POINT_OUTSIDE)
+    if (image == AGX_REFINE_PLANE || !any_window) {
+        p.img = (const float *)d_frames;  // (!any_window: never read)
+        p.pitch = (long long)(row_stride_bytes / 4);
+        p.frame_stride = (long long)(frame_stride_bytes / 4);
+        p.padded = 0;
+    } else {
+        // the front end and K1 as they are: the blur planes of the workspace, tight [n_frames][H][W]
+        const int rc = batch_enqueue_impl(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, nullptr, 0,
+                                          nullptr, true);
+        if (rc) return rc;
+        p.img = det->args.blur;
+        p.pitch = width;
+        p.frame_stride = det->args.plane;
+        p.padded = 1;  // (ensure_workspace: 16 floats behind the last plane)
+    }
+    if (!d_out) {
+        if (!side_ensure_pair(det, SB_REFINE_OUT, slots * sizeof(agx_saddle), 0, SB_REFINE_STATUS, slots * sizeof(uint32_t), 0))
+            return fail(det, AGX_ERR_HIP, "hipMalloc: refined points");
+        d_out = det->side[SB_REFINE_OUT].ptr<agx_saddle>();
+        d_status = det->side[SB_REFINE_STATUS].ptr<uint32_t>();
+        det->refine.kind = 1;
+    } else {
+        det->refine.kind = 2;
+    }
+    p.points = static_cast<const float *>(d_points);
+    p.points_per_frame = points_per_frame;
+    p.counts = d_counts;
+    p.out = reinterpret_cast<float *>(d_out);
+    p.status = d_status;
+    hipError_t e = (hipError_t)launch_refine_points(p, det->rc, n_frames, det->stream);
+    if (e != hipSuccess) {
+        det->refine.kind = 0;
+        return fail(det, AGX_ERR_HIP, std::string("k_refine_points: ") + hipGetErrorString(e));
+    }
+    det->refine.n_frames = n_frames;
+    det->refine.points_per_frame = points_per_frame;
+    det->refine.d_counts = d_counts;
+    return AGX_OK;
+}
+
+static int refine_points_fetch_impl(agx_detector *det, agx_saddle *out, uint32_t *status)
+{
+    if (!det) return AGX_ERR_ARG;
+    const RefinePending b = det->refine;
+    if (!b.kind) return fail(det, AGX_ERR_STATE, "no agx_refine_points_enqueue batch in flight");
+    if (b.kind == 1 && (!out || !status)) return fail(det, AGX_ERR_ARG, "null output");  // (the batch stays in flight)
+    HIP_TRY(det, hipSetDevice(det->device));
+    det->refine.kind = 0;  // resolved by this call, whatever it returns
+    const size_t slots = (size_t)b.n_frames * b.points_per_frame;
+    if (b.kind == 1) {
+        const agx_saddle *d_out = det->side[SB_REFINE_OUT].ptr<agx_saddle>();
+        const uint32_t *d_status = det->side[SB_REFINE_STATUS].ptr<uint32_t>();
+        if (!b.d_counts) {
+            HIP_TRY(det, hipMemcpyAsync(out, d_out, slots * sizeof(agx_saddle), hipMemcpyDeviceToHost, det->stream));
+            HIP_TRY(det, hipMemcpyAsync(status, d_status, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, det->stream));
+        } else {  // only the slots the kernel wrote reach the caller's arrays: by way of a host copy of everything + the counts
+            std::vector<uint32_t> &h = det->refine_host;
+            h.resize(slots * 6 + (size_t)b.n_frames);
+            HIP_TRY(det, hipMemcpyAsync(h.data(), d_out, slots * sizeof(agx_saddle), hipMemcpyDeviceToHost, det->stream));
+            HIP_TRY(det, hipMemcpyAsync(h.data() + slots * 5, d_status, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, det->stream));
+            HIP_TRY(det, hipMemcpyAsync(h.data() + slots * 6, b.d_counts, (size_t)b.n_frames * sizeof(uint32_t), hipMemcpyDeviceToHost, det->stream));
+        }
+    }
+    HIP_TRY(det, hipStreamSynchronize(det->stream));
+    harvest_events(det);
+    if (b.kind == 1 && b.d_counts) {
+        const std::vector<uint32_t> &h = det->refine_host;
+        for (int f = 0; f < b.n_frames; ++f) {
+            const size_t n = std::min(h[slots * 6 + (size_t)f], b.points_per_frame), s0 = (size_t)f * b.points_per_frame;
+            if (!n) continue;
+            std::memcpy(out + s0, h.data() + s0 * 5, n * sizeof(agx_saddle));
+            std::memcpy(status + s0, h.data() + slots * 5 + s0, n * sizeof(uint32_t));
+        }
+    }
+    return AGX_OK;
+}
+
+extern "C" {
+
+int agx_refine_points_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                              size_t frame_stride_bytes, int format, int image, const void *d_points, uint32_t points_per_frame,
+                              const uint32_t *d_counts, agx_saddle *d_out, uint32_t *d_status)
+{
+    return agx_guard(det, [&]() -> int {
+    return refine_points_enqueue_impl(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, image,
+                                      d_points, points_per_frame, d_counts, d_out, d_status);
+    });
+}
+
+int agx_refine_points_fetch(agx_detector *det, agx_saddle *out, uint32_t *status)
+{
+    return agx_guard(det, [&]() -> int { return refine_points_fetch_impl(det, out, status); });
+}
+
+int agx_rochade_refine(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes, int format, int image,
+                       const void *points, uint32_t n_points, agx_saddle *out, uint32_t *status, uint32_t *n_refined)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    if (!pixels || !n_refined || (n_points && (!points || !out || !status))) return fail(det, AGX_ERR_ARG, "null argument");
+    if (image != AGX_REFINE_BLURRED && image != AGX_REFINE_PLANE) return fail(det, AGX_ERR_ARG, "image must be AGX_REFINE_BLURRED or AGX_REFINE_PLANE");
+    if (!format_px_bytes(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
+    if (image == AGX_REFINE_PLANE && format != AGX_LF32) return fail(det, AGX_ERR_FORMAT, "AGX_REFINE_PLANE takes an AGX_LF32 plane");
+    if (width < 1 || height < 1) return fail(det, AGX_ERR_ARG, "width and height must be >= 1");
+    const size_t row_bytes = (size_t)width * format_px_bytes(format);
+    if (row_stride_bytes < row_bytes) return fail(det, AGX_ERR_ARG, "row stride smaller than a row");
+    if (image == AGX_REFINE_PLANE && (row_stride_bytes & 3)) return fail(det, AGX_ERR_ARG, "the row stride of an f32 plane must be a multiple of 4 bytes");
+    *n_refined = 0;
+    if (!n_points) return AGX_OK;  // (the reference: an empty Vec)
+    HIP_TRY(det, hipSetDevice(det->device));
+    const size_t pitch = (row_bytes + 3) & ~(size_t)3;
+    const size_t rows = format_rows(format, height);
+    const size_t need = pitch * rows;
+    void *d_stage = side_ensure(det, SB_STAGE, need, 0);
+    if (!d_stage) return fail(det, AGX_ERR_HIP, "hipMalloc: staging buffer");
+    agx_point *d_points = static_cast<agx_point *>(side_ensure(det, SB_REFINE_POINTS, (size_t)n_points * sizeof(agx_point), 0));
+    if (!d_points) return fail(det, AGX_ERR_HIP, "hipMalloc: points");
+    HIP_TRY(det, hipMemcpy2DAsync(d_stage, pitch, pixels, row_stride_bytes, row_bytes, rows, hipMemcpyHostToDevice, det->stream));
+    HIP_TRY(det, hipMemcpyAsync(d_points, points, (size_t)n_points * sizeof(agx_point), hipMemcpyHostToDevice, det->stream));
+    int rc = refine_points_enqueue_impl(det, d_stage, 1, width, height, pitch, need, format, image, d_points, n_points, nullptr, nullptr,
+                                        nullptr);
+    if (rc) return rc;
+    rc = refine_points_fetch_impl(det, out, status);
+    if (rc) return rc;
+    uint32_t n = 0;
+    for (uint32_t i = 0; i < n_points; ++i) n += status[i] == AGX_POINT_REFINED;
+    *n_refined = n;
+    return AGX_OK;
     });
 }
 

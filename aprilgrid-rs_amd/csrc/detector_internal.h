@@ -52,6 +52,16 @@ struct DetectPending {
     int *d_status = nullptr;
 };
 
+// agx_refine_points_enqueue: what agx_refine_points_fetch needs of the batch in flight.  The third kind of batch on a handle:
+// while it is in flight `enqueued` is false (nothing of the chain is there to be fetched), and every enqueue of the chain
+// resets it.
+struct RefinePending {
+    int kind = 0;  // 0 none, 1 results in SB_REFINE_OUT / SB_REFINE_STATUS (the fetch copies them out), 2 in the caller's device arrays
+    int n_frames = 0;
+    uint32_t points_per_frame = 0;
+    const uint32_t *d_counts = nullptr;  // the caller's per-frame counts (kind 1: the fetch copies only the slots that were written)
+};
+
 struct EventPair {
     hipEvent_t a, b;
     int kernel;
@@ -81,6 +91,9 @@ enum {
     SB_FRONT,       // k_front_luma's integer luma plane of a batch in one of the layouts AGX_LA8 .. AGX_RGBA16
     SB_RESP_STORE,  // option "store_response": the [n_frames][H][W] planes K1's parity-test instantiation writes
     SB_DBG_RESP,    // agx_debug_fetch(AGX_DBG_RESP_RECOMPUTED): one plane
+    SB_REFINE_OUT,     // agx_refine_points_enqueue without caller-owned results: [n_frames][points_per_frame] agx_saddle ...
+    SB_REFINE_STATUS,  // ... and [n_frames][points_per_frame] uint32 (AGX_POINT_*)
+    SB_REFINE_POINTS,  // agx_rochade_refine: the host's points on the device
     SB_COUNT
 };
 }  // namespace agx
@@ -174,6 +187,8 @@ struct agx_detector {
     uint32_t tail_tag_cap = 0, dtail_tag_cap = 0;  // ... and tags per row (0: the pair does not exist)
     int last_tail_frames = 0, last_tail_fallbacks = 0, last_tail_uncertain = 0;  // of the last agx_detect_batch call
     agx::DetectPending detect;          // agx_detect_batch_enqueue / _to: the batch agx_detect_batch_fetch resolves
+    agx::RefinePending refine;          // agx_refine_points_enqueue: the batch agx_refine_points_fetch resolves
+    std::vector<uint32_t> refine_host;  // its host staging when per-frame counts were given (records, statuses, counts)
 
     std::string last_error;
 };

@@ -8,6 +8,7 @@ Same names, argument meaning and error behaviour as the reference where Python a
   TagDetector.refined_saddle_points   src/detector.rs:408-446
   TagDetector.detect                  src/detector.rs:505-540
   TagDetector.detect_kornia           src/detector.rs:478-503
+  TagDetector.rochade_refine          src/detector.rs:194-361 (the crate's pub fn, half_size_patch = 2)
 An image is a numpy array standing for the DynamicImage variants the reference is fed:
 HxW uint8 (ImageLuma8), HxW uint16 (ImageLuma16), HxWx3 uint8 (ImageRgb8); HxWx2 / HxWx4 uint8 (ImageLumaA8, ImageRgba8),
 HxWx2 / HxWx3 / HxWx4 uint16 (ImageLumaA16, ImageRgb16, ImageRgba16).  BGR / BGRA order and channel-first planes (3xHxW uint8)
@@ -147,6 +148,7 @@ class TagDetector:
         self.device = device
         self._batch = None
         self._detect = None  # detect_batch_enqueue's batch: (n, cap, frames kept alive, device outputs or None)
+        self._refine = None  # refine_points_enqueue's batch: (n, points per frame, tensors kept alive, device outputs or None)
 
     new = classmethod(lambda cls, tag_family, optional_detector_params=None, device=0:
                       cls(tag_family, optional_detector_params, device))
@@ -393,6 +395,7 @@ class TagDetector:
         self._check(self._lib.agx_saddles_batch_enqueue(self._h, frames.data_ptr(), n, w, h, rs, fs, fmt))
         self._batch = (n, frames)  # keep the tensor alive until fetched
         self._detect = None
+        self._refine = None
 
     def saddles_batch_enqueue_to(self, frames, out_saddles, frame_table, format=None):
         """Device-resident results: out_saddles float32 [capacity, 5] and frame_table int32
@@ -407,6 +410,7 @@ class TagDetector:
             out_saddles.shape[0], frame_table.data_ptr()))
         self._batch = None
         self._detect = None
+        self._refine = None
 
     def saddles_batch_enqueue_ptr(self, dptr, n, w, h, row_stride, frame_stride, fmt, follow_torch_stream=True):
         """agx_saddles_batch_enqueue on a raw device address (any row / frame stride: a view cut out of a larger allocation).
@@ -419,6 +423,7 @@ class TagDetector:
                                                         fmt))
         self._batch = (n, None)
         self._detect = None
+        self._refine = None
 
     def saddles_batch_fetch(self, cap_per_frame=None, raise_on_overflow=True):
         """-> (list of SADDLE_DTYPE arrays, one per frame; per-frame status array).  cap_per_frame None:
@@ -477,6 +482,7 @@ class TagDetector:
     def _enqueue_detect(self, dptr, n, w, h, row_stride, frame_stride, fmt, cap, out, keep):
         self._batch = None  # (one batch in flight per handle: this one replaces a saddle batch)
         self._detect = None
+        self._refine = None
         if out is None:
             self._check(self._lib.agx_detect_batch_enqueue(self._h, C.c_void_p(dptr), n, w, h, row_stride, frame_stride, fmt, cap))
         else:
@@ -534,6 +540,78 @@ class TagDetector:
         """tags int32 [..., cap, 9] of detect_batch_enqueue(out=...) -> (ids int32 [..., cap], corners float32 [..., cap, 4, 2])."""
         import torch
         return tags[..., 0], tags[..., 1:].contiguous().view(torch.float32).reshape(*tags.shape[:-1], 4, 2)
+
+    # ---- rochade_refine of caller-given points (src/detector.rs:194-361) ------------------
+    _REFINE_IMAGE = {"blurred": _ffi.AGX_REFINE_BLURRED, "plane": _ffi.AGX_REFINE_PLANE}
+
+    def _refine_image(self, image):
+        if image not in self._REFINE_IMAGE:
+            raise AgxError(_ffi.AGX_ERR_ARG, "image must be 'blurred' or 'plane', got %r" % (image,))
+        return self._REFINE_IMAGE[image]
+
+    def rochade_refine(self, img, points, image="blurred", format=None):
+        """detector::rochade_refine(image_input, initial_corners, 2) on a host image: points = n (x, y) pairs.
+        image="blurred": img is an image of any format and is refined on its sigma = 1.5 blur, as refined_saddle_points does;
+        image="plane": img is an HxW float32 plane and IS image_input.  -> (records [n] SADDLE_DTYPE, status [n] uint32
+        AGX_POINT_*), in input order; a rejected point's record is zero.  The reference's Vec<Saddle> is
+        records[status == AGX_POINT_REFINED]."""
+        a, fmt, stride = _image_args(img, format)
+        h, w = _image_hw(a, fmt)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+        n = pts.shape[0]
+        out = np.zeros(n, SADDLE_DTYPE)
+        status = np.zeros(n, np.uint32)
+        n_refined = C.c_uint32(0)
+        self._batch = self._detect = self._refine = None
+        self._check(self._lib.agx_rochade_refine(self._h, a.ctypes.data, w, h, stride, fmt, self._refine_image(image), pts.ctypes.data, n,
+                                                 out.ctypes.data, status.ctypes.data, C.byref(n_refined)))
+        assert n_refined.value == int((status == _ffi.AGX_POINT_REFINED).sum())
+        return out, status
+
+    def refine_points_enqueue(self, frames, points, counts=None, out=None, status=None, image="blurred", format=None):
+        """rochade_refine over a batch on this detector's GPU, stream-ordered behind torch's current stream; returns immediately.
+        frames and format= as saddles_batch_enqueue (image="plane": [N,H,W] float32, refined as it is); points: float32 [N,P,2]
+        (x, y); counts: optional int32 [N], the points of frame f (at most P; slots beyond are not written); out float32 [N,P,5]
+        and status int32 [N,P]: device-resident results (both or neither) -- without them refine_points_fetch returns arrays."""
+        import torch
+        fmt, bpp = self._tensor_format(frames, format)
+        n, w, h, rs, fs = self._tensor_geometry(frames, fmt, bpp)
+        dev = frames.device
+
+        def tensor(t, dtype, shape, what):
+            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == shape and t.device == dev):
+                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s tensor %s on the frames' device" % (what, dtype, shape))
+            return t.data_ptr()
+
+        if not (getattr(points, "is_cuda", False) and points.dim() == 3 and points.shape[0] == n and points.shape[2] == 2):
+            raise AgxError(_ffi.AGX_ERR_ARG, "points must be a device tensor [N, P, 2]")
+        ppf = int(points.shape[1])
+        p_points = tensor(points, torch.float32, (n, ppf, 2), "points")
+        p_counts = tensor(counts, torch.int32, (n,), "counts") if counts is not None else None
+        if (out is None) != (status is None):
+            raise AgxError(_ffi.AGX_ERR_ARG, "out and status: both or neither")
+        p_out = tensor(out, torch.float32, (n, ppf, 5), "out") if out is not None else None
+        p_status = tensor(status, torch.int32, (n, ppf), "status") if status is not None else None
+        self._follow_torch_stream(frames)
+        self._batch = self._detect = self._refine = None
+        self._check(self._lib.agx_refine_points_enqueue(self._h, frames.data_ptr(), n, w, h, rs, fs, fmt, self._refine_image(image), p_points,
+                                                        ppf, p_counts, p_out, p_status))
+        self._refine = (n, ppf, (frames, points, counts), (out, status) if out is not None else None)
+
+    def refine_points_fetch(self):
+        """Wait for refine_points_enqueue's batch -> (records [N,P] SADDLE_DTYPE, status [N,P] uint32); slots beyond a frame's
+        count read zero records and status 0xFFFFFFFF.  After refine_points_enqueue(out=, status=): the two device tensors."""
+        if self._refine is None:
+            raise AgxError(_ffi.AGX_ERR_STATE, "no refine batch enqueued")
+        n, ppf, _, dev_out = self._refine
+        self._refine = None
+        if dev_out is not None:
+            self._check(self._lib.agx_refine_points_fetch(self._h, None, None))
+            return dev_out
+        out = np.zeros((n, ppf), SADDLE_DTYPE)
+        status = np.full((n, ppf), 0xFFFFFFFF, np.uint32)
+        self._check(self._lib.agx_refine_points_fetch(self._h, out.ctypes.data, status.ctypes.data))
+        return out, status
 
     # ---- measurement / parity hooks ------------------------------------------------------
     def profile_enable(self, level=2):

@@ -57,6 +57,15 @@ pub struct agx_cluster_info {
     pub cy: c_float,
 }
 
+/// `agx_point`: one `(f32, f32)` of rochade_refine's `initial_corners` (reference src/detector.rs:194-361).  The header passes
+/// arrays of them as `const void *`; tests/test_refine_points_cpu.py holds this layout to the header's.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct agx_point {
+    pub x: c_float,
+    pub y: c_float,
+}
+
 pub const AGX_ABI_VERSION: c_int = 1;
 pub const AGX_N_KERNELS: c_int = 5;
 
@@ -100,6 +109,13 @@ pub const AGX_FRAME_LARGE_RESULT: c_int = 64;
 // transports of a detector group
 pub const AGX_GATHER_RCCL: c_int = 0;
 pub const AGX_GATHER_PEER: c_int = 1;
+// rochade_refine of caller-given points: a point's status, and the plane it is refined on
+pub const AGX_POINT_REFINED: c_int = 0;
+pub const AGX_POINT_OUTSIDE: c_int = 1;
+pub const AGX_POINT_NOT_SADDLE: c_int = 2;
+pub const AGX_POINT_MOVED: c_int = 3;
+pub const AGX_REFINE_BLURRED: c_int = 0;
+pub const AGX_REFINE_PLANE: c_int = 1;
 // agx_debug_fetch items
 pub const AGX_DBG_BLUR: c_int = 0;
 pub const AGX_DBG_RESP: c_int = 1;
@@ -158,6 +174,15 @@ extern "C" {
                                         saddle_capacity: u32, d_frame_table: *mut c_void) -> c_int;
     pub fn agx_saddles_batch_fetch(det: *mut agx_detector, out: *mut agx_saddle, cap_per_frame: u32, counts: *mut u32,
                                    frame_status: *mut c_int) -> c_int;
+
+    pub fn agx_refine_points_enqueue(det: *mut agx_detector, d_frames: *const c_void, n_frames: c_int, width: c_int, height: c_int,
+                                     row_stride_bytes: usize, frame_stride_bytes: usize, format: c_int, image: c_int,
+                                     d_points: *const c_void, points_per_frame: u32, d_counts: *const u32, d_out: *mut agx_saddle,
+                                     d_status: *mut u32) -> c_int;
+    pub fn agx_refine_points_fetch(det: *mut agx_detector, out: *mut agx_saddle, status: *mut u32) -> c_int;
+    pub fn agx_rochade_refine(det: *mut agx_detector, pixels: *const c_void, width: c_int, height: c_int, row_stride_bytes: usize,
+                              format: c_int, image: c_int, points: *const c_void, n_points: u32, out: *mut agx_saddle,
+                              status: *mut u32, n_refined: *mut u32) -> c_int;
 
     pub fn agx_detect_from_saddles(det: *const agx_detector, saddles: *const agx_saddle, n_saddles: u32, luma8: *const u8, width: c_int,
                                    height: c_int, row_stride_bytes: usize, out: *mut agx_tag, cap: u32, n_out: *mut u32) -> c_int;

@@ -199,6 +199,35 @@ impl TagDetector {
         out[..n as usize].iter().map(|s| Saddle { p: (s.x, s.y), k: s.k, theta: s.theta, phi: s.phi }).collect()
     }
 
+    /// reference src/detector.rs:194-361, `rochade_refine(image_input, initial_corners, 2)` with `image_input` the sigma = 1.5
+    /// blur of `img`, as `refined_saddle_points` feeds it (:409-410, :430): the refined corners, in input order.
+    pub fn rochade_refine(&self, img: &image::DynamicImage, initial_corners: &[(f32, f32)]) -> Vec<Saddle> {
+        let (records, status) = self.rochade_refine_with_status(img, initial_corners);
+        records.into_iter().zip(status).filter(|(_, st)| *st == ffi::AGX_POINT_REFINED as u32).map(|(s, _)| s).collect()
+    }
+
+    /// The same with an answer for every corner: its record (zeros unless refined) and why it was kept or dropped
+    /// (`AGX_POINT_REFINED`, `_OUTSIDE`, `_NOT_SADDLE`, `_MOVED`), in input order.
+    pub fn rochade_refine_with_status(&self, img: &image::DynamicImage, initial_corners: &[(f32, f32)]) -> (Vec<Saddle>, Vec<u32>) {
+        let (inp, w, h) = Self::input(img);
+        let (px, stride, fmt) = match &inp {
+            Input::Native { px, stride, fmt, .. } => (*px, *stride, *fmt),
+            Input::Planes { luma32f, .. } => (luma32f.as_raw().as_ptr() as *const c_void, 4 * w as usize, ffi::AGX_LF32),
+        };
+        let points: Vec<ffi::agx_point> = initial_corners.iter().map(|p| ffi::agx_point { x: p.0, y: p.1 }).collect();
+        let mut out = vec![ffi::agx_saddle::default(); points.len()];
+        let mut status = vec![0u32; points.len()];
+        let mut n_refined = 0u32;
+        let st = self.with_handle(|d| unsafe {
+            ffi::agx_rochade_refine(
+                d, px, w as c_int, h as c_int, stride, fmt, ffi::AGX_REFINE_BLURRED, points.as_ptr() as *const c_void,
+                points.len() as u32, out.as_mut_ptr(), status.as_mut_ptr(), &mut n_refined,
+            )
+        });
+        assert_eq!(st, ffi::AGX_OK, "agx_rochade_refine failed: {}", st);
+        (out.iter().map(|s| Saddle { p: (s.x, s.y), k: s.k, theta: s.theta, phi: s.phi }).collect(), status)
+    }
+
     fn tags_to_map(out: &[ffi::agx_tag]) -> HashMap<u32, [(f32, f32); 4]> {
         // later entries replace earlier ones, as HashMap::insert does at src/detector.rs:520
         out.iter().map(|t| (t.id, [(t.xy[0], t.xy[1]), (t.xy[2], t.xy[3]), (t.xy[4], t.xy[5]), (t.xy[6], t.xy[7])])).collect()

@@ -312,6 +312,56 @@ int agx_detect_batch_enqueue_to(agx_detector *det, const void *d_frames, int n_f
  * AGX_ERR_STATE with nothing in flight.  The batch is resolved by this call: a second fetch is AGX_ERR_STATE. */
 int agx_detect_batch_fetch(agx_detector *det, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads);
 
+/* ---- rochade_refine of caller-given points ---------------------------------------------- */
+
+/* detector::rochade_refine(image_input, initial_corners, half_size_patch) -> Vec<Saddle> -- src/detector.rs:194-361, a `pub fn`
+ * of the crate: the sub-pixel refinement of ANY list of corner guesses (last frame's corners, corners predicted from a board
+ * homography, another detector's), not only of the centroids the chain's own flood fill produced.  half_size_patch is 2, the
+ * only value the reference's detector passes (:430): there is no parameter for it.  Every point is answered in its own slot,
+ * in input order, with a record and one of these reasons; a rejected point's record is five zero floats. */
+struct agx_point {
+    float x, y;
+}; /* one (f32,f32) of initial_corners -- src/detector.rs:194-361; 8 bytes.  Arrays of them cross the boundary as `const void *`,
+      like the saddle records of agx_saddles_batch_enqueue_to: an [n][2] float array is the same memory */
+typedef struct agx_point agx_point;
+enum { AGX_POINT_REFINED = 0,
+       AGX_POINT_OUTSIDE = 1,     /* :266-274: the 9x9 window around round(x), round(y) leaves the image: unless both coordinates
+                                     are finite, roundf(x) in [4, W-5] and roundf(y) in [4, H-5].  Decided in float before anything
+                                     is converted or read -- NaN, +-inf and values beyond the int range, undefined in the reference
+                                     (`as i32`, unchecked indexing), are OUTSIDE; so is every point of a frame smaller than 9x9 */
+       AGX_POINT_NOT_SADDLE = 2,  /* :331-339: not (d < 0) */
+       AGX_POINT_MOVED = 3 };     /* :342-347: |x0| or |y0| > 1, or not |c5| < k */
+enum { AGX_REFINE_BLURRED = 0,    /* frames of any agx_format; refined on their sigma = 1.5 blur, as
+                                     refined_saddle_points does (:409-410, :430) */
+       AGX_REFINE_PLANE = 1 };    /* format must be AGX_LF32 (else AGX_ERR_FORMAT): the plane IS image_input, taken as is
+                                     (row stride a multiple of 4 bytes); no blur, no workspace plane */
+
+/* rochade_refine (src/detector.rs:194-361) over a batch in DEVICE memory, stream-ordered on the detector's stream (the caller's
+ * after agx_detector_set_stream); returns without waiting.  d_frames / n_frames / width / height / strides / format as
+ * agx_saddles_batch_enqueue (width, height >= 1).  image: AGX_REFINE_BLURRED or AGX_REFINE_PLANE.  d_points: agx_point records; frame f's are
+ * d_points[f*points_per_frame .. + n_f); n_f = d_counts[f] where d_counts is given and that is at most points_per_frame, else
+ * points_per_frame.  Point i of frame f writes record and status [f*points_per_frame + i]; slots at or beyond n_f are not
+ * written.  d_out ([n_frames*points_per_frame] agx_saddle) and d_status: caller-owned device memory, 4-byte aligned, or both
+ * NULL -- internal buffers, copied out by agx_refine_points_fetch.  Frames, points and counts stay in place until the fetch
+ * has returned.  A third kind of batch on the handle: one batch is in flight, a later enqueue of any kind replaces it;
+ * agx_saddles_batch_fetch / agx_detect_batch_fetch of it are AGX_ERR_STATE.  AGX_ERR_ARG: NULL d_frames or d_points,
+ * points_per_frame == 0, exactly one of d_out / d_status NULL, an unknown image. */
+int agx_refine_points_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height,
+                              size_t row_stride_bytes, size_t frame_stride_bytes, int format, int image,
+                              const void *d_points, uint32_t points_per_frame, const uint32_t *d_counts,
+                              agx_saddle *d_out, uint32_t *d_status);
+/* Wait for the batch of agx_refine_points_enqueue (src/detector.rs:194-361).  Internal buffers: out and status, host arrays of
+ * n_frames*points_per_frame entries, receive the slots the batch wrote (slots at or beyond a frame's count stay as they were).
+ * Caller-owned device buffers: out and status are NULL, the call only waits.  AGX_ERR_STATE: no such batch in flight (another
+ * kind, none, or fetched already). */
+int agx_refine_points_fetch(agx_detector *det, agx_saddle *out, uint32_t *status);
+/* rochade_refine (src/detector.rs:194-361) of one image in HOST memory: uploads pixels and points, runs a batch of one, writes
+ * record and status of every point (points: n_points agx_point records; out, status: n_points entries each, in input order) and *n_refined, the number of
+ * AGX_POINT_REFINED ones: the reference's Vec<Saddle> is those records in input order.  n_points == 0: AGX_OK, *n_refined = 0. */
+int agx_rochade_refine(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes, int format,
+                       int image, const void *points, uint32_t n_points, agx_saddle *out, uint32_t *status,
+                       uint32_t *n_refined);
+
 /* ---- detector groups: several GPUs of one node driven from ONE process ----------------- */
 
 /* The reference's detect(&self) is stateless, so a batch shards by frame:
@@ -432,7 +482,7 @@ enum { AGX_DBG_BLUR = 0, AGX_DBG_RESP = 1, AGX_DBG_MIN = 2, AGX_DBG_CENTERS = 3,
                                check of the check).  Buffers = the chain's workspace, then the staging buffer, the luma
                                planes and the device tail's code list, tag rows and frame table (mapped pinned host memory), then
                                agx_detect_batch_enqueue_to's device-memory tag rows and frame table, agx_detect_batch_fetch's
-                               pinned luma planes and the front-end kernel's luma plane (AGX_LA8 .. AGX_RGBA16), as far as they exist.  Needs no enqueued batch.  Guard bytes exist only in handles created with
+                               pinned luma planes, the front-end kernel's luma plane (AGX_LA8 .. AGX_RGBA16), the stored / recomputed response planes, and agx_refine_points_enqueue's internal records and statuses and agx_rochade_refine's points, as far as they exist.  Needs no enqueued batch.  Guard bytes exist only in handles created with
                                AGX_REDZONE_BYTES=<n> in the environment (memory-safety tests of the kernels) */
        AGX_DBG_TAIL_TABLE_ADDR = 11 /* 2 x uint64: host address and payload bytes of the device tail's frame table (the check
                                        of the check for a buffer in mapped host memory).  Needs no enqueued batch */ };
