@@ -19,6 +19,8 @@ AGX_GATHER_RCCL, AGX_GATHER_PEER = 0, 1
 # rochade_refine of caller-given points (src/detector.rs:194-361): the status of a point, and which plane is refined on
 AGX_POINT_REFINED, AGX_POINT_OUTSIDE, AGX_POINT_NOT_SADDLE, AGX_POINT_MOVED = 0, 1, 2, 3
 AGX_REFINE_BLURRED, AGX_REFINE_PLANE = 0, 1
+# try_decode_quad of caller-given quads (src/detector.rs:448-476): what became of a quad
+AGX_QUAD_DECODED, AGX_QUAD_OUTSIDE, AGX_QUAD_LOW_CONTRAST, AGX_QUAD_AMBIGUOUS, AGX_QUAD_NO_MATCH, AGX_QUAD_SKIPPED = 0, 1, 2, 3, 4, 5
 AGX_DBG_BLUR, AGX_DBG_RESP, AGX_DBG_MIN, AGX_DBG_CENTERS, AGX_DBG_REFINED = 0, 1, 2, 3, 4
 AGX_N_KERNELS = 5
 
@@ -83,6 +85,11 @@ SYMBOLS = {
     "agx_refine_points_fetch": (C.c_int, [_P, _P, _P]),
     "agx_rochade_refine": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, _P, C.c_uint32, _P, _P,
                                      C.POINTER(C.c_uint32)]),
+    "agx_decode_quads_enqueue": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, _P, C.c_size_t, C.c_uint32,
+                                           _P, _P, _P, _P, _P]),
+    "agx_decode_quads_fetch": (C.c_int, [_P, _P, _P, _P]),
+    "agx_decode_quads": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32)]),
+    "agx_decode_quads_tail": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_size_t, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32)]),
     "agx_group_create": (C.c_int, [C.c_int, C.POINTER(Params), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "agx_group_destroy": (None, [_P]),
     "agx_group_size": (C.c_int, [_P]),

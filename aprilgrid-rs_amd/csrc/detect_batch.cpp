@@ -949,6 +949,136 @@ int agx::detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_fram
     return AGX_OK;
 }
 
+// ---- agx_decode_quads_enqueue / _fetch: try_decode_quad (src/detector.rs:448-476) of caller-given quads ----------------------
+// to_luma8 of the frames (L8: the frames themselves; else k_luma8 / the front-end kernel into SB_LUMA_D, as
+// agx_detect_batch_enqueue does) and k_decode_quads on the detector's stream.  The saddle chain is not run and the workspace
+// is not touched.
+int agx::decode_quads_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                                   size_t frame_stride_bytes, int format, const void *d_quads, size_t point_stride_bytes,
+                                   uint32_t quads_per_frame, const uint32_t *d_counts, const uint32_t *d_point_status, agx_tag *d_tags,
+                                   uint32_t *d_status, uint64_t *d_bits)
+{
+    if (!det) return AGX_ERR_ARG;
+    if (!d_frames || !d_quads || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null frames, null quads or n_frames <= 0");
+    if (!quads_per_frame) return fail(det, AGX_ERR_ARG, "quads_per_frame must be > 0");
+    if (point_stride_bytes < 8 || (point_stride_bytes & 3) || point_stride_bytes > 0x7fffffffu)
+        return fail(det, AGX_ERR_ARG, "point_stride_bytes must be a multiple of 4 and at least 8");
+    if ((d_tags == nullptr) != (d_status == nullptr)) return fail(det, AGX_ERR_ARG, "d_tags and d_status: both or neither");
+    if (!d_tags && d_bits) return fail(det, AGX_ERR_ARG, "d_bits needs d_tags and d_status (internal results: the fetch's bits argument)");
+    if ((((uintptr_t)d_quads | (uintptr_t)d_counts | (uintptr_t)d_point_status | (uintptr_t)d_tags | (uintptr_t)d_status) & 3) || ((uintptr_t)d_bits & 7))
+        return fail(det, AGX_ERR_ARG, "quads, counts, point statuses, tags and statuses must be 4-byte aligned, bits 8-byte aligned");
+    if (!format_px_bytes(format) || format == AGX_LF32) return fail(det, AGX_ERR_FORMAT, "format must be one of AGX_L8 .. AGX_RGBA16 but AGX_LF32 (the decode reads to_luma8)");
+    if (width < 1 || height < 1) return fail(det, AGX_ERR_ARG, "width and height must be >= 1");
+    if ((long long)width * height >= (1ll << 30) || width > 65000) return fail(det, AGX_ERR_ARG, "frame too large (>= 2^30 px or wider than 65000)");
+    if (n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
+    if (format_front(format) && height > 16 * 65535) return fail(det, AGX_ERR_ARG, "frames of this format may have at most 1048560 rows");
+    const size_t slots = (size_t)n_frames * quads_per_frame;
+    if (slots >= ((size_t)1 << 29)) return fail(det, AGX_ERR_ARG, "at most 2^29 - 1 quads per batch");
+    const size_t px_bytes = (size_t)format_px_bytes(format);
+    if (row_stride_bytes < (size_t)width * px_bytes || row_stride_bytes > 0x7fffffffu ||
+        (n_frames > 1 && frame_stride_bytes < row_stride_bytes * format_rows(format, height)))
+        return fail(det, AGX_ERR_ARG, "strides must cover a row / a frame");
+    if (format_16bit(format) && ((row_stride_bytes | (n_frames > 1 ? frame_stride_bytes : 0) | (uintptr_t)d_frames) & 1))
+        return fail(det, AGX_ERR_ARG, "16-bit pixels must be 2-byte aligned");
+    if (hipSetDevice(det->device) != hipSuccess) return fail(det, AGX_ERR_HIP, "hipSetDevice");
+    // this batch replaces whatever was in flight (SB_LUMA_D may grow below: nothing points into it any more)
+    det->detect.kind = 0;
+    det->refine.kind = 0;
+    det->decode.kind = 0;
+    det->front_format = -1;
+    det->enqueued = false;
+    if (tail_prepare(det)) return fail(det, AGX_ERR_HIP, "hipMalloc / hipMemcpy: the family's code list");
+    const uint8_t *d_luma = static_cast<const uint8_t *>(d_frames);  // detector.rs:507: L8 frames are their own u8 luma
+    size_t luma_row = row_stride_bytes, luma_frame = frame_stride_bytes;
+    if (format != AGX_L8) {
+        if (chunk_luma8(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, 0, 1, (size_t)n_frames, nullptr, &d_luma))
+            return fail(det, AGX_ERR_HIP, "to_luma8 of the frames on the device");
+        luma_row = (size_t)width;
+        luma_frame = (size_t)width * (size_t)height;
+    }
+    int kind = 2;
+    if (!d_tags) {
+        d_tags = static_cast<agx_tag *>(side_ensure(det, SB_DECODE_TAGS, slots * sizeof(agx_tag), 0));
+        d_status = static_cast<uint32_t *>(side_ensure(det, SB_DECODE_STATUS, slots * sizeof(uint32_t), 0));
+        d_bits = static_cast<uint64_t *>(side_ensure(det, SB_DECODE_BITS, slots * sizeof(uint64_t), 0));
+        if (!d_tags || !d_status || !d_bits) return fail(det, AGX_ERR_HIP, "hipMalloc: decoded quads");
+        kind = 1;
+    }
+    DecodeQuadsArgs q{};
+    q.luma = d_luma;
+    q.luma_frame_stride = (long long)luma_frame;
+    q.luma_row_stride = (int)luma_row;
+    q.W = width;
+    q.H = height;
+    q.n_frames = n_frames;
+    q.edge = det->fam.edge;
+    q.border = det->fam.border;
+    q.hamming = det->fam.hamming;
+    q.n_codes = det->fam.n_codes;
+    q.codes = det->side[SB_CODES].ptr<uint64_t>();
+    q.quads = static_cast<const uint8_t *>(d_quads);
+    q.point_stride = (uint32_t)point_stride_bytes;
+    q.quads_per_frame = quads_per_frame;
+    q.counts = d_counts;
+    q.point_status = d_point_status;
+    q.tags = d_tags;
+    q.status = d_status;
+    q.bits = d_bits;
+    const hipError_t e = (hipError_t)launch_decode_quads(q, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_decode_quads: ") + hipGetErrorString(e));
+    det->decode.kind = kind;
+    det->decode.n_frames = n_frames;
+    det->decode.quads_per_frame = quads_per_frame;
+    det->decode.d_counts = d_counts;
+    return AGX_OK;
+}
+
+int agx::decode_quads_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *status, uint64_t *bits)
+{
+    if (!det) return AGX_ERR_ARG;
+    const DecodePending b = det->decode;
+    if (!b.kind) return fail(det, AGX_ERR_STATE, "no agx_decode_quads_enqueue batch in flight");
+    if (b.kind == 1 && (!out || !status)) return fail(det, AGX_ERR_ARG, "null output");  // (the batch stays in flight)
+    if (hipSetDevice(det->device) != hipSuccess) return fail(det, AGX_ERR_HIP, "hipSetDevice");
+    det->decode.kind = 0;  // resolved by this call, whatever it returns
+    const size_t slots = (size_t)b.n_frames * b.quads_per_frame;
+    // host staging when counts were given (only the slots the kernel wrote reach the caller's arrays): in 8-byte words, the
+    // bits, then the tags (9 x 4 bytes each), the statuses and the counts
+    const size_t w_tags = slots, w_status = w_tags + (slots * sizeof(agx_tag) + 7) / 8, w_counts = w_status + (slots * 4 + 7) / 8;
+    bool ok = true;
+    if (b.kind == 1) {
+        const agx_tag *d_tags = det->side[SB_DECODE_TAGS].ptr<agx_tag>();
+        const uint32_t *d_status = det->side[SB_DECODE_STATUS].ptr<uint32_t>();
+        const uint64_t *d_bits = det->side[SB_DECODE_BITS].ptr<uint64_t>();
+        if (!b.d_counts) {
+            ok = hipMemcpyAsync(out, d_tags, slots * sizeof(agx_tag), hipMemcpyDeviceToHost, det->stream) == hipSuccess &&
+                 hipMemcpyAsync(status, d_status, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, det->stream) == hipSuccess &&
+                 (!bits || hipMemcpyAsync(bits, d_bits, slots * sizeof(uint64_t), hipMemcpyDeviceToHost, det->stream) == hipSuccess);
+        } else {
+            std::vector<uint64_t> &h = det->decode_host;
+            h.resize(w_counts + ((size_t)b.n_frames * 4 + 7) / 8);
+            ok = hipMemcpyAsync(h.data(), d_bits, slots * sizeof(uint64_t), hipMemcpyDeviceToHost, det->stream) == hipSuccess &&
+                 hipMemcpyAsync(h.data() + w_tags, d_tags, slots * sizeof(agx_tag), hipMemcpyDeviceToHost, det->stream) == hipSuccess &&
+                 hipMemcpyAsync(h.data() + w_status, d_status, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, det->stream) == hipSuccess &&
+                 hipMemcpyAsync(h.data() + w_counts, b.d_counts, (size_t)b.n_frames * sizeof(uint32_t), hipMemcpyDeviceToHost, det->stream) == hipSuccess;
+        }
+    }
+    if (hipStreamSynchronize(det->stream) != hipSuccess || !ok) return fail(det, AGX_ERR_HIP, "agx_decode_quads_fetch: copy / wait");
+    if (b.kind == 1 && b.d_counts) {
+        const std::vector<uint64_t> &h = det->decode_host;
+        const char *h_tags = reinterpret_cast<const char *>(h.data() + w_tags);
+        const uint32_t *h_status = reinterpret_cast<const uint32_t *>(h.data() + w_status), *h_counts = reinterpret_cast<const uint32_t *>(h.data() + w_counts);
+        for (int f = 0; f < b.n_frames; ++f) {
+            const size_t n = std::min(h_counts[f], b.quads_per_frame), s0 = (size_t)f * b.quads_per_frame;
+            if (!n) continue;
+            std::memcpy(out + s0, h_tags + s0 * sizeof(agx_tag), n * sizeof(agx_tag));
+            std::memcpy(status + s0, h_status + s0, n * sizeof(uint32_t));
+            if (bits) std::memcpy(bits + s0, h.data() + s0, n * sizeof(uint64_t));
+        }
+    }
+    return AGX_OK;
+}
+
 // The host tail of the frames `back` marks (1 handed back, 2 handed back as uncertain; without the device tail: every frame) of
 // the batch `b` in flight on `det`, on the pool: from the chain's compact saddle lists and those frames' u8 luma, copied down
 // from the device a group at a time.  cnt / st [n] get those frames' counts and statuses (a list of the chain overflowed: 0,

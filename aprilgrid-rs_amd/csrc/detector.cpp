@@ -771,6 +771,7 @@ static int batch_enqueue_impl(agx_detector *det, const void *d_frames, int n_fra
         return fail(det, AGX_ERR_ARG, "frames of this format may have at most 1048560 rows");
     det->detect.kind = 0;  // (this batch replaces whatever was in flight, an agx_detect_batch_enqueue's included)
     det->refine.kind = 0;  // (... and an agx_refine_points_enqueue's)
+    det->decode.kind = 0;  // (... and an agx_decode_quads_enqueue's)
     det->front_format = -1;
     HIP_TRY(det, hipSetDevice(det->device));
     int rc = ensure_workspace(det, n_frames, width, height);
@@ -938,6 +939,8 @@ int agx_saddles_batch_fetch(agx_detector *det, agx_saddle *out, uint32_t cap_per
     return agx_guard(det, [&]() -> int {
     if (det && det->refine.kind)
         return fail(det, AGX_ERR_STATE, "the batch in flight is agx_refine_points_enqueue's: fetch it with agx_refine_points_fetch");
+    if (det && det->decode.kind)
+        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_decode_quads_enqueue's: fetch it with agx_decode_quads_fetch");
     if (det && det->enqueued && det->detect.kind)
         return fail(det, AGX_ERR_STATE, "the batch in flight is agx_detect_batch_enqueue's: fetch it with agx_detect_batch_fetch");
     return saddles_fetch_impl(det, out, cap_per_frame, counts, frame_status);
@@ -984,6 +987,8 @@ int agx_detect_batch_fetch(agx_detector *det, agx_tag *out, uint32_t *counts, in
     if (!det) return AGX_ERR_ARG;
     if (det->refine.kind)
         return fail(det, AGX_ERR_STATE, "the batch in flight is agx_refine_points_enqueue's: fetch it with agx_refine_points_fetch");
+    if (det->decode.kind)
+        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_decode_quads_enqueue's: fetch it with agx_decode_quads_fetch");
     if (!det->detect.kind || !det->enqueued) return fail(det, AGX_ERR_STATE, "no agx_detect_batch_enqueue batch in flight");
     if (det->detect.kind == 3) return fail(det, AGX_ERR_STATE, "the batch in flight is a group's: fetch it with agx_group_detect_fetch");
     det->last_error.clear();
@@ -1026,6 +1031,7 @@ static int refine_points_enqueue_impl(agx_detector *det, const void *d_frames, i
     // this batch replaces whatever was in flight
     det->detect.kind = 0;
     det->refine.kind = 0;
+    det->decode.kind = 0;
     det->front_format = -1;
     det->enqueued = false;
     RefinePointsArgs p{};
@@ -1076,6 +1082,8 @@ static int refine_points_fetch_impl(agx_detector *det, agx_saddle *out, uint32_t
 {
     if (!det) return AGX_ERR_ARG;
     const RefinePending b = det->refine;
+    if (!b.kind && det->decode.kind)
+        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_decode_quads_enqueue's: fetch it with agx_decode_quads_fetch");
     if (!b.kind) return fail(det, AGX_ERR_STATE, "no agx_refine_points_enqueue batch in flight");
     if (b.kind == 1 && (!out || !status)) return fail(det, AGX_ERR_ARG, "null output");  // (the batch stays in flight)
     HIP_TRY(det, hipSetDevice(det->device));
@@ -1159,6 +1167,95 @@ int agx_rochade_refine(agx_detector *det, const void *pixels, int width, int hei
     uint32_t n = 0;
     for (uint32_t i = 0; i < n_points; ++i) n += status[i] == AGX_POINT_REFINED;
     *n_refined = n;
+    return AGX_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- try_decode_quad of caller-given quads (src/detector.rs:448-476; csrc/detect_batch.cpp, tail_kernels.hip) ------------------
+extern "C" {
+
+int agx_decode_quads_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                             size_t frame_stride_bytes, int format, const void *d_quads, size_t point_stride_bytes,
+                             uint32_t quads_per_frame, const uint32_t *d_counts, const uint32_t *d_point_status, agx_tag *d_tags,
+                             uint32_t *d_status, uint64_t *d_bits)
+{
+    return agx_guard(det, [&]() -> int {
+    return decode_quads_enqueue_impl(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, d_quads,
+                                     point_stride_bytes, quads_per_frame, d_counts, d_point_status, d_tags, d_status, d_bits);
+    });
+}
+
+int agx_decode_quads_fetch(agx_detector *det, agx_tag *out, uint32_t *status, uint64_t *bits)
+{
+    return agx_guard(det, [&]() -> int { return decode_quads_fetch_impl(det, out, status, bits); });
+}
+
+int agx_decode_quads(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes, int format,
+                     const void *quads, uint32_t n_quads, agx_tag *out, uint32_t *status, uint64_t *bits, uint32_t *n_decoded)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    if (!pixels || !n_decoded || (n_quads && (!quads || !out || !status))) return fail(det, AGX_ERR_ARG, "null argument");
+    if (!format_px_bytes(format) || format == AGX_LF32) return fail(det, AGX_ERR_FORMAT, "format must be one of AGX_L8 .. AGX_RGBA16 but AGX_LF32 (the decode reads to_luma8)");
+    if (width < 1 || height < 1) return fail(det, AGX_ERR_ARG, "width and height must be >= 1");
+    const size_t row_bytes = (size_t)width * format_px_bytes(format);
+    if (row_stride_bytes < row_bytes) return fail(det, AGX_ERR_ARG, "row stride smaller than a row");
+    *n_decoded = 0;
+    if (!n_quads) return AGX_OK;
+    HIP_TRY(det, hipSetDevice(det->device));
+    const size_t pitch = (row_bytes + 3) & ~(size_t)3;
+    const size_t rows = format_rows(format, height);
+    const size_t need = pitch * rows;
+    void *d_stage = side_ensure(det, SB_STAGE, need, 0);
+    if (!d_stage) return fail(det, AGX_ERR_HIP, "hipMalloc: staging buffer");
+    void *d_quads = side_ensure(det, SB_DECODE_QUADS, (size_t)n_quads * 8 * sizeof(float), 0);
+    if (!d_quads) return fail(det, AGX_ERR_HIP, "hipMalloc: quads");
+    HIP_TRY(det, hipMemcpy2DAsync(d_stage, pitch, pixels, row_stride_bytes, row_bytes, rows, hipMemcpyHostToDevice, det->stream));
+    HIP_TRY(det, hipMemcpyAsync(d_quads, quads, (size_t)n_quads * 8 * sizeof(float), hipMemcpyHostToDevice, det->stream));
+    int rc = decode_quads_enqueue_impl(det, d_stage, 1, width, height, pitch, need, format, d_quads, 8, n_quads, nullptr, nullptr, nullptr,
+                                       nullptr, nullptr);
+    if (rc) return rc;
+    rc = decode_quads_fetch_impl(det, out, status, bits);
+    if (rc) return rc;
+    uint32_t n = 0;
+    for (uint32_t i = 0; i < n_quads; ++i) n += status[i] == AGX_QUAD_DECODED;
+    *n_decoded = n;
+    return AGX_OK;
+    });
+}
+
+int agx_decode_quads_tail(int family, const uint8_t *luma8, int width, int height, size_t row_stride_bytes, const void *quads,
+                          uint32_t n_quads, agx_tag *out, uint32_t *status, uint64_t *bits, uint32_t *n_decoded)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (!luma8 || !n_decoded || (n_quads && (!quads || !out || !status)) || width < 1 || height < 1 || row_stride_bytes < (size_t)width)
+        return AGX_ERR_ARG;
+    FamilyInfo fam;
+    if (!family_info(family, fam)) return AGX_ERR_FAMILY;
+    uint32_t n = 0;
+    for (uint32_t i = 0; i < n_quads; ++i) {
+        float q[8];
+        std::memcpy(q, static_cast<const char *>(quads) + (size_t)i * sizeof q, sizeof q);
+        bool finite = true;
+        for (float v : q) finite = finite && std::isfinite(v);
+        agx_tag tag{};
+        uint64_t b = 0;
+        int id = 0;
+        float corners[8];
+        // a coordinate that is not finite: AGX_QUAD_OUTSIDE before anything is read (the reference's `as u32` would take NaN for 0)
+        const int why = finite ? decode_quad(fam, luma8, (uint32_t)width, (uint32_t)height, row_stride_bytes, q, id, corners, b) : (int)AGX_QUAD_OUTSIDE;
+        if (why == AGX_QUAD_DECODED) {
+            tag.id = (uint32_t)id;
+            std::memcpy(tag.xy, corners, sizeof corners);
+            ++n;
+        }
+        out[i] = tag;
+        status[i] = (uint32_t)why;
+        if (bits) bits[i] = b;
+    }
+    *n_decoded = n;
     return AGX_OK;
     });
 }

@@ -62,6 +62,17 @@ struct RefinePending {
     const uint32_t *d_counts = nullptr;  // the caller's per-frame counts (kind 1: the fetch copies only the slots that were written)
 };
 
+// agx_decode_quads_enqueue: what agx_decode_quads_fetch needs of the batch in flight.  The fourth kind of batch on a handle, with
+// RefinePending's rules: `enqueued` is false while it is in flight, and every enqueue of any kind resets it.  Resetting
+// RefinePending (or this) forgets a batch, it does not wait for it or undo it: a refine batch whose results go to the caller's
+// device arrays may be followed by a decode batch that reads those arrays without a fetch in between -- same stream, in order.
+struct DecodePending {
+    int kind = 0;  // 0 none, 1 results in SB_DECODE_TAGS / _STATUS / _BITS (the fetch copies them out), 2 in the caller's device arrays
+    int n_frames = 0;
+    uint32_t quads_per_frame = 0;
+    const uint32_t *d_counts = nullptr;  // the caller's per-frame counts (kind 1: the fetch copies only the slots that were written)
+};
+
 struct EventPair {
     hipEvent_t a, b;
     int kernel;
@@ -94,6 +105,10 @@ enum {
     SB_REFINE_OUT,     // agx_refine_points_enqueue without caller-owned results: [n_frames][points_per_frame] agx_saddle ...
     SB_REFINE_STATUS,  // ... and [n_frames][points_per_frame] uint32 (AGX_POINT_*)
     SB_REFINE_POINTS,  // agx_rochade_refine: the host's points on the device
+    SB_DECODE_TAGS,    // agx_decode_quads_enqueue without caller-owned results: [n_frames][quads_per_frame] agx_tag ...
+    SB_DECODE_STATUS,  // ... [n_frames][quads_per_frame] uint32 (AGX_QUAD_*) ...
+    SB_DECODE_BITS,    // ... and [n_frames][quads_per_frame] uint64 (bit_code's value)
+    SB_DECODE_QUADS,   // agx_decode_quads: the host's quads on the device
     SB_COUNT
 };
 }  // namespace agx
@@ -189,6 +204,8 @@ struct agx_detector {
     agx::DetectPending detect;          // agx_detect_batch_enqueue / _to: the batch agx_detect_batch_fetch resolves
     agx::RefinePending refine;          // agx_refine_points_enqueue: the batch agx_refine_points_fetch resolves
     std::vector<uint32_t> refine_host;  // its host staging when per-frame counts were given (records, statuses, counts)
+    agx::DecodePending decode;          // agx_decode_quads_enqueue: the batch agx_decode_quads_fetch resolves
+    std::vector<uint64_t> decode_host;  // its host staging when per-frame counts were given (bits, tags, statuses, counts)
 
     std::string last_error;
 };
@@ -222,6 +239,12 @@ int detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, i
                         size_t frame_stride_bytes, int format, uint32_t cap_per_frame, int kind, agx_tag *d_tags,
                         uint32_t *d_counts, int *d_status, uint32_t slab_records);
 int detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads);
+// try_decode_quad of caller-given quads over a batch in device memory (detect_batch.cpp: to_luma8, k_decode_quads, the fetch)
+int decode_quads_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                              size_t frame_stride_bytes, int format, const void *d_quads, size_t point_stride_bytes,
+                              uint32_t quads_per_frame, const uint32_t *d_counts, const uint32_t *d_point_status, agx_tag *d_tags,
+                              uint32_t *d_status, uint64_t *d_bits);
+int decode_quads_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *status, uint64_t *bits);
 int group_detect_fetch_impl(agx_detector *det, const char *back, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads);
 // What group.cpp calls for rank r's share of a detect batch (detector.cpp: the entry points' argument checks and guard around
 // the two functions above).  After the enqueue det->detect.device_tail says whether the pack kernel ran.

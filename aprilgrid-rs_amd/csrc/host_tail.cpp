@@ -1242,15 +1242,15 @@ bool best_tag(uint64_t bits, int thres, const uint64_t *codes, int n_codes, int 
     return best_tag_impl(bits, thres, codes, n_codes, edge_bits, idx, rot, [](uint64_t v) { return (unsigned)__builtin_popcountll(v); });
 }
 
-namespace {
-
-// try_decode_quad, src/detector.rs:448-476 (decode_positions :42-72, bit_code :74-122)
-bool decode_quad(const FamilyInfo &fam, const uint8_t *luma8, uint32_t w, uint32_t h, size_t stride,
-                 const float quad_xy[8], int &tag_id, float corners[8])
+// try_decode_quad, src/detector.rs:448-476 (decode_positions :42-72, bit_code :74-122), with the reason it gave None for
+// (AGX_QUAD_*) and bit_code's value where there is one
+int decode_quad(const FamilyInfo &fam, const uint8_t *luma8, uint32_t w, uint32_t h, size_t stride,
+                const float quad_xy[8], int &tag_id, float corners[8], uint64_t &bits_out)
 {
+    bits_out = 0;
     for (int i = 0; i < 4; ++i) {
         const uint32_t x = f32_as_u32(round_half_away(quad_xy[2 * i])), y = f32_as_u32(round_half_away(quad_xy[2 * i + 1]));
-        if (x >= w || y >= h) return false;
+        if (x >= w || y >= h) return AGX_QUAD_OUTSIDE;
     }
     float aff[6];
     tag_affine(quad_xy, fam.border * 2 + fam.edge, 0.5f, aff);
@@ -1262,7 +1262,7 @@ bool decode_quad(const FamilyInfo &fam, const uint8_t *luma8, uint32_t w, uint32
             const float px = aff[0] * fx + aff[1] * fy + aff[2] * 1.0f;
             const float py = aff[3] * fx + aff[4] * fy + aff[5] * 1.0f;
             const uint32_t ix = f32_as_u32(round_half_away(px)), iy = f32_as_u32(round_half_away(py));
-            if (ix >= w || iy >= h) return false;
+            if (ix >= w || iy >= h) return AGX_QUAD_OUTSIDE;
             samples[n++] = luma8[(size_t)iy * stride + ix];
         }
     int lo = 255, hi = 0;
@@ -1270,7 +1270,7 @@ bool decode_quad(const FamilyInfo &fam, const uint8_t *luma8, uint32_t w, uint32
         lo = std::min<int>(lo, samples[i]);
         hi = std::max<int>(hi, samples[i]);
     }
-    if (hi - lo < 50) return false;
+    if (hi - lo < 50) return AGX_QUAD_LOW_CONTRAST;
     const int mid = (int)(uint8_t)f32_as_u32(round_half_away(((float)lo + (float)hi) / 2.0f));
     uint64_t bits = 0;
     uint32_t invalid = 0;
@@ -1279,9 +1279,10 @@ bool decode_quad(const FamilyInfo &fam, const uint8_t *luma8, uint32_t w, uint32
         if (std::abs(mid - b) < 10) ++invalid;
         if (b > mid) bits |= 1ull << i;
     }
-    if (invalid > 3) return false;
+    if (invalid > 3) return AGX_QUAD_AMBIGUOUS;
+    bits_out = bits;
     int idx, rot;
-    if (!best_tag(bits, fam.hamming, fam.codes, fam.n_codes, fam.edge, idx, rot)) return false;
+    if (!best_tag(bits, fam.hamming, fam.codes, fam.n_codes, fam.edge, idx, rot)) return AGX_QUAD_NO_MATCH;
     // rotate_left(rot) then reverse, :468-469
     for (int i = 0; i < 4; ++i) {
         const int src = ((3 - i) + rot) & 3;
@@ -1289,10 +1290,8 @@ bool decode_quad(const FamilyInfo &fam, const uint8_t *luma8, uint32_t w, uint32
         corners[2 * i + 1] = quad_xy[2 * src + 1];
     }
     tag_id = idx;
-    return true;
+    return AGX_QUAD_DECODED;
 }
-
-}  // namespace
 
 namespace {
 // detect's loop body (detector.rs:510-539) over a working copy of the saddle list (consumed: the saddles of decoded
@@ -1316,8 +1315,9 @@ void detect_tail_rounds(const FamilyInfo &fam, int max_num_of_boards, std::vecto
             }
             int id;
             float corners[8];
+            uint64_t bits;
             AGX_TAIL_TIME(4);
-            if (!decode_quad(fam, luma8, (uint32_t)width, (uint32_t)height, row_stride, qxy, id, corners)) continue;
+            if (decode_quad(fam, luma8, (uint32_t)width, (uint32_t)height, row_stride, qxy, id, corners, bits) != AGX_QUAD_DECODED) continue;
             auto it = std::find_if(tags.begin(), tags.end(), [&](const agx_tag &t) { return t.id == (uint32_t)id; });
             if (it == tags.end()) {
                 tags.push_back(agx_tag{});

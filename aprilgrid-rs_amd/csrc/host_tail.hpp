@@ -57,6 +57,13 @@ void tag_affine(const float quad_xy[8], int side_bits, float margin, float h[6])
 uint64_t rotate_bits(uint64_t bits, int edge_bits);
 bool best_tag(uint64_t bits, int thres, const uint64_t *codes, int n_codes, int edge_bits, int &idx, int &rot);
 
+// try_decode_quad, detector.rs:448-476, of one quad (x, y of its four corners) on the u8 luma plane: AGX_QUAD_DECODED with the
+// code's index and the corners after rotate_left(rotation); reverse() (:467-470), or the reason for None (AGX_QUAD_OUTSIDE,
+// _LOW_CONTRAST, _AMBIGUOUS, _NO_MATCH); bits = bit_code's value before any rotation (DECODED and NO_MATCH; else 0).
+// tag_id and corners are written only for AGX_QUAD_DECODED.
+int decode_quad(const FamilyInfo &fam, const uint8_t *luma8, uint32_t w, uint32_t h, size_t stride, const float quad_xy[8],
+                int &tag_id, float corners[8], uint64_t &bits);
+
 // detector.rs:510-539: board search + decode over a saddle list and the u8 luma plane.
 // Tags in first-insertion order; a repeated id replaces the earlier corners.
 void detect_tail(const FamilyInfo &fam, int max_num_of_boards, std::vector<agx_saddle> refined,

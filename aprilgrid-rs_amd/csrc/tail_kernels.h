@@ -67,6 +67,27 @@ enum : uint32_t {
 // d_table must be 16-byte aligned; n_frames <= 65535.  hipError_t.
 int launch_pack_tags(const uint32_t *table, const agx_tag *tags, uint32_t tag_stride, const FrameCounters *ctr, int n_frames,
                      uint32_t cap, uint32_t *d_table, agx_tag *d_slab, uint32_t slab_records, void *stream);
+// k_decode_quads (agx_decode_quads_enqueue): try_decode_quad (detector.rs:448-476) of caller-given quads on the frames' u8 luma.
+// All pointers are device pointers.
+struct DecodeQuadsArgs {
+    const uint8_t *luma;  // to_luma8 of frame f at luma + f * luma_frame_stride, rows luma_row_stride bytes apart
+    long long luma_frame_stride;
+    int luma_row_stride;
+    int W, H;
+    int n_frames;
+    int edge, border, hamming, n_codes;  // the family (src/detector.rs:17-23)
+    const uint64_t *codes;               // its code list
+    const uint8_t *quads;        // point p of slot s: two floats at quads + (s * 4 + p) * point_stride; slot = f * quads_per_frame + q
+    uint32_t point_stride;       // bytes: a multiple of 4, >= 8
+    uint32_t quads_per_frame;
+    const uint32_t *counts;        // [n_frames] quads of frame f (capped at quads_per_frame), or null: quads_per_frame each
+    const uint32_t *point_status;  // [slots * 4] AGX_POINT_* of every point, or null: a quad with a word != 0 is AGX_QUAD_SKIPPED
+    agx_tag *tags;     // [slots]: {id, xy}; zeros unless AGX_QUAD_DECODED
+    uint32_t *status;  // [slots]: AGX_QUAD_*
+    uint64_t *bits;    // [slots] or null: bit_code's value (DECODED, NO_MATCH), else 0
+};
+// one row of 16 lanes per slot, grid-stride; n_frames * quads_per_frame < 2^31; hipError_t
+int launch_decode_quads(const DecodeQuadsArgs &d, void *stream);
 int init_tail_kernels();  // per-device kernel attributes (current device); hipError_t
 
 }  // namespace agx

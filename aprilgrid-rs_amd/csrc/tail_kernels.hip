@@ -35,7 +35,11 @@
 //             candidate quadruples are tested one per lane (is_valid_quad memoised) and the first valid one in the reference's
 //             loop order is taken; the wave that grew the chosen board keeps its cells;
 //   the rest  (try_fix_missing, decode -- best_tag by rows of 16 lanes --, the tag map, removing the used saddles) on the first wave.
+//
+// k_decode_quads (at the end of the file) is the decode alone, for quads the caller names: agx_decode_quads_enqueue.
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "libm_f32.h"
 #include "tail_kernels.h"
@@ -661,8 +665,9 @@ __device__ __forceinline__ uint32_t half_reduce_u(uint32_t v, F f)
     return f(v, dpp_u<0x141>(v));  // row_half_mirror
 }
 // decode_positions + bit_code (detector.rs:42-122) of one quad by EIGHT lanes (sub = 0 .. 7 takes every eighth sample of the up to 40:
-// the samples' loads side by side instead of one after the other): true + the bits in every lane of the eight; false = None
-__device__ bool quad_bits8(const TailArgs &a, const uint8_t *luma, const float q[8], int sub, u64 &bits_out)
+// the samples' loads side by side instead of one after the other): AGX_QUAD_DECODED (0) + the bits in every lane of the eight;
+// else the reason for None, in the order the reference meets them (AGX_QUAD_OUTSIDE, _LOW_CONTRAST, _AMBIGUOUS)
+__device__ __forceinline__ int quad_bits8_why(const TailArgs &a, const uint8_t *luma, const float q[8], int sub, u64 &bits_out)
 {
     const uint32_t w = (uint32_t)a.W, h = (uint32_t)a.H;
     bool outside = false;
@@ -718,7 +723,8 @@ __device__ bool quad_bits8(const TailArgs &a, const uint8_t *luma, const float q
     lo = (int)half_reduce_u((uint32_t)lo, [](uint32_t x, uint32_t y) { return x < y ? x : y; });
     hi = (int)half_reduce_u((uint32_t)hi, [](uint32_t x, uint32_t y) { return x > y ? x : y; });
     outside = half_reduce_u(outside ? 1u : 0u, [](uint32_t x, uint32_t y) { return x | y; }) != 0;
-    if (outside || hi - lo < 50) return false;  // (the eight alike)
+    if (outside) return AGX_QUAD_OUTSIDE;  // (the eight alike)
+    if (hi - lo < 50) return AGX_QUAD_LOW_CONTRAST;
     const int mid = (int)(uint8_t)f32_as_u32(round_half_away(((float)lo + (float)hi) / 2.0f));
     u64 bits = 0;
     uint32_t invalid = 0;
@@ -730,10 +736,15 @@ __device__ bool quad_bits8(const TailArgs &a, const uint8_t *luma, const float q
             if (b > mid) bits |= 1ull << (nb - 1 - (sub + 8 * k));
         }
     invalid = half_reduce_u(invalid, [](uint32_t x, uint32_t y) { return x + y; });
-    if (invalid > 3) return false;
+    if (invalid > 3) return AGX_QUAD_AMBIGUOUS;
     bits_out = (u64)half_reduce_u((uint32_t)(bits >> 32), [](uint32_t x, uint32_t y) { return x | y; }) << 32 |
                half_reduce_u((uint32_t)bits, [](uint32_t x, uint32_t y) { return x | y; });
-    return true;
+    return AGX_QUAD_DECODED;
+}
+// the same for the board search, which only asks whether there are bits: false = None
+__device__ bool quad_bits8(const TailArgs &a, const uint8_t *luma, const float q[8], int sub, u64 &bits_out)
+{
+    return quad_bits8_why(a, luma, q, sub, bits_out) == AGX_QUAD_DECODED;
 }
 
 // OR over the lane's row of 16, in every lane of the row
@@ -1554,7 +1565,106 @@ __global__ void __launch_bounds__(256) k_pack_tags(const uint4 *d_table, const a
     for (uint32_t i = (uint32_t)lane; i < words; i += 64u) dst[i] = src[i];
 }
 
+
+// ---- agx_decode_quads_enqueue: try_decode_quad (detector.rs:448-476) of caller-given quads ------------------------------------
+// The three stages above on quads that no board search produced.  A ROW of 16 lanes per quad slot, four slots per wave, a
+// workgroup of 256 threads (16 slots at a time), grid-stride over the batch's n_frames * quads_per_frame slots; the family's
+// code list (at most 587 x 8 bytes) is read into LDS once per workgroup -- DQ_LDS_BYTES = TCODES * 8 = 5120 bytes, the only
+// LDS.  Both halves of a row run quad_bits8_why (eight lanes per quad: the halves compute the same bits, which saves the
+// exchange between them), then the row scans the codes once for the four rotations (best_tag_row).  Lanes 0 .. 8 of the row
+// store the nine words of the slot's agx_tag -- for a decoded quad the corners are read again from the input in their rotated
+// order: no register array is indexed by the rotation --, lane 9 the status, lane 10 the bits.  Every store is a per-lane
+// global store.  A row's lanes take every branch together, so the row-wide DPP reductions see all of their lanes.
+// 256 threads, at least four waves per SIMD (__launch_bounds__'s second argument): at most 128 VGPRs, no scratch.
+constexpr int DQ_THREADS = 256;
+constexpr int DQ_LDS_BYTES = TCODES * 8;
+__device__ __forceinline__ bool dq_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+__global__ void __launch_bounds__(DQ_THREADS, 4) k_decode_quads(DecodeQuadsArgs d)
+{
+    __shared__ u64 codes[DQ_LDS_BYTES / 8];
+    for (int i = (int)threadIdx.x; i < d.n_codes && i < TCODES; i += DQ_THREADS) codes[i] = d.codes[i];
+    __syncthreads();
+    TailArgs a{};  // what quad_bits8_why and best_tag_row read
+    a.W = d.W;
+    a.H = d.H;
+    a.luma_row_stride = d.luma_row_stride;
+    a.edge = d.edge;
+    a.border = d.border;
+    a.hamming = d.hamming;
+    a.n_codes = d.n_codes < TCODES ? d.n_codes : TCODES;
+    const int l_row = (int)(threadIdx.x & 15u);
+    // (the launcher: n_slots < 2^31 and at most 2048 workgroups, so neither the product nor slot + step wraps)
+    const uint32_t n_slots = (uint32_t)d.n_frames * d.quads_per_frame, step = gridDim.x * (DQ_THREADS / 16);
+    for (uint32_t slot = blockIdx.x * (DQ_THREADS / 16) + (threadIdx.x >> 4); slot < n_slots; slot += step) {
+        // the lane's place in its row, opaque to the optimiser: what depends on it alone (which samples and codes the lane takes,
+        // which word it stores) is then worked out per slot in a few VALU instructions instead of being kept across the loop as
+        // a dozen lane masks in SGPR pairs, which the register file does not hold (they were spilled to VGPR lanes)
+        int l = l_row;
+        asm volatile("" : "+v"(l));
+        const uint32_t f = slot / d.quads_per_frame, qf = slot - f * d.quads_per_frame;
+        if (d.counts) {
+            const uint32_t n_f = d.counts[f];
+            if (qf >= n_f) continue;  // (a count above quads_per_frame: every slot of the frame; slots beyond a count are not written)
+        }
+        const uint8_t *pts = d.quads + (u64)slot * 4u * (u64)d.point_stride;
+        uint32_t why = AGX_QUAD_DECODED;
+        if (d.point_status) {
+            const uint32_t *ps = d.point_status + (u64)slot * 4u;
+            if ((ps[0] | ps[1] | ps[2] | ps[3]) != 0u) why = AGX_QUAD_SKIPPED;  // (AGX_POINT_REFINED is 0)
+        }
+        u64 bits = 0;
+        int id = 0, rot = 0;
+        if (why == AGX_QUAD_DECODED) {
+            float q[8];
+            bool finite = true;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const float *pp = reinterpret_cast<const float *>(pts + (size_t)p * d.point_stride);
+                q[2 * p] = pp[0];
+                q[2 * p + 1] = pp[1];
+                finite = finite && dq_finite(q[2 * p]) && dq_finite(q[2 * p + 1]);
+            }
+            if (!finite) {
+                why = AGX_QUAD_OUTSIDE;  // before anything of the frame is read
+            } else {
+                why = (uint32_t)quad_bits8_why(a, d.luma + (long long)f * d.luma_frame_stride, q, l & 7, bits);
+                if (why != AGX_QUAD_DECODED) bits = 0;
+                else if (!best_tag_row(a, codes, bits, l, id, rot)) why = AGX_QUAD_NO_MATCH;
+            }
+        }
+        const bool hit = why == AGX_QUAD_DECODED;
+        if (l < 9) {
+            uint32_t w = 0;
+            if (hit) {
+                if (l == 0) {
+                    w = (uint32_t)id;
+                } else {  // rotate_left(rot) then reverse, :468-469
+                    const int i = (l - 1) >> 1, c = (l - 1) & 1, src = ((3 - i) + rot) & 3;
+                    w = reinterpret_cast<const uint32_t *>(pts + (size_t)src * d.point_stride)[c];
+                }
+            }
+            reinterpret_cast<uint32_t *>(d.tags + slot)[l] = w;
+        } else if (l == 9) {
+            d.status[slot] = why;
+        } else if (l == 10 && d.bits) {
+            d.bits[slot] = bits;
+        }
+    }
+}
+
 }  // namespace
+
+int launch_decode_quads(const DecodeQuadsArgs &d, void *stream)
+{
+    if (d.n_frames <= 0 || !d.quads_per_frame) return (int)hipSuccess;
+    if (d.n_codes < 1 || d.n_codes > TCODES || d.point_stride < 8 || (d.point_stride & 3) || d.W < 1 || d.H < 1) return (int)hipErrorInvalidValue;
+    const unsigned long long n_slots = (unsigned long long)d.n_frames * d.quads_per_frame, per_wg = DQ_THREADS / 16;
+    if (n_slots >= (1ull << 31)) return (int)hipErrorInvalidValue;
+    const unsigned grid = (unsigned)std::min<unsigned long long>((n_slots + per_wg - 1) / per_wg, 2048ull);  // (256 CUs x 8 workgroups; the rest by the stride)
+    hipLaunchKernelGGL(k_decode_quads, dim3(grid), dim3(DQ_THREADS), 0, (hipStream_t)stream, d);
+    return (int)hipGetLastError();
+}
 
 int launch_pack_tags(const uint32_t *table, const agx_tag *tags, uint32_t tag_stride, const FrameCounters *ctr, int n_frames,
                      uint32_t cap, uint32_t *d_table, agx_tag *d_slab, uint32_t slab_records, void *stream)

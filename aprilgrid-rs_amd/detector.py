@@ -9,6 +9,7 @@ Same names, argument meaning and error behaviour as the reference where Python a
   TagDetector.detect                  src/detector.rs:505-540
   TagDetector.detect_kornia           src/detector.rs:478-503
   TagDetector.rochade_refine          src/detector.rs:194-361 (the crate's pub fn, half_size_patch = 2)
+  TagDetector.decode_quads            src/detector.rs:448-476 (try_decode_quad = the pub fns decode_positions, bit_code, best_tag)
 An image is a numpy array standing for the DynamicImage variants the reference is fed:
 HxW uint8 (ImageLuma8), HxW uint16 (ImageLuma16), HxWx3 uint8 (ImageRgb8); HxWx2 / HxWx4 uint8 (ImageLumaA8, ImageRgba8),
 HxWx2 / HxWx3 / HxWx4 uint16 (ImageLumaA16, ImageRgb16, ImageRgba16).  BGR / BGRA order and channel-first planes (3xHxW uint8)
@@ -149,6 +150,7 @@ class TagDetector:
         self._batch = None
         self._detect = None  # detect_batch_enqueue's batch: (n, cap, frames kept alive, device outputs or None)
         self._refine = None  # refine_points_enqueue's batch: (n, points per frame, tensors kept alive, device outputs or None)
+        self._decode = None  # decode_quads_enqueue's batch: (n, quads per frame, tensors kept alive, device outputs or None)
 
     new = classmethod(lambda cls, tag_family, optional_detector_params=None, device=0:
                       cls(tag_family, optional_detector_params, device))
@@ -396,6 +398,7 @@ class TagDetector:
         self._batch = (n, frames)  # keep the tensor alive until fetched
         self._detect = None
         self._refine = None
+        self._decode = None
 
     def saddles_batch_enqueue_to(self, frames, out_saddles, frame_table, format=None):
         """Device-resident results: out_saddles float32 [capacity, 5] and frame_table int32
@@ -411,6 +414,7 @@ class TagDetector:
         self._batch = None
         self._detect = None
         self._refine = None
+        self._decode = None
 
     def saddles_batch_enqueue_ptr(self, dptr, n, w, h, row_stride, frame_stride, fmt, follow_torch_stream=True):
         """agx_saddles_batch_enqueue on a raw device address (any row / frame stride: a view cut out of a larger allocation).
@@ -424,6 +428,7 @@ class TagDetector:
         self._batch = (n, None)
         self._detect = None
         self._refine = None
+        self._decode = None
 
     def saddles_batch_fetch(self, cap_per_frame=None, raise_on_overflow=True):
         """-> (list of SADDLE_DTYPE arrays, one per frame; per-frame status array).  cap_per_frame None:
@@ -483,6 +488,7 @@ class TagDetector:
         self._batch = None  # (one batch in flight per handle: this one replaces a saddle batch)
         self._detect = None
         self._refine = None
+        self._decode = None
         if out is None:
             self._check(self._lib.agx_detect_batch_enqueue(self._h, C.c_void_p(dptr), n, w, h, row_stride, frame_stride, fmt, cap))
         else:
@@ -562,7 +568,7 @@ class TagDetector:
         out = np.zeros(n, SADDLE_DTYPE)
         status = np.zeros(n, np.uint32)
         n_refined = C.c_uint32(0)
-        self._batch = self._detect = self._refine = None
+        self._batch = self._detect = self._refine = self._decode = None
         self._check(self._lib.agx_rochade_refine(self._h, a.ctypes.data, w, h, stride, fmt, self._refine_image(image), pts.ctypes.data, n,
                                                  out.ctypes.data, status.ctypes.data, C.byref(n_refined)))
         assert n_refined.value == int((status == _ffi.AGX_POINT_REFINED).sum())
@@ -593,7 +599,7 @@ class TagDetector:
         p_out = tensor(out, torch.float32, (n, ppf, 5), "out") if out is not None else None
         p_status = tensor(status, torch.int32, (n, ppf), "status") if status is not None else None
         self._follow_torch_stream(frames)
-        self._batch = self._detect = self._refine = None
+        self._batch = self._detect = self._refine = self._decode = None
         self._check(self._lib.agx_refine_points_enqueue(self._h, frames.data_ptr(), n, w, h, rs, fs, fmt, self._refine_image(image), p_points,
                                                         ppf, p_counts, p_out, p_status))
         self._refine = (n, ppf, (frames, points, counts), (out, status) if out is not None else None)
@@ -605,6 +611,7 @@ class TagDetector:
             raise AgxError(_ffi.AGX_ERR_STATE, "no refine batch enqueued")
         n, ppf, _, dev_out = self._refine
         self._refine = None
+        self._decode = None
         if dev_out is not None:
             self._check(self._lib.agx_refine_points_fetch(self._h, None, None))
             return dev_out
@@ -612,6 +619,92 @@ class TagDetector:
         status = np.full((n, ppf), 0xFFFFFFFF, np.uint32)
         self._check(self._lib.agx_refine_points_fetch(self._h, out.ctypes.data, status.ctypes.data))
         return out, status
+
+    # ---- try_decode_quad of caller-given quads (src/detector.rs:448-476) --------------------
+    def decode_quads(self, image, quads, format=None, with_bits=False):
+        """try_decode_quad of every quad of `quads` (n x 4 corners (x, y), any array that reshapes to [n, 8]) on a host image
+        of any format but a float32 plane; the saddle chain is not run.  -> (tags [n] TAG_DTYPE, status [n] uint32 AGX_QUAD_*),
+        in input order; with_bits: also bit_code's values [n] uint64.  tags[i] is zero unless status[i] == AGX_QUAD_DECODED:
+        id = the index into the family's code list, xy = the corners after rotate_left(rotation); reverse() (:467-470)."""
+        a, fmt, stride = _image_args(image, format)
+        h, w = _image_hw(a, fmt)
+        q = np.ascontiguousarray(quads, np.float32).reshape(-1, 8)
+        n = q.shape[0]
+        out = np.zeros(n, self.TAG_DTYPE)
+        status = np.zeros(n, np.uint32)
+        bits = np.zeros(n, np.uint64)
+        n_decoded = C.c_uint32(0)
+        self._batch = self._detect = self._refine = self._decode = None
+        self._check(self._lib.agx_decode_quads(self._h, a.ctypes.data, w, h, stride, fmt, q.ctypes.data, n, out.ctypes.data,
+                                               status.ctypes.data, bits.ctypes.data if with_bits else None, C.byref(n_decoded)))
+        assert n_decoded.value == int((status == _ffi.AGX_QUAD_DECODED).sum())
+        return (out, status, bits) if with_bits else (out, status)
+
+    def decode_quads_enqueue(self, frames, quads=None, counts=None, out=None, status=None, bits=None, refined=None, format=None):
+        """try_decode_quad over a batch on this detector's GPU, stream-ordered behind torch's current stream; returns immediately.
+        frames and format= as saddles_batch_enqueue (float32 planes are refused).  quads: float32 [N,Q,4,2] (or [N,Q,8]) device
+        tensor.  refined=(records, point_status) instead of quads: refine_points_enqueue's out [N,4Q,5] and status [N,4Q] device
+        tensors as they are -- that batch need not be fetched first; a quad with a corner that was not refined is
+        AGX_QUAD_SKIPPED.  counts: optional int32 [N], the quads of frame f (at most Q; slots beyond are not written).
+        out int32 [N,Q,9] (split_device_tags reads it) and status int32 [N,Q]: device-resident results (both or neither),
+        bits int64 [N,Q] optionally with them -- without them decode_quads_fetch returns arrays."""
+        import torch
+        fmt, bpp = self._tensor_format(frames, format)
+        n, w, h, rs, fs = self._tensor_geometry(frames, fmt, bpp)
+        dev = frames.device
+
+        def tensor(t, dtype, shape, what):
+            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == shape and t.device == dev):
+                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s tensor %s on the frames' device" % (what, dtype, shape))
+            return t.data_ptr()
+
+        if (quads is None) == (refined is None):
+            raise AgxError(_ffi.AGX_ERR_ARG, "quads or refined=(records, point_status): one of them")
+        p_point_status = None
+        if refined is not None:
+            records, point_status = refined
+            if not (getattr(records, "is_cuda", False) and records.dim() == 3 and records.shape[0] == n and records.shape[1] % 4 == 0
+                    and records.shape[1] > 0 and records.shape[2] == 5):
+                raise AgxError(_ffi.AGX_ERR_ARG, "refined records must be a device tensor [N, 4 Q, 5]")
+            qpf, stride = int(records.shape[1]) // 4, 20
+            p_quads = tensor(records, torch.float32, (n, 4 * qpf, 5), "refined records")
+            p_point_status = tensor(point_status, torch.int32, (n, 4 * qpf), "refined point status")
+        else:
+            if not (getattr(quads, "is_cuda", False) and quads.dim() in (3, 4) and quads.shape[0] == n and quads.shape[1] > 0
+                    and tuple(quads.shape[2:]) in ((8,), (4, 2))):
+                raise AgxError(_ffi.AGX_ERR_ARG, "quads must be a device tensor [N, Q, 4, 2] or [N, Q, 8]")
+            qpf, stride = int(quads.shape[1]), 8
+            p_quads = tensor(quads, torch.float32, tuple(quads.shape), "quads")
+        p_counts = tensor(counts, torch.int32, (n,), "counts") if counts is not None else None
+        if (out is None) != (status is None):
+            raise AgxError(_ffi.AGX_ERR_ARG, "out and status: both or neither")
+        if bits is not None and out is None:
+            raise AgxError(_ffi.AGX_ERR_ARG, "bits goes with out and status (without them decode_quads_fetch returns the bits)")
+        p_out = tensor(out, torch.int32, (n, qpf, 9), "out") if out is not None else None
+        p_status = tensor(status, torch.int32, (n, qpf), "status") if status is not None else None
+        p_bits = tensor(bits, torch.int64, (n, qpf), "bits") if bits is not None else None
+        self._follow_torch_stream(frames)
+        self._batch = self._detect = self._refine = self._decode = None
+        self._check(self._lib.agx_decode_quads_enqueue(self._h, frames.data_ptr(), n, w, h, rs, fs, fmt, p_quads, stride, qpf, p_counts,
+                                                       p_point_status, p_out, p_status, p_bits))
+        self._decode = (n, qpf, (frames, quads, refined, counts), (out, status, bits) if out is not None else None)
+
+    def decode_quads_fetch(self):
+        """Wait for decode_quads_enqueue's batch -> (tags [N,Q] TAG_DTYPE, status [N,Q] uint32, bits [N,Q] uint64); slots beyond a
+        frame's count read zero tags, status 0xFFFFFFFF and bits 0.  After decode_quads_enqueue(out=, status=): those device
+        tensors (out, status, bits or None)."""
+        if self._decode is None:
+            raise AgxError(_ffi.AGX_ERR_STATE, "no decode batch enqueued")
+        n, qpf, _, dev_out = self._decode
+        self._decode = None
+        if dev_out is not None:
+            self._check(self._lib.agx_decode_quads_fetch(self._h, None, None, None))
+            return dev_out
+        out = np.zeros((n, qpf), self.TAG_DTYPE)
+        status = np.full((n, qpf), 0xFFFFFFFF, np.uint32)
+        bits = np.zeros((n, qpf), np.uint64)
+        self._check(self._lib.agx_decode_quads_fetch(self._h, out.ctypes.data, status.ctypes.data, bits.ctypes.data))
+        return out, status, bits
 
     # ---- measurement / parity hooks ------------------------------------------------------
     def profile_enable(self, level=2):
@@ -676,6 +769,29 @@ class TagDetector:
         if code in (3, 4):
             return buf[: n.value].copy()
         return buf
+
+
+def decode_quads_tail(tag_family, luma8, quads, with_bits=False):
+    """The host's try_decode_quad (src/detector.rs:448-476) without a device: luma8 an HxW uint8 plane (to_luma8; rows may be
+    strided), quads n x 4 corners (x, y).  -> (tags [n] TagDetector.TAG_DTYPE, status [n] uint32 AGX_QUAD_*) and, with_bits,
+    bit_code's values [n] uint64 -- what TagDetector.decode_quads returns."""
+    fam = TagFamily.from_str(tag_family) if isinstance(tag_family, str) else TagFamily(tag_family)
+    g = np.asarray(luma8)
+    if g.dtype != np.uint8 or g.ndim != 2 or g.strides[1] != 1 or g.strides[0] < g.shape[1]:
+        g = np.ascontiguousarray(luma8, np.uint8)
+    h, w = g.shape
+    q = np.ascontiguousarray(quads, np.float32).reshape(-1, 8)
+    n = q.shape[0]
+    out = np.zeros(n, TagDetector.TAG_DTYPE)
+    status = np.zeros(n, np.uint32)
+    bits = np.zeros(n, np.uint64)
+    n_decoded = C.c_uint32(0)
+    st = _ffi.lib().agx_decode_quads_tail(int(fam), g.ctypes.data, w, h, g.strides[0], q.ctypes.data, n, out.ctypes.data, status.ctypes.data,
+                                          bits.ctypes.data if with_bits else None, C.byref(n_decoded))
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    assert n_decoded.value == int((status == _ffi.AGX_QUAD_DECODED).sum())
+    return (out, status, bits) if with_bits else (out, status)
 
 
 class DetectorGroup:

@@ -116,6 +116,13 @@ pub const AGX_POINT_NOT_SADDLE: c_int = 2;
 pub const AGX_POINT_MOVED: c_int = 3;
 pub const AGX_REFINE_BLURRED: c_int = 0;
 pub const AGX_REFINE_PLANE: c_int = 1;
+// try_decode_quad of caller-given quads (reference src/detector.rs:448-476): what became of a quad
+pub const AGX_QUAD_DECODED: c_int = 0;
+pub const AGX_QUAD_OUTSIDE: c_int = 1;
+pub const AGX_QUAD_LOW_CONTRAST: c_int = 2;
+pub const AGX_QUAD_AMBIGUOUS: c_int = 3;
+pub const AGX_QUAD_NO_MATCH: c_int = 4;
+pub const AGX_QUAD_SKIPPED: c_int = 5;
 // agx_debug_fetch items
 pub const AGX_DBG_BLUR: c_int = 0;
 pub const AGX_DBG_RESP: c_int = 1;
@@ -183,6 +190,18 @@ extern "C" {
     pub fn agx_rochade_refine(det: *mut agx_detector, pixels: *const c_void, width: c_int, height: c_int, row_stride_bytes: usize,
                               format: c_int, image: c_int, points: *const c_void, n_points: u32, out: *mut agx_saddle,
                               status: *mut u32, n_refined: *mut u32) -> c_int;
+
+    pub fn agx_decode_quads_enqueue(det: *mut agx_detector, d_frames: *const c_void, n_frames: c_int, width: c_int, height: c_int,
+                                    row_stride_bytes: usize, frame_stride_bytes: usize, format: c_int, d_quads: *const c_void,
+                                    point_stride_bytes: usize, quads_per_frame: u32, d_counts: *const u32, d_point_status: *const u32,
+                                    d_tags: *mut agx_tag, d_status: *mut u32, d_bits: *mut u64) -> c_int;
+    pub fn agx_decode_quads_fetch(det: *mut agx_detector, out: *mut agx_tag, status: *mut u32, bits: *mut u64) -> c_int;
+    pub fn agx_decode_quads(det: *mut agx_detector, pixels: *const c_void, width: c_int, height: c_int, row_stride_bytes: usize,
+                            format: c_int, quads: *const c_void, n_quads: u32, out: *mut agx_tag, status: *mut u32, bits: *mut u64,
+                            n_decoded: *mut u32) -> c_int;
+    pub fn agx_decode_quads_tail(family: c_int, luma8: *const u8, width: c_int, height: c_int, row_stride_bytes: usize,
+                                 quads: *const c_void, n_quads: u32, out: *mut agx_tag, status: *mut u32, bits: *mut u64,
+                                 n_decoded: *mut u32) -> c_int;
 
     pub fn agx_detect_from_saddles(det: *const agx_detector, saddles: *const agx_saddle, n_saddles: u32, luma8: *const u8, width: c_int,
                                    height: c_int, row_stride_bytes: usize, out: *mut agx_tag, cap: u32, n_out: *mut u32) -> c_int;

@@ -228,6 +228,47 @@ impl TagDetector {
         (out.iter().map(|s| Saddle { p: (s.x, s.y), k: s.k, theta: s.theta, phi: s.phi }).collect(), status)
     }
 
+    /// reference src/detector.rs:448-476, `try_decode_quad(&self, img, quad)` for every quad of `quads` (the crate's pub fns
+    /// `decode_positions`, `bit_code`, `best_tag` and the corner rotation of :467-470), on `img.to_luma8()`; the board search is
+    /// not run.  `Some((id, corners))` where the reference returns `Some`, in input order.
+    pub fn decode_quads(&self, img: &image::DynamicImage, quads: &[[(f32, f32); 4]]) -> Vec<Option<(u32, [(f32, f32); 4])>> {
+        self.decode_quads_with_status(img, quads).0
+    }
+
+    /// The same with the reason for every `None` (`AGX_QUAD_OUTSIDE`, `_LOW_CONTRAST`, `_AMBIGUOUS`, `_NO_MATCH`; a corner that is
+    /// not finite is `AGX_QUAD_OUTSIDE`) and `bit_code`'s value where there is one, in input order.
+    pub fn decode_quads_with_status(&self, img: &image::DynamicImage, quads: &[[(f32, f32); 4]]) -> (Vec<Option<(u32, [(f32, f32); 4])>>, Vec<u32>, Vec<u64>) {
+        let (inp, w, h) = Self::input(img);
+        let (px, stride, fmt) = match &inp {
+            Input::Native { px, stride, fmt, .. } => (*px, *stride, *fmt),
+            Input::Planes { luma8, .. } => (luma8.as_raw().as_ptr() as *const c_void, w as usize, ffi::AGX_L8),
+        };
+        let flat: Vec<f32> = quads.iter().flat_map(|q| q.iter().flat_map(|p| [p.0, p.1])).collect();
+        let mut out = vec![ffi::agx_tag { id: 0, xy: [0.0; 8] }; quads.len()];
+        let mut status = vec![0u32; quads.len()];
+        let mut bits = vec![0u64; quads.len()];
+        let mut n_decoded = 0u32;
+        let st = self.with_handle(|d| unsafe {
+            ffi::agx_decode_quads(
+                d, px, w as c_int, h as c_int, stride, fmt, flat.as_ptr() as *const c_void, quads.len() as u32, out.as_mut_ptr(),
+                status.as_mut_ptr(), bits.as_mut_ptr(), &mut n_decoded,
+            )
+        });
+        assert_eq!(st, ffi::AGX_OK, "agx_decode_quads failed: {}", st);
+        let tags = out
+            .iter()
+            .zip(&status)
+            .map(|(t, s)| {
+                if *s == ffi::AGX_QUAD_DECODED as u32 {
+                    Some((t.id, [(t.xy[0], t.xy[1]), (t.xy[2], t.xy[3]), (t.xy[4], t.xy[5]), (t.xy[6], t.xy[7])]))
+                } else {
+                    None
+                }
+            })
+            .collect();
+        (tags, status, bits)
+    }
+
     fn tags_to_map(out: &[ffi::agx_tag]) -> HashMap<u32, [(f32, f32); 4]> {
         // later entries replace earlier ones, as HashMap::insert does at src/detector.rs:520
         out.iter().map(|t| (t.id, [(t.xy[0], t.xy[1]), (t.xy[2], t.xy[3]), (t.xy[4], t.xy[5]), (t.xy[6], t.xy[7])])).collect()

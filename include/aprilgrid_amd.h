@@ -362,6 +362,71 @@ int agx_rochade_refine(agx_detector *det, const void *pixels, int width, int hei
                        int image, const void *points, uint32_t n_points, agx_saddle *out, uint32_t *status,
                        uint32_t *n_refined);
 
+/* ---- decode of caller-given quads -------------------------------------------------------- */
+
+/* TagDetector::try_decode_quad(&self, img, quad) -> Option<(usize, [(f32,f32);4])> -- src/detector.rs:448-476 -- built from the
+ * crate's pub fns decode_positions (:42-72), bit_code (:74-122) and best_tag (:142-169): which tag is in ANY quad (a tracked
+ * board's corners, corners predicted from a pose, agx_refine_points_enqueue's output), without the board search that detect
+ * runs to find its quads.  The decode reads to_luma8 of the image; the saddle chain is not run.  Every quad is answered in its
+ * own slot, in input order, with an agx_tag, one of these statuses and (optionally) bit_code's value; the agx_tag of a quad
+ * that is not AGX_QUAD_DECODED is all zero. */
+enum { AGX_QUAD_DECODED = 0,      /* src/detector.rs:448-476: id = index into the family's code list, xy = the input corners
+                                     after rotate_left(rotation); reverse() (:467-470) */
+       AGX_QUAD_OUTSIDE = 1,      /* a corner coordinate that is not finite (decided first, before anything is read); or
+                                     :50-56, a rounded corner with x >= width or y >= height under Rust's saturating `as u32`
+                                     (a finite negative coordinate saturates to 0 and is inside, as in the reference); or
+                                     :84-93, a sample point outside the image */
+       AGX_QUAD_LOW_CONTRAST = 2, /* :97-99: max - min < 50 over the samples */
+       AGX_QUAD_AMBIGUOUS = 3,    /* :117-118: more than 3 samples within 10 of the mid brightness */
+       AGX_QUAD_NO_MATCH = 4,     /* :160-168: no rotation within the family's Hamming distance of a code */
+       AGX_QUAD_SKIPPED = 5 };    /* d_point_status was given and one of the quad's corners is not AGX_POINT_REFINED: nothing
+                                     of the quad's pixels is read */
+
+/* try_decode_quad (src/detector.rs:448-476) over a batch in DEVICE memory, stream-ordered on the detector's stream (the
+ * caller's after agx_detector_set_stream); returns without waiting.  d_frames / n_frames / width / height / strides / format
+ * as agx_detect_batch_enqueue; AGX_LF32 is AGX_ERR_FORMAT.  L8 frames are read as they are; of every other format the
+ * frames' to_luma8 plane is computed on the device first (as agx_detect_batch_enqueue does).
+ * Quad q of frame f has four points; point p is two floats (x, y) at
+ * d_quads + ((f*quads_per_frame + q)*4 + p) * point_stride_bytes.  point_stride_bytes is a multiple of 4 and at least 8, and
+ * d_quads is 4-byte aligned: 8 is a packed [n][4][2] float array, 20 reads agx_saddle records --
+ * agx_refine_points_enqueue's d_out with points_per_frame = 4*quads_per_frame is a valid d_quads as it stands.
+ * d_point_status: NULL, or that call's d_status, one word per point: a quad with a corner whose word is not
+ * AGX_POINT_REFINED is AGX_QUAD_SKIPPED.  d_counts: NULL, or per-frame quad counts as in agx_refine_points_enqueue (a count above
+ * quads_per_frame means quads_per_frame; slots at or beyond a frame's count are not written).
+ * Results, slot = f*quads_per_frame + q: d_tags[slot], d_status[slot] (AGX_QUAD_*), and, if d_bits is given, d_bits[slot] =
+ * bit_code's value before any rotation for AGX_QUAD_DECODED and AGX_QUAD_NO_MATCH slots, 0 for the others.  d_tags and
+ * d_status are caller-owned device memory (4-byte aligned; d_bits 8-byte aligned, may be NULL on its own), or both NULL:
+ * internal buffers, copied out by agx_decode_quads_fetch, whose `bits` argument then decides about the bits (d_bits must be
+ * NULL here).  Frames, quads, counts and point statuses stay in place until the fetch has returned.
+ * A fourth kind of batch on the handle: one batch is in flight, a later enqueue of any kind replaces it; the other kinds'
+ * fetches of it are AGX_ERR_STATE.  Replacing is not waiting and not discarding: an agx_refine_points_enqueue batch whose
+ * results go to caller-owned device arrays need not be fetched before those arrays are passed here -- the kernels run in
+ * stream order, so the decode reads the finished records and statuses (the refine batch is then no longer fetchable).
+ * AGX_ERR_ARG: NULL d_frames or d_quads, quads_per_frame == 0, a bad point stride, exactly one of d_tags / d_status NULL. */
+int agx_decode_quads_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height,
+                             size_t row_stride_bytes, size_t frame_stride_bytes, int format,
+                             const void *d_quads, size_t point_stride_bytes, uint32_t quads_per_frame,
+                             const uint32_t *d_counts, const uint32_t *d_point_status,
+                             agx_tag *d_tags, uint32_t *d_status, uint64_t *d_bits);
+/* Wait for the batch of agx_decode_quads_enqueue (src/detector.rs:448-476).  Internal buffers: out and status, host arrays
+ * of n_frames*quads_per_frame entries, receive the slots the batch wrote (slots at or beyond a frame's count stay as they
+ * were); bits, the same for bit_code's values, may be NULL.  Caller-owned device buffers: out, status and bits are NULL, the
+ * call only waits.  AGX_ERR_STATE: no such batch in flight (another kind, none, or fetched already). */
+int agx_decode_quads_fetch(agx_detector *det, agx_tag *out, uint32_t *status, uint64_t *bits);
+/* try_decode_quad (src/detector.rs:448-476) of n_quads quads of one image in HOST memory: uploads pixels and quads (a packed
+ * [n_quads][8] float array: x, y of the four corners), runs a batch of one and writes out, status and, unless NULL, bits
+ * (n_quads entries each, in input order) and *n_decoded, the number of AGX_QUAD_DECODED ones.  n_quads == 0: AGX_OK,
+ * *n_decoded = 0. */
+int agx_decode_quads(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes, int format,
+                     const void *quads, uint32_t n_quads, agx_tag *out, uint32_t *status, uint64_t *bits,
+                     uint32_t *n_decoded);
+/* The host's try_decode_quad (src/detector.rs:448-476) without a detector handle (no device needed, like agx_detect_tail):
+ * family as in agx_detector_create, luma8 the to_luma8 plane in host memory, quads a packed [n_quads][8] float array.
+ * Statuses, zero records and bits as the batch call's; bits may be NULL. */
+int agx_decode_quads_tail(int family, const uint8_t *luma8, int width, int height, size_t row_stride_bytes,
+                          const void *quads, uint32_t n_quads, agx_tag *out, uint32_t *status, uint64_t *bits,
+                          uint32_t *n_decoded);
+
 /* ---- detector groups: several GPUs of one node driven from ONE process ----------------- */
 
 /* The reference's detect(&self) is stateless, so a batch shards by frame:
@@ -482,7 +547,7 @@ enum { AGX_DBG_BLUR = 0, AGX_DBG_RESP = 1, AGX_DBG_MIN = 2, AGX_DBG_CENTERS = 3,
                                check of the check).  Buffers = the chain's workspace, then the staging buffer, the luma
                                planes and the device tail's code list, tag rows and frame table (mapped pinned host memory), then
                                agx_detect_batch_enqueue_to's device-memory tag rows and frame table, agx_detect_batch_fetch's
-                               pinned luma planes, the front-end kernel's luma plane (AGX_LA8 .. AGX_RGBA16), the stored / recomputed response planes, and agx_refine_points_enqueue's internal records and statuses and agx_rochade_refine's points, as far as they exist.  Needs no enqueued batch.  Guard bytes exist only in handles created with
+                               pinned luma planes, the front-end kernel's luma plane (AGX_LA8 .. AGX_RGBA16), the stored / recomputed response planes, agx_refine_points_enqueue's internal records and statuses and agx_rochade_refine's points, and agx_decode_quads_enqueue's internal tags, statuses and bits and agx_decode_quads' quads, as far as they exist.  Needs no enqueued batch.  Guard bytes exist only in handles created with
                                AGX_REDZONE_BYTES=<n> in the environment (memory-safety tests of the kernels) */
        AGX_DBG_TAIL_TABLE_ADDR = 11 /* 2 x uint64: host address and payload bytes of the device tail's frame table (the check
                                        of the check for a buffer in mapped host memory).  Needs no enqueued batch */ };
