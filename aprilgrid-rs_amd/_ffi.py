@@ -21,6 +21,8 @@ AGX_POINT_REFINED, AGX_POINT_OUTSIDE, AGX_POINT_NOT_SADDLE, AGX_POINT_MOVED = 0,
 AGX_REFINE_BLURRED, AGX_REFINE_PLANE = 0, 1
 # try_decode_quad of caller-given quads (src/detector.rs:448-476): what became of a quad
 AGX_QUAD_DECODED, AGX_QUAD_OUTSIDE, AGX_QUAD_LOW_CONTRAST, AGX_QUAD_AMBIGUOUS, AGX_QUAD_NO_MATCH, AGX_QUAD_SKIPPED = 0, 1, 2, 3, 4, 5
+# try_find_best_board of caller-given saddle lists (src/detector.rs:588-639): what became of a frame
+AGX_BOARD_FOUND, AGX_BOARD_NONE, AGX_BOARD_CAPACITY, AGX_BOARD_INPUT, AGX_BOARD_PENDING = 0, 1, 2, 3, 4
 AGX_DBG_BLUR, AGX_DBG_RESP, AGX_DBG_MIN, AGX_DBG_CENTERS, AGX_DBG_REFINED = 0, 1, 2, 3, 4
 AGX_N_KERNELS = 5
 
@@ -90,6 +92,10 @@ SYMBOLS = {
     "agx_decode_quads_fetch": (C.c_int, [_P, _P, _P, _P]),
     "agx_decode_quads": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32)]),
     "agx_decode_quads_tail": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_size_t, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32)]),
+    "agx_find_boards_enqueue": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
+    "agx_find_boards_fetch": (C.c_int, [_P, _P, _P, _P, _P, C.c_int]),
+    "agx_find_board": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "agx_find_board_tail": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "agx_group_create": (C.c_int, [C.c_int, C.POINTER(Params), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "agx_group_destroy": (None, [_P]),
     "agx_group_size": (C.c_int, [_P]),

@@ -985,6 +985,7 @@ int agx::decode_quads_enqueue_impl(agx_detector *det, const void *d_frames, int 
     det->detect.kind = 0;
     det->refine.kind = 0;
     det->decode.kind = 0;
+    det->find.kind = 0;
     det->front_format = -1;
     det->enqueued = false;
     if (tail_prepare(det)) return fail(det, AGX_ERR_HIP, "hipMalloc / hipMemcpy: the family's code list");
@@ -1037,6 +1038,8 @@ int agx::decode_quads_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *stat
 {
     if (!det) return AGX_ERR_ARG;
     const DecodePending b = det->decode;
+    if (!b.kind && det->find.kind)
+        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_find_boards_enqueue's: fetch it with agx_find_boards_fetch");
     if (!b.kind) return fail(det, AGX_ERR_STATE, "no agx_decode_quads_enqueue batch in flight");
     if (b.kind == 1 && (!out || !status)) return fail(det, AGX_ERR_ARG, "null output");  // (the batch stays in flight)
     if (hipSetDevice(det->device) != hipSuccess) return fail(det, AGX_ERR_HIP, "hipSetDevice");
@@ -1077,6 +1080,213 @@ int agx::decode_quads_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *stat
         }
     }
     return AGX_OK;
+}
+
+// ---- agx_find_boards_enqueue / _fetch: try_find_best_board (src/detector.rs:588-639) of caller-given saddle lists --------------
+// k_find_boards on the detector's stream, one workgroup per frame.  No pixels, no chain, no workspace.  Without the device tail
+// (option "device_tail" 0, or this process's atan2f is not the routine the kernel restates) the kernel only marks every frame
+// AGX_BOARD_PENDING, and the fetch's host form answers them all.
+int agx::find_boards_enqueue_impl(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
+                                  const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status,
+                                  uint32_t quads_per_frame, uint32_t *d_quads, float *d_quad_points, uint32_t *d_n_quads, uint32_t *d_status)
+{
+    if (!det) return AGX_ERR_ARG;
+    if (!d_saddles || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null saddles or n_frames <= 0");
+    if (saddle_stride_bytes < 20 || (saddle_stride_bytes & 3) || saddle_stride_bytes > 0x7fffffffu)
+        return fail(det, AGX_ERR_ARG, "saddle_stride_bytes must be a multiple of 4 and at least 20");
+    if (!saddles_per_frame || !quads_per_frame) return fail(det, AGX_ERR_ARG, "saddles_per_frame and quads_per_frame must be > 0");
+    if (d_counts && d_frame_table) return fail(det, AGX_ERR_ARG, "d_counts and d_frame_table: at most one of them");
+    if ((d_quads == nullptr) != (d_n_quads == nullptr) || (d_quads == nullptr) != (d_status == nullptr))
+        return fail(det, AGX_ERR_ARG, "d_quads, d_n_quads and d_status: all or none");
+    if (((uintptr_t)d_saddles | (uintptr_t)d_counts | (uintptr_t)d_frame_table | (uintptr_t)d_point_status | (uintptr_t)d_quads |
+         (uintptr_t)d_quad_points | (uintptr_t)d_n_quads | (uintptr_t)d_status) & 3)
+        return fail(det, AGX_ERR_ARG, "saddles, counts, frame table, point statuses and the results must be 4-byte aligned");
+    if (n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
+    const size_t rows = (size_t)n_frames * quads_per_frame;
+    if (rows >= ((size_t)1 << 27)) return fail(det, AGX_ERR_ARG, "at most 2^27 - 1 quad rows per batch");
+    if (hipSetDevice(det->device) != hipSuccess) return fail(det, AGX_ERR_HIP, "hipSetDevice");
+    // this batch replaces whatever was in flight
+    det->detect.kind = 0;
+    det->refine.kind = 0;
+    det->decode.kind = 0;
+    det->find.kind = 0;
+    det->front_format = -1;
+    det->enqueued = false;
+    const bool host_only = device_tail_mode(det) == 0;
+    if (!host_only && tail_prepare(det)) return fail(det, AGX_ERR_HIP, "the device tail's set-up (code list, kernel attributes)");
+    int kind = 2;
+    if (!d_quads) {
+        d_quads = static_cast<uint32_t *>(side_ensure(det, SB_FIND_QUADS, rows * 4 * sizeof(uint32_t), 0));
+        d_n_quads = static_cast<uint32_t *>(side_ensure(det, SB_FIND_COUNTS, (size_t)n_frames * sizeof(uint32_t), 0));
+        d_status = static_cast<uint32_t *>(side_ensure(det, SB_FIND_STATUS, (size_t)n_frames * sizeof(uint32_t), 0));
+        if (!d_quad_points) d_quad_points = static_cast<float *>(side_ensure(det, SB_FIND_POINTS, rows * 8 * sizeof(float), 0));
+        if (!d_quads || !d_n_quads || !d_status || !d_quad_points) return fail(det, AGX_ERR_HIP, "hipMalloc: board quads");
+        kind = 1;
+    }
+    FindBoardsArgs q{};
+    q.saddles = static_cast<const uint8_t *>(d_saddles);
+    q.stride = (uint32_t)saddle_stride_bytes;
+    q.n_frames = n_frames;
+    q.saddles_per_frame = saddles_per_frame;
+    q.counts = d_counts;
+    q.frame_table = static_cast<const uint32_t *>(d_frame_table);
+    q.point_status = d_point_status;
+    q.quads_per_frame = quads_per_frame;
+    q.quads = d_quads;
+    q.quad_points = d_quad_points;
+    q.n_quads = d_n_quads;
+    q.status = d_status;
+    q.debug_band = (float)det->tail_debug_band_mdeg * 1e-3f;
+    q.host_only = host_only ? 1 : 0;
+    const hipError_t e = (hipError_t)launch_find_boards(q, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_find_boards: ") + hipGetErrorString(e));
+    FindPending &p = det->find;
+    p.kind = kind;
+    p.n_frames = n_frames;
+    p.saddles_per_frame = saddles_per_frame;
+    p.quads_per_frame = quads_per_frame;
+    p.stride = saddle_stride_bytes;
+    p.d_saddles = q.saddles;
+    p.d_counts = d_counts;
+    p.d_frame_table = q.frame_table;
+    p.d_point_status = d_point_status;
+    p.d_quads = d_quads;
+    p.d_n_quads = d_n_quads;
+    p.d_status = d_status;
+    p.d_quad_points = d_quad_points;
+    return AGX_OK;
+}
+
+int agx::find_boards_fetch_impl(agx_detector *det, uint32_t *quads, float *quad_points, uint32_t *n_quads, uint32_t *status, int n_threads)
+{
+    if (!det) return AGX_ERR_ARG;
+    const FindPending b = det->find;
+    if (!b.kind) return fail(det, AGX_ERR_STATE, "no agx_find_boards_enqueue batch in flight");
+    if (b.kind == 1 && (!quads || !n_quads || !status)) return fail(det, AGX_ERR_ARG, "null output");  // (the batch stays in flight)
+    if (hipSetDevice(det->device) != hipSuccess) return fail(det, AGX_ERR_HIP, "hipSetDevice");
+    det->find.kind = 0;  // resolved by this call, whatever it returns
+    det->last_find_frames = b.n_frames;
+    det->last_find_handed_back = 0;
+    if (n_threads <= 0) n_threads = agx_host_parallelism();
+    hipStream_t stream = det->stream;
+    const size_t n = (size_t)b.n_frames, qpf = b.quads_per_frame;
+    int rc = AGX_OK;
+    try {
+        std::vector<uint32_t> h_status(n), h_count(n, 0u);
+        if (hipMemcpyAsync(h_status.data(), b.d_status, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipStreamSynchronize(stream) != hipSuccess)
+            return fail(det, AGX_ERR_HIP, "agx_find_boards_fetch: copy / wait");
+        std::vector<int> pending;
+        for (size_t f = 0; f < n; ++f)
+            if (h_status[f] == AGX_BOARD_PENDING) pending.push_back((int)f);
+        det->last_find_handed_back = (int)pending.size();
+        // the handed-back frames: their slots (and status words) down, the host form on the pool, the answers up
+        std::vector<std::vector<uint8_t>> slots(pending.size());
+        std::vector<std::vector<uint32_t>> words(pending.size()), rows(pending.size());
+        std::vector<std::vector<float>> pts(pending.size());
+        if (!pending.empty()) {
+            WorkerPool *pool = worker_pool(det, n_threads);
+            if (!pool) return fail(det, AGX_ERR_ARG, "n_threads");
+            std::vector<uint32_t> own(b.d_frame_table ? 4 * n : (b.d_counts ? n : 0));  // the frames' own slots: table entries or counts
+            if (!own.empty() &&
+                (hipMemcpyAsync(own.data(), b.d_frame_table ? b.d_frame_table : b.d_counts, own.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                 hipStreamSynchronize(stream) != hipSuccess))
+                return fail(det, AGX_ERR_HIP, "agx_find_boards_fetch: the frames' counts");
+            bool ok = true;
+            std::vector<char> no_list(pending.size(), 0);
+            for (size_t k = 0; k < pending.size() && ok; ++k) {
+                const size_t f = (size_t)pending[k];
+                size_t first = f * b.saddles_per_frame, count = b.saddles_per_frame;
+                if (b.d_frame_table) {
+                    count = own[4 * f];
+                    first = own[4 * f + 1];
+                    if (own[4 * f + 2] & 7u) {  // an overflow bit: there is no list (the kernel says so itself unless it read nothing)
+                        no_list[k] = 1;
+                        continue;
+                    }
+                } else if (b.d_counts) {
+                    count = std::min<size_t>(own[f], b.saddles_per_frame);
+                }
+                if (!count) continue;
+                slots[k].resize((count - 1) * b.stride + sizeof(agx_saddle));
+                ok = hipMemcpyAsync(slots[k].data(), b.d_saddles + first * b.stride, slots[k].size(), hipMemcpyDeviceToHost, stream) == hipSuccess;
+                if (ok && b.d_point_status) {
+                    words[k].resize(count);
+                    ok = hipMemcpyAsync(words[k].data(), b.d_point_status + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
+                }
+            }
+            if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, "agx_find_boards_fetch: the handed-back frames' lists");
+            std::atomic<bool> nomem{false};
+            const bool want_pts = b.d_quad_points != nullptr;
+            try {
+            for (size_t k = 0; k < pending.size(); ++k) {
+                const size_t f = (size_t)pending[k];
+                if (no_list[k]) {
+                    h_status[f] = AGX_BOARD_INPUT;
+                    continue;
+                }
+                const size_t stride = b.stride;
+                pool->submit([&, k, f, stride, want_pts] {
+                    try {
+                        const uint32_t count = slots[k].empty() ? 0u : (uint32_t)((slots[k].size() - sizeof(agx_saddle)) / stride + 1);
+                        const int st = find_board_in_slots(slots[k].data(), stride, count, words[k].empty() ? nullptr : words[k].data(), rows[k]);
+                        uint32_t nq = (uint32_t)(rows[k].size() / 4);
+                        h_status[f] = (uint32_t)st;
+                        if (st == AGX_BOARD_FOUND && nq > qpf) {
+                            h_status[f] = AGX_BOARD_CAPACITY;
+                            rows[k].clear();
+                        }
+                        h_count[f] = st == AGX_BOARD_FOUND ? nq : 0u;
+                        if (want_pts)
+                            for (uint32_t s : rows[k]) {
+                                float xy[2];
+                                std::memcpy(xy, slots[k].data() + (size_t)s * stride, sizeof xy);
+                                pts[k].push_back(xy[0]);
+                                pts[k].push_back(xy[1]);
+                            }
+                    } catch (...) {
+                        nomem.store(true);
+                    }
+                });
+            }
+            } catch (...) {  // a task could not be queued: the ones that were read this call's vectors
+                (void)pool->wait();
+                throw;
+            }
+            if (!pool->wait() || nomem.load()) return fail(det, AGX_ERR_NOMEM, "agx_find_boards_fetch: the host form");
+            for (size_t k = 0; k < pending.size() && ok; ++k) {
+                const size_t f = (size_t)pending[k];
+                if (!rows[k].empty())
+                    ok = hipMemcpyAsync(b.d_quads + f * qpf * 4, rows[k].data(), rows[k].size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess &&
+                         (!want_pts || hipMemcpyAsync(b.d_quad_points + f * qpf * 8, pts[k].data(), pts[k].size() * sizeof(float), hipMemcpyHostToDevice, stream) == hipSuccess);
+                ok = ok && hipMemcpyAsync(b.d_n_quads + f, &h_count[f], sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess &&
+                     hipMemcpyAsync(b.d_status + f, &h_status[f], sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess;
+            }
+            if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, "agx_find_boards_fetch: the host form's answers to the device");
+        }
+        // the caller's host arrays: counts and statuses, and the rows below each frame's count
+        if (quads || quad_points || n_quads || status) {
+            std::vector<uint32_t> h_quads(quads ? n * qpf * 4 : 0);
+            std::vector<float> h_pts(quad_points && b.d_quad_points ? n * qpf * 8 : 0);
+            if (quad_points && !b.d_quad_points) return fail(det, AGX_ERR_ARG, "quad_points: the batch was enqueued without d_quad_points");
+            bool ok = hipMemcpyAsync(h_count.data(), b.d_n_quads, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
+                      hipMemcpyAsync(h_status.data(), b.d_status, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
+            if (ok && quads) ok = hipMemcpyAsync(h_quads.data(), b.d_quads, h_quads.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
+            if (ok && quad_points) ok = hipMemcpyAsync(h_pts.data(), b.d_quad_points, h_pts.size() * sizeof(float), hipMemcpyDeviceToHost, stream) == hipSuccess;
+            if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, "agx_find_boards_fetch: copy / wait");
+            for (size_t f = 0; f < n; ++f) {
+                if (n_quads) n_quads[f] = h_count[f];
+                if (status) status[f] = h_status[f];
+                if (h_status[f] != AGX_BOARD_FOUND || !h_count[f]) continue;
+                const size_t nq = std::min<size_t>(h_count[f], qpf);
+                if (quads) std::memcpy(quads + f * qpf * 4, h_quads.data() + f * qpf * 4, nq * 4 * sizeof(uint32_t));
+                if (quad_points) std::memcpy(quad_points + f * qpf * 8, h_pts.data() + f * qpf * 8, nq * 8 * sizeof(float));
+            }
+        }
+    } catch (...) {
+        rc = fail(det, AGX_ERR_NOMEM, "agx_find_boards_fetch: host memory");
+    }
+    return rc;
 }
 
 // The host tail of the frames `back` marks (1 handed back, 2 handed back as uncertain; without the device tail: every frame) of

@@ -725,6 +725,8 @@ int agx_detector_get_option(const agx_detector *det, const char *name, int *valu
     else if (!std::strcmp(name, "tail_threads")) *value = det->tail_threads;
     else if (!std::strcmp(name, "device_tail")) *value = det->device_tail;  // (-1: by the batch's size, where available)
     else if (!std::strcmp(name, "tail_debug_band")) *value = det->tail_debug_band_mdeg;
+    else if (!std::strcmp(name, "last_find_boards_frames")) *value = det->last_find_frames;  // (of the last agx_find_boards_fetch)
+    else if (!std::strcmp(name, "last_find_boards_handed_back")) *value = det->last_find_handed_back;
     else if (!std::strcmp(name, "last_device_tail_frames")) *value = det->last_tail_frames;
     else if (!std::strcmp(name, "last_device_tail_fallbacks")) *value = det->last_tail_fallbacks;
     else if (!std::strcmp(name, "last_device_tail_uncertain")) *value = det->last_tail_uncertain;  // (of them: an angle inside its guard band)
@@ -772,6 +774,7 @@ static int batch_enqueue_impl(agx_detector *det, const void *d_frames, int n_fra
     det->detect.kind = 0;  // (this batch replaces whatever was in flight, an agx_detect_batch_enqueue's included)
     det->refine.kind = 0;  // (... and an agx_refine_points_enqueue's)
     det->decode.kind = 0;  // (... and an agx_decode_quads_enqueue's)
+    det->find.kind = 0;    // (... and an agx_find_boards_enqueue's)
     det->front_format = -1;
     HIP_TRY(det, hipSetDevice(det->device));
     int rc = ensure_workspace(det, n_frames, width, height);
@@ -941,6 +944,8 @@ int agx_saddles_batch_fetch(agx_detector *det, agx_saddle *out, uint32_t cap_per
         return fail(det, AGX_ERR_STATE, "the batch in flight is agx_refine_points_enqueue's: fetch it with agx_refine_points_fetch");
     if (det && det->decode.kind)
         return fail(det, AGX_ERR_STATE, "the batch in flight is agx_decode_quads_enqueue's: fetch it with agx_decode_quads_fetch");
+    if (det && det->find.kind)
+        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_find_boards_enqueue's: fetch it with agx_find_boards_fetch");
     if (det && det->enqueued && det->detect.kind)
         return fail(det, AGX_ERR_STATE, "the batch in flight is agx_detect_batch_enqueue's: fetch it with agx_detect_batch_fetch");
     return saddles_fetch_impl(det, out, cap_per_frame, counts, frame_status);
@@ -989,6 +994,8 @@ int agx_detect_batch_fetch(agx_detector *det, agx_tag *out, uint32_t *counts, in
         return fail(det, AGX_ERR_STATE, "the batch in flight is agx_refine_points_enqueue's: fetch it with agx_refine_points_fetch");
     if (det->decode.kind)
         return fail(det, AGX_ERR_STATE, "the batch in flight is agx_decode_quads_enqueue's: fetch it with agx_decode_quads_fetch");
+    if (det->find.kind)
+        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_find_boards_enqueue's: fetch it with agx_find_boards_fetch");
     if (!det->detect.kind || !det->enqueued) return fail(det, AGX_ERR_STATE, "no agx_detect_batch_enqueue batch in flight");
     if (det->detect.kind == 3) return fail(det, AGX_ERR_STATE, "the batch in flight is a group's: fetch it with agx_group_detect_fetch");
     det->last_error.clear();
@@ -1032,6 +1039,7 @@ static int refine_points_enqueue_impl(agx_detector *det, const void *d_frames, i
     det->detect.kind = 0;
     det->refine.kind = 0;
     det->decode.kind = 0;
+    det->find.kind = 0;
     det->front_format = -1;
     det->enqueued = false;
     RefinePointsArgs p{};
@@ -1084,6 +1092,8 @@ static int refine_points_fetch_impl(agx_detector *det, agx_saddle *out, uint32_t
     const RefinePending b = det->refine;
     if (!b.kind && det->decode.kind)
         return fail(det, AGX_ERR_STATE, "the batch in flight is agx_decode_quads_enqueue's: fetch it with agx_decode_quads_fetch");
+    if (!b.kind && det->find.kind)
+        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_find_boards_enqueue's: fetch it with agx_find_boards_fetch");
     if (!b.kind) return fail(det, AGX_ERR_STATE, "no agx_refine_points_enqueue batch in flight");
     if (b.kind == 1 && (!out || !status)) return fail(det, AGX_ERR_ARG, "null output");  // (the batch stays in flight)
     HIP_TRY(det, hipSetDevice(det->device));
@@ -1256,6 +1266,70 @@ int agx_decode_quads_tail(int family, const uint8_t *luma8, int width, int heigh
         if (bits) bits[i] = b;
     }
     *n_decoded = n;
+    return AGX_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- try_find_best_board of caller-given saddle lists (src/detector.rs:588-639; csrc/detect_batch.cpp, tail_kernels.hip) -------
+extern "C" {
+
+int agx_find_boards_enqueue(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
+                            const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status, uint32_t quads_per_frame,
+                            uint32_t *d_quads, float *d_quad_points, uint32_t *d_n_quads, uint32_t *d_status)
+{
+    return agx_guard(det, [&]() -> int {
+    return find_boards_enqueue_impl(det, d_saddles, saddle_stride_bytes, n_frames, saddles_per_frame, d_counts, d_frame_table, d_point_status,
+                                    quads_per_frame, d_quads, d_quad_points, d_n_quads, d_status);
+    });
+}
+
+int agx_find_boards_fetch(agx_detector *det, uint32_t *quads, float *quad_points, uint32_t *n_quads, uint32_t *status, int n_threads)
+{
+    return agx_guard(det, [&]() -> int { return find_boards_fetch_impl(det, quads, quad_points, n_quads, status, n_threads); });
+}
+
+int agx_find_board(agx_detector *det, const agx_saddle *saddles, uint32_t n_saddles, uint32_t *quads, uint32_t cap, uint32_t *n_quads,
+                   uint32_t *status)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    if (!n_quads || !status || (n_saddles && !saddles) || (cap && !quads)) return fail(det, AGX_ERR_ARG, "null argument");
+    *n_quads = 0;
+    *status = AGX_BOARD_NONE;
+    if (!n_saddles) return AGX_OK;
+    HIP_TRY(det, hipSetDevice(det->device));
+    void *d_list = side_ensure(det, SB_FIND_SADDLES, (size_t)n_saddles * sizeof(agx_saddle), 0);
+    if (!d_list) return fail(det, AGX_ERR_HIP, "hipMalloc: saddles");
+    HIP_TRY(det, hipMemcpyAsync(d_list, saddles, (size_t)n_saddles * sizeof(agx_saddle), hipMemcpyHostToDevice, det->stream));
+    // rows for the caller's cap: a board with more quads is AGX_BOARD_CAPACITY with its true count, as in a batch
+    const uint32_t qpf = cap ? cap : 1u;
+    int rc = find_boards_enqueue_impl(det, d_list, sizeof(agx_saddle), 1, n_saddles, nullptr, nullptr, nullptr, qpf, nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    std::vector<uint32_t> rows((size_t)qpf * 4);
+    uint32_t n = 0, st = 0;
+    rc = find_boards_fetch_impl(det, rows.data(), nullptr, &n, &st, 1);
+    if (rc) return rc;
+    if (st == AGX_BOARD_FOUND && n > cap) st = AGX_BOARD_CAPACITY;
+    if (st == AGX_BOARD_FOUND && n) std::memcpy(quads, rows.data(), (size_t)n * 4 * sizeof(uint32_t));
+    *n_quads = n;
+    *status = st;
+    return AGX_OK;
+    });
+}
+
+int agx_find_board_tail(const agx_saddle *saddles, uint32_t n_saddles, uint32_t *quads, uint32_t cap, uint32_t *n_quads, uint32_t *status)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (!n_quads || !status || (n_saddles && !saddles) || (cap && !quads)) return AGX_ERR_ARG;
+    std::vector<uint32_t> rows;
+    uint32_t st = (uint32_t)find_board_in_slots(saddles, sizeof(agx_saddle), n_saddles, nullptr, rows);
+    const uint32_t n = (uint32_t)(rows.size() / 4);
+    if (st == AGX_BOARD_FOUND && n > cap) st = AGX_BOARD_CAPACITY;
+    if (st == AGX_BOARD_FOUND && n) std::memcpy(quads, rows.data(), rows.size() * sizeof(uint32_t));
+    *n_quads = st == AGX_BOARD_FOUND || st == AGX_BOARD_CAPACITY ? n : 0u;
+    *status = st;
     return AGX_OK;
     });
 }

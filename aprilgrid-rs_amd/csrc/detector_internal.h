@@ -73,6 +73,19 @@ struct DecodePending {
     const uint32_t *d_counts = nullptr;  // the caller's per-frame counts (kind 1: the fetch copies only the slots that were written)
 };
 
+// agx_find_boards_enqueue: what agx_find_boards_fetch needs of the batch in flight.  The fifth kind of batch on a handle, with
+// DecodePending's rules.  The fetch reads the inputs again for the frames the kernel handed back (AGX_BOARD_PENDING).
+struct FindPending {
+    int kind = 0;  // 0 none, 1 results in SB_FIND_QUADS / _COUNTS / _STATUS (the fetch copies them out), 2 in the caller's device arrays
+    int n_frames = 0;
+    uint32_t saddles_per_frame = 0, quads_per_frame = 0;
+    size_t stride = 0;
+    const uint8_t *d_saddles = nullptr;
+    const uint32_t *d_counts = nullptr, *d_frame_table = nullptr, *d_point_status = nullptr;
+    uint32_t *d_quads = nullptr, *d_n_quads = nullptr, *d_status = nullptr;
+    float *d_quad_points = nullptr;  // the caller's, SB_FIND_POINTS (kind 1 without the caller's), or null
+};
+
 struct EventPair {
     hipEvent_t a, b;
     int kernel;
@@ -109,6 +122,11 @@ enum {
     SB_DECODE_STATUS,  // ... [n_frames][quads_per_frame] uint32 (AGX_QUAD_*) ...
     SB_DECODE_BITS,    // ... and [n_frames][quads_per_frame] uint64 (bit_code's value)
     SB_DECODE_QUADS,   // agx_decode_quads: the host's quads on the device
+    SB_FIND_QUADS,     // agx_find_boards_enqueue without caller-owned results: [n_frames][quads_per_frame][4] uint32 ...
+    SB_FIND_POINTS,    // ... [n_frames][quads_per_frame][4][2] float (unless the caller gave d_quad_points) ...
+    SB_FIND_COUNTS,    // ... [n_frames] uint32 ...
+    SB_FIND_STATUS,    // ... and [n_frames] uint32 (AGX_BOARD_*)
+    SB_FIND_SADDLES,   // agx_find_board: the host's list on the device
     SB_COUNT
 };
 }  // namespace agx
@@ -206,6 +224,8 @@ struct agx_detector {
     std::vector<uint32_t> refine_host;  // its host staging when per-frame counts were given (records, statuses, counts)
     agx::DecodePending decode;          // agx_decode_quads_enqueue: the batch agx_decode_quads_fetch resolves
     std::vector<uint64_t> decode_host;  // its host staging when per-frame counts were given (bits, tags, statuses, counts)
+    agx::FindPending find;              // agx_find_boards_enqueue: the batch agx_find_boards_fetch resolves
+    int last_find_frames = 0, last_find_handed_back = 0;  // of the last agx_find_boards_fetch
 
     std::string last_error;
 };
@@ -245,6 +265,11 @@ int decode_quads_enqueue_impl(agx_detector *det, const void *d_frames, int n_fra
                               uint32_t quads_per_frame, const uint32_t *d_counts, const uint32_t *d_point_status, agx_tag *d_tags,
                               uint32_t *d_status, uint64_t *d_bits);
 int decode_quads_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *status, uint64_t *bits);
+// try_find_best_board of caller-given saddle lists over a batch in device memory (detect_batch.cpp: k_find_boards, the fetch)
+int find_boards_enqueue_impl(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
+                             const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status, uint32_t quads_per_frame,
+                             uint32_t *d_quads, float *d_quad_points, uint32_t *d_n_quads, uint32_t *d_status);
+int find_boards_fetch_impl(agx_detector *det, uint32_t *quads, float *quad_points, uint32_t *n_quads, uint32_t *status, int n_threads);
 int group_detect_fetch_impl(agx_detector *det, const char *back, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads);
 // What group.cpp calls for rank r's share of a detect batch (detector.cpp: the entry points' argument checks and guard around
 // the two functions above).  After the enqueue det->detect.device_tail says whether the pack kernel ran.

@@ -1293,6 +1293,28 @@ int decode_quad(const FamilyInfo &fam, const uint8_t *luma8, uint32_t w, uint32_
     return AGX_QUAD_DECODED;
 }
 
+int find_board_in_slots(const void *slots, size_t stride, uint32_t n_slots, const uint32_t *point_status, std::vector<uint32_t> &quads)
+{
+    quads.clear();
+    std::vector<agx_saddle> list;
+    std::vector<uint32_t> slot_of;
+    for (uint32_t i = 0; i < n_slots; ++i) {
+        if (point_status && point_status[i] != 0u) continue;  // (AGX_POINT_REFINED is 0)
+        agx_saddle s;
+        std::memcpy(&s, static_cast<const char *>(slots) + (size_t)i * stride, sizeof s);
+        if (!std::isfinite(s.x) || !std::isfinite(s.y) || !std::isfinite(s.theta)) return AGX_BOARD_INPUT;  // (:594 panics on the coordinates)
+        s.k = 0.0f;  // (never read: whatever the slot holds there)
+        s.phi = 0.0f;
+        list.push_back(s);
+        slot_of.push_back(i);
+    }
+    std::vector<Quad> found;
+    if (!try_find_best_board(list, found, nullptr)) return AGX_BOARD_NONE;
+    for (const Quad &q : found)
+        for (int i = 0; i < 4; ++i) quads.push_back(slot_of[(size_t)q[i]]);
+    return AGX_BOARD_FOUND;
+}
+
 namespace {
 // detect's loop body (detector.rs:510-539) over a working copy of the saddle list (consumed: the saddles of decoded
 // quads are removed between the rounds)

@@ -51,6 +51,12 @@ struct TailWorkers {
 // chosen is the one the sequential loop chooses.
 bool try_find_best_board(const std::vector<agx_saddle> &refined, std::vector<Quad> &quads, TailWorkers *workers = nullptr);
 
+// The host form of agx_find_boards_enqueue / agx_find_board_tail: one try_find_best_board (detector.rs:588-639) over the slots
+// of one frame (floats x, y, k, theta, phi every `stride` bytes) that point_status admits (null: all; else a word per slot, 0 =
+// listed).  AGX_BOARD_INPUT (a listed x, y or theta that is not finite), AGX_BOARD_NONE or AGX_BOARD_FOUND with the quads as SLOT
+// numbers, four per quad, in all_tag_indexes' order.
+int find_board_in_slots(const void *slots, size_t stride, uint32_t n_slots, const uint32_t *point_status, std::vector<uint32_t> &quads);
+
 // image_util.rs:39-70 (h = 2x3 affine, row-major)
 void tag_affine(const float quad_xy[8], int side_bits, float margin, float h[6]);
 // detector.rs:124-140, 142-169

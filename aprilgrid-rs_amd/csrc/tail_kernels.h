@@ -88,6 +88,26 @@ struct DecodeQuadsArgs {
 };
 // one row of 16 lanes per slot, grid-stride; n_frames * quads_per_frame < 2^31; hipError_t
 int launch_decode_quads(const DecodeQuadsArgs &d, void *stream);
+// k_find_boards (agx_find_boards_enqueue): one try_find_best_board (detector.rs:588-639) per frame over caller-given saddle
+// slots -- k_board_tail's round up to its complete quad list, the quads out as slot numbers.  All pointers are device pointers.
+struct FindBoardsArgs {
+    const uint8_t *saddles;  // slot s: floats x, y, k, theta, phi at saddles + s * stride (k and phi are never read)
+    uint32_t stride;         // bytes: a multiple of 4, >= 20
+    int n_frames;
+    uint32_t saddles_per_frame;   // frame f owns the slots from f * saddles_per_frame ...
+    const uint32_t *counts;       // ... min(counts[f], saddles_per_frame) of them, or null: saddles_per_frame; or ...
+    const uint32_t *frame_table;  // ... agx_frame_result[n_frames]: count slots from offset (status & 7: AGX_BOARD_INPUT, nothing read)
+    const uint32_t *point_status;  // a word per slot (the batch's numbering), or null: only slots whose word is 0 enter the list
+    uint32_t quads_per_frame;
+    uint32_t *quads;      // [n_frames][quads_per_frame][4]: slot numbers WITHIN the frame; a frame's own rows only
+    float *quad_points;   // [n_frames][quads_per_frame][4][2] or null: the corners' x, y
+    uint32_t *n_quads;    // [n_frames]
+    uint32_t *status;     // [n_frames]: AGX_BOARD_* (AGX_BOARD_PENDING: handed back, the host form answers)
+    float debug_band;     // option "tail_debug_band", as TailArgs::debug_band
+    int host_only;        // every frame is AGX_BOARD_PENDING and nothing is read (option "device_tail" 0, or refused)
+};
+// one workgroup per frame, k_board_tail's LDS; needs init_tail_kernels on the device; hipError_t
+int launch_find_boards(const FindBoardsArgs &b, void *stream);
 int init_tail_kernels();  // per-device kernel attributes (current device); hipError_t
 
 }  // namespace agx

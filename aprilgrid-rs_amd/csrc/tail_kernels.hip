@@ -37,6 +37,8 @@
 //   the rest  (try_fix_missing, decode -- best_tag by rows of 16 lanes --, the tag map, removing the used saddles) on the first wave.
 //
 // k_decode_quads (at the end of the file) is the decode alone, for quads the caller names: agx_decode_quads_enqueue.
+// k_find_boards is the board search alone, for saddle lists the caller names (agx_find_boards_enqueue): the same body as
+// k_board_tail (board_tail_body), one round of it up to the complete quad list, which goes out instead of being decoded.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -970,7 +972,16 @@ __device__ int init_quads_w(const Ctx &c, uint8_t *wv, int s0, int lane, uint32_
     return nc;
 }
 
-__global__ void __launch_bounds__(64 * TW) k_board_tail(TailArgs a)
+__device__ __forceinline__ bool fb_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// The body of both kernels of the board search, one workgroup per frame.
+//   FIND false: k_board_tail -- up to max_boards rounds of try_find_best_board + try_decode_quad over the chain's list (a), tags out.
+//   FIND true:  k_find_boards -- exactly one try_find_best_board (detector.rs:588-639) over a caller-given list (b): the round
+//               up to the point where quads[n_quads] is complete, then the quads go out as slot numbers; no luma, no code list
+//               (their 5120 bytes of LDS hold the list-to-slot map).  Of `a` only debug_band / debug / debug_frame are read.
+// Everything FIND decides is a compile-time branch: each kernel's instruction stream holds its own side only.
+template <bool FIND>
+__device__ __forceinline__ void board_tail_body(const TailArgs &a, const FindBoardsArgs &b)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int f = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -995,9 +1006,16 @@ __global__ void __launch_bounds__(64 * TW) k_board_tail(TailArgs a)
     (void)n_cands_total; (void)n_boards; (void)dk;  // (only the timers' build reads them)
 #define DK(i) AGX_TT(do { const unsigned long long t_now = wall_clock64(); dk[i] += t_now - t_last; t_last = t_now; } while (0))
 #define TK(i) AGX_TT(do { const unsigned long long t_now = wall_clock64(); tk[i] += t_now - t_last; t_last = t_now; } while (0))
+    int n = 0, n_first = 0;
+    int group_no = 0;  // (counts the groups of seeds over all rounds)
+    u64 *codes = reinterpret_cast<u64 *>(lds + OFF_CODES);
+    uint32_t *slot_of = reinterpret_cast<uint32_t *>(lds + OFF_CODES);  // FIND: u32[TN], list position -> slot number within the frame
+    const uint8_t *luma = nullptr;
+    uint32_t tag_cap = 0;
+    if constexpr (!FIND) {
     const FrameCounters &fc = a.ctr[f];
-    int n = (int)fc.n_out;
-    const int n_first = n;
+    n = (int)fc.n_out;
+    n_first = n;
     const uint32_t cflags = fc.flags;
     if ((cflags & (FLAG_CAND_OVERFLOW | FLAG_ROOT_OVERFLOW | FLAG_OUT_OVERFLOW)) || n > TN) {  // (the whole workgroup alike)
         if (tid == 0) {
@@ -1009,8 +1027,6 @@ __global__ void __launch_bounds__(64 * TW) k_board_tail(TailArgs a)
         return;
     }
     if (tid < 8 + 6 * TW) sh[tid] = tid == 4 ? __float_as_uint(a.debug_band) : 0u;  // ([4]: white_block's debug band)
-    int group_no = 0;  // (counts the groups of seeds over all rounds)
-    u64 *codes = reinterpret_cast<u64 *>(lds + OFF_CODES);
     for (int i = tid; i < a.n_codes && i < TCODES; i += 64 * TW) codes[i] = a.codes[i];
     if (a.n_codes > TCODES) status |= TAIL_CAPACITY;
     {
@@ -1024,14 +1040,89 @@ __global__ void __launch_bounds__(64 * TW) k_board_tail(TailArgs a)
             if (!(fabsf(x) < 1e6f && fabsf(y) < 1e6f && t >= -180.0f && t <= 180.0f)) status |= TAIL_CAPACITY;
         }
     }
-    const uint8_t *luma = a.luma + (size_t)f * (size_t)a.luma_frame_stride;
-    const uint32_t tag_cap = a.tag_cap < (uint32_t)TTAGS ? a.tag_cap : (uint32_t)TTAGS;
+    luma = a.luma + (size_t)f * (size_t)a.luma_frame_stride;
+    tag_cap = a.tag_cap < (uint32_t)TTAGS ? a.tag_cap : (uint32_t)TTAGS;
     __syncthreads();
     if (status) atomicOr(&sh[0], status);
     __syncthreads();
     if (sh[0]) n = 0;  // nothing is searched; the status goes out below
+    } else {
+    // ---- the frame's list: its slots, those d_point_status admits, in slot order; decided before any search, all lanes alike ----
+    uint32_t early = 0xffffffffu;  // an AGX_BOARD_* status that ends the frame here
+    u64 first_slot = (u64)f * (u64)b.saddles_per_frame;  // (in the batch's slot numbering: where the records and status words are)
+    u64 n_slots = b.saddles_per_frame;
+    if (b.host_only) {
+        early = AGX_BOARD_PENDING;  // option "device_tail" 0, or refused: the fetch's host form answers every frame
+    } else if (b.frame_table) {
+        const uint32_t *e = b.frame_table + 4 * (size_t)f;  // agx_frame_result: count, offset, status
+        if (e[2] & 7u) early = AGX_BOARD_INPUT;  // an overflow bit: there is no list; nothing of the frame is read
+        n_slots = e[0];
+        first_slot = e[1];
+    } else if (b.counts) {
+        const uint32_t c = b.counts[f];
+        n_slots = c < b.saddles_per_frame ? c : b.saddles_per_frame;
+    }
+    if (early == 0xffffffffu) {
+        uint32_t *wcnt = hist;  // [TW]: listed slots of each wave's 64 (the histogram's space: cleared before its use)
+        bool bad = false;
+        u64 listed_all = 0;
+        for (u64 base = 0; base < n_slots; base += 64 * TW) {
+            const u64 i = base + (u64)tid;
+            bool listed = i < n_slots;
+            if (listed && b.point_status) listed = b.point_status[first_slot + i] == 0u;  // (AGX_POINT_REFINED is 0)
+            float x = 0.0f, y = 0.0f, t = 0.0f;
+            if (listed) {
+                const float *src = reinterpret_cast<const float *>(b.saddles + (first_slot + i) * (u64)b.stride);
+                x = src[0];
+                y = src[1];
+                t = src[3];
+                if (!(fb_finite(x) && fb_finite(y) && fb_finite(t))) bad = true;
+                // as the chain's lists above: anything else is the host form's business
+                else if (!(fabsf(x) < 1e6f && fabsf(y) < 1e6f && t >= -180.0f && t <= 180.0f)) status |= TAIL_CAPACITY;
+            }
+            const u64 mk = __ballot(listed);
+            if (lane == 0) wcnt[wave] = (uint32_t)__popcll(mk);
+            __syncthreads();
+            u64 at = listed_all + (u64)__popcll(mk & below), total = 0;
+            for (int w = 0; w < TW; ++w) {
+                const uint32_t cw = wcnt[w];
+                if (w < wave) at += cw;
+                total += cw;
+            }
+            if (listed && at < (u64)TN) {
+                sx[at] = x;
+                sy[at] = y;
+                st[at] = t;
+                slot_of[at] = (uint32_t)i;
+            }
+            listed_all += total;
+            __syncthreads();
+        }
+        if (tid < 8 + 6 * TW) sh[tid] = tid == 4 ? __float_as_uint(a.debug_band) : 0u;  // ([4]: white_block's debug band)
+        __syncthreads();
+        if (bad) atomicOr(&sh[3], 1u);
+        if (listed_all > (u64)TN) status |= TAIL_CAPACITY;
+        if (status) atomicOr(&sh[0], status);
+        __syncthreads();
+        if (sh[3]) early = AGX_BOARD_INPUT;  // (tree.add(..).unwrap() panics on these, :594)
+        else if (listed_all == 0) early = AGX_BOARD_NONE;  // :589-591
+        else if (sh[0]) early = AGX_BOARD_PENDING;
+        n = listed_all > (u64)TN ? TN : (int)listed_all;
+        n_first = n;
+        __syncthreads();  // (sh[3] is read; the search's first wave writes the shared words)
+        if (tid == 0) sh[3] = 0;
+    }
+    if (early != 0xffffffffu) {  // (the whole workgroup alike)
+        if (tid == 0) {
+            b.n_quads[f] = 0;
+            b.status[f] = early;
+        }
+        return;
+    }
+    __syncthreads();
+    }
 
-    for (int round = 0; round < a.max_boards && n > 0; ++round) {
+    for (int round = 0; round < (FIND ? 1 : a.max_boards) && n > 0; ++round) {
         // ---- the k-NN grid over this round's saddles (every wave derives the geometry, the first one fills the cells) ----
         Ctx c;
         c.sx = sx; c.sy = sy; c.st = st; c.gx = gx; c.gy = gy; c.gi = gi; c.gstart = gstart; c.n = n;
@@ -1313,6 +1404,14 @@ __global__ void __launch_bounds__(64 * TW) k_board_tail(TailArgs a)
             }
             wsync();
             TK(6);
+            if constexpr (FIND) {  // the board's quads are the result: sh[1] their number, sh[3] "Some"
+                status = wave_or_u(status);
+                if (lane == 0) {
+                    sh[1] = (uint32_t)n_quads;
+                    sh[3] = 1u;
+                    if (status) atomicOr(&sh[0], status);
+                }
+            } else {
 
             // ---- decode the board's quads (detector.rs:514-527); results in the candidates' space ---------------------
             float *dec_xy = reinterpret_cast<float *>(wv + WV_CAND);           // [BCELLS][8]
@@ -1430,8 +1529,10 @@ __global__ void __launch_bounds__(64 * TW) k_board_tail(TailArgs a)
                 sh[3] = (uint32_t)n_used;
                 if (status) atomicOr(&sh[0], status);
             }
+            }
         }
         __syncthreads();
+        if constexpr (FIND) break;  // exactly one try_find_best_board
         if (sh[0]) break;
         if (sh[3] == 0) break;  // nothing removed: the next round would repeat this one
         n = (int)sh[1];
@@ -1447,12 +1548,47 @@ __global__ void __launch_bounds__(64 * TW) k_board_tail(TailArgs a)
     if (a.debug >= 2 && f == a.debug_frame && tid == 0)
         printf("  expand_one: scan %llu reduce+filter %llu broadcast %llu combos %llu; calls %llu, with all four lists %llu; queries that missed the memo %llu of %llu\n", ek[0], ek[1], ek[2], ek[3], ek[5], ek[6], ek[7], 4 * ek[5]);
 #endif
+    if constexpr (FIND) {
+        // a status word: the frame is handed back (AGX_BOARD_PENDING until the fetch's host form has answered it).  Else the quads
+        // in all_tag_indexes' order, a corner per thread (BCELLS * 4 = the workgroup): the saddle's slot number within the frame
+        // and, optionally, its x, y.  More quads than quads_per_frame: the true count and no row.
+        const uint32_t nq = sh[1];
+        uint32_t fst = AGX_BOARD_FOUND;
+        if (st_all) fst = AGX_BOARD_PENDING;
+        else if (!sh[3]) fst = AGX_BOARD_NONE;  // no board scored above 0
+        else if (nq > b.quads_per_frame) fst = AGX_BOARD_CAPACITY;
+        if (fst == AGX_BOARD_FOUND && (uint32_t)tid < 4u * nq) {
+            const int idx = q_at(quads[tid >> 2], tid & 3);
+            const u64 at = ((u64)f * (u64)b.quads_per_frame + (u64)(tid >> 2)) * 4u + (u64)(tid & 3);
+            b.quads[at] = slot_of[idx];
+            if (b.quad_points) {
+                b.quad_points[2 * at] = sx[idx];
+                b.quad_points[2 * at + 1] = sy[idx];
+            }
+        }
+        if (tid == 0) {
+            b.n_quads[f] = fst == AGX_BOARD_FOUND || fst == AGX_BOARD_CAPACITY ? nq : 0u;
+            b.status[f] = fst;
+        }
+        (void)n_first; (void)n_tags; (void)t_start; (void)n_seeds_done;
+    } else {
     if (tid == 0) {
         a.table[4 * f] = st_all ? 0u : (uint32_t)n_tags;
         a.table[4 * f + 1] = st_all;
         a.table[4 * f + 2] = (uint32_t)(wall_clock64() - t_start);  // 100 MHz ticks this frame took
         a.table[4 * f + 3] = (uint32_t)n_first | (uint32_t)n_seeds_done << 16;  // saddles; seeds wave 0 listed quads for
     }
+    }
+}
+
+__global__ void __launch_bounds__(64 * TW) k_board_tail(TailArgs a) { board_tail_body<false>(a, FindBoardsArgs{}); }
+
+// agx_find_boards_enqueue: try_find_best_board (detector.rs:588-639) of caller-given saddle lists, one workgroup per frame
+__global__ void __launch_bounds__(64 * TW) k_find_boards(FindBoardsArgs b)
+{
+    TailArgs a{};
+    a.debug_band = b.debug_band;
+    board_tail_body<true>(a, b);
 }
 
 // agx_detect_batch_enqueue_to: frame f's entry of the tail's table (count, status) and its rows into the caller's arrays, as
@@ -1691,7 +1827,19 @@ int launch_publish_tags(const uint32_t *table, const agx_tag *tags, uint32_t tag
 
 int init_tail_kernels()
 {
-    return (int)hipFuncSetAttribute((const void *)k_board_tail, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    const hipError_t e = hipFuncSetAttribute((const void *)k_board_tail, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    if (e != hipSuccess) return (int)e;
+    return (int)hipFuncSetAttribute((const void *)k_find_boards, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+}
+
+int launch_find_boards(const FindBoardsArgs &b, void *stream)
+{
+    if (b.n_frames <= 0) return (int)hipSuccess;
+    if (b.stride < 20 || (b.stride & 3) || !b.saddles_per_frame || !b.quads_per_frame || (b.counts && b.frame_table) || !b.saddles || !b.quads ||
+        !b.n_quads || !b.status)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_find_boards, dim3((unsigned)b.n_frames), dim3(64 * TW), LDS_BYTES, (hipStream_t)stream, b);
+    return (int)hipGetLastError();
 }
 
 int launch_board_tail(const TailArgs &t, void *stream)

@@ -10,6 +10,7 @@ Same names, argument meaning and error behaviour as the reference where Python a
   TagDetector.detect_kornia           src/detector.rs:478-503
   TagDetector.rochade_refine          src/detector.rs:194-361 (the crate's pub fn, half_size_patch = 2)
   TagDetector.decode_quads            src/detector.rs:448-476 (try_decode_quad = the pub fns decode_positions, bit_code, best_tag)
+  TagDetector.find_board              src/detector.rs:588-639 (the crate's pub fn try_find_best_board)
 An image is a numpy array standing for the DynamicImage variants the reference is fed:
 HxW uint8 (ImageLuma8), HxW uint16 (ImageLuma16), HxWx3 uint8 (ImageRgb8); HxWx2 / HxWx4 uint8 (ImageLumaA8, ImageRgba8),
 HxWx2 / HxWx3 / HxWx4 uint16 (ImageLumaA16, ImageRgb16, ImageRgba16).  BGR / BGRA order and channel-first planes (3xHxW uint8)
@@ -151,6 +152,7 @@ class TagDetector:
         self._detect = None  # detect_batch_enqueue's batch: (n, cap, frames kept alive, device outputs or None)
         self._refine = None  # refine_points_enqueue's batch: (n, points per frame, tensors kept alive, device outputs or None)
         self._decode = None  # decode_quads_enqueue's batch: (n, quads per frame, tensors kept alive, device outputs or None)
+        self._find = None    # find_boards_enqueue's batch: (n, quads per frame, tensors kept alive, device outputs or None)
 
     new = classmethod(lambda cls, tag_family, optional_detector_params=None, device=0:
                       cls(tag_family, optional_detector_params, device))
@@ -398,7 +400,7 @@ class TagDetector:
         self._batch = (n, frames)  # keep the tensor alive until fetched
         self._detect = None
         self._refine = None
-        self._decode = None
+        self._decode = self._find = None
 
     def saddles_batch_enqueue_to(self, frames, out_saddles, frame_table, format=None):
         """Device-resident results: out_saddles float32 [capacity, 5] and frame_table int32
@@ -414,7 +416,7 @@ class TagDetector:
         self._batch = None
         self._detect = None
         self._refine = None
-        self._decode = None
+        self._decode = self._find = None
 
     def saddles_batch_enqueue_ptr(self, dptr, n, w, h, row_stride, frame_stride, fmt, follow_torch_stream=True):
         """agx_saddles_batch_enqueue on a raw device address (any row / frame stride: a view cut out of a larger allocation).
@@ -428,7 +430,7 @@ class TagDetector:
         self._batch = (n, None)
         self._detect = None
         self._refine = None
-        self._decode = None
+        self._decode = self._find = None
 
     def saddles_batch_fetch(self, cap_per_frame=None, raise_on_overflow=True):
         """-> (list of SADDLE_DTYPE arrays, one per frame; per-frame status array).  cap_per_frame None:
@@ -488,7 +490,7 @@ class TagDetector:
         self._batch = None  # (one batch in flight per handle: this one replaces a saddle batch)
         self._detect = None
         self._refine = None
-        self._decode = None
+        self._decode = self._find = None
         if out is None:
             self._check(self._lib.agx_detect_batch_enqueue(self._h, C.c_void_p(dptr), n, w, h, row_stride, frame_stride, fmt, cap))
         else:
@@ -568,7 +570,7 @@ class TagDetector:
         out = np.zeros(n, SADDLE_DTYPE)
         status = np.zeros(n, np.uint32)
         n_refined = C.c_uint32(0)
-        self._batch = self._detect = self._refine = self._decode = None
+        self._batch = self._detect = self._refine = self._decode = self._find = None
         self._check(self._lib.agx_rochade_refine(self._h, a.ctypes.data, w, h, stride, fmt, self._refine_image(image), pts.ctypes.data, n,
                                                  out.ctypes.data, status.ctypes.data, C.byref(n_refined)))
         assert n_refined.value == int((status == _ffi.AGX_POINT_REFINED).sum())
@@ -599,7 +601,7 @@ class TagDetector:
         p_out = tensor(out, torch.float32, (n, ppf, 5), "out") if out is not None else None
         p_status = tensor(status, torch.int32, (n, ppf), "status") if status is not None else None
         self._follow_torch_stream(frames)
-        self._batch = self._detect = self._refine = self._decode = None
+        self._batch = self._detect = self._refine = self._decode = self._find = None
         self._check(self._lib.agx_refine_points_enqueue(self._h, frames.data_ptr(), n, w, h, rs, fs, fmt, self._refine_image(image), p_points,
                                                         ppf, p_counts, p_out, p_status))
         self._refine = (n, ppf, (frames, points, counts), (out, status) if out is not None else None)
@@ -611,7 +613,7 @@ class TagDetector:
             raise AgxError(_ffi.AGX_ERR_STATE, "no refine batch enqueued")
         n, ppf, _, dev_out = self._refine
         self._refine = None
-        self._decode = None
+        self._decode = self._find = None
         if dev_out is not None:
             self._check(self._lib.agx_refine_points_fetch(self._h, None, None))
             return dev_out
@@ -634,7 +636,7 @@ class TagDetector:
         status = np.zeros(n, np.uint32)
         bits = np.zeros(n, np.uint64)
         n_decoded = C.c_uint32(0)
-        self._batch = self._detect = self._refine = self._decode = None
+        self._batch = self._detect = self._refine = self._decode = self._find = None
         self._check(self._lib.agx_decode_quads(self._h, a.ctypes.data, w, h, stride, fmt, q.ctypes.data, n, out.ctypes.data,
                                                status.ctypes.data, bits.ctypes.data if with_bits else None, C.byref(n_decoded)))
         assert n_decoded.value == int((status == _ffi.AGX_QUAD_DECODED).sum())
@@ -684,7 +686,7 @@ class TagDetector:
         p_status = tensor(status, torch.int32, (n, qpf), "status") if status is not None else None
         p_bits = tensor(bits, torch.int64, (n, qpf), "bits") if bits is not None else None
         self._follow_torch_stream(frames)
-        self._batch = self._detect = self._refine = self._decode = None
+        self._batch = self._detect = self._refine = self._decode = self._find = None
         self._check(self._lib.agx_decode_quads_enqueue(self._h, frames.data_ptr(), n, w, h, rs, fs, fmt, p_quads, stride, qpf, p_counts,
                                                        p_point_status, p_out, p_status, p_bits))
         self._decode = (n, qpf, (frames, quads, refined, counts), (out, status, bits) if out is not None else None)
@@ -696,7 +698,7 @@ class TagDetector:
         if self._decode is None:
             raise AgxError(_ffi.AGX_ERR_STATE, "no decode batch enqueued")
         n, qpf, _, dev_out = self._decode
-        self._decode = None
+        self._decode = self._find = None
         if dev_out is not None:
             self._check(self._lib.agx_decode_quads_fetch(self._h, None, None, None))
             return dev_out
@@ -705,6 +707,86 @@ class TagDetector:
         bits = np.zeros((n, qpf), np.uint64)
         self._check(self._lib.agx_decode_quads_fetch(self._h, out.ctypes.data, status.ctypes.data, bits.ctypes.data))
         return out, status, bits
+
+    # ---- try_find_best_board of caller-given saddle lists (src/detector.rs:588-639) --------
+    def find_board(self, saddles, cap=128):
+        """try_find_best_board of one host list (SADDLE_DTYPE array, or anything that reshapes to [n, 5] float32: x, y, k, theta,
+        phi) on this detector's GPU -> (quads [n_quads, 4] uint32 indices into the list, status AGX_BOARD_*, n_quads).  More than `cap`
+        quads: AGX_BOARD_CAPACITY and no rows."""
+        return _find_board_call(lambda *a: self._check(self._lib.agx_find_board(self._h, *a)), saddles, cap, self)
+
+    def find_boards_enqueue(self, saddles, counts=None, frame_table=None, point_status=None, quads_per_frame=128, quads=None,
+                            quad_points=None, n_quads=None, status=None):
+        """try_find_best_board once per frame over saddle lists on this detector's GPU, stream-ordered behind torch's current
+        stream; returns immediately.  saddles: float32 device tensor [N, S, K] with K >= 5 (x, y, k, theta, phi first: K = 5 is
+        refine_points_enqueue's out), frame f owning counts[f] (int32 [N], optional) of its S slots; or, with frame_table (int32
+        [N, 4], saddles_batch_enqueue_to's), the flat [capacity, K] list that call wrote.  point_status: int32, one word per
+        slot (refine_points_enqueue's status): only slots whose word is 0 are listed.  quads int32 [N, Q, 4], n_quads int32 [N]
+        and status int32 [N]: device-resident results (all or none; Q = quads_per_frame without them); quad_points float32
+        [N, Q, 4, 2] optionally -- with n_quads as counts it is decode_quads_enqueue's quads.  Indices are slot numbers
+        within the frame."""
+        import torch
+        if not (getattr(saddles, "is_cuda", False) and saddles.is_contiguous() and saddles.dtype == torch.float32 and saddles.shape[-1] >= 5):
+            raise AgxError(_ffi.AGX_ERR_ARG, "saddles must be a contiguous float32 device tensor [N, S, K >= 5] (or [capacity, K] with frame_table)")
+        dev = saddles.device
+        stride = 4 * int(saddles.shape[-1])
+
+        def tensor(t, dtype, shape, what):
+            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and (shape is None or tuple(t.shape) == shape)
+                    and t.device == dev):
+                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s tensor %s on the saddles' device" % (what, dtype, shape))
+            return t.data_ptr()
+
+        if frame_table is not None:
+            if saddles.dim() != 2 or frame_table.dim() != 2 or frame_table.shape[1] != 4:
+                raise AgxError(_ffi.AGX_ERR_ARG, "with frame_table [N, 4]: saddles [capacity, K]")
+            n, spf, n_slots = int(frame_table.shape[0]), int(saddles.shape[0]), int(saddles.shape[0])
+            p_table = tensor(frame_table, torch.int32, (n, 4), "frame_table")
+        else:
+            if saddles.dim() != 3 or saddles.shape[1] == 0:
+                raise AgxError(_ffi.AGX_ERR_ARG, "saddles must be [N, S, K]")
+            n, spf = int(saddles.shape[0]), int(saddles.shape[1])
+            n_slots, p_table = n * spf, None
+        p_counts = tensor(counts, torch.int32, (n,), "counts") if counts is not None else None
+        p_ps = None
+        if point_status is not None:
+            p_ps = tensor(point_status, torch.int32, None, "point_status")
+            if point_status.numel() != n_slots:
+                raise AgxError(_ffi.AGX_ERR_ARG, "point_status: one word per slot")
+        given = [t is not None for t in (quads, n_quads, status)]
+        if any(given) != all(given):
+            raise AgxError(_ffi.AGX_ERR_ARG, "quads, n_quads and status: all or none")
+        qpf = int(quads.shape[1]) if quads is not None and quads.dim() == 3 else int(quads_per_frame)
+        p_quads = tensor(quads, torch.int32, (n, qpf, 4), "quads") if quads is not None else None
+        p_n = tensor(n_quads, torch.int32, (n,), "n_quads") if n_quads is not None else None
+        p_st = tensor(status, torch.int32, (n,), "status") if status is not None else None
+        p_pts = tensor(quad_points, torch.float32, (n, qpf, 4, 2), "quad_points") if quad_points is not None else None
+        self._follow_torch_stream(saddles)
+        self._batch = self._detect = self._refine = self._decode = self._find = None
+        self._check(self._lib.agx_find_boards_enqueue(self._h, saddles.data_ptr(), stride, n, spf, p_counts, p_table, p_ps, qpf, p_quads, p_pts,
+                                                      p_n, p_st))
+        self._find = (n, qpf, (saddles, counts, frame_table, point_status, quad_points),
+                      (quads, quad_points, n_quads, status) if quads is not None else None)
+
+    def find_boards_fetch(self, n_threads=0):
+        """Wait for find_boards_enqueue's batch and let the host form answer the frames the kernel handed back ->
+        (quads [N, Q, 4] uint32, quad_points [N, Q, 4, 2] float32, n_quads [N] uint32, status [N] uint32 AGX_BOARD_*); rows at
+        or beyond a frame's count read 0xFFFFFFFF / NaN.  After find_boards_enqueue(quads=, n_quads=, status=): those device
+        tensors (quads, quad_points or None, n_quads, status), complete."""
+        if self._find is None:
+            raise AgxError(_ffi.AGX_ERR_STATE, "no find-boards batch enqueued")
+        n, qpf, keep, dev_out = self._find
+        self._batch = self._detect = self._refine = self._decode = self._find = None
+        if dev_out is not None:
+            self._check(self._lib.agx_find_boards_fetch(self._h, None, None, None, None, n_threads))
+            return dev_out
+        quads = np.full((n, qpf, 4), 0xFFFFFFFF, np.uint32)
+        pts = np.full((n, qpf, 4, 2), np.nan, np.float32)
+        n_quads = np.zeros(n, np.uint32)
+        status = np.zeros(n, np.uint32)
+        self._check(self._lib.agx_find_boards_fetch(self._h, quads.ctypes.data, pts.ctypes.data, n_quads.ctypes.data, status.ctypes.data,
+                                                    n_threads))
+        return quads, pts, n_quads, status
 
     # ---- measurement / parity hooks ------------------------------------------------------
     def profile_enable(self, level=2):
@@ -792,6 +874,31 @@ def decode_quads_tail(tag_family, luma8, quads, with_bits=False):
         raise AgxError(st)
     assert n_decoded.value == int((status == _ffi.AGX_QUAD_DECODED).sum())
     return (out, status, bits) if with_bits else (out, status)
+
+
+def _find_board_call(call, saddles, cap, keep=None):
+    a = np.asarray(saddles)
+    if a.dtype == SADDLE_DTYPE:
+        a = np.ascontiguousarray(a).view(np.float32)
+    a = np.ascontiguousarray(a, np.float32).reshape(-1, 5)
+    quads = np.zeros((max(int(cap), 0), 4), np.uint32)
+    n_quads, status = C.c_uint32(0), C.c_uint32(0)
+    if keep is not None:
+        keep._batch = keep._detect = keep._refine = keep._decode = keep._find = None
+    call(a.ctypes.data if a.shape[0] else None, a.shape[0], quads.ctypes.data if quads.shape[0] else None, quads.shape[0], C.byref(n_quads),
+         C.byref(status))
+    found = status.value == _ffi.AGX_BOARD_FOUND
+    return quads[:n_quads.value if found else 0].copy(), status.value, n_quads.value
+
+
+def find_board_tail(saddles, cap=128):
+    """The host's try_find_best_board (src/detector.rs:588-639) without a device: saddles a SADDLE_DTYPE array (or [n, 5] float32)
+    -> (quads [n_quads, 4] uint32 indices into the list, status AGX_BOARD_*, n_quads) -- what TagDetector.find_board returns."""
+    def call(*a):
+        st = _ffi.lib().agx_find_board_tail(*a)
+        if st != _ffi.AGX_OK:
+            raise AgxError(st)
+    return _find_board_call(call, saddles, cap)
 
 
 class DetectorGroup:

@@ -123,6 +123,12 @@ pub const AGX_QUAD_LOW_CONTRAST: c_int = 2;
 pub const AGX_QUAD_AMBIGUOUS: c_int = 3;
 pub const AGX_QUAD_NO_MATCH: c_int = 4;
 pub const AGX_QUAD_SKIPPED: c_int = 5;
+// try_find_best_board of caller-given saddle lists (reference src/detector.rs:588-639): what became of a frame
+pub const AGX_BOARD_FOUND: c_int = 0;
+pub const AGX_BOARD_NONE: c_int = 1;
+pub const AGX_BOARD_CAPACITY: c_int = 2;
+pub const AGX_BOARD_INPUT: c_int = 3;
+pub const AGX_BOARD_PENDING: c_int = 4;
 // agx_debug_fetch items
 pub const AGX_DBG_BLUR: c_int = 0;
 pub const AGX_DBG_RESP: c_int = 1;
@@ -202,6 +208,17 @@ extern "C" {
     pub fn agx_decode_quads_tail(family: c_int, luma8: *const u8, width: c_int, height: c_int, row_stride_bytes: usize,
                                  quads: *const c_void, n_quads: u32, out: *mut agx_tag, status: *mut u32, bits: *mut u64,
                                  n_decoded: *mut u32) -> c_int;
+
+    pub fn agx_find_boards_enqueue(det: *mut agx_detector, d_saddles: *const c_void, saddle_stride_bytes: usize, n_frames: c_int,
+                                   saddles_per_frame: u32, d_counts: *const u32, d_frame_table: *const c_void, d_point_status: *const u32,
+                                   quads_per_frame: u32, d_quads: *mut u32, d_quad_points: *mut c_float, d_n_quads: *mut u32,
+                                   d_status: *mut u32) -> c_int;
+    pub fn agx_find_boards_fetch(det: *mut agx_detector, quads: *mut u32, quad_points: *mut c_float, n_quads: *mut u32, status: *mut u32,
+                                 n_threads: c_int) -> c_int;
+    pub fn agx_find_board(det: *mut agx_detector, saddles: *const agx_saddle, n_saddles: u32, quads: *mut u32, cap: u32,
+                          n_quads: *mut u32, status: *mut u32) -> c_int;
+    pub fn agx_find_board_tail(saddles: *const agx_saddle, n_saddles: u32, quads: *mut u32, cap: u32, n_quads: *mut u32,
+                               status: *mut u32) -> c_int;
 
     pub fn agx_detect_from_saddles(det: *const agx_detector, saddles: *const agx_saddle, n_saddles: u32, luma8: *const u8, width: c_int,
                                    height: c_int, row_stride_bytes: usize, out: *mut agx_tag, cap: u32, n_out: *mut u32) -> c_int;

@@ -350,6 +350,29 @@ impl Drop for TagDetector {
     }
 }
 
+/// reference src/detector.rs:588-639, `try_find_best_board(refined: &[Saddle]) -> Option<Vec<[usize; 4]>>`: the quads of the
+/// best board in a saddle list, as indices into `refined`, in the reference's order.  The host form (no device is used).
+/// Panics on a saddle whose x, y or theta is not finite, as the reference does on such coordinates (:594).
+pub fn find_best_board(refined: &[Saddle]) -> Option<Vec<[usize; 4]>> {
+    let list: Vec<ffi::agx_saddle> =
+        refined.iter().map(|s| ffi::agx_saddle { x: s.p.0, y: s.p.1, k: s.k, theta: s.theta, phi: s.phi }).collect();
+    let mut cap = 128u32;
+    loop {
+        let mut quads = vec![0u32; cap as usize * 4];
+        let (mut n, mut status) = (0u32, 0u32);
+        let st = unsafe { ffi::agx_find_board_tail(list.as_ptr(), list.len() as u32, quads.as_mut_ptr(), cap, &mut n, &mut status) };
+        assert_eq!(st, ffi::AGX_OK, "agx_find_board_tail failed: {}", st);
+        match status as c_int {
+            ffi::AGX_BOARD_FOUND => {
+                return Some(quads[..n as usize * 4].chunks(4).map(|q| [q[0] as usize, q[1] as usize, q[2] as usize, q[3] as usize]).collect())
+            }
+            ffi::AGX_BOARD_CAPACITY => cap = n,
+            ffi::AGX_BOARD_NONE => return None,
+            _ => panic!("find_best_board: a saddle's x, y or theta is not finite"),
+        }
+    }
+}
+
 fn last_error(det: *const ffi::agx_detector) -> String {
     unsafe {
         let p = ffi::agx_last_error(det);

@@ -427,6 +427,74 @@ int agx_decode_quads_tail(int family, const uint8_t *luma8, int width, int heigh
                           const void *quads, uint32_t n_quads, agx_tag *out, uint32_t *status, uint64_t *bits,
                           uint32_t *n_decoded);
 
+/* ---- board search in caller-given saddle lists ------------------------------------------- */
+
+/* try_find_best_board(refined: &[Saddle]) -> Option<Vec<[usize; 4]>> -- src/detector.rs:588-639, a pub fn of the crate: which
+ * saddles of ANY list (last frame's corners after agx_refine_points_enqueue, another detector's, the device lists of
+ * agx_saddles_batch_enqueue_to) form the quads of a board, without running the saddle chain on pixels.  Between
+ * agx_refine_points_enqueue and agx_decode_quads_enqueue it completes detect's stages on the device, in stream order; each is
+ * usable alone.  A frame's answer is a count, one of these statuses and its quads: four saddle numbers each, quads in
+ * all_tag_indexes' order (cells in insertion order), within a quad the order init_quads gives (:577-581). */
+enum { AGX_BOARD_FOUND = 0,    /* src/detector.rs:588-639 returned Some: n_quads quads */
+       AGX_BOARD_NONE = 1,     /* None: an empty list (:589-591), or no board scored above 0 */
+       AGX_BOARD_CAPACITY = 2, /* more quads than the caller's rows hold: the true count and no row; nothing is truncated */
+       AGX_BOARD_INPUT = 3,    /* a listed saddle whose x, y or theta is not finite (the reference panics on such coordinates,
+                                  :594; a non-finite theta is refused as well), or a frame-table entry with an overflow bit.
+                                  Decided before any search */
+       AGX_BOARD_PENDING = 4 };/* device arrays only, between enqueue and fetch: the kernel handed the frame back to the host
+                                  form (src/detector.rs:588-639 on the host); final after agx_find_boards_fetch */
+
+/* try_find_best_board (src/detector.rs:588-639) once per frame over saddle lists in DEVICE memory, stream-ordered on the
+ * detector's stream (the caller's after agx_detector_set_stream); returns without waiting.  No pixels are read.
+ * d_saddles is a run of saddle SLOTS: slot s holds the floats x, y, k, theta, phi at d_saddles + s*saddle_stride_bytes (a
+ * multiple of 4, at least 20; 20 = agx_saddle records: agx_refine_points_enqueue's d_out and agx_saddles_batch_enqueue_to's
+ * d_saddles as they stand).  k and phi are never read.
+ *   d_counts       frame f owns the slots [f*saddles_per_frame, + min(d_counts[f], saddles_per_frame)); NULL: saddles_per_frame;
+ *   d_frame_table  instead (at most one of the two): the agx_frame_result entries of agx_saddles_batch_enqueue_to: frame f owns
+ *                  `count` slots from `offset` (saddles_per_frame does not bound them).  A frame whose status carries an overflow
+ *                  bit (AGX_FRAME_CANDIDATE_ / _CLUSTER_ / _SADDLE_OVERFLOW) is AGX_BOARD_INPUT and nothing of it is read;
+ *   d_point_status NULL, or one word per slot (indexed like the slots): only slots whose word is AGX_POINT_REFINED (0) enter
+ *                  the list, in slot order -- agx_refine_points_enqueue's d_out / d_status are read in place, and a caller
+ *                  removes the saddles of decoded quads between rounds of max_num_of_boards by marking their words non-zero.
+ * Results, frame f: d_n_quads[f], d_status[f] (AGX_BOARD_*), d_quads[f][quads_per_frame][4]: uint32 SLOT NUMBERS WITHIN THE
+ * FRAME (not positions in the list after d_point_status), and, if d_quad_points is given, [f][quads_per_frame][4][2] floats: the
+ * corners' x, y in that order -- with d_n_quads as d_counts a valid d_quads (point stride 8) of agx_decode_quads_enqueue.  Only
+ * rows below a frame's count are written; more quads than quads_per_frame is AGX_BOARD_CAPACITY with the true count and no row.
+ * A listed saddle whose x, y or theta is not finite makes the frame AGX_BOARD_INPUT; an empty list is AGX_BOARD_NONE; both
+ * before any search.  d_quads, d_n_quads and d_status are caller-owned device memory (4-byte aligned) or all NULL: internal
+ * buffers, copied out by agx_find_boards_fetch; d_quad_points is optional on its own.
+ * The kernel answers what the device tail of agx_detect_batch_enqueue answers (options "device_tail", "tail_debug_band"): a
+ * frame with more than 1024 listed saddles, a coordinate beyond 1e6, a theta outside [-180, 180], lists beyond the kernel's
+ * fixed sizes or an angle inside a guard band is AGX_BOARD_PENDING in d_status until agx_find_boards_fetch has run the host
+ * form on it -- the same rows either way.  With "device_tail" 0, or where it is refused, that is every frame.
+ * A fifth kind of batch on the handle (src/detector.rs:588-639): one batch is in flight, a later enqueue of any kind replaces
+ * it without waiting, the other kinds' fetches of it are AGX_ERR_STATE.  A refine batch into caller-owned arrays need not be
+ * fetched before those arrays are passed here, and this batch's caller-owned outputs may go straight into
+ * agx_decode_quads_enqueue once no frame can be pending (else: after the fetch).
+ * AGX_ERR_ARG: NULL d_saddles, a bad stride, saddles_per_frame or quads_per_frame == 0, both d_counts and d_frame_table, a mixed
+ * NULL / non-NULL d_quads, d_n_quads, d_status. */
+int agx_find_boards_enqueue(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames,
+                            uint32_t saddles_per_frame, const uint32_t *d_counts, const void *d_frame_table,
+                            const uint32_t *d_point_status, uint32_t quads_per_frame, uint32_t *d_quads,
+                            float *d_quad_points, uint32_t *d_n_quads, uint32_t *d_status);
+/* Wait for the batch of agx_find_boards_enqueue (src/detector.rs:588-639) and resolve every AGX_BOARD_PENDING frame: its listed
+ * slots are copied down, the host form runs on the detector's pool (n_threads host threads; 0: agx_host_parallelism()), and the
+ * frame's rows, count and status are written to the device arrays on the detector's stream before the call returns.  Internal
+ * buffers: quads [n_frames][quads_per_frame][4], n_quads and status [n_frames] are host arrays (required); quad_points
+ * [n_frames][quads_per_frame][4][2] may be NULL; rows at or beyond a frame's count stay as they were.  Caller-owned device
+ * arrays: all four may be NULL (given ones are filled the same way).  AGX_ERR_STATE: no such batch in flight. */
+int agx_find_boards_fetch(agx_detector *det, uint32_t *quads, float *quad_points, uint32_t *n_quads, uint32_t *status,
+                          int n_threads);
+/* try_find_best_board (src/detector.rs:588-639) of one list in HOST memory: uploads it, runs a batch of one and fetches it.
+ * quads [cap][4]: saddle indices into `saddles`; *n_quads the count, *status an AGX_BOARD_* value (never PENDING).
+ * n_saddles == 0: AGX_OK, AGX_BOARD_NONE. */
+int agx_find_board(agx_detector *det, const agx_saddle *saddles, uint32_t n_saddles, uint32_t *quads, uint32_t cap,
+                   uint32_t *n_quads, uint32_t *status);
+/* The host form of try_find_best_board (src/detector.rs:588-639) without a detector handle (no device needed, like
+ * agx_detect_tail): what agx_find_boards_fetch runs on a handed-back frame.  Statuses, counts and rows as the batch call's. */
+int agx_find_board_tail(const agx_saddle *saddles, uint32_t n_saddles, uint32_t *quads, uint32_t cap, uint32_t *n_quads,
+                        uint32_t *status);
+
 /* ---- detector groups: several GPUs of one node driven from ONE process ----------------- */
 
 /* The reference's detect(&self) is stateless, so a batch shards by frame:
@@ -547,7 +615,7 @@ enum { AGX_DBG_BLUR = 0, AGX_DBG_RESP = 1, AGX_DBG_MIN = 2, AGX_DBG_CENTERS = 3,
                                check of the check).  Buffers = the chain's workspace, then the staging buffer, the luma
                                planes and the device tail's code list, tag rows and frame table (mapped pinned host memory), then
                                agx_detect_batch_enqueue_to's device-memory tag rows and frame table, agx_detect_batch_fetch's
-                               pinned luma planes, the front-end kernel's luma plane (AGX_LA8 .. AGX_RGBA16), the stored / recomputed response planes, agx_refine_points_enqueue's internal records and statuses and agx_rochade_refine's points, and agx_decode_quads_enqueue's internal tags, statuses and bits and agx_decode_quads' quads, as far as they exist.  Needs no enqueued batch.  Guard bytes exist only in handles created with
+                               pinned luma planes, the front-end kernel's luma plane (AGX_LA8 .. AGX_RGBA16), the stored / recomputed response planes, agx_refine_points_enqueue's internal records and statuses and agx_rochade_refine's points, agx_decode_quads_enqueue's internal tags, statuses and bits and agx_decode_quads' quads, and agx_find_boards_enqueue's internal quads, quad points, counts and statuses and agx_find_board's list, as far as they exist.  Needs no enqueued batch.  Guard bytes exist only in handles created with
                                AGX_REDZONE_BYTES=<n> in the environment (memory-safety tests of the kernels) */
        AGX_DBG_TAIL_TABLE_ADDR = 11 /* 2 x uint64: host address and payload bytes of the device tail's frame table (the check
                                        of the check for a buffer in mapped host memory).  Needs no enqueued batch */ };
