@@ -96,6 +96,10 @@ SYMBOLS = {
     "agx_find_boards_fetch": (C.c_int, [_P, _P, _P, _P, _P, C.c_int]),
     "agx_find_board": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "agx_find_board_tail": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "agx_planes_enqueue": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_float, _P, _P, C.c_size_t,
+                                     C.c_size_t]),
+    "agx_gaussian_blur_f32": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_float, _P]),
+    "agx_hessian_response": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, _P]),
     "agx_group_create": (C.c_int, [C.c_int, C.POINTER(Params), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "agx_group_destroy": (None, [_P]),
     "agx_group_size": (C.c_int, [_P]),
@@ -123,6 +127,7 @@ SYMBOLS = {
     "agx_profile_read": (C.c_int, [_P, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "agx_debug_fetch": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "agx_detector_constants": (C.c_int, [_P, _P, _P, _P]),
+    "agx_debug_blur_weights": (C.c_int, [C.c_float, _P, C.c_int, C.POINTER(C.c_int)]),
 }
 
 

@@ -188,4 +188,37 @@ int launch_front_luma(const void *src, size_t row_stride, size_t frame_stride, i
 int launch_luma8(const void *src, size_t pitch, size_t frame_stride, int n_frames, int format, uint8_t *dst, int W, int H,
                  void *stream);
 
+
+// k_gauss_blur (agx_planes_enqueue): gaussian_blur_f32 (image_util.rs:110-206) of to_luma32f of n_frames frames, radius
+// 1 .. GB_MAX_RADIUS.  All pointers are device pointers.
+constexpr int GB_MAX_RADIUS = 16;
+constexpr int GB_TX = 64, GB_TY = 64;  // output tile of a workgroup
+constexpr int GB_HPITCH = GB_TX + 1;   // LDS pitch of the horizontal pass's result
+struct GaussBlurArgs {
+    const uint8_t *src;  // frames of format 0 .. 3 (AGX_L8, AGX_L16, AGX_RGB8, AGX_LF32)
+    long long src_frame_stride;  // bytes
+    int src_row_stride;          // bytes
+    int W, H;
+    float *dst;                  // frame f, row y at dst + f * dst_frame_stride + y * dst_row_stride; W floats per row are written
+    long long dst_frame_stride;  // floats
+    long long dst_row_stride;    // floats
+    int radius;
+    float w[2 * GB_MAX_RADIUS + 1];  // the taps (uniform: the kernel reads them by scalar loads)
+};
+size_t gauss_blur_lds_bytes(int radius);
+// grid (ceil(W / GB_TX), min(ceil(H / GB_TY), 65535), n_frames <= 65535); hipError_t
+int launch_gauss_blur(const GaussBlurArgs &a, int format, int n_frames, void *stream);
+
+// k_hessian_response (agx_planes_enqueue): hessian_response (image_util.rs:72-109) of to_luma32f of n_frames frames of format
+// 0 .. 3 (3: an f32 plane as it is, such as k_gauss_blur's).  Strides as GaussBlurArgs.
+struct HessianArgs {
+    const uint8_t *src;
+    long long src_frame_stride;
+    int src_row_stride;
+    int W, H;
+    float *dst;
+    long long dst_frame_stride, dst_row_stride;
+};
+int launch_hessian_response(const HessianArgs &a, int format, int n_frames, void *stream);
+
 }  // namespace agx

@@ -1970,6 +1970,17 @@ __device__ __forceinline__ void generic_frame(const ChainArgs &a, int frame)
 }
 
 
+// hessian_response of one interior pixel from its 3x3 neighbourhood (image_util.rs:100-104), in the reference's order
+__device__ __forceinline__ float hessian_det(float v11, float v12, float v13, float v21, float v22, float v23, float v31, float v32,
+                                             float v33)
+{
+    const float t22 = v22 * 2.0f;
+    const float lxx = (v21 - t22) + v23;
+    const float lyy = (v12 - t22) + v32;
+    const float lxy = (((v13 - v11) + v31) - v33) * 0.25f;
+    return lxx * lyy - lxy * lxy;
+}
+
 // Debug only (agx_debug_fetch AGX_DBG_RESP): the response plane K2 thresholds, materialised.
 __global__ void k_debug_resp(const float *__restrict__ blur, float *__restrict__ resp, int W, int H)
 {
@@ -1979,14 +1990,7 @@ __global__ void k_debug_resp(const float *__restrict__ blur, float *__restrict__
         float d = 0.0f;
         if (x > 0 && x < W - 1 && y > 0 && y < H - 1) {
             const float *c = blur + i;
-            const float v11 = c[-W - 1], v12 = c[-W], v13 = c[-W + 1];
-            const float v21 = c[-1], v22 = c[0], v23 = c[1];
-            const float v31 = c[W - 1], v32 = c[W], v33 = c[W + 1];
-            const float t22 = v22 * 2.0f;
-            const float lxx = (v21 - t22) + v23;
-            const float lyy = (v12 - t22) + v32;
-            const float lxy = (((v13 - v11) + v31) - v33) * 0.25f;
-            d = lxx * lyy - lxy * lxy;
+            d = hessian_det(c[-W - 1], c[-W], c[-W + 1], c[-1], c[0], c[1], c[W - 1], c[W], c[W + 1]);
         }
         resp[i] = d;
     }
@@ -3465,6 +3469,156 @@ int launch_debug_resp(const ChainArgs &a, int frame, float *dst, void *stream)
 {
     hipLaunchKernelGGL(k_debug_resp, dim3(1024), dim3(256), 0, (hipStream_t)stream,
                        a.blur + (size_t)frame * (size_t)a.plane, dst, a.W, a.H);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// agx_planes_enqueue: gaussian_blur_f32 (image_util.rs:110-206) at the caller's sigma and hessian_response
+// (image_util.rs:72-109) as planes of their own; not part of the chain (K1 keeps its 7-tap register design).
+// ------------------------------------------------------------------------------------------
+// to_luma32f of pixel x of a row: K1's conversion (convert_px) of the pixel in slot 0
+template <int FMT>
+__device__ __forceinline__ float luma32f_at(const uint8_t *__restrict__ rowp, int x)
+{
+    RawPx<FMT> r;
+    if (FMT == 0) r.d[0] = rowp[x];
+    else if (FMT == 1) r.d[0] = reinterpret_cast<const uint16_t *>(rowp)[x];
+    else if (FMT == 2) r.d[0] = (uint32_t)rowp[3 * (size_t)x] | ((uint32_t)rowp[3 * (size_t)x + 1] << 8) | ((uint32_t)rowp[3 * (size_t)x + 2] << 16);
+    else r.d[0] = reinterpret_cast<const uint32_t *>(rowp)[x];
+#pragma unroll
+    for (int i = 1; i < RawPx<FMT>::BPP; ++i) r.d[i] = 0u;
+    float m[4];
+    convert_px<FMT>(r, m);
+    return m[0];
+}
+
+// Four neighbouring outputs of one pass: out[j] = 0; out[j] += p[(j + i) * stride] * w[i] for i ascending (the reference's
+// multiply, then add, per tap: image_util.rs:145-152 / :197-201).  The four windows overlap in all but one value per tap, so a
+// tap costs one LDS read.
+__device__ __forceinline__ void blur_taps4(const float *p, int stride, int taps, const float *__restrict__ w, float out[4])
+{
+    float v0 = p[0], v1 = p[stride], v2 = p[2 * stride];
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+#pragma unroll 4
+    for (int i = 0; i < taps; ++i) {
+        const float v3 = p[(i + 3) * stride], wi = w[i];
+        a0 += v0 * wi;
+        a1 += v1 * wi;
+        a2 += v2 * wi;
+        a3 += v3 * wi;
+        v0 = v1;
+        v1 = v2;
+        v2 = v3;
+    }
+    out[0] = a0;
+    out[1] = a1;
+    out[2] = a2;
+    out[3] = a3;
+}
+
+// One workgroup per GB_TX x GB_TY output tile: the tile's luma with a halo of r on every side goes to LDS (clamped coordinates:
+// the reference's border rule of both passes), the horizontal pass runs LDS -> LDS over the tile's rows and its vertical halo,
+// the vertical pass LDS -> global.  Both LDS pitches are odd: the horizontal pass has a lane per row, the vertical pass a lane
+// per column, and neither then meets a bank twice.
+template <int FMT>
+__global__ void __launch_bounds__(256) k_gauss_blur(GaussBlurArgs a)
+{
+    extern __shared__ float gb_lds[];
+    const int r = a.radius, taps = 2 * r + 1, W = a.W, H = a.H;
+    const int rows_in = GB_TY + 2 * r, in_pitch = (GB_TX + 2 * r) | 1;
+    float *tile = gb_lds, *hbuf = gb_lds + rows_in * in_pitch;
+    const int t = (int)threadIdx.x, tx0 = (int)blockIdx.x * GB_TX;
+    const uint8_t *frame = a.src + (size_t)blockIdx.z * (size_t)a.src_frame_stride;
+    float *out = a.dst + (size_t)blockIdx.z * (size_t)a.dst_frame_stride;
+    for (int ty0 = (int)blockIdx.y * GB_TY; ty0 < H; ty0 += (int)gridDim.y * GB_TY) {
+        const int cols_in = GB_TX + 2 * r;
+        for (int k = t; k < rows_in * cols_in; k += 256) {
+            const int ry = k / cols_in, rx = k - ry * cols_in;
+            const int y = min(max(ty0 - r + ry, 0), H - 1), x = min(max(tx0 - r + rx, 0), W - 1);
+            tile[ry * in_pitch + rx] = luma32f_at<FMT>(frame + (size_t)y * (size_t)a.src_row_stride, x);
+        }
+        __syncthreads();
+        // horizontal: item = (staged row, group of 4 columns), rows fastest
+        for (int k = t; k < rows_in * (GB_TX / 4); k += 256) {
+            const int cg = k / rows_in, ry = k - cg * rows_in;
+            if (tx0 + 4 * cg >= W) continue;
+            float o[4];
+            blur_taps4(tile + ry * in_pitch + 4 * cg, 1, taps, a.w, o);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) hbuf[ry * GB_HPITCH + 4 * cg + j] = o[j];
+        }
+        __syncthreads();
+        // vertical: item = (column, group of 4 rows), columns fastest
+        for (int k = t; k < GB_TX * (GB_TY / 4); k += 256) {
+            const int rg = k / GB_TX, cx = k - rg * GB_TX;
+            const int x = tx0 + cx, y0 = ty0 + 4 * rg;
+            if (x >= W || y0 >= H) continue;
+            float o[4];
+            blur_taps4(hbuf + 4 * rg * GB_HPITCH + cx, GB_HPITCH, taps, a.w, o);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (y0 + j < H) out[(size_t)(y0 + j) * (size_t)a.dst_row_stride + (size_t)x] = o[j];
+        }
+        __syncthreads();  // (the next tile of this workgroup overwrites both LDS regions)
+    }
+}
+
+size_t gauss_blur_lds_bytes(int radius)
+{
+    const int rows_in = GB_TY + 2 * radius;
+    return (size_t)rows_in * (size_t)(((GB_TX + 2 * radius) | 1) + GB_HPITCH) * sizeof(float);
+}
+
+int launch_gauss_blur(const GaussBlurArgs &a, int format, int n_frames, void *stream)
+{
+    if (a.radius < 1 || a.radius > GB_MAX_RADIUS || n_frames <= 0 || n_frames > 65535 || a.W < 1 || a.H < 1) return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)((a.W + GB_TX - 1) / GB_TX), (unsigned)std::min((a.H + GB_TY - 1) / GB_TY, 65535), (unsigned)n_frames);
+    const size_t lds = gauss_blur_lds_bytes(a.radius);
+    hipStream_t st = (hipStream_t)stream;
+    switch (format) {
+    case 0: hipLaunchKernelGGL((k_gauss_blur<0>), grid, dim3(256), lds, st, a); break;
+    case 1: hipLaunchKernelGGL((k_gauss_blur<1>), grid, dim3(256), lds, st, a); break;
+    case 2: hipLaunchKernelGGL((k_gauss_blur<2>), grid, dim3(256), lds, st, a); break;
+    case 3: hipLaunchKernelGGL((k_gauss_blur<3>), grid, dim3(256), lds, st, a); break;
+    default: return (int)hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// hessian_response (image_util.rs:72-109) of the f32 planes to_luma32f(src): a blur plane (FMT 3) or, with no blur, the frames
+// themselves.  One pixel per thread; the border ring -- every pixel of a frame with W < 3 or H < 3 -- is +0.0.
+template <int FMT>
+__global__ void __launch_bounds__(256) k_hessian_response(HessianArgs a)
+{
+    const int x = (int)blockIdx.x * 64 + (int)threadIdx.x, W = a.W, H = a.H;
+    if (x >= W) return;
+    const uint8_t *frame = a.src + (size_t)blockIdx.z * (size_t)a.src_frame_stride;
+    float *out = a.dst + (size_t)blockIdx.z * (size_t)a.dst_frame_stride;
+    for (int y = (int)blockIdx.y * 4 + (int)threadIdx.y; y < H; y += (int)gridDim.y * 4) {
+        float d = 0.0f;
+        if (x > 0 && x < W - 1 && y > 0 && y < H - 1) {
+            const uint8_t *c = frame + (size_t)y * (size_t)a.src_row_stride;
+            const uint8_t *p = c - a.src_row_stride, *n = c + a.src_row_stride;
+            d = hessian_det(luma32f_at<FMT>(p, x - 1), luma32f_at<FMT>(p, x), luma32f_at<FMT>(p, x + 1), luma32f_at<FMT>(c, x - 1),
+                            luma32f_at<FMT>(c, x), luma32f_at<FMT>(c, x + 1), luma32f_at<FMT>(n, x - 1), luma32f_at<FMT>(n, x),
+                            luma32f_at<FMT>(n, x + 1));
+        }
+        out[(size_t)y * (size_t)a.dst_row_stride + (size_t)x] = d;
+    }
+}
+
+int launch_hessian_response(const HessianArgs &a, int format, int n_frames, void *stream)
+{
+    if (n_frames <= 0 || n_frames > 65535 || a.W < 1 || a.H < 1) return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)((a.W + 63) / 64), (unsigned)std::min((a.H + 3) / 4, 65535), (unsigned)n_frames), block(64, 4);
+    hipStream_t st = (hipStream_t)stream;
+    switch (format) {
+    case 0: hipLaunchKernelGGL((k_hessian_response<0>), grid, block, 0, st, a); break;
+    case 1: hipLaunchKernelGGL((k_hessian_response<1>), grid, block, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((k_hessian_response<2>), grid, block, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((k_hessian_response<3>), grid, block, 0, st, a); break;
+    default: return (int)hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -75,10 +75,12 @@ int agx_guard(const agx_detector *det_c, F &&body) noexcept
             return fail((det), AGX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-// Blur taps, reference src/image_util.rs:111-124 (sigma = 1.5 at the call site detector.rs:410)
-void make_blur_weights(float sigma, float w[7])
+// Blur taps, reference src/image_util.rs:111-124 (sigma = 1.5 at the call site detector.rs:410: radius 3, seven taps): the
+// 2 * radius + 1 taps into w, which has room for them.  Returns the radius.
+int blur_radius(float sigma) { return (int)std::ceil(sigma * 2.0f); }
+int make_blur_weights(float sigma, float *w)
 {
-    const int radius = (int)std::ceil(sigma * 2.0f);  // == 3
+    const int radius = blur_radius(sigma);
     const float two_sigma_sq = 2.0f * sigma * sigma;
     float sum = 0.0f;
     for (int i = 0; i < 2 * radius + 1; ++i) {
@@ -88,7 +90,11 @@ void make_blur_weights(float sigma, float w[7])
         sum += v;
     }
     for (int i = 0; i < 2 * radius + 1; ++i) w[i] /= sum;
+    return radius;
 }
+
+// a sigma agx_planes_enqueue / agx_debug_blur_weights can blur with: finite, positive, at most GB_MAX_RADIUS
+bool blur_sigma_ok(float sigma) { return std::isfinite(sigma) && sigma > 0.0f && std::ceil(sigma * 2.0f) <= (float)GB_MAX_RADIUS; }
 
 // Constants of rochade_refine for half_size_patch = 2 (the only value the reference passes,
 // detector.rs:430): cone kernel (:240-254) and the 25x6 pseudo-inverse of the quadratic
@@ -1336,6 +1342,164 @@ int agx_find_board_tail(const agx_saddle *saddles, uint32_t n_saddles, uint32_t 
 
 }  // extern "C"
 
+// ---- gaussian_blur_f32 / hessian_response as planes (src/image_util.rs:110-206, :72-109; chain_kernels.hip) ---------------------
+static int planes_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                               size_t frame_stride_bytes, int format, float sigma, float *d_blur, float *d_response,
+                               size_t out_row_stride_bytes, size_t out_frame_stride_bytes)
+{
+    if (!det) return AGX_ERR_ARG;
+    if (!d_frames || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null frames or n_frames <= 0");
+    if (!d_blur && !d_response) return fail(det, AGX_ERR_ARG, "d_blur and d_response are both NULL");
+    if (sigma != 0.0f && !blur_sigma_ok(sigma)) return fail(det, AGX_ERR_ARG, "sigma must be 0 (no blur) or positive and finite with ceil(2 sigma) <= 16");
+    if (sigma == 0.0f && d_blur) return fail(det, AGX_ERR_ARG, "sigma 0 means no blur: d_blur must be NULL");
+    if (!format_px_bytes(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
+    if (width < 1 || height < 1) return fail(det, AGX_ERR_ARG, "width and height must be >= 1");
+    if ((long long)width * height >= (1ll << 30) || width > 65000) return fail(det, AGX_ERR_ARG, "frame too large (>= 2^30 px or wider than 65000)");
+    if (n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
+    const size_t px_bytes = (size_t)format_px_bytes(format);
+    if (row_stride_bytes < (size_t)width * px_bytes || row_stride_bytes > 0x7fffffffu ||
+        (n_frames > 1 && frame_stride_bytes < row_stride_bytes * format_rows(format, height)))
+        return fail(det, AGX_ERR_ARG, "strides must cover a row / a frame");
+    if (format_16bit(format) && ((row_stride_bytes | (n_frames > 1 ? frame_stride_bytes : 0) | (uintptr_t)d_frames) & 1))
+        return fail(det, AGX_ERR_ARG, "16-bit pixels must be 2-byte aligned");
+    if (format == AGX_LF32 && ((row_stride_bytes | (n_frames > 1 ? frame_stride_bytes : 0) | (uintptr_t)d_frames) & 3))
+        return fail(det, AGX_ERR_ARG, "f32 pixels must be 4-byte aligned");
+    if (format_front(format) && height > 16 * 65535)  // (k_front_luma's grid)
+        return fail(det, AGX_ERR_ARG, "frames of this format may have at most 1048560 rows");
+    if (out_row_stride_bytes < 4 * (size_t)width || (out_row_stride_bytes & 3))
+        return fail(det, AGX_ERR_ARG, "out_row_stride_bytes must be a multiple of 4 and cover width floats");
+    if (out_frame_stride_bytes < (size_t)height * out_row_stride_bytes || (out_frame_stride_bytes & 3))
+        return fail(det, AGX_ERR_ARG, "out_frame_stride_bytes must be a multiple of 4 and cover height rows");
+    if (((uintptr_t)d_blur | (uintptr_t)d_response) & 3) return fail(det, AGX_ERR_ARG, "the output planes must be 4-byte aligned");
+    HIP_TRY(det, hipSetDevice(det->device));
+    // this batch replaces whatever was in flight; there is nothing of it to be fetched
+    det->detect.kind = 0;
+    det->refine.kind = 0;
+    det->decode.kind = 0;
+    det->find.kind = 0;
+    det->front_format = -1;
+    det->enqueued = false;
+    if (format_front(format)) {  // as the chain: k_front_luma's integer luma plane, read as L8 / L16
+        const size_t out_px = format_16bit(format) ? 2 : 1, need = (size_t)n_frames * (size_t)width * (size_t)height * out_px;
+        void *d_front = side_ensure(det, SB_FRONT, need, 0);
+        if (!d_front) return fail(det, AGX_ERR_HIP, "hipMalloc: front-end luma plane");
+        hipError_t e = (hipError_t)launch_front_luma(d_frames, row_stride_bytes, frame_stride_bytes, n_frames, format, d_front, 0, width,
+                                                     height, det->stream);
+        if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_front_luma: ") + hipGetErrorString(e));
+        d_frames = d_front;
+        row_stride_bytes = (size_t)width * out_px;
+        frame_stride_bytes = row_stride_bytes * (size_t)height;
+        format = out_px == 2 ? AGX_L16 : AGX_L8;
+    }
+    HessianArgs h{};
+    h.src = static_cast<const uint8_t *>(d_frames);
+    h.src_frame_stride = (long long)frame_stride_bytes;
+    h.src_row_stride = (int)row_stride_bytes;
+    int h_format = format;
+    if (sigma != 0.0f) {
+        GaussBlurArgs g{};
+        g.src = h.src;
+        g.src_frame_stride = h.src_frame_stride;
+        g.src_row_stride = h.src_row_stride;
+        g.W = width;
+        g.H = height;
+        g.dst = d_blur;
+        g.dst_row_stride = (long long)(out_row_stride_bytes / 4);
+        g.dst_frame_stride = (long long)(out_frame_stride_bytes / 4);
+        if (!d_blur) {  // only the response is wanted: the blur goes to the workspace plane, tight
+            g.dst = static_cast<float *>(side_ensure(det, SB_PLANES_BLUR, (size_t)n_frames * (size_t)width * (size_t)height * sizeof(float), 0));
+            if (!g.dst) return fail(det, AGX_ERR_HIP, "hipMalloc: blur planes");
+            g.dst_row_stride = width;
+            g.dst_frame_stride = (long long)width * height;
+        }
+        g.radius = make_blur_weights(sigma, g.w);
+        hipError_t e = (hipError_t)launch_gauss_blur(g, format, n_frames, det->stream);
+        if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_gauss_blur: ") + hipGetErrorString(e));
+        h.src = reinterpret_cast<const uint8_t *>(g.dst);
+        h.src_frame_stride = g.dst_frame_stride * 4;
+        h.src_row_stride = (int)(g.dst_row_stride * 4);
+        h_format = AGX_LF32;
+    }
+    if (d_response) {
+        h.W = width;
+        h.H = height;
+        h.dst = d_response;
+        h.dst_row_stride = (long long)(out_row_stride_bytes / 4);
+        h.dst_frame_stride = (long long)(out_frame_stride_bytes / 4);
+        hipError_t e = (hipError_t)launch_hessian_response(h, h_format, n_frames, det->stream);
+        if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_hessian_response: ") + hipGetErrorString(e));
+    }
+    return AGX_OK;
+}
+
+// agx_gaussian_blur_f32 / agx_hessian_response: upload, a batch of one, the plane (blur, or with want_response the response) down
+static int planes_host_impl(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes, int format, float sigma,
+                            bool want_response, float *out)
+{
+    if (!det) return AGX_ERR_ARG;
+    if (!pixels || !out) return fail(det, AGX_ERR_ARG, "null argument");
+    if (!format_px_bytes(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
+    if (width < 1 || height < 1) return fail(det, AGX_ERR_ARG, "width and height must be >= 1");
+    const size_t row_bytes = (size_t)width * format_px_bytes(format);
+    if (row_stride_bytes < row_bytes) return fail(det, AGX_ERR_ARG, "row stride smaller than a row");
+    HIP_TRY(det, hipSetDevice(det->device));
+    const size_t pitch = (row_bytes + 3) & ~(size_t)3;
+    const size_t rows = format_rows(format, height);
+    const size_t need = pitch * rows, plane_bytes = (size_t)width * (size_t)height * sizeof(float);
+    void *d_stage = side_ensure(det, SB_STAGE, need, 0);
+    if (!d_stage) return fail(det, AGX_ERR_HIP, "hipMalloc: staging buffer");
+    float *d_plane = static_cast<float *>(side_ensure(det, SB_PLANES_OUT, plane_bytes, 0));
+    if (!d_plane) return fail(det, AGX_ERR_HIP, "hipMalloc: plane");
+    HIP_TRY(det, hipMemcpy2DAsync(d_stage, pitch, pixels, row_stride_bytes, row_bytes, rows, hipMemcpyHostToDevice, det->stream));
+    const int rc = planes_enqueue_impl(det, d_stage, 1, width, height, pitch, need, format, sigma, want_response ? nullptr : d_plane,
+                                       want_response ? d_plane : nullptr, (size_t)width * sizeof(float), plane_bytes);
+    if (rc) return rc;
+    HIP_TRY(det, hipMemcpyAsync(out, d_plane, plane_bytes, hipMemcpyDeviceToHost, det->stream));
+    HIP_TRY(det, hipStreamSynchronize(det->stream));
+    return AGX_OK;
+}
+
+extern "C" {
+
+int agx_planes_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                       size_t frame_stride_bytes, int format, float sigma, float *d_blur, float *d_response,
+                       size_t out_row_stride_bytes, size_t out_frame_stride_bytes)
+{
+    return agx_guard(det, [&]() -> int {
+    return planes_enqueue_impl(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, sigma, d_blur,
+                               d_response, out_row_stride_bytes, out_frame_stride_bytes);
+    });
+}
+
+int agx_gaussian_blur_f32(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes, int format, float sigma,
+                          float *out)
+{
+    return agx_guard(det, [&]() -> int {
+    if (det && !blur_sigma_ok(sigma)) return fail(det, AGX_ERR_ARG, "sigma must be positive and finite with ceil(2 sigma) <= 16");
+    return planes_host_impl(det, pixels, width, height, row_stride_bytes, format, sigma, false, out);
+    });
+}
+
+int agx_hessian_response(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes, int format, float *out)
+{
+    return agx_guard(det, [&]() -> int {
+    return planes_host_impl(det, pixels, width, height, row_stride_bytes, format, 0.0f, true, out);
+    });
+}
+
+int agx_debug_blur_weights(float sigma, float *weights, int cap, int *radius)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (!weights || !radius || !blur_sigma_ok(sigma)) return AGX_ERR_ARG;
+    *radius = blur_radius(sigma);
+    if (cap < 2 * *radius + 1) return AGX_ERR_CAPACITY;
+    make_blur_weights(sigma, weights);
+    return AGX_OK;
+    });
+}
+
+}  // extern "C"
+
 int agx::group_detect_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
                               size_t frame_stride_bytes, int format, uint32_t cap_per_frame, uint32_t *d_table, agx_tag *d_slab,
                               uint32_t slab_records)
@@ -1652,8 +1816,8 @@ int agx_detector_constants(const agx_detector *det, float *blur_w7, float *cone2
 namespace {
 // AGX_DBG_REDZONES: {buffers, damaged guard bytes, first damaged buffer, its offset (from the payload start, as int32),
 // device address of buffer 0's payload (lo, hi)}.  Buffers = the chain's workspace in allocation order, then the side
-// buffers that exist (staging, luma planes, the device tail's code list / tag rows / frame table) -- the last three in
-// mapped pinned HOST memory, whose guards are read in place.
+// buffers that exist, in the order of their slots (staging, luma planes, the device tail's code list / tag rows / frame table,
+// .., agx_planes_enqueue's blur planes) -- the pinned HOST ones' guards are read in place.
 int fetch_redzones(agx_detector *det, void *host_out, size_t cap_bytes, size_t *n_items)
 {
     *n_items = 6;

@@ -127,6 +127,8 @@ enum {
     SB_FIND_COUNTS,    // ... [n_frames] uint32 ...
     SB_FIND_STATUS,    // ... and [n_frames] uint32 (AGX_BOARD_*)
     SB_FIND_SADDLES,   // agx_find_board: the host's list on the device
+    SB_PLANES_BLUR,    // agx_planes_enqueue without d_blur: the tight [n_frames][H][W] blur planes the response is taken of
+    SB_PLANES_OUT,     // agx_gaussian_blur_f32 / agx_hessian_response: the plane on the device before it is copied down
     SB_COUNT
 };
 }  // namespace agx

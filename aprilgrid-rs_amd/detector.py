@@ -11,6 +11,8 @@ Same names, argument meaning and error behaviour as the reference where Python a
   TagDetector.rochade_refine          src/detector.rs:194-361 (the crate's pub fn, half_size_patch = 2)
   TagDetector.decode_quads            src/detector.rs:448-476 (try_decode_quad = the pub fns decode_positions, bit_code, best_tag)
   TagDetector.find_board              src/detector.rs:588-639 (the crate's pub fn try_find_best_board)
+  TagDetector.gaussian_blur_f32       src/image_util.rs:110-206 (the crate's pub fn, any sigma up to 8)
+  TagDetector.hessian_response        src/image_util.rs:72-109 (the crate's pub fn)
 An image is a numpy array standing for the DynamicImage variants the reference is fed:
 HxW uint8 (ImageLuma8), HxW uint16 (ImageLuma16), HxWx3 uint8 (ImageRgb8); HxWx2 / HxWx4 uint8 (ImageLumaA8, ImageRgba8),
 HxWx2 / HxWx3 / HxWx4 uint16 (ImageLumaA16, ImageRgb16, ImageRgba16).  BGR / BGRA order and channel-first planes (3xHxW uint8)
@@ -352,10 +354,11 @@ class TagDetector:
             self.set_stream(s)
 
     @staticmethod
-    def _tensor_format(frames, format=None):
-        """-> (agx_format, bytes per pixel of a row); format: the caller's word instead of what the shape suggests."""
+    def _tensor_format(frames, format=None, strided=False):
+        """-> (agx_format, bytes per pixel of a row); format: the caller's word instead of what the shape suggests.
+        strided: the caller takes the strides from the tensor (planes_enqueue)."""
         import torch
-        if not frames.is_cuda or not frames.is_contiguous():
+        if not frames.is_cuda or not (strided or frames.is_contiguous()):
             raise AgxError(_ffi.AGX_ERR_ARG, "frames must be a contiguous device tensor")
         if format is not None:
             kind = "f" if frames.dtype.is_floating_point else "i"
@@ -788,6 +791,70 @@ class TagDetector:
                                                     n_threads))
         return quads, pts, n_quads, status
 
+    # ---- gaussian_blur_f32 / hessian_response as planes (src/image_util.rs:110-206, :72-109) ----
+    @staticmethod
+    def _strided_frames(frames, format=None):
+        """-> (agx_format, n, w, h, row stride, frame stride in bytes) of a device tensor of frames whose rows (and, for the
+        planar layout, planes) may be padded: a view cut out of a larger tensor."""
+        fmt, bpp = TagDetector._tensor_format(frames, format, strided=True)
+        planes = _ffi.FORMAT_LAYOUT[fmt][1]
+        el, st = frames.element_size(), frames.stride()
+        n = int(frames.shape[0])
+        h, w = (int(frames.shape[2]), int(frames.shape[3])) if planes == 3 else (int(frames.shape[1]), int(frames.shape[2]))
+        row = st[2] if planes == 3 else st[1]
+        inner = tuple(st[3:]) if planes == 3 else tuple(st[2:])
+        dense = (1,) if frames.dim() == 3 or planes == 3 else (int(frames.shape[3]), 1)
+        if inner != dense or (planes == 3 and st[1] != h * row):
+            raise AgxError(_ffi.AGX_ERR_ARG, "frames: the pixels of a row must be contiguous (rows and frames may be padded)")
+        return fmt, n, w, h, row * el, st[0] * el
+
+    def planes_enqueue(self, frames, sigma, blur=None, response=None, format=None):
+        """gaussian_blur_f32(to_luma32f(frame), sigma) into `blur` and hessian_response of it into `response` (either may be
+        None, not both), over a batch on this detector's GPU, stream-ordered behind torch's current stream; returns immediately
+        and there is nothing to fetch: the planes are complete in stream order.  frames and format= as saddles_batch_enqueue,
+        but rows and frames may be padded (a view); blur, response: float32 device tensors [N,H,W] with contiguous rows and the
+        same strides.  sigma 0: no blur -- blur must be None and response is hessian_response(to_luma32f(frame)).
+        The handle keeps no reference to frames, blur or response: the caller keeps the outputs alive to use them, and frames may
+        be dropped at once, because the kernels run on torch's current stream and torch's allocator hands freed memory out
+        again only to work queued behind them on that stream (a tensor used on another stream needs record_stream, as ever)."""
+        import torch
+        fmt, n, w, h, rs, fs = self._strided_frames(frames, format)
+        strides = None
+        for t, what in ((blur, "blur"), (response, "response")):
+            if t is None:
+                continue
+            if not (getattr(t, "is_cuda", False) and t.dtype == torch.float32 and tuple(t.shape) == (n, h, w) and t.stride(2) == 1
+                    and t.device == frames.device):
+                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a float32 tensor %s with contiguous rows on the frames' device" % (what, (n, h, w)))
+            if strides is not None and strides != (t.stride(0), t.stride(1)):
+                raise AgxError(_ffi.AGX_ERR_ARG, "blur and response must have the same strides")
+            strides = (t.stride(0), t.stride(1))
+        ors, ofs = (4 * strides[1], 4 * strides[0]) if strides else (4 * w, 4 * w * h)
+        self._follow_torch_stream(frames)
+        self._batch = self._detect = self._refine = self._decode = self._find = None
+        self._check(self._lib.agx_planes_enqueue(self._h, frames.data_ptr(), n, w, h, rs, fs, fmt, float(sigma),
+                                                 blur.data_ptr() if blur is not None else None,
+                                                 response.data_ptr() if response is not None else None, ors, ofs))
+
+    def gaussian_blur_f32(self, img, sigma=1.5, format=None):
+        """image_util::gaussian_blur_f32(img.to_luma32f(), sigma) of a host image (any format; an HxW float32 plane is taken
+        as it is) -> HxW float32 array."""
+        a, fmt, stride = _image_args(img, format)
+        h, w = _image_hw(a, fmt)
+        out = np.empty((h, w), np.float32)
+        self._batch = self._detect = self._refine = self._decode = self._find = None
+        self._check(self._lib.agx_gaussian_blur_f32(self._h, a.ctypes.data, w, h, stride, fmt, float(sigma), out.ctypes.data))
+        return out
+
+    def hessian_response(self, img, format=None):
+        """image_util::hessian_response(img.to_luma32f()) of a host image, no blur -> HxW float32 array."""
+        a, fmt, stride = _image_args(img, format)
+        h, w = _image_hw(a, fmt)
+        out = np.empty((h, w), np.float32)
+        self._batch = self._detect = self._refine = self._decode = self._find = None
+        self._check(self._lib.agx_hessian_response(self._h, a.ctypes.data, w, h, stride, fmt, out.ctypes.data))
+        return out
+
     # ---- measurement / parity hooks ------------------------------------------------------
     def profile_enable(self, level=2):
         """0/False off, 1 = time the blur kernel only, 2/True = time every kernel."""
@@ -851,6 +918,16 @@ class TagDetector:
         if code in (3, 4):
             return buf[: n.value].copy()
         return buf
+
+
+def blur_weights(sigma):
+    """The taps of gaussian_blur_f32 at sigma (src/image_util.rs:111-124): 2 * ceil(2 sigma) + 1 float32 weights; no device."""
+    w = np.zeros(2 * 16 + 1, np.float32)
+    radius = C.c_int(0)
+    st = _ffi.lib().agx_debug_blur_weights(float(sigma), w.ctypes.data, len(w), C.byref(radius))
+    if st != _ffi.AGX_OK:
+        raise AgxError(st, "sigma %r" % (sigma,))
+    return w[: 2 * radius.value + 1].copy()
 
 
 def decode_quads_tail(tag_family, luma8, quads, with_bits=False):

@@ -220,6 +220,15 @@ extern "C" {
     pub fn agx_find_board_tail(saddles: *const agx_saddle, n_saddles: u32, quads: *mut u32, cap: u32, n_quads: *mut u32,
                                status: *mut u32) -> c_int;
 
+    pub fn agx_planes_enqueue(det: *mut agx_detector, d_frames: *const c_void, n_frames: c_int, width: c_int, height: c_int,
+                              row_stride_bytes: usize, frame_stride_bytes: usize, format: c_int, sigma: c_float, d_blur: *mut c_float,
+                              d_response: *mut c_float, out_row_stride_bytes: usize, out_frame_stride_bytes: usize) -> c_int;
+    pub fn agx_gaussian_blur_f32(det: *mut agx_detector, pixels: *const c_void, width: c_int, height: c_int, row_stride_bytes: usize,
+                                 format: c_int, sigma: c_float, out: *mut c_float) -> c_int;
+    pub fn agx_hessian_response(det: *mut agx_detector, pixels: *const c_void, width: c_int, height: c_int, row_stride_bytes: usize,
+                                format: c_int, out: *mut c_float) -> c_int;
+    pub fn agx_debug_blur_weights(sigma: c_float, weights: *mut c_float, cap: c_int, radius: *mut c_int) -> c_int;
+
     pub fn agx_detect_from_saddles(det: *const agx_detector, saddles: *const agx_saddle, n_saddles: u32, luma8: *const u8, width: c_int,
                                    height: c_int, row_stride_bytes: usize, out: *mut agx_tag, cap: u32, n_out: *mut u32) -> c_int;
     pub fn agx_detect_tail(family: c_int, params: *const agx_params, saddles: *const agx_saddle, n_saddles: u32, luma8: *const u8,

@@ -21,6 +21,9 @@ use std::collections::HashMap;
 use std::os::raw::{c_int, c_void};
 use std::sync::Mutex;
 
+/// The reference's `GrayImagef32` (src/image_util.rs): an f32 luma plane.
+pub type GrayImagef32 = image::ImageBuffer<image::Luma<f32>, Vec<f32>>;
+
 /// reference src/tag_families.rs:5-13 -- the discriminants are `agx_family` (checked by tests/test_rust_binding.py).
 #[derive(Debug, Clone, Copy, PartialEq, Eq)]
 #[repr(i32)]
@@ -226,6 +229,31 @@ impl TagDetector {
         });
         assert_eq!(st, ffi::AGX_OK, "agx_rochade_refine failed: {}", st);
         (out.iter().map(|s| Saddle { p: (s.x, s.y), k: s.k, theta: s.theta, phi: s.phi }).collect(), status)
+    }
+
+    /// reference src/image_util.rs:110-206, `gaussian_blur_f32(img, sigma)`: the blur of an f32 luma plane at any sigma with
+    /// `ceil(2 sigma)` in 1 ..= 16, bit for bit.
+    pub fn gaussian_blur_f32(&self, img: &GrayImagef32, sigma: f32) -> GrayImagef32 {
+        let (w, h) = (img.width(), img.height());
+        let mut out = vec![0f32; w as usize * h as usize];
+        let st = self.with_handle(|d| unsafe {
+            ffi::agx_gaussian_blur_f32(
+                d, img.as_raw().as_ptr() as *const c_void, w as c_int, h as c_int, 4 * w as usize, ffi::AGX_LF32, sigma, out.as_mut_ptr(),
+            )
+        });
+        assert_eq!(st, ffi::AGX_OK, "agx_gaussian_blur_f32 failed: {}", st);
+        GrayImagef32::from_raw(w, h, out).unwrap()
+    }
+
+    /// reference src/image_util.rs:72-109, `hessian_response(img)`: the Hessian determinant of an f32 plane (the border ring is 0).
+    pub fn hessian_response(&self, img: &GrayImagef32) -> GrayImagef32 {
+        let (w, h) = (img.width(), img.height());
+        let mut out = vec![0f32; w as usize * h as usize];
+        let st = self.with_handle(|d| unsafe {
+            ffi::agx_hessian_response(d, img.as_raw().as_ptr() as *const c_void, w as c_int, h as c_int, 4 * w as usize, ffi::AGX_LF32, out.as_mut_ptr())
+        });
+        assert_eq!(st, ffi::AGX_OK, "agx_hessian_response failed: {}", st);
+        GrayImagef32::from_raw(w, h, out).unwrap()
     }
 
     /// reference src/detector.rs:448-476, `try_decode_quad(&self, img, quad)` for every quad of `quads` (the crate's pub fns

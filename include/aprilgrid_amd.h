@@ -495,6 +495,38 @@ int agx_find_board(agx_detector *det, const agx_saddle *saddles, uint32_t n_sadd
 int agx_find_board_tail(const agx_saddle *saddles, uint32_t n_saddles, uint32_t *quads, uint32_t cap, uint32_t *n_quads,
                         uint32_t *status);
 
+/* ---- blur and Hessian-response planes at any sigma ---------------------------------------- */
+
+/* image_util::gaussian_blur_f32(img, sigma) -- src/image_util.rs:110-206 -- and image_util::hessian_response(img) --
+ * src/image_util.rs:72-109 --, two `pub fn`s of the crate, over a batch in DEVICE memory: stream-ordered on the detector's stream
+ * (the caller's after agx_detector_set_stream), returns without waiting.  d_frames / n_frames / width / height / strides / format
+ * as agx_saddles_batch_enqueue (every agx_format, AGX_LF32 included -- its row stride a multiple of 4 bytes; width, height >= 1).
+ * sigma > 0: d_blur, if given, receives gaussian_blur_f32(to_luma32f(frame), sigma) and d_response, if given,
+ * hessian_response of that blur -- what refined_saddle_points computes at src/detector.rs:410-411 for sigma 1.5; with d_response
+ * alone the blur goes to a workspace plane.  The radius ceilf(2 sigma) may be 1 .. 16 (sigma up to 8.0).  sigma == 0.0f: no blur
+ * (the reference's weights are NaN there) -- d_blur must be NULL and d_response receives hessian_response(to_luma32f(frame)).
+ * d_blur, d_response: caller-owned device memory, 4-byte aligned, with the same strides: frame f, row y starts at
+ * f*out_frame_stride_bytes + y*out_row_stride_bytes; only the width floats of a row are written, padding is never touched.  The
+ * outputs must not overlap the frames or each other.  Every value is the reference's, bit for bit; the border ring of a response
+ * plane -- all of it where width < 3 or height < 3 -- is +0.0.
+ * AGX_ERR_ARG: NULL d_frames, both outputs NULL, sigma negative, NaN, infinite or with ceilf(2 sigma) > 16, sigma == 0 with d_blur,
+ * out_row_stride_bytes below 4*width or not a multiple of 4, out_frame_stride_bytes below height*out_row_stride_bytes or not a
+ * multiple of 4, an AGX_LF32 row stride that is not a multiple of 4.
+ * A sixth kind of batch on the handle: it replaces whatever is in flight and has no fetch of its own -- the planes are complete in
+ * stream order (or after agx_detector_sync), and every other kind's fetch is AGX_ERR_STATE then.  Replacing is neither waiting nor
+ * discarding: a plane written here may go straight into agx_refine_points_enqueue(.., AGX_LF32, AGX_REFINE_PLANE, ..) with no
+ * sync in between. */
+int agx_planes_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height,
+                       size_t row_stride_bytes, size_t frame_stride_bytes, int format, float sigma,
+                       float *d_blur, float *d_response, size_t out_row_stride_bytes, size_t out_frame_stride_bytes);
+/* gaussian_blur_f32(to_luma32f(image), sigma) (src/image_util.rs:110-206) of one image in HOST memory: uploads it, runs a batch
+ * of one, writes the width*height floats of the plane, tightly packed, to out.  sigma as above, but not 0. */
+int agx_gaussian_blur_f32(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes,
+                          int format, float sigma, float *out);
+/* hessian_response(to_luma32f(image)) (src/image_util.rs:72-109) of one image in HOST memory, no blur; out as above. */
+int agx_hessian_response(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes,
+                         int format, float *out);
+
 /* ---- detector groups: several GPUs of one node driven from ONE process ----------------- */
 
 /* The reference's detect(&self) is stateless, so a batch shards by frame:
@@ -615,7 +647,7 @@ enum { AGX_DBG_BLUR = 0, AGX_DBG_RESP = 1, AGX_DBG_MIN = 2, AGX_DBG_CENTERS = 3,
                                check of the check).  Buffers = the chain's workspace, then the staging buffer, the luma
                                planes and the device tail's code list, tag rows and frame table (mapped pinned host memory), then
                                agx_detect_batch_enqueue_to's device-memory tag rows and frame table, agx_detect_batch_fetch's
-                               pinned luma planes, the front-end kernel's luma plane (AGX_LA8 .. AGX_RGBA16), the stored / recomputed response planes, agx_refine_points_enqueue's internal records and statuses and agx_rochade_refine's points, agx_decode_quads_enqueue's internal tags, statuses and bits and agx_decode_quads' quads, and agx_find_boards_enqueue's internal quads, quad points, counts and statuses and agx_find_board's list, as far as they exist.  Needs no enqueued batch.  Guard bytes exist only in handles created with
+                               pinned luma planes, the front-end kernel's luma plane (AGX_LA8 .. AGX_RGBA16), the stored / recomputed response planes, agx_refine_points_enqueue's internal records and statuses and agx_rochade_refine's points, agx_decode_quads_enqueue's internal tags, statuses and bits and agx_decode_quads' quads, and agx_find_boards_enqueue's internal quads, quad points, counts and statuses and agx_find_board's list, and agx_planes_enqueue's workspace blur planes and the device plane of agx_gaussian_blur_f32 / agx_hessian_response, as far as they exist.  Needs no enqueued batch.  Guard bytes exist only in handles created with
                                AGX_REDZONE_BYTES=<n> in the environment (memory-safety tests of the kernels) */
        AGX_DBG_TAIL_TABLE_ADDR = 11 /* 2 x uint64: host address and payload bytes of the device tail's frame table (the check
                                        of the check for a buffer in mapped host memory).  Needs no enqueued batch */ };
@@ -647,6 +679,10 @@ int agx_debug_fetch(agx_detector *det, int frame, int what, void *host_out, size
 /* Constants computed at create time (for parity tests): 7 blur weights, 25 cone taps,
  * 25x6 pseudo-inverse (row i, column j at [i*6+j]). */
 int agx_detector_constants(const agx_detector *det, float *blur_w7, float *cone25, float *pmat150);
+/* The taps of gaussian_blur_f32 at `sigma` (src/image_util.rs:110-206, the kernel at :111-124): *radius = ceilf(2 sigma) and the
+ * 2*radius + 1 weights; no handle, no device.  AGX_ERR_CAPACITY: cap is smaller than that (*radius is set); AGX_ERR_ARG: sigma is
+ * not positive and finite, or ceilf(2 sigma) > 16. */
+int agx_debug_blur_weights(float sigma, float *weights, int cap, int *radius);
 
 const char *agx_status_string(int status);
 /* Message of the last failure on this detector (HIP error text etc.); never NULL.
