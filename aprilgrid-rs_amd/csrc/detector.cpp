@@ -1366,8 +1366,9 @@ static int planes_enqueue_impl(agx_detector *det, const void *d_frames, int n_fr
         return fail(det, AGX_ERR_ARG, "f32 pixels must be 4-byte aligned");
     if (format_front(format) && height > 16 * 65535)  // (k_front_luma's grid)
         return fail(det, AGX_ERR_ARG, "frames of this format may have at most 1048560 rows");
-    if (out_row_stride_bytes < 4 * (size_t)width || (out_row_stride_bytes & 3))
-        return fail(det, AGX_ERR_ARG, "out_row_stride_bytes must be a multiple of 4 and cover width floats");
+    // (at most 0x7fffffff, as the frames' row stride: k_hessian_response reads the blur plane back with an int row stride in bytes)
+    if (out_row_stride_bytes < 4 * (size_t)width || (out_row_stride_bytes & 3) || out_row_stride_bytes > 0x7fffffffu)
+        return fail(det, AGX_ERR_ARG, "out_row_stride_bytes must be a multiple of 4, cover width floats and be below 2^31");
     if (out_frame_stride_bytes < (size_t)height * out_row_stride_bytes || (out_frame_stride_bytes & 3))
         return fail(det, AGX_ERR_ARG, "out_frame_stride_bytes must be a multiple of 4 and cover height rows");
     if (((uintptr_t)d_blur | (uintptr_t)d_response) & 3) return fail(det, AGX_ERR_ARG, "the output planes must be 4-byte aligned");

@@ -510,7 +510,7 @@ int agx_find_board_tail(const agx_saddle *saddles, uint32_t n_saddles, uint32_t 
  * outputs must not overlap the frames or each other.  Every value is the reference's, bit for bit; the border ring of a response
  * plane -- all of it where width < 3 or height < 3 -- is +0.0.
  * AGX_ERR_ARG: NULL d_frames, both outputs NULL, sigma negative, NaN, infinite or with ceilf(2 sigma) > 16, sigma == 0 with d_blur,
- * out_row_stride_bytes below 4*width or not a multiple of 4, out_frame_stride_bytes below height*out_row_stride_bytes or not a
+ * out_row_stride_bytes below 4*width, above 0x7fffffff or not a multiple of 4, out_frame_stride_bytes below height*out_row_stride_bytes or not a
  * multiple of 4, an AGX_LF32 row stride that is not a multiple of 4.
  * A sixth kind of batch on the handle: it replaces whatever is in flight and has no fetch of its own -- the planes are complete in
  * stream order (or after agx_detector_sync), and every other kind's fetch is AGX_ERR_STATE then.  Replacing is neither waiting nor
