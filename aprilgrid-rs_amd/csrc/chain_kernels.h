@@ -221,4 +221,11 @@ struct HessianArgs {
 };
 int launch_hessian_response(const HessianArgs &a, int format, int n_frames, void *stream);
 
+// k_response_front: the chain's front behind k_gauss_blur for a blur sigma other than 1.5.  From the workspace blur plane a.blur
+// it fills what K1 otherwise hands to the sparse stages: a.ctr[frame].min_key_inv (final when the first of its two launches is
+// through), every mask word of the image area (exact: resp < 0.05 * min), every cand_max block of those words and, if non-null,
+// a.resp_dbg.  Reads of `a`: blur, resp_dbg, ctr, mask, cand_max and their geometry; nothing of K1's tiling.
+// grid (ceil(W / 64), min(ceil(H / 128), 65535), n_frames <= 65535); hipError_t
+int launch_response_front(const ChainArgs &a, void *stream);
+
 }  // namespace agx

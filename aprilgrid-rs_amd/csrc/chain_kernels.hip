@@ -3622,4 +3622,87 @@ int launch_hessian_response(const HessianArgs &a, int format, int n_frames, void
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// k_response_front: the chain's front for a blur sigma other than 1.5.  k_gauss_blur has written the workspace blur plane;
+// this kernel derives from it the other three products K1 hands to the sparse stages ("Two fronts, one
+// contract"), in two launches:
+//   MASK = false  the frame minimum: the fold `e < acc ? e : acc` of hessian_response over the plane, started at the border
+//                 ring's +0.0 (so neither a -0.0 nor a NaN response can win, as in the reference's sequential fold), reduced
+//                 over the wave by DPP and published with one atomicMax of ~order_key per wave;
+//   MASK = true   the response evaluated again, compared with the FINAL threshold 0.05 * min (the expression k_verify_seeds
+//                 uses): the exact candidate mask, every word of the image area written, zero words included, and per
+//                 4-column x 32-row block the largest admitted response (-inf where none) -- below the threshold everywhere,
+//                 so k_verify_seeds re-tests nothing.
+// A wave owns 64 columns x one word row (32 image rows); lane = column, so the three loads of a row are coalesced and the
+// lane's word is built in a register.  Loads use clamped coordinates (always inside the plane); what is not an interior
+// pixel of the image gets the ring's response 0 and no bit.  No lane leaves early: the 4-lane maximum is a DPP exchange.
+// ------------------------------------------------------------------------------------------
+template <bool MASK>
+__global__ void __launch_bounds__(256) k_response_front(ChainArgs a)
+{
+    const int W = a.W, H = a.H, lane = (int)threadIdx.x, n_yb = (H + 31) >> 5;
+    const int frame = (int)blockIdx.z, x = (int)blockIdx.x * 64 + lane;
+    const int xc = min(x, W - 1), xl = max(xc - 1, 0), xr = min(xc + 1, W - 1);
+    const bool col_in = x > 0 && x < W - 1;
+    const float *blur = a.blur + (size_t)frame * (size_t)a.plane;
+    float *resp = a.resp_dbg ? a.resp_dbg + (size_t)frame * (size_t)a.plane : nullptr;
+    FrameCounters &ctr = a.ctr[frame];
+    float thr = 0.0f;
+    if (MASK) thr = f32_from_order_key(~ctr.min_key_inv) * 0.05f;  // detector.rs:418; final: the minimum launch is through
+    float run_min = 0.0f;
+    for (int yb = (int)blockIdx.y * 4 + (int)threadIdx.y; yb < n_yb; yb += (int)gridDim.y * 4) {  // wave-uniform
+        const int y0 = yb * 32;
+        const float *r0 = blur + (size_t)max(y0 - 1, 0) * (size_t)W, *r1 = blur + (size_t)y0 * (size_t)W;
+        float v11 = r0[xl], v12 = r0[xc], v13 = r0[xr];
+        float v21 = r1[xl], v22 = r1[xc], v23 = r1[xr];
+        uint32_t word = 0u;
+        float cmax = -__builtin_inff();
+#pragma unroll 8
+        for (int b = 0; b < 32; ++b) {
+            const int y = y0 + b;
+            const float *r2 = blur + (size_t)min(y + 1, H - 1) * (size_t)W;
+            const float v31 = r2[xl], v32 = r2[xc], v33 = r2[xr];
+            const bool interior = col_in && y > 0 && y < H - 1;
+            const float d = interior ? hessian_det(v11, v12, v13, v21, v22, v23, v31, v32, v33) : 0.0f;
+            if (MASK) {
+                if (interior && d < thr) {
+                    word |= 1u << b;
+                    cmax = fmaxf(cmax, d);
+                }
+            } else {
+                run_min = d < run_min ? d : run_min;
+                if (resp && x < W && y < H) resp[(size_t)y * (size_t)W + (size_t)x] = d;
+            }
+            v11 = v21, v12 = v22, v13 = v23;
+            v21 = v31, v22 = v32, v23 = v33;
+        }
+        if (MASK) {
+            // the block's maximum: lanes 4k .. 4k + 3 (quad_perm [1,0,3,2], then [2,3,0,1]; every lane has a source)
+            cmax = fmaxf(cmax, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cmax), 0xB1, 0xf, 0xf, false)));
+            cmax = fmaxf(cmax, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cmax), 0x4E, 0xf, 0xf, false)));
+            if (x < W) {
+                a.mask[(size_t)frame * (size_t)a.mask_plane + (size_t)yb * (size_t)a.mask_wpr + (size_t)(MASK_PAD_X + x)] = word;
+                if ((lane & 3) == 0)
+                    a.cand_max[((size_t)frame * (size_t)a.mask_yb + (size_t)yb) * (size_t)(a.mask_wpr >> 2) + (size_t)((MASK_PAD_X + x) >> 2)] = cmax;
+            }
+        }
+    }
+    if (!MASK) {
+        run_min = wave_min_f32(run_min);
+        if (lane == 0) atomicMax(&ctr.min_key_inv, ~f32_order_key(run_min));
+    }
+}
+
+int launch_response_front(const ChainArgs &a, void *stream)
+{
+    if (a.n_frames <= 0 || a.n_frames > 65535 || a.W < 2 || a.H < 2) return (int)hipErrorInvalidValue;
+    const int n_yb = (a.H + 31) >> 5;
+    const dim3 grid((unsigned)((a.W + 63) / 64), (unsigned)std::min((n_yb + 3) / 4, 65535), (unsigned)a.n_frames), block(64, 4);
+    hipLaunchKernelGGL((k_response_front<false>), grid, block, 0, (hipStream_t)stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((k_response_front<true>), grid, block, 0, (hipStream_t)stream, a);
+    return hipGetLastError();
+}
+
 }  // namespace agx

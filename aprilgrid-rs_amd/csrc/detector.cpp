@@ -355,6 +355,35 @@ void harvest_events(agx_detector *d)
     d->pending_events.clear();
 }
 
+// The chain's front at a blur sigma other than 1.5, for the frames of `a` on `st`: k_gauss_blur into the workspace blur plane and,
+// with_response, k_response_front -- the frame minima, the candidate mask and cand_max, which K1 otherwise hands to the sparse
+// stages.  Neither launch is among the AGX_N_KERNELS that agx_profile_* times.
+bool chain_any_sigma(const agx_detector *d)
+{
+    const float k1_sigma = 1.5f;
+    return std::memcmp(&d->blur_sigma, &k1_sigma, sizeof k1_sigma) != 0;
+}
+int enqueue_any_sigma_front(agx_detector *d, const ChainArgs &a, hipStream_t st, bool with_response)
+{
+    GaussBlurArgs g{};
+    g.src = a.frames;
+    g.src_frame_stride = a.frame_stride;
+    g.src_row_stride = a.row_stride;
+    g.W = a.W;
+    g.H = a.H;
+    g.dst = a.blur;
+    g.dst_row_stride = a.W;
+    g.dst_frame_stride = a.plane;
+    g.radius = d->front_radius;
+    std::memcpy(g.w, d->front_w, sizeof(g.w));
+    hipError_t e = (hipError_t)launch_gauss_blur(g, a.fmt, a.n_frames, st);
+    if (e != hipSuccess) return fail(d, AGX_ERR_HIP, std::string("launch k_gauss_blur: ") + hipGetErrorString(e));
+    if (!with_response) return AGX_OK;
+    e = (hipError_t)launch_response_front(a, st);
+    if (e != hipSuccess) return fail(d, AGX_ERR_HIP, std::string("launch k_response_front: ") + hipGetErrorString(e));
+    return AGX_OK;
+}
+
 // The chain of one chunk (frames [f0, f0+nf) of the batch) on stream `st`.
 int enqueue_chunk(agx_detector *d, int f0, int nf, hipStream_t st)
 {
@@ -404,7 +433,13 @@ int enqueue_chunk(agx_detector *d, int f0, int nf, hipStream_t st)
               plan_v_fe[] = {K_BLUR_HESSIAN, K_THRESHOLD, K_SPARSE};
     const int *plan = fused ? (path == 3 ? plan_v_fe : plan_fused) : plan_multi;
     const int n_plan = fused ? (path == 3 ? 3 : 2) : 4;
-    for (int pi = 0; pi < n_plan; ++pi) {
+    const bool any_sigma = chain_any_sigma(d);  // the plan's first entry, K1, is replaced by the any-sigma front
+    d->last_chain_front = any_sigma ? 1 : 0;
+    if (any_sigma) {
+        const int rc = enqueue_any_sigma_front(d, a, st, true);
+        if (rc) return rc;
+    }
+    for (int pi = any_sigma ? 1 : 0; pi < n_plan; ++pi) {
         const int k = plan[pi];
         EventPair ev{nullptr, nullptr, k};
         // (an event pair costs the stream two ~5 us gaps around the kernel: level 1 can sample)
@@ -479,6 +514,12 @@ int enqueue_blur_only(agx_detector *d)
     a.ctr = d->d_ctr[p];
     a.ctr_next = d->d_ctr[p ^ 1];
     a.total_out = &a.ctr[a.n_frames].min_key_inv;
+    if (chain_any_sigma(d)) {  // the blur alone: nothing behind it looks at a minimum or a mask
+        const int rc = enqueue_any_sigma_front(d, a, d->stream, false);
+        if (rc) return rc;
+        d->ctr_cur = p;
+        return AGX_OK;
+    }
     hipError_t e = (hipError_t)launch_kernel(K_BLUR_HESSIAN, a, d->rc, d->stream);
     if (e != hipSuccess) return fail(d, AGX_ERR_HIP, std::string("launch ") + kKernelNames[K_BLUR_HESSIAN] + ": " + hipGetErrorString(e));
     d->ctr_cur = p;
@@ -617,6 +658,7 @@ int agx_detector_create(int family, const agx_params *params, int device, agx_de
         return AGX_ERR_HIP;
     }
     make_blur_weights(1.5f, d->blur_w);
+    d->front_radius = make_blur_weights(d->blur_sigma, d->front_w);
     make_refine_consts(d->rc);
     *out = d.release();
     return AGX_OK;
@@ -666,6 +708,26 @@ int agx_detector_set_limits(agx_detector *det, uint32_t max_candidates, uint32_t
     det->lim_cand = max_candidates;
     det->lim_roots = max_clusters;
     det->lim_out = max_saddles;
+    return AGX_OK;
+    });
+}
+
+int agx_detector_set_blur_sigma(agx_detector *det, float sigma)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    if (!blur_sigma_ok(sigma)) return fail(det, AGX_ERR_ARG, "sigma must be positive and finite with ceil(2 sigma) <= 16");
+    det->blur_sigma = sigma;
+    det->front_radius = make_blur_weights(sigma, det->front_w);
+    return AGX_OK;
+    });
+}
+
+int agx_detector_get_blur_sigma(const agx_detector *det, float *sigma)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det || !sigma) return AGX_ERR_ARG;
+    *sigma = det->blur_sigma;
     return AGX_OK;
     });
 }
@@ -740,6 +802,7 @@ int agx_detector_get_option(const agx_detector *det, const char *name, int *valu
     else if (!std::strcmp(name, "k1_rows_per_segment")) *value = a.rows_per_seg;
     else if (!std::strcmp(name, "sparse_path")) *value = det->sparse_path;
     else if (!std::strcmp(name, "last_sparse_path")) *value = det->last_sparse_path;
+    else if (!std::strcmp(name, "last_chain_front")) *value = det->last_chain_front;
     else if (!std::strcmp(name, "k1_segments")) *value = a.n_segs;
     else if (!std::strcmp(name, "k1_strips")) *value = a.n_strips;
     else if (!std::strcmp(name, "k1_strip_columns")) *value = a.strip_cols;

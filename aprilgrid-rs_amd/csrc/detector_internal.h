@@ -142,6 +142,12 @@ struct agx_detector {
     hipStream_t stream = nullptr;  // what the kernels are enqueued on: own_stream, or the caller's after agx_detector_set_stream
     agx::RefineConsts rc{};
     float blur_w[7]{};
+    // agx_detector_set_blur_sigma: the chain's blur sigma.  Bit-equal to 1.5f: the chain starts with K1 (blur_w above); else with
+    // k_gauss_blur (front_radius, front_w: the taps of agx_debug_blur_weights(blur_sigma)) + k_response_front
+    float blur_sigma = 1.5f;
+    int front_radius = 3;
+    float front_w[2 * agx::GB_MAX_RADIUS + 1]{};
+    int last_chain_front = 0;  // option "last_chain_front": the last chain batch ran 0 = K1, 1 = the any-sigma front
     uint32_t lim_cand = 0, lim_roots = 0, lim_out = 0;
     int force_generic = 0;
     int k1_rows = 0;

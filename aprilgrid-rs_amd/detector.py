@@ -136,7 +136,7 @@ class TagDetector:
     """aprilgrid::detector::TagDetector on one MI355X (one handle = one device + stream;
     use one instance per thread)."""
 
-    def __init__(self, tag_family, optional_detector_params=None, device=0):
+    def __init__(self, tag_family, optional_detector_params=None, device=0, blur_sigma=None):
         self._lib = _ffi.lib()
         self._h = C.c_void_p()
         self._saddle_buf = None  # refined_saddle_points' output buffer: (array [cap][5] f32, its address, count word)
@@ -155,9 +155,15 @@ class TagDetector:
         self._refine = None  # refine_points_enqueue's batch: (n, points per frame, tensors kept alive, device outputs or None)
         self._decode = None  # decode_quads_enqueue's batch: (n, quads per frame, tensors kept alive, device outputs or None)
         self._find = None    # find_boards_enqueue's batch: (n, quads per frame, tensors kept alive, device outputs or None)
+        if blur_sigma is not None:
+            try:
+                self.set_blur_sigma(blur_sigma)
+            except AgxError:
+                self.close()
+                raise
 
-    new = classmethod(lambda cls, tag_family, optional_detector_params=None, device=0:
-                      cls(tag_family, optional_detector_params, device))
+    new = classmethod(lambda cls, tag_family, optional_detector_params=None, device=0, blur_sigma=None:
+                      cls(tag_family, optional_detector_params, device, blur_sigma))
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -332,6 +338,21 @@ class TagDetector:
         external=False: back to the detector's own stream."""
         self._check(self._lib.agx_detector_set_stream(self._h, C.c_void_p(hip_stream_ptr or 0), 1 if external else 0))
         self._stream_ptr = hip_stream_ptr if external else "own"
+
+    def set_blur_sigma(self, sigma):
+        """The sigma of the chain's blur from the next enqueue on (the reference hard-codes 1.5, the default): positive,
+        finite, at most 8.  Every entry that runs the chain on this detector follows it."""
+        self._check(self._lib.agx_detector_set_blur_sigma(self._h, float(sigma)))
+
+    @property
+    def blur_sigma(self):
+        v = C.c_float(0.0)
+        self._check(self._lib.agx_detector_get_blur_sigma(self._h, C.byref(v)))
+        return v.value
+
+    @blur_sigma.setter
+    def blur_sigma(self, sigma):
+        self.set_blur_sigma(sigma)
 
     def set_option(self, name, value):
         self._check(self._lib.agx_detector_set_option(self._h, name.encode(), int(value)))
@@ -984,7 +1005,7 @@ class DetectorGroup:
     per-rank result slabs are gathered to devices[0] (transport "rccl": ncclSend / ncclRecv over
     xGMI; "peer": hipMemcpyPeerAsync -- also accepts the same device twice, for one-GPU boxes)."""
 
-    def __init__(self, tag_family, devices, optional_detector_params=None, transport="rccl"):
+    def __init__(self, tag_family, devices, optional_detector_params=None, transport="rccl", blur_sigma=None):
         self._lib = _ffi.lib()
         self._g = C.c_void_p()
         fam = TagFamily.from_str(tag_family) if isinstance(tag_family, str) else TagFamily(tag_family)
@@ -1000,6 +1021,20 @@ class DetectorGroup:
         self._keep = None
         self._frames_per_rank = 0
         self._detect = None
+        if blur_sigma is not None:
+            try:
+                self.set_blur_sigma(blur_sigma)
+            except AgxError:
+                self.close()
+                raise
+
+    def set_blur_sigma(self, sigma):
+        """TagDetector.set_blur_sigma on every rank's detector."""
+        for r in range(len(self.devices)):
+            h = C.c_void_p(self._lib.agx_group_detector(self._g, r))
+            st = self._lib.agx_detector_set_blur_sigma(h, float(sigma))
+            if st != _ffi.AGX_OK:
+                raise AgxError(st, "rank %d: %s" % (r, self._lib.agx_last_error(h).decode()))
 
     def close(self):
         if getattr(self, "_g", None) and self._g.value:

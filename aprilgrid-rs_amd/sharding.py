@@ -162,7 +162,7 @@ class ChainPipeline:
     """
 
     def __init__(self, tag_family, n_frames, device, depth=2, params=None, dst=0, group=None, slab_records=SLAB_RECORDS,
-                 detector_cls=None, force_collective=False, gather_every=1, steps_per_gather=1):
+                 detector_cls=None, force_collective=False, gather_every=1, steps_per_gather=1, blur_sigma=None):
         # detector_cls: a stand-in with TagDetector's enqueue interface (the CPU test of bench.py's N > 1 control flow)
         if detector_cls is None:
             from .detector import TagDetector
@@ -174,6 +174,9 @@ class ChainPipeline:
         # (3 or 4 in flight is where the gain levels off; each one holds a full workspace)
         self.depth = min(max(1, int(depth)), 6)
         self.dets = [TagDetector(tag_family, params, device=index) for _ in range(self.depth)]
+        if blur_sigma is not None:  # the chain's blur sigma on every detector of the pipeline (default: the reference's 1.5)
+            for det in self.dets:
+                det.set_blur_sigma(blur_sigma)
         # depth 1 stays on the caller's stream (no cross-stream events at all)
         self.streams = [torch.cuda.Stream(dev) for _ in range(self.depth)] if self.depth > 1 else [None]
         self.gather = GatherPipeline(n_frames, dev, dst=dst, group=group, depth=max(2, self.depth),

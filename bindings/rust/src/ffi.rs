@@ -157,6 +157,8 @@ extern "C" {
     pub fn agx_detector_set_limits(det: *mut agx_detector, max_candidates: u32, max_clusters: u32, max_saddles: u32) -> c_int;
     pub fn agx_detector_set_option(det: *mut agx_detector, name: *const c_char, value: c_int) -> c_int;
     pub fn agx_detector_get_option(det: *const agx_detector, name: *const c_char, value: *mut c_int) -> c_int;
+    pub fn agx_detector_set_blur_sigma(det: *mut agx_detector, sigma: c_float) -> c_int;
+    pub fn agx_detector_get_blur_sigma(det: *const agx_detector, sigma: *mut c_float) -> c_int;
     pub fn agx_detector_set_stream(det: *mut agx_detector, hip_stream: *mut c_void, external: c_int) -> c_int;
     pub fn agx_detector_sync(det: *mut agx_detector) -> c_int;
     pub fn agx_detector_constants(det: *const agx_detector, blur_w7: *mut c_float, cone25: *mut c_float, pmat150: *mut c_float) -> c_int;

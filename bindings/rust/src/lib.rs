@@ -121,6 +121,7 @@ pub struct TagDetector {
     family: c_int,
     params: ffi::agx_params,
     device: c_int,
+    blur_sigma: Option<f32>,
 }
 
 impl TagDetector {
@@ -142,7 +143,19 @@ impl TagDetector {
                 max_saddle_angle: p.max_saddle_angle,
                 max_num_of_boards: p.max_num_of_boards,
             },
+            blur_sigma: None,
         }
+    }
+
+    /// The sigma of the chain's blur (the reference hard-codes 1.5 at src/detector.rs:410, the default): positive, finite,
+    /// at most 8.  Applied to every pooled handle when it is created; a sigma the library refuses panics there, like a
+    /// failed creation.  Handles that already exist are dropped, so the value holds from the next call on.
+    pub fn with_blur_sigma(mut self, sigma: f32) -> TagDetector {
+        self.blur_sigma = Some(sigma);
+        for h in self.pool.get_mut().unwrap().drain(..) {
+            unsafe { ffi::agx_detector_destroy(h.0) };
+        }
+        self
     }
 
     fn with_handle<R>(&self, f: impl FnOnce(*mut ffi::agx_detector) -> R) -> R {
@@ -151,6 +164,10 @@ impl TagDetector {
             let mut h: *mut ffi::agx_detector = std::ptr::null_mut();
             let st = unsafe { ffi::agx_detector_create(self.family, &self.params, self.device, &mut h) };
             assert_eq!(st, ffi::AGX_OK, "agx_detector_create failed: {} ({})", st, last_error(std::ptr::null()));
+            if let Some(sigma) = self.blur_sigma {
+                let st = unsafe { ffi::agx_detector_set_blur_sigma(h, sigma) };
+                assert_eq!(st, ffi::AGX_OK, "agx_detector_set_blur_sigma({}) failed: {} ({})", sigma, st, last_error(h));
+            }
             Handle(h)
         });
         let lease = Lease { pool: &self.pool, h: Some(h) };

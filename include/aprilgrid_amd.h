@@ -180,6 +180,19 @@ int agx_detector_set_option(agx_detector *det, const char *name, int value);
  * of it, 3 = the verify launch, then a workgroup per frame (the values of option "sparse_path"). */
 int agx_detector_get_option(const agx_detector *det, const char *name, int *value);
 
+/* The sigma of the chain's blur (src/detector.rs:410 hard-codes 1.5f, the default here).  Per-handle state; it applies from the
+ * next enqueue on to every entry that runs the chain on this handle: agx_refined_saddle_points, agx_detect, agx_detect_planes,
+ * agx_saddles_batch_enqueue[_to], agx_detect_batch, agx_detect_batch_enqueue[_to], agx_refine_points_enqueue with
+ * AGX_REFINE_BLURRED, and a group's ranks through agx_group_detector(group, r).  sigma as agx_planes_enqueue's when positive:
+ * finite, > 0, ceilf(2 sigma) in 1 .. 16; anything else, 0 included, is AGX_ERR_ARG and the stored value stays (so does a NULL
+ * det or a NULL sigma).  With the stored value bit-equal to 1.5f the chain starts with its fused seven-tap blur kernel, as it
+ * always did; at any other value with k_gauss_blur (the taps of agx_debug_blur_weights(sigma)) and k_response_front, which
+ * hand the same products to the unchanged sparse stages: results are the reference's with `1.5` replaced by sigma, bit for
+ * bit (tests/test_gpu_sigma.py).  Read-only option "last_chain_front": 0 = the last chain batch ran the fused kernel, 1 = the
+ * any-sigma front. */
+int agx_detector_set_blur_sigma(agx_detector *det, float sigma);
+int agx_detector_get_blur_sigma(const agx_detector *det, float *sigma);
+
 /* Stream selection.  external != 0: launch on the caller's stream `hip_stream` (hipStream_t as
  * void*; NULL is HIP's legacy default stream) so that the chain is stream-ordered behind the
  * producer of the frames and in front of consumers of the results (e.g. an RCCL gather), and
@@ -331,7 +344,7 @@ enum { AGX_POINT_REFINED = 0,
                                      (`as i32`, unchecked indexing), are OUTSIDE; so is every point of a frame smaller than 9x9 */
        AGX_POINT_NOT_SADDLE = 2,  /* :331-339: not (d < 0) */
        AGX_POINT_MOVED = 3 };     /* :342-347: |x0| or |y0| > 1, or not |c5| < k */
-enum { AGX_REFINE_BLURRED = 0,    /* frames of any agx_format; refined on their sigma = 1.5 blur, as
+enum { AGX_REFINE_BLURRED = 0,    /* frames of any agx_format; refined on their blur at the handle's sigma, as
                                      refined_saddle_points does (:409-410, :430) */
        AGX_REFINE_PLANE = 1 };    /* format must be AGX_LF32 (else AGX_ERR_FORMAT): the plane IS image_input, taken as is
                                      (row stride a multiple of 4 bytes); no blur, no workspace plane */
@@ -616,7 +629,9 @@ int agx_luma8(const void *pixels, int width, int height, size_t row_stride_bytes
 /* Per-kernel device time of the chain, from hipEvents recorded on the detector's stream
  * around each launch while profiling is on.  names/ms/launches are arrays of
  * AGX_N_KERNELS entries (the chain has four launches since round 3: entries behind the last one
- * carry a NULL name and zeros); ms accumulates since the last reset. */
+ * carry a NULL name and zeros); ms accumulates since the last reset.  At a blur sigma other than 1.5
+ * (agx_detector_set_blur_sigma) the launches of the any-sigma front -- k_gauss_blur, k_response_front -- are NOT timed and entry 0
+ * stays as it is; the sparse stages' entries are timed as ever (tools/bench_sigma.py brackets the rest with its own events). */
 #define AGX_N_KERNELS 5
 int agx_profile_enable(agx_detector *det, int on); /* 0 off, 1 = the blur kernel only (2 events per batch), 2 = every kernel */
 int agx_profile_reset(agx_detector *det);
