@@ -194,7 +194,7 @@ static int chunk_luma8(agx_detector *det, const void *d_frames, int n_frames, in
     if (slot < 0 || slot >= n_slots) return AGX_ERR_ARG;
     // a layout of the front-end kernel whose plane the chain of these very frames has just read (the batch enqueued last):
     // 8-bit: that plane IS their to_luma8; 16-bit: k_luma8 narrows it (2 bytes per pixel to read instead of the frames' 4 .. 8)
-    const bool same_batch = format_front(format) && det->enqueued && det->front_format == format && det->front_src == d_frames &&
+    const bool same_batch = format_front(format) && chain_in_flight(det) && det->front_format == format && det->front_src == d_frames &&
                             det->front_frames == n_frames;
     const bool front = same_batch && !format_16bit(format), front16 = same_batch && format_16bit(format);
     uint8_t *d_front = det->side[SB_FRONT].ptr<uint8_t>();
@@ -257,7 +257,7 @@ static int tail_prepare(agx_detector *det)
 // largest frame count and the largest capacity seen.
 static int enqueue_tail(agx_detector *det, const void *d_luma, size_t luma_row_stride, size_t luma_frame_stride, uint32_t tag_cap, bool to_device)
 {
-    if (!det->enqueued || det->external_out) return AGX_ERR_STATE;
+    if (!chain_in_flight(det) || det->external_out) return AGX_ERR_STATE;
     const ChainArgs &a = det->args;
     if (tag_cap == 0 || luma_row_stride > 0x7fffffffu) return AGX_ERR_ARG;
     if (tag_cap > 128u) tag_cap = 128u;  // (the kernel's own list of distinct ids; frames beyond it take the host tail)
@@ -305,7 +305,7 @@ static int enqueue_tail(agx_detector *det, const void *d_luma, size_t luma_row_s
 // tail on the detector's stream (tail_kernels.hip, k_publish_tags)
 static int publish_tags(agx_detector *det, uint32_t cap_per_frame, agx_tag *d_tags, uint32_t *d_counts, int *d_status)
 {
-    if (!det->enqueued || !det->dtail_frames) return AGX_ERR_STATE;
+    if (!chain_in_flight(det) || !det->dtail_frames) return AGX_ERR_STATE;
     const int e = launch_publish_tags(det->side[SB_DTABLE].ptr<uint32_t>(), det->side[SB_DTAGS].ptr<agx_tag>(), det->dtail_tag_cap, det->args.ctr,
                                       det->args.n_frames, cap_per_frame, d_tags, d_counts, d_status, det->stream);
     return e == 0 ? AGX_OK : AGX_ERR_HIP;
@@ -313,7 +313,7 @@ static int publish_tags(agx_detector *det, uint32_t cap_per_frame, agx_tag *d_ta
 // agx_group_detect_enqueue: the same results packed -- frame table + slab in the group's device buffers (k_pack_scan, k_pack_tags)
 static int pack_tags(agx_detector *det, uint32_t cap_per_frame, uint32_t *d_table, agx_tag *d_slab, uint32_t slab_records)
 {
-    if (!det->enqueued || !det->dtail_frames) return AGX_ERR_STATE;
+    if (!chain_in_flight(det) || !det->dtail_frames) return AGX_ERR_STATE;
     const int e = launch_pack_tags(det->side[SB_DTABLE].ptr<uint32_t>(), det->side[SB_DTAGS].ptr<agx_tag>(), det->dtail_tag_cap, det->args.ctr,
                                    det->args.n_frames, cap_per_frame, d_table, d_slab, slab_records, det->stream);
     return e == 0 ? AGX_OK : AGX_ERR_HIP;
@@ -893,10 +893,10 @@ static int detect_batch_impl(agx_detector *det, const void *frames, const void *
 // pool for the frames the kernel handed back -- every frame without the device tail -- from the chain's compact saddle lists and
 // the u8 luma of those frames only, copied down from the device.  No frame ever exists in host memory as the caller's pixels.
 int agx::detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
-                             size_t frame_stride_bytes, int format, uint32_t cap_per_frame, int kind, agx_tag *d_tags,
+                             size_t frame_stride_bytes, int format, uint32_t cap_per_frame, int results, agx_tag *d_tags,
                              uint32_t *d_counts, int *d_status, uint32_t slab_records)
 {
-    const bool to_device = kind != 1;  // the tail's rows and table stay in device memory (SB_DTAGS + SB_DTABLE)
+    const bool to_device = results != RESULTS_HOST;  // the tail's rows and table stay in device memory (SB_DTAGS + SB_DTABLE)
     // option "device_tail" -1 (default) or 1: the device tail wherever this process may use it (no batch-size rule: with the frames
     // on the device there is no upload for the host tail to hide behind); 0, or a tail this process may not use: the host tail
     const int tail_mode = device_tail_mode(det);
@@ -916,7 +916,7 @@ int agx::detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_fram
         luma_frame = (size_t)width * (size_t)height;
     }
     if (!rc && on_device) rc = enqueue_tail(det, d_luma, luma_row, luma_frame, std::max(cap_per_frame, 1u), to_device);
-    if (!rc && kind == 3) {
+    if (!rc && results == RESULTS_GROUP) {
         // a group's batch: d_counts = the packed frame table [n_frames][4], d_tags = the slab (group.cpp owns both).  Without
         // the device tail no pack kernel runs: the group fills the table with "handed back" itself
         if (on_device) rc = pack_tags(det, cap_per_frame, d_counts, d_tags, slab_records);
@@ -933,8 +933,9 @@ int agx::detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_fram
         abandon_batch(det);  // (nothing half-enqueued is left to be fetched)
         return rc;
     }
+    det->batch = BATCH_DETECT;  // (over the chain's BATCH_SADDLES)
     DetectPending &p = det->detect;
-    p.kind = kind;
+    p.results = results;
     p.device_tail = on_device;
     p.n_frames = n_frames;
     p.width = width;
@@ -967,27 +968,13 @@ int agx::decode_quads_enqueue_impl(agx_detector *det, const void *d_frames, int 
     if (!d_tags && d_bits) return fail(det, AGX_ERR_ARG, "d_bits needs d_tags and d_status (internal results: the fetch's bits argument)");
     if ((((uintptr_t)d_quads | (uintptr_t)d_counts | (uintptr_t)d_point_status | (uintptr_t)d_tags | (uintptr_t)d_status) & 3) || ((uintptr_t)d_bits & 7))
         return fail(det, AGX_ERR_ARG, "quads, counts, point statuses, tags and statuses must be 4-byte aligned, bits 8-byte aligned");
-    if (!format_px_bytes(format) || format == AGX_LF32) return fail(det, AGX_ERR_FORMAT, "format must be one of AGX_L8 .. AGX_RGBA16 but AGX_LF32 (the decode reads to_luma8)");
-    if (width < 1 || height < 1) return fail(det, AGX_ERR_ARG, "width and height must be >= 1");
-    if ((long long)width * height >= (1ll << 30) || width > 65000) return fail(det, AGX_ERR_ARG, "frame too large (>= 2^30 px or wider than 65000)");
-    if (n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
-    if (format_front(format) && height > 16 * 65535) return fail(det, AGX_ERR_ARG, "frames of this format may have at most 1048560 rows");
+    if (const int rc = check_frame_batch(det, {d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format},
+                                         {/*min_side*/ 1, /*lf32*/ false, /*lone_frame_stride*/ false, /*align16*/ true, /*front_rows*/ true}))
+        return rc;
     const size_t slots = (size_t)n_frames * quads_per_frame;
     if (slots >= ((size_t)1 << 29)) return fail(det, AGX_ERR_ARG, "at most 2^29 - 1 quads per batch");
-    const size_t px_bytes = (size_t)format_px_bytes(format);
-    if (row_stride_bytes < (size_t)width * px_bytes || row_stride_bytes > 0x7fffffffu ||
-        (n_frames > 1 && frame_stride_bytes < row_stride_bytes * format_rows(format, height)))
-        return fail(det, AGX_ERR_ARG, "strides must cover a row / a frame");
-    if (format_16bit(format) && ((row_stride_bytes | (n_frames > 1 ? frame_stride_bytes : 0) | (uintptr_t)d_frames) & 1))
-        return fail(det, AGX_ERR_ARG, "16-bit pixels must be 2-byte aligned");
-    if (hipSetDevice(det->device) != hipSuccess) return fail(det, AGX_ERR_HIP, "hipSetDevice");
-    // this batch replaces whatever was in flight (SB_LUMA_D may grow below: nothing points into it any more)
-    det->detect.kind = 0;
-    det->refine.kind = 0;
-    det->decode.kind = 0;
-    det->find.kind = 0;
-    det->front_format = -1;
-    det->enqueued = false;
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // (SB_LUMA_D may grow below: nothing points into it any more)
     if (tail_prepare(det)) return fail(det, AGX_ERR_HIP, "hipMalloc / hipMemcpy: the family's code list");
     const uint8_t *d_luma = static_cast<const uint8_t *>(d_frames);  // detector.rs:507: L8 frames are their own u8 luma
     size_t luma_row = row_stride_bytes, luma_frame = frame_stride_bytes;
@@ -997,13 +984,13 @@ int agx::decode_quads_enqueue_impl(agx_detector *det, const void *d_frames, int 
         luma_row = (size_t)width;
         luma_frame = (size_t)width * (size_t)height;
     }
-    int kind = 2;
+    int results = RESULTS_CALLER;
     if (!d_tags) {
         d_tags = static_cast<agx_tag *>(side_ensure(det, SB_DECODE_TAGS, slots * sizeof(agx_tag), 0));
         d_status = static_cast<uint32_t *>(side_ensure(det, SB_DECODE_STATUS, slots * sizeof(uint32_t), 0));
         d_bits = static_cast<uint64_t *>(side_ensure(det, SB_DECODE_BITS, slots * sizeof(uint64_t), 0));
         if (!d_tags || !d_status || !d_bits) return fail(det, AGX_ERR_HIP, "hipMalloc: decoded quads");
-        kind = 1;
+        results = RESULTS_HOST;
     }
     DecodeQuadsArgs q{};
     q.luma = d_luma;
@@ -1027,7 +1014,8 @@ int agx::decode_quads_enqueue_impl(agx_detector *det, const void *d_frames, int 
     q.bits = d_bits;
     const hipError_t e = (hipError_t)launch_decode_quads(q, det->stream);
     if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_decode_quads: ") + hipGetErrorString(e));
-    det->decode.kind = kind;
+    det->batch = BATCH_DECODE;
+    det->decode.results = results;
     det->decode.n_frames = n_frames;
     det->decode.quads_per_frame = quads_per_frame;
     det->decode.d_counts = d_counts;
@@ -1037,19 +1025,18 @@ int agx::decode_quads_enqueue_impl(agx_detector *det, const void *d_frames, int 
 int agx::decode_quads_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *status, uint64_t *bits)
 {
     if (!det) return AGX_ERR_ARG;
+    if (const int other = refuse_other_batch(det, BATCH_DECODE)) return other;
     const DecodePending b = det->decode;
-    if (!b.kind && det->find.kind)
-        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_find_boards_enqueue's: fetch it with agx_find_boards_fetch");
-    if (!b.kind) return fail(det, AGX_ERR_STATE, "no agx_decode_quads_enqueue batch in flight");
-    if (b.kind == 1 && (!out || !status)) return fail(det, AGX_ERR_ARG, "null output");  // (the batch stays in flight)
-    if (hipSetDevice(det->device) != hipSuccess) return fail(det, AGX_ERR_HIP, "hipSetDevice");
-    det->decode.kind = 0;  // resolved by this call, whatever it returns
+    const bool to_host = b.results == RESULTS_HOST;
+    if (to_host && (!out || !status)) return fail(det, AGX_ERR_ARG, "null output");  // (the batch stays in flight)
+    HIP_TRY(det, hipSetDevice(det->device));
+    det->batch = BATCH_NONE;  // resolved by this call, whatever it returns
     const size_t slots = (size_t)b.n_frames * b.quads_per_frame;
     // host staging when counts were given (only the slots the kernel wrote reach the caller's arrays): in 8-byte words, the
     // bits, then the tags (9 x 4 bytes each), the statuses and the counts
     const size_t w_tags = slots, w_status = w_tags + (slots * sizeof(agx_tag) + 7) / 8, w_counts = w_status + (slots * 4 + 7) / 8;
     bool ok = true;
-    if (b.kind == 1) {
+    if (to_host) {
         const agx_tag *d_tags = det->side[SB_DECODE_TAGS].ptr<agx_tag>();
         const uint32_t *d_status = det->side[SB_DECODE_STATUS].ptr<uint32_t>();
         const uint64_t *d_bits = det->side[SB_DECODE_BITS].ptr<uint64_t>();
@@ -1067,7 +1054,7 @@ int agx::decode_quads_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *stat
         }
     }
     if (hipStreamSynchronize(det->stream) != hipSuccess || !ok) return fail(det, AGX_ERR_HIP, "agx_decode_quads_fetch: copy / wait");
-    if (b.kind == 1 && b.d_counts) {
+    if (to_host && b.d_counts) {
         const std::vector<uint64_t> &h = det->decode_host;
         const char *h_tags = reinterpret_cast<const char *>(h.data() + w_tags);
         const uint32_t *h_status = reinterpret_cast<const uint32_t *>(h.data() + w_status), *h_counts = reinterpret_cast<const uint32_t *>(h.data() + w_counts);
@@ -1104,24 +1091,18 @@ int agx::find_boards_enqueue_impl(agx_detector *det, const void *d_saddles, size
     if (n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
     const size_t rows = (size_t)n_frames * quads_per_frame;
     if (rows >= ((size_t)1 << 27)) return fail(det, AGX_ERR_ARG, "at most 2^27 - 1 quad rows per batch");
-    if (hipSetDevice(det->device) != hipSuccess) return fail(det, AGX_ERR_HIP, "hipSetDevice");
-    // this batch replaces whatever was in flight
-    det->detect.kind = 0;
-    det->refine.kind = 0;
-    det->decode.kind = 0;
-    det->find.kind = 0;
-    det->front_format = -1;
-    det->enqueued = false;
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);
     const bool host_only = device_tail_mode(det) == 0;
     if (!host_only && tail_prepare(det)) return fail(det, AGX_ERR_HIP, "the device tail's set-up (code list, kernel attributes)");
-    int kind = 2;
+    int results = RESULTS_CALLER;
     if (!d_quads) {
         d_quads = static_cast<uint32_t *>(side_ensure(det, SB_FIND_QUADS, rows * 4 * sizeof(uint32_t), 0));
         d_n_quads = static_cast<uint32_t *>(side_ensure(det, SB_FIND_COUNTS, (size_t)n_frames * sizeof(uint32_t), 0));
         d_status = static_cast<uint32_t *>(side_ensure(det, SB_FIND_STATUS, (size_t)n_frames * sizeof(uint32_t), 0));
         if (!d_quad_points) d_quad_points = static_cast<float *>(side_ensure(det, SB_FIND_POINTS, rows * 8 * sizeof(float), 0));
         if (!d_quads || !d_n_quads || !d_status || !d_quad_points) return fail(det, AGX_ERR_HIP, "hipMalloc: board quads");
-        kind = 1;
+        results = RESULTS_HOST;
     }
     FindBoardsArgs q{};
     q.saddles = static_cast<const uint8_t *>(d_saddles);
@@ -1140,8 +1121,9 @@ int agx::find_boards_enqueue_impl(agx_detector *det, const void *d_saddles, size
     q.host_only = host_only ? 1 : 0;
     const hipError_t e = (hipError_t)launch_find_boards(q, det->stream);
     if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_find_boards: ") + hipGetErrorString(e));
+    det->batch = BATCH_FIND;
     FindPending &p = det->find;
-    p.kind = kind;
+    p.results = results;
     p.n_frames = n_frames;
     p.saddles_per_frame = saddles_per_frame;
     p.quads_per_frame = quads_per_frame;
@@ -1160,11 +1142,11 @@ int agx::find_boards_enqueue_impl(agx_detector *det, const void *d_saddles, size
 int agx::find_boards_fetch_impl(agx_detector *det, uint32_t *quads, float *quad_points, uint32_t *n_quads, uint32_t *status, int n_threads)
 {
     if (!det) return AGX_ERR_ARG;
+    if (const int other = refuse_other_batch(det, BATCH_FIND)) return other;
     const FindPending b = det->find;
-    if (!b.kind) return fail(det, AGX_ERR_STATE, "no agx_find_boards_enqueue batch in flight");
-    if (b.kind == 1 && (!quads || !n_quads || !status)) return fail(det, AGX_ERR_ARG, "null output");  // (the batch stays in flight)
-    if (hipSetDevice(det->device) != hipSuccess) return fail(det, AGX_ERR_HIP, "hipSetDevice");
-    det->find.kind = 0;  // resolved by this call, whatever it returns
+    if (b.results == RESULTS_HOST && (!quads || !n_quads || !status)) return fail(det, AGX_ERR_ARG, "null output");  // (the batch stays in flight)
+    HIP_TRY(det, hipSetDevice(det->device));
+    det->batch = BATCH_NONE;  // resolved by this call, whatever it returns
     det->last_find_frames = b.n_frames;
     det->last_find_handed_back = 0;
     if (n_threads <= 0) n_threads = agx_host_parallelism();
@@ -1400,14 +1382,13 @@ static int resolve_on_host(agx_detector *det, const DetectPending &b, const std:
 
 int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads)
 {
-    DetectPending &pend = det->detect;
-    const DetectPending b = pend;
-    if ((b.kind == 1 && !counts) || (out && b.cap && !counts)) return AGX_ERR_ARG;  // (the batch stays in flight)
-    if (b.kind == 1 && !out && b.cap) return AGX_ERR_ARG;
-    pend.kind = 0;  // resolved by this call, whatever happens below
+    const DetectPending b = det->detect;
+    if ((b.results == RESULTS_HOST && !counts) || (out && b.cap && !counts)) return AGX_ERR_ARG;  // (the batch stays in flight)
+    if (b.results == RESULTS_HOST && !out && b.cap) return AGX_ERR_ARG;
+    det->batch = BATCH_SADDLES;  // resolved by this call, whatever happens below; fetch_compact reads the chain's results under it
     const int n = b.n_frames;
     const uint32_t cap = b.cap;
-    const bool to_dev = b.kind == 2;
+    const bool to_dev = b.results == RESULTS_CALLER;
     hipStream_t stream = det->stream;
     if (n_threads <= 0) n_threads = agx_host_parallelism();
     // every frame's result as the host knows it (the device arrays of _enqueue_to get the same), the frames the host tail takes,
@@ -1499,10 +1480,9 @@ int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, in
 // counts and statuses are written: the other frames' are the group's, from the gathered table and slab.  Resolves the batch.
 int agx::group_detect_fetch_impl(agx_detector *det, const char *back_in, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads)
 {
-    DetectPending &pend = det->detect;
-    const DetectPending b = pend;
-    if (b.kind != 3 || !det->enqueued) return AGX_ERR_STATE;  // (something else was enqueued on the borrowed detector since)
-    pend.kind = 0;
+    const DetectPending b = det->detect;
+    if (det->batch != BATCH_DETECT || b.results != RESULTS_GROUP) return AGX_ERR_STATE;  // (something else was enqueued on the borrowed detector since)
+    det->batch = BATCH_SADDLES;  // (as detect_fetch_impl)
     const int n = b.n_frames;
     if (n_threads <= 0) n_threads = agx_host_parallelism();
     std::vector<uint32_t> cnt;

@@ -28,6 +28,52 @@ int agx::fail(agx_detector *d, int status, const std::string &msg)
     return status;
 }
 
+// The enqueue / fetch pair of every kind of batch (BatchKind), for the refusals of the other pairs' fetches
+static const struct { const char *enqueue, *fetch; } kBatchPair[BATCH_KINDS] = {
+    {nullptr, nullptr},
+    {"agx_saddles_batch_enqueue", "agx_saddles_batch_fetch"},
+    {"agx_detect_batch_enqueue", "agx_detect_batch_fetch"},
+    {"agx_refine_points_enqueue", "agx_refine_points_fetch"},
+    {"agx_decode_quads_enqueue", "agx_decode_quads_fetch"},
+    {"agx_find_boards_enqueue", "agx_find_boards_fetch"}};
+
+int agx::refuse_other_batch(agx_detector *det, int wanted)
+{
+    const int have = det->batch;
+    if (have == wanted) return AGX_OK;
+    if (have == BATCH_NONE) return fail(det, AGX_ERR_STATE, std::string("no ") + kBatchPair[wanted].enqueue + " batch in flight");
+    return fail(det, AGX_ERR_STATE, std::string("the batch in flight is ") + kBatchPair[have].enqueue + "'s: fetch it with " + kBatchPair[have].fetch);
+}
+
+// AGX_OK for an agx_format (lf32: AGX_LF32 among them), else AGX_ERR_FORMAT
+static int check_format(agx_detector *det, int format, bool lf32)
+{
+    if (format_px_bytes(format) && (lf32 || format != AGX_LF32)) return AGX_OK;
+    return fail(det, AGX_ERR_FORMAT, lf32 ? "format must be one of AGX_L8 .. AGX_RGBA16 (agx_format)"
+                                          : "format must be one of AGX_L8 .. AGX_RGBA16 but AGX_LF32 (the decode reads to_luma8)");
+}
+
+int agx::check_frame_batch(agx_detector *det, const FrameBatch &b, const BatchRules &rules)
+{
+    if (!b.frames || b.n_frames <= 0) return fail(det, AGX_ERR_ARG, "null frames or n_frames <= 0");
+    if (const int rc = check_format(det, b.format, rules.lf32)) return rc;
+    const size_t px_bytes = (size_t)format_px_bytes(b.format);
+    if (b.width < rules.min_side || b.height < rules.min_side)
+        return fail(det, AGX_ERR_ARG, "width and height must be >= " + std::to_string(rules.min_side));
+    if ((long long)b.width * b.height >= (1ll << 30) || b.width > 65000) return fail(det, AGX_ERR_ARG, "frame too large (>= 2^30 px or wider than 65000)");
+    if (b.n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
+    // (the kernels take the row stride as an int)
+    if (b.row_stride < (size_t)b.width * px_bytes || b.row_stride > 0x7fffffffu ||
+        (b.n_frames > 1 && b.frame_stride < b.row_stride * format_rows(b.format, b.height)))
+        return fail(det, AGX_ERR_ARG, "strides must cover a row / a frame");
+    const size_t low_bits = b.row_stride | (uintptr_t)b.frames | (b.n_frames > 1 || rules.lone_frame_stride ? b.frame_stride : 0);
+    if (rules.align16 && format_16bit(b.format) && (low_bits & 1)) return fail(det, AGX_ERR_ARG, "16-bit pixels must be 2-byte aligned");
+    if (b.format == AGX_LF32 && (low_bits & 3)) return fail(det, AGX_ERR_ARG, "f32 pixels must be 4-byte aligned");
+    if (rules.front_rows && format_front(b.format) && b.height > 16 * 65535)  // (k_front_luma's grid: 16 rows per workgroup, 65535 workgroups)
+        return fail(det, AGX_ERR_ARG, "frames of this format may have at most 1048560 rows");
+    return AGX_OK;
+}
+
 namespace {
 
 const char *kKernelNames[K_COUNT] = {"k_blur_hessian", "k_verify_seeds", "k_flood_refine", "k_rare_emit", "k_sparse_frame"};
@@ -67,13 +113,6 @@ int agx_guard(const agx_detector *det_c, F &&body) noexcept
         return AGX_ERR_STATE;
     }
 }
-
-#define HIP_TRY(det, expr)                                                                     \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail((det), AGX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 // Blur taps, reference src/image_util.rs:111-124 (sigma = 1.5 at the call site detector.rs:410: radius 3, seven taps): the
 // 2 * radius + 1 taps into w, which has room for them.  Returns the radius.
@@ -491,7 +530,7 @@ int enqueue_chain(agx_detector *d)
     if (rc) return rc;
     d->ctr_cleared[p ^ 1] = capturing ? 0 : need;  // k_rare of this batch clears it, stream-ordered before the next batch
     d->ctr_cur = p;
-    d->enqueued = true;
+    d->batch = BATCH_SADDLES;
     return AGX_OK;
 }
 
@@ -545,7 +584,39 @@ bool counters_of_row(const uint32_t *row, FrameCounters &c)
     return !(row[2] & (FLAG_CAND_OVERFLOW | FLAG_ROOT_OVERFLOW | FLAG_OUT_OVERFLOW));
 }
 
-const char *kFormatMsg = "format must be one of AGX_L8 .. AGX_RGBA16 (agx_format)";
+// AGX_LA8 .. AGX_RGBA16: the front-end kernel writes the batch's integer luma plane (tight u8 / u16, SB_FRONT) and b becomes that
+// plane, which the L8 / L16 paths read: to_luma32f of an integer image is its integer luma / 255 (/ 65535)
+int front_luma_plane(agx_detector *det, FrameBatch &b)
+{
+    const size_t out_px = format_16bit(b.format) ? 2 : 1, need = (size_t)b.n_frames * (size_t)b.width * (size_t)b.height * out_px;
+    void *d_front = side_ensure(det, SB_FRONT, need, 0);
+    if (!d_front) return fail(det, AGX_ERR_HIP, "hipMalloc: front-end luma plane");
+    hipError_t e = (hipError_t)launch_front_luma(b.frames, b.row_stride, b.frame_stride, b.n_frames, b.format, d_front, 0, b.width, b.height,
+                                                 det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_front_luma: ") + hipGetErrorString(e));
+    b = {d_front, b.n_frames, b.width, b.height, b.width * out_px, b.width * out_px * b.height, out_px == 2 ? AGX_L16 : AGX_L8};
+    return AGX_OK;
+}
+
+// One image in host memory: the checks every host entry point makes of it (min_side, lf32: as BatchRules) and, with upload, its
+// copy into SB_STAGE, rows a multiple of 4 bytes apart, on the detector's stream: out = the batch of one it is there
+int stage_host_frame(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes, int format, int min_side, bool lf32,
+                     bool upload, FrameBatch &out)
+{
+    if (!pixels) return fail(det, AGX_ERR_ARG, "null argument");
+    if (const int rc = check_format(det, format, lf32)) return rc;
+    if (width < min_side || height < min_side) return fail(det, AGX_ERR_ARG, "width and height must be >= " + std::to_string(min_side));
+    const size_t row_bytes = (size_t)width * format_px_bytes(format), pitch = (row_bytes + 3) & ~(size_t)3;
+    if (row_stride_bytes < row_bytes) return fail(det, AGX_ERR_ARG, "row stride smaller than a row");
+    if (!upload) return AGX_OK;
+    HIP_TRY(det, hipSetDevice(det->device));
+    const size_t rows = format_rows(format, height);  // (the planar layout: three planes, one under the other)
+    void *d_stage = side_ensure(det, SB_STAGE, pitch * rows, 0);
+    if (!d_stage) return fail(det, AGX_ERR_HIP, "hipMalloc: staging buffer");
+    HIP_TRY(det, hipMemcpy2DAsync(d_stage, pitch, pixels, row_stride_bytes, row_bytes, rows, hipMemcpyHostToDevice, det->stream));
+    out = {d_stage, 1, width, height, pitch, pitch * rows, format};
+    return AGX_OK;
+}
 
 }  // namespace
 
@@ -825,46 +896,24 @@ static int batch_enqueue_impl(agx_detector *det, const void *d_frames, int n_fra
                               size_t row_stride_bytes, size_t frame_stride_bytes, int format, void *d_saddles,
                               uint32_t saddle_capacity, void *d_frame_table, bool blur_only = false)
 {
-    if (!det || !d_frames || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null frames or n_frames <= 0");
-    if (!format_px_bytes(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
-    if (width < 2 || height < 2) return fail(det, AGX_ERR_ARG, "width and height must be >= 2");
-    if ((long long)width * height >= (1ll << 30) || width > 65000) return fail(det, AGX_ERR_ARG, "frame too large (>= 2^30 px or wider than 65000)");
-    const size_t px_bytes = (size_t)format_px_bytes(format);
-    if (row_stride_bytes < (size_t)width * px_bytes || row_stride_bytes > 0x7fffffffu ||
-        (n_frames > 1 && frame_stride_bytes < row_stride_bytes * format_rows(format, height)))
-        return fail(det, AGX_ERR_ARG, "strides must cover a row / a frame");
-    if (format_16bit(format) && ((row_stride_bytes | frame_stride_bytes | (uintptr_t)d_frames) & 1))
-        return fail(det, AGX_ERR_ARG, "16-bit pixels must be 2-byte aligned");
-    if (format == AGX_LF32 && ((row_stride_bytes | frame_stride_bytes | (uintptr_t)d_frames) & 3))
-        return fail(det, AGX_ERR_ARG, "f32 pixels must be 4-byte aligned");
-    if (n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
-    if (format_front(format) && height > 16 * 65535)  // (k_front_luma's grid: 16 rows per workgroup, 65535 workgroups)
-        return fail(det, AGX_ERR_ARG, "frames of this format may have at most 1048560 rows");
-    det->detect.kind = 0;  // (this batch replaces whatever was in flight, an agx_detect_batch_enqueue's included)
-    det->refine.kind = 0;  // (... and an agx_refine_points_enqueue's)
-    det->decode.kind = 0;  // (... and an agx_decode_quads_enqueue's)
-    det->find.kind = 0;    // (... and an agx_find_boards_enqueue's)
-    det->front_format = -1;
-    HIP_TRY(det, hipSetDevice(det->device));
-    int rc = ensure_workspace(det, n_frames, width, height);
+    if (!det) return AGX_ERR_ARG;
+    FrameBatch b{d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format};
+    int rc = check_frame_batch(det, b, {/*min_side*/ 2, /*lf32*/ true, /*lone_frame_stride*/ true, /*align16*/ true, /*front_rows*/ true});
     if (rc) return rc;
-    if (format_front(format)) {
-        // AGX_LA8 .. AGX_RGBA16: the front-end kernel writes the batch's integer luma plane (tight u8 / u16) and the L8 / L16
-        // chain reads that: to_luma32f of an integer image is its integer luma / 255 (/ 65535)
-        const size_t out_px = format_16bit(format) ? 2 : 1, need = (size_t)n_frames * (size_t)width * (size_t)height * out_px;
-        void *d_front = side_ensure(det, SB_FRONT, need, 0);
-        if (!d_front) return fail(det, AGX_ERR_HIP, "hipMalloc: front-end luma plane");
-        hipError_t e = (hipError_t)launch_front_luma(d_frames, row_stride_bytes, frame_stride_bytes, n_frames, format, d_front, 0,
-                                                     width, height, det->stream);
-        if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_front_luma: ") + hipGetErrorString(e));
+    begin_batch(det);
+    HIP_TRY(det, hipSetDevice(det->device));
+    rc = ensure_workspace(det, n_frames, width, height);
+    if (rc) return rc;
+    if (format_front(format)) {  // the chain reads the front-end kernel's plane, and to_luma8 of this batch may be derived from it
+        if ((rc = front_luma_plane(det, b))) return rc;
         det->front_src = d_frames;
         det->front_format = format;
         det->front_frames = n_frames;
-        d_frames = d_front;
-        row_stride_bytes = (size_t)width * out_px;
-        frame_stride_bytes = row_stride_bytes * (size_t)height;
-        format = out_px == 2 ? AGX_L16 : AGX_L8;
     }
+    d_frames = b.frames;
+    row_stride_bytes = b.row_stride;
+    frame_stride_bytes = b.frame_stride;
+    format = b.format;
     // rows that are not 4-byte aligned (tightly packed L8 / RGB8 of a width that is not a multiple
     // of 4, odd-width L16): the blur kernel gathers bytes instead of loading dwords
     const bool byte_rows = ((row_stride_bytes | (uintptr_t)d_frames | (n_frames > 1 ? frame_stride_bytes : 0)) & 3) != 0;
@@ -910,10 +959,7 @@ static int batch_enqueue_impl(agx_detector *det, const void *d_frames, int n_fra
         det->resp_stored = true;
     }
     if (!plan_k1(a, det->k1_rows)) return fail(det, AGX_ERR_ARG, "unsupported frame geometry");
-    if (blur_only) {  // agx_refine_points_enqueue: nothing of the chain will be there to be fetched
-        det->enqueued = false;
-        return enqueue_blur_only(det);
-    }
+    if (blur_only) return enqueue_blur_only(det);  // agx_refine_points_enqueue: nothing of the chain will be there to be fetched
     return enqueue_chain(det);
 }
 
@@ -943,7 +989,7 @@ static int saddles_fetch_impl(agx_detector *det, agx_saddle *out, uint32_t cap_p
 {
     return agx_guard(det, [&]() -> int {
     if (!det || !counts || (!out && cap_per_frame)) return fail(det, AGX_ERR_ARG, "null output");
-    if (!det->enqueued) return fail(det, AGX_ERR_STATE, "no batch enqueued");
+    if (!chain_in_flight(det)) return fail(det, AGX_ERR_STATE, "no batch enqueued");
     if (det->external_out) return fail(det, AGX_ERR_STATE, "last batch wrote to caller-owned device buffers");
     HIP_TRY(det, hipSetDevice(det->device));
     const ChainArgs &a = det->args;
@@ -1009,30 +1055,26 @@ int agx_saddles_batch_fetch(agx_detector *det, agx_saddle *out, uint32_t cap_per
                             int *frame_status)
 {
     return agx_guard(det, [&]() -> int {
-    if (det && det->refine.kind)
-        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_refine_points_enqueue's: fetch it with agx_refine_points_fetch");
-    if (det && det->decode.kind)
-        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_decode_quads_enqueue's: fetch it with agx_decode_quads_fetch");
-    if (det && det->find.kind)
-        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_find_boards_enqueue's: fetch it with agx_find_boards_fetch");
-    if (det && det->enqueued && det->detect.kind)
-        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_detect_batch_enqueue's: fetch it with agx_detect_batch_fetch");
+    if (det && det->batch != BATCH_NONE)  // (none: the null-output check comes first, below)
+        if (const int rc = refuse_other_batch(det, BATCH_SADDLES)) return rc;
     return saddles_fetch_impl(det, out, cap_per_frame, counts, frame_status);
     });
 }
 
 // detect over a batch in device memory, stream-ordered (csrc/detect_batch.cpp: the chain, k_luma8, the device tail, the fetch)
 static int detect_enqueue_checked(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
-                                  size_t frame_stride_bytes, int format, uint32_t cap_per_frame, int kind, agx_tag *d_tags,
+                                  size_t frame_stride_bytes, int format, uint32_t cap_per_frame, int results, agx_tag *d_tags,
                                   uint32_t *d_counts, int *d_status, uint32_t slab_records = 0)
 {
-    const bool to_device = kind == 2;
+    const bool to_device = results == RESULTS_CALLER;
     if (!det) return AGX_ERR_ARG;
-    if (!format_px_bytes(format) || format == AGX_LF32)  // (the decode needs to_luma8: agx_detect_planes for an f32 plane)
+    // the format alone, ahead of everything else (the decode needs to_luma8: agx_detect_planes for an f32 plane); the chain's
+    // enqueue checks the whole batch
+    if (!format_px_bytes(format) || format == AGX_LF32)
         return fail(det, AGX_ERR_FORMAT, "format must be an integer agx_format (AGX_LF32: agx_detect_planes)");
     if (to_device && (!d_counts || !d_status || (!d_tags && cap_per_frame) || (((uintptr_t)d_tags | (uintptr_t)d_counts | (uintptr_t)d_status) & 3)))
         return fail(det, AGX_ERR_ARG, "null or misaligned output buffers");
-    return detect_enqueue_impl(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, cap_per_frame, kind,
+    return detect_enqueue_impl(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, cap_per_frame, results,
                                d_tags, d_counts, d_status, slab_records);
 }
 
@@ -1041,7 +1083,7 @@ int agx_detect_batch_enqueue(agx_detector *det, const void *d_frames, int n_fram
 {
     return agx_guard(det, [&]() -> int {
     return detect_enqueue_checked(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, cap_per_frame,
-                                  1, nullptr, nullptr, nullptr);
+                                  RESULTS_HOST, nullptr, nullptr, nullptr);
     });
 }
 
@@ -1051,7 +1093,7 @@ int agx_detect_batch_enqueue_to(agx_detector *det, const void *d_frames, int n_f
 {
     return agx_guard(det, [&]() -> int {
     return detect_enqueue_checked(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, cap_per_frame,
-                                  2, d_tags, d_counts, d_status);
+                                  RESULTS_CALLER, d_tags, d_counts, d_status);
     });
 }
 
@@ -1059,14 +1101,8 @@ int agx_detect_batch_fetch(agx_detector *det, agx_tag *out, uint32_t *counts, in
 {
     return agx_guard(det, [&]() -> int {
     if (!det) return AGX_ERR_ARG;
-    if (det->refine.kind)
-        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_refine_points_enqueue's: fetch it with agx_refine_points_fetch");
-    if (det->decode.kind)
-        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_decode_quads_enqueue's: fetch it with agx_decode_quads_fetch");
-    if (det->find.kind)
-        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_find_boards_enqueue's: fetch it with agx_find_boards_fetch");
-    if (!det->detect.kind || !det->enqueued) return fail(det, AGX_ERR_STATE, "no agx_detect_batch_enqueue batch in flight");
-    if (det->detect.kind == 3) return fail(det, AGX_ERR_STATE, "the batch in flight is a group's: fetch it with agx_group_detect_fetch");
+    if (const int other = refuse_other_batch(det, BATCH_DETECT)) return other;
+    if (det->detect.results == RESULTS_GROUP) return fail(det, AGX_ERR_STATE, "the batch in flight is a group's: fetch it with agx_group_detect_fetch");
     det->last_error.clear();
     const int rc = detect_fetch_impl(det, out, counts, frame_status, n_threads);
     if (rc == AGX_ERR_NOMEM) det->last_error = "out of host memory or threads";
@@ -1090,27 +1126,15 @@ static int refine_points_enqueue_impl(agx_detector *det, const void *d_frames, i
     if (image != AGX_REFINE_BLURRED && image != AGX_REFINE_PLANE) return fail(det, AGX_ERR_ARG, "image must be AGX_REFINE_BLURRED or AGX_REFINE_PLANE");
     if ((((uintptr_t)d_points | (uintptr_t)d_counts | (uintptr_t)d_out | (uintptr_t)d_status) & 3))
         return fail(det, AGX_ERR_ARG, "points, counts and result buffers must be 4-byte aligned");
-    if (!format_px_bytes(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
     if (image == AGX_REFINE_PLANE && format != AGX_LF32) return fail(det, AGX_ERR_FORMAT, "AGX_REFINE_PLANE takes an AGX_LF32 plane");
-    if (width < 1 || height < 1) return fail(det, AGX_ERR_ARG, "width and height must be >= 1");
-    if ((long long)width * height >= (1ll << 30) || width > 65000) return fail(det, AGX_ERR_ARG, "frame too large (>= 2^30 px or wider than 65000)");
-    if (n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
+    // (the 16-bit alignment and the front-end row limit are the chain's to check, where it runs: batch_enqueue_impl below)
+    if (const int rc = check_frame_batch(det, {d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format},
+                                         {/*min_side*/ 1, /*lf32*/ true, /*lone_frame_stride*/ false, /*align16*/ false, /*front_rows*/ false}))
+        return rc;
     const size_t slots = (size_t)n_frames * points_per_frame;
     if (slots >= ((size_t)1 << 31)) return fail(det, AGX_ERR_ARG, "at most 2^31 - 1 points per batch");
-    const size_t px_bytes = (size_t)format_px_bytes(format);
-    if (row_stride_bytes < (size_t)width * px_bytes || row_stride_bytes > 0x7fffffffu ||
-        (n_frames > 1 && frame_stride_bytes < row_stride_bytes * format_rows(format, height)))
-        return fail(det, AGX_ERR_ARG, "strides must cover a row / a frame");
-    if (format == AGX_LF32 && ((row_stride_bytes | (n_frames > 1 ? frame_stride_bytes : 0) | (uintptr_t)d_frames) & 3))
-        return fail(det, AGX_ERR_ARG, "f32 pixels must be 4-byte aligned");
     HIP_TRY(det, hipSetDevice(det->device));
-    // this batch replaces whatever was in flight
-    det->detect.kind = 0;
-    det->refine.kind = 0;
-    det->decode.kind = 0;
-    det->find.kind = 0;
-    det->front_format = -1;
-    det->enqueued = false;
+    begin_batch(det);
     RefinePointsArgs p{};
     p.W = width;
     p.H = height;
@@ -1135,9 +1159,9 @@ static int refine_points_enqueue_impl(agx_detector *det, const void *d_frames, i
             return fail(det, AGX_ERR_HIP, "hipMalloc: refined points");
         d_out = det->side[SB_REFINE_OUT].ptr<agx_saddle>();
         d_status = det->side[SB_REFINE_STATUS].ptr<uint32_t>();
-        det->refine.kind = 1;
+        det->refine.results = RESULTS_HOST;
     } else {
-        det->refine.kind = 2;
+        det->refine.results = RESULTS_CALLER;
     }
     p.points = static_cast<const float *>(d_points);
     p.points_per_frame = points_per_frame;
@@ -1145,10 +1169,8 @@ static int refine_points_enqueue_impl(agx_detector *det, const void *d_frames, i
     p.out = reinterpret_cast<float *>(d_out);
     p.status = d_status;
     hipError_t e = (hipError_t)launch_refine_points(p, det->rc, n_frames, det->stream);
-    if (e != hipSuccess) {
-        det->refine.kind = 0;
-        return fail(det, AGX_ERR_HIP, std::string("k_refine_points: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_refine_points: ") + hipGetErrorString(e));
+    det->batch = BATCH_REFINE;
     det->refine.n_frames = n_frames;
     det->refine.points_per_frame = points_per_frame;
     det->refine.d_counts = d_counts;
@@ -1158,17 +1180,14 @@ static int refine_points_enqueue_impl(agx_detector *det, const void *d_frames, i
 static int refine_points_fetch_impl(agx_detector *det, agx_saddle *out, uint32_t *status)
 {
     if (!det) return AGX_ERR_ARG;
+    if (const int other = refuse_other_batch(det, BATCH_REFINE)) return other;
     const RefinePending b = det->refine;
-    if (!b.kind && det->decode.kind)
-        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_decode_quads_enqueue's: fetch it with agx_decode_quads_fetch");
-    if (!b.kind && det->find.kind)
-        return fail(det, AGX_ERR_STATE, "the batch in flight is agx_find_boards_enqueue's: fetch it with agx_find_boards_fetch");
-    if (!b.kind) return fail(det, AGX_ERR_STATE, "no agx_refine_points_enqueue batch in flight");
-    if (b.kind == 1 && (!out || !status)) return fail(det, AGX_ERR_ARG, "null output");  // (the batch stays in flight)
+    const bool to_host = b.results == RESULTS_HOST;
+    if (to_host && (!out || !status)) return fail(det, AGX_ERR_ARG, "null output");  // (the batch stays in flight)
     HIP_TRY(det, hipSetDevice(det->device));
-    det->refine.kind = 0;  // resolved by this call, whatever it returns
+    det->batch = BATCH_NONE;  // resolved by this call, whatever it returns
     const size_t slots = (size_t)b.n_frames * b.points_per_frame;
-    if (b.kind == 1) {
+    if (to_host) {
         const agx_saddle *d_out = det->side[SB_REFINE_OUT].ptr<agx_saddle>();
         const uint32_t *d_status = det->side[SB_REFINE_STATUS].ptr<uint32_t>();
         if (!b.d_counts) {
@@ -1184,7 +1203,7 @@ static int refine_points_fetch_impl(agx_detector *det, agx_saddle *out, uint32_t
     }
     HIP_TRY(det, hipStreamSynchronize(det->stream));
     harvest_events(det);
-    if (b.kind == 1 && b.d_counts) {
+    if (to_host && b.d_counts) {
         const std::vector<uint32_t> &h = det->refine_host;
         for (int f = 0; f < b.n_frames; ++f) {
             const size_t n = std::min(h[slots * 6 + (size_t)f], b.points_per_frame), s0 = (size_t)f * b.points_per_frame;
@@ -1220,26 +1239,18 @@ int agx_rochade_refine(agx_detector *det, const void *pixels, int width, int hei
     if (!det) return AGX_ERR_ARG;
     if (!pixels || !n_refined || (n_points && (!points || !out || !status))) return fail(det, AGX_ERR_ARG, "null argument");
     if (image != AGX_REFINE_BLURRED && image != AGX_REFINE_PLANE) return fail(det, AGX_ERR_ARG, "image must be AGX_REFINE_BLURRED or AGX_REFINE_PLANE");
-    if (!format_px_bytes(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
     if (image == AGX_REFINE_PLANE && format != AGX_LF32) return fail(det, AGX_ERR_FORMAT, "AGX_REFINE_PLANE takes an AGX_LF32 plane");
-    if (width < 1 || height < 1) return fail(det, AGX_ERR_ARG, "width and height must be >= 1");
-    const size_t row_bytes = (size_t)width * format_px_bytes(format);
-    if (row_stride_bytes < row_bytes) return fail(det, AGX_ERR_ARG, "row stride smaller than a row");
     if (image == AGX_REFINE_PLANE && (row_stride_bytes & 3)) return fail(det, AGX_ERR_ARG, "the row stride of an f32 plane must be a multiple of 4 bytes");
+    FrameBatch b;
+    int rc = stage_host_frame(det, pixels, width, height, row_stride_bytes, format, /*min_side*/ 1, /*lf32*/ true, /*upload*/ n_points != 0, b);
+    if (rc) return rc;
     *n_refined = 0;
-    if (!n_points) return AGX_OK;  // (the reference: an empty Vec)
-    HIP_TRY(det, hipSetDevice(det->device));
-    const size_t pitch = (row_bytes + 3) & ~(size_t)3;
-    const size_t rows = format_rows(format, height);
-    const size_t need = pitch * rows;
-    void *d_stage = side_ensure(det, SB_STAGE, need, 0);
-    if (!d_stage) return fail(det, AGX_ERR_HIP, "hipMalloc: staging buffer");
+    if (!n_points) return AGX_OK;  // (the reference: an empty Vec; nothing was staged)
     agx_point *d_points = static_cast<agx_point *>(side_ensure(det, SB_REFINE_POINTS, (size_t)n_points * sizeof(agx_point), 0));
     if (!d_points) return fail(det, AGX_ERR_HIP, "hipMalloc: points");
-    HIP_TRY(det, hipMemcpy2DAsync(d_stage, pitch, pixels, row_stride_bytes, row_bytes, rows, hipMemcpyHostToDevice, det->stream));
     HIP_TRY(det, hipMemcpyAsync(d_points, points, (size_t)n_points * sizeof(agx_point), hipMemcpyHostToDevice, det->stream));
-    int rc = refine_points_enqueue_impl(det, d_stage, 1, width, height, pitch, need, format, image, d_points, n_points, nullptr, nullptr,
-                                        nullptr);
+    rc = refine_points_enqueue_impl(det, b.frames, 1, width, height, b.row_stride, b.frame_stride, format, image, d_points, n_points, nullptr,
+                                    nullptr, nullptr);
     if (rc) return rc;
     rc = refine_points_fetch_impl(det, out, status);
     if (rc) return rc;
@@ -1277,24 +1288,16 @@ int agx_decode_quads(agx_detector *det, const void *pixels, int width, int heigh
     return agx_guard(det, [&]() -> int {
     if (!det) return AGX_ERR_ARG;
     if (!pixels || !n_decoded || (n_quads && (!quads || !out || !status))) return fail(det, AGX_ERR_ARG, "null argument");
-    if (!format_px_bytes(format) || format == AGX_LF32) return fail(det, AGX_ERR_FORMAT, "format must be one of AGX_L8 .. AGX_RGBA16 but AGX_LF32 (the decode reads to_luma8)");
-    if (width < 1 || height < 1) return fail(det, AGX_ERR_ARG, "width and height must be >= 1");
-    const size_t row_bytes = (size_t)width * format_px_bytes(format);
-    if (row_stride_bytes < row_bytes) return fail(det, AGX_ERR_ARG, "row stride smaller than a row");
+    FrameBatch b;
+    int rc = stage_host_frame(det, pixels, width, height, row_stride_bytes, format, /*min_side*/ 1, /*lf32*/ false, /*upload*/ n_quads != 0, b);
+    if (rc) return rc;
     *n_decoded = 0;
-    if (!n_quads) return AGX_OK;
-    HIP_TRY(det, hipSetDevice(det->device));
-    const size_t pitch = (row_bytes + 3) & ~(size_t)3;
-    const size_t rows = format_rows(format, height);
-    const size_t need = pitch * rows;
-    void *d_stage = side_ensure(det, SB_STAGE, need, 0);
-    if (!d_stage) return fail(det, AGX_ERR_HIP, "hipMalloc: staging buffer");
+    if (!n_quads) return AGX_OK;  // (nothing was staged)
     void *d_quads = side_ensure(det, SB_DECODE_QUADS, (size_t)n_quads * 8 * sizeof(float), 0);
     if (!d_quads) return fail(det, AGX_ERR_HIP, "hipMalloc: quads");
-    HIP_TRY(det, hipMemcpy2DAsync(d_stage, pitch, pixels, row_stride_bytes, row_bytes, rows, hipMemcpyHostToDevice, det->stream));
     HIP_TRY(det, hipMemcpyAsync(d_quads, quads, (size_t)n_quads * 8 * sizeof(float), hipMemcpyHostToDevice, det->stream));
-    int rc = decode_quads_enqueue_impl(det, d_stage, 1, width, height, pitch, need, format, d_quads, 8, n_quads, nullptr, nullptr, nullptr,
-                                       nullptr, nullptr);
+    rc = decode_quads_enqueue_impl(det, b.frames, 1, width, height, b.row_stride, b.frame_stride, format, d_quads, 8, n_quads, nullptr, nullptr,
+                                   nullptr, nullptr, nullptr);
     if (rc) return rc;
     rc = decode_quads_fetch_impl(det, out, status, bits);
     if (rc) return rc;
@@ -1411,24 +1414,12 @@ static int planes_enqueue_impl(agx_detector *det, const void *d_frames, int n_fr
                                size_t out_row_stride_bytes, size_t out_frame_stride_bytes)
 {
     if (!det) return AGX_ERR_ARG;
-    if (!d_frames || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null frames or n_frames <= 0");
     if (!d_blur && !d_response) return fail(det, AGX_ERR_ARG, "d_blur and d_response are both NULL");
     if (sigma != 0.0f && !blur_sigma_ok(sigma)) return fail(det, AGX_ERR_ARG, "sigma must be 0 (no blur) or positive and finite with ceil(2 sigma) <= 16");
     if (sigma == 0.0f && d_blur) return fail(det, AGX_ERR_ARG, "sigma 0 means no blur: d_blur must be NULL");
-    if (!format_px_bytes(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
-    if (width < 1 || height < 1) return fail(det, AGX_ERR_ARG, "width and height must be >= 1");
-    if ((long long)width * height >= (1ll << 30) || width > 65000) return fail(det, AGX_ERR_ARG, "frame too large (>= 2^30 px or wider than 65000)");
-    if (n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
-    const size_t px_bytes = (size_t)format_px_bytes(format);
-    if (row_stride_bytes < (size_t)width * px_bytes || row_stride_bytes > 0x7fffffffu ||
-        (n_frames > 1 && frame_stride_bytes < row_stride_bytes * format_rows(format, height)))
-        return fail(det, AGX_ERR_ARG, "strides must cover a row / a frame");
-    if (format_16bit(format) && ((row_stride_bytes | (n_frames > 1 ? frame_stride_bytes : 0) | (uintptr_t)d_frames) & 1))
-        return fail(det, AGX_ERR_ARG, "16-bit pixels must be 2-byte aligned");
-    if (format == AGX_LF32 && ((row_stride_bytes | (n_frames > 1 ? frame_stride_bytes : 0) | (uintptr_t)d_frames) & 3))
-        return fail(det, AGX_ERR_ARG, "f32 pixels must be 4-byte aligned");
-    if (format_front(format) && height > 16 * 65535)  // (k_front_luma's grid)
-        return fail(det, AGX_ERR_ARG, "frames of this format may have at most 1048560 rows");
+    FrameBatch b{d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format};
+    if (const int rc = check_frame_batch(det, b, {/*min_side*/ 1, /*lf32*/ true, /*lone_frame_stride*/ false, /*align16*/ true, /*front_rows*/ true}))
+        return rc;
     // (at most 0x7fffffff, as the frames' row stride: k_hessian_response reads the blur plane back with an int row stride in bytes)
     if (out_row_stride_bytes < 4 * (size_t)width || (out_row_stride_bytes & 3) || out_row_stride_bytes > 0x7fffffffu)
         return fail(det, AGX_ERR_ARG, "out_row_stride_bytes must be a multiple of 4, cover width floats and be below 2^31");
@@ -1436,29 +1427,14 @@ static int planes_enqueue_impl(agx_detector *det, const void *d_frames, int n_fr
         return fail(det, AGX_ERR_ARG, "out_frame_stride_bytes must be a multiple of 4 and cover height rows");
     if (((uintptr_t)d_blur | (uintptr_t)d_response) & 3) return fail(det, AGX_ERR_ARG, "the output planes must be 4-byte aligned");
     HIP_TRY(det, hipSetDevice(det->device));
-    // this batch replaces whatever was in flight; there is nothing of it to be fetched
-    det->detect.kind = 0;
-    det->refine.kind = 0;
-    det->decode.kind = 0;
-    det->find.kind = 0;
-    det->front_format = -1;
-    det->enqueued = false;
-    if (format_front(format)) {  // as the chain: k_front_luma's integer luma plane, read as L8 / L16
-        const size_t out_px = format_16bit(format) ? 2 : 1, need = (size_t)n_frames * (size_t)width * (size_t)height * out_px;
-        void *d_front = side_ensure(det, SB_FRONT, need, 0);
-        if (!d_front) return fail(det, AGX_ERR_HIP, "hipMalloc: front-end luma plane");
-        hipError_t e = (hipError_t)launch_front_luma(d_frames, row_stride_bytes, frame_stride_bytes, n_frames, format, d_front, 0, width,
-                                                     height, det->stream);
-        if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_front_luma: ") + hipGetErrorString(e));
-        d_frames = d_front;
-        row_stride_bytes = (size_t)width * out_px;
-        frame_stride_bytes = row_stride_bytes * (size_t)height;
-        format = out_px == 2 ? AGX_L16 : AGX_L8;
-    }
+    begin_batch(det);  // and there is nothing of this one to be fetched
+    if (format_front(format))  // as the chain: k_front_luma's integer luma plane, read as L8 / L16
+        if (const int rc = front_luma_plane(det, b)) return rc;
+    format = b.format;
     HessianArgs h{};
-    h.src = static_cast<const uint8_t *>(d_frames);
-    h.src_frame_stride = (long long)frame_stride_bytes;
-    h.src_row_stride = (int)row_stride_bytes;
+    h.src = static_cast<const uint8_t *>(b.frames);
+    h.src_frame_stride = (long long)b.frame_stride;
+    h.src_row_stride = (int)b.row_stride;
     int h_format = format;
     if (sigma != 0.0f) {
         GaussBlurArgs g{};
@@ -1501,22 +1477,15 @@ static int planes_host_impl(agx_detector *det, const void *pixels, int width, in
                             bool want_response, float *out)
 {
     if (!det) return AGX_ERR_ARG;
-    if (!pixels || !out) return fail(det, AGX_ERR_ARG, "null argument");
-    if (!format_px_bytes(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
-    if (width < 1 || height < 1) return fail(det, AGX_ERR_ARG, "width and height must be >= 1");
-    const size_t row_bytes = (size_t)width * format_px_bytes(format);
-    if (row_stride_bytes < row_bytes) return fail(det, AGX_ERR_ARG, "row stride smaller than a row");
-    HIP_TRY(det, hipSetDevice(det->device));
-    const size_t pitch = (row_bytes + 3) & ~(size_t)3;
-    const size_t rows = format_rows(format, height);
-    const size_t need = pitch * rows, plane_bytes = (size_t)width * (size_t)height * sizeof(float);
-    void *d_stage = side_ensure(det, SB_STAGE, need, 0);
-    if (!d_stage) return fail(det, AGX_ERR_HIP, "hipMalloc: staging buffer");
+    if (!out) return fail(det, AGX_ERR_ARG, "null argument");
+    FrameBatch b;
+    int rc = stage_host_frame(det, pixels, width, height, row_stride_bytes, format, /*min_side*/ 1, /*lf32*/ true, /*upload*/ true, b);
+    if (rc) return rc;
+    const size_t plane_bytes = (size_t)width * (size_t)height * sizeof(float);
     float *d_plane = static_cast<float *>(side_ensure(det, SB_PLANES_OUT, plane_bytes, 0));
     if (!d_plane) return fail(det, AGX_ERR_HIP, "hipMalloc: plane");
-    HIP_TRY(det, hipMemcpy2DAsync(d_stage, pitch, pixels, row_stride_bytes, row_bytes, rows, hipMemcpyHostToDevice, det->stream));
-    const int rc = planes_enqueue_impl(det, d_stage, 1, width, height, pitch, need, format, sigma, want_response ? nullptr : d_plane,
-                                       want_response ? d_plane : nullptr, (size_t)width * sizeof(float), plane_bytes);
+    rc = planes_enqueue_impl(det, b.frames, 1, width, height, b.row_stride, b.frame_stride, format, sigma, want_response ? nullptr : d_plane,
+                             want_response ? d_plane : nullptr, (size_t)width * sizeof(float), plane_bytes);
     if (rc) return rc;
     HIP_TRY(det, hipMemcpyAsync(out, d_plane, plane_bytes, hipMemcpyDeviceToHost, det->stream));
     HIP_TRY(det, hipStreamSynchronize(det->stream));
@@ -1570,7 +1539,7 @@ int agx::group_detect_enqueue(agx_detector *det, const void *d_frames, int n_fra
 {
     return agx_guard(det, [&]() -> int {
     return detect_enqueue_checked(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, cap_per_frame,
-                                  3, d_slab, d_table, nullptr, slab_records);
+                                  RESULTS_GROUP, d_slab, d_table, nullptr, slab_records);
     });
 }
 
@@ -1588,7 +1557,7 @@ int agx::group_detect_fetch(agx_detector *det, const char *back, agx_tag *out, u
 
 int agx::fetch_compact(agx_detector *det, const agx_saddle **records, uint32_t *counts, uint32_t *offsets, int *status)
 {
-    const int n = det->enqueued ? det->args.n_frames : 0;
+    const int n = chain_in_flight(det) ? det->args.n_frames : 0;
     // cap 0: counts and status only (a frame with any saddles reads "capacity" against cap 0: the real status is
     // derived from the counters below, with no limit on the list's length)
     int rc = saddles_fetch_impl(det, nullptr, 0, counts, status);
@@ -1608,7 +1577,7 @@ void agx::abandon_batch(agx_detector *det)
 {
     (void)hipStreamSynchronize(det->stream);
     harvest_events(det);
-    det->enqueued = false;
+    det->batch = BATCH_NONE;
 }
 
 namespace {
@@ -1629,19 +1598,13 @@ int refetch_single(agx_detector *det, agx_saddle *out, uint32_t cap, uint32_t *n
 int refined_saddle_points_impl(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes,
                                int format, agx_saddle *out, uint32_t cap, uint32_t *n_out, bool want_luma8)
 {
-    if (!det || !pixels || !n_out) return fail(det, AGX_ERR_ARG, "null argument");
-    if (!format_px_bytes(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
-    if (width < 2 || height < 2) return fail(det, AGX_ERR_ARG, "width and height must be >= 2");
-    const size_t row_bytes = (size_t)width * format_px_bytes(format);
-    if (row_stride_bytes < row_bytes) return fail(det, AGX_ERR_ARG, "row stride smaller than a row");
-    HIP_TRY(det, hipSetDevice(det->device));
-    const size_t pitch = (row_bytes + 3) & ~(size_t)3;
-    const size_t rows = format_rows(format, height);  // (the planar layout: three planes, one under the other)
-    const size_t need = pitch * rows;
-    void *d_stage = side_ensure(det, SB_STAGE, need, 0);
-    if (!d_stage) return fail(det, AGX_ERR_HIP, "hipMalloc: staging buffer");
-    HIP_TRY(det, hipMemcpy2DAsync(d_stage, pitch, pixels, row_stride_bytes, row_bytes, rows, hipMemcpyHostToDevice, det->stream));
-    int rc = agx_saddles_batch_enqueue(det, d_stage, 1, width, height, pitch, need, format);
+    if (!det || !n_out) return fail(det, AGX_ERR_ARG, "null argument");
+    FrameBatch b;
+    int rc = stage_host_frame(det, pixels, width, height, row_stride_bytes, format, /*min_side*/ 2, /*lf32*/ true, /*upload*/ true, b);
+    if (rc) return rc;
+    const void *d_stage = b.frames;
+    const size_t pitch = b.row_stride, need = b.frame_stride;
+    rc = agx_saddles_batch_enqueue(det, d_stage, 1, width, height, pitch, need, format);
     if (rc) return rc;
     if (want_luma8) {  // stream-ordered behind the chain; the fetch below waits for the stream
         const size_t lb = (size_t)width * (size_t)height;
@@ -1774,7 +1737,7 @@ int agx_detect(agx_detector *det, const void *pixels, int width, int height, siz
 {
     return agx_guard(det, [&]() -> int {
     if (!det || !pixels || !n_out) return fail(det, AGX_ERR_ARG, "null argument");
-    if (!format_px_bytes(format)) return fail(det, AGX_ERR_FORMAT, kFormatMsg);
+    if (!format_px_bytes(format)) return fail(det, AGX_ERR_FORMAT, "format must be one of AGX_L8 .. AGX_RGBA16 (agx_format)");
     if (width < 2 || height < 2) return fail(det, AGX_ERR_ARG, "width and height must be >= 2");
     if (format == AGX_LF32) return fail(det, AGX_ERR_FORMAT, "an f32 luma plane carries no u8 luma for the decode: use agx_detect_planes");
     // detector.rs:507-508: u8 luma for the decode, saddle chain on the device.  L8 is its own luma; for
@@ -1930,7 +1893,7 @@ int agx_debug_fetch(agx_detector *det, int frame, int what, void *host_out, size
         std::memcpy(host_out, v, sizeof v);
         return AGX_OK;
     }
-    if (!det->enqueued) return fail(det, AGX_ERR_STATE, "no batch enqueued");
+    if (!chain_in_flight(det)) return fail(det, AGX_ERR_STATE, "no batch enqueued");
     const ChainArgs &a = det->args;
     if (frame < 0 || frame >= a.n_frames) return fail(det, AGX_ERR_ARG, "frame out of range");
     HIP_TRY(det, hipSetDevice(det->device));

@@ -11,6 +11,13 @@
 #include "host_tail.hpp"
 
 #define AGX_UPLOAD_STREAMS 3
+// a HIP call that must succeed: else AGX_ERR_HIP with the call and HIP's reason in agx_last_error
+#define HIP_TRY(det, expr)                                                                          \
+    do {                                                                                            \
+        hipError_t e_ = (expr);                                                                     \
+        if (e_ != hipSuccess)                                                                       \
+            return agx::fail((det), AGX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
 
 namespace agx {
 // agx_format: bytes between horizontally adjacent pixels (0: not a format), the rows a frame of `height` spans (the planar
@@ -37,53 +44,76 @@ void destroy_worker_pool(WorkerPool *pool);
 TailWorkers *create_tail_workers(int n_threads);  // nullptr for n_threads <= 1
 void destroy_tail_workers(TailWorkers *w);
 
-// agx_detect_batch_enqueue / _enqueue_to: what agx_detect_batch_fetch needs of the batch in flight.  Any enqueue of the chain
-// (either pair, agx_detect_batch, agx_detect) resets it: one batch in flight per handle, the last one enqueued.
+// The batch in flight on a handle: one at a time, the last one enqueued.  agx_detector::batch says whose it is and so which fetch
+// resolves it; the payload of that kind (below) is valid while it does.  begin_batch() is the only place that forgets a batch;
+// every enqueue calls it behind its argument checks, so a refused enqueue leaves the batch in flight where it was.  Forgetting
+// a batch does not wait for it or undo it: a refine batch whose results go to the caller's device arrays may be followed by a
+// decode batch that reads those arrays without a fetch in between -- same stream, in order.  ("The batch in flight")
+enum BatchKind {
+    BATCH_NONE,     // nothing to fetch (also behind agx_planes_enqueue, which has no fetch)
+    BATCH_SADDLES,  // the chain's results: stays fetchable after a fetch (refetch_single, agx_detect's retry, agx_debug_fetch)
+    BATCH_DETECT,   // the chain's results + DetectPending; agx::fetch_compact reads the chain's part while the fetch resolves it
+    BATCH_REFINE,   // RefinePending; nothing of the chain is there to be fetched, even where K1 ran for the blur planes
+    BATCH_DECODE,   // DecodePending
+    BATCH_FIND,     // FindPending
+    BATCH_KINDS
+};
+// where a kind's results are: the fetch copies them out of the handle's side buffers / they are in the caller's device arrays
+// already / (BATCH_DETECT only) they are a group's, and only agx_group_detect_fetch resolves the batch
+enum { RESULTS_HOST = 1, RESULTS_CALLER = 2, RESULTS_GROUP = 3 };
+
 struct DetectPending {
-    int kind = 0;              // 0 none, 1 results to host arrays (agx_detect_batch_enqueue), 2 to the caller's device arrays,
-                               // 3 owned by a group (agx_group_detect_enqueue): only agx_group_detect_fetch resolves it
+    int results = 0;           // RESULTS_*
     bool device_tail = false;  // the device tail runs behind the chain; else the fetch runs the host tail on every frame
     int n_frames = 0, width = 0, height = 0;
     uint32_t cap = 0;
     const uint8_t *d_luma = nullptr;  // the batch's u8 luma on the device: the L8 frames themselves or the k_luma8 planes
     size_t luma_row = 0, luma_frame = 0;
-    agx_tag *d_tags = nullptr;  // kind 2: [n_frames][cap]; kind 3: the group's tag slab of this rank
-    uint32_t *d_counts = nullptr;  // kind 3: the group's packed frame table [n_frames][4]
+    agx_tag *d_tags = nullptr;  // RESULTS_CALLER: [n_frames][cap]; RESULTS_GROUP: the group's tag slab of this rank
+    uint32_t *d_counts = nullptr;  // RESULTS_GROUP: the group's packed frame table [n_frames][4]
     int *d_status = nullptr;
 };
 
-// agx_refine_points_enqueue: what agx_refine_points_fetch needs of the batch in flight.  The third kind of batch on a handle:
-// while it is in flight `enqueued` is false (nothing of the chain is there to be fetched), and every enqueue of the chain
-// resets it.
 struct RefinePending {
-    int kind = 0;  // 0 none, 1 results in SB_REFINE_OUT / SB_REFINE_STATUS (the fetch copies them out), 2 in the caller's device arrays
+    int results = 0;  // RESULTS_HOST: in SB_REFINE_OUT / SB_REFINE_STATUS, or RESULTS_CALLER
     int n_frames = 0;
     uint32_t points_per_frame = 0;
-    const uint32_t *d_counts = nullptr;  // the caller's per-frame counts (kind 1: the fetch copies only the slots that were written)
+    const uint32_t *d_counts = nullptr;  // the caller's per-frame counts (RESULTS_HOST: the fetch copies only the slots that were written)
 };
 
-// agx_decode_quads_enqueue: what agx_decode_quads_fetch needs of the batch in flight.  The fourth kind of batch on a handle, with
-// RefinePending's rules: `enqueued` is false while it is in flight, and every enqueue of any kind resets it.  Resetting
-// RefinePending (or this) forgets a batch, it does not wait for it or undo it: a refine batch whose results go to the caller's
-// device arrays may be followed by a decode batch that reads those arrays without a fetch in between -- same stream, in order.
 struct DecodePending {
-    int kind = 0;  // 0 none, 1 results in SB_DECODE_TAGS / _STATUS / _BITS (the fetch copies them out), 2 in the caller's device arrays
+    int results = 0;  // RESULTS_HOST: in SB_DECODE_TAGS / _STATUS / _BITS, or RESULTS_CALLER
     int n_frames = 0;
     uint32_t quads_per_frame = 0;
-    const uint32_t *d_counts = nullptr;  // the caller's per-frame counts (kind 1: the fetch copies only the slots that were written)
+    const uint32_t *d_counts = nullptr;  // the caller's per-frame counts (RESULTS_HOST: the fetch copies only the slots that were written)
 };
 
-// agx_find_boards_enqueue: what agx_find_boards_fetch needs of the batch in flight.  The fifth kind of batch on a handle, with
-// DecodePending's rules.  The fetch reads the inputs again for the frames the kernel handed back (AGX_BOARD_PENDING).
+// The fetch reads the inputs again for the frames the kernel handed back (AGX_BOARD_PENDING).
 struct FindPending {
-    int kind = 0;  // 0 none, 1 results in SB_FIND_QUADS / _COUNTS / _STATUS (the fetch copies them out), 2 in the caller's device arrays
+    int results = 0;  // RESULTS_HOST: in SB_FIND_QUADS / _COUNTS / _STATUS, or RESULTS_CALLER
     int n_frames = 0;
     uint32_t saddles_per_frame = 0, quads_per_frame = 0;
     size_t stride = 0;
     const uint8_t *d_saddles = nullptr;
     const uint32_t *d_counts = nullptr, *d_frame_table = nullptr, *d_point_status = nullptr;
     uint32_t *d_quads = nullptr, *d_n_quads = nullptr, *d_status = nullptr;
-    float *d_quad_points = nullptr;  // the caller's, SB_FIND_POINTS (kind 1 without the caller's), or null
+    float *d_quad_points = nullptr;  // the caller's, SB_FIND_POINTS (RESULTS_HOST without the caller's), or null
+};
+
+// A batch of equally sized frames in device memory as an entry point was handed it, and what differs between the entry points'
+// checks of one (check_frame_batch)
+struct FrameBatch {
+    const void *frames = nullptr;
+    int n_frames = 0, width = 0, height = 0;
+    size_t row_stride = 0, frame_stride = 0;  // bytes
+    int format = -1;
+};
+struct BatchRules {
+    int min_side;            // smallest width / height: 2 where the chain runs, 1 elsewhere
+    bool lf32;               // AGX_LF32 is accepted (refused where the entry point needs to_luma8)
+    bool lone_frame_stride;  // the frame stride of a single frame takes part in the alignment tests (else only from 2 frames on)
+    bool align16;            // the 16-bit layouts' 2-byte alignment is checked (agx_refine_points_enqueue leaves it to the chain)
+    bool front_rows;         // the front-end layouts' row limit is checked (agx_refine_points_enqueue leaves it to the chain)
 };
 
 struct EventPair {
@@ -176,8 +206,8 @@ struct agx_detector {
     agx::SideBuf side[agx::SB_COUNT];
     // SB_FRONT holds the plane the chain reads instead of the frames; front_src / front_format / front_frames name the batch it
     // holds, so that to_luma8 is derived from it instead of from the frames again (an 8-bit layout: it IS that plane).  They are
-    // valid only from batch_enqueue_impl to the next enqueue on the handle, which resets them first (format -1: none): whoever
-    // asks for the luma of a batch does so right behind that batch's enqueue, on the same stream
+    // valid only from batch_enqueue_impl to the next enqueue on the handle, whose begin_batch resets them first (format -1: none):
+    // whoever asks for the luma of a batch does so right behind that batch's enqueue, on the same stream
     const void *front_src = nullptr;
     int front_format = -1, front_frames = 0;
     // pinned host mirrors
@@ -200,7 +230,7 @@ struct agx_detector {
     size_t ctr_cleared[2] = {0, 0};  // records of the set known to be zero (0 = in use / unknown)
     int ctr_cur = 0;
 
-    bool enqueued = false;
+    int batch = agx::BATCH_NONE;  // agx::BatchKind: the batch in flight
     int profiling = 0;  // 0 off, 1 = K1 only, 2 = every kernel
     int prof_stride = 1;        // level 1: time the selected kernel of every prof_stride-th batch only
     int prof_kernel = agx::K_BLUR_HESSIAN;  // level 1: which kernel (option "profile_kernel", default the blur kernel)
@@ -227,12 +257,12 @@ struct agx_detector {
     size_t tail_frames = 0, dtail_frames = 0;      // layout of SB_TAGS + SB_TAIL_TABLE and of SB_DTAGS + SB_DTABLE: rows ...
     uint32_t tail_tag_cap = 0, dtail_tag_cap = 0;  // ... and tags per row (0: the pair does not exist)
     int last_tail_frames = 0, last_tail_fallbacks = 0, last_tail_uncertain = 0;  // of the last agx_detect_batch call
-    agx::DetectPending detect;          // agx_detect_batch_enqueue / _to: the batch agx_detect_batch_fetch resolves
-    agx::RefinePending refine;          // agx_refine_points_enqueue: the batch agx_refine_points_fetch resolves
+    agx::DetectPending detect;          // BATCH_DETECT: what agx_detect_batch_fetch needs of it
+    agx::RefinePending refine;          // BATCH_REFINE: what agx_refine_points_fetch needs of it
     std::vector<uint32_t> refine_host;  // its host staging when per-frame counts were given (records, statuses, counts)
-    agx::DecodePending decode;          // agx_decode_quads_enqueue: the batch agx_decode_quads_fetch resolves
+    agx::DecodePending decode;          // BATCH_DECODE: what agx_decode_quads_fetch needs of it
     std::vector<uint64_t> decode_host;  // its host staging when per-frame counts were given (bits, tags, statuses, counts)
-    agx::FindPending find;              // agx_find_boards_enqueue: the batch agx_find_boards_fetch resolves
+    agx::FindPending find;              // BATCH_FIND: what agx_find_boards_fetch needs of it
     int last_find_frames = 0, last_find_handed_back = 0;  // of the last agx_find_boards_fetch
 
     std::string last_error;
@@ -240,13 +270,25 @@ struct agx_detector {
 
 namespace agx {
 int fail(agx_detector *d, int status, const std::string &msg);  // sets agx_last_error, returns status
+// This batch replaces whatever was in flight: nothing is fetchable and SB_FRONT names no batch until the enqueue says otherwise
+inline void begin_batch(agx_detector *det)
+{
+    det->batch = BATCH_NONE;
+    det->front_format = -1;
+}
+// the chain's results of the batch in flight are there to be read (agx_saddles_batch_fetch's rule, agx_debug_fetch, the tails)
+inline bool chain_in_flight(const agx_detector *det) { return det->batch == BATCH_SADDLES || det->batch == BATCH_DETECT; }
+// A fetch of `wanted`'s pair: AGX_OK where that is the batch in flight, else AGX_ERR_STATE with the pair that is (or none)
+int refuse_other_batch(agx_detector *det, int wanted);
+// AGX_OK, or the status and message of the first rule b breaks: null frames / frame count, format, then size and strides
+int check_frame_batch(agx_detector *det, const FrameBatch &b, const BatchRules &rules);
 // The payload of slot `which`, at least `bytes` long, or nullptr (the slot is then empty).  kind: 0 device, 1 pinned host,
 // 2 pinned host mapped into the device (dev() = its device address).  A slot that is large enough is returned as it is;
 // otherwise the handle's stream is waited for first -- work in flight may still read the buffer about to be freed -- and the
 // slot is freed and allocated again: whatever pointed into it is void.
 // DetectPending::d_luma and args.frames point into SB_LUMA_D / SB_FRONT from an agx_detect_batch_enqueue to its fetch.  Those
-// two slots are grown only behind an enqueue of the chain (batch_enqueue_impl; chunk_luma8 and agx_detect, which follow their
-// own enqueue), and every such enqueue resets `detect` and front_format first; the fetch itself grows SB_FETCH_LUMA only.
+// two slots are grown only behind an enqueue's begin_batch (batch_enqueue_impl; chunk_luma8 and agx_detect, which follow their
+// own enqueue), when no batch points into them any more; the fetch itself grows SB_FETCH_LUMA only.
 void *side_ensure(agx_detector *d, int which, size_t bytes, int kind);
 // Two slots that are only of use together (SB_LUMA_D + SB_LUMA_H, SB_TAGS + SB_TAIL_TABLE, SB_DTAGS + SB_DTABLE): both as
 // asked for, or both empty
@@ -262,9 +304,9 @@ void abandon_batch(agx_detector *det);
 // on 2^20 operand pairs: the device tail is offered only where there are none
 uint64_t libm_check_once();
 // detect over a batch in device memory, stream-ordered (detect_batch.cpp)
-// kind: DetectPending::kind (1, 2 or 3; 3: d_counts = the packed frame table, d_tags = the slab of slab_records records)
+// results: RESULTS_* (RESULTS_GROUP: d_counts = the packed frame table, d_tags = the slab of slab_records records)
 int detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
-                        size_t frame_stride_bytes, int format, uint32_t cap_per_frame, int kind, agx_tag *d_tags,
+                        size_t frame_stride_bytes, int format, uint32_t cap_per_frame, int results, agx_tag *d_tags,
                         uint32_t *d_counts, int *d_status, uint32_t slab_records);
 int detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads);
 // try_decode_quad of caller-given quads over a batch in device memory (detect_batch.cpp: to_luma8, k_decode_quads, the fetch)

@@ -336,10 +336,7 @@ int enqueue_gather(agx_group *g, const Payload *pl, int n_pl)
 void drop_detect_batch(agx_group *g)
 {
     for (agx_detector *d : g->dets)
-        if (d->detect.kind == 3) {
-            d->detect.kind = 0;
-            agx::abandon_batch(d);
-        }
+        if (d->batch == agx::BATCH_DETECT && d->detect.results == agx::RESULTS_GROUP) agx::abandon_batch(d);
     g->pending = 0;
 }
 

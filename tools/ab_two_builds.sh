@@ -5,7 +5,8 @@
 #   cp aprilgrid-rs_amd/libaprilgrid_amd.so scratch/lib_old.so      # build A (scratch/ travels to the GPU box, git ignores it)
 #   ... change, make ...; cp aprilgrid-rs_amd/libaprilgrid_amd.so scratch/lib_new.so
 #   gpurun -- 'tools/ab_two_builds.sh scratch/lib_old.so scratch/lib_new.so'
-# default command: the device tail on the bench's 256 frames, per-frame ticks and the call's time
+# default command: the device tail on the bench's 256 frames, per-frame ticks and the call's time; AB_GREP selects the lines
+# of another command's output that are kept (AB_GREP='"ms_per_step"' for bench.py's result line)
 A=${1:-scratch/lib_old.so}; B=${2:-scratch/lib_new.so}
 shift 2 2>/dev/null
 CMD=${*:-env AGX_TAIL_DEBUG=1 python tools/device_tail_check.py 256 0 L8}
@@ -14,7 +15,7 @@ cp aprilgrid-rs_amd/libaprilgrid_amd.so /tmp/lib_keep.so
 for r in 1 2 3; do
   for v in "$A" "$B"; do
     cp "$v" aprilgrid-rs_amd/libaprilgrid_amd.so
-    echo "== $v"; $CMD 2>&1 | grep -E "ticks per frame|device tail:" | tail -2 | cut -c1-140
+    echo "== $v"; $CMD 2>&1 | grep -E "${AB_GREP:-ticks per frame|device tail:}" | tail -${AB_LINES:-2} | cut -c1-${AB_COLS:-140}
   done
 done
 cp /tmp/lib_keep.so aprilgrid-rs_amd/libaprilgrid_amd.so
