@@ -87,8 +87,12 @@ SYMBOLS = {
     "agx_refine_points_enqueue": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _P, C.c_uint32,
                                             _P, _P, _P]),
     "agx_refine_points_fetch": (C.c_int, [_P, _P, _P]),
+    "agx_refine_points_enqueue_h": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _P, C.c_uint32,
+                                              _P, _P, _P, C.c_int]),
     "agx_rochade_refine": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, _P, C.c_uint32, _P, _P,
                                      C.POINTER(C.c_uint32)]),
+    "agx_rochade_refine_h": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, _P, C.c_uint32, _P, _P,
+                                       C.POINTER(C.c_uint32), C.c_int]),
     "agx_decode_quads_enqueue": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, _P, C.c_size_t, C.c_uint32,
                                            _P, _P, _P, _P, _P]),
     "agx_decode_quads_fetch": (C.c_int, [_P, _P, _P, _P]),
@@ -130,6 +134,7 @@ SYMBOLS = {
     "agx_debug_fetch": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "agx_detector_constants": (C.c_int, [_P, _P, _P, _P]),
     "agx_debug_blur_weights": (C.c_int, [C.c_float, _P, C.c_int, C.POINTER(C.c_int)]),
+    "agx_debug_refine_constants": (C.c_int, [C.c_int, _P, _P, C.c_int, C.POINTER(C.c_int)]),
 }
 
 

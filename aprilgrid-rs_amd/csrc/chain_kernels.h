@@ -162,6 +162,19 @@ struct RefinePointsArgs {
 // grid (ceil(points_per_frame / 64), n_frames <= 65535), one point per lane; hipError_t
 int launch_refine_points(const RefinePointsArgs &p, const RefineConsts &rc, int n_frames, void *stream);
 
+// k_refine_patch<HALF> (agx_refine_points_enqueue_h): the same rochade_refine at half_size_patch = HALF in 1 .. 4, sixteen lanes
+// to a point.  The constants of one half size, as they lie in the handle's device table: record `half - 1` of
+// REFINE_PATCH_MAX_HALF such records.
+constexpr int REFINE_PATCH_MAX_HALF = 4;
+constexpr int REFINE_PATCH_MAX_TAPS = (2 * REFINE_PATCH_MAX_HALF + 1) * (2 * REFINE_PATCH_MAX_HALF + 1);  // 81
+struct RefinePatchConsts {
+    float cone[REFINE_PATCH_MAX_TAPS];      // normalised ks x ks cone kernel, the first ks*ks entries (detector.rs:240-254)
+    float pmat[REFINE_PATCH_MAX_TAPS * 6];  // ks*ks x 6 pseudo-inverse, [i*6+j] (detector.rs:208-237)
+};
+// grid (ceil(points_per_frame / 4), n_frames <= 65535); `consts` is the device record of `half`; a plane is never read outside
+// a point's own (4*half+1)^2 window, whatever p.padded says.  hipError_t
+int launch_refine_patch(const RefinePointsArgs &p, const RefinePatchConsts *consts, int half, int n_frames, void *stream);
+
 size_t k5_lds_bytes(const ChainArgs &a);
 
 constexpr size_t WAVE_TIMES_STRIDE = (size_t)1 << 20;  // records per kernel (debug_ablation & 4096)

@@ -31,6 +31,8 @@
 //                       the large-list sort (> 1024 refined records per frame)
 //   k_refine_points     rochade_refine (detector.rs:194-361) of caller-given points, one point per lane, on the
 //                       chain's blur planes or a caller's f32 plane (agx_refine_points_enqueue); not part of the chain
+//   k_refine_patch<HALF> the same at half_size_patch 1 .. 4, sixteen lanes per point, window and conv outputs in LDS
+//                       (agx_refine_points_enqueue_h); not part of the chain
 #include <hip/hip_runtime.h>
 
 #include <map>
@@ -3331,6 +3333,48 @@ int launch_clear_counters(FrameCounters *ctr, size_t n_records, void *stream)
 // ------------------------------------------------------------------------------------------
 enum : uint32_t { POINT_REFINED = 0u, POINT_OUTSIDE = 1u, POINT_NOT_SADDLE = 2u, POINT_MOVED = 3u };  // AGX_POINT_*
 
+// The end of rochade_refine, from the six parameter sums on (:330-357): the saddle test, find_xy, the move threshold, k, phi
+// and theta.  One copy for k_refine_points and k_refine_patch, so that the two give the same bytes from the same sums.
+__device__ __forceinline__ uint32_t refine_tail(const float (&prm)[6], float rxf, float ryf, float (&rec)[5])
+{
+    const float a1 = prm[0], a2 = prm[1], a3 = prm[2], a4 = prm[3], a5 = prm[4];
+    const float fxx = 2.0f * a1, fyy = 2.0f * a3, fxy = a2;
+    const float d = fxx * fyy - fxy * fxy;
+    if (!(d < 0.0f)) return POINT_NOT_SADDLE;  // :331-339
+    // find_xy(2a1, a2, a4, a2, 2a3, a5), math_util.rs:5-12: 2x2 LU with row pivoting
+    float x0, y0;
+    {
+        const float A0 = 2.0f * a1, B0 = a2, R0 = -a4;
+        const float A1 = a2, B1 = 2.0f * a3, R1 = -a5;
+        float pa, pb, pr_, qa, qb, qr;
+        if (fabsf(A1) > fabsf(A0)) {
+            pa = A1; pb = B1; pr_ = R1; qa = A0; qb = B0; qr = R0;
+        } else {
+            pa = A0; pb = B0; pr_ = R0; qa = A1; qb = B1; qr = R1;
+        }
+        const float l = qa / pa;
+        const float u22 = qb - l * pb;
+        const float y2 = qr - l * pr_;
+        y0 = y2 / u22;
+        x0 = (pr_ - pb * y0) / pa;
+    }
+    if (!(fabsf(x0) <= 1.0f && fabsf(y0) <= 1.0f)) return POINT_MOVED;  // :342-347
+    const float c5 = (a1 + a3) / 2.0f;
+    const float c4 = (a1 - a3) / 2.0f;
+    const float c3 = a2 / 2.0f;
+    const float k = sqrtf(c4 * c4 + c3 * c3);
+    if (!(fabsf(c5) < k)) return POINT_MOVED;
+    const float PI_F = 3.14159274101257324219f;
+    const float phi = acosf(-c5 / k) / 2.0f / PI_F * 180.0f;
+    const float theta = atan2f(c3, c4) / 2.0f / PI_F * 180.0f;
+    rec[0] = rxf + x0;
+    rec[1] = ryf + y0;
+    rec[2] = k;
+    rec[3] = theta;
+    rec[4] = phi;
+    return POINT_REFINED;
+}
+
 template <bool VEC>
 __device__ __forceinline__ uint32_t refine_point(const RefineConsts &rc, const float *img, size_t pitch, int W, int H, float initial_x,
                                                  float initial_y, float (&rec)[5])
@@ -3397,42 +3441,7 @@ __device__ __forceinline__ uint32_t refine_point(const RefineConsts &rc, const f
                 for (int j = 0; j < 6; ++j) prm[j] = prm[j] + rc.pmat[(r * 5 + c) * 6 + j] * conv[r * 5 + c];
         }
     }
-    const float a1 = prm[0], a2 = prm[1], a3 = prm[2], a4 = prm[3], a5 = prm[4];
-    const float fxx = 2.0f * a1, fyy = 2.0f * a3, fxy = a2;
-    const float d = fxx * fyy - fxy * fxy;
-    if (!(d < 0.0f)) return POINT_NOT_SADDLE;  // :331-339
-    // find_xy(2a1, a2, a4, a2, 2a3, a5), math_util.rs:5-12: 2x2 LU with row pivoting
-    float x0, y0;
-    {
-        const float A0 = 2.0f * a1, B0 = a2, R0 = -a4;
-        const float A1 = a2, B1 = 2.0f * a3, R1 = -a5;
-        float pa, pb, pr_, qa, qb, qr;
-        if (fabsf(A1) > fabsf(A0)) {
-            pa = A1; pb = B1; pr_ = R1; qa = A0; qb = B0; qr = R0;
-        } else {
-            pa = A0; pb = B0; pr_ = R0; qa = A1; qb = B1; qr = R1;
-        }
-        const float l = qa / pa;
-        const float u22 = qb - l * pb;
-        const float y2 = qr - l * pr_;
-        y0 = y2 / u22;
-        x0 = (pr_ - pb * y0) / pa;
-    }
-    if (!(fabsf(x0) <= 1.0f && fabsf(y0) <= 1.0f)) return POINT_MOVED;  // :342-347
-    const float c5 = (a1 + a3) / 2.0f;
-    const float c4 = (a1 - a3) / 2.0f;
-    const float c3 = a2 / 2.0f;
-    const float k = sqrtf(c4 * c4 + c3 * c3);
-    if (!(fabsf(c5) < k)) return POINT_MOVED;
-    const float PI_F = 3.14159274101257324219f;
-    const float phi = acosf(-c5 / k) / 2.0f / PI_F * 180.0f;
-    const float theta = atan2f(c3, c4) / 2.0f / PI_F * 180.0f;
-    rec[0] = rxf + x0;
-    rec[1] = ryf + y0;
-    rec[2] = k;
-    rec[3] = theta;
-    rec[4] = phi;
-    return POINT_REFINED;
+    return refine_tail(prm, rxf, ryf, rec);
 }
 
 // grid (ceil(points_per_frame / 64), n_frames): point i of frame f reads points[f * ppf + i] and writes record and status
@@ -3462,6 +3471,98 @@ int launch_refine_points(const RefinePointsArgs &p, const RefineConsts &rc, int 
     const bool vec = p.padded && (p.pitch & 3) == 0 && (p.frame_stride & 3) == 0 && ((uintptr_t)p.img & 15) == 0;
     if (vec) hipLaunchKernelGGL((k_refine_points<true>), grid, block, 0, (hipStream_t)stream, p, rc);
     else hipLaunchKernelGGL((k_refine_points<false>), grid, block, 0, (hipStream_t)stream, p, rc);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// k_refine_patch<HALF>: rochade_refine (detector.rs:194-361) of caller-given points at half_size_patch = HALF in 1 .. 4
+// -- agx_refine_points_enqueue_h.  k_refine_points keeps its KS*KS running sums in one lane's registers; at HALF = 4 that
+// would be 81 sums of 81 taps over a 17 x 17 window, so here SIXTEEN LANES SERVE ONE POINT, four points to a one-wave
+// workgroup:
+//   1. the (4*HALF+1)^2 window goes to LDS, the 16 lanes taking consecutive floats of its rows (no float outside the
+//      window is read: a caller's plane may end with it);
+//   2. lane l owns the conv outputs l, l+16, ..: each ONE running sum from 0.0f over pr, then pc, ascending -- the
+//      reference's order (:300-317; the unrolled branch :280-298 has the same) -- and writes smooth[] to LDS;
+//   3. lanes 0 .. 5 each form one parameter sum over i ascending (:321-328);
+//   4. lane 0 runs refine_tail and writes the slot.
+// No float crosses lanes except through a finished sum: there is no reduction and no tree.  The cone weight of a tap is
+// the same for all lanes (a scalar load from the handle's table); the pseudo-inverse is read [i*6 + lane].
+// LDS: a window row has WIN = 4*HALF+1 floats, odd, so the rows of a point's 16 outputs fall on different banks; the
+// windows and smooth[] arrays of the two points that share a 32-lane half start 16 banks apart.
+// ------------------------------------------------------------------------------------------
+constexpr int REFINE_PATCH_LANES = 16, REFINE_PATCH_POINTS = 64 / REFINE_PATCH_LANES;
+
+template <int HALF>
+__global__ void __launch_bounds__(64) k_refine_patch(RefinePointsArgs p, const RefinePatchConsts *__restrict__ rc)
+{
+    constexpr int KS = 2 * HALF + 1, N = KS * KS, WIN = 4 * HALF + 1, NWIN = WIN * WIN;
+    constexpr int WIN_STRIDE = (NWIN + 31) / 32 * 32 + 16, SMOOTH_STRIDE = (N + 31) / 32 * 32 + 16;
+    __shared__ float s_win[REFINE_PATCH_POINTS][WIN_STRIDE];
+    __shared__ float s_smooth[REFINE_PATCH_POINTS][SMOOTH_STRIDE];
+    __shared__ float s_prm[REFINE_PATCH_POINTS][8];
+    const uint32_t g = threadIdx.x / REFINE_PATCH_LANES, l = threadIdx.x % REFINE_PATCH_LANES;
+    const uint32_t f = blockIdx.y, i = blockIdx.x * REFINE_PATCH_POINTS + g;
+    uint32_t n = p.points_per_frame;
+    if (p.counts) n = min(p.counts[f], n);
+    const bool live = i < n;  // (no lane leaves before the last barrier)
+    const size_t slot = (size_t)f * p.points_per_frame + (live ? i : 0u);
+    float rxf = 0.0f, ryf = 0.0f;
+    bool inside = false;
+    if (live) {
+        rxf = roundf(p.points[2 * slot]);
+        ryf = roundf(p.points[2 * slot + 1]);
+        // :266-274, decided in float: NaN fails every comparison, and what passes converts to int exactly
+        inside = rxf >= (float)(2 * HALF) && ryf >= (float)(2 * HALF) && rxf <= 1073741824.0f && ryf <= 1073741824.0f;
+        if (inside) inside = (int)ryf + 2 * HALF < p.H && (int)rxf + 2 * HALF < p.W;
+    }
+    if (inside) {
+        const float *win = p.img + (size_t)f * (size_t)p.frame_stride + (size_t)((int)ryf - 2 * HALF) * (size_t)p.pitch + ((int)rxf - 2 * HALF);
+        for (int e = (int)l; e < NWIN; e += REFINE_PATCH_LANES) s_win[g][e] = win[(size_t)(e / WIN) * (size_t)p.pitch + (e % WIN)];
+    }
+    __syncthreads();
+    if (inside) {
+        for (int o = (int)l; o < N; o += REFINE_PATCH_LANES) {
+            const float *w = &s_win[g][(o / KS) * WIN + (o % KS)];
+            float sum = 0.0f;
+#pragma unroll
+            for (int pr = 0; pr < KS; ++pr)
+#pragma unroll
+                for (int pc = 0; pc < KS; ++pc) sum = sum + w[pr * WIN + pc] * rc->cone[pr * KS + pc];
+            s_smooth[g][o] = sum;
+        }
+    }
+    __syncthreads();
+    if (inside && l < 6) {
+        float sum = 0.0f;
+#pragma unroll 9
+        for (int q = 0; q < N; ++q) sum = sum + rc->pmat[q * 6 + (int)l] * s_smooth[g][q];
+        s_prm[g][l] = sum;
+    }
+    __syncthreads();
+    if (!live || l != 0) return;
+    float rec[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    uint32_t st = POINT_OUTSIDE;
+    if (inside) {
+        const float prm[6] = {s_prm[g][0], s_prm[g][1], s_prm[g][2], s_prm[g][3], s_prm[g][4], s_prm[g][5]};
+        st = refine_tail(prm, rxf, ryf, rec);
+    }
+#pragma unroll
+    for (int q = 0; q < 5; ++q) p.out[slot * 5 + q] = st == POINT_REFINED ? rec[q] : 0.0f;
+    p.status[slot] = st;
+}
+
+int launch_refine_patch(const RefinePointsArgs &p, const RefinePatchConsts *consts, int half, int n_frames, void *stream)
+{
+    if (n_frames <= 0 || n_frames > 65535 || !p.points_per_frame || !consts) return (int)hipErrorInvalidValue;
+    const dim3 grid((p.points_per_frame + (REFINE_PATCH_POINTS - 1)) / REFINE_PATCH_POINTS, (unsigned)n_frames), block(64);
+    hipStream_t s = (hipStream_t)stream;
+    switch (half) {
+    case 1: hipLaunchKernelGGL((k_refine_patch<1>), grid, block, 0, s, p, consts); break;
+    case 2: hipLaunchKernelGGL((k_refine_patch<2>), grid, block, 0, s, p, consts); break;
+    case 3: hipLaunchKernelGGL((k_refine_patch<3>), grid, block, 0, s, p, consts); break;
+    case 4: hipLaunchKernelGGL((k_refine_patch<4>), grid, block, 0, s, p, consts); break;
+    default: return (int)hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

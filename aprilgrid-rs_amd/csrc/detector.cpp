@@ -135,14 +135,14 @@ int make_blur_weights(float sigma, float *w)
 // a sigma agx_planes_enqueue / agx_debug_blur_weights can blur with: finite, positive, at most GB_MAX_RADIUS
 bool blur_sigma_ok(float sigma) { return std::isfinite(sigma) && sigma > 0.0f && std::ceil(sigma * 2.0f) <= (float)GB_MAX_RADIUS; }
 
-// Constants of rochade_refine for half_size_patch = 2 (the only value the reference passes,
-// detector.rs:430): cone kernel (:240-254) and the 25x6 pseudo-inverse of the quadratic
-// design matrix (:208-237).  The design's normal matrix is block diagonal on the symmetric
-// 5x5 grid (odd moments vanish): {xy}, {x}, {y} decouple and {x^2, y^2, 1} is a 3x3 block,
-// inverted here by its adjugate in binary64; one rounding to binary32.
-void make_refine_consts(RefineConsts &rc)
+// Constants of rochade_refine at half_size_patch = half in 1 .. REFINE_PATCH_MAX_HALF, ks = 2*half+1: cone kernel (:240-254)
+// and the ks*ks x 6 pseudo-inverse of the quadratic design matrix (:208-237).  The design's normal matrix is block diagonal
+// on the symmetric ks x ks grid (odd moments vanish): {xy}, {x}, {y} decouple and {x^2, y^2, 1} is a 3x3 block, inverted
+// here by its adjugate in binary64 (every intermediate is an integer far below 2^53 for these sizes, so the quotient is that
+// of the exact numerator and determinant); one rounding to binary32.
+static void refine_consts_at(int half, float *cone, float *pmat)
 {
-    const int half = 2, ks = 5;
+    const int ks = 2 * half + 1;
     double sx2 = 0, sx4 = 0;
     for (int c = 0; c < ks; ++c) {
         const double x = c - half;
@@ -168,22 +168,31 @@ void make_refine_consts(RefineConsts &rc)
             const double q[3] = {x * x, y * y, 1.0};
             double blk[3];
             for (int a = 0; a < 3; ++a) blk[a] = (adj[a][0] * q[0] + adj[a][1] * q[1] + adj[a][2] * q[2]) / det;
-            rc.pmat[i * 6 + 0] = (float)blk[0];          // x^2
-            rc.pmat[i * 6 + 1] = (float)(x * y / m_x2y2 + 0.0); // xy (+0.0: no negative zeros)
-            rc.pmat[i * 6 + 2] = (float)blk[1];          // y^2
-            rc.pmat[i * 6 + 3] = (float)(x / m_x2 + 0.0);      // x
-            rc.pmat[i * 6 + 4] = (float)(y / m_x2 + 0.0);      // y
-            rc.pmat[i * 6 + 5] = (float)blk[2];          // 1
+            pmat[i * 6 + 0] = (float)blk[0];          // x^2
+            pmat[i * 6 + 1] = (float)(x * y / m_x2y2 + 0.0); // xy (+0.0: no negative zeros)
+            pmat[i * 6 + 2] = (float)blk[1];          // y^2
+            pmat[i * 6 + 3] = (float)(x / m_x2 + 0.0);      // x
+            pmat[i * 6 + 4] = (float)(y / m_x2 + 0.0);      // y
+            pmat[i * 6 + 5] = (float)blk[2];          // 1
         }
     const float gamma = (float)half;
     float s = 0.0f;
     for (int a = 0; a < ks; ++a)
         for (int b = 0; b < ks; ++b) {
             const float da = gamma - (float)a, db = gamma - (float)b;
-            rc.cone[a * ks + b] = std::max(0.0f, gamma + 1.0f - std::sqrt(da * da + db * db));
+            cone[a * ks + b] = std::max(0.0f, gamma + 1.0f - std::sqrt(da * da + db * db));
         }
-    for (int a = 0; a < ks * ks; ++a) s += rc.cone[a];
-    for (int a = 0; a < ks * ks; ++a) rc.cone[a] = rc.cone[a] / s;
+    for (int a = 0; a < ks * ks; ++a) s += cone[a];
+    for (int a = 0; a < ks * ks; ++a) cone[a] = cone[a] / s;
+}
+
+// half_size_patch = 2, the value the chain's own refinement passes (detector.rs:430)
+void make_refine_consts(RefineConsts &rc) { refine_consts_at(2, rc.cone, rc.pmat); }
+
+void make_refine_patch_consts(int half, RefinePatchConsts &rc)
+{
+    rc = RefinePatchConsts{};
+    refine_consts_at(half, rc.cone, rc.pmat);
 }
 
 template <typename T>
@@ -824,6 +833,7 @@ int agx_detector_set_option(agx_detector *det, const char *name, int value)
     else if (!std::strcmp(name, "sparse_path")) det->sparse_path = value >= 0 && value <= 3 ? value : 0;
     else if (!std::strcmp(name, "debug_ablation")) det->dbg = value;  // timing only, results invalid
     else if (!std::strcmp(name, "store_response")) det->store_resp = value != 0;
+    else if (!std::strcmp(name, "refine_general_kernel")) det->refine_general_kernel = value != 0;  // tests, measurement: same results
     else if (!std::strcmp(name, "profile_stride")) det->prof_stride = value > 1 ? value : 1;
     else if (!std::strcmp(name, "profile_kernel")) det->prof_kernel = value >= 0 && value < K_COUNT ? value : K_BLUR_HESSIAN;
     else if (!std::strcmp(name, "device_tail")) {  // 1 on (refused where libm differs), 0 off, -1 back to the default (on where possible)
@@ -874,6 +884,8 @@ int agx_detector_get_option(const agx_detector *det, const char *name, int *valu
     else if (!std::strcmp(name, "sparse_path")) *value = det->sparse_path;
     else if (!std::strcmp(name, "last_sparse_path")) *value = det->last_sparse_path;
     else if (!std::strcmp(name, "last_chain_front")) *value = det->last_chain_front;
+    else if (!std::strcmp(name, "refine_general_kernel")) *value = det->refine_general_kernel;
+    else if (!std::strcmp(name, "last_refine_kernel")) *value = det->last_refine_kernel;  // (of the last refine batch: 0 k_refine_points, 1 k_refine_patch)
     else if (!std::strcmp(name, "k1_segments")) *value = a.n_segs;
     else if (!std::strcmp(name, "k1_strips")) *value = a.n_strips;
     else if (!std::strcmp(name, "k1_strip_columns")) *value = a.strip_cols;
@@ -1117,9 +1129,10 @@ int agx_detect_batch_fetch(agx_detector *det, agx_tag *out, uint32_t *counts, in
 static int refine_points_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, int width, int height,
                                       size_t row_stride_bytes, size_t frame_stride_bytes, int format, int image,
                                       const void *d_points, uint32_t points_per_frame, const uint32_t *d_counts,
-                                      agx_saddle *d_out, uint32_t *d_status)
+                                      agx_saddle *d_out, uint32_t *d_status, int half)
 {
     if (!det) return AGX_ERR_ARG;
+    if (half < 1 || half > REFINE_PATCH_MAX_HALF) return fail(det, AGX_ERR_ARG, "half_size_patch must be in 1 .. 4");
     if (!d_frames || !d_points || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null frames, null points or n_frames <= 0");
     if (!points_per_frame) return fail(det, AGX_ERR_ARG, "points_per_frame must be > 0");
     if ((d_out == nullptr) != (d_status == nullptr)) return fail(det, AGX_ERR_ARG, "d_out and d_status: both or neither");
@@ -1135,10 +1148,27 @@ static int refine_points_enqueue_impl(agx_detector *det, const void *d_frames, i
     if (slots >= ((size_t)1 << 31)) return fail(det, AGX_ERR_ARG, "at most 2^31 - 1 points per batch");
     HIP_TRY(det, hipSetDevice(det->device));
     begin_batch(det);
+    // half_size_patch = 2 is k_refine_points, one point per lane; every other size, and 2 under "refine_general_kernel", is
+    // k_refine_patch with its constants from the handle's device table (all four sizes, uploaded once)
+    const bool general = half != 2 || det->refine_general_kernel;
+    const RefinePatchConsts *d_consts = nullptr;
+    if (general) {
+        d_consts = static_cast<const RefinePatchConsts *>(side_ensure(det, SB_REFINE_CONSTS, REFINE_PATCH_MAX_HALF * sizeof(RefinePatchConsts), 0));
+        if (!d_consts) return fail(det, AGX_ERR_HIP, "hipMalloc: refine constants");
+        if (!det->patch_consts_uploaded) {
+            det->patch_consts.resize(REFINE_PATCH_MAX_HALF);
+            for (int h = 1; h <= REFINE_PATCH_MAX_HALF; ++h) make_refine_patch_consts(h, det->patch_consts[h - 1]);
+            HIP_TRY(det, hipMemcpyAsync(const_cast<RefinePatchConsts *>(d_consts), det->patch_consts.data(),
+                                        REFINE_PATCH_MAX_HALF * sizeof(RefinePatchConsts), hipMemcpyHostToDevice, det->stream));
+            det->patch_consts_uploaded = true;
+        }
+        d_consts += half - 1;
+    }
     RefinePointsArgs p{};
     p.W = width;
     p.H = height;
-    const bool any_window = width >= 9 && height >= 9;  // (a smaller frame is valid input: all its points are AGX_POINT_OUTSIDE)
+    const int win = 4 * half + 1;
+    const bool any_window = width >= win && height >= win;  // (a smaller frame is valid input: all its points are AGX_POINT_OUTSIDE)
     if (image == AGX_REFINE_PLANE || !any_window) {
         p.img = (const float *)d_frames;  // (!any_window: never read)
         p.pitch = (long long)(row_stride_bytes / 4);
@@ -1168,8 +1198,10 @@ static int refine_points_enqueue_impl(agx_detector *det, const void *d_frames, i
     p.counts = d_counts;
     p.out = reinterpret_cast<float *>(d_out);
     p.status = d_status;
-    hipError_t e = (hipError_t)launch_refine_points(p, det->rc, n_frames, det->stream);
-    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_refine_points: ") + hipGetErrorString(e));
+    hipError_t e = (hipError_t)(general ? launch_refine_patch(p, d_consts, half, n_frames, det->stream)
+                                        : launch_refine_points(p, det->rc, n_frames, det->stream));
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string(general ? "k_refine_patch: " : "k_refine_points: ") + hipGetErrorString(e));
+    det->last_refine_kernel = general ? 1 : 0;
     det->batch = BATCH_REFINE;
     det->refine.n_frames = n_frames;
     det->refine.points_per_frame = points_per_frame;
@@ -1217,14 +1249,22 @@ static int refine_points_fetch_impl(agx_detector *det, agx_saddle *out, uint32_t
 
 extern "C" {
 
+int agx_refine_points_enqueue_h(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                                size_t frame_stride_bytes, int format, int image, const void *d_points, uint32_t points_per_frame,
+                                const uint32_t *d_counts, agx_saddle *d_out, uint32_t *d_status, int half_size_patch)
+{
+    return agx_guard(det, [&]() -> int {
+    return refine_points_enqueue_impl(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, image,
+                                      d_points, points_per_frame, d_counts, d_out, d_status, half_size_patch);
+    });
+}
+
 int agx_refine_points_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
                               size_t frame_stride_bytes, int format, int image, const void *d_points, uint32_t points_per_frame,
                               const uint32_t *d_counts, agx_saddle *d_out, uint32_t *d_status)
 {
-    return agx_guard(det, [&]() -> int {
-    return refine_points_enqueue_impl(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, image,
-                                      d_points, points_per_frame, d_counts, d_out, d_status);
-    });
+    return agx_refine_points_enqueue_h(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, image, d_points,
+                                       points_per_frame, d_counts, d_out, d_status, 2);
 }
 
 int agx_refine_points_fetch(agx_detector *det, agx_saddle *out, uint32_t *status)
@@ -1232,11 +1272,12 @@ int agx_refine_points_fetch(agx_detector *det, agx_saddle *out, uint32_t *status
     return agx_guard(det, [&]() -> int { return refine_points_fetch_impl(det, out, status); });
 }
 
-int agx_rochade_refine(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes, int format, int image,
-                       const void *points, uint32_t n_points, agx_saddle *out, uint32_t *status, uint32_t *n_refined)
+int agx_rochade_refine_h(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes, int format, int image,
+                         const void *points, uint32_t n_points, agx_saddle *out, uint32_t *status, uint32_t *n_refined, int half_size_patch)
 {
     return agx_guard(det, [&]() -> int {
     if (!det) return AGX_ERR_ARG;
+    if (half_size_patch < 1 || half_size_patch > REFINE_PATCH_MAX_HALF) return fail(det, AGX_ERR_ARG, "half_size_patch must be in 1 .. 4");
     if (!pixels || !n_refined || (n_points && (!points || !out || !status))) return fail(det, AGX_ERR_ARG, "null argument");
     if (image != AGX_REFINE_BLURRED && image != AGX_REFINE_PLANE) return fail(det, AGX_ERR_ARG, "image must be AGX_REFINE_BLURRED or AGX_REFINE_PLANE");
     if (image == AGX_REFINE_PLANE && format != AGX_LF32) return fail(det, AGX_ERR_FORMAT, "AGX_REFINE_PLANE takes an AGX_LF32 plane");
@@ -1250,7 +1291,7 @@ int agx_rochade_refine(agx_detector *det, const void *pixels, int width, int hei
     if (!d_points) return fail(det, AGX_ERR_HIP, "hipMalloc: points");
     HIP_TRY(det, hipMemcpyAsync(d_points, points, (size_t)n_points * sizeof(agx_point), hipMemcpyHostToDevice, det->stream));
     rc = refine_points_enqueue_impl(det, b.frames, 1, width, height, b.row_stride, b.frame_stride, format, image, d_points, n_points, nullptr,
-                                    nullptr, nullptr);
+                                    nullptr, nullptr, half_size_patch);
     if (rc) return rc;
     rc = refine_points_fetch_impl(det, out, status);
     if (rc) return rc;
@@ -1259,6 +1300,12 @@ int agx_rochade_refine(agx_detector *det, const void *pixels, int width, int hei
     *n_refined = n;
     return AGX_OK;
     });
+}
+
+int agx_rochade_refine(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes, int format, int image,
+                       const void *points, uint32_t n_points, agx_saddle *out, uint32_t *status, uint32_t *n_refined)
+{
+    return agx_rochade_refine_h(det, pixels, width, height, row_stride_bytes, format, image, points, n_points, out, status, n_refined, 2);
 }
 
 }  // extern "C"
@@ -1527,6 +1574,21 @@ int agx_debug_blur_weights(float sigma, float *weights, int cap, int *radius)
     *radius = blur_radius(sigma);
     if (cap < 2 * *radius + 1) return AGX_ERR_CAPACITY;
     make_blur_weights(sigma, weights);
+    return AGX_OK;
+    });
+}
+
+int agx_debug_refine_constants(int half_size_patch, float *cone, float *pmat, int cap_points, int *n_points)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (!cone || !pmat || !n_points || half_size_patch < 1 || half_size_patch > REFINE_PATCH_MAX_HALF) return AGX_ERR_ARG;
+    const int ks = 2 * half_size_patch + 1;
+    *n_points = ks * ks;
+    if (cap_points < *n_points) return AGX_ERR_CAPACITY;
+    RefinePatchConsts rc;
+    make_refine_patch_consts(half_size_patch, rc);
+    std::memcpy(cone, rc.cone, (size_t)*n_points * sizeof(float));
+    std::memcpy(pmat, rc.pmat, (size_t)*n_points * 6 * sizeof(float));
     return AGX_OK;
     });
 }

@@ -148,6 +148,7 @@ enum {
     SB_REFINE_OUT,     // agx_refine_points_enqueue without caller-owned results: [n_frames][points_per_frame] agx_saddle ...
     SB_REFINE_STATUS,  // ... and [n_frames][points_per_frame] uint32 (AGX_POINT_*)
     SB_REFINE_POINTS,  // agx_rochade_refine: the host's points on the device
+    SB_REFINE_CONSTS,  // k_refine_patch: RefinePatchConsts of half_size_patch 1 .. 4, uploaded by the first batch that needs them
     SB_DECODE_TAGS,    // agx_decode_quads_enqueue without caller-owned results: [n_frames][quads_per_frame] agx_tag ...
     SB_DECODE_STATUS,  // ... [n_frames][quads_per_frame] uint32 (AGX_QUAD_*) ...
     SB_DECODE_BITS,    // ... and [n_frames][quads_per_frame] uint64 (bit_code's value)
@@ -259,6 +260,10 @@ struct agx_detector {
     int last_tail_frames = 0, last_tail_fallbacks = 0, last_tail_uncertain = 0;  // of the last agx_detect_batch call
     agx::DetectPending detect;          // BATCH_DETECT: what agx_detect_batch_fetch needs of it
     agx::RefinePending refine;          // BATCH_REFINE: what agx_refine_points_fetch needs of it
+    int refine_general_kernel = 0;      // option "refine_general_kernel": half_size_patch 2 runs k_refine_patch<2> too
+    int last_refine_kernel = 0;         // option "last_refine_kernel": the last refine batch ran 0 = k_refine_points, 1 = k_refine_patch
+    std::vector<agx::RefinePatchConsts> patch_consts;  // host copy of SB_REFINE_CONSTS (the upload's source)
+    bool patch_consts_uploaded = false;
     std::vector<uint32_t> refine_host;  // its host staging when per-frame counts were given (records, statuses, counts)
     agx::DecodePending decode;          // BATCH_DECODE: what agx_decode_quads_fetch needs of it
     std::vector<uint64_t> decode_host;  // its host staging when per-frame counts were given (bits, tags, statuses, counts)

@@ -581,9 +581,10 @@ class TagDetector:
             raise AgxError(_ffi.AGX_ERR_ARG, "image must be 'blurred' or 'plane', got %r" % (image,))
         return self._REFINE_IMAGE[image]
 
-    def rochade_refine(self, img, points, image="blurred", format=None):
-        """detector::rochade_refine(image_input, initial_corners, 2) on a host image: points = n (x, y) pairs.
-        image="blurred": img is an image of any format and is refined on its sigma = 1.5 blur, as refined_saddle_points does;
+    def rochade_refine(self, img, points, image="blurred", format=None, half_size_patch=2):
+        """detector::rochade_refine(image_input, initial_corners, half_size_patch) on a host image: points = n (x, y) pairs;
+        half_size_patch in 1 .. 4 (2: what the detector itself passes).
+        image="blurred": img is an image of any format and is refined on its blur at the handle's sigma, as refined_saddle_points does;
         image="plane": img is an HxW float32 plane and IS image_input.  -> (records [n] SADDLE_DTYPE, status [n] uint32
         AGX_POINT_*), in input order; a rejected point's record is zero.  The reference's Vec<Saddle> is
         records[status == AGX_POINT_REFINED]."""
@@ -595,16 +596,17 @@ class TagDetector:
         status = np.zeros(n, np.uint32)
         n_refined = C.c_uint32(0)
         self._batch = self._detect = self._refine = self._decode = self._find = None
-        self._check(self._lib.agx_rochade_refine(self._h, a.ctypes.data, w, h, stride, fmt, self._refine_image(image), pts.ctypes.data, n,
-                                                 out.ctypes.data, status.ctypes.data, C.byref(n_refined)))
+        self._check(self._lib.agx_rochade_refine_h(self._h, a.ctypes.data, w, h, stride, fmt, self._refine_image(image), pts.ctypes.data, n,
+                                                   out.ctypes.data, status.ctypes.data, C.byref(n_refined), int(half_size_patch)))
         assert n_refined.value == int((status == _ffi.AGX_POINT_REFINED).sum())
         return out, status
 
-    def refine_points_enqueue(self, frames, points, counts=None, out=None, status=None, image="blurred", format=None):
+    def refine_points_enqueue(self, frames, points, counts=None, out=None, status=None, image="blurred", format=None, half_size_patch=2):
         """rochade_refine over a batch on this detector's GPU, stream-ordered behind torch's current stream; returns immediately.
         frames and format= as saddles_batch_enqueue (image="plane": [N,H,W] float32, refined as it is); points: float32 [N,P,2]
         (x, y); counts: optional int32 [N], the points of frame f (at most P; slots beyond are not written); out float32 [N,P,5]
-        and status int32 [N,P]: device-resident results (both or neither) -- without them refine_points_fetch returns arrays."""
+        and status int32 [N,P]: device-resident results (both or neither) -- without them refine_points_fetch returns arrays.
+        half_size_patch: rochade_refine's third argument, 1 .. 4 (a 3x3 .. 9x9 fit in a 5x5 .. 17x17 window)."""
         import torch
         fmt, bpp = self._tensor_format(frames, format)
         n, w, h, rs, fs = self._tensor_geometry(frames, fmt, bpp)
@@ -626,8 +628,8 @@ class TagDetector:
         p_status = tensor(status, torch.int32, (n, ppf), "status") if status is not None else None
         self._follow_torch_stream(frames)
         self._batch = self._detect = self._refine = self._decode = self._find = None
-        self._check(self._lib.agx_refine_points_enqueue(self._h, frames.data_ptr(), n, w, h, rs, fs, fmt, self._refine_image(image), p_points,
-                                                        ppf, p_counts, p_out, p_status))
+        self._check(self._lib.agx_refine_points_enqueue_h(self._h, frames.data_ptr(), n, w, h, rs, fs, fmt, self._refine_image(image), p_points,
+                                                          ppf, p_counts, p_out, p_status, int(half_size_patch)))
         self._refine = (n, ppf, (frames, points, counts), (out, status) if out is not None else None)
 
     def refine_points_fetch(self):
@@ -949,6 +951,18 @@ def blur_weights(sigma):
     if st != _ffi.AGX_OK:
         raise AgxError(st, "sigma %r" % (sigma,))
     return w[: 2 * radius.value + 1].copy()
+
+
+def refine_constants(half_size_patch):
+    """rochade_refine's constants at half_size_patch in 1 .. 4 (src/detector.rs:208-254), ks = 2 * half_size_patch + 1:
+    -> (cone [ks*ks] float32, pmat [ks*ks, 6] float32); no device."""
+    cone = np.zeros(81, np.float32)
+    pmat = np.zeros(81 * 6, np.float32)
+    n = C.c_int(0)
+    st = _ffi.lib().agx_debug_refine_constants(int(half_size_patch), cone.ctypes.data, pmat.ctypes.data, 81, C.byref(n))
+    if st != _ffi.AGX_OK:
+        raise AgxError(st, "half_size_patch %r" % (half_size_patch,))
+    return cone[: n.value].copy(), pmat[: n.value * 6].reshape(n.value, 6).copy()
 
 
 def decode_quads_tail(tag_family, luma8, quads, with_bits=False):

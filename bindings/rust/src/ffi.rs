@@ -195,9 +195,16 @@ extern "C" {
                                      d_points: *const c_void, points_per_frame: u32, d_counts: *const u32, d_out: *mut agx_saddle,
                                      d_status: *mut u32) -> c_int;
     pub fn agx_refine_points_fetch(det: *mut agx_detector, out: *mut agx_saddle, status: *mut u32) -> c_int;
+    pub fn agx_refine_points_enqueue_h(det: *mut agx_detector, d_frames: *const c_void, n_frames: c_int, width: c_int, height: c_int,
+                                       row_stride_bytes: usize, frame_stride_bytes: usize, format: c_int, image: c_int,
+                                       d_points: *const c_void, points_per_frame: u32, d_counts: *const u32, d_out: *mut agx_saddle,
+                                       d_status: *mut u32, half_size_patch: c_int) -> c_int;
     pub fn agx_rochade_refine(det: *mut agx_detector, pixels: *const c_void, width: c_int, height: c_int, row_stride_bytes: usize,
                               format: c_int, image: c_int, points: *const c_void, n_points: u32, out: *mut agx_saddle,
                               status: *mut u32, n_refined: *mut u32) -> c_int;
+    pub fn agx_rochade_refine_h(det: *mut agx_detector, pixels: *const c_void, width: c_int, height: c_int, row_stride_bytes: usize,
+                                format: c_int, image: c_int, points: *const c_void, n_points: u32, out: *mut agx_saddle,
+                                status: *mut u32, n_refined: *mut u32, half_size_patch: c_int) -> c_int;
 
     pub fn agx_decode_quads_enqueue(det: *mut agx_detector, d_frames: *const c_void, n_frames: c_int, width: c_int, height: c_int,
                                     row_stride_bytes: usize, frame_stride_bytes: usize, format: c_int, d_quads: *const c_void,
@@ -230,6 +237,8 @@ extern "C" {
     pub fn agx_hessian_response(det: *mut agx_detector, pixels: *const c_void, width: c_int, height: c_int, row_stride_bytes: usize,
                                 format: c_int, out: *mut c_float) -> c_int;
     pub fn agx_debug_blur_weights(sigma: c_float, weights: *mut c_float, cap: c_int, radius: *mut c_int) -> c_int;
+    pub fn agx_debug_refine_constants(half_size_patch: c_int, cone: *mut c_float, pmat: *mut c_float, cap_points: c_int,
+                                      n_points: *mut c_int) -> c_int;
 
     pub fn agx_detect_from_saddles(det: *const agx_detector, saddles: *const agx_saddle, n_saddles: u32, luma8: *const u8, width: c_int,
                                    height: c_int, row_stride_bytes: usize, out: *mut agx_tag, cap: u32, n_out: *mut u32) -> c_int;

@@ -229,6 +229,18 @@ impl TagDetector {
     /// The same with an answer for every corner: its record (zeros unless refined) and why it was kept or dropped
     /// (`AGX_POINT_REFINED`, `_OUTSIDE`, `_NOT_SADDLE`, `_MOVED`), in input order.
     pub fn rochade_refine_with_status(&self, img: &image::DynamicImage, initial_corners: &[(f32, f32)]) -> (Vec<Saddle>, Vec<u32>) {
+        self.rochade_refine_h_with_status(img, initial_corners, 2)
+    }
+
+    /// reference src/detector.rs:194-361, `rochade_refine(image_input, initial_corners, half_size_patch)` with the crate's third
+    /// argument, 1 ..= 4: the refined corners, in input order.  `rochade_refine` is this at 2, what the detector passes (:430).
+    pub fn rochade_refine_h(&self, img: &image::DynamicImage, initial_corners: &[(f32, f32)], half_size_patch: i32) -> Vec<Saddle> {
+        let (records, status) = self.rochade_refine_h_with_status(img, initial_corners, half_size_patch);
+        records.into_iter().zip(status).filter(|(_, st)| *st == ffi::AGX_POINT_REFINED as u32).map(|(s, _)| s).collect()
+    }
+
+    /// The same with an answer for every corner, as `rochade_refine_with_status`.
+    pub fn rochade_refine_h_with_status(&self, img: &image::DynamicImage, initial_corners: &[(f32, f32)], half_size_patch: i32) -> (Vec<Saddle>, Vec<u32>) {
         let (inp, w, h) = Self::input(img);
         let (px, stride, fmt) = match &inp {
             Input::Native { px, stride, fmt, .. } => (*px, *stride, *fmt),
@@ -239,12 +251,12 @@ impl TagDetector {
         let mut status = vec![0u32; points.len()];
         let mut n_refined = 0u32;
         let st = self.with_handle(|d| unsafe {
-            ffi::agx_rochade_refine(
+            ffi::agx_rochade_refine_h(
                 d, px, w as c_int, h as c_int, stride, fmt, ffi::AGX_REFINE_BLURRED, points.as_ptr() as *const c_void,
-                points.len() as u32, out.as_mut_ptr(), status.as_mut_ptr(), &mut n_refined,
+                points.len() as u32, out.as_mut_ptr(), status.as_mut_ptr(), &mut n_refined, half_size_patch as c_int,
             )
         });
-        assert_eq!(st, ffi::AGX_OK, "agx_rochade_refine failed: {}", st);
+        assert_eq!(st, ffi::AGX_OK, "agx_rochade_refine_h failed: {}", st);
         (out.iter().map(|s| Saddle { p: (s.x, s.y), k: s.k, theta: s.theta, phi: s.phi }).collect(), status)
     }
 

@@ -329,9 +329,11 @@ int agx_detect_batch_fetch(agx_detector *det, agx_tag *out, uint32_t *counts, in
 
 /* detector::rochade_refine(image_input, initial_corners, half_size_patch) -> Vec<Saddle> -- src/detector.rs:194-361, a `pub fn`
  * of the crate: the sub-pixel refinement of ANY list of corner guesses (last frame's corners, corners predicted from a board
- * homography, another detector's), not only of the centroids the chain's own flood fill produced.  half_size_patch is 2, the
- * only value the reference's detector passes (:430): there is no parameter for it.  Every point is answered in its own slot,
- * in input order, with a record and one of these reasons; a rejected point's record is five zero floats. */
+ * homography, another detector's), not only of the centroids the chain's own flood fill produced.  half_size_patch is the last
+ * argument of the _h forms below, 1 .. 4 (fitted patch 3x3 .. 9x9, window 5x5 .. 17x17); the forms without it pass 2, the
+ * value the reference's detector passes (:430).  The chain's own refinement (agx_refined_saddle_points, the saddle and detect
+ * batches) stays at 2, as refined_saddle_points has it.  Every point is answered in its own slot, in input order, with a
+ * record and one of these reasons; a rejected point's record is five zero floats. */
 struct agx_point {
     float x, y;
 }; /* one (f32,f32) of initial_corners -- src/detector.rs:194-361; 8 bytes.  Arrays of them cross the boundary as `const void *`,
@@ -341,7 +343,9 @@ enum { AGX_POINT_REFINED = 0,
        AGX_POINT_OUTSIDE = 1,     /* :266-274: the 9x9 window around round(x), round(y) leaves the image: unless both coordinates
                                      are finite, roundf(x) in [4, W-5] and roundf(y) in [4, H-5].  Decided in float before anything
                                      is converted or read -- NaN, +-inf and values beyond the int range, undefined in the reference
-                                     (`as i32`, unchecked indexing), are OUTSIDE; so is every point of a frame smaller than 9x9 */
+                                     (`as i32`, unchecked indexing), are OUTSIDE; so is every point of a frame smaller than 9x9.
+                                     At half_size_patch = h the window is (4h+1)x(4h+1): roundf(x) in [2h, W-1-2h], roundf(y) in
+                                     [2h, H-1-2h], and every point of a frame smaller than 4h+1 in either direction is OUTSIDE */
        AGX_POINT_NOT_SADDLE = 2,  /* :331-339: not (d < 0) */
        AGX_POINT_MOVED = 3 };     /* :342-347: |x0| or |y0| > 1, or not |c5| < k */
 enum { AGX_REFINE_BLURRED = 0,    /* frames of any agx_format; refined on their blur at the handle's sigma, as
@@ -368,12 +372,28 @@ int agx_refine_points_enqueue(agx_detector *det, const void *d_frames, int n_fra
  * Caller-owned device buffers: out and status are NULL, the call only waits.  AGX_ERR_STATE: no such batch in flight (another
  * kind, none, or fetched already). */
 int agx_refine_points_fetch(agx_detector *det, agx_saddle *out, uint32_t *status);
+/* agx_refine_points_enqueue with rochade_refine's third argument (src/detector.rs:194-361): half_size_patch in 1 .. 4, anything
+ * else is AGX_ERR_ARG and leaves a batch in flight where it is.  Every other argument, the batch (the same third kind, fetched by
+ * agx_refine_points_fetch) and the records are agx_refine_points_enqueue's, which is this call at 2 and gives the same bytes as
+ * it.  AGX_REFINE_BLURRED refines on the blur at the handle's sigma as before: the patch size is chosen by the caller, to go
+ * with the sigma or not.  An AGX_REFINE_PLANE plane is read inside a point's own window only.  Option "refine_general_kernel"
+ * (0; tests and measurements) = 1 runs half_size_patch 2 on the kernel of the other sizes, with identical results; the
+ * read-only option "last_refine_kernel" says which kernel the last refine batch ran (0: the one of 2, 1: the general one). */
+int agx_refine_points_enqueue_h(agx_detector *det, const void *d_frames, int n_frames, int width, int height,
+                                size_t row_stride_bytes, size_t frame_stride_bytes, int format, int image,
+                                const void *d_points, uint32_t points_per_frame, const uint32_t *d_counts,
+                                agx_saddle *d_out, uint32_t *d_status, int half_size_patch);
 /* rochade_refine (src/detector.rs:194-361) of one image in HOST memory: uploads pixels and points, runs a batch of one, writes
  * record and status of every point (points: n_points agx_point records; out, status: n_points entries each, in input order) and *n_refined, the number of
  * AGX_POINT_REFINED ones: the reference's Vec<Saddle> is those records in input order.  n_points == 0: AGX_OK, *n_refined = 0. */
 int agx_rochade_refine(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes, int format,
                        int image, const void *points, uint32_t n_points, agx_saddle *out, uint32_t *status,
                        uint32_t *n_refined);
+/* agx_rochade_refine with rochade_refine's third argument (src/detector.rs:194-361): half_size_patch in 1 .. 4, else AGX_ERR_ARG.
+ * agx_rochade_refine is this call at 2. */
+int agx_rochade_refine_h(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes, int format,
+                         int image, const void *points, uint32_t n_points, agx_saddle *out, uint32_t *status,
+                         uint32_t *n_refined, int half_size_patch);
 
 /* ---- decode of caller-given quads -------------------------------------------------------- */
 
@@ -698,6 +718,12 @@ int agx_detector_constants(const agx_detector *det, float *blur_w7, float *cone2
  * 2*radius + 1 weights; no handle, no device.  AGX_ERR_CAPACITY: cap is smaller than that (*radius is set); AGX_ERR_ARG: sigma is
  * not positive and finite, or ceilf(2 sigma) > 16. */
 int agx_debug_blur_weights(float sigma, float *weights, int cap, int *radius);
+/* The constants of rochade_refine at half_size_patch (src/detector.rs:194-361; the pseudo-inverse at :208-237, the cone kernel at
+ * :240-254): *n_points = (2*half_size_patch + 1)^2, cone receives n_points floats and pmat n_points*6, row i, column j at
+ * [i*6+j]; no handle, no device.  The pseudo-inverse is the exact one of the quadratic design matrix rounded to binary32, with no
+ * negative zeros; at 2 both are agx_detector_constants'.  AGX_ERR_CAPACITY: cap_points is smaller than that (*n_points is set);
+ * AGX_ERR_ARG: half_size_patch outside 1 .. 4, or a NULL output. */
+int agx_debug_refine_constants(int half_size_patch, float *cone, float *pmat, int cap_points, int *n_points);
 
 const char *agx_status_string(int status);
 /* Message of the last failure on this detector (HIP error text etc.); never NULL.
