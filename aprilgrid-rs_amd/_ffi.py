@@ -67,6 +67,8 @@ SYMBOLS = {
     "agx_detector_get_option": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int)]),
     "agx_detector_set_blur_sigma": (C.c_int, [_P, C.c_float]),
     "agx_detector_get_blur_sigma": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "agx_detector_set_half_size_patch": (C.c_int, [_P, C.c_int]),
+    "agx_detector_get_half_size_patch": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "agx_refined_saddle_points": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, _P, C.c_uint32,
                                             C.POINTER(C.c_uint32)]),
     "agx_detect": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, _P, C.c_uint32,

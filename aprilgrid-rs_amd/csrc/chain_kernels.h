@@ -143,7 +143,10 @@ void tuning_env_reload();
 bool plan_k1(ChainArgs &a, int override_rows_per_seg);
 
 // Enqueue one kernel of the chain on `stream` (hipStream_t as void*).  Returns hipError_t.
-int launch_kernel(int which, const ChainArgs &a, const RefineConsts &rc, void *stream);
+// deferred_refine (agx_detector_set_half_size_patch: the chain's refinement as launches of its own, see launch_refine_clusters):
+// K_FLOOD_REFINE then launches the instantiation that clusters without refining, K_RARE the one that only emits.  ChainArgs
+// carries nothing of this, so that the kernels of the default plan keep their argument layout.
+int launch_kernel(int which, const ChainArgs &a, const RefineConsts &rc, void *stream, bool deferred_refine = false);
 
 // k_refine_points (agx_refine_points_enqueue): rochade_refine (detector.rs:194-361, half_size_patch = 2) of caller-given points
 // on the f32 plane(s) `img` -- the chain's blur planes, or a caller's own.  All pointers are device pointers.
@@ -174,6 +177,13 @@ struct RefinePatchConsts {
 // grid (ceil(points_per_frame / 4), n_frames <= 65535); `consts` is the device record of `half`; a plane is never read outside
 // a point's own (4*half+1)^2 window, whatever p.padded says.  hipError_t
 int launch_refine_patch(const RefinePointsArgs &p, const RefinePatchConsts *consts, int half, int n_frames, void *stream);
+
+// The chain's deferred refinement, between launch_kernel(K_FLOOD_REFINE, .., true) and launch_kernel(K_RARE, .., true):
+// k_generic_cluster (a.n_frames workgroups; generic_frame for the frames that need it) and k_refine_clusters<half>, rochade_refine
+// at half_size_patch `half` in 1 .. 4 of every frame's cluster table on its blur plane (a fixed number of one-wave workgroups per
+// frame that loop over the table).  `consts`: the handle's device table of REFINE_PATCH_MAX_HALF records.  hipError_t
+int launch_generic_cluster(const ChainArgs &a, void *stream);
+int launch_refine_clusters(const ChainArgs &a, const RefinePatchConsts *consts, int half, void *stream);
 
 size_t k5_lds_bytes(const ChainArgs &a);
 

@@ -2179,6 +2179,16 @@ __device__ __forceinline__ void refine_values(const ChainArgs &a, const RefineCo
     atomicMax(sink.max_k_bits, __float_as_uint(k));
 }
 
+// The f32 centroid of a cluster from its size and integer coordinate sums, as refine_values forms it (detector.rs:427), for the
+// stages that cluster without refining.
+__device__ __forceinline__ void cluster_centroid(uint32_t *flags, uint32_t cn, uint32_t sx, uint32_t sy, float &cx, float &cy)
+{
+    if (sx >= (1u << 24) || sy >= (1u << 24)) atomicOr(flags, FLAG_CENTROID_INEXACT);
+    const float fn = (float)cn;
+    cx = (float)sx / fn;
+    cy = (float)sy / fn;
+}
+
 // rochade_refine of cluster record s of `frame` as it stands in the cluster table.
 template <bool VEC>
 __device__ __forceinline__ void refine_cluster(const ChainArgs &a, const RefineConsts &rc, int frame, size_t cbase,
@@ -2203,7 +2213,10 @@ __device__ __forceinline__ void refine_cluster(const ChainArgs &a, const RefineC
 // run under the window reads of the others.)  Seeds whose component may leave the window are flooded again by
 // the whole wave (128 x 64 window) before the refinement; what leaves that window too sends the frame to k_rare.
 // ------------------------------------------------------------------------------------------
-template <bool VEC, typename CLK>
+// REFINE = false (the chain at a half_size_patch other than 2, or at 2 under "chain_refine_general"): the floods and the cluster
+// records only -- first pixel, size, f32 centroid (detector.rs:427) -- and nothing is appended to the refined list;
+// k_refine_clusters refines the table in a launch of its own.  The REFINE = true instantiations compile as they did.
+template <bool VEC, typename CLK, bool REFINE = true>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AGX_FLOOD_WPE, 8))) k_flood_refine(ChainArgs a, RefineConsts rc)
 {
     const WaveTimer wt(a, K_FLOOD_REFINE);
@@ -2266,8 +2279,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AGX_FLO
             // atomic's round trip runs under the window loads (a frame whose cluster list overflows is void as a whole)
             const uint32_t o = atomicAdd(&ctr.n_clusters, 1u);
             float cx, cy;
-            const RecSinkGlobal sink{&ctr.n_refined, &ctr.max_k_bits, &ctr.flags};
-            refine_values<VEC>(a, rc, frame, img, a.W, a.H, p, cnt, sumx, sumy, sink, cx, cy, clk);
+            if constexpr (REFINE) {
+                const RecSinkGlobal sink{&ctr.n_refined, &ctr.max_k_bits, &ctr.flags};
+                refine_values<VEC>(a, rc, frame, img, a.W, a.H, p, cnt, sumx, sumy, sink, cx, cy, clk);
+            } else {
+                cluster_centroid(&ctr.flags, cnt, sumx, sumy, cx, cy);
+            }
             if (o < a.cap_roots) {
                 a.clu_key[cbase + o] = p;
                 a.clu_cnt[cbase + o] = cnt;
@@ -2514,13 +2531,16 @@ __device__ __forceinline__ FrameHead load_frame_head(const FrameCounters &ctr)
     return h;
 }
 
+// EMIT_ONLY (k_rare behind k_generic_cluster + k_refine_clusters): the frame is clustered and refined already, whatever its
+// flags say, and `head` is final; only the emission is left.
+template <bool EMIT_ONLY = false>
 __device__ __forceinline__ void rare_frame(const ChainArgs &a, const RefineConsts &rc, int frame, uint32_t *lds_u, uint32_t lds_entries,
                                            uint32_t *s_misc3, const FrameHead &head)
 {
     uint32_t &s_count = s_misc3[0], &s_offset = s_misc3[1], &s_fits = s_misc3[2];
     FrameCounters &ctr = a.ctr[frame];
     uint32_t flags0 = head.flags, n_ref0 = head.n_refined, maxk0 = head.max_k_bits;
-    const bool generic = a.force_generic || (flags0 & FLAG_BIG_CLUSTER);
+    const bool generic = !EMIT_ONLY && (a.force_generic || (flags0 & FLAG_BIG_CLUSTER));
     const size_t cbase = (size_t)frame * a.cap_roots;
     const float *img = a.blur + (size_t)frame * (size_t)a.plane;
     if (generic) {
@@ -2690,11 +2710,10 @@ __device__ __forceinline__ bool emit_large_split(const ChainArgs &a, int frame, 
 // rare work and its emission (rare_frame); the other parts only exist for frames with a large list, which the parts emit
 // together (emit_large_split).
 constexpr uint32_t RARE_MAX_PARTS = 8;
-__global__ void __launch_bounds__(1024) k_rare(ChainArgs a, RefineConsts rc, uint32_t lds_entries, uint32_t n_parts)
+template <bool EMIT_ONLY>
+__device__ __forceinline__ void rare_parts(const ChainArgs &a, const RefineConsts &rc, uint32_t lds_entries, uint32_t n_parts,
+                                           uint32_t *lds_u, uint32_t *s_misc3, uint32_t *s_cnt /*[RARE_MAX_PARTS + 2]*/)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_u[];  // (emit_wide reads its keys 16 bytes at a time)
-    __shared__ uint32_t s_misc3[3];
-    __shared__ uint32_t s_cnt[RARE_MAX_PARTS + 2];
     const WaveTimer wt(a, K_RARE);
     const int frame = (int)(blockIdx.x / n_parts);
     const uint32_t part = blockIdx.x - (uint32_t)frame * n_parts;
@@ -2702,7 +2721,7 @@ __global__ void __launch_bounds__(1024) k_rare(ChainArgs a, RefineConsts rc, uin
     FrameCounters &ctr = a.ctr[frame];
     const FrameHead head = load_frame_head(ctr);
     if (n_parts > 1) {
-        const bool generic = a.force_generic || (head.flags & FLAG_BIG_CLUSTER);
+        const bool generic = !EMIT_ONLY && (a.force_generic || (head.flags & FLAG_BIG_CLUSTER));
         const bool void_frame = (head.flags & (FLAG_CAND_OVERFLOW | FLAG_ROOT_OVERFLOW)) != 0;
         const bool split = !generic && !void_frame && head.n_refined > TAIL_CAP;  // (the same decision in every part of the frame)
         if (split) {
@@ -2712,7 +2731,22 @@ __global__ void __launch_bounds__(1024) k_rare(ChainArgs a, RefineConsts rc, uin
         }
         if (part != 0) return;
     }
-    rare_frame(a, rc, frame, lds_u, lds_entries, s_misc3, head);
+    rare_frame<EMIT_ONLY>(a, rc, frame, lds_u, lds_entries, s_misc3, head);
+}
+__global__ void __launch_bounds__(1024) k_rare(ChainArgs a, RefineConsts rc, uint32_t lds_entries, uint32_t n_parts)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_u[];  // (emit_wide reads its keys 16 bytes at a time)
+    __shared__ uint32_t s_misc3[3];
+    __shared__ uint32_t s_cnt[RARE_MAX_PARTS + 2];
+    rare_parts<false>(a, rc, lds_entries, n_parts, lds_u, s_misc3, s_cnt);
+}
+// k_rare behind k_generic_cluster + k_refine_clusters: the emission alone (rare_frame<true>)
+__global__ void __launch_bounds__(1024) k_rare_emit_only(ChainArgs a, RefineConsts rc, uint32_t lds_entries, uint32_t n_parts)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_u[];
+    __shared__ uint32_t s_misc3[3];
+    __shared__ uint32_t s_cnt[RARE_MAX_PARTS + 2];
+    rare_parts<true>(a, rc, lds_entries, n_parts, lds_u, s_misc3, s_cnt);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2984,7 +3018,7 @@ static int sparse_grid_x(const ChainArgs &a, int per_frame_default, const char *
     return (int)gx;
 }
 
-int launch_kernel(int which, const ChainArgs &a, const RefineConsts &rc, void *stream)
+int launch_kernel(int which, const ChainArgs &a, const RefineConsts &rc, void *stream, bool deferred_refine)
 {
     hipStream_t st = (hipStream_t)stream;
     switch (which) {
@@ -3012,7 +3046,9 @@ int launch_kernel(int which, const ChainArgs &a, const RefineConsts &rc, void *s
         // chunks of 64 seeds (17 on the bench's frames) instead of 48 workgroups per frame of which 31 find nothing to do
         // (72 -> 68 us, tools/env_sweep.py)
         dim3 grid((unsigned)sparse_grid_x(a, 16, "AGX_G_FLOOD") * (unsigned)a.n_frames), block(64);  // slot-major, see frame_slot
-        if (a.dbg & 16384) {  // phase timeline (tools/flood_phases.py)
+        if (deferred_refine) {  // the cluster table only: k_refine_clusters refines it
+            hipLaunchKernelGGL((k_flood_refine<false, NoClock, false>), grid, block, 0, st, a, rc);
+        } else if (a.dbg & 16384) {  // phase timeline (tools/flood_phases.py)
             if ((a.W & 3) == 0) hipLaunchKernelGGL((k_flood_refine<true, PhaseClock>), grid, block, 0, st, a, rc);
             else hipLaunchKernelGGL((k_flood_refine<false, PhaseClock>), grid, block, 0, st, a, rc);
         } else if ((a.W & 3) == 0) {
@@ -3030,7 +3066,8 @@ int launch_kernel(int which, const ChainArgs &a, const RefineConsts &rc, void *s
         const int forced = env_int("AGX_RARE_PARTS", 0);
         if (forced >= 1 && forced <= (int)RARE_MAX_PARTS) parts = (uint32_t)forced;
         dim3 grid((unsigned)a.n_frames * parts), block(1024);
-        hipLaunchKernelGGL(k_rare, grid, block, lds, st, a, rc, (uint32_t)(lds / 8), parts);
+        if (deferred_refine) hipLaunchKernelGGL(k_rare_emit_only, grid, block, lds, st, a, rc, (uint32_t)(lds / 8), parts);
+        else hipLaunchKernelGGL(k_rare, grid, block, lds, st, a, rc, (uint32_t)(lds / 8), parts);
         return hipGetLastError();
     }
     case K_SPARSE: {
@@ -3054,6 +3091,7 @@ int launch_kernel(int which, const ChainArgs &a, const RefineConsts &rc, void *s
 int init_device_kernels()
 {
     hipError_t e = hipFuncSetAttribute((const void *)k_rare, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rare_emit_only, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_sparse_frame<true, NoClock>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_sparse_frame<false, NoClock>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_sparse_frame<true, PhaseClock>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
@@ -3492,14 +3530,52 @@ int launch_refine_points(const RefinePointsArgs &p, const RefineConsts &rc, int 
 // ------------------------------------------------------------------------------------------
 constexpr int REFINE_PATCH_LANES = 16, REFINE_PATCH_POINTS = 64 / REFINE_PATCH_LANES;
 
+// The point body of k_refine_patch and k_refine_clusters: steps 1 .. 3 above for the four points of a one-wave workgroup, ONE
+// statement of the arithmetic for both kernels.  Point g (lanes l = 0 .. 15) has its window's first float at `win` (rows `pitch`
+// floats apart) if `inside`, else it reads nothing; behind the call prm[g][0 .. 5] hold its six parameter sums.  All 64 lanes
+// call it together: it contains three workgroup barriers, the last one behind the sums.
+template <int HALF>
+struct RefinePatchLds {
+    static constexpr int KS = 2 * HALF + 1, N = KS * KS, WIN = 4 * HALF + 1, NWIN = WIN * WIN;
+    static constexpr int WIN_STRIDE = (NWIN + 31) / 32 * 32 + 16, SMOOTH_STRIDE = (N + 31) / 32 * 32 + 16;
+    float win[REFINE_PATCH_POINTS][WIN_STRIDE];
+    float smooth[REFINE_PATCH_POINTS][SMOOTH_STRIDE];
+    float prm[REFINE_PATCH_POINTS][8];
+};
+template <int HALF>
+__device__ __forceinline__ void refine_patch_body(RefinePatchLds<HALF> &s, uint32_t g, uint32_t l, bool inside, const float *win,
+                                                  size_t pitch, const RefinePatchConsts *__restrict__ rc)
+{
+    constexpr int KS = RefinePatchLds<HALF>::KS, N = RefinePatchLds<HALF>::N, WIN = RefinePatchLds<HALF>::WIN, NWIN = RefinePatchLds<HALF>::NWIN;
+    if (inside) {
+        for (int e = (int)l; e < NWIN; e += REFINE_PATCH_LANES) s.win[g][e] = win[(size_t)(e / WIN) * pitch + (e % WIN)];
+    }
+    __syncthreads();
+    if (inside) {
+        for (int o = (int)l; o < N; o += REFINE_PATCH_LANES) {
+            const float *w = &s.win[g][(o / KS) * WIN + (o % KS)];
+            float sum = 0.0f;
+#pragma unroll
+            for (int pr = 0; pr < KS; ++pr)
+#pragma unroll
+                for (int pc = 0; pc < KS; ++pc) sum = sum + w[pr * WIN + pc] * rc->cone[pr * KS + pc];
+            s.smooth[g][o] = sum;
+        }
+    }
+    __syncthreads();
+    if (inside && l < 6) {
+        float sum = 0.0f;
+#pragma unroll 9
+        for (int q = 0; q < N; ++q) sum = sum + rc->pmat[q * 6 + (int)l] * s.smooth[g][q];
+        s.prm[g][l] = sum;
+    }
+    __syncthreads();
+}
+
 template <int HALF>
 __global__ void __launch_bounds__(64) k_refine_patch(RefinePointsArgs p, const RefinePatchConsts *__restrict__ rc)
 {
-    constexpr int KS = 2 * HALF + 1, N = KS * KS, WIN = 4 * HALF + 1, NWIN = WIN * WIN;
-    constexpr int WIN_STRIDE = (NWIN + 31) / 32 * 32 + 16, SMOOTH_STRIDE = (N + 31) / 32 * 32 + 16;
-    __shared__ float s_win[REFINE_PATCH_POINTS][WIN_STRIDE];
-    __shared__ float s_smooth[REFINE_PATCH_POINTS][SMOOTH_STRIDE];
-    __shared__ float s_prm[REFINE_PATCH_POINTS][8];
+    __shared__ RefinePatchLds<HALF> s;
     const uint32_t g = threadIdx.x / REFINE_PATCH_LANES, l = threadIdx.x % REFINE_PATCH_LANES;
     const uint32_t f = blockIdx.y, i = blockIdx.x * REFINE_PATCH_POINTS + g;
     uint32_t n = p.points_per_frame;
@@ -3515,35 +3591,14 @@ __global__ void __launch_bounds__(64) k_refine_patch(RefinePointsArgs p, const R
         inside = rxf >= (float)(2 * HALF) && ryf >= (float)(2 * HALF) && rxf <= 1073741824.0f && ryf <= 1073741824.0f;
         if (inside) inside = (int)ryf + 2 * HALF < p.H && (int)rxf + 2 * HALF < p.W;
     }
-    if (inside) {
-        const float *win = p.img + (size_t)f * (size_t)p.frame_stride + (size_t)((int)ryf - 2 * HALF) * (size_t)p.pitch + ((int)rxf - 2 * HALF);
-        for (int e = (int)l; e < NWIN; e += REFINE_PATCH_LANES) s_win[g][e] = win[(size_t)(e / WIN) * (size_t)p.pitch + (e % WIN)];
-    }
-    __syncthreads();
-    if (inside) {
-        for (int o = (int)l; o < N; o += REFINE_PATCH_LANES) {
-            const float *w = &s_win[g][(o / KS) * WIN + (o % KS)];
-            float sum = 0.0f;
-#pragma unroll
-            for (int pr = 0; pr < KS; ++pr)
-#pragma unroll
-                for (int pc = 0; pc < KS; ++pc) sum = sum + w[pr * WIN + pc] * rc->cone[pr * KS + pc];
-            s_smooth[g][o] = sum;
-        }
-    }
-    __syncthreads();
-    if (inside && l < 6) {
-        float sum = 0.0f;
-#pragma unroll 9
-        for (int q = 0; q < N; ++q) sum = sum + rc->pmat[q * 6 + (int)l] * s_smooth[g][q];
-        s_prm[g][l] = sum;
-    }
-    __syncthreads();
+    const float *win = p.img;
+    if (inside) win = p.img + (size_t)f * (size_t)p.frame_stride + (size_t)((int)ryf - 2 * HALF) * (size_t)p.pitch + ((int)rxf - 2 * HALF);
+    refine_patch_body<HALF>(s, g, l, inside, win, (size_t)p.pitch, rc);
     if (!live || l != 0) return;
     float rec[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     uint32_t st = POINT_OUTSIDE;
     if (inside) {
-        const float prm[6] = {s_prm[g][0], s_prm[g][1], s_prm[g][2], s_prm[g][3], s_prm[g][4], s_prm[g][5]};
+        const float prm[6] = {s.prm[g][0], s.prm[g][1], s.prm[g][2], s.prm[g][3], s.prm[g][4], s.prm[g][5]};
         st = refine_tail(prm, rxf, ryf, rec);
     }
 #pragma unroll
@@ -3561,6 +3616,110 @@ int launch_refine_patch(const RefinePointsArgs &p, const RefinePatchConsts *cons
     case 2: hipLaunchKernelGGL((k_refine_patch<2>), grid, block, 0, s, p, consts); break;
     case 3: hipLaunchKernelGGL((k_refine_patch<3>), grid, block, 0, s, p, consts); break;
     case 4: hipLaunchKernelGGL((k_refine_patch<4>), grid, block, 0, s, p, consts); break;
+    default: return (int)hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// The chain's refinement as launches of their own (launch_kernel's deferred_refine): behind k_verify_seeds and the flood stage that
+// only clusters (k_flood_refine<.., false>) run
+//   k_generic_cluster      frames with a component beyond the flood windows (or all, under force_generic): generic_frame, one
+//                          workgroup per frame; every other frame's workgroup leaves at once
+//   k_refine_clusters<H>   rochade_refine at half_size_patch H of every frame's cluster table on its blur plane
+//   k_rare_emit_only       the emission alone
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(1024) k_generic_cluster(ChainArgs a)
+{
+    const int frame = (int)blockIdx.x;
+    FrameCounters &ctr = a.ctr[frame];
+    if (!frame_is_generic(a, ctr)) return;  // (workgroup-uniform: the flags are final since the flood launch ended)
+    generic_frame(a, frame);
+    if (threadIdx.x == 0) {  // nothing has been refined yet on this plan; the emission must not see a stale list whatever ran before
+        __hip_atomic_store(&ctr.n_refined, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&ctr.max_k_bits, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    phase_barrier();
+    // the records' integer sums -> the f32 centroid, as the flood stage leaves it (AGX_DBG_CENTERS, k_refine_clusters)
+    const uint32_t n = min(__hip_atomic_load(&ctr.n_clusters, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), a.cap_roots);
+    const size_t cbase = (size_t)frame * a.cap_roots;
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+        float cx, cy;
+        cluster_centroid(&ctr.flags, a.clu_cnt[cbase + i], a.clu_sx[cbase + i], a.clu_sy[cbase + i], cx, cy);
+        a.clu_sx[cbase + i] = __float_as_uint(cx);
+        a.clu_sy[cbase + i] = __float_as_uint(cy);
+    }
+}
+
+// One-wave workgroups, a fixed number per frame (slot-major grid, see frame_slot); a workgroup takes four clusters a round --
+// sixteen lanes to a cluster, refine_patch_body -- and loops over the frame's table with a trip count that is the same for all
+// its lanes: no lane leaves before the last barrier of its last round.  A cluster whose window leaves the frame reads no pixel
+// and appends nothing; a cluster whose fit passes appends its record to the frame's refined list as RecSinkGlobal does (the
+// emission sorts by key: the order of the appends is free).  Frames whose seed or cluster list overflowed are void and skipped.
+template <int HALF>
+__global__ void __launch_bounds__(64) k_refine_clusters(ChainArgs a, const RefinePatchConsts *__restrict__ consts)
+{
+    __shared__ RefinePatchLds<HALF> s;
+    const FrameSlot fs = frame_slot(a.n_frames, true);  // latest-written blur planes first (cache)
+    const int frame = fs.frame;
+    FrameCounters &ctr = a.ctr[frame];
+    const uint32_t g = threadIdx.x / REFINE_PATCH_LANES, l = threadIdx.x % REFINE_PATCH_LANES;
+    uint32_t flags0 = ctr.flags, n0 = ctr.n_clusters;  // (final: written by earlier launches)
+    if (flags0 & (FLAG_CAND_OVERFLOW | FLAG_ROOT_OVERFLOW)) return;  // workgroup-uniform
+    const uint32_t n = min(n0, a.cap_roots);
+    const size_t cbase = (size_t)frame * a.cap_roots;
+    const float *img = a.blur + (size_t)frame * (size_t)a.plane;
+    const RefinePatchConsts *rc = consts + (HALF - 1);
+    const RecSinkGlobal sink{&ctr.n_refined, &ctr.max_k_bits, &ctr.flags};
+    for (uint32_t base = fs.slot * REFINE_PATCH_POINTS; base < n; base += fs.n_slots * REFINE_PATCH_POINTS) {  // workgroup-uniform trip count
+        const uint32_t i = base + g;
+        const bool live = i < n;
+        float rxf = 0.0f, ryf = 0.0f;
+        bool inside = false;
+        if (live) {
+            rxf = roundf(__uint_as_float(a.clu_sx[cbase + i]));
+            ryf = roundf(__uint_as_float(a.clu_sy[cbase + i]));
+            // :266-274 in float, as k_refine_patch decides it (a centroid lies inside the frame; NaN -- a corrupted table -- fails)
+            inside = rxf >= (float)(2 * HALF) && ryf >= (float)(2 * HALF) && rxf <= 1073741824.0f && ryf <= 1073741824.0f;
+            if (inside) inside = (int)ryf + 2 * HALF < a.H && (int)rxf + 2 * HALF < a.W;
+        }
+        const float *win = img;
+        if (inside) win = img + (size_t)((int)ryf - 2 * HALF) * (size_t)a.W + ((int)rxf - 2 * HALF);
+        refine_patch_body<HALF>(s, g, l, inside, win, (size_t)a.W, rc);
+        if (inside && l == 0) {
+            const float prm[6] = {s.prm[g][0], s.prm[g][1], s.prm[g][2], s.prm[g][3], s.prm[g][4], s.prm[g][5]};
+            float rec[5];
+            if (refine_tail(prm, rxf, ryf, rec) == POINT_REFINED) {
+                const uint32_t o = atomicAdd(sink.n_refined, 1u);
+                if (o < a.cap_roots) {  // (o < n_clusters <= cap_roots always here; the bound keeps the store inside the list regardless)
+                    const uint32_t f6[6] = {a.clu_key[cbase + i],    __float_as_uint(rec[0]), __float_as_uint(rec[1]),
+                                            __float_as_uint(rec[2]), __float_as_uint(rec[3]), __float_as_uint(rec[4])};
+                    sink.put(a, frame, o, f6);
+                    atomicMax(sink.max_k_bits, __float_as_uint(rec[2]));
+                }
+            }
+        }
+        // (the next round's first LDS write of a region comes behind a barrier that follows this round's last read of it)
+    }
+}
+
+int launch_generic_cluster(const ChainArgs &a, void *stream)
+{
+    hipLaunchKernelGGL(k_generic_cluster, dim3((unsigned)a.n_frames), dim3(1024), 0, (hipStream_t)stream, a);
+    return hipGetLastError();
+}
+
+int launch_refine_clusters(const ChainArgs &a, const RefinePatchConsts *consts, int half, void *stream)
+{
+    if (!consts) return (int)hipErrorInvalidValue;
+    // workgroups per frame as the flood stage's: the table's length is not known to the host
+    const dim3 grid((unsigned)sparse_grid_x(a, 16, "AGX_G_REFINE") * (unsigned)a.n_frames), block(64);  // slot-major, see frame_slot
+    hipStream_t s = (hipStream_t)stream;
+    switch (half) {
+    case 1: hipLaunchKernelGGL((k_refine_clusters<1>), grid, block, 0, s, a, consts); break;
+    case 2: hipLaunchKernelGGL((k_refine_clusters<2>), grid, block, 0, s, a, consts); break;
+    case 3: hipLaunchKernelGGL((k_refine_clusters<3>), grid, block, 0, s, a, consts); break;
+    case 4: hipLaunchKernelGGL((k_refine_clusters<4>), grid, block, 0, s, a, consts); break;
     default: return (int)hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -403,6 +403,32 @@ void harvest_events(agx_detector *d)
     d->pending_events.clear();
 }
 
+// The handle's device table of RefinePatchConsts (all four half sizes), uploaded on the handle's stream by the first batch that
+// needs it.  While the stream is being captured nothing can be allocated or uploaded: a captured batch needs one eager batch
+// that used the table first.
+int ensure_patch_consts(agx_detector *det, const RefinePatchConsts **table)
+{
+    *table = nullptr;
+    if (!det->patch_consts_uploaded) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        (void)hipStreamIsCapturing(det->stream, &cap);
+        if (cap == hipStreamCaptureStatusActive)
+            return fail(det, AGX_ERR_STATE, "the refine constants are not on the device yet: run one eager batch at this half_size_patch before capturing");
+    }
+    const RefinePatchConsts *d_consts =
+        static_cast<const RefinePatchConsts *>(side_ensure(det, SB_REFINE_CONSTS, REFINE_PATCH_MAX_HALF * sizeof(RefinePatchConsts), 0));
+    if (!d_consts) return fail(det, AGX_ERR_HIP, "hipMalloc: refine constants");
+    if (!det->patch_consts_uploaded) {
+        det->patch_consts.resize(REFINE_PATCH_MAX_HALF);
+        for (int h = 1; h <= REFINE_PATCH_MAX_HALF; ++h) make_refine_patch_consts(h, det->patch_consts[h - 1]);
+        HIP_TRY(det, hipMemcpyAsync(const_cast<RefinePatchConsts *>(d_consts), det->patch_consts.data(),
+                                    REFINE_PATCH_MAX_HALF * sizeof(RefinePatchConsts), hipMemcpyHostToDevice, det->stream));
+        det->patch_consts_uploaded = true;
+    }
+    *table = d_consts;
+    return AGX_OK;
+}
+
 // The chain's front at a blur sigma other than 1.5, for the frames of `a` on `st`: k_gauss_blur into the workspace blur plane and,
 // with_response, k_response_front -- the frame minima, the candidate mask and cand_max, which K1 otherwise hands to the sparse
 // stages.  Neither launch is among the AGX_N_KERNELS that agx_profile_* times.
@@ -473,7 +499,17 @@ int enqueue_chunk(agx_detector *d, int f0, int nf, hipStream_t st)
     // 33 .. 75 us per frame of the verify stage inside k_sparse_frame) and flood + refine + emission share one (path 3)
     const int cus = d->n_cus > 0 ? d->n_cus : 256, nearly = cus - cus / 4;  // (MI355X: 256 CUs, 192)
     if (path == 0) path = (nf >= nearly && (nf % cus == 0 || nf % cus >= nearly)) ? 3 : 1;
-    const bool fused = (path == 2 || path == 3) && !(a.dbg & sparse_dbg);
+    // agx_detector_set_half_size_patch: at 2 the flood stages refine as they always did; every other size (and 2 under
+    // "chain_refine_general") runs as launches of its own -- the flood stage only clusters, then k_generic_cluster,
+    // k_refine_clusters and the emission-only k_rare (chain_kernels.h: launch_refine_clusters)
+    const bool deferred = d->half_size_patch != 2 || d->chain_refine_general;
+    const int chain_half = d->half_size_patch;
+    const RefinePatchConsts *patch_consts = nullptr;
+    if (deferred) {
+        if (const int rc = ensure_patch_consts(d, &patch_consts)) return rc;
+    }
+    d->last_chain_refine = deferred ? 1 : 0;
+    const bool fused = (path == 2 || path == 3) && !(a.dbg & sparse_dbg) && !deferred;
     d->last_sparse_frame = fused;
     d->last_sparse_path = fused ? path : 1;
     a.sparse_after_verify = fused && path == 3;
@@ -492,12 +528,18 @@ int enqueue_chunk(agx_detector *d, int f0, int nf, hipStream_t st)
         EventPair ev{nullptr, nullptr, k};
         // (an event pair costs the stream two ~5 us gaps around the kernel: level 1 can sample)
         const bool timed = d->profiling >= 2 || (d->profiling == 1 && k == d->prof_kernel && d->prof_batches % (uint64_t)d->prof_stride == (uint64_t)d->prof_stride - 1);  // the last of each group: never the first batch after an idle stream
+        if (deferred && k == K_RARE) {  // between the flood stage and the emission; like the any-sigma front, not among the timed entries
+            hipError_t e = (hipError_t)launch_generic_cluster(a, st);
+            if (e != hipSuccess) return fail(d, AGX_ERR_HIP, std::string("launch k_generic_cluster: ") + hipGetErrorString(e));
+            e = (hipError_t)launch_refine_clusters(a, patch_consts, chain_half, st);
+            if (e != hipSuccess) return fail(d, AGX_ERR_HIP, std::string("launch k_refine_clusters: ") + hipGetErrorString(e));
+        }
         if (timed) {
             ev.a = get_event(d);
             ev.b = get_event(d);
             HIP_TRY(d, hipEventRecord(ev.a, st));
         }
-        hipError_t e = (hipError_t)launch_kernel(k, a, d->rc, st);
+        hipError_t e = (hipError_t)launch_kernel(k, a, d->rc, st, deferred);
         if (e != hipSuccess)
             return fail(d, AGX_ERR_HIP, std::string("launch ") + kKernelNames[k] + ": " + hipGetErrorString(e));
         if (timed) {
@@ -812,6 +854,25 @@ int agx_detector_get_blur_sigma(const agx_detector *det, float *sigma)
     });
 }
 
+int agx_detector_set_half_size_patch(agx_detector *det, int half_size_patch)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    if (half_size_patch < 1 || half_size_patch > REFINE_PATCH_MAX_HALF) return fail(det, AGX_ERR_ARG, "half_size_patch must be in 1 .. 4");
+    det->half_size_patch = half_size_patch;  // (read by the next enqueue: a batch in flight keeps what it was enqueued with)
+    return AGX_OK;
+    });
+}
+
+int agx_detector_get_half_size_patch(const agx_detector *det, int *half_size_patch)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det || !half_size_patch) return AGX_ERR_ARG;
+    *half_size_patch = det->half_size_patch;
+    return AGX_OK;
+    });
+}
+
 int agx_detector_set_stream(agx_detector *det, void *hip_stream, int external)
 {
     return agx_guard(det, [&]() -> int {
@@ -834,6 +895,7 @@ int agx_detector_set_option(agx_detector *det, const char *name, int value)
     else if (!std::strcmp(name, "debug_ablation")) det->dbg = value;  // timing only, results invalid
     else if (!std::strcmp(name, "store_response")) det->store_resp = value != 0;
     else if (!std::strcmp(name, "refine_general_kernel")) det->refine_general_kernel = value != 0;  // tests, measurement: same results
+    else if (!std::strcmp(name, "chain_refine_general")) det->chain_refine_general = value != 0;    // tests, measurement: same results
     else if (!std::strcmp(name, "profile_stride")) det->prof_stride = value > 1 ? value : 1;
     else if (!std::strcmp(name, "profile_kernel")) det->prof_kernel = value >= 0 && value < K_COUNT ? value : K_BLUR_HESSIAN;
     else if (!std::strcmp(name, "device_tail")) {  // 1 on (refused where libm differs), 0 off, -1 back to the default (on where possible)
@@ -885,6 +947,8 @@ int agx_detector_get_option(const agx_detector *det, const char *name, int *valu
     else if (!std::strcmp(name, "last_sparse_path")) *value = det->last_sparse_path;
     else if (!std::strcmp(name, "last_chain_front")) *value = det->last_chain_front;
     else if (!std::strcmp(name, "refine_general_kernel")) *value = det->refine_general_kernel;
+    else if (!std::strcmp(name, "chain_refine_general")) *value = det->chain_refine_general;
+    else if (!std::strcmp(name, "last_chain_refine")) *value = det->last_chain_refine;  // (of the last chain batch: 0 inside the flood stages, 1 k_refine_clusters)
     else if (!std::strcmp(name, "last_refine_kernel")) *value = det->last_refine_kernel;  // (of the last refine batch: 0 k_refine_points, 1 k_refine_patch)
     else if (!std::strcmp(name, "k1_segments")) *value = a.n_segs;
     else if (!std::strcmp(name, "k1_strips")) *value = a.n_strips;
@@ -1153,15 +1217,7 @@ static int refine_points_enqueue_impl(agx_detector *det, const void *d_frames, i
     const bool general = half != 2 || det->refine_general_kernel;
     const RefinePatchConsts *d_consts = nullptr;
     if (general) {
-        d_consts = static_cast<const RefinePatchConsts *>(side_ensure(det, SB_REFINE_CONSTS, REFINE_PATCH_MAX_HALF * sizeof(RefinePatchConsts), 0));
-        if (!d_consts) return fail(det, AGX_ERR_HIP, "hipMalloc: refine constants");
-        if (!det->patch_consts_uploaded) {
-            det->patch_consts.resize(REFINE_PATCH_MAX_HALF);
-            for (int h = 1; h <= REFINE_PATCH_MAX_HALF; ++h) make_refine_patch_consts(h, det->patch_consts[h - 1]);
-            HIP_TRY(det, hipMemcpyAsync(const_cast<RefinePatchConsts *>(d_consts), det->patch_consts.data(),
-                                        REFINE_PATCH_MAX_HALF * sizeof(RefinePatchConsts), hipMemcpyHostToDevice, det->stream));
-            det->patch_consts_uploaded = true;
-        }
+        if (const int rc = ensure_patch_consts(det, &d_consts)) return rc;
         d_consts += half - 1;
     }
     RefinePointsArgs p{};

@@ -148,7 +148,7 @@ enum {
     SB_REFINE_OUT,     // agx_refine_points_enqueue without caller-owned results: [n_frames][points_per_frame] agx_saddle ...
     SB_REFINE_STATUS,  // ... and [n_frames][points_per_frame] uint32 (AGX_POINT_*)
     SB_REFINE_POINTS,  // agx_rochade_refine: the host's points on the device
-    SB_REFINE_CONSTS,  // k_refine_patch: RefinePatchConsts of half_size_patch 1 .. 4, uploaded by the first batch that needs them
+    SB_REFINE_CONSTS,  // k_refine_patch, k_refine_clusters: RefinePatchConsts of half_size_patch 1 .. 4, uploaded by the first batch that needs them
     SB_DECODE_TAGS,    // agx_decode_quads_enqueue without caller-owned results: [n_frames][quads_per_frame] agx_tag ...
     SB_DECODE_STATUS,  // ... [n_frames][quads_per_frame] uint32 (AGX_QUAD_*) ...
     SB_DECODE_BITS,    // ... and [n_frames][quads_per_frame] uint64 (bit_code's value)
@@ -179,6 +179,12 @@ struct agx_detector {
     int front_radius = 3;
     float front_w[2 * agx::GB_MAX_RADIUS + 1]{};
     int last_chain_front = 0;  // option "last_chain_front": the last chain batch ran 0 = K1, 1 = the any-sigma front
+    // agx_detector_set_half_size_patch: rochade_refine's half_size_patch behind every chain entry.  2 refines inside the flood
+    // stages (k_flood_refine, k_sparse_frame, k_rare); every other size, and 2 under option "chain_refine_general", clusters
+    // there and refines by k_refine_clusters (enqueue_chunk)
+    int half_size_patch = 2;
+    int chain_refine_general = 0;  // option "chain_refine_general": half_size_patch 2 takes the deferred refinement too
+    int last_chain_refine = 0;     // option "last_chain_refine": the last chain batch refined 0 = inside the flood stages, 1 = by k_refine_clusters
     uint32_t lim_cand = 0, lim_roots = 0, lim_out = 0;
     int force_generic = 0;
     int k1_rows = 0;

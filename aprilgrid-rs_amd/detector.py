@@ -136,7 +136,7 @@ class TagDetector:
     """aprilgrid::detector::TagDetector on one MI355X (one handle = one device + stream;
     use one instance per thread)."""
 
-    def __init__(self, tag_family, optional_detector_params=None, device=0, blur_sigma=None):
+    def __init__(self, tag_family, optional_detector_params=None, device=0, blur_sigma=None, half_size_patch=None):
         self._lib = _ffi.lib()
         self._h = C.c_void_p()
         self._saddle_buf = None  # refined_saddle_points' output buffer: (array [cap][5] f32, its address, count word)
@@ -155,15 +155,17 @@ class TagDetector:
         self._refine = None  # refine_points_enqueue's batch: (n, points per frame, tensors kept alive, device outputs or None)
         self._decode = None  # decode_quads_enqueue's batch: (n, quads per frame, tensors kept alive, device outputs or None)
         self._find = None    # find_boards_enqueue's batch: (n, quads per frame, tensors kept alive, device outputs or None)
-        if blur_sigma is not None:
-            try:
+        try:
+            if blur_sigma is not None:
                 self.set_blur_sigma(blur_sigma)
-            except AgxError:
-                self.close()
-                raise
+            if half_size_patch is not None:
+                self.set_half_size_patch(half_size_patch)
+        except AgxError:
+            self.close()
+            raise
 
-    new = classmethod(lambda cls, tag_family, optional_detector_params=None, device=0, blur_sigma=None:
-                      cls(tag_family, optional_detector_params, device, blur_sigma))
+    new = classmethod(lambda cls, tag_family, optional_detector_params=None, device=0, blur_sigma=None, half_size_patch=None:
+                      cls(tag_family, optional_detector_params, device, blur_sigma, half_size_patch))
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -353,6 +355,22 @@ class TagDetector:
     @blur_sigma.setter
     def blur_sigma(self, sigma):
         self.set_blur_sigma(sigma)
+
+    def set_half_size_patch(self, half_size_patch):
+        """rochade_refine's half_size_patch inside the chain from the next enqueue on (the reference hard-codes 2, the default):
+        1 .. 4.  Every entry that runs the chain on this detector follows it; refine_points / rochade_refine do not (they
+        refine at 2, or at their own half_size_patch argument)."""
+        self._check(self._lib.agx_detector_set_half_size_patch(self._h, int(half_size_patch)))
+
+    @property
+    def half_size_patch(self):
+        v = C.c_int(0)
+        self._check(self._lib.agx_detector_get_half_size_patch(self._h, C.byref(v)))
+        return v.value
+
+    @half_size_patch.setter
+    def half_size_patch(self, half_size_patch):
+        self.set_half_size_patch(half_size_patch)
 
     def set_option(self, name, value):
         self._check(self._lib.agx_detector_set_option(self._h, name.encode(), int(value)))

@@ -159,6 +159,8 @@ extern "C" {
     pub fn agx_detector_get_option(det: *const agx_detector, name: *const c_char, value: *mut c_int) -> c_int;
     pub fn agx_detector_set_blur_sigma(det: *mut agx_detector, sigma: c_float) -> c_int;
     pub fn agx_detector_get_blur_sigma(det: *const agx_detector, sigma: *mut c_float) -> c_int;
+    pub fn agx_detector_set_half_size_patch(det: *mut agx_detector, half_size_patch: c_int) -> c_int;
+    pub fn agx_detector_get_half_size_patch(det: *const agx_detector, half_size_patch: *mut c_int) -> c_int;
     pub fn agx_detector_set_stream(det: *mut agx_detector, hip_stream: *mut c_void, external: c_int) -> c_int;
     pub fn agx_detector_sync(det: *mut agx_detector) -> c_int;
     pub fn agx_detector_constants(det: *const agx_detector, blur_w7: *mut c_float, cone25: *mut c_float, pmat150: *mut c_float) -> c_int;

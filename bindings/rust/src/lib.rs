@@ -122,6 +122,7 @@ pub struct TagDetector {
     params: ffi::agx_params,
     device: c_int,
     blur_sigma: Option<f32>,
+    half_size_patch: Option<i32>,
 }
 
 impl TagDetector {
@@ -144,6 +145,7 @@ impl TagDetector {
                 max_num_of_boards: p.max_num_of_boards,
             },
             blur_sigma: None,
+            half_size_patch: None,
         }
     }
 
@@ -152,6 +154,17 @@ impl TagDetector {
     /// failed creation.  Handles that already exist are dropped, so the value holds from the next call on.
     pub fn with_blur_sigma(mut self, sigma: f32) -> TagDetector {
         self.blur_sigma = Some(sigma);
+        for h in self.pool.get_mut().unwrap().drain(..) {
+            unsafe { ffi::agx_detector_destroy(h.0) };
+        }
+        self
+    }
+
+    /// rochade_refine's half_size_patch inside the chain (the reference hard-codes 2 at src/detector.rs:430, the default):
+    /// 1 ..= 4.  Applied like `with_blur_sigma`: to every pooled handle when it is created, a refused value panics there, and
+    /// handles that already exist are dropped.
+    pub fn with_half_size_patch(mut self, half_size_patch: i32) -> TagDetector {
+        self.half_size_patch = Some(half_size_patch);
         for h in self.pool.get_mut().unwrap().drain(..) {
             unsafe { ffi::agx_detector_destroy(h.0) };
         }
@@ -167,6 +180,10 @@ impl TagDetector {
             if let Some(sigma) = self.blur_sigma {
                 let st = unsafe { ffi::agx_detector_set_blur_sigma(h, sigma) };
                 assert_eq!(st, ffi::AGX_OK, "agx_detector_set_blur_sigma({}) failed: {} ({})", sigma, st, last_error(h));
+            }
+            if let Some(half) = self.half_size_patch {
+                let st = unsafe { ffi::agx_detector_set_half_size_patch(h, half) };
+                assert_eq!(st, ffi::AGX_OK, "agx_detector_set_half_size_patch({}) failed: {} ({})", half, st, last_error(h));
             }
             Handle(h)
         });

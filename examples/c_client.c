@@ -2,9 +2,10 @@
  * does, without Python or torch in the process.  Build:
  *   gcc -std=c99 -Iinclude examples/c_client.c -Laprilgrid-rs_amd -laprilgrid_amd \
  *       -Wl,-rpath,$PWD/aprilgrid-rs_amd -o c_client
- * Usage: c_client [--sigma S] <raw L8 file> <width> <height> [n_frames]   (prints saddle and tag counts of the first frame;
+ * Usage: c_client [--sigma S] [--half N] <raw L8 file> <width> <height> [n_frames]   (prints saddle and tag counts of the first frame;
  *        with n_frames > 1 the file holds that many frames back to back and every frame also goes through agx_detect_batch;
- *        --sigma: the chain's blur sigma, agx_detector_set_blur_sigma -- default 1.5, the reference's)
+ *        --sigma: the chain's blur sigma, agx_detector_set_blur_sigma -- default 1.5, the reference's;
+ *        --half: the chain's half_size_patch, agx_detector_set_half_size_patch, 1 .. 4 -- default 2, the reference's)
  * Mirrors: TagDetector::new(&TagFamily::T36H11, None) -> refined_saddle_points / detect. */
 #include "aprilgrid_amd.h"
 
@@ -17,14 +18,20 @@ int main(int argc, char **argv)
     const char *prog = argv[0];
     int have_sigma = 0;
     float sigma = 1.5f;
-    if (argc >= 3 && !strcmp(argv[1], "--sigma")) {
-        have_sigma = 1;
-        sigma = (float)atof(argv[2]);
+    int have_half = 0, half = 2;
+    while (argc >= 3 && (!strcmp(argv[1], "--sigma") || !strcmp(argv[1], "--half"))) {
+        if (!strcmp(argv[1], "--sigma")) {
+            have_sigma = 1;
+            sigma = (float)atof(argv[2]);
+        } else {
+            have_half = 1;
+            half = atoi(argv[2]);
+        }
         argv += 2;
         argc -= 2;
     }
     if (argc != 4 && argc != 5) {
-        fprintf(stderr, "usage: %s [--sigma S] <raw L8 file> <width> <height> [n_frames]\n", prog);
+        fprintf(stderr, "usage: %s [--sigma S] [--half N] <raw L8 file> <width> <height> [n_frames]\n", prog);
         return 2;
     }
     const int w = atoi(argv[2]), h = atoi(argv[3]), n_frames = argc == 5 ? atoi(argv[4]) : 1;
@@ -49,6 +56,10 @@ int main(int argc, char **argv)
     }
     if (have_sigma && (st = agx_detector_set_blur_sigma(det, sigma)) != AGX_OK) {
         fprintf(stderr, "agx_detector_set_blur_sigma(%g): %s (%s)\n", sigma, agx_status_string(st), agx_last_error(det));
+        return 1;
+    }
+    if (have_half && (st = agx_detector_set_half_size_patch(det, half)) != AGX_OK) {
+        fprintf(stderr, "agx_detector_set_half_size_patch(%d): %s (%s)\n", half, agx_status_string(st), agx_last_error(det));
         return 1;
     }
     static agx_saddle saddles[16384];

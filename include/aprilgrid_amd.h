@@ -136,7 +136,13 @@ int agx_detector_set_limits(agx_detector *det, uint32_t max_candidates, uint32_t
  *   "sparse_path"          how a batch's sparse stages (verify, clusters, refinement, emission) are launched: 0 = by batch size
  *                          (default), 1 = three batch-wide launches, 2 = one 1024-thread workgroup per frame for all of it,
  *                          3 = the verify launch, then one workgroup per frame for the rest (what batches that fill the chip
- *                          take by themselves).  Results are identical on every path (tests/test_gpu_sparse_paths.py)
+ *                          take by themselves).  Results are identical on every path (tests/test_gpu_sparse_paths.py).  At a
+ *                          chain half_size_patch other than 2 (agx_detector_set_half_size_patch; 2 under "chain_refine_general")
+ *                          the values 2 and 3 stay accepted, but such a batch runs as launches of its own whatever the option says,
+ *                          and "last_sparse_path" reads 1
+ *   "chain_refine_general" 1 = the chain at half_size_patch 2 refines by the kernel of the other sizes (k_refine_clusters, behind
+ *                          flood stages that only cluster) instead of inside the flood stages; byte-identical lists.  Default 0;
+ *                          the counterpart of "refine_general_kernel", for tests and measurements
  *   "store_response"       1 = the blur kernel also stores the Hessian response it evaluates in
  *                          registers (parity tests: agx_debug_fetch AGX_DBG_RESP); slower
  *   "profile_stride"       with agx_profile_enable(det, 1): time the blur kernel of every n-th batch
@@ -177,7 +183,9 @@ int agx_detector_set_option(agx_detector *det, const char *name, int value);
 /* Read an option back; additionally the tiling the blur kernel used for the last enqueued batch:
  * "k1_rows_per_segment" (effective value), "k1_segments", "k1_strips", "k1_strip_columns", and
  * "last_sparse_path": how the last batch's sparse stages ran: 1 = the three launches, 2 = one workgroup per frame for all
- * of it, 3 = the verify launch, then a workgroup per frame (the values of option "sparse_path"). */
+ * of it, 3 = the verify launch, then a workgroup per frame (the values of option "sparse_path"); and
+ * "last_chain_refine": 0 = the last chain batch refined inside the flood stages (half_size_patch 2), 1 = it ran the deferred
+ * refinement, k_refine_clusters (agx_detector_set_half_size_patch). */
 int agx_detector_get_option(const agx_detector *det, const char *name, int *value);
 
 /* The sigma of the chain's blur (src/detector.rs:410 hard-codes 1.5f, the default here).  Per-handle state; it applies from the
@@ -192,6 +200,22 @@ int agx_detector_get_option(const agx_detector *det, const char *name, int *valu
  * any-sigma front. */
 int agx_detector_set_blur_sigma(agx_detector *det, float sigma);
 int agx_detector_get_blur_sigma(const agx_detector *det, float *sigma);
+
+/* rochade_refine's half_size_patch inside the chain (src/detector.rs:430 hard-codes 2, the default here): the patch that goes
+ * with the blur.  Per-handle state; it applies from the next enqueue on to the entries agx_detector_set_blur_sigma lists --
+ * agx_refined_saddle_points, agx_detect, agx_detect_planes, agx_saddles_batch_enqueue[_to], agx_detect_batch,
+ * agx_detect_batch_enqueue[_to], and a group's ranks through agx_group_detector(group, r) -- EXCEPT the refine-points entries:
+ * agx_refine_points_enqueue and agx_rochade_refine keep refining at 2 whatever this value is, and their _h forms keep taking
+ * their own argument.  Anything outside 1 .. 4 is AGX_ERR_ARG and the stored value stays (so does a NULL det or a NULL out
+ * pointer); a batch in flight is never touched.  At 2 the chain is what it always was: the flood stages refine the clusters they
+ * find.  At 1, 3 and 4 (and at 2 under option "chain_refine_general") the flood stages only cluster, and k_refine_clusters --
+ * sixteen lanes to a cluster, the arithmetic of agx_refine_points_enqueue_h -- refines every frame's cluster table on its blur
+ * plane before the unchanged emission: results are the reference's with `2` replaced (and `1.5` by the handle's sigma), x, y and k
+ * bit for bit (tests/test_gpu_patch.py).  A cluster whose (4h+1) x (4h+1) window leaves the frame gives no saddle, as in the
+ * reference.  HIP graphs: the first such batch uploads the kernel's constants, so a captured batch needs one eager batch at a
+ * half that takes this path first (as it does for the workspace).  Read-only option "last_chain_refine": 0 / 1. */
+int agx_detector_set_half_size_patch(agx_detector *det, int half_size_patch);
+int agx_detector_get_half_size_patch(const agx_detector *det, int *half_size_patch);
 
 /* Stream selection.  external != 0: launch on the caller's stream `hip_stream` (hipStream_t as
  * void*; NULL is HIP's legacy default stream) so that the chain is stream-ordered behind the
@@ -651,7 +675,10 @@ int agx_luma8(const void *pixels, int width, int height, size_t row_stride_bytes
  * AGX_N_KERNELS entries (the chain has four launches since round 3: entries behind the last one
  * carry a NULL name and zeros); ms accumulates since the last reset.  At a blur sigma other than 1.5
  * (agx_detector_set_blur_sigma) the launches of the any-sigma front -- k_gauss_blur, k_response_front -- are NOT timed and entry 0
- * stays as it is; the sparse stages' entries are timed as ever (tools/bench_sigma.py brackets the rest with its own events). */
+ * stays as it is; the sparse stages' entries are timed as ever (tools/bench_sigma.py brackets the rest with its own events).
+ * Likewise at a chain half_size_patch that defers the refinement (agx_detector_set_half_size_patch): k_generic_cluster and
+ * k_refine_clusters are NOT timed, the flood entry then times the clustering alone and the last entry the emission alone
+ * (tools/bench_patch.py brackets the sparse stages with its own events). */
 #define AGX_N_KERNELS 5
 int agx_profile_enable(agx_detector *det, int on); /* 0 off, 1 = the blur kernel only (2 events per batch), 2 = every kernel */
 int agx_profile_reset(agx_detector *det);
