@@ -6,9 +6,10 @@ include/aprilgrid_amd.h.  All compute happens in libaprilgrid_amd.so (hand-writt
 gfx950 plus the C++ host tail); importing this package fails loudly if that library has not
 been built -- there is no CPU fallback.
 """
-from .detector import (DetectorGroup, DetectorParams, Saddle, TagDetector, TagFamily, AgxError, SADDLE_DTYPE,
+from .detector import (DetectorGroup, DetectorParams, Saddle, TagDetector, TagFamily, AgxError, SADDLE_DTYPE, CLUSTER_DTYPE,
                        blur_weights, build_library, decode_quads_tail, find_board_tail, library_path,
-                       refine_constants)
+                       refine_constants, filter_saddles)
 
-__all__ = ["DetectorGroup", "DetectorParams", "Saddle", "TagDetector", "TagFamily", "AgxError", "SADDLE_DTYPE",
-           "blur_weights", "build_library", "decode_quads_tail", "find_board_tail", "library_path", "refine_constants"]
+__all__ = ["DetectorGroup", "DetectorParams", "Saddle", "TagDetector", "TagFamily", "AgxError", "SADDLE_DTYPE", "CLUSTER_DTYPE",
+           "blur_weights", "build_library", "decode_quads_tail", "find_board_tail", "library_path", "refine_constants",
+           "filter_saddles"]

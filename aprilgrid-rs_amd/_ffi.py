@@ -23,6 +23,9 @@ AGX_REFINE_BLURRED, AGX_REFINE_PLANE = 0, 1
 AGX_QUAD_DECODED, AGX_QUAD_OUTSIDE, AGX_QUAD_LOW_CONTRAST, AGX_QUAD_AMBIGUOUS, AGX_QUAD_NO_MATCH, AGX_QUAD_SKIPPED = 0, 1, 2, 3, 4, 5
 # try_find_best_board of caller-given saddle lists (src/detector.rs:588-639): what became of a frame
 AGX_BOARD_FOUND, AGX_BOARD_NONE, AGX_BOARD_CAPACITY, AGX_BOARD_INPUT, AGX_BOARD_PENDING = 0, 1, 2, 3, 4
+# cluster centres of caller-given response planes (src/detector.rs:414-429): what became of a frame; INEXACT is a flag OR'd in
+AGX_CLUSTERS_OK, AGX_CLUSTERS_CAPACITY, AGX_CLUSTERS_BORDER, AGX_CLUSTERS_OVERFLOW, AGX_CLUSTERS_INEXACT = 0, 1, 2, 3, 0x100
+AGX_POINT_FILTERED = 4  # the k / phi filter (src/detector.rs:432-445) removed a refined point
 AGX_DBG_BLUR, AGX_DBG_RESP, AGX_DBG_MIN, AGX_DBG_CENTERS, AGX_DBG_REFINED = 0, 1, 2, 3, 4
 AGX_N_KERNELS = 5
 
@@ -108,6 +111,11 @@ SYMBOLS = {
                                      C.c_size_t]),
     "agx_gaussian_blur_f32": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_float, _P]),
     "agx_hessian_response": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, _P]),
+    "agx_clusters_enqueue": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32, _P, _P, _P, _P]),
+    "agx_clusters_fetch": (C.c_int, [_P, _P, _P, _P, _P]),
+    "agx_cluster_centers": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "agx_filter_saddles_enqueue": (C.c_int, [_P, _P, _P, C.c_int, C.c_uint32, _P]),
+    "agx_filter_saddles_tail": (C.c_int, [C.POINTER(Params), _P, _P, C.c_uint32]),
     "agx_group_create": (C.c_int, [C.c_int, C.POINTER(Params), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "agx_group_destroy": (None, [_P]),
     "agx_group_size": (C.c_int, [_P]),

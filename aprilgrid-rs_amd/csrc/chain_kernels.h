@@ -57,6 +57,7 @@ enum : uint32_t {
     FLAG_CENTROID_INEXACT = 8u,  // a cluster's coordinate sum reached 2^24 (f32 sums of the
                                  // reference would round there)
     FLAG_BIG_CLUSTER = 16u,      // a component left the flood windows: frame redone generically
+    FLAG_RING_BELOW = 32u,       // k_plane_front (agx_clusters_enqueue): a pixel of the outermost ring is below the threshold
     FLAG_LARGE_RESULT = 64u      // more than 1024 refined records: emitted by k_rare's large-list sort
 };
 
@@ -250,5 +251,44 @@ int launch_hessian_response(const HessianArgs &a, int format, int n_frames, void
 // a.resp_dbg.  Reads of `a`: blur, resp_dbg, ctr, mask, cand_max and their geometry; nothing of K1's tiling.
 // grid (ceil(W / 64), min(ceil(H / 128), 65535), n_frames <= 65535); hipError_t
 int launch_response_front(const ChainArgs &a, void *stream);
+
+// k_plane_front (agx_clusters_enqueue): the front for a caller's response plane -- the products of k_response_front, taken from
+// the plane as it is instead of from a blur plane: a.ctr[frame].min_key_inv = the fold `e < acc ? e : acc` from f32::MAX over all
+// W*H values (detector.rs:414-417; final when the first of its two launches is through), every mask word of the image area
+// (exact: v < 0.05 * min, interior pixels only: no ring bits) and every cand_max block of those words.  A ring pixel below the
+// threshold raises FLAG_RING_BELOW of the frame (frames with an interior).  Reads of `a`: ctr, mask, cand_max and their geometry,
+// W, H, n_frames.  Only the W floats of a row are read, each once per launch.
+struct PlaneFrontArgs {
+    const float *src;        // frame f, row y at src + f * frame_stride + y * row_stride
+    long long frame_stride;  // floats
+    long long row_stride;    // floats
+};
+// grid (ceil(W / 64), min(ceil(H / 128), 65535), n_frames <= 65535); hipError_t
+int launch_plane_front(const ChainArgs &a, const PlaneFrontArgs &p, void *stream);
+
+// k_emit_clusters (agx_clusters_enqueue): the cluster table the cluster-only sparse stages leave per frame (clu_key, clu_cnt and
+// the f32 centroid bits in clu_sx / clu_sy, ctr.n_clusters, ctr.flags) -> the caller's rows in the order of clu_key, one
+// 1024-thread workgroup per frame.  Status values are AGX_CLUSTERS_* of include/aprilgrid_amd.h.
+constexpr uint32_t EMIT_CLUSTERS_MAX = 16384;  // rows per frame: the keys are ordered in 64 KB of LDS
+struct EmitClustersArgs {
+    uint32_t per_frame;  // clusters_per_frame, 1 .. EMIT_CLUSTERS_MAX
+    uint32_t *rows;      // [n_frames][per_frame][4]: first_index, size, cx, cy (agx_cluster_info)
+    float *points;       // [n_frames][per_frame][2]: cx, cy (agx_point), or null
+    uint32_t *counts;    // [n_frames]
+    uint32_t *status;    // [n_frames]
+};
+int launch_emit_clusters(const ChainArgs &a, const EmitClustersArgs &e, void *stream);
+
+// k_filter_saddles (agx_filter_saddles_enqueue): the k / phi filter (detector.rs:432-445) of every frame's refined slots, one
+// wave per frame: status words that are 0 (AGX_POINT_REFINED) become `filtered` where the record fails.
+struct FilterSaddlesArgs {
+    const float *records;  // [n_frames][per_frame][5]: x, y, k, theta, phi
+    uint32_t *status;      // [n_frames][per_frame]
+    const uint32_t *counts;  // [n_frames] (capped at per_frame), or null: per_frame each
+    uint32_t per_frame;
+    float min_angle, max_angle;
+    uint32_t filtered;     // AGX_POINT_FILTERED
+};
+int launch_filter_saddles(const FilterSaddlesArgs &f, int n_frames, void *stream);
 
 }  // namespace agx

@@ -3965,4 +3965,194 @@ int launch_response_front(const ChainArgs &a, void *stream)
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// agx_clusters_enqueue: cluster centres of a caller-given response plane (detector.rs:414-429 on the plane as it is).
+// k_plane_front is k_response_front without the Hessian: the same two launches hand the same three products -- the frame
+// minimum, the exact transposed candidate mask, cand_max below the threshold -- to the unchanged cluster-only sparse stages
+// (k_verify_seeds, k_flood_refine<.., false>, k_generic_cluster), none of which reads a blur plane then.
+//   MASK = false  the fold `e < acc ? e : acc` over ALL W * H values, started at f32::MAX (a NaN never wins), reduced over the
+//                 wave by DPP, one atomicMax of ~order_key per wave (every wave publishes: the word is never left at its
+//                 cleared value);
+//   MASK = true   v < 0.05 * min, the expression k_verify_seeds uses: every mask word of the image area, interior pixels only
+//                 -- the sparse stages rely on ring bits being clear (retest_word) --, and per 4-column x 32-row block the
+//                 largest admitted value (-inf where none).  A ring pixel below the threshold is where the reference's flood
+//                 would leave the interior its seeds come from: the frame is flagged (FLAG_RING_BELOW) and refused by the
+//                 emission instead of being clustered differently.  A frame without an interior has no seeds and no flag.
+// Lane = column, a wave owns 64 columns x one word row; one coalesced load per pixel through the caller's strides, nothing
+// outside the W floats of a row is read.
+// ------------------------------------------------------------------------------------------
+template <bool MASK>
+__global__ void __launch_bounds__(256) k_plane_front(ChainArgs a, PlaneFrontArgs p)
+{
+    const int W = a.W, H = a.H, lane = (int)threadIdx.x, n_yb = (H + 31) >> 5;
+    const int frame = (int)blockIdx.z, x = (int)blockIdx.x * 64 + lane;
+    const bool col = x < W, col_ring = x == 0 || x == W - 1;
+    const float *src = p.src + (size_t)frame * (size_t)p.frame_stride + (size_t)(col ? x : 0);
+    FrameCounters &ctr = a.ctr[frame];
+    float thr = 0.0f;
+    if (MASK) thr = f32_from_order_key(~ctr.min_key_inv) * 0.05f;  // detector.rs:418; final: the minimum launch is through
+    float run_min = 3.40282346638528859812e+38f;  // f32::MAX, detector.rs:417
+    bool ring_below = false;
+    for (int yb = (int)blockIdx.y * 4 + (int)threadIdx.y; yb < n_yb; yb += (int)gridDim.y * 4) {  // wave-uniform
+        const int y0 = yb * 32;
+        uint32_t word = 0u;
+        float cmax = -__builtin_inff();
+#pragma unroll 8
+        for (int b = 0; b < 32; ++b) {
+            const int y = y0 + b;
+            if (col && y < H) {
+                const float v = src[(size_t)y * (size_t)p.row_stride];
+                if (MASK) {
+                    if (v < thr) {
+                        if (col_ring || y == 0 || y == H - 1) {
+                            ring_below = true;
+                        } else {
+                            word |= 1u << b;
+                            cmax = fmaxf(cmax, v);
+                        }
+                    }
+                } else {
+                    run_min = v < run_min ? v : run_min;
+                }
+            }
+        }
+        if (MASK) {
+            // the block's maximum: lanes 4k .. 4k + 3 (quad_perm [1,0,3,2], then [2,3,0,1]; every lane has a source)
+            cmax = fmaxf(cmax, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cmax), 0xB1, 0xf, 0xf, false)));
+            cmax = fmaxf(cmax, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cmax), 0x4E, 0xf, 0xf, false)));
+            if (col) {
+                a.mask[(size_t)frame * (size_t)a.mask_plane + (size_t)yb * (size_t)a.mask_wpr + (size_t)(MASK_PAD_X + x)] = word;
+                if ((lane & 3) == 0)
+                    a.cand_max[((size_t)frame * (size_t)a.mask_yb + (size_t)yb) * (size_t)(a.mask_wpr >> 2) + (size_t)((MASK_PAD_X + x) >> 2)] = cmax;
+            }
+        }
+    }
+    if (MASK) {
+        const bool any_ring = __ballot(ring_below) != 0ull;
+        if (any_ring && lane == 0 && W >= 3 && H >= 3) atomicOr(&ctr.flags, FLAG_RING_BELOW);
+    } else {
+        run_min = wave_min_f32(run_min);
+        if (lane == 0) atomicMax(&ctr.min_key_inv, ~f32_order_key(run_min));
+    }
+}
+
+int launch_plane_front(const ChainArgs &a, const PlaneFrontArgs &p, void *stream)
+{
+    if (a.n_frames <= 0 || a.n_frames > 65535 || a.W < 2 || a.H < 2 || !p.src || p.row_stride < a.W) return (int)hipErrorInvalidValue;
+    const int n_yb = (a.H + 31) >> 5;
+    const dim3 grid((unsigned)((a.W + 63) / 64), (unsigned)std::min((n_yb + 3) / 4, 65535), (unsigned)a.n_frames), block(64, 4);
+    hipLaunchKernelGGL((k_plane_front<false>), grid, block, 0, (hipStream_t)stream, a, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((k_plane_front<true>), grid, block, 0, (hipStream_t)stream, a, p);
+    return hipGetLastError();
+}
+
+// The ordered emission of a frame's cluster table by one workgroup.  The table's records are final (first pixel, size, f32
+// centroid formed by cluster_centroid in the flood stage / k_generic_cluster); the reference lists a cluster where its raster
+// scan first meets it, which is the table's key, and all keys of a frame differ: the keys are sorted in LDS (bitonic, padded to
+// a power of two with 0xffffffff) and every record finds its row by binary search.  What a frame's status is -- border,
+// overflow, capacity -- is decided from the counters before any row is written; such a frame writes no row.
+enum : uint32_t { CLUSTERS_OK = 0u, CLUSTERS_CAPACITY = 1u, CLUSTERS_BORDER = 2u, CLUSTERS_OVERFLOW = 3u, CLUSTERS_INEXACT = 0x100u };  // AGX_CLUSTERS_*
+__global__ void __launch_bounds__(1024) k_emit_clusters(ChainArgs a, EmitClustersArgs e)
+{
+    extern __shared__ uint32_t ec_keys[];
+    const int frame = (int)blockIdx.x;
+    const FrameCounters &ctr = a.ctr[frame];
+    const uint32_t t = threadIdx.x, T = blockDim.x;
+    const uint32_t flags = ctr.flags, n = ctr.n_clusters;  // (final: written by earlier launches; workgroup-uniform)
+    uint32_t status = CLUSTERS_OK, count = n;
+    if (flags & FLAG_RING_BELOW) status = CLUSTERS_BORDER, count = 0u;
+    else if (flags & (FLAG_CAND_OVERFLOW | FLAG_ROOT_OVERFLOW)) status = CLUSTERS_OVERFLOW, count = 0u;
+    else if (n > e.per_frame) status = CLUSTERS_CAPACITY;
+    const bool rows = status == CLUSTERS_OK;
+    if ((status == CLUSTERS_OK || status == CLUSTERS_CAPACITY) && (flags & FLAG_CENTROID_INEXACT)) status |= CLUSTERS_INEXACT;
+    if (t == 0) {
+        e.counts[frame] = count;
+        e.status[frame] = status;
+    }
+    if (!rows || n == 0u) return;  // (n <= per_frame <= EMIT_CLUSTERS_MAX and, with no overflow flag, n <= cap_roots from here on)
+    const size_t cbase = (size_t)frame * a.cap_roots;
+    uint32_t P = 1u;
+    while (P < n) P <<= 1;
+    for (uint32_t i = t; i < P; i += T) ec_keys[i] = i < n ? a.clu_key[cbase + i] : 0xffffffffu;
+    __syncthreads();
+    for (uint32_t k = 2u; k <= P; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0u; j >>= 1) {
+            for (uint32_t i = t; i < P; i += T) {
+                const uint32_t l = i ^ j;
+                if (l > i) {
+                    const uint32_t u = ec_keys[i], v = ec_keys[l];
+                    if (((i & k) == 0u) == (u > v)) {
+                        ec_keys[i] = v;
+                        ec_keys[l] = u;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    const size_t obase = (size_t)frame * e.per_frame;
+    for (uint32_t i = t; i < n; i += T) {
+        const uint32_t key = a.clu_key[cbase + i];
+        uint32_t lo = 0u, hi = n;  // the first sorted key >= key: the record's row
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (ec_keys[mid] < key) lo = mid + 1u;
+            else hi = mid;
+        }
+        if (lo >= n) continue;  // (cannot happen: the key is in the list; the bound keeps the store inside the frame's rows)
+        const uint32_t cx = a.clu_sx[cbase + i], cy = a.clu_sy[cbase + i];  // f32 bits (detector.rs:427)
+        uint32_t *row = e.rows + (obase + lo) * 4;
+        row[0] = key;
+        row[1] = a.clu_cnt[cbase + i];
+        row[2] = cx;
+        row[3] = cy;
+        if (e.points) {
+            e.points[(obase + lo) * 2] = __uint_as_float(cx);
+            e.points[(obase + lo) * 2 + 1] = __uint_as_float(cy);
+        }
+    }
+}
+
+int launch_emit_clusters(const ChainArgs &a, const EmitClustersArgs &e, void *stream)
+{
+    if (a.n_frames <= 0 || !e.per_frame || e.per_frame > EMIT_CLUSTERS_MAX || !e.rows || !e.counts || !e.status) return (int)hipErrorInvalidValue;
+    uint32_t P = 1u;
+    while (P < e.per_frame) P <<= 1;
+    hipLaunchKernelGGL(k_emit_clusters, dim3((unsigned)a.n_frames), dim3(1024), (size_t)P * sizeof(uint32_t), (hipStream_t)stream, a, e);
+    return hipGetLastError();
+}
+
+// The k / phi filter (detector.rs:432-445) over the records of agx_refine_points_enqueue, one wave per frame: the largest k of
+// the frame's refined slots (the f32::MIN-started max fold; a NaN never wins, as f32::max has it), then the rewrite of the
+// status words of the refined slots that fail.  A frame with no refined slot (:432-434) changes nothing.
+__global__ void __launch_bounds__(64) k_filter_saddles(FilterSaddlesArgs f)
+{
+    const uint32_t frame = blockIdx.x, lane = threadIdx.x;
+    const uint32_t n = f.counts ? min(f.counts[frame], f.per_frame) : f.per_frame;
+    const size_t s0 = (size_t)frame * f.per_frame;
+    float max_k = -3.40282346638528859812e+38f;  // f32::MIN
+    bool any = false;
+    for (uint32_t i = lane; i < n; i += 64u)
+        if (f.status[s0 + i] == POINT_REFINED) {
+            max_k = fmaxf(max_k, f.records[(s0 + i) * 5 + 2]);
+            any = true;
+        }
+    if (!__ballot(any)) return;  // wave-uniform
+    max_k = -wave_min_f32(-max_k);
+    const float s_max_k = max_k / 10.0f;  // detector.rs:436
+    for (uint32_t i = lane; i < n; i += 64u)
+        if (f.status[s0 + i] == POINT_REFINED) {
+            const float k = f.records[(s0 + i) * 5 + 2], phi = f.records[(s0 + i) * 5 + 4];
+            if (!(k >= s_max_k && phi >= f.min_angle && phi <= f.max_angle)) f.status[s0 + i] = f.filtered;
+        }
+}
+
+int launch_filter_saddles(const FilterSaddlesArgs &f, int n_frames, void *stream)
+{
+    if (n_frames <= 0 || !f.records || !f.status || !f.per_frame) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_filter_saddles, dim3((unsigned)n_frames), dim3(64), 0, (hipStream_t)stream, f);
+    return hipGetLastError();
+}
+
 }  // namespace agx

@@ -35,7 +35,8 @@ static const struct { const char *enqueue, *fetch; } kBatchPair[BATCH_KINDS] = {
     {"agx_detect_batch_enqueue", "agx_detect_batch_fetch"},
     {"agx_refine_points_enqueue", "agx_refine_points_fetch"},
     {"agx_decode_quads_enqueue", "agx_decode_quads_fetch"},
-    {"agx_find_boards_enqueue", "agx_find_boards_fetch"}};
+    {"agx_find_boards_enqueue", "agx_find_boards_fetch"},
+    {"agx_clusters_enqueue", "agx_clusters_fetch"}};
 
 int agx::refuse_other_batch(agx_detector *det, int wanted)
 {
@@ -394,13 +395,44 @@ void harvest_events(agx_detector *d)
     for (EventPair &p : d->pending_events) {
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
-            d->prof_ms[p.kernel] += ms;
-            d->prof_launches[p.kernel] += 1;
+            if (p.kernel >= K_COUNT) {
+                d->last_extra_us[p.kernel - K_COUNT] = (int)std::lround(1000.0 * ms);
+            } else {
+                d->prof_ms[p.kernel] += ms;
+                d->prof_launches[p.kernel] += 1;
+            }
         }
         d->free_events.push_back(p.a);
         d->free_events.push_back(p.b);
     }
     d->pending_events.clear();
+}
+
+// Profiling level 2 around a launch that is not among agx_profile_read's entries (XT_*): an event in front of it and one behind
+// it on `st`, harvested like the others.  Nothing is recorded into a stream that is being captured.
+EventPair extra_timer_begin(agx_detector *d, hipStream_t st, int which)
+{
+    EventPair ev{nullptr, nullptr, K_COUNT + which};
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (d->profiling < 2 || hipStreamIsCapturing(st, &cap) != hipSuccess || cap == hipStreamCaptureStatusActive) return ev;
+    ev.a = get_event(d);
+    ev.b = get_event(d);
+    if (!ev.a || !ev.b || hipEventRecord(ev.a, st) != hipSuccess) {
+        if (ev.a) d->free_events.push_back(ev.a);
+        if (ev.b) d->free_events.push_back(ev.b);
+        ev.a = ev.b = nullptr;
+    }
+    return ev;
+}
+void extra_timer_end(agx_detector *d, hipStream_t st, const EventPair &ev)
+{
+    if (!ev.a) return;
+    if (hipEventRecord(ev.b, st) == hipSuccess) {
+        d->pending_events.push_back(ev);
+    } else {
+        d->free_events.push_back(ev.a);
+        d->free_events.push_back(ev.b);
+    }
 }
 
 // The handle's device table of RefinePatchConsts (all four half sizes), uploaded on the handle's stream by the first batch that
@@ -453,7 +485,9 @@ int enqueue_any_sigma_front(agx_detector *d, const ChainArgs &a, hipStream_t st,
     hipError_t e = (hipError_t)launch_gauss_blur(g, a.fmt, a.n_frames, st);
     if (e != hipSuccess) return fail(d, AGX_ERR_HIP, std::string("launch k_gauss_blur: ") + hipGetErrorString(e));
     if (!with_response) return AGX_OK;
+    const EventPair ev = extra_timer_begin(d, st, XT_RESPONSE_FRONT);  // (level 2 only: option "last_response_front_us")
     e = (hipError_t)launch_response_front(a, st);
+    extra_timer_end(d, st, ev);
     if (e != hipSuccess) return fail(d, AGX_ERR_HIP, std::string("launch k_response_front: ") + hipGetErrorString(e));
     return AGX_OK;
 }
@@ -949,6 +983,9 @@ int agx_detector_get_option(const agx_detector *det, const char *name, int *valu
     else if (!std::strcmp(name, "refine_general_kernel")) *value = det->refine_general_kernel;
     else if (!std::strcmp(name, "chain_refine_general")) *value = det->chain_refine_general;
     else if (!std::strcmp(name, "last_chain_refine")) *value = det->last_chain_refine;  // (of the last chain batch: 0 inside the flood stages, 1 k_refine_clusters)
+    else if (!std::strcmp(name, "last_response_front_us")) *value = det->last_extra_us[XT_RESPONSE_FRONT];  // (profiling level 2: of the last batch a fetch, sync or agx_profile_read harvested)
+    else if (!std::strcmp(name, "last_clusters_front_us")) *value = det->last_extra_us[XT_PLANE_FRONT];
+    else if (!std::strcmp(name, "last_clusters_emit_us")) *value = det->last_extra_us[XT_EMIT_CLUSTERS];
     else if (!std::strcmp(name, "last_refine_kernel")) *value = det->last_refine_kernel;  // (of the last refine batch: 0 k_refine_points, 1 k_refine_patch)
     else if (!std::strcmp(name, "k1_segments")) *value = a.n_segs;
     else if (!std::strcmp(name, "k1_strips")) *value = a.n_strips;
@@ -1645,6 +1682,217 @@ int agx_debug_refine_constants(int half_size_patch, float *cone, float *pmat, in
     make_refine_patch_consts(half_size_patch, rc);
     std::memcpy(cone, rc.cone, (size_t)*n_points * sizeof(float));
     std::memcpy(pmat, rc.pmat, (size_t)*n_points * 6 * sizeof(float));
+    return AGX_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- cluster centres of caller-given response planes, the k / phi filter (src/detector.rs:414-429, :432-445; chain_kernels.hip) --
+// The launches of the deferred plan's clustering (enqueue_chunk) behind a front that reads the caller's plane, and an emission of
+// the cluster table instead of a refinement: k_plane_front x 2, k_verify_seeds, k_flood_refine<.., false>, k_generic_cluster,
+// k_emit_clusters.  Nothing of it reads a.blur or a.frames.
+// What the entry refuses, before anything is allocated, uploaded or replaced (`plane` is the batch's planes wherever they lie).
+static int clusters_check_args(agx_detector *det, const float *plane, int n_frames, int width, int height, size_t row_stride_bytes,
+                               size_t frame_stride_bytes, uint32_t clusters_per_frame, const agx_cluster_info *d_clusters,
+                               const void *d_points, const uint32_t *d_counts, const uint32_t *d_status)
+{
+    const bool any = d_clusters || d_counts || d_status, all = d_clusters && d_counts && d_status;
+    if (any != all) return fail(det, AGX_ERR_ARG, "d_clusters, d_counts and d_status: all or none");
+    if (!clusters_per_frame || clusters_per_frame > EMIT_CLUSTERS_MAX) return fail(det, AGX_ERR_ARG, "clusters_per_frame must be in 1 .. 16384");
+    if (((uintptr_t)d_clusters | (uintptr_t)d_points | (uintptr_t)d_counts | (uintptr_t)d_status) & 3)
+        return fail(det, AGX_ERR_ARG, "the result buffers must be 4-byte aligned");
+    return check_frame_batch(det, {plane, n_frames, width, height, row_stride_bytes, frame_stride_bytes, AGX_LF32},
+                             {/*min_side*/ 2, /*lf32*/ true, /*lone_frame_stride*/ true, /*align16*/ false, /*front_rows*/ false});
+}
+
+static int clusters_enqueue_impl(agx_detector *det, const float *d_response, int n_frames, int width, int height, size_t row_stride_bytes,
+                                 size_t frame_stride_bytes, uint32_t clusters_per_frame, agx_cluster_info *d_clusters, void *d_points,
+                                 uint32_t *d_counts, uint32_t *d_status)
+{
+    if (!det) return AGX_ERR_ARG;
+    if (const int rc = clusters_check_args(det, d_response, n_frames, width, height, row_stride_bytes, frame_stride_bytes, clusters_per_frame,
+                                           d_clusters, d_points, d_counts, d_status))
+        return rc;
+    const bool all = d_clusters != nullptr;
+    const size_t slots = (size_t)n_frames * clusters_per_frame;
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);
+    if (const int rc = ensure_workspace(det, n_frames, width, height)) return rc;
+    EmitClustersArgs e{};
+    e.per_frame = clusters_per_frame;
+    if (!all) {
+        if (!side_ensure(det, SB_CLUSTERS_ROWS, slots * sizeof(agx_cluster_info), 0) || !side_ensure(det, SB_CLUSTERS_COUNTS, (size_t)n_frames * 4, 0) ||
+            !side_ensure(det, SB_CLUSTERS_STATUS, (size_t)n_frames * 4, 0) || (!d_points && !side_ensure(det, SB_CLUSTERS_POINTS, slots * sizeof(agx_point), 0)))
+            return fail(det, AGX_ERR_HIP, "hipMalloc: cluster rows");
+        e.rows = det->side[SB_CLUSTERS_ROWS].ptr<uint32_t>();
+        e.counts = det->side[SB_CLUSTERS_COUNTS].ptr<uint32_t>();
+        e.status = det->side[SB_CLUSTERS_STATUS].ptr<uint32_t>();
+        e.points = d_points ? static_cast<float *>(d_points) : det->side[SB_CLUSTERS_POINTS].ptr<float>();
+    } else {
+        e.rows = reinterpret_cast<uint32_t *>(d_clusters);
+        e.counts = d_counts;
+        e.status = d_status;
+        e.points = static_cast<float *>(d_points);
+    }
+    ChainArgs &a = det->args;
+    a.frames = reinterpret_cast<const uint8_t *>(d_response);  // (for the record: no kernel of this batch reads it through `a`)
+    a.frame_stride = (long long)frame_stride_bytes;
+    a.row_stride = (int)row_stride_bytes;
+    a.byte_rows = 0;
+    a.fmt = AGX_LF32;
+    a.W = width;
+    a.H = height;
+    a.n_frames = n_frames;
+    a.plane = (long long)width * height;
+    a.min_angle = det->params.min_saddle_angle;
+    a.max_angle = det->params.max_saddle_angle;
+    a.out = det->d_out_internal;
+    a.out_total_cap = (uint32_t)std::min<size_t>((size_t)n_frames * a.cap_out, 0xffffffffu);
+    a.frame_table = nullptr;
+    det->external_out = false;
+    det->out_in_host = false;
+    a.force_generic = det->force_generic;
+    a.sparse_after_verify = 0;
+    a.dbg = 0;  // (the measurement switches instrument the chain's own batches)
+    a.wave_times = nullptr;
+    a.resp_dbg = nullptr;
+    det->resp_stored = false;
+    // the counters, as enqueue_blur_only: no kernel of this batch clears the other set, so neither is known to be clear afterwards
+    const int p = det->ctr_cur ^ 1;
+    const size_t need = (size_t)n_frames + 1;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(det->stream, &cap);
+    if (cap == hipStreamCaptureStatusActive) {  // (a replayed graph clears its own set every time)
+        HIP_TRY(det, (hipError_t)launch_clear_counters(det->d_ctr[p], need, det->stream));
+    } else if (det->ctr_cleared[p] < need) {
+        HIP_TRY(det, hipMemsetAsync(det->d_ctr[p], 0, need * sizeof(FrameCounters), det->stream));
+    }
+    det->ctr_cleared[0] = det->ctr_cleared[1] = 0;
+    a.ctr = det->d_ctr[p];
+    a.ctr_next = det->d_ctr[p ^ 1];
+    a.total_out = &a.ctr[n_frames].min_key_inv;
+    det->ctr_cur = p;
+    const PlaneFrontArgs front{d_response, (long long)(frame_stride_bytes / 4), (long long)(row_stride_bytes / 4)};
+    // profiling level 2: the two new kernels between events of their own (XT_*; an event pair costs the stream a gap on either
+    // side, so the whole entry is measured with profiling off)
+    const EventPair ev_front = extra_timer_begin(det, det->stream, XT_PLANE_FRONT);
+    hipError_t err = (hipError_t)launch_plane_front(a, front, det->stream);
+    extra_timer_end(det, det->stream, ev_front);
+    if (err != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("launch k_plane_front: ") + hipGetErrorString(err));
+    err = (hipError_t)launch_kernel(K_THRESHOLD, a, det->rc, det->stream, true);
+    if (err != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("launch k_verify_seeds: ") + hipGetErrorString(err));
+    err = (hipError_t)launch_kernel(K_FLOOD_REFINE, a, det->rc, det->stream, true);
+    if (err != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("launch k_flood_refine: ") + hipGetErrorString(err));
+    err = (hipError_t)launch_generic_cluster(a, det->stream);
+    if (err != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("launch k_generic_cluster: ") + hipGetErrorString(err));
+    const EventPair ev_emit = extra_timer_begin(det, det->stream, XT_EMIT_CLUSTERS);
+    err = (hipError_t)launch_emit_clusters(a, e, det->stream);
+    extra_timer_end(det, det->stream, ev_emit);
+    if (err != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("launch k_emit_clusters: ") + hipGetErrorString(err));
+    det->batch = BATCH_CLUSTERS;
+    det->clusters.results = all ? RESULTS_CALLER : RESULTS_HOST;
+    det->clusters.n_frames = n_frames;
+    det->clusters.clusters_per_frame = clusters_per_frame;
+    det->clusters.d_points = all ? nullptr : reinterpret_cast<const agx_point *>(e.points);
+    return AGX_OK;
+}
+
+static int clusters_fetch_impl(agx_detector *det, agx_cluster_info *clusters, void *points, uint32_t *counts, uint32_t *status)
+{
+    if (!det) return AGX_ERR_ARG;
+    if (const int other = refuse_other_batch(det, BATCH_CLUSTERS)) return other;
+    const ClustersPending b = det->clusters;
+    const bool to_host = b.results == RESULTS_HOST;
+    if (to_host && (!clusters || !counts || !status)) return fail(det, AGX_ERR_ARG, "null output");  // (the batch stays in flight)
+    HIP_TRY(det, hipSetDevice(det->device));
+    det->batch = BATCH_NONE;  // resolved by this call, whatever it returns
+    if (to_host) {
+        const size_t F = (size_t)b.n_frames;
+        HIP_TRY(det, hipMemcpyAsync(counts, det->side[SB_CLUSTERS_COUNTS].payload, F * 4, hipMemcpyDeviceToHost, det->stream));
+        HIP_TRY(det, hipMemcpyAsync(status, det->side[SB_CLUSTERS_STATUS].payload, F * 4, hipMemcpyDeviceToHost, det->stream));
+        HIP_TRY(det, hipStreamSynchronize(det->stream));
+        // only the rows the batch wrote reach the caller's arrays; the points come from where this batch wrote them (the
+        // caller's d_points or SB_CLUSTERS_POINTS: the slot may not exist, or be an earlier batch's, when d_points was given)
+        const agx_cluster_info *d_rows = det->side[SB_CLUSTERS_ROWS].ptr<agx_cluster_info>();
+        const agx_point *d_pts = points ? b.d_points : nullptr;
+        for (size_t f = 0; f < F; ++f) {
+            const size_t n = (status[f] & 0xffu) == AGX_CLUSTERS_OK ? std::min(counts[f], b.clusters_per_frame) : 0u, s0 = f * b.clusters_per_frame;
+            if (!n) continue;
+            HIP_TRY(det, hipMemcpyAsync(clusters + s0, d_rows + s0, n * sizeof(agx_cluster_info), hipMemcpyDeviceToHost, det->stream));
+            if (d_pts) HIP_TRY(det, hipMemcpyAsync(static_cast<agx_point *>(points) + s0, d_pts + s0, n * sizeof(agx_point), hipMemcpyDeviceToHost, det->stream));
+        }
+    }
+    HIP_TRY(det, hipStreamSynchronize(det->stream));
+    harvest_events(det);
+    return AGX_OK;
+}
+
+extern "C" {
+
+int agx_clusters_enqueue(agx_detector *det, const float *d_response, int n_frames, int width, int height, size_t row_stride_bytes,
+                         size_t frame_stride_bytes, uint32_t clusters_per_frame, agx_cluster_info *d_clusters, void *d_points,
+                         uint32_t *d_counts, uint32_t *d_status)
+{
+    return agx_guard(det, [&]() -> int {
+    return clusters_enqueue_impl(det, d_response, n_frames, width, height, row_stride_bytes, frame_stride_bytes, clusters_per_frame,
+                                 d_clusters, d_points, d_counts, d_status);
+    });
+}
+
+int agx_clusters_fetch(agx_detector *det, agx_cluster_info *clusters, void *points, uint32_t *counts, uint32_t *status)
+{
+    return agx_guard(det, [&]() -> int { return clusters_fetch_impl(det, clusters, points, counts, status); });
+}
+
+int agx_cluster_centers(agx_detector *det, const float *response, int width, int height, size_t row_stride_bytes, agx_cluster_info *out,
+                        uint32_t cap, uint32_t *n_out, uint32_t *status)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    if (!response || !out || !n_out || !status) return fail(det, AGX_ERR_ARG, "null argument");
+    // the batch's own rules on the host plane, before the upload: whatever they refuse has waited for and uploaded nothing
+    if (const int rc = clusters_check_args(det, response, 1, width, height, row_stride_bytes, row_stride_bytes * (size_t)std::max(height, 0), cap,
+                                           nullptr, nullptr, nullptr, nullptr))
+        return rc;
+    HIP_TRY(det, hipSetDevice(det->device));
+    const size_t pitch = (size_t)width * 4;
+    float *d_plane = static_cast<float *>(side_ensure(det, SB_CLUSTERS_PLANE, pitch * (size_t)height, 0));
+    if (!d_plane) return fail(det, AGX_ERR_HIP, "hipMalloc: response plane");
+    HIP_TRY(det, hipMemcpy2DAsync(d_plane, pitch, response, row_stride_bytes, pitch, (size_t)height, hipMemcpyHostToDevice, det->stream));
+    const int rc = clusters_enqueue_impl(det, d_plane, 1, width, height, pitch, pitch * (size_t)height, cap, nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    return clusters_fetch_impl(det, out, nullptr, n_out, status);
+    });
+}
+
+int agx_filter_saddles_enqueue(agx_detector *det, const agx_saddle *d_records, uint32_t *d_status, int n_frames, uint32_t points_per_frame,
+                               const uint32_t *d_counts)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    if (!d_records || !d_status || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null records, null status or n_frames <= 0");
+    if (!points_per_frame) return fail(det, AGX_ERR_ARG, "points_per_frame must be > 0");
+    if (((uintptr_t)d_records | (uintptr_t)d_status | (uintptr_t)d_counts) & 3) return fail(det, AGX_ERR_ARG, "records, status and counts must be 4-byte aligned");
+    if ((size_t)n_frames * points_per_frame >= ((size_t)1 << 31)) return fail(det, AGX_ERR_ARG, "at most 2^31 - 1 slots per batch");
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // and there is nothing of this one to be fetched
+    const FilterSaddlesArgs f{reinterpret_cast<const float *>(d_records), d_status, d_counts, points_per_frame,
+                              det->params.min_saddle_angle, det->params.max_saddle_angle, (uint32_t)AGX_POINT_FILTERED};
+    hipError_t e = (hipError_t)launch_filter_saddles(f, n_frames, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_filter_saddles: ") + hipGetErrorString(e));
+    return AGX_OK;
+    });
+}
+
+int agx_filter_saddles_tail(const agx_params *params, const agx_saddle *records, uint32_t *status, uint32_t n)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (n && (!records || !status)) return AGX_ERR_ARG;
+    agx_params prm;
+    if (params) prm = *params;
+    else agx_default_params(&prm);
+    filter_saddles(prm, records, status, n);
     return AGX_OK;
     });
 }

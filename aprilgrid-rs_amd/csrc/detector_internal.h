@@ -56,6 +56,7 @@ enum BatchKind {
     BATCH_REFINE,   // RefinePending; nothing of the chain is there to be fetched, even where K1 ran for the blur planes
     BATCH_DECODE,   // DecodePending
     BATCH_FIND,     // FindPending
+    BATCH_CLUSTERS, // ClustersPending; the chain's kernels ran on the workspace, but nothing of the chain is there to be fetched
     BATCH_KINDS
 };
 // where a kind's results are: the fetch copies them out of the handle's side buffers / they are in the caller's device arrays
@@ -100,6 +101,13 @@ struct FindPending {
     float *d_quad_points = nullptr;  // the caller's, SB_FIND_POINTS (RESULTS_HOST without the caller's), or null
 };
 
+struct ClustersPending {
+    int results = 0;  // RESULTS_HOST: in SB_CLUSTERS_ROWS / _POINTS / _COUNTS / _STATUS, or RESULTS_CALLER
+    int n_frames = 0;
+    uint32_t clusters_per_frame = 0;
+    const agx_point *d_points = nullptr;  // RESULTS_HOST: where the batch wrote the points -- the caller's d_points, else SB_CLUSTERS_POINTS
+};
+
 // A batch of equally sized frames in device memory as an entry point was handed it, and what differs between the entry points'
 // checks of one (check_frame_batch)
 struct FrameBatch {
@@ -118,8 +126,11 @@ struct BatchRules {
 
 struct EventPair {
     hipEvent_t a, b;
-    int kernel;
+    int kernel;  // K_* (agx_profile_read's totals), or K_COUNT + XT_* (the time of the last one)
 };
+// Launches outside agx_profile_read's table that profiling level 2 times all the same: the device time of the last one, read
+// back as option "last_response_front_us" / "last_clusters_front_us" / "last_clusters_emit_us" (tools/bench_clusters.py)
+enum { XT_RESPONSE_FRONT, XT_PLANE_FRONT, XT_EMIT_CLUSTERS, XT_COUNT };
 
 // A buffer outside the chain's workspace, device memory or pinned host memory, with the handle's guard bytes in front and
 // behind.  The slot is the only record of it: who needs the buffer asks the slot (side_ensure below grows it).
@@ -160,6 +171,11 @@ enum {
     SB_FIND_SADDLES,   // agx_find_board: the host's list on the device
     SB_PLANES_BLUR,    // agx_planes_enqueue without d_blur: the tight [n_frames][H][W] blur planes the response is taken of
     SB_PLANES_OUT,     // agx_gaussian_blur_f32 / agx_hessian_response: the plane on the device before it is copied down
+    SB_CLUSTERS_ROWS,    // agx_clusters_enqueue without caller-owned results: [n_frames][clusters_per_frame] agx_cluster_info ...
+    SB_CLUSTERS_POINTS,  // ... [n_frames][clusters_per_frame] agx_point (unless the caller gave d_points) ...
+    SB_CLUSTERS_COUNTS,  // ... [n_frames] uint32 ...
+    SB_CLUSTERS_STATUS,  // ... and [n_frames] uint32 (AGX_CLUSTERS_*)
+    SB_CLUSTERS_PLANE,   // agx_cluster_centers: the host's plane on the device
     SB_COUNT
 };
 }  // namespace agx
@@ -275,6 +291,8 @@ struct agx_detector {
     std::vector<uint64_t> decode_host;  // its host staging when per-frame counts were given (bits, tags, statuses, counts)
     agx::FindPending find;              // BATCH_FIND: what agx_find_boards_fetch needs of it
     int last_find_frames = 0, last_find_handed_back = 0;  // of the last agx_find_boards_fetch
+    agx::ClustersPending clusters;      // BATCH_CLUSTERS: what agx_clusters_fetch needs of it
+    int last_extra_us[agx::XT_COUNT]{};  // harvest_events: the XT_* launches' last times (profiling level 2)
 
     std::string last_error;
 };

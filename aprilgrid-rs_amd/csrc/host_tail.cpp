@@ -1430,4 +1430,22 @@ int luma8(const void *pixels, int width, int height, size_t row_stride, int form
     return AGX_OK;
 }
 
+
+void filter_saddles(const agx_params &params, const agx_saddle *records, uint32_t *status, uint32_t n)
+{
+    float max_k = -3.40282346638528859812e+38f;  // f32::MIN; f32::max keeps acc where k is NaN
+    bool any = false;
+    for (uint32_t i = 0; i < n; ++i)
+        if (status[i] == AGX_POINT_REFINED) {
+            if (records[i].k > max_k) max_k = records[i].k;
+            any = true;
+        }
+    if (!any) return;  // :432-434
+    const float s_max_k = max_k / 10.0f;
+    for (uint32_t i = 0; i < n; ++i)
+        if (status[i] == AGX_POINT_REFINED &&
+            !(records[i].k >= s_max_k && records[i].phi >= params.min_saddle_angle && records[i].phi <= params.max_saddle_angle))
+            status[i] = AGX_POINT_FILTERED;
+}
+
 }  // namespace agx

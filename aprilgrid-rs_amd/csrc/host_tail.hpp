@@ -84,4 +84,9 @@ const std::vector<agx_tag> &detect_tail_scratch(const FamilyInfo &fam, int max_n
 // image 0.25.9 to_luma8 (call site detector.rs:507)
 int luma8(const void *pixels, int width, int height, size_t row_stride, int format, uint8_t *out);
 
+// The k / phi filter of refined_saddle_points (detector.rs:432-445) over n records and their status words, in place: the words
+// that are AGX_POINT_REFINED and whose record fails become AGX_POINT_FILTERED (agx_filter_saddles_tail; k_filter_saddles is
+// the device form)
+void filter_saddles(const agx_params &params, const agx_saddle *records, uint32_t *status, uint32_t n);
+
 }  // namespace agx

@@ -30,6 +30,7 @@ from ._ffi import LIB_PATH, build_library
 
 SADDLE_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("k", "f4"), ("theta", "f4"), ("phi", "f4")])
 _CLUSTER_DTYPE = np.dtype([("first_index", "u4"), ("size", "u4"), ("cx", "f4"), ("cy", "f4")])
+CLUSTER_DTYPE = _CLUSTER_DTYPE  # agx_cluster_info
 
 Saddle = namedtuple("Saddle", ["p", "k", "theta", "phi"])  # p = (x, y)
 
@@ -155,6 +156,7 @@ class TagDetector:
         self._refine = None  # refine_points_enqueue's batch: (n, points per frame, tensors kept alive, device outputs or None)
         self._decode = None  # decode_quads_enqueue's batch: (n, quads per frame, tensors kept alive, device outputs or None)
         self._find = None    # find_boards_enqueue's batch: (n, quads per frame, tensors kept alive, device outputs or None)
+        self._clusters = None  # clusters_enqueue's batch: (n, clusters per frame, tensors kept alive, device outputs or None)
         try:
             if blur_sigma is not None:
                 self.set_blur_sigma(blur_sigma)
@@ -896,6 +898,98 @@ class TagDetector:
         self._check(self._lib.agx_hessian_response(self._h, a.ctypes.data, w, h, stride, fmt, out.ctypes.data))
         return out
 
+    # ---- cluster centres of caller-given response planes, the k / phi filter (src/detector.rs:414-429, :432-445) ----
+    def cluster_centers(self, resp, cap=16384):
+        """src/detector.rs:414-429 on an HxW float32 response plane in host memory: the frame minimum, thr = 0.05 * min,
+        init_saddle_clusters and the centroid map -> (rows CLUSTER_DTYPE (first_index, size, cx, cy) in the reference's order,
+        status AGX_CLUSTERS_*, count).  A plane with a pixel of its outermost ring below thr is refused (AGX_CLUSTERS_BORDER, no
+        rows); more than `cap` clusters is AGX_CLUSTERS_CAPACITY with the true count and no rows."""
+        a = np.asarray(resp)
+        if a.dtype != np.float32 or a.ndim != 2 or a.strides[1] != 4 or a.strides[0] < 4 * a.shape[1]:
+            a = np.ascontiguousarray(resp, np.float32)
+        if a.ndim != 2:
+            raise AgxError(_ffi.AGX_ERR_ARG, "resp must be an HxW float32 plane")
+        h, w = a.shape
+        out = np.zeros(int(cap), _CLUSTER_DTYPE)
+        n, status = C.c_uint32(0), C.c_uint32(0)
+        self._batch = self._detect = self._refine = self._decode = self._find = self._clusters = None
+        self._check(self._lib.agx_cluster_centers(self._h, a.ctypes.data, w, h, a.strides[0], out.ctypes.data, int(cap), C.byref(n), C.byref(status)))
+        ok = (status.value & 0xFF) == _ffi.AGX_CLUSTERS_OK
+        return out[:n.value if ok else 0].copy(), status.value, n.value
+
+    def clusters_enqueue(self, response, clusters_per_frame=4096, clusters=None, points=None, counts=None, status=None):
+        """src/detector.rs:414-429 over a batch of response planes on this detector's GPU, stream-ordered behind torch's current
+        stream; returns immediately.  response: float32 device tensor [N,H,W] with contiguous rows (rows and frames may be padded:
+        planes_enqueue's `response`, or any plane of the caller's).  clusters int32 [N,C,4] (first_index, size and the float
+        bits of cx, cy: view it as CLUSTER_DTYPE on the host), counts int32 [N] and status int32 [N]: device-resident results
+        (all or none; C = clusters_per_frame without them); points float32 [N,C,2] optionally -- with counts it is
+        refine_points_enqueue's points / counts as it stands."""
+        import torch
+        if not (getattr(response, "is_cuda", False) and response.dtype == torch.float32 and response.dim() == 3 and response.stride(2) == 1):
+            raise AgxError(_ffi.AGX_ERR_ARG, "response must be a float32 device tensor [N, H, W] with contiguous rows")
+        n, h, w = (int(v) for v in response.shape)
+        dev = response.device
+
+        def tensor(t, dtype, shape, what):
+            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == shape and t.device == dev):
+                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s tensor %s on the planes' device" % (what, dtype, shape))
+            return t.data_ptr()
+
+        given = [t is not None for t in (clusters, counts, status)]
+        if any(given) != all(given):
+            raise AgxError(_ffi.AGX_ERR_ARG, "clusters, counts and status: all or none")
+        cpf = int(clusters.shape[1]) if clusters is not None and clusters.dim() == 3 else int(clusters_per_frame)
+        p_rows = tensor(clusters, torch.int32, (n, cpf, 4), "clusters") if clusters is not None else None
+        p_counts = tensor(counts, torch.int32, (n,), "counts") if counts is not None else None
+        p_status = tensor(status, torch.int32, (n,), "status") if status is not None else None
+        p_points = tensor(points, torch.float32, (n, cpf, 2), "points") if points is not None else None
+        self._follow_torch_stream(response)
+        self._batch = self._detect = self._refine = self._decode = self._find = self._clusters = None
+        self._check(self._lib.agx_clusters_enqueue(self._h, response.data_ptr(), n, w, h, 4 * response.stride(1), 4 * response.stride(0), cpf,
+                                                   p_rows, p_points, p_counts, p_status))
+        self._clusters = (n, cpf, (response, points), (clusters, points, counts, status) if clusters is not None else None)
+
+    def clusters_fetch(self):
+        """Wait for clusters_enqueue's batch -> (rows [N,C] CLUSTER_DTYPE, points [N,C,2] float32, counts [N] uint32, status [N]
+        uint32 AGX_CLUSTERS_*); slots at or beyond a frame's count read 0xFFFFFFFF / NaN (points given to the enqueue stay on the
+        device: None here).  After clusters_enqueue(clusters=, counts=, status=): those device tensors (clusters, points or None,
+        counts, status), complete."""
+        if getattr(self, "_clusters", None) is None:
+            raise AgxError(_ffi.AGX_ERR_STATE, "no clusters batch enqueued")
+        n, cpf, keep, dev_out = self._clusters
+        self._batch = self._detect = self._refine = self._decode = self._find = self._clusters = None
+        if dev_out is not None:
+            self._check(self._lib.agx_clusters_fetch(self._h, None, None, None, None))
+            return dev_out
+        rows = np.full((n, cpf, 4), 0xFFFFFFFF, np.uint32).view(_CLUSTER_DTYPE).reshape(n, cpf)
+        pts = np.full((n, cpf, 2), np.nan, np.float32) if keep[1] is None else None
+        counts = np.zeros(n, np.uint32)
+        status = np.zeros(n, np.uint32)
+        self._check(self._lib.agx_clusters_fetch(self._h, rows.ctypes.data, pts.ctypes.data if pts is not None else None, counts.ctypes.data,
+                                                 status.ctypes.data))
+        return rows, pts, counts, status
+
+    def filter_saddles_enqueue(self, records, status, counts=None):
+        """The k / phi filter of refined_saddle_points (src/detector.rs:432-445) on refine_points_enqueue's device tensors, in
+        place and stream-ordered behind torch's current stream: records float32 [N,P,5], status int32 [N,P], counts int32 [N]
+        (optional).  Refined slots (status 0) that fail k >= max_k / 10 or min_saddle_angle <= phi <= max_saddle_angle get
+        AGX_POINT_FILTERED; status then serves as find_boards_enqueue's point_status.  Nothing to fetch."""
+        import torch
+        if not (getattr(records, "is_cuda", False) and records.is_contiguous() and records.dtype == torch.float32 and records.dim() == 3
+                and records.shape[2] == 5):
+            raise AgxError(_ffi.AGX_ERR_ARG, "records must be a contiguous float32 device tensor [N, P, 5]")
+        n, ppf = int(records.shape[0]), int(records.shape[1])
+        for t, shape, what in ((status, (n, ppf), "status"), (counts, (n,), "counts")):
+            if t is not None and not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == torch.int32 and tuple(t.shape) == shape
+                                      and t.device == records.device):
+                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous int32 tensor %s on the records' device" % (what, shape))
+        if status is None:
+            raise AgxError(_ffi.AGX_ERR_ARG, "status must be given")
+        self._follow_torch_stream(records)
+        self._batch = self._detect = self._refine = self._decode = self._find = self._clusters = None
+        self._check(self._lib.agx_filter_saddles_enqueue(self._h, records.data_ptr(), status.data_ptr(), n, ppf,
+                                                         counts.data_ptr() if counts is not None else None))
+
     # ---- measurement / parity hooks ------------------------------------------------------
     def profile_enable(self, level=2):
         """0/False off, 1 = time the blur kernel only, 2/True = time every kernel."""
@@ -981,6 +1075,25 @@ def refine_constants(half_size_patch):
     if st != _ffi.AGX_OK:
         raise AgxError(st, "half_size_patch %r" % (half_size_patch,))
     return cone[: n.value].copy(), pmat[: n.value * 6].reshape(n.value, 6).copy()
+
+
+def filter_saddles(records, status, optional_detector_params=None):
+    """The host's k / phi filter (src/detector.rs:432-445) without a device: records a SADDLE_DTYPE array (or [n, 5] float32) and
+    their status words [n] (AGX_POINT_*) -> a copy of status in which the refined records that refined_saddle_points drops read
+    AGX_POINT_FILTERED -- what TagDetector.filter_saddles_enqueue leaves on the device."""
+    a = np.asarray(records)
+    if a.dtype == SADDLE_DTYPE:
+        a = np.ascontiguousarray(a).view(np.float32)
+    a = np.ascontiguousarray(a, np.float32).reshape(-1, 5)
+    st = np.array(status, np.uint32).reshape(-1)
+    if st.shape[0] != a.shape[0]:
+        raise AgxError(_ffi.AGX_ERR_ARG, "one status word per record")
+    prm = optional_detector_params._c() if optional_detector_params is not None else None
+    rc = _ffi.lib().agx_filter_saddles_tail(C.byref(prm) if prm is not None else None, a.ctypes.data if len(a) else None,
+                                            st.ctypes.data if len(a) else None, a.shape[0])
+    if rc != _ffi.AGX_OK:
+        raise AgxError(rc)
+    return st
 
 
 def decode_quads_tail(tag_family, luma8, quads, with_bits=False):

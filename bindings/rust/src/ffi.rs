@@ -129,6 +129,14 @@ pub const AGX_BOARD_NONE: c_int = 1;
 pub const AGX_BOARD_CAPACITY: c_int = 2;
 pub const AGX_BOARD_INPUT: c_int = 3;
 pub const AGX_BOARD_PENDING: c_int = 4;
+// cluster centres of caller-given response planes (reference src/detector.rs:414-429): what became of a frame
+pub const AGX_CLUSTERS_OK: c_int = 0;
+pub const AGX_CLUSTERS_CAPACITY: c_int = 1;
+pub const AGX_CLUSTERS_BORDER: c_int = 2;
+pub const AGX_CLUSTERS_OVERFLOW: c_int = 3;
+pub const AGX_CLUSTERS_INEXACT: c_int = 256;
+// the k / phi filter (reference src/detector.rs:432-445): the status of a refined point it removes
+pub const AGX_POINT_FILTERED: c_int = 4;
 // agx_debug_fetch items
 pub const AGX_DBG_BLUR: c_int = 0;
 pub const AGX_DBG_RESP: c_int = 1;
@@ -238,6 +246,16 @@ extern "C" {
                                  format: c_int, sigma: c_float, out: *mut c_float) -> c_int;
     pub fn agx_hessian_response(det: *mut agx_detector, pixels: *const c_void, width: c_int, height: c_int, row_stride_bytes: usize,
                                 format: c_int, out: *mut c_float) -> c_int;
+    pub fn agx_clusters_enqueue(det: *mut agx_detector, d_response: *const c_float, n_frames: c_int, width: c_int, height: c_int,
+                                row_stride_bytes: usize, frame_stride_bytes: usize, clusters_per_frame: u32, d_clusters: *mut agx_cluster_info,
+                                d_points: *mut c_void, d_counts: *mut u32, d_status: *mut u32) -> c_int;
+    pub fn agx_clusters_fetch(det: *mut agx_detector, clusters: *mut agx_cluster_info, points: *mut c_void, counts: *mut u32,
+                              status: *mut u32) -> c_int;
+    pub fn agx_cluster_centers(det: *mut agx_detector, response: *const c_float, width: c_int, height: c_int, row_stride_bytes: usize,
+                               out: *mut agx_cluster_info, cap: u32, n_out: *mut u32, status: *mut u32) -> c_int;
+    pub fn agx_filter_saddles_enqueue(det: *mut agx_detector, d_records: *const agx_saddle, d_status: *mut u32, n_frames: c_int,
+                                      points_per_frame: u32, d_counts: *const u32) -> c_int;
+    pub fn agx_filter_saddles_tail(params: *const agx_params, records: *const agx_saddle, status: *mut u32, n: u32) -> c_int;
     pub fn agx_debug_blur_weights(sigma: c_float, weights: *mut c_float, cap: c_int, radius: *mut c_int) -> c_int;
     pub fn agx_debug_refine_constants(half_size_patch: c_int, cone: *mut c_float, pmat: *mut c_float, cap_points: c_int,
                                       n_points: *mut c_int) -> c_int;

@@ -302,6 +302,25 @@ impl TagDetector {
         GrayImagef32::from_raw(w, h, out).unwrap()
     }
 
+    /// reference src/detector.rs:414-429 on a response plane of the caller's: the frame minimum, the threshold `0.05 * min`,
+    /// `init_saddle_clusters` and the centroid map.  `Some(centres)` in the reference's order; `None` where the plane is refused
+    /// (a pixel of its outermost ring is below the threshold, AGX_CLUSTERS_BORDER) or holds more than 16384 clusters.
+    pub fn cluster_centers(&self, response: &GrayImagef32) -> Option<Vec<(f32, f32)>> {
+        let (w, h) = (response.width(), response.height());
+        let cap = 16384u32;
+        let mut rows: Vec<ffi::agx_cluster_info> = Vec::with_capacity(cap as usize);
+        let (mut n, mut status) = (0u32, 0u32);
+        let st = self.with_handle(|d| unsafe {
+            ffi::agx_cluster_centers(d, response.as_raw().as_ptr(), w as c_int, h as c_int, 4 * w as usize, rows.as_mut_ptr(), cap, &mut n, &mut status)
+        });
+        assert_eq!(st, ffi::AGX_OK, "agx_cluster_centers failed: {}", st);
+        if (status & 0xff) as c_int != ffi::AGX_CLUSTERS_OK {
+            return None;
+        }
+        unsafe { rows.set_len(n as usize) };
+        Some(rows.iter().map(|c| (c.cx, c.cy)).collect())
+    }
+
     /// reference src/detector.rs:448-476, `try_decode_quad(&self, img, quad)` for every quad of `quads` (the crate's pub fns
     /// `decode_positions`, `bit_code`, `best_tag` and the corner rotation of :467-470), on `img.to_luma8()`; the board search is
     /// not run.  `Some((id, corners))` where the reference returns `Some`, in input order.

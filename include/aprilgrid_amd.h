@@ -185,7 +185,11 @@ int agx_detector_set_option(agx_detector *det, const char *name, int value);
  * "last_sparse_path": how the last batch's sparse stages ran: 1 = the three launches, 2 = one workgroup per frame for all
  * of it, 3 = the verify launch, then a workgroup per frame (the values of option "sparse_path"); and
  * "last_chain_refine": 0 = the last chain batch refined inside the flood stages (half_size_patch 2), 1 = it ran the deferred
- * refinement, k_refine_clusters (agx_detector_set_half_size_patch). */
+ * refinement, k_refine_clusters (agx_detector_set_half_size_patch); and, with agx_profile_enable(det, 2),
+ * "last_clusters_front_us" / "last_clusters_emit_us": the device time of k_plane_front's two launches and of k_emit_clusters of the
+ * last agx_clusters_enqueue batch, and "last_response_front_us": that of k_response_front's two launches of the last chain batch
+ * at a sigma other than 1.5 -- each as of the last fetch, agx_detector_sync or agx_profile_read behind that batch (microseconds;
+ * tools/bench_clusters.py). */
 int agx_detector_get_option(const agx_detector *det, const char *name, int *value);
 
 /* The sigma of the chain's blur (src/detector.rs:410 hard-codes 1.5f, the default here).  Per-handle state; it applies from the
@@ -584,6 +588,75 @@ int agx_gaussian_blur_f32(agx_detector *det, const void *pixels, int width, int 
 int agx_hessian_response(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes,
                          int format, float *out);
 
+/* ---- cluster centres of caller-given response planes, and the k / phi filter ----------------- */
+
+typedef struct agx_cluster_info {
+    uint32_t first_index, size;
+    float cx, cy;
+} agx_cluster_info;
+
+/* src/detector.rs:414-429 on ANY response plane -- agx_planes_enqueue's d_response, or a caller's own (another derivative, a
+ * masked plane, one combined from several exposures or pyramid levels) -- over a batch in DEVICE memory, stream-ordered on the
+ * detector's stream (the caller's after agx_detector_set_stream); returns without waiting.  Per frame: min = the fold
+ * `e < acc ? e : acc` from f32::MAX over all width*height values (:414-417; a NaN never wins), thr = min * 0.05f (:418), the
+ * 4-connected components of v < thr (init_saddle_clusters / pixel_bfs, :171-187, src/image_util.rs:208-236), one cluster per
+ * component in the order of its first pixel in the raster scan, and the centroid map (:421-429): agx_cluster_info =
+ * {first_index = y*width + x of that pixel, size, cx, cy}.  cx, cy are the reference's bit for bit while the coordinate sums
+ * stay below 2^24; beyond that they are the quotients of the exact integer sums and AGX_CLUSTERS_INEXACT is set (as
+ * AGX_FRAME_CENTROID_INEXACT).
+ * The outermost ring: the reference scans seeds in the interior only but lets a flood run into the ring where a ring pixel is
+ * below thr; a component's first scanned pixel is then not its smallest pixel.  That is not emulated: a frame with any ring
+ * pixel below thr is refused -- AGX_CLUSTERS_BORDER, count 0, no row -- and the other frames of the batch are unaffected.
+ * Every hessian_response plane has a +0.0 ring and thr <= 0, so agx_planes_enqueue's d_response is never refused.  A frame
+ * with width or height below 3 has no interior: count 0, AGX_CLUSTERS_OK.
+ * d_response: 4-byte aligned; frame f, row y starts at f*frame_stride_bytes + y*row_stride_bytes; strides are multiples of 4,
+ * row_stride_bytes >= 4*width, frame_stride_bytes >= height*row_stride_bytes; width, height >= 2; only the width floats of a
+ * row are read.  clusters_per_frame in 1 .. 16384.  Anything else is AGX_ERR_ARG (a batch in flight stays where it is).
+ * Results, frame f: d_counts[f], d_status[f] (AGX_CLUSTERS_*), d_clusters[f*clusters_per_frame + i] for i below the count and,
+ * if d_points is given, the agx_point (cx, cy) at the same slot -- with d_counts a valid d_points / points_per_frame / d_counts
+ * of agx_refine_points_enqueue[_h] as it stands.  Slots at or beyond the count are not written; a frame whose status is not
+ * AGX_CLUSTERS_OK (INEXACT aside) writes no row.  d_clusters, d_counts, d_status: caller-owned device memory (4-byte aligned),
+ * or all NULL: internal buffers, copied out by agx_clusters_fetch; d_points is optional on its own.
+ * A seventh kind of batch on the handle: it replaces whatever is in flight without waiting, the other kinds' fetches of it are
+ * AGX_ERR_STATE.  It runs on the handle's workspace (agx_detector_set_limits, option "force_generic" apply); HIP graphs: one
+ * eager batch of the geometry first, as for agx_saddles_batch_enqueue. */
+enum { AGX_CLUSTERS_OK = 0,
+       AGX_CLUSTERS_CAPACITY = 1, /* more clusters than clusters_per_frame (at most 16384 can be listed): the true count, no row */
+       AGX_CLUSTERS_BORDER = 2,   /* a pixel of the outermost ring is below the threshold: count 0, no row */
+       AGX_CLUSTERS_OVERFLOW = 3, /* an internal list overflowed (agx_detector_set_limits): count 0, no row */
+       AGX_CLUSTERS_INEXACT = 256 /* 0x100, a flag OR'd into OK / CAPACITY: a coordinate sum reached 2^24 */ };
+int agx_clusters_enqueue(agx_detector *det, const float *d_response, int n_frames, int width, int height,
+                         size_t row_stride_bytes, size_t frame_stride_bytes, uint32_t clusters_per_frame,
+                         agx_cluster_info *d_clusters, void *d_points, uint32_t *d_counts, uint32_t *d_status);
+/* Wait for the batch of agx_clusters_enqueue (src/detector.rs:414-429).  Internal buffers: counts and status ([n_frames],
+ * required) and clusters ([n_frames][clusters_per_frame]) receive what the batch wrote, points ([n_frames][clusters_per_frame]
+ * agx_point, may be NULL) the (cx, cy) of the rows -- copied from the enqueue's d_points where that was given --; slots at or
+ * beyond a frame's count stay as they were.  Caller-owned device arrays: all four are NULL, the call only waits.  AGX_ERR_STATE: no such batch in flight (another kind, none, or fetched
+ * already). */
+int agx_clusters_fetch(agx_detector *det, agx_cluster_info *clusters, void *points, uint32_t *counts, uint32_t *status);
+/* The same (src/detector.rs:414-429) for one plane in HOST memory: uploads it, runs a batch of one with cap rows and fetches it.
+ * *n_out = the count, *status an AGX_CLUSTERS_* value; out receives the rows of an AGX_CLUSTERS_OK frame.  response and
+ * row_stride_bytes as d_response's (4-byte aligned, a multiple of 4, >= 4*width), cap as clusters_per_frame: anything else is
+ * AGX_ERR_ARG before anything is uploaded or a batch in flight is touched. */
+int agx_cluster_centers(agx_detector *det, const float *response, int width, int height, size_t row_stride_bytes,
+                        agx_cluster_info *out, uint32_t cap, uint32_t *n_out, uint32_t *status);
+
+/* The k / phi filter of refined_saddle_points -- src/detector.rs:432-445 -- on the records of agx_refine_points_enqueue, in
+ * place, stream-ordered on the detector's stream, caller-owned device arrays only; nothing to fetch (like agx_planes_enqueue it
+ * replaces the batch in flight).  Once per frame over the slots below the frame's count (d_counts as in
+ * agx_refine_points_enqueue; NULL: points_per_frame) whose word in d_status is AGX_POINT_REFINED: max_k = the f32::MIN-started
+ * max fold of their k, s_max_k = max_k / 10.0f, and a slot that fails k >= s_max_k && phi >= min_saddle_angle && phi <=
+ * max_saddle_angle (the handle's params) gets AGX_POINT_FILTERED.  Records and every other word stay as they are; a frame with
+ * no refined slot changes nothing (:432-434).  d_status then serves as d_point_status of agx_find_boards_enqueue, and the
+ * surviving records in slot order are refined_saddle_points' Vec.  AGX_ERR_ARG: NULL or misaligned d_records / d_status,
+ * n_frames <= 0, points_per_frame == 0, 2^31 slots or more. */
+enum { AGX_POINT_FILTERED = 4 }; /* :436-443: k < max_k / 10, or phi outside [min_saddle_angle, max_saddle_angle] */
+int agx_filter_saddles_enqueue(agx_detector *det, const agx_saddle *d_records, uint32_t *d_status, int n_frames,
+                               uint32_t points_per_frame, const uint32_t *d_counts);
+/* The same filter (src/detector.rs:432-445) over ONE list in host memory, without a detector handle (no device needed): n
+ * records and their status words; params may be NULL (agx_default_params). */
+int agx_filter_saddles_tail(const agx_params *params, const agx_saddle *records, uint32_t *status, uint32_t n);
+
 /* ---- detector groups: several GPUs of one node driven from ONE process ----------------- */
 
 /* The reference's detect(&self) is stateless, so a batch shards by frame:
@@ -709,14 +782,11 @@ enum { AGX_DBG_BLUR = 0, AGX_DBG_RESP = 1, AGX_DBG_MIN = 2, AGX_DBG_CENTERS = 3,
                                check of the check).  Buffers = the chain's workspace, then the staging buffer, the luma
                                planes and the device tail's code list, tag rows and frame table (mapped pinned host memory), then
                                agx_detect_batch_enqueue_to's device-memory tag rows and frame table, agx_detect_batch_fetch's
-                               pinned luma planes, the front-end kernel's luma plane (AGX_LA8 .. AGX_RGBA16), the stored / recomputed response planes, agx_refine_points_enqueue's internal records and statuses and agx_rochade_refine's points, agx_decode_quads_enqueue's internal tags, statuses and bits and agx_decode_quads' quads, and agx_find_boards_enqueue's internal quads, quad points, counts and statuses and agx_find_board's list, and agx_planes_enqueue's workspace blur planes and the device plane of agx_gaussian_blur_f32 / agx_hessian_response, as far as they exist.  Needs no enqueued batch.  Guard bytes exist only in handles created with
+                               pinned luma planes, the front-end kernel's luma plane (AGX_LA8 .. AGX_RGBA16), the stored / recomputed response planes, agx_refine_points_enqueue's internal records and statuses and agx_rochade_refine's points, agx_decode_quads_enqueue's internal tags, statuses and bits and agx_decode_quads' quads, and agx_find_boards_enqueue's internal quads, quad points, counts and statuses and agx_find_board's list, and agx_planes_enqueue's workspace blur planes and the device plane of agx_gaussian_blur_f32 / agx_hessian_response, and agx_clusters_enqueue's internal rows, points, counts and statuses and agx_cluster_centers' plane, as far as they exist.  Needs no enqueued batch.  Guard bytes exist only in handles created with
                                AGX_REDZONE_BYTES=<n> in the environment (memory-safety tests of the kernels) */
        AGX_DBG_TAIL_TABLE_ADDR = 11 /* 2 x uint64: host address and payload bytes of the device tail's frame table (the check
                                        of the check for a buffer in mapped host memory).  Needs no enqueued batch */ };
-typedef struct agx_cluster_info {
-    uint32_t first_index, size;
-    float cx, cy;
-} agx_cluster_info;
+/* (agx_cluster_info, the element of AGX_DBG_CENTERS: declared with agx_clusters_enqueue above) */
 /* Test hook of the host tail: for n pairs of vectors (v0x, v0y, v1x, v1y) the reference's
  * angle(v0, v1) in degrees (math_util.rs:27-33) and the bounded approximation the board search uses
  * to decide threshold comparisons that are not close (csrc/host_tail.cpp, LazyAngle); has_approx[i] = 0
