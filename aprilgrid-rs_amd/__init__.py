@@ -8,8 +8,8 @@ been built -- there is no CPU fallback.
 """
 from .detector import (DetectorGroup, DetectorParams, Saddle, TagDetector, TagFamily, AgxError, SADDLE_DTYPE, CLUSTER_DTYPE,
                        blur_weights, build_library, decode_quads_tail, find_board_tail, library_path,
-                       refine_constants, filter_saddles)
+                       refine_constants, filter_saddles, collect_tags)
 
 __all__ = ["DetectorGroup", "DetectorParams", "Saddle", "TagDetector", "TagFamily", "AgxError", "SADDLE_DTYPE", "CLUSTER_DTYPE",
            "blur_weights", "build_library", "decode_quads_tail", "find_board_tail", "library_path", "refine_constants",
-           "filter_saddles"]
+           "filter_saddles", "collect_tags"]

@@ -26,6 +26,9 @@ AGX_BOARD_FOUND, AGX_BOARD_NONE, AGX_BOARD_CAPACITY, AGX_BOARD_INPUT, AGX_BOARD_
 # cluster centres of caller-given response planes (src/detector.rs:414-429): what became of a frame; INEXACT is a flag OR'd in
 AGX_CLUSTERS_OK, AGX_CLUSTERS_CAPACITY, AGX_CLUSTERS_BORDER, AGX_CLUSTERS_OVERFLOW, AGX_CLUSTERS_INEXACT = 0, 1, 2, 3, 0x100
 AGX_POINT_FILTERED = 4  # the k / phi filter (src/detector.rs:432-445) removed a refined point
+# the rounds of max_num_of_boards (src/detector.rs:510-539): a saddle of a quad an earlier round decoded; a frame's tag table
+AGX_POINT_USED = 5
+AGX_TAGS_OK, AGX_TAGS_CAPACITY, AGX_TAGS_INPUT, AGX_TAGS_PENDING = 0, 1, 2, 3
 AGX_DBG_BLUR, AGX_DBG_RESP, AGX_DBG_MIN, AGX_DBG_CENTERS, AGX_DBG_REFINED = 0, 1, 2, 3, 4
 AGX_N_KERNELS = 5
 
@@ -116,6 +119,8 @@ SYMBOLS = {
     "agx_cluster_centers": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "agx_filter_saddles_enqueue": (C.c_int, [_P, _P, _P, C.c_int, C.c_uint32, _P]),
     "agx_filter_saddles_tail": (C.c_int, [C.POINTER(Params), _P, _P, C.c_uint32]),
+    "agx_collect_tags_enqueue": (C.c_int, [_P, C.c_int, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P, C.c_int]),
+    "agx_collect_tags_tail": (C.c_int, [C.c_int, C.c_uint32, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P]),
     "agx_group_create": (C.c_int, [C.c_int, C.POINTER(Params), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "agx_group_destroy": (None, [_P]),
     "agx_group_size": (C.c_int, [_P]),

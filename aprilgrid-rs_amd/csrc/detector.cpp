@@ -1897,6 +1897,63 @@ int agx_filter_saddles_tail(const agx_params *params, const agx_saddle *records,
     });
 }
 
+// One round of detect's loop behind its board search and decode (src/detector.rs:510-539): k_collect_tags, one wave per frame
+int agx_collect_tags_enqueue(agx_detector *det, int n_frames, uint32_t quads_per_frame, const uint32_t *d_quads, const uint32_t *d_n_quads,
+                             const uint32_t *d_board_status, const agx_tag *d_quad_tags, const uint32_t *d_quad_status,
+                             uint32_t saddles_per_frame, const void *d_frame_table, uint32_t *d_point_status, uint32_t tags_per_frame,
+                             agx_tag *d_tags, uint32_t *d_n_tags, uint32_t *d_tag_status, int reset)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    if (!d_quads || !d_n_quads || !d_board_status || !d_quad_tags || !d_quad_status || !d_tags || !d_n_tags || !d_tag_status || n_frames <= 0)
+        return fail(det, AGX_ERR_ARG, "a null array or n_frames <= 0");
+    if (!quads_per_frame || !tags_per_frame) return fail(det, AGX_ERR_ARG, "quads_per_frame and tags_per_frame must be > 0");
+    if (!d_frame_table && !saddles_per_frame) return fail(det, AGX_ERR_ARG, "saddles_per_frame must be > 0 without a frame table");
+    if (((uintptr_t)d_quads | (uintptr_t)d_n_quads | (uintptr_t)d_board_status | (uintptr_t)d_quad_tags | (uintptr_t)d_quad_status |
+         (uintptr_t)d_frame_table | (uintptr_t)d_point_status | (uintptr_t)d_tags | (uintptr_t)d_n_tags | (uintptr_t)d_tag_status) & 3)
+        return fail(det, AGX_ERR_ARG, "every array must be 4-byte aligned");
+    const size_t lim = (size_t)1 << 31, F = (size_t)n_frames;
+    if (F * quads_per_frame >= lim || F * tags_per_frame >= lim || (!d_frame_table && F * saddles_per_frame >= lim))
+        return fail(det, AGX_ERR_ARG, "at most 2^31 - 1 quad rows, tag rows and slots per batch");
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // and there is nothing of this one to be fetched
+    CollectTagsArgs c{};
+    c.n_frames = n_frames;
+    c.quads_per_frame = quads_per_frame;
+    c.quads = d_quads;
+    c.n_quads = d_n_quads;
+    c.board_status = d_board_status;
+    c.quad_tags = d_quad_tags;
+    c.quad_status = d_quad_status;
+    c.saddles_per_frame = saddles_per_frame;
+    c.frame_table = static_cast<const uint32_t *>(d_frame_table);
+    c.point_status = d_point_status;
+    c.tags_per_frame = tags_per_frame;
+    c.tags = d_tags;
+    c.n_tags = d_n_tags;
+    c.tag_status = d_tag_status;
+    c.n_codes = det->fam.n_codes;
+    c.reset = reset != 0;
+    hipError_t e = (hipError_t)launch_collect_tags(c, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_collect_tags: ") + hipGetErrorString(e));
+    return AGX_OK;
+    });
+}
+
+int agx_collect_tags_tail(int family, uint32_t n_quads, const uint32_t *quads, uint32_t board_status, const agx_tag *quad_tags,
+                          const uint32_t *quad_status, uint32_t n_slots, uint32_t *point_status, uint32_t tag_cap, agx_tag *tags,
+                          uint32_t *n_tags, uint32_t *tag_status)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    FamilyInfo fam;
+    if (!family_info(family, fam)) return AGX_ERR_FAMILY;
+    if (!n_tags || !tag_status || !tags || !tag_cap) return AGX_ERR_ARG;
+    if (board_status == AGX_BOARD_FOUND && n_quads && (!quads || !quad_tags || !quad_status)) return AGX_ERR_ARG;
+    collect_tags(fam.n_codes, n_quads, quads, board_status, quad_tags, quad_status, n_slots, point_status, tag_cap, tags, n_tags, tag_status);  // src/detector.rs:510-539
+    return AGX_OK;
+    });
+}
+
 }  // extern "C"
 
 int agx::group_detect_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,

@@ -1448,4 +1448,59 @@ void filter_saddles(const agx_params &params, const agx_saddle *records, uint32_
             status[i] = AGX_POINT_FILTERED;
 }
 
+void collect_tags(int n_codes, uint32_t n_quads, const uint32_t *quads, uint32_t board_status, const agx_tag *quad_tags,
+                  const uint32_t *quad_status, uint32_t n_slots, uint32_t *point_status, uint32_t tag_cap, agx_tag *tags,
+                  uint32_t *n_tags, uint32_t *tag_status)
+{
+    if (*tag_status != AGX_TAGS_OK) return;  // sticky
+    if (board_status == AGX_BOARD_PENDING) {
+        *tag_status = AGX_TAGS_PENDING;
+        return;
+    }
+    if (board_status == AGX_BOARD_NONE) return;  // the reference's loop runs on (:512)
+    if (board_status != AGX_BOARD_FOUND) {
+        *tag_status = AGX_TAGS_INPUT;
+        return;
+    }
+    // everything that refuses the round, before anything is written
+    const uint32_t cnt = *n_tags;
+    bool any = false, bad = false;
+    for (uint32_t q = 0; q < n_quads; ++q) {
+        if (quad_status[q] != AGX_QUAD_DECODED) continue;
+        any = true;
+        bad = bad || quad_tags[q].id >= (uint32_t)n_codes;
+        for (int i = 0; i < 4; ++i) bad = bad || quads[4 * (size_t)q + i] >= n_slots;
+    }
+    if (!any) return;  // a round that decodes nothing changes nothing
+    if (cnt > tag_cap) bad = true;
+    for (uint32_t t = 0; t < cnt && !bad; ++t) bad = tags[t].id >= (uint32_t)n_codes;
+    if (bad) {
+        *tag_status = AGX_TAGS_INPUT;
+        return;
+    }
+    // detected_tags.insert (:520) in quad order: the row of every id, known or new, then the corners of its last quad
+    std::vector<uint32_t> place((size_t)n_codes, 0xffffffffu), last((size_t)n_codes, 0u);
+    for (uint32_t t = cnt; t-- > 0;) place[tags[t].id] = t;  // (the first row of an id, should a caller's table repeat one)
+    uint32_t total = cnt;
+    for (uint32_t q = 0; q < n_quads; ++q) {
+        if (quad_status[q] != AGX_QUAD_DECODED) continue;
+        const uint32_t id = quad_tags[q].id;
+        if (place[id] == 0xffffffffu) place[id] = total++;
+        last[id] = q;
+    }
+    if (total > tag_cap) {
+        *n_tags = total;
+        *tag_status = AGX_TAGS_CAPACITY;
+        return;
+    }
+    for (uint32_t q = 0; q < n_quads; ++q) {
+        if (quad_status[q] != AGX_QUAD_DECODED) continue;
+        const uint32_t id = quad_tags[q].id;
+        if (last[id] == q) std::memcpy(&tags[place[id]], &quad_tags[q], sizeof(agx_tag));
+        if (point_status)
+            for (int i = 0; i < 4; ++i) point_status[quads[4 * (size_t)q + i]] = AGX_POINT_USED;  // :521-536
+    }
+    *n_tags = total;
+}
+
 }  // namespace agx

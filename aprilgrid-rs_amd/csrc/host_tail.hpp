@@ -89,4 +89,12 @@ int luma8(const void *pixels, int width, int height, size_t row_stride, int form
 // the device form)
 void filter_saddles(const agx_params &params, const agx_saddle *records, uint32_t *status, uint32_t n);
 
+// One round of detect's loop behind its board search and decode (detector.rs:510-539) for one frame: the round's decoded quads
+// into the tag table (:520; a tag keeps the row of its first insertion and takes the corners of its last) and AGX_POINT_USED into
+// the words of their saddles (:521-536; point_status may be null).  *n_tags / *tag_status (AGX_TAGS_*) in and out; a status that
+// is not AGX_TAGS_OK is sticky.  n_codes = the family's code count.  (agx_collect_tags_tail; k_collect_tags is the device form)
+void collect_tags(int n_codes, uint32_t n_quads, const uint32_t *quads, uint32_t board_status, const agx_tag *quad_tags,
+                  const uint32_t *quad_status, uint32_t n_slots, uint32_t *point_status, uint32_t tag_cap, agx_tag *tags,
+                  uint32_t *n_tags, uint32_t *tag_status);
+
 }  // namespace agx

@@ -108,6 +108,30 @@ struct FindBoardsArgs {
 };
 // one workgroup per frame, k_board_tail's LDS; needs init_tail_kernels on the device; hipError_t
 int launch_find_boards(const FindBoardsArgs &b, void *stream);
+// k_collect_tags (agx_collect_tags_enqueue): one round's bookkeeping of detect's loop (detector.rs:510-539) per frame -- the
+// decoded quads of the round into the frame's tag table (detected_tags.insert, :520: a tag keeps the row of its first insertion and
+// takes the corners of its last) and AGX_POINT_USED into the status words of their saddles (:521-536).  No pixels.  All pointers
+// are device pointers; host_tail.cpp's collect_tags is the same round on the host.
+struct CollectTagsArgs {
+    int n_frames;
+    uint32_t quads_per_frame;
+    const uint32_t *quads;         // [n_frames][quads_per_frame][4]: slot numbers within the frame (k_find_boards' rows)
+    const uint32_t *n_quads;       // [n_frames]
+    const uint32_t *board_status;  // [n_frames]: AGX_BOARD_*
+    const agx_tag *quad_tags;      // [n_frames * quads_per_frame] (k_decode_quads' rows)
+    const uint32_t *quad_status;   // [n_frames * quads_per_frame]: AGX_QUAD_*
+    uint32_t saddles_per_frame;    // frame f's words start at f * saddles_per_frame, saddles_per_frame of them; or ...
+    const uint32_t *frame_table;   // ... agx_frame_result[n_frames]: `count` words from `offset`
+    uint32_t *point_status;        // a word per slot, or null: nothing is marked
+    uint32_t tags_per_frame;
+    agx_tag *tags;         // [n_frames][tags_per_frame]: rows below the frame's count
+    uint32_t *n_tags;      // [n_frames]
+    uint32_t *tag_status;  // [n_frames]: AGX_TAGS_*
+    int n_codes;           // the family's code count: a decoded id is below it
+    int reset;             // != 0: every frame's table is empty (count 0, AGX_TAGS_OK) whatever the arrays hold
+};
+// one wave per frame; n_codes in 1 .. 640 (the LDS tables are indexed by id); hipError_t
+int launch_collect_tags(const CollectTagsArgs &c, void *stream);
 int init_tail_kernels();  // per-device kernel attributes (current device); hipError_t
 
 }  // namespace agx

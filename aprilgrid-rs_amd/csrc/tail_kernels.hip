@@ -1789,7 +1789,131 @@ __global__ void __launch_bounds__(DQ_THREADS, 4) k_decode_quads(DecodeQuadsArgs 
     }
 }
 
+// ---- agx_collect_tags_enqueue: one round of detect's loop behind its board search and decode (detector.rs:510-539) ------------
+// The insert of :520 and the removal of :521-536 over a frame's quads, one wave per frame -- what k_board_tail's round does with
+// its own lists, on the arrays k_find_boards and k_decode_quads left.  Three LDS tables indexed by tag id: the row of an id the
+// table knows, and the first and the last quad of the round that decoded it (atomicMin / atomicMax over all quads, so that no
+// pass of 64 quads has a boundary to get wrong).  A new id's row is the table's count plus the number of first-of-a-new-id quads
+// in front of its own first quad, a prefix over the quads in order; the quad that is an id's last writes its corners.
+// Everything that refuses the frame is decided before its first store, and every early exit is taken by the whole wave.
+constexpr uint32_t CT_NONE = 0xffffffffu;
+
+__global__ void __launch_bounds__(64) k_collect_tags(CollectTagsArgs c)
+{
+    __shared__ uint32_t place[TCODES], first_q[TCODES], last_q[TCODES];
+    const uint32_t f = blockIdx.x, lane = threadIdx.x;
+    const uint32_t n_codes = (uint32_t)c.n_codes;  // (the launcher: 1 .. TCODES)
+    if (!c.reset && c.tag_status[f] != AGX_TAGS_OK) return;  // sticky: the frame stays exactly as it is
+    const uint32_t cnt = c.reset ? 0u : c.n_tags[f];
+    const uint32_t bs = c.board_status[f];
+    uint32_t st = AGX_TAGS_OK, nq = 0;
+    if (bs == AGX_BOARD_PENDING) {
+        st = AGX_TAGS_PENDING;
+    } else if (bs == AGX_BOARD_FOUND) {
+        nq = c.n_quads[f];
+        if (nq > c.quads_per_frame) st = AGX_TAGS_INPUT;
+    } else if (bs != AGX_BOARD_NONE) {
+        st = AGX_TAGS_INPUT;
+    }
+    uint32_t bound = c.saddles_per_frame;
+    u64 word0 = (u64)f * c.saddles_per_frame;
+    if (c.frame_table) {
+        bound = c.frame_table[4 * f];
+        word0 = c.frame_table[4 * f + 1];
+    }
+    const u64 q0 = (u64)f * c.quads_per_frame;
+    const uint32_t *quads = c.quads + q0 * 4u;
+    const uint32_t *rows_in = reinterpret_cast<const uint32_t *>(c.tags + (u64)f * c.tags_per_frame);
+    bool any = false;
+    if (st == AGX_TAGS_OK) {
+        bool bad = false;
+        for (uint32_t q = lane; q < nq; q += 64u)
+            if (c.quad_status[q0 + q] == AGX_QUAD_DECODED) {
+                any = true;
+                bad = bad || c.quad_tags[q0 + q].id >= n_codes;
+                for (int i = 0; i < 4; ++i) bad = bad || quads[4u * q + i] >= bound;
+            }
+        any = __ballot(any) != 0;
+        if (any) {  // the table is merged into: its count and its ids index the rows and the LDS tables
+            if (cnt > c.tags_per_frame) bad = true;
+            else
+                for (uint32_t t = lane; t < cnt; t += 64u) bad = bad || rows_in[9u * t] >= n_codes;
+        }
+        if (__ballot(bad)) st = AGX_TAGS_INPUT;
+    }
+    if (st != AGX_TAGS_OK || !any) {  // refused, or a round that changes nothing (AGX_BOARD_NONE, nothing decoded)
+        if (lane == 0 && (c.reset || st != AGX_TAGS_OK)) {
+            if (c.reset) c.n_tags[f] = 0u;
+            c.tag_status[f] = st;
+        }
+        return;
+    }
+    for (uint32_t i = lane; i < n_codes; i += 64u) {
+        place[i] = CT_NONE;
+        first_q[i] = CT_NONE;
+        last_q[i] = 0u;
+    }
+    __syncthreads();
+    for (uint32_t t = lane; t < cnt; t += 64u) atomicMin(&place[rows_in[9u * t]], t);
+    for (uint32_t q = lane; q < nq; q += 64u)
+        if (c.quad_status[q0 + q] == AGX_QUAD_DECODED) {
+            const uint32_t id = c.quad_tags[q0 + q].id;
+            atomicMin(&first_q[id], q);
+            atomicMax(&last_q[id], q);
+        }
+    __syncthreads();
+    // the rows of the new ids: only an id's first quad passes the test, so its row can be entered at once
+    const u64 below = (1ull << lane) - 1ull;
+    uint32_t n_new = 0;
+    for (uint32_t base = 0; base < nq; base += 64u) {
+        const uint32_t q = base + lane;  // (nq <= quads_per_frame < 2^31: no wrap)
+        uint32_t id = 0;
+        bool is_new = false;
+        if (q < nq && c.quad_status[q0 + q] == AGX_QUAD_DECODED) {
+            id = c.quad_tags[q0 + q].id;
+            is_new = place[id] == CT_NONE && first_q[id] == q;
+        }
+        const u64 m = __ballot(is_new);
+        if (is_new) place[id] = cnt + n_new + (uint32_t)__popcll(m & below);
+        n_new += (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    const uint32_t total = cnt + n_new;  // (cnt <= tags_per_frame < 2^31, n_new <= n_codes)
+    if (total > c.tags_per_frame) {
+        if (lane == 0) {
+            c.n_tags[f] = total;
+            c.tag_status[f] = AGX_TAGS_CAPACITY;
+        }
+        return;
+    }
+    uint32_t *rows = reinterpret_cast<uint32_t *>(c.tags + (u64)f * c.tags_per_frame);
+    for (uint32_t q = lane; q < nq; q += 64u)
+        if (c.quad_status[q0 + q] == AGX_QUAD_DECODED) {
+            const uint32_t *src = reinterpret_cast<const uint32_t *>(c.quad_tags + q0 + q);
+            const uint32_t id = src[0];
+            if (last_q[id] == q) {
+                uint32_t *o = rows + 9u * place[id];  // (place < total <= tags_per_frame)
+                for (int i = 0; i < 9; ++i) o[i] = src[i];
+            }
+            if (c.point_status)
+                for (int i = 0; i < 4; ++i) c.point_status[word0 + quads[4u * q + i]] = AGX_POINT_USED;
+        }
+    if (lane == 0) {
+        c.n_tags[f] = total;
+        c.tag_status[f] = AGX_TAGS_OK;
+    }
+}
+
 }  // namespace
+
+int launch_collect_tags(const CollectTagsArgs &c, void *stream)
+{
+    if (c.n_frames <= 0 || !c.quads_per_frame || !c.tags_per_frame || c.n_codes < 1 || c.n_codes > TCODES || !c.quads || !c.n_quads ||
+        !c.board_status || !c.quad_tags || !c.quad_status || !c.tags || !c.n_tags || !c.tag_status || (!c.frame_table && !c.saddles_per_frame))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_collect_tags, dim3((unsigned)c.n_frames), dim3(64), 0, (hipStream_t)stream, c);
+    return (int)hipGetLastError();
+}
 
 int launch_decode_quads(const DecodeQuadsArgs &d, void *stream)
 {

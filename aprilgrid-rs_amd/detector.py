@@ -11,6 +11,8 @@ Same names, argument meaning and error behaviour as the reference where Python a
   TagDetector.rochade_refine          src/detector.rs:194-361 (the crate's pub fn, half_size_patch = 2)
   TagDetector.decode_quads            src/detector.rs:448-476 (try_decode_quad = the pub fns decode_positions, bit_code, best_tag)
   TagDetector.find_board              src/detector.rs:588-639 (the crate's pub fn try_find_best_board)
+  TagDetector.detect_staged           src/detector.rs:505-540 as the staged chain on device tensors; its rounds (:510-539) by
+                                      TagDetector.collect_tags_enqueue / collect_tags
   TagDetector.gaussian_blur_f32       src/image_util.rs:110-206 (the crate's pub fn, any sigma up to 8)
   TagDetector.hessian_response        src/image_util.rs:72-109 (the crate's pub fn)
 An image is a numpy array standing for the DynamicImage variants the reference is fed:
@@ -990,6 +992,111 @@ class TagDetector:
         self._check(self._lib.agx_filter_saddles_enqueue(self._h, records.data_ptr(), status.data_ptr(), n, ppf,
                                                          counts.data_ptr() if counts is not None else None))
 
+    # ---- the rounds of max_num_of_boards on the device (src/detector.rs:510-539) ----------------
+    def collect_tags_enqueue(self, quads, n_quads, board_status, quad_tags, quad_status, point_status, tags, n_tags, tag_status,
+                             reset=False, frame_table=None, saddles_per_frame=None):
+        """One round of detect's loop behind its board search and decode (src/detector.rs:510-539), per frame, in place and
+        stream-ordered behind torch's current stream; nothing to fetch.  quads int32 [N,Q,4], n_quads and board_status int32 [N]:
+        find_boards_enqueue's quads, n_quads and status; quad_tags int32 [N,Q,9] and quad_status int32 [N,Q]:
+        decode_quads_enqueue's out and status.  tags int32 [N,T,9] (split_device_tags reads it), n_tags and tag_status int32 [N]:
+        the frames' tag tables, in and out -- every decoded quad inserts (id, corners): a new id takes the next row, a known one
+        keeps its row and takes the new corners; tag_status is AGX_TAGS_*, and a frame that is not AGX_TAGS_OK stays as it is.
+        reset=True takes every table as empty (the first round).  point_status int32 [N,S] (or, with frame_table int32 [N,4],
+        the flat words that table indexes): find_boards_enqueue's point_status; the saddles of decoded quads get
+        AGX_POINT_USED.  None: nothing is marked (the last round) and saddles_per_frame= names S, the bound of a slot number."""
+        import torch
+        if not (getattr(quads, "is_cuda", False) and quads.dim() == 3 and quads.shape[2] == 4 and quads.shape[1] > 0):
+            raise AgxError(_ffi.AGX_ERR_ARG, "quads must be a device tensor [N, Q, 4]")
+        if not (getattr(tags, "is_cuda", False) and tags.dim() == 3 and tags.shape[2] == 9 and tags.shape[1] > 0):
+            raise AgxError(_ffi.AGX_ERR_ARG, "tags must be a device tensor [N, T, 9]")
+        n, qpf, tpf = int(quads.shape[0]), int(quads.shape[1]), int(tags.shape[1])
+        dev = quads.device
+
+        def tensor(t, shape, what):
+            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == torch.int32 and (shape is None or tuple(t.shape) == shape)
+                    and t.device == dev):
+                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous int32 tensor %s on the quads' device" % (what, shape))
+            return t.data_ptr()
+
+        p = [tensor(quads, (n, qpf, 4), "quads"), tensor(n_quads, (n,), "n_quads"), tensor(board_status, (n,), "board_status"),
+             tensor(quad_tags, (n, qpf, 9), "quad_tags"), tensor(quad_status, (n, qpf), "quad_status")]
+        p_table = tensor(frame_table, (n, 4), "frame_table") if frame_table is not None else None
+        p_ps = None
+        if point_status is not None:
+            p_ps = tensor(point_status, None, "point_status")
+            if frame_table is None:
+                if point_status.dim() != 2 or point_status.shape[0] != n or point_status.shape[1] == 0:
+                    raise AgxError(_ffi.AGX_ERR_ARG, "point_status must be [N, S] (or the flat words of frame_table)")
+                if saddles_per_frame is not None and int(saddles_per_frame) != int(point_status.shape[1]):
+                    raise AgxError(_ffi.AGX_ERR_ARG, "saddles_per_frame is point_status' second dimension")
+                saddles_per_frame = int(point_status.shape[1])
+        if frame_table is None and not saddles_per_frame:
+            raise AgxError(_ffi.AGX_ERR_ARG, "without point_status and frame_table: saddles_per_frame= bounds the slot numbers")
+        out = [tensor(tags, (n, tpf, 9), "tags"), tensor(n_tags, (n,), "n_tags"), tensor(tag_status, (n,), "tag_status")]
+        self._follow_torch_stream(quads)
+        self._batch = self._detect = self._refine = self._decode = self._find = self._clusters = None
+        self._check(self._lib.agx_collect_tags_enqueue(self._h, n, qpf, *p, int(saddles_per_frame or 0), p_table, p_ps, tpf, *out,
+                                                       1 if reset else 0))
+
+    _TAGS_STATUS = {_ffi.AGX_TAGS_CAPACITY: "AGX_TAGS_CAPACITY (more tags than tags_per_frame)",
+                    _ffi.AGX_TAGS_INPUT: "AGX_TAGS_INPUT (a board beyond quads_per_frame, or a refused saddle list)",
+                    _ffi.AGX_TAGS_PENDING: "AGX_TAGS_PENDING"}
+
+    def detect_staged(self, frames, clusters_per_frame=4096, quads_per_frame=128, tags_per_frame=None, format=None):
+        """detect (src/detector.rs:505-540) as the staged chain on device tensors, every stage handing its arrays to the next in
+        place: planes at the handle's sigma, clusters, refine on the blur plane at the handle's half_size_patch, the k / phi
+        filter, then max_num_of_boards rounds of find boards -> find_boards_fetch (which lets the host form answer a frame the
+        kernel hands back) -> decode -> collect (src/detector.rs:510-539).  frames and format= as detect_batch_enqueue.
+        tags_per_frame: rows of a frame's tag table (None: one per code of the family, which always holds).
+        -> one {tag_id: 4x2 corners} per frame in row order, as detect_batch.  A frame whose clusters or tags could not be held
+        raises AgxError naming the frame and its status."""
+        import torch
+        fmt, bpp = self._tensor_format(frames, format)
+        n, w, h, _, _ = self._tensor_geometry(frames, fmt, bpp)
+        n, w, h = int(n), int(w), int(h)
+        cpf, qpf = int(clusters_per_frame), int(quads_per_frame)
+        if tags_per_frame is None:
+            n_codes = C.c_int(0)
+            self._check(self._lib.agx_detector_family_info(self._h, None, None, None, None, C.byref(n_codes)))
+            tags_per_frame = n_codes.value
+        tpf = int(tags_per_frame)
+        dev = frames.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        blur = torch.empty((n, h, w), dtype=torch.float32, device=dev)
+        resp = torch.empty_like(blur)
+        rows, pts = torch.zeros((n, cpf, 4), **i32), torch.zeros((n, cpf, 2), dtype=torch.float32, device=dev)
+        counts, cstatus = torch.zeros(n, **i32), torch.zeros(n, **i32)
+        records, pstatus = torch.zeros((n, cpf, 5), dtype=torch.float32, device=dev), torch.zeros((n, cpf), **i32)
+        self.planes_enqueue(frames, self.blur_sigma, blur=blur, response=resp, format=format)
+        self.clusters_enqueue(resp, clusters=rows, points=pts, counts=counts, status=cstatus)
+        self.refine_points_enqueue(blur, pts, counts=counts, out=records, status=pstatus, image="plane", half_size_patch=self.half_size_patch)
+        self.filter_saddles_enqueue(records, pstatus, counts=counts)
+        quads, qpts = torch.zeros((n, qpf, 4), **i32), torch.zeros((n, qpf, 4, 2), dtype=torch.float32, device=dev)
+        nq, bst = torch.zeros(n, **i32), torch.zeros(n, **i32)
+        qtags, qst = torch.zeros((n, qpf, 9), **i32), torch.zeros((n, qpf), **i32)
+        tags, ntags, tst = torch.zeros((n, tpf, 9), **i32), torch.zeros(n, **i32), torch.zeros(n, **i32)
+        rounds = int(self.detector_params.max_num_of_boards)
+        for r in range(rounds):
+            self.find_boards_enqueue(records, counts=counts, point_status=pstatus, quads=quads, quad_points=qpts, n_quads=nq, status=bst)
+            self.find_boards_fetch()
+            self.decode_quads_enqueue(frames, qpts, counts=nq, out=qtags, status=qst, format=format)
+            self.collect_tags_enqueue(quads, nq, bst, qtags, qst, pstatus if r + 1 < rounds else None, tags, ntags, tst, reset=r == 0,
+                                      saddles_per_frame=cpf)
+        self.sync()
+        cstatus, tst, ntags = cstatus.cpu().numpy(), tst.cpu().numpy(), ntags.cpu().numpy()
+        table = tags.cpu().numpy().view(np.uint32).reshape(n, tpf, 9)
+        out = []
+        for f in range(n):
+            if (int(cstatus[f]) & 0xFF) != _ffi.AGX_CLUSTERS_OK:
+                raise AgxError(_ffi.AGX_ERR_CAPACITY, "detect_staged: frame %d: cluster status %d (AGX_CLUSTERS_*; clusters_per_frame = %d)"
+                               % (f, int(cstatus[f]), cpf))
+            if int(tst[f]) != _ffi.AGX_TAGS_OK:
+                raise AgxError(_ffi.AGX_ERR_CAPACITY if int(tst[f]) != _ffi.AGX_TAGS_PENDING else _ffi.AGX_ERR_STATE,
+                               "detect_staged: frame %d: tag status %s" % (f, self._TAGS_STATUS.get(int(tst[f]), str(int(tst[f])))))
+            t = table[f, :int(ntags[f])]
+            out.append({int(row[0]): row[1:].view(np.float32).reshape(4, 2).copy() for row in t})
+        return out
+
     # ---- measurement / parity hooks ------------------------------------------------------
     def profile_enable(self, level=2):
         """0/False off, 1 = time the blur kernel only, 2/True = time every kernel."""
@@ -1094,6 +1201,39 @@ def filter_saddles(records, status, optional_detector_params=None):
     if rc != _ffi.AGX_OK:
         raise AgxError(rc)
     return st
+
+
+def collect_tags(tag_family, quads, board_status, quad_tags, quad_status, n_slots, point_status=None, tags=None, n_tags=0, tag_status=0,
+                 tag_cap=None):
+    """One round of detect's loop behind its board search and decode (src/detector.rs:510-539) for one frame on the host, without
+    a device -- what TagDetector.collect_tags_enqueue leaves on the device.  quads [n, 4] saddle indices and board_status as
+    find_board_tail answered, quad_tags [n] TagDetector.TAG_DTYPE and quad_status [n] as decode_quads_tail did; n_slots bounds
+    the indices; point_status: n_slots words or None (nothing is marked).  tags (TAG_DTYPE rows), n_tags and tag_status: the
+    table so far (nothing for the first round); tag_cap: its rows (None: len(tags), or one per code of the family).
+    -> (tags [tag_cap], n_tags, tag_status AGX_TAGS_*, point_status): copies; rows below n_tags are the table."""
+    fam = TagFamily.from_str(tag_family) if isinstance(tag_family, str) else TagFamily(tag_family)
+    q = np.ascontiguousarray(quads, np.uint32).reshape(-1, 4)
+    qt = np.ascontiguousarray(quad_tags, TagDetector.TAG_DTYPE).reshape(-1)
+    qs = np.ascontiguousarray(quad_status, np.uint32).reshape(-1)
+    if not (len(q) == len(qt) == len(qs)):
+        raise AgxError(_ffi.AGX_ERR_ARG, "one tag and one status per quad")
+    if tag_cap is None:
+        tag_cap = len(tags) if tags is not None and len(tags) else 587
+    rows = np.zeros(int(tag_cap), TagDetector.TAG_DTYPE)
+    if tags is not None:
+        t = np.asarray(tags, TagDetector.TAG_DTYPE).reshape(-1)[:int(tag_cap)]
+        rows[:len(t)] = t
+    ps = np.array(point_status, np.uint32).reshape(-1) if point_status is not None else None
+    if ps is not None and len(ps) != int(n_slots):
+        raise AgxError(_ffi.AGX_ERR_ARG, "point_status: n_slots words")
+    n, st = C.c_uint32(int(n_tags)), C.c_uint32(int(tag_status))
+    rc = _ffi.lib().agx_collect_tags_tail(int(fam), len(q), q.ctypes.data if len(q) else None,
+                                          int(board_status), qt.ctypes.data if len(q) else None, qs.ctypes.data if len(q) else None,
+                                          int(n_slots), ps.ctypes.data if ps is not None and len(ps) else None, int(tag_cap),
+                                          rows.ctypes.data if len(rows) else None, C.byref(n), C.byref(st))
+    if rc != _ffi.AGX_OK:
+        raise AgxError(rc)
+    return rows, n.value, st.value, ps
 
 
 def decode_quads_tail(tag_family, luma8, quads, with_bits=False):

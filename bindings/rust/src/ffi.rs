@@ -137,6 +137,13 @@ pub const AGX_CLUSTERS_OVERFLOW: c_int = 3;
 pub const AGX_CLUSTERS_INEXACT: c_int = 256;
 // the k / phi filter (reference src/detector.rs:432-445): the status of a refined point it removes
 pub const AGX_POINT_FILTERED: c_int = 4;
+// the rounds of max_num_of_boards (reference src/detector.rs:510-539): a saddle of a quad an earlier round decoded, and what
+// became of a frame's tag table
+pub const AGX_POINT_USED: c_int = 5;
+pub const AGX_TAGS_OK: c_int = 0;
+pub const AGX_TAGS_CAPACITY: c_int = 1;
+pub const AGX_TAGS_INPUT: c_int = 2;
+pub const AGX_TAGS_PENDING: c_int = 3;
 // agx_debug_fetch items
 pub const AGX_DBG_BLUR: c_int = 0;
 pub const AGX_DBG_RESP: c_int = 1;
@@ -256,6 +263,14 @@ extern "C" {
     pub fn agx_filter_saddles_enqueue(det: *mut agx_detector, d_records: *const agx_saddle, d_status: *mut u32, n_frames: c_int,
                                       points_per_frame: u32, d_counts: *const u32) -> c_int;
     pub fn agx_filter_saddles_tail(params: *const agx_params, records: *const agx_saddle, status: *mut u32, n: u32) -> c_int;
+    pub fn agx_collect_tags_enqueue(det: *mut agx_detector, n_frames: c_int, quads_per_frame: u32, d_quads: *const u32,
+                                    d_n_quads: *const u32, d_board_status: *const u32, d_quad_tags: *const agx_tag,
+                                    d_quad_status: *const u32, saddles_per_frame: u32, d_frame_table: *const c_void,
+                                    d_point_status: *mut u32, tags_per_frame: u32, d_tags: *mut agx_tag, d_n_tags: *mut u32,
+                                    d_tag_status: *mut u32, reset: c_int) -> c_int;
+    pub fn agx_collect_tags_tail(family: c_int, n_quads: u32, quads: *const u32, board_status: u32, quad_tags: *const agx_tag,
+                                 quad_status: *const u32, n_slots: u32, point_status: *mut u32, tag_cap: u32, tags: *mut agx_tag,
+                                 n_tags: *mut u32, tag_status: *mut u32) -> c_int;
     pub fn agx_debug_blur_weights(sigma: c_float, weights: *mut c_float, cap: c_int, radius: *mut c_int) -> c_int;
     pub fn agx_debug_refine_constants(half_size_patch: c_int, cone: *mut c_float, pmat: *mut c_float, cap_points: c_int,
                                       n_points: *mut c_int) -> c_int;

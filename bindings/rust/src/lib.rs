@@ -466,6 +466,44 @@ pub fn find_best_board(refined: &[Saddle]) -> Option<Vec<[usize; 4]>> {
     }
 }
 
+/// One round of `detect`'s loop behind its board search and decode, reference src/detector.rs:510-539, on the host (no device is
+/// used): every quad of `quads` (saddle indices, as `find_best_board` returns them) whose `quad_status` is `AGX_QUAD_DECODED`
+/// inserts its `quad_tags` entry into `tags` -- a known id keeps its place and takes the new corners (:520) -- and, where
+/// `point_status` is given (a word per saddle), marks its four saddles `AGX_POINT_USED` (:521-536).  `tag_cap` bounds `tags`.
+/// Returns the frame's `AGX_TAGS_*` status; pass it back in as `tag_status` for the next round (a status other than
+/// `AGX_TAGS_OK` is sticky: the round changes nothing).
+pub fn collect_tags_tail(tag_family: &TagFamily, quads: &[[u32; 4]], board_status: u32, quad_tags: &[(u32, [(f32, f32); 4])],
+                         quad_status: &[u32], point_status: Option<&mut [u32]>, tag_cap: usize,
+                         tags: &mut Vec<(u32, [(f32, f32); 4])>, tag_status: u32) -> u32 {
+    assert!(quad_tags.len() == quads.len() && quad_status.len() == quads.len(), "one tag and one status per quad");
+    assert!(tag_cap > 0 && tags.len() <= tag_cap, "tag_cap must hold the table");
+    let flat: Vec<u32> = quads.iter().flat_map(|q| q.iter().copied()).collect();
+    let to_c = |t: &(u32, [(f32, f32); 4])| ffi::agx_tag {
+        id: t.0,
+        xy: [t.1[0].0, t.1[0].1, t.1[1].0, t.1[1].1, t.1[2].0, t.1[2].1, t.1[3].0, t.1[3].1],
+    };
+    let c_quad_tags: Vec<ffi::agx_tag> = quad_tags.iter().map(to_c).collect();
+    let mut rows: Vec<ffi::agx_tag> = tags.iter().map(to_c).collect();
+    rows.resize_with(tag_cap, || ffi::agx_tag { id: 0, xy: [0.0; 8] });
+    let (mut n_tags, mut status) = (tags.len() as u32, tag_status);
+    let (n_slots, words) = match point_status {
+        Some(w) => (w.len() as u32, w.as_mut_ptr()),
+        None => (u32::MAX, std::ptr::null_mut()),
+    };
+    let st = unsafe {
+        ffi::agx_collect_tags_tail(*tag_family as c_int, quads.len() as u32, flat.as_ptr(), board_status, c_quad_tags.as_ptr(),
+                                   quad_status.as_ptr(), n_slots, words, tag_cap as u32, rows.as_mut_ptr(), &mut n_tags, &mut status)
+    };
+    assert_eq!(st, ffi::AGX_OK, "agx_collect_tags_tail failed: {}", st);
+    if status as c_int == ffi::AGX_TAGS_OK {
+        tags.clear();
+        for r in &rows[..n_tags as usize] {
+            tags.push((r.id, [(r.xy[0], r.xy[1]), (r.xy[2], r.xy[3]), (r.xy[4], r.xy[5]), (r.xy[6], r.xy[7])]));
+        }
+    }
+    status
+}
+
 fn last_error(det: *const ffi::agx_detector) -> String {
     unsafe {
         let p = ffi::agx_last_error(det);

@@ -516,7 +516,8 @@ enum { AGX_BOARD_FOUND = 0,    /* src/detector.rs:588-639 returned Some: n_quads
  *                  bit (AGX_FRAME_CANDIDATE_ / _CLUSTER_ / _SADDLE_OVERFLOW) is AGX_BOARD_INPUT and nothing of it is read;
  *   d_point_status NULL, or one word per slot (indexed like the slots): only slots whose word is AGX_POINT_REFINED (0) enter
  *                  the list, in slot order -- agx_refine_points_enqueue's d_out / d_status are read in place, and a caller
- *                  removes the saddles of decoded quads between rounds of max_num_of_boards by marking their words non-zero.
+ *                  removes the saddles of decoded quads between rounds of max_num_of_boards by marking their words non-zero:
+ *                  agx_collect_tags_enqueue (below) does that on the device, AGX_POINT_USED, behind the round's decode.
  * Results, frame f: d_n_quads[f], d_status[f] (AGX_BOARD_*), d_quads[f][quads_per_frame][4]: uint32 SLOT NUMBERS WITHIN THE
  * FRAME (not positions in the list after d_point_status), and, if d_quad_points is given, [f][quads_per_frame][4][2] floats: the
  * corners' x, y in that order -- with d_n_quads as d_counts a valid d_quads (point stride 8) of agx_decode_quads_enqueue.  Only
@@ -656,6 +657,57 @@ int agx_filter_saddles_enqueue(agx_detector *det, const agx_saddle *d_records, u
 /* The same filter (src/detector.rs:432-445) over ONE list in host memory, without a detector handle (no device needed): n
  * records and their status words; params may be NULL (agx_default_params). */
 int agx_filter_saddles_tail(const agx_params *params, const agx_saddle *records, uint32_t *status, uint32_t n);
+
+/* ---- the rounds of max_num_of_boards on the device: tag table and used saddles ----------------- */
+
+/* What detect's loop does with a round's board besides finding and decoding it -- src/detector.rs:510-539: every decoded quad
+ * goes into detected_tags (:520) and its four saddles leave the list before the next round (:521-536).  One round per call, once
+ * per frame, on the outputs of agx_find_boards_enqueue and agx_decode_quads_enqueue as they stand; stream-ordered on the
+ * detector's stream (the caller's after agx_detector_set_stream), caller-owned device arrays only, no pixels, nothing to fetch
+ * (like agx_filter_saddles_enqueue it replaces the batch in flight without waiting).  With it the staged chain runs detect's
+ * rounds: find boards -> (agx_find_boards_fetch where a frame may be pending) -> decode -> collect, max_num_of_boards times.
+ *   d_quads [n_frames][quads_per_frame][4], d_n_quads, d_board_status [n_frames]: agx_find_boards_enqueue's d_quads, d_n_quads and
+ *     d_status (slot numbers within the frame);
+ *   d_quad_tags, d_quad_status [n_frames*quads_per_frame]: agx_decode_quads_enqueue's d_tags and d_status;
+ *   d_tags [n_frames][tags_per_frame], d_n_tags, d_tag_status [n_frames]: the frames' tag tables, in and out.  reset != 0 takes
+ *     every table as empty (count 0, AGX_TAGS_OK) whatever the arrays hold: the first round needs no memset;
+ *   d_point_status: the words agx_find_boards_enqueue reads as its d_point_status, or NULL: nothing is marked (the last round).
+ *     Frame f's words start at f*saddles_per_frame and its slot numbers are below saddles_per_frame; with d_frame_table (the
+ *     agx_frame_result entries, as in agx_find_boards_enqueue) they start at the entry's `offset` and are below its `count`.
+ * A frame whose board status is AGX_BOARD_FOUND: in quad order, every quad below the count whose status is AGX_QUAD_DECODED
+ * inserts (id, xy).  A new id takes the next row; a known id -- of an earlier round or an earlier quad of this one -- keeps its
+ * row and takes the new corners, so the last quad in quad order wins, as HashMap::insert has it, and the rows are in order of
+ * first insertion.  All four saddle slots of every decoded quad, one that only repeats an id included, get AGX_POINT_USED in
+ * d_point_status.  Records and every other word are untouched; rows at or beyond the count are never written.  AGX_BOARD_NONE
+ * changes nothing (the reference's loop runs on), and neither does a round that decodes nothing.
+ * d_tag_status[f]: AGX_TAGS_OK, or -- decided before anything of the frame is written, and sticky: later rounds leave such a
+ * frame exactly as it is --
+ *   AGX_TAGS_CAPACITY  the round needs more than tags_per_frame rows: d_n_tags[f] = the number of distinct ids it would have
+ *                      reached; no row is written and no word is marked this round;
+ *   AGX_TAGS_INPUT     the round's board status is AGX_BOARD_CAPACITY or AGX_BOARD_INPUT (or no AGX_BOARD_* value); an
+ *                      AGX_BOARD_FOUND count above quads_per_frame; a decoded quad with an id at or above the family's code
+ *                      count or a slot number at or above the frame's slot bound; a table to merge into whose count is above
+ *                      tags_per_frame or that holds such an id;
+ *   AGX_TAGS_PENDING   the round's board status is AGX_BOARD_PENDING: agx_find_boards_fetch has to resolve it first.
+ * AGX_ERR_ARG (a batch in flight stays where it is): a NULL array other than d_frame_table and d_point_status, n_frames <= 0,
+ * quads_per_frame or tags_per_frame == 0, saddles_per_frame == 0 without a table, a pointer that is not 4-byte aligned, 2^31
+ * or more quad rows, tag rows or (without a table) slots. */
+enum { AGX_POINT_USED = 5 }; /* src/detector.rs:521-536: a saddle of a quad that an earlier round decoded */
+enum { AGX_TAGS_OK = 0, AGX_TAGS_CAPACITY = 1, AGX_TAGS_INPUT = 2, AGX_TAGS_PENDING = 3 }; /* src/detector.rs:510-539, per frame */
+int agx_collect_tags_enqueue(agx_detector *det, int n_frames, uint32_t quads_per_frame,
+                             const uint32_t *d_quads, const uint32_t *d_n_quads, const uint32_t *d_board_status,
+                             const agx_tag *d_quad_tags, const uint32_t *d_quad_status,
+                             uint32_t saddles_per_frame, const void *d_frame_table, uint32_t *d_point_status,
+                             uint32_t tags_per_frame, agx_tag *d_tags, uint32_t *d_n_tags, uint32_t *d_tag_status, int reset);
+/* One frame and one round of the same (src/detector.rs:510-539) in HOST memory, without a detector handle (no device needed,
+ * like agx_find_board_tail): family as in agx_detector_create; quads [n_quads][4] and board_status as agx_find_board_tail
+ * answered (n_quads is not read unless that is AGX_BOARD_FOUND), quad_tags / quad_status [n_quads] as agx_decode_quads_tail did;
+ * point_status: n_slots words, or NULL; tags [tag_cap], *n_tags and *tag_status in and out -- the caller zeroes the last two
+ * for the first round.  Statuses and everything else as the batch call's.  AGX_ERR_ARG: a NULL n_tags or tag_status, tag_cap
+ * == 0 or NULL tags, NULL quads, quad_tags or quad_status with an AGX_BOARD_FOUND count above 0; AGX_ERR_FAMILY. */
+int agx_collect_tags_tail(int family, uint32_t n_quads, const uint32_t *quads, uint32_t board_status,
+                          const agx_tag *quad_tags, const uint32_t *quad_status, uint32_t n_slots, uint32_t *point_status,
+                          uint32_t tag_cap, agx_tag *tags, uint32_t *n_tags, uint32_t *tag_status);
 
 /* ---- detector groups: several GPUs of one node driven from ONE process ----------------- */
 
