@@ -120,7 +120,8 @@ struct ChainArgs {
     // cluster records [n_frames][cap_roots]
     uint32_t *clu_key;    // smallest pixel index of the cluster
     uint32_t *clu_cnt;
-    uint32_t *clu_sx, *clu_sy;  // integer coordinate sums (K4 leaves the f32 centroid bits here)
+    // integer coordinate sums, on the generic path their low words (K4 leaves the f32 centroid bits here)
+    uint32_t *clu_sx, *clu_sy;
     // generic path: candidate arrays [n_frames][cap_cand]
     uint32_t *cand;    // pixel index | left<<30 | up<<31
     uint32_t *parent;

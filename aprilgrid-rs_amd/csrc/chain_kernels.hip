@@ -1959,16 +1959,27 @@ __device__ __forceinline__ void generic_frame(const ChainArgs &a, int frame)
         const size_t q = (size_t)frame * a.cap_roots + i;
         a.clu_key[q] = __hip_atomic_load(&a.minidx[base + s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         a.clu_cnt[q] = __hip_atomic_load(&a.cnt[base + s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // the cluster record keeps 32 bits; a sum beyond that saturates (>= 2^24: K4 raises FLAG_CENTROID_INEXACT)
-        const unsigned long long sx64 = __hip_atomic_load(&a.sumx[base + s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long sy64 = __hip_atomic_load(&a.sumy[base + s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        a.clu_sx[q] = sx64 > 0xffffffffull ? 0xffffffffu : (uint32_t)sx64;
-        a.clu_sy[q] = sy64 > 0xffffffffull ? 0xffffffffu : (uint32_t)sy64;
+        // the cluster record keeps the low 32 bits; what reads a generic frame's sums (k_generic_cluster's centroids, rare_frame's
+        // refine_cluster) takes all 64 from the root's words: generic_sums
+        a.clu_sx[q] = (uint32_t)__hip_atomic_load(&a.sumx[base + s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        a.clu_sy[q] = (uint32_t)__hip_atomic_load(&a.sumy[base + s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (t == 0) {
         ctr.n_clusters = nr;
         ctr.n_clusters2 = 0u;  // whatever the fast path's second tier appended is void
     }
+}
+
+
+// The exact coordinate sums of cluster record i of a frame generic_frame has just clustered (behind a phase_barrier): record i
+// is root a.roots[i] of phase 3, whose 64-bit sums stay where phase 3 added them.  One component of a caller's masked plane
+// passes 2^32 (64 rows of 11 585 columns do).
+__device__ __forceinline__ void generic_sums(const ChainArgs &a, int frame, uint32_t i, unsigned long long &sx, unsigned long long &sy)
+{
+    const size_t base = (size_t)frame * a.cap_cand;
+    const uint32_t s = __hip_atomic_load(&a.roots[(size_t)frame * a.cap_roots + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    sx = __hip_atomic_load(&a.sumx[base + s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    sy = __hip_atomic_load(&a.sumy[base + s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 
@@ -2035,9 +2046,9 @@ struct RecSinkLds {
     }
 };
 
-template <bool VEC, typename CLK, typename SINK>
+template <bool VEC, typename CLK, typename SINK, typename SUM>
 __device__ __forceinline__ void refine_values(const ChainArgs &a, const RefineConsts &rc, int frame, const float *img, int W, int H,
-                                              uint32_t key, uint32_t cn, uint32_t sx, uint32_t sy, const SINK &sink, float &cx,
+                                              uint32_t key, uint32_t cn, SUM sx, SUM sy, const SINK &sink, float &cx,
                                               float &cy, CLK &clk)
 {
     if (sx >= (1u << 24) || sy >= (1u << 24)) atomicOr(sink.flags, FLAG_CENTROID_INEXACT);
@@ -2181,7 +2192,8 @@ __device__ __forceinline__ void refine_values(const ChainArgs &a, const RefineCo
 
 // The f32 centroid of a cluster from its size and integer coordinate sums, as refine_values forms it (detector.rs:427), for the
 // stages that cluster without refining.
-__device__ __forceinline__ void cluster_centroid(uint32_t *flags, uint32_t cn, uint32_t sx, uint32_t sy, float &cx, float &cy)
+template <typename SUM>
+__device__ __forceinline__ void cluster_centroid(uint32_t *flags, uint32_t cn, SUM sx, SUM sy, float &cx, float &cy)
 {
     if (sx >= (1u << 24) || sy >= (1u << 24)) atomicOr(flags, FLAG_CENTROID_INEXACT);
     const float fn = (float)cn;
@@ -2189,7 +2201,7 @@ __device__ __forceinline__ void cluster_centroid(uint32_t *flags, uint32_t cn, u
     cy = (float)sy / fn;
 }
 
-// rochade_refine of cluster record s of `frame` as it stands in the cluster table.
+// rochade_refine of cluster record s of `frame` as generic_frame left it (its sums: generic_sums).
 template <bool VEC>
 __device__ __forceinline__ void refine_cluster(const ChainArgs &a, const RefineConsts &rc, int frame, size_t cbase,
                                                const float *img, int W, int H, uint32_t s, uint32_t *n_refined,
@@ -2198,8 +2210,9 @@ __device__ __forceinline__ void refine_cluster(const ChainArgs &a, const RefineC
     float cx, cy;
     NoClock clk;
     const RecSinkGlobal sink{n_refined, max_k_bits, &a.ctr[frame].flags};
-    refine_values<VEC>(a, rc, frame, img, W, H, a.clu_key[cbase + s], a.clu_cnt[cbase + s], a.clu_sx[cbase + s], a.clu_sy[cbase + s],
-                       sink, cx, cy, clk);
+    unsigned long long sx, sy;
+    generic_sums(a, frame, s, sx, sy);
+    refine_values<VEC>(a, rc, frame, img, W, H, a.clu_key[cbase + s], a.clu_cnt[cbase + s], sx, sy, sink, cx, cy, clk);
     a.clu_sx[cbase + s] = __float_as_uint(cx);  // kept for agx_debug_fetch
     a.clu_sy[cbase + s] = __float_as_uint(cy);
 }
@@ -3645,7 +3658,9 @@ __global__ void __launch_bounds__(1024) k_generic_cluster(ChainArgs a)
     const size_t cbase = (size_t)frame * a.cap_roots;
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
         float cx, cy;
-        cluster_centroid(&ctr.flags, a.clu_cnt[cbase + i], a.clu_sx[cbase + i], a.clu_sy[cbase + i], cx, cy);
+        unsigned long long sx, sy;
+        generic_sums(a, frame, i, sx, sy);
+        cluster_centroid(&ctr.flags, a.clu_cnt[cbase + i], sx, sy, cx, cy);
         a.clu_sx[cbase + i] = __float_as_uint(cx);
         a.clu_sy[cbase + i] = __float_as_uint(cy);
     }

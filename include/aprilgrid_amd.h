@@ -603,8 +603,8 @@ typedef struct agx_cluster_info {
  * 4-connected components of v < thr (init_saddle_clusters / pixel_bfs, :171-187, src/image_util.rs:208-236), one cluster per
  * component in the order of its first pixel in the raster scan, and the centroid map (:421-429): agx_cluster_info =
  * {first_index = y*width + x of that pixel, size, cx, cy}.  cx, cy are the reference's bit for bit while the coordinate sums
- * stay below 2^24; beyond that they are the quotients of the exact integer sums and AGX_CLUSTERS_INEXACT is set (as
- * AGX_FRAME_CENTROID_INEXACT).
+ * stay below 2^24; beyond that they are the quotients of the exact integer sums -- f32(sum) / f32(size), the sums held in
+ * 64 bits: one component of a masked plane passes 2^32 -- and AGX_CLUSTERS_INEXACT is set (as AGX_FRAME_CENTROID_INEXACT).
  * The outermost ring: the reference scans seeds in the interior only but lets a flood run into the ring where a ring pixel is
  * below thr; a component's first scanned pixel is then not its smallest pixel.  That is not emulated: a frame with any ring
  * pixel below thr is refused -- AGX_CLUSTERS_BORDER, count 0, no row -- and the other frames of the batch are unaffected.

@@ -153,3 +153,64 @@ def members(plane, first_index):
 
 def batch(names):
     return np.stack([CASES[n]() for n in names])
+
+
+# ---- coordinate sums at 2^24 and beyond 2^32 --------------------------------------------------------------------------------
+# Planes of their own sizes (not BATCHES' 160 x 96): one large component -- full rows of `width` columns from (1, 1), a partial
+# row below them and one more pixel below that, which tunes the sum -- whose sum of x (or, transposed, of y) is the target, and
+# a small cluster (three pixels, the frame minimum among them) beside it.  Every component is far beyond a wave's 128 x 64
+# window: the generic path.
+def _sum_plane(target, width):
+    """-> plane [rows + 4, width + 6] whose large component has sum of x == target."""
+    row = width * (width + 1) // 2            # x = 1 .. width
+    full, rest = divmod(target, row)
+    m = int((np.sqrt(8.0 * rest + 1.0) - 1.0) / 2.0)  # the partial row: x = 1 .. m
+    while m * (m + 1) // 2 > rest:
+        m -= 1
+    tune = rest - m * (m + 1) // 2            # the last pixel's x, below the partial row
+    assert 1 <= tune <= m <= width and full >= 1, (target, width, full, m, tune)
+    p = np.zeros((full + 4, width + 6), np.float32)
+    p[1:1 + full, 1:1 + width] = LOW
+    p[1 + full, 1:1 + m] = LOW
+    p[2 + full, tune] = LOW
+    p[1, width + 2] = MIN                     # the small cluster: columns width + 2 .. width + 3 (column width + 1 separates)
+    p[1, width + 3] = LOW
+    p[2, width + 3] = LOW
+    return p
+
+
+E24 = 1 << 24
+WIDE_CASES = {
+    "sum x 2^24 - 1": lambda: _sum_plane(E24 - 1, 1024),
+    "sum x 2^24": lambda: _sum_plane(E24, 1024),
+    "sum x 2^24 + 1": lambda: _sum_plane(E24 + 1, 1024),
+    "sum y 2^24 - 1": lambda: np.ascontiguousarray(_sum_plane(E24 - 1, 1024).T),
+    "sum y 2^24": lambda: np.ascontiguousarray(_sum_plane(E24, 1024).T),
+    "sum y 2^24 + 1": lambda: np.ascontiguousarray(_sum_plane(E24 + 1, 1024).T),
+    # 64 full rows of w columns from x = 1 sum to 32 w (w + 1): beyond 2^32 from w = WIDTH_32 = 11585 on (11584 * 11585 < 2^27 <
+    # 11585 * 11586); the target just beyond 2^32 takes 63 full rows of that width and most of the 64th
+    "sum x beyond 2^32": lambda: _sum_plane((1 << 32) + 4097, WIDTH_32),
+}
+WIDTH_32 = 11585
+WIDE_CANDIDATES = 1 << 20  # agx_detector_set_limits: the largest plane has 741 412 pixels below thr, the default list holds half a plane
+
+
+@functools.lru_cache(maxsize=None)
+def wide_expected(name):
+    """-> (rows, status, sums): first index and size from the oracle's components; the centre f32(exact integer sum) / f32(size)
+    (DESIGN section 3), which below 2^24 is the oracle's own; AGX_CLUSTERS_INEXACT from the sums.  sums[i] = (sum x, sum y)."""
+    plane = WIDE_CASES[name]()
+    assert not ring_below(plane)
+    rows = oracle_rows(plane).copy()
+    sums = []
+    for r in rows:
+        m = members(plane, r["first_index"])
+        assert len(m) == r["size"] and int(r["first_index"]) == int((m[:, 1] * plane.shape[1] + m[:, 0]).min())
+        sx, sy = int(m[:, 0].sum()), int(m[:, 1].sum())
+        sums.append((sx, sy))
+        if sx >= E24 or sy >= E24:
+            r["cx"] = np.float32(sx) / np.float32(r["size"])  # (an integer below 2^53 -> float32: one rounding)
+            r["cy"] = np.float32(sy) / np.float32(r["size"])
+    status = OK | (INEXACT if any(max(s) >= E24 for s in sums) else 0)
+    rows.setflags(write=False)
+    return rows, status, sums

@@ -1,5 +1,6 @@
 """tests/cluster_cases.py from the oracle alone: every hand-built plane is what its name says (sizes and bounding boxes of the
-oracle's components), no coordinate sum reaches 2^24, and the host form of the k / phi filter (agx_filter_saddles_tail) is
+oracle's components), no coordinate sum of the 160 x 96 planes reaches 2^24, the planes of K.WIDE_CASES have the sums they name
+and the centres of the exact integer sums, and the host form of the k / phi filter (agx_filter_saddles_tail) is
 src/detector.rs:432-445."""
 import numpy as np
 
@@ -81,6 +82,49 @@ def test_no_coordinate_sum_reaches_2_to_24_and_centroids_are_the_quotients():
         for r, c in zip(rows, boxes(name)):
             assert c[6] < 1 << 24 and c[7] < 1 << 24
             assert r["cx"] == np.float32(c[6]) / np.float32(c[1]) and r["cy"] == np.float32(c[7]) / np.float32(c[1])
+
+
+# ---- sums at 2^24 and beyond 2^32 (K.WIDE_CASES) -----------------------------------------------------------------------------
+def test_wide_planes_have_the_sums_they_name_and_the_centres_of_the_exact_sums():
+    want = {"sum x 2^24 - 1": (0, K.E24 - 1), "sum x 2^24": (0, K.E24), "sum x 2^24 + 1": (0, K.E24 + 1),
+            "sum y 2^24 - 1": (1, K.E24 - 1), "sum y 2^24": (1, K.E24), "sum y 2^24 + 1": (1, K.E24 + 1),
+            "sum x beyond 2^32": (0, (1 << 32) + 4097)}
+    assert sorted(want) == sorted(K.WIDE_CASES)
+    for name, (axis, total) in want.items():
+        plane = K.WIDE_CASES[name]()
+        rows, status, sums = K.wide_expected(name)
+        orc = K.oracle_rows(plane)
+        assert len(rows) == 2 and rows["first_index"].tobytes() == orc["first_index"].tobytes() and rows["size"].tobytes() == orc["size"].tobytes()
+        big, small = (0, 1) if rows["size"][0] > rows["size"][1] else (1, 0)
+        assert sums[big][axis] == total, (name, sums)                       # the sum the name says, exactly
+        m = K.members(plane, rows["first_index"][big])
+        assert np.ptp(m[:, 0]) + 1 > 128 or np.ptp(m[:, 1]) + 1 > 64          # beyond a wave's window: the generic path
+        assert rows["size"][small] == 3 and max(sums[small]) < K.E24
+        assert rows[small].tobytes() == orc[small].tobytes()                 # the small cluster: the oracle's centre, always
+        m, thr = K.threshold(plane)
+        assert m == K.MIN and thr == np.float32(-5.0) and not K.ring_below(plane)
+        if max(sums[big]) < K.E24:
+            assert status == K.OK and rows.tobytes() == orc.tobytes()        # below 2^24: the oracle's rows bit for bit
+        else:
+            assert status == K.OK | K.INEXACT
+            assert rows["cx"][big] == np.float32(sums[big][0]) / np.float32(rows["size"][big])
+            assert rows["cy"][big] == np.float32(sums[big][1]) / np.float32(rows["size"][big])
+            # the reference's f32 running sums: near the exact centre, not on it
+            assert abs(float(rows["cx"][big]) - float(orc["cx"][big])) < 0.5 and abs(float(rows["cy"][big]) - float(orc["cy"][big])) < 0.5
+    # the other sum of the three planes around 2^24 stays below it: the flag comes from the named sum alone
+    for name in list(want)[:6]:
+        axis = want[name][0]
+        assert K.wide_expected(name)[2][0][1 - axis] < K.E24
+    # 2^32: the smallest width at which 64 full rows pass it, and a sum that no 32-bit word holds
+    w = K.WIDTH_32
+    assert 64 * (w - 1) * w // 2 < 1 << 32 <= 64 * w * (w + 1) // 2
+    plane = K.WIDE_CASES["sum x beyond 2^32"]()
+    assert plane.shape[1] == w + 6 and plane.nbytes < 3.2e6 and int((plane < -5).sum()) < K.WIDE_CANDIDATES
+    rows, status, sums = K.wide_expected("sum x beyond 2^32")
+    assert sums[0][0] > 0xFFFFFFFF
+    saturated = np.float32(0xFFFFFFFF) / np.float32(rows["size"][0])       # what a sum saturated at 2^32 - 1 gives
+    wrapped = np.float32(sums[0][0] & 0xFFFFFFFF) / np.float32(rows["size"][0])  # ... and one truncated to 32 bits
+    assert rows["cx"][0] != saturated and rows["cx"][0] != wrapped
 
 
 # ---- agx_filter_saddles_tail --------------------------------------------------------------------------------------------------

@@ -213,6 +213,43 @@ def test_fetch_copies_points_from_where_the_batch_wrote_them(det):
     assert h_pts2.tobytes() == h_pts.tobytes()
 
 
+# ---- 1b. coordinate sums at 2^24 and beyond 2^32 ----------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def wide_det():
+    import aprilgrid_rs_amd as A
+    d = A.TagDetector("t36h11", None, device=0)
+    d.set_limits(max_candidates=K.WIDE_CANDIDATES)  # (the largest plane is one component of 741 412 pixels: more than half a plane)
+    yield d
+    d.close()
+
+
+@pytest.mark.parametrize("name", sorted(K.WIDE_CASES))
+def test_centres_are_the_quotients_of_the_exact_integer_sums(wide_det, name):
+    """First index and size are the oracle's, the centre is f32(exact integer sum) / f32(size) -- the oracle's own below 2^24 --
+    and AGX_CLUSTERS_INEXACT is set from 2^24 on and not below; the small cluster beside the large one has the oracle's centre.
+    Caller-owned arrays, the same under force_generic, and the host form agx_cluster_centers."""
+    want, wst, sums = K.wide_expected(name)
+    plane = K.WIDE_CASES[name]()
+    planes = dev(plane[None])
+    got = []
+    for generic in (0, 1):
+        wide_det.set_option("force_generic", generic)
+        try:
+            rows, pts, counts, status = run_caller_owned(wide_det, planes, cpf=8)
+        finally:
+            wide_det.set_option("force_generic", 0)
+        what = "%s, force_generic %d" % (name, generic)
+        assert int(status[0]) == wst, "%s: status %#x, expected %#x" % (what, status[0], wst)
+        assert int(counts[0]) == len(want) == 2
+        assert rows[0, :2].tobytes() == want.tobytes(), "%s: rows %s, expected %s" % (what, rows[0, :2], want)
+        assert bits_equal(pts[0, :2, 0], want["cx"]) and bits_equal(pts[0, :2, 1], want["cy"])
+        assert (rows[0, 2:].view(np.uint32) == SENT).all() and (pts[0, 2:] == np.float32(SENT_F)).all()
+        got.append(rows.tobytes() + status.tobytes())
+    assert got[0] == got[1]
+    r, st, n = wide_det.cluster_centers(plane, cap=8)
+    assert (st, n) == (wst, 2) and r.tobytes() == want.tobytes(), name + ": the host form"
+
+
 # ---- 2. behind agx_planes_enqueue: the fused chain's cluster table, saddles and tags -----------------------------------------
 @pytest.fixture(scope="module")
 def boards():
