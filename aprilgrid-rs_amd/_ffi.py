@@ -106,6 +106,14 @@ SYMBOLS = {
     "agx_decode_quads_fetch": (C.c_int, [_P, _P, _P, _P]),
     "agx_decode_quads": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32)]),
     "agx_decode_quads_tail": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_size_t, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32)]),
+    "agx_decode_positions_enqueue": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_float,
+                                               _P, _P]),
+    "agx_decode_positions_tail": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_float, _P, _P]),
+    "agx_bit_code_enqueue": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, _P, C.c_uint32, C.c_uint32, _P, _P,
+                                       C.c_int, C.c_uint32, _P, _P]),
+    "agx_bit_code_tail": (C.c_int, [_P, C.c_int, C.c_int, C.c_size_t, _P, C.c_uint32, C.c_uint32, _P, C.c_int, C.c_uint32, _P, _P]),
+    "agx_best_tag_enqueue": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_int, _P, C.c_uint32, C.c_int, _P, C.c_size_t, _P, _P, _P, _P]),
+    "agx_best_tag_tail": (C.c_int, [_P, C.c_uint32, _P, C.c_int, C.c_int, _P, C.c_uint32, C.c_int, _P, _P, _P, _P, _P]),
     "agx_find_boards_enqueue": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
     "agx_find_boards_fetch": (C.c_int, [_P, _P, _P, _P, _P, C.c_int]),
     "agx_find_board": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -25,6 +26,7 @@
 #include "../../include/aprilgrid_amd.h"
 #include "detector_internal.h"
 #include "host_tail.hpp"
+#include "decode_stages.h"
 #include "tail_kernels.h"
 
 namespace agx {
@@ -1066,6 +1068,147 @@ int agx::decode_quads_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *stat
             if (bits) std::memcpy(bits + s0, h.data() + s0, n * sizeof(uint64_t));
         }
     }
+    return AGX_OK;
+}
+
+// ---- the decode in three stages (decode_stages.hip): decode_positions (src/detector.rs:42-72), bit_code (:74-122), best_tag
+// (:142-169) on caller-owned device arrays.  Like agx_filter_saddles_enqueue: every argument is checked before begin_batch, the
+// launch replaces the batch in flight, and there is nothing to fetch.
+static bool decode_stage_stride_ok(size_t point_stride_bytes)
+{
+    return point_stride_bytes >= 8 && !(point_stride_bytes & 3) && point_stride_bytes <= 0x7fffffffu;
+}
+
+bool agx::decode_square_ok(int border_bits, int edge_bits, float margin)
+{
+    if (edge_bits < 1 || edge_bits > 8 || border_bits < 0 || border_bits > 16 || !std::isfinite(margin)) return false;
+    const float S = (float)(border_bits * 2 + edge_bits) - 1.0f + margin;  // image_util.rs:39-70: the square's far side ...
+    return S != -margin;                                                   // ... and its near side: equal, the square is a point
+}
+
+int agx::decode_positions_enqueue_impl(agx_detector *det, const void *d_quads, size_t point_stride_bytes, int n_frames, uint32_t quads_per_frame,
+                                       const uint32_t *d_counts, const uint32_t *d_point_status, uint32_t img_w, uint32_t img_h, int border_bits,
+                                       int edge_bits, float margin, float *d_points, uint32_t *d_status)
+{
+    if (!det) return AGX_ERR_ARG;
+    if (!d_quads || !d_points || !d_status || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null quads, points or status, or n_frames <= 0");
+    if (!quads_per_frame) return fail(det, AGX_ERR_ARG, "quads_per_frame must be > 0");
+    if (!decode_stage_stride_ok(point_stride_bytes)) return fail(det, AGX_ERR_ARG, "point_stride_bytes must be a multiple of 4 and at least 8");
+    if (((uintptr_t)d_quads | (uintptr_t)d_counts | (uintptr_t)d_point_status | (uintptr_t)d_points | (uintptr_t)d_status) & 3)
+        return fail(det, AGX_ERR_ARG, "quads, counts, point statuses, points and statuses must be 4-byte aligned");
+    if (!decode_square_ok(border_bits, edge_bits, margin))
+        return fail(det, AGX_ERR_ARG, "edge_bits 1 .. 8, border_bits 0 .. 16, a finite margin and a source square that is not a point");
+    if ((size_t)n_frames * quads_per_frame >= ((size_t)1 << 29)) return fail(det, AGX_ERR_ARG, "at most 2^29 - 1 quads per batch");
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // and there is nothing of this one to be fetched
+    DecodePositionsArgs p{};
+    p.quads = static_cast<const uint8_t *>(d_quads);
+    p.point_stride = (uint32_t)point_stride_bytes;
+    p.n_frames = n_frames;
+    p.quads_per_frame = quads_per_frame;
+    p.counts = d_counts;
+    p.point_status = d_point_status;
+    p.W = img_w;
+    p.H = img_h;
+    p.border = border_bits;
+    p.edge = edge_bits;
+    p.margin = margin;
+    p.points = d_points;
+    p.status = d_status;
+    const hipError_t e = (hipError_t)launch_decode_positions(p, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_decode_positions: ") + hipGetErrorString(e));
+    return AGX_OK;
+}
+
+int agx::bit_code_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                               size_t frame_stride_bytes, int format, const float *d_points, uint32_t points_per_slot, uint32_t quads_per_frame,
+                               const uint32_t *d_counts, const uint32_t *d_status_in, int valid_brightness_threshold, uint32_t max_invalid_bit,
+                               uint64_t *d_bits, uint32_t *d_status)
+{
+    if (!det) return AGX_ERR_ARG;
+    if (!d_frames || !d_points || !d_bits || !d_status || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null frames, points, bits or status, or n_frames <= 0");
+    if (!quads_per_frame) return fail(det, AGX_ERR_ARG, "quads_per_frame must be > 0");
+    if (points_per_slot < 1 || points_per_slot > 64) return fail(det, AGX_ERR_ARG, "points_per_slot must be 1 .. 64");
+    if (valid_brightness_threshold < 0 || valid_brightness_threshold > 255) return fail(det, AGX_ERR_ARG, "valid_brightness_threshold must be 0 .. 255");
+    if ((((uintptr_t)d_points | (uintptr_t)d_counts | (uintptr_t)d_status_in | (uintptr_t)d_status) & 3) || ((uintptr_t)d_bits & 7))
+        return fail(det, AGX_ERR_ARG, "points, counts and statuses must be 4-byte aligned, bits 8-byte aligned");
+    if (const int rc = check_frame_batch(det, {d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format},
+                                         {/*min_side*/ 1, /*lf32*/ false, /*lone_frame_stride*/ false, /*align16*/ true, /*front_rows*/ true}))
+        return rc;
+    if ((size_t)n_frames * quads_per_frame >= ((size_t)1 << 29)) return fail(det, AGX_ERR_ARG, "at most 2^29 - 1 slots per batch");
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // (SB_LUMA_D may grow below: nothing points into it any more)
+    const uint8_t *d_luma = static_cast<const uint8_t *>(d_frames);  // detector.rs:507: L8 frames are their own u8 luma
+    size_t luma_row = row_stride_bytes, luma_frame = frame_stride_bytes;
+    if (format != AGX_L8) {
+        if (chunk_luma8(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, 0, 1, (size_t)n_frames, nullptr, &d_luma))
+            return fail(det, AGX_ERR_HIP, "to_luma8 of the frames on the device");
+        luma_row = (size_t)width;
+        luma_frame = (size_t)width * (size_t)height;
+    }
+    BitCodeArgs b{};
+    b.luma = d_luma;
+    b.luma_frame_stride = (long long)luma_frame;
+    b.luma_row_stride = (int)luma_row;
+    b.W = width;
+    b.H = height;
+    b.n_frames = n_frames;
+    b.points = d_points;
+    b.points_per_slot = points_per_slot;
+    b.quads_per_frame = quads_per_frame;
+    b.counts = d_counts;
+    b.status_in = d_status_in;
+    b.threshold = valid_brightness_threshold;
+    b.max_invalid = max_invalid_bit;
+    b.bits = d_bits;
+    b.status = d_status;
+    const hipError_t e = (hipError_t)launch_bit_code(b, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_bit_code: ") + hipGetErrorString(e));
+    return AGX_OK;
+}
+
+int agx::best_tag_enqueue_impl(agx_detector *det, const uint64_t *d_bits, uint32_t n_slots, uint32_t quads_per_frame, const uint32_t *d_counts,
+                               const uint32_t *d_status_in, int thres, const uint64_t *d_codes, uint32_t n_codes, int edge_bits, const void *d_quads,
+                               size_t point_stride_bytes, uint32_t *d_ids, uint32_t *d_rotations, uint32_t *d_status, agx_tag *d_tags)
+{
+    if (!det) return AGX_ERR_ARG;
+    if (!d_bits || !d_ids || !d_rotations || !d_status) return fail(det, AGX_ERR_ARG, "null bits, ids, rotations or status");
+    if (!n_slots || n_slots >= (1u << 31)) return fail(det, AGX_ERR_ARG, "n_slots must be 1 .. 2^31 - 1");
+    if (d_counts && (!quads_per_frame || n_slots % quads_per_frame)) return fail(det, AGX_ERR_ARG, "d_counts: n_slots must be a multiple of quads_per_frame");
+    if (thres < 0 || thres > 255) return fail(det, AGX_ERR_ARG, "thres must be 0 .. 255");
+    if (d_codes ? (n_codes < 1 || n_codes > 65535) : n_codes != 0)
+        return fail(det, AGX_ERR_ARG, "d_codes with n_codes 1 .. 65535, or NULL with 0 (the handle's family list)");
+    if (edge_bits < 1 || edge_bits > 8) return fail(det, AGX_ERR_ARG, "edge_bits must be 1 .. 8");
+    if ((d_quads == nullptr) != (d_tags == nullptr)) return fail(det, AGX_ERR_ARG, "d_quads and d_tags: both or neither");
+    if (d_quads && !decode_stage_stride_ok(point_stride_bytes)) return fail(det, AGX_ERR_ARG, "point_stride_bytes must be a multiple of 4 and at least 8");
+    if ((((uintptr_t)d_counts | (uintptr_t)d_status_in | (uintptr_t)d_quads | (uintptr_t)d_ids | (uintptr_t)d_rotations | (uintptr_t)d_status | (uintptr_t)d_tags) & 3) ||
+        (((uintptr_t)d_bits | (uintptr_t)d_codes) & 7))
+        return fail(det, AGX_ERR_ARG, "counts, statuses, quads, ids, rotations and tags must be 4-byte aligned, bits and codes 8-byte aligned");
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // and there is nothing of this one to be fetched
+    if (!d_codes) {
+        if (tail_prepare(det)) return fail(det, AGX_ERR_HIP, "hipMalloc / hipMemcpy: the family's code list");
+        d_codes = det->side[SB_CODES].ptr<uint64_t>();
+        n_codes = (uint32_t)det->fam.n_codes;
+    }
+    BestTagArgs t{};
+    t.bits = d_bits;
+    t.n_slots = n_slots;
+    t.quads_per_frame = quads_per_frame;
+    t.counts = d_counts;
+    t.status_in = d_status_in;
+    t.thres = (uint32_t)thres;
+    t.codes = d_codes;
+    t.n_codes = n_codes;
+    t.edge = edge_bits;
+    t.quads = static_cast<const uint8_t *>(d_quads);
+    t.point_stride = (uint32_t)point_stride_bytes;
+    t.ids = d_ids;
+    t.rotations = d_rotations;
+    t.status = d_status;
+    t.tags = d_tags;
+    const hipError_t e = (hipError_t)launch_best_tag(t, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_best_tag: ") + hipGetErrorString(e));
     return AGX_OK;
 }
 

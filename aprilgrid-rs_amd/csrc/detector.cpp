@@ -16,6 +16,7 @@
 
 #include "../../include/aprilgrid_amd.h"
 #include "chain_kernels.h"
+#include "decode_stages.h"
 #include "detector_internal.h"
 #include "host_tail.hpp"
 #include "tail_kernels.h"
@@ -1478,6 +1479,131 @@ int agx_decode_quads_tail(int family, const uint8_t *luma8, int width, int heigh
         if (bits) bits[i] = b;
     }
     *n_decoded = n;
+    return AGX_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- the decode in three stages: decode_positions (src/detector.rs:42-72), bit_code (:74-122), best_tag (:142-169) -----------
+// (csrc/detect_batch.cpp, decode_stages.hip; the host forms run the functions decode_quad is made of, csrc/host_tail.cpp)
+extern "C" {
+
+int agx_decode_positions_enqueue(agx_detector *det, const void *d_quads, size_t point_stride_bytes, int n_frames, uint32_t quads_per_frame,
+                                 const uint32_t *d_counts, const uint32_t *d_point_status, uint32_t img_w, uint32_t img_h, int border_bits,
+                                 int edge_bits, float margin, float *d_points, uint32_t *d_status)
+{
+    return agx_guard(det, [&]() -> int {
+    return decode_positions_enqueue_impl(det, d_quads, point_stride_bytes, n_frames, quads_per_frame, d_counts, d_point_status, img_w, img_h,
+                                         border_bits, edge_bits, margin, d_points, d_status);
+    });
+}
+
+int agx_decode_positions_tail(const void *quads, uint32_t n_quads, uint32_t img_w, uint32_t img_h, int border_bits, int edge_bits, float margin,
+                              float *points, uint32_t *status)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if ((n_quads && (!quads || !points || !status)) || !decode_square_ok(border_bits, edge_bits, margin)) return AGX_ERR_ARG;
+    const size_t per_slot = (size_t)(2 * edge_bits * edge_bits);
+    for (uint32_t i = 0; i < n_quads; ++i) {
+        float q[8], pts[2 * 64];
+        std::memcpy(q, static_cast<const char *>(quads) + (size_t)i * sizeof q, sizeof q);
+        bool finite = true;
+        for (float v : q) finite = finite && std::isfinite(v);
+        // a coordinate that is not finite: AGX_QUAD_OUTSIDE before anything else (the reference's `as u32` would take NaN for 0)
+        const int why = finite ? decode_positions(img_w, img_h, q, border_bits, edge_bits, margin, pts) : (int)AGX_QUAD_OUTSIDE;
+        if (why == AGX_QUAD_DECODED) std::memcpy(points + (size_t)i * per_slot, pts, per_slot * sizeof(float));
+        status[i] = (uint32_t)why;
+    }
+    return AGX_OK;
+    });
+}
+
+int agx_bit_code_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                         size_t frame_stride_bytes, int format, const float *d_points, uint32_t points_per_slot, uint32_t quads_per_frame,
+                         const uint32_t *d_counts, const uint32_t *d_status_in, int valid_brightness_threshold, uint32_t max_invalid_bit,
+                         uint64_t *d_bits, uint32_t *d_status)
+{
+    return agx_guard(det, [&]() -> int {
+    return bit_code_enqueue_impl(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, d_points, points_per_slot,
+                                 quads_per_frame, d_counts, d_status_in, valid_brightness_threshold, max_invalid_bit, d_bits, d_status);
+    });
+}
+
+int agx_bit_code_tail(const uint8_t *luma8, int width, int height, size_t row_stride_bytes, const float *points, uint32_t points_per_slot,
+                      uint32_t n_slots, const uint32_t *status_in, int valid_brightness_threshold, uint32_t max_invalid_bit, uint64_t *bits,
+                      uint32_t *status)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (!luma8 || width < 1 || height < 1 || row_stride_bytes < (size_t)width || (n_slots && (!points || !bits || !status)) || points_per_slot < 1 ||
+        points_per_slot > 64 || valid_brightness_threshold < 0 || valid_brightness_threshold > 255)
+        return AGX_ERR_ARG;
+    for (uint32_t i = 0; i < n_slots; ++i) {
+        uint64_t b = 0;
+        uint32_t why = status_in ? status_in[i] : (uint32_t)AGX_QUAD_DECODED;
+        if (why == AGX_QUAD_DECODED) {
+            const float *pts = points + (size_t)i * 2 * points_per_slot;
+            bool finite = true;
+            for (uint32_t k = 0; k < 2 * points_per_slot; ++k) finite = finite && std::isfinite(pts[k]);
+            // a sample coordinate that is not finite: AGX_QUAD_OUTSIDE before any read, as for a quad's corners
+            why = finite ? (uint32_t)bit_code(luma8, (uint32_t)width, (uint32_t)height, row_stride_bytes, pts, (int)points_per_slot,
+                                              valid_brightness_threshold, max_invalid_bit, b)
+                         : (uint32_t)AGX_QUAD_OUTSIDE;
+        }
+        bits[i] = b;
+        status[i] = why;
+    }
+    return AGX_OK;
+    });
+}
+
+int agx_best_tag_enqueue(agx_detector *det, const uint64_t *d_bits, uint32_t n_slots, uint32_t quads_per_frame, const uint32_t *d_counts,
+                         const uint32_t *d_status_in, int thres, const uint64_t *d_codes, uint32_t n_codes, int edge_bits, const void *d_quads,
+                         size_t point_stride_bytes, uint32_t *d_ids, uint32_t *d_rotations, uint32_t *d_status, agx_tag *d_tags)
+{
+    return agx_guard(det, [&]() -> int {
+    return best_tag_enqueue_impl(det, d_bits, n_slots, quads_per_frame, d_counts, d_status_in, thres, d_codes, n_codes, edge_bits, d_quads,
+                                 point_stride_bytes, d_ids, d_rotations, d_status, d_tags);
+    });
+}
+
+int agx_best_tag_tail(const uint64_t *bits, uint32_t n_slots, const uint32_t *status_in, int thres, int family, const uint64_t *codes,
+                      uint32_t n_codes, int edge_bits, const void *quads, uint32_t *ids, uint32_t *rotations, uint32_t *status, agx_tag *tags)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if ((n_slots && (!bits || !ids || !rotations || !status)) || thres < 0 || thres > 255 || edge_bits < 1 || edge_bits > 8 ||
+        (codes ? (n_codes < 1 || n_codes > 65535) : n_codes != 0) || (quads == nullptr) != (tags == nullptr))
+        return AGX_ERR_ARG;
+    if (!codes) {
+        FamilyInfo fam;
+        if (!family_info(family, fam)) return AGX_ERR_FAMILY;
+        codes = fam.codes;
+        n_codes = (uint32_t)fam.n_codes;
+    }
+    for (uint32_t i = 0; i < n_slots; ++i) {
+        uint32_t why = status_in ? status_in[i] : (uint32_t)AGX_QUAD_DECODED;
+        int idx = 0, rot = 0;
+        if (why == AGX_QUAD_DECODED && !best_tag(bits[i], thres, codes, (int)n_codes, edge_bits, idx, rot)) {
+            why = AGX_QUAD_NO_MATCH;
+            idx = rot = 0;
+        }
+        const bool hit = why == AGX_QUAD_DECODED;
+        ids[i] = hit ? (uint32_t)idx : 0u;
+        rotations[i] = hit ? (uint32_t)rot : 0u;
+        status[i] = why;
+        if (tags) {
+            agx_tag tag{};
+            if (hit) {  // rotate_left(rot) then reverse, :468-469
+                const float *q = static_cast<const float *>(quads) + (size_t)i * 8;
+                tag.id = (uint32_t)idx;
+                for (int c = 0; c < 4; ++c) {
+                    const int src = ((3 - c) + rot) & 3;
+                    std::memcpy(&tag.xy[2 * c], q + 2 * src, 2 * sizeof(float));
+                }
+            }
+            tags[i] = tag;
+        }
+    }
     return AGX_OK;
     });
 }

@@ -344,6 +344,19 @@ int decode_quads_enqueue_impl(agx_detector *det, const void *d_frames, int n_fra
                               uint32_t quads_per_frame, const uint32_t *d_counts, const uint32_t *d_point_status, agx_tag *d_tags,
                               uint32_t *d_status, uint64_t *d_bits);
 int decode_quads_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *status, uint64_t *bits);
+// the decode's three stages on caller-owned device arrays (detect_batch.cpp: k_decode_positions, to_luma8 + k_bit_code, k_best_tag)
+// edge_bits 1 .. 8, border_bits 0 .. 16, a finite margin and a source square of tag_affine that is not a point
+bool decode_square_ok(int border_bits, int edge_bits, float margin);
+int decode_positions_enqueue_impl(agx_detector *det, const void *d_quads, size_t point_stride_bytes, int n_frames, uint32_t quads_per_frame,
+                                  const uint32_t *d_counts, const uint32_t *d_point_status, uint32_t img_w, uint32_t img_h, int border_bits,
+                                  int edge_bits, float margin, float *d_points, uint32_t *d_status);
+int bit_code_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                          size_t frame_stride_bytes, int format, const float *d_points, uint32_t points_per_slot, uint32_t quads_per_frame,
+                          const uint32_t *d_counts, const uint32_t *d_status_in, int valid_brightness_threshold, uint32_t max_invalid_bit,
+                          uint64_t *d_bits, uint32_t *d_status);
+int best_tag_enqueue_impl(agx_detector *det, const uint64_t *d_bits, uint32_t n_slots, uint32_t quads_per_frame, const uint32_t *d_counts,
+                          const uint32_t *d_status_in, int thres, const uint64_t *d_codes, uint32_t n_codes, int edge_bits, const void *d_quads,
+                          size_t point_stride_bytes, uint32_t *d_ids, uint32_t *d_rotations, uint32_t *d_status, agx_tag *d_tags);
 // try_find_best_board of caller-given saddle lists over a batch in device memory (detect_batch.cpp: k_find_boards, the fetch)
 int find_boards_enqueue_impl(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
                              const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status, uint32_t quads_per_frame,

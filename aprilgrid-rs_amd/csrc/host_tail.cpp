@@ -1242,29 +1242,38 @@ bool best_tag(uint64_t bits, int thres, const uint64_t *codes, int n_codes, int 
     return best_tag_impl(bits, thres, codes, n_codes, edge_bits, idx, rot, [](uint64_t v) { return (unsigned)__builtin_popcountll(v); });
 }
 
-// try_decode_quad, src/detector.rs:448-476 (decode_positions :42-72, bit_code :74-122), with the reason it gave None for
-// (AGX_QUAD_*) and bit_code's value where there is one
-int decode_quad(const FamilyInfo &fam, const uint8_t *luma8, uint32_t w, uint32_t h, size_t stride,
-                const float quad_xy[8], int &tag_id, float corners[8], uint64_t &bits_out)
+// decode_positions, src/detector.rs:42-72: AGX_QUAD_OUTSIDE for None (:50-56), else AGX_QUAD_DECODED and the edge * edge sample
+// points, x outer and y inner (:60-70)
+int decode_positions(uint32_t w, uint32_t h, const float quad_xy[8], int border, int edge, float margin, float *pts)
 {
-    bits_out = 0;
     for (int i = 0; i < 4; ++i) {
         const uint32_t x = f32_as_u32(round_half_away(quad_xy[2 * i])), y = f32_as_u32(round_half_away(quad_xy[2 * i + 1]));
         if (x >= w || y >= h) return AGX_QUAD_OUTSIDE;
     }
     float aff[6];
-    tag_affine(quad_xy, fam.border * 2 + fam.edge, 0.5f, aff);
-    uint8_t samples[64];
-    int n = 0;
-    for (int gx = fam.border; gx < fam.border + fam.edge; ++gx)
-        for (int gy = fam.border; gy < fam.border + fam.edge; ++gy) {
+    tag_affine(quad_xy, border * 2 + edge, margin, aff);
+    for (int gx = border; gx < border + edge; ++gx)
+        for (int gy = border; gy < border + edge; ++gy) {
             const float fx = (float)gx, fy = (float)gy;
-            const float px = aff[0] * fx + aff[1] * fy + aff[2] * 1.0f;
-            const float py = aff[3] * fx + aff[4] * fy + aff[5] * 1.0f;
-            const uint32_t ix = f32_as_u32(round_half_away(px)), iy = f32_as_u32(round_half_away(py));
-            if (ix >= w || iy >= h) return AGX_QUAD_OUTSIDE;
-            samples[n++] = luma8[(size_t)iy * stride + ix];
+            *pts++ = aff[0] * fx + aff[1] * fy + aff[2] * 1.0f;
+            *pts++ = aff[3] * fx + aff[4] * fy + aff[5] * 1.0f;
         }
+    return AGX_QUAD_DECODED;
+}
+
+// bit_code, src/detector.rs:74-122, of n <= 64 sample points: AGX_QUAD_DECODED and the bits (the first point is the most
+// significant of the n), or the reason for None in the reference's order (AGX_QUAD_OUTSIDE :84-93, _LOW_CONTRAST :97-99,
+// _AMBIGUOUS :117-118); bits_out is 0 then
+int bit_code(const uint8_t *luma8, uint32_t w, uint32_t h, size_t stride, const float *pts, int n, int valid_brightness_threshold,
+             uint32_t max_invalid_bit, uint64_t &bits_out)
+{
+    bits_out = 0;
+    uint8_t samples[64];
+    for (int i = 0; i < n; ++i) {
+        const uint32_t ix = f32_as_u32(round_half_away(pts[2 * i])), iy = f32_as_u32(round_half_away(pts[2 * i + 1]));
+        if (ix >= w || iy >= h) return AGX_QUAD_OUTSIDE;
+        samples[i] = luma8[(size_t)iy * stride + ix];
+    }
     int lo = 255, hi = 0;
     for (int i = 0; i < n; ++i) {
         lo = std::min<int>(lo, samples[i]);
@@ -1276,10 +1285,26 @@ int decode_quad(const FamilyInfo &fam, const uint8_t *luma8, uint32_t w, uint32_
     uint32_t invalid = 0;
     for (int i = 0; i < n; ++i) {  // first sample is the most significant bit
         const int b = samples[n - 1 - i];
-        if (std::abs(mid - b) < 10) ++invalid;
+        if (std::abs(mid - b) < valid_brightness_threshold) ++invalid;
         if (b > mid) bits |= 1ull << i;
     }
-    if (invalid > 3) return AGX_QUAD_AMBIGUOUS;
+    if (invalid > max_invalid_bit) return AGX_QUAD_AMBIGUOUS;
+    bits_out = bits;
+    return AGX_QUAD_DECODED;
+}
+
+// try_decode_quad, src/detector.rs:448-476 (decode_positions :42-72, bit_code :74-122), with the reason it gave None for
+// (AGX_QUAD_*) and bit_code's value where there is one
+int decode_quad(const FamilyInfo &fam, const uint8_t *luma8, uint32_t w, uint32_t h, size_t stride,
+                const float quad_xy[8], int &tag_id, float corners[8], uint64_t &bits_out)
+{
+    bits_out = 0;
+    float pts[2 * 64];
+    int why = decode_positions(w, h, quad_xy, fam.border, fam.edge, 0.5f, pts);
+    if (why != AGX_QUAD_DECODED) return why;
+    uint64_t bits;
+    why = bit_code(luma8, w, h, stride, pts, fam.edge * fam.edge, 10, 3, bits);
+    if (why != AGX_QUAD_DECODED) return why;
     bits_out = bits;
     int idx, rot;
     if (!best_tag(bits, fam.hamming, fam.codes, fam.n_codes, fam.edge, idx, rot)) return AGX_QUAD_NO_MATCH;

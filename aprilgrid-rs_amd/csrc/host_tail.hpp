@@ -63,6 +63,16 @@ void tag_affine(const float quad_xy[8], int side_bits, float margin, float h[6])
 uint64_t rotate_bits(uint64_t bits, int edge_bits);
 bool best_tag(uint64_t bits, int thres, const uint64_t *codes, int n_codes, int edge_bits, int &idx, int &rot);
 
+// The stages decode_quad below is made of, with the crate's own arguments (agx_decode_positions_tail / agx_bit_code_tail;
+// k_decode_positions and k_bit_code are the device forms):
+// decode_positions, detector.rs:42-72: AGX_QUAD_OUTSIDE (None), or AGX_QUAD_DECODED and the edge * edge points (x, y) in pts, x
+// outer and y inner.  The corners are finite (the callers' rule) and the source square is not degenerate.
+int decode_positions(uint32_t w, uint32_t h, const float quad_xy[8], int border, int edge, float margin, float *pts);
+// bit_code, detector.rs:74-122, over n <= 64 points: AGX_QUAD_DECODED and the bits (first point = most significant of the n), or
+// AGX_QUAD_OUTSIDE / _LOW_CONTRAST / _AMBIGUOUS in the reference's order, bits 0
+int bit_code(const uint8_t *luma8, uint32_t w, uint32_t h, size_t stride, const float *pts, int n, int valid_brightness_threshold,
+             uint32_t max_invalid_bit, uint64_t &bits);
+
 // try_decode_quad, detector.rs:448-476, of one quad (x, y of its four corners) on the u8 luma plane: AGX_QUAD_DECODED with the
 // code's index and the corners after rotate_left(rotation); reverse() (:467-470), or the reason for None (AGX_QUAD_OUTSIDE,
 // _LOW_CONTRAST, _AMBIGUOUS, _NO_MATCH); bits = bit_code's value before any rotation (DECODED and NO_MATCH; else 0).

@@ -10,6 +10,8 @@ Same names, argument meaning and error behaviour as the reference where Python a
   TagDetector.detect_kornia           src/detector.rs:478-503
   TagDetector.rochade_refine          src/detector.rs:194-361 (the crate's pub fn, half_size_patch = 2)
   TagDetector.decode_quads            src/detector.rs:448-476 (try_decode_quad = the pub fns decode_positions, bit_code, best_tag)
+  decode_positions, bit_code, best_tag  src/detector.rs:42-72, :74-122, :142-169 (the three pub fns themselves; on device tensors
+                                      TagDetector.decode_positions_enqueue / bit_code_enqueue / best_tag_enqueue / decode_quads_staged)
   TagDetector.find_board              src/detector.rs:588-639 (the crate's pub fn try_find_best_board)
   TagDetector.detect_staged           src/detector.rs:505-540 as the staged chain on device tensors; its rounds (:510-539) by
                                       TagDetector.collect_tags_enqueue / collect_tags
@@ -756,6 +758,159 @@ class TagDetector:
         self._check(self._lib.agx_decode_quads_fetch(self._h, out.ctypes.data, status.ctypes.data, bits.ctypes.data))
         return out, status, bits
 
+    # ---- the decode in three stages: decode_positions, bit_code, best_tag (src/detector.rs:42-72, :74-122, :142-169) --------
+    def _family_info(self):
+        """-> (edge_bits, border_bits, hamming_distance, n_codes) of the handle's family (src/detector.rs:369-405)."""
+        e, b, hd, n = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self._lib.agx_detector_family_info(self._h, C.byref(e), C.byref(b), C.byref(hd), None, C.byref(n)))
+        return e.value, b.value, hd.value, n.value
+
+    @staticmethod
+    def _stage_tensor(t, dtype, shape, what, dev):
+        if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and (shape is None or tuple(t.shape) == shape)
+                and t.device == dev):
+            raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s device tensor %s on the batch's device" % (what, dtype, shape))
+        return t.data_ptr()
+
+    def _stage_quads(self, quads, refined):
+        """quads [N,Q,4,2] / [N,Q,8], or refined=(records [N,4Q,5], point_status [N,4Q]) -> (n, qpf, stride, p_quads, p_point_status, dev)"""
+        import torch
+        if (quads is None) == (refined is None):
+            raise AgxError(_ffi.AGX_ERR_ARG, "quads or refined=(records, point_status): one of them")
+        if refined is not None:
+            records, point_status = refined
+            if not (getattr(records, "is_cuda", False) and records.dim() == 3 and records.shape[1] % 4 == 0 and records.shape[1] > 0
+                    and records.shape[2] == 5):
+                raise AgxError(_ffi.AGX_ERR_ARG, "refined records must be a device tensor [N, 4 Q, 5]")
+            n, qpf, dev = int(records.shape[0]), int(records.shape[1]) // 4, records.device
+            return (n, qpf, 20, self._stage_tensor(records, torch.float32, (n, 4 * qpf, 5), "refined records", dev),
+                    self._stage_tensor(point_status, torch.int32, (n, 4 * qpf), "refined point status", dev), dev)
+        if not (getattr(quads, "is_cuda", False) and quads.dim() in (3, 4) and quads.shape[1] > 0 and tuple(quads.shape[2:]) in ((8,), (4, 2))):
+            raise AgxError(_ffi.AGX_ERR_ARG, "quads must be a device tensor [N, Q, 4, 2] or [N, Q, 8]")
+        n, qpf, dev = int(quads.shape[0]), int(quads.shape[1]), quads.device
+        return n, qpf, 8, self._stage_tensor(quads, torch.float32, tuple(quads.shape), "quads", dev), None, dev
+
+    def _replaces_batch(self):
+        self._batch = self._detect = self._refine = self._decode = self._find = self._clusters = None
+
+    def decode_positions_enqueue(self, quads=None, points=None, status=None, img_size=None, border_bits=None, edge_bits=None, margin=0.5,
+                                 counts=None, refined=None):
+        """decode_positions (src/detector.rs:42-72) of every quad slot, stream-ordered behind torch's current stream; nothing to
+        fetch.  quads / refined= / counts as decode_quads_enqueue; img_size=(width, height) the corners are tested against (no
+        pixel is read); border_bits, edge_bits default to the family's.  points float32 [N,Q,edge_bits^2,2]: the samples of the
+        slots whose status is AGX_QUAD_DECODED, x outer and y inner; status int32 [N,Q]: AGX_QUAD_DECODED / _OUTSIDE / _SKIPPED."""
+        import torch
+        n, qpf, stride, p_quads, p_ps, dev = self._stage_quads(quads, refined)
+        fam = self._family_info()
+        edge = fam[0] if edge_bits is None else int(edge_bits)
+        border = fam[1] if border_bits is None else int(border_bits)
+        if img_size is None:
+            raise AgxError(_ffi.AGX_ERR_ARG, "img_size=(width, height) must be given")
+        w, h = int(img_size[0]), int(img_size[1])
+        if not (0 <= w < 2 ** 32 and 0 <= h < 2 ** 32) or not 1 <= edge <= 8:
+            raise AgxError(_ffi.AGX_ERR_ARG, "img_size within uint32, edge_bits 1 .. 8")
+        p_points = self._stage_tensor(points, torch.float32, (n, qpf, edge * edge, 2), "points", dev)
+        p_status = self._stage_tensor(status, torch.int32, (n, qpf), "status", dev)
+        p_counts = self._stage_tensor(counts, torch.int32, (n,), "counts", dev) if counts is not None else None
+        self._follow_torch_stream(points)
+        self._replaces_batch()
+        self._check(self._lib.agx_decode_positions_enqueue(self._h, p_quads, stride, n, qpf, p_counts, p_ps, w, h, border, edge, float(margin),
+                                                           p_points, p_status))
+
+    def bit_code_enqueue(self, frames, points, bits, status, counts=None, status_in=None, valid_brightness_threshold=10, max_invalid_bit=3,
+                         format=None):
+        """bit_code (src/detector.rs:74-122) of ANY sample points, stream-ordered behind torch's current stream; nothing to fetch.
+        frames and format= as decode_quads_enqueue; points float32 [N,Q,P,2] with P in 1 .. 64 (decode_positions_enqueue's, or a
+        grid of the caller's own).  status_in int32 [N,Q] (optional; may be `status` itself): a slot whose word is non-zero reads
+        no pixel and keeps its word.  bits int64 [N,Q]: the first point is the most significant of the P bits, 0 unless
+        AGX_QUAD_DECODED; status int32 [N,Q]: AGX_QUAD_DECODED / _OUTSIDE / _LOW_CONTRAST / _AMBIGUOUS."""
+        import torch
+        fmt, bpp = self._tensor_format(frames, format)
+        n, w, h, rs, fs = self._tensor_geometry(frames, fmt, bpp)
+        dev = frames.device
+        if not (getattr(points, "is_cuda", False) and points.dim() == 4 and points.shape[0] == n and points.shape[1] > 0 and points.shape[3] == 2):
+            raise AgxError(_ffi.AGX_ERR_ARG, "points must be a device tensor [N, Q, P, 2]")
+        qpf, pps = int(points.shape[1]), int(points.shape[2])
+        p_points = self._stage_tensor(points, torch.float32, (n, qpf, pps, 2), "points", dev)
+        p_bits = self._stage_tensor(bits, torch.int64, (n, qpf), "bits", dev)
+        p_status = self._stage_tensor(status, torch.int32, (n, qpf), "status", dev)
+        p_counts = self._stage_tensor(counts, torch.int32, (n,), "counts", dev) if counts is not None else None
+        p_in = self._stage_tensor(status_in, torch.int32, (n, qpf), "status_in", dev) if status_in is not None else None
+        if not 0 <= int(max_invalid_bit) < 2 ** 32:
+            raise AgxError(_ffi.AGX_ERR_ARG, "max_invalid_bit is a uint32")
+        self._follow_torch_stream(frames)
+        self._replaces_batch()
+        self._check(self._lib.agx_bit_code_enqueue(self._h, frames.data_ptr(), n, w, h, rs, fs, fmt, p_points, pps, qpf, p_counts, p_in,
+                                                   int(valid_brightness_threshold), int(max_invalid_bit), p_bits, p_status))
+
+    def best_tag_enqueue(self, bits, ids, rotations, status, thres=None, codes=None, edge_bits=None, counts=None, status_in=None,
+                         quads=None, refined=None, tags=None):
+        """best_tag (src/detector.rs:142-169) against ANY code list, stream-ordered behind torch's current stream; nothing to
+        fetch.  bits int64 [N,Q]; codes: an int64 device tensor of 1 .. 65535 codes, or None: the family's list; thres (None: the
+        family's Hamming distance): a rotation matches at a distance below it; edge_bits (None: the family's).  counts and
+        status_in as bit_code_enqueue.  ids, rotations, status int32 [N,Q]: the code's index, the rotation (0 unless
+        AGX_QUAD_DECODED) and AGX_QUAD_DECODED / _NO_MATCH.  With quads (or refined=, decode_positions_enqueue's input) and tags
+        int32 [N,Q,9]: decode_quads_enqueue's records, {id, corners after rotate_left(rotation); reverse()}."""
+        import torch
+        if not (getattr(bits, "is_cuda", False) and bits.dim() == 2 and bits.shape[1] > 0):
+            raise AgxError(_ffi.AGX_ERR_ARG, "bits must be a device tensor [N, Q]")
+        n, qpf, dev = int(bits.shape[0]), int(bits.shape[1]), bits.device
+        fam = self._family_info()
+        p_bits = self._stage_tensor(bits, torch.int64, (n, qpf), "bits", dev)
+        p_out = [self._stage_tensor(t, torch.int32, (n, qpf), what, dev) for t, what in ((ids, "ids"), (rotations, "rotations"), (status, "status"))]
+        p_counts = self._stage_tensor(counts, torch.int32, (n,), "counts", dev) if counts is not None else None
+        p_in = self._stage_tensor(status_in, torch.int32, (n, qpf), "status_in", dev) if status_in is not None else None
+        p_codes, n_codes = None, 0
+        if codes is not None:
+            if not (getattr(codes, "is_cuda", False) and codes.dim() == 1):
+                raise AgxError(_ffi.AGX_ERR_ARG, "codes must be a one-dimensional int64 device tensor")
+            n_codes = int(codes.shape[0])
+            p_codes = self._stage_tensor(codes, torch.int64, (n_codes,), "codes", dev)
+        p_quads, stride, p_tags = None, 0, None
+        if (quads is not None or refined is not None) != (tags is not None):
+            raise AgxError(_ffi.AGX_ERR_ARG, "quads (or refined=) and tags: both or neither")
+        if tags is not None:
+            qn, qq, stride, p_quads, _, _ = self._stage_quads(quads, refined)
+            if (qn, qq) != (n, qpf):
+                raise AgxError(_ffi.AGX_ERR_ARG, "quads must have the bits' [N, Q]")
+            p_tags = self._stage_tensor(tags, torch.int32, (n, qpf, 9), "tags", dev)
+        self._follow_torch_stream(bits)
+        self._replaces_batch()
+        self._check(self._lib.agx_best_tag_enqueue(self._h, p_bits, n * qpf, qpf, p_counts, p_in, fam[2] if thres is None else int(thres),
+                                                   p_codes, n_codes, fam[0] if edge_bits is None else int(edge_bits), p_quads, stride,
+                                                   *p_out, p_tags))
+
+    def decode_quads_staged(self, frames, quads, *, margin=0.5, valid_brightness_threshold=10, max_invalid_bit=3, thres=None, codes=None,
+                            counts=None, format=None):
+        """try_decode_quad (src/detector.rs:448-476) as its three stages chained on device tensors with no sync in between --
+        decode_positions_enqueue -> bit_code_enqueue -> best_tag_enqueue, one status array handed on in place -- with the crate's
+        arguments open: margin, the brightness rules, thres (None: the family's Hamming distance) and codes (None: the family's
+        list; else 1 .. 65535 codes, a host array or an int64 device tensor).  frames, quads [N,Q,4,2] and counts as
+        decode_quads_enqueue.  At the defaults the result is decode_quads_enqueue's, byte for byte.
+        -> (tags [N,Q] TAG_DTYPE, status [N,Q] uint32, bits [N,Q] uint64, points [N,Q,edge_bits^2,2] float32) as decode_quads_fetch
+        returns them: slots beyond a frame's count read zero tags, status 0xFFFFFFFF, bits 0; the points of a slot whose quad
+        gave none are 0."""
+        import torch
+        fmt, bpp = self._tensor_format(frames, format)
+        n, w, h, _, _ = self._tensor_geometry(frames, fmt, bpp)
+        n, qpf, _, _, _, dev = self._stage_quads(quads, None)
+        edge = self._family_info()[0]
+        i32 = dict(dtype=torch.int32, device=dev)
+        points = torch.zeros((n, qpf, edge * edge, 2), dtype=torch.float32, device=dev)
+        status = torch.full((n, qpf), -1, **i32)
+        bits = torch.zeros((n, qpf), dtype=torch.int64, device=dev)
+        ids, rotations = torch.zeros((n, qpf), **i32), torch.zeros((n, qpf), **i32)
+        tags = torch.zeros((n, qpf, 9), **i32)
+        if codes is not None and not getattr(codes, "is_cuda", False):
+            codes = torch.from_numpy(np.ascontiguousarray(codes, np.uint64).view(np.int64).reshape(-1)).to(dev)
+        self.decode_positions_enqueue(quads, points, status, img_size=(int(w), int(h)), margin=margin, counts=counts)
+        self.bit_code_enqueue(frames, points, bits, status, counts=counts, status_in=status, valid_brightness_threshold=valid_brightness_threshold,
+                              max_invalid_bit=max_invalid_bit, format=format)
+        self.best_tag_enqueue(bits, ids, rotations, status, thres=thres, codes=codes, counts=counts, status_in=status, quads=quads, tags=tags)
+        self.sync()
+        out = np.ascontiguousarray(tags.cpu().numpy()).view(np.uint32).reshape(n, qpf, 9).copy().view(self.TAG_DTYPE).reshape(n, qpf)
+        return out, status.cpu().numpy().view(np.uint32), bits.cpu().numpy().view(np.uint64), points.cpu().numpy()
+
     # ---- try_find_best_board of caller-given saddle lists (src/detector.rs:588-639) --------
     def find_board(self, saddles, cap=128):
         """try_find_best_board of one host list (SADDLE_DTYPE array, or anything that reshapes to [n, 5] float32: x, y, k, theta,
@@ -1257,6 +1412,75 @@ def decode_quads_tail(tag_family, luma8, quads, with_bits=False):
         raise AgxError(st)
     assert n_decoded.value == int((status == _ffi.AGX_QUAD_DECODED).sum())
     return (out, status, bits) if with_bits else (out, status)
+
+
+def decode_positions(quads, img_w, img_h, border_bits, edge_bits, margin=0.5):
+    """The host's decode_positions (src/detector.rs:42-72) without a device -- the first stage of decode_quads_tail, the same
+    code: quads n x 4 corners (x, y).  -> (points [n, edge_bits^2, 2] float32, x outer and y inner, zero where the quad gave none;
+    status [n] uint32: AGX_QUAD_DECODED or AGX_QUAD_OUTSIDE)."""
+    q = np.ascontiguousarray(quads, np.float32).reshape(-1, 8)
+    n, e = q.shape[0], int(edge_bits)
+    points = np.zeros((n, max(e * e, 1) if 1 <= e <= 8 else 1, 2), np.float32)
+    status = np.zeros(n, np.uint32)
+    st = _ffi.lib().agx_decode_positions_tail(q.ctypes.data, n, int(img_w), int(img_h), int(border_bits), e, float(margin), points.ctypes.data,
+                                              status.ctypes.data)
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    return points, status
+
+
+def bit_code(luma8, points, valid_brightness_threshold=10, max_invalid_bit=3, status_in=None):
+    """The host's bit_code (src/detector.rs:74-122) without a device -- the second stage of decode_quads_tail, the same code:
+    luma8 an HxW uint8 plane (rows may be strided), points [n, P, 2] with P in 1 .. 64, status_in [n] optional (a non-zero word
+    is passed through, and the slot reads nothing).  -> (bits [n] uint64, the first point the most significant of the P bits and
+    0 unless AGX_QUAD_DECODED; status [n] uint32: AGX_QUAD_DECODED / _OUTSIDE / _LOW_CONTRAST / _AMBIGUOUS)."""
+    g = np.asarray(luma8)
+    if g.dtype != np.uint8 or g.ndim != 2 or g.strides[1] != 1 or g.strides[0] < g.shape[1]:
+        g = np.ascontiguousarray(luma8, np.uint8)
+    h, w = g.shape
+    p = np.ascontiguousarray(points, np.float32)
+    if p.ndim != 3 or p.shape[2] != 2:
+        raise AgxError(_ffi.AGX_ERR_ARG, "points must be [n, P, 2]")
+    n, pps = p.shape[0], p.shape[1]
+    bits = np.zeros(n, np.uint64)
+    status = np.zeros(n, np.uint32)
+    s_in = np.ascontiguousarray(status_in, np.uint32).reshape(n) if status_in is not None else None
+    st = _ffi.lib().agx_bit_code_tail(g.ctypes.data, w, h, g.strides[0], p.ctypes.data, pps, n, s_in.ctypes.data if s_in is not None else None,
+                                      int(valid_brightness_threshold), int(max_invalid_bit), bits.ctypes.data, status.ctypes.data)
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    return bits, status
+
+
+def best_tag(bits, thres, codes=None, edge_bits=None, tag_family=None, status_in=None, quads=None):
+    """The host's best_tag (src/detector.rs:142-169) without a device -- the third stage of decode_quads_tail, the same code:
+    bits [n] uint64, thres 0 .. 255 (a rotation matches at a distance below it), codes 1 .. 65535 uint64 codes, or None: the
+    list of tag_family; edge_bits (None: tag_family's).  status_in as bit_code's.  -> (ids [n], rotations [n], status [n]
+    uint32: AGX_QUAD_DECODED or AGX_QUAD_NO_MATCH) and, with quads (n x 4 corners), the tags [n] TagDetector.TAG_DTYPE that
+    decode_quads_tail gives."""
+    b = np.ascontiguousarray(bits, np.uint64).reshape(-1)
+    n = b.shape[0]
+    fam = 0
+    if tag_family is not None:
+        fam = int(TagFamily.from_str(tag_family) if isinstance(tag_family, str) else TagFamily(tag_family))
+    if edge_bits is None:
+        if tag_family is None:
+            raise AgxError(_ffi.AGX_ERR_ARG, "edge_bits or tag_family must be given")
+        edge_bits = {TagFamily.T16H5: 4, TagFamily.T25H7: 5, TagFamily.T25H9: 5, TagFamily.T36H11: 6, TagFamily.T36H11B1: 6}[TagFamily(fam)]
+    if codes is None and tag_family is None:
+        raise AgxError(_ffi.AGX_ERR_ARG, "codes or tag_family must be given")
+    c = np.ascontiguousarray(codes, np.uint64).reshape(-1) if codes is not None else None
+    ids, rotations, status = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    s_in = np.ascontiguousarray(status_in, np.uint32).reshape(n) if status_in is not None else None
+    q = np.ascontiguousarray(quads, np.float32).reshape(n, 8) if quads is not None else None
+    tags = np.zeros(n, TagDetector.TAG_DTYPE) if quads is not None else None
+    st = _ffi.lib().agx_best_tag_tail(b.ctypes.data, n, s_in.ctypes.data if s_in is not None else None, int(thres), fam,
+                                      c.ctypes.data if c is not None else None, len(c) if c is not None else 0, int(edge_bits),
+                                      q.ctypes.data if q is not None else None, ids.ctypes.data, rotations.ctypes.data, status.ctypes.data,
+                                      tags.ctypes.data if tags is not None else None)
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    return (ids, rotations, status, tags) if tags is not None else (ids, rotations, status)
 
 
 def _find_board_call(call, saddles, cap, keep=None):

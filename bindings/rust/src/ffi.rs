@@ -235,6 +235,28 @@ extern "C" {
                                  quads: *const c_void, n_quads: u32, out: *mut agx_tag, status: *mut u32, bits: *mut u64,
                                  n_decoded: *mut u32) -> c_int;
 
+    // the decode in three stages: decode_positions, bit_code, best_tag (reference src/detector.rs:42-72, :74-122, :142-169)
+    pub fn agx_decode_positions_enqueue(det: *mut agx_detector, d_quads: *const c_void, point_stride_bytes: usize, n_frames: c_int,
+                                        quads_per_frame: u32, d_counts: *const u32, d_point_status: *const u32, img_w: u32, img_h: u32,
+                                        border_bits: c_int, edge_bits: c_int, margin: c_float, d_points: *mut c_float,
+                                        d_status: *mut u32) -> c_int;
+    pub fn agx_decode_positions_tail(quads: *const c_void, n_quads: u32, img_w: u32, img_h: u32, border_bits: c_int, edge_bits: c_int,
+                                     margin: c_float, points: *mut c_float, status: *mut u32) -> c_int;
+    pub fn agx_bit_code_enqueue(det: *mut agx_detector, d_frames: *const c_void, n_frames: c_int, width: c_int, height: c_int,
+                                row_stride_bytes: usize, frame_stride_bytes: usize, format: c_int, d_points: *const c_float,
+                                points_per_slot: u32, quads_per_frame: u32, d_counts: *const u32, d_status_in: *const u32,
+                                valid_brightness_threshold: c_int, max_invalid_bit: u32, d_bits: *mut u64, d_status: *mut u32) -> c_int;
+    pub fn agx_bit_code_tail(luma8: *const u8, width: c_int, height: c_int, row_stride_bytes: usize, points: *const c_float,
+                             points_per_slot: u32, n_slots: u32, status_in: *const u32, valid_brightness_threshold: c_int,
+                             max_invalid_bit: u32, bits: *mut u64, status: *mut u32) -> c_int;
+    pub fn agx_best_tag_enqueue(det: *mut agx_detector, d_bits: *const u64, n_slots: u32, quads_per_frame: u32, d_counts: *const u32,
+                                d_status_in: *const u32, thres: c_int, d_codes: *const u64, n_codes: u32, edge_bits: c_int,
+                                d_quads: *const c_void, point_stride_bytes: usize, d_ids: *mut u32, d_rotations: *mut u32,
+                                d_status: *mut u32, d_tags: *mut agx_tag) -> c_int;
+    pub fn agx_best_tag_tail(bits: *const u64, n_slots: u32, status_in: *const u32, thres: c_int, family: c_int, codes: *const u64,
+                             n_codes: u32, edge_bits: c_int, quads: *const c_void, ids: *mut u32, rotations: *mut u32, status: *mut u32,
+                             tags: *mut agx_tag) -> c_int;
+
     pub fn agx_find_boards_enqueue(det: *mut agx_detector, d_saddles: *const c_void, saddle_stride_bytes: usize, n_frames: c_int,
                                    saddles_per_frame: u32, d_counts: *const u32, d_frame_table: *const c_void, d_point_status: *const u32,
                                    quads_per_frame: u32, d_quads: *mut u32, d_quad_points: *mut c_float, d_n_quads: *mut u32,

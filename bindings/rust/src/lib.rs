@@ -466,6 +466,57 @@ pub fn find_best_board(refined: &[Saddle]) -> Option<Vec<[usize; 4]>> {
     }
 }
 
+/// reference src/detector.rs:42-72, `decode_positions`: the sample points of a quad (four corners), x outer and y inner, or
+/// `None` where a rounded corner lies outside the image.  The host form (no device is used).  A corner that is not finite is
+/// `None`.  Panics where the library refuses the arguments: `edge_bits` outside 1..=8, `border_bits` above 16, a margin that
+/// is not finite or a source square that is a point, or a quad that does not have four corners.
+pub fn decode_positions(img_w: u32, img_h: u32, quad_pts: &[(f32, f32)], border_bits: u8, edge_bits: u8, margin: f32) -> Option<Vec<(f32, f32)>> {
+    assert_eq!(quad_pts.len(), 4, "decode_positions: a quad has four corners");
+    let flat: Vec<f32> = quad_pts.iter().flat_map(|p| [p.0, p.1]).collect();
+    let n = edge_bits as usize * edge_bits as usize;
+    let mut points = vec![0f32; 2 * n.max(1)];
+    let mut status = 0u32;
+    let st = unsafe {
+        ffi::agx_decode_positions_tail(flat.as_ptr() as *const c_void, 1, img_w, img_h, border_bits as c_int, edge_bits as c_int, margin,
+                                       points.as_mut_ptr(), &mut status)
+    };
+    assert_eq!(st, ffi::AGX_OK, "agx_decode_positions_tail failed: {}", st);
+    if status as c_int != ffi::AGX_QUAD_DECODED {
+        return None;
+    }
+    Some(points[..2 * n].chunks(2).map(|p| (p[0], p[1])).collect())
+}
+
+/// reference src/detector.rs:74-122, `bit_code`: the bits of up to 64 sample points on a grey image, the first point the most
+/// significant, or `None` (a point outside the image, too little contrast, too many samples near the mid brightness).  The
+/// host form (no device is used).  A coordinate that is not finite is `None`.
+pub fn bit_code(img: &image::GrayImage, decode_pts: &[(f32, f32)], valid_brightness_threshold: u8, max_invalid_bit: u32) -> Option<u64> {
+    assert!(!decode_pts.is_empty() && decode_pts.len() <= 64, "bit_code: 1 to 64 points");
+    let flat: Vec<f32> = decode_pts.iter().flat_map(|p| [p.0, p.1]).collect();
+    let (mut bits, mut status) = (0u64, 0u32);
+    let st = unsafe {
+        ffi::agx_bit_code_tail(img.as_raw().as_ptr(), img.width() as c_int, img.height() as c_int, img.width() as usize, flat.as_ptr(),
+                               decode_pts.len() as u32, 1, std::ptr::null(), valid_brightness_threshold as c_int, max_invalid_bit, &mut bits,
+                               &mut status)
+    };
+    assert_eq!(st, ffi::AGX_OK, "agx_bit_code_tail failed: {}", st);
+    if status as c_int == ffi::AGX_QUAD_DECODED { Some(bits) } else { None }
+}
+
+/// reference src/detector.rs:142-169, `best_tag`: `(index into tag_family, rotation)` of the first rotation that lies within
+/// `thres` of a code -- per rotation the first code with the smallest distance --, or `None`.  The host form (no device is
+/// used).  `tag_family` holds 1 to 65535 codes.
+pub fn best_tag(bits: u64, thres: u8, tag_family: &[u64], edge_bits: u8) -> Option<(usize, usize)> {
+    assert!(!tag_family.is_empty() && tag_family.len() <= 65535, "best_tag: 1 to 65535 codes");
+    let (mut id, mut rotation, mut status) = (0u32, 0u32, 0u32);
+    let st = unsafe {
+        ffi::agx_best_tag_tail(&bits, 1, std::ptr::null(), thres as c_int, 0, tag_family.as_ptr(), tag_family.len() as u32, edge_bits as c_int,
+                               std::ptr::null(), &mut id, &mut rotation, &mut status, std::ptr::null_mut())
+    };
+    assert_eq!(st, ffi::AGX_OK, "agx_best_tag_tail failed: {}", st);
+    if status as c_int == ffi::AGX_QUAD_DECODED { Some((id as usize, rotation as usize)) } else { None }
+}
+
 /// One round of `detect`'s loop behind its board search and decode, reference src/detector.rs:510-539, on the host (no device is
 /// used): every quad of `quads` (saddle indices, as `find_best_board` returns them) whose `quad_status` is `AGX_QUAD_DECODED`
 /// inserts its `quad_tags` entry into `tags` -- a known id keeps its place and takes the new corners (:520) -- and, where

@@ -488,6 +488,92 @@ int agx_decode_quads_tail(int family, const uint8_t *luma8, int width, int heigh
                           const void *quads, uint32_t n_quads, agx_tag *out, uint32_t *status, uint64_t *bits,
                           uint32_t *n_decoded);
 
+/* ---- the decode in three stages: decode_positions, bit_code, best_tag -------------------------- */
+
+/* The crate's three pub fns that try_decode_quad is built from, each with its own arguments -- decode_positions(img_w, img_h,
+ * quad_pts, border_bits, edge_bits, margin) (src/detector.rs:42-72), bit_code(img, decode_pts, valid_brightness_threshold,
+ * max_invalid_bit) (src/detector.rs:74-122) and best_tag(bits, thres, tag_family, edge_bits) (src/detector.rs:142-169) -- over
+ * device batches: a caller samples a tag on its own grid, sets the brightness rules of its camera, or matches against a code
+ * list of its own.  All three follow agx_filter_saddles_enqueue / agx_collect_tags_enqueue: caller-owned device arrays only,
+ * stream-ordered on the detector's stream (the caller's after agx_detector_set_stream), they return without waiting, there is
+ * nothing to fetch, and they replace the batch in flight without waiting; a refused argument (AGX_ERR_ARG, AGX_ERR_FORMAT)
+ * leaves a batch in flight where it is.  Slot = f*quads_per_frame + q; d_counts as in agx_decode_quads_enqueue (a count above
+ * quads_per_frame means quads_per_frame; slots at or beyond a frame's count are neither read nor written).  Statuses are the
+ * AGX_QUAD_* values.  Chained at (the family's border_bits / edge_bits, 0.5, 10, 3, the family's Hamming distance, its code list)
+ * with no sync in between -- each d_status passed on as the next d_status_in -- they leave what agx_decode_quads_enqueue leaves,
+ * byte for byte (tags, statuses, bits), and with it the input of agx_collect_tags_enqueue.  One exception, outside any image:
+ * corners beyond 1e37 can overflow a sample to NaN, which try_decode_quad's `as u32` reads as pixel 0 and agx_bit_code_enqueue
+ * calls AGX_QUAD_OUTSIDE.
+ *
+ * decode_positions (src/detector.rs:42-72).  d_quads / point_stride_bytes / n_frames / quads_per_frame / d_counts /
+ * d_point_status exactly as agx_decode_quads_enqueue reads them (stride 8 or 20; a quad with a corner whose word is non-zero is
+ * AGX_QUAD_SKIPPED).  img_w, img_h: the image size the corners are tested against; no pixel is read.  d_status[slot]:
+ * AGX_QUAD_DECODED (Some), AGX_QUAD_OUTSIDE (None: a corner that is not finite, decided first; or :50-56, a rounded corner >=
+ * img_w / img_h under the saturating `as u32`, where a finite negative corner is inside) or AGX_QUAD_SKIPPED.  d_points
+ * [slots][edge_bits*edge_bits][2] floats: the samples of an AGX_QUAD_DECODED slot in the reference's order, x outer and y inner
+ * (:60-70); any other slot writes no point.  The arithmetic is the project's tag_affine -- the least-squares map over the
+ * axis-aligned source square in closed form, binary64, rounded once to binary32 -- and h0*x + h1*y + h2*1.0f left to right in
+ * binary32: the points are those the fused decode samples at, and within 1e-3 px of any other correctly rounded solve.
+ * AGX_ERR_ARG: a NULL or misaligned (4 bytes) array other than d_counts / d_point_status, n_frames <= 0, quads_per_frame == 0,
+ * a bad point stride, 2^29 slots or more, edge_bits outside 1 .. 8 (the bits fit a u64), border_bits outside 0 .. 16, a
+ * margin that is not finite, or a degenerate source square: (float)side_bits - 1 + margin == -margin as floats. */
+int agx_decode_positions_enqueue(agx_detector *det, const void *d_quads, size_t point_stride_bytes, int n_frames,
+                                 uint32_t quads_per_frame, const uint32_t *d_counts, const uint32_t *d_point_status,
+                                 uint32_t img_w, uint32_t img_h, int border_bits, int edge_bits, float margin,
+                                 float *d_points, uint32_t *d_status);
+/* decode_positions (src/detector.rs:42-72) in HOST memory, without a detector handle (no device needed, like
+ * agx_decode_quads_tail, whose first stage this is -- the same code): quads a packed [n_quads][8] float array, points
+ * [n_quads][edge_bits*edge_bits][2], status [n_quads].  Statuses, untouched points and AGX_ERR_ARG as the batch call's. */
+int agx_decode_positions_tail(const void *quads, uint32_t n_quads, uint32_t img_w, uint32_t img_h, int border_bits,
+                              int edge_bits, float margin, float *points, uint32_t *status);
+/* bit_code (src/detector.rs:74-122) of ANY sample points.  d_frames / n_frames / width / height / strides / format as
+ * agx_decode_quads_enqueue (AGX_LF32 is AGX_ERR_FORMAT; every format but AGX_L8 goes through the device's to_luma8 plane).
+ * d_points [slots][points_per_slot][2] floats, points_per_slot in 1 .. 64 (agx_decode_positions_enqueue's d_points with
+ * edge_bits*edge_bits, or a caller's own grid).  d_status_in: NULL, or one word per slot, and it may be d_status itself: a slot
+ * whose word is non-zero reads no pixel, gets bits 0, and its word is passed through to d_status.  valid_brightness_threshold in
+ * 0 .. 255 (a u8 in the crate), max_invalid_bit any uint32.  d_status[slot], decided in the reference's order: AGX_QUAD_OUTSIDE
+ * (:84-93, a sample that rounds outside the image; and, as for a quad's corners, a sample coordinate that is not finite,
+ * decided before any read), AGX_QUAD_LOW_CONTRAST (:97-99, max - min < 50), AGX_QUAD_AMBIGUOUS (:117-118, more than
+ * max_invalid_bit samples within valid_brightness_threshold of the mid brightness), else AGX_QUAD_DECODED.  d_bits[slot]
+ * (8-byte aligned): the first point is the most significant of the points_per_slot bits; 0 unless AGX_QUAD_DECODED.
+ * AGX_ERR_ARG: a NULL or misaligned array other than d_counts / d_status_in, quads_per_frame == 0, points_per_slot or the
+ * threshold out of range, 2^29 slots or more, and what agx_decode_quads_enqueue refuses of the frames. */
+int agx_bit_code_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height,
+                         size_t row_stride_bytes, size_t frame_stride_bytes, int format,
+                         const float *d_points, uint32_t points_per_slot, uint32_t quads_per_frame,
+                         const uint32_t *d_counts, const uint32_t *d_status_in, int valid_brightness_threshold,
+                         uint32_t max_invalid_bit, uint64_t *d_bits, uint32_t *d_status);
+/* bit_code (src/detector.rs:74-122) of n_slots point lists on ONE u8 plane in HOST memory (tight or padded rows), without a
+ * detector handle: agx_decode_quads_tail's second stage, the same code.  Statuses, zero bits and status_in as the batch call's. */
+int agx_bit_code_tail(const uint8_t *luma8, int width, int height, size_t row_stride_bytes, const float *points,
+                      uint32_t points_per_slot, uint32_t n_slots, const uint32_t *status_in,
+                      int valid_brightness_threshold, uint32_t max_invalid_bit, uint64_t *bits, uint32_t *status);
+/* best_tag (src/detector.rs:142-169) against ANY code list.  d_bits [n_slots] (8-byte aligned); d_status_in as in
+ * agx_bit_code_enqueue (NULL, or pass-through of non-zero words; may be d_status).  d_counts: NULL (then quads_per_frame is not
+ * read), or per-frame counts with n_slots a multiple of quads_per_frame, as above.  thres in 0 .. 255 (a u8 in the crate): a
+ * rotation matches at a distance BELOW it, so 0 matches nothing.  d_codes: a device list of n_codes in 1 .. 65535 64-bit codes,
+ * or NULL with n_codes == 0: the handle's family list.  edge_bits in 1 .. 8.  The reference's result bit for bit: per rotation,
+ * in rotation order, the FIRST code with the smallest distance; rotation 0 counts all 64 bits of the XOR while rotate_bits
+ * (:124-140) keeps only the low edge_bits^2 bits, so bits above them matter at rotation 0 only.  d_ids, d_rotations
+ * [n_slots]: the code's index and the rotation, 0 unless AGX_QUAD_DECODED; d_status: AGX_QUAD_DECODED or AGX_QUAD_NO_MATCH
+ * (:160-168).  d_quads + point_stride_bytes (agx_decode_positions_enqueue's input) and d_tags, given together or not at all:
+ * d_tags[slot] = {id, the corners after rotate_left(rotation); reverse()} (src/detector.rs:448-476, :467-470), exactly
+ * agx_decode_quads_enqueue's record, all zero unless AGX_QUAD_DECODED.
+ * AGX_ERR_ARG: a NULL or misaligned d_bits, d_ids, d_rotations or d_status, n_slots == 0 or 2^31 and more, thres, n_codes or
+ * edge_bits out of range, d_codes and n_codes that do not go together, d_counts with a quads_per_frame that does not divide
+ * n_slots, exactly one of d_quads / d_tags, a bad point stride. */
+int agx_best_tag_enqueue(agx_detector *det, const uint64_t *d_bits, uint32_t n_slots, uint32_t quads_per_frame,
+                         const uint32_t *d_counts, const uint32_t *d_status_in, int thres, const uint64_t *d_codes,
+                         uint32_t n_codes, int edge_bits, const void *d_quads, size_t point_stride_bytes,
+                         uint32_t *d_ids, uint32_t *d_rotations, uint32_t *d_status, agx_tag *d_tags);
+/* best_tag (src/detector.rs:142-169) in HOST memory, without a detector handle: agx_decode_quads_tail's third stage, the same
+ * code.  codes / n_codes as d_codes / n_codes, with `family` (as in agx_detector_create; else not read) naming the list where
+ * codes is NULL; quads a packed [n_slots][8] float array, given together with tags or not at all.  Everything else as the batch
+ * call's; AGX_ERR_FAMILY. */
+int agx_best_tag_tail(const uint64_t *bits, uint32_t n_slots, const uint32_t *status_in, int thres, int family,
+                      const uint64_t *codes, uint32_t n_codes, int edge_bits, const void *quads, uint32_t *ids,
+                      uint32_t *rotations, uint32_t *status, agx_tag *tags);
+
 /* ---- board search in caller-given saddle lists ------------------------------------------- */
 
 /* try_find_best_board(refined: &[Saddle]) -> Option<Vec<[usize; 4]>> -- src/detector.rs:588-639, a pub fn of the crate: which
