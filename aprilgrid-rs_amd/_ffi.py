@@ -23,6 +23,7 @@ AGX_REFINE_BLURRED, AGX_REFINE_PLANE = 0, 1
 AGX_QUAD_DECODED, AGX_QUAD_OUTSIDE, AGX_QUAD_LOW_CONTRAST, AGX_QUAD_AMBIGUOUS, AGX_QUAD_NO_MATCH, AGX_QUAD_SKIPPED = 0, 1, 2, 3, 4, 5
 # try_find_best_board of caller-given saddle lists (src/detector.rs:588-639): what became of a frame
 AGX_BOARD_FOUND, AGX_BOARD_NONE, AGX_BOARD_CAPACITY, AGX_BOARD_INPUT, AGX_BOARD_PENDING = 0, 1, 2, 3, 4
+AGX_GROW_FIX_MISSING = 1  # agx_grow_boards_enqueue / agx_grow_board_tail: flags
 # cluster centres of caller-given response planes (src/detector.rs:414-429): what became of a frame; INEXACT is a flag OR'd in
 AGX_CLUSTERS_OK, AGX_CLUSTERS_CAPACITY, AGX_CLUSTERS_BORDER, AGX_CLUSTERS_OVERFLOW, AGX_CLUSTERS_INEXACT = 0, 1, 2, 3, 0x100
 AGX_POINT_FILTERED = 4  # the k / phi filter (src/detector.rs:432-445) removed a refined point
@@ -118,6 +119,11 @@ SYMBOLS = {
     "agx_find_boards_fetch": (C.c_int, [_P, _P, _P, _P, _P, C.c_int]),
     "agx_find_board": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "agx_find_board_tail": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "agx_grow_boards_enqueue": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P, C.c_float, C.c_uint32, C.c_int,
+                                          C.c_uint32, _P, _P, _P, _P, _P, _P]),
+    "agx_grow_boards_fetch": (C.c_int, [_P, C.c_int]),
+    "agx_grow_board_tail": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, C.c_float, C.c_uint32, C.c_int, _P, C.c_uint32, C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_uint32), _P, C.POINTER(C.c_uint32)]),
     "agx_planes_enqueue": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_float, _P, _P, C.c_size_t,
                                      C.c_size_t]),
     "agx_gaussian_blur_f32": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_float, _P]),

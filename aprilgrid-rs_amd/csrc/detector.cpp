@@ -37,7 +37,8 @@ static const struct { const char *enqueue, *fetch; } kBatchPair[BATCH_KINDS] = {
     {"agx_refine_points_enqueue", "agx_refine_points_fetch"},
     {"agx_decode_quads_enqueue", "agx_decode_quads_fetch"},
     {"agx_find_boards_enqueue", "agx_find_boards_fetch"},
-    {"agx_clusters_enqueue", "agx_clusters_fetch"}};
+    {"agx_clusters_enqueue", "agx_clusters_fetch"},
+    {"agx_grow_boards_enqueue", "agx_grow_boards_fetch"}};
 
 int agx::refuse_other_batch(agx_detector *det, int wanted)
 {
@@ -973,6 +974,8 @@ int agx_detector_get_option(const agx_detector *det, const char *name, int *valu
     else if (!std::strcmp(name, "tail_debug_band")) *value = det->tail_debug_band_mdeg;
     else if (!std::strcmp(name, "last_find_boards_frames")) *value = det->last_find_frames;  // (of the last agx_find_boards_fetch)
     else if (!std::strcmp(name, "last_find_boards_handed_back")) *value = det->last_find_handed_back;
+    else if (!std::strcmp(name, "last_grow_boards_frames")) *value = det->last_grow_frames;  // (of the last agx_grow_boards_fetch)
+    else if (!std::strcmp(name, "last_grow_boards_handed_back")) *value = det->last_grow_handed_back;
     else if (!std::strcmp(name, "last_device_tail_frames")) *value = det->last_tail_frames;
     else if (!std::strcmp(name, "last_device_tail_fallbacks")) *value = det->last_tail_fallbacks;
     else if (!std::strcmp(name, "last_device_tail_uncertain")) *value = det->last_tail_uncertain;  // (of them: an angle inside its guard band)
@@ -1668,6 +1671,48 @@ int agx_find_board_tail(const agx_saddle *saddles, uint32_t n_saddles, uint32_t 
     if (st == AGX_BOARD_FOUND && n) std::memcpy(quads, rows.data(), rows.size() * sizeof(uint32_t));
     *n_quads = st == AGX_BOARD_FOUND || st == AGX_BOARD_CAPACITY ? n : 0u;
     *status = st;
+    return AGX_OK;
+    });
+}
+
+// ---- boards from the caller's seed quads (src/board.rs:26-112; csrc/detect_batch.cpp, tail_kernels.hip: k_grow_boards) ----------
+int agx_grow_boards_enqueue(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
+                            const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status, const uint32_t *d_seed_quads,
+                            uint32_t seeds_per_frame, const uint32_t *d_seed_counts, float spacing_ratio, uint32_t stop_score, int flags,
+                            uint32_t quads_per_frame, uint32_t *d_quads, float *d_quad_points, uint32_t *d_n_quads, uint32_t *d_status,
+                            uint32_t *d_seed_scores, uint32_t *d_best_seed)
+{
+    return agx_guard(det, [&]() -> int {
+    return grow_boards_enqueue_impl(det, d_saddles, saddle_stride_bytes, n_frames, saddles_per_frame, d_counts, d_frame_table, d_point_status,
+                                    d_seed_quads, seeds_per_frame, d_seed_counts, spacing_ratio, stop_score, flags, quads_per_frame, d_quads,
+                                    d_quad_points, d_n_quads, d_status, d_seed_scores, d_best_seed);
+    });
+}
+
+int agx_grow_boards_fetch(agx_detector *det, int n_threads)
+{
+    return agx_guard(det, [&]() -> int { return grow_boards_fetch_impl(det, n_threads); });
+}
+
+int agx_grow_board_tail(const agx_saddle *saddles, uint32_t n_saddles, const uint32_t *point_status, const uint32_t *seed_quads, uint32_t n_seeds,
+                        float spacing_ratio, uint32_t stop_score, int flags, uint32_t *quads, uint32_t cap, uint32_t *n_quads, uint32_t *status,
+                        uint32_t *seed_scores, uint32_t *best_seed)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (!n_quads || !status || (n_saddles && !saddles) || (cap && !quads) || (n_seeds && !seed_quads)) return AGX_ERR_ARG;
+    if (!std::isfinite(spacing_ratio) || !(1.0f + spacing_ratio > 0.0f) || (flags & ~AGX_GROW_FIX_MISSING)) return AGX_ERR_ARG;
+    std::vector<uint32_t> rows, scores;
+    uint32_t best = 0;
+    uint32_t st = (uint32_t)grow_boards_in_slots(saddles, sizeof(agx_saddle), n_saddles, point_status, seed_quads, n_seeds, spacing_ratio, stop_score,
+                                                 flags, rows, scores, best);
+    const uint32_t n = (uint32_t)(rows.size() / 4);
+    if (st == AGX_BOARD_FOUND && n > cap) st = AGX_BOARD_CAPACITY;
+    if (st == AGX_BOARD_FOUND && n) std::memcpy(quads, rows.data(), rows.size() * sizeof(uint32_t));
+    const bool some = st == AGX_BOARD_FOUND || st == AGX_BOARD_CAPACITY;
+    *n_quads = some ? n : 0u;
+    *status = st;
+    if (some && seed_scores && n_seeds) std::memcpy(seed_scores, scores.data(), (size_t)n_seeds * sizeof(uint32_t));
+    if (some && best_seed) *best_seed = best;
     return AGX_OK;
     });
 }

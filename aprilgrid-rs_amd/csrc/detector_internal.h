@@ -57,6 +57,7 @@ enum BatchKind {
     BATCH_DECODE,   // DecodePending
     BATCH_FIND,     // FindPending
     BATCH_CLUSTERS, // ClustersPending; the chain's kernels ran on the workspace, but nothing of the chain is there to be fetched
+    BATCH_GROW,     // GrowPending
     BATCH_KINDS
 };
 // where a kind's results are: the fetch copies them out of the handle's side buffers / they are in the caller's device arrays
@@ -99,6 +100,15 @@ struct FindPending {
     const uint32_t *d_counts = nullptr, *d_frame_table = nullptr, *d_point_status = nullptr;
     uint32_t *d_quads = nullptr, *d_n_quads = nullptr, *d_status = nullptr;
     float *d_quad_points = nullptr;  // the caller's, SB_FIND_POINTS (RESULTS_HOST without the caller's), or null
+};
+
+// FindPending's list and result arrays (always RESULTS_CALLER) and what the host form needs besides
+struct GrowPending : FindPending {
+    const uint32_t *d_seed_quads = nullptr, *d_seed_counts = nullptr;
+    uint32_t seeds_per_frame = 0, stop_score = 0;
+    float spacing_ratio = 0.3f;
+    int flags = 0;
+    uint32_t *d_seed_scores = nullptr, *d_best_seed = nullptr;
 };
 
 struct ClustersPending {
@@ -292,6 +302,8 @@ struct agx_detector {
     agx::FindPending find;              // BATCH_FIND: what agx_find_boards_fetch needs of it
     int last_find_frames = 0, last_find_handed_back = 0;  // of the last agx_find_boards_fetch
     agx::ClustersPending clusters;      // BATCH_CLUSTERS: what agx_clusters_fetch needs of it
+    agx::GrowPending grow;              // BATCH_GROW: what agx_grow_boards_fetch needs of it
+    int last_grow_frames = 0, last_grow_handed_back = 0;  // of the last agx_grow_boards_fetch
     int last_extra_us[agx::XT_COUNT]{};  // harvest_events: the XT_* launches' last times (profiling level 2)
 
     std::string last_error;
@@ -362,6 +374,13 @@ int find_boards_enqueue_impl(agx_detector *det, const void *d_saddles, size_t sa
                              const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status, uint32_t quads_per_frame,
                              uint32_t *d_quads, float *d_quad_points, uint32_t *d_n_quads, uint32_t *d_status);
 int find_boards_fetch_impl(agx_detector *det, uint32_t *quads, float *quad_points, uint32_t *n_quads, uint32_t *status, int n_threads);
+// boards from caller-given seed quads over the same lists (detect_batch.cpp: k_grow_boards, the fetch's host form)
+int grow_boards_enqueue_impl(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
+                             const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status, const uint32_t *d_seed_quads,
+                             uint32_t seeds_per_frame, const uint32_t *d_seed_counts, float spacing_ratio, uint32_t stop_score, int flags,
+                             uint32_t quads_per_frame, uint32_t *d_quads, float *d_quad_points, uint32_t *d_n_quads, uint32_t *d_status,
+                             uint32_t *d_seed_scores, uint32_t *d_best_seed);
+int grow_boards_fetch_impl(agx_detector *det, int n_threads);
 int group_detect_fetch_impl(agx_detector *det, const char *back, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads);
 // What group.cpp calls for rank r's share of a detect batch (detector.cpp: the entry points' argument checks and guard around
 // the two functions above).  After the enqueue det->detect.device_tail says whether the pack kernel ran.

@@ -1340,6 +1340,73 @@ int find_board_in_slots(const void *slots, size_t stride, uint32_t n_slots, cons
     return AGX_BOARD_FOUND;
 }
 
+// Boards from the caller's seed quads (agx_grow_board_tail, agx_grow_boards_fetch; k_grow_boards is the device form): the loop of
+// try_find_best_board (:613-629) over the caller's quads instead of init_quads', Board::new at the caller's spacing_ratio.
+int grow_boards(const std::vector<agx_saddle> &listed, const std::vector<Quad> &seeds, float spacing_ratio, uint32_t stop_score, bool fix_missing,
+                std::vector<Quad> &quads, std::vector<uint32_t> &seed_scores, uint32_t &best_seed)
+{
+    quads.clear();
+    seed_scores.assign(seeds.size(), 0u);
+    best_seed = 0;
+    if (seeds.empty() || listed.empty()) return AGX_BOARD_NONE;
+    TailScratch &sc = tail_scratch();
+    sc.index.reset(listed);  // (and its memo tables: the pairs' candidates are this call's ratio's)
+    BoardStorage *storage = sc.storage;
+    unsigned best_score = 0;
+    int cur = 0, best_at = -1;
+    for (size_t i = 0; i < seeds.size(); ++i) {
+        const Board b(listed, sc.index, seeds[i], spacing_ratio, storage[cur]);
+        seed_scores[i] = b.score();
+        if (b.score() > best_score) {  // :622: strictly
+            best_score = b.score();
+            best_seed = (uint32_t)i;
+            best_at = cur;
+            cur ^= 1;
+        }
+        if (stop_score && best_score >= stop_score) break;
+    }
+    if (best_at < 0) return AGX_BOARD_NONE;
+    Board best(listed, sc.index, storage[best_at], best_score);
+    if (fix_missing) best.fix_missing();
+    best.collect(quads);
+    return AGX_BOARD_FOUND;
+}
+
+int grow_boards_in_slots(const void *slots, size_t stride, uint32_t n_slots, const uint32_t *point_status, const uint32_t *seed_quads,
+                         uint32_t n_seeds, float spacing_ratio, uint32_t stop_score, int flags, std::vector<uint32_t> &quads,
+                         std::vector<uint32_t> &seed_scores, uint32_t &best_seed)
+{
+    quads.clear();
+    seed_scores.assign(n_seeds, 0u);
+    best_seed = 0;
+    std::vector<agx_saddle> list;
+    std::vector<uint32_t> slot_of;
+    std::vector<int> pos_of(n_slots, -1);
+    for (uint32_t i = 0; i < n_slots; ++i) {
+        if (point_status && point_status[i] != 0u) continue;  // (AGX_POINT_REFINED is 0)
+        agx_saddle s;
+        std::memcpy(&s, static_cast<const char *>(slots) + (size_t)i * stride, sizeof s);
+        if (!std::isfinite(s.x) || !std::isfinite(s.y) || !std::isfinite(s.theta)) return AGX_BOARD_INPUT;
+        s.k = 0.0f;  // (never read: whatever the slot holds there)
+        s.phi = 0.0f;
+        pos_of[i] = (int)list.size();
+        list.push_back(s);
+        slot_of.push_back(i);
+    }
+    std::vector<Quad> seeds(n_seeds);
+    for (uint32_t k = 0; k < n_seeds; ++k)
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t s = seed_quads[4 * (size_t)k + j];
+            if (s >= n_slots || pos_of[s] < 0) return AGX_BOARD_INPUT;  // beyond the frame's count, or not listed
+            seeds[k][j] = pos_of[s];
+        }
+    std::vector<Quad> found;
+    const int st = grow_boards(list, seeds, spacing_ratio, stop_score, (flags & AGX_GROW_FIX_MISSING) != 0, found, seed_scores, best_seed);
+    for (const Quad &q : found)
+        for (int i = 0; i < 4; ++i) quads.push_back(slot_of[(size_t)q[i]]);
+    return st;
+}
+
 namespace {
 // detect's loop body (detector.rs:510-539) over a working copy of the saddle list (consumed: the saddles of decoded
 // quads are removed between the rounds)

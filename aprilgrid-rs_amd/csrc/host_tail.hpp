@@ -57,6 +57,20 @@ bool try_find_best_board(const std::vector<agx_saddle> &refined, std::vector<Qua
 // numbers, four per quad, in all_tag_indexes' order.
 int find_board_in_slots(const void *slots, size_t stride, uint32_t n_slots, const uint32_t *point_status, std::vector<uint32_t> &quads);
 
+// Boards from the caller's seed quads: try_find_best_board's loop (:613-629) over `seeds` (indices into `listed`, taken as they
+// are: Board::new does not test them) instead of init_quads' quads, with Board::new (board.rs:26-48) at spacing_ratio.  The
+// board is the first seed whose score is strictly above every earlier one (:622); with stop_score > 0 the loop ends behind the
+// first seed that leaves the best score at or above it (the seeds behind it: score 0).  try_fix_missing only with fix_missing.
+// AGX_BOARD_NONE (no seed, or an empty list) or AGX_BOARD_FOUND with the quads in all_tag_indexes' order.
+int grow_boards(const std::vector<agx_saddle> &listed, const std::vector<Quad> &seeds, float spacing_ratio, uint32_t stop_score, bool fix_missing,
+                std::vector<Quad> &quads, std::vector<uint32_t> &seed_scores, uint32_t &best_seed);
+// The host form of agx_grow_boards_enqueue / agx_grow_board_tail over the slots of one frame, as find_board_in_slots: seed_quads
+// [n_seeds][4] and the quads are SLOT numbers.  AGX_BOARD_INPUT (a listed x, y or theta that is not finite; else a seed naming a
+// slot at or beyond n_slots or one that is not listed -- every seed is looked at first), AGX_BOARD_NONE, AGX_BOARD_FOUND.
+int grow_boards_in_slots(const void *slots, size_t stride, uint32_t n_slots, const uint32_t *point_status, const uint32_t *seed_quads,
+                         uint32_t n_seeds, float spacing_ratio, uint32_t stop_score, int flags, std::vector<uint32_t> &quads,
+                         std::vector<uint32_t> &seed_scores, uint32_t &best_seed);
+
 // image_util.rs:39-70 (h = 2x3 affine, row-major)
 void tag_affine(const float quad_xy[8], int side_bits, float margin, float h[6]);
 // detector.rs:124-140, 142-169

@@ -108,6 +108,21 @@ struct FindBoardsArgs {
 };
 // one workgroup per frame, k_board_tail's LDS; needs init_tail_kernels on the device; hipError_t
 int launch_find_boards(const FindBoardsArgs &b, void *stream);
+// k_grow_boards (agx_grow_boards_enqueue): per frame the boards of caller-given seed quads, Board::new (board.rs:26-48) at the
+// caller's spacing_ratio, and the best of them out as k_find_boards writes its board.  The list and the results are
+// FindBoardsArgs'; all pointers are device pointers.
+struct GrowBoardsArgs : FindBoardsArgs {
+    const uint32_t *seed_quads;   // [n_frames][seeds_per_frame][4]: slot numbers within the frame, init_quads' corner order
+    uint32_t seeds_per_frame;     // > 0
+    const uint32_t *seed_counts;  // [n_frames]: frame f has min(seed_counts[f], seeds_per_frame) seeds, or null: seeds_per_frame
+    float spacing_ratio;          // finite, 1.0f + spacing_ratio > 0
+    uint32_t stop_score;          // > 0: no seed is taken behind the first one that leaves the best score at or above it
+    int flags;                    // AGX_GROW_FIX_MISSING
+    uint32_t *seed_scores;        // [n_frames][seeds_per_frame] or null: the seeds' scores (0 behind the stop); FOUND / CAPACITY frames
+    uint32_t *best_seed;          // [n_frames] or null: the chosen board's seed; FOUND / CAPACITY frames
+};
+// as launch_find_boards; n_frames * seeds_per_frame < 2^27; hipError_t
+int launch_grow_boards(const GrowBoardsArgs &b, void *stream);
 // k_collect_tags (agx_collect_tags_enqueue): one round's bookkeeping of detect's loop (detector.rs:510-539) per frame -- the
 // decoded quads of the round into the frame's tag table (detected_tags.insert, :520: a tag keeps the row of its first insertion and
 // takes the corners of its last) and AGX_POINT_USED into the status words of their saddles (:521-536).  No pixels.  All pointers

@@ -39,9 +39,12 @@
 // k_decode_quads (at the end of the file) is the decode alone, for quads the caller names: agx_decode_quads_enqueue.
 // k_find_boards is the board search alone, for saddle lists the caller names (agx_find_boards_enqueue): the same body as
 // k_board_tail (board_tail_body), one round of it up to the complete quad list, which goes out instead of being decoded.
+// k_grow_boards is that body once more with the caller's seed quads in place of init_quads' and the caller's spacing_ratio in
+// place of 0.3 (agx_grow_boards_enqueue): build_board_w / expand_one_w / probe4_w instantiated with the ratio at run time.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "libm_f32.h"
 #include "tail_kernels.h"
@@ -128,6 +131,11 @@ struct Ctx {
     float ox, oy, inv_cell;
     int nx, ny, n;
     u64 *memo_p, *memo_q;
+};
+// k_grow_boards' Ctx: 1 + the caller's spacing_ratio with it (the other kernels' is the constant 1.0f + 0.3f, and their Ctx --
+// which the compiler keeps partly in scratch -- stays as it is).  What is instantiated with RT is handed one of these.
+struct CtxRatio : Ctx {
+    float ratio0;
 };
 
 __device__ __forceinline__ float theta_dist(float t0, float t1)  // math_util.rs:15-23
@@ -372,6 +380,9 @@ __device__ __forceinline__ u64 q_make(int a, int b, int c, int d) { return (u64)
 // by `dist_sq <= radius_sq` leaves: a saddle within the radius that is among the three nearest of all is among the three
 // nearest of those within the radius, and the other way round), found in the grid cells the radius reaches.  Then the
 // reference's four nested loops as one combination per lane; the first valid one in loop order is the result.
+// RT: Board::new's spacing_ratio (board.rs:26, :186) is the launch's (c.ratio0) instead of detect's constant 0.3 -- a query point
+// may then lie anywhere, and one beyond 1e9 looks at every saddle instead of at grid cells (a cell number is an int).
+template <bool RT = false>
 __device__ bool expand_one_w(const Ctx &c, const uint8_t *slot, u64 qs, u64 &out, int lane, uint32_t &status, unsigned long long *ek)
 {
     AGX_TT(unsigned long long e_last = wall_clock64();)
@@ -388,14 +399,14 @@ __device__ bool expand_one_w(const Ctx &c, const uint8_t *slot, u64 qs, u64 &out
     AGX_TT(ek[7] += (unsigned long long)__popcll(__ballot((uint32_t)(pe >> 32) != pkey)) / 16;)  // (queries of this call that miss the memo)
     if ((uint32_t)(pe >> 32) != pkey) {  // (the 16 lanes of a query alike)
         const float ax = c.sx[ia], ay = c.sy[ia], bx = c.sx[ib], by = c.sy[ib];
-        const float ratio0 = 1.0f + 0.3f;
+        const float ratio0 = RT ? static_cast<const CtxRatio &>(c).ratio0 : 1.0f + 0.3f;
         const float ex = ax - bx, ey = ay - by;
         const float radius_sq = 0.5f * (ex * ex + ey * ey);
         const float v10x = bx - ax, v10y = by - ay;
         const float qx = c.sx[anchor] + v10x * ratio0, qy = c.sy[anchor] + v10y * ratio0;
         u64 k0 = ~0ull, k1 = ~0ull, k2 = ~0ull;
         const float r = __builtin_amdgcn_sqrtf(radius_sq) * 1.0001f + 1e-3f;  // (only bounds the cells looked at: the hardware's square root, 1 ulp, and a margin)
-        if (!(r < 3e38f)) {  // (not on image coordinates) everything
+        if (!(r < 3e38f) || (RT && !(fabsf(qx) < 1e9f && fabsf(qy) < 1e9f))) {  // (not on image coordinates) everything
             for (int t = l; t < c.n; t += 16) top3_insert(dist_key(qx, qy, c.gx[t], c.gy[t], c.gi[t]), k0, k1, k2);
         } else {
             // the cell rows the radius reaches, four at a time: four lanes per row, each takes every fourth saddle of the row's
@@ -500,6 +511,7 @@ __device__ __forceinline__ uint32_t quad_min_u(uint32_t v)
 // is no tag's: all four): try_expand then need not ask.  Asked of a board's first cell only -- most boards end there; for the
 // cells found later it costs more than it saves (measured).  The lists go to the memo: a direction that can be expanded
 // finds them there.  -> bit d: direction d cannot be expanded
+template <bool RT = false>
 __device__ uint32_t probe4_w(const Ctx &c, u64 quad, int lane)
 {
     const int q16 = lane >> 2, sub = lane & 3, dir = q16 >> 2, g = q16 & 3;
@@ -512,14 +524,14 @@ __device__ uint32_t probe4_w(const Ctx &c, u64 quad, int lane)
     uint32_t raw = (uint32_t)pe;
     if ((uint32_t)(pe >> 32) != pkey) {  // (the four lanes of a query alike)
         const float ax = c.sx[ia], ay = c.sy[ia], bx = c.sx[ib], by = c.sy[ib];
-        const float ratio0 = 1.0f + 0.3f;
+        const float ratio0 = RT ? static_cast<const CtxRatio &>(c).ratio0 : 1.0f + 0.3f;
         const float ex = ax - bx, ey = ay - by;
         const float radius_sq = 0.5f * (ex * ex + ey * ey);
         const float v10x = bx - ax, v10y = by - ay;
         const float qx = c.sx[anchor] + v10x * ratio0, qy = c.sy[anchor] + v10y * ratio0;
         u64 k0 = ~0ull, k1 = ~0ull, k2 = ~0ull;
         const float r = __builtin_amdgcn_sqrtf(radius_sq) * 1.0001f + 1e-3f;
-        if (!(r < 3e38f)) {
+        if (!(r < 3e38f) || (RT && !(fabsf(qx) < 1e9f && fabsf(qy) < 1e9f))) {
             for (int t = sub; t < c.n; t += 4) top3_insert(dist_key(qx, qy, c.gx[t], c.gy[t], c.gi[t]), k0, k1, k2);
         } else {
             const int xa = cell_x(c, qx - r), xb = cell_x(c, qx + r), ya = cell_y(c, qy - r), yb = cell_y(c, qy + r);
@@ -560,6 +572,7 @@ __device__ uint32_t probe4_w(const Ctx &c, u64 quad, int lane)
 // Board::new (board.rs:26-48): the board grown from a seed quad; returns its score, the cells stay in the slot.
 // try_expand's recursion (:114-152) is a stack of (cell, next direction) walked by all lanes alike: the top of the stack lives
 // in registers, lane 0 writes the slot, one wave-level ordering point per step.  A grid byte = the cell's number, bit 7 = found.
+template <bool RT = false>
 __device__ int build_board_w(const Ctx &c, uint8_t *slot, u64 seed, int lane, int &n_cells_out, uint32_t &status, unsigned long long *ek)
 {
     {
@@ -589,7 +602,7 @@ __device__ int build_board_w(const Ctx &c, uint8_t *slot, u64 seed, int lane, in
     int n_cells = 1, score = 1, sp = 1;
     int cur = 0, cur_i = 0, cur_x = 0, cur_y = 0;  // the top of the stack: cell, next direction, the cell's coordinates and quad
     u64 cur_quad = seed;
-    uint32_t cur_dead = probe4_w(c, seed, lane);  // its directions that cannot be expanded (probe4_w)
+    uint32_t cur_dead = probe4_w<RT>(c, seed, lane);  // its directions that cannot be expanded (probe4_w)
     for (;;) {
         if (cur_i == 4) {  // this cell is done: back to the one it was reached from
             if (--sp == 0) break;
@@ -612,7 +625,7 @@ __device__ int build_board_w(const Ctx &c, uint8_t *slot, u64 seed, int lane, in
         if (e != 0xff && (e & 0x80)) continue;  // :132-136 already found
         const u64 qs = i ? (cur_quad >> (16 * i) | cur_quad << (64 - 16 * i)) : cur_quad;  // qs[j] = quad[(j + i) & 3]
         u64 nq = 0;
-        const bool ok = ((cur_dead >> i) & 1u) ? false : expand_one_w(c, slot, qs, nq, lane, status, ek);
+        const bool ok = ((cur_dead >> i) & 1u) ? false : expand_one_w<RT>(c, slot, qs, nq, lane, status, ek);
         int at = e & 0x7f;
         if (e == 0xff) {
             if (n_cells == BCELLS) {
@@ -979,10 +992,15 @@ __device__ __forceinline__ bool fb_finite(float v) { return (__float_as_uint(v) 
 //   FIND true:  k_find_boards -- exactly one try_find_best_board (detector.rs:588-639) over a caller-given list (b): the round
 //               up to the point where quads[n_quads] is complete, then the quads go out as slot numbers; no luma, no code list
 //               (their 5120 bytes of LDS hold the list-to-slot map).  Of `a` only debug_band / debug / debug_frame are read.
-// Everything FIND decides is a compile-time branch: each kernel's instruction stream holds its own side only.
-template <bool FIND>
-__device__ __forceinline__ void board_tail_body(const TailArgs &a, const FindBoardsArgs &b)
+//   GROW:       k_grow_boards -- FIND's frame set-up and results, but no seeds and no init_quads: the boards of the caller's seed
+//               quads (b: GrowBoardsArgs), Board::new (board.rs:26-48) at the caller's spacing_ratio, a wave per seed, the seeds
+//               in groups of TW with the caller's stop rule between the groups; the first seed with the highest score is the
+//               board (detector.rs:622's `>`), try_fix_missing only if the caller asks for it.
+// Everything MODE decides is a compile-time branch: each kernel's instruction stream holds its own side only.
+template <int MODE, typename B>
+__device__ __forceinline__ void board_tail_body(const TailArgs &a, const B &b)
 {
+    constexpr bool FIND = MODE != 0, GROW = MODE == 2;  // (MODE 0: k_board_tail, 1: k_find_boards, 2: k_grow_boards)
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int f = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const u64 below = (1ull << lane) - 1ull;
@@ -1008,6 +1026,8 @@ __device__ __forceinline__ void board_tail_body(const TailArgs &a, const FindBoa
 #define TK(i) AGX_TT(do { const unsigned long long t_now = wall_clock64(); tk[i] += t_now - t_last; t_last = t_now; } while (0))
     int n = 0, n_first = 0;
     int group_no = 0;  // (counts the groups of seeds over all rounds)
+    uint32_t g_seeds = 0, g_best_seed = 0;  // GROW: the frame's seed quads; the seed of the chosen board
+    (void)g_seeds; (void)g_best_seed;
     u64 *codes = reinterpret_cast<u64 *>(lds + OFF_CODES);
     uint32_t *slot_of = reinterpret_cast<uint32_t *>(lds + OFF_CODES);  // FIND: u32[TN], list position -> slot number within the frame
     const uint8_t *luma = nullptr;
@@ -1111,6 +1131,24 @@ __device__ __forceinline__ void board_tail_body(const TailArgs &a, const FindBoa
         n_first = n;
         __syncthreads();  // (sh[3] is read; the search's first wave writes the shared words)
         if (tid == 0) sh[3] = 0;
+        if constexpr (GROW) {
+            // the frame's seeds: every corner names a listed slot of the frame, or the frame is AGX_BOARD_INPUT (asked of the
+            // caller's words, not of the list in LDS: that one ends at TN).  No seed: no board.
+            g_seeds = b.seeds_per_frame;
+            if (b.seed_counts) g_seeds = b.seed_counts[f] < g_seeds ? b.seed_counts[f] : g_seeds;
+            const uint32_t *sq = b.seed_quads + (u64)f * (u64)b.seeds_per_frame * 4u;
+            bool bad_seed = false;
+            for (u64 i = (u64)tid; i < 4ull * g_seeds; i += 64 * TW) {
+                const uint32_t s = sq[i];
+                if ((u64)s >= n_slots) bad_seed = true;
+                else if (b.point_status && b.point_status[first_slot + s] != 0u) bad_seed = true;
+            }
+            const int any_bad = __syncthreads_or(bad_seed ? 1 : 0);
+            if (early != AGX_BOARD_INPUT) {
+                if (any_bad) early = AGX_BOARD_INPUT;
+                else if (g_seeds == 0) early = AGX_BOARD_NONE;
+            }
+        }
     }
     if (early != 0xffffffffu) {  // (the whole workgroup alike)
         if (tid == 0) {
@@ -1124,7 +1162,7 @@ __device__ __forceinline__ void board_tail_body(const TailArgs &a, const FindBoa
 
     for (int round = 0; round < (FIND ? 1 : a.max_boards) && n > 0; ++round) {
         // ---- the k-NN grid over this round's saddles (every wave derives the geometry, the first one fills the cells) ----
-        Ctx c;
+        typename std::conditional<GROW, CtxRatio, Ctx>::type c;
         c.sx = sx; c.sy = sy; c.st = st; c.gx = gx; c.gy = gy; c.gi = gi; c.gstart = gstart; c.n = n;
         c.memo_p = reinterpret_cast<u64 *>(lds + OFF_MEMO_P);
         c.memo_q = reinterpret_cast<u64 *>(lds + OFF_MEMO_Q);
@@ -1181,6 +1219,7 @@ __device__ __forceinline__ void board_tail_body(const TailArgs &a, const FindBoa
             }
             wsync();
             TK(0);
+            if constexpr (!GROW) {  // (the caller's quads are the seeds there)
             // ---- seeds: the most populated round(theta) bin (ties: the smallest angle), in index order ---------------
             for (int i = lane; i < 364; i += 64) hist[i] = 0;
             wsync();
@@ -1203,6 +1242,7 @@ __device__ __forceinline__ void board_tail_body(const TailArgs &a, const FindBoa
             }
             if (lane == 0) sh[2] = (uint32_t)ns_;
             TK(1);
+            }
         }
         __syncthreads();
         for (int i = tid; i < 2 * TMEMO; i += 64 * TW) c.memo_p[i] = 0ull;  // both memo tables: this round's saddle numbers
@@ -1216,6 +1256,97 @@ __device__ __forceinline__ void board_tail_body(const TailArgs &a, const FindBoa
         uint32_t best_score = 0, win_stamp = 0;
         u64 best_quad = 0;
         bool stop = false;
+        if constexpr (GROW) {
+        // ---- the caller's seed quads in their order, TW at a time: the waves take the group's seeds from a common counter and
+        // grow a board each (Board::new at the launch's ratio); a seed's word is its score.  Behind the group's barrier every
+        // thread walks the words in seed order: the first seed that beats everything before it is the board so far, and the
+        // loop ends behind the first seed that leaves the best score at stop_score or above -- the seeds behind it read 0,
+        // whatever a wave has grown of them.  The wave that grew the board so far keeps its cells (as in the search below).
+        // Shared words: sh[8], sh[9] the groups' counters (alternately: a group clears the other one), sh[10 + k] the score and
+        // sh[18 + 2 k], sh[19 + 2 k] the quad (list positions) of the group's seed k.
+        c.ratio0 = 1.0f + b.spacing_ratio;
+        const uint32_t *sq = b.seed_quads + (u64)f * (u64)b.seeds_per_frame * 4u;
+        uint32_t *sc_out = b.seed_scores ? b.seed_scores + (u64)f * (u64)b.seeds_per_frame : nullptr;
+        uint32_t done = 0;  // seeds whose score is written
+        for (uint32_t base = 0; base < g_seeds && !stop; base += TW, ++group_no) {
+            const uint32_t gw = g_seeds - base < (uint32_t)TW ? g_seeds - base : (uint32_t)TW;
+            uint32_t *ctr = sh + 8 + (group_no & 1);
+            if (tid == 0) sh[8 + ((group_no & 1) ^ 1)] = 0;  // (last read before the barrier that ended the group before this one)
+            uint32_t kept_score = 0;
+            int kept_k = 0, kept_cells = 0;
+            for (;;) {
+                uint32_t k = lane == 0 ? atomicAdd(ctr, 1u) : 0u;
+                k = (uint32_t)__shfl((int)k, 0);
+                if (k >= gw) break;
+                // the seed's slots -> positions in the list (slot_of ascends: the list is in slot order), a corner per lane
+                int pos = 0;
+                {
+                    const uint32_t s = sq[4ull * (base + k) + (uint32_t)(lane & 3)];
+                    int lo = 0, hi = n - 1;
+                    while (lo < hi) {
+                        const int mid = (lo + hi) >> 1;
+                        if (slot_of[mid] < s) lo = mid + 1;
+                        else hi = mid;
+                    }
+                    pos = lo;
+                }
+                const u64 q = q_make(__shfl(pos, 0), __shfl(pos, 1), __shfl(pos, 2), __shfl(pos, 3));
+                int cells;
+                const uint32_t score = (uint32_t)build_board_w<true>(c, wv + WV_SLOT, q, lane, cells, status, ek);
+                ++n_boards;
+                if (lane == 0) {
+                    sh[10 + k] = score;
+                    sh[18 + 2 * k] = (uint32_t)q;
+                    sh[19 + 2 * k] = (uint32_t)(q >> 32);
+                }
+                if (score > best_score && (score > kept_score || (score == kept_score && (int)k < kept_k))) {
+                    kept_score = score;
+                    kept_k = (int)k;
+                    kept_cells = cells;
+                    const uint32_t *src = reinterpret_cast<const uint32_t *>(wv + WV_SLOT);
+                    uint32_t *dst = reinterpret_cast<uint32_t *>(wv + WV_KEEP);
+                    for (int i = lane; i < SL_GRID / 4; i += 64) dst[i] = src[i];
+                    wsync();
+                }
+            }
+            status = wave_or_u(status);
+            if (lane == 0 && status) atomicOr(&sh[0], status);
+            __syncthreads();
+            int win_k = -1;
+            uint32_t live = gw;  // seeds of the group the loop has reached
+            for (uint32_t k = 0; k < gw; ++k) {
+                if (sh[10 + k] > best_score) {
+                    best_score = sh[10 + k];
+                    win_k = (int)k;
+                    g_best_seed = base + k;
+                    best_quad = (u64)sh[19 + 2 * k] << 32 | sh[18 + 2 * k];
+                }
+                if (b.stop_score && best_score >= b.stop_score) {
+                    stop = true;
+                    live = k + 1;
+                    break;
+                }
+            }
+            if (sc_out && (uint32_t)tid < gw) sc_out[base + (uint32_t)tid] = (uint32_t)tid < live ? sh[10 + tid] : 0u;
+            done = base + gw;
+            if (sh[0]) stop = true;  // the frame goes to the host anyway
+            // sh[5 .. 7] outlive the group: a wave overwrites its WV_KEEP only with a board that beats best_score, that is in a group
+            // that chooses anew and so takes a new stamp -- then either the holder of the new board rewrites all three words, or
+            // nobody does and sh[7] no longer equals win_stamp: the board is grown again from best_quad.  Never stale cells.
+            if (win_k >= 0) {  // (every thread alike)
+                win_stamp = base + (uint32_t)win_k + 1u;
+                if (lane == 0 && kept_score == best_score && kept_k == win_k) {
+                    sh[5] = (uint32_t)wave + 1u;
+                    sh[6] = (uint32_t)kept_cells;
+                    sh[7] = win_stamp;
+                }
+            }
+            __syncthreads();
+        }
+        if (sc_out)
+            for (u64 i = (u64)done + (u64)tid; i < (u64)g_seeds; i += 64 * TW) sc_out[i] = 0u;
+        (void)total;
+        } else {
         // Seeds in groups of TW: every wave lists the candidate quads of one; then the boards.  The first group's boards in two
         // steps -- the first seed alone (it usually finds the board and ends the loop: its neighbours in the list would find
         // it again, fifty times the work), then the other seven, whose lists are there already.
@@ -1307,6 +1438,7 @@ __device__ __forceinline__ void board_tail_body(const TailArgs &a, const FindBoa
             __syncthreads();
             }
         }
+        }
         TK(5);
         if (sh[0] || best_score == 0) break;  // (None: the remaining rounds would find nothing either)
 
@@ -1327,7 +1459,7 @@ __device__ __forceinline__ void board_tail_body(const TailArgs &a, const FindBoa
                     slot[SL_GRID + (xy[2 * i + 1] + BGR) * BGN + (xy[2 * i] + BGR)] = (uint8_t)(i | (slot[SL_FOUND + i] ? 0x80 : 0));
                 wsync();
             } else {
-                (void)build_board_w(c, slot, best_quad, lane, best_cells, status, ek);
+                (void)build_board_w<GROW>(c, slot, best_quad, lane, best_cells, status, ek);
             }
             int n_quads = 0;
             {
@@ -1367,6 +1499,9 @@ __device__ __forceinline__ void board_tail_body(const TailArgs &a, const FindBoa
                         fm[at] = (uint8_t)i;
                     }
                     n_fix += __popcll(mk);
+                }
+                if constexpr (GROW) {
+                    if (!(b.flags & AGX_GROW_FIX_MISSING)) n_fix = 0;  // (the board as Board::new left it)
                 }
                 if (n_fix) {  // (rare)
                     wsync();
@@ -1569,6 +1704,9 @@ __device__ __forceinline__ void board_tail_body(const TailArgs &a, const FindBoa
         if (tid == 0) {
             b.n_quads[f] = fst == AGX_BOARD_FOUND || fst == AGX_BOARD_CAPACITY ? nq : 0u;
             b.status[f] = fst;
+            if constexpr (GROW) {
+                if (b.best_seed && (fst == AGX_BOARD_FOUND || fst == AGX_BOARD_CAPACITY)) b.best_seed[f] = g_best_seed;
+            }
         }
         (void)n_first; (void)n_tags; (void)t_start; (void)n_seeds_done;
     } else {
@@ -1581,14 +1719,23 @@ __device__ __forceinline__ void board_tail_body(const TailArgs &a, const FindBoa
     }
 }
 
-__global__ void __launch_bounds__(64 * TW) k_board_tail(TailArgs a) { board_tail_body<false>(a, FindBoardsArgs{}); }
+__global__ void __launch_bounds__(64 * TW) k_board_tail(TailArgs a) { board_tail_body<0>(a, FindBoardsArgs{}); }
 
 // agx_find_boards_enqueue: try_find_best_board (detector.rs:588-639) of caller-given saddle lists, one workgroup per frame
 __global__ void __launch_bounds__(64 * TW) k_find_boards(FindBoardsArgs b)
 {
     TailArgs a{};
     a.debug_band = b.debug_band;
-    board_tail_body<true>(a, b);
+    board_tail_body<1>(a, b);
+}
+
+// agx_grow_boards_enqueue: the boards of caller-given seed quads at the caller's spacing_ratio (board.rs:26-48), the best of
+// them out as k_find_boards writes its board; one workgroup per frame
+__global__ void __launch_bounds__(64 * TW) k_grow_boards(GrowBoardsArgs b)
+{
+    TailArgs a{};
+    a.debug_band = b.debug_band;
+    board_tail_body<2>(a, b);
 }
 
 // agx_detect_batch_enqueue_to: frame f's entry of the tail's table (count, status) and its rows into the caller's arrays, as
@@ -1953,7 +2100,19 @@ int init_tail_kernels()
 {
     const hipError_t e = hipFuncSetAttribute((const void *)k_board_tail, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     if (e != hipSuccess) return (int)e;
-    return (int)hipFuncSetAttribute((const void *)k_find_boards, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    const hipError_t e2 = hipFuncSetAttribute((const void *)k_find_boards, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    if (e2 != hipSuccess) return (int)e2;
+    return (int)hipFuncSetAttribute((const void *)k_grow_boards, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+}
+
+int launch_grow_boards(const GrowBoardsArgs &b, void *stream)
+{
+    if (b.n_frames <= 0) return (int)hipSuccess;
+    if (b.stride < 20 || (b.stride & 3) || !b.saddles_per_frame || !b.quads_per_frame || (b.counts && b.frame_table) || !b.saddles || !b.quads ||
+        !b.n_quads || !b.status || !b.seed_quads || !b.seeds_per_frame || !__builtin_isfinite(b.spacing_ratio) || !(1.0f + b.spacing_ratio > 0.0f))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_grow_boards, dim3((unsigned)b.n_frames), dim3(64 * TW), LDS_BYTES, (hipStream_t)stream, b);
+    return (int)hipGetLastError();
 }
 
 int launch_find_boards(const FindBoardsArgs &b, void *stream)

@@ -160,6 +160,7 @@ class TagDetector:
         self._refine = None  # refine_points_enqueue's batch: (n, points per frame, tensors kept alive, device outputs or None)
         self._decode = None  # decode_quads_enqueue's batch: (n, quads per frame, tensors kept alive, device outputs or None)
         self._find = None    # find_boards_enqueue's batch: (n, quads per frame, tensors kept alive, device outputs or None)
+        self._grow = None    # grow_boards_enqueue's batch: the tensors kept alive (the library itself knows whether it is in flight)
         self._clusters = None  # clusters_enqueue's batch: (n, clusters per frame, tensors kept alive, device outputs or None)
         try:
             if blur_sigma is not None:
@@ -448,7 +449,7 @@ class TagDetector:
         self._batch = (n, frames)  # keep the tensor alive until fetched
         self._detect = None
         self._refine = None
-        self._decode = self._find = None
+        self._decode = self._grow = self._find = None
 
     def saddles_batch_enqueue_to(self, frames, out_saddles, frame_table, format=None):
         """Device-resident results: out_saddles float32 [capacity, 5] and frame_table int32
@@ -464,7 +465,7 @@ class TagDetector:
         self._batch = None
         self._detect = None
         self._refine = None
-        self._decode = self._find = None
+        self._decode = self._grow = self._find = None
 
     def saddles_batch_enqueue_ptr(self, dptr, n, w, h, row_stride, frame_stride, fmt, follow_torch_stream=True):
         """agx_saddles_batch_enqueue on a raw device address (any row / frame stride: a view cut out of a larger allocation).
@@ -478,7 +479,7 @@ class TagDetector:
         self._batch = (n, None)
         self._detect = None
         self._refine = None
-        self._decode = self._find = None
+        self._decode = self._grow = self._find = None
 
     def saddles_batch_fetch(self, cap_per_frame=None, raise_on_overflow=True):
         """-> (list of SADDLE_DTYPE arrays, one per frame; per-frame status array).  cap_per_frame None:
@@ -538,7 +539,7 @@ class TagDetector:
         self._batch = None  # (one batch in flight per handle: this one replaces a saddle batch)
         self._detect = None
         self._refine = None
-        self._decode = self._find = None
+        self._decode = self._grow = self._find = None
         if out is None:
             self._check(self._lib.agx_detect_batch_enqueue(self._h, C.c_void_p(dptr), n, w, h, row_stride, frame_stride, fmt, cap))
         else:
@@ -619,7 +620,7 @@ class TagDetector:
         out = np.zeros(n, SADDLE_DTYPE)
         status = np.zeros(n, np.uint32)
         n_refined = C.c_uint32(0)
-        self._batch = self._detect = self._refine = self._decode = self._find = None
+        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = None
         self._check(self._lib.agx_rochade_refine_h(self._h, a.ctypes.data, w, h, stride, fmt, self._refine_image(image), pts.ctypes.data, n,
                                                    out.ctypes.data, status.ctypes.data, C.byref(n_refined), int(half_size_patch)))
         assert n_refined.value == int((status == _ffi.AGX_POINT_REFINED).sum())
@@ -651,7 +652,7 @@ class TagDetector:
         p_out = tensor(out, torch.float32, (n, ppf, 5), "out") if out is not None else None
         p_status = tensor(status, torch.int32, (n, ppf), "status") if status is not None else None
         self._follow_torch_stream(frames)
-        self._batch = self._detect = self._refine = self._decode = self._find = None
+        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = None
         self._check(self._lib.agx_refine_points_enqueue_h(self._h, frames.data_ptr(), n, w, h, rs, fs, fmt, self._refine_image(image), p_points,
                                                           ppf, p_counts, p_out, p_status, int(half_size_patch)))
         self._refine = (n, ppf, (frames, points, counts), (out, status) if out is not None else None)
@@ -663,7 +664,7 @@ class TagDetector:
             raise AgxError(_ffi.AGX_ERR_STATE, "no refine batch enqueued")
         n, ppf, _, dev_out = self._refine
         self._refine = None
-        self._decode = self._find = None
+        self._decode = self._grow = self._find = None
         if dev_out is not None:
             self._check(self._lib.agx_refine_points_fetch(self._h, None, None))
             return dev_out
@@ -686,7 +687,7 @@ class TagDetector:
         status = np.zeros(n, np.uint32)
         bits = np.zeros(n, np.uint64)
         n_decoded = C.c_uint32(0)
-        self._batch = self._detect = self._refine = self._decode = self._find = None
+        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = None
         self._check(self._lib.agx_decode_quads(self._h, a.ctypes.data, w, h, stride, fmt, q.ctypes.data, n, out.ctypes.data,
                                                status.ctypes.data, bits.ctypes.data if with_bits else None, C.byref(n_decoded)))
         assert n_decoded.value == int((status == _ffi.AGX_QUAD_DECODED).sum())
@@ -736,7 +737,7 @@ class TagDetector:
         p_status = tensor(status, torch.int32, (n, qpf), "status") if status is not None else None
         p_bits = tensor(bits, torch.int64, (n, qpf), "bits") if bits is not None else None
         self._follow_torch_stream(frames)
-        self._batch = self._detect = self._refine = self._decode = self._find = None
+        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = None
         self._check(self._lib.agx_decode_quads_enqueue(self._h, frames.data_ptr(), n, w, h, rs, fs, fmt, p_quads, stride, qpf, p_counts,
                                                        p_point_status, p_out, p_status, p_bits))
         self._decode = (n, qpf, (frames, quads, refined, counts), (out, status, bits) if out is not None else None)
@@ -748,7 +749,7 @@ class TagDetector:
         if self._decode is None:
             raise AgxError(_ffi.AGX_ERR_STATE, "no decode batch enqueued")
         n, qpf, _, dev_out = self._decode
-        self._decode = self._find = None
+        self._decode = self._grow = self._find = None
         if dev_out is not None:
             self._check(self._lib.agx_decode_quads_fetch(self._h, None, None, None))
             return dev_out
@@ -791,7 +792,7 @@ class TagDetector:
         return n, qpf, 8, self._stage_tensor(quads, torch.float32, tuple(quads.shape), "quads", dev), None, dev
 
     def _replaces_batch(self):
-        self._batch = self._detect = self._refine = self._decode = self._find = self._clusters = None
+        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = self._clusters = None
 
     def decode_positions_enqueue(self, quads=None, points=None, status=None, img_size=None, border_bits=None, edge_bits=None, margin=0.5,
                                  counts=None, refined=None):
@@ -965,7 +966,7 @@ class TagDetector:
         p_st = tensor(status, torch.int32, (n,), "status") if status is not None else None
         p_pts = tensor(quad_points, torch.float32, (n, qpf, 4, 2), "quad_points") if quad_points is not None else None
         self._follow_torch_stream(saddles)
-        self._batch = self._detect = self._refine = self._decode = self._find = None
+        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = None
         self._check(self._lib.agx_find_boards_enqueue(self._h, saddles.data_ptr(), stride, n, spf, p_counts, p_table, p_ps, qpf, p_quads, p_pts,
                                                       p_n, p_st))
         self._find = (n, qpf, (saddles, counts, frame_table, point_status, quad_points),
@@ -979,7 +980,7 @@ class TagDetector:
         if self._find is None:
             raise AgxError(_ffi.AGX_ERR_STATE, "no find-boards batch enqueued")
         n, qpf, keep, dev_out = self._find
-        self._batch = self._detect = self._refine = self._decode = self._find = None
+        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = None
         if dev_out is not None:
             self._check(self._lib.agx_find_boards_fetch(self._h, None, None, None, None, n_threads))
             return dev_out
@@ -990,6 +991,66 @@ class TagDetector:
         self._check(self._lib.agx_find_boards_fetch(self._h, quads.ctypes.data, pts.ctypes.data, n_quads.ctypes.data, status.ctypes.data,
                                                     n_threads))
         return quads, pts, n_quads, status
+
+    # ---- boards from the caller's seed quads (src/board.rs:26-112) --------------------------
+    def grow_boards_enqueue(self, saddles, seed_quads, quads, n_quads, status, counts=None, frame_table=None, point_status=None,
+                            seed_counts=None, spacing_ratio=0.3, stop_score=0, fix_missing=True, quad_points=None, seed_scores=None,
+                            best_seed=None):
+        """Board::new from every seed quad of every frame at spacing_ratio, the first seed with the highest score out as
+        find_boards_enqueue writes its board; stream-ordered behind torch's current stream, returns immediately.  saddles, counts,
+        frame_table and point_status as find_boards_enqueue's.  seed_quads int32 [N, S, 4]: slot numbers within the frame (a row of
+        find_boards_enqueue's quads is one); seed_counts int32 [N] optionally.  quads int32 [N, Q, 4], n_quads and status int32 [N]:
+        the device-resident results (required); quad_points float32 [N, Q, 4, 2], seed_scores int32 [N, S] and best_seed int32 [N]
+        optionally.  stop_score > 0: no seed is grown behind the first one that leaves the best score at or above it."""
+        import torch
+        if not (getattr(saddles, "is_cuda", False) and saddles.is_contiguous() and saddles.dtype == torch.float32 and saddles.shape[-1] >= 5):
+            raise AgxError(_ffi.AGX_ERR_ARG, "saddles must be a contiguous float32 device tensor [N, S, K >= 5] (or [capacity, K] with frame_table)")
+        dev = saddles.device
+        stride = 4 * int(saddles.shape[-1])
+
+        def tensor(t, dtype, shape, what):
+            if t is None:
+                return None
+            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and (shape is None or tuple(t.shape) == shape)
+                    and t.device == dev):
+                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s tensor %s on the saddles' device" % (what, dtype, shape))
+            return t.data_ptr()
+
+        if frame_table is not None:
+            if saddles.dim() != 2 or frame_table.dim() != 2 or frame_table.shape[1] != 4:
+                raise AgxError(_ffi.AGX_ERR_ARG, "with frame_table [N, 4]: saddles [capacity, K]")
+            n, spf, n_slots = int(frame_table.shape[0]), int(saddles.shape[0]), int(saddles.shape[0])
+        else:
+            if saddles.dim() != 3 or saddles.shape[1] == 0:
+                raise AgxError(_ffi.AGX_ERR_ARG, "saddles must be [N, S, K]")
+            n, spf = int(saddles.shape[0]), int(saddles.shape[1])
+            n_slots = n * spf
+        if point_status is not None and point_status.numel() != n_slots:
+            raise AgxError(_ffi.AGX_ERR_ARG, "point_status: one word per slot")
+        if seed_quads is None or seed_quads.dim() != 3 or quads is None or quads.dim() != 3:
+            raise AgxError(_ffi.AGX_ERR_ARG, "seed_quads [N, S, 4] and quads [N, Q, 4]")
+        seeds, qpf = int(seed_quads.shape[1]), int(quads.shape[1])
+        ptrs = (tensor(counts, torch.int32, (n,), "counts"), tensor(frame_table, torch.int32, (n, 4), "frame_table"),
+                tensor(point_status, torch.int32, None, "point_status"), tensor(seed_quads, torch.int32, (n, seeds, 4), "seed_quads"),
+                tensor(seed_counts, torch.int32, (n,), "seed_counts"))
+        outs = (tensor(quads, torch.int32, (n, qpf, 4), "quads"), tensor(quad_points, torch.float32, (n, qpf, 4, 2), "quad_points"),
+                tensor(n_quads, torch.int32, (n,), "n_quads"), tensor(status, torch.int32, (n,), "status"),
+                tensor(seed_scores, torch.int32, (n, seeds), "seed_scores"), tensor(best_seed, torch.int32, (n,), "best_seed"))
+        self._follow_torch_stream(saddles)
+        rc = self._lib.agx_grow_boards_enqueue(self._h, saddles.data_ptr(), stride, n, spf, ptrs[0], ptrs[1], ptrs[2], ptrs[3], seeds, ptrs[4],
+                                               float(spacing_ratio), int(stop_score), _ffi.AGX_GROW_FIX_MISSING if fix_missing else 0, qpf, *outs)
+        if rc == _ffi.AGX_OK:  # (a refused argument leaves the batch in flight where it is)
+            self._replaces_batch()
+            self._grow = (saddles, counts, frame_table, point_status, seed_quads, seed_counts, quads, quad_points, n_quads, status, seed_scores,
+                          best_seed)
+        self._check(rc)
+
+    def grow_boards_fetch(self, n_threads=0):
+        """Wait for grow_boards_enqueue's batch and let the host form answer the frames the kernel handed back: the device tensors
+        that call was given are complete when this returns."""
+        if self._grow is not None:  # in flight: the library resolves it whatever it returns
+            self._replaces_batch()
+        self._check(self._lib.agx_grow_boards_fetch(self._h, n_threads))
 
     # ---- gaussian_blur_f32 / hessian_response as planes (src/image_util.rs:110-206, :72-109) ----
     @staticmethod
@@ -1031,7 +1092,7 @@ class TagDetector:
             strides = (t.stride(0), t.stride(1))
         ors, ofs = (4 * strides[1], 4 * strides[0]) if strides else (4 * w, 4 * w * h)
         self._follow_torch_stream(frames)
-        self._batch = self._detect = self._refine = self._decode = self._find = None
+        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = None
         self._check(self._lib.agx_planes_enqueue(self._h, frames.data_ptr(), n, w, h, rs, fs, fmt, float(sigma),
                                                  blur.data_ptr() if blur is not None else None,
                                                  response.data_ptr() if response is not None else None, ors, ofs))
@@ -1042,7 +1103,7 @@ class TagDetector:
         a, fmt, stride = _image_args(img, format)
         h, w = _image_hw(a, fmt)
         out = np.empty((h, w), np.float32)
-        self._batch = self._detect = self._refine = self._decode = self._find = None
+        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = None
         self._check(self._lib.agx_gaussian_blur_f32(self._h, a.ctypes.data, w, h, stride, fmt, float(sigma), out.ctypes.data))
         return out
 
@@ -1051,7 +1112,7 @@ class TagDetector:
         a, fmt, stride = _image_args(img, format)
         h, w = _image_hw(a, fmt)
         out = np.empty((h, w), np.float32)
-        self._batch = self._detect = self._refine = self._decode = self._find = None
+        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = None
         self._check(self._lib.agx_hessian_response(self._h, a.ctypes.data, w, h, stride, fmt, out.ctypes.data))
         return out
 
@@ -1069,7 +1130,7 @@ class TagDetector:
         h, w = a.shape
         out = np.zeros(int(cap), _CLUSTER_DTYPE)
         n, status = C.c_uint32(0), C.c_uint32(0)
-        self._batch = self._detect = self._refine = self._decode = self._find = self._clusters = None
+        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = self._clusters = None
         self._check(self._lib.agx_cluster_centers(self._h, a.ctypes.data, w, h, a.strides[0], out.ctypes.data, int(cap), C.byref(n), C.byref(status)))
         ok = (status.value & 0xFF) == _ffi.AGX_CLUSTERS_OK
         return out[:n.value if ok else 0].copy(), status.value, n.value
@@ -1101,7 +1162,7 @@ class TagDetector:
         p_status = tensor(status, torch.int32, (n,), "status") if status is not None else None
         p_points = tensor(points, torch.float32, (n, cpf, 2), "points") if points is not None else None
         self._follow_torch_stream(response)
-        self._batch = self._detect = self._refine = self._decode = self._find = self._clusters = None
+        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = self._clusters = None
         self._check(self._lib.agx_clusters_enqueue(self._h, response.data_ptr(), n, w, h, 4 * response.stride(1), 4 * response.stride(0), cpf,
                                                    p_rows, p_points, p_counts, p_status))
         self._clusters = (n, cpf, (response, points), (clusters, points, counts, status) if clusters is not None else None)
@@ -1114,7 +1175,7 @@ class TagDetector:
         if getattr(self, "_clusters", None) is None:
             raise AgxError(_ffi.AGX_ERR_STATE, "no clusters batch enqueued")
         n, cpf, keep, dev_out = self._clusters
-        self._batch = self._detect = self._refine = self._decode = self._find = self._clusters = None
+        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = self._clusters = None
         if dev_out is not None:
             self._check(self._lib.agx_clusters_fetch(self._h, None, None, None, None))
             return dev_out
@@ -1143,7 +1204,7 @@ class TagDetector:
         if status is None:
             raise AgxError(_ffi.AGX_ERR_ARG, "status must be given")
         self._follow_torch_stream(records)
-        self._batch = self._detect = self._refine = self._decode = self._find = self._clusters = None
+        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = self._clusters = None
         self._check(self._lib.agx_filter_saddles_enqueue(self._h, records.data_ptr(), status.data_ptr(), n, ppf,
                                                          counts.data_ptr() if counts is not None else None))
 
@@ -1189,7 +1250,7 @@ class TagDetector:
             raise AgxError(_ffi.AGX_ERR_ARG, "without point_status and frame_table: saddles_per_frame= bounds the slot numbers")
         out = [tensor(tags, (n, tpf, 9), "tags"), tensor(n_tags, (n,), "n_tags"), tensor(tag_status, (n,), "tag_status")]
         self._follow_torch_stream(quads)
-        self._batch = self._detect = self._refine = self._decode = self._find = self._clusters = None
+        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = self._clusters = None
         self._check(self._lib.agx_collect_tags_enqueue(self._h, n, qpf, *p, int(saddles_per_frame or 0), p_table, p_ps, tpf, *out,
                                                        1 if reset else 0))
 
@@ -1491,7 +1552,7 @@ def _find_board_call(call, saddles, cap, keep=None):
     quads = np.zeros((max(int(cap), 0), 4), np.uint32)
     n_quads, status = C.c_uint32(0), C.c_uint32(0)
     if keep is not None:
-        keep._batch = keep._detect = keep._refine = keep._decode = keep._find = None
+        keep._batch = keep._detect = keep._refine = keep._decode = keep._grow = keep._find = None
     call(a.ctypes.data if a.shape[0] else None, a.shape[0], quads.ctypes.data if quads.shape[0] else None, quads.shape[0], C.byref(n_quads),
          C.byref(status))
     found = status.value == _ffi.AGX_BOARD_FOUND
@@ -1506,6 +1567,30 @@ def find_board_tail(saddles, cap=128):
         if st != _ffi.AGX_OK:
             raise AgxError(st)
     return _find_board_call(call, saddles, cap)
+
+
+def grow_board_tail(saddles, seeds, spacing_ratio=0.3, stop_score=0, fix_missing=True, cap=128, point_status=None):
+    """The host form of boards from seed quads (src/board.rs:26-112; agx_grow_board_tail) without a device: saddles a SADDLE_DTYPE
+    array (or [n, 5] float32), seeds [n_seeds, 4] indices into it -> (quads [n_quads, 4] uint32, status AGX_BOARD_*, n_quads,
+    seed_scores [n_seeds] uint32, best_seed); seed_scores and best_seed are None unless a board was found."""
+    a = np.asarray(saddles)
+    if a.dtype == SADDLE_DTYPE:
+        a = np.ascontiguousarray(a).view(np.float32)
+    a = np.ascontiguousarray(a, np.float32).reshape(-1, 5)
+    s = np.ascontiguousarray(seeds, np.uint32).reshape(-1, 4)
+    ps = None if point_status is None else np.ascontiguousarray(point_status, np.uint32).reshape(a.shape[0])
+    quads = np.zeros((max(int(cap), 0), 4), np.uint32)
+    scores = np.zeros(s.shape[0], np.uint32)
+    n_quads, status, best = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    st = _ffi.lib().agx_grow_board_tail(a.ctypes.data if a.shape[0] else None, a.shape[0], ps.ctypes.data if ps is not None and ps.size else None,
+                                        s.ctypes.data if s.shape[0] else None, s.shape[0], float(spacing_ratio), int(stop_score),
+                                        _ffi.AGX_GROW_FIX_MISSING if fix_missing else 0, quads.ctypes.data if quads.shape[0] else None,
+                                        quads.shape[0], C.byref(n_quads), C.byref(status), scores.ctypes.data if s.shape[0] else None, C.byref(best))
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    found = status.value == _ffi.AGX_BOARD_FOUND
+    some = found or status.value == _ffi.AGX_BOARD_CAPACITY
+    return quads[:n_quads.value if found else 0].copy(), status.value, n_quads.value, scores if some else None, best.value if some else None
 
 
 class DetectorGroup:

@@ -129,6 +129,8 @@ pub const AGX_BOARD_NONE: c_int = 1;
 pub const AGX_BOARD_CAPACITY: c_int = 2;
 pub const AGX_BOARD_INPUT: c_int = 3;
 pub const AGX_BOARD_PENDING: c_int = 4;
+// agx_grow_boards_enqueue / agx_grow_board_tail: flags
+pub const AGX_GROW_FIX_MISSING: c_int = 1;
 // cluster centres of caller-given response planes (reference src/detector.rs:414-429): what became of a frame
 pub const AGX_CLUSTERS_OK: c_int = 0;
 pub const AGX_CLUSTERS_CAPACITY: c_int = 1;
@@ -267,6 +269,16 @@ extern "C" {
                           n_quads: *mut u32, status: *mut u32) -> c_int;
     pub fn agx_find_board_tail(saddles: *const agx_saddle, n_saddles: u32, quads: *mut u32, cap: u32, n_quads: *mut u32,
                                status: *mut u32) -> c_int;
+
+    pub fn agx_grow_boards_enqueue(det: *mut agx_detector, d_saddles: *const c_void, saddle_stride_bytes: usize, n_frames: c_int,
+                                   saddles_per_frame: u32, d_counts: *const u32, d_frame_table: *const c_void, d_point_status: *const u32,
+                                   d_seed_quads: *const u32, seeds_per_frame: u32, d_seed_counts: *const u32, spacing_ratio: c_float,
+                                   stop_score: u32, flags: c_int, quads_per_frame: u32, d_quads: *mut u32, d_quad_points: *mut c_float,
+                                   d_n_quads: *mut u32, d_status: *mut u32, d_seed_scores: *mut u32, d_best_seed: *mut u32) -> c_int;
+    pub fn agx_grow_boards_fetch(det: *mut agx_detector, n_threads: c_int) -> c_int;
+    pub fn agx_grow_board_tail(saddles: *const agx_saddle, n_saddles: u32, point_status: *const u32, seed_quads: *const u32, n_seeds: u32,
+                               spacing_ratio: c_float, stop_score: u32, flags: c_int, quads: *mut u32, cap: u32, n_quads: *mut u32,
+                               status: *mut u32, seed_scores: *mut u32, best_seed: *mut u32) -> c_int;
 
     pub fn agx_planes_enqueue(det: *mut agx_detector, d_frames: *const c_void, n_frames: c_int, width: c_int, height: c_int,
                               row_stride_bytes: usize, frame_stride_bytes: usize, format: c_int, sigma: c_float, d_blur: *mut c_float,

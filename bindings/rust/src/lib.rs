@@ -466,6 +466,41 @@ pub fn find_best_board(refined: &[Saddle]) -> Option<Vec<[usize; 4]>> {
     }
 }
 
+/// reference src/board.rs:26-112 as try_find_best_board uses it (src/detector.rs:613-633), for a caller who already knows quads of
+/// the board: `Board::new(refined, all-true mask, seed, spacing_ratio, tree)` for every seed in order, the first one whose score is
+/// strictly above every earlier one, `try_fix_missing` on it if `fix_missing`, then `all_tag_indexes`.  `stop_score > 0` ends the
+/// loop behind the first seed that leaves the best score at or above it (the caller's rule, not the reference's `>= 36` per seed
+/// saddle).  Returns `(quads, score of every seed, index of the chosen seed)`, or `None` without a seed.  The host form (no
+/// device is used).  Panics on a saddle whose x, y or theta is not finite, on a seed index beyond the list and on a
+/// `spacing_ratio` that is not finite or at or below -1.
+pub fn grow_board_tail(refined: &[Saddle], seeds: &[[usize; 4]], spacing_ratio: f32, stop_score: u32, fix_missing: bool)
+                       -> Option<(Vec<[usize; 4]>, Vec<u32>, usize)> {
+    let list: Vec<ffi::agx_saddle> =
+        refined.iter().map(|s| ffi::agx_saddle { x: s.p.0, y: s.p.1, k: s.k, theta: s.theta, phi: s.phi }).collect();
+    let seed_rows: Vec<u32> = seeds.iter().flat_map(|q| q.iter().map(|&i| i as u32)).collect();
+    let flags = if fix_missing { ffi::AGX_GROW_FIX_MISSING } else { 0 };
+    let mut cap = 128u32;
+    loop {
+        let mut quads = vec![0u32; cap as usize * 4];
+        let mut scores = vec![0u32; seeds.len()];
+        let (mut n, mut status, mut best) = (0u32, 0u32, 0u32);
+        let st = unsafe {
+            ffi::agx_grow_board_tail(list.as_ptr(), list.len() as u32, std::ptr::null(), seed_rows.as_ptr(), seeds.len() as u32, spacing_ratio,
+                                     stop_score, flags, quads.as_mut_ptr(), cap, &mut n, &mut status, scores.as_mut_ptr(), &mut best)
+        };
+        assert_eq!(st, ffi::AGX_OK, "agx_grow_board_tail failed: {}", st);
+        match status as c_int {
+            ffi::AGX_BOARD_FOUND => {
+                let rows = quads[..n as usize * 4].chunks(4).map(|q| [q[0] as usize, q[1] as usize, q[2] as usize, q[3] as usize]).collect();
+                return Some((rows, scores, best as usize));
+            }
+            ffi::AGX_BOARD_CAPACITY => cap = n,
+            ffi::AGX_BOARD_NONE => return None,
+            _ => panic!("grow_board_tail: a saddle's x, y or theta is not finite, or a seed names no saddle of the list"),
+        }
+    }
+}
+
 /// reference src/detector.rs:42-72, `decode_positions`: the sample points of a quad (four corners), x outer and y inner, or
 /// `None` where a rounded corner lies outside the image.  The host form (no device is used).  A corner that is not finite is
 /// `None`.  Panics where the library refuses the arguments: `edge_bits` outside 1..=8, `border_bits` above 16, a margin that

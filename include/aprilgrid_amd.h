@@ -643,6 +643,69 @@ int agx_find_board(agx_detector *det, const agx_saddle *saddles, uint32_t n_sadd
 int agx_find_board_tail(const agx_saddle *saddles, uint32_t n_saddles, uint32_t *quads, uint32_t cap, uint32_t *n_quads,
                         uint32_t *status);
 
+/* ---- boards from the caller's seed quads ------------------------------------------------- */
+
+/* Board::new(refined, active_idxs, quad_idxs, spacing_ratio, tree) -- src/board.rs:26-48 -- with try_fix_missing (:52-112),
+ * all_tag_indexes and score: the `pub` items try_find_best_board itself is made of, for a caller who already knows one quad of
+ * the board (a row of an earlier frame's d_quads after agx_refine_points_enqueue, a quad predicted from a pose) and so needs
+ * neither init_quads' 50-NN nor a board per candidate quad -- and with the crate's spacing_ratio as an argument: detect's own
+ * search passes the literal 0.3 (:621; agx_params.tag_spacing_ratio is never read, as in the reference), which loses a board
+ * whose tags lie more than about one tag side apart.  The neighbour's corner is looked for at a + (b - a)*(1 + spacing_ratio),
+ * within sqrt(0.5)*|b - a| (:186-213). */
+enum { AGX_GROW_FIX_MISSING = 1 };  /* flags: run try_fix_missing (board.rs:52-112) on the chosen board, as try_find_best_board does (:633) */
+
+/* Per frame over saddle lists in DEVICE memory, stream-ordered on the detector's stream; returns without waiting.  d_saddles,
+ * saddle_stride_bytes, n_frames, saddles_per_frame, d_counts, d_frame_table and d_point_status are read exactly as
+ * agx_find_boards_enqueue reads them (at most one of d_counts and d_frame_table; an overflow bit or a listed saddle with a
+ * non-finite x, y or theta: AGX_BOARD_INPUT).
+ *   d_seed_quads   [n_frames][seeds_per_frame][4] uint32: slot numbers within the frame in init_quads' corner order (:577-581) --
+ *                  a row of agx_find_boards_enqueue's d_quads is one as it stands.  Frame f has min(d_seed_counts[f],
+ *                  seeds_per_frame) seeds, seeds_per_frame with d_seed_counts NULL.  A seed is NOT tested with is_valid_quad
+ *                  (Board::new does not either: its score is at least 1).  Every seed of the frame is looked at before any
+ *                  board is grown: one that names a slot at or beyond the frame's count, or a slot that is not listed, makes the
+ *                  frame AGX_BOARD_INPUT; no seed at all is AGX_BOARD_NONE.
+ *   spacing_ratio  finite with 1.0f + spacing_ratio > 0; at 0.3f the arithmetic is agx_find_boards_enqueue's bit for bit
+ *                  (1.0f + 0.3f in binary32).
+ *   stop_score     0: every seed is grown.  Else the seeds are taken in order until the best score so far is >= stop_score:
+ *                  the seeds behind that one read score 0 and are never chosen.  This is the CALLER'S rule per seed quad; the
+ *                  reference's own `>= 36` (:626) stops per seed SADDLE, after all of its candidate quads, and is not this.
+ *   flags          AGX_GROW_FIX_MISSING or 0.
+ * The board of seed i is Board::new(listed saddles, all-true mask, seed i, spacing_ratio, tree); d_seed_scores[f][i] (optional)
+ * is its score.  The chosen board is the first seed whose score is strictly above every earlier one (:622's `>`): d_best_seed[f]
+ * (optional).  Its quads -- after try_fix_missing under AGX_GROW_FIX_MISSING -- go out exactly as agx_find_boards_enqueue's:
+ * d_quads [n_frames][quads_per_frame][4] slot numbers within the frame, cells in insertion order, d_quad_points (optional),
+ * d_n_quads, d_status (AGX_BOARD_*; AGX_BOARD_CAPACITY: the true count and no row), so agx_decode_quads_enqueue and
+ * agx_collect_tags_enqueue follow unchanged.  d_seed_scores and d_best_seed are written for frames that end AGX_BOARD_FOUND or
+ * AGX_BOARD_CAPACITY only.  All arrays are caller-owned device memory, 4-byte aligned; d_quads, d_n_quads and d_status are
+ * required.
+ * The kernel hands a frame back as AGX_BOARD_PENDING where agx_find_boards_enqueue's does (more than 1024 listed saddles, a
+ * coordinate beyond 1e6, a theta outside [-180, 180], a board beyond the kernel's fixed sizes, an angle inside a guard band,
+ * option "tail_debug_band"; every frame with "device_tail" 0 or refused) until agx_grow_boards_fetch has run the host form.
+ * A further kind of batch on the handle: it replaces whatever is in flight without waiting, the other kinds' fetches of it are
+ * AGX_ERR_STATE, and a refused argument leaves the batch in flight where it is.
+ * AGX_ERR_ARG: agx_find_boards_enqueue's, NULL d_quads, d_n_quads, d_status or d_seed_quads, seeds_per_frame == 0, 2^27 or more
+ * seed rows in the batch, a spacing_ratio that is not finite or with 1.0f + spacing_ratio <= 0, an unknown flag. */
+int agx_grow_boards_enqueue(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames,
+                            uint32_t saddles_per_frame, const uint32_t *d_counts, const void *d_frame_table,
+                            const uint32_t *d_point_status,
+                            const uint32_t *d_seed_quads, uint32_t seeds_per_frame, const uint32_t *d_seed_counts,
+                            float spacing_ratio, uint32_t stop_score, int flags,
+                            uint32_t quads_per_frame, uint32_t *d_quads, float *d_quad_points, uint32_t *d_n_quads,
+                            uint32_t *d_status, uint32_t *d_seed_scores, uint32_t *d_best_seed);
+/* Wait for the batch of agx_grow_boards_enqueue and resolve every AGX_BOARD_PENDING frame: the host form (agx_grow_board_tail's
+ * code) runs on the detector's pool (n_threads host threads; 0: agx_host_parallelism()), and the frame's rows, count, status,
+ * seed scores and best seed are written to the device arrays on the detector's stream before the call returns.
+ * AGX_ERR_STATE: no such batch in flight. */
+int agx_grow_boards_fetch(agx_detector *det, int n_threads);
+/* The host form without a detector handle (no device needed, like agx_find_board_tail): one list, the same semantics.
+ * seed_quads [n_seeds][4] and quads [cap][4] are indices into `saddles`; point_status NULL or a word per saddle (0 = listed);
+ * seed_scores [n_seeds] and best_seed may be NULL.  *n_quads, *status as agx_find_board_tail's; seed_scores and *best_seed are
+ * written for AGX_BOARD_FOUND and AGX_BOARD_CAPACITY only.  AGX_ERR_ARG as the batch call's. */
+int agx_grow_board_tail(const agx_saddle *saddles, uint32_t n_saddles, const uint32_t *point_status,
+                        const uint32_t *seed_quads, uint32_t n_seeds, float spacing_ratio, uint32_t stop_score, int flags,
+                        uint32_t *quads, uint32_t cap, uint32_t *n_quads, uint32_t *status,
+                        uint32_t *seed_scores, uint32_t *best_seed);
+
 /* ---- blur and Hessian-response planes at any sigma ---------------------------------------- */
 
 /* image_util::gaussian_blur_f32(img, sigma) -- src/image_util.rs:110-206 -- and image_util::hessian_response(img) --
