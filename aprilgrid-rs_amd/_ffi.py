@@ -119,6 +119,11 @@ SYMBOLS = {
     "agx_find_boards_fetch": (C.c_int, [_P, _P, _P, _P, _P, C.c_int]),
     "agx_find_board": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "agx_find_board_tail": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "agx_init_quads_enqueue": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P, _P,
+                                         _P, _P, _P, _P]),
+    "agx_init_quads_fetch": (C.c_int, [_P, C.c_int]),
+    "agx_init_quads_tail": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_uint32), _P, _P, C.POINTER(C.c_uint32)]),
     "agx_grow_boards_enqueue": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P, C.c_float, C.c_uint32, C.c_int,
                                           C.c_uint32, _P, _P, _P, _P, _P, _P]),
     "agx_grow_boards_fetch": (C.c_int, [_P, C.c_int]),

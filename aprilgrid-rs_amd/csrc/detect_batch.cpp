@@ -1619,6 +1619,212 @@ int agx::grow_boards_fetch_impl(agx_detector *det, int n_threads)
     return rc;
 }
 
+// ---- agx_init_quads_enqueue / _fetch: init_quads (src/detector.rs:543-586) of caller-given seed saddles over the same lists ------
+// k_init_quads on the detector's stream, one workgroup per frame; everything in the caller's device arrays.  The list arguments
+// are agx_find_boards_enqueue's and are refused in its words.
+int agx::init_quads_enqueue_impl(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
+                                 const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status, const uint32_t *d_seed_saddles,
+                                 uint32_t seeds_per_frame, const uint32_t *d_seed_counts, uint32_t n_nearest, uint32_t quads_per_frame,
+                                 uint32_t *d_quads, float *d_quad_points, uint32_t *d_n_quads, uint32_t *d_status, uint32_t *d_seed_quad_counts,
+                                 uint32_t *d_seeds_out, uint32_t *d_n_seeds_out)
+{
+    if (!det) return AGX_ERR_ARG;
+    if (!d_saddles || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null saddles or n_frames <= 0");
+    if (saddle_stride_bytes < 20 || (saddle_stride_bytes & 3) || saddle_stride_bytes > 0x7fffffffu)
+        return fail(det, AGX_ERR_ARG, "saddle_stride_bytes must be a multiple of 4 and at least 20");
+    if (!saddles_per_frame || !quads_per_frame || !seeds_per_frame)
+        return fail(det, AGX_ERR_ARG, "saddles_per_frame, seeds_per_frame and quads_per_frame must be > 0");
+    if (d_counts && d_frame_table) return fail(det, AGX_ERR_ARG, "d_counts and d_frame_table: at most one of them");
+    if (!d_quads || !d_n_quads || !d_status) return fail(det, AGX_ERR_ARG, "d_quads, d_n_quads and d_status are required");
+    if (d_seed_counts && !d_seed_saddles) return fail(det, AGX_ERR_ARG, "d_seed_counts without d_seed_saddles");
+    if (n_nearest < 2 || n_nearest > 64) return fail(det, AGX_ERR_ARG, "n_nearest must be 2 .. 64");
+    if (((uintptr_t)d_saddles | (uintptr_t)d_counts | (uintptr_t)d_frame_table | (uintptr_t)d_point_status | (uintptr_t)d_quads |
+         (uintptr_t)d_quad_points | (uintptr_t)d_n_quads | (uintptr_t)d_status | (uintptr_t)d_seed_saddles | (uintptr_t)d_seed_counts |
+         (uintptr_t)d_seed_quad_counts | (uintptr_t)d_seeds_out | (uintptr_t)d_n_seeds_out) & 3)
+        return fail(det, AGX_ERR_ARG, "saddles, counts, frame table, point statuses, seeds and the results must be 4-byte aligned");
+    if (n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
+    if ((size_t)n_frames * quads_per_frame >= ((size_t)1 << 27)) return fail(det, AGX_ERR_ARG, "at most 2^27 - 1 quad rows per batch");
+    if ((size_t)n_frames * seeds_per_frame >= ((size_t)1 << 27)) return fail(det, AGX_ERR_ARG, "at most 2^27 - 1 seed rows per batch");
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);
+    const bool host_only = device_tail_mode(det) == 0;
+    if (!host_only && tail_prepare(det)) return fail(det, AGX_ERR_HIP, "the device tail's set-up (code list, kernel attributes)");
+    InitQuadsArgs q{};
+    q.saddles = static_cast<const uint8_t *>(d_saddles);
+    q.stride = (uint32_t)saddle_stride_bytes;
+    q.n_frames = n_frames;
+    q.saddles_per_frame = saddles_per_frame;
+    q.counts = d_counts;
+    q.frame_table = static_cast<const uint32_t *>(d_frame_table);
+    q.point_status = d_point_status;
+    q.quads_per_frame = quads_per_frame;
+    q.quads = d_quads;
+    q.quad_points = d_quad_points;
+    q.n_quads = d_n_quads;
+    q.status = d_status;
+    q.debug_band = (float)det->tail_debug_band_mdeg * 1e-3f;
+    q.host_only = host_only ? 1 : 0;
+    q.seed_saddles = d_seed_saddles;
+    q.seeds_per_frame = seeds_per_frame;
+    q.seed_counts = d_seed_counts;
+    q.n_nearest = n_nearest;
+    q.seed_quad_counts = d_seed_quad_counts;
+    q.seeds_out = d_seeds_out;
+    q.n_seeds_out = d_n_seeds_out;
+    const hipError_t e = (hipError_t)launch_init_quads(q, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_init_quads: ") + hipGetErrorString(e));
+    det->batch = BATCH_INIT;
+    InitPending &p = det->init;
+    p.results = RESULTS_CALLER;
+    p.n_frames = n_frames;
+    p.saddles_per_frame = saddles_per_frame;
+    p.quads_per_frame = quads_per_frame;
+    p.stride = saddle_stride_bytes;
+    p.d_saddles = q.saddles;
+    p.d_counts = d_counts;
+    p.d_frame_table = q.frame_table;
+    p.d_point_status = d_point_status;
+    p.d_quads = d_quads;
+    p.d_n_quads = d_n_quads;
+    p.d_status = d_status;
+    p.d_quad_points = d_quad_points;
+    p.d_seed_saddles = d_seed_saddles;
+    p.d_seed_counts = d_seed_counts;
+    p.seeds_per_frame = seeds_per_frame;
+    p.n_nearest = n_nearest;
+    p.d_seed_quad_counts = d_seed_quad_counts;
+    p.d_seeds_out = d_seeds_out;
+    p.d_n_seeds_out = d_n_seeds_out;
+    return AGX_OK;
+}
+
+// The handed-back frames as in agx_grow_boards_fetch: their slots, status words and seeds down, the host form on the pool, the
+// answers up -- rows, count and status, and (unless the frame is AGX_BOARD_INPUT) the per-seed counts and the seeds taken.
+int agx::init_quads_fetch_impl(agx_detector *det, int n_threads)
+{
+    if (!det) return AGX_ERR_ARG;
+    if (const int other = refuse_other_batch(det, BATCH_INIT)) return other;
+    const InitPending b = det->init;
+    HIP_TRY(det, hipSetDevice(det->device));
+    det->batch = BATCH_NONE;  // resolved by this call, whatever it returns
+    det->last_init_frames = b.n_frames;
+    det->last_init_handed_back = 0;
+    if (n_threads <= 0) n_threads = agx_host_parallelism();
+    hipStream_t stream = det->stream;
+    const size_t n = (size_t)b.n_frames, qpf = b.quads_per_frame, spf = b.seeds_per_frame;
+    int rc = AGX_OK;
+    try {
+        std::vector<uint32_t> h_status(n), h_count(n, 0u), h_seeds(n, 0u);
+        if (hipMemcpyAsync(h_status.data(), b.d_status, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipStreamSynchronize(stream) != hipSuccess)
+            return fail(det, AGX_ERR_HIP, "agx_init_quads_fetch: copy / wait");
+        std::vector<int> pending;
+        for (size_t f = 0; f < n; ++f)
+            if (h_status[f] == AGX_BOARD_PENDING) pending.push_back((int)f);
+        det->last_init_handed_back = (int)pending.size();
+        if (pending.empty()) return AGX_OK;
+        WorkerPool *pool = worker_pool(det, n_threads);
+        if (!pool) return fail(det, AGX_ERR_ARG, "n_threads");
+        std::vector<std::vector<uint8_t>> slots(pending.size());
+        std::vector<std::vector<uint32_t>> words(pending.size()), rows(pending.size()), seeds(pending.size()), counts(pending.size()), taken(pending.size());
+        std::vector<std::vector<float>> pts(pending.size());
+        std::vector<uint32_t> own(b.d_frame_table ? 4 * n : (b.d_counts ? n : 0)), seed_counts(b.d_seed_counts ? n : 0);
+        bool ok = true;
+        if (!own.empty())
+            ok = hipMemcpyAsync(own.data(), b.d_frame_table ? b.d_frame_table : b.d_counts, own.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
+        if (ok && !seed_counts.empty())
+            ok = hipMemcpyAsync(seed_counts.data(), b.d_seed_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
+        if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, "agx_init_quads_fetch: the frames' counts");
+        std::vector<char> no_list(pending.size(), 0);
+        for (size_t k = 0; k < pending.size() && ok; ++k) {
+            const size_t f = (size_t)pending[k];
+            size_t first = f * b.saddles_per_frame, count = b.saddles_per_frame;
+            if (b.d_frame_table) {
+                count = own[4 * f];
+                first = own[4 * f + 1];
+                if (own[4 * f + 2] & 7u) {  // an overflow bit: there is no list
+                    no_list[k] = 1;
+                    continue;
+                }
+            } else if (b.d_counts) {
+                count = std::min<size_t>(own[f], b.saddles_per_frame);
+            }
+            if (b.d_seed_saddles) {
+                const size_t n_seeds = b.d_seed_counts ? std::min<size_t>(seed_counts[f], spf) : spf;
+                seeds[k].resize(n_seeds);
+                if (n_seeds) ok = hipMemcpyAsync(seeds[k].data(), b.d_seed_saddles + f * spf, n_seeds * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
+            }
+            if (!count) continue;
+            slots[k].resize((count - 1) * b.stride + sizeof(agx_saddle));
+            ok = ok && hipMemcpyAsync(slots[k].data(), b.d_saddles + first * b.stride, slots[k].size(), hipMemcpyDeviceToHost, stream) == hipSuccess;
+            if (ok && b.d_point_status) {
+                words[k].resize(count);
+                ok = hipMemcpyAsync(words[k].data(), b.d_point_status + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
+            }
+        }
+        if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, "agx_init_quads_fetch: the handed-back frames' lists");
+        std::atomic<bool> nomem{false};
+        const bool want_pts = b.d_quad_points != nullptr, caller_seeds = b.d_seed_saddles != nullptr;
+        try {
+        for (size_t k = 0; k < pending.size(); ++k) {
+            const size_t f = (size_t)pending[k];
+            if (no_list[k]) {
+                h_status[f] = AGX_BOARD_INPUT;
+                continue;
+            }
+            const size_t stride = b.stride;
+            pool->submit([&, k, f, stride, want_pts, caller_seeds] {
+                try {
+                    const uint32_t count = slots[k].empty() ? 0u : (uint32_t)((slots[k].size() - sizeof(agx_saddle)) / stride + 1);
+                    static const uint32_t no_seed = 0;  // (a non-null pointer for a frame without seeds: null asks for the reference's)
+                    const uint32_t *sd = caller_seeds ? (seeds[k].empty() ? &no_seed : seeds[k].data()) : nullptr;
+                    const int st = init_quads_in_slots(slots[k].data(), stride, count, words[k].empty() ? nullptr : words[k].data(), sd,
+                                                       (uint32_t)seeds[k].size(), b.seeds_per_frame, b.n_nearest, rows[k], counts[k], taken[k]);
+                    const uint32_t nq = (uint32_t)(rows[k].size() / 4);
+                    h_status[f] = (uint32_t)st;
+                    if (st == AGX_BOARD_FOUND && nq > qpf) {
+                        h_status[f] = AGX_BOARD_CAPACITY;
+                        rows[k].clear();
+                    }
+                    h_count[f] = st == AGX_BOARD_FOUND ? nq : 0u;
+                    h_seeds[f] = (uint32_t)taken[k].size();
+                    if (want_pts)
+                        for (uint32_t s : rows[k]) {
+                            float xy[2];
+                            std::memcpy(xy, slots[k].data() + (size_t)s * stride, sizeof xy);
+                            pts[k].push_back(xy[0]);
+                            pts[k].push_back(xy[1]);
+                        }
+                } catch (...) {
+                    nomem.store(true);
+                }
+            });
+        }
+        } catch (...) {  // a task could not be queued: the ones that were read this call's vectors
+            (void)pool->wait();
+            throw;
+        }
+        if (!pool->wait() || nomem.load()) return fail(det, AGX_ERR_NOMEM, "agx_init_quads_fetch: the host form");
+        for (size_t k = 0; k < pending.size() && ok; ++k) {
+            const size_t f = (size_t)pending[k];
+            if (!rows[k].empty())
+                ok = hipMemcpyAsync(b.d_quads + f * qpf * 4, rows[k].data(), rows[k].size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess &&
+                     (!want_pts || hipMemcpyAsync(b.d_quad_points + f * qpf * 8, pts[k].data(), pts[k].size() * sizeof(float), hipMemcpyHostToDevice, stream) == hipSuccess);
+            if (ok && b.d_seed_quad_counts && !counts[k].empty())
+                ok = hipMemcpyAsync(b.d_seed_quad_counts + f * spf, counts[k].data(), counts[k].size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess;
+            if (ok && b.d_seeds_out && !taken[k].empty())
+                ok = hipMemcpyAsync(b.d_seeds_out + f * spf, taken[k].data(), taken[k].size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess;
+            if (ok && b.d_n_seeds_out) ok = hipMemcpyAsync(b.d_n_seeds_out + f, &h_seeds[f], sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess;
+            ok = ok && hipMemcpyAsync(b.d_n_quads + f, &h_count[f], sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess &&
+                 hipMemcpyAsync(b.d_status + f, &h_status[f], sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess;
+        }
+        if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, "agx_init_quads_fetch: the host form's answers to the device");
+    } catch (...) {
+        rc = fail(det, AGX_ERR_NOMEM, "agx_init_quads_fetch: host memory");
+    }
+    return rc;
+}
+
 // The host tail of the frames `back` marks (1 handed back, 2 handed back as uncertain; without the device tail: every frame) of
 // the batch `b` in flight on `det`, on the pool: from the chain's compact saddle lists and those frames' u8 luma, copied down
 // from the device a group at a time.  cnt / st [n] get those frames' counts and statuses (a list of the chain overflowed: 0,

@@ -38,7 +38,8 @@ static const struct { const char *enqueue, *fetch; } kBatchPair[BATCH_KINDS] = {
     {"agx_decode_quads_enqueue", "agx_decode_quads_fetch"},
     {"agx_find_boards_enqueue", "agx_find_boards_fetch"},
     {"agx_clusters_enqueue", "agx_clusters_fetch"},
-    {"agx_grow_boards_enqueue", "agx_grow_boards_fetch"}};
+    {"agx_grow_boards_enqueue", "agx_grow_boards_fetch"},
+    {"agx_init_quads_enqueue", "agx_init_quads_fetch"}};
 
 int agx::refuse_other_batch(agx_detector *det, int wanted)
 {
@@ -976,6 +977,8 @@ int agx_detector_get_option(const agx_detector *det, const char *name, int *valu
     else if (!std::strcmp(name, "last_find_boards_handed_back")) *value = det->last_find_handed_back;
     else if (!std::strcmp(name, "last_grow_boards_frames")) *value = det->last_grow_frames;  // (of the last agx_grow_boards_fetch)
     else if (!std::strcmp(name, "last_grow_boards_handed_back")) *value = det->last_grow_handed_back;
+    else if (!std::strcmp(name, "last_init_quads_frames")) *value = det->last_init_frames;  // (of the last agx_init_quads_fetch)
+    else if (!std::strcmp(name, "last_init_quads_handed_back")) *value = det->last_init_handed_back;
     else if (!std::strcmp(name, "last_device_tail_frames")) *value = det->last_tail_frames;
     else if (!std::strcmp(name, "last_device_tail_fallbacks")) *value = det->last_tail_fallbacks;
     else if (!std::strcmp(name, "last_device_tail_uncertain")) *value = det->last_tail_uncertain;  // (of them: an angle inside its guard band)
@@ -1671,6 +1674,49 @@ int agx_find_board_tail(const agx_saddle *saddles, uint32_t n_saddles, uint32_t 
     if (st == AGX_BOARD_FOUND && n) std::memcpy(quads, rows.data(), rows.size() * sizeof(uint32_t));
     *n_quads = st == AGX_BOARD_FOUND || st == AGX_BOARD_CAPACITY ? n : 0u;
     *status = st;
+    return AGX_OK;
+    });
+}
+
+// ---- candidate quads of caller-given seed saddles (src/detector.rs:543-586; csrc/detect_batch.cpp, tail_kernels.hip: k_init_quads) ----
+int agx_init_quads_enqueue(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
+                           const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status, const uint32_t *d_seed_saddles,
+                           uint32_t seeds_per_frame, const uint32_t *d_seed_counts, uint32_t n_nearest, uint32_t quads_per_frame,
+                           uint32_t *d_quads, float *d_quad_points, uint32_t *d_n_quads, uint32_t *d_status, uint32_t *d_seed_quad_counts,
+                           uint32_t *d_seeds_out, uint32_t *d_n_seeds_out)
+{
+    return agx_guard(det, [&]() -> int {
+    return init_quads_enqueue_impl(det, d_saddles, saddle_stride_bytes, n_frames, saddles_per_frame, d_counts, d_frame_table, d_point_status,
+                                   d_seed_saddles, seeds_per_frame, d_seed_counts, n_nearest, quads_per_frame, d_quads, d_quad_points,
+                                   d_n_quads, d_status, d_seed_quad_counts, d_seeds_out, d_n_seeds_out);
+    });
+}
+
+int agx_init_quads_fetch(agx_detector *det, int n_threads)
+{
+    return agx_guard(det, [&]() -> int { return init_quads_fetch_impl(det, n_threads); });
+}
+
+int agx_init_quads_tail(const agx_saddle *saddles, uint32_t n_saddles, const uint32_t *point_status, const uint32_t *seed_saddles,
+                        uint32_t n_seeds, uint32_t max_seeds, uint32_t n_nearest, uint32_t *quads, uint32_t cap, uint32_t *n_quads,
+                        uint32_t *status, uint32_t *seed_quad_counts, uint32_t *seeds_out, uint32_t *n_seeds_out)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (!n_quads || !status || (n_saddles && !saddles) || (cap && !quads) || (n_seeds && !seed_saddles)) return AGX_ERR_ARG;
+    if (!max_seeds || n_nearest < 2 || n_nearest > 64) return AGX_ERR_ARG;
+    std::vector<uint32_t> rows, counts, seeds;
+    uint32_t st = (uint32_t)init_quads_in_slots(saddles, sizeof(agx_saddle), n_saddles, point_status, seed_saddles, n_seeds, max_seeds, n_nearest,
+                                                rows, counts, seeds);
+    const uint32_t n = (uint32_t)(rows.size() / 4);
+    if (st == AGX_BOARD_FOUND && n > cap) st = AGX_BOARD_CAPACITY;
+    if (st == AGX_BOARD_FOUND && n) std::memcpy(quads, rows.data(), rows.size() * sizeof(uint32_t));
+    *n_quads = st == AGX_BOARD_FOUND || st == AGX_BOARD_CAPACITY ? n : 0u;
+    *status = st;
+    if (n_seeds_out) *n_seeds_out = (uint32_t)seeds.size();
+    if (st != AGX_BOARD_INPUT) {
+        if (seed_quad_counts) std::memcpy(seed_quad_counts, counts.data(), counts.size() * sizeof(uint32_t));
+        if (seeds_out && !seeds.empty()) std::memcpy(seeds_out, seeds.data(), seeds.size() * sizeof(uint32_t));
+    }
     return AGX_OK;
     });
 }

@@ -58,6 +58,7 @@ enum BatchKind {
     BATCH_FIND,     // FindPending
     BATCH_CLUSTERS, // ClustersPending; the chain's kernels ran on the workspace, but nothing of the chain is there to be fetched
     BATCH_GROW,     // GrowPending
+    BATCH_INIT,     // InitPending
     BATCH_KINDS
 };
 // where a kind's results are: the fetch copies them out of the handle's side buffers / they are in the caller's device arrays
@@ -109,6 +110,13 @@ struct GrowPending : FindPending {
     float spacing_ratio = 0.3f;
     int flags = 0;
     uint32_t *d_seed_scores = nullptr, *d_best_seed = nullptr;
+};
+
+// FindPending's list and result arrays (always RESULTS_CALLER) and the seeds
+struct InitPending : FindPending {
+    const uint32_t *d_seed_saddles = nullptr, *d_seed_counts = nullptr;
+    uint32_t seeds_per_frame = 0, n_nearest = 50;
+    uint32_t *d_seed_quad_counts = nullptr, *d_seeds_out = nullptr, *d_n_seeds_out = nullptr;
 };
 
 struct ClustersPending {
@@ -304,6 +312,8 @@ struct agx_detector {
     agx::ClustersPending clusters;      // BATCH_CLUSTERS: what agx_clusters_fetch needs of it
     agx::GrowPending grow;              // BATCH_GROW: what agx_grow_boards_fetch needs of it
     int last_grow_frames = 0, last_grow_handed_back = 0;  // of the last agx_grow_boards_fetch
+    agx::InitPending init;              // BATCH_INIT: what agx_init_quads_fetch needs of it
+    int last_init_frames = 0, last_init_handed_back = 0;  // of the last agx_init_quads_fetch
     int last_extra_us[agx::XT_COUNT]{};  // harvest_events: the XT_* launches' last times (profiling level 2)
 
     std::string last_error;
@@ -381,6 +391,13 @@ int grow_boards_enqueue_impl(agx_detector *det, const void *d_saddles, size_t sa
                              uint32_t quads_per_frame, uint32_t *d_quads, float *d_quad_points, uint32_t *d_n_quads, uint32_t *d_status,
                              uint32_t *d_seed_scores, uint32_t *d_best_seed);
 int grow_boards_fetch_impl(agx_detector *det, int n_threads);
+// init_quads of caller-given seed saddles over the same lists (detect_batch.cpp: k_init_quads, the fetch's host form)
+int init_quads_enqueue_impl(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
+                            const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status, const uint32_t *d_seed_saddles,
+                            uint32_t seeds_per_frame, const uint32_t *d_seed_counts, uint32_t n_nearest, uint32_t quads_per_frame,
+                            uint32_t *d_quads, float *d_quad_points, uint32_t *d_n_quads, uint32_t *d_status, uint32_t *d_seed_quad_counts,
+                            uint32_t *d_seeds_out, uint32_t *d_n_seeds_out);
+int init_quads_fetch_impl(agx_detector *det, int n_threads);
 int group_detect_fetch_impl(agx_detector *det, const char *back, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads);
 // What group.cpp calls for rank r's share of a detect batch (detector.cpp: the entry points' argument checks and guard around
 // the two functions above).  After the enqueue det->detect.device_tail says whether the pack kernel ran.

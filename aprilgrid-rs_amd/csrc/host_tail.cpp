@@ -879,17 +879,19 @@ private:
 // Every entry is computed by the reference's expression on the reference's operands, so each test
 // sees the same floats; only the order of the (side-effect free) tests differs, and three of the
 // four atan2 per combination become table look-ups.  Quads are emitted in the reference's order.
-void init_quads(const std::vector<agx_saddle> &refined, SaddleIndex &index, int s0_idx, std::vector<Quad> &out)
+// n_nearest: :550's 50 (agx_init_quads_tail passes the caller's, 2 .. kMaxNearest; the arrays below are sized for that).
+constexpr int kMaxNearest = 64;
+void init_quads(const std::vector<agx_saddle> &refined, SaddleIndex &index, int s0_idx, std::vector<Quad> &out, int n_nearest = 50)
 {
     out.clear();
     const agx_saddle &s0 = refined[s0_idx];
-    SaddleIndex::Hit near[50];
+    SaddleIndex::Hit near[kMaxNearest];
     int m;
     {
         AGX_TAIL_TIME(6);
-        m = index.nearest(s0.x, s0.y, 50, near);
+        m = index.nearest(s0.x, s0.y, n_nearest, near);
     }
-    int same[50], diff[50];
+    int same[kMaxNearest], diff[kMaxNearest];
     int ns = 0, nd = 0;
     for (int i = 1; i < m; ++i) {
         const int idx = near[i].idx;
@@ -899,7 +901,7 @@ void init_quads(const std::vector<agx_saddle> &refined, SaddleIndex &index, int 
     }
     if (!ns || nd < 2) return;
     // (d): v0d = d - s0 (v01 / v03), v30 = s0 - d;  (d0, d1): part 0, a3 on demand
-    float v0x[50], v0y[50], v30x[50], v30y[50], dpx[50], dpy[50];  // (dpx / dpy: the d saddles' coordinates side by side for the loops over s1)
+    float v0x[kMaxNearest], v0y[kMaxNearest], v30x[kMaxNearest], v30y[kMaxNearest], dpx[kMaxNearest], dpy[kMaxNearest];  // (dpx / dpy: the d saddles' coordinates side by side for the loops over s1)
     for (int d = 0; d < nd; ++d) {
         const agx_saddle &p = refined[diff[d]];
         dpx[d] = p.x; dpy[d] = p.y;
@@ -909,8 +911,8 @@ void init_quads(const std::vector<agx_saddle> &refined, SaddleIndex &index, int 
     // the (d0, d1) combinations that pass part 0 as one bit row per a (bit b > a set: the pair is a candidate), and their
     // running number in the reference's order (a ascending, then b).  The loops over s1
     // below visit only the pairs whose two saddles also lie on s1's side of s0 (a second bit row per s1), in that same order.
-    uint64_t p0[50];
-    static thread_local uint16_t pair_no[50 * 50];         // the running number of pair (a, b), written where the bit is set
+    uint64_t p0[kMaxNearest];
+    static thread_local uint16_t pair_no[kMaxNearest * kMaxNearest];         // the running number of pair (a, b), written where the bit is set
     static thread_local std::vector<LazyAngle> a3_store;  // a3 = angle(v30, v01) per listed pair, on demand ...
     static thread_local std::vector<uint64_t> a3_set;      // ... one bit per listed pair: evaluated yet?
     int n_pairs = 0;
@@ -919,7 +921,7 @@ void init_quads(const std::vector<agx_saddle> &refined, SaddleIndex &index, int 
         for (int b = a + 1; b < nd; ++b)
             if (quad_part0(refined[diff[a]], refined[diff[b]])) {
                 row |= 1ull << b;
-                pair_no[a * 50 + b] = (uint16_t)n_pairs++;
+                pair_no[a * kMaxNearest + b] = (uint16_t)n_pairs++;
             }
         p0[a] = row;
     }
@@ -934,8 +936,8 @@ void init_quads(const std::vector<agx_saddle> &refined, SaddleIndex &index, int 
         const agx_saddle &s1 = refined[s1_idx];
         if (!quad_part1_dir(s0, s1, cos0, sin0)) continue;
         const float v02x = s1.x - s0.x, v02y = s1.y - s0.y;
-        float cA[50], cB[50], c01[50], v12x[50], v12y[50], v23x[50], v23y[50];
-        LazyAngle a0v[50], a2v[50];
+        float cA[kMaxNearest], cB[kMaxNearest], c01[kMaxNearest], v12x[kMaxNearest], v12y[kMaxNearest], v23x[kMaxNearest], v23y[kMaxNearest];
+        LazyAngle a0v[kMaxNearest], a2v[kMaxNearest];
         uint64_t a0_set = 0, a2_set = 0;  // which of them have been evaluated for this s1
         uint64_t ok = 0;  // bit d: dot(v0d, v02) >= 0 (saddle.rs:62-64), needed of both d0 and d1
         // the winding test cA[a] * cB[b] < 0 (saddle.rs:44-46) as bit rows: with both factors at least 2^-60 in magnitude the
@@ -943,7 +945,7 @@ void init_quads(const std::vector<agx_saddle> &refined, SaddleIndex &index, int 
         // signs decide it; smaller factors (never seen on image coordinates) keep the explicit product below
         uint64_t b_pos = 0, b_neg = 0;
         constexpr float kTiny = 8.67361737988403547e-19f;  // 2^-60
-        float dt[50];
+        float dt[kMaxNearest];
         const float s1x = s1.x, s1y = s1.y;
         for (int d = 0; d < nd; ++d) {  // (plain arrays in, plain arrays out: the compiler vectorises this loop)
             cA[d] = v0x[d] * v02y - v0y[d] * v02x;        // cross(v0d, v02): c0 with d as d0 (also the winding test)
@@ -976,7 +978,7 @@ void init_quads(const std::vector<agx_saddle> &refined, SaddleIndex &index, int 
                     a2_set |= 1ull << b;
                 }
                 if (angles_differ_by_more_than(a0v[a], a2v[b], 10.0f)) continue;
-                const int pi = pair_no[a * 50 + b];
+                const int pi = pair_no[a * kMaxNearest + b];
                 if (!(a3_set[(size_t)pi >> 6] >> (pi & 63) & 1ull)) {
                     a3v[pi].set(v30x[b], v30y[b], v0x[a], v0y[a]);
                     a3_set[(size_t)pi >> 6] |= 1ull << (pi & 63);
@@ -1089,20 +1091,10 @@ TailScratch &tail_scratch()
     static thread_local TailScratch s;
     return s;
 }
-}  // namespace
-
-bool try_find_best_board(const std::vector<agx_saddle> &refined, std::vector<Quad> &quads, TailWorkers *workers)
+// try_find_best_board's seeds (:601-612): the most populated round(theta) bin (ties -> smallest angle; the reference's
+// HashMap order makes its own tie-break arbitrary), in list order -- the loop pops them from the back
+void reference_seeds(const std::vector<agx_saddle> &refined, TailScratch &sc, std::vector<int> &seeds)
 {
-    quads.clear();
-    if (refined.empty()) return false;
-    TailScratch &sc = tail_scratch();
-    {
-        AGX_TAIL_TIME(0);
-        sc.index.reset(refined);
-    }
-    SaddleIndex &index = sc.index;
-    // seeds: the most populated round(theta) bin (ties -> smallest angle; the reference's
-    // HashMap order makes its own tie-break arbitrary), popped from the back
     int best_angle = 0, best_len = -1;
     bool small_angles = true;  // theta is half an atan2 in degrees: (-90, 90]; anything else (a caller's own list) takes the map
     for (const agx_saddle &s : refined)
@@ -1127,11 +1119,24 @@ bool try_find_best_board(const std::vector<agx_saddle> &refined, std::vector<Qua
                 best_angle = kv.first;
             }
     }
-    std::vector<int> &seeds = sc.seeds;
     seeds.clear();
     for (size_t i = 0; i < refined.size(); ++i)
         if ((int)round_half_away(refined[i].theta) == best_angle) seeds.push_back((int)i);
+}
+}  // namespace
 
+bool try_find_best_board(const std::vector<agx_saddle> &refined, std::vector<Quad> &quads, TailWorkers *workers)
+{
+    quads.clear();
+    if (refined.empty()) return false;
+    TailScratch &sc = tail_scratch();
+    {
+        AGX_TAIL_TIME(0);
+        sc.index.reset(refined);
+    }
+    SaddleIndex &index = sc.index;
+    std::vector<int> &seeds = sc.seeds;
+    reference_seeds(refined, sc, seeds);
     if (workers && workers->size() > 1 && seeds.size() > 1) return find_best_board_parallel(refined, seeds, index, quads, *workers);
 
     unsigned best_score = 0;
@@ -1405,6 +1410,60 @@ int grow_boards_in_slots(const void *slots, size_t stride, uint32_t n_slots, con
     for (const Quad &q : found)
         for (int i = 0; i < 4; ++i) quads.push_back(slot_of[(size_t)q[i]]);
     return st;
+}
+
+int init_quads_in_slots(const void *slots, size_t stride, uint32_t n_slots, const uint32_t *point_status, const uint32_t *seed_saddles,
+                        uint32_t n_seeds, uint32_t max_seeds, uint32_t n_nearest, std::vector<uint32_t> &quads,
+                        std::vector<uint32_t> &seed_quad_counts, std::vector<uint32_t> &seeds_out)
+{
+    quads.clear();
+    seed_quad_counts.clear();
+    seeds_out.clear();
+    std::vector<agx_saddle> list;
+    std::vector<uint32_t> slot_of;
+    std::vector<int> pos_of(n_slots, -1);
+    for (uint32_t i = 0; i < n_slots; ++i) {
+        if (point_status && point_status[i] != 0u) continue;  // (AGX_POINT_REFINED is 0)
+        agx_saddle s;
+        std::memcpy(&s, static_cast<const char *>(slots) + (size_t)i * stride, sizeof s);
+        if (!std::isfinite(s.x) || !std::isfinite(s.y) || !std::isfinite(s.theta)) return AGX_BOARD_INPUT;
+        s.k = 0.0f;  // (never read: whatever the slot holds there)
+        s.phi = 0.0f;
+        pos_of[i] = (int)list.size();
+        list.push_back(s);
+        slot_of.push_back(i);
+    }
+    std::vector<int> seeds;  // positions in the list, in the order they are taken
+    if (seed_saddles) {
+        const uint32_t take = std::min(n_seeds, max_seeds);
+        for (uint32_t k = 0; k < take; ++k) {
+            const uint32_t s = seed_saddles[k];
+            if (s >= n_slots || pos_of[s] < 0) return AGX_BOARD_INPUT;  // beyond the frame's count, or not listed
+            seeds.push_back(pos_of[s]);
+        }
+    }
+    seed_quad_counts.assign(max_seeds, 0u);
+    if (list.empty()) return AGX_BOARD_NONE;
+    TailScratch &sc = tail_scratch();
+    if (!seed_saddles) {  // :601-616: the fullest bin's saddles from the back, at most max_seeds of them
+        std::vector<int> &bin = sc.seeds;
+        reference_seeds(list, sc, bin);
+        while (!bin.empty() && seeds.size() < (size_t)max_seeds) {
+            seeds.push_back(bin.back());
+            bin.pop_back();
+        }
+    }
+    if (seeds.empty()) return AGX_BOARD_NONE;
+    sc.index.reset(list);
+    std::vector<Quad> &cand = sc.cand;
+    for (size_t k = 0; k < seeds.size(); ++k) {
+        init_quads(list, sc.index, seeds[k], cand, (int)n_nearest);
+        seed_quad_counts[k] = (uint32_t)cand.size();
+        seeds_out.push_back(slot_of[(size_t)seeds[k]]);
+        for (const Quad &q : cand)
+            for (int i = 0; i < 4; ++i) quads.push_back(slot_of[(size_t)q[i]]);
+    }
+    return quads.empty() ? AGX_BOARD_NONE : AGX_BOARD_FOUND;
 }
 
 namespace {

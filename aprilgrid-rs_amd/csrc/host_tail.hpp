@@ -70,6 +70,15 @@ int grow_boards(const std::vector<agx_saddle> &listed, const std::vector<Quad> &
 int grow_boards_in_slots(const void *slots, size_t stride, uint32_t n_slots, const uint32_t *point_status, const uint32_t *seed_quads,
                          uint32_t n_seeds, float spacing_ratio, uint32_t stop_score, int flags, std::vector<uint32_t> &quads,
                          std::vector<uint32_t> &seed_scores, uint32_t &best_seed);
+// The host form of agx_init_quads_enqueue / agx_init_quads_tail over the slots of one frame, as find_board_in_slots: init_quads
+// (detector.rs:543-586) with n_nearest (2 .. 64) in place of :550's 50 for the first min(n_seeds, max_seeds) of seed_saddles (SLOT
+// numbers) or, with seed_saddles null, for try_find_best_board's own seeds (:601-616), the first max_seeds in pop order.  quads:
+// SLOT numbers, four per quad, seed after seed in init_quads' order; seed_quad_counts [max_seeds] (0 behind the seeds taken) and
+// seeds_out (the seeds taken) are filled unless the answer is AGX_BOARD_INPUT (as grow_boards_in_slots'; every seed is looked at
+// first).  AGX_BOARD_NONE (an empty list, no seed, no quad) or AGX_BOARD_FOUND else.
+int init_quads_in_slots(const void *slots, size_t stride, uint32_t n_slots, const uint32_t *point_status, const uint32_t *seed_saddles,
+                        uint32_t n_seeds, uint32_t max_seeds, uint32_t n_nearest, std::vector<uint32_t> &quads,
+                        std::vector<uint32_t> &seed_quad_counts, std::vector<uint32_t> &seeds_out);
 
 // image_util.rs:39-70 (h = 2x3 affine, row-major)
 void tag_affine(const float quad_xy[8], int side_bits, float margin, float h[6]);

@@ -123,6 +123,20 @@ struct GrowBoardsArgs : FindBoardsArgs {
 };
 // as launch_find_boards; n_frames * seeds_per_frame < 2^27; hipError_t
 int launch_grow_boards(const GrowBoardsArgs &b, void *stream);
+// k_init_quads (agx_init_quads_enqueue): per frame init_quads (detector.rs:543-586) of caller-given seed saddles -- or of
+// try_find_best_board's own seeds (:601-616) -- over the same lists, the candidate quads of seed i behind those of seed i - 1.
+// The list and quads / quad_points / n_quads / status are FindBoardsArgs'; all pointers are device pointers.
+struct InitQuadsArgs : FindBoardsArgs {
+    const uint32_t *seed_saddles;  // [n_frames][seeds_per_frame]: slot numbers within the frame, or null: the reference's seeds in pop order
+    uint32_t seeds_per_frame;      // > 0; with seed_saddles null: at most this many of the reference's seeds
+    const uint32_t *seed_counts;   // [n_frames]: frame f has min(seed_counts[f], seeds_per_frame) seeds, or null: seeds_per_frame
+    uint32_t n_nearest;            // 2 .. 64: :550's 50
+    uint32_t *seed_quad_counts;    // [n_frames][seeds_per_frame] or null: the quads of each seed (0 behind the frame's seeds); FOUND / NONE / CAPACITY frames
+    uint32_t *seeds_out;           // [n_frames][seeds_per_frame] or null: the seeds taken (rows below n_seeds_out); FOUND / NONE / CAPACITY frames
+    uint32_t *n_seeds_out;         // [n_frames] or null
+};
+// one workgroup per frame, an LDS layout of its own (100 656 bytes); n_frames * seeds_per_frame < 2^27; needs init_tail_kernels; hipError_t
+int launch_init_quads(const InitQuadsArgs &b, void *stream);
 // k_collect_tags (agx_collect_tags_enqueue): one round's bookkeeping of detect's loop (detector.rs:510-539) per frame -- the
 // decoded quads of the round into the frame's tag table (detected_tags.insert, :520: a tag keeps the row of its first insertion and
 // takes the corners of its last) and AGX_POINT_USED into the status words of their saddles (:521-536).  No pixels.  All pointers

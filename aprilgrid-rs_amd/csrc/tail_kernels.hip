@@ -41,6 +41,8 @@
 // k_board_tail (board_tail_body), one round of it up to the complete quad list, which goes out instead of being decoded.
 // k_grow_boards is that body once more with the caller's seed quads in place of init_quads' and the caller's spacing_ratio in
 // place of 0.3 (agx_grow_boards_enqueue): build_board_w / expand_one_w / probe4_w instantiated with the ratio at run time.
+// k_init_quads is init_quads alone, for seed saddles the caller names (agx_init_quads_enqueue): FIND's frame set-up and
+// init_quads_w in an LDS layout of its own, the seeds' quads out in order.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -225,6 +227,8 @@ __device__ __forceinline__ int differ10_coarse(float pc, float qc)
 // Nearly every angle is degrees away from 60 and 120: those are decided from the reference's expression evaluated with
 // this device's sincosf (<= 4 ulp, the OpenCL bound: the angle within 2e-4 degrees of the reference's -- the argument of
 // kBandAbs with a 4-ulp direction on one side); only within 1e-3 degrees of a threshold is the binary64 evaluation made.
+// BAND: where the frame's LDS keeps the debug band (k_init_quads has a layout of its own).
+template <int BAND = OFF_SHARED + 4 * 4>
 __device__ __forceinline__ int white_block(float s0_theta, float v02x, float v02y)
 {
     // s1 == s0 (try_expand_one pairs the same saddle with itself when the candidate lists overlap): both atan2f operands are
@@ -239,7 +243,7 @@ __device__ __forceinline__ int white_block(float s0_theta, float v02x, float v02
             {  // (tests only, TailArgs::debug_band: a wide band so that a known share of frames takes the hand-back path; the
                // value lies in the frame's shared words -- sh[4] -- so that no register carries it through the search)
                 extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-                const float debug_band = *reinterpret_cast<const float *>(lds + OFF_SHARED + 4 * 4);
+                const float debug_band = *reinterpret_cast<const float *>(lds + BAND);
                 if (debug_band > 0.0f && (fabsf(ac - 60.0f) <= debug_band || fabsf(ac - 120.0f) <= debug_band)) return 2;
             }
             if (ac < 60.0f - kCoarseBand || ac > 120.0f + kCoarseBand) return 0;
@@ -819,22 +823,32 @@ __device__ bool best_tag_row(const TailArgs &a, const u64 *codes, u64 bits, int 
 
 // ---- init_quads (detector.rs:543-586) for the seed s0, by one wave: the candidate quads into the wave's list, in the
 // reference's order; returns how many
+// L: where the wave's lists lie (the board search's: WaveLay; k_init_quads': IqLay, whose pair list holds the combinations of 63
+// neighbours).  NN: :550's 50 is the launch's n_nearest (2 .. 64, CtxNearest) -- the board search's kernels keep the constant.
+struct WaveLay {
+    static constexpr int CAND = WV_CAND, A3 = WV_A3, PAIRS = WV_PAIRS, SMALL = WV_SMALL, BAND = OFF_SHARED + 4 * 4;
+};
+struct CtxNearest : Ctx {
+    int n_nearest;
+};
+template <typename L = WaveLay, bool NN = false>
 __device__ int init_quads_w(const Ctx &c, uint8_t *wv, int s0, int lane, uint32_t &status, unsigned long long *tk)
 {
     AGX_TT(unsigned long long t_last = wall_clock64();)
 #define TKS(i) AGX_TT(do { const unsigned long long t_now = wall_clock64(); tk[i] += t_now - t_last; t_last = t_now; } while (0))
     const u64 below = (1ull << lane) - 1ull;
-    u64 *cand = reinterpret_cast<u64 *>(wv + WV_CAND);
-    uint16_t *pairs = reinterpret_cast<uint16_t *>(wv + WV_PAIRS);
-    uint16_t *same = reinterpret_cast<uint16_t *>(wv + WV_SMALL), *diff = same + 64, *s1ok = same + 128;
-    float *a0s = reinterpret_cast<float *>(wv + WV_SMALL + 384), *a2s = a0s + 64, *a3tab = reinterpret_cast<float *>(wv + WV_A3);
+    u64 *cand = reinterpret_cast<u64 *>(wv + L::CAND);
+    uint16_t *pairs = reinterpret_cast<uint16_t *>(wv + L::PAIRS);
+    uint16_t *same = reinterpret_cast<uint16_t *>(wv + L::SMALL), *diff = same + 64, *s1ok = same + 128;
+    float *a0s = reinterpret_cast<float *>(wv + L::SMALL + 384), *a2s = a0s + 64, *a3tab = reinterpret_cast<float *>(wv + L::A3);
     const int n = c.n;
+    const int nearest = NN ? static_cast<const CtxNearest &>(c).n_nearest : 50;
     const float *sx = c.sx, *sy = c.sy, *st = c.st;
     const float s0x = sx[s0], s0y = sy[s0], s0t = st[s0];
     int nc = 0;
     // 50 nearest: the distance keys, sorted.  Of more than 128 saddles only those are sorted that can be among the 50: the 50th
     // smallest of the 64 lanes' minima (each lane's own keys: every 64th saddle) is one of 64 keys of the set, so the set's 50th
-    // smallest is not above it -- usually 50 to 80 keys are left.
+    // smallest is not above it -- usually 50 to 80 keys are left.  (With NN: `nearest` for 50, up to all 64 minima.)
     int P = 64;
     u64 *keys = cand;
     wsync();  // (the previous seed's candidates are done with)
@@ -851,7 +865,7 @@ __device__ int init_quads_w(const Ctx &c, uint8_t *wv, int s0, int lane, uint32_
                 const bool keep_min = ((lane & j) == 0) == ((lane & k2) == 0);
                 v = (o < v) == keep_min ? o : v;
             }
-        const u64 bound = shfl_u64(v, 49);
+        const u64 bound = shfl_u64(v, nearest - 1);
         int cnt = 0;
         for (int base = 0; base < n; base += 64) {
             const int i = base + lane;
@@ -888,7 +902,7 @@ __device__ int init_quads_w(const Ctx &c, uint8_t *wv, int s0, int lane, uint32_
             wsync();
         }
     TKS(2);
-    const int m = n < 50 ? n : 50;
+    const int m = n < nearest ? n : nearest;
     int ns = 0, nd = 0;
     {
         const int idx = (lane >= 1 && lane < m) ? (int)(uint32_t)keys[lane] : 0;
@@ -912,7 +926,7 @@ __device__ int init_quads_w(const Ctx &c, uint8_t *wv, int s0, int lane, uint32_
             n_pairs += __popcll(mk);
         }
         // the white-block test depends on (s0, s1) only: once per s1 (0 fails, 1 passes, 2 undecided here)
-        if (lane < ns) s1ok[lane] = (uint16_t)white_block(s0t, sx[same[lane]] - s0x, sy[same[lane]] - s0y);
+        if (lane < ns) s1ok[lane] = (uint16_t)white_block<L::BAND>(s0t, sx[same[lane]] - s0x, sy[same[lane]] - s0y);
         wsync();
         // a3 = angle(v30, v01) (saddle.rs:59) depends on (d0, d1) only: once per pair (its coarse value; the exact one on demand)
         for (int p = lane; p < n_pairs && p < TA3; p += 64) {
@@ -1738,6 +1752,258 @@ __global__ void __launch_bounds__(64 * TW) k_grow_boards(GrowBoardsArgs b)
     board_tail_body<2>(a, b);
 }
 
+// ---- k_init_quads (agx_init_quads_enqueue): init_quads (detector.rs:543-586) of caller-given seed saddles ----------------------
+// One workgroup per frame, a wave per seed, the seeds in groups of TW; the frame set-up is k_find_boards' and init_quads_w is
+// the board search's own, on the launch's n_nearest.  None of the board search's LDS is needed (grid index, memo tables, code
+// list, board slots), so the layout is this kernel's: the list, the list-to-slot map, the reference's seed list, and per wave the
+// key / candidate space with init_quads_w's small tables -- IQ_LDS_BYTES, one frame per CU as before but two thirds of the
+// bytes; what holds it above half a CU's LDS is the 8 KB of keys a wave sorts when the pruning of a 1024-saddle list fails.
+// Emission is ordered (seed i's quads behind seed i - 1's) and a frame's capacity verdict comes before its first row: a group's
+// waves publish their counts, every wave takes its prefix, and the rows gather in an LDS list (IQ_ROWS of them) that goes out once
+// the total is known.  A frame with more rows than that list but not more than the caller's rows is listed a second time, each
+// group's rows straight to memory behind the same prefix (the verdict is known by then).
+struct IqLay {
+    static constexpr int CAND = 0;                    // u64[TCAND]; with what lies behind it also u64[TN] distance keys
+    static constexpr int A3 = CAND + TCAND * 8;       // f32[TA3]
+    static constexpr int PAIRS = A3 + TA3 * 4;        // u16[1953 + pad]: the (d0, d1) pairs of up to 63 neighbours
+    static constexpr int SMALL = PAIRS + 1960 * 2;    // as WV_SMALL
+    static constexpr int BYTES = SMALL + 1024;
+    static constexpr int BAND = 3 * TN * 4 + TN * 4 + TN * 2 + 364 * 4 + 4 * 4;  // IQ_SH's word 4 (below)
+};
+constexpr int IQ_ROWS = 1024;  // rows of a frame kept in LDS until its count is known
+constexpr int IQ_SX = 0, IQ_SY = IQ_SX + TN * 4, IQ_ST = IQ_SY + TN * 4;
+constexpr int IQ_SLOT = IQ_ST + TN * 4;       // u32[TN]: list position -> slot number within the frame
+constexpr int IQ_SEEDS = IQ_SLOT + TN * 4;    // u16[TN]: the saddles of the fullest round(theta) bin, in list order
+constexpr int IQ_HIST = IQ_SEEDS + TN * 2;    // u32[364]
+constexpr int IQ_SH = IQ_HIST + 364 * 4;      // u32[64]: [0] status, [2] seeds, [3] a non-finite saddle, [4] debug band, [8 .. 24) the groups' counts (two sets)
+constexpr int IQ_QBUF = IQ_SH + 64 * 4;       // u64[IQ_ROWS]
+constexpr int IQ_WAVES = IQ_QBUF + IQ_ROWS * 8;
+constexpr int IQ_LDS_BYTES = IQ_WAVES + TW * IqLay::BYTES;
+static_assert(IqLay::BAND == IQ_SH + 4 * 4 && IqLay::BYTES % 8 == 0 && IqLay::BYTES >= TN * 8 && IQ_QBUF % 8 == 0 && IQ_WAVES % 8 == 0, "k_init_quads' layout");
+static_assert(IQ_LDS_BYTES <= 160 * 1024, "LDS of a CU");
+
+__global__ void __launch_bounds__(64 * TW) k_init_quads(InitQuadsArgs b)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int f = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const u64 below = (1ull << lane) - 1ull;
+    float *sx = reinterpret_cast<float *>(lds + IQ_SX), *sy = reinterpret_cast<float *>(lds + IQ_SY), *st = reinterpret_cast<float *>(lds + IQ_ST);
+    uint32_t *slot_of = reinterpret_cast<uint32_t *>(lds + IQ_SLOT);
+    uint16_t *seeds = reinterpret_cast<uint16_t *>(lds + IQ_SEEDS);
+    uint32_t *hist = reinterpret_cast<uint32_t *>(lds + IQ_HIST);
+    uint32_t *sh = reinterpret_cast<uint32_t *>(lds + IQ_SH);
+    u64 *qbuf = reinterpret_cast<u64 *>(lds + IQ_QBUF);
+    uint8_t *wv = lds + IQ_WAVES + wave * IqLay::BYTES;
+    const u64 spf = b.seeds_per_frame;
+    uint32_t *cnt_out = b.seed_quad_counts ? b.seed_quad_counts + (u64)f * spf : nullptr;
+    const uint32_t *sd = b.seed_saddles ? b.seed_saddles + (u64)f * spf : nullptr;
+
+    uint32_t status = 0;  // per lane; merged through the groups' words
+    int n = 0;
+    // ---- the frame's list, as k_find_boards takes it; then the caller's seeds.  Decided before anything is listed ----
+    uint32_t early = 0xffffffffu;
+    u64 first_slot = (u64)f * (u64)b.saddles_per_frame;
+    u64 n_slots = b.saddles_per_frame;
+    uint32_t total = 0;  // the frame's seeds
+    if (b.host_only) {
+        early = AGX_BOARD_PENDING;
+    } else if (b.frame_table) {
+        const uint32_t *e = b.frame_table + 4 * (size_t)f;
+        if (e[2] & 7u) early = AGX_BOARD_INPUT;
+        n_slots = e[0];
+        first_slot = e[1];
+    } else if (b.counts) {
+        const uint32_t c = b.counts[f];
+        n_slots = c < b.saddles_per_frame ? c : b.saddles_per_frame;
+    }
+    if (early == 0xffffffffu) {
+        uint32_t *wcnt = hist;
+        bool bad = false;
+        u64 listed_all = 0;
+        for (u64 base = 0; base < n_slots; base += 64 * TW) {
+            const u64 i = base + (u64)tid;
+            bool listed = i < n_slots;
+            if (listed && b.point_status) listed = b.point_status[first_slot + i] == 0u;
+            float x = 0.0f, y = 0.0f, t = 0.0f;
+            if (listed) {
+                const float *src = reinterpret_cast<const float *>(b.saddles + (first_slot + i) * (u64)b.stride);
+                x = src[0];
+                y = src[1];
+                t = src[3];
+                if (!(fb_finite(x) && fb_finite(y) && fb_finite(t))) bad = true;
+                else if (!(fabsf(x) < 1e6f && fabsf(y) < 1e6f && t >= -180.0f && t <= 180.0f)) status |= TAIL_CAPACITY;
+            }
+            const u64 mk = __ballot(listed);
+            if (lane == 0) wcnt[wave] = (uint32_t)__popcll(mk);
+            __syncthreads();
+            u64 at = listed_all + (u64)__popcll(mk & below), sum = 0;
+            for (int w = 0; w < TW; ++w) {
+                const uint32_t cw = wcnt[w];
+                if (w < wave) at += cw;
+                sum += cw;
+            }
+            if (listed && at < (u64)TN) {
+                sx[at] = x;
+                sy[at] = y;
+                st[at] = t;
+                slot_of[at] = (uint32_t)i;
+            }
+            listed_all += sum;
+            __syncthreads();
+        }
+        if (tid < 64) sh[tid] = tid == 4 ? __float_as_uint(b.debug_band) : 0u;
+        __syncthreads();
+        if (bad) atomicOr(&sh[3], 1u);
+        if (listed_all > (u64)TN) status |= TAIL_CAPACITY;
+        if (status) atomicOr(&sh[0], status);
+        __syncthreads();
+        if (sh[3]) early = AGX_BOARD_INPUT;
+        else if (listed_all == 0) early = AGX_BOARD_NONE;
+        else if (sh[0]) early = AGX_BOARD_PENDING;
+        n = listed_all > (u64)TN ? TN : (int)listed_all;
+        status = 0;
+        if (sd) {
+            // every seed names a listed slot of the frame, or the frame is AGX_BOARD_INPUT (asked of the caller's words, not of
+            // the list in LDS: that one ends at TN).  No seed: no quad.
+            total = b.seeds_per_frame;
+            if (b.seed_counts) total = b.seed_counts[f] < total ? b.seed_counts[f] : total;
+            bool bad_seed = false;
+            for (u64 i = (u64)tid; i < (u64)total; i += 64 * TW) {
+                const uint32_t s = sd[i];
+                if ((u64)s >= n_slots) bad_seed = true;
+                else if (b.point_status && b.point_status[first_slot + s] != 0u) bad_seed = true;
+            }
+            const int any_bad = __syncthreads_or(bad_seed ? 1 : 0);
+            if (early != AGX_BOARD_INPUT) {
+                if (any_bad) early = AGX_BOARD_INPUT;
+                else if (total == 0) early = AGX_BOARD_NONE;
+            }
+        }
+    }
+    if (early != 0xffffffffu) {  // (the whole workgroup alike)
+        if (tid == 0) {
+            b.n_quads[f] = 0;
+            b.status[f] = early;
+            if (b.n_seeds_out) b.n_seeds_out[f] = 0;
+        }
+        if (early == AGX_BOARD_NONE && cnt_out)
+            for (u64 i = (u64)tid; i < spf; i += 64 * TW) cnt_out[i] = 0u;
+        return;
+    }
+    __syncthreads();
+    int n_bin = 0;  // the reference's seed list (:601-612), popped from the back
+    if (!sd) {
+        if (wave == 0) {  // the most populated round(theta) bin (ties: the smallest angle), in list order -- as k_board_tail's
+            for (int i = lane; i < 364; i += 64) hist[i] = 0;
+            wsync();
+            for (int i = lane; i < n; i += 64) atomicAdd(&hist[(int)round_half_away(st[i]) + 180], 1u);
+            wsync();
+            uint32_t bestk = 0;
+            for (int i = lane; i < 361; i += 64) {
+                const uint32_t k = hist[i] << 16 | (uint32_t)(0xffff - i);
+                bestk = k > bestk ? k : bestk;
+            }
+            bestk = wave_max_u(bestk);
+            const int best_angle = (int)(0xffff - (bestk & 0xffffu)) - 180;
+            int ns_ = 0;
+            for (int base = 0; base < n; base += 64) {
+                const int i = base + lane;
+                const bool is = i < n && (int)round_half_away(st[i]) == best_angle;
+                const u64 m = __ballot(is);
+                if (is) seeds[ns_ + __popcll(m & below)] = (uint16_t)i;
+                ns_ += __popcll(m);
+            }
+            if (lane == 0) sh[2] = (uint32_t)ns_;
+        }
+        __syncthreads();
+        n_bin = (int)sh[2];
+        total = (uint32_t)n_bin < b.seeds_per_frame ? (uint32_t)n_bin : b.seeds_per_frame;
+    }
+    if (b.seeds_out)
+        for (u64 i = (u64)tid; i < (u64)total; i += 64 * TW) b.seeds_out[(u64)f * spf + i] = sd ? sd[i] : slot_of[seeds[n_bin - 1 - (int)i]];
+    if (tid == 0 && b.n_seeds_out) b.n_seeds_out[f] = total;
+
+    CtxNearest c;
+    c.sx = sx; c.sy = sy; c.st = st; c.n = n;
+    c.n_nearest = (int)b.n_nearest;
+    unsigned long long tk[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const u64 row0 = (u64)f * (u64)b.quads_per_frame;
+    auto put = [&](u64 row, int corner, u64 q) {  // a corner of a row: the saddle's slot number within the frame and, optionally, its x, y
+        const int idx = q_at(q, corner);
+        const u64 at = (row0 + row) * 4u + (u64)corner;
+        b.quads[at] = slot_of[idx];
+        if (b.quad_points) {
+            b.quad_points[2 * at] = sx[idx];
+            b.quad_points[2 * at + 1] = sy[idx];
+        }
+    };
+    u64 run = 0;          // rows of the groups so far (every thread alike)
+    bool handed = false;  // a wave has raised a status word (every thread alike: read from the groups' words)
+    int group_no = 0;
+    for (int pass = 0; pass < 2; ++pass) {  // 0: count, rows into the LDS list; 1 (only for more rows than it holds): rows to memory
+        run = 0;
+        for (uint32_t base = 0; base < total && !handed; base += TW, ++group_no) {
+            const uint32_t gw = total - base < (uint32_t)TW ? total - base : (uint32_t)TW;
+            uint32_t *gc = sh + 8 + TW * (group_no & 1);  // the group's counts (bit 31: a status word); two sets, used alternately
+            int nc = 0;
+            if ((uint32_t)wave < gw) {
+                const uint32_t k = base + (uint32_t)wave;
+                int s0;
+                if (sd) {  // the seed's slot -> its position in the list (slot_of ascends: the list is in slot order)
+                    const uint32_t s = sd[k];
+                    int lo = 0, hi = n - 1;
+                    while (lo < hi) {
+                        const int mid = (lo + hi) >> 1;
+                        if (slot_of[mid] < s) lo = mid + 1;
+                        else hi = mid;
+                    }
+                    s0 = lo;
+                } else {
+                    s0 = seeds[n_bin - 1 - (int)k];
+                }
+                nc = init_quads_w<IqLay, true>(c, wv, s0, lane, status, tk);
+            }
+            status = wave_or_u(status);
+            if (lane == 0) gc[wave] = (uint32_t)nc | (status ? 0x80000000u : 0u);
+            __syncthreads();
+            uint32_t pre = 0, sum = 0;
+            for (int w = 0; w < TW; ++w) {
+                const uint32_t cw = gc[w];
+                handed = handed || (cw & 0x80000000u);
+                if (w < wave) pre += cw & 0x7fffffffu;
+                sum += cw & 0x7fffffffu;
+            }
+            const u64 at0 = run + pre;
+            const u64 *cand = reinterpret_cast<const u64 *>(wv + IqLay::CAND);
+            if (pass == 0) {
+                for (int i = lane; i < nc; i += 64)
+                    if (at0 + (u64)i < (u64)IQ_ROWS) qbuf[at0 + (u64)i] = cand[i];
+                if (cnt_out && (uint32_t)wave < gw && lane == 0) cnt_out[base + (uint32_t)wave] = (uint32_t)nc;
+            } else {
+                for (int i = lane; i < 4 * nc; i += 64) put(at0 + (u64)(i >> 2), i & 3, cand[i >> 2]);
+            }
+            run += sum;
+        }
+        if (pass == 1) break;
+        __syncthreads();  // (the LDS list is complete)
+        if (handed || run == 0 || run > (u64)b.quads_per_frame) break;
+        if (run <= (u64)IQ_ROWS) {
+            for (u64 i = (u64)tid; i < 4 * run; i += 64 * TW) put(i >> 2, (int)(i & 3), qbuf[i >> 2]);
+            break;
+        }
+    }
+    uint32_t fst = AGX_BOARD_FOUND;
+    if (handed) fst = AGX_BOARD_PENDING;
+    else if (run == 0) fst = AGX_BOARD_NONE;
+    else if (run > (u64)b.quads_per_frame) fst = AGX_BOARD_CAPACITY;
+    if (cnt_out && !handed)
+        for (u64 i = (u64)total + (u64)tid; i < spf; i += 64 * TW) cnt_out[i] = 0u;
+    if (tid == 0) {
+        b.n_quads[f] = fst == AGX_BOARD_FOUND || fst == AGX_BOARD_CAPACITY ? (run > 0xffffffffull ? 0xffffffffu : (uint32_t)run) : 0u;
+        b.status[f] = fst;
+    }
+}
+
 // agx_detect_batch_enqueue_to: frame f's entry of the tail's table (count, status) and its rows into the caller's arrays, as
 // agx_detect_batch_fetch reports them: TAIL_OK -> its rows, AGX_OK (more tags than cap: AGX_ERR_CAPACITY with the true count
 // and no row); a list of the chain that overflowed -> AGX_ERR_CAPACITY, count 0; handed back -> count 0, AGX_ERR_STATE until the
@@ -2102,7 +2368,19 @@ int init_tail_kernels()
     if (e != hipSuccess) return (int)e;
     const hipError_t e2 = hipFuncSetAttribute((const void *)k_find_boards, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     if (e2 != hipSuccess) return (int)e2;
-    return (int)hipFuncSetAttribute((const void *)k_grow_boards, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    const hipError_t e3 = hipFuncSetAttribute((const void *)k_grow_boards, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    if (e3 != hipSuccess) return (int)e3;
+    return (int)hipFuncSetAttribute((const void *)k_init_quads, hipFuncAttributeMaxDynamicSharedMemorySize, IQ_LDS_BYTES);
+}
+
+int launch_init_quads(const InitQuadsArgs &b, void *stream)
+{
+    if (b.n_frames <= 0) return (int)hipSuccess;
+    if (b.stride < 20 || (b.stride & 3) || !b.saddles_per_frame || !b.quads_per_frame || (b.counts && b.frame_table) || !b.saddles || !b.quads ||
+        !b.n_quads || !b.status || !b.seeds_per_frame || (b.seed_counts && !b.seed_saddles) || b.n_nearest < 2 || b.n_nearest > 64)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_init_quads, dim3((unsigned)b.n_frames), dim3(64 * TW), IQ_LDS_BYTES, (hipStream_t)stream, b);
+    return (int)hipGetLastError();
 }
 
 int launch_grow_boards(const GrowBoardsArgs &b, void *stream)

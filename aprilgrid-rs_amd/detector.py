@@ -161,6 +161,7 @@ class TagDetector:
         self._decode = None  # decode_quads_enqueue's batch: (n, quads per frame, tensors kept alive, device outputs or None)
         self._find = None    # find_boards_enqueue's batch: (n, quads per frame, tensors kept alive, device outputs or None)
         self._grow = None    # grow_boards_enqueue's batch: the tensors kept alive (the library itself knows whether it is in flight)
+        self._init = None    # init_quads_enqueue's batch: likewise
         self._clusters = None  # clusters_enqueue's batch: (n, clusters per frame, tensors kept alive, device outputs or None)
         try:
             if blur_sigma is not None:
@@ -792,7 +793,7 @@ class TagDetector:
         return n, qpf, 8, self._stage_tensor(quads, torch.float32, tuple(quads.shape), "quads", dev), None, dev
 
     def _replaces_batch(self):
-        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = self._clusters = None
+        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = self._clusters = self._init = None
 
     def decode_positions_enqueue(self, quads=None, points=None, status=None, img_size=None, border_bits=None, edge_bits=None, margin=0.5,
                                  counts=None, refined=None):
@@ -1051,6 +1052,132 @@ class TagDetector:
         if self._grow is not None:  # in flight: the library resolves it whatever it returns
             self._replaces_batch()
         self._check(self._lib.agx_grow_boards_fetch(self._h, n_threads))
+
+    # ---- candidate quads of caller-given seed saddles (src/detector.rs:543-586) -------------------
+    def init_quads_enqueue(self, saddles, quads, n_quads, status, seed_saddles=None, seed_counts=None, seeds_per_frame=None, n_nearest=50,
+                           counts=None, frame_table=None, point_status=None, quad_points=None, seed_quad_counts=None, seeds_out=None,
+                           n_seeds_out=None):
+        """init_quads of every seed saddle of every frame, seed i's quads behind seed i - 1's; stream-ordered behind torch's current
+        stream, returns immediately.  saddles, counts, frame_table and point_status as find_boards_enqueue's.  seed_saddles int32
+        [N, S]: slot numbers within the frame (seed_counts int32 [N] optionally), or None: the reference's own seeds, at most
+        seeds_per_frame of them (default 30, the reference's bound).  quads int32 [N, Q, 4], n_quads and status int32 [N]: the
+        device-resident results (required) -- quads with n_quads are grow_boards_enqueue's seed_quads with seed_counts as they
+        stand; quad_points float32 [N, Q, 4, 2], seed_quad_counts and seeds_out int32 [N, S], n_seeds_out int32 [N] optionally."""
+        import torch
+        if not (getattr(saddles, "is_cuda", False) and saddles.is_contiguous() and saddles.dtype == torch.float32 and saddles.shape[-1] >= 5):
+            raise AgxError(_ffi.AGX_ERR_ARG, "saddles must be a contiguous float32 device tensor [N, S, K >= 5] (or [capacity, K] with frame_table)")
+        dev = saddles.device
+        stride = 4 * int(saddles.shape[-1])
+
+        def tensor(t, dtype, shape, what):
+            if t is None:
+                return None
+            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and (shape is None or tuple(t.shape) == shape)
+                    and t.device == dev):
+                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s tensor %s on the saddles' device" % (what, dtype, shape))
+            return t.data_ptr()
+
+        if frame_table is not None:
+            if saddles.dim() != 2 or frame_table.dim() != 2 or frame_table.shape[1] != 4:
+                raise AgxError(_ffi.AGX_ERR_ARG, "with frame_table [N, 4]: saddles [capacity, K]")
+            n, spf, n_slots = int(frame_table.shape[0]), int(saddles.shape[0]), int(saddles.shape[0])
+        else:
+            if saddles.dim() != 3 or saddles.shape[1] == 0:
+                raise AgxError(_ffi.AGX_ERR_ARG, "saddles must be [N, S, K]")
+            n, spf = int(saddles.shape[0]), int(saddles.shape[1])
+            n_slots = n * spf
+        if point_status is not None and point_status.numel() != n_slots:
+            raise AgxError(_ffi.AGX_ERR_ARG, "point_status: one word per slot")
+        if quads is None or quads.dim() != 3 or (seed_saddles is not None and seed_saddles.dim() != 2):
+            raise AgxError(_ffi.AGX_ERR_ARG, "quads [N, Q, 4] and seed_saddles [N, S]")
+        if seed_saddles is not None:
+            seeds = int(seed_saddles.shape[1])
+        else:
+            seeds = 30 if seeds_per_frame is None else int(seeds_per_frame)
+        qpf = int(quads.shape[1])
+        ptrs = (tensor(counts, torch.int32, (n,), "counts"), tensor(frame_table, torch.int32, (n, 4), "frame_table"),
+                tensor(point_status, torch.int32, None, "point_status"), tensor(seed_saddles, torch.int32, (n, seeds), "seed_saddles"),
+                tensor(seed_counts, torch.int32, (n,), "seed_counts"))
+        outs = (tensor(quads, torch.int32, (n, qpf, 4), "quads"), tensor(quad_points, torch.float32, (n, qpf, 4, 2), "quad_points"),
+                tensor(n_quads, torch.int32, (n,), "n_quads"), tensor(status, torch.int32, (n,), "status"),
+                tensor(seed_quad_counts, torch.int32, (n, seeds), "seed_quad_counts"), tensor(seeds_out, torch.int32, (n, seeds), "seeds_out"),
+                tensor(n_seeds_out, torch.int32, (n,), "n_seeds_out"))
+        self._follow_torch_stream(saddles)
+        rc = self._lib.agx_init_quads_enqueue(self._h, saddles.data_ptr(), stride, n, spf, ptrs[0], ptrs[1], ptrs[2], ptrs[3], seeds, ptrs[4],
+                                              int(n_nearest), qpf, *outs)
+        if rc == _ffi.AGX_OK:  # (a refused argument leaves the batch in flight where it is)
+            self._replaces_batch()
+            self._init = (saddles, counts, frame_table, point_status, seed_saddles, seed_counts, quads, quad_points, n_quads, status,
+                          seed_quad_counts, seeds_out, n_seeds_out)
+        self._check(rc)
+
+    def init_quads_fetch(self, n_threads=0):
+        """Wait for init_quads_enqueue's batch and let the host form answer the frames the kernel handed back: the device tensors
+        that call was given are complete when this returns."""
+        if self._init is not None:  # in flight: the library resolves it whatever it returns
+            self._replaces_batch()
+        self._check(self._lib.agx_init_quads_fetch(self._h, n_threads))
+
+    def find_boards_staged(self, saddles, spacing_ratio=0.3, counts=None, point_status=None, quads_per_frame=128, candidates_per_frame=1024,
+                           n_nearest=50):
+        """try_find_best_board (src/detector.rs:588-639) as its stages on device tensors, at ANY spacing_ratio: the reference's seeds
+        and their candidate quads (init_quads_enqueue), a board from every candidate (grow_boards_enqueue), then the reference's
+        stop rule per seed SADDLE (:626) on the host from the seeds' scores and the quads per seed: the board is the first
+        candidate that strictly beats all before it among those of the seeds up to and including the first seed after which the
+        best score is >= 36.  Where that is not the first maximum over all candidates, a second grow launch restricted to that
+        prefix gives the board.  saddles / counts / point_status as find_boards_enqueue's.  -> (quads, quad_points, n_quads,
+        status) as find_boards_fetch returns them: at 0.3 what find_boards_enqueue + find_boards_fetch answer."""
+        import torch
+        n, dev = int(saddles.shape[0]), saddles.device
+        qpf, cpf = int(quads_per_frame), int(candidates_per_frame)
+        i32 = dict(dtype=torch.int32, device=dev)
+        cand, ncand, cst = torch.zeros((n, cpf, 4), **i32), torch.zeros(n, **i32), torch.zeros(n, **i32)
+        per_seed = torch.zeros((n, 30), **i32)
+        self.init_quads_enqueue(saddles, cand, ncand, cst, seeds_per_frame=30, n_nearest=n_nearest, counts=counts, point_status=point_status,
+                                seed_quad_counts=per_seed)
+        self.init_quads_fetch()
+        quads, qpts = torch.zeros((n, qpf, 4), **i32), torch.zeros((n, qpf, 4, 2), dtype=torch.float32, device=dev)
+        nq, bst, best = torch.zeros(n, **i32), torch.zeros(n, **i32), torch.zeros(n, **i32)
+        scores = torch.zeros((n, cpf), **i32)
+
+        def grow(seed_counts):
+            self.grow_boards_enqueue(saddles, cand, quads, nq, bst, counts=counts, point_status=point_status, seed_counts=seed_counts,
+                                     spacing_ratio=spacing_ratio, stop_score=0, fix_missing=True, quad_points=qpts, seed_scores=scores,
+                                     best_seed=best)
+            self.grow_boards_fetch()
+
+        grow(ncand)
+        h_cst, h_ncand, h_per = cst.cpu().numpy(), ncand.cpu().numpy(), per_seed.cpu().numpy()
+        h_bst, h_best, h_scores = bst.cpu().numpy(), best.cpu().numpy(), scores.cpu().numpy()
+        prefix = h_ncand.copy()
+        again = False
+        for f in range(n):
+            if h_cst[f] != _ffi.AGX_BOARD_FOUND or h_bst[f] not in (_ffi.AGX_BOARD_FOUND, _ffi.AGX_BOARD_CAPACITY):
+                continue
+            best_score, best_at, done = 0, -1, 0
+            for per in h_per[f]:  # the reference's loop over the seed saddles (:613-629)
+                for i in range(done, done + int(per)):
+                    if int(h_scores[f, i]) > best_score:
+                        best_score, best_at = int(h_scores[f, i]), i
+                done += int(per)
+                if best_score >= 36:
+                    break
+            prefix[f] = done
+            again = again or best_at != int(h_best[f])
+        if again:
+            grow(torch.from_numpy(prefix.astype(np.int32)).to(dev))
+        out_q = np.full((n, qpf, 4), 0xFFFFFFFF, np.uint32)
+        out_p = np.full((n, qpf, 4, 2), np.nan, np.float32)
+        h_q, h_p = quads.cpu().numpy().view(np.uint32), qpts.cpu().numpy()
+        out_n, out_s = nq.cpu().numpy().view(np.uint32).copy(), bst.cpu().numpy().view(np.uint32).copy()
+        for f in range(n):
+            if h_cst[f] == _ffi.AGX_BOARD_CAPACITY:
+                raise AgxError(_ffi.AGX_ERR_CAPACITY, "find_boards_staged: frame %d has %d candidate quads (candidates_per_frame = %d)"
+                               % (f, int(h_ncand[f]), cpf))
+            if out_s[f] == _ffi.AGX_BOARD_FOUND:
+                k = int(out_n[f])
+                out_q[f, :k], out_p[f, :k] = h_q[f, :k], h_p[f, :k]
+        return out_q, out_p, out_n, out_s
 
     # ---- gaussian_blur_f32 / hessian_response as planes (src/image_util.rs:110-206, :72-109) ----
     @staticmethod
@@ -1591,6 +1718,37 @@ def grow_board_tail(saddles, seeds, spacing_ratio=0.3, stop_score=0, fix_missing
     found = status.value == _ffi.AGX_BOARD_FOUND
     some = found or status.value == _ffi.AGX_BOARD_CAPACITY
     return quads[:n_quads.value if found else 0].copy(), status.value, n_quads.value, scores if some else None, best.value if some else None
+
+
+def init_quads_tail(saddles, seeds=None, max_seeds=None, n_nearest=50, cap=1024, point_status=None):
+    """The host form of init_quads for a list of seeds (src/detector.rs:543-586; agx_init_quads_tail) without a device: saddles a
+    SADDLE_DTYPE array (or [n, 5] float32); seeds: indices into it, or None for the reference's own seeds (:601-616), at most
+    max_seeds of them (default 30; with seeds: default all of them) -> (quads [n_quads, 4] uint32, status AGX_BOARD_*, n_quads,
+    seed_quad_counts [max_seeds] uint32, seeds_taken uint32); the last two are None for AGX_BOARD_INPUT."""
+    a = np.asarray(saddles)
+    if a.dtype == SADDLE_DTYPE:
+        a = np.ascontiguousarray(a).view(np.float32)
+    a = np.ascontiguousarray(a, np.float32).reshape(-1, 5)
+    s = None if seeds is None else np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+    if max_seeds is None:
+        max_seeds = 30 if s is None else max(1, s.shape[0])
+    room = max(int(max_seeds), 0)
+    ps = None if point_status is None else np.ascontiguousarray(point_status, np.uint32).reshape(a.shape[0])
+    quads = np.zeros((max(int(cap), 0), 4), np.uint32)
+    per_seed, taken = np.zeros(room, np.uint32), np.zeros(room, np.uint32)
+    none = np.zeros(1, np.uint32)  # (a non-null pointer for an empty seed list: null asks for the reference's seeds)
+    n_quads, status, n_taken = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    st = _ffi.lib().agx_init_quads_tail(a.ctypes.data if a.shape[0] else None, a.shape[0], ps.ctypes.data if ps is not None and ps.size else None,
+                                        None if s is None else (s.ctypes.data if s.shape[0] else none.ctypes.data), 0 if s is None else s.shape[0],
+                                        room, int(n_nearest), quads.ctypes.data if quads.shape[0] else None, quads.shape[0], C.byref(n_quads),
+                                        C.byref(status), per_seed.ctypes.data if room else None, taken.ctypes.data if room else None,
+                                        C.byref(n_taken))
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    found = status.value == _ffi.AGX_BOARD_FOUND
+    bad = status.value == _ffi.AGX_BOARD_INPUT
+    return (quads[:n_quads.value if found else 0].copy(), status.value, n_quads.value, None if bad else per_seed,
+            None if bad else taken[:n_taken.value].copy())
 
 
 class DetectorGroup:

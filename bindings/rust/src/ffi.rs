@@ -270,6 +270,16 @@ extern "C" {
     pub fn agx_find_board_tail(saddles: *const agx_saddle, n_saddles: u32, quads: *mut u32, cap: u32, n_quads: *mut u32,
                                status: *mut u32) -> c_int;
 
+    pub fn agx_init_quads_enqueue(det: *mut agx_detector, d_saddles: *const c_void, saddle_stride_bytes: usize, n_frames: c_int,
+                                  saddles_per_frame: u32, d_counts: *const u32, d_frame_table: *const c_void, d_point_status: *const u32,
+                                  d_seed_saddles: *const u32, seeds_per_frame: u32, d_seed_counts: *const u32, n_nearest: u32,
+                                  quads_per_frame: u32, d_quads: *mut u32, d_quad_points: *mut c_float, d_n_quads: *mut u32,
+                                  d_status: *mut u32, d_seed_quad_counts: *mut u32, d_seeds_out: *mut u32, d_n_seeds_out: *mut u32) -> c_int;
+    pub fn agx_init_quads_fetch(det: *mut agx_detector, n_threads: c_int) -> c_int;
+    pub fn agx_init_quads_tail(saddles: *const agx_saddle, n_saddles: u32, point_status: *const u32, seed_saddles: *const u32, n_seeds: u32,
+                               max_seeds: u32, n_nearest: u32, quads: *mut u32, cap: u32, n_quads: *mut u32, status: *mut u32,
+                               seed_quad_counts: *mut u32, seeds_out: *mut u32, n_seeds_out: *mut u32) -> c_int;
+
     pub fn agx_grow_boards_enqueue(det: *mut agx_detector, d_saddles: *const c_void, saddle_stride_bytes: usize, n_frames: c_int,
                                    saddles_per_frame: u32, d_counts: *const u32, d_frame_table: *const c_void, d_point_status: *const u32,
                                    d_seed_quads: *const u32, seeds_per_frame: u32, d_seed_counts: *const u32, spacing_ratio: c_float,

@@ -466,6 +466,51 @@ pub fn find_best_board(refined: &[Saddle]) -> Option<Vec<[usize; 4]>> {
     }
 }
 
+/// reference src/detector.rs:543-586, `init_quads(refined, s0_idx, tree)`, for every seed in order: the candidate quads of each
+/// seed saddle as indices into `refined`, in the reference's loop and corner order, among the `n_nearest` (2 ..= 64; the
+/// reference's is 50) nearest saddles of the seed.  `seeds = None`: try_find_best_board's own seeds (:601-616), at most
+/// `max_seeds` of them (the reference takes 30).  Returns `(quads, quads per seed, the seeds taken)`.  The host form (no device is
+/// used).  Panics on a saddle whose x, y or theta is not finite, on a seed index beyond the list and on an `n_nearest` outside
+/// 2 ..= 64.
+pub fn init_quads_tail(refined: &[Saddle], seeds: Option<&[usize]>, max_seeds: usize, n_nearest: u32) -> (Vec<[usize; 4]>, Vec<u32>, Vec<usize>) {
+    let list: Vec<ffi::agx_saddle> =
+        refined.iter().map(|s| ffi::agx_saddle { x: s.p.0, y: s.p.1, k: s.k, theta: s.theta, phi: s.phi }).collect();
+    let given: Option<Vec<u32>> = seeds.map(|s| s.iter().map(|&i| i as u32).collect());
+    let room = match &given {
+        Some(s) => s.len().max(1),
+        None => max_seeds.max(1),
+    };
+    let no_seed = [0u32; 1];  // (a non-null pointer for an empty seed list: null asks for the reference's seeds)
+    let (seed_ptr, n_seeds) = match &given {
+        Some(s) if !s.is_empty() => (s.as_ptr(), s.len() as u32),
+        Some(_) => (no_seed.as_ptr(), 0u32),
+        None => (std::ptr::null(), 0u32),
+    };
+    let mut cap = 1024u32;
+    loop {
+        let mut quads = vec![0u32; cap as usize * 4];
+        let mut counts = vec![0u32; room];
+        let mut taken = vec![0u32; room];
+        let (mut n, mut status, mut n_taken) = (0u32, 0u32, 0u32);
+        let st = unsafe {
+            ffi::agx_init_quads_tail(list.as_ptr(), list.len() as u32, std::ptr::null(), seed_ptr, n_seeds, room as u32, n_nearest,
+                                     quads.as_mut_ptr(), cap, &mut n, &mut status, counts.as_mut_ptr(), taken.as_mut_ptr(), &mut n_taken)
+        };
+        assert_eq!(st, ffi::AGX_OK, "agx_init_quads_tail failed: {}", st);
+        counts.truncate(n_taken as usize);
+        let taken: Vec<usize> = taken[..n_taken as usize].iter().map(|&s| s as usize).collect();
+        match status as c_int {
+            ffi::AGX_BOARD_FOUND => {
+                let rows = quads[..n as usize * 4].chunks(4).map(|q| [q[0] as usize, q[1] as usize, q[2] as usize, q[3] as usize]).collect();
+                return (rows, counts, taken);
+            }
+            ffi::AGX_BOARD_CAPACITY => cap = n,
+            ffi::AGX_BOARD_NONE => return (Vec::new(), counts, taken),
+            _ => panic!("init_quads_tail: a saddle's x, y or theta is not finite, or a seed names no saddle of the list"),
+        }
+    }
+}
+
 /// reference src/board.rs:26-112 as try_find_best_board uses it (src/detector.rs:613-633), for a caller who already knows quads of
 /// the board: `Board::new(refined, all-true mask, seed, spacing_ratio, tree)` for every seed in order, the first one whose score is
 /// strictly above every earlier one, `try_fix_missing` on it if `fix_missing`, then `all_tag_indexes`.  `stop_score > 0` ends the

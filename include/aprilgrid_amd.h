@@ -643,6 +643,69 @@ int agx_find_board(agx_detector *det, const agx_saddle *saddles, uint32_t n_sadd
 int agx_find_board_tail(const agx_saddle *saddles, uint32_t n_saddles, uint32_t *quads, uint32_t cap, uint32_t *n_quads,
                         uint32_t *status);
 
+/* ---- candidate quads of caller-given seed saddles ---------------------------------------- */
+
+/* init_quads(refined, s0_idx, tree) -- src/detector.rs:543-586, with is_valid_quad (src/saddle.rs:17-67) -- the `pub fn` between
+ * a refined saddle list and the seed quads of a board: for a caller who knows one CORNER of the board (a tracked saddle, a
+ * predicted point snapped to the nearest saddle) rather than one quad.  Its rows are agx_grow_boards_enqueue's seeds as they
+ * stand, so saddles -> init_quads -> grow boards (at any spacing ratio) -> decode -> collect runs without a host step.
+ * Per frame over saddle lists in DEVICE memory, stream-ordered on the detector's stream; returns without waiting.  d_saddles,
+ * saddle_stride_bytes, n_frames, saddles_per_frame, d_counts, d_frame_table and d_point_status are read exactly as
+ * agx_find_boards_enqueue reads them (an overflow bit or a listed saddle with a non-finite x, y or theta: AGX_BOARD_INPUT).
+ *   d_seed_saddles [n_frames][seeds_per_frame] uint32: slot numbers within the frame.  Frame f has min(d_seed_counts[f],
+ *                  seeds_per_frame) seeds, seeds_per_frame with d_seed_counts NULL.  Every seed of the frame is looked at
+ *                  before anything is written: one that names a slot at or beyond the frame's count, or a slot that is not
+ *                  listed, makes the frame AGX_BOARD_INPUT.  The same saddle twice yields its quads twice.
+ *                  NULL: try_find_best_board's own seeds (:601-616) -- the saddles of the fullest round(theta) bin (of equally
+ *                  full bins the one with the smallest angle), taken from the back of the list -- the first seeds_per_frame of
+ *                  them; 30 is the reference's loop bound (:613).
+ *   n_nearest      2 .. 64: the 50 of :550, the neighbours (the seed itself among them) a seed's quads are made of.  A seed
+ *                  among fewer listed saddles uses all of them; saddles at exactly the same binary32 squared distance are taken
+ *                  in list order.
+ * Results, frame f: d_quads [f][quads_per_frame][4]: slot numbers within the frame, seed i's quads behind seed i - 1's, each
+ * seed's in init_quads' loop order and every row in its corner order (:577-581), so column 0 is the row's seed; d_n_quads[f]
+ * their number -- d_quads with d_n_quads are d_seed_quads with d_seed_counts of agx_grow_boards_enqueue (seeds_per_frame =
+ * quads_per_frame) --; d_quad_points (optional) as agx_find_boards_enqueue's; d_status[f]:
+ *   AGX_BOARD_FOUND     at least one quad;
+ *   AGX_BOARD_NONE      an empty list, no seed, or no valid quad;
+ *   AGX_BOARD_CAPACITY  more quads than quads_per_frame: the true count and no row;
+ *   AGX_BOARD_INPUT     as above; only d_n_quads (0), d_status and d_n_seeds_out (0) are written;
+ *   AGX_BOARD_PENDING   handed back, until agx_init_quads_fetch has run the host form.
+ * d_seed_quad_counts [n_frames][seeds_per_frame] (optional): the quads of each seed, 0 behind the frame's seeds -- what maps
+ * agx_grow_boards_enqueue's d_best_seed back to a saddle, and what the reference's per-saddle `>= 36` rule (:626) is applied
+ * with.  d_seeds_out [n_frames][seeds_per_frame], d_n_seeds_out [n_frames] (optional): the seeds taken, rows below the count.
+ * These three are written for frames that end FOUND, NONE or CAPACITY.  All arrays are caller-owned device memory, 4-byte
+ * aligned; d_quads, d_n_quads and d_status are required.
+ * The kernel hands a frame back as AGX_BOARD_PENDING where agx_find_boards_enqueue's does: more than 1024 listed saddles, a
+ * coordinate beyond 1e6, a theta outside [-180, 180], a seed with more than 256 candidate quads, a quad that hangs on a
+ * white-block angle inside the guard band, option "tail_debug_band"; every frame with "device_tail" 0 or refused.
+ * A further kind of batch on the handle: it replaces whatever is in flight without waiting, the other kinds' fetches of it are
+ * AGX_ERR_STATE, and a refused argument leaves the batch in flight where it is.
+ * AGX_ERR_ARG: agx_find_boards_enqueue's, NULL d_quads, d_n_quads or d_status, seeds_per_frame == 0, d_seed_counts without
+ * d_seed_saddles, n_nearest outside 2 .. 64, 2^27 or more seed rows in the batch. */
+int agx_init_quads_enqueue(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames,
+                           uint32_t saddles_per_frame, const uint32_t *d_counts, const void *d_frame_table,
+                           const uint32_t *d_point_status,
+                           const uint32_t *d_seed_saddles, uint32_t seeds_per_frame, const uint32_t *d_seed_counts,
+                           uint32_t n_nearest,
+                           uint32_t quads_per_frame, uint32_t *d_quads, float *d_quad_points, uint32_t *d_n_quads,
+                           uint32_t *d_status, uint32_t *d_seed_quad_counts, uint32_t *d_seeds_out, uint32_t *d_n_seeds_out);
+/* Wait for the batch of agx_init_quads_enqueue and resolve every AGX_BOARD_PENDING frame: the host form (agx_init_quads_tail's
+ * code) runs on the detector's pool (n_threads host threads; 0: agx_host_parallelism()), and the frame's rows, count, status,
+ * per-seed counts and seeds are written to the device arrays on the detector's stream before the call returns.
+ * AGX_ERR_STATE: no such batch in flight. */
+int agx_init_quads_fetch(agx_detector *det, int n_threads);
+/* The host form without a detector handle (no device needed, like agx_find_board_tail): one list, the same semantics.
+ * seed_saddles [n_seeds] and quads [cap][4] are indices into `saddles`; point_status NULL or a word per saddle (0 = listed).
+ * The first min(n_seeds, max_seeds) seeds are taken; seed_saddles NULL (with n_seeds 0): the reference's own seeds, at most
+ * max_seeds of them.  seed_quad_counts [max_seeds], seeds_out [max_seeds] and n_seeds_out may be NULL; the first two are left as
+ * they are for AGX_BOARD_INPUT.  AGX_ERR_ARG: a NULL n_quads or status, seeds without seed_saddles, max_seeds == 0, n_nearest
+ * outside 2 .. 64. */
+int agx_init_quads_tail(const agx_saddle *saddles, uint32_t n_saddles, const uint32_t *point_status,
+                        const uint32_t *seed_saddles, uint32_t n_seeds, uint32_t max_seeds, uint32_t n_nearest,
+                        uint32_t *quads, uint32_t cap, uint32_t *n_quads, uint32_t *status,
+                        uint32_t *seed_quad_counts, uint32_t *seeds_out, uint32_t *n_seeds_out);
+
 /* ---- boards from the caller's seed quads ------------------------------------------------- */
 
 /* Board::new(refined, active_idxs, quad_idxs, spacing_ratio, tree) -- src/board.rs:26-48 -- with try_fix_missing (:52-112),
