@@ -125,7 +125,15 @@ int agx_detector_family_info(const agx_detector *det, int *edge_bits, int *borde
  * candidates W*H/2, clusters W*H/8, saddles W*H/64 (lists of up to 16384 saddles are ordered in
  * LDS, longer ones -- pure-noise frames of several megapixels -- in global memory).
  * Overflow of any of them
- * is reported as AGX_ERR_CAPACITY for that frame, never truncated. */
+ * is reported as AGX_ERR_CAPACITY for that frame, never truncated.  An explicit limit is taken as given, however small (the
+ * floors of the defaults, 4096 / 1024 / 256, apply to the defaults only).  What each limit must cover for a frame to succeed
+ * (a limit equal to the count changes nothing; one below voids that frame and no other -- tests/test_gpu_list_limits.py):
+ *   max_saddles     the frame's saddles after the k / phi filter; one short: AGX_FRAME_SADDLE_OVERFLOW alone
+ *   max_clusters    the frame's flood seeds -- candidate pixels that may start a cluster, at least one per cluster and a few per
+ *                   cent more (AGX_DBG_COUNTERS word 1) -- on every path: the seed list shares this limit with the cluster list
+ *                   behind it and is the longer of the two; one short: AGX_FRAME_CANDIDATE_OVERFLOW (the seed appends' bit)
+ *   max_candidates  the pixels below the frame's threshold, only where the generic kernels cluster the frame ("force_generic",
+ *                   or a component beyond the flood windows: AGX_FRAME_GENERIC_PATH); one short: AGX_FRAME_CANDIDATE_OVERFLOW */
 int agx_detector_set_limits(agx_detector *det, uint32_t max_candidates, uint32_t max_clusters,
                             uint32_t max_saddles);
 
@@ -286,6 +294,14 @@ typedef struct agx_frame_result {
     uint32_t status;  /* 0 or a combination of AGX_FRAME_* bits    */
     uint32_t n_clusters;
 } agx_frame_result;
+/* Which overflow sets which bit (agx_detector_set_limits says what each limit must cover):
+ *   CANDIDATE_OVERFLOW  the generic path's candidate list beyond max_candidates -- and the flood seed list beyond max_clusters,
+ *                       on every sparse path and under "force_generic" alike (a seed is a candidate pixel; the seed appends
+ *                       of k_verify_seeds and k_sparse_frame raise this bit, not CLUSTER_OVERFLOW)
+ *   CLUSTER_OVERFLOW    the cluster list (flood clusters, the generic path's roots) beyond max_clusters -- reachable only where
+ *                       the seed list fitted
+ *   SADDLE_OVERFLOW     the frame's saddle list beyond max_saddles, or beyond what is left of a caller-owned slab
+ *                       (agx_saddles_batch_enqueue_to: saddle_capacity), and nothing else */
 enum {
     AGX_FRAME_CANDIDATE_OVERFLOW = 1,
     AGX_FRAME_CLUSTER_OVERFLOW = 2,
