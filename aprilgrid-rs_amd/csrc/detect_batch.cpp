@@ -1212,150 +1212,261 @@ int agx::best_tag_enqueue_impl(agx_detector *det, const uint64_t *d_bits, uint32
     return AGX_OK;
 }
 
-// ---- agx_find_boards_enqueue / _fetch: try_find_best_board (src/detector.rs:588-639) of caller-given saddle lists --------------
-// k_find_boards on the detector's stream, one workgroup per frame.  No pixels, no chain, no workspace.  Without the device tail
+// ---- the three stages over caller-given saddle lists: agx_find_boards_*, agx_grow_boards_*, agx_init_quads_* ---------------------
+// One kernel each on the detector's stream, one workgroup per frame.  No pixels, no chain, no workspace.  Without the device tail
 // (option "device_tail" 0, or this process's atan2f is not the routine the kernel restates) the kernel only marks every frame
 // AGX_BOARD_PENDING, and the fetch's host form answers them all.
-int agx::find_boards_enqueue_impl(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
-                                  const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status,
-                                  uint32_t quads_per_frame, uint32_t *d_quads, float *d_quad_points, uint32_t *d_n_quads, uint32_t *d_status)
+namespace {
+// What the three enqueues are handed alike: the lists and the result arrays
+struct ListArgs {
+    const void *d_saddles;
+    size_t saddle_stride_bytes;
+    int n_frames;
+    uint32_t saddles_per_frame;
+    const uint32_t *d_counts;
+    const void *d_frame_table;
+    const uint32_t *d_point_status;
+    uint32_t quads_per_frame;
+    uint32_t *d_quads;
+    float *d_quad_points;
+    uint32_t *d_n_quads, *d_status;
+};
+
+// The checks of the list arguments, in the one order all three refuse them in.  seeds_per_frame: null where the stage has no
+// seeds; own(): the stage's own checks, between the lists' and the alignment's; own_ptrs: its own device pointers, or'ed.
+// (All of it ahead of begin_batch: refused arguments leave the batch in flight.)
+template <class Own>
+int check_list_args(agx_detector *det, const ListArgs &l, const uint32_t *seeds_per_frame, uintptr_t own_ptrs, Own own)
 {
-    if (!det) return AGX_ERR_ARG;
-    if (!d_saddles || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null saddles or n_frames <= 0");
-    if (saddle_stride_bytes < 20 || (saddle_stride_bytes & 3) || saddle_stride_bytes > 0x7fffffffu)
+    if (!l.d_saddles || l.n_frames <= 0) return fail(det, AGX_ERR_ARG, "null saddles or n_frames <= 0");
+    if (l.saddle_stride_bytes < 20 || (l.saddle_stride_bytes & 3) || l.saddle_stride_bytes > 0x7fffffffu)
         return fail(det, AGX_ERR_ARG, "saddle_stride_bytes must be a multiple of 4 and at least 20");
-    if (!saddles_per_frame || !quads_per_frame) return fail(det, AGX_ERR_ARG, "saddles_per_frame and quads_per_frame must be > 0");
-    if (d_counts && d_frame_table) return fail(det, AGX_ERR_ARG, "d_counts and d_frame_table: at most one of them");
-    if ((d_quads == nullptr) != (d_n_quads == nullptr) || (d_quads == nullptr) != (d_status == nullptr))
-        return fail(det, AGX_ERR_ARG, "d_quads, d_n_quads and d_status: all or none");
-    if (((uintptr_t)d_saddles | (uintptr_t)d_counts | (uintptr_t)d_frame_table | (uintptr_t)d_point_status | (uintptr_t)d_quads |
-         (uintptr_t)d_quad_points | (uintptr_t)d_n_quads | (uintptr_t)d_status) & 3)
-        return fail(det, AGX_ERR_ARG, "saddles, counts, frame table, point statuses and the results must be 4-byte aligned");
-    if (n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
-    const size_t rows = (size_t)n_frames * quads_per_frame;
-    if (rows >= ((size_t)1 << 27)) return fail(det, AGX_ERR_ARG, "at most 2^27 - 1 quad rows per batch");
-    HIP_TRY(det, hipSetDevice(det->device));
-    begin_batch(det);
-    const bool host_only = device_tail_mode(det) == 0;
-    if (!host_only && tail_prepare(det)) return fail(det, AGX_ERR_HIP, "the device tail's set-up (code list, kernel attributes)");
-    int results = RESULTS_CALLER;
-    if (!d_quads) {
-        d_quads = static_cast<uint32_t *>(side_ensure(det, SB_FIND_QUADS, rows * 4 * sizeof(uint32_t), 0));
-        d_n_quads = static_cast<uint32_t *>(side_ensure(det, SB_FIND_COUNTS, (size_t)n_frames * sizeof(uint32_t), 0));
-        d_status = static_cast<uint32_t *>(side_ensure(det, SB_FIND_STATUS, (size_t)n_frames * sizeof(uint32_t), 0));
-        if (!d_quad_points) d_quad_points = static_cast<float *>(side_ensure(det, SB_FIND_POINTS, rows * 8 * sizeof(float), 0));
-        if (!d_quads || !d_n_quads || !d_status || !d_quad_points) return fail(det, AGX_ERR_HIP, "hipMalloc: board quads");
-        results = RESULTS_HOST;
-    }
-    FindBoardsArgs q{};
-    q.saddles = static_cast<const uint8_t *>(d_saddles);
-    q.stride = (uint32_t)saddle_stride_bytes;
-    q.n_frames = n_frames;
-    q.saddles_per_frame = saddles_per_frame;
-    q.counts = d_counts;
-    q.frame_table = static_cast<const uint32_t *>(d_frame_table);
-    q.point_status = d_point_status;
-    q.quads_per_frame = quads_per_frame;
-    q.quads = d_quads;
-    q.quad_points = d_quad_points;
-    q.n_quads = d_n_quads;
-    q.status = d_status;
-    q.debug_band = (float)det->tail_debug_band_mdeg * 1e-3f;
-    q.host_only = host_only ? 1 : 0;
-    const hipError_t e = (hipError_t)launch_find_boards(q, det->stream);
-    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_find_boards: ") + hipGetErrorString(e));
-    det->batch = BATCH_FIND;
-    FindPending &p = det->find;
-    p.results = results;
-    p.n_frames = n_frames;
-    p.saddles_per_frame = saddles_per_frame;
-    p.quads_per_frame = quads_per_frame;
-    p.stride = saddle_stride_bytes;
-    p.d_saddles = q.saddles;
-    p.d_counts = d_counts;
-    p.d_frame_table = q.frame_table;
-    p.d_point_status = d_point_status;
-    p.d_quads = d_quads;
-    p.d_n_quads = d_n_quads;
-    p.d_status = d_status;
-    p.d_quad_points = d_quad_points;
+    if (!l.saddles_per_frame || !l.quads_per_frame || (seeds_per_frame && !*seeds_per_frame))
+        return fail(det, AGX_ERR_ARG, seeds_per_frame ? "saddles_per_frame, seeds_per_frame and quads_per_frame must be > 0"
+                                                      : "saddles_per_frame and quads_per_frame must be > 0");
+    if (l.d_counts && l.d_frame_table) return fail(det, AGX_ERR_ARG, "d_counts and d_frame_table: at most one of them");
+    if (const int rc = own()) return rc;
+    if (((uintptr_t)l.d_saddles | (uintptr_t)l.d_counts | (uintptr_t)l.d_frame_table | (uintptr_t)l.d_point_status | (uintptr_t)l.d_quads |
+         (uintptr_t)l.d_quad_points | (uintptr_t)l.d_n_quads | (uintptr_t)l.d_status | own_ptrs) & 3)
+        return fail(det, AGX_ERR_ARG, seeds_per_frame ? "saddles, counts, frame table, point statuses, seeds and the results must be 4-byte aligned"
+                                                      : "saddles, counts, frame table, point statuses and the results must be 4-byte aligned");
+    if (l.n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
+    if ((size_t)l.n_frames * l.quads_per_frame >= ((size_t)1 << 27)) return fail(det, AGX_ERR_ARG, "at most 2^27 - 1 quad rows per batch");
+    if (seeds_per_frame && (size_t)l.n_frames * *seeds_per_frame >= ((size_t)1 << 27))
+        return fail(det, AGX_ERR_ARG, "at most 2^27 - 1 seed rows per batch");
     return AGX_OK;
 }
 
-int agx::find_boards_fetch_impl(agx_detector *det, uint32_t *quads, float *quad_points, uint32_t *n_quads, uint32_t *status, int n_threads)
+// Behind the checks: this batch replaces the one in flight; host_only = the kernel will only mark the frames
+int begin_list_batch(agx_detector *det, bool &host_only)
 {
-    if (!det) return AGX_ERR_ARG;
-    if (const int other = refuse_other_batch(det, BATCH_FIND)) return other;
-    const FindPending b = det->find;
-    if (b.results == RESULTS_HOST && (!quads || !n_quads || !status)) return fail(det, AGX_ERR_ARG, "null output");  // (the batch stays in flight)
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);
+    host_only = device_tail_mode(det) == 0;
+    if (!host_only && tail_prepare(det)) return fail(det, AGX_ERR_HIP, "the device tail's set-up (code list, kernel attributes)");
+    return AGX_OK;
+}
+
+void fill_list_args(FindBoardsArgs &q, const agx_detector *det, const ListArgs &l, bool host_only)
+{
+    q.saddles = static_cast<const uint8_t *>(l.d_saddles);
+    q.stride = (uint32_t)l.saddle_stride_bytes;
+    q.n_frames = l.n_frames;
+    q.saddles_per_frame = l.saddles_per_frame;
+    q.counts = l.d_counts;
+    q.frame_table = static_cast<const uint32_t *>(l.d_frame_table);
+    q.point_status = l.d_point_status;
+    q.quads_per_frame = l.quads_per_frame;
+    q.quads = l.d_quads;
+    q.quad_points = l.d_quad_points;
+    q.n_quads = l.d_n_quads;
+    q.status = l.d_status;
+    q.debug_band = (float)det->tail_debug_band_mdeg * 1e-3f;
+    q.host_only = host_only ? 1 : 0;
+}
+
+void fill_list_pending(FindPending &p, const ListArgs &l, int results, const uint32_t *d_seed_counts, uint32_t seeds_per_frame)
+{
+    p.results = results;
+    p.n_frames = l.n_frames;
+    p.saddles_per_frame = l.saddles_per_frame;
+    p.quads_per_frame = l.quads_per_frame;
+    p.stride = l.saddle_stride_bytes;
+    p.d_saddles = static_cast<const uint8_t *>(l.d_saddles);
+    p.d_counts = l.d_counts;
+    p.d_frame_table = static_cast<const uint32_t *>(l.d_frame_table);
+    p.d_point_status = l.d_point_status;
+    p.d_quads = l.d_quads;
+    p.d_n_quads = l.d_n_quads;
+    p.d_status = l.d_status;
+    p.d_quad_points = l.d_quad_points;
+    p.d_seed_counts = d_seed_counts;
+    p.seeds_per_frame = seeds_per_frame;
+}
+
+bool to_host(void *dst, const void *src, size_t bytes, hipStream_t stream)
+{
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) == hipSuccess;
+}
+bool to_device(void *dst, const void *src, size_t bytes, hipStream_t stream)
+{
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) == hipSuccess;
+}
+
+// What differs between the three fetches.  Per stage: its batch record (Pending), where its counters are (WHICH) and its name
+// in messages; a handed-back frame's extra inputs and outputs on the host (Frame); and three pieces --
+//   inputs_down(b, f, n_seeds, x, stream): the frame's extra inputs down (n_seeds: the frame's seeds by the batch's counts);
+//   run(b, slots, stride, count, words, rows, x): its *_in_slots, on the pool;
+//   outputs_up(b, f, status, x, stream): the extra outputs up, and when.  What it copies from lives in x.
+struct FindStage {
+    using Pending = FindPending;
+    static constexpr int WHICH = LIST_FIND;
+    static constexpr const char *NAME = "agx_find_boards_fetch";
+    struct Frame {};
+    static bool inputs_down(const Pending &, size_t, size_t, Frame &, hipStream_t) { return true; }
+    static int run(const Pending &, const void *slots, size_t stride, uint32_t count, const uint32_t *words, std::vector<uint32_t> &rows, Frame &)
+    {
+        return find_board_in_slots(slots, stride, count, words, rows);
+    }
+    static bool outputs_up(const Pending &, size_t, uint32_t, const Frame &, hipStream_t) { return true; }
+};
+
+struct GrowStage {
+    using Pending = GrowPending;
+    static constexpr int WHICH = LIST_GROW;
+    static constexpr const char *NAME = "agx_grow_boards_fetch";
+    struct Frame {
+        std::vector<uint32_t> seeds, scores;  // [4 * n_seeds]; the seeds' scores
+        uint32_t best = 0;
+    };
+    static bool inputs_down(const Pending &b, size_t f, size_t n_seeds, Frame &x, hipStream_t stream)
+    {
+        x.seeds.resize(4 * n_seeds);
+        return !n_seeds || to_host(x.seeds.data(), b.d_seed_quads + f * b.seeds_per_frame * 4, 4 * n_seeds * sizeof(uint32_t), stream);
+    }
+    static int run(const Pending &b, const void *slots, size_t stride, uint32_t count, const uint32_t *words, std::vector<uint32_t> &rows, Frame &x)
+    {
+        const int st = grow_boards_in_slots(slots, stride, count, words, x.seeds.data(), (uint32_t)(x.seeds.size() / 4), b.spacing_ratio,
+                                            b.stop_score, b.flags, rows, x.scores, x.best);
+        if (st != AGX_BOARD_FOUND) x.scores.clear();  // (written for frames that have a board only)
+        return st;
+    }
+    static bool outputs_up(const Pending &b, size_t f, uint32_t status, const Frame &x, hipStream_t stream)
+    {
+        if (status != AGX_BOARD_FOUND && status != AGX_BOARD_CAPACITY) return true;
+        return (!b.d_seed_scores || x.scores.empty() ||
+                to_device(b.d_seed_scores + f * b.seeds_per_frame, x.scores.data(), x.scores.size() * sizeof(uint32_t), stream)) &&
+               (!b.d_best_seed || to_device(b.d_best_seed + f, &x.best, sizeof(uint32_t), stream));
+    }
+};
+
+struct InitStage {
+    using Pending = InitPending;
+    static constexpr int WHICH = LIST_INIT;
+    static constexpr const char *NAME = "agx_init_quads_fetch";
+    struct Frame {
+        std::vector<uint32_t> seeds, counts, taken;  // the caller's seeds; the quads of each seed; the seeds taken
+        uint32_t n_taken = 0;
+    };
+    static bool inputs_down(const Pending &b, size_t f, size_t n_seeds, Frame &x, hipStream_t stream)
+    {
+        if (!b.d_seed_saddles) return true;
+        x.seeds.resize(n_seeds);
+        return !n_seeds || to_host(x.seeds.data(), b.d_seed_saddles + f * b.seeds_per_frame, n_seeds * sizeof(uint32_t), stream);
+    }
+    static int run(const Pending &b, const void *slots, size_t stride, uint32_t count, const uint32_t *words, std::vector<uint32_t> &rows, Frame &x)
+    {
+        static const uint32_t no_seed = 0;  // (a non-null pointer for a frame without seeds: null asks for the reference's)
+        const uint32_t *sd = b.d_seed_saddles ? (x.seeds.empty() ? &no_seed : x.seeds.data()) : nullptr;
+        const int st = init_quads_in_slots(slots, stride, count, words, sd, (uint32_t)x.seeds.size(), b.seeds_per_frame, b.n_nearest, rows, x.counts,
+                                           x.taken);
+        x.n_taken = (uint32_t)x.taken.size();
+        return st;
+    }
+    // (an AGX_BOARD_INPUT frame has neither counts nor seeds taken; its n_seeds_out is 0 like every frame's without a list)
+    static bool outputs_up(const Pending &b, size_t f, uint32_t, const Frame &x, hipStream_t stream)
+    {
+        return (!b.d_seed_quad_counts || x.counts.empty() ||
+                to_device(b.d_seed_quad_counts + f * b.seeds_per_frame, x.counts.data(), x.counts.size() * sizeof(uint32_t), stream)) &&
+               (!b.d_seeds_out || x.taken.empty() ||
+                to_device(b.d_seeds_out + f * b.seeds_per_frame, x.taken.data(), x.taken.size() * sizeof(uint32_t), stream)) &&
+               (!b.d_n_seeds_out || to_device(b.d_n_seeds_out + f, &x.n_taken, sizeof(uint32_t), stream));
+    }
+};
+
+// The fetch of any of the three, behind its own checks: the statuses down; for the frames the kernel handed back
+// (AGX_BOARD_PENDING) their slots, status words and the stage's extra inputs down, the host form on the pool, the answers up --
+// rows, corner points, count and status, and the stage's extra outputs.  The batch is resolved by this call, whatever it returns.
+template <class Stage>
+int resolve_handed_back(agx_detector *det, const typename Stage::Pending b, int n_threads)
+{
+    const std::string name = Stage::NAME;
     HIP_TRY(det, hipSetDevice(det->device));
     det->batch = BATCH_NONE;  // resolved by this call, whatever it returns
-    det->last_find_frames = b.n_frames;
-    det->last_find_handed_back = 0;
+    det->last_list_frames[Stage::WHICH] = b.n_frames;
+    det->last_list_handed_back[Stage::WHICH] = 0;
     if (n_threads <= 0) n_threads = agx_host_parallelism();
     hipStream_t stream = det->stream;
-    const size_t n = (size_t)b.n_frames, qpf = b.quads_per_frame;
-    int rc = AGX_OK;
+    const size_t n = (size_t)b.n_frames, qpf = b.quads_per_frame, spf = b.seeds_per_frame, stride = b.stride;
     try {
         std::vector<uint32_t> h_status(n), h_count(n, 0u);
-        if (hipMemcpyAsync(h_status.data(), b.d_status, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipStreamSynchronize(stream) != hipSuccess)
-            return fail(det, AGX_ERR_HIP, "agx_find_boards_fetch: copy / wait");
+        if (!to_host(h_status.data(), b.d_status, n * sizeof(uint32_t), stream) || hipStreamSynchronize(stream) != hipSuccess)
+            return fail(det, AGX_ERR_HIP, name + ": copy / wait");
         std::vector<int> pending;
         for (size_t f = 0; f < n; ++f)
             if (h_status[f] == AGX_BOARD_PENDING) pending.push_back((int)f);
-        det->last_find_handed_back = (int)pending.size();
-        // the handed-back frames: their slots (and status words) down, the host form on the pool, the answers up
-        std::vector<std::vector<uint8_t>> slots(pending.size());
-        std::vector<std::vector<uint32_t>> words(pending.size()), rows(pending.size());
-        std::vector<std::vector<float>> pts(pending.size());
-        if (!pending.empty()) {
-            WorkerPool *pool = worker_pool(det, n_threads);
-            if (!pool) return fail(det, AGX_ERR_ARG, "n_threads");
-            std::vector<uint32_t> own(b.d_frame_table ? 4 * n : (b.d_counts ? n : 0));  // the frames' own slots: table entries or counts
-            if (!own.empty() &&
-                (hipMemcpyAsync(own.data(), b.d_frame_table ? b.d_frame_table : b.d_counts, own.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-                 hipStreamSynchronize(stream) != hipSuccess))
-                return fail(det, AGX_ERR_HIP, "agx_find_boards_fetch: the frames' counts");
-            bool ok = true;
-            std::vector<char> no_list(pending.size(), 0);
-            for (size_t k = 0; k < pending.size() && ok; ++k) {
-                const size_t f = (size_t)pending[k];
-                size_t first = f * b.saddles_per_frame, count = b.saddles_per_frame;
-                if (b.d_frame_table) {
-                    count = own[4 * f];
-                    first = own[4 * f + 1];
-                    if (own[4 * f + 2] & 7u) {  // an overflow bit: there is no list (the kernel says so itself unless it read nothing)
-                        no_list[k] = 1;
-                        continue;
-                    }
-                } else if (b.d_counts) {
-                    count = std::min<size_t>(own[f], b.saddles_per_frame);
+        det->last_list_handed_back[Stage::WHICH] = (int)pending.size();
+        if (pending.empty()) return AGX_OK;
+        WorkerPool *pool = worker_pool(det, n_threads);
+        if (!pool) return fail(det, AGX_ERR_ARG, "n_threads");
+        const size_t np = pending.size();
+        std::vector<std::vector<uint8_t>> slots(np);
+        std::vector<std::vector<uint32_t>> words(np), rows(np);
+        std::vector<std::vector<float>> pts(np);
+        std::vector<typename Stage::Frame> extra(np);
+        // the frames' own slots (table entries or counts) and seed counts
+        std::vector<uint32_t> own(b.d_frame_table ? 4 * n : (b.d_counts ? n : 0)), seed_counts(b.d_seed_counts ? n : 0);
+        bool ok = own.empty() || to_host(own.data(), b.d_frame_table ? b.d_frame_table : b.d_counts, own.size() * sizeof(uint32_t), stream);
+        if (ok && !seed_counts.empty()) ok = to_host(seed_counts.data(), b.d_seed_counts, n * sizeof(uint32_t), stream);
+        if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, name + ": the frames' counts");
+        std::vector<char> no_list(np, 0);
+        for (size_t k = 0; k < np && ok; ++k) {
+            const size_t f = (size_t)pending[k];
+            size_t first = f * b.saddles_per_frame, count = b.saddles_per_frame;
+            if (b.d_frame_table) {
+                count = own[4 * f];
+                first = own[4 * f + 1];
+                if (own[4 * f + 2] & 7u) {  // an overflow bit: there is no list (the kernel says so itself unless it read nothing)
+                    no_list[k] = 1;
+                    continue;
                 }
-                if (!count) continue;
-                slots[k].resize((count - 1) * b.stride + sizeof(agx_saddle));
-                ok = hipMemcpyAsync(slots[k].data(), b.d_saddles + first * b.stride, slots[k].size(), hipMemcpyDeviceToHost, stream) == hipSuccess;
-                if (ok && b.d_point_status) {
-                    words[k].resize(count);
-                    ok = hipMemcpyAsync(words[k].data(), b.d_point_status + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
-                }
+            } else if (b.d_counts) {
+                count = std::min<size_t>(own[f], b.saddles_per_frame);
             }
-            if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, "agx_find_boards_fetch: the handed-back frames' lists");
-            std::atomic<bool> nomem{false};
-            const bool want_pts = b.d_quad_points != nullptr;
-            try {
-            for (size_t k = 0; k < pending.size(); ++k) {
+            ok = Stage::inputs_down(b, f, b.d_seed_counts ? std::min<size_t>(seed_counts[f], spf) : spf, extra[k], stream);
+            if (!count) continue;
+            slots[k].resize((count - 1) * stride + sizeof(agx_saddle));
+            ok = ok && to_host(slots[k].data(), b.d_saddles + first * stride, slots[k].size(), stream);
+            if (ok && b.d_point_status) {
+                words[k].resize(count);
+                ok = to_host(words[k].data(), b.d_point_status + first, count * sizeof(uint32_t), stream);
+            }
+        }
+        if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, name + ": the handed-back frames' lists");
+        std::atomic<bool> nomem{false};
+        const bool want_pts = b.d_quad_points != nullptr;
+        try {
+            for (size_t k = 0; k < np; ++k) {
                 const size_t f = (size_t)pending[k];
                 if (no_list[k]) {
                     h_status[f] = AGX_BOARD_INPUT;
                     continue;
                 }
-                const size_t stride = b.stride;
-                pool->submit([&, k, f, stride, want_pts] {
+                pool->submit([&, k, f] {
                     try {
                         const uint32_t count = slots[k].empty() ? 0u : (uint32_t)((slots[k].size() - sizeof(agx_saddle)) / stride + 1);
-                        const int st = find_board_in_slots(slots[k].data(), stride, count, words[k].empty() ? nullptr : words[k].data(), rows[k]);
-                        uint32_t nq = (uint32_t)(rows[k].size() / 4);
+                        const int st = Stage::run(b, slots[k].data(), stride, count, words[k].empty() ? nullptr : words[k].data(), rows[k], extra[k]);
+                        const uint32_t nq = (uint32_t)(rows[k].size() / 4);
                         h_status[f] = (uint32_t)st;
                         if (st == AGX_BOARD_FOUND && nq > qpf) {
                             h_status[f] = AGX_BOARD_CAPACITY;
@@ -1374,49 +1485,97 @@ int agx::find_boards_fetch_impl(agx_detector *det, uint32_t *quads, float *quad_
                     }
                 });
             }
-            } catch (...) {  // a task could not be queued: the ones that were read this call's vectors
-                (void)pool->wait();
-                throw;
-            }
-            if (!pool->wait() || nomem.load()) return fail(det, AGX_ERR_NOMEM, "agx_find_boards_fetch: the host form");
-            for (size_t k = 0; k < pending.size() && ok; ++k) {
-                const size_t f = (size_t)pending[k];
-                if (!rows[k].empty())
-                    ok = hipMemcpyAsync(b.d_quads + f * qpf * 4, rows[k].data(), rows[k].size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess &&
-                         (!want_pts || hipMemcpyAsync(b.d_quad_points + f * qpf * 8, pts[k].data(), pts[k].size() * sizeof(float), hipMemcpyHostToDevice, stream) == hipSuccess);
-                ok = ok && hipMemcpyAsync(b.d_n_quads + f, &h_count[f], sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess &&
-                     hipMemcpyAsync(b.d_status + f, &h_status[f], sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess;
-            }
-            if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, "agx_find_boards_fetch: the host form's answers to the device");
+        } catch (...) {  // a task could not be queued: the ones that were read this call's vectors
+            (void)pool->wait();
+            throw;
         }
-        // the caller's host arrays: counts and statuses, and the rows below each frame's count
-        if (quads || quad_points || n_quads || status) {
-            std::vector<uint32_t> h_quads(quads ? n * qpf * 4 : 0);
-            std::vector<float> h_pts(quad_points && b.d_quad_points ? n * qpf * 8 : 0);
-            if (quad_points && !b.d_quad_points) return fail(det, AGX_ERR_ARG, "quad_points: the batch was enqueued without d_quad_points");
-            bool ok = hipMemcpyAsync(h_count.data(), b.d_n_quads, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
-                      hipMemcpyAsync(h_status.data(), b.d_status, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
-            if (ok && quads) ok = hipMemcpyAsync(h_quads.data(), b.d_quads, h_quads.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
-            if (ok && quad_points) ok = hipMemcpyAsync(h_pts.data(), b.d_quad_points, h_pts.size() * sizeof(float), hipMemcpyDeviceToHost, stream) == hipSuccess;
-            if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, "agx_find_boards_fetch: copy / wait");
-            for (size_t f = 0; f < n; ++f) {
-                if (n_quads) n_quads[f] = h_count[f];
-                if (status) status[f] = h_status[f];
-                if (h_status[f] != AGX_BOARD_FOUND || !h_count[f]) continue;
-                const size_t nq = std::min<size_t>(h_count[f], qpf);
-                if (quads) std::memcpy(quads + f * qpf * 4, h_quads.data() + f * qpf * 4, nq * 4 * sizeof(uint32_t));
-                if (quad_points) std::memcpy(quad_points + f * qpf * 8, h_pts.data() + f * qpf * 8, nq * 8 * sizeof(float));
-            }
+        if (!pool->wait() || nomem.load()) return fail(det, AGX_ERR_NOMEM, name + ": the host form");
+        for (size_t k = 0; k < np && ok; ++k) {
+            const size_t f = (size_t)pending[k];
+            if (!rows[k].empty())
+                ok = to_device(b.d_quads + f * qpf * 4, rows[k].data(), rows[k].size() * sizeof(uint32_t), stream) &&
+                     (!want_pts || to_device(b.d_quad_points + f * qpf * 8, pts[k].data(), pts[k].size() * sizeof(float), stream));
+            ok = ok && Stage::outputs_up(b, f, h_status[f], extra[k], stream) && to_device(b.d_n_quads + f, &h_count[f], sizeof(uint32_t), stream) &&
+                 to_device(b.d_status + f, &h_status[f], sizeof(uint32_t), stream);
         }
+        if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, name + ": the host form's answers to the device");
     } catch (...) {
-        rc = fail(det, AGX_ERR_NOMEM, "agx_find_boards_fetch: host memory");
+        return fail(det, AGX_ERR_NOMEM, name + ": host memory");
     }
-    return rc;
+    return AGX_OK;
+}
+}  // namespace
+
+// ---- agx_find_boards_enqueue / _fetch: try_find_best_board (src/detector.rs:588-639) of caller-given saddle lists: k_find_boards ----
+int agx::find_boards_enqueue_impl(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
+                                  const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status,
+                                  uint32_t quads_per_frame, uint32_t *d_quads, float *d_quad_points, uint32_t *d_n_quads, uint32_t *d_status)
+{
+    if (!det) return AGX_ERR_ARG;
+    ListArgs l{d_saddles, saddle_stride_bytes, n_frames, saddles_per_frame, d_counts, d_frame_table, d_point_status,
+               quads_per_frame, d_quads, d_quad_points, d_n_quads, d_status};
+    if (const int rc = check_list_args(det, l, nullptr, 0, [&] {
+            if ((d_quads == nullptr) != (d_n_quads == nullptr) || (d_quads == nullptr) != (d_status == nullptr))
+                return fail(det, AGX_ERR_ARG, "d_quads, d_n_quads and d_status: all or none");
+            return (int)AGX_OK;
+        }))
+        return rc;
+    bool host_only;
+    if (const int rc = begin_list_batch(det, host_only)) return rc;
+    int results = RESULTS_CALLER;
+    if (!d_quads) {
+        const size_t rows = (size_t)n_frames * quads_per_frame;
+        l.d_quads = static_cast<uint32_t *>(side_ensure(det, SB_FIND_QUADS, rows * 4 * sizeof(uint32_t), 0));
+        l.d_n_quads = static_cast<uint32_t *>(side_ensure(det, SB_FIND_COUNTS, (size_t)n_frames * sizeof(uint32_t), 0));
+        l.d_status = static_cast<uint32_t *>(side_ensure(det, SB_FIND_STATUS, (size_t)n_frames * sizeof(uint32_t), 0));
+        if (!d_quad_points) l.d_quad_points = static_cast<float *>(side_ensure(det, SB_FIND_POINTS, rows * 8 * sizeof(float), 0));
+        if (!l.d_quads || !l.d_n_quads || !l.d_status || !l.d_quad_points) return fail(det, AGX_ERR_HIP, "hipMalloc: board quads");
+        results = RESULTS_HOST;
+    }
+    FindBoardsArgs q{};
+    fill_list_args(q, det, l, host_only);
+    const hipError_t e = (hipError_t)launch_find_boards(q, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_find_boards: ") + hipGetErrorString(e));
+    det->batch = BATCH_FIND;
+    fill_list_pending(det->find, l, results, nullptr, 0);
+    return AGX_OK;
 }
 
-// ---- agx_grow_boards_enqueue / _fetch: boards from caller-given seed quads (src/board.rs:26-112) over the same lists ----------------
-// k_grow_boards on the detector's stream, one workgroup per frame; everything in the caller's device arrays.  The list arguments
-// are agx_find_boards_enqueue's and are refused in its words.
+int agx::find_boards_fetch_impl(agx_detector *det, uint32_t *quads, float *quad_points, uint32_t *n_quads, uint32_t *status, int n_threads)
+{
+    if (!det) return AGX_ERR_ARG;
+    if (const int other = refuse_other_batch(det, BATCH_FIND)) return other;
+    const FindPending b = det->find;
+    if (b.results == RESULTS_HOST && (!quads || !n_quads || !status)) return fail(det, AGX_ERR_ARG, "null output");  // (the batch stays in flight)
+    if (const int rc = resolve_handed_back<FindStage>(det, b, n_threads)) return rc;
+    // the caller's host arrays (also where no frame was handed back): counts and statuses, and the rows below each frame's count
+    if (!(quads || quad_points || n_quads || status)) return AGX_OK;
+    if (quad_points && !b.d_quad_points) return fail(det, AGX_ERR_ARG, "quad_points: the batch was enqueued without d_quad_points");
+    hipStream_t stream = det->stream;
+    const size_t n = (size_t)b.n_frames, qpf = b.quads_per_frame;
+    try {
+        std::vector<uint32_t> h_status(n), h_count(n), h_quads(quads ? n * qpf * 4 : 0);
+        std::vector<float> h_pts(quad_points ? n * qpf * 8 : 0);
+        bool ok = to_host(h_count.data(), b.d_n_quads, n * sizeof(uint32_t), stream) && to_host(h_status.data(), b.d_status, n * sizeof(uint32_t), stream);
+        if (ok && quads) ok = to_host(h_quads.data(), b.d_quads, h_quads.size() * sizeof(uint32_t), stream);
+        if (ok && quad_points) ok = to_host(h_pts.data(), b.d_quad_points, h_pts.size() * sizeof(float), stream);
+        if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, "agx_find_boards_fetch: copy / wait");
+        for (size_t f = 0; f < n; ++f) {
+            if (n_quads) n_quads[f] = h_count[f];
+            if (status) status[f] = h_status[f];
+            if (h_status[f] != AGX_BOARD_FOUND || !h_count[f]) continue;
+            const size_t nq = std::min<size_t>(h_count[f], qpf);
+            if (quads) std::memcpy(quads + f * qpf * 4, h_quads.data() + f * qpf * 4, nq * 4 * sizeof(uint32_t));
+            if (quad_points) std::memcpy(quad_points + f * qpf * 8, h_pts.data() + f * qpf * 8, nq * 8 * sizeof(float));
+        }
+    } catch (...) {
+        return fail(det, AGX_ERR_NOMEM, "agx_find_boards_fetch: host memory");
+    }
+    return AGX_OK;
+}
+
+// ---- agx_grow_boards_enqueue / _fetch: boards from caller-given seed quads (src/board.rs:26-112) over the same lists: k_grow_boards ----
+// Everything in the caller's device arrays.
 int agx::grow_boards_enqueue_impl(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
                                   const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status, const uint32_t *d_seed_quads,
                                   uint32_t seeds_per_frame, const uint32_t *d_seed_counts, float spacing_ratio, uint32_t stop_score, int flags,
@@ -1424,42 +1583,22 @@ int agx::grow_boards_enqueue_impl(agx_detector *det, const void *d_saddles, size
                                   uint32_t *d_seed_scores, uint32_t *d_best_seed)
 {
     if (!det) return AGX_ERR_ARG;
-    if (!d_saddles || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null saddles or n_frames <= 0");
-    if (saddle_stride_bytes < 20 || (saddle_stride_bytes & 3) || saddle_stride_bytes > 0x7fffffffu)
-        return fail(det, AGX_ERR_ARG, "saddle_stride_bytes must be a multiple of 4 and at least 20");
-    if (!saddles_per_frame || !quads_per_frame || !seeds_per_frame)
-        return fail(det, AGX_ERR_ARG, "saddles_per_frame, seeds_per_frame and quads_per_frame must be > 0");
-    if (d_counts && d_frame_table) return fail(det, AGX_ERR_ARG, "d_counts and d_frame_table: at most one of them");
-    if (!d_quads || !d_n_quads || !d_status || !d_seed_quads) return fail(det, AGX_ERR_ARG, "d_seed_quads, d_quads, d_n_quads and d_status are required");
-    if (!std::isfinite(spacing_ratio) || !(1.0f + spacing_ratio > 0.0f))
-        return fail(det, AGX_ERR_ARG, "spacing_ratio must be finite with 1 + spacing_ratio > 0");
-    if (flags & ~AGX_GROW_FIX_MISSING) return fail(det, AGX_ERR_ARG, "flags: AGX_GROW_FIX_MISSING or 0");
-    if (((uintptr_t)d_saddles | (uintptr_t)d_counts | (uintptr_t)d_frame_table | (uintptr_t)d_point_status | (uintptr_t)d_quads |
-         (uintptr_t)d_quad_points | (uintptr_t)d_n_quads | (uintptr_t)d_status | (uintptr_t)d_seed_quads | (uintptr_t)d_seed_counts |
-         (uintptr_t)d_seed_scores | (uintptr_t)d_best_seed) & 3)
-        return fail(det, AGX_ERR_ARG, "saddles, counts, frame table, point statuses, seeds and the results must be 4-byte aligned");
-    if (n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
-    if ((size_t)n_frames * quads_per_frame >= ((size_t)1 << 27)) return fail(det, AGX_ERR_ARG, "at most 2^27 - 1 quad rows per batch");
-    if ((size_t)n_frames * seeds_per_frame >= ((size_t)1 << 27)) return fail(det, AGX_ERR_ARG, "at most 2^27 - 1 seed rows per batch");
-    HIP_TRY(det, hipSetDevice(det->device));
-    begin_batch(det);
-    const bool host_only = device_tail_mode(det) == 0;
-    if (!host_only && tail_prepare(det)) return fail(det, AGX_ERR_HIP, "the device tail's set-up (code list, kernel attributes)");
+    const ListArgs l{d_saddles, saddle_stride_bytes, n_frames, saddles_per_frame, d_counts, d_frame_table, d_point_status,
+                     quads_per_frame, d_quads, d_quad_points, d_n_quads, d_status};
+    const uintptr_t own_ptrs = (uintptr_t)d_seed_quads | (uintptr_t)d_seed_counts | (uintptr_t)d_seed_scores | (uintptr_t)d_best_seed;
+    if (const int rc = check_list_args(det, l, &seeds_per_frame, own_ptrs, [&] {
+            if (!d_quads || !d_n_quads || !d_status || !d_seed_quads)
+                return fail(det, AGX_ERR_ARG, "d_seed_quads, d_quads, d_n_quads and d_status are required");
+            if (!std::isfinite(spacing_ratio) || !(1.0f + spacing_ratio > 0.0f))
+                return fail(det, AGX_ERR_ARG, "spacing_ratio must be finite with 1 + spacing_ratio > 0");
+            if (flags & ~AGX_GROW_FIX_MISSING) return fail(det, AGX_ERR_ARG, "flags: AGX_GROW_FIX_MISSING or 0");
+            return (int)AGX_OK;
+        }))
+        return rc;
+    bool host_only;
+    if (const int rc = begin_list_batch(det, host_only)) return rc;
     GrowBoardsArgs q{};
-    q.saddles = static_cast<const uint8_t *>(d_saddles);
-    q.stride = (uint32_t)saddle_stride_bytes;
-    q.n_frames = n_frames;
-    q.saddles_per_frame = saddles_per_frame;
-    q.counts = d_counts;
-    q.frame_table = static_cast<const uint32_t *>(d_frame_table);
-    q.point_status = d_point_status;
-    q.quads_per_frame = quads_per_frame;
-    q.quads = d_quads;
-    q.quad_points = d_quad_points;
-    q.n_quads = d_n_quads;
-    q.status = d_status;
-    q.debug_band = (float)det->tail_debug_band_mdeg * 1e-3f;
-    q.host_only = host_only ? 1 : 0;
+    fill_list_args(q, det, l, host_only);
     q.seed_quads = d_seed_quads;
     q.seeds_per_frame = seeds_per_frame;
     q.seed_counts = d_seed_counts;
@@ -1472,22 +1611,8 @@ int agx::grow_boards_enqueue_impl(agx_detector *det, const void *d_saddles, size
     if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_grow_boards: ") + hipGetErrorString(e));
     det->batch = BATCH_GROW;
     GrowPending &p = det->grow;
-    p.results = RESULTS_CALLER;
-    p.n_frames = n_frames;
-    p.saddles_per_frame = saddles_per_frame;
-    p.quads_per_frame = quads_per_frame;
-    p.stride = saddle_stride_bytes;
-    p.d_saddles = q.saddles;
-    p.d_counts = d_counts;
-    p.d_frame_table = q.frame_table;
-    p.d_point_status = d_point_status;
-    p.d_quads = d_quads;
-    p.d_n_quads = d_n_quads;
-    p.d_status = d_status;
-    p.d_quad_points = d_quad_points;
+    fill_list_pending(p, l, RESULTS_CALLER, d_seed_counts, seeds_per_frame);
     p.d_seed_quads = d_seed_quads;
-    p.d_seed_counts = d_seed_counts;
-    p.seeds_per_frame = seeds_per_frame;
     p.stop_score = stop_score;
     p.spacing_ratio = spacing_ratio;
     p.flags = flags;
@@ -1496,132 +1621,15 @@ int agx::grow_boards_enqueue_impl(agx_detector *det, const void *d_saddles, size
     return AGX_OK;
 }
 
-// The handed-back frames as in agx_find_boards_fetch: their slots, status words and seeds down, the host form on the pool, the
-// answers up -- rows, count and status, and the seed scores and best seed of the frames that have a board.
 int agx::grow_boards_fetch_impl(agx_detector *det, int n_threads)
 {
     if (!det) return AGX_ERR_ARG;
     if (const int other = refuse_other_batch(det, BATCH_GROW)) return other;
-    const GrowPending b = det->grow;
-    HIP_TRY(det, hipSetDevice(det->device));
-    det->batch = BATCH_NONE;  // resolved by this call, whatever it returns
-    det->last_grow_frames = b.n_frames;
-    det->last_grow_handed_back = 0;
-    if (n_threads <= 0) n_threads = agx_host_parallelism();
-    hipStream_t stream = det->stream;
-    const size_t n = (size_t)b.n_frames, qpf = b.quads_per_frame, spf = b.seeds_per_frame;
-    int rc = AGX_OK;
-    try {
-        std::vector<uint32_t> h_status(n), h_count(n, 0u), h_best(n, 0u);
-        if (hipMemcpyAsync(h_status.data(), b.d_status, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipStreamSynchronize(stream) != hipSuccess)
-            return fail(det, AGX_ERR_HIP, "agx_grow_boards_fetch: copy / wait");
-        std::vector<int> pending;
-        for (size_t f = 0; f < n; ++f)
-            if (h_status[f] == AGX_BOARD_PENDING) pending.push_back((int)f);
-        det->last_grow_handed_back = (int)pending.size();
-        if (pending.empty()) return AGX_OK;
-        WorkerPool *pool = worker_pool(det, n_threads);
-        if (!pool) return fail(det, AGX_ERR_ARG, "n_threads");
-        std::vector<std::vector<uint8_t>> slots(pending.size());
-        std::vector<std::vector<uint32_t>> words(pending.size()), rows(pending.size()), seeds(pending.size()), scores(pending.size());
-        std::vector<std::vector<float>> pts(pending.size());
-        std::vector<uint32_t> own(b.d_frame_table ? 4 * n : (b.d_counts ? n : 0)), seed_counts(b.d_seed_counts ? n : 0);
-        bool ok = true;
-        if (!own.empty())
-            ok = hipMemcpyAsync(own.data(), b.d_frame_table ? b.d_frame_table : b.d_counts, own.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
-        if (ok && !seed_counts.empty())
-            ok = hipMemcpyAsync(seed_counts.data(), b.d_seed_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
-        if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, "agx_grow_boards_fetch: the frames' counts");
-        std::vector<char> no_list(pending.size(), 0);
-        for (size_t k = 0; k < pending.size() && ok; ++k) {
-            const size_t f = (size_t)pending[k];
-            size_t first = f * b.saddles_per_frame, count = b.saddles_per_frame;
-            if (b.d_frame_table) {
-                count = own[4 * f];
-                first = own[4 * f + 1];
-                if (own[4 * f + 2] & 7u) {  // an overflow bit: there is no list
-                    no_list[k] = 1;
-                    continue;
-                }
-            } else if (b.d_counts) {
-                count = std::min<size_t>(own[f], b.saddles_per_frame);
-            }
-            const size_t n_seeds = b.d_seed_counts ? std::min<size_t>(seed_counts[f], spf) : spf;
-            seeds[k].resize(4 * n_seeds);
-            if (n_seeds) ok = hipMemcpyAsync(seeds[k].data(), b.d_seed_quads + f * spf * 4, 4 * n_seeds * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
-            if (!count) continue;
-            slots[k].resize((count - 1) * b.stride + sizeof(agx_saddle));
-            ok = ok && hipMemcpyAsync(slots[k].data(), b.d_saddles + first * b.stride, slots[k].size(), hipMemcpyDeviceToHost, stream) == hipSuccess;
-            if (ok && b.d_point_status) {
-                words[k].resize(count);
-                ok = hipMemcpyAsync(words[k].data(), b.d_point_status + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
-            }
-        }
-        if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, "agx_grow_boards_fetch: the handed-back frames' lists");
-        std::atomic<bool> nomem{false};
-        const bool want_pts = b.d_quad_points != nullptr;
-        try {
-        for (size_t k = 0; k < pending.size(); ++k) {
-            const size_t f = (size_t)pending[k];
-            if (no_list[k]) {
-                h_status[f] = AGX_BOARD_INPUT;
-                continue;
-            }
-            const size_t stride = b.stride;
-            pool->submit([&, k, f, stride, want_pts] {
-                try {
-                    const uint32_t count = slots[k].empty() ? 0u : (uint32_t)((slots[k].size() - sizeof(agx_saddle)) / stride + 1);
-                    const int st = grow_boards_in_slots(slots[k].data(), stride, count, words[k].empty() ? nullptr : words[k].data(), seeds[k].data(),
-                                                        (uint32_t)(seeds[k].size() / 4), b.spacing_ratio, b.stop_score, b.flags, rows[k], scores[k],
-                                                        h_best[f]);
-                    const uint32_t nq = (uint32_t)(rows[k].size() / 4);
-                    h_status[f] = (uint32_t)st;
-                    if (st == AGX_BOARD_FOUND && nq > qpf) {
-                        h_status[f] = AGX_BOARD_CAPACITY;
-                        rows[k].clear();
-                    }
-                    h_count[f] = st == AGX_BOARD_FOUND ? nq : 0u;
-                    if (st != AGX_BOARD_FOUND) scores[k].clear();  // (written for frames that have a board only)
-                    if (want_pts)
-                        for (uint32_t s : rows[k]) {
-                            float xy[2];
-                            std::memcpy(xy, slots[k].data() + (size_t)s * stride, sizeof xy);
-                            pts[k].push_back(xy[0]);
-                            pts[k].push_back(xy[1]);
-                        }
-                } catch (...) {
-                    nomem.store(true);
-                }
-            });
-        }
-        } catch (...) {  // a task could not be queued: the ones that were read this call's vectors
-            (void)pool->wait();
-            throw;
-        }
-        if (!pool->wait() || nomem.load()) return fail(det, AGX_ERR_NOMEM, "agx_grow_boards_fetch: the host form");
-        for (size_t k = 0; k < pending.size() && ok; ++k) {
-            const size_t f = (size_t)pending[k];
-            const bool some = h_status[f] == AGX_BOARD_FOUND || h_status[f] == AGX_BOARD_CAPACITY;
-            if (!rows[k].empty())
-                ok = hipMemcpyAsync(b.d_quads + f * qpf * 4, rows[k].data(), rows[k].size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess &&
-                     (!want_pts || hipMemcpyAsync(b.d_quad_points + f * qpf * 8, pts[k].data(), pts[k].size() * sizeof(float), hipMemcpyHostToDevice, stream) == hipSuccess);
-            if (ok && some && b.d_seed_scores && !scores[k].empty())
-                ok = hipMemcpyAsync(b.d_seed_scores + f * spf, scores[k].data(), scores[k].size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess;
-            if (ok && some && b.d_best_seed) ok = hipMemcpyAsync(b.d_best_seed + f, &h_best[f], sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess;
-            ok = ok && hipMemcpyAsync(b.d_n_quads + f, &h_count[f], sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess &&
-                 hipMemcpyAsync(b.d_status + f, &h_status[f], sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess;
-        }
-        if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, "agx_grow_boards_fetch: the host form's answers to the device");
-    } catch (...) {
-        rc = fail(det, AGX_ERR_NOMEM, "agx_grow_boards_fetch: host memory");
-    }
-    return rc;
+    return resolve_handed_back<GrowStage>(det, det->grow, n_threads);
 }
 
-// ---- agx_init_quads_enqueue / _fetch: init_quads (src/detector.rs:543-586) of caller-given seed saddles over the same lists ------
-// k_init_quads on the detector's stream, one workgroup per frame; everything in the caller's device arrays.  The list arguments
-// are agx_find_boards_enqueue's and are refused in its words.
+// ---- agx_init_quads_enqueue / _fetch: init_quads (src/detector.rs:543-586) of caller-given seed saddles over the same lists: k_init_quads ----
+// Everything in the caller's device arrays.
 int agx::init_quads_enqueue_impl(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
                                  const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status, const uint32_t *d_seed_saddles,
                                  uint32_t seeds_per_frame, const uint32_t *d_seed_counts, uint32_t n_nearest, uint32_t quads_per_frame,
@@ -1629,41 +1637,21 @@ int agx::init_quads_enqueue_impl(agx_detector *det, const void *d_saddles, size_
                                  uint32_t *d_seeds_out, uint32_t *d_n_seeds_out)
 {
     if (!det) return AGX_ERR_ARG;
-    if (!d_saddles || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null saddles or n_frames <= 0");
-    if (saddle_stride_bytes < 20 || (saddle_stride_bytes & 3) || saddle_stride_bytes > 0x7fffffffu)
-        return fail(det, AGX_ERR_ARG, "saddle_stride_bytes must be a multiple of 4 and at least 20");
-    if (!saddles_per_frame || !quads_per_frame || !seeds_per_frame)
-        return fail(det, AGX_ERR_ARG, "saddles_per_frame, seeds_per_frame and quads_per_frame must be > 0");
-    if (d_counts && d_frame_table) return fail(det, AGX_ERR_ARG, "d_counts and d_frame_table: at most one of them");
-    if (!d_quads || !d_n_quads || !d_status) return fail(det, AGX_ERR_ARG, "d_quads, d_n_quads and d_status are required");
-    if (d_seed_counts && !d_seed_saddles) return fail(det, AGX_ERR_ARG, "d_seed_counts without d_seed_saddles");
-    if (n_nearest < 2 || n_nearest > 64) return fail(det, AGX_ERR_ARG, "n_nearest must be 2 .. 64");
-    if (((uintptr_t)d_saddles | (uintptr_t)d_counts | (uintptr_t)d_frame_table | (uintptr_t)d_point_status | (uintptr_t)d_quads |
-         (uintptr_t)d_quad_points | (uintptr_t)d_n_quads | (uintptr_t)d_status | (uintptr_t)d_seed_saddles | (uintptr_t)d_seed_counts |
-         (uintptr_t)d_seed_quad_counts | (uintptr_t)d_seeds_out | (uintptr_t)d_n_seeds_out) & 3)
-        return fail(det, AGX_ERR_ARG, "saddles, counts, frame table, point statuses, seeds and the results must be 4-byte aligned");
-    if (n_frames > 65535) return fail(det, AGX_ERR_ARG, "at most 65535 frames per batch");
-    if ((size_t)n_frames * quads_per_frame >= ((size_t)1 << 27)) return fail(det, AGX_ERR_ARG, "at most 2^27 - 1 quad rows per batch");
-    if ((size_t)n_frames * seeds_per_frame >= ((size_t)1 << 27)) return fail(det, AGX_ERR_ARG, "at most 2^27 - 1 seed rows per batch");
-    HIP_TRY(det, hipSetDevice(det->device));
-    begin_batch(det);
-    const bool host_only = device_tail_mode(det) == 0;
-    if (!host_only && tail_prepare(det)) return fail(det, AGX_ERR_HIP, "the device tail's set-up (code list, kernel attributes)");
+    const ListArgs l{d_saddles, saddle_stride_bytes, n_frames, saddles_per_frame, d_counts, d_frame_table, d_point_status,
+                     quads_per_frame, d_quads, d_quad_points, d_n_quads, d_status};
+    const uintptr_t own_ptrs = (uintptr_t)d_seed_saddles | (uintptr_t)d_seed_counts | (uintptr_t)d_seed_quad_counts | (uintptr_t)d_seeds_out |
+                               (uintptr_t)d_n_seeds_out;
+    if (const int rc = check_list_args(det, l, &seeds_per_frame, own_ptrs, [&] {
+            if (!d_quads || !d_n_quads || !d_status) return fail(det, AGX_ERR_ARG, "d_quads, d_n_quads and d_status are required");
+            if (d_seed_counts && !d_seed_saddles) return fail(det, AGX_ERR_ARG, "d_seed_counts without d_seed_saddles");
+            if (n_nearest < 2 || n_nearest > 64) return fail(det, AGX_ERR_ARG, "n_nearest must be 2 .. 64");
+            return (int)AGX_OK;
+        }))
+        return rc;
+    bool host_only;
+    if (const int rc = begin_list_batch(det, host_only)) return rc;
     InitQuadsArgs q{};
-    q.saddles = static_cast<const uint8_t *>(d_saddles);
-    q.stride = (uint32_t)saddle_stride_bytes;
-    q.n_frames = n_frames;
-    q.saddles_per_frame = saddles_per_frame;
-    q.counts = d_counts;
-    q.frame_table = static_cast<const uint32_t *>(d_frame_table);
-    q.point_status = d_point_status;
-    q.quads_per_frame = quads_per_frame;
-    q.quads = d_quads;
-    q.quad_points = d_quad_points;
-    q.n_quads = d_n_quads;
-    q.status = d_status;
-    q.debug_band = (float)det->tail_debug_band_mdeg * 1e-3f;
-    q.host_only = host_only ? 1 : 0;
+    fill_list_args(q, det, l, host_only);
     q.seed_saddles = d_seed_saddles;
     q.seeds_per_frame = seeds_per_frame;
     q.seed_counts = d_seed_counts;
@@ -1675,22 +1663,8 @@ int agx::init_quads_enqueue_impl(agx_detector *det, const void *d_saddles, size_
     if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_init_quads: ") + hipGetErrorString(e));
     det->batch = BATCH_INIT;
     InitPending &p = det->init;
-    p.results = RESULTS_CALLER;
-    p.n_frames = n_frames;
-    p.saddles_per_frame = saddles_per_frame;
-    p.quads_per_frame = quads_per_frame;
-    p.stride = saddle_stride_bytes;
-    p.d_saddles = q.saddles;
-    p.d_counts = d_counts;
-    p.d_frame_table = q.frame_table;
-    p.d_point_status = d_point_status;
-    p.d_quads = d_quads;
-    p.d_n_quads = d_n_quads;
-    p.d_status = d_status;
-    p.d_quad_points = d_quad_points;
+    fill_list_pending(p, l, RESULTS_CALLER, d_seed_counts, seeds_per_frame);
     p.d_seed_saddles = d_seed_saddles;
-    p.d_seed_counts = d_seed_counts;
-    p.seeds_per_frame = seeds_per_frame;
     p.n_nearest = n_nearest;
     p.d_seed_quad_counts = d_seed_quad_counts;
     p.d_seeds_out = d_seeds_out;
@@ -1698,131 +1672,11 @@ int agx::init_quads_enqueue_impl(agx_detector *det, const void *d_saddles, size_
     return AGX_OK;
 }
 
-// The handed-back frames as in agx_grow_boards_fetch: their slots, status words and seeds down, the host form on the pool, the
-// answers up -- rows, count and status, and (unless the frame is AGX_BOARD_INPUT) the per-seed counts and the seeds taken.
 int agx::init_quads_fetch_impl(agx_detector *det, int n_threads)
 {
     if (!det) return AGX_ERR_ARG;
     if (const int other = refuse_other_batch(det, BATCH_INIT)) return other;
-    const InitPending b = det->init;
-    HIP_TRY(det, hipSetDevice(det->device));
-    det->batch = BATCH_NONE;  // resolved by this call, whatever it returns
-    det->last_init_frames = b.n_frames;
-    det->last_init_handed_back = 0;
-    if (n_threads <= 0) n_threads = agx_host_parallelism();
-    hipStream_t stream = det->stream;
-    const size_t n = (size_t)b.n_frames, qpf = b.quads_per_frame, spf = b.seeds_per_frame;
-    int rc = AGX_OK;
-    try {
-        std::vector<uint32_t> h_status(n), h_count(n, 0u), h_seeds(n, 0u);
-        if (hipMemcpyAsync(h_status.data(), b.d_status, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipStreamSynchronize(stream) != hipSuccess)
-            return fail(det, AGX_ERR_HIP, "agx_init_quads_fetch: copy / wait");
-        std::vector<int> pending;
-        for (size_t f = 0; f < n; ++f)
-            if (h_status[f] == AGX_BOARD_PENDING) pending.push_back((int)f);
-        det->last_init_handed_back = (int)pending.size();
-        if (pending.empty()) return AGX_OK;
-        WorkerPool *pool = worker_pool(det, n_threads);
-        if (!pool) return fail(det, AGX_ERR_ARG, "n_threads");
-        std::vector<std::vector<uint8_t>> slots(pending.size());
-        std::vector<std::vector<uint32_t>> words(pending.size()), rows(pending.size()), seeds(pending.size()), counts(pending.size()), taken(pending.size());
-        std::vector<std::vector<float>> pts(pending.size());
-        std::vector<uint32_t> own(b.d_frame_table ? 4 * n : (b.d_counts ? n : 0)), seed_counts(b.d_seed_counts ? n : 0);
-        bool ok = true;
-        if (!own.empty())
-            ok = hipMemcpyAsync(own.data(), b.d_frame_table ? b.d_frame_table : b.d_counts, own.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
-        if (ok && !seed_counts.empty())
-            ok = hipMemcpyAsync(seed_counts.data(), b.d_seed_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
-        if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, "agx_init_quads_fetch: the frames' counts");
-        std::vector<char> no_list(pending.size(), 0);
-        for (size_t k = 0; k < pending.size() && ok; ++k) {
-            const size_t f = (size_t)pending[k];
-            size_t first = f * b.saddles_per_frame, count = b.saddles_per_frame;
-            if (b.d_frame_table) {
-                count = own[4 * f];
-                first = own[4 * f + 1];
-                if (own[4 * f + 2] & 7u) {  // an overflow bit: there is no list
-                    no_list[k] = 1;
-                    continue;
-                }
-            } else if (b.d_counts) {
-                count = std::min<size_t>(own[f], b.saddles_per_frame);
-            }
-            if (b.d_seed_saddles) {
-                const size_t n_seeds = b.d_seed_counts ? std::min<size_t>(seed_counts[f], spf) : spf;
-                seeds[k].resize(n_seeds);
-                if (n_seeds) ok = hipMemcpyAsync(seeds[k].data(), b.d_seed_saddles + f * spf, n_seeds * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
-            }
-            if (!count) continue;
-            slots[k].resize((count - 1) * b.stride + sizeof(agx_saddle));
-            ok = ok && hipMemcpyAsync(slots[k].data(), b.d_saddles + first * b.stride, slots[k].size(), hipMemcpyDeviceToHost, stream) == hipSuccess;
-            if (ok && b.d_point_status) {
-                words[k].resize(count);
-                ok = hipMemcpyAsync(words[k].data(), b.d_point_status + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
-            }
-        }
-        if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, "agx_init_quads_fetch: the handed-back frames' lists");
-        std::atomic<bool> nomem{false};
-        const bool want_pts = b.d_quad_points != nullptr, caller_seeds = b.d_seed_saddles != nullptr;
-        try {
-        for (size_t k = 0; k < pending.size(); ++k) {
-            const size_t f = (size_t)pending[k];
-            if (no_list[k]) {
-                h_status[f] = AGX_BOARD_INPUT;
-                continue;
-            }
-            const size_t stride = b.stride;
-            pool->submit([&, k, f, stride, want_pts, caller_seeds] {
-                try {
-                    const uint32_t count = slots[k].empty() ? 0u : (uint32_t)((slots[k].size() - sizeof(agx_saddle)) / stride + 1);
-                    static const uint32_t no_seed = 0;  // (a non-null pointer for a frame without seeds: null asks for the reference's)
-                    const uint32_t *sd = caller_seeds ? (seeds[k].empty() ? &no_seed : seeds[k].data()) : nullptr;
-                    const int st = init_quads_in_slots(slots[k].data(), stride, count, words[k].empty() ? nullptr : words[k].data(), sd,
-                                                       (uint32_t)seeds[k].size(), b.seeds_per_frame, b.n_nearest, rows[k], counts[k], taken[k]);
-                    const uint32_t nq = (uint32_t)(rows[k].size() / 4);
-                    h_status[f] = (uint32_t)st;
-                    if (st == AGX_BOARD_FOUND && nq > qpf) {
-                        h_status[f] = AGX_BOARD_CAPACITY;
-                        rows[k].clear();
-                    }
-                    h_count[f] = st == AGX_BOARD_FOUND ? nq : 0u;
-                    h_seeds[f] = (uint32_t)taken[k].size();
-                    if (want_pts)
-                        for (uint32_t s : rows[k]) {
-                            float xy[2];
-                            std::memcpy(xy, slots[k].data() + (size_t)s * stride, sizeof xy);
-                            pts[k].push_back(xy[0]);
-                            pts[k].push_back(xy[1]);
-                        }
-                } catch (...) {
-                    nomem.store(true);
-                }
-            });
-        }
-        } catch (...) {  // a task could not be queued: the ones that were read this call's vectors
-            (void)pool->wait();
-            throw;
-        }
-        if (!pool->wait() || nomem.load()) return fail(det, AGX_ERR_NOMEM, "agx_init_quads_fetch: the host form");
-        for (size_t k = 0; k < pending.size() && ok; ++k) {
-            const size_t f = (size_t)pending[k];
-            if (!rows[k].empty())
-                ok = hipMemcpyAsync(b.d_quads + f * qpf * 4, rows[k].data(), rows[k].size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess &&
-                     (!want_pts || hipMemcpyAsync(b.d_quad_points + f * qpf * 8, pts[k].data(), pts[k].size() * sizeof(float), hipMemcpyHostToDevice, stream) == hipSuccess);
-            if (ok && b.d_seed_quad_counts && !counts[k].empty())
-                ok = hipMemcpyAsync(b.d_seed_quad_counts + f * spf, counts[k].data(), counts[k].size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess;
-            if (ok && b.d_seeds_out && !taken[k].empty())
-                ok = hipMemcpyAsync(b.d_seeds_out + f * spf, taken[k].data(), taken[k].size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess;
-            if (ok && b.d_n_seeds_out) ok = hipMemcpyAsync(b.d_n_seeds_out + f, &h_seeds[f], sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess;
-            ok = ok && hipMemcpyAsync(b.d_n_quads + f, &h_count[f], sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess &&
-                 hipMemcpyAsync(b.d_status + f, &h_status[f], sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess;
-        }
-        if (!ok || hipStreamSynchronize(stream) != hipSuccess) return fail(det, AGX_ERR_HIP, "agx_init_quads_fetch: the host form's answers to the device");
-    } catch (...) {
-        rc = fail(det, AGX_ERR_NOMEM, "agx_init_quads_fetch: host memory");
-    }
-    return rc;
+    return resolve_handed_back<InitStage>(det, det->init, n_threads);
 }
 
 // The host tail of the frames `back` marks (1 handed back, 2 handed back as uncertain; without the device tail: every frame) of

@@ -973,12 +973,12 @@ int agx_detector_get_option(const agx_detector *det, const char *name, int *valu
     else if (!std::strcmp(name, "tail_threads")) *value = det->tail_threads;
     else if (!std::strcmp(name, "device_tail")) *value = det->device_tail;  // (-1: by the batch's size, where available)
     else if (!std::strcmp(name, "tail_debug_band")) *value = det->tail_debug_band_mdeg;
-    else if (!std::strcmp(name, "last_find_boards_frames")) *value = det->last_find_frames;  // (of the last agx_find_boards_fetch)
-    else if (!std::strcmp(name, "last_find_boards_handed_back")) *value = det->last_find_handed_back;
-    else if (!std::strcmp(name, "last_grow_boards_frames")) *value = det->last_grow_frames;  // (of the last agx_grow_boards_fetch)
-    else if (!std::strcmp(name, "last_grow_boards_handed_back")) *value = det->last_grow_handed_back;
-    else if (!std::strcmp(name, "last_init_quads_frames")) *value = det->last_init_frames;  // (of the last agx_init_quads_fetch)
-    else if (!std::strcmp(name, "last_init_quads_handed_back")) *value = det->last_init_handed_back;
+    else if (!std::strcmp(name, "last_find_boards_frames")) *value = det->last_list_frames[LIST_FIND];  // (of the last agx_find_boards_fetch)
+    else if (!std::strcmp(name, "last_find_boards_handed_back")) *value = det->last_list_handed_back[LIST_FIND];
+    else if (!std::strcmp(name, "last_grow_boards_frames")) *value = det->last_list_frames[LIST_GROW];  // (of the last agx_grow_boards_fetch)
+    else if (!std::strcmp(name, "last_grow_boards_handed_back")) *value = det->last_list_handed_back[LIST_GROW];
+    else if (!std::strcmp(name, "last_init_quads_frames")) *value = det->last_list_frames[LIST_INIT];  // (of the last agx_init_quads_fetch)
+    else if (!std::strcmp(name, "last_init_quads_handed_back")) *value = det->last_list_handed_back[LIST_INIT];
     else if (!std::strcmp(name, "last_device_tail_frames")) *value = det->last_tail_frames;
     else if (!std::strcmp(name, "last_device_tail_fallbacks")) *value = det->last_tail_fallbacks;
     else if (!std::strcmp(name, "last_device_tail_uncertain")) *value = det->last_tail_uncertain;  // (of them: an angle inside its guard band)
@@ -1617,6 +1617,19 @@ int agx_best_tag_tail(const uint64_t *bits, uint32_t n_slots, const uint32_t *st
 }  // extern "C"
 
 // ---- try_find_best_board of caller-given saddle lists (src/detector.rs:588-639; csrc/detect_batch.cpp, tail_kernels.hip) -------
+// The ending of agx_find_board_tail, agx_grow_board_tail and agx_init_quads_tail: the host form's rows (slot numbers, four per
+// quad) and status `st` for a caller with room for `cap` quads.  A board with more is AGX_BOARD_CAPACITY with its true count and
+// no rows.  -> the status written.
+static uint32_t tail_rows_out(int st, const std::vector<uint32_t> &rows, uint32_t *quads, uint32_t cap, uint32_t *n_quads, uint32_t *status)
+{
+    const uint32_t n = (uint32_t)(rows.size() / 4);
+    if (st == AGX_BOARD_FOUND && n > cap) st = AGX_BOARD_CAPACITY;
+    if (st == AGX_BOARD_FOUND && n) std::memcpy(quads, rows.data(), rows.size() * sizeof(uint32_t));
+    *n_quads = st == AGX_BOARD_FOUND || st == AGX_BOARD_CAPACITY ? n : 0u;
+    *status = (uint32_t)st;
+    return (uint32_t)st;
+}
+
 extern "C" {
 
 int agx_find_boards_enqueue(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
@@ -1668,12 +1681,8 @@ int agx_find_board_tail(const agx_saddle *saddles, uint32_t n_saddles, uint32_t 
     return agx_guard(nullptr, [&]() -> int {
     if (!n_quads || !status || (n_saddles && !saddles) || (cap && !quads)) return AGX_ERR_ARG;
     std::vector<uint32_t> rows;
-    uint32_t st = (uint32_t)find_board_in_slots(saddles, sizeof(agx_saddle), n_saddles, nullptr, rows);
-    const uint32_t n = (uint32_t)(rows.size() / 4);
-    if (st == AGX_BOARD_FOUND && n > cap) st = AGX_BOARD_CAPACITY;
-    if (st == AGX_BOARD_FOUND && n) std::memcpy(quads, rows.data(), rows.size() * sizeof(uint32_t));
-    *n_quads = st == AGX_BOARD_FOUND || st == AGX_BOARD_CAPACITY ? n : 0u;
-    *status = st;
+    const int st = find_board_in_slots(saddles, sizeof(agx_saddle), n_saddles, nullptr, rows);
+    tail_rows_out(st, rows, quads, cap, n_quads, status);
     return AGX_OK;
     });
 }
@@ -1705,13 +1714,9 @@ int agx_init_quads_tail(const agx_saddle *saddles, uint32_t n_saddles, const uin
     if (!n_quads || !status || (n_saddles && !saddles) || (cap && !quads) || (n_seeds && !seed_saddles)) return AGX_ERR_ARG;
     if (!max_seeds || n_nearest < 2 || n_nearest > 64) return AGX_ERR_ARG;
     std::vector<uint32_t> rows, counts, seeds;
-    uint32_t st = (uint32_t)init_quads_in_slots(saddles, sizeof(agx_saddle), n_saddles, point_status, seed_saddles, n_seeds, max_seeds, n_nearest,
-                                                rows, counts, seeds);
-    const uint32_t n = (uint32_t)(rows.size() / 4);
-    if (st == AGX_BOARD_FOUND && n > cap) st = AGX_BOARD_CAPACITY;
-    if (st == AGX_BOARD_FOUND && n) std::memcpy(quads, rows.data(), rows.size() * sizeof(uint32_t));
-    *n_quads = st == AGX_BOARD_FOUND || st == AGX_BOARD_CAPACITY ? n : 0u;
-    *status = st;
+    const uint32_t st = tail_rows_out(init_quads_in_slots(saddles, sizeof(agx_saddle), n_saddles, point_status, seed_saddles, n_seeds, max_seeds,
+                                                          n_nearest, rows, counts, seeds),
+                                      rows, quads, cap, n_quads, status);
     if (n_seeds_out) *n_seeds_out = (uint32_t)seeds.size();
     if (st != AGX_BOARD_INPUT) {
         if (seed_quad_counts) std::memcpy(seed_quad_counts, counts.data(), counts.size() * sizeof(uint32_t));
@@ -1749,14 +1754,10 @@ int agx_grow_board_tail(const agx_saddle *saddles, uint32_t n_saddles, const uin
     if (!std::isfinite(spacing_ratio) || !(1.0f + spacing_ratio > 0.0f) || (flags & ~AGX_GROW_FIX_MISSING)) return AGX_ERR_ARG;
     std::vector<uint32_t> rows, scores;
     uint32_t best = 0;
-    uint32_t st = (uint32_t)grow_boards_in_slots(saddles, sizeof(agx_saddle), n_saddles, point_status, seed_quads, n_seeds, spacing_ratio, stop_score,
-                                                 flags, rows, scores, best);
-    const uint32_t n = (uint32_t)(rows.size() / 4);
-    if (st == AGX_BOARD_FOUND && n > cap) st = AGX_BOARD_CAPACITY;
-    if (st == AGX_BOARD_FOUND && n) std::memcpy(quads, rows.data(), rows.size() * sizeof(uint32_t));
+    const uint32_t st = tail_rows_out(grow_boards_in_slots(saddles, sizeof(agx_saddle), n_saddles, point_status, seed_quads, n_seeds, spacing_ratio,
+                                                           stop_score, flags, rows, scores, best),
+                                      rows, quads, cap, n_quads, status);
     const bool some = st == AGX_BOARD_FOUND || st == AGX_BOARD_CAPACITY;
-    *n_quads = some ? n : 0u;
-    *status = st;
     if (some && seed_scores && n_seeds) std::memcpy(seed_scores, scores.data(), (size_t)n_seeds * sizeof(uint32_t));
     if (some && best_seed) *best_seed = best;
     return AGX_OK;

@@ -91,6 +91,10 @@ struct DecodePending {
     const uint32_t *d_counts = nullptr;  // the caller's per-frame counts (RESULTS_HOST: the fetch copies only the slots that were written)
 };
 
+// The three stages over caller-given saddle lists (agx_find_boards_*, agx_grow_boards_*, agx_init_quads_*), as the handle's
+// per-stage records are indexed
+enum { LIST_FIND, LIST_GROW, LIST_INIT, LIST_STAGES };
+
 // The fetch reads the inputs again for the frames the kernel handed back (AGX_BOARD_PENDING).
 struct FindPending {
     int results = 0;  // RESULTS_HOST: in SB_FIND_QUADS / _COUNTS / _STATUS, or RESULTS_CALLER
@@ -101,12 +105,15 @@ struct FindPending {
     const uint32_t *d_counts = nullptr, *d_frame_table = nullptr, *d_point_status = nullptr;
     uint32_t *d_quads = nullptr, *d_n_quads = nullptr, *d_status = nullptr;
     float *d_quad_points = nullptr;  // the caller's, SB_FIND_POINTS (RESULTS_HOST without the caller's), or null
+    // the stages with seeds (GrowPending, InitPending): frame f has min(d_seed_counts[f], seeds_per_frame) of them, or seeds_per_frame
+    const uint32_t *d_seed_counts = nullptr;
+    uint32_t seeds_per_frame = 0;
 };
 
 // FindPending's list and result arrays (always RESULTS_CALLER) and what the host form needs besides
 struct GrowPending : FindPending {
-    const uint32_t *d_seed_quads = nullptr, *d_seed_counts = nullptr;
-    uint32_t seeds_per_frame = 0, stop_score = 0;
+    const uint32_t *d_seed_quads = nullptr;
+    uint32_t stop_score = 0;
     float spacing_ratio = 0.3f;
     int flags = 0;
     uint32_t *d_seed_scores = nullptr, *d_best_seed = nullptr;
@@ -114,8 +121,8 @@ struct GrowPending : FindPending {
 
 // FindPending's list and result arrays (always RESULTS_CALLER) and the seeds
 struct InitPending : FindPending {
-    const uint32_t *d_seed_saddles = nullptr, *d_seed_counts = nullptr;
-    uint32_t seeds_per_frame = 0, n_nearest = 50;
+    const uint32_t *d_seed_saddles = nullptr;
+    uint32_t n_nearest = 50;
     uint32_t *d_seed_quad_counts = nullptr, *d_seeds_out = nullptr, *d_n_seeds_out = nullptr;
 };
 
@@ -308,12 +315,10 @@ struct agx_detector {
     agx::DecodePending decode;          // BATCH_DECODE: what agx_decode_quads_fetch needs of it
     std::vector<uint64_t> decode_host;  // its host staging when per-frame counts were given (bits, tags, statuses, counts)
     agx::FindPending find;              // BATCH_FIND: what agx_find_boards_fetch needs of it
-    int last_find_frames = 0, last_find_handed_back = 0;  // of the last agx_find_boards_fetch
+    int last_list_frames[agx::LIST_STAGES]{}, last_list_handed_back[agx::LIST_STAGES]{};  // of each stage's last fetch (LIST_*)
     agx::ClustersPending clusters;      // BATCH_CLUSTERS: what agx_clusters_fetch needs of it
     agx::GrowPending grow;              // BATCH_GROW: what agx_grow_boards_fetch needs of it
-    int last_grow_frames = 0, last_grow_handed_back = 0;  // of the last agx_grow_boards_fetch
     agx::InitPending init;              // BATCH_INIT: what agx_init_quads_fetch needs of it
-    int last_init_frames = 0, last_init_handed_back = 0;  // of the last agx_init_quads_fetch
     int last_extra_us[agx::XT_COUNT]{};  // harvest_events: the XT_* launches' last times (profiling level 2)
 
     std::string last_error;

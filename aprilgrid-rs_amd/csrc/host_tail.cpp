@@ -1323,25 +1323,50 @@ int decode_quad(const FamilyInfo &fam, const uint8_t *luma8, uint32_t w, uint32_
     return AGX_QUAD_DECODED;
 }
 
+namespace {
+// The listed saddles of one frame's slots (floats x, y, k, theta, phi every `stride` bytes): those point_status admits (null: all),
+// in slot order.
+struct SlotList {
+    std::vector<agx_saddle> list;
+    std::vector<uint32_t> slot_of;  // list position -> slot
+    std::vector<int> pos_of;        // slot -> list position, -1: not listed
+
+    // false: a listed x, y or theta is not finite -- the frame is AGX_BOARD_INPUT (:594 panics on the coordinates)
+    bool build(const void *slots, size_t stride, uint32_t n_slots, const uint32_t *point_status)
+    {
+        pos_of.assign(n_slots, -1);
+        for (uint32_t i = 0; i < n_slots; ++i) {
+            if (point_status && point_status[i] != 0u) continue;  // (AGX_POINT_REFINED is 0)
+            agx_saddle s;
+            std::memcpy(&s, static_cast<const char *>(slots) + (size_t)i * stride, sizeof s);
+            if (!std::isfinite(s.x) || !std::isfinite(s.y) || !std::isfinite(s.theta)) return false;
+            s.k = 0.0f;  // (never read: whatever the slot holds there)
+            s.phi = 0.0f;
+            pos_of[i] = (int)list.size();
+            list.push_back(s);
+            slot_of.push_back(i);
+        }
+        return true;
+    }
+    // the position of slot s in the list, or -1: beyond the frame's count, or not listed
+    int pos(uint32_t s) const { return s < pos_of.size() ? pos_of[s] : -1; }
+    // quads of list positions behind `rows` as slot numbers, four per quad
+    void append_slots(const std::vector<Quad> &found, std::vector<uint32_t> &rows) const
+    {
+        for (const Quad &q : found)
+            for (int i = 0; i < 4; ++i) rows.push_back(slot_of[(size_t)q[i]]);
+    }
+};
+}  // namespace
+
 int find_board_in_slots(const void *slots, size_t stride, uint32_t n_slots, const uint32_t *point_status, std::vector<uint32_t> &quads)
 {
     quads.clear();
-    std::vector<agx_saddle> list;
-    std::vector<uint32_t> slot_of;
-    for (uint32_t i = 0; i < n_slots; ++i) {
-        if (point_status && point_status[i] != 0u) continue;  // (AGX_POINT_REFINED is 0)
-        agx_saddle s;
-        std::memcpy(&s, static_cast<const char *>(slots) + (size_t)i * stride, sizeof s);
-        if (!std::isfinite(s.x) || !std::isfinite(s.y) || !std::isfinite(s.theta)) return AGX_BOARD_INPUT;  // (:594 panics on the coordinates)
-        s.k = 0.0f;  // (never read: whatever the slot holds there)
-        s.phi = 0.0f;
-        list.push_back(s);
-        slot_of.push_back(i);
-    }
+    SlotList l;
+    if (!l.build(slots, stride, n_slots, point_status)) return AGX_BOARD_INPUT;
     std::vector<Quad> found;
-    if (!try_find_best_board(list, found, nullptr)) return AGX_BOARD_NONE;
-    for (const Quad &q : found)
-        for (int i = 0; i < 4; ++i) quads.push_back(slot_of[(size_t)q[i]]);
+    if (!try_find_best_board(l.list, found, nullptr)) return AGX_BOARD_NONE;
+    l.append_slots(found, quads);
     return AGX_BOARD_FOUND;
 }
 
@@ -1384,31 +1409,15 @@ int grow_boards_in_slots(const void *slots, size_t stride, uint32_t n_slots, con
     quads.clear();
     seed_scores.assign(n_seeds, 0u);
     best_seed = 0;
-    std::vector<agx_saddle> list;
-    std::vector<uint32_t> slot_of;
-    std::vector<int> pos_of(n_slots, -1);
-    for (uint32_t i = 0; i < n_slots; ++i) {
-        if (point_status && point_status[i] != 0u) continue;  // (AGX_POINT_REFINED is 0)
-        agx_saddle s;
-        std::memcpy(&s, static_cast<const char *>(slots) + (size_t)i * stride, sizeof s);
-        if (!std::isfinite(s.x) || !std::isfinite(s.y) || !std::isfinite(s.theta)) return AGX_BOARD_INPUT;
-        s.k = 0.0f;  // (never read: whatever the slot holds there)
-        s.phi = 0.0f;
-        pos_of[i] = (int)list.size();
-        list.push_back(s);
-        slot_of.push_back(i);
-    }
+    SlotList l;
+    if (!l.build(slots, stride, n_slots, point_status)) return AGX_BOARD_INPUT;
     std::vector<Quad> seeds(n_seeds);
     for (uint32_t k = 0; k < n_seeds; ++k)
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t s = seed_quads[4 * (size_t)k + j];
-            if (s >= n_slots || pos_of[s] < 0) return AGX_BOARD_INPUT;  // beyond the frame's count, or not listed
-            seeds[k][j] = pos_of[s];
-        }
+        for (int j = 0; j < 4; ++j)
+            if ((seeds[k][j] = l.pos(seed_quads[4 * (size_t)k + j])) < 0) return AGX_BOARD_INPUT;
     std::vector<Quad> found;
-    const int st = grow_boards(list, seeds, spacing_ratio, stop_score, (flags & AGX_GROW_FIX_MISSING) != 0, found, seed_scores, best_seed);
-    for (const Quad &q : found)
-        for (int i = 0; i < 4; ++i) quads.push_back(slot_of[(size_t)q[i]]);
+    const int st = grow_boards(l.list, seeds, spacing_ratio, stop_score, (flags & AGX_GROW_FIX_MISSING) != 0, found, seed_scores, best_seed);
+    l.append_slots(found, quads);
     return st;
 }
 
@@ -1419,27 +1428,15 @@ int init_quads_in_slots(const void *slots, size_t stride, uint32_t n_slots, cons
     quads.clear();
     seed_quad_counts.clear();
     seeds_out.clear();
-    std::vector<agx_saddle> list;
-    std::vector<uint32_t> slot_of;
-    std::vector<int> pos_of(n_slots, -1);
-    for (uint32_t i = 0; i < n_slots; ++i) {
-        if (point_status && point_status[i] != 0u) continue;  // (AGX_POINT_REFINED is 0)
-        agx_saddle s;
-        std::memcpy(&s, static_cast<const char *>(slots) + (size_t)i * stride, sizeof s);
-        if (!std::isfinite(s.x) || !std::isfinite(s.y) || !std::isfinite(s.theta)) return AGX_BOARD_INPUT;
-        s.k = 0.0f;  // (never read: whatever the slot holds there)
-        s.phi = 0.0f;
-        pos_of[i] = (int)list.size();
-        list.push_back(s);
-        slot_of.push_back(i);
-    }
+    SlotList l;
+    if (!l.build(slots, stride, n_slots, point_status)) return AGX_BOARD_INPUT;
+    const std::vector<agx_saddle> &list = l.list;
     std::vector<int> seeds;  // positions in the list, in the order they are taken
     if (seed_saddles) {
         const uint32_t take = std::min(n_seeds, max_seeds);
         for (uint32_t k = 0; k < take; ++k) {
-            const uint32_t s = seed_saddles[k];
-            if (s >= n_slots || pos_of[s] < 0) return AGX_BOARD_INPUT;  // beyond the frame's count, or not listed
-            seeds.push_back(pos_of[s]);
+            seeds.push_back(l.pos(seed_saddles[k]));
+            if (seeds.back() < 0) return AGX_BOARD_INPUT;
         }
     }
     seed_quad_counts.assign(max_seeds, 0u);
@@ -1459,9 +1456,8 @@ int init_quads_in_slots(const void *slots, size_t stride, uint32_t n_slots, cons
     for (size_t k = 0; k < seeds.size(); ++k) {
         init_quads(list, sc.index, seeds[k], cand, (int)n_nearest);
         seed_quad_counts[k] = (uint32_t)cand.size();
-        seeds_out.push_back(slot_of[(size_t)seeds[k]]);
-        for (const Quad &q : cand)
-            for (int i = 0; i < 4; ++i) quads.push_back(slot_of[(size_t)q[i]]);
+        seeds_out.push_back(l.slot_of[(size_t)seeds[k]]);
+        l.append_slots(cand, quads);
     }
     return quads.empty() ? AGX_BOARD_NONE : AGX_BOARD_FOUND;
 }

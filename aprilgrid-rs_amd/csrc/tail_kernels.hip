@@ -1001,6 +1001,91 @@ __device__ int init_quads_w(const Ctx &c, uint8_t *wv, int s0, int lane, uint32_
 
 __device__ __forceinline__ bool fb_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
+// The frame's list as k_find_boards, k_grow_boards and k_init_quads take it: the frame's slots, those d_point_status admits, in
+// slot order, into sx / sy / st with slot_of (list position -> slot number within the frame).  Decided before any search, all
+// lanes alike.
+struct FrameList {
+    uint32_t early;  // an AGX_BOARD_* status that ends the frame here, or 0xffffffff
+    bool read;       // the frame's slots were read (else `early` was decided without them, and nothing of the frame may be read)
+    int n;           // saddles listed, at most TN
+    u64 first_slot;  // (in the batch's slot numbering: where the records and status words are)
+    u64 n_slots;
+};
+// wcnt: u32[TW] of scratch; sh: the kernel's shared words, the first sh_words of them initialised here ([0] status, [3] a saddle
+// that is not finite -- left set, [4] the debug band).  The workgroup passes the same barriers whatever the frame holds.
+__device__ __forceinline__ FrameList frame_list(const FindBoardsArgs &b, float *sx, float *sy, float *st, uint32_t *slot_of, uint32_t *wcnt,
+                                                uint32_t *sh, int sh_words, int f, int tid)
+{
+    const int wave = tid >> 6, lane = tid & 63;
+    const u64 below = (1ull << lane) - 1ull;
+    FrameList l;
+    l.early = 0xffffffffu;
+    l.read = false;
+    l.n = 0;
+    l.first_slot = (u64)f * (u64)b.saddles_per_frame;
+    l.n_slots = b.saddles_per_frame;
+    if (b.host_only) {
+        l.early = AGX_BOARD_PENDING;  // option "device_tail" 0, or refused: the fetch's host form answers every frame
+    } else if (b.frame_table) {
+        const uint32_t *e = b.frame_table + 4 * (size_t)f;  // agx_frame_result: count, offset, status
+        if (e[2] & 7u) l.early = AGX_BOARD_INPUT;  // an overflow bit: there is no list; nothing of the frame is read
+        l.n_slots = e[0];
+        l.first_slot = e[1];
+    } else if (b.counts) {
+        const uint32_t c = b.counts[f];
+        l.n_slots = c < b.saddles_per_frame ? c : b.saddles_per_frame;
+    }
+    if (l.early != 0xffffffffu) return l;
+    l.read = true;
+    const u64 first_slot = l.first_slot, n_slots = l.n_slots;
+    uint32_t status = 0;  // per lane; merged through sh[0]
+    bool bad = false;
+    u64 listed_all = 0;
+    for (u64 base = 0; base < n_slots; base += 64 * TW) {
+        const u64 i = base + (u64)tid;
+        bool listed = i < n_slots;
+        if (listed && b.point_status) listed = b.point_status[first_slot + i] == 0u;  // (AGX_POINT_REFINED is 0)
+        float x = 0.0f, y = 0.0f, t = 0.0f;
+        if (listed) {
+            const float *src = reinterpret_cast<const float *>(b.saddles + (first_slot + i) * (u64)b.stride);
+            x = src[0];
+            y = src[1];
+            t = src[3];
+            if (!(fb_finite(x) && fb_finite(y) && fb_finite(t))) bad = true;
+            // as the chain's lists: coordinates of an image and half an atan2 in degrees; anything else is the host form's business
+            else if (!(fabsf(x) < 1e6f && fabsf(y) < 1e6f && t >= -180.0f && t <= 180.0f)) status |= TAIL_CAPACITY;
+        }
+        const u64 mk = __ballot(listed);
+        if (lane == 0) wcnt[wave] = (uint32_t)__popcll(mk);
+        __syncthreads();
+        u64 at = listed_all + (u64)__popcll(mk & below), total = 0;
+        for (int w = 0; w < TW; ++w) {
+            const uint32_t cw = wcnt[w];
+            if (w < wave) at += cw;
+            total += cw;
+        }
+        if (listed && at < (u64)TN) {
+            sx[at] = x;
+            sy[at] = y;
+            st[at] = t;
+            slot_of[at] = (uint32_t)i;
+        }
+        listed_all += total;
+        __syncthreads();
+    }
+    if (tid < sh_words) sh[tid] = tid == 4 ? __float_as_uint(b.debug_band) : 0u;  // ([4]: white_block's debug band)
+    __syncthreads();
+    if (bad) atomicOr(&sh[3], 1u);
+    if (listed_all > (u64)TN) status |= TAIL_CAPACITY;
+    if (status) atomicOr(&sh[0], status);
+    __syncthreads();
+    if (sh[3]) l.early = AGX_BOARD_INPUT;  // (tree.add(..).unwrap() panics on these, :594)
+    else if (listed_all == 0) l.early = AGX_BOARD_NONE;  // :589-591
+    else if (sh[0]) l.early = AGX_BOARD_PENDING;
+    l.n = listed_all > (u64)TN ? TN : (int)listed_all;
+    return l;
+}
+
 // The body of both kernels of the board search, one workgroup per frame.
 //   FIND false: k_board_tail -- up to max_boards rounds of try_find_best_board + try_decode_quad over the chain's list (a), tags out.
 //   FIND true:  k_find_boards -- exactly one try_find_best_board (detector.rs:588-639) over a caller-given list (b): the round
@@ -1081,67 +1166,13 @@ __device__ __forceinline__ void board_tail_body(const TailArgs &a, const B &b)
     __syncthreads();
     if (sh[0]) n = 0;  // nothing is searched; the status goes out below
     } else {
-    // ---- the frame's list: its slots, those d_point_status admits, in slot order; decided before any search, all lanes alike ----
-    uint32_t early = 0xffffffffu;  // an AGX_BOARD_* status that ends the frame here
-    u64 first_slot = (u64)f * (u64)b.saddles_per_frame;  // (in the batch's slot numbering: where the records and status words are)
-    u64 n_slots = b.saddles_per_frame;
-    if (b.host_only) {
-        early = AGX_BOARD_PENDING;  // option "device_tail" 0, or refused: the fetch's host form answers every frame
-    } else if (b.frame_table) {
-        const uint32_t *e = b.frame_table + 4 * (size_t)f;  // agx_frame_result: count, offset, status
-        if (e[2] & 7u) early = AGX_BOARD_INPUT;  // an overflow bit: there is no list; nothing of the frame is read
-        n_slots = e[0];
-        first_slot = e[1];
-    } else if (b.counts) {
-        const uint32_t c = b.counts[f];
-        n_slots = c < b.saddles_per_frame ? c : b.saddles_per_frame;
-    }
-    if (early == 0xffffffffu) {
-        uint32_t *wcnt = hist;  // [TW]: listed slots of each wave's 64 (the histogram's space: cleared before its use)
-        bool bad = false;
-        u64 listed_all = 0;
-        for (u64 base = 0; base < n_slots; base += 64 * TW) {
-            const u64 i = base + (u64)tid;
-            bool listed = i < n_slots;
-            if (listed && b.point_status) listed = b.point_status[first_slot + i] == 0u;  // (AGX_POINT_REFINED is 0)
-            float x = 0.0f, y = 0.0f, t = 0.0f;
-            if (listed) {
-                const float *src = reinterpret_cast<const float *>(b.saddles + (first_slot + i) * (u64)b.stride);
-                x = src[0];
-                y = src[1];
-                t = src[3];
-                if (!(fb_finite(x) && fb_finite(y) && fb_finite(t))) bad = true;
-                // as the chain's lists above: anything else is the host form's business
-                else if (!(fabsf(x) < 1e6f && fabsf(y) < 1e6f && t >= -180.0f && t <= 180.0f)) status |= TAIL_CAPACITY;
-            }
-            const u64 mk = __ballot(listed);
-            if (lane == 0) wcnt[wave] = (uint32_t)__popcll(mk);
-            __syncthreads();
-            u64 at = listed_all + (u64)__popcll(mk & below), total = 0;
-            for (int w = 0; w < TW; ++w) {
-                const uint32_t cw = wcnt[w];
-                if (w < wave) at += cw;
-                total += cw;
-            }
-            if (listed && at < (u64)TN) {
-                sx[at] = x;
-                sy[at] = y;
-                st[at] = t;
-                slot_of[at] = (uint32_t)i;
-            }
-            listed_all += total;
-            __syncthreads();
-        }
-        if (tid < 8 + 6 * TW) sh[tid] = tid == 4 ? __float_as_uint(a.debug_band) : 0u;  // ([4]: white_block's debug band)
-        __syncthreads();
-        if (bad) atomicOr(&sh[3], 1u);
-        if (listed_all > (u64)TN) status |= TAIL_CAPACITY;
-        if (status) atomicOr(&sh[0], status);
-        __syncthreads();
-        if (sh[3]) early = AGX_BOARD_INPUT;  // (tree.add(..).unwrap() panics on these, :594)
-        else if (listed_all == 0) early = AGX_BOARD_NONE;  // :589-591
-        else if (sh[0]) early = AGX_BOARD_PENDING;
-        n = listed_all > (u64)TN ? TN : (int)listed_all;
+    // ---- the frame's list (frame_list above); GROW: then the caller's seeds ----
+    const FrameList fl = frame_list(b, sx, sy, st, slot_of, hist /* the histogram's space: cleared before its use */, sh, 8 + 6 * TW, f, tid);
+    uint32_t early = fl.early;
+    const u64 first_slot = fl.first_slot, n_slots = fl.n_slots;
+    (void)first_slot; (void)n_slots;  // (only GROW reads them)
+    if (fl.read) {
+        n = fl.n;
         n_first = n;
         __syncthreads();  // (sh[3] is read; the search's first wave writes the shared words)
         if (tid == 0) sh[3] = 0;
@@ -1800,68 +1831,13 @@ __global__ void __launch_bounds__(64 * TW) k_init_quads(InitQuadsArgs b)
 
     uint32_t status = 0;  // per lane; merged through the groups' words
     int n = 0;
-    // ---- the frame's list, as k_find_boards takes it; then the caller's seeds.  Decided before anything is listed ----
-    uint32_t early = 0xffffffffu;
-    u64 first_slot = (u64)f * (u64)b.saddles_per_frame;
-    u64 n_slots = b.saddles_per_frame;
+    // ---- the frame's list, as k_find_boards takes it (frame_list); then the caller's seeds.  Decided before anything is listed ----
+    const FrameList fl = frame_list(b, sx, sy, st, slot_of, hist, sh, 64, f, tid);
+    uint32_t early = fl.early;
+    const u64 first_slot = fl.first_slot, n_slots = fl.n_slots;
     uint32_t total = 0;  // the frame's seeds
-    if (b.host_only) {
-        early = AGX_BOARD_PENDING;
-    } else if (b.frame_table) {
-        const uint32_t *e = b.frame_table + 4 * (size_t)f;
-        if (e[2] & 7u) early = AGX_BOARD_INPUT;
-        n_slots = e[0];
-        first_slot = e[1];
-    } else if (b.counts) {
-        const uint32_t c = b.counts[f];
-        n_slots = c < b.saddles_per_frame ? c : b.saddles_per_frame;
-    }
-    if (early == 0xffffffffu) {
-        uint32_t *wcnt = hist;
-        bool bad = false;
-        u64 listed_all = 0;
-        for (u64 base = 0; base < n_slots; base += 64 * TW) {
-            const u64 i = base + (u64)tid;
-            bool listed = i < n_slots;
-            if (listed && b.point_status) listed = b.point_status[first_slot + i] == 0u;
-            float x = 0.0f, y = 0.0f, t = 0.0f;
-            if (listed) {
-                const float *src = reinterpret_cast<const float *>(b.saddles + (first_slot + i) * (u64)b.stride);
-                x = src[0];
-                y = src[1];
-                t = src[3];
-                if (!(fb_finite(x) && fb_finite(y) && fb_finite(t))) bad = true;
-                else if (!(fabsf(x) < 1e6f && fabsf(y) < 1e6f && t >= -180.0f && t <= 180.0f)) status |= TAIL_CAPACITY;
-            }
-            const u64 mk = __ballot(listed);
-            if (lane == 0) wcnt[wave] = (uint32_t)__popcll(mk);
-            __syncthreads();
-            u64 at = listed_all + (u64)__popcll(mk & below), sum = 0;
-            for (int w = 0; w < TW; ++w) {
-                const uint32_t cw = wcnt[w];
-                if (w < wave) at += cw;
-                sum += cw;
-            }
-            if (listed && at < (u64)TN) {
-                sx[at] = x;
-                sy[at] = y;
-                st[at] = t;
-                slot_of[at] = (uint32_t)i;
-            }
-            listed_all += sum;
-            __syncthreads();
-        }
-        if (tid < 64) sh[tid] = tid == 4 ? __float_as_uint(b.debug_band) : 0u;
-        __syncthreads();
-        if (bad) atomicOr(&sh[3], 1u);
-        if (listed_all > (u64)TN) status |= TAIL_CAPACITY;
-        if (status) atomicOr(&sh[0], status);
-        __syncthreads();
-        if (sh[3]) early = AGX_BOARD_INPUT;
-        else if (listed_all == 0) early = AGX_BOARD_NONE;
-        else if (sh[0]) early = AGX_BOARD_PENDING;
-        n = listed_all > (u64)TN ? TN : (int)listed_all;
-        status = 0;
+    if (fl.read) {
+        n = fl.n;
         if (sd) {
             // every seed names a listed slot of the frame, or the frame is AGX_BOARD_INPUT (asked of the caller's words, not of
             // the list in LDS: that one ends at TN).  No seed: no quad.

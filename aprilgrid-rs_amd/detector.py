@@ -768,11 +768,41 @@ class TagDetector:
         return e.value, b.value, hd.value, n.value
 
     @staticmethod
-    def _stage_tensor(t, dtype, shape, what, dev):
+    def _stage_tensor(t, dtype, shape, what, dev, optional=False, where="device tensor %s on the batch's device"):
+        if t is None and optional:
+            return None
         if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and (shape is None or tuple(t.shape) == shape)
                 and t.device == dev):
-            raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s device tensor %s on the batch's device" % (what, dtype, shape))
+            raise AgxError(_ffi.AGX_ERR_ARG, ("%s must be a contiguous %s " + where) % (what, dtype, shape))
         return t.data_ptr()
+
+    def _stage_lists(self, saddles, counts, frame_table, point_status):
+        """The saddle lists of find_boards_enqueue, grow_boards_enqueue and init_quads_enqueue -> (n, spf, stride, tensor, p_counts,
+        p_table, p_point_status): frames, slots per frame, bytes per slot, and `tensor(t, dtype, shape, what)`, the pointer of an
+        optional tensor on the saddles' device (None: None)."""
+        import torch
+        if not (getattr(saddles, "is_cuda", False) and saddles.is_contiguous() and saddles.dtype == torch.float32 and saddles.shape[-1] >= 5):
+            raise AgxError(_ffi.AGX_ERR_ARG, "saddles must be a contiguous float32 device tensor [N, S, K >= 5] (or [capacity, K] with frame_table)")
+        dev = saddles.device
+
+        def tensor(t, dtype, shape, what):
+            return self._stage_tensor(t, dtype, shape, what, dev, optional=True, where="tensor %s on the saddles' device")
+
+        if frame_table is not None:
+            if saddles.dim() != 2 or frame_table.dim() != 2 or frame_table.shape[1] != 4:
+                raise AgxError(_ffi.AGX_ERR_ARG, "with frame_table [N, 4]: saddles [capacity, K]")
+            n, spf, n_slots = int(frame_table.shape[0]), int(saddles.shape[0]), int(saddles.shape[0])
+        else:
+            if saddles.dim() != 3 or saddles.shape[1] == 0:
+                raise AgxError(_ffi.AGX_ERR_ARG, "saddles must be [N, S, K]")
+            n, spf = int(saddles.shape[0]), int(saddles.shape[1])
+            n_slots = n * spf
+        p_table = tensor(frame_table, torch.int32, (n, 4), "frame_table")
+        p_counts = tensor(counts, torch.int32, (n,), "counts")
+        p_ps = tensor(point_status, torch.int32, None, "point_status")
+        if point_status is not None and point_status.numel() != n_slots:
+            raise AgxError(_ffi.AGX_ERR_ARG, "point_status: one word per slot")
+        return n, spf, 4 * int(saddles.shape[-1]), tensor, p_counts, p_table, p_ps
 
     def _stage_quads(self, quads, refined):
         """quads [N,Q,4,2] / [N,Q,8], or refined=(records [N,4Q,5], point_status [N,4Q]) -> (n, qpf, stride, p_quads, p_point_status, dev)"""
@@ -931,43 +961,17 @@ class TagDetector:
         [N, Q, 4, 2] optionally -- with n_quads as counts it is decode_quads_enqueue's quads.  Indices are slot numbers
         within the frame."""
         import torch
-        if not (getattr(saddles, "is_cuda", False) and saddles.is_contiguous() and saddles.dtype == torch.float32 and saddles.shape[-1] >= 5):
-            raise AgxError(_ffi.AGX_ERR_ARG, "saddles must be a contiguous float32 device tensor [N, S, K >= 5] (or [capacity, K] with frame_table)")
-        dev = saddles.device
-        stride = 4 * int(saddles.shape[-1])
-
-        def tensor(t, dtype, shape, what):
-            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and (shape is None or tuple(t.shape) == shape)
-                    and t.device == dev):
-                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s tensor %s on the saddles' device" % (what, dtype, shape))
-            return t.data_ptr()
-
-        if frame_table is not None:
-            if saddles.dim() != 2 or frame_table.dim() != 2 or frame_table.shape[1] != 4:
-                raise AgxError(_ffi.AGX_ERR_ARG, "with frame_table [N, 4]: saddles [capacity, K]")
-            n, spf, n_slots = int(frame_table.shape[0]), int(saddles.shape[0]), int(saddles.shape[0])
-            p_table = tensor(frame_table, torch.int32, (n, 4), "frame_table")
-        else:
-            if saddles.dim() != 3 or saddles.shape[1] == 0:
-                raise AgxError(_ffi.AGX_ERR_ARG, "saddles must be [N, S, K]")
-            n, spf = int(saddles.shape[0]), int(saddles.shape[1])
-            n_slots, p_table = n * spf, None
-        p_counts = tensor(counts, torch.int32, (n,), "counts") if counts is not None else None
-        p_ps = None
-        if point_status is not None:
-            p_ps = tensor(point_status, torch.int32, None, "point_status")
-            if point_status.numel() != n_slots:
-                raise AgxError(_ffi.AGX_ERR_ARG, "point_status: one word per slot")
+        n, spf, stride, tensor, p_counts, p_table, p_ps = self._stage_lists(saddles, counts, frame_table, point_status)
         given = [t is not None for t in (quads, n_quads, status)]
         if any(given) != all(given):
             raise AgxError(_ffi.AGX_ERR_ARG, "quads, n_quads and status: all or none")
         qpf = int(quads.shape[1]) if quads is not None and quads.dim() == 3 else int(quads_per_frame)
-        p_quads = tensor(quads, torch.int32, (n, qpf, 4), "quads") if quads is not None else None
-        p_n = tensor(n_quads, torch.int32, (n,), "n_quads") if n_quads is not None else None
-        p_st = tensor(status, torch.int32, (n,), "status") if status is not None else None
-        p_pts = tensor(quad_points, torch.float32, (n, qpf, 4, 2), "quad_points") if quad_points is not None else None
+        p_quads = tensor(quads, torch.int32, (n, qpf, 4), "quads")
+        p_n = tensor(n_quads, torch.int32, (n,), "n_quads")
+        p_st = tensor(status, torch.int32, (n,), "status")
+        p_pts = tensor(quad_points, torch.float32, (n, qpf, 4, 2), "quad_points")
         self._follow_torch_stream(saddles)
-        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = None
+        self._replaces_batch()
         self._check(self._lib.agx_find_boards_enqueue(self._h, saddles.data_ptr(), stride, n, spf, p_counts, p_table, p_ps, qpf, p_quads, p_pts,
                                                       p_n, p_st))
         self._find = (n, qpf, (saddles, counts, frame_table, point_status, quad_points),
@@ -981,7 +985,7 @@ class TagDetector:
         if self._find is None:
             raise AgxError(_ffi.AGX_ERR_STATE, "no find-boards batch enqueued")
         n, qpf, keep, dev_out = self._find
-        self._batch = self._detect = self._refine = self._decode = self._grow = self._find = None
+        self._replaces_batch()
         if dev_out is not None:
             self._check(self._lib.agx_find_boards_fetch(self._h, None, None, None, None, n_threads))
             return dev_out
@@ -1004,41 +1008,16 @@ class TagDetector:
         the device-resident results (required); quad_points float32 [N, Q, 4, 2], seed_scores int32 [N, S] and best_seed int32 [N]
         optionally.  stop_score > 0: no seed is grown behind the first one that leaves the best score at or above it."""
         import torch
-        if not (getattr(saddles, "is_cuda", False) and saddles.is_contiguous() and saddles.dtype == torch.float32 and saddles.shape[-1] >= 5):
-            raise AgxError(_ffi.AGX_ERR_ARG, "saddles must be a contiguous float32 device tensor [N, S, K >= 5] (or [capacity, K] with frame_table)")
-        dev = saddles.device
-        stride = 4 * int(saddles.shape[-1])
-
-        def tensor(t, dtype, shape, what):
-            if t is None:
-                return None
-            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and (shape is None or tuple(t.shape) == shape)
-                    and t.device == dev):
-                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s tensor %s on the saddles' device" % (what, dtype, shape))
-            return t.data_ptr()
-
-        if frame_table is not None:
-            if saddles.dim() != 2 or frame_table.dim() != 2 or frame_table.shape[1] != 4:
-                raise AgxError(_ffi.AGX_ERR_ARG, "with frame_table [N, 4]: saddles [capacity, K]")
-            n, spf, n_slots = int(frame_table.shape[0]), int(saddles.shape[0]), int(saddles.shape[0])
-        else:
-            if saddles.dim() != 3 or saddles.shape[1] == 0:
-                raise AgxError(_ffi.AGX_ERR_ARG, "saddles must be [N, S, K]")
-            n, spf = int(saddles.shape[0]), int(saddles.shape[1])
-            n_slots = n * spf
-        if point_status is not None and point_status.numel() != n_slots:
-            raise AgxError(_ffi.AGX_ERR_ARG, "point_status: one word per slot")
+        n, spf, stride, tensor, p_counts, p_table, p_ps = self._stage_lists(saddles, counts, frame_table, point_status)
         if seed_quads is None or seed_quads.dim() != 3 or quads is None or quads.dim() != 3:
             raise AgxError(_ffi.AGX_ERR_ARG, "seed_quads [N, S, 4] and quads [N, Q, 4]")
         seeds, qpf = int(seed_quads.shape[1]), int(quads.shape[1])
-        ptrs = (tensor(counts, torch.int32, (n,), "counts"), tensor(frame_table, torch.int32, (n, 4), "frame_table"),
-                tensor(point_status, torch.int32, None, "point_status"), tensor(seed_quads, torch.int32, (n, seeds, 4), "seed_quads"),
-                tensor(seed_counts, torch.int32, (n,), "seed_counts"))
+        p_seeds, p_seed_counts = tensor(seed_quads, torch.int32, (n, seeds, 4), "seed_quads"), tensor(seed_counts, torch.int32, (n,), "seed_counts")
         outs = (tensor(quads, torch.int32, (n, qpf, 4), "quads"), tensor(quad_points, torch.float32, (n, qpf, 4, 2), "quad_points"),
                 tensor(n_quads, torch.int32, (n,), "n_quads"), tensor(status, torch.int32, (n,), "status"),
                 tensor(seed_scores, torch.int32, (n, seeds), "seed_scores"), tensor(best_seed, torch.int32, (n,), "best_seed"))
         self._follow_torch_stream(saddles)
-        rc = self._lib.agx_grow_boards_enqueue(self._h, saddles.data_ptr(), stride, n, spf, ptrs[0], ptrs[1], ptrs[2], ptrs[3], seeds, ptrs[4],
+        rc = self._lib.agx_grow_boards_enqueue(self._h, saddles.data_ptr(), stride, n, spf, p_counts, p_table, p_ps, p_seeds, seeds, p_seed_counts,
                                                float(spacing_ratio), int(stop_score), _ffi.AGX_GROW_FIX_MISSING if fix_missing else 0, qpf, *outs)
         if rc == _ffi.AGX_OK:  # (a refused argument leaves the batch in flight where it is)
             self._replaces_batch()
@@ -1064,30 +1043,7 @@ class TagDetector:
         device-resident results (required) -- quads with n_quads are grow_boards_enqueue's seed_quads with seed_counts as they
         stand; quad_points float32 [N, Q, 4, 2], seed_quad_counts and seeds_out int32 [N, S], n_seeds_out int32 [N] optionally."""
         import torch
-        if not (getattr(saddles, "is_cuda", False) and saddles.is_contiguous() and saddles.dtype == torch.float32 and saddles.shape[-1] >= 5):
-            raise AgxError(_ffi.AGX_ERR_ARG, "saddles must be a contiguous float32 device tensor [N, S, K >= 5] (or [capacity, K] with frame_table)")
-        dev = saddles.device
-        stride = 4 * int(saddles.shape[-1])
-
-        def tensor(t, dtype, shape, what):
-            if t is None:
-                return None
-            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and (shape is None or tuple(t.shape) == shape)
-                    and t.device == dev):
-                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s tensor %s on the saddles' device" % (what, dtype, shape))
-            return t.data_ptr()
-
-        if frame_table is not None:
-            if saddles.dim() != 2 or frame_table.dim() != 2 or frame_table.shape[1] != 4:
-                raise AgxError(_ffi.AGX_ERR_ARG, "with frame_table [N, 4]: saddles [capacity, K]")
-            n, spf, n_slots = int(frame_table.shape[0]), int(saddles.shape[0]), int(saddles.shape[0])
-        else:
-            if saddles.dim() != 3 or saddles.shape[1] == 0:
-                raise AgxError(_ffi.AGX_ERR_ARG, "saddles must be [N, S, K]")
-            n, spf = int(saddles.shape[0]), int(saddles.shape[1])
-            n_slots = n * spf
-        if point_status is not None and point_status.numel() != n_slots:
-            raise AgxError(_ffi.AGX_ERR_ARG, "point_status: one word per slot")
+        n, spf, stride, tensor, p_counts, p_table, p_ps = self._stage_lists(saddles, counts, frame_table, point_status)
         if quads is None or quads.dim() != 3 or (seed_saddles is not None and seed_saddles.dim() != 2):
             raise AgxError(_ffi.AGX_ERR_ARG, "quads [N, Q, 4] and seed_saddles [N, S]")
         if seed_saddles is not None:
@@ -1095,15 +1051,13 @@ class TagDetector:
         else:
             seeds = 30 if seeds_per_frame is None else int(seeds_per_frame)
         qpf = int(quads.shape[1])
-        ptrs = (tensor(counts, torch.int32, (n,), "counts"), tensor(frame_table, torch.int32, (n, 4), "frame_table"),
-                tensor(point_status, torch.int32, None, "point_status"), tensor(seed_saddles, torch.int32, (n, seeds), "seed_saddles"),
-                tensor(seed_counts, torch.int32, (n,), "seed_counts"))
+        p_seeds, p_seed_counts = tensor(seed_saddles, torch.int32, (n, seeds), "seed_saddles"), tensor(seed_counts, torch.int32, (n,), "seed_counts")
         outs = (tensor(quads, torch.int32, (n, qpf, 4), "quads"), tensor(quad_points, torch.float32, (n, qpf, 4, 2), "quad_points"),
                 tensor(n_quads, torch.int32, (n,), "n_quads"), tensor(status, torch.int32, (n,), "status"),
                 tensor(seed_quad_counts, torch.int32, (n, seeds), "seed_quad_counts"), tensor(seeds_out, torch.int32, (n, seeds), "seeds_out"),
                 tensor(n_seeds_out, torch.int32, (n,), "n_seeds_out"))
         self._follow_torch_stream(saddles)
-        rc = self._lib.agx_init_quads_enqueue(self._h, saddles.data_ptr(), stride, n, spf, ptrs[0], ptrs[1], ptrs[2], ptrs[3], seeds, ptrs[4],
+        rc = self._lib.agx_init_quads_enqueue(self._h, saddles.data_ptr(), stride, n, spf, p_counts, p_table, p_ps, p_seeds, seeds, p_seed_counts,
                                               int(n_nearest), qpf, *outs)
         if rc == _ffi.AGX_OK:  # (a refused argument leaves the batch in flight where it is)
             self._replaces_batch()

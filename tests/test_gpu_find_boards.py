@@ -311,6 +311,40 @@ def test_statuses_counts_strides_and_output_modes(det, base):
     det.find_boards_enqueue(base["d_saddles"], frame_table=table, quads_per_frame=Q)
     _, _, n4, st4 = det.find_boards_fetch()
     assert (st4[5], n4[5]) == (INPUT, 0) and (np.delete(st4, 5) == FOUND).all()
+    # such an entry through the host form: with option device_tail 0 the kernel reads no table and hands every frame back.  Two
+    # lattices back to back in one flat array and a third entry with an overflow bit, with and without the device tail
+    import aprilgrid_rs_amd as A
+    from tests import board_cases as BC
+    l7, l9 = BC.lattice(7, 7), BC.lattice(9, 9)
+    flat = np.concatenate([np.zeros((3, 5), np.float32), l7, l9])
+    small = np.array([[49, 3, 0, 0], [81, 52, 0, 0], [49, 3, 2, 0]], np.int32)
+    w7, w9 = host(l7), host(l9)
+    assert w7[1] == FOUND and w9[1] == FOUND
+
+    def table_pass(d, host_only):
+        i32 = dict(dtype=torch.int32, device="cuda")
+        out = dict(quads=torch.full((3, Q, 4), SENTINEL, **i32), quad_points=torch.full((3, Q, 4, 2), -7.0, dtype=torch.float32, device="cuda"),
+                   n_quads=torch.full((3,), SENTINEL, **i32), status=torch.full((3,), SENTINEL, **i32))
+        d.find_boards_enqueue(dev(flat), frame_table=dev(small), **out)
+        d.sync()
+        if host_only:
+            assert (out["status"].cpu().numpy() == PENDING).all()
+        d.find_boards_fetch()
+        res = {k: v.cpu().numpy().view(np.uint32 if v.dtype == torch.int32 else np.float32).copy() for k, v in out.items()}
+        assert list(res["status"]) == [FOUND, FOUND, INPUT] and list(res["n_quads"]) == [w7[2], w9[2], 0]
+        assert res["quads"][0, :w7[2]].tobytes() == w7[0].tobytes() and res["quads"][1, :w9[2]].tobytes() == w9[0].tobytes()
+        assert (res["quads"][2] == SENTINEL).all() and (res["quad_points"][2] == np.float32(-7.0)).all()
+        return res
+
+    first = table_pass(det, False)
+    d0 = A.TagDetector("t36h11", None, device=0)
+    try:
+        d0.set_option("device_tail", 0)
+        second = table_pass(d0, True)
+        assert handed_back(d0) == (3, 3)
+    finally:
+        d0.close()
+    assert all(first[k].tobytes() == second[k].tobytes() for k in first)
 
 
 def test_state_and_argument_rules(det, base):

@@ -257,13 +257,34 @@ def test_padded_stride_point_status_capacity_and_frame_table(det):
     l9 = BC.lattice(9, 9)
     sq = np.stack([np.asarray(seed, np.uint32), np.asarray(first_quad(l9), np.uint32), np.asarray(seed, np.uint32)]).reshape(3, 1, 4)
     i32 = dict(dtype=torch.int32, device="cuda")
-    quads, nq, st = torch.full((3, Q, 4), SENT, **i32), torch.full((3,), SENT, **i32), torch.full((3,), SENT, **i32)
-    det.grow_boards_enqueue(dev(flat), dev(sq.view(np.int32)), quads, nq, st, frame_table=dev(table))
-    det.grow_boards_fetch()
-    quads, nq, st = quads.cpu().numpy().view(np.uint32), nq.cpu().numpy(), st.cpu().numpy()
-    assert list(st) == [FOUND, FOUND, INPUT] and list(nq) == [9, 16, 0]
-    assert quads[0, :9].tobytes() == host(l, seed)[0].tobytes() and quads[1, :16].tobytes() == host(l9, first_quad(l9))[0].tobytes()
-    assert (quads[2] == SENT).all()
+
+    def table_pass(d, host_only):
+        out = dict(quads=torch.full((3, Q, 4), SENT, **i32), quad_points=torch.full((3, Q, 4, 2), -7.0, dtype=torch.float32, device="cuda"),
+                   n_quads=torch.full((3,), SENT, **i32), status=torch.full((3,), SENT, **i32), seed_scores=torch.full((3, 1), SENT, **i32),
+                   best_seed=torch.full((3,), SENT, **i32))
+        d.grow_boards_enqueue(dev(flat), dev(sq.view(np.int32)), frame_table=dev(table), **out)
+        d.sync()
+        if host_only:  # the kernel read no table: the overflow entry is the host form's to refuse
+            assert (out["status"].cpu().numpy() == PENDING).all()
+        d.grow_boards_fetch()
+        res = {k: v.cpu().numpy().view(np.uint32 if v.dtype == torch.int32 else np.float32).copy() for k, v in out.items()}
+        quads, nq, st = res["quads"], res["n_quads"], res["status"]
+        assert list(st) == [FOUND, FOUND, INPUT] and list(nq) == [9, 16, 0]
+        assert quads[0, :9].tobytes() == host(l, seed)[0].tobytes() and quads[1, :16].tobytes() == host(l9, first_quad(l9))[0].tobytes()
+        assert (quads[2] == SENT).all()
+        assert (res["quad_points"][2] == np.float32(-7.0)).all() and res["seed_scores"][2, 0] == SENT and res["best_seed"][2] == SENT
+        return res
+
+    first = table_pass(det, False)
+    # the same batch without the device tail: the fetch's host form answers all three, the overflow entry included
+    d0 = A.TagDetector("t36h11", None, device=0)
+    try:
+        d0.set_option("device_tail", 0)
+        second = table_pass(d0, True)
+        assert d0.get_option("last_grow_boards_handed_back") == 3
+    finally:
+        d0.close()
+    assert all(first[k].tobytes() == second[k].tobytes() for k in first)
 
 
 def test_frame_table_and_records_of_the_saddle_chain_for_one_rendered_frame(det):

@@ -271,16 +271,36 @@ def test_padded_stride_point_status_capacity_and_frame_table(det):
     table = np.array([[49, 3, 0, 0], [81, 52, 0, 0], [49, 3, 2, 0]], np.int32)
     sd = np.array([[24], [40], [24]], np.int32)
     i32 = dict(dtype=torch.int32, device="cuda")
-    quads, nq, st = torch.full((3, Q, 4), SENT, **i32), torch.full((3,), SENT, **i32), torch.full((3,), SENT, **i32)
-    det.init_quads_enqueue(dev(flat), quads, nq, st, seed_saddles=dev(sd), frame_table=dev(table))
-    det.sync()
-    assert not (st.cpu().numpy() == PENDING).any()
-    det.init_quads_fetch()
-    quads, nq, st = quads.cpu().numpy().view(np.uint32), nq.cpu().numpy(), st.cpu().numpy()
     w7, w9 = A.init_quads_tail(l, [24]), A.init_quads_tail(l9, [40])
-    assert list(st) == [FOUND, FOUND, INPUT] and list(nq) == [w7[2], w9[2], 0]
-    assert quads[0, :w7[2]].tobytes() == w7[0].tobytes() and quads[1, :w9[2]].tobytes() == w9[0].tobytes()
-    assert (quads[2] == SENT).all() and (quads[0, w7[2]:] == SENT).all()
+
+    def table_pass(d, host_only):
+        out = dict(quads=torch.full((3, Q, 4), SENT, **i32), quad_points=torch.full((3, Q, 4, 2), -7.0, dtype=torch.float32, device="cuda"),
+                   n_quads=torch.full((3,), SENT, **i32), status=torch.full((3,), SENT, **i32), seed_quad_counts=torch.full((3, 1), SENT, **i32),
+                   seeds_out=torch.full((3, 1), SENT, **i32), n_seeds_out=torch.full((3,), SENT, **i32))
+        d.init_quads_enqueue(dev(flat), seed_saddles=dev(sd), frame_table=dev(table), **out)
+        d.sync()
+        pending = out["status"].cpu().numpy() == PENDING
+        assert pending.all() if host_only else not pending.any()  # (without the device tail the kernel read no table)
+        d.init_quads_fetch()
+        res = {k: v.cpu().numpy().view(np.uint32 if v.dtype == torch.int32 else np.float32).copy() for k, v in out.items()}
+        quads, nq, st = res["quads"], res["n_quads"], res["status"]
+        assert list(st) == [FOUND, FOUND, INPUT] and list(nq) == [w7[2], w9[2], 0]
+        assert quads[0, :w7[2]].tobytes() == w7[0].tobytes() and quads[1, :w9[2]].tobytes() == w9[0].tobytes()
+        assert (quads[2] == SENT).all() and (quads[0, w7[2]:] == SENT).all()
+        assert (res["quad_points"][2] == np.float32(-7.0)).all() and res["seed_quad_counts"][2, 0] == SENT and res["seeds_out"][2, 0] == SENT
+        assert res["n_seeds_out"][2] == 0
+        return res
+
+    first = table_pass(det, False)
+    # the same batch without the device tail: the fetch's host form answers all three, the overflow entry included
+    d0 = A.TagDetector("t36h11", None, device=0)
+    try:
+        d0.set_option("device_tail", 0)
+        second = table_pass(d0, True)
+        assert d0.get_option("last_init_quads_handed_back") == 3
+    finally:
+        d0.close()
+    assert all(first[k].tobytes() == second[k].tobytes() for k in first)
 
 
 def test_more_rows_than_the_kernels_own_list(det):
