@@ -4,7 +4,7 @@
 // saddles per frame.  Decisions here depend on f32 comparisons, so the f32 expressions keep
 // the reference's operand order and this file is compiled with -ffp-contract=off.
 #include "host_tail.hpp"
-#include "libm_f32.h"
+#include "decode_math.h"  // round_half_away, f32_as_u32, tag_affine: the decode kernels' own definitions
 
 #ifdef AGX_TAIL_PROFILE
 #include <chrono>
@@ -49,20 +49,6 @@ bool family_info(int family, FamilyInfo &out)
 }
 
 static const float kPi = 3.14159274101257324219f;
-
-// f32::round (half away from zero) without the call into libm the baseline x86-64 target makes of std::round (no SSE4.1
-// rounding instruction): x - trunc(x) is exact in binary32, so the comparison with 0.5 decides exactly what roundf decides.
-// Values of magnitude >= 2^23 (and NaN / inf) are their own rounding.  (The sign of a zero result may differ from roundf's --
-// every use below converts the result to an integer.  Compared with roundf on all 2^32 bit patterns: equal.)
-static inline float round_half_away(float x)
-{
-    if (!(std::fabs(x) < 8388608.0f)) return x;
-    float t = (float)(int32_t)x;
-    const float d = x - t;
-    if (d >= 0.5f) t += 1.0f;
-    else if (d <= -0.5f) t -= 1.0f;
-    return t;
-}
 
 float theta_distance_degree(float t0, float t1)
 {
@@ -993,13 +979,6 @@ void init_quads(const std::vector<agx_saddle> &refined, SaddleIndex &index, int 
     }
 }
 
-inline uint32_t f32_as_u32(float v)  // Rust `as u32`: saturating, NaN -> 0
-{
-    if (!(v > 0.0f)) return 0u;
-    if (v >= 4294967296.0f) return 0xffffffffu;
-    return (uint32_t)v;
-}
-
 }  // namespace
 
 namespace {
@@ -1170,29 +1149,6 @@ bool try_find_best_board(const std::vector<agx_saddle> &refined, std::vector<Qua
     best.fix_missing();
     best.collect(quads);
     return true;
-}
-
-void tag_affine(const float quad_xy[8], int side_bits, float margin, float h[6])
-{
-    // Least-squares affine map from the tag's corner grid (-m,-m), (-m,S), (S,S), (S,-m) to
-    // the image quad.  The source points are the corners of an axis-aligned square, so the
-    // normal equations diagonalise about its centre.  Evaluated in binary64, rounded once.
-    const double S = (double)((float)side_bits - 1.0f + margin), m = (double)margin;
-    const double c = 0.5 * (S - m), a = 0.5 * (S + m);
-    const double su[4] = {-a, -a, a, a}, sv[4] = {-a, a, a, -a};
-    for (int axis = 0; axis < 2; ++axis) {
-        double gu = 0, gv = 0, mean = 0;
-        for (int p = 0; p < 4; ++p) {
-            const double t = quad_xy[2 * p + axis];
-            gu += su[p] * t;
-            gv += sv[p] * t;
-            mean += t;
-        }
-        const double hu = gu / (4.0 * a * a), hv = gv / (4.0 * a * a);
-        h[3 * axis + 0] = (float)hu;
-        h[3 * axis + 1] = (float)hv;
-        h[3 * axis + 2] = (float)(mean / 4.0 - hu * c - hv * c);
-    }
 }
 
 uint64_t rotate_bits(uint64_t bits, int edge_bits)

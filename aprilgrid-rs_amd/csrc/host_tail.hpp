@@ -80,8 +80,7 @@ int init_quads_in_slots(const void *slots, size_t stride, uint32_t n_slots, cons
                         uint32_t n_seeds, uint32_t max_seeds, uint32_t n_nearest, std::vector<uint32_t> &quads,
                         std::vector<uint32_t> &seed_quad_counts, std::vector<uint32_t> &seeds_out);
 
-// image_util.rs:39-70 (h = 2x3 affine, row-major)
-void tag_affine(const float quad_xy[8], int side_bits, float margin, float h[6]);
+// (tag_affine, image_util.rs:39-70, is decode_math.h's: the decode kernels run the same definition)
 // detector.rs:124-140, 142-169
 uint64_t rotate_bits(uint64_t bits, int edge_bits);
 bool best_tag(uint64_t bits, int thres, const uint64_t *codes, int n_codes, int edge_bits, int &idx, int &rot);

@@ -36,6 +36,10 @@
 //             loop order is taken; the wave that grew the chosen board keeps its cells;
 //   the rest  (try_fix_missing, decode -- best_tag by rows of 16 lanes --, the tag map, removing the used saddles) on the first wave.
 //
+// The decode's arithmetic is not this file's own: f32::round, `as u32`, the finite test and tag_affine are decode_math.h's (the
+// host tail runs the same definitions), the lane-group reductions, the sampler, the bit rotation, the code scan and the tag
+// store are decode_lanes.h's (the staged kernels of decode_stages.hip run the same ones); quad_bits8_why and best_tag_row
+// below only bind them to TailArgs and the reference's constants.
 // k_decode_quads (at the end of the file) is the decode alone, for quads the caller names: agx_decode_quads_enqueue.
 // k_find_boards is the board search alone, for saddle lists the caller names (agx_find_boards_enqueue): the same body as
 // k_board_tail (board_tail_body), one round of it up to the complete quad list, which goes out instead of being decoded.
@@ -48,7 +52,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "libm_f32.h"
+#include "decode_lanes.h"
 #include "tail_kernels.h"
 
 namespace agx {
@@ -114,7 +118,6 @@ constexpr float kPiF = 3.14159274101257324219f;
 // conversion to degrees (two roundings, a binary32 pi that is divided by here as well) by 1.6e-5: < 5e-5 degrees.  Twice that.
 constexpr double kBandAbs = 1e-4;
 constexpr double kDegD = 180.0 / (double)kPiF;
-typedef unsigned long long u64;
 
 // Phase timers of the kernel (100 MHz wall clock, frame 0's first wave prints them with AGX_TAIL_DEBUG=2): compiled in only
 // with -DAGX_TAIL_TIMERS (make EXTRA=-DAGX_TAIL_TIMERS): a clock read costs about what a dozen instructions cost, and
@@ -146,21 +149,6 @@ __device__ __forceinline__ float theta_dist(float t0, float t1)  // math_util.rs
     if (d < 0.0f) d += 180.0f;
     else if (d > 180.0f) d -= 180.0f;
     return d > 90.0f ? d - 90.0f : 90.0f - d;
-}
-__device__ __forceinline__ float round_half_away(float x)  // f32::round
-{
-    if (!(fabsf(x) < 8388608.0f)) return x;
-    float t = (float)(int32_t)x;
-    const float d = x - t;
-    if (d >= 0.5f) t += 1.0f;
-    else if (d <= -0.5f) t -= 1.0f;
-    return t;
-}
-__device__ __forceinline__ uint32_t f32_as_u32(float v)  // Rust `as u32`
-{
-    if (!(v > 0.0f)) return 0u;
-    if (v >= 4294967296.0f) return 0xffffffffu;
-    return (uint32_t)v;
 }
 __device__ __forceinline__ float cross2(float ax, float ay, float bx, float by) { return ax * by - ay * bx; }
 __device__ __forceinline__ float dot2(float ax, float ay, float bx, float by) { return ax * bx + ay * by; }
@@ -330,23 +318,6 @@ __device__ __forceinline__ uint32_t wave_or_u(uint32_t v)
     for (int o = 32; o; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o);
     return v;
 }
-// minimum over the lane's row of 16, in every lane of the row (DPP: no LDS crossbar)
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_u(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xf, 0xf, false);
-}
-__device__ __forceinline__ uint32_t row_min_u(uint32_t v)
-{
-    uint32_t t = dpp_u<0xB1>(v);  // quad_perm [1, 0, 3, 2]
-    v = t < v ? t : v;
-    t = dpp_u<0x4E>(v);           // quad_perm [2, 3, 0, 1]
-    v = t < v ? t : v;
-    t = dpp_u<0x141>(v);          // row_half_mirror
-    v = t < v ? t : v;
-    t = dpp_u<0x140>(v);          // row_mirror
-    return t < v ? t : v;
-}
 __device__ __forceinline__ u64 shfl_xor_u64(u64 v, int mask)
 {
     const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, mask), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mask);
@@ -426,16 +397,16 @@ __device__ bool expand_one_w(const Ctx &c, const uint8_t *slot, u64 qs, u64 &out
         }
         // the three smallest keys of the 16 lanes ((distance, index): the distance first, then the index among the nearest) ...
         u64 top0, top1, top2;
-        uint32_t hi0 = (uint32_t)(k0 >> 32), mh = row_min_u(hi0);
-        uint32_t ml = row_min_u(hi0 == mh ? (uint32_t)k0 : 0xffffffffu);
+        uint32_t hi0 = (uint32_t)(k0 >> 32), mh = lanes_reduce<16>(hi0, u_min);
+        uint32_t ml = lanes_reduce<16>(hi0 == mh ? (uint32_t)k0 : 0xffffffffu, u_min);
         top0 = (u64)mh << 32 | ml;
         if (k0 == top0 && top0 != ~0ull) { k0 = k1; k1 = k2; k2 = ~0ull; }
-        hi0 = (uint32_t)(k0 >> 32); mh = row_min_u(hi0);
-        ml = row_min_u(hi0 == mh ? (uint32_t)k0 : 0xffffffffu);
+        hi0 = (uint32_t)(k0 >> 32); mh = lanes_reduce<16>(hi0, u_min);
+        ml = lanes_reduce<16>(hi0 == mh ? (uint32_t)k0 : 0xffffffffu, u_min);
         top1 = (u64)mh << 32 | ml;
         if (k0 == top1 && top1 != ~0ull) { k0 = k1; k1 = k2; k2 = ~0ull; }
-        hi0 = (uint32_t)(k0 >> 32); mh = row_min_u(hi0);
-        ml = row_min_u(hi0 == mh ? (uint32_t)k0 : 0xffffffffu);
+        hi0 = (uint32_t)(k0 >> 32); mh = lanes_reduce<16>(hi0, u_min);
+        ml = lanes_reduce<16>(hi0 == mh ? (uint32_t)k0 : 0xffffffffu, u_min);
         top2 = (u64)mh << 32 | ml;
         // ... within the radius and of the anchor's orientation: lanes 0 .. 2 of the query take one each
         const u64 mine = l == 0 ? top0 : (l == 1 ? top1 : top2);
@@ -500,15 +471,6 @@ __device__ bool expand_one_w(const Ctx &c, const uint8_t *slot, u64 qs, u64 &out
     return false;
 }
 
-// minimum over the lane's quad of four, in every lane of the four
-__device__ __forceinline__ uint32_t quad_min_u(uint32_t v)
-{
-    uint32_t t = dpp_u<0xB1>(v);  // quad_perm [1, 0, 3, 2]
-    v = t < v ? t : v;
-    t = dpp_u<0x4E>(v);           // quad_perm [2, 3, 0, 1]
-    return t < v ? t : v;
-}
-
 // The SIXTEEN queries of a cell's four directions at once, four lanes each (a lane per cell row): which directions cannot be
 // expanded whatever the board has used -- one of the direction's four lists is empty before the board's own test, and
 // try_expand_one's loops are empty with it (:160-174).  Most directions of most cells are such (a board grown from a quad that
@@ -545,16 +507,16 @@ __device__ uint32_t probe4_w(const Ctx &c, u64 quad, int lane)
             }
         }
         u64 top0, top1, top2;
-        uint32_t hi0 = (uint32_t)(k0 >> 32), mh = quad_min_u(hi0);
-        uint32_t ml = quad_min_u(hi0 == mh ? (uint32_t)k0 : 0xffffffffu);
+        uint32_t hi0 = (uint32_t)(k0 >> 32), mh = lanes_reduce<4>(hi0, u_min);
+        uint32_t ml = lanes_reduce<4>(hi0 == mh ? (uint32_t)k0 : 0xffffffffu, u_min);
         top0 = (u64)mh << 32 | ml;
         if (k0 == top0 && top0 != ~0ull) { k0 = k1; k1 = k2; k2 = ~0ull; }
-        hi0 = (uint32_t)(k0 >> 32); mh = quad_min_u(hi0);
-        ml = quad_min_u(hi0 == mh ? (uint32_t)k0 : 0xffffffffu);
+        hi0 = (uint32_t)(k0 >> 32); mh = lanes_reduce<4>(hi0, u_min);
+        ml = lanes_reduce<4>(hi0 == mh ? (uint32_t)k0 : 0xffffffffu, u_min);
         top1 = (u64)mh << 32 | ml;
         if (k0 == top1 && top1 != ~0ull) { k0 = k1; k1 = k2; k2 = ~0ull; }
-        hi0 = (uint32_t)(k0 >> 32); mh = quad_min_u(hi0);
-        ml = quad_min_u(hi0 == mh ? (uint32_t)k0 : 0xffffffffu);
+        hi0 = (uint32_t)(k0 >> 32); mh = lanes_reduce<4>(hi0, u_min);
+        ml = lanes_reduce<4>(hi0 == mh ? (uint32_t)k0 : 0xffffffffu, u_min);
         top2 = (u64)mh << 32 | ml;
         const u64 mine = sub == 0 ? top0 : (sub == 1 ? top1 : top2);
         const bool have = sub < 3 && mine != ~0ull;
@@ -674,15 +636,6 @@ __device__ int build_board_w(const Ctx &c, uint8_t *slot, u64 seed, int lane, in
 
 // ---- decode (detector.rs:42-169, 448-476; image_util.rs:39-70) -----------------------------------------------------
 
-// decode_positions + bit_code (detector.rs:42-122) of one quad: false = None
-// reductions over the lane's EIGHT (half a row of 16), in every lane of the eight
-template <typename F>
-__device__ __forceinline__ uint32_t half_reduce_u(uint32_t v, F f)
-{
-    v = f(v, dpp_u<0xB1>(v));   // quad_perm [1, 0, 3, 2]
-    v = f(v, dpp_u<0x4E>(v));   // quad_perm [2, 3, 0, 1]
-    return f(v, dpp_u<0x141>(v));  // row_half_mirror
-}
 // decode_positions + bit_code (detector.rs:42-122) of one quad by EIGHT lanes (sub = 0 .. 7 takes every eighth sample of the up to 40:
 // the samples' loads side by side instead of one after the other): AGX_QUAD_DECODED (0) + the bits in every lane of the eight;
 // else the reason for None, in the order the reference meets them (AGX_QUAD_OUTSIDE, _LOW_CONTRAST, _AMBIGUOUS)
@@ -694,71 +647,17 @@ __device__ __forceinline__ int quad_bits8_why(const TailArgs &a, const uint8_t *
         const uint32_t x = f32_as_u32(round_half_away(q[2 * i])), y = f32_as_u32(round_half_away(q[2 * i + 1]));
         outside = outside || x >= w || y >= h;
     }
-    // tag_affine: least squares over the corners of an axis-aligned square, in binary64, rounded once (host_tail.cpp)
     float aff[6];
-    {
-        const int side_bits = a.border * 2 + a.edge;
-        const double S = (double)((float)side_bits - 1.0f + 0.5f), m = 0.5;
-        const double cc = 0.5 * (S - m), aa = 0.5 * (S + m);
-        const double su[4] = {-aa, -aa, aa, aa}, sv[4] = {-aa, aa, aa, -aa};
-#pragma unroll
-        for (int axis = 0; axis < 2; ++axis) {
-            double gu = 0, gv = 0, mean = 0;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const double t = q[2 * p + axis];
-                gu += su[p] * t;
-                gv += sv[p] * t;
-                mean += t;
-            }
-            const double hu = gu / (4.0 * aa * aa), hv = gv / (4.0 * aa * aa);
-            aff[3 * axis + 0] = (float)hu;
-            aff[3 * axis + 1] = (float)hv;
-            aff[3 * axis + 2] = (float)(mean / 4.0 - hu * cc - hv * cc);
-        }
-    }
-    // the samples in the reference's order (x outer, y inner): number sub, sub + 8, ...  (a sample outside the image ends the
-    // reference's loop with None: here it is remembered and the coordinates are clamped)
-    const int nb = a.edge * a.edge, edge = a.edge, border = a.border, pitch = a.luma_row_stride;
-    int lo = 255, hi = 0;
-    int vals[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const int n = sub + 8 * k;
-        const bool valid = n < nb;
-        const int nn = valid ? n : 0;
-        const float fx = (float)(border + nn / edge), fy = (float)(border + nn % edge);
-        const float px = aff[0] * fx + aff[1] * fy + aff[2] * 1.0f;
-        const float py = aff[3] * fx + aff[4] * fy + aff[5] * 1.0f;
-        uint32_t ix = f32_as_u32(round_half_away(px)), iy = f32_as_u32(round_half_away(py));
-        outside = outside || (valid && (ix >= w || iy >= h));
-        ix = ix < w ? ix : w - 1;
-        iy = iy < h ? iy : h - 1;
-        const int b = luma[(size_t)iy * (size_t)pitch + ix];
-        vals[k] = valid ? b : -1;
-        lo = valid && b < lo ? b : lo;
-        hi = valid && b > hi ? b : hi;
-    }
-    lo = (int)half_reduce_u((uint32_t)lo, [](uint32_t x, uint32_t y) { return x < y ? x : y; });
-    hi = (int)half_reduce_u((uint32_t)hi, [](uint32_t x, uint32_t y) { return x > y ? x : y; });
-    outside = half_reduce_u(outside ? 1u : 0u, [](uint32_t x, uint32_t y) { return x | y; }) != 0;
-    if (outside) return AGX_QUAD_OUTSIDE;  // (the eight alike)
-    if (hi - lo < 50) return AGX_QUAD_LOW_CONTRAST;
-    const int mid = (int)(uint8_t)f32_as_u32(round_half_away(((float)lo + (float)hi) / 2.0f));
-    u64 bits = 0;
-    uint32_t invalid = 0;
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-        if (vals[k] >= 0) {  // the first sample is the most significant bit
-            const int b = vals[k], d = mid - b;
-            if ((d < 0 ? -d : d) < 10) ++invalid;
-            if (b > mid) bits |= 1ull << (nb - 1 - (sub + 8 * k));
-        }
-    invalid = half_reduce_u(invalid, [](uint32_t x, uint32_t y) { return x + y; });
-    if (invalid > 3) return AGX_QUAD_AMBIGUOUS;
-    bits_out = (u64)half_reduce_u((uint32_t)(bits >> 32), [](uint32_t x, uint32_t y) { return x | y; }) << 32 |
-               half_reduce_u((uint32_t)bits, [](uint32_t x, uint32_t y) { return x | y; });
-    return AGX_QUAD_DECODED;
+    tag_affine(q, a.border * 2 + a.edge, 0.5f, aff);
+    // the samples in the reference's order (x outer, y inner), evaluated where they are read: none is stored
+    const int edge = a.edge, border = a.border;
+    const auto point = [&](int n, float &px, float &py) {
+        const float fx = (float)(border + n / edge), fy = (float)(border + n % edge);
+        px = aff[0] * fx + aff[1] * fy + aff[2] * 1.0f;
+        py = aff[3] * fx + aff[4] * fy + aff[5] * 1.0f;
+        return true;  // (a sample that overflowed to NaN is pixel 0 to `as u32`, as in the reference)
+    };
+    return bit_code_lanes<8, 5>(luma, w, h, a.luma_row_stride, sub, a.edge * a.edge, 10, 3u, outside, point, bits_out);
 }
 // the same for the board search, which only asks whether there are bits: false = None
 __device__ bool quad_bits8(const TailArgs &a, const uint8_t *luma, const float q[8], int sub, u64 &bits_out)
@@ -766,59 +665,13 @@ __device__ bool quad_bits8(const TailArgs &a, const uint8_t *luma, const float q
     return quad_bits8_why(a, luma, q, sub, bits_out) == AGX_QUAD_DECODED;
 }
 
-// OR over the lane's row of 16, in every lane of the row
-__device__ __forceinline__ uint32_t row_or_u(uint32_t v)
-{
-    v |= dpp_u<0xB1>(v);
-    v |= dpp_u<0x4E>(v);
-    v |= dpp_u<0x141>(v);
-    return v | dpp_u<0x140>(v);
-}
-// rotate_bits (detector.rs:124-140) by a row of 16 lanes: output bit `count` is input bit r + c * edge with
-// count = (edge - 1 - r) * edge + c; every lane sets the output bits l, l + 16, l + 32
-__device__ __forceinline__ u64 rotate_bits_row(u64 bits, int edge, int l)
-{
-    u64 out = 0;
-    for (int count = l; count < edge * edge; count += 16) {
-        const int r = edge - 1 - count / edge, cc = count % edge;
-        out |= ((bits >> (r + cc * edge)) & 1ull) << count;
-    }
-    return (u64)row_or_u((uint32_t)(out >> 32)) << 32 | row_or_u((uint32_t)out);
-}
-
-// best_tag (detector.rs:142-169) by a row of 16 lanes (four quads per wave at a time), the family's codes in LDS.  The
-// reference scans the family once per rotation until one matches; here ONE scan serves the four rotations (every lane takes
-// every 16th code; per rotation the first code with the smallest distance = the smallest (distance, index) pair), then the
-// rotations are looked at in the reference's order -- the same (index, rotation).
+// best_tag (detector.rs:142-169) by a row of 16 lanes (four quads per wave at a time), the family's codes in LDS: the row's one
+// scan for the four rotations, then the rotations in the reference's order (decode_lanes.h) -- the same (index, rotation)
 __device__ bool best_tag_row(const TailArgs &a, const u64 *codes, u64 bits, int l, int &idx, int &rot)
 {
-    const int n_codes = a.n_codes, edge = a.edge;
-    const uint32_t hamming = (uint32_t)a.hamming;
-    const u64 b0 = bits, b1 = rotate_bits_row(b0, edge, l), b2 = rotate_bits_row(b1, edge, l), b3 = rotate_bits_row(b2, edge, l);
-    uint32_t m0 = 0xffffffffu, m1 = 0xffffffffu, m2 = 0xffffffffu, m3 = 0xffffffffu;
-#pragma unroll 2
-    for (int i = l; i < n_codes; i += 16) {
-        const u64 code = codes[i];
-        const uint32_t k0 = (uint32_t)__popcll(code ^ b0) << 16 | (uint32_t)i, k1 = (uint32_t)__popcll(code ^ b1) << 16 | (uint32_t)i;
-        const uint32_t k2 = (uint32_t)__popcll(code ^ b2) << 16 | (uint32_t)i, k3 = (uint32_t)__popcll(code ^ b3) << 16 | (uint32_t)i;
-        m0 = k0 < m0 ? k0 : m0;
-        m1 = k1 < m1 ? k1 : m1;
-        m2 = k2 < m2 ? k2 : m2;
-        m3 = k3 < m3 ? k3 : m3;
-    }
-    m0 = row_min_u(m0);
-    m1 = row_min_u(m1);
-    m2 = row_min_u(m2);
-    m3 = row_min_u(m3);
-    const uint32_t ms[4] = {m0, m1, m2, m3};
-#pragma unroll
-    for (int rotated = 0; rotated < 4; ++rotated)
-        if ((ms[rotated] >> 16) < hamming) {
-            idx = (int)(ms[rotated] & 0xffffu);
-            rot = rotated;
-            return true;
-        }
-    return false;
+    uint32_t ms[4];
+    best_tag_scan(codes, a.n_codes, bits, a.edge, l, ms);
+    return pick_rotation(ms, (uint32_t)a.hamming, idx, rot);
 }
 
 // ---- init_quads (detector.rs:543-586) for the seed s0, by one wave: the candidate quads into the wave's list, in the
@@ -999,8 +852,6 @@ __device__ int init_quads_w(const Ctx &c, uint8_t *wv, int s0, int lane, uint32_
     return nc;
 }
 
-__device__ __forceinline__ bool fb_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
 // The frame's list as k_find_boards, k_grow_boards and k_init_quads take it: the frame's slots, those d_point_status admits, in
 // slot order, into sx / sy / st with slot_of (list position -> slot number within the frame).  Decided before any search, all
 // lanes alike.
@@ -1051,7 +902,7 @@ __device__ __forceinline__ FrameList frame_list(const FindBoardsArgs &b, float *
             x = src[0];
             y = src[1];
             t = src[3];
-            if (!(fb_finite(x) && fb_finite(y) && fb_finite(t))) bad = true;
+            if (!(f32_finite(x) && f32_finite(y) && f32_finite(t))) bad = true;
             // as the chain's lists: coordinates of an image and half an atan2 in degrees; anything else is the host form's business
             else if (!(fabsf(x) < 1e6f && fabsf(y) < 1e6f && t >= -180.0f && t <= 180.0f)) status |= TAIL_CAPACITY;
         }
@@ -2103,7 +1954,6 @@ __global__ void __launch_bounds__(256) k_pack_tags(const uint4 *d_table, const a
 // 256 threads, at least four waves per SIMD (__launch_bounds__'s second argument): at most 128 VGPRs, no scratch.
 constexpr int DQ_THREADS = 256;
 constexpr int DQ_LDS_BYTES = TCODES * 8;
-__device__ __forceinline__ bool dq_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 __global__ void __launch_bounds__(DQ_THREADS, 4) k_decode_quads(DecodeQuadsArgs d)
 {
@@ -2127,11 +1977,8 @@ __global__ void __launch_bounds__(DQ_THREADS, 4) k_decode_quads(DecodeQuadsArgs 
         // a dozen lane masks in SGPR pairs, which the register file does not hold (they were spilled to VGPR lanes)
         int l = l_row;
         asm volatile("" : "+v"(l));
-        const uint32_t f = slot / d.quads_per_frame, qf = slot - f * d.quads_per_frame;
-        if (d.counts) {
-            const uint32_t n_f = d.counts[f];
-            if (qf >= n_f) continue;  // (a count above quads_per_frame: every slot of the frame; slots beyond a count are not written)
-        }
+        if (slot_beyond_count(d.counts, slot, d.quads_per_frame)) continue;  // (slots beyond a count are not written)
+        const uint32_t f = slot / d.quads_per_frame;
         const uint8_t *pts = d.quads + (u64)slot * 4u * (u64)d.point_stride;
         uint32_t why = AGX_QUAD_DECODED;
         if (d.point_status) {
@@ -2148,7 +1995,7 @@ __global__ void __launch_bounds__(DQ_THREADS, 4) k_decode_quads(DecodeQuadsArgs 
                 const float *pp = reinterpret_cast<const float *>(pts + (size_t)p * d.point_stride);
                 q[2 * p] = pp[0];
                 q[2 * p + 1] = pp[1];
-                finite = finite && dq_finite(q[2 * p]) && dq_finite(q[2 * p + 1]);
+                finite = finite && f32_finite(q[2 * p]) && f32_finite(q[2 * p + 1]);
             }
             if (!finite) {
                 why = AGX_QUAD_OUTSIDE;  // before anything of the frame is read
@@ -2160,16 +2007,7 @@ __global__ void __launch_bounds__(DQ_THREADS, 4) k_decode_quads(DecodeQuadsArgs 
         }
         const bool hit = why == AGX_QUAD_DECODED;
         if (l < 9) {
-            uint32_t w = 0;
-            if (hit) {
-                if (l == 0) {
-                    w = (uint32_t)id;
-                } else {  // rotate_left(rot) then reverse, :468-469
-                    const int i = (l - 1) >> 1, c = (l - 1) & 1, src = ((3 - i) + rot) & 3;
-                    w = reinterpret_cast<const uint32_t *>(pts + (size_t)src * d.point_stride)[c];
-                }
-            }
-            reinterpret_cast<uint32_t *>(d.tags + slot)[l] = w;
+            reinterpret_cast<uint32_t *>(d.tags + slot)[l] = tag_word(l, hit, id, rot, pts, d.point_stride);
         } else if (l == 9) {
             d.status[slot] = why;
         } else if (l == 10 && d.bits) {

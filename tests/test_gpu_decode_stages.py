@@ -22,6 +22,7 @@ DECODED, OUTSIDE, LOW_CONTRAST, AMBIGUOUS, NO_MATCH, SKIPPED = range(6)
 SENT = 0x7E7E7E7E
 MARGIN = 64  # sentinel words in front of and behind every output
 W, H = S.PW, S.PH
+S_BT_LDS_CODES = 640  # csrc/decode_stages.h BT_LDS_CODES: the longest code list k_best_tag stages in LDS
 
 
 @pytest.fixture(scope="module")
@@ -267,6 +268,63 @@ def test_best_tag_counts_status_pass_through_aliasing_and_stride_20(det):
     assert np.array_equal(gs[live], hs[live]) and np.array_equal(gi[live], hi[live]) and np.array_equal(gr[live], hr[live])
     assert gt[live].tobytes() == ht[live].tobytes() and (hs[live] == DECODED).sum() >= 8
     assert np.array_equal(gs[~live], s_in[~live]) and (gi[~live] == SENT).all() and (gr[~live] == SENT).all() and (gt[~live] == SENT).all()
+
+
+# ---- where a sampler and a scan written for any lane count and pass count can go wrong ----------------------------------------
+@pytest.mark.parametrize("p", [1, 16, 17, 48, 49, 64])
+def test_bit_code_at_the_pass_boundaries_of_the_row(det, p):
+    """points_per_slot at the ends of the 16-lane form's four passes: the last sample is lane 15's of a pass or lane 0's of the next.
+    Frame 0: noise under random points; frame 1: bright samples exactly at the indices 0, 15, 16, 31, 32, 47, 48, p - 1 (their bits
+    are the ones a wrong pass count drops or misplaces), and the same points with the LAST one outside the image."""
+    import aprilgrid_rs_amd as A
+    rng = np.random.default_rng(100 + p)
+    pts = np.zeros((2, 8, p, 2), np.float32)
+    pts[0] = np.stack([rng.uniform(-0.4, W - 0.6, (8, p)), rng.uniform(-0.4, H - 0.6, (8, p))], axis=-1)
+    grid = S.grid_points(p)
+    pts[1, :] = grid
+    pts[1, 1, p - 1] = (W - 0.5, 3.0)
+    marks = [i for i in (0, 15, 16, 31, 32, 47, 48, p - 1) if i < p]
+    planes = np.stack([rng.integers(0, 256, (H, W), dtype=np.uint8), S.painted(grid, np.where(np.isin(np.arange(p), marks), 210, 20))])
+    bits, st = Guarded((2, 8), np.uint64), Guarded((2, 8), np.uint32)
+    det.bit_code_enqueue(dev(planes), dev(pts), bits.t, st.t, valid_brightness_threshold=10, max_invalid_bit=3)
+    det.sync()
+    hb, hs = host_bit_code_batch(planes, pts)
+    gb, gs = bits.host(), st.host()
+    assert np.array_equal(gs, hs) and np.array_equal(gb, hb), (p, gs, hs, gb, hb)
+    assert hs[1, 1] == OUTSIDE and hs[1, 0] == (LOW_CONTRAST if len(set(marks)) == p else DECODED)
+    if hs[1, 0] == DECODED:
+        assert int(hb[1, 0]) == sum(1 << (p - 1 - i) for i in set(marks))
+
+
+@pytest.mark.parametrize("n", [1, 15, 16, 17, S_BT_LDS_CODES + 1])
+def test_best_tag_best_code_last_and_ties_at_the_list_lengths_of_the_scan(det, n):
+    """Lists that end in lane 0, 14, 15 and 0 of the next pass, and the first length that is read where it lies: the best code is
+    the LAST of the list (exact and one bit away), and two codes at the same distance -- in neighbouring lanes (n - 3, n - 2) and
+    in the same lane a pass apart (n - 17, n - 1: the last code again) -- where the lower index wins."""
+    import aprilgrid_rs_amd as A
+    rng = np.random.default_rng(500 + n)
+    codes = rng.integers(0, 1 << 36, n, dtype=np.uint64)
+    a, b = 0x5A5A5A5A5, 0x3C3C3C3C3
+    probes, want = [], []
+    if n >= 15:
+        codes[n - 3], codes[n - 2] = a, a ^ 0b11
+        probes, want = [a ^ 0b01], [n - 3]
+    if n >= 17:
+        codes[n - 17], codes[n - 1] = b, b ^ 0b11
+        probes, want = probes + [b ^ 0b10], want + [n - 17]
+    last = int(codes[n - 1])
+    bits = np.array(probes + [last, last ^ (1 << 20)], np.uint64)
+    want += [n - 1, n - 1]
+    m = len(bits)
+    quads = rng.uniform(0, 60, (1, m, 8)).astype(np.float32)
+    hi, hr, hs, ht = A.best_tag(bits, 4, codes=codes, edge_bits=6, quads=quads)
+    assert (hs == DECODED).all() and list(hi) == want and (hr == 0).all(), "the inputs are not what the test is about"
+    ids, rots, st, tags = Guarded((1, m), np.uint32), Guarded((1, m), np.uint32), Guarded((1, m), np.uint32), Guarded((1, m, 9), np.uint32)
+    det.best_tag_enqueue(dev(bits.view(np.int64).reshape(1, m)), ids.t, rots.t, st.t, thres=4, codes=dev(codes.view(np.int64)), edge_bits=6,
+                         quads=dev(quads), tags=tags.t)
+    det.sync()
+    assert np.array_equal(st.host()[0], hs) and np.array_equal(ids.host()[0], hi) and np.array_equal(rots.host()[0], hr), n
+    assert tags.host().tobytes() == ht.tobytes(), n
 
 
 # ---- the three chained against the fused kernel -------------------------------------------------------------------------------
