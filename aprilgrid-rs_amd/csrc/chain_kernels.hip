@@ -30,7 +30,9 @@
 //                       (mask -> candidate list -> lock-free union-find -> sums) and its refinement;
 //                       the large-list sort (> 1024 refined records per frame)
 //   k_refine_points     rochade_refine (detector.rs:194-361) of caller-given points, one point per lane, on the
-//                       chain's blur planes or a caller's f32 plane (agx_refine_points_enqueue); not part of the chain
+//                       chain's blur planes or a caller's f32 plane (agx_refine_points_enqueue); not part of the chain.
+//                       Every kernel that refines shares refine_window_inside (except refine_values: integer centroids),
+//                       refine_tail (the fit) and append_refined / write_point_slot (where the record goes)
 //   k_refine_patch<HALF> the same at half_size_patch 1 .. 4, sixteen lanes per point, window and conv outputs in LDS
 //                       (agx_refine_points_enqueue_h); not part of the chain
 #include <hip/hip_runtime.h>
@@ -985,17 +987,21 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(((A4 |
     if (lane == 0 && !known_smaller) atomicMax(&ctr.min_key_inv, ~f32_order_key(run_min));
 }
 
-// The Hessian determinant of pixel c[0] of the blur plane -- same expression, same operands as K1.
-__device__ __forceinline__ float det_at(const float *c, int W)
+// hessian_response of one interior pixel from its 3x3 neighbourhood (image_util.rs:100-104), in the reference's order
+__device__ __forceinline__ float hessian_det(float v11, float v12, float v13, float v21, float v22, float v23, float v31, float v32,
+                                             float v33)
 {
-    const float v11 = c[-W - 1], v12 = c[-W], v13 = c[-W + 1];
-    const float v21 = c[-1], v22 = c[0], v23 = c[1];
-    const float v31 = c[W - 1], v32 = c[W], v33 = c[W + 1];
     const float t22 = v22 * 2.0f;
     const float lxx = (v21 - t22) + v23;
     const float lyy = (v12 - t22) + v32;
     const float lxy = (((v13 - v11) + v31) - v33) * 0.25f;
     return lxx * lyy - lxy * lxy;
+}
+
+// The Hessian determinant of pixel c[0] of the blur plane -- same expression, same operands as K1.
+__device__ __forceinline__ float det_at(const float *c, int W)
+{
+    return hessian_det(c[-W - 1], c[-W], c[-W + 1], c[-1], c[0], c[1], c[W - 1], c[W], c[W + 1]);
 }
 
 // Re-test the set bits of one mask word against the final threshold (exact response from the blur
@@ -1983,17 +1989,6 @@ __device__ __forceinline__ void generic_sums(const ChainArgs &a, int frame, uint
 }
 
 
-// hessian_response of one interior pixel from its 3x3 neighbourhood (image_util.rs:100-104), in the reference's order
-__device__ __forceinline__ float hessian_det(float v11, float v12, float v13, float v21, float v22, float v23, float v31, float v32,
-                                             float v33)
-{
-    const float t22 = v22 * 2.0f;
-    const float lxx = (v21 - t22) + v23;
-    const float lyy = (v12 - t22) + v32;
-    const float lxy = (((v13 - v11) + v31) - v33) * 0.25f;
-    return lxx * lyy - lxy * lxy;
-}
-
 // Debug only (agx_debug_fetch AGX_DBG_RESP): the response plane K2 thresholds, materialised.
 __global__ void k_debug_resp(const float *__restrict__ blur, float *__restrict__ resp, int W, int H)
 {
@@ -2046,18 +2041,100 @@ struct RecSinkLds {
     }
 };
 
+// The f32 centroid of a cluster from its size and integer coordinate sums (detector.rs:427): refine_values' first step, and all
+// that the stages that cluster without refining take from it.
+template <typename SUM>
+__device__ __forceinline__ void cluster_centroid(uint32_t *flags, uint32_t cn, SUM sx, SUM sy, float &cx, float &cy)
+{
+    if (sx >= (1u << 24) || sy >= (1u << 24)) atomicOr(flags, FLAG_CENTROID_INEXACT);
+    const float fn = (float)cn;
+    cx = (float)sx / fn;
+    cy = (float)sy / fn;
+}
+
+enum : uint32_t { POINT_REFINED = 0u, POINT_OUTSIDE = 1u, POINT_NOT_SADDLE = 2u, POINT_MOVED = 3u };  // AGX_POINT_*
+
+// Whether the (4*HALF+1)^2 window of the point rounded to (rxf, ryf) lies in the W x H frame (:266-274).  Decided in float BEFORE
+// anything is converted to int: NaN fails every comparison, infinities and coordinates beyond the int range (undefined in the
+// reference: `as i32`, unchecked indexing) fail the upper bound, and what passes converts to int exactly.
+template <int HALF>
+__device__ __forceinline__ bool refine_window_inside(float x, float y, int W, int H, float &rxf, float &ryf)
+{
+    rxf = roundf(x);
+    ryf = roundf(y);
+    if (!(rxf >= (float)(2 * HALF) && ryf >= (float)(2 * HALF) && rxf <= 1073741824.0f && ryf <= 1073741824.0f)) return false;
+    return (int)ryf + 2 * HALF < H && (int)rxf + 2 * HALF < W;
+}
+
+// The end of rochade_refine, from the six parameter sums on (:330-357): the saddle test, find_xy, the move threshold, k, phi
+// and theta.  The one statement of the fit: every kernel that refines gives the same bytes from the same sums.
+__device__ __forceinline__ uint32_t refine_tail(const float (&prm)[6], float rxf, float ryf, float (&rec)[5])
+{
+    const float a1 = prm[0], a2 = prm[1], a3 = prm[2], a4 = prm[3], a5 = prm[4];
+    const float fxx = 2.0f * a1, fyy = 2.0f * a3, fxy = a2;
+    const float d = fxx * fyy - fxy * fxy;
+    if (!(d < 0.0f)) return POINT_NOT_SADDLE;  // :331-339
+    // find_xy(2a1, a2, a4, a2, 2a3, a5), math_util.rs:5-12: 2x2 LU with row pivoting
+    float x0, y0;
+    {
+        const float A0 = 2.0f * a1, B0 = a2, R0 = -a4;
+        const float A1 = a2, B1 = 2.0f * a3, R1 = -a5;
+        float pa, pb, pr_, qa, qb, qr;
+        if (fabsf(A1) > fabsf(A0)) {
+            pa = A1; pb = B1; pr_ = R1; qa = A0; qb = B0; qr = R0;
+        } else {
+            pa = A0; pb = B0; pr_ = R0; qa = A1; qb = B1; qr = R1;
+        }
+        const float l = qa / pa;
+        const float u22 = qb - l * pb;
+        const float y2 = qr - l * pr_;
+        y0 = y2 / u22;
+        x0 = (pr_ - pb * y0) / pa;
+    }
+    if (!(fabsf(x0) <= 1.0f && fabsf(y0) <= 1.0f)) return POINT_MOVED;  // :342-347
+    const float c5 = (a1 + a3) / 2.0f;
+    const float c4 = (a1 - a3) / 2.0f;
+    const float c3 = a2 / 2.0f;
+    const float k = sqrtf(c4 * c4 + c3 * c3);
+    if (!(fabsf(c5) < k)) return POINT_MOVED;
+    const float PI_F = 3.14159274101257324219f;
+    const float phi = acosf(-c5 / k) / 2.0f / PI_F * 180.0f;
+    const float theta = atan2f(c3, c4) / 2.0f / PI_F * 180.0f;
+    rec[0] = rxf + x0;
+    rec[1] = ryf + y0;
+    rec[2] = k;
+    rec[3] = theta;
+    rec[4] = phi;
+    return POINT_REFINED;
+}
+
+// A refined record (key, then refine_tail's five words) goes to the end of the frame's list.  o < n_clusters <= cap_roots --
+// unless the frame's cluster list has overflowed (the fused flood + refine kernel refines before it knows its record index):
+// such a frame is void as a whole and nothing is stored for it; the bound keeps the store inside the list regardless.
+template <typename SINK, typename CLK>
+__device__ __forceinline__ void append_refined(const ChainArgs &a, int frame, const SINK &sink, uint32_t key, const float (&rec)[5],
+                                               CLK &clk)
+{
+    uint32_t o = atomicAdd(sink.n_refined, 1u);
+    if (CLK::on) {
+        asm volatile("" : "+v"(o));
+        clk.mark(15);  // the record's index (atomic round trip)
+    }
+    if (o >= a.cap_roots) return;
+    const uint32_t f[6] = {key, __float_as_uint(rec[0]), __float_as_uint(rec[1]), __float_as_uint(rec[2]), __float_as_uint(rec[3]), __float_as_uint(rec[4])};
+    sink.put(a, frame, o, f);
+    atomicMax(sink.max_k_bits, __float_as_uint(rec[2]));
+}
+
 template <bool VEC, typename CLK, typename SINK, typename SUM>
 __device__ __forceinline__ void refine_values(const ChainArgs &a, const RefineConsts &rc, int frame, const float *img, int W, int H,
                                               uint32_t key, uint32_t cn, SUM sx, SUM sy, const SINK &sink, float &cx,
                                               float &cy, CLK &clk)
 {
-    if (sx >= (1u << 24) || sy >= (1u << 24)) atomicOr(sink.flags, FLAG_CENTROID_INEXACT);
-    const float fn = (float)cn;
-    const float initial_x = (float)sx / fn;  // detector.rs:427
-    const float initial_y = (float)sy / fn;
-    cx = initial_x;
-    cy = initial_y;
-    const float rxf = roundf(initial_x), ryf = roundf(initial_y);
+    cluster_centroid(sink.flags, cn, sx, sy, cx, cy);
+    // (an integer test, where the caller-given points take refine_window_inside: a centroid is a quotient of pixel sums by a
+    // pixel count -- finite, non-negative and inside the frame by construction)
+    const float rxf = roundf(cx), ryf = roundf(cy);
     const int round_x = (int)rxf, round_y = (int)ryf;
     if (round_y - 4 < 0 || round_y + 4 >= H || round_x - 4 < 0 || round_x + 4 >= W) return;
     // The 9x9 window is streamed row by row through 25 running sums.  Patch value (r,c)
@@ -2141,64 +2218,14 @@ __device__ __forceinline__ void refine_values(const ChainArgs &a, const RefineCo
         asm volatile("" : "+v"(prm[0]), "+v"(prm[1]), "+v"(prm[2]), "+v"(prm[3]), "+v"(prm[4]), "+v"(prm[5]));
         clk.mark(16);  // arithmetic of rows 5..8
     }
-    const float a1 = prm[0], a2 = prm[1], a3 = prm[2], a4 = prm[3], a5 = prm[4];
-    const float fxx = 2.0f * a1, fyy = 2.0f * a3, fxy = a2;
-    const float d = fxx * fyy - fxy * fxy;
-    if (!(d < 0.0f)) return;
-    // find_xy(2a1, a2, a4, a2, 2a3, a5), math_util.rs:5-12: 2x2 LU with row pivoting
-    float x0, y0;
-    {
-        const float A0 = 2.0f * a1, B0 = a2, R0 = -a4;
-        const float A1 = a2, B1 = 2.0f * a3, R1 = -a5;
-        float pa, pb, pr_, qa, qb, qr;
-        if (fabsf(A1) > fabsf(A0)) {
-            pa = A1; pb = B1; pr_ = R1; qa = A0; qb = B0; qr = R0;
-        } else {
-            pa = A0; pb = B0; pr_ = R0; qa = A1; qb = B1; qr = R1;
-        }
-        const float l = qa / pa;
-        const float u22 = qb - l * pb;
-        const float y2 = qr - l * pr_;
-        y0 = y2 / u22;
-        x0 = (pr_ - pb * y0) / pa;
-    }
-    if (!(fabsf(x0) <= 1.0f && fabsf(y0) <= 1.0f)) return;
-    const float c5 = (a1 + a3) / 2.0f;
-    const float c4 = (a1 - a3) / 2.0f;
-    const float c3 = a2 / 2.0f;
-    const float k = sqrtf(c4 * c4 + c3 * c3);
-    if (!(fabsf(c5) < k)) return;
-    const float PI_F = 3.14159274101257324219f;
-    const float phi = acosf(-c5 / k) / 2.0f / PI_F * 180.0f;
-    const float theta = atan2f(c3, c4) / 2.0f / PI_F * 180.0f;
+    float rec[5];
+    if (refine_tail(prm, rxf, ryf, rec) != POINT_REFINED) return;
     if (CLK::on) {
-        float th = theta, ph = phi;
+        float th = rec[3], ph = rec[4];
         asm volatile("" : "+v"(th), "+v"(ph));
         clk.mark(17);  // the fit: divisions, sqrt, acos, atan2 (lanes that pass)
     }
-    uint32_t o = atomicAdd(sink.n_refined, 1u);
-    if (CLK::on) {
-        asm volatile("" : "+v"(o));
-        clk.mark(15);  // the record's index (atomic round trip)
-    }
-    // o < n_clusters <= cap_roots -- unless the frame's cluster list has overflowed (the fused flood + refine kernel
-    // refines before it knows its record index): such a frame is void as a whole and nothing is stored for it
-    if (o >= a.cap_roots) return;
-    const uint32_t f[6] = {key, __float_as_uint(rxf + x0), __float_as_uint(ryf + y0),
-                           __float_as_uint(k),  __float_as_uint(theta),     __float_as_uint(phi)};
-    sink.put(a, frame, o, f);
-    atomicMax(sink.max_k_bits, __float_as_uint(k));
-}
-
-// The f32 centroid of a cluster from its size and integer coordinate sums, as refine_values forms it (detector.rs:427), for the
-// stages that cluster without refining.
-template <typename SUM>
-__device__ __forceinline__ void cluster_centroid(uint32_t *flags, uint32_t cn, SUM sx, SUM sy, float &cx, float &cy)
-{
-    if (sx >= (1u << 24) || sy >= (1u << 24)) atomicOr(flags, FLAG_CENTROID_INEXACT);
-    const float fn = (float)cn;
-    cx = (float)sx / fn;
-    cy = (float)sy / fn;
+    append_refined(a, frame, sink, key, rec, clk);
 }
 
 // rochade_refine of cluster record s of `frame` as generic_frame left it (its sums: generic_sums).
@@ -3373,68 +3400,27 @@ int launch_clear_counters(FrameCounters *ctr, size_t n_records, void *stream)
 
 // ------------------------------------------------------------------------------------------
 // k_refine_points: rochade_refine (detector.rs:194-361, half_size_patch = 2) of CALLER-GIVEN points, one point per
-// lane -- agx_refine_points_enqueue.  The arithmetic is refine_values' from initial_x, initial_y on, restated here
-// so that the chain's kernels compile as they did (tests/test_gpu_refine_points.py holds the two copies together,
-// bit for bit): the 9 x 9 window in two load batches, the 25 running sums in the reference's tap order, the six
-// parameter sums, the 2 x 2 LU with row pivoting, sqrtf / acosf / atan2f.  What differs is around it: the plane has
-// a row pitch (a caller's plane need not be tight, nor 16-byte aligned: VEC = false), every point writes its own
-// slot -- record and status, in input order -- and a point is refused BEFORE anything is converted to int or read:
-// NaN, infinities and coordinates beyond the int range (undefined in the reference: `as i32`, unchecked indexing)
-// are AGX_POINT_OUTSIDE like every point whose window leaves the image.
+// lane -- agx_refine_points_enqueue.  The fit is refine_values' own (refine_tail); the window core -- the 9 x 9 window in two
+// load batches, the 25 running sums in the reference's tap order, the six parameter sums -- stands here a second time (see
+// below).  What differs is around it: the plane has a row pitch (a caller's plane need not be tight, nor 16-byte aligned:
+// VEC = false), every point writes its own slot -- record and status, in input order -- and a point is refused by
+// refine_window_inside BEFORE anything is converted to int or read: NaN, infinities and coordinates beyond the int range are
+// AGX_POINT_OUTSIDE like every point whose window leaves the image.
 // ------------------------------------------------------------------------------------------
-enum : uint32_t { POINT_REFINED = 0u, POINT_OUTSIDE = 1u, POINT_NOT_SADDLE = 2u, POINT_MOVED = 3u };  // AGX_POINT_*
-
-// The end of rochade_refine, from the six parameter sums on (:330-357): the saddle test, find_xy, the move threshold, k, phi
-// and theta.  One copy for k_refine_points and k_refine_patch, so that the two give the same bytes from the same sums.
-__device__ __forceinline__ uint32_t refine_tail(const float (&prm)[6], float rxf, float ryf, float (&rec)[5])
-{
-    const float a1 = prm[0], a2 = prm[1], a3 = prm[2], a4 = prm[3], a5 = prm[4];
-    const float fxx = 2.0f * a1, fyy = 2.0f * a3, fxy = a2;
-    const float d = fxx * fyy - fxy * fxy;
-    if (!(d < 0.0f)) return POINT_NOT_SADDLE;  // :331-339
-    // find_xy(2a1, a2, a4, a2, 2a3, a5), math_util.rs:5-12: 2x2 LU with row pivoting
-    float x0, y0;
-    {
-        const float A0 = 2.0f * a1, B0 = a2, R0 = -a4;
-        const float A1 = a2, B1 = 2.0f * a3, R1 = -a5;
-        float pa, pb, pr_, qa, qb, qr;
-        if (fabsf(A1) > fabsf(A0)) {
-            pa = A1; pb = B1; pr_ = R1; qa = A0; qb = B0; qr = R0;
-        } else {
-            pa = A0; pb = B0; pr_ = R0; qa = A1; qb = B1; qr = R1;
-        }
-        const float l = qa / pa;
-        const float u22 = qb - l * pb;
-        const float y2 = qr - l * pr_;
-        y0 = y2 / u22;
-        x0 = (pr_ - pb * y0) / pa;
-    }
-    if (!(fabsf(x0) <= 1.0f && fabsf(y0) <= 1.0f)) return POINT_MOVED;  // :342-347
-    const float c5 = (a1 + a3) / 2.0f;
-    const float c4 = (a1 - a3) / 2.0f;
-    const float c3 = a2 / 2.0f;
-    const float k = sqrtf(c4 * c4 + c3 * c3);
-    if (!(fabsf(c5) < k)) return POINT_MOVED;
-    const float PI_F = 3.14159274101257324219f;
-    const float phi = acosf(-c5 / k) / 2.0f / PI_F * 180.0f;
-    const float theta = atan2f(c3, c4) / 2.0f / PI_F * 180.0f;
-    rec[0] = rxf + x0;
-    rec[1] = ryf + y0;
-    rec[2] = k;
-    rec[3] = theta;
-    rec[4] = phi;
-    return POINT_REFINED;
-}
-
 template <bool VEC>
 __device__ __forceinline__ uint32_t refine_point(const RefineConsts &rc, const float *img, size_t pitch, int W, int H, float initial_x,
                                                  float initial_y, float (&rec)[5])
 {
-    const float rxf = roundf(initial_x), ryf = roundf(initial_y);
-    // :266-274, decided in float: NaN fails every comparison, and what passes converts to int exactly
-    if (!(rxf >= 4.0f && ryf >= 4.0f && rxf <= 1073741824.0f && ryf <= 1073741824.0f)) return POINT_OUTSIDE;
+    float rxf, ryf;
+    if (!refine_window_inside<2>(initial_x, initial_y, W, H, rxf, ryf)) return POINT_OUTSIDE;
     const int round_x = (int)rxf, round_y = (int)ryf;
-    if (round_y + 4 >= H || round_x + 4 >= W) return POINT_OUTSIDE;
+    // From here to refine_tail: refine_values' window core with `pitch` for W and without the CLK marks, the one piece of
+    // rochade_refine that stands twice (tests/test_gpu_refine_points.py holds the two together, bit for bit).  One
+    // refine_window_sums<VEC, CLK>(rc, win, pitch, al, prm, clk) for both was tried in three forms -- the callers' raw / conv /
+    // prm arrays passed by reference; `fetch` as a free function template; refine_values' text kept to the letter with the pitch's
+    // type a template parameter (int on the chain's plane) -- and each took k_sparse_frame<true, NoClock>, the benchmark's sparse
+    // kernel, from 127 to 128 VGPRs and from 19 201 to 19 780 / 19 737 / 19 737 instructions (<false, NoClock> 19 023 -> 19 049 /
+    // 19 057 / 19 057; k_flood_refine<*, NoClock> and k_rare within 10): the register count had to stay, so none was timed.
     const int wx0 = round_x - 4;
     const int al = VEC ? (wx0 & 3) : 0;
     const float *win = img + (size_t)(round_y - 4) * pitch + (wx0 - al);
@@ -3495,6 +3481,14 @@ __device__ __forceinline__ uint32_t refine_point(const RefineConsts &rc, const f
     return refine_tail(prm, rxf, ryf, rec);
 }
 
+// A point's slot: its record -- five zeros unless it refined -- and its status.
+__device__ __forceinline__ void write_point_slot(const RefinePointsArgs &p, size_t slot, uint32_t st, const float (&rec)[5])
+{
+#pragma unroll
+    for (int q = 0; q < 5; ++q) p.out[slot * 5 + q] = st == POINT_REFINED ? rec[q] : 0.0f;
+    p.status[slot] = st;
+}
+
 // grid (ceil(points_per_frame / 64), n_frames): point i of frame f reads points[f * ppf + i] and writes record and status
 // [f * ppf + i]; slots at or beyond the frame's count are left alone.
 template <bool VEC>
@@ -3507,10 +3501,7 @@ __global__ void __launch_bounds__(64) k_refine_points(RefinePointsArgs p, Refine
     const size_t slot = (size_t)f * p.points_per_frame + i;
     const float x = p.points[2 * slot], y = p.points[2 * slot + 1];
     float rec[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    const uint32_t st = refine_point<VEC>(rc, p.img + (size_t)f * (size_t)p.frame_stride, (size_t)p.pitch, p.W, p.H, x, y, rec);
-#pragma unroll
-    for (int q = 0; q < 5; ++q) p.out[slot * 5 + q] = st == POINT_REFINED ? rec[q] : 0.0f;
-    p.status[slot] = st;
+    write_point_slot(p, slot, refine_point<VEC>(rc, p.img + (size_t)f * (size_t)p.frame_stride, (size_t)p.pitch, p.W, p.H, x, y, rec), rec);
 }
 
 int launch_refine_points(const RefinePointsArgs &p, const RefineConsts &rc, int n_frames, void *stream)
@@ -3597,13 +3588,7 @@ __global__ void __launch_bounds__(64) k_refine_patch(RefinePointsArgs p, const R
     const size_t slot = (size_t)f * p.points_per_frame + (live ? i : 0u);
     float rxf = 0.0f, ryf = 0.0f;
     bool inside = false;
-    if (live) {
-        rxf = roundf(p.points[2 * slot]);
-        ryf = roundf(p.points[2 * slot + 1]);
-        // :266-274, decided in float: NaN fails every comparison, and what passes converts to int exactly
-        inside = rxf >= (float)(2 * HALF) && ryf >= (float)(2 * HALF) && rxf <= 1073741824.0f && ryf <= 1073741824.0f;
-        if (inside) inside = (int)ryf + 2 * HALF < p.H && (int)rxf + 2 * HALF < p.W;
-    }
+    if (live) inside = refine_window_inside<HALF>(p.points[2 * slot], p.points[2 * slot + 1], p.W, p.H, rxf, ryf);
     const float *win = p.img;
     if (inside) win = p.img + (size_t)f * (size_t)p.frame_stride + (size_t)((int)ryf - 2 * HALF) * (size_t)p.pitch + ((int)rxf - 2 * HALF);
     refine_patch_body<HALF>(s, g, l, inside, win, (size_t)p.pitch, rc);
@@ -3614,9 +3599,7 @@ __global__ void __launch_bounds__(64) k_refine_patch(RefinePointsArgs p, const R
         const float prm[6] = {s.prm[g][0], s.prm[g][1], s.prm[g][2], s.prm[g][3], s.prm[g][4], s.prm[g][5]};
         st = refine_tail(prm, rxf, ryf, rec);
     }
-#pragma unroll
-    for (int q = 0; q < 5; ++q) p.out[slot * 5 + q] = st == POINT_REFINED ? rec[q] : 0.0f;
-    p.status[slot] = st;
+    write_point_slot(p, slot, st, rec);
 }
 
 int launch_refine_patch(const RefinePointsArgs &p, const RefinePatchConsts *consts, int half, int n_frames, void *stream)
@@ -3691,28 +3674,16 @@ __global__ void __launch_bounds__(64) k_refine_clusters(ChainArgs a, const Refin
         const bool live = i < n;
         float rxf = 0.0f, ryf = 0.0f;
         bool inside = false;
-        if (live) {
-            rxf = roundf(__uint_as_float(a.clu_sx[cbase + i]));
-            ryf = roundf(__uint_as_float(a.clu_sy[cbase + i]));
-            // :266-274 in float, as k_refine_patch decides it (a centroid lies inside the frame; NaN -- a corrupted table -- fails)
-            inside = rxf >= (float)(2 * HALF) && ryf >= (float)(2 * HALF) && rxf <= 1073741824.0f && ryf <= 1073741824.0f;
-            if (inside) inside = (int)ryf + 2 * HALF < a.H && (int)rxf + 2 * HALF < a.W;
-        }
+        // (a centroid lies inside the frame; NaN -- a corrupted table -- fails like any caller's point)
+        if (live) inside = refine_window_inside<HALF>(__uint_as_float(a.clu_sx[cbase + i]), __uint_as_float(a.clu_sy[cbase + i]), a.W, a.H, rxf, ryf);
         const float *win = img;
         if (inside) win = img + (size_t)((int)ryf - 2 * HALF) * (size_t)a.W + ((int)rxf - 2 * HALF);
         refine_patch_body<HALF>(s, g, l, inside, win, (size_t)a.W, rc);
         if (inside && l == 0) {
             const float prm[6] = {s.prm[g][0], s.prm[g][1], s.prm[g][2], s.prm[g][3], s.prm[g][4], s.prm[g][5]};
             float rec[5];
-            if (refine_tail(prm, rxf, ryf, rec) == POINT_REFINED) {
-                const uint32_t o = atomicAdd(sink.n_refined, 1u);
-                if (o < a.cap_roots) {  // (o < n_clusters <= cap_roots always here; the bound keeps the store inside the list regardless)
-                    const uint32_t f6[6] = {a.clu_key[cbase + i],    __float_as_uint(rec[0]), __float_as_uint(rec[1]),
-                                            __float_as_uint(rec[2]), __float_as_uint(rec[3]), __float_as_uint(rec[4])};
-                    sink.put(a, frame, o, f6);
-                    atomicMax(sink.max_k_bits, __float_as_uint(rec[2]));
-                }
-            }
+            NoClock clk;
+            if (refine_tail(prm, rxf, ryf, rec) == POINT_REFINED) append_refined(a, frame, sink, a.clu_key[cbase + i], rec, clk);
         }
         // (the next round's first LDS write of a region comes behind a barrier that follows this round's last read of it)
     }
@@ -3898,6 +3869,42 @@ int launch_hessian_response(const HessianArgs &a, int format, int n_frames, void
 }
 
 // ------------------------------------------------------------------------------------------
+// What the two exact fronts below (k_response_front, k_plane_front) share: a wave owns 64 columns x one word row, lane = column.
+// ------------------------------------------------------------------------------------------
+// The maximum over lanes 4k .. 4k + 3 in each of them (quad_perm [1,0,3,2], then [2,3,0,1]; every lane has a source).
+__device__ __forceinline__ float quad_max_f32(float v)
+{
+    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false)));
+    return fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, false)));
+}
+// Column x < W of word row yb: the lane's mask word, and from the first lane of a quad the 4-column block's cand_max.
+__device__ __forceinline__ void store_mask_word(const ChainArgs &a, int frame, int yb, int x, int lane, uint32_t word, float cmax)
+{
+    a.mask[(size_t)frame * (size_t)a.mask_plane + (size_t)yb * (size_t)a.mask_wpr + (size_t)(MASK_PAD_X + x)] = word;
+    if ((lane & 3) == 0)
+        a.cand_max[((size_t)frame * (size_t)a.mask_yb + (size_t)yb) * (size_t)(a.mask_wpr >> 2) + (size_t)((MASK_PAD_X + x) >> 2)] = cmax;
+}
+// The wave's fold goes to the frame's minimum word: reduced by DPP, one atomicMax of ~order_key per wave.
+__device__ __forceinline__ void publish_frame_min(FrameCounters &ctr, float run_min, int lane)
+{
+    run_min = wave_min_f32(run_min);
+    if (lane == 0) atomicMax(&ctr.min_key_inv, ~f32_order_key(run_min));
+}
+// The fronts' two launches, the minimum and then the mask, on one grid: 64 columns x four word rows to a workgroup.
+template <typename... REST>
+static int launch_front_pair(void (*k_min)(ChainArgs, REST...), void (*k_mask)(ChainArgs, REST...), const ChainArgs &a, void *stream,
+                             REST... rest)
+{
+    const int n_yb = (a.H + 31) >> 5;
+    const dim3 grid((unsigned)((a.W + 63) / 64), (unsigned)std::min((n_yb + 3) / 4, 65535), (unsigned)a.n_frames), block(64, 4);
+    hipLaunchKernelGGL(k_min, grid, block, 0, (hipStream_t)stream, a, rest...);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_mask, grid, block, 0, (hipStream_t)stream, a, rest...);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
 // k_response_front: the chain's front for a blur sigma other than 1.5.  k_gauss_blur has written the workspace blur plane;
 // this kernel derives from it the other three products K1 hands to the sparse stages ("Two fronts, one
 // contract"), in two launches:
@@ -3952,32 +3959,17 @@ __global__ void __launch_bounds__(256) k_response_front(ChainArgs a)
             v21 = v31, v22 = v32, v23 = v33;
         }
         if (MASK) {
-            // the block's maximum: lanes 4k .. 4k + 3 (quad_perm [1,0,3,2], then [2,3,0,1]; every lane has a source)
-            cmax = fmaxf(cmax, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cmax), 0xB1, 0xf, 0xf, false)));
-            cmax = fmaxf(cmax, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cmax), 0x4E, 0xf, 0xf, false)));
-            if (x < W) {
-                a.mask[(size_t)frame * (size_t)a.mask_plane + (size_t)yb * (size_t)a.mask_wpr + (size_t)(MASK_PAD_X + x)] = word;
-                if ((lane & 3) == 0)
-                    a.cand_max[((size_t)frame * (size_t)a.mask_yb + (size_t)yb) * (size_t)(a.mask_wpr >> 2) + (size_t)((MASK_PAD_X + x) >> 2)] = cmax;
-            }
+            cmax = quad_max_f32(cmax);
+            if (x < W) store_mask_word(a, frame, yb, x, lane, word, cmax);
         }
     }
-    if (!MASK) {
-        run_min = wave_min_f32(run_min);
-        if (lane == 0) atomicMax(&ctr.min_key_inv, ~f32_order_key(run_min));
-    }
+    if (!MASK) publish_frame_min(ctr, run_min, lane);
 }
 
 int launch_response_front(const ChainArgs &a, void *stream)
 {
     if (a.n_frames <= 0 || a.n_frames > 65535 || a.W < 2 || a.H < 2) return (int)hipErrorInvalidValue;
-    const int n_yb = (a.H + 31) >> 5;
-    const dim3 grid((unsigned)((a.W + 63) / 64), (unsigned)std::min((n_yb + 3) / 4, 65535), (unsigned)a.n_frames), block(64, 4);
-    hipLaunchKernelGGL((k_response_front<false>), grid, block, 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_response_front<true>), grid, block, 0, (hipStream_t)stream, a);
-    return hipGetLastError();
+    return launch_front_pair(k_response_front<false>, k_response_front<true>, a, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -4032,35 +4024,22 @@ __global__ void __launch_bounds__(256) k_plane_front(ChainArgs a, PlaneFrontArgs
             }
         }
         if (MASK) {
-            // the block's maximum: lanes 4k .. 4k + 3 (quad_perm [1,0,3,2], then [2,3,0,1]; every lane has a source)
-            cmax = fmaxf(cmax, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cmax), 0xB1, 0xf, 0xf, false)));
-            cmax = fmaxf(cmax, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cmax), 0x4E, 0xf, 0xf, false)));
-            if (col) {
-                a.mask[(size_t)frame * (size_t)a.mask_plane + (size_t)yb * (size_t)a.mask_wpr + (size_t)(MASK_PAD_X + x)] = word;
-                if ((lane & 3) == 0)
-                    a.cand_max[((size_t)frame * (size_t)a.mask_yb + (size_t)yb) * (size_t)(a.mask_wpr >> 2) + (size_t)((MASK_PAD_X + x) >> 2)] = cmax;
-            }
+            cmax = quad_max_f32(cmax);
+            if (col) store_mask_word(a, frame, yb, x, lane, word, cmax);
         }
     }
     if (MASK) {
         const bool any_ring = __ballot(ring_below) != 0ull;
         if (any_ring && lane == 0 && W >= 3 && H >= 3) atomicOr(&ctr.flags, FLAG_RING_BELOW);
     } else {
-        run_min = wave_min_f32(run_min);
-        if (lane == 0) atomicMax(&ctr.min_key_inv, ~f32_order_key(run_min));
+        publish_frame_min(ctr, run_min, lane);
     }
 }
 
 int launch_plane_front(const ChainArgs &a, const PlaneFrontArgs &p, void *stream)
 {
     if (a.n_frames <= 0 || a.n_frames > 65535 || a.W < 2 || a.H < 2 || !p.src || p.row_stride < a.W) return (int)hipErrorInvalidValue;
-    const int n_yb = (a.H + 31) >> 5;
-    const dim3 grid((unsigned)((a.W + 63) / 64), (unsigned)std::min((n_yb + 3) / 4, 65535), (unsigned)a.n_frames), block(64, 4);
-    hipLaunchKernelGGL((k_plane_front<false>), grid, block, 0, (hipStream_t)stream, a, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_plane_front<true>), grid, block, 0, (hipStream_t)stream, a, p);
-    return hipGetLastError();
+    return launch_front_pair(k_plane_front<false>, k_plane_front<true>, a, stream, p);
 }
 
 // The ordered emission of a frame's cluster table by one workgroup.  The table's records are final (first pixel, size, f32

@@ -341,6 +341,47 @@ def test_staged_detect_equals_detect_batch(boards):
         d.close()
 
 
+def test_both_exact_fronts_and_the_fused_front_alternate_on_one_handle():
+    """agx_clusters_enqueue (k_plane_front), a chain batch at sigma 2.0 (k_response_front) and one at sigma 1.5 (K1) take turns on
+    one handle and one mask: every word of the image area is written in every batch ("Two fronts, one contract"), so
+    no batch sees a bit of the one before.  70 x 40: two waves across with a partial second, two word rows with a partial second.
+    The planes are another image's responses than the chain's frames: a word left unwritten would hold foreign bits."""
+    import aprilgrid_rs_amd as A
+    from tests import sigma_oracle
+    from tests.util import check_saddles
+    w, h = 70, 40
+    y, x = np.mgrid[0:h, 0:w]
+    rng = np.random.default_rng(11)
+    def board(dx, dy):
+        return (((x + dx) // 6 + (y + dy) // 6) % 2 * 180 + 30 + rng.integers(0, 8, (h, w))).astype(np.uint8)
+    frames = np.stack([board(0, 0), board(1, 1)])
+    others = [board(3, 3), board(5, 2)]
+    planes = np.stack([sigma_oracle.refined_saddle_points(f, 2.0)[1]["resp"] for f in others])
+    want = [K.expected_of(p) for p in planes]
+    refs = {sg: [sigma_oracle.refined_saddle_points(f, sg) for f in frames] for sg in (2.0, 1.5)}
+    for rows, st in want:  # premise: clusters in the second wave's columns and in the second word row
+        assert st == K.OK and (rows["cx"] >= 64).any() and (rows["cy"] >= 32).any() and len(rows) >= 8
+    for sg in refs:
+        for ref, dbg in refs[sg]:
+            assert len(ref) >= 4 and (dbg["centers"][:, 0] >= 64).any() and (dbg["centers"][:, 1] >= 32).any(), "premise"
+    d = A.TagDetector("t36h11", None, device=0)
+    try:
+        d_planes, d_frames = dev(planes), dev(frames)
+        for turn in range(2):
+            rows, pts, counts, status = run_caller_owned(d, d_planes, cpf=128)  # (84 and 72 clusters)
+            for f, (wr, wst) in enumerate(want):
+                assert status[f] == wst and counts[f] == len(wr) and rows[f, :len(wr)].tobytes() == wr.tobytes(), "turn %d: plane %d" % (turn, f)
+            for sg, front in ((2.0, 1), (1.5, 0)):
+                d.set_blur_sigma(sg)
+                d.saddles_batch_enqueue(d_frames)
+                res, st = d.saddles_batch_fetch()
+                assert (st == 0).all() and d.get_option("last_chain_front") == front
+                for f in range(2):
+                    check_saddles(res[f], refs[sg][f][0], "turn %d: sigma %g frame %d" % (turn, sg, f))
+    finally:
+        d.close()
+
+
 # ---- 3. the filter ----------------------------------------------------------------------------------------------------------
 def test_filter_edges_counts_and_the_host_form(det):
     import aprilgrid_rs_amd as A

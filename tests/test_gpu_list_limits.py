@@ -431,20 +431,27 @@ def test_detect_batch_with_max_saddles_one_below(mixed, device_tail):
     d.close()
 
 
-@pytest.mark.parametrize("mode", ["half_size_patch_3", "blur_sigma_2"])
+@pytest.mark.parametrize("mode", ["half_size_patch_3", "blur_sigma_2", "chain_refine_general"])
 def test_deferred_refinement_and_any_sigma_front(mixed, mode):
-    """half_size_patch 3: k_refine_clusters behind flood stages that only cluster; sigma 2: the any-sigma response front."""
+    """half_size_patch 3: k_refine_clusters behind flood stages that only cluster; sigma 2: the any-sigma response front;
+    chain_refine_general: the deferred plan at the reference's half 2 -- k_refine_clusters appends through the same append_refined
+    as the fused kernels, and the seed list one short must void the frame there too."""
     host, dev, counts = mixed
     pick = [0, 1, 2, L.I_NOISE, L.I_FLAT]
     sub = cuda(host[pick])
     if mode == "half_size_patch_3":
         kw, orc = dict(half_size_patch=3), (lambda img: patch_oracle.refined_saddle_points(img, 1.5, 3))
-    else:
+    elif mode == "blur_sigma_2":
         kw, orc = dict(blur_sigma=2.0), (lambda img: sigma_oracle.refined_saddle_points(img, 2.0))
+    else:
+        kw, orc = dict(), (lambda img: patch_oracle.refined_saddle_points(img, 1.5, 2))
     refs = [orc(np.ascontiguousarray(host[i])) for i in pick]
     csub = [L.counts_of(*r) for r in refs]
     d = make("path1", **kw)
+    if mode == "chain_refine_general":
+        d.set_option("chain_refine_general", 1)
     base = Run(d, sub, max(c["n_saddles"] for c in csub) + 2)
+    assert d.get_option("last_chain_refine") == (0 if mode == "blur_sigma_2" else 1), "premise: the plan that ran"
     for i, (c, (ref, dbg)) in enumerate(zip(csub, refs)):
         what = "premise (%s, frame %d)" % (mode, i)
         print(what, base.ctr[i], c)

@@ -319,6 +319,44 @@ def test_edge_coordinates(det, oracle, case1, half):
     assert (st[0][off2] == OUTSIDE).all()
 
 
+def placement_points(w, h, half):
+    """Rounded coordinates exactly at the first and last allowed value (inside), one beyond each (outside), the x.5 values that
+    roundf takes away from zero onto either, and what no int can hold."""
+    m = 2 * half
+    xs = [m, w - 1 - m, m - 1, w - m, m - 0.5, m - 1.5, w - 1 - m + 0.5, w - 1 - m - 0.5, -0.5]
+    ys = [m, h - 1 - m, m - 1, h - m, m - 0.5, m - 1.5, h - 1 - m + 0.5, h - 1 - m - 0.5, -0.5]
+    bad = [float("nan"), float("inf"), float("-inf"), 2147483648.0, -2147483648.0]
+    pts = [(vx, float(m)) for vx in xs + bad] + [(float(m), vy) for vy in ys + bad] + [(w - 1 - m, h - 1 - m), (w - m, h - m)]
+    return np.array(pts, np.float32)
+
+
+@pytest.mark.parametrize("half", HALVES)
+def test_window_placement_on_the_smallest_plane_with_an_interior_at_half_4(det, oracle, half):
+    """24 x 20: a 17 x 17 window still has 8 x 4 places.  Statuses and records are the oracle's at every half; at 2 the one-lane
+    kernel and the sixteen-lane kernel decide every point alike, byte for byte."""
+    w, h = 24, 20
+    plane = saddle_plane(w, h, half)
+    pts = placement_points(w, h, half)
+    rule = outside_rule(pts, w, h, half)
+    m = 2 * half
+    assert list(rule[:9]) == [False, False, True, True, False, True, True, False, True] and rule[9:14].all(), "premise: the x sweep"
+    assert list(rule[14:23]) == [False, False, True, True, False, True, True, False, True] and rule[23:28].all(), "premise: the y sweep"
+    assert not rule[28] and rule[29]
+    d_plane = dev(plane)  # (kept alive across the calls that are given its address)
+    rec, st = run_raw(det, d_plane.data_ptr(), 1, w, h, 4 * w, 4 * w * h, LF32, PLANE, pts[None], half)
+    assert det.get_option("last_refine_kernel") == (0 if half == 2 else 1)
+    check_points(oracle, plane, pts, rec[0], st[0], half, "placement on 24 x 20")
+    assert (st[0][rule] == OUTSIDE).all() and (st[0][~rule] != OUTSIDE).all()
+    if half == 2:
+        det.set_option("refine_general_kernel", 1)
+        try:
+            rec_g, st_g = run_raw(det, d_plane.data_ptr(), 1, w, h, 4 * w, 4 * w * h, LF32, PLANE, pts[None], half)
+            assert det.get_option("last_refine_kernel") == 1
+        finally:
+            det.set_option("refine_general_kernel", 0)
+        assert rec_g.tobytes() == rec.tobytes() and st_g.tobytes() == st.tobytes()
+
+
 @pytest.mark.parametrize("half", HALVES)
 def test_a_frame_smaller_than_the_window_has_only_outside_points(det, oracle, half):
     rng = np.random.default_rng(4)
