@@ -21,6 +21,9 @@ AGX_POINT_REFINED, AGX_POINT_OUTSIDE, AGX_POINT_NOT_SADDLE, AGX_POINT_MOVED = 0,
 AGX_REFINE_BLURRED, AGX_REFINE_PLANE = 0, 1
 # try_decode_quad of caller-given quads (src/detector.rs:448-476): what became of a quad
 AGX_QUAD_DECODED, AGX_QUAD_OUTSIDE, AGX_QUAD_LOW_CONTRAST, AGX_QUAD_AMBIGUOUS, AGX_QUAD_NO_MATCH, AGX_QUAD_SKIPPED = 0, 1, 2, 3, 4, 5
+# the sampling model of decode_positions (src/image_util.rs:39-70 tag_affine, :5-37 tag_homography); the homography's refusal
+AGX_TAG_MAP_AFFINE, AGX_TAG_MAP_HOMOGRAPHY = 0, 1
+AGX_QUAD_DEGENERATE = 6
 # try_find_best_board of caller-given saddle lists (src/detector.rs:588-639): what became of a frame
 AGX_BOARD_FOUND, AGX_BOARD_NONE, AGX_BOARD_CAPACITY, AGX_BOARD_INPUT, AGX_BOARD_PENDING = 0, 1, 2, 3, 4
 AGX_GROW_FIX_MISSING = 1  # agx_grow_boards_enqueue / agx_grow_board_tail: flags
@@ -110,6 +113,11 @@ SYMBOLS = {
     "agx_decode_positions_enqueue": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_float,
                                                _P, _P]),
     "agx_decode_positions_tail": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_float, _P, _P]),
+    "agx_decode_positions_enqueue_m": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_float,
+                                                 _P, _P, C.c_int]),
+    "agx_decode_positions_tail_m": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_float, _P, _P, C.c_int]),
+    "agx_tag_maps_enqueue": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_uint32, _P, _P, C.c_int, C.c_float, C.c_int, _P, _P]),
+    "agx_tag_maps_tail": (C.c_int, [_P, C.c_uint32, C.c_int, C.c_float, C.c_int, _P, _P]),
     "agx_bit_code_enqueue": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, _P, C.c_uint32, C.c_uint32, _P, _P,
                                        C.c_int, C.c_uint32, _P, _P]),
     "agx_bit_code_tail": (C.c_int, [_P, C.c_int, C.c_int, C.c_size_t, _P, C.c_uint32, C.c_uint32, _P, C.c_int, C.c_uint32, _P, _P]),

@@ -27,6 +27,25 @@ struct DecodePositionsArgs {
 };
 // one row of 16 lanes per slot, grid-stride; n_frames * quads_per_frame < 2^31; hipError_t
 int launch_decode_positions(const DecodePositionsArgs &p, void *stream);
+// k_positions_homography (agx_decode_positions_enqueue_m at AGX_TAG_MAP_HOMOGRAPHY): the same arguments, the samples through
+// tag_homography (image_util.rs:5-37); status also AGX_QUAD_DEGENERATE, and AGX_QUAD_OUTSIDE for a sample whose w is not > 0
+int launch_positions_homography(const DecodePositionsArgs &p, void *stream);
+
+// k_tag_maps (agx_tag_maps_enqueue): tag_affine / tag_homography themselves.  All pointers are device pointers.
+struct TagMapsArgs {
+    const uint8_t *quads;  // as DecodePositionsArgs
+    uint32_t point_stride;
+    int n_frames;
+    uint32_t quads_per_frame;
+    const uint32_t *counts;
+    const uint32_t *point_status;
+    int side_bits;  // 1 .. 40
+    float margin;
+    int model;         // AGX_TAG_MAP_*
+    float *maps;       // [slots][9] row-major 3 x 3; written for AGX_QUAD_DECODED slots only
+    uint32_t *status;  // [slots]: AGX_QUAD_DECODED, _OUTSIDE (a corner that is not finite), _SKIPPED or _DEGENERATE
+};
+int launch_tag_maps(const TagMapsArgs &p, void *stream);
 
 // k_bit_code (agx_bit_code_enqueue).  All pointers are device pointers.
 struct BitCodeArgs {

@@ -3,6 +3,9 @@
 //   k_decode_positions   decode_positions (detector.rs:42-72): the sample points of every quad slot, stored
 //   k_bit_code           bit_code (:74-122) over ANY list of up to 64 sample points per slot
 //   k_best_tag           best_tag (:142-169) against ANY code list of up to 65535 codes
+// and the sampling model opened (image_util.rs:5-37, :39-70):
+//   k_positions_homography   decode_positions with tag_homography in tag_affine's place (agx_decode_positions_enqueue_m)
+//   k_tag_maps               tag_affine / tag_homography themselves, a 3 x 3 matrix per slot (agx_tag_maps_enqueue)
 // k_decode_quads (tail_kernels.hip) stays the fused form with the reference's constants; these three chained give its bytes
 // (tests/test_gpu_decode_stages.py), and the two forms run the same code: the scalar arithmetic of decode_math.h (tag_affine,
 // binary64 and rounded once, with `margin` where the fused kernel passes 0.5; f32::round; Rust's saturating `as u32`; the finite
@@ -67,6 +70,93 @@ __global__ void __launch_bounds__(DS_THREADS, 4) k_decode_positions(DecodePositi
             }
         }
         if (l == 0) d.status[slot] = why;
+    }
+}
+
+// ---- agx_decode_positions_enqueue_m at AGX_TAG_MAP_HOMOGRAPHY, agx_tag_maps_enqueue (image_util.rs:5-37, :39-70) ---------------
+// The front of a slot as k_decode_positions has it: the point statuses, then the four corners -> AGX_QUAD_DECODED and q, or
+// AGX_QUAD_SKIPPED / AGX_QUAD_OUTSIDE.  image: the corners are tested against W x H (:50-56) too.
+__device__ __forceinline__ uint32_t slot_corners(const uint8_t *quads, uint32_t point_stride, const uint32_t *point_status, uint32_t slot, bool image,
+                                                 uint32_t W, uint32_t H, float q[8])
+{
+    if (point_status) {
+        const uint32_t *ps = point_status + (u64)slot * 4u;
+        if ((ps[0] | ps[1] | ps[2] | ps[3]) != 0u) return AGX_QUAD_SKIPPED;  // (AGX_POINT_REFINED is 0)
+    }
+    const uint8_t *pts = quads + (u64)slot * 4u * (u64)point_stride;
+    bool finite = true, outside = false;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const float *pp = reinterpret_cast<const float *>(pts + (size_t)p * point_stride);
+        q[2 * p] = pp[0];
+        q[2 * p + 1] = pp[1];
+        finite = finite && f32_finite(q[2 * p]) && f32_finite(q[2 * p + 1]);
+        outside = outside || (image && (f32_as_u32(round_half_away(q[2 * p])) >= W || f32_as_u32(round_half_away(q[2 * p + 1])) >= H));
+    }
+    return !finite || outside ? (uint32_t)AGX_QUAD_OUTSIDE : (uint32_t)AGX_QUAD_DECODED;
+}
+
+// k_decode_positions' scheme.  Every lane of the row evaluates the slot's map -- the closed form's three binary64 divisions
+// included: the row's lanes issue together, so one lane evaluating for the others would take the wave the same time and add
+// nine broadcasts.  A pass first decides the slot (every sample's w), the row's verdict by DPP, then a second pass stores.
+__global__ void __launch_bounds__(DS_THREADS, 4) k_positions_homography(DecodePositionsArgs d)
+{
+    const int l = (int)(threadIdx.x & 15u);
+    const uint32_t n_slots = (uint32_t)d.n_frames * d.quads_per_frame, step = gridDim.x * (DS_THREADS / 16);
+    const int nb = d.edge * d.edge;
+    for (uint32_t slot = blockIdx.x * (DS_THREADS / 16) + (threadIdx.x >> 4); slot < n_slots; slot += step) {
+        if (slot_beyond_count(d.counts, slot, d.quads_per_frame)) continue;
+        float q[8], h[9];
+        uint32_t why = slot_corners(d.quads, d.point_stride, d.point_status, slot, true, d.W, d.H, q);
+        if (why == AGX_QUAD_DECODED && !tag_homography(q, d.border * 2 + d.edge, d.margin, h)) why = AGX_QUAD_DEGENERATE;
+        if (why == AGX_QUAD_DECODED) {  // (the row alike: its lanes read the same corners)
+            uint32_t bad = 0;
+            for (int n = l; n < nb; n += 16)
+                if (!homography_w_ok(homography_w(h, (float)(d.border + n / d.edge), (float)(d.border + n % d.edge)))) bad = 1;
+            if (lanes_reduce<16>(bad, u_or)) {
+                why = AGX_QUAD_OUTSIDE;
+            } else {
+                float *out = d.points + (u64)slot * (u64)(2 * nb);
+                for (int n = l; n < nb; n += 16) {  // the reference's order: x outer, y inner
+                    const float fx = (float)(d.border + n / d.edge), fy = (float)(d.border + n % d.edge);
+                    float px, py;
+                    homography_point(h, fx, fy, homography_w(h, fx, fy), px, py);
+                    out[2 * n] = px;
+                    out[2 * n + 1] = py;
+                }
+            }
+        }
+        if (l == 0) d.status[slot] = why;
+    }
+}
+
+// tag_affine / tag_homography of every slot: lanes 0 .. 8 store the nine words of the slot's matrix (36 consecutive bytes), lane
+// 9 the status.  No image size: neither function takes one.
+__global__ void __launch_bounds__(DS_THREADS, 4) k_tag_maps(TagMapsArgs t)
+{
+    const int l = (int)(threadIdx.x & 15u);
+    const uint32_t n_slots = (uint32_t)t.n_frames * t.quads_per_frame, step = gridDim.x * (DS_THREADS / 16);
+    for (uint32_t slot = blockIdx.x * (DS_THREADS / 16) + (threadIdx.x >> 4); slot < n_slots; slot += step) {
+        if (slot_beyond_count(t.counts, slot, t.quads_per_frame)) continue;
+        float q[8], h[9];
+        uint32_t why = slot_corners(t.quads, t.point_stride, t.point_status, slot, false, 0u, 0u, q);
+        if (why == AGX_QUAD_DECODED) {
+            if (t.model == AGX_TAG_MAP_HOMOGRAPHY) {
+                if (!tag_homography(q, t.side_bits, t.margin, h)) why = AGX_QUAD_DEGENERATE;
+            } else {
+                tag_affine(q, t.side_bits, t.margin, h);
+                h[6] = 0.0f;
+                h[7] = 0.0f;
+                h[8] = 1.0f;
+            }
+        }
+        if (why == AGX_QUAD_DECODED && l < 9) {
+            float v = h[0];  // (no register array is indexed by the lane)
+#pragma unroll
+            for (int j = 1; j < 9; ++j) v = l == j ? h[j] : v;
+            t.maps[(u64)slot * 9u + (u64)l] = v;
+        }
+        if (l == 9) t.status[slot] = why;
     }
 }
 
@@ -157,6 +247,26 @@ int launch_decode_positions(const DecodePositionsArgs &p, void *stream)
         p.edge > 8 || p.border < 0 || p.border > 16)
         return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_decode_positions, dim3(ds_grid(n_slots)), dim3(DS_THREADS), 0, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+}
+
+int launch_positions_homography(const DecodePositionsArgs &p, void *stream)
+{
+    const unsigned long long n_slots = (unsigned long long)(p.n_frames > 0 ? p.n_frames : 0) * p.quads_per_frame;
+    if (!n_slots || n_slots >= (1ull << 31) || !p.quads || !p.points || !p.status || p.point_stride < 8 || (p.point_stride & 3) || p.edge < 1 ||
+        p.edge > 8 || p.border < 0 || p.border > 16)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_positions_homography, dim3(ds_grid(n_slots)), dim3(DS_THREADS), 0, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+}
+
+int launch_tag_maps(const TagMapsArgs &p, void *stream)
+{
+    const unsigned long long n_slots = (unsigned long long)(p.n_frames > 0 ? p.n_frames : 0) * p.quads_per_frame;
+    if (!n_slots || n_slots >= (1ull << 31) || !p.quads || !p.maps || !p.status || p.point_stride < 8 || (p.point_stride & 3) || p.side_bits < 1 ||
+        p.side_bits > 40 || (p.model != AGX_TAG_MAP_AFFINE && p.model != AGX_TAG_MAP_HOMOGRAPHY))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_tag_maps, dim3(ds_grid(n_slots)), dim3(DS_THREADS), 0, (hipStream_t)stream, p);
     return (int)hipGetLastError();
 }
 

@@ -1088,9 +1088,10 @@ bool agx::decode_square_ok(int border_bits, int edge_bits, float margin)
 
 int agx::decode_positions_enqueue_impl(agx_detector *det, const void *d_quads, size_t point_stride_bytes, int n_frames, uint32_t quads_per_frame,
                                        const uint32_t *d_counts, const uint32_t *d_point_status, uint32_t img_w, uint32_t img_h, int border_bits,
-                                       int edge_bits, float margin, float *d_points, uint32_t *d_status)
+                                       int edge_bits, float margin, float *d_points, uint32_t *d_status, int model)
 {
     if (!det) return AGX_ERR_ARG;
+    if (model != AGX_TAG_MAP_AFFINE && model != AGX_TAG_MAP_HOMOGRAPHY) return fail(det, AGX_ERR_ARG, "model must be AGX_TAG_MAP_AFFINE or AGX_TAG_MAP_HOMOGRAPHY");
     if (!d_quads || !d_points || !d_status || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null quads, points or status, or n_frames <= 0");
     if (!quads_per_frame) return fail(det, AGX_ERR_ARG, "quads_per_frame must be > 0");
     if (!decode_stage_stride_ok(point_stride_bytes)) return fail(det, AGX_ERR_ARG, "point_stride_bytes must be a multiple of 4 and at least 8");
@@ -1115,8 +1116,47 @@ int agx::decode_positions_enqueue_impl(agx_detector *det, const void *d_quads, s
     p.margin = margin;
     p.points = d_points;
     p.status = d_status;
-    const hipError_t e = (hipError_t)launch_decode_positions(p, det->stream);
-    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_decode_positions: ") + hipGetErrorString(e));
+    const hipError_t e = (hipError_t)(model == AGX_TAG_MAP_HOMOGRAPHY ? launch_positions_homography(p, det->stream) : launch_decode_positions(p, det->stream));
+    if (e != hipSuccess)
+        return fail(det, AGX_ERR_HIP, std::string(model == AGX_TAG_MAP_HOMOGRAPHY ? "k_positions_homography: " : "k_decode_positions: ") + hipGetErrorString(e));
+    return AGX_OK;
+}
+
+bool agx::tag_square_ok(int side_bits, float margin)
+{
+    if (side_bits < 1 || side_bits > 40 || !std::isfinite(margin)) return false;
+    return (float)side_bits - 1.0f + margin != -margin;  // (decode_square_ok's rule: the square is not a point)
+}
+
+int agx::tag_maps_enqueue_impl(agx_detector *det, const void *d_quads, size_t point_stride_bytes, int n_frames, uint32_t quads_per_frame,
+                               const uint32_t *d_counts, const uint32_t *d_point_status, int side_bits, float margin, int model, float *d_maps,
+                               uint32_t *d_status)
+{
+    if (!det) return AGX_ERR_ARG;
+    if (model != AGX_TAG_MAP_AFFINE && model != AGX_TAG_MAP_HOMOGRAPHY) return fail(det, AGX_ERR_ARG, "model must be AGX_TAG_MAP_AFFINE or AGX_TAG_MAP_HOMOGRAPHY");
+    if (!d_quads || !d_maps || !d_status || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null quads, maps or status, or n_frames <= 0");
+    if (!quads_per_frame) return fail(det, AGX_ERR_ARG, "quads_per_frame must be > 0");
+    if (!decode_stage_stride_ok(point_stride_bytes)) return fail(det, AGX_ERR_ARG, "point_stride_bytes must be a multiple of 4 and at least 8");
+    if (((uintptr_t)d_quads | (uintptr_t)d_counts | (uintptr_t)d_point_status | (uintptr_t)d_maps | (uintptr_t)d_status) & 3)
+        return fail(det, AGX_ERR_ARG, "quads, counts, point statuses, maps and statuses must be 4-byte aligned");
+    if (!tag_square_ok(side_bits, margin)) return fail(det, AGX_ERR_ARG, "side_bits 1 .. 40, a finite margin and a source square that is not a point");
+    if ((size_t)n_frames * quads_per_frame >= ((size_t)1 << 29)) return fail(det, AGX_ERR_ARG, "at most 2^29 - 1 quads per batch");
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // and there is nothing of this one to be fetched
+    TagMapsArgs p{};
+    p.quads = static_cast<const uint8_t *>(d_quads);
+    p.point_stride = (uint32_t)point_stride_bytes;
+    p.n_frames = n_frames;
+    p.quads_per_frame = quads_per_frame;
+    p.counts = d_counts;
+    p.point_status = d_point_status;
+    p.side_bits = side_bits;
+    p.margin = margin;
+    p.model = model;
+    p.maps = d_maps;
+    p.status = d_status;
+    const hipError_t e = (hipError_t)launch_tag_maps(p, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_tag_maps: ") + hipGetErrorString(e));
     return AGX_OK;
 }
 

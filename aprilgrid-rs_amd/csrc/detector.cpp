@@ -16,6 +16,7 @@
 
 #include "../../include/aprilgrid_amd.h"
 #include "chain_kernels.h"
+#include "decode_math.h"
 #include "decode_stages.h"
 #include "detector_internal.h"
 #include "host_tail.hpp"
@@ -1499,17 +1500,33 @@ int agx_decode_positions_enqueue(agx_detector *det, const void *d_quads, size_t 
                                  const uint32_t *d_counts, const uint32_t *d_point_status, uint32_t img_w, uint32_t img_h, int border_bits,
                                  int edge_bits, float margin, float *d_points, uint32_t *d_status)
 {
+    return agx_decode_positions_enqueue_m(det, d_quads, point_stride_bytes, n_frames, quads_per_frame, d_counts, d_point_status, img_w, img_h,
+                                          border_bits, edge_bits, margin, d_points, d_status, AGX_TAG_MAP_AFFINE);
+}
+
+int agx_decode_positions_enqueue_m(agx_detector *det, const void *d_quads, size_t point_stride_bytes, int n_frames, uint32_t quads_per_frame,
+                                   const uint32_t *d_counts, const uint32_t *d_point_status, uint32_t img_w, uint32_t img_h, int border_bits,
+                                   int edge_bits, float margin, float *d_points, uint32_t *d_status, int model)
+{
     return agx_guard(det, [&]() -> int {
     return decode_positions_enqueue_impl(det, d_quads, point_stride_bytes, n_frames, quads_per_frame, d_counts, d_point_status, img_w, img_h,
-                                         border_bits, edge_bits, margin, d_points, d_status);
+                                         border_bits, edge_bits, margin, d_points, d_status, model);
     });
 }
 
 int agx_decode_positions_tail(const void *quads, uint32_t n_quads, uint32_t img_w, uint32_t img_h, int border_bits, int edge_bits, float margin,
                               float *points, uint32_t *status)
 {
+    return agx_decode_positions_tail_m(quads, n_quads, img_w, img_h, border_bits, edge_bits, margin, points, status, AGX_TAG_MAP_AFFINE);
+}
+
+int agx_decode_positions_tail_m(const void *quads, uint32_t n_quads, uint32_t img_w, uint32_t img_h, int border_bits, int edge_bits, float margin,
+                                float *points, uint32_t *status, int model)
+{
     return agx_guard(nullptr, [&]() -> int {
-    if ((n_quads && (!quads || !points || !status)) || !decode_square_ok(border_bits, edge_bits, margin)) return AGX_ERR_ARG;
+    if ((n_quads && (!quads || !points || !status)) || !decode_square_ok(border_bits, edge_bits, margin) ||
+        (model != AGX_TAG_MAP_AFFINE && model != AGX_TAG_MAP_HOMOGRAPHY))
+        return AGX_ERR_ARG;
     const size_t per_slot = (size_t)(2 * edge_bits * edge_bits);
     for (uint32_t i = 0; i < n_quads; ++i) {
         float q[8], pts[2 * 64];
@@ -1517,9 +1534,51 @@ int agx_decode_positions_tail(const void *quads, uint32_t n_quads, uint32_t img_
         bool finite = true;
         for (float v : q) finite = finite && std::isfinite(v);
         // a coordinate that is not finite: AGX_QUAD_OUTSIDE before anything else (the reference's `as u32` would take NaN for 0)
-        const int why = finite ? decode_positions(img_w, img_h, q, border_bits, edge_bits, margin, pts) : (int)AGX_QUAD_OUTSIDE;
+        int why = AGX_QUAD_OUTSIDE;
+        if (finite)
+            why = model == AGX_TAG_MAP_HOMOGRAPHY ? decode_positions_homography(img_w, img_h, q, border_bits, edge_bits, margin, pts)
+                                                  : decode_positions(img_w, img_h, q, border_bits, edge_bits, margin, pts);
         if (why == AGX_QUAD_DECODED) std::memcpy(points + (size_t)i * per_slot, pts, per_slot * sizeof(float));
         status[i] = (uint32_t)why;
+    }
+    return AGX_OK;
+    });
+}
+
+// tag_affine (src/image_util.rs:39-70) / tag_homography (src/image_util.rs:5-37) themselves (k_tag_maps is the device form)
+int agx_tag_maps_enqueue(agx_detector *det, const void *d_quads, size_t point_stride_bytes, int n_frames, uint32_t quads_per_frame,
+                         const uint32_t *d_counts, const uint32_t *d_point_status, int side_bits, float margin, int model, float *d_maps,
+                         uint32_t *d_status)
+{
+    return agx_guard(det, [&]() -> int {
+    return tag_maps_enqueue_impl(det, d_quads, point_stride_bytes, n_frames, quads_per_frame, d_counts, d_point_status, side_bits, margin, model,
+                                 d_maps, d_status);
+    });
+}
+
+int agx_tag_maps_tail(const void *quads, uint32_t n_quads, int side_bits, float margin, int model, float *maps, uint32_t *status)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if ((n_quads && (!quads || !maps || !status)) || !tag_square_ok(side_bits, margin) || (model != AGX_TAG_MAP_AFFINE && model != AGX_TAG_MAP_HOMOGRAPHY))
+        return AGX_ERR_ARG;
+    for (uint32_t i = 0; i < n_quads; ++i) {
+        float q[8], h[9];
+        std::memcpy(q, static_cast<const char *>(quads) + (size_t)i * sizeof q, sizeof q);
+        bool finite = true;
+        for (float v : q) finite = finite && std::isfinite(v);
+        uint32_t why = finite ? AGX_QUAD_DECODED : AGX_QUAD_OUTSIDE;
+        if (finite) {
+            if (model == AGX_TAG_MAP_HOMOGRAPHY) {
+                if (!tag_homography(q, side_bits, margin, h)) why = AGX_QUAD_DEGENERATE;
+            } else {
+                tag_affine(q, side_bits, margin, h);
+                h[6] = 0.0f;
+                h[7] = 0.0f;
+                h[8] = 1.0f;
+            }
+        }
+        if (why == AGX_QUAD_DECODED) std::memcpy(maps + (size_t)i * 9, h, sizeof h);
+        status[i] = why;
     }
     return AGX_OK;
     });

@@ -376,7 +376,12 @@ int decode_quads_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *status, u
 bool decode_square_ok(int border_bits, int edge_bits, float margin);
 int decode_positions_enqueue_impl(agx_detector *det, const void *d_quads, size_t point_stride_bytes, int n_frames, uint32_t quads_per_frame,
                                   const uint32_t *d_counts, const uint32_t *d_point_status, uint32_t img_w, uint32_t img_h, int border_bits,
-                                  int edge_bits, float margin, float *d_points, uint32_t *d_status);
+                                  int edge_bits, float margin, float *d_points, uint32_t *d_status, int model);
+// side_bits 1 .. 40, a finite margin and a source square that is not a point; tag_affine / tag_homography per slot (k_tag_maps)
+bool tag_square_ok(int side_bits, float margin);
+int tag_maps_enqueue_impl(agx_detector *det, const void *d_quads, size_t point_stride_bytes, int n_frames, uint32_t quads_per_frame,
+                          const uint32_t *d_counts, const uint32_t *d_point_status, int side_bits, float margin, int model, float *d_maps,
+                          uint32_t *d_status);
 int bit_code_enqueue_impl(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
                           size_t frame_stride_bytes, int format, const float *d_points, uint32_t points_per_slot, uint32_t quads_per_frame,
                           const uint32_t *d_counts, const uint32_t *d_status_in, int valid_brightness_threshold, uint32_t max_invalid_bit,

@@ -1222,6 +1222,28 @@ int decode_positions(uint32_t w, uint32_t h, const float quad_xy[8], int border,
     return AGX_QUAD_DECODED;
 }
 
+// decode_positions with src/detector.rs:58's map replaced by tag_homography (src/image_util.rs:5-37).  The slot is decided before a
+// point is written: the corners (:50-56), the map (AGX_QUAD_DEGENERATE), then every sample's w (AGX_QUAD_OUTSIDE)
+int decode_positions_homography(uint32_t w, uint32_t h, const float quad_xy[8], int border, int edge, float margin, float *pts)
+{
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t x = f32_as_u32(round_half_away(quad_xy[2 * i])), y = f32_as_u32(round_half_away(quad_xy[2 * i + 1]));
+        if (x >= w || y >= h) return AGX_QUAD_OUTSIDE;
+    }
+    float hm[9];
+    if (!tag_homography(quad_xy, border * 2 + edge, margin, hm)) return AGX_QUAD_DEGENERATE;
+    for (int gx = border; gx < border + edge; ++gx)
+        for (int gy = border; gy < border + edge; ++gy)
+            if (!homography_w_ok(homography_w(hm, (float)gx, (float)gy))) return AGX_QUAD_OUTSIDE;
+    for (int gx = border; gx < border + edge; ++gx)
+        for (int gy = border; gy < border + edge; ++gy) {
+            const float fx = (float)gx, fy = (float)gy;
+            homography_point(hm, fx, fy, homography_w(hm, fx, fy), pts[0], pts[1]);
+            pts += 2;
+        }
+    return AGX_QUAD_DECODED;
+}
+
 // bit_code, src/detector.rs:74-122, of n <= 64 sample points: AGX_QUAD_DECODED and the bits (the first point is the most
 // significant of the n), or the reason for None in the reference's order (AGX_QUAD_OUTSIDE :84-93, _LOW_CONTRAST :97-99,
 // _AMBIGUOUS :117-118); bits_out is 0 then

@@ -90,6 +90,9 @@ bool best_tag(uint64_t bits, int thres, const uint64_t *codes, int n_codes, int 
 // decode_positions, detector.rs:42-72: AGX_QUAD_OUTSIDE (None), or AGX_QUAD_DECODED and the edge * edge points (x, y) in pts, x
 // outer and y inner.  The corners are finite (the callers' rule) and the source square is not degenerate.
 int decode_positions(uint32_t w, uint32_t h, const float quad_xy[8], int border, int edge, float margin, float *pts);
+// the same with tag_homography (image_util.rs:5-37) in tag_affine's place (agx_decode_positions_tail_m; k_positions_homography is
+// the device form): also AGX_QUAD_DEGENERATE (no map), and AGX_QUAD_OUTSIDE for a sample whose w is not > 0 or not finite
+int decode_positions_homography(uint32_t w, uint32_t h, const float quad_xy[8], int border, int edge, float margin, float *pts);
 // bit_code, detector.rs:74-122, over n <= 64 points: AGX_QUAD_DECODED and the bits (first point = most significant of the n), or
 // AGX_QUAD_OUTSIDE / _LOW_CONTRAST / _AMBIGUOUS in the reference's order, bits 0
 int bit_code(const uint8_t *luma8, uint32_t w, uint32_t h, size_t stride, const float *pts, int n, int valid_brightness_threshold,

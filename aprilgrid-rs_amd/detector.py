@@ -826,12 +826,15 @@ class TagDetector:
         self._batch = self._detect = self._refine = self._decode = self._grow = self._find = self._clusters = self._init = None
 
     def decode_positions_enqueue(self, quads=None, points=None, status=None, img_size=None, border_bits=None, edge_bits=None, margin=0.5,
-                                 counts=None, refined=None):
+                                 counts=None, refined=None, model="affine"):
         """decode_positions (src/detector.rs:42-72) of every quad slot, stream-ordered behind torch's current stream; nothing to
         fetch.  quads / refined= / counts as decode_quads_enqueue; img_size=(width, height) the corners are tested against (no
         pixel is read); border_bits, edge_bits default to the family's.  points float32 [N,Q,edge_bits^2,2]: the samples of the
-        slots whose status is AGX_QUAD_DECODED, x outer and y inner; status int32 [N,Q]: AGX_QUAD_DECODED / _OUTSIDE / _SKIPPED."""
+        slots whose status is AGX_QUAD_DECODED, x outer and y inner; status int32 [N,Q]: AGX_QUAD_DECODED / _OUTSIDE / _SKIPPED.
+        model: "affine" (tag_affine, src/image_util.rs:39-70: the reference's decode) or "homography" (tag_homography,
+        src/image_util.rs:5-37: the projective map through the corners; also AGX_QUAD_DEGENERATE)."""
         import torch
+        model = tag_map_model(model)
         n, qpf, stride, p_quads, p_ps, dev = self._stage_quads(quads, refined)
         fam = self._family_info()
         edge = fam[0] if edge_bits is None else int(edge_bits)
@@ -846,8 +849,34 @@ class TagDetector:
         p_counts = self._stage_tensor(counts, torch.int32, (n,), "counts", dev) if counts is not None else None
         self._follow_torch_stream(points)
         self._replaces_batch()
-        self._check(self._lib.agx_decode_positions_enqueue(self._h, p_quads, stride, n, qpf, p_counts, p_ps, w, h, border, edge, float(margin),
-                                                           p_points, p_status))
+        if model == _ffi.AGX_TAG_MAP_AFFINE:
+            self._check(self._lib.agx_decode_positions_enqueue(self._h, p_quads, stride, n, qpf, p_counts, p_ps, w, h, border, edge, float(margin),
+                                                               p_points, p_status))
+        else:
+            self._check(self._lib.agx_decode_positions_enqueue_m(self._h, p_quads, stride, n, qpf, p_counts, p_ps, w, h, border, edge, float(margin),
+                                                                 p_points, p_status, model))
+
+    def tag_maps_enqueue(self, quads=None, maps=None, status=None, side_bits=None, margin=0.5, model="homography", counts=None, refined=None):
+        """tag_affine (src/image_util.rs:39-70) or tag_homography (src/image_util.rs:5-37) of every quad slot, stream-ordered behind
+        torch's current stream; nothing to fetch.  quads / refined= / counts as decode_positions_enqueue; side_bits in 1 .. 40
+        (None: the family's 2 border_bits + edge_bits).  maps float32 [N,Q,3,3] (or [N,Q,9]): the row-major matrix from the source
+        square to the image of the slots whose status is AGX_QUAD_DECODED (affine: last row 0, 0, 1; homography: w = 1 at the
+        square's centre); status int32 [N,Q]: AGX_QUAD_DECODED / _OUTSIDE / _SKIPPED / _DEGENERATE."""
+        import torch
+        model = tag_map_model(model)
+        n, qpf, stride, p_quads, p_ps, dev = self._stage_quads(quads, refined)
+        if side_bits is None:
+            fam = self._family_info()
+            side_bits = 2 * fam[1] + fam[0]
+        if maps is None or tuple(maps.shape) not in ((n, qpf, 3, 3), (n, qpf, 9)):
+            raise AgxError(_ffi.AGX_ERR_ARG, "maps must be a device tensor [N, Q, 3, 3] or [N, Q, 9]")
+        p_maps = self._stage_tensor(maps, torch.float32, tuple(maps.shape), "maps", dev)
+        p_status = self._stage_tensor(status, torch.int32, (n, qpf), "status", dev)
+        p_counts = self._stage_tensor(counts, torch.int32, (n,), "counts", dev) if counts is not None else None
+        self._follow_torch_stream(maps)
+        self._replaces_batch()
+        self._check(self._lib.agx_tag_maps_enqueue(self._h, p_quads, stride, n, qpf, p_counts, p_ps, int(side_bits), float(margin), model, p_maps,
+                                                   p_status))
 
     def bit_code_enqueue(self, frames, points, bits, status, counts=None, status_in=None, valid_brightness_threshold=10, max_invalid_bit=3,
                          format=None):
@@ -913,12 +942,13 @@ class TagDetector:
                                                    *p_out, p_tags))
 
     def decode_quads_staged(self, frames, quads, *, margin=0.5, valid_brightness_threshold=10, max_invalid_bit=3, thres=None, codes=None,
-                            counts=None, format=None):
+                            counts=None, format=None, model="affine"):
         """try_decode_quad (src/detector.rs:448-476) as its three stages chained on device tensors with no sync in between --
         decode_positions_enqueue -> bit_code_enqueue -> best_tag_enqueue, one status array handed on in place -- with the crate's
         arguments open: margin, the brightness rules, thres (None: the family's Hamming distance) and codes (None: the family's
-        list; else 1 .. 65535 codes, a host array or an int64 device tensor).  frames, quads [N,Q,4,2] and counts as
-        decode_quads_enqueue.  At the defaults the result is decode_quads_enqueue's, byte for byte.
+        list; else 1 .. 65535 codes, a host array or an int64 device tensor) and model ("affine", or "homography":
+        decode_positions_enqueue's).  frames, quads [N,Q,4,2] and counts as decode_quads_enqueue.  At the defaults the result is
+        decode_quads_enqueue's, byte for byte.
         -> (tags [N,Q] TAG_DTYPE, status [N,Q] uint32, bits [N,Q] uint64, points [N,Q,edge_bits^2,2] float32) as decode_quads_fetch
         returns them: slots beyond a frame's count read zero tags, status 0xFFFFFFFF, bits 0; the points of a slot whose quad
         gave none are 0."""
@@ -935,7 +965,7 @@ class TagDetector:
         tags = torch.zeros((n, qpf, 9), **i32)
         if codes is not None and not getattr(codes, "is_cuda", False):
             codes = torch.from_numpy(np.ascontiguousarray(codes, np.uint64).view(np.int64).reshape(-1)).to(dev)
-        self.decode_positions_enqueue(quads, points, status, img_size=(int(w), int(h)), margin=margin, counts=counts)
+        self.decode_positions_enqueue(quads, points, status, img_size=(int(w), int(h)), margin=margin, counts=counts, model=model)
         self.bit_code_enqueue(frames, points, bits, status, counts=counts, status_in=status, valid_brightness_threshold=valid_brightness_threshold,
                               max_invalid_bit=max_invalid_bit, format=format)
         self.best_tag_enqueue(bits, ids, rotations, status, thres=thres, codes=codes, counts=counts, status_in=status, quads=quads, tags=tags)
@@ -1339,11 +1369,13 @@ class TagDetector:
                     _ffi.AGX_TAGS_INPUT: "AGX_TAGS_INPUT (a board beyond quads_per_frame, or a refused saddle list)",
                     _ffi.AGX_TAGS_PENDING: "AGX_TAGS_PENDING"}
 
-    def detect_staged(self, frames, clusters_per_frame=4096, quads_per_frame=128, tags_per_frame=None, format=None):
+    def detect_staged(self, frames, clusters_per_frame=4096, quads_per_frame=128, tags_per_frame=None, format=None, decode_model="affine"):
         """detect (src/detector.rs:505-540) as the staged chain on device tensors, every stage handing its arrays to the next in
         place: planes at the handle's sigma, clusters, refine on the blur plane at the handle's half_size_patch, the k / phi
         filter, then max_num_of_boards rounds of find boards -> find_boards_fetch (which lets the host form answer a frame the
         kernel hands back) -> decode -> collect (src/detector.rs:510-539).  frames and format= as detect_batch_enqueue.
+        decode_model: "affine" -- the fused decode, the reference's -- or "homography": the decode as its three stages with
+        tag_homography (src/image_util.rs:5-37) as the sampling model, for tags seen under strong perspective.
         tags_per_frame: rows of a frame's tag table (None: one per code of the family, which always holds).
         -> one {tag_id: 4x2 corners} per frame in row order, as detect_batch.  A frame whose clusters or tags could not be held
         raises AgxError naming the frame and its status."""
@@ -1373,10 +1405,21 @@ class TagDetector:
         qtags, qst = torch.zeros((n, qpf, 9), **i32), torch.zeros((n, qpf), **i32)
         tags, ntags, tst = torch.zeros((n, tpf, 9), **i32), torch.zeros(n, **i32), torch.zeros(n, **i32)
         rounds = int(self.detector_params.max_num_of_boards)
+        decode_model = tag_map_model(decode_model)
+        if decode_model != _ffi.AGX_TAG_MAP_AFFINE:
+            edge = self._family_info()[0]
+            spts = torch.zeros((n, qpf, edge * edge, 2), dtype=torch.float32, device=dev)
+            sbits = torch.zeros((n, qpf), dtype=torch.int64, device=dev)
+            sids, srots = torch.zeros((n, qpf), **i32), torch.zeros((n, qpf), **i32)
         for r in range(rounds):
             self.find_boards_enqueue(records, counts=counts, point_status=pstatus, quads=quads, quad_points=qpts, n_quads=nq, status=bst)
             self.find_boards_fetch()
-            self.decode_quads_enqueue(frames, qpts, counts=nq, out=qtags, status=qst, format=format)
+            if decode_model == _ffi.AGX_TAG_MAP_AFFINE:
+                self.decode_quads_enqueue(frames, qpts, counts=nq, out=qtags, status=qst, format=format)
+            else:
+                self.decode_positions_enqueue(qpts, spts, qst, img_size=(w, h), counts=nq, model=decode_model)
+                self.bit_code_enqueue(frames, spts, sbits, qst, counts=nq, status_in=qst, format=format)
+                self.best_tag_enqueue(sbits, sids, srots, qst, counts=nq, status_in=qst, quads=qpts, tags=qtags)
             self.collect_tags_enqueue(quads, nq, bst, qtags, qst, pstatus if r + 1 < rounds else None, tags, ntags, tst, reset=r == 0,
                                       saddles_per_frame=cpf)
         self.sync()
@@ -1556,19 +1599,50 @@ def decode_quads_tail(tag_family, luma8, quads, with_bits=False):
     return (out, status, bits) if with_bits else (out, status)
 
 
-def decode_positions(quads, img_w, img_h, border_bits, edge_bits, margin=0.5):
+def tag_map_model(model):
+    """"affine" / "homography" (or an AGX_TAG_MAP_* value) -> the value the library takes"""
+    if isinstance(model, str):
+        try:
+            return {"affine": _ffi.AGX_TAG_MAP_AFFINE, "homography": _ffi.AGX_TAG_MAP_HOMOGRAPHY}[model]
+        except KeyError:
+            raise AgxError(_ffi.AGX_ERR_ARG, 'model must be "affine" or "homography"')
+    return int(model)
+
+
+def decode_positions(quads, img_w, img_h, border_bits, edge_bits, margin=0.5, model="affine"):
     """The host's decode_positions (src/detector.rs:42-72) without a device -- the first stage of decode_quads_tail, the same
     code: quads n x 4 corners (x, y).  -> (points [n, edge_bits^2, 2] float32, x outer and y inner, zero where the quad gave none;
-    status [n] uint32: AGX_QUAD_DECODED or AGX_QUAD_OUTSIDE)."""
+    status [n] uint32: AGX_QUAD_DECODED or AGX_QUAD_OUTSIDE).  model="homography": tag_homography (src/image_util.rs:5-37) in
+    tag_affine's place; the status may be AGX_QUAD_DEGENERATE too."""
+    model = tag_map_model(model)
     q = np.ascontiguousarray(quads, np.float32).reshape(-1, 8)
     n, e = q.shape[0], int(edge_bits)
     points = np.zeros((n, max(e * e, 1) if 1 <= e <= 8 else 1, 2), np.float32)
     status = np.zeros(n, np.uint32)
-    st = _ffi.lib().agx_decode_positions_tail(q.ctypes.data, n, int(img_w), int(img_h), int(border_bits), e, float(margin), points.ctypes.data,
-                                              status.ctypes.data)
+    if model == _ffi.AGX_TAG_MAP_AFFINE:
+        st = _ffi.lib().agx_decode_positions_tail(q.ctypes.data, n, int(img_w), int(img_h), int(border_bits), e, float(margin), points.ctypes.data,
+                                                  status.ctypes.data)
+    else:
+        st = _ffi.lib().agx_decode_positions_tail_m(q.ctypes.data, n, int(img_w), int(img_h), int(border_bits), e, float(margin),
+                                                    points.ctypes.data, status.ctypes.data, model)
     if st != _ffi.AGX_OK:
         raise AgxError(st)
     return points, status
+
+
+def tag_maps(quads, side_bits, margin=0.5, model="homography"):
+    """The host's tag_affine (src/image_util.rs:39-70) / tag_homography (src/image_util.rs:5-37) without a device: quads n x 4
+    corners (x, y), side_bits in 1 .. 40.  -> (maps [n, 3, 3] float32, row-major from the source square (-margin, -margin) ..
+    (side_bits - 1 + margin, side_bits - 1 + margin) to the image, zero where the quad gave none; status [n] uint32:
+    AGX_QUAD_DECODED, AGX_QUAD_OUTSIDE (a corner that is not finite) or AGX_QUAD_DEGENERATE)."""
+    q = np.ascontiguousarray(quads, np.float32).reshape(-1, 8)
+    n = q.shape[0]
+    maps = np.zeros((n, 3, 3), np.float32)
+    status = np.zeros(n, np.uint32)
+    st = _ffi.lib().agx_tag_maps_tail(q.ctypes.data, n, int(side_bits), float(margin), tag_map_model(model), maps.ctypes.data, status.ctypes.data)
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    return maps, status
 
 
 def bit_code(luma8, points, valid_brightness_threshold=10, max_invalid_bit=3, status_in=None):

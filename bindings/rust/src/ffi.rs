@@ -123,6 +123,10 @@ pub const AGX_QUAD_LOW_CONTRAST: c_int = 2;
 pub const AGX_QUAD_AMBIGUOUS: c_int = 3;
 pub const AGX_QUAD_NO_MATCH: c_int = 4;
 pub const AGX_QUAD_SKIPPED: c_int = 5;
+pub const AGX_QUAD_DEGENERATE: c_int = 6;
+// the sampling model of decode_positions (reference src/image_util.rs:39-70 tag_affine, :5-37 tag_homography)
+pub const AGX_TAG_MAP_AFFINE: c_int = 0;
+pub const AGX_TAG_MAP_HOMOGRAPHY: c_int = 1;
 // try_find_best_board of caller-given saddle lists (reference src/detector.rs:588-639): what became of a frame
 pub const AGX_BOARD_FOUND: c_int = 0;
 pub const AGX_BOARD_NONE: c_int = 1;
@@ -244,6 +248,18 @@ extern "C" {
                                         d_status: *mut u32) -> c_int;
     pub fn agx_decode_positions_tail(quads: *const c_void, n_quads: u32, img_w: u32, img_h: u32, border_bits: c_int, edge_bits: c_int,
                                      margin: c_float, points: *mut c_float, status: *mut u32) -> c_int;
+    // the sampling model opened (reference src/image_util.rs:5-37 tag_homography, :39-70 tag_affine)
+    pub fn agx_decode_positions_enqueue_m(det: *mut agx_detector, d_quads: *const c_void, point_stride_bytes: usize, n_frames: c_int,
+                                          quads_per_frame: u32, d_counts: *const u32, d_point_status: *const u32, img_w: u32, img_h: u32,
+                                          border_bits: c_int, edge_bits: c_int, margin: c_float, d_points: *mut c_float,
+                                          d_status: *mut u32, model: c_int) -> c_int;
+    pub fn agx_decode_positions_tail_m(quads: *const c_void, n_quads: u32, img_w: u32, img_h: u32, border_bits: c_int, edge_bits: c_int,
+                                       margin: c_float, points: *mut c_float, status: *mut u32, model: c_int) -> c_int;
+    pub fn agx_tag_maps_enqueue(det: *mut agx_detector, d_quads: *const c_void, point_stride_bytes: usize, n_frames: c_int,
+                                quads_per_frame: u32, d_counts: *const u32, d_point_status: *const u32, side_bits: c_int,
+                                margin: c_float, model: c_int, d_maps: *mut c_float, d_status: *mut u32) -> c_int;
+    pub fn agx_tag_maps_tail(quads: *const c_void, n_quads: u32, side_bits: c_int, margin: c_float, model: c_int, maps: *mut c_float,
+                             status: *mut u32) -> c_int;
     pub fn agx_bit_code_enqueue(det: *mut agx_detector, d_frames: *const c_void, n_frames: c_int, width: c_int, height: c_int,
                                 row_stride_bytes: usize, frame_stride_bytes: usize, format: c_int, d_points: *const c_float,
                                 points_per_slot: u32, quads_per_frame: u32, d_counts: *const u32, d_status_in: *const u32,

@@ -567,6 +567,69 @@ pub fn decode_positions(img_w: u32, img_h: u32, quad_pts: &[(f32, f32)], border_
     Some(points[..2 * n].chunks(2).map(|p| (p[0], p[1])).collect())
 }
 
+/// The sampling model of `decode_positions`: `tag_affine` (reference src/image_util.rs:39-70, what src/detector.rs:58 calls) or
+/// `tag_homography` (src/image_util.rs:5-37).
+#[repr(i32)]
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub enum TagMap {
+    Affine = 0,
+    Homography = 1,
+}
+
+/// `decode_positions` (reference src/detector.rs:42-72) with the map of :58 chosen by `model`.  `Err(status)` carries the reason
+/// for `None` (`AGX_QUAD_OUTSIDE`, or `AGX_QUAD_DEGENERATE` where the homography refuses the quad).  Panics as `decode_positions`.
+pub fn decode_positions_m(img_w: u32, img_h: u32, quad_pts: &[(f32, f32)], border_bits: u8, edge_bits: u8, margin: f32,
+                          model: TagMap) -> Result<Vec<(f32, f32)>, u32> {
+    assert_eq!(quad_pts.len(), 4, "decode_positions_m: a quad has four corners");
+    let flat: Vec<f32> = quad_pts.iter().flat_map(|p| [p.0, p.1]).collect();
+    let n = edge_bits as usize * edge_bits as usize;
+    let mut points = vec![0f32; 2 * n.max(1)];
+    let mut status = 0u32;
+    let st = unsafe {
+        ffi::agx_decode_positions_tail_m(flat.as_ptr() as *const c_void, 1, img_w, img_h, border_bits as c_int, edge_bits as c_int, margin,
+                                         points.as_mut_ptr(), &mut status, model as c_int)
+    };
+    assert_eq!(st, ffi::AGX_OK, "agx_decode_positions_tail_m failed: {}", st);
+    if status as c_int != ffi::AGX_QUAD_DECODED {
+        return Err(status);
+    }
+    Ok(points[..2 * n].chunks(2).map(|p| (p[0], p[1])).collect())
+}
+
+/// `tag_affine` / `tag_homography` (reference src/image_util.rs:39-70, :5-37) of quads of four corners each: the row-major 3 x 3
+/// map from the source square of `side_bits` and `margin` to the image per quad, or `Err(status)` (`AGX_QUAD_OUTSIDE`: a corner
+/// that is not finite; `AGX_QUAD_DEGENERATE`).  The host form.  Panics where the library refuses the arguments: `side_bits`
+/// outside 1..=40, a margin that is not finite, a source square that is a point.
+pub fn tag_maps_tail(quads: &[[(f32, f32); 4]], side_bits: u8, margin: f32, model: TagMap) -> Vec<Result<[f32; 9], u32>> {
+    let flat: Vec<f32> = quads.iter().flat_map(|q| q.iter().flat_map(|p| [p.0, p.1])).collect();
+    let mut maps = vec![0f32; 9 * quads.len().max(1)];
+    let mut status = vec![0u32; quads.len().max(1)];
+    let st = unsafe {
+        ffi::agx_tag_maps_tail(flat.as_ptr() as *const c_void, quads.len() as u32, side_bits as c_int, margin, model as c_int,
+                               maps.as_mut_ptr(), status.as_mut_ptr())
+    };
+    assert_eq!(st, ffi::AGX_OK, "agx_tag_maps_tail failed: {}", st);
+    (0..quads.len())
+        .map(|i| {
+            if status[i] as c_int != ffi::AGX_QUAD_DECODED {
+                return Err(status[i]);
+            }
+            let mut m = [0f32; 9];
+            m.copy_from_slice(&maps[9 * i..9 * i + 9]);
+            Ok(m)
+        })
+        .collect()
+}
+
+/// reference src/image_util.rs:5-37, `tag_homography`: the projective map from the tag's corner grid onto `quad_pts`, row-major,
+/// scaled so that w is 1 at the grid's centre (the reference's vector has unit norm and an arbitrary sign); `None` where there
+/// is no such map or the quad is not strictly convex.
+pub fn tag_homography(quad_pts: &[(f32, f32)], side_bits: u8, margin: f32) -> Option<[f32; 9]> {
+    assert_eq!(quad_pts.len(), 4, "tag_homography: a quad has four corners");
+    let q = [quad_pts[0], quad_pts[1], quad_pts[2], quad_pts[3]];
+    tag_maps_tail(&[q], side_bits, margin, TagMap::Homography)[0].ok()
+}
+
 /// reference src/detector.rs:74-122, `bit_code`: the bits of up to 64 sample points on a grey image, the first point the most
 /// significant, or `None` (a point outside the image, too little contrast, too many samples near the mid brightness).  The
 /// host form (no device is used).  A coordinate that is not finite is `None`.

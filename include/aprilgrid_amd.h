@@ -456,8 +456,11 @@ enum { AGX_QUAD_DECODED = 0,      /* src/detector.rs:448-476: id = index into th
        AGX_QUAD_LOW_CONTRAST = 2, /* :97-99: max - min < 50 over the samples */
        AGX_QUAD_AMBIGUOUS = 3,    /* :117-118: more than 3 samples within 10 of the mid brightness */
        AGX_QUAD_NO_MATCH = 4,     /* :160-168: no rotation within the family's Hamming distance of a code */
-       AGX_QUAD_SKIPPED = 5 };    /* d_point_status was given and one of the quad's corners is not AGX_POINT_REFINED: nothing
+       AGX_QUAD_SKIPPED = 5,      /* d_point_status was given and one of the quad's corners is not AGX_POINT_REFINED: nothing
                                      of the quad's pixels is read */
+       AGX_QUAD_DEGENERATE = 6 }; /* src/image_util.rs:5-37: AGX_TAG_MAP_HOMOGRAPHY refused the quad -- no projective map through
+                                     its corners, or the quad is not strictly convex, or its horizon crosses the tag.  Never
+                                     produced under AGX_TAG_MAP_AFFINE or by an entry that takes no model */
 
 /* try_decode_quad (src/detector.rs:448-476) over a batch in DEVICE memory, stream-ordered on the detector's stream (the
  * caller's after agx_detector_set_stream); returns without waiting.  d_frames / n_frames / width / height / strides / format
@@ -542,6 +545,52 @@ int agx_decode_positions_enqueue(agx_detector *det, const void *d_quads, size_t 
  * [n_quads][edge_bits*edge_bits][2], status [n_quads].  Statuses, untouched points and AGX_ERR_ARG as the batch call's. */
 int agx_decode_positions_tail(const void *quads, uint32_t n_quads, uint32_t img_w, uint32_t img_h, int border_bits,
                               int edge_bits, float margin, float *points, uint32_t *status);
+
+/* The sampling model of decode_positions, opened.  src/detector.rs:58 maps the tag's cell grid into the image with tag_affine
+ * (src/image_util.rs:39-70), a least-squares affine fit through the four corners of what is a projective image of a square;
+ * the crate's other pub fn, tag_homography (src/image_util.rs:5-37), is the projective map through the same corners, which
+ * samples every cell centre of a tag seen at close range on a wide lens where the affine fit leaves its cell. */
+enum { AGX_TAG_MAP_AFFINE = 0,       /* src/image_util.rs:39-70 tag_affine: what decode_positions calls (src/detector.rs:58) */
+       AGX_TAG_MAP_HOMOGRAPHY = 1 }; /* src/image_util.rs:5-37 tag_homography */
+/* decode_positions (src/detector.rs:42-72) with the map of src/detector.rs:58 chosen by `model`; every other argument is
+ * agx_decode_positions_enqueue's.  AGX_TAG_MAP_AFFINE: that call, and its bytes.  AGX_TAG_MAP_HOMOGRAPHY: the map is
+ * tag_homography (src/image_util.rs:5-37) of the same source square (-m,-m), (-m,S), (S,S), (S,-m) -- the reference's 8 x 9
+ * system has a one-dimensional null space for four points, so its SVD's last vector is THE projective map through them up to
+ * scale; the project evaluates that map in closed form, binary64 with + - * / only, rounded once to binary32, scaled so that
+ * w = h6*c + h7*c + h8 is 1 at the square's centre c.  u, v and w are each h0*x + h1*y + h2*1.0f left to right in binary32 and
+ * the point is (u / w, v / w) by correctly rounded binary32 division.  d_status[slot], decided for the whole slot before its
+ * first store and in this order: AGX_QUAD_SKIPPED, AGX_QUAD_OUTSIDE (the corners, as in the existing call),
+ * AGX_QUAD_DEGENERATE (no map: the closed form's denominator or the centre's w is zero or not finite, or w at one of the four
+ * source corners is not > 0 after scaling -- a quad that is not strictly convex, or whose horizon crosses the tag),
+ * AGX_QUAD_OUTSIDE (a sample whose w is not > 0 or not finite), else AGX_QUAD_DECODED; only that one writes points.  The status
+ * is a non-zero word like the others: agx_bit_code_enqueue and agx_best_tag_enqueue pass it through, agx_collect_tags_enqueue
+ * skips it.  AGX_ERR_ARG: the existing call's, and a model that is neither (a batch in flight stays where it is). */
+int agx_decode_positions_enqueue_m(agx_detector *det, const void *d_quads, size_t point_stride_bytes, int n_frames,
+                                   uint32_t quads_per_frame, const uint32_t *d_counts, const uint32_t *d_point_status,
+                                   uint32_t img_w, uint32_t img_h, int border_bits, int edge_bits, float margin,
+                                   float *d_points, uint32_t *d_status, int model);
+/* agx_decode_positions_tail (src/detector.rs:42-72) with the model: the host form of the call above, the same code. */
+int agx_decode_positions_tail_m(const void *quads, uint32_t n_quads, uint32_t img_w, uint32_t img_h, int border_bits,
+                                int edge_bits, float margin, float *points, uint32_t *status, int model);
+/* tag_affine (src/image_util.rs:39-70) or tag_homography (src/image_util.rs:5-37) of every quad slot, themselves: d_maps
+ * [slots][9] floats, a row-major 3 x 3 matrix from the source square of side_bits and margin to the image (affine: tag_affine's
+ * two rows, then 0, 0, 1; homography: as above, w = 1 at the square's centre) -- to warp a tag patch, or to sample on a grid of
+ * the caller's own in front of agx_bit_code_enqueue.  d_quads / point_stride_bytes / n_frames / quads_per_frame / d_counts /
+ * d_point_status as agx_decode_positions_enqueue; side_bits in 1 .. 40 (2*16 + 8); no image size: neither function takes one.
+ * d_status[slot]: AGX_QUAD_SKIPPED, AGX_QUAD_OUTSIDE (a corner that is not finite), AGX_QUAD_DEGENERATE (homography only) or
+ * AGX_QUAD_DECODED; any other slot than the last writes no map.  Like agx_decode_positions_enqueue in every respect:
+ * caller-owned device arrays, stream-ordered, nothing to fetch, replaces the batch in flight without waiting.
+ * AGX_ERR_ARG: a NULL or misaligned (4 bytes) array other than d_counts / d_point_status, n_frames <= 0, quads_per_frame == 0,
+ * a bad point stride, 2^29 slots or more, side_bits outside 1 .. 40, a margin that is not finite, a degenerate source square,
+ * an unknown model. */
+int agx_tag_maps_enqueue(agx_detector *det, const void *d_quads, size_t point_stride_bytes, int n_frames,
+                         uint32_t quads_per_frame, const uint32_t *d_counts, const uint32_t *d_point_status, int side_bits,
+                         float margin, int model, float *d_maps, uint32_t *d_status);
+/* The two pub fns (src/image_util.rs:5-37, :39-70) in HOST memory, without a detector handle: quads a packed [n_quads][8]
+ * float array, maps [n_quads][9], status [n_quads].  Statuses, untouched maps and AGX_ERR_ARG as the batch call's. */
+int agx_tag_maps_tail(const void *quads, uint32_t n_quads, int side_bits, float margin, int model, float *maps,
+                      uint32_t *status);
+
 /* bit_code (src/detector.rs:74-122) of ANY sample points.  d_frames / n_frames / width / height / strides / format as
  * agx_decode_quads_enqueue (AGX_LF32 is AGX_ERR_FORMAT; every format but AGX_L8 goes through the device's to_luma8 plane).
  * d_points [slots][points_per_slot][2] floats, points_per_slot in 1 .. 64 (agx_decode_positions_enqueue's d_points with
