@@ -27,6 +27,10 @@ AGX_QUAD_DEGENERATE = 6
 # try_find_best_board of caller-given saddle lists (src/detector.rs:588-639): what became of a frame
 AGX_BOARD_FOUND, AGX_BOARD_NONE, AGX_BOARD_CAPACITY, AGX_BOARD_INPUT, AGX_BOARD_PENDING = 0, 1, 2, 3, 4
 AGX_GROW_FIX_MISSING = 1  # agx_grow_boards_enqueue / agx_grow_board_tail: flags
+# caller points snapped to the nearest listed saddle (agx_snap_points_enqueue / _tail): flag, per-frame status, "did not snap"
+AGX_SNAP_REVERSE = 1
+AGX_SNAP_OK, AGX_SNAP_INPUT = 0, 1
+AGX_SNAP_NONE = 0xFFFFFFFF
 # cluster centres of caller-given response planes (src/detector.rs:414-429): what became of a frame; INEXACT is a flag OR'd in
 AGX_CLUSTERS_OK, AGX_CLUSTERS_CAPACITY, AGX_CLUSTERS_BORDER, AGX_CLUSTERS_OVERFLOW, AGX_CLUSTERS_INEXACT = 0, 1, 2, 3, 0x100
 AGX_POINT_FILTERED = 4  # the k / phi filter (src/detector.rs:432-445) removed a refined point
@@ -137,6 +141,10 @@ SYMBOLS = {
     "agx_grow_boards_fetch": (C.c_int, [_P, C.c_int]),
     "agx_grow_board_tail": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, C.c_float, C.c_uint32, C.c_int, _P, C.c_uint32, C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_uint32), _P, C.POINTER(C.c_uint32)]),
+    "agx_snap_points_enqueue": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_uint32, _P, _P, _P, _P, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, _P,
+                                          C.c_float, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "agx_snap_points_tail": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.c_float, C.c_int, _P, _P, _P,
+                                       C.POINTER(C.c_uint32), _P, C.POINTER(C.c_uint32)]),
     "agx_planes_enqueue": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_float, _P, _P, C.c_size_t,
                                      C.c_size_t]),
     "agx_gaussian_blur_f32": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_float, _P]),

@@ -1719,6 +1719,65 @@ int agx::init_quads_fetch_impl(agx_detector *det, int n_threads)
     return resolve_handed_back<InitStage>(det, det->init, n_threads);
 }
 
+// ---- agx_snap_points_enqueue: caller points to the nearest listed saddle over the same lists: k_snap_points ----------------------
+// Everything in the caller's device arrays; nothing is handed back, so there is no batch record and no fetch.
+bool agx::snap_point_args_ok(size_t row_stride_bytes, size_t point_stride_bytes, uint32_t points_per_row, float max_dist_sq, int flags)
+{
+    if (points_per_row < 1 || points_per_row > 4) return false;
+    if ((row_stride_bytes & 3) || (point_stride_bytes & 3) || point_stride_bytes < 8 || point_stride_bytes > 0x7fffffffu) return false;
+    if (row_stride_bytes < (size_t)(points_per_row - 1) * point_stride_bytes + 8) return false;
+    return max_dist_sq >= 0.0f && !(flags & ~AGX_SNAP_REVERSE);  // (a NaN fails the comparison)
+}
+
+int agx::snap_points_enqueue_impl(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
+                                  const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status, const void *d_points,
+                                  size_t row_stride_bytes, size_t point_stride_bytes, uint32_t rows_per_frame, uint32_t points_per_row,
+                                  const uint32_t *d_row_counts, float max_dist_sq, int flags, uint32_t *d_slots, float *d_dist_sq, uint32_t *d_rows,
+                                  uint32_t *d_n_rows, uint32_t *d_row_index, uint32_t *d_status)
+{
+    if (!det) return AGX_ERR_ARG;
+    // the lists' checks with the rows in the seeds' place (this stage has no quads: 1 passes that check)
+    const ListArgs l{d_saddles, saddle_stride_bytes, n_frames, saddles_per_frame, d_counts, d_frame_table, d_point_status, 1u, nullptr, nullptr,
+                     nullptr, nullptr};
+    const uintptr_t own_ptrs = (uintptr_t)d_points | (uintptr_t)d_row_counts | (uintptr_t)d_slots | (uintptr_t)d_dist_sq | (uintptr_t)d_rows |
+                               (uintptr_t)d_n_rows | (uintptr_t)d_row_index | (uintptr_t)d_status;
+    if (const int rc = check_list_args(det, l, &rows_per_frame, own_ptrs, [&] {
+            if (!d_points || !d_slots || !d_rows || !d_n_rows || !d_status)
+                return fail(det, AGX_ERR_ARG, "d_points, d_slots, d_rows, d_n_rows and d_status are required");
+            if (!snap_point_args_ok(row_stride_bytes, point_stride_bytes, points_per_row, max_dist_sq, flags))
+                return fail(det, AGX_ERR_ARG, "points_per_row 1 .. 4, strides multiples of 4 that cover a point and a row, max_dist_sq >= 0, flags AGX_SNAP_REVERSE or 0");
+            return (int)AGX_OK;
+        }))
+        return rc;
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // and there is nothing of this one to be fetched
+    SnapPointsArgs s{};
+    s.saddles = static_cast<const uint8_t *>(d_saddles);
+    s.stride = (uint32_t)saddle_stride_bytes;
+    s.n_frames = n_frames;
+    s.saddles_per_frame = saddles_per_frame;
+    s.counts = d_counts;
+    s.frame_table = static_cast<const uint32_t *>(d_frame_table);
+    s.point_status = d_point_status;
+    s.points = static_cast<const uint8_t *>(d_points);
+    s.row_stride = row_stride_bytes;
+    s.point_stride = (uint32_t)point_stride_bytes;
+    s.rows_per_frame = rows_per_frame;
+    s.points_per_row = points_per_row;
+    s.row_counts = d_row_counts;
+    s.max_dist_sq = max_dist_sq;
+    s.flags = flags;
+    s.slots = d_slots;
+    s.dist_sq = d_dist_sq;
+    s.rows = d_rows;
+    s.n_rows = d_n_rows;
+    s.row_index = d_row_index;
+    s.status = d_status;
+    const hipError_t e = (hipError_t)launch_snap_points(s, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_snap_points: ") + hipGetErrorString(e));
+    return AGX_OK;
+}
+
 // The host tail of the frames `back` marks (1 handed back, 2 handed back as uncertain; without the device tail: every frame) of
 // the batch `b` in flight on `det`, on the pool: from the chain's compact saddle lists and those frames' u8 luma, copied down
 // from the device a group at a time.  cnt / st [n] get those frames' counts and statuses (a list of the chain overflowed: 0,

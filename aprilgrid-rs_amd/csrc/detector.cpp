@@ -1823,6 +1823,37 @@ int agx_grow_board_tail(const agx_saddle *saddles, uint32_t n_saddles, const uin
     });
 }
 
+// ---- caller points snapped to the nearest listed saddle (csrc/detect_batch.cpp, tail_kernels.hip: k_snap_points) ----------------
+int agx_snap_points_enqueue(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
+                            const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status, const void *d_points,
+                            size_t row_stride_bytes, size_t point_stride_bytes, uint32_t rows_per_frame, uint32_t points_per_row,
+                            const uint32_t *d_row_counts, float max_dist_sq, int flags, uint32_t *d_slots, float *d_dist_sq, uint32_t *d_rows,
+                            uint32_t *d_n_rows, uint32_t *d_row_index, uint32_t *d_status)
+{
+    return agx_guard(det, [&]() -> int {
+    return snap_points_enqueue_impl(det, d_saddles, saddle_stride_bytes, n_frames, saddles_per_frame, d_counts, d_frame_table, d_point_status,
+                                    d_points, row_stride_bytes, point_stride_bytes, rows_per_frame, points_per_row, d_row_counts, max_dist_sq,
+                                    flags, d_slots, d_dist_sq, d_rows, d_n_rows, d_row_index, d_status);
+    });
+}
+
+int agx_snap_points_tail(const agx_saddle *saddles, uint32_t n_saddles, const uint32_t *point_status, const void *points, size_t row_stride_bytes,
+                         size_t point_stride_bytes, uint32_t n_rows, uint32_t points_per_row, float max_dist_sq, int flags, uint32_t *slots,
+                         float *dist_sq, uint32_t *rows, uint32_t *n_rows_out, uint32_t *row_index, uint32_t *status)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (!n_rows_out || !status || (n_saddles && !saddles) || (n_rows && (!points || !slots || !rows))) return AGX_ERR_ARG;
+    if (!snap_point_args_ok(row_stride_bytes, point_stride_bytes, points_per_row, max_dist_sq, flags)) return AGX_ERR_ARG;
+    if (((uintptr_t)saddles | (uintptr_t)point_status | (uintptr_t)points | (uintptr_t)slots | (uintptr_t)dist_sq | (uintptr_t)rows |
+         (uintptr_t)row_index) & 3)
+        return AGX_ERR_ARG;
+    if (n_rows >= (1u << 27)) return AGX_ERR_ARG;
+    *status = snap_points(saddles, sizeof(agx_saddle), n_saddles, point_status, points, row_stride_bytes, point_stride_bytes, n_rows,
+                          points_per_row, max_dist_sq, flags, slots, dist_sq, rows, n_rows_out, row_index);
+    return AGX_OK;
+    });
+}
+
 }  // extern "C"
 
 // ---- gaussian_blur_f32 / hessian_response as planes (src/image_util.rs:110-206, :72-109; chain_kernels.hip) ---------------------

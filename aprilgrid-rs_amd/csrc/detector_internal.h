@@ -408,6 +408,14 @@ int init_quads_enqueue_impl(agx_detector *det, const void *d_saddles, size_t sad
                             uint32_t *d_quads, float *d_quad_points, uint32_t *d_n_quads, uint32_t *d_status, uint32_t *d_seed_quad_counts,
                             uint32_t *d_seeds_out, uint32_t *d_n_seeds_out);
 int init_quads_fetch_impl(agx_detector *det, int n_threads);
+// caller points to the nearest listed saddle over the same lists (detect_batch.cpp: k_snap_points; nothing to fetch)
+int snap_points_enqueue_impl(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames, uint32_t saddles_per_frame,
+                             const uint32_t *d_counts, const void *d_frame_table, const uint32_t *d_point_status, const void *d_points,
+                             size_t row_stride_bytes, size_t point_stride_bytes, uint32_t rows_per_frame, uint32_t points_per_row,
+                             const uint32_t *d_row_counts, float max_dist_sq, int flags, uint32_t *d_slots, float *d_dist_sq, uint32_t *d_rows,
+                             uint32_t *d_n_rows, uint32_t *d_row_index, uint32_t *d_status);
+// what both forms of the stage refuse in their point arguments (detector.cpp's agx_snap_points_tail checks the same)
+bool snap_point_args_ok(size_t row_stride_bytes, size_t point_stride_bytes, uint32_t points_per_row, float max_dist_sq, int flags);
 int group_detect_fetch_impl(agx_detector *det, const char *back, agx_tag *out, uint32_t *counts, int *frame_status, int n_threads);
 // What group.cpp calls for rank r's share of a detect batch (detector.cpp: the entry points' argument checks and guard around
 // the two functions above).  After the enqueue det->detect.device_tail says whether the pack kernel ran.

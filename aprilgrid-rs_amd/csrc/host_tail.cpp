@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <unordered_map>
 
@@ -1626,6 +1627,54 @@ void collect_tags(int n_codes, uint32_t n_quads, const uint32_t *quads, uint32_t
             for (int i = 0; i < 4; ++i) point_status[quads[4 * (size_t)q + i]] = AGX_POINT_USED;  // :521-536
     }
     *n_tags = total;
+}
+
+uint32_t snap_points(const void *slots, size_t stride, uint32_t n_slots, const uint32_t *point_status, const void *points, size_t row_stride,
+                     size_t point_stride, uint32_t n_rows, uint32_t points_per_row, float max_dist_sq, int flags, uint32_t *out_slots,
+                     float *dist_sq, uint32_t *rows, uint32_t *n_rows_out, uint32_t *row_index)
+{
+    const uint8_t *list = static_cast<const uint8_t *>(slots), *pts = static_cast<const uint8_t *>(points);
+    const auto listed = [&](uint32_t i) { return !point_status || point_status[i] == 0u; };
+    const auto coord = [&](uint32_t i, int c) {
+        float v;
+        std::memcpy(&v, list + (size_t)i * stride + 4 * (size_t)c, sizeof v);
+        return v;
+    };
+    *n_rows_out = 0;
+    for (uint32_t i = 0; i < n_slots; ++i)  // before anything is written
+        if (listed(i) && !(std::isfinite(coord(i, 0)) && std::isfinite(coord(i, 1)))) return AGX_SNAP_INPUT;
+    uint32_t kept = 0;
+    for (uint32_t r = 0; r < n_rows; ++r) {
+        uint32_t sp[4];
+        bool ok = true;
+        for (uint32_t p = 0; p < points_per_row; ++p) {
+            const uint32_t j = (flags & AGX_SNAP_REVERSE) ? points_per_row - 1 - p : p;
+            float q[2];
+            std::memcpy(q, pts + (size_t)r * row_stride + (size_t)j * point_stride, sizeof q);
+            float best = std::numeric_limits<float>::infinity();
+            uint32_t at = AGX_SNAP_NONE;
+            for (uint32_t i = 0; i < n_slots; ++i) {
+                if (!listed(i)) continue;
+                const float dx = coord(i, 0) - q[0], dy = coord(i, 1) - q[1];
+                const float d2 = dx * dx + dy * dy;  // squared_euclidean's fold; no contraction (the build's -ffp-contract=off)
+                if (d2 < best) {  // (+inf and NaN are no distance; at equal d2 the lowest slot stays)
+                    best = d2;
+                    at = i;
+                }
+            }
+            sp[p] = at != AGX_SNAP_NONE && best <= max_dist_sq ? at : AGX_SNAP_NONE;
+            out_slots[(size_t)r * points_per_row + p] = sp[p];
+            if (dist_sq) dist_sq[(size_t)r * points_per_row + p] = best;
+            ok = ok && sp[p] != AGX_SNAP_NONE;
+            for (uint32_t k = 0; k < p; ++k) ok = ok && sp[k] != sp[p];
+        }
+        if (!ok) continue;
+        std::memcpy(rows + (size_t)kept * points_per_row, sp, points_per_row * sizeof(uint32_t));
+        if (row_index) row_index[kept] = r;
+        ++kept;
+    }
+    *n_rows_out = kept;
+    return AGX_SNAP_OK;
 }
 
 }  // namespace agx

@@ -132,4 +132,14 @@ void collect_tags(int n_codes, uint32_t n_quads, const uint32_t *quads, uint32_t
                   const uint32_t *quad_status, uint32_t n_slots, uint32_t *point_status, uint32_t tag_cap, agx_tag *tags,
                   uint32_t *n_tags, uint32_t *tag_status);
 
+// Caller points to the nearest listed saddle of one frame's slots (agx_snap_points_tail; k_snap_points is the device form): row r
+// of n_rows has points_per_row (1 .. 4) points, point j two floats at points + r * row_stride + j * point_stride, read back to
+// front under AGX_SNAP_REVERSE.  d2 = dx*dx + dy*dy in binary32 (squared_euclidean's fold); the nearest is the smallest d2 below
+// +inf, at equal d2 the lowest slot; it is taken if d2 <= max_dist_sq.  out_slots / dist_sq (may be null) [n_rows][points_per_row]
+// in the order read; rows / row_index (may be null): the rows whose points all snapped to pairwise distinct slots, compacted.
+// -> AGX_SNAP_INPUT (a listed x or y that is not finite: only *n_rows_out = 0 is written) or AGX_SNAP_OK.
+uint32_t snap_points(const void *slots, size_t stride, uint32_t n_slots, const uint32_t *point_status, const void *points, size_t row_stride,
+                     size_t point_stride, uint32_t n_rows, uint32_t points_per_row, float max_dist_sq, int flags, uint32_t *out_slots,
+                     float *dist_sq, uint32_t *rows, uint32_t *n_rows_out, uint32_t *row_index);
+
 }  // namespace agx

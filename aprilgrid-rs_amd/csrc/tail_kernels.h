@@ -161,6 +161,37 @@ struct CollectTagsArgs {
 };
 // one wave per frame; n_codes in 1 .. 640 (the LDS tables are indexed by id); hipError_t
 int launch_collect_tags(const CollectTagsArgs &c, void *stream);
+// k_snap_points (agx_snap_points_enqueue): per frame every caller point to the nearest listed saddle of the frame's list, and the
+// rows whose points all snapped to pairwise distinct slots compacted in row order -- k_grow_boards' seed quads (4 points per row)
+// or k_init_quads' seed saddles (1) as they stand.  The list is read as FindBoardsArgs' (x and y only).  All pointers are device
+// pointers; host_tail.cpp's snap_points is the same on the host.
+constexpr uint32_t SNAP_CHUNK = 1024;        // listed saddles staged in LDS at a time
+constexpr uint32_t SNAP_ROWS_PER_WAVE = 4;   // rows one wave answers per pass: 16 lanes to a row, 4 to a point
+struct SnapPointsArgs {
+    const uint8_t *saddles;  // slot s: floats x, y at saddles + s * stride (k, theta and phi are never read)
+    uint32_t stride;         // bytes: a multiple of 4, >= 20
+    int n_frames;
+    uint32_t saddles_per_frame;
+    const uint32_t *counts;        // as FindBoardsArgs::counts
+    const uint32_t *frame_table;   // as FindBoardsArgs::frame_table (status & 7: AGX_SNAP_INPUT, nothing read)
+    const uint32_t *point_status;  // as FindBoardsArgs::point_status
+    const uint8_t *points;         // point j of row r of frame f: two floats at points + (f * rows_per_frame + r) * row_stride + j * point_stride
+    unsigned long long row_stride;  // bytes: a multiple of 4
+    uint32_t point_stride;          // bytes: a multiple of 4, >= 8
+    uint32_t rows_per_frame;        // > 0
+    uint32_t points_per_row;        // 1 .. 4
+    const uint32_t *row_counts;     // [n_frames]: frame f has min(row_counts[f], rows_per_frame) rows, or null: rows_per_frame
+    float max_dist_sq;              // >= 0, +inf allowed: a point snaps if d2 <= max_dist_sq
+    int flags;                      // AGX_SNAP_REVERSE
+    uint32_t *slots;      // [n_frames][rows_per_frame][points_per_row]: the slot within the frame or AGX_SNAP_NONE, in stored order
+    float *dist_sq;       // the same shape, or null: d2 to the nearest candidate, +inf where there is none
+    uint32_t *rows;       // [n_frames][rows_per_frame][points_per_row]: the compacted rows
+    uint32_t *n_rows;     // [n_frames]
+    uint32_t *row_index;  // [n_frames][rows_per_frame] or null: the row a compacted row came from
+    uint32_t *status;     // [n_frames]: AGX_SNAP_*
+};
+// one workgroup of four waves per frame; n_frames * rows_per_frame < 2^27; hipError_t
+int launch_snap_points(const SnapPointsArgs &s, void *stream);
 int init_tail_kernels();  // per-device kernel attributes (current device); hipError_t
 
 }  // namespace agx

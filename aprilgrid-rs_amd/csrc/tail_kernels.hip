@@ -2131,7 +2131,154 @@ __global__ void __launch_bounds__(64) k_collect_tags(CollectTagsArgs c)
     }
 }
 
+// ---- agx_snap_points_enqueue: caller points to the nearest listed saddle, and the rows that snapped whole ---------------------
+// One workgroup of SNAP_WAVES waves per frame.  A first walk over the frame's slots decides AGX_SNAP_INPUT before anything is
+// stored and leaves the first SNAP_CHUNK slots' x, y in LDS (an unlisted slot as NaN, which no comparison admits: the list needs
+// no compaction and a position in the chunk is its slot number).  Then passes of SNAP_ROWS_PER_WAVE rows per wave: sixteen lanes
+// to a row, four to a point, every lane folding its quarter of the chunk into one 64-bit key -- d2's bits above the slot number,
+// so that the unsigned minimum is the smallest d2 and at equal d2 the lowest slot (d2 >= +0: its bits order as it does) -- and
+// two xor-shuffles merge the four.  Lists beyond SNAP_CHUNK are restaged chunk by chunk inside every pass.  The rows that snapped
+// whole are placed by ballot within the wave, by a count per wave across them and by a running total across the passes: row order.
+constexpr int SNAP_WAVES = 4, SNAP_THREADS = 64 * SNAP_WAVES;
+constexpr uint32_t SNAP_ROWS_PER_PASS = SNAP_ROWS_PER_WAVE * SNAP_WAVES;
+constexpr u64 SNAP_EMPTY = ((u64)0x7f800000u << 32) | 0xffffffffull;  // (+inf, AGX_SNAP_NONE): no candidate
+static_assert(SNAP_ROWS_PER_WAVE * 16 == 64, "sixteen lanes to a row");
+
+__global__ void __launch_bounds__(SNAP_THREADS) k_snap_points(SnapPointsArgs s)
+{
+    __shared__ float lx[SNAP_CHUNK], ly[SNAP_CHUNK];
+    __shared__ uint32_t wcnt[2][SNAP_WAVES];
+    __shared__ uint32_t sh_bad;
+    const uint32_t f = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    u64 first_slot = (u64)f * (u64)s.saddles_per_frame, n_slots = s.saddles_per_frame;
+    bool input = false;
+    if (s.frame_table) {
+        const uint32_t *e = s.frame_table + 4 * (size_t)f;  // agx_frame_result: count, offset, status
+        input = (e[2] & 7u) != 0u;  // an overflow bit: there is no list; nothing of the frame is read
+        n_slots = e[0];
+        first_slot = e[1];
+    } else if (s.counts) {
+        const uint32_t c = s.counts[f];
+        n_slots = c < s.saddles_per_frame ? c : s.saddles_per_frame;
+    }
+    if (tid == 0) sh_bad = 0u;
+    __syncthreads();
+    // slots [base, base + SNAP_CHUNK) of the frame into lx / ly; `check`: every slot from base on is looked at
+    auto stage = [&](u64 base, bool check) {
+        bool bad = false;
+        for (u64 i = base + tid; i < n_slots && (check || i < base + SNAP_CHUNK); i += SNAP_THREADS) {
+            float x = __builtin_nanf(""), y = 0.0f;
+            if (!s.point_status || s.point_status[first_slot + i] == 0u) {  // (AGX_POINT_REFINED is 0)
+                const float *src = reinterpret_cast<const float *>(s.saddles + (first_slot + i) * (u64)s.stride);
+                x = src[0];
+                y = src[1];
+                bad = bad || !(f32_finite(x) && f32_finite(y));
+            }
+            if (i < base + SNAP_CHUNK) {
+                lx[i - base] = x;
+                ly[i - base] = y;
+            }
+        }
+        return bad;
+    };
+    if (!input && stage(0, true)) atomicOr(&sh_bad, 1u);
+    __syncthreads();
+    if (input || sh_bad) {  // (the whole workgroup alike)
+        if (tid == 0) {
+            s.n_rows[f] = 0u;
+            s.status[f] = AGX_SNAP_INPUT;
+        }
+        return;
+    }
+    const bool multi = n_slots > SNAP_CHUNK;
+    uint32_t n_rows = s.rows_per_frame;
+    if (s.row_counts) {
+        const uint32_t c = s.row_counts[f];
+        n_rows = c < n_rows ? c : n_rows;
+    }
+    const uint32_t ppr = s.points_per_row;
+    const uint32_t p = (lane >> 2) & 3u, sub = lane & 3u, lead = lane & 48u;  // the lane's point (stored order), its quarter, its row's first lane
+    const u64 row0 = (u64)f * (u64)s.rows_per_frame;
+    uint32_t total = 0;
+    for (uint32_t base = 0, pass = 0; base < n_rows; base += SNAP_ROWS_PER_PASS, ++pass) {
+        const uint32_t r = base + wave * SNAP_ROWS_PER_WAVE + (lane >> 4);  // (n_rows < 2^27: no wrap)
+        const bool have = r < n_rows && p < ppr;
+        float px = __builtin_nanf(""), py = 0.0f;  // (a lane without a point folds nothing: NaN admits no candidate)
+        if (have) {
+            const uint32_t j = (s.flags & AGX_SNAP_REVERSE) ? ppr - 1u - p : p;
+            const float *q = reinterpret_cast<const float *>(s.points + (row0 + r) * s.row_stride + (u64)j * s.point_stride);
+            px = q[0];
+            py = q[1];
+        }
+        u64 best = SNAP_EMPTY;
+        for (u64 cb = 0; cb < n_slots; cb += SNAP_CHUNK) {
+            if (multi) {
+                __syncthreads();
+                stage(cb, false);
+                __syncthreads();
+            }
+            const uint32_t cn = n_slots - cb < (u64)SNAP_CHUNK ? (uint32_t)(n_slots - cb) : SNAP_CHUNK;
+            for (uint32_t i = sub; i < cn; i += 4u) {
+                const float dx = __fsub_rn(lx[i], px), dy = __fsub_rn(ly[i], py);
+                const uint32_t bits = __float_as_uint(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+                const u64 key = ((u64)bits << 32) | (u64)(uint32_t)(cb + i);
+                if (bits < 0x7f800000u && key < best) best = key;  // (+inf and NaN are no distance)
+            }
+        }
+        u64 o = __shfl_xor(best, 1);
+        best = o < best ? o : best;
+        o = __shfl_xor(best, 2);
+        best = o < best ? o : best;
+        const float d2 = __uint_as_float((uint32_t)(best >> 32));
+        const uint32_t slot = have && best != SNAP_EMPTY && d2 <= s.max_dist_sq ? (uint32_t)best : AGX_SNAP_NONE;
+        if (have && sub == 0u) {
+            const u64 at = (row0 + r) * ppr + p;
+            s.slots[at] = slot;
+            if (s.dist_sq) s.dist_sq[at] = d2;
+        }
+        // the row: all of its points snapped, to pairwise distinct slots (its sixteen lanes decide alike)
+        uint32_t sp[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sp[k] = __shfl(slot, (int)(lead + 4u * k));
+        bool ok = r < n_rows;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if ((uint32_t)k < ppr) {
+                ok = ok && sp[k] != AGX_SNAP_NONE;
+#pragma unroll
+                for (int k2 = 0; k2 < k; ++k2) ok = ok && sp[k2] != sp[k];
+            }
+        const u64 mk = __ballot(ok && (lane & 15u) == 0u);
+        if (lane == 0) wcnt[pass & 1u][wave] = (uint32_t)__popcll(mk);
+        __syncthreads();  // (the other half of wcnt is the next pass's: one barrier a pass)
+        uint32_t at = total + (uint32_t)__popcll(mk & ((1ull << lead) - 1ull));
+        for (uint32_t w = 0; w < (uint32_t)SNAP_WAVES; ++w) {
+            const uint32_t cw = wcnt[pass & 1u][w];
+            if (w < wave) at += cw;
+            total += cw;
+        }
+        if (ok && sub == 0u && p < ppr) s.rows[(row0 + at) * ppr + p] = slot;  // (at < n_rows <= rows_per_frame)
+        if (ok && (lane & 15u) == 0u && s.row_index) s.row_index[row0 + at] = r;
+    }
+    if (tid == 0) {
+        s.n_rows[f] = total;
+        s.status[f] = AGX_SNAP_OK;
+    }
+}
+
 }  // namespace
+
+int launch_snap_points(const SnapPointsArgs &s, void *stream)
+{
+    if (s.n_frames <= 0 || s.stride < 20 || (s.stride & 3) || !s.saddles_per_frame || (s.counts && s.frame_table) || !s.saddles || !s.points ||
+        !s.rows_per_frame || s.points_per_row < 1 || s.points_per_row > 4 || s.point_stride < 8 || (s.point_stride & 3) || (s.row_stride & 3) ||
+        s.row_stride < (unsigned long long)(s.points_per_row - 1) * s.point_stride + 8 || !(s.max_dist_sq >= 0.0f) ||
+        (s.flags & ~AGX_SNAP_REVERSE) || (unsigned long long)s.n_frames * s.rows_per_frame >= (1ull << 27) || !s.slots || !s.rows || !s.n_rows ||
+        !s.status)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_snap_points, dim3((unsigned)s.n_frames), dim3(SNAP_THREADS), 0, (hipStream_t)stream, s);
+    return (int)hipGetLastError();
+}
 
 int launch_collect_tags(const CollectTagsArgs &c, void *stream)
 {

@@ -15,6 +15,8 @@ Same names, argument meaning and error behaviour as the reference where Python a
   TagDetector.find_board              src/detector.rs:588-639 (the crate's pub fn try_find_best_board)
   TagDetector.detect_staged           src/detector.rs:505-540 as the staged chain on device tensors; its rounds (:510-539) by
                                       TagDetector.collect_tags_enqueue / collect_tags
+  TagDetector.detect_tracked          the same from last call's tags: TagDetector.snap_points_enqueue / snap_points (no reference
+                                      item: the prior corners snapped to this frame's saddles) -> grow boards -> decode -> collect
   TagDetector.gaussian_blur_f32       src/image_util.rs:110-206 (the crate's pub fn, any sigma up to 8)
   TagDetector.hessian_response        src/image_util.rs:72-109 (the crate's pub fn)
 An image is a numpy array standing for the DynamicImage variants the reference is fed:
@@ -1102,6 +1104,41 @@ class TagDetector:
             self._replaces_batch()
         self._check(self._lib.agx_init_quads_fetch(self._h, n_threads))
 
+    # ---- caller points snapped to the nearest listed saddle (agx_snap_points_enqueue) -----------
+    def snap_points_enqueue(self, saddles, points, slots, rows, n_rows, status, max_dist_sq, counts=None, frame_table=None, point_status=None,
+                            row_counts=None, reverse=False, dist_sq=None, row_index=None):
+        """Every caller point to the nearest listed saddle of its frame (squared distance in binary32, the lowest slot at equal
+        distance, taken if it is <= max_dist_sq), stream-ordered behind torch's current stream; nothing to fetch.  saddles, counts,
+        frame_table and point_status as find_boards_enqueue's.  points: float32 [N, R, P, 2] with P in 1 .. 4 -- or a tag table,
+        int32 [N, R, 9] as collect_tags_enqueue and detect_batch_enqueue(out=...) leave it, whose corners are read in place (P = 4;
+        with reverse=True they are a quad in init_quads' winding); row_counts int32 [N] optionally.  slots int32 [N, R, P]: the
+        slot within the frame or -1 (AGX_SNAP_NONE), in the order read; rows int32 [N, R, P] with n_rows int32 [N]: the rows whose
+        points all snapped to distinct slots, compacted -- grow_boards_enqueue's seed_quads / seed_counts (P = 4) or
+        init_quads_enqueue's seed_saddles / seed_counts (P = 1; pass rows.view(N, R)) as they stand; status int32 [N]: AGX_SNAP_*.
+        dist_sq float32 [N, R, P] and row_index int32 [N, R] optionally."""
+        import torch
+        n, spf, stride, tensor, p_counts, p_table, p_ps = self._stage_lists(saddles, counts, frame_table, point_status)
+        ok = getattr(points, "is_cuda", False) and points.is_contiguous() and points.device == saddles.device and points.shape[0] == n
+        if ok and points.dtype == torch.int32 and points.dim() == 3 and points.shape[2] == 9 and points.shape[1] > 0:
+            rpf, ppr, p_points, row_stride = int(points.shape[1]), 4, points.data_ptr() + 4, 36
+        elif ok and points.dtype == torch.float32 and points.dim() == 4 and points.shape[3] == 2 and points.shape[1] > 0 and 1 <= points.shape[2] <= 4:
+            rpf, ppr, p_points = int(points.shape[1]), int(points.shape[2]), points.data_ptr()
+            row_stride = 8 * ppr
+        else:
+            raise AgxError(_ffi.AGX_ERR_ARG, "points must be a contiguous device tensor on the saddles' device: float32 [N, R, 1..4, 2] or a tag table int32 [N, R, 9]")
+        if slots is None or rows is None or n_rows is None or status is None:
+            raise AgxError(_ffi.AGX_ERR_ARG, "slots, rows, n_rows and status must be given")
+        outs = (tensor(slots, torch.int32, (n, rpf, ppr), "slots"), tensor(dist_sq, torch.float32, (n, rpf, ppr), "dist_sq"),
+                tensor(rows, torch.int32, (n, rpf, ppr), "rows"), tensor(n_rows, torch.int32, (n,), "n_rows"),
+                tensor(row_index, torch.int32, (n, rpf), "row_index"), tensor(status, torch.int32, (n,), "status"))
+        p_row_counts = tensor(row_counts, torch.int32, (n,), "row_counts")
+        self._follow_torch_stream(saddles)
+        rc = self._lib.agx_snap_points_enqueue(self._h, saddles.data_ptr(), stride, n, spf, p_counts, p_table, p_ps, p_points, row_stride, 8, rpf, ppr,
+                                               p_row_counts, float(max_dist_sq), _ffi.AGX_SNAP_REVERSE if reverse else 0, *outs)
+        if rc == _ffi.AGX_OK:  # (a refused argument leaves the batch in flight where it is)
+            self._replaces_batch()
+        self._check(rc)
+
     def find_boards_staged(self, saddles, spacing_ratio=0.3, counts=None, point_status=None, quads_per_frame=128, candidates_per_frame=1024,
                            n_nearest=50):
         """try_find_best_board (src/detector.rs:588-639) as its stages on device tensors, at ANY spacing_ratio: the reference's seeds
@@ -1391,15 +1428,7 @@ class TagDetector:
         tpf = int(tags_per_frame)
         dev = frames.device
         i32 = dict(dtype=torch.int32, device=dev)
-        blur = torch.empty((n, h, w), dtype=torch.float32, device=dev)
-        resp = torch.empty_like(blur)
-        rows, pts = torch.zeros((n, cpf, 4), **i32), torch.zeros((n, cpf, 2), dtype=torch.float32, device=dev)
-        counts, cstatus = torch.zeros(n, **i32), torch.zeros(n, **i32)
-        records, pstatus = torch.zeros((n, cpf, 5), dtype=torch.float32, device=dev), torch.zeros((n, cpf), **i32)
-        self.planes_enqueue(frames, self.blur_sigma, blur=blur, response=resp, format=format)
-        self.clusters_enqueue(resp, clusters=rows, points=pts, counts=counts, status=cstatus)
-        self.refine_points_enqueue(blur, pts, counts=counts, out=records, status=pstatus, image="plane", half_size_patch=self.half_size_patch)
-        self.filter_saddles_enqueue(records, pstatus, counts=counts)
+        records, counts, pstatus, cstatus = self._staged_saddles(frames, n, w, h, cpf, format)
         quads, qpts = torch.zeros((n, qpf, 4), **i32), torch.zeros((n, qpf, 4, 2), dtype=torch.float32, device=dev)
         nq, bst = torch.zeros(n, **i32), torch.zeros(n, **i32)
         qtags, qst = torch.zeros((n, qpf, 9), **i32), torch.zeros((n, qpf), **i32)
@@ -1423,19 +1452,118 @@ class TagDetector:
             self.collect_tags_enqueue(quads, nq, bst, qtags, qst, pstatus if r + 1 < rounds else None, tags, ntags, tst, reset=r == 0,
                                       saddles_per_frame=cpf)
         self.sync()
+        return self._staged_result("detect_staged", cstatus, cpf, tags, ntags, tst)
+
+    def _staged_saddles(self, frames, n, w, h, cpf, format):
+        """The staged chain up to the saddle lists: planes at the handle's sigma, clusters, refine on the blur plane at the
+        handle's half_size_patch, the k / phi filter -> (records float32 [N, cpf, 5], counts int32 [N], point status int32 [N, cpf],
+        cluster status int32 [N]), device tensors as find_boards_enqueue reads them."""
+        import torch
+        dev = frames.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        blur = torch.empty((n, h, w), dtype=torch.float32, device=dev)
+        resp = torch.empty_like(blur)
+        rows, pts = torch.zeros((n, cpf, 4), **i32), torch.zeros((n, cpf, 2), dtype=torch.float32, device=dev)
+        counts, cstatus = torch.zeros(n, **i32), torch.zeros(n, **i32)
+        records, pstatus = torch.zeros((n, cpf, 5), dtype=torch.float32, device=dev), torch.zeros((n, cpf), **i32)
+        self.planes_enqueue(frames, self.blur_sigma, blur=blur, response=resp, format=format)
+        self.clusters_enqueue(resp, clusters=rows, points=pts, counts=counts, status=cstatus)
+        self.refine_points_enqueue(blur, pts, counts=counts, out=records, status=pstatus, image="plane", half_size_patch=self.half_size_patch)
+        self.filter_saddles_enqueue(records, pstatus, counts=counts)
+        return records, counts, pstatus, cstatus
+
+    def _staged_result(self, who, cstatus, cpf, tags, ntags, tst, skip=None):
+        """The frames' tag tables (device tensors of collect_tags_enqueue) -> one {tag_id: 4x2 corners} per frame in row order; a
+        frame whose clusters or tags could not be held raises.  skip: a bool per frame, True = not looked at (its entry is None)."""
+        n, tpf = int(tags.shape[0]), int(tags.shape[1])
         cstatus, tst, ntags = cstatus.cpu().numpy(), tst.cpu().numpy(), ntags.cpu().numpy()
         table = tags.cpu().numpy().view(np.uint32).reshape(n, tpf, 9)
         out = []
         for f in range(n):
+            if skip is not None and skip[f]:
+                out.append(None)
+                continue
             if (int(cstatus[f]) & 0xFF) != _ffi.AGX_CLUSTERS_OK:
-                raise AgxError(_ffi.AGX_ERR_CAPACITY, "detect_staged: frame %d: cluster status %d (AGX_CLUSTERS_*; clusters_per_frame = %d)"
-                               % (f, int(cstatus[f]), cpf))
+                raise AgxError(_ffi.AGX_ERR_CAPACITY, "%s: frame %d: cluster status %d (AGX_CLUSTERS_*; clusters_per_frame = %d)"
+                               % (who, f, int(cstatus[f]), cpf))
             if int(tst[f]) != _ffi.AGX_TAGS_OK:
                 raise AgxError(_ffi.AGX_ERR_CAPACITY if int(tst[f]) != _ffi.AGX_TAGS_PENDING else _ffi.AGX_ERR_STATE,
-                               "detect_staged: frame %d: tag status %s" % (f, self._TAGS_STATUS.get(int(tst[f]), str(int(tst[f])))))
+                               "%s: frame %d: tag status %s" % (who, f, self._TAGS_STATUS.get(int(tst[f]), str(int(tst[f])))))
             t = table[f, :int(ntags[f])]
             out.append({int(row[0]): row[1:].view(np.float32).reshape(4, 2).copy() for row in t})
         return out
+
+    def detect_tracked(self, frames, prior, max_dist=5.0, spacing_ratio=0.3, seeds_per_frame=None, clusters_per_frame=4096, quads_per_frame=128,
+                       tags_per_frame=None, format=None):
+        """detect (src/detector.rs:505-540) of a batch whose boards are known from the last call: instead of the board search, the
+        prior tags' corners are snapped to this frame's saddles (snap_points_enqueue, within max_dist px) and the boards grown from
+        them as seed quads.  frames and format= as detect_batch_enqueue.  prior: last call's tags per frame -- a list of
+        {tag_id: 4x2 corners} (what detect_batch returns), or (tags int32 [N, T, 9], counts int32 [N]), the device tag table of
+        detect_batch_enqueue(out=...) / collect_tags_enqueue and its counts.  The staged chain up to the saddle lists, then
+        max_num_of_boards rounds of snap (corners back to front, listed slots only) -> grow boards at spacing_ratio with
+        try_fix_missing -> grow_boards_fetch -> decode -> collect.  seeds_per_frame: only the first that many prior tags of a frame
+        are seeds (None: all of them).  A frame with no snapped row, or whose first round's board status is not AGX_BOARD_FOUND, is
+        not tracked: those frames, and only those, are run through detect_staged.
+        -> (one {tag_id: 4x2 corners} per frame as detect_batch, tracked bool [N])."""
+        import torch
+        fmt, bpp = self._tensor_format(frames, format)
+        n, w, h, _, _ = self._tensor_geometry(frames, fmt, bpp)
+        n, w, h = int(n), int(w), int(h)
+        cpf, qpf = int(clusters_per_frame), int(quads_per_frame)
+        if tags_per_frame is None:
+            n_codes = C.c_int(0)
+            self._check(self._lib.agx_detector_family_info(self._h, None, None, None, None, C.byref(n_codes)))
+            tags_per_frame = n_codes.value
+        tpf = int(tags_per_frame)
+        dev = frames.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        if isinstance(prior, (list, tuple)) and len(prior) == 2 and getattr(prior[0], "is_cuda", False):
+            ptags, pcounts = prior
+            if ptags.dim() != 3 or ptags.shape[0] != n or pcounts.shape != (n,):
+                raise AgxError(_ffi.AGX_ERR_ARG, "prior tags int32 [N, T, 9] and counts int32 [N]")
+        else:
+            if len(prior) != n:
+                raise AgxError(_ffi.AGX_ERR_ARG, "prior: one {tag_id: corners} per frame")
+            table = np.zeros((n, max([len(d) for d in prior] + [1]), 9), np.uint32)
+            for f, d in enumerate(prior):
+                for r, (tag_id, xy) in enumerate(d.items()):
+                    table[f, r, 0] = int(tag_id)
+                    table[f, r, 1:] = np.ascontiguousarray(xy, np.float32).reshape(8).view(np.uint32)
+            ptags = torch.from_numpy(table.view(np.int32)).to(dev)
+            pcounts = torch.tensor([len(d) for d in prior], **i32)
+        if seeds_per_frame is not None:
+            pcounts = torch.clamp(pcounts, max=int(seeds_per_frame))
+        rpf = int(ptags.shape[1])
+        records, counts, pstatus, cstatus = self._staged_saddles(frames, n, w, h, cpf, format)
+        slots, seeds = torch.zeros((n, rpf, 4), **i32), torch.zeros((n, rpf, 4), **i32)
+        nseeds, sst = torch.zeros(n, **i32), torch.zeros(n, **i32)
+        quads, qpts = torch.zeros((n, qpf, 4), **i32), torch.zeros((n, qpf, 4, 2), dtype=torch.float32, device=dev)
+        nq, bst = torch.zeros(n, **i32), torch.zeros(n, **i32)
+        qtags, qst = torch.zeros((n, qpf, 9), **i32), torch.zeros((n, qpf), **i32)
+        tags, ntags, tst = torch.zeros((n, tpf, 9), **i32), torch.zeros(n, **i32), torch.zeros(n, **i32)
+        rounds = int(self.detector_params.max_num_of_boards)
+        tracked = None
+        for r in range(rounds):
+            self.snap_points_enqueue(records, ptags, slots, seeds, nseeds, sst, float(max_dist) * float(max_dist), counts=counts,
+                                     point_status=pstatus, row_counts=pcounts, reverse=True)
+            self.grow_boards_enqueue(records, seeds, quads, nq, bst, counts=counts, point_status=pstatus, seed_counts=nseeds,
+                                     spacing_ratio=spacing_ratio, fix_missing=True, quad_points=qpts)
+            self.grow_boards_fetch()
+            if r == 0:
+                tracked = (nseeds > 0) & (bst == _ffi.AGX_BOARD_FOUND)
+            self.decode_quads_enqueue(frames, qpts, counts=nq, out=qtags, status=qst, format=format)
+            self.collect_tags_enqueue(quads, nq, bst, qtags, qst, pstatus if r + 1 < rounds else None, tags, ntags, tst, reset=r == 0,
+                                      saddles_per_frame=cpf)
+        self.sync()
+        tracked = tracked.cpu().numpy().astype(bool) if tracked is not None else np.zeros(n, bool)
+        out = self._staged_result("detect_tracked", cstatus, cpf, tags, ntags, tst, skip=~tracked)
+        lost = np.flatnonzero(~tracked)
+        if lost.size:
+            again = self.detect_staged(frames[torch.from_numpy(lost).to(dev)].contiguous(), clusters_per_frame=cpf, quads_per_frame=qpf,
+                                       tags_per_frame=tpf, format=format)
+            for f, res in zip(lost, again):
+                out[int(f)] = res
+        return out, tracked
 
     # ---- measurement / parity hooks ------------------------------------------------------
     def profile_enable(self, level=2):
@@ -1697,6 +1825,37 @@ def best_tag(bits, thres, codes=None, edge_bits=None, tag_family=None, status_in
     if st != _ffi.AGX_OK:
         raise AgxError(st)
     return (ids, rotations, status, tags) if tags is not None else (ids, rotations, status)
+
+
+def snap_points(saddles, points, max_dist_sq, reverse=False, point_status=None):
+    """The host form of snap_points_enqueue for one list (agx_snap_points_tail) without a device: saddles a SADDLE_DTYPE array (or
+    [n, 5] float32); points float32 [R, P, 2] with P in 1 .. 4, or R rows of TagDetector.TAG_DTYPE, whose corners are read in
+    place (P = 4) -> (slots [R, P] uint32, AGX_SNAP_NONE where a point did not snap; dist_sq [R, P] float32; rows [K, P] uint32,
+    the rows that snapped whole, compacted; row_index [K] uint32; status AGX_SNAP_*)."""
+    a = np.asarray(saddles)
+    if a.dtype == SADDLE_DTYPE:
+        a = np.ascontiguousarray(a).view(np.float32)
+    a = np.ascontiguousarray(a, np.float32).reshape(-1, 5)
+    pts = np.asarray(points)
+    if pts.dtype == TagDetector.TAG_DTYPE:
+        pts = np.ascontiguousarray(pts).reshape(-1)
+        n_rows, ppr, row_stride, p_points = pts.shape[0], 4, 36, pts.ctypes.data + 4
+    else:
+        pts = np.ascontiguousarray(pts, np.float32)
+        if pts.ndim != 3 or pts.shape[2] != 2:
+            raise AgxError(_ffi.AGX_ERR_ARG, "points must be [R, P, 2] or rows of TAG_DTYPE")
+        n_rows, ppr, p_points = pts.shape[0], pts.shape[1], pts.ctypes.data
+        row_stride = 8 * ppr
+    ps = None if point_status is None else np.ascontiguousarray(point_status, np.uint32).reshape(a.shape[0])
+    room = (max(n_rows, 1), max(ppr, 1))
+    slots, dist, rows, index = np.zeros(room, np.uint32), np.zeros(room, np.float32), np.zeros(room, np.uint32), np.zeros(room[0], np.uint32)
+    kept, status = C.c_uint32(0), C.c_uint32(0)
+    st = _ffi.lib().agx_snap_points_tail(a.ctypes.data if a.shape[0] else None, a.shape[0], ps.ctypes.data if ps is not None and ps.size else None,
+                                         p_points, row_stride, 8, n_rows, ppr, float(max_dist_sq), _ffi.AGX_SNAP_REVERSE if reverse else 0,
+                                         slots.ctypes.data, dist.ctypes.data, rows.ctypes.data, C.byref(kept), index.ctypes.data, C.byref(status))
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    return slots[:n_rows], dist[:n_rows], rows[:kept.value].copy(), index[:kept.value].copy(), status.value
 
 
 def _find_board_call(call, saddles, cap, keep=None):

@@ -135,6 +135,11 @@ pub const AGX_BOARD_INPUT: c_int = 3;
 pub const AGX_BOARD_PENDING: c_int = 4;
 // agx_grow_boards_enqueue / agx_grow_board_tail: flags
 pub const AGX_GROW_FIX_MISSING: c_int = 1;
+// agx_snap_points_enqueue / agx_snap_points_tail: flag, what became of a frame, and the slot of a point that did not snap
+pub const AGX_SNAP_REVERSE: c_int = 1;
+pub const AGX_SNAP_OK: c_int = 0;
+pub const AGX_SNAP_INPUT: c_int = 1;
+pub const AGX_SNAP_NONE: u32 = 0xFFFF_FFFF;
 // cluster centres of caller-given response planes (reference src/detector.rs:414-429): what became of a frame
 pub const AGX_CLUSTERS_OK: c_int = 0;
 pub const AGX_CLUSTERS_CAPACITY: c_int = 1;
@@ -305,6 +310,17 @@ extern "C" {
     pub fn agx_grow_board_tail(saddles: *const agx_saddle, n_saddles: u32, point_status: *const u32, seed_quads: *const u32, n_seeds: u32,
                                spacing_ratio: c_float, stop_score: u32, flags: c_int, quads: *mut u32, cap: u32, n_quads: *mut u32,
                                status: *mut u32, seed_scores: *mut u32, best_seed: *mut u32) -> c_int;
+
+    pub fn agx_snap_points_enqueue(det: *mut agx_detector, d_saddles: *const c_void, saddle_stride_bytes: usize, n_frames: c_int,
+                                   saddles_per_frame: u32, d_counts: *const u32, d_frame_table: *const c_void, d_point_status: *const u32,
+                                   d_points: *const c_void, row_stride_bytes: usize, point_stride_bytes: usize, rows_per_frame: u32,
+                                   points_per_row: u32, d_row_counts: *const u32, max_dist_sq: c_float, flags: c_int, d_slots: *mut u32,
+                                   d_dist_sq: *mut c_float, d_rows: *mut u32, d_n_rows: *mut u32, d_row_index: *mut u32,
+                                   d_status: *mut u32) -> c_int;
+    pub fn agx_snap_points_tail(saddles: *const agx_saddle, n_saddles: u32, point_status: *const u32, points: *const c_void,
+                                row_stride_bytes: usize, point_stride_bytes: usize, n_rows: u32, points_per_row: u32, max_dist_sq: c_float,
+                                flags: c_int, slots: *mut u32, dist_sq: *mut c_float, rows: *mut u32, n_rows_out: *mut u32,
+                                row_index: *mut u32, status: *mut u32) -> c_int;
 
     pub fn agx_planes_enqueue(det: *mut agx_detector, d_frames: *const c_void, n_frames: c_int, width: c_int, height: c_int,
                               row_stride_bytes: usize, frame_stride_bytes: usize, format: c_int, sigma: c_float, d_blur: *mut c_float,

@@ -546,6 +546,36 @@ pub fn grow_board_tail(refined: &[Saddle], seeds: &[[usize; 4]], spacing_ratio: 
     }
 }
 
+/// Corners known from an earlier frame snapped to this frame's saddles: every point of every row (`N` = 1..=4 points a row) to the
+/// nearest saddle of `refined` by `kdtree::distance::squared_euclidean` in `f32` (reference src/detector.rs:15), the lowest index
+/// at equal distance, taken if the squared distance is at most `max_dist_sq`; `reverse` reads a row back to front (a tag's
+/// corners, src/detector.rs:467-470, are then a quad in `init_quads`' winding).  Returns `(slots, rows)`: per row and point the
+/// saddle index or `None`, and `(row, indices)` of the rows whose points all snapped to pairwise distinct saddles, in row order --
+/// with `N` = 4 the seeds of `grow_board_tail`.  The host form (no device is used).  Panics on a saddle whose x or y is not finite
+/// and on a `max_dist_sq` that is negative or NaN.
+pub fn snap_points_tail<const N: usize>(refined: &[Saddle], rows: &[[(f32, f32); N]], max_dist_sq: f32, reverse: bool)
+                                        -> (Vec<[Option<usize>; N]>, Vec<(usize, [usize; N])>) {
+    assert!((1..=4).contains(&N), "snap_points_tail: 1 to 4 points a row");
+    let list: Vec<ffi::agx_saddle> =
+        refined.iter().map(|s| ffi::agx_saddle { x: s.p.0, y: s.p.1, k: s.k, theta: s.theta, phi: s.phi }).collect();
+    let flat: Vec<f32> = rows.iter().flat_map(|r| r.iter().flat_map(|p| [p.0, p.1])).collect();
+    let mut slots = vec![0u32; (rows.len() * N).max(1)];
+    let mut kept = vec![0u32; (rows.len() * N).max(1)];
+    let mut index = vec![0u32; rows.len().max(1)];
+    let (mut n_kept, mut status) = (0u32, 0u32);
+    let st = unsafe {
+        ffi::agx_snap_points_tail(list.as_ptr(), list.len() as u32, std::ptr::null(), flat.as_ptr() as *const c_void, 8 * N, 8, rows.len() as u32,
+                                  N as u32, max_dist_sq, if reverse { ffi::AGX_SNAP_REVERSE } else { 0 }, slots.as_mut_ptr(),
+                                  std::ptr::null_mut(), kept.as_mut_ptr(), &mut n_kept, index.as_mut_ptr(), &mut status)
+    };
+    assert_eq!(st, ffi::AGX_OK, "agx_snap_points_tail failed: {}", st);
+    assert_eq!(status as c_int, ffi::AGX_SNAP_OK, "snap_points_tail: a saddle's x or y is not finite");
+    let per_point = |v: u32| if v == ffi::AGX_SNAP_NONE { None } else { Some(v as usize) };
+    let all: Vec<[Option<usize>; N]> = (0..rows.len()).map(|r| std::array::from_fn(|p| per_point(slots[r * N + p]))).collect();
+    let whole = (0..n_kept as usize).map(|k| (index[k] as usize, std::array::from_fn(|p| kept[k * N + p] as usize))).collect();
+    (all, whole)
+}
+
 /// reference src/detector.rs:42-72, `decode_positions`: the sample points of a quad (four corners), x outer and y inner, or
 /// `None` where a rounded corner lies outside the image.  The host form (no device is used).  A corner that is not finite is
 /// `None`.  Panics where the library refuses the arguments: `edge_bits` outside 1..=8, `border_bits` above 16, a margin that

@@ -834,6 +834,70 @@ int agx_grow_board_tail(const agx_saddle *saddles, uint32_t n_saddles, const uin
                         uint32_t *quads, uint32_t cap, uint32_t *n_quads, uint32_t *status,
                         uint32_t *seed_scores, uint32_t *best_seed);
 
+/* ---- caller points snapped to the nearest listed saddle ------------------------------------ */
+
+/* The link from an earlier frame's corners -- a tag table, a quad predicted from a pose, one tracked corner -- to THIS frame's
+ * slot numbers: every caller point is mapped to the nearest listed saddle of its frame's list, and the rows whose points all
+ * snapped are compacted into the seeds agx_grow_boards_enqueue (4 points per row: d_seed_quads / d_seed_counts) and
+ * agx_init_quads_enqueue (1: d_seed_saddles / d_seed_counts) take as they stand.  The reference has no such function; the
+ * distance is kdtree::distance::squared_euclidean, the fold over the two axes that init_quads' tree is asked with
+ * (src/detector.rs:15, :550).  A corner may have
+ * moved by any distance up to sqrt(max_dist_sq): agx_refine_points_enqueue, the other way from old corners to new records,
+ * rejects a point that moved more than 1 px.
+ * Per frame over saddle lists in DEVICE memory, stream-ordered on the detector's stream (the caller's after
+ * agx_detector_set_stream); returns without waiting.  d_saddles, saddle_stride_bytes, n_frames, saddles_per_frame, d_counts,
+ * d_frame_table and d_point_status are read exactly as agx_find_boards_enqueue reads them: only slots whose status word is 0 are
+ * candidates; an overflow bit in a table entry, or a listed saddle with a non-finite x or y, makes the frame AGX_SNAP_INPUT,
+ * decided before the frame's first store.  k, theta and phi are never read.  Lists of any length are answered on the device:
+ * nothing is handed back, no frame is ever pending and there is nothing to fetch.
+ *   d_points        row r of frame f starts at d_points + (f*rows_per_frame + r)*row_stride_bytes, its point j is two floats
+ *                   (x, y) at + j*point_stride_bytes; points_per_row is 1 .. 4.  Both strides are multiples of 4, the point
+ *                   stride at least 8, and the row stride covers (points_per_row - 1)*point_stride_bytes + 8.  With
+ *                   &d_tags[0].xy, row stride sizeof(agx_tag) and point stride 8 a tag table of agx_collect_tags_enqueue or
+ *                   agx_detect_batch_enqueue_to is read in place (rows_per_frame = its rows per frame, d_row_counts = its counts).
+ *   d_row_counts    NULL, or [n_frames]: frame f has min(d_row_counts[f], rows_per_frame) rows.
+ *   max_dist_sq     the SQUARED distance itself, >= 0, +inf allowed: nothing is squared on either side.
+ *   flags           AGX_SNAP_REVERSE reads a row's points back to front.  A tag's xy is rotate_left(rotation); reverse() of its
+ *                   quad (src/detector.rs:467-470): read backwards it is a cyclic rotation of that quad in init_quads' winding
+ *                   (:577-581), which Board::new grows in all four directions alike.
+ * Arithmetic, all binary32 with no contraction: dx = sx - px, dy = sy - py, d2 = dx*dx + dy*dy.  The nearest is the candidate
+ * with the smallest d2 below +inf; at equal d2 the lowest slot number wins.  The point snaps if d2 <= max_dist_sq.  A point with
+ * a non-finite coordinate has no d2 below +inf and never snaps.
+ * Results, frame f, all caller-owned device memory, 4-byte aligned:
+ *   d_slots   [n_frames][rows_per_frame][points_per_row]: the slot within the frame, or AGX_SNAP_NONE, in the order the row was
+ *             read (under AGX_SNAP_REVERSE the reversed order);
+ *   d_dist_sq the same shape, optional: d2 to the nearest candidate, whether it snapped or not; +inf where there is none;
+ *   d_rows    [n_frames][rows_per_frame][points_per_row] with d_n_rows[f]: the rows whose points ALL snapped, to pairwise distinct
+ *             slots, compacted in row order.  Two rows that snap to the same slots are both kept;
+ *   d_row_index [n_frames][rows_per_frame], optional: the row each compacted row came from;
+ *   d_status[f]: AGX_SNAP_OK, or AGX_SNAP_INPUT: d_n_rows[f] = 0, and nothing else of the frame is written.
+ * Only entries below a frame's row count (d_slots, d_dist_sq) and below d_n_rows[f] (d_rows, d_row_index) are ever written.
+ * Like agx_filter_saddles_enqueue the call replaces the batch in flight without waiting; every kind's fetch is AGX_ERR_STATE then.
+ * AGX_ERR_ARG (a batch in flight stays where it is): the list-argument errors of agx_find_boards_enqueue; NULL d_points, d_slots,
+ * d_rows, d_n_rows or d_status; points_per_row outside 1 .. 4; rows_per_frame == 0; a stride that is not a multiple of 4, a
+ * point stride below 8 or a row stride that does not cover the row; a negative or NaN max_dist_sq; an unknown flag; a pointer
+ * that is not 4-byte aligned; 2^27 or more rows in the batch. */
+enum { AGX_SNAP_REVERSE = 1 };                /* flags */
+enum { AGX_SNAP_OK = 0, AGX_SNAP_INPUT = 1 }; /* per frame */
+#define AGX_SNAP_NONE 0xFFFFFFFFu             /* d_slots: the point did not snap */
+int agx_snap_points_enqueue(agx_detector *det, const void *d_saddles, size_t saddle_stride_bytes, int n_frames,
+                            uint32_t saddles_per_frame, const uint32_t *d_counts, const void *d_frame_table,
+                            const uint32_t *d_point_status,
+                            const void *d_points, size_t row_stride_bytes, size_t point_stride_bytes, uint32_t rows_per_frame,
+                            uint32_t points_per_row, const uint32_t *d_row_counts, float max_dist_sq, int flags,
+                            uint32_t *d_slots, float *d_dist_sq, uint32_t *d_rows, uint32_t *d_n_rows, uint32_t *d_row_index,
+                            uint32_t *d_status);
+/* The host form without a detector handle (no device needed, like agx_find_board_tail): one list and its n_rows rows, the same
+ * arithmetic and semantics.  point_status NULL or a word per saddle (0 = listed); slots / dist_sq (may be NULL) [n_rows]
+ * [points_per_row]; rows [n_rows][points_per_row], row_index (may be NULL) [n_rows]; *n_rows_out the compacted count, *status
+ * AGX_SNAP_OK or AGX_SNAP_INPUT (then *n_rows_out = 0 and nothing else is written).  AGX_ERR_ARG as the batch call's; n_rows
+ * may be 0. */
+int agx_snap_points_tail(const agx_saddle *saddles, uint32_t n_saddles, const uint32_t *point_status,
+                         const void *points, size_t row_stride_bytes, size_t point_stride_bytes, uint32_t n_rows,
+                         uint32_t points_per_row, float max_dist_sq, int flags,
+                         uint32_t *slots, float *dist_sq, uint32_t *rows, uint32_t *n_rows_out, uint32_t *row_index,
+                         uint32_t *status);
+
 /* ---- blur and Hessian-response planes at any sigma ---------------------------------------- */
 
 /* image_util::gaussian_blur_f32(img, sigma) -- src/image_util.rs:110-206 -- and image_util::hessian_response(img) --
