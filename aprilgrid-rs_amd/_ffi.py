@@ -37,6 +37,10 @@ AGX_POINT_FILTERED = 4  # the k / phi filter (src/detector.rs:432-445) removed a
 # the rounds of max_num_of_boards (src/detector.rs:510-539): a saddle of a quad an earlier round decoded; a frame's tag table
 AGX_POINT_USED = 5
 AGX_TAGS_OK, AGX_TAGS_CAPACITY, AGX_TAGS_INPUT, AGX_TAGS_PENDING = 0, 1, 2, 3
+# the board's homography from a tag table (agx_board_fit_enqueue / _tail): flag, what became of a frame, what became of a row
+AGX_FIT_PREDICT_MISSING = 1
+AGX_FIT_OK, AGX_FIT_LOOSE, AGX_FIT_FEW, AGX_FIT_SINGULAR, AGX_FIT_INPUT = 0, 1, 2, 3, 4
+AGX_FIT_ROW_INLIER, AGX_FIT_ROW_OUTLIER, AGX_FIT_ROW_OFF_BOARD = 0, 1, 2
 AGX_DBG_BLUR, AGX_DBG_RESP, AGX_DBG_MIN, AGX_DBG_CENTERS, AGX_DBG_REFINED = 0, 1, 2, 3, 4
 AGX_N_KERNELS = 5
 
@@ -156,6 +160,11 @@ SYMBOLS = {
     "agx_filter_saddles_tail": (C.c_int, [C.POINTER(Params), _P, _P, C.c_uint32]),
     "agx_collect_tags_enqueue": (C.c_int, [_P, C.c_int, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P, C.c_int]),
     "agx_collect_tags_tail": (C.c_int, [C.c_int, C.c_uint32, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P]),
+    "agx_board_fit_enqueue": (C.c_int, [_P, C.c_int, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int, C.c_int,
+                                        C.c_float, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "agx_board_fit_tail": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int, C.c_int,
+                                     C.c_float, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_float), _P,
+                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "agx_group_create": (C.c_int, [C.c_int, C.POINTER(Params), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "agx_group_destroy": (None, [_P]),
     "agx_group_size": (C.c_int, [_P]),

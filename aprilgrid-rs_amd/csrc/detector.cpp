@@ -15,6 +15,8 @@
 #include <vector>
 
 #include "../../include/aprilgrid_amd.h"
+#include "board_fit.h"
+#include "board_fit_math.h"
 #include "chain_kernels.h"
 #include "decode_math.h"
 #include "decode_stages.h"
@@ -2258,6 +2260,82 @@ int agx_collect_tags_tail(int family, uint32_t n_quads, const uint32_t *quads, u
     if (!n_tags || !tag_status || !tags || !tag_cap) return AGX_ERR_ARG;
     if (board_status == AGX_BOARD_FOUND && n_quads && (!quads || !quad_tags || !quad_status)) return AGX_ERR_ARG;
     collect_tags(fam.n_codes, n_quads, quads, board_status, quad_tags, quad_status, n_slots, point_status, tag_cap, tags, n_tags, tag_status);  // src/detector.rs:510-539
+    return AGX_OK;
+    });
+}
+
+// ---- the board's homography from the tag table (board_fit.hip: k_board_fit; host_tail.cpp: board_fit) ---------------------------
+// what both forms refuse in their scalar arguments
+static bool board_fit_args_ok(uint32_t cols, uint32_t rows, float spacing_ratio, int img_w, int img_h, float max_err_sq, uint32_t min_tags,
+                              int flags)
+{
+    if (!cols || !rows || (uint64_t)cols * rows > FIT_MAX_BOARD) return false;
+    if (!std::isfinite(spacing_ratio) || !(spacing_ratio > -1.0f) || img_w <= 0 || img_h <= 0) return false;
+    return max_err_sq >= 0.0f && min_tags != 0 && !(flags & ~AGX_FIT_PREDICT_MISSING);  // (a NaN fails the comparison)
+}
+
+int agx_board_fit_enqueue(agx_detector *det, int n_frames, const agx_tag *d_tags, uint32_t tags_per_frame, const uint32_t *d_n_tags,
+                          const uint32_t *d_tag_status, uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, int img_w,
+                          int img_h, float max_err_sq, uint32_t max_drop, uint32_t min_tags, int flags, double *d_h, float *d_err_sq,
+                          uint32_t *d_row_status, uint32_t *d_n_inliers, float *d_rms, agx_tag *d_pred, uint32_t *d_n_pred, uint32_t *d_status)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    if (!d_tags || !d_n_tags || !d_h || !d_err_sq || !d_row_status || !d_n_inliers || !d_rms || !d_pred || !d_n_pred || !d_status || n_frames <= 0 ||
+        !tags_per_frame)
+        return fail(det, AGX_ERR_ARG, "a null array, n_frames <= 0 or tags_per_frame == 0");
+    if (!board_fit_args_ok(cols, rows, spacing_ratio, img_w, img_h, max_err_sq, min_tags, flags))
+        return fail(det, AGX_ERR_ARG, "rows * cols in 1 .. 4096, spacing_ratio finite and > -1, img_w and img_h > 0, max_err_sq >= 0, min_tags >= 1, flags AGX_FIT_PREDICT_MISSING or 0");
+    if ((((uintptr_t)d_tags | (uintptr_t)d_n_tags | (uintptr_t)d_tag_status | (uintptr_t)d_err_sq | (uintptr_t)d_row_status | (uintptr_t)d_n_inliers |
+          (uintptr_t)d_rms | (uintptr_t)d_pred | (uintptr_t)d_n_pred | (uintptr_t)d_status) & 3) || ((uintptr_t)d_h & 7))
+        return fail(det, AGX_ERR_ARG, "d_h must be 8-byte aligned, every other array 4-byte aligned");
+    if ((size_t)n_frames * tags_per_frame >= ((size_t)1 << 27)) return fail(det, AGX_ERR_ARG, "at most 2^27 - 1 tag rows per batch");
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // and there is nothing of this one to be fetched
+    BoardFitArgs b{};
+    b.n_frames = n_frames;
+    b.tags = d_tags;
+    b.tags_per_frame = tags_per_frame;
+    b.n_tags = d_n_tags;
+    b.tag_status = d_tag_status;
+    b.cols = cols;
+    b.rows = rows;
+    b.first_id = first_id;
+    b.spacing_ratio = spacing_ratio;
+    b.img_w = img_w;
+    b.img_h = img_h;
+    b.max_err_sq = max_err_sq;
+    b.max_drop = max_drop;
+    b.min_tags = min_tags;
+    b.flags = flags;
+    b.h = d_h;
+    b.err_sq = d_err_sq;
+    b.row_status = d_row_status;
+    b.n_inliers = d_n_inliers;
+    b.rms = d_rms;
+    b.pred = d_pred;
+    b.n_pred = d_n_pred;
+    b.status = d_status;
+    const hipError_t e = (hipError_t)launch_board_fit(b, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_board_fit: ") + hipGetErrorString(e));
+    return AGX_OK;
+    });
+}
+
+int agx_board_fit_tail(const agx_tag *tags, uint32_t tags_per_frame, uint32_t n_tags, uint32_t tag_status, uint32_t cols, uint32_t rows,
+                       uint32_t first_id, float spacing_ratio, int img_w, int img_h, float max_err_sq, uint32_t max_drop, uint32_t min_tags,
+                       int flags, double *h, float *err_sq, uint32_t *row_status, uint32_t *n_inliers, float *rms, agx_tag *pred,
+                       uint32_t *n_pred, uint32_t *status)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (!h || !n_inliers || !rms || !pred || !n_pred || !status || (n_tags && (!tags || !err_sq || !row_status))) return AGX_ERR_ARG;
+    if (!board_fit_args_ok(cols, rows, spacing_ratio, img_w, img_h, max_err_sq, min_tags, flags)) return AGX_ERR_ARG;
+    if ((((uintptr_t)tags | (uintptr_t)err_sq | (uintptr_t)row_status | (uintptr_t)n_inliers | (uintptr_t)rms | (uintptr_t)pred | (uintptr_t)n_pred |
+          (uintptr_t)status) & 3) || ((uintptr_t)h & 7))
+        return AGX_ERR_ARG;
+    if (tags_per_frame >= (1u << 27)) return AGX_ERR_ARG;
+    *status = board_fit(tags, tags_per_frame, n_tags, tag_status, cols, rows, first_id, spacing_ratio, img_w, img_h, max_err_sq, max_drop, min_tags,
+                        flags, h, err_sq, row_status, n_inliers, rms, pred, n_pred);
     return AGX_OK;
     });
 }

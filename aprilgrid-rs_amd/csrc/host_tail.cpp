@@ -5,6 +5,7 @@
 // the reference's operand order and this file is compiled with -ffp-contract=off.
 #include "host_tail.hpp"
 #include "decode_math.h"  // round_half_away, f32_as_u32, tag_affine: the decode kernels' own definitions
+#include "board_fit_math.h"  // the board fit's arithmetic and order of summation: k_board_fit's own definitions
 
 #ifdef AGX_TAIL_PROFILE
 #include <chrono>
@@ -1675,6 +1676,99 @@ uint32_t snap_points(const void *slots, size_t stride, uint32_t n_slots, const u
     }
     *n_rows_out = kept;
     return AGX_SNAP_OK;
+}
+
+uint32_t board_fit(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint32_t tag_status, uint32_t cols, uint32_t rows, uint32_t first_id,
+                   float spacing_ratio, int img_w, int img_h, float max_err_sq, uint32_t max_drop, uint32_t min_tags, int flags, double *h_out,
+                   float *err_sq, uint32_t *row_status, uint32_t *n_inliers, float *rms, agx_tag *pred, uint32_t *n_pred)
+{
+    const FitGeom g = fit_geom(cols, rows, first_id, spacing_ratio, img_w, img_h);
+    const auto refuse = [&](uint32_t status) {
+        *n_inliers = 0;
+        *n_pred = 0;
+        return status;
+    };
+    if (n_tags > tag_cap || n_tags > FIT_MAX_ROWS || tag_status != AGX_TAGS_OK) return refuse(AGX_FIT_INPUT);
+    std::vector<uint8_t> st(n_tags);
+    uint32_t n_inl = 0;
+    for (uint32_t r = 0; r < n_tags; ++r) {
+        st[r] = AGX_FIT_ROW_OFF_BOARD;
+        if (!fit_on_board(g, tags[r].id)) continue;
+        for (int j = 0; j < 8; ++j)
+            if (!f32_finite(tags[r].xy[j])) return refuse(AGX_FIT_INPUT);
+        st[r] = AGX_FIT_ROW_INLIER;
+        ++n_inl;
+    }
+    // the kernel's 64 lanes one after the other: lane l takes the rows l, l + 64, ...; the fold is p[l] + p[l ^ m] over m = 32 .. 1,
+    // of which lane 0's value needs p[l] += p[l + m] for l < m only
+    const auto fold = [](double (*p)[FIT_SUMS], int n) {
+        for (int m = 32; m >= 1; m >>= 1)
+            for (int l = 0; l < m; ++l)
+                for (int k = 0; k < n; ++k) p[l][k] = p[l][k] + p[l + m][k];
+    };
+    uint32_t status = AGX_FIT_OK, drops = 0;
+    double h[8] = {0}, sum_sq = 0.0;
+    std::unique_ptr<double[][FIT_SUMS]> lanes(new double[64][FIT_SUMS]);
+    for (;;) {
+        if (n_inl < min_tags) return refuse(AGX_FIT_FEW);
+        for (int l = 0; l < 64; ++l) {
+            for (int k = 0; k < FIT_SUMS; ++k) lanes[l][k] = 0.0;
+            for (uint32_t r = (uint32_t)l; r < n_tags; r += 64u)
+                if (st[r] == AGX_FIT_ROW_INLIER) fit_accumulate_row(g, lanes[l], tags[r].id, tags[r].xy);
+        }
+        fold(lanes.get(), FIT_SUMS);
+        double m[72];
+        fit_system(lanes[0], m);
+        if (!fit_solve(m, h)) return refuse(AGX_FIT_SINGULAR);
+        float worst = 0.0f;
+        uint32_t worst_row = 0xffffffffu;
+        for (int l = 0; l < 64; ++l) {
+            lanes[l][0] = 0.0;
+            for (uint32_t r = (uint32_t)l; r < n_tags; r += 64u) {
+                if (st[r] != AGX_FIT_ROW_INLIER) continue;
+                double sum;
+                const float e = fit_row_residual(g, h, tags[r].id, tags[r].xy, &sum);
+                lanes[l][0] += sum;
+                if (worst_row == 0xffffffffu || e > worst || (e == worst && r < worst_row)) {  // the lowest row at equal residual
+                    worst = e;
+                    worst_row = r;
+                }
+            }
+        }
+        if (worst > max_err_sq) {
+            if (drops < max_drop) {
+                st[worst_row] = AGX_FIT_ROW_OUTLIER;
+                ++drops;
+                --n_inl;
+                continue;
+            }
+            status = AGX_FIT_LOOSE;
+        }
+        fold(lanes.get(), 1);
+        sum_sq = lanes[0][0];
+        break;
+    }
+    for (uint32_t r = 0; r < n_tags; ++r) {
+        row_status[r] = st[r];
+        double sum;
+        if (st[r] != AGX_FIT_ROW_OFF_BOARD) err_sq[r] = fit_row_residual(g, h, tags[r].id, tags[r].xy, &sum);
+    }
+    fit_h_matrix(g, h, h_out);
+    *n_inliers = n_inl;
+    *rms = fit_rms(sum_sq, n_inl);
+    std::vector<bool> member(g.n_board, false);
+    if (flags & AGX_FIT_PREDICT_MISSING)
+        for (uint32_t r = 0; r < n_tags; ++r)
+            if (st[r] == AGX_FIT_ROW_INLIER) member[tags[r].id - first_id] = true;
+    uint32_t kept = 0;
+    for (uint32_t t = 0; t < g.n_board; ++t) {
+        if (member[t]) continue;
+        pred[kept].id = first_id + t;
+        fit_predict(g, h, t, pred[kept].xy);
+        ++kept;
+    }
+    *n_pred = kept;
+    return status;
 }
 
 }  // namespace agx

@@ -142,4 +142,12 @@ uint32_t snap_points(const void *slots, size_t stride, uint32_t n_slots, const u
                      size_t point_stride, uint32_t n_rows, uint32_t points_per_row, float max_dist_sq, int flags, uint32_t *out_slots,
                      float *dist_sq, uint32_t *rows, uint32_t *n_rows_out, uint32_t *row_index);
 
+// The board-to-image homography through one frame's tag table, its outlier rounds and the predicted corners of the layout's tags
+// (agx_board_fit_tail; k_board_fit is the device form, board_fit_math.h the arithmetic and the order of summation of both).
+// tags [n_tags] of a table of tag_cap rows whose status word is tag_status.  -> AGX_FIT_*; for AGX_FIT_FEW, _SINGULAR and _INPUT
+// only *n_inliers = *n_pred = 0 is written.  h [9], err_sq / row_status [n_tags], pred [rows * cols].
+uint32_t board_fit(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint32_t tag_status, uint32_t cols, uint32_t rows, uint32_t first_id,
+                   float spacing_ratio, int img_w, int img_h, float max_err_sq, uint32_t max_drop, uint32_t min_tags, int flags, double *h,
+                   float *err_sq, uint32_t *row_status, uint32_t *n_inliers, float *rms, agx_tag *pred, uint32_t *n_pred);
+
 }  // namespace agx

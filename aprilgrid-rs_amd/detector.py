@@ -1139,6 +1139,47 @@ class TagDetector:
             self._replaces_batch()
         self._check(rc)
 
+    # ---- the board's homography from the tag table (agx_board_fit_enqueue) -----------------------
+    @staticmethod
+    def board_fit(tags, cols, rows, img_size, **kw):
+        """The host form for one frame, no device needed: the module's board_fit."""
+        return board_fit(tags, cols, rows, img_size, **kw)
+
+    def board_fit_enqueue(self, tags, n_tags, cols, rows, img_size, h, err_sq, row_status, n_inliers, rms, pred, n_pred, status, first_id=0,
+                          spacing_ratio=0.3, max_err_sq=4.0, max_drop=0, min_tags=1, predict_missing=False, tag_status=None):
+        """Per frame the homography from the printed board to the image through every corner of the frame's tag table, its
+        outlier rounds and the predicted corners of the layout's tags (board_fit, the host form, says what is computed), in
+        device tensors and stream-ordered behind torch's current stream; nothing to fetch.  tags int32 [N, T, 9], n_tags and
+        tag_status (optional) int32 [N]: the tables of collect_tags_enqueue / detect_batch_enqueue(out=...), read in place.
+        h float64 [N, 9]; err_sq float32 and row_status int32 [N, T]; n_inliers int32, rms float32, n_pred, status int32 [N];
+        pred int32 [N, rows*cols, 9]: tag rows as snap_points_enqueue reads them in place (row_counts = n_pred)."""
+        import torch
+        if not (getattr(tags, "is_cuda", False) and tags.dtype == torch.int32 and tags.is_contiguous() and tags.dim() == 3 and tags.shape[2] == 9
+                and tags.shape[1] > 0):
+            raise AgxError(_ffi.AGX_ERR_ARG, "tags must be a contiguous int32 device tensor [N, T, 9]")
+        n, tpf, dev = int(tags.shape[0]), int(tags.shape[1]), tags.device
+        n_board = int(cols) * int(rows)
+
+        def tensor(t, dtype, shape, what, optional=False):
+            if t is None and optional:
+                return None
+            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == shape and t.device == dev):
+                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s tensor %s on the tags' device" % (what, dtype, shape))
+            return t.data_ptr()
+
+        ins = (tensor(n_tags, torch.int32, (n,), "n_tags"), tensor(tag_status, torch.int32, (n,), "tag_status", optional=True))
+        outs = (tensor(h, torch.float64, (n, 9), "h"), tensor(err_sq, torch.float32, (n, tpf), "err_sq"),
+                tensor(row_status, torch.int32, (n, tpf), "row_status"), tensor(n_inliers, torch.int32, (n,), "n_inliers"),
+                tensor(rms, torch.float32, (n,), "rms"), tensor(pred, torch.int32, (n, n_board, 9), "pred"),
+                tensor(n_pred, torch.int32, (n,), "n_pred"), tensor(status, torch.int32, (n,), "status"))
+        self._follow_torch_stream(tags)
+        rc = self._lib.agx_board_fit_enqueue(self._h, n, tags.data_ptr(), tpf, *ins, int(cols), int(rows), int(first_id), float(spacing_ratio),
+                                             int(img_size[0]), int(img_size[1]), float(max_err_sq), int(max_drop), int(min_tags),
+                                             _ffi.AGX_FIT_PREDICT_MISSING if predict_missing else 0, *outs)
+        if rc == _ffi.AGX_OK:  # (a refused argument leaves the batch in flight where it is)
+            self._replaces_batch()
+        self._check(rc)
+
     def find_boards_staged(self, saddles, spacing_ratio=0.3, counts=None, point_status=None, quads_per_frame=128, candidates_per_frame=1024,
                            n_nearest=50):
         """try_find_best_board (src/detector.rs:588-639) as its stages on device tensors, at ANY spacing_ratio: the reference's seeds
@@ -1416,6 +1457,14 @@ class TagDetector:
         tags_per_frame: rows of a frame's tag table (None: one per code of the family, which always holds).
         -> one {tag_id: 4x2 corners} per frame in row order, as detect_batch.  A frame whose clusters or tags could not be held
         raises AgxError naming the frame and its status."""
+        _lists, cstatus, tags, ntags, tst = self._staged_tables(frames, clusters_per_frame, quads_per_frame, tags_per_frame, format, decode_model)
+        self.sync()
+        return self._staged_result("detect_staged", cstatus, int(clusters_per_frame), tags, ntags, tst)
+
+    def _staged_tables(self, frames, clusters_per_frame, quads_per_frame, tags_per_frame, format, decode_model, keep_listed=False):
+        """detect_staged's chain and rounds, enqueued -> ((records, counts, listed point status), cluster status, tags, n_tags,
+        tag_status): device tensors, complete in stream order.  keep_listed: the point status words as the k / phi filter left
+        them, before any round marked a saddle used (a copy; else None)."""
         import torch
         fmt, bpp = self._tensor_format(frames, format)
         n, w, h, _, _ = self._tensor_geometry(frames, fmt, bpp)
@@ -1429,6 +1478,7 @@ class TagDetector:
         dev = frames.device
         i32 = dict(dtype=torch.int32, device=dev)
         records, counts, pstatus, cstatus = self._staged_saddles(frames, n, w, h, cpf, format)
+        listed = pstatus.clone() if keep_listed else None
         quads, qpts = torch.zeros((n, qpf, 4), **i32), torch.zeros((n, qpf, 4, 2), dtype=torch.float32, device=dev)
         nq, bst = torch.zeros(n, **i32), torch.zeros(n, **i32)
         qtags, qst = torch.zeros((n, qpf, 9), **i32), torch.zeros((n, qpf), **i32)
@@ -1451,8 +1501,85 @@ class TagDetector:
                 self.best_tag_enqueue(sbits, sids, srots, qst, counts=nq, status_in=qst, quads=qpts, tags=qtags)
             self.collect_tags_enqueue(quads, nq, bst, qtags, qst, pstatus if r + 1 < rounds else None, tags, ntags, tst, reset=r == 0,
                                       saddles_per_frame=cpf)
+        return (records, counts, listed), cstatus, tags, ntags, tst
+
+    def recover_tags_enqueue(self, frames, saddles, counts, point_status, tags, n_tags, tag_status, cols, rows, first_id=0, spacing_ratio=0.3,
+                             max_dist=3.0, max_err=2.0, max_drop=4, min_tags=2, format=None):
+        """The tags of a printed board that a frame's table lacks, recovered in place on device tensors, stream-ordered behind
+        torch's current stream, with no host step: board_fit_enqueue over the tables with only the missing tags predicted (the
+        layout cols x rows from first_id at spacing_ratio; a row more than max_err px off goes, at most max_drop of them) ->
+        snap_points_enqueue on the predicted rows in place, back to front, within max_dist px of a listed saddle -> the snapped
+        slots' (x, y) gathered from the records -> decode_quads_enqueue -> a quad counts only if it decoded TO THE ID PREDICTED
+        FOR IT (every other one gets AGX_QUAD_NO_MATCH) -> collect_tags_enqueue into the frame's table.  frames and format= as
+        decode_quads_enqueue; saddles float32 [N, S, 5], counts int32 [N] and point_status int32 [N, S] (or None) as
+        find_boards_enqueue reads them; tags int32 [N, T, 9], n_tags and tag_status int32 [N]: the tables, in and out.  A frame
+        whose fit is not AGX_FIT_OK or AGX_FIT_LOOSE predicts nothing and keeps its table; a recovered id that an outlier row
+        already holds takes that row (collect's rule), and the fit returned says which rows those were.
+        -> the fit's device tensors: dict(h, err_sq, row_status, n_inliers, rms, pred, n_pred, status) of board_fit_enqueue, and
+        recovered int32 [N], the quads accepted per frame."""
+        import torch
+        if not (getattr(saddles, "is_cuda", False) and saddles.dim() == 3 and saddles.shape[2] >= 2):
+            raise AgxError(_ffi.AGX_ERR_ARG, "saddles must be a device tensor [N, S, K >= 5]")
+        fmt, bpp = self._tensor_format(frames, format)
+        n, w, h, _, _ = self._tensor_geometry(frames, fmt, bpp)
+        n, w, h, spf, tpf, nb = int(n), int(w), int(h), int(saddles.shape[1]), int(tags.shape[1]), int(cols) * int(rows)
+        dev = frames.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        fit = dict(h=torch.zeros((n, 9), dtype=torch.float64, device=dev), err_sq=torch.zeros((n, tpf), **f32),
+                   row_status=torch.zeros((n, tpf), **i32), n_inliers=torch.zeros(n, **i32), rms=torch.zeros(n, **f32),
+                   pred=torch.zeros((n, max(nb, 1), 9), **i32), n_pred=torch.zeros(n, **i32), status=torch.zeros(n, **i32))
+        self.board_fit_enqueue(tags, n_tags, cols, rows, (w, h), first_id=first_id, spacing_ratio=spacing_ratio,
+                               max_err_sq=float(max_err) * float(max_err), max_drop=max_drop, min_tags=min_tags, predict_missing=True,
+                               tag_status=tag_status, **fit)
+        slots, quads = torch.zeros((n, nb, 4), **i32), torch.zeros((n, nb, 4), **i32)
+        nq, sst, index = torch.zeros(n, **i32), torch.zeros(n, **i32), torch.zeros((n, nb), **i32)
+        self.snap_points_enqueue(saddles, fit["pred"], slots, quads, nq, sst, float(max_dist) * float(max_dist), counts=counts,
+                                 point_status=point_status, row_counts=fit["n_pred"], reverse=True, row_index=index)
+        at = quads.long().clamp_(0, spf - 1).view(n, nb * 4, 1).expand(-1, -1, 2)  # (rows beyond a frame's count hold zeros)
+        qpts = torch.gather(saddles[:, :, :2], 1, at).view(n, nb, 4, 2).contiguous()
+        qtags, qst = torch.zeros((n, nb, 9), **i32), torch.zeros((n, nb), **i32)
+        self.decode_quads_enqueue(frames, qpts, counts=nq, out=qtags, status=qst, format=format)
+        want = torch.gather(fit["pred"][:, :, 0], 1, index.long().clamp_(0, nb - 1))
+        below = torch.arange(nb, device=dev)[None, :] < nq[:, None]
+        ok = below & (qst == _ffi.AGX_QUAD_DECODED) & (qtags[:, :, 0] == want)
+        qst = torch.where(ok, qst, torch.full_like(qst, _ffi.AGX_QUAD_NO_MATCH))
+        found = torch.full((n,), _ffi.AGX_BOARD_FOUND, **i32)
+        self.collect_tags_enqueue(quads, nq, found, qtags, qst, None, tags, n_tags, tag_status, reset=False, saddles_per_frame=spf)
+        fit["recovered"] = ok.sum(dim=1).to(torch.int32)
+        return fit
+
+    def detect_recovered(self, frames, cols, rows, first_id=0, spacing_ratio=0.3, max_dist=3.0, max_err=2.0, max_drop=4, min_tags=2,
+                         clusters_per_frame=4096, quads_per_frame=128, tags_per_frame=None, format=None, return_fit=False):
+        """detect (src/detector.rs:505-540) of frames that show ONE printed board whose layout is known (Kalibr's AprilGrid:
+        cols x rows tags from first_id, spacing_ratio), with the tags the board search dropped recovered: detect_staged's chain
+        and rounds, then recover_tags_enqueue on its arrays as they stand -- fit, predict the missing tags, snap, decode, accept
+        what decoded to the predicted id, collect.  Frames whose fit is neither AGX_FIT_OK nor AGX_FIT_LOOSE keep
+        detect_staged's result.  Outlier rows are reported, never removed.
+        -> one {tag_id: 4x2 corners} per frame in row order (detect_staged's rows first, bit for bit); with return_fit also a
+        list of dict(status, H, rms, n_inliers, row_status, err_sq, recovered) per frame, row_status / err_sq over detect_staged's
+        rows (AGX_FIT_ROW_*); H, rms, row_status and err_sq are None where the fit was refused."""
+        (records, counts, listed), cstatus, tags, ntags, tst = self._staged_tables(frames, clusters_per_frame, quads_per_frame, tags_per_frame,
+                                                                                   format, "affine", keep_listed=True)
+        before = ntags.clone()
+        fit = self.recover_tags_enqueue(frames, records, counts, listed, tags, ntags, tst, cols, rows, first_id=first_id,
+                                        spacing_ratio=spacing_ratio, max_dist=max_dist, max_err=max_err, max_drop=max_drop, min_tags=min_tags,
+                                        format=format)
         self.sync()
-        return self._staged_result("detect_staged", cstatus, cpf, tags, ntags, tst)
+        out = self._staged_result("detect_recovered", cstatus, int(clusters_per_frame), tags, ntags, tst)
+        if not return_fit:
+            return out
+        host = {k: v.cpu().numpy() for k, v in fit.items() if k != "pred"}
+        before = before.cpu().numpy()
+        fits = []
+        for f in range(len(out)):
+            st, k = int(host["status"][f]), int(before[f])
+            good = st in (_ffi.AGX_FIT_OK, _ffi.AGX_FIT_LOOSE)
+            fits.append({"status": st, "n_inliers": int(host["n_inliers"][f]), "recovered": int(host["recovered"][f]),
+                         "H": host["h"][f].reshape(3, 3).copy() if good else None, "rms": float(host["rms"][f]) if good else None,
+                         "row_status": host["row_status"][f, :k].view(np.uint32).copy() if good else None,
+                         "err_sq": host["err_sq"][f, :k].copy() if good else None})
+        return out, fits
 
     def _staged_saddles(self, frames, n, w, h, cpf, format):
         """The staged chain up to the saddle lists: planes at the handle's sigma, clusters, refine on the blur plane at the
@@ -1856,6 +1983,50 @@ def snap_points(saddles, points, max_dist_sq, reverse=False, point_status=None):
     if st != _ffi.AGX_OK:
         raise AgxError(st)
     return slots[:n_rows], dist[:n_rows], rows[:kept.value].copy(), index[:kept.value].copy(), status.value
+
+
+def _tag_rows(tags):
+    """{tag_id: 4x2 corners} (rows in the dict's order) or rows of TagDetector.TAG_DTYPE -> contiguous rows of TAG_DTYPE"""
+    if isinstance(tags, dict):
+        rows = np.zeros(len(tags), TagDetector.TAG_DTYPE)
+        for r, (tag_id, xy) in enumerate(tags.items()):
+            rows[r]["id"] = int(tag_id)
+            rows[r]["xy"] = np.asarray(xy, np.float32).reshape(8)
+        return rows
+    rows = np.ascontiguousarray(tags)
+    if rows.dtype != TagDetector.TAG_DTYPE:
+        raise AgxError(_ffi.AGX_ERR_ARG, "tags must be {tag_id: 4x2 corners} or rows of TAG_DTYPE")
+    return rows.reshape(-1)
+
+
+def board_fit(tags, cols, rows, img_size, first_id=0, spacing_ratio=0.3, max_err_sq=4.0, max_drop=0, min_tags=1, predict_missing=False,
+              tag_status=0, tags_per_frame=None):
+    """The host form of board_fit_enqueue for one frame (agx_board_fit_tail) without a device: the homography from the printed
+    board (Kalibr's AprilGrid layout: tag first_id + r*cols + c at column c, row r; corner j at (c*(1+s) + (0,1,1,0)[j],
+    r*(1+s) + (0,0,1,1)[j]) in tag sides) to the image through every corner of `tags` -- {tag_id: 4x2 corners} or rows of
+    TagDetector.TAG_DTYPE -- with rounds that drop the row of the largest residual while that is above max_err_sq (px^2) and
+    fewer than max_drop rows went, and the predicted corners of the layout's tags (predict_missing: only of those that are not
+    inlier rows).  img_size (w, h) only centres and scales the image coordinates.
+    -> dict: status AGX_FIT_*; for AGX_FIT_OK and AGX_FIT_LOOSE also H [3, 3] float64 (board units -> pixels), err_sq float32 and
+    row_status uint32 per row (AGX_FIT_ROW_*; err_sq is NaN for an off-board row), n_inliers, rms, pred (rows of TAG_DTYPE)."""
+    t = _tag_rows(tags)
+    n = int(t.shape[0])
+    cap = n if tags_per_frame is None else int(tags_per_frame)
+    n_board = max(int(cols) * int(rows), 1) if 0 < int(cols) * int(rows) <= 4096 else 1
+    h = np.zeros(9, np.float64)
+    err, rst = np.full(max(n, 1), np.nan, np.float32), np.zeros(max(n, 1), np.uint32)
+    pred = np.zeros(n_board, TagDetector.TAG_DTYPE)
+    n_inl, n_pred, status, rms = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_float(0)
+    st = _ffi.lib().agx_board_fit_tail(t.ctypes.data if n else None, cap, n, int(tag_status), int(cols), int(rows), int(first_id),
+                                       float(spacing_ratio), int(img_size[0]), int(img_size[1]), float(max_err_sq), int(max_drop), int(min_tags),
+                                       _ffi.AGX_FIT_PREDICT_MISSING if predict_missing else 0, h.ctypes.data, err.ctypes.data, rst.ctypes.data,
+                                       C.byref(n_inl), C.byref(rms), pred.ctypes.data, C.byref(n_pred), C.byref(status))
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    out = {"status": status.value, "n_inliers": n_inl.value, "n_pred": n_pred.value}
+    if status.value in (_ffi.AGX_FIT_OK, _ffi.AGX_FIT_LOOSE):
+        out.update(H=h.reshape(3, 3), err_sq=err[:n], row_status=rst[:n], rms=rms.value, pred=pred[:n_pred.value].copy())
+    return out
 
 
 def _find_board_call(call, saddles, cap, keep=None):

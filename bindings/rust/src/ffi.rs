@@ -155,6 +155,16 @@ pub const AGX_TAGS_OK: c_int = 0;
 pub const AGX_TAGS_CAPACITY: c_int = 1;
 pub const AGX_TAGS_INPUT: c_int = 2;
 pub const AGX_TAGS_PENDING: c_int = 3;
+// agx_board_fit_enqueue / agx_board_fit_tail: flag, what became of a frame, what became of a row
+pub const AGX_FIT_PREDICT_MISSING: c_int = 1;
+pub const AGX_FIT_OK: c_int = 0;
+pub const AGX_FIT_LOOSE: c_int = 1;
+pub const AGX_FIT_FEW: c_int = 2;
+pub const AGX_FIT_SINGULAR: c_int = 3;
+pub const AGX_FIT_INPUT: c_int = 4;
+pub const AGX_FIT_ROW_INLIER: c_int = 0;
+pub const AGX_FIT_ROW_OUTLIER: c_int = 1;
+pub const AGX_FIT_ROW_OFF_BOARD: c_int = 2;
 // agx_debug_fetch items
 pub const AGX_DBG_BLUR: c_int = 0;
 pub const AGX_DBG_RESP: c_int = 1;
@@ -347,6 +357,16 @@ extern "C" {
     pub fn agx_collect_tags_tail(family: c_int, n_quads: u32, quads: *const u32, board_status: u32, quad_tags: *const agx_tag,
                                  quad_status: *const u32, n_slots: u32, point_status: *mut u32, tag_cap: u32, tags: *mut agx_tag,
                                  n_tags: *mut u32, tag_status: *mut u32) -> c_int;
+
+    pub fn agx_board_fit_enqueue(det: *mut agx_detector, n_frames: c_int, d_tags: *const agx_tag, tags_per_frame: u32, d_n_tags: *const u32,
+                                 d_tag_status: *const u32, cols: u32, rows: u32, first_id: u32, spacing_ratio: c_float, img_w: c_int,
+                                 img_h: c_int, max_err_sq: c_float, max_drop: u32, min_tags: u32, flags: c_int, d_h: *mut c_double,
+                                 d_err_sq: *mut c_float, d_row_status: *mut u32, d_n_inliers: *mut u32, d_rms: *mut c_float,
+                                 d_pred: *mut agx_tag, d_n_pred: *mut u32, d_status: *mut u32) -> c_int;
+    pub fn agx_board_fit_tail(tags: *const agx_tag, tags_per_frame: u32, n_tags: u32, tag_status: u32, cols: u32, rows: u32, first_id: u32,
+                              spacing_ratio: c_float, img_w: c_int, img_h: c_int, max_err_sq: c_float, max_drop: u32, min_tags: u32,
+                              flags: c_int, h: *mut c_double, err_sq: *mut c_float, row_status: *mut u32, n_inliers: *mut u32,
+                              rms: *mut c_float, pred: *mut agx_tag, n_pred: *mut u32, status: *mut u32) -> c_int;
     pub fn agx_debug_blur_weights(sigma: c_float, weights: *mut c_float, cap: c_int, radius: *mut c_int) -> c_int;
     pub fn agx_debug_refine_constants(half_size_patch: c_int, cone: *mut c_float, pmat: *mut c_float, cap_points: c_int,
                                       n_points: *mut c_int) -> c_int;

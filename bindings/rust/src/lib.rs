@@ -728,6 +728,72 @@ pub fn collect_tags_tail(tag_family: &TagFamily, quads: &[[u32; 4]], board_statu
     status
 }
 
+/// The layout of a printed board, Kalibr's AprilGrid: tag `first_id + r * cols + c` sits at column `c`, row `r`; corner `j` of
+/// its corners is the board point `(c (1 + s) + (0,1,1,0)[j], r (1 + s) + (0,0,1,1)[j])` in units of the tag side,
+/// `s = spacing_ratio`.
+#[derive(Clone, Copy, Debug)]
+pub struct BoardLayout {
+    pub cols: u32,
+    pub rows: u32,
+    pub first_id: u32,
+    pub spacing_ratio: f32,
+}
+
+/// What `board_fit_tail` found for one frame.
+#[derive(Clone, Debug)]
+pub struct BoardFit {
+    /// `AGX_FIT_OK` or `AGX_FIT_LOOSE`
+    pub status: u32,
+    /// row major, board units -> pixels, w = 1 at the board's centre
+    pub h: [f64; 9],
+    /// per row of the table: `AGX_FIT_ROW_*` and the squared residual in pixels (not written for an off-board row: NaN)
+    pub rows: Vec<(u32, f32)>,
+    pub n_inliers: usize,
+    pub rms: f32,
+    /// predicted tags in id order: all of the layout, or under `predict_missing` those that are not inlier rows
+    pub pred: Vec<(u32, [(f32, f32); 4])>,
+}
+
+/// The homography from the printed board to the image through every corner of a frame's tag table (what `detect` returns), with
+/// rounds that drop the row of the largest residual while that is above `max_err_sq` (px^2) and fewer than `max_drop` rows went,
+/// and the predicted corners of the layout's tags.  The host form (no device is used); the reference has no such function (its
+/// README's open item "Robustness").  `Err(status)`: `AGX_FIT_FEW`, `AGX_FIT_SINGULAR` or `AGX_FIT_INPUT`.  Panics where the
+/// library refuses the arguments.
+pub fn board_fit_tail(tags: &[(u32, [(f32, f32); 4])], layout: &BoardLayout, img_w: u32, img_h: u32, max_err_sq: f32, max_drop: u32,
+                      min_tags: u32, predict_missing: bool) -> Result<BoardFit, u32> {
+    let table: Vec<ffi::agx_tag> = tags.iter().map(|t| ffi::agx_tag {
+        id: t.0,
+        xy: [t.1[0].0, t.1[0].1, t.1[1].0, t.1[1].1, t.1[2].0, t.1[2].1, t.1[3].0, t.1[3].1],
+    }).collect();
+    // (the library refuses such a layout; checked here before the prediction rows are allocated from it)
+    assert!(layout.cols > 0 && layout.rows > 0 && layout.cols as u64 * layout.rows as u64 <= 4096, "board_fit_tail: rows * cols in 1..=4096");
+    let n_board = layout.cols as usize * layout.rows as usize;
+    let mut h = [0f64; 9];
+    let mut err = vec![f32::NAN; tags.len().max(1)];
+    let mut row_status = vec![0u32; tags.len().max(1)];
+    let mut pred = vec![ffi::agx_tag { id: 0, xy: [0.0; 8] }; n_board];
+    let (mut n_inliers, mut n_pred, mut status, mut rms) = (0u32, 0u32, 0u32, 0f32);
+    let st = unsafe {
+        ffi::agx_board_fit_tail(table.as_ptr(), table.len() as u32, table.len() as u32, ffi::AGX_TAGS_OK as u32, layout.cols, layout.rows,
+                                layout.first_id, layout.spacing_ratio, img_w as c_int, img_h as c_int, max_err_sq, max_drop, min_tags,
+                                if predict_missing { ffi::AGX_FIT_PREDICT_MISSING } else { 0 }, h.as_mut_ptr(), err.as_mut_ptr(),
+                                row_status.as_mut_ptr(), &mut n_inliers, &mut rms, pred.as_mut_ptr(), &mut n_pred, &mut status)
+    };
+    assert_eq!(st, ffi::AGX_OK, "agx_board_fit_tail failed: {}", st);
+    if status as c_int != ffi::AGX_FIT_OK && status as c_int != ffi::AGX_FIT_LOOSE {
+        return Err(status);
+    }
+    Ok(BoardFit {
+        status,
+        h,
+        rows: (0..tags.len()).map(|r| (row_status[r], err[r])).collect(),
+        n_inliers: n_inliers as usize,
+        rms,
+        pred: pred[..n_pred as usize].iter()
+            .map(|r| (r.id, [(r.xy[0], r.xy[1]), (r.xy[2], r.xy[3]), (r.xy[4], r.xy[5]), (r.xy[6], r.xy[7])])).collect(),
+    })
+}
+
 fn last_error(det: *const ffi::agx_detector) -> String {
     unsafe {
         let p = ffi::agx_last_error(det);

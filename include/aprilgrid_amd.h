@@ -1050,6 +1050,67 @@ int agx_collect_tags_tail(int family, uint32_t n_quads, const uint32_t *quads, u
                           const agx_tag *quad_tags, const uint32_t *quad_status, uint32_t n_slots, uint32_t *point_status,
                           uint32_t tag_cap, agx_tag *tags, uint32_t *n_tags, uint32_t *tag_status);
 
+/* ---- the board's homography from the tag table: fit, outliers, predicted corners ------------ */
+
+/* What a calibration pipeline does with a frame's tag table {id, 4 corners} next (the reference stops at the table; its README's
+ * open item "Robustness"): relate the ids to the printed board, fit the board-to-image homography through all 4 n
+ * correspondences, take the RMS reprojection error as the frame's quality, throw out tags that disagree with the board (best_tag
+ * accepts a Hamming distance, so a wrong id is a real event), and predict the corners of the board's OTHER tags -- the ones the
+ * search missed in this frame, and all of them in the next.  The layout is Kalibr's AprilGrid: tag first_id + r*cols + c sits at
+ * column c, row r; corner j of its xy is the board point (c*(1+s) + ox[j], r*(1+s) + oy[j]) with (ox, oy)[j] = (0,0), (1,0),
+ * (1,1), (0,1), in units of the tag side, s = spacing_ratio, y along increasing row.
+ * Per frame over tag tables in DEVICE memory, stream-ordered on the detector's stream (the caller's after
+ * agx_detector_set_stream), caller-owned device arrays only; returns without waiting, nothing is handed back and there is nothing
+ * to fetch.  d_tags [n_frames][tags_per_frame], d_n_tags and d_tag_status (may be NULL) [n_frames]: the tables of
+ * agx_collect_tags_enqueue and agx_detect_batch_enqueue_to, read in place.  Predicted corners are agx_tag rows:
+ * agx_snap_points_enqueue reads them in place (&d_pred[0].xy, row stride sizeof(agx_tag), point stride 8, d_row_counts = d_n_pred;
+ * a NaN point never snaps).
+ * Arithmetic (csrc/board_fit_math.h states it once for both forms): binary64, + - * / only, no contraction.  Board and image
+ * coordinates are centred and scaled into [-1, 1] (board: by its extent cols*(1+s) - s by rows*(1+s) - s; image: by img_w,
+ * img_h), the 8 unknowns (h33 = 1 at the board's centre) solve the normal equations, whose 44 sums are added in a fixed order --
+ * 64 lanes over the rows in table order, folded by the tree l ^ 32, 16, 8, 4, 2, 1; no floating-point atomics -- by Gaussian
+ * elimination with partial pivoting.  Rounds: fit on the inlier rows; the worst inlier row is the one with the largest residual
+ * (the largest of its four corners' squared distances in pixels, stored as binary32), the lowest row at equal residual; if that
+ * is above max_err_sq and fewer than max_drop rows have been dropped, the row becomes AGX_FIT_ROW_OUTLIER and the fit is
+ * repeated from fresh sums; otherwise the rounds end.
+ * Results, frame f, all required, caller-owned device memory:
+ *   d_h [n_frames][9]  H, row major, board units -> pixels, w = 1 at the board's centre;
+ *   d_row_status, d_err_sq [n_frames][tags_per_frame], rows below the frame's count: AGX_FIT_ROW_INLIER, AGX_FIT_ROW_OUTLIER
+ *     (dropped) or AGX_FIT_ROW_OFF_BOARD (id outside [first_id, first_id + rows*cols): never in the fit, its residual is not
+ *     written); the residual under the final fit (+inf where a corner's w is not > 0);
+ *   d_n_inliers[f], d_rms[f]: the inlier rows and the root mean square over their 4 n_inliers correspondences;
+ *   d_pred [n_frames][rows*cols] with d_n_pred[f]: {id, xy} of every tag of the layout in id order, rounded to binary32, a point
+ *     whose w is not > 0 as (NaN, NaN); under AGX_FIT_PREDICT_MISSING only the tags that are not inlier rows, compacted;
+ *   d_status[f]: AGX_FIT_OK; AGX_FIT_LOOSE (everything written, but after max_drop drops the worst inlier is still above
+ *     max_err_sq); or, decided before the frame's first store, with d_n_pred[f] = d_n_inliers[f] = 0 and nothing else written:
+ *     AGX_FIT_FEW (fewer than min_tags inlier rows at some round), AGX_FIT_SINGULAR (a pivot that is zero, not finite or not
+ *     above 2^-40 of the largest diagonal sum, or a solution that is not finite), AGX_FIT_INPUT (a count above tags_per_frame or
+ *     above 640 -- no family has that many codes --, a d_tag_status word that is not AGX_TAGS_OK, a non-finite corner in an
+ *     on-board row).
+ * Only entries below the counts are ever written.  No table is changed: outliers are reported, never removed.
+ * Like agx_snap_points_enqueue the call replaces the batch in flight without waiting; every kind's fetch is AGX_ERR_STATE then.
+ * AGX_ERR_ARG (a batch in flight stays where it is): a NULL array other than d_tag_status; n_frames <= 0; tags_per_frame == 0;
+ * cols or rows == 0 or rows*cols > 4096; spacing_ratio not finite or <= -1; img_w or img_h <= 0; a negative or NaN max_err_sq;
+ * min_tags == 0; an unknown flag; a misaligned pointer (d_h: 8 bytes, the rest 4); 2^27 or more rows in the batch. */
+enum { AGX_FIT_PREDICT_MISSING = 1 }; /* flags */
+enum { AGX_FIT_OK = 0, AGX_FIT_LOOSE = 1, AGX_FIT_FEW = 2, AGX_FIT_SINGULAR = 3, AGX_FIT_INPUT = 4 }; /* per frame */
+enum { AGX_FIT_ROW_INLIER = 0, AGX_FIT_ROW_OUTLIER = 1, AGX_FIT_ROW_OFF_BOARD = 2 };                 /* per row */
+int agx_board_fit_enqueue(agx_detector *det, int n_frames,
+                          const agx_tag *d_tags, uint32_t tags_per_frame, const uint32_t *d_n_tags, const uint32_t *d_tag_status,
+                          uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, int img_w, int img_h,
+                          float max_err_sq, uint32_t max_drop, uint32_t min_tags, int flags,
+                          double *d_h, float *d_err_sq, uint32_t *d_row_status, uint32_t *d_n_inliers, float *d_rms,
+                          agx_tag *d_pred, uint32_t *d_n_pred, uint32_t *d_status);
+/* The host form without a detector handle (no device needed, like agx_collect_tags_tail): ONE frame in host memory, the same
+ * arithmetic, order of summation and bytes.  tags: a table of tags_per_frame rows of which n_tags are filled, tag_status its
+ * status word; h [9], err_sq / row_status [n_tags], pred [rows*cols]; *status AGX_FIT_*.  AGX_ERR_ARG as the batch call's (tags,
+ * err_sq and row_status may be NULL with n_tags == 0; tags_per_frame may be 0). */
+int agx_board_fit_tail(const agx_tag *tags, uint32_t tags_per_frame, uint32_t n_tags, uint32_t tag_status,
+                       uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, int img_w, int img_h,
+                       float max_err_sq, uint32_t max_drop, uint32_t min_tags, int flags,
+                       double *h, float *err_sq, uint32_t *row_status, uint32_t *n_inliers, float *rms,
+                       agx_tag *pred, uint32_t *n_pred, uint32_t *status);
+
 /* ---- detector groups: several GPUs of one node driven from ONE process ----------------- */
 
 /* The reference's detect(&self) is stateless, so a batch shards by frame:
