@@ -165,6 +165,15 @@ SYMBOLS = {
     "agx_board_fit_tail": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int, C.c_int,
                                      C.c_float, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_float), _P,
                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "agx_board_pose_enqueue": (C.c_int, [_P, C.c_int, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_double,
+                                         C.POINTER(C.c_double), C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, _P, _P, _P,
+                                         _P, _P, _P]),
+    "agx_board_pose_tail": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_double,
+                                      C.POINTER(C.c_double), C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P,
+                                      C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_uint32), _P, C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_uint32)]),
+    "agx_debug_board_pose_sums": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_double,
+                                            C.POINTER(C.c_double), C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), _P]),
     "agx_group_create": (C.c_int, [C.c_int, C.POINTER(Params), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "agx_group_destroy": (None, [_P]),
     "agx_group_size": (C.c_int, [_P]),

@@ -109,21 +109,24 @@ AGX_HD void fit_system(const double acc[FIT_SUMS], double *m)
     for (int i = 0; i < 8; ++i) m[9 * i + 8] = acc[36 + i];
 }
 
-// m [8][9] -> h [8]; m is destroyed.  false: AGX_FIT_SINGULAR.  (m is indexed at run time: the kernel keeps it in LDS)
-AGX_HD bool fit_solve(double *m, double *h)
+// m [N][N + 1] -> h [N]; m is destroyed.  false: AGX_FIT_SINGULAR.  (m is indexed at run time: the kernels keep it in LDS)
+// One statement of the elimination for the 8 x 9 system here and the 6 x 7 system of board_pose_math.h.
+template <int N>
+AGX_HD bool fit_solve_n(double *m, double *h)
 {
+    constexpr int W = N + 1;
     double scale = 0.0;
-    for (int i = 0; i < 8; ++i) {
-        const double d = __builtin_fabs(m[9 * i + i]);
+    for (int i = 0; i < N; ++i) {
+        const double d = __builtin_fabs(m[W * i + i]);
         if (!f64_finite(d)) return false;
         if (d > scale) scale = d;
     }
     const double tiny = scale * (1.0 / 1099511627776.0);  // 2^-40
-    for (int c = 0; c < 8; ++c) {
+    for (int c = 0; c < N; ++c) {
         int p = c;
-        double best = __builtin_fabs(m[9 * c + c]);
-        for (int r = c + 1; r < 8; ++r) {
-            const double a = __builtin_fabs(m[9 * r + c]);
+        double best = __builtin_fabs(m[W * c + c]);
+        for (int r = c + 1; r < N; ++r) {
+            const double a = __builtin_fabs(m[W * r + c]);
             if (a > best) {  // (strictly: the lowest row stays at equal magnitude; a NaN never wins and fails below)
                 best = a;
                 p = r;
@@ -131,25 +134,28 @@ AGX_HD bool fit_solve(double *m, double *h)
         }
         if (!f64_finite(best) || !(best > tiny)) return false;
         if (p != c)
-            for (int j = c; j < 9; ++j) {
-                const double t = m[9 * c + j];
-                m[9 * c + j] = m[9 * p + j];
-                m[9 * p + j] = t;
+            for (int j = c; j < W; ++j) {
+                const double t = m[W * c + j];
+                m[W * c + j] = m[W * p + j];
+                m[W * p + j] = t;
             }
-        const double piv = m[9 * c + c];
-        for (int r = c + 1; r < 8; ++r) {
-            const double f = m[9 * r + c] / piv;
-            for (int j = c + 1; j < 9; ++j) m[9 * r + j] = m[9 * r + j] - f * m[9 * c + j];
+        const double piv = m[W * c + c];
+        for (int r = c + 1; r < N; ++r) {
+            const double f = m[W * r + c] / piv;
+            for (int j = c + 1; j < W; ++j) m[W * r + j] = m[W * r + j] - f * m[W * c + j];
         }
     }
-    for (int c = 7; c >= 0; --c) {
-        double s = m[9 * c + 8];
-        for (int j = c + 1; j < 8; ++j) s = s - m[9 * c + j] * h[j];
-        h[c] = s / m[9 * c + c];
+    for (int c = N - 1; c >= 0; --c) {
+        double s = m[W * c + N];
+        for (int j = c + 1; j < N; ++j) s = s - m[W * c + j] * h[j];
+        h[c] = s / m[W * c + c];
         if (!f64_finite(h[c])) return false;
     }
     return true;
 }
+
+// m [8][9] -> h [8]: the homography's system
+AGX_HD bool fit_solve(double *m, double *h) { return fit_solve_n<8>(m, h); }
 
 // a normalised board point to pixels; false: w is not > 0 (u, v untouched)
 AGX_HD bool fit_project(const FitGeom &g, const double h[8], double xn, double yn, double &u, double &v)

@@ -1,0 +1,310 @@
+// board_pose_math.h -- the board's pose (R, t: board -> camera) through a frame's tag table under the pinhole + radial-tangential
+// lens model, one definition each for the host form (host_tail.cpp: board_pose) and the kernel (board_pose.hip: k_board_pose).
+// Binary64, + - * / and the square roots named below, no contraction (every file that includes it is compiled with
+// -ffp-contract=off), so both forms give the same bytes.  The reference has no such function.
+//
+// Camera (OpenCV's model; Kalibr's pinhole-radtan with k3 = 0).  THE ORDER OF OPERATIONS, for a board point (X, Y, 0):
+//   Xc = R0 X + R1 Y + t0,  Yc = R3 X + R4 Y + t1,  Zc = R6 X + R7 Y + t2      (left to right);  Zc not > 0: no projection
+//   x = Xc / Zc,  y = Yc / Zc,  r2 = x x + y y,  r4 = r2 r2,  r6 = r4 r2,  rad = 1 + k1 r2 + k2 r4 + k3 r6   (left to right)
+//   xd = x rad + 2 p1 x y + p2 (r2 + 2 x x),   yd = y rad + p1 (r2 + 2 y y) + 2 p2 x y    (2 p1 x y = ((2 p1) x) y)
+//   u = fx xd + cx,  v = fy yd + cy.
+// A prediction without a projection is (NaN, NaN), a residual +inf, as in board_fit_math.h.
+// Board points: board_fit_math.h's layout centred on the board's centre, times tag_size:
+//   X = (c (1 + s) + ox[j] - Bw/2) tag_size,  Y = (r (1 + s) + oy[j] - Bh/2) tag_size,  so t is in tag_size's unit.
+// Seed.  (1) Every inlier corner is undistorted: x0 = (u - cx) / fx, y0 = (v - cy) / fy, (x, y) = (x0, y0), then 8 times, no
+// early exit: r2, rad as above, dx = 2 p1 x y + p2 (r2 + 2 x x), dy = p1 (r2 + 2 y y) + 2 p2 x y, x = (x0 - dx) / rad,
+// y = (y0 - dy) / rad.  (2) The homography from board_fit_math.h's normalised board points (X' = X sb / tag_size) to (x, y):
+// fit_accumulate's 44 sums in fit's order of summation, fit_system, fit_solve.  (3) With q = sb / tag_size, a = q (h0, h3, h6),
+// b = q (h1, h4, h7), c = (h2, h5, 1):  lambda = 2 / (|a| + |b|), r1 = lambda a, r2 = lambda b, t = lambda c, all negated if
+// t_z < 0; Gram-Schmidt: r1 / |r1|, r2 - (r1 . r2) r1 normalised, r3 = r1 x r2.  A norm that is zero or not finite, or a t that
+// is not finite: AGX_FIT_SINGULAR.
+// Square roots: the norms of the seed and of the Gram-Schmidt, nowhere else (pose_sqrt: the correctly rounded binary64 root).
+// Refinement: Gauss-Newton on the pixel residual e = observed - projected, local update R <- R C(w), t <- t + dt,
+//   C(w) = (I - [w/2]x)^-1 (I + [w/2]x) = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a),  a = w / 2.
+// Jacobian of a correspondence (2 x 6, unknowns w then dt) = M [G | I]:  M = diag(fx, fy) D P  with D the 2 x 2 derivative of
+// (xd, yd) by (x, y), drad = k1 + 2 k2 r2 + 3 k3 r4,  P = [1 0 -x; 0 1 -y] / Zc;  G = -R [P]x, whose columns for Z = 0 are
+// Y c3, -X c3, X c2 - Y c1 (ci the columns of R).
+// Sums: the 21 entries i <= j of J^T J row by row (each correspondence as ja[i] ja[j] + jb[i] jb[j], one addition into the
+// sum), the 6 of J^T e, and the sum of |e|^2 -- POSE_SUMS = 28 doubles, added in board_fit_math.h's order: lane l of 64 takes the
+// inlier rows l, l + 64, ... in increasing order, corners 0 .. 3; the tree l ^ 32, 16, 8, 4, 2, 1.  A correspondence without a
+// projection, or whose |e|^2 is not below +inf, adds +inf to the last sum and nothing to the others.
+// Solve: fit_solve_n<6>, board_fit_math.h's elimination and pivot test on the 6 x 7 system.
+// Iterates of a round: iterate 0 is the round's starting pose (the seed in the first round, the last round's answer after);
+// iterate i + 1 is iterate i updated.  A singular system ends the round at the iterates so far; at iterate 0 (iterations > 0)
+// it is AGX_FIT_SINGULAR.  The round's answer is the iterate with the lowest finite sum of |e|^2, the earliest at equal bits
+// (iterate 0 if none is finite); the sum of the last iterate is one more pass.  The answer's R goes through the Gram-Schmidt once.
+#pragma once
+#include <cstdint>
+
+#include "../../include/aprilgrid_amd.h"
+#include "board_fit_math.h"
+
+namespace agx {
+
+constexpr int POSE_SUMS = 28;  // 21 of J^T J (i <= j) + 6 of J^T e + the sum of |e|^2
+constexpr uint32_t POSE_MAX_ITERATIONS = 64;
+constexpr int POSE_UNDISTORT_STEPS = 8;
+
+struct Pose {
+    double R[9];  // row major, board -> camera
+    double t[3];
+};
+
+// the layout's geometry as the pose reads it (the image half of FitGeom is not used)
+AGX_HD FitGeom pose_geom(uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio)
+{
+    return fit_geom(cols, rows, first_id, spacing_ratio, 1, 1);
+}
+
+AGX_HD double pose_sqrt(double v) { return __builtin_sqrt(v); }
+
+// corner j of the layout's tag t (0 .. n_board - 1) in the board's frame, in tag_size's unit
+AGX_HD void pose_board_point(const FitGeom &g, double tag_size, uint32_t t, int j, double &X, double &Y)
+{
+    const uint32_t r = t / g.cols, c = t - r * g.cols;
+    const double ox = (j == 1 || j == 2) ? 1.0 : 0.0, oy = j >= 2 ? 1.0 : 0.0;
+    X = ((double)c * g.pitch + ox - g.bx) * tag_size;
+    Y = ((double)r * g.pitch + oy - g.by) * tag_size;
+}
+
+// what the projection of one board point leaves for its Jacobian
+struct PosePoint {
+    double x, y, zc, r2, r4, rad, u, v;
+};
+
+// false: Zc is not > 0 (q untouched beyond zc)
+AGX_HD bool pose_project(const agx_camera &c, const Pose &p, double X, double Y, PosePoint &q)
+{
+    const double xc = p.R[0] * X + p.R[1] * Y + p.t[0];
+    const double yc = p.R[3] * X + p.R[4] * Y + p.t[1];
+    q.zc = p.R[6] * X + p.R[7] * Y + p.t[2];
+    if (!(q.zc > 0.0)) return false;
+    const double x = xc / q.zc, y = yc / q.zc;
+    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+    const double rad = 1.0 + c.k1 * r2 + c.k2 * r4 + c.k3 * r6;
+    const double xd = x * rad + 2.0 * c.p1 * x * y + c.p2 * (r2 + 2.0 * x * x);
+    const double yd = y * rad + c.p1 * (r2 + 2.0 * y * y) + 2.0 * c.p2 * x * y;
+    q.x = x;
+    q.y = y;
+    q.r2 = r2;
+    q.r4 = r4;
+    q.rad = rad;
+    q.u = c.fx * xd + c.cx;
+    q.v = c.fy * yd + c.cy;
+    return true;
+}
+
+// |e|^2 of one correspondence: +inf without a projection or where the value is not below +inf
+AGX_HD double pose_error(const agx_camera &c, const Pose &p, double X, double Y, double uo, double vo, PosePoint &q, double &eu, double &ev)
+{
+    if (!pose_project(c, p, X, Y, q)) return __builtin_inf();
+    eu = uo - q.u;
+    ev = vo - q.v;
+    const double e = eu * eu + ev * ev;
+    return e < __builtin_inf() ? e : __builtin_inf();
+}
+
+// a pixel to normalised coordinates: POSE_UNDISTORT_STEPS steps of the fixed-point iteration
+AGX_HD void pose_undistort(const agx_camera &c, double u, double v, double &x, double &y)
+{
+    const double x0 = (u - c.cx) / c.fx, y0 = (v - c.cy) / c.fy;
+    x = x0;
+    y = y0;
+    for (int i = 0; i < POSE_UNDISTORT_STEPS; ++i) {
+        const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+        const double rad = 1.0 + c.k1 * r2 + c.k2 * r4 + c.k3 * r6;
+        const double dx = 2.0 * c.p1 * x * y + c.p2 * (r2 + 2.0 * x * x);
+        const double dy = c.p1 * (r2 + 2.0 * y * y) + 2.0 * c.p2 * x * y;
+        x = (x0 - dx) / rad;
+        y = (y0 - dy) / rad;
+    }
+}
+
+// the seed's sums: the four correspondences of one table row (id on the board, corners finite) into a lane's FIT_SUMS
+AGX_HD void pose_seed_accumulate_row(const FitGeom &g, const agx_camera &c, double acc[FIT_SUMS], uint32_t id, const float xy[8])
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double xn, yn, x, y;
+        fit_board_point(g, id - g.first_id, j, xn, yn);
+        pose_undistort(c, (double)xy[2 * j], (double)xy[2 * j + 1], x, y);
+        fit_accumulate(acc, xn, yn, x, y);
+    }
+}
+
+// columns 0 and 1 of R normalised and made orthogonal, column 2 their cross product; false: a norm that is zero or not finite
+AGX_HD bool pose_gram_schmidt(double R[9])
+{
+    double a0 = R[0], a1 = R[3], a2 = R[6], b0 = R[1], b1 = R[4], b2 = R[7];
+    const double na = pose_sqrt(a0 * a0 + a1 * a1 + a2 * a2);
+    if (!f64_finite(na) || !(na > 0.0)) return false;
+    a0 = a0 / na;
+    a1 = a1 / na;
+    a2 = a2 / na;
+    const double d = a0 * b0 + a1 * b1 + a2 * b2;
+    b0 = b0 - d * a0;
+    b1 = b1 - d * a1;
+    b2 = b2 - d * a2;
+    const double nb = pose_sqrt(b0 * b0 + b1 * b1 + b2 * b2);
+    if (!f64_finite(nb) || !(nb > 0.0)) return false;
+    b0 = b0 / nb;
+    b1 = b1 / nb;
+    b2 = b2 / nb;
+    R[0] = a0;
+    R[3] = a1;
+    R[6] = a2;
+    R[1] = b0;
+    R[4] = b1;
+    R[7] = b2;
+    R[2] = a1 * b2 - a2 * b1;
+    R[5] = a2 * b0 - a0 * b2;
+    R[8] = a0 * b1 - a1 * b0;
+    return true;
+}
+
+// the seed: the homography h (normalised board points -> normalised image points) decomposed; false: AGX_FIT_SINGULAR
+AGX_HD bool pose_from_homography(const FitGeom &g, double tag_size, const double h[8], Pose &p)
+{
+    const double q = g.sb / tag_size;
+    const double a0 = h[0] * q, a1 = h[3] * q, a2 = h[6] * q, b0 = h[1] * q, b1 = h[4] * q, b2 = h[7] * q;
+    const double na = pose_sqrt(a0 * a0 + a1 * a1 + a2 * a2), nb = pose_sqrt(b0 * b0 + b1 * b1 + b2 * b2);
+    const double lam = 2.0 / (na + nb);  // (t_z = lambda h33 with h33 = 1: never negative, so the negation never happens here)
+    if (!f64_finite(lam) || !(lam > 0.0)) return false;
+    p.R[0] = lam * a0;
+    p.R[3] = lam * a1;
+    p.R[6] = lam * a2;
+    p.R[1] = lam * b0;
+    p.R[4] = lam * b1;
+    p.R[7] = lam * b2;
+    p.t[0] = lam * h[2];
+    p.t[1] = lam * h[5];
+    p.t[2] = lam;
+    if (!f64_finite(p.t[0]) || !f64_finite(p.t[1])) return false;
+    return pose_gram_schmidt(p.R);
+}
+
+// one correspondence into a lane's sums
+AGX_HD void pose_accumulate(const agx_camera &c, const Pose &p, double acc[POSE_SUMS], double X, double Y, double uo, double vo)
+{
+    PosePoint q;
+    double eu = 0.0, ev = 0.0;
+    const double e = pose_error(c, p, X, Y, uo, vo, q, eu, ev);
+    acc[27] += e;
+    if (!(e < __builtin_inf())) return;
+    const double x = q.x, y = q.y;
+    const double drad = c.k1 + 2.0 * c.k2 * q.r2 + 3.0 * c.k3 * q.r4;
+    const double d00 = q.rad + 2.0 * x * x * drad + 2.0 * c.p1 * y + 6.0 * c.p2 * x;
+    const double d01 = 2.0 * x * y * drad + 2.0 * c.p1 * x + 2.0 * c.p2 * y;
+    const double d10 = 2.0 * x * y * drad + 2.0 * c.p1 * x + 2.0 * c.p2 * y;
+    const double d11 = q.rad + 2.0 * y * y * drad + 6.0 * c.p1 * y + 2.0 * c.p2 * x;
+    const double m00 = c.fx * d00 / q.zc, m01 = c.fx * d01 / q.zc, m02 = -(m00 * x + m01 * y);
+    const double m10 = c.fy * d10 / q.zc, m11 = c.fy * d11 / q.zc, m12 = -(m10 * x + m11 * y);
+    // G = -R [P]x for P = (X, Y, 0): columns Y c3, -X c3, X c2 - Y c1
+    const double g00 = Y * p.R[2], g10 = Y * p.R[5], g20 = Y * p.R[8];
+    const double g01 = -(X * p.R[2]), g11 = -(X * p.R[5]), g21 = -(X * p.R[8]);
+    const double g02 = X * p.R[1] - Y * p.R[0], g12 = X * p.R[4] - Y * p.R[3], g22 = X * p.R[7] - Y * p.R[6];
+    const double ja[7] = {m00 * g00 + m01 * g10 + m02 * g20, m00 * g01 + m01 * g11 + m02 * g21, m00 * g02 + m01 * g12 + m02 * g22, m00, m01, m02, eu};
+    const double jb[7] = {m10 * g00 + m11 * g10 + m12 * g20, m10 * g01 + m11 * g11 + m12 * g21, m10 * g02 + m11 * g12 + m12 * g22, m10, m11, m12, ev};
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j, ++k) acc[k] += ja[i] * ja[j] + jb[i] * jb[j];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) acc[21 + i] += ja[i] * ja[6] + jb[i] * jb[6];
+}
+
+// the four correspondences of one inlier row into a lane's sums
+AGX_HD void pose_accumulate_row(const FitGeom &g, double tag_size, const agx_camera &c, const Pose &p, double acc[POSE_SUMS], uint32_t id,
+                                const float xy[8])
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double X, Y;
+        pose_board_point(g, tag_size, id - g.first_id, j, X, Y);
+        pose_accumulate(c, p, acc, X, Y, (double)xy[2 * j], (double)xy[2 * j + 1]);
+    }
+}
+
+// the folded sums as the augmented matrix m [6][7] (both halves of J^T J)
+AGX_HD void pose_system(const double acc[POSE_SUMS], double *m)
+{
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j, ++k) {
+            m[7 * i + j] = acc[k];
+            m[7 * j + i] = acc[k];
+        }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) m[7 * i + 6] = acc[21 + i];
+}
+
+// R <- R C(w), t <- t + dt;  d = (w, dt)
+AGX_HD void pose_update(Pose &p, const double d[6])
+{
+    const double a = d[0] / 2.0, b = d[1] / 2.0, c = d[2] / 2.0;
+    const double n = a * a + b * b + c * c, den = 1.0 + n, k = 1.0 - n;
+    const double C[9] = {(k + 2.0 * a * a) / den,       (2.0 * a * b - 2.0 * c) / den, (2.0 * a * c + 2.0 * b) / den,
+                         (2.0 * a * b + 2.0 * c) / den, (k + 2.0 * b * b) / den,       (2.0 * b * c - 2.0 * a) / den,
+                         (2.0 * a * c - 2.0 * b) / den, (2.0 * b * c + 2.0 * a) / den, (k + 2.0 * c * c) / den};
+    double R[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) R[3 * i + j] = p.R[3 * i] * C[j] + p.R[3 * i + 1] * C[3 + j] + p.R[3 * i + 2] * C[6 + j];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) p.R[i] = R[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) p.t[i] = p.t[i] + d[3 + i];
+}
+
+// the residual of one table row under the pose: the largest of its four corners' |e|^2 in pixels, binary64 rounded to binary32;
+// *sum gets the four corners' sum in corner order
+AGX_HD float pose_row_residual(const FitGeom &g, double tag_size, const agx_camera &c, const Pose &p, uint32_t id, const float xy[8], double *sum)
+{
+    double worst = 0.0, total = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double X, Y, eu, ev;
+        PosePoint q;
+        pose_board_point(g, tag_size, id - g.first_id, j, X, Y);
+        const double e = pose_error(c, p, X, Y, (double)xy[2 * j], (double)xy[2 * j + 1], q, eu, ev);
+        total += e;
+        if (e > worst) worst = e;
+    }
+    *sum = total;
+    return (float)worst;
+}
+
+// the predicted corners of the layout's tag t, rounded to binary32; NaN, NaN where Zc is not > 0
+AGX_HD void pose_predict(const FitGeom &g, double tag_size, const agx_camera &c, const Pose &p, uint32_t t, float xy[8])
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double X, Y;
+        PosePoint q;
+        pose_board_point(g, tag_size, t, j, X, Y);
+        if (pose_project(c, p, X, Y, q)) {
+            xy[2 * j] = (float)q.u;
+            xy[2 * j + 1] = (float)q.v;
+        } else {
+            xy[2 * j] = xy[2 * j + 1] = f32_from_bits(0x7fc00000u);
+        }
+    }
+}
+
+// the best-iterate rule: does an iterate whose sum of |e|^2 is `cost` replace the best so far
+AGX_HD bool pose_better(double cost, bool have, double best_cost) { return f64_finite(cost) && (!have || cost < best_cost); }
+
+// what both forms refuse in the camera and the pose's own scalars
+AGX_HD bool pose_args_ok(const agx_camera &c, double tag_size, uint32_t iterations)
+{
+    const double v[9] = {c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2, c.k3};
+    for (int i = 0; i < 9; ++i)
+        if (!f64_finite(v[i])) return false;
+    return c.fx > 0.0 && c.fy > 0.0 && f64_finite(tag_size) && tag_size > 0.0 && iterations <= POSE_MAX_ITERATIONS;
+}
+
+}  // namespace agx

@@ -6,6 +6,7 @@
 #include "host_tail.hpp"
 #include "decode_math.h"  // round_half_away, f32_as_u32, tag_affine: the decode kernels' own definitions
 #include "board_fit_math.h"  // the board fit's arithmetic and order of summation: k_board_fit's own definitions
+#include "board_pose_math.h"  // the board pose's: k_board_pose's own definitions
 
 #ifdef AGX_TAIL_PROFILE
 #include <chrono>
@@ -1765,6 +1766,137 @@ uint32_t board_fit(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint3
         if (member[t]) continue;
         pred[kept].id = first_id + t;
         fit_predict(g, h, t, pred[kept].xy);
+        ++kept;
+    }
+    *n_pred = kept;
+    return status;
+}
+
+uint32_t board_pose(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint32_t tag_status, uint32_t cols, uint32_t rows, uint32_t first_id,
+                    float spacing_ratio, double tag_size, const agx_camera &cam, float max_err_sq, uint32_t max_drop, uint32_t min_tags,
+                    uint32_t iterations, int flags, double *pose_out, float *err_sq, uint32_t *row_status, uint32_t *n_inliers, float *rms,
+                    uint32_t *best_iter, agx_tag *pred, uint32_t *n_pred, double *iter_sums)
+{
+    const FitGeom g = pose_geom(cols, rows, first_id, spacing_ratio);
+    const auto refuse = [&](uint32_t status) {
+        *n_inliers = 0;
+        *n_pred = 0;
+        return status;
+    };
+    if (n_tags > tag_cap || n_tags > FIT_MAX_ROWS || tag_status != AGX_TAGS_OK) return refuse(AGX_FIT_INPUT);
+    std::vector<uint8_t> st(n_tags);
+    uint32_t n_inl = 0;
+    for (uint32_t r = 0; r < n_tags; ++r) {
+        st[r] = AGX_FIT_ROW_OFF_BOARD;
+        if (!fit_on_board(g, tags[r].id)) continue;
+        for (int j = 0; j < 8; ++j)
+            if (!f32_finite(tags[r].xy[j])) return refuse(AGX_FIT_INPUT);
+        st[r] = AGX_FIT_ROW_INLIER;
+        ++n_inl;
+    }
+    // the kernel's 64 lanes one after the other, as in board_fit
+    const auto fold = [](double (*p)[FIT_SUMS], int n) {
+        for (int m = 32; m >= 1; m >>= 1)
+            for (int l = 0; l < m; ++l)
+                for (int k = 0; k < n; ++k) p[l][k] = p[l][k] + p[l + m][k];
+    };
+    static_assert(POSE_SUMS <= FIT_SUMS, "board_pose: the lanes' sums share board_fit's rows");
+    std::unique_ptr<double[][FIT_SUMS]> lanes(new double[64][FIT_SUMS]);
+    if (n_inl < min_tags) return refuse(AGX_FIT_FEW);
+    Pose pose;
+    {  // the seed
+        for (int l = 0; l < 64; ++l) {
+            for (int k = 0; k < FIT_SUMS; ++k) lanes[l][k] = 0.0;
+            for (uint32_t r = (uint32_t)l; r < n_tags; r += 64u)
+                if (st[r] == AGX_FIT_ROW_INLIER) pose_seed_accumulate_row(g, cam, lanes[l], tags[r].id, tags[r].xy);
+        }
+        fold(lanes.get(), FIT_SUMS);
+        double m[72], h[8];
+        fit_system(lanes[0], m);
+        if (!fit_solve(m, h) || !pose_from_homography(g, tag_size, h, pose)) return refuse(AGX_FIT_SINGULAR);
+    }
+    uint32_t status = AGX_FIT_OK, drops = 0, best_it = 0;
+    double sum_sq = 0.0;
+    for (;;) {  // a round
+        if (n_inl < min_tags) return refuse(AGX_FIT_FEW);
+        Pose cur = pose;
+        double best_cost = 0.0;
+        bool have = false;
+        best_it = 0;
+        if (iter_sums)
+            for (uint32_t i = 0; i <= iterations; ++i) iter_sums[i] = std::numeric_limits<double>::quiet_NaN();
+        for (uint32_t it = 0;; ++it) {
+            for (int l = 0; l < 64; ++l) {
+                for (int k = 0; k < POSE_SUMS; ++k) lanes[l][k] = 0.0;
+                for (uint32_t r = (uint32_t)l; r < n_tags; r += 64u)
+                    if (st[r] == AGX_FIT_ROW_INLIER) pose_accumulate_row(g, tag_size, cam, cur, lanes[l], tags[r].id, tags[r].xy);
+            }
+            fold(lanes.get(), POSE_SUMS);
+            const double cost = lanes[0][27];
+            if (iter_sums) iter_sums[it] = cost;
+            if (pose_better(cost, have, best_cost)) {
+                pose = cur;
+                best_cost = cost;
+                best_it = it;
+                have = true;
+            }
+            if (it == iterations) break;
+            double m[42], d[6];
+            pose_system(lanes[0], m);
+            if (!fit_solve_n<6>(m, d)) {
+                if (it == 0) return refuse(AGX_FIT_SINGULAR);
+                break;
+            }
+            pose_update(cur, d);
+        }
+        if (!pose_gram_schmidt(pose.R)) return refuse(AGX_FIT_SINGULAR);
+        float worst = 0.0f;
+        uint32_t worst_row = 0xffffffffu;
+        for (int l = 0; l < 64; ++l) {
+            lanes[l][0] = 0.0;
+            for (uint32_t r = (uint32_t)l; r < n_tags; r += 64u) {
+                if (st[r] != AGX_FIT_ROW_INLIER) continue;
+                double sum;
+                const float e = pose_row_residual(g, tag_size, cam, pose, tags[r].id, tags[r].xy, &sum);
+                lanes[l][0] += sum;
+                if (worst_row == 0xffffffffu || e > worst || (e == worst && r < worst_row)) {  // the lowest row at equal residual
+                    worst = e;
+                    worst_row = r;
+                }
+            }
+        }
+        if (worst > max_err_sq) {
+            if (drops < max_drop) {
+                st[worst_row] = AGX_FIT_ROW_OUTLIER;
+                ++drops;
+                --n_inl;
+                continue;
+            }
+            status = AGX_FIT_LOOSE;
+        }
+        fold(lanes.get(), 1);
+        sum_sq = lanes[0][0];
+        break;
+    }
+    for (uint32_t r = 0; r < n_tags; ++r) {
+        row_status[r] = st[r];
+        double sum;
+        if (st[r] != AGX_FIT_ROW_OFF_BOARD) err_sq[r] = pose_row_residual(g, tag_size, cam, pose, tags[r].id, tags[r].xy, &sum);
+    }
+    for (int i = 0; i < 9; ++i) pose_out[i] = pose.R[i];
+    for (int i = 0; i < 3; ++i) pose_out[9 + i] = pose.t[i];
+    *n_inliers = n_inl;
+    *rms = fit_rms(sum_sq, n_inl);
+    *best_iter = best_it;
+    std::vector<bool> member(g.n_board, false);
+    if (flags & AGX_FIT_PREDICT_MISSING)
+        for (uint32_t r = 0; r < n_tags; ++r)
+            if (st[r] == AGX_FIT_ROW_INLIER) member[tags[r].id - first_id] = true;
+    uint32_t kept = 0;
+    for (uint32_t t = 0; t < g.n_board; ++t) {
+        if (member[t]) continue;
+        pred[kept].id = first_id + t;
+        pose_predict(g, tag_size, cam, pose, t, pred[kept].xy);
         ++kept;
     }
     *n_pred = kept;

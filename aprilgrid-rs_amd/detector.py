@@ -1180,6 +1180,49 @@ class TagDetector:
             self._replaces_batch()
         self._check(rc)
 
+    # ---- the board's pose under a lens model (agx_board_pose_enqueue) --------------------------------
+    @staticmethod
+    def board_pose(tags, cols, rows, camera, **kw):
+        """The host form for one frame, no device needed: the module's board_pose."""
+        return board_pose(tags, cols, rows, camera, **kw)
+
+    def board_pose_enqueue(self, tags, n_tags, cols, rows, camera, pose, err_sq, row_status, n_inliers, rms, best_iter, pred, n_pred, status,
+                           tag_size=1.0, first_id=0, spacing_ratio=0.3, max_err_sq=4.0, max_drop=0, min_tags=1, iterations=10,
+                           predict_missing=False, tag_status=None):
+        """Per frame the pose of the printed board in the camera frame under `camera` (a Camera: pinhole + radial-tangential)
+        through every corner of the frame's tag table, its outlier rounds and the predicted corners of the layout's tags through
+        the lens model (board_pose, the host form, says what is computed), in device tensors and stream-ordered behind torch's
+        current stream; nothing to fetch.  tags, n_tags, tag_status and err_sq, row_status, n_inliers, rms, pred, n_pred, status
+        as board_fit_enqueue's; pose float64 [N, 12] (R row major, then t); best_iter int32 [N]."""
+        import torch
+        if not (getattr(tags, "is_cuda", False) and tags.dtype == torch.int32 and tags.is_contiguous() and tags.dim() == 3 and tags.shape[2] == 9
+                and tags.shape[1] > 0):
+            raise AgxError(_ffi.AGX_ERR_ARG, "tags must be a contiguous int32 device tensor [N, T, 9]")
+        n, tpf, dev = int(tags.shape[0]), int(tags.shape[1]), tags.device
+        n_board = int(cols) * int(rows)
+
+        def tensor(t, dtype, shape, what, optional=False):
+            if t is None and optional:
+                return None
+            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == shape and t.device == dev):
+                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s tensor %s on the tags' device" % (what, dtype, shape))
+            return t.data_ptr()
+
+        ins = (tensor(n_tags, torch.int32, (n,), "n_tags"), tensor(tag_status, torch.int32, (n,), "tag_status", optional=True))
+        outs = (tensor(pose, torch.float64, (n, 12), "pose"), tensor(err_sq, torch.float32, (n, tpf), "err_sq"),
+                tensor(row_status, torch.int32, (n, tpf), "row_status"), tensor(n_inliers, torch.int32, (n,), "n_inliers"),
+                tensor(rms, torch.float32, (n,), "rms"), tensor(best_iter, torch.int32, (n,), "best_iter"),
+                tensor(pred, torch.int32, (n, n_board, 9), "pred"), tensor(n_pred, torch.int32, (n,), "n_pred"),
+                tensor(status, torch.int32, (n,), "status"))
+        cam = _camera(camera)
+        self._follow_torch_stream(tags)
+        rc = self._lib.agx_board_pose_enqueue(self._h, n, tags.data_ptr(), tpf, *ins, int(cols), int(rows), int(first_id), float(spacing_ratio),
+                                              float(tag_size), cam, float(max_err_sq), int(max_drop), int(min_tags), int(iterations),
+                                              _ffi.AGX_FIT_PREDICT_MISSING if predict_missing else 0, *outs)
+        if rc == _ffi.AGX_OK:  # (a refused argument leaves the batch in flight where it is)
+            self._replaces_batch()
+        self._check(rc)
+
     def find_boards_staged(self, saddles, spacing_ratio=0.3, counts=None, point_status=None, quads_per_frame=128, candidates_per_frame=1024,
                            n_nearest=50):
         """try_find_best_board (src/detector.rs:588-639) as its stages on device tensors, at ANY spacing_ratio: the reference's seeds
@@ -1504,7 +1547,7 @@ class TagDetector:
         return (records, counts, listed), cstatus, tags, ntags, tst
 
     def recover_tags_enqueue(self, frames, saddles, counts, point_status, tags, n_tags, tag_status, cols, rows, first_id=0, spacing_ratio=0.3,
-                             max_dist=3.0, max_err=2.0, max_drop=4, min_tags=2, format=None):
+                             max_dist=3.0, max_err=2.0, max_drop=4, min_tags=2, format=None, camera=None, tag_size=1.0, iterations=10):
         """The tags of a printed board that a frame's table lacks, recovered in place on device tensors, stream-ordered behind
         torch's current stream, with no host step: board_fit_enqueue over the tables with only the missing tags predicted (the
         layout cols x rows from first_id at spacing_ratio; a row more than max_err px off goes, at most max_drop of them) ->
@@ -1515,8 +1558,10 @@ class TagDetector:
         find_boards_enqueue reads them; tags int32 [N, T, 9], n_tags and tag_status int32 [N]: the tables, in and out.  A frame
         whose fit is not AGX_FIT_OK or AGX_FIT_LOOSE predicts nothing and keeps its table; a recovered id that an outlier row
         already holds takes that row (collect's rule), and the fit returned says which rows those were.
-        -> the fit's device tensors: dict(h, err_sq, row_status, n_inliers, rms, pred, n_pred, status) of board_fit_enqueue, and
-        recovered int32 [N], the quads accepted per frame."""
+        With camera= (a Camera) the first step is board_pose_enqueue at tag_size and iterations instead: the predictions go
+        through the lens model, everything behind them is unchanged.
+        -> the fit's device tensors: dict(h, err_sq, row_status, n_inliers, rms, pred, n_pred, status) of board_fit_enqueue -- with
+        a camera pose and best_iter of board_pose_enqueue in place of h --, and recovered int32 [N], the quads accepted per frame."""
         import torch
         if not (getattr(saddles, "is_cuda", False) and saddles.dim() == 3 and saddles.shape[2] >= 2):
             raise AgxError(_ffi.AGX_ERR_ARG, "saddles must be a device tensor [N, S, K >= 5]")
@@ -1526,12 +1571,20 @@ class TagDetector:
         dev = frames.device
         i32 = dict(dtype=torch.int32, device=dev)
         f32 = dict(dtype=torch.float32, device=dev)
-        fit = dict(h=torch.zeros((n, 9), dtype=torch.float64, device=dev), err_sq=torch.zeros((n, tpf), **f32),
+        fit = dict(err_sq=torch.zeros((n, tpf), **f32),
                    row_status=torch.zeros((n, tpf), **i32), n_inliers=torch.zeros(n, **i32), rms=torch.zeros(n, **f32),
                    pred=torch.zeros((n, max(nb, 1), 9), **i32), n_pred=torch.zeros(n, **i32), status=torch.zeros(n, **i32))
-        self.board_fit_enqueue(tags, n_tags, cols, rows, (w, h), first_id=first_id, spacing_ratio=spacing_ratio,
-                               max_err_sq=float(max_err) * float(max_err), max_drop=max_drop, min_tags=min_tags, predict_missing=True,
-                               tag_status=tag_status, **fit)
+        if camera is None:
+            fit["h"] = torch.zeros((n, 9), dtype=torch.float64, device=dev)
+            self.board_fit_enqueue(tags, n_tags, cols, rows, (w, h), first_id=first_id, spacing_ratio=spacing_ratio,
+                                   max_err_sq=float(max_err) * float(max_err), max_drop=max_drop, min_tags=min_tags, predict_missing=True,
+                                   tag_status=tag_status, **fit)
+        else:
+            fit["pose"] = torch.zeros((n, 12), dtype=torch.float64, device=dev)
+            fit["best_iter"] = torch.zeros(n, **i32)
+            self.board_pose_enqueue(tags, n_tags, cols, rows, camera, tag_size=tag_size, first_id=first_id, spacing_ratio=spacing_ratio,
+                                    max_err_sq=float(max_err) * float(max_err), max_drop=max_drop, min_tags=min_tags, iterations=iterations,
+                                    predict_missing=True, tag_status=tag_status, **fit)
         slots, quads = torch.zeros((n, nb, 4), **i32), torch.zeros((n, nb, 4), **i32)
         nq, sst, index = torch.zeros(n, **i32), torch.zeros(n, **i32), torch.zeros((n, nb), **i32)
         self.snap_points_enqueue(saddles, fit["pred"], slots, quads, nq, sst, float(max_dist) * float(max_dist), counts=counts,
@@ -1550,7 +1603,8 @@ class TagDetector:
         return fit
 
     def detect_recovered(self, frames, cols, rows, first_id=0, spacing_ratio=0.3, max_dist=3.0, max_err=2.0, max_drop=4, min_tags=2,
-                         clusters_per_frame=4096, quads_per_frame=128, tags_per_frame=None, format=None, return_fit=False):
+                         clusters_per_frame=4096, quads_per_frame=128, tags_per_frame=None, format=None, return_fit=False, camera=None,
+                         tag_size=1.0, iterations=10):
         """detect (src/detector.rs:505-540) of frames that show ONE printed board whose layout is known (Kalibr's AprilGrid:
         cols x rows tags from first_id, spacing_ratio), with the tags the board search dropped recovered: detect_staged's chain
         and rounds, then recover_tags_enqueue on its arrays as they stand -- fit, predict the missing tags, snap, decode, accept
@@ -1558,13 +1612,15 @@ class TagDetector:
         detect_staged's result.  Outlier rows are reported, never removed.
         -> one {tag_id: 4x2 corners} per frame in row order (detect_staged's rows first, bit for bit); with return_fit also a
         list of dict(status, H, rms, n_inliers, row_status, err_sq, recovered) per frame, row_status / err_sq over detect_staged's
-        rows (AGX_FIT_ROW_*); H, rms, row_status and err_sq are None where the fit was refused."""
+        rows (AGX_FIT_ROW_*); H, rms, row_status and err_sq are None where the fit was refused.  With camera= (a Camera) the
+        predictions go through the lens model (recover_tags_enqueue's camera=), and the dicts carry pose (float64 [12]: R row major,
+        then t, at tag_size) and best_iter in place of H."""
         (records, counts, listed), cstatus, tags, ntags, tst = self._staged_tables(frames, clusters_per_frame, quads_per_frame, tags_per_frame,
                                                                                    format, "affine", keep_listed=True)
         before = ntags.clone()
         fit = self.recover_tags_enqueue(frames, records, counts, listed, tags, ntags, tst, cols, rows, first_id=first_id,
                                         spacing_ratio=spacing_ratio, max_dist=max_dist, max_err=max_err, max_drop=max_drop, min_tags=min_tags,
-                                        format=format)
+                                        format=format, camera=camera, tag_size=tag_size, iterations=iterations)
         self.sync()
         out = self._staged_result("detect_recovered", cstatus, int(clusters_per_frame), tags, ntags, tst)
         if not return_fit:
@@ -1575,8 +1631,10 @@ class TagDetector:
         for f in range(len(out)):
             st, k = int(host["status"][f]), int(before[f])
             good = st in (_ffi.AGX_FIT_OK, _ffi.AGX_FIT_LOOSE)
-            fits.append({"status": st, "n_inliers": int(host["n_inliers"][f]), "recovered": int(host["recovered"][f]),
-                         "H": host["h"][f].reshape(3, 3).copy() if good else None, "rms": float(host["rms"][f]) if good else None,
+            model = ({"H": host["h"][f].reshape(3, 3).copy() if good else None} if camera is None else
+                     {"pose": host["pose"][f].copy() if good else None, "best_iter": int(host["best_iter"][f]) if good else None})
+            fits.append({"status": st, "n_inliers": int(host["n_inliers"][f]), "recovered": int(host["recovered"][f]), **model,
+                         "rms": float(host["rms"][f]) if good else None,
                          "row_status": host["row_status"][f, :k].view(np.uint32).copy() if good else None,
                          "err_sq": host["err_sq"][f, :k].copy() if good else None})
         return out, fits
@@ -2026,6 +2084,59 @@ def board_fit(tags, cols, rows, img_size, first_id=0, spacing_ratio=0.3, max_err
     out = {"status": status.value, "n_inliers": n_inl.value, "n_pred": n_pred.value}
     if status.value in (_ffi.AGX_FIT_OK, _ffi.AGX_FIT_LOOSE):
         out.update(H=h.reshape(3, 3), err_sq=err[:n], row_status=rst[:n], rms=rms.value, pred=pred[:n_pred.value].copy())
+    return out
+
+
+class Camera(namedtuple("Camera", "fx fy cx cy k1 k2 p1 p2 k3", defaults=(0.0, 0.0, 0.0, 0.0, 0.0))):
+    """agx_camera: the pinhole + radial-tangential model (OpenCV's; Kalibr's pinhole-radtan with k3 = 0).  Camera(fx, fy, cx, cy)
+    is a pinhole."""
+    __slots__ = ()
+
+    def as_doubles(self):
+        """The nine doubles agx_board_pose_enqueue / _tail read."""
+        return (C.c_double * 9)(*[float(v) for v in self])
+
+
+def _camera(camera):
+    if camera is None:
+        raise AgxError(_ffi.AGX_ERR_ARG, "camera must be given")
+    return (camera if isinstance(camera, Camera) else Camera(*camera)).as_doubles()
+
+
+def board_pose(tags, cols, rows, camera, tag_size=1.0, first_id=0, spacing_ratio=0.3, max_err_sq=4.0, max_drop=0, min_tags=1, iterations=10,
+               predict_missing=False, tag_status=0, tags_per_frame=None, return_iter_sums=False):
+    """The host form of board_pose_enqueue for one frame (agx_board_pose_tail) without a device: the pose of the printed board
+    (board_fit's layout in the plane Z = 0, centred on the board's centre, times tag_size) in the camera frame, Xc = R X + t, under
+    `camera` (a Camera, or its nine numbers) through every corner of `tags`: a homography seed on undistorted corners, then
+    `iterations` Gauss-Newton steps on the pixel residual, the best iterate kept; board_fit's outlier rounds on the pose's
+    residuals; the predicted corners of the layout's tags through the lens model.
+    -> dict: status AGX_FIT_*; for AGX_FIT_OK and AGX_FIT_LOOSE also R [3, 3] and t [3] float64, pose (the 12 numbers as stored),
+    best_iter, err_sq, row_status, n_inliers, rms, pred as board_fit's; with return_iter_sums (a debug return, a second run through
+    agx_debug_board_pose_sums) also iter_sums [iterations + 1], the sum of |e|^2 of every iterate of the last round (NaN: not
+    reached)."""
+    t = _tag_rows(tags)
+    n = int(t.shape[0])
+    cap = n if tags_per_frame is None else int(tags_per_frame)
+    n_board = max(int(cols) * int(rows), 1) if 0 < int(cols) * int(rows) <= 4096 else 1
+    pose = np.zeros(12, np.float64)
+    sums = np.full(max(int(iterations), 0) + 1 if 0 <= int(iterations) <= 64 else 1, np.nan, np.float64)
+    err, rst = np.full(max(n, 1), np.nan, np.float32), np.zeros(max(n, 1), np.uint32)
+    pred = np.zeros(n_board, TagDetector.TAG_DTYPE)
+    n_inl, n_pred, status, rms, best = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_float(0), C.c_uint32(0)
+    head = (t.ctypes.data if n else None, cap, n, int(tag_status), int(cols), int(rows), int(first_id), float(spacing_ratio), float(tag_size),
+            _camera(camera), float(max_err_sq), int(max_drop), int(min_tags), int(iterations), _ffi.AGX_FIT_PREDICT_MISSING if predict_missing else 0)
+    st = _ffi.lib().agx_board_pose_tail(*head, pose.ctypes.data, err.ctypes.data, rst.ctypes.data, C.byref(n_inl), C.byref(rms), C.byref(best),
+                                        pred.ctypes.data, C.byref(n_pred), C.byref(status))
+    if st == _ffi.AGX_OK and return_iter_sums:
+        st = _ffi.lib().agx_debug_board_pose_sums(*head, C.byref(C.c_uint32(0)), sums.ctypes.data)
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    out = {"status": status.value, "n_inliers": n_inl.value, "n_pred": n_pred.value}
+    if status.value in (_ffi.AGX_FIT_OK, _ffi.AGX_FIT_LOOSE):
+        out.update(R=pose[:9].reshape(3, 3), t=pose[9:], pose=pose, best_iter=best.value, err_sq=err[:n], row_status=rst[:n], rms=rms.value,
+                   pred=pred[:n_pred.value].copy())
+        if return_iter_sums:
+            out["iter_sums"] = sums
     return out
 
 

@@ -367,6 +367,22 @@ extern "C" {
                               spacing_ratio: c_float, img_w: c_int, img_h: c_int, max_err_sq: c_float, max_drop: u32, min_tags: u32,
                               flags: c_int, h: *mut c_double, err_sq: *mut c_float, row_status: *mut u32, n_inliers: *mut u32,
                               rms: *mut c_float, pred: *mut agx_tag, n_pred: *mut u32, status: *mut u32) -> c_int;
+    // camera: the nine doubles of an agx_camera (fx, fy, cx, cy, k1, k2, p1, p2, k3), host memory
+    pub fn agx_board_pose_enqueue(det: *mut agx_detector, n_frames: c_int, d_tags: *const agx_tag, tags_per_frame: u32, d_n_tags: *const u32,
+                                  d_tag_status: *const u32, cols: u32, rows: u32, first_id: u32, spacing_ratio: c_float, tag_size: c_double,
+                                  camera: *const c_double, max_err_sq: c_float, max_drop: u32, min_tags: u32, iterations: u32, flags: c_int,
+                                  d_pose: *mut c_double, d_err_sq: *mut c_float, d_row_status: *mut u32, d_n_inliers: *mut u32,
+                                  d_rms: *mut c_float, d_best_iter: *mut u32, d_pred: *mut agx_tag, d_n_pred: *mut u32,
+                                  d_status: *mut u32) -> c_int;
+    pub fn agx_board_pose_tail(tags: *const agx_tag, tags_per_frame: u32, n_tags: u32, tag_status: u32, cols: u32, rows: u32, first_id: u32,
+                               spacing_ratio: c_float, tag_size: c_double, camera: *const c_double, max_err_sq: c_float, max_drop: u32,
+                               min_tags: u32, iterations: u32, flags: c_int, pose: *mut c_double, err_sq: *mut c_float,
+                               row_status: *mut u32, n_inliers: *mut u32, rms: *mut c_float, best_iter: *mut u32, pred: *mut agx_tag,
+                               n_pred: *mut u32, status: *mut u32) -> c_int;
+    pub fn agx_debug_board_pose_sums(tags: *const agx_tag, tags_per_frame: u32, n_tags: u32, tag_status: u32, cols: u32, rows: u32,
+                                     first_id: u32, spacing_ratio: c_float, tag_size: c_double, camera: *const c_double,
+                                     max_err_sq: c_float, max_drop: u32, min_tags: u32, iterations: u32, flags: c_int,
+                                     status: *mut u32, iter_sums: *mut c_double) -> c_int;
     pub fn agx_debug_blur_weights(sigma: c_float, weights: *mut c_float, cap: c_int, radius: *mut c_int) -> c_int;
     pub fn agx_debug_refine_constants(half_size_patch: c_int, cone: *mut c_float, pmat: *mut c_float, cap_points: c_int,
                                       n_points: *mut c_int) -> c_int;

@@ -794,6 +794,85 @@ pub fn board_fit_tail(tags: &[(u32, [(f32, f32); 4])], layout: &BoardLayout, img
     })
 }
 
+/// `agx_camera`: the pinhole + radial-tangential model (OpenCV's; Kalibr's pinhole-radtan with `k3 = 0`).
+#[derive(Clone, Copy, Debug, Default)]
+pub struct Camera {
+    pub fx: f64,
+    pub fy: f64,
+    pub cx: f64,
+    pub cy: f64,
+    pub k1: f64,
+    pub k2: f64,
+    pub p1: f64,
+    pub p2: f64,
+    pub k3: f64,
+}
+
+/// What `board_pose_tail` found for one frame.
+#[derive(Clone, Debug)]
+pub struct BoardPose {
+    /// `AGX_FIT_OK` or `AGX_FIT_LOOSE`
+    pub status: u32,
+    /// row major, board -> camera
+    pub r: [f64; 9],
+    /// in `tag_size`'s unit
+    pub t: [f64; 3],
+    /// the iterate of the last round that became the answer (0 = the pose the round started from)
+    pub best_iter: u32,
+    /// per row of the table: `AGX_FIT_ROW_*` and the squared residual in pixels (not written for an off-board row: NaN)
+    pub rows: Vec<(u32, f32)>,
+    pub n_inliers: usize,
+    pub rms: f32,
+    /// predicted tags in id order, through the lens model
+    pub pred: Vec<(u32, [(f32, f32); 4])>,
+}
+
+/// The pose of the printed board in the camera frame (`Xc = R X + t`, board points in the plane Z = 0 centred on the board's
+/// centre, times `tag_size`) under `camera` through every corner of a frame's tag table: a homography seed on undistorted corners,
+/// `iterations` (0..=64) Gauss-Newton steps with the best iterate kept, `board_fit_tail`'s outlier rounds on the pose's residuals,
+/// and the predicted corners of the layout's tags through the lens model.  The host form (no device is used).  `Err(status)`:
+/// `AGX_FIT_FEW`, `AGX_FIT_SINGULAR` or `AGX_FIT_INPUT`.  Panics where the library refuses the arguments.
+pub fn board_pose_tail(tags: &[(u32, [(f32, f32); 4])], layout: &BoardLayout, camera: &Camera, tag_size: f64, max_err_sq: f32, max_drop: u32,
+                       min_tags: u32, iterations: u32, predict_missing: bool) -> Result<BoardPose, u32> {
+    let table: Vec<ffi::agx_tag> = tags.iter().map(|t| ffi::agx_tag {
+        id: t.0,
+        xy: [t.1[0].0, t.1[0].1, t.1[1].0, t.1[1].1, t.1[2].0, t.1[2].1, t.1[3].0, t.1[3].1],
+    }).collect();
+    assert!(layout.cols > 0 && layout.rows > 0 && layout.cols as u64 * layout.rows as u64 <= 4096, "board_pose_tail: rows * cols in 1..=4096");
+    let n_board = layout.cols as usize * layout.rows as usize;
+    let cam = [camera.fx, camera.fy, camera.cx, camera.cy, camera.k1, camera.k2, camera.p1, camera.p2, camera.k3];
+    let mut pose = [0f64; 12];
+    let mut err = vec![f32::NAN; tags.len().max(1)];
+    let mut row_status = vec![0u32; tags.len().max(1)];
+    let mut pred = vec![ffi::agx_tag { id: 0, xy: [0.0; 8] }; n_board];
+    let (mut n_inliers, mut n_pred, mut status, mut best_iter, mut rms) = (0u32, 0u32, 0u32, 0u32, 0f32);
+    let st = unsafe {
+        ffi::agx_board_pose_tail(table.as_ptr(), table.len() as u32, table.len() as u32, ffi::AGX_TAGS_OK as u32, layout.cols, layout.rows,
+                                 layout.first_id, layout.spacing_ratio, tag_size, cam.as_ptr(), max_err_sq, max_drop, min_tags, iterations,
+                                 if predict_missing { ffi::AGX_FIT_PREDICT_MISSING } else { 0 }, pose.as_mut_ptr(), err.as_mut_ptr(),
+                                 row_status.as_mut_ptr(), &mut n_inliers, &mut rms, &mut best_iter, pred.as_mut_ptr(), &mut n_pred,
+                                 &mut status)
+    };
+    assert_eq!(st, ffi::AGX_OK, "agx_board_pose_tail failed: {}", st);
+    if status as c_int != ffi::AGX_FIT_OK && status as c_int != ffi::AGX_FIT_LOOSE {
+        return Err(status);
+    }
+    let (mut r, mut t) = ([0f64; 9], [0f64; 3]);
+    r.copy_from_slice(&pose[..9]);
+    t.copy_from_slice(&pose[9..]);
+    Ok(BoardPose {
+        status,
+        r,
+        t,
+        best_iter,
+        rows: (0..tags.len()).map(|k| (row_status[k], err[k])).collect(),
+        n_inliers: n_inliers as usize,
+        rms,
+        pred: pred[..n_pred as usize].iter()
+            .map(|q| (q.id, [(q.xy[0], q.xy[1]), (q.xy[2], q.xy[3]), (q.xy[4], q.xy[5]), (q.xy[6], q.xy[7])])).collect(),
+    })
+}
+
 fn last_error(det: *const ffi::agx_detector) -> String {
     unsafe {
         let p = ffi::agx_last_error(det);

@@ -1111,6 +1111,77 @@ int agx_board_fit_tail(const agx_tag *tags, uint32_t tags_per_frame, uint32_t n_
                        double *h, float *err_sq, uint32_t *row_status, uint32_t *n_inliers, float *rms,
                        agx_tag *pred, uint32_t *n_pred, uint32_t *status);
 
+/* ---- the board's pose under a lens model: R, t, outliers, predicted corners ------------------ */
+
+/* What a calibration, VIO or hand-eye pipeline computes next from a frame's tag table once the camera's intrinsics are known: the
+ * pose of the printed board in the camera frame, Xc = R X + t.  agx_board_fit_enqueue's homography is exact for a pinhole only;
+ * under lens distortion its RMS measures the lens, its rounds drop good tags near the border, and its predictions drift where
+ * the search loses tags.  This call is that one with the camera in the model: the same tables, layout, rounds, statuses,
+ * prediction rows and contract, the 8 unknowns of H replaced by the 6 of (R, t).
+ * Model (OpenCV's; Kalibr's pinhole-radtan with k3 = 0): for a point (X, Y, Z) in the camera frame, x = X/Z, y = Y/Z,
+ * r2 = x^2 + y^2, x' = x (1 + k1 r2 + k2 r2^2 + k3 r2^3) + 2 p1 x y + p2 (r2 + 2 x^2), y' = y (1 + ...) + p1 (r2 + 2 y^2) + 2 p2 x y,
+ * u = fx x' + cx, v = fy y' + cy; a point whose Z is not > 0 has no projection (a prediction is (NaN, NaN), a residual +inf).
+ * Board points: agx_board_fit_enqueue's layout in the plane Z = 0, centred on the board's centre, times tag_size (the tag's
+ * side in the caller's unit): t comes out in that unit.  camera: nine doubles in the order fx, fy, cx, cy, k1,
+ * k2, p1, p2, k3, HOST memory, copied by the call.  The prototypes take them as const double *: struct agx_camera below only
+ * names the nine (it is asserted here to be exactly nine doubles, so &cam.fx is the argument); no prototype takes the struct.
+ * Arithmetic (csrc/board_pose_math.h states it once for both forms, the order of operations included): binary64, + - * / and
+ * correctly rounded square roots (the norms of the seed and of the Gram-Schmidt only), no contraction.  Seed: every inlier
+ * corner undistorted by 8 steps of the fixed-point iteration, the homography to those by agx_board_fit_enqueue's sums and
+ * solve, decomposed (lambda = 2 / (|h1| + |h2|), Gram-Schmidt).  Refinement: `iterations` Gauss-Newton steps on the pixel
+ * residual through the full model, analytic Jacobian, local update R <- R C(w) by the Cayley map (no sin, no cos), t <- t + dt;
+ * 28 sums added in agx_board_fit_enqueue's fixed order (64 lanes, the tree l ^ 32 .. 1, no floating-point atomics), the 6 x 7
+ * system by the same elimination and pivot test.  Iterate 0 of a round is the pose it starts from; the round's answer is the
+ * iterate with the lowest finite sum of |e|^2, the earliest at equal bits (iterate 0 if no sum is finite), so a diverging step
+ * never makes the result worse than the seed; a singular system ends the round at the iterates so far.  The answer's R is
+ * re-orthonormalised once.  Rounds as agx_board_fit_enqueue's on the pose's residuals; a round after a drop starts from the
+ * last round's answer (the seed is not redone) with another `iterations` steps on fresh sums.
+ * Results, frame f, all required, caller-owned device memory:
+ *   d_pose [n_frames][12]  R row major (board -> camera), then t;
+ *   d_row_status, d_err_sq, d_n_inliers, d_rms, d_pred, d_n_pred: as agx_board_fit_enqueue's, under the pose and the lens model
+ *     (d_pred rows go to agx_snap_points_enqueue as they stand);
+ *   d_best_iter[f]: the iterate of the last round that became the answer, 0 .. iterations;
+ *   d_status[f]: AGX_FIT_OK, AGX_FIT_LOOSE, or -- decided before the frame's first store, with d_n_pred[f] = d_n_inliers[f] = 0
+ *     and nothing else written -- AGX_FIT_FEW, AGX_FIT_INPUT (both as agx_board_fit_enqueue's) or AGX_FIT_SINGULAR (the seed's
+ *     system or decomposition: a refused pivot, a norm that is zero or not finite; or a round's system at its iterate 0 with
+ *     iterations > 0).
+ * Only entries below the counts are ever written.  No table is changed.  The call replaces the batch in flight without waiting.
+ * AGX_ERR_ARG (a batch in flight stays where it is): agx_board_fit_enqueue's list (without img_w, img_h), and a NULL camera, a
+ * camera field that is not finite, fx or fy not > 0, tag_size not finite or not > 0, iterations > 64, d_pose not 8-byte
+ * aligned. */
+struct agx_camera { double fx, fy, cx, cy, k1, k2, p1, p2, k3; };
+typedef struct agx_camera agx_camera;
+#ifdef __cplusplus
+static_assert(sizeof(agx_camera) == 9 * sizeof(double), "agx_camera: nine doubles");
+#else
+_Static_assert(sizeof(agx_camera) == 9 * sizeof(double), "agx_camera: nine doubles");
+#endif
+int agx_board_pose_enqueue(agx_detector *det, int n_frames,
+                           const agx_tag *d_tags, uint32_t tags_per_frame, const uint32_t *d_n_tags, const uint32_t *d_tag_status,
+                           uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
+                           const double *camera,
+                           float max_err_sq, uint32_t max_drop, uint32_t min_tags, uint32_t iterations, int flags,
+                           double *d_pose, float *d_err_sq, uint32_t *d_row_status,
+                           uint32_t *d_n_inliers, float *d_rms, uint32_t *d_best_iter,
+                           agx_tag *d_pred, uint32_t *d_n_pred, uint32_t *d_status);
+/* The host form without a detector handle (no device needed): ONE frame in host memory, the same arithmetic, order of summation
+ * and bytes.  pose [12], err_sq / row_status [n_tags], pred [rows*cols]; *status AGX_FIT_*.
+ * AGX_ERR_ARG as the batch call's (tags, err_sq and row_status may be NULL with n_tags == 0; tags_per_frame may be 0). */
+int agx_board_pose_tail(const agx_tag *tags, uint32_t tags_per_frame, uint32_t n_tags, uint32_t tag_status,
+                        uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
+                        const double *camera,
+                        float max_err_sq, uint32_t max_drop, uint32_t min_tags, uint32_t iterations, int flags,
+                        double *pose, float *err_sq, uint32_t *row_status, uint32_t *n_inliers, float *rms, uint32_t *best_iter,
+                        agx_tag *pred, uint32_t *n_pred, uint32_t *status);
+/* For tests of the best-iterate rule: the host form run on the same frame, of which only *status and iter_sums [iterations + 1]
+ * (8-byte aligned) are handed out -- the sum of |e|^2 of every iterate of the last round, NaN for an iterate that was not
+ * reached.  AGX_ERR_ARG as agx_board_pose_tail's. */
+int agx_debug_board_pose_sums(const agx_tag *tags, uint32_t tags_per_frame, uint32_t n_tags, uint32_t tag_status,
+                              uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
+                              const double *camera,
+                              float max_err_sq, uint32_t max_drop, uint32_t min_tags, uint32_t iterations, int flags,
+                              uint32_t *status, double *iter_sums);
+
 /* ---- detector groups: several GPUs of one node driven from ONE process ----------------- */
 
 /* The reference's detect(&self) is stateless, so a batch shards by frame:
