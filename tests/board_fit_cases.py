@@ -60,7 +60,7 @@ def numpy_fit(table, cols, rows, size, first_id=0, s=0.3, keep=None):
     P = board_points(cols, rows, s)
     a, b = [], []
     for i, row in enumerate(table):
-        t = int(row["id"]) - first_id
+        t = (int(row["id"]) - int(first_id)) % (1 << 32)  # the window may pass 2^32: id 3 is tag 19 of a layout from 0xFFFFFFF0
         if not 0 <= t < rows * cols or (keep is not None and not keep[i]):
             continue
         for j in range(4):
@@ -83,9 +83,14 @@ def exact_table(cols, rows, ids, H, first_id=0, s=0.3, noise=0.0, seed=1):
     rng = np.random.RandomState(seed)
     P = P + noise * (2.0 * rng.rand(*P.shape) - 1.0)
     out = np.zeros(len(ids), TAG)
-    out["id"] = np.asarray(ids, np.uint32) + first_id
+    out["id"] = wrapped_ids(first_id, ids)
     out["xy"] = P.reshape(len(ids), 8).astype(np.float32)
     return out
+
+
+def wrapped_ids(first_id, t):
+    """The ids of the layout's tags t: (first_id + t) mod 2^32 as uint32, computed in int64."""
+    return ((np.asarray(t, np.int64) + int(first_id)) & 0xFFFFFFFF).astype(np.uint32)
 
 
 def pose(cols, rows, size, s=0.3, tilt=0.0):
@@ -158,6 +163,18 @@ def swap_id(table, row, new_id):
     return t
 
 
+WRAP_FIRST_ID = 0xFFFFFFF0
+WRAP_RATIOS = (0.0, -0.5, 1.0)
+WRAP_GONE = (3, 15, 16, 22)  # tags of the 7 x 4 layout taken out on either side of the wrap: ids 0xFFFFFFF3, 0xFFFFFFFF, 0, 6
+WRAP_OFF_IDS = (0xFFFFFFEF, 12)
+WRAP_TILT = 0.02
+
+
+def wrap_table(s):
+    """Every tag of the 7 x 4 layout from WRAP_FIRST_ID at spacing ratio s under pose(7, 4, (800, 600), s, WRAP_TILT), exact."""
+    return exact_table(7, 4, range(28), pose(7, 4, (800, 600), s=s, tilt=WRAP_TILT), first_id=WRAP_FIRST_ID, s=s)
+
+
 @functools.lru_cache(maxsize=None)
 def cases():
     """Every case of the CPU suite, which the GPU suite runs again for byte parity: name -> Batch."""
@@ -216,6 +233,16 @@ def cases():
     many = exact_table(64, 64, range(650), pose(64, 64, (1280, 800)))
     out.append(Batch("count_641", [many[:641]], 64, 64, (1280, 800), tpf=700))
     out.append(Batch("count_640", [many[:640]], 64, 64, (1280, 800), tpf=700))
+    # the id window past 2^32, at the spacing ratios 0 (tags edge to edge), -0.5 (overlapping) and 1: the 7 x 4 layout from
+    # 0xFFFFFFF0, whose 28 ids run through 0xFFFFFFFF, wrap to 0 and end at 11
+    for s in WRAP_RATIOS:
+        out.append(Batch("wrap_s%g" % s, [wrap_table(s)], 7, 4, (800, 600), first_id=WRAP_FIRST_ID, s=s))
+    keep = [t for t in range(28) if t not in WRAP_GONE]
+    out.append(Batch("wrap_s1_missing", [wrap_table(1.0)[keep]], 7, 4, (800, 600), first_id=WRAP_FIRST_ID, s=1.0, flags=_ffi.AGX_FIT_PREDICT_MISSING))
+    off = wrap_table(1.0)[[5, 20]]
+    off["id"] = WRAP_OFF_IDS  # the ids next to the window on either side: first_id - 1 and first_id + 28 mod 2^32
+    off["xy"][0, 1] = np.nan  # never read
+    out.append(Batch("wrap_off_board", [np.concatenate([off[:1], wrap_table(1.0), off[1:]])], 7, 4, (800, 600), first_id=WRAP_FIRST_ID, s=1.0))
     _, _, tags, (w, h, rows, cols) = frame(2)  # 100 tags: the lane stride wraps at 64
     t = tag_rows(tags)
     for n in (63, 64, 65):

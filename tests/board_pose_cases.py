@@ -12,7 +12,7 @@ import numpy as np
 import aprilgrid_rs_amd as A
 from aprilgrid_rs_amd import _ffi
 
-from tests.board_fit_cases import FILL, TAG, untouched, swap_id  # noqa: F401  (one sentinel, one row type)
+from tests.board_fit_cases import FILL, TAG, untouched, swap_id, wrapped_ids  # noqa: F401  (one sentinel, one row type, one id wrap)
 
 OK, LOOSE, FEW, SINGULAR, INPUT = _ffi.AGX_FIT_OK, _ffi.AGX_FIT_LOOSE, _ffi.AGX_FIT_FEW, _ffi.AGX_FIT_SINGULAR, _ffi.AGX_FIT_INPUT
 INLIER, OUTLIER, OFF_BOARD = _ffi.AGX_FIT_ROW_INLIER, _ffi.AGX_FIT_ROW_OUTLIER, _ffi.AGX_FIT_ROW_OFF_BOARD
@@ -24,6 +24,14 @@ CAMERAS = {
     "pinhole": A.Camera(400.0, 400.0, 400.0, 300.0),
     "mild": A.Camera(400.0, 410.0, 395.0, 305.0, -0.1, 0.01, 1e-3, -1e-3, 0.0),
     "barrel": A.Camera(400.0, 400.0, 400.0, 300.0, -0.3, 0.1, 0.0, 0.0, 0.0),
+    # every term of the model live.  "k3": the radial map r rad(r) stays monotone out to the image's corner, where its slope
+    # 1 + 3 k1 r^2 + 5 k2 r^4 + 7 k3 r^6 is 0.28 (a map that folds inside the image, k1 = k2 = 0, k3 = 0.05 for one, is not inverted
+    # by the seed's 8 undistortion steps: a test under it measures the seed, not the model); without its k3 the "near" board's corners
+    # move by hundreds of pixels, the frontal board's by 6.5 px.  "tangential": p1, p2 twenty times "mild"'s.  "full": anisotropic,
+    # off-centre, no coefficient zero.
+    "k3": A.Camera(400.0, 400.0, 400.0, 300.0, -0.3, 0.1, 0.0, 0.0, -0.02),
+    "tangential": A.Camera(400.0, 400.0, 400.0, 300.0, 0.0, 0.0, 0.02, -0.015, 0.0),
+    "full": A.Camera(380.0, 420.0, 410.0, 290.0, -0.25, 0.08, 0.01, -0.008, -0.015),
 }
 KEYS = ("pose", "err_sq", "row_status", "n_inliers", "rms", "best_iter", "pred", "n_pred", "status")
 
@@ -86,9 +94,14 @@ def extent(cols, rows, s=0.3, tag_size=TAG_SIZE):
     return max(cols * (1.0 + s) - s, rows * (1.0 + s) - s) * tag_size
 
 
-def pose(name, cols, rows, tag_size=TAG_SIZE):
+def pose(name, cols, rows, tag_size=TAG_SIZE, s=0.3):
     ang, t = POSES[name]
-    return rotation(*ang), np.asarray(t, np.float64) * extent(cols, rows, tag_size=tag_size)
+    return rotation(*ang), np.asarray(t, np.float64) * extent(cols, rows, s, tag_size)
+
+
+def layout_index(ids, first_id):
+    """The layout's tag under each id: (id - first_id) mod 2^32 in int64 (what the header's wrapping subtraction gives)."""
+    return (np.asarray(ids).astype(np.int64) - int(first_id)) & 0xFFFFFFFF
 
 
 def splitmix64(n, seed):
@@ -112,7 +125,7 @@ def exact_table(cols, rows, ids, cam, R, t, tag_size=TAG_SIZE, first_id=0, s=0.3
     if noise:
         uv = uv + noise * splitmix64(uv.size, seed).reshape(uv.shape)
     out = np.zeros(len(ids), TAG)
-    out["id"] = ids.astype(np.uint32) + first_id
+    out["id"] = wrapped_ids(first_id, ids)
     out["xy"] = uv.reshape(len(ids), 8).astype(np.float32)
     return out
 
@@ -120,7 +133,7 @@ def exact_table(cols, rows, ids, cam, R, t, tag_size=TAG_SIZE, first_id=0, s=0.3
 def yardstick(table, cols, rows, cam, R0, t0, tag_size=TAG_SIZE, first_id=0, s=0.3):
     """The least-squares pose of the table's rows by scipy, started from (R0, t0) -> (R, t, sum of |e|^2)."""
     from scipy.optimize import least_squares
-    P = board_points(cols, rows, s, tag_size)[table["id"].astype(np.int64) - first_id]
+    P = board_points(cols, rows, s, tag_size)[layout_index(table["id"], first_id)]
     obs = table["xy"].astype(np.float64).reshape(-1, 4, 2)
 
     def res(p):
@@ -204,19 +217,30 @@ SEED_ONLY_STATUS = {
     "64x64_mild_it0_drop0_all": [LOOSE] + [OK] * 8 + [LOOSE, FEW, SINGULAR, INPUT, INPUT, INPUT],
     "6x6_barrel_it0_drop2_missing": [OK, OK, LOOSE, OK, OK, LOOSE, FEW, SINGULAR, INPUT, LOOSE],
 }
+# The launches under the cameras with every term live and with a wrapping id window (first_id = 0xFFFFFFF0: the 36 ids run
+# through 0xFFFFFFFF to 19): the statuses as the host form gives them, pinned.
+WRAP_FIRST_ID = 0xFFFFFFF0
+LIVE_STATUS = {
+    "64x64_full_it10_drop2_missing": [OK] * 9 + [LOOSE, OK, FEW, SINGULAR, INPUT, INPUT, INPUT],
+    "6x6_full_it10_drop2_missing": [OK] * 5 + [LOOSE, FEW, SINGULAR, INPUT, OK],
+    "6x6_k3_it10_drop0_all": [OK] * 5 + [LOOSE, FEW, SINGULAR, INPUT],
+    "6x6_full_s1_wrap": [OK] * 5 + [LOOSE, FEW, SINGULAR, INPUT, OK],
+    "6x6_full_s-0.5_wrap": [OK] * 5 + [LOOSE, FEW, SINGULAR, INPUT, OK],
+    "6x6_full_s0_wrap": [OK] * 5 + [LOOSE, FEW, SINGULAR, INPUT, OK],
+}
 
 
 @functools.lru_cache(maxsize=None)
 def gpu_batches():
     """The launches of the GPU parity test: name -> (PoseBatch, the statuses its first frames must have).  The layout, the camera,
-    iterations, max_drop and the flag are scalars of a call, so each combination is a launch of its own; every launch holds
-    every frame status and tables whose row counts straddle the lane stride."""
+    iterations, max_drop, the flag, the spacing ratio and first_id are scalars of a call, so each combination is a launch of its
+    own; every launch holds every frame status and tables whose row counts straddle the lane stride."""
     out = {}
     rng = np.random.RandomState(7)
     # 64 x 64, tag_size 0.01: the board spans 0.83; counts 1, 4, 36, 63, 64, 65, 129, 587 of a table of 600 rows
     R, t = pose("tilt40", 64, 64, 0.01)
     ids = rng.permutation(4096)[:587]
-    for cam, it, drop, flags in (("barrel", 10, 2, MISSING), ("mild", 0, 0, 0)):
+    for cam, it, drop, flags in (("barrel", 10, 2, MISSING), ("mild", 0, 0, 0), ("full", 10, 2, MISSING)):
         full = exact_table(64, 64, ids, CAMERAS[cam], R, t, 0.01, first_id=5, noise=0.05)
         off = full[:3].copy()
         off["id"] = [4, 5 + 4096, 0xFFFFFFFF]  # ids around the layout: never fitted
@@ -237,15 +261,19 @@ def gpu_batches():
         status += [INPUT, INPUT]  # a count above the rows per frame; a table whose status word is not AGX_TAGS_OK
         tag_status = [0] * (len(tables) - 1) + [_ffi.AGX_TAGS_CAPACITY]
         name = "64x64_%s_it%d_drop%d_%s" % (cam, it, drop, "missing" if flags else "all")
-        status = SEED_ONLY_STATUS.get(name, status)
+        status = LIVE_STATUS.get(name, SEED_ONLY_STATUS.get(name, status))
         out[name] = (PoseBatch(name, tables, 64, 64, CAMERAS[cam], 0.01, first_id=5, max_drop=drop, iterations=it, flags=flags, counts=counts,
                                tag_status=tag_status, tpf=600), status)
     # 6 x 6: the five poses under one camera a launch, a wrong id, and the refusals
-    for cam, it, drop, flags in (("pinhole", 10, 0, MISSING), ("mild", 10, 2, 0), ("barrel", 0, 2, MISSING), ("barrel", 10, 0, 0)):
+    # (the launches after the first four draw from rng after them: the first four stay what they were)
+    for cam, it, drop, flags, s, first_id in (("pinhole", 10, 0, MISSING, 0.3, 0), ("mild", 10, 2, 0, 0.3, 0), ("barrel", 0, 2, MISSING, 0.3, 0),
+                                              ("barrel", 10, 0, 0, 0.3, 0), ("full", 10, 2, MISSING, 0.3, 0), ("k3", 10, 0, 0, 0.3, 0),
+                                              ("full", 10, 1, MISSING, 1.0, WRAP_FIRST_ID), ("full", 10, 1, MISSING, -0.5, WRAP_FIRST_ID),
+                                              ("full", 10, 1, MISSING, 0.0, WRAP_FIRST_ID)):
         tables, status = [], []
         for k, p in enumerate(sorted(POSES)):
-            R, t = pose(p, 6, 6)
-            full = exact_table(6, 6, range(36), CAMERAS[cam], R, t, noise=0.1, seed=k + 1)
+            R, t = pose(p, 6, 6, s=s)
+            full = exact_table(6, 6, range(36), CAMERAS[cam], R, t, first_id=first_id, s=s, noise=0.1, seed=k + 1)
             tables.append(full[rng.permutation(36)[:36 - 5 * k]])
             status.append(OK)
         base = tables[0]
@@ -255,8 +283,10 @@ def gpu_batches():
             tables.append(_wrong(base, 1))
             status.append(OK)
         name = "6x6_%s_it%d_drop%d_%s" % (cam, it, drop, "missing" if flags else "all")
-        status = SEED_ONLY_STATUS.get(name, status)
-        out[name] = (PoseBatch(name, tables, 6, 6, CAMERAS[cam], max_drop=drop, iterations=it, flags=flags, tpf=40), status)
+        if first_id:
+            name = "6x6_%s_s%g_wrap" % (cam, s)
+        status = LIVE_STATUS.get(name, SEED_ONLY_STATUS.get(name, status))
+        out[name] = (PoseBatch(name, tables, 6, 6, CAMERAS[cam], first_id=first_id, s=s, max_drop=drop, iterations=it, flags=flags, tpf=40), status)
     R, t = pose("tilt40", 1, 1)
     one = exact_table(1, 1, [0], CAMERAS["mild"], R, t, first_id=7)
     out["1x1"] = (PoseBatch("1x1", [one, one[:0], flat_row(one)], 1, 1, CAMERAS["mild"], first_id=7, flags=MISSING, tpf=3), [OK, FEW, SINGULAR])
@@ -335,14 +365,31 @@ def warped_frame():
     return luma, cam, O.refined_saddle_points(luma), O.detect(luma), (w, h, rows, cols)
 
 
-def recovered_host(luma, saddles, tags, cols, rows, camera=None, max_dist=3.0, max_err=2.0, max_drop=4, min_tags=2, family="t36h11"):
+FRAME_FIRST_ID = 100
+
+
+@functools.lru_cache(maxsize=None)
+def frame_from_100():
+    """The rendered 6 x 6 frame (seed 12, 800 x 600) of a board whose ids run from 100 to 135 -> (luma, the oracle's saddle list,
+    the oracle's detect {id: 4x2}, the pinhole camera_of the homography fitted to it)."""
+    from oracle import oracle as O
+    from aprilgrid_rs_amd import synth
+    img, _ = synth.render_frame(12, 800, 600, spec=synth.BoardSpec(rows=6, cols=6, first_id=FRAME_FIRST_ID))
+    img = np.ascontiguousarray(img.numpy())
+    tags = O.detect(img)
+    from tests import board_fit_cases as BC
+    K = camera_of(A.board_fit(BC.tag_rows(tags), 6, 6, (800, 600), first_id=FRAME_FIRST_ID)["H"], 800, 600)
+    return img, O.refined_saddle_points(img), tags, A.Camera(*K)
+
+
+def recovered_host(luma, saddles, tags, cols, rows, camera=None, first_id=0, max_dist=3.0, max_err=2.0, max_drop=4, min_tags=2, family="t36h11"):
     """recover_tags_enqueue restated over the host forms for one frame, with board_pose in board_fit's place when a camera is
     given (board_fit_cases.recovered_host is the same without one) -> ({id: 4x2 corners} in row order, the fit's dict)."""
     from tests import board_fit_cases as BC
     saddles = np.ascontiguousarray(saddles, A.SADDLE_DTYPE)
     h, w = luma.shape
     table = BC.tag_rows(tags)
-    kw = dict(max_err_sq=max_err * max_err, max_drop=max_drop, min_tags=min_tags, predict_missing=True)
+    kw = dict(first_id=first_id, max_err_sq=max_err * max_err, max_drop=max_drop, min_tags=min_tags, predict_missing=True)
     fit = A.board_fit(table, cols, rows, (w, h), **kw) if camera is None else A.board_pose(table, cols, rows, camera, **kw)
     if fit["status"] not in (OK, LOOSE) or not len(fit["pred"]) or not len(saddles):
         return dict(tags), fit

@@ -165,6 +165,54 @@ def test_off_board_rows_are_marked_and_never_fitted():
             assert bad[k].tobytes() == out[k].tobytes(), (name, k)
 
 
+def wrap_fit(name, s):
+    """A case on the wrapping 7 x 4 layout -> (batch, outputs, the lstsq yardstick's corners, the exact homography's corners);
+    the yardstick does its own modular id subtraction, and H is held to it."""
+    b, out = run(name)
+    assert (b.cols, b.rows, b.first_id, b.s) == (7, 4, 0xFFFFFFF0, s) and out["status"][0] == OK
+    _, want = BC.numpy_fit(b.tables[0], 7, 4, b.size, first_id=b.first_id, s=s)
+    P = BC.board_points(7, 4, s)
+    worst = np.abs(BC.project(out["h"][0], P) - want).max()
+    exact = BC.project(BC.pose(7, 4, b.size, s=s, tilt=BC.WRAP_TILT), P)
+    print("%s: H-projected corners against lstsq %.3e px, lstsq against the exact homography %.3e px" % (name, worst, np.abs(want - exact).max()))
+    assert worst <= TOL
+    return b, out, want, exact
+
+
+@pytest.mark.parametrize("s", BC.WRAP_RATIOS)
+def test_spacing_ratios_with_an_id_window_that_passes_2_to_the_32(s):
+    """first_id = 0xFFFFFFF0: the layout's 28 ids run through 0xFFFFFFFF, wrap to 0 and end at 11 (fit_on_board's wrapping
+    subtraction, the prediction's first_id + t), at spacing ratios the other cases never take: 0, -0.5 and 1."""
+    b, out, want, exact = wrap_fit("wrap_s%g" % s, s)
+    layout = [(0xFFFFFFF0 + t) % (1 << 32) for t in range(28)]
+    assert b.tables[0]["id"].tolist() == layout and layout[15:17] == [0xFFFFFFFF, 0] and layout[-1] == 11
+    assert out["n_inliers"][0] == 28 and (out["row_status"][0, :28] == INLIER).all()
+    ids, pred = pred_corners(out)
+    assert ids.dtype == np.uint32 and ids.tolist() == layout
+    assert np.abs(pred - want).max() <= TOL and np.abs(pred - exact).max() <= TOL
+    assert out["err_sq"][0, :28].max() <= TOL ** 2 and out["rms"][0] <= TOL
+
+
+def test_missing_tags_on_either_side_of_the_wrap_are_predicted():
+    b, out, want, exact = wrap_fit("wrap_s1_missing", 1.0)
+    gone = list(BC.WRAP_GONE)
+    ids, pred = pred_corners(out)
+    assert out["n_inliers"][0] == 24 and ids.tolist() == [(0xFFFFFFF0 + t) % (1 << 32) for t in gone] == [0xFFFFFFF3, 0xFFFFFFFF, 0, 6]
+    d = np.abs(pred - exact[gone]).max()
+    print("wrap_s1_missing: predicted corners of the missing tags against the exact homography %.3e px" % d)
+    assert d <= TOL and np.abs(pred - want[gone]).max() <= TOL
+    assert BC.untouched(out["pred"][0, 4:])
+
+
+def test_ids_next_to_a_wrapped_window_are_off_the_board():
+    b, out, want, exact = wrap_fit("wrap_off_board", 1.0)
+    ids = b.tables[0]["id"].tolist()
+    assert (ids[0], ids[-1]) == (0xFFFFFFEF, 12) == BC.WRAP_OFF_IDS and len(ids) == 30
+    assert out["row_status"][0, :30].tolist() == [OFF_BOARD] + [INLIER] * 28 + [OFF_BOARD] and out["n_inliers"][0] == 28
+    assert BC.untouched(out["err_sq"][0, [0, 29]]) and out["err_sq"][0, 1:29].max() <= TOL ** 2
+    assert np.abs(pred_corners(out)[1] - exact).max() <= TOL
+
+
 def test_a_steep_pose_predicts_nan_where_w_is_not_positive():
     b, out = run("steep")
     assert out["status"][0] == OK and out["rms"][0] < 1e-3

@@ -3,10 +3,17 @@ yardstick written independently of csrc/board_pose_math.h: numpy float64 project
 rotation vector and t, started from the ground truth (tests/board_pose_cases.py).
 
 Measured on the cases below (printed by the tests before they assert):
-  exact data   the largest corner distance between the host form's reprojection and the yardstick's: 2.55e-5 px over 30 cases
-               (2 layouts x 5 poses x 3 cameras; the corners are rounded to binary32, 3e-5 px at 800 px, and the minimum is flat
-               at that level), so the bound is 10 x that, 2.55e-4 px (the ceiling is 1e-3 px);
+  exact data   the largest corner distance between the host form's reprojection and the yardstick's: 2.55e-5 px over 60 cases
+               (2 layouts x 5 poses x 6 cameras, three of them with k3, strong tangential terms and all nine numbers live; the
+               corners are rounded to binary32, 3e-5 px at 800 px, and the minimum is flat at that level), so the bound is 10 x
+               that, 2.55e-4 px (the ceiling is 1e-3 px); the worst of the three live cameras alone is 1.11e-5 px;
   noisy data   +-0.1 px: the host form's sum of |e|^2 exceeds the yardstick's minimum by at most 1.75e-9 relative (bound 1e-6);
+  step         one Gauss-Newton step from the seed against the step of a central-difference Jacobian (cameras full, k3, barrel x
+               poses tilt40, near): the reference at h = 1e-5 against itself at h / 2 differs by 5.6e-8 px at worst, so the bound
+               is 10 x that, 5.6e-7 px (the ceiling is 1e-3 px); the library's iterate 1 lies 1.4e-12 .. 7.4e-8 px from the
+               reference's, after steps that move the corners 0.016 .. 87 px;
+  scale        tag_size 1e-3 and 1e3 against 0.05 on the same pixels: R differs by 1.7e-15 at most, t / tag_size by 2.0e-11
+               relative, rms and all 288 predicted values by 0 ulp; the pose's doubles are not bit-equal;
   barrel       board_fit's rms over the whole board 21.3 px, its predictions of the 20 tags of the outermost ring (taken out
                four at a time) 10.7 .. 199.7 px off; board_pose's rms 0.077 .. 0.079 px, its predictions 0.127 px off at most;
   rendered     board_fit / board_pose rms on the three rendered frames: 0.0294 / 0.0294, 0.0368 / 0.0368, 0.0445 / 0.0445 px;
@@ -29,6 +36,7 @@ from aprilgrid_rs_amd import _ffi
 EXACT_MEASURED = 2.55e-5  # px: see the module's docstring
 EXACT_BOUND = min(10.0 * EXACT_MEASURED, 1e-3)
 CASES = [(c, r, p, k) for c, r in LAYOUTS for p in sorted(POSES) for k in sorted(CAMERAS)]
+LIVE = ("full", "k3", "tangential")  # the cameras whose k3 and tangential products are not products with 0 or 1e-3
 
 
 @functools.lru_cache(maxsize=None)
@@ -45,18 +53,21 @@ def is_rotation(R):
 
 
 def test_exact_data_reprojects_like_the_yardstick():
-    worst = 0.0
+    worst = worst_live = 0.0
     for cols, rows, p, cam in CASES:
         table, got, (Ry, ty, _), (R, t) = solved(cols, rows, p, cam, 0.0)
         assert got["status"] == OK, (cols, rows, p, cam)
         P = PC.board_points(cols, rows, tag_size=TAG_SIZE)
         d = np.linalg.norm(PC.project(CAMERAS[cam], got["R"], got["t"], P) - PC.project(CAMERAS[cam], Ry, ty, P), axis=-1).max()
         worst = max(worst, d)
+        if cam in LIVE:
+            worst_live = max(worst_live, d)
         is_rotation(got["R"])
         assert np.abs(got["R"] - R).max() < 1e-4 and np.abs(got["t"] - t).max() < 1e-4 * PC.extent(cols, rows), (p, cam)
         # the predicted rows are the pose's reprojection rounded to binary32
         assert np.abs(got["pred"]["xy"].reshape(-1, 4, 2) - PC.project(CAMERAS[cam], got["R"], got["t"], P)).max() < 1e-4
-    print("exact data: largest corner distance to the yardstick %.3g px (bound %.3g)" % (worst, EXACT_BOUND))
+    print("exact data: largest corner distance to the yardstick %.3g px over %d cases (bound %.3g); under %s alone %.3g px"
+          % (worst, len(CASES), EXACT_BOUND, ", ".join(LIVE), worst_live))
     assert worst <= EXACT_BOUND
 
 
@@ -72,6 +83,148 @@ def test_noisy_data_reaches_the_yardsticks_minimum():
         is_rotation(got["R"])
     print("noisy data: largest relative gap of the sum of |e|^2 to the yardstick's minimum %.3g (bound 1e-6)" % worst)
     assert worst <= 1e-6
+
+
+def test_the_ninth_double_of_the_camera_is_read():
+    """k3 on the whole way Python -> C ABI -> the host form: the predicted rows under camera "k3" are the numpy projection with
+    k3, and far from the projection without it."""
+    cam = CAMERAS["k3"]
+    table, got, _, _ = solved(6, 6, "tilt40", "k3", 0.0)
+    assert got["status"] == OK and cam.k3 == -0.02 and len(got["pred"]) == 36
+    P = PC.board_points(6, 6, tag_size=TAG_SIZE)
+    pred = got["pred"]["xy"].reshape(36, 4, 2).astype(np.float64)
+    with_k3 = np.linalg.norm(pred - PC.project(cam, got["R"], got["t"], P), axis=-1).max()
+    without = np.linalg.norm(pred - PC.project(cam._replace(k3=0.0), got["R"], got["t"], P), axis=-1).max()
+    print("k3: pred against the projection with k3 %.3g px, with k3 = 0 %.3g px" % (with_k3, without))
+    assert with_k3 < 1e-4 and without > 10.0
+
+
+# ---- one Gauss-Newton step against a step from a finite-difference Jacobian ---------------------------------------------------------
+STEP_H = 1e-5  # the difference step: radians for w, tag sides for dt
+# The ABI carries spacing_ratio as binary32: at 0.3 the library's board is the one of 0.300000012, whose corners lie up to 2e-5 px
+# from the board of the binary64 0.3 -- two hundred times the reference's own error, so the reference takes the ratio the library gets.
+STEP_S = float(np.float32(0.3))
+STEP_SELF_MEASURED = 5.6e-8  # px: see the module's docstring
+STEP_BOUND = min(10.0 * STEP_SELF_MEASURED, 1e-3)
+STEP_CASES = [(cam, p) for cam in ("full", "k3", "barrel") for p in ("tilt40", "near")]
+STEP_NOISE_SEED = 11
+
+
+def cayley(w):
+    """C(w) = (I - [w/2]x)^-1 (I + [w/2]x)."""
+    a = np.asarray(w, np.float64) / 2.0
+    K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    return np.linalg.solve(np.eye(3) - K, np.eye(3) + K)
+
+
+def reference_step(cam, R0, t0, P, obs, h):
+    """Iterate 1 of Gauss-Newton from (R0, t0) in numpy float64: the Jacobian of the projection by (w, dt) from central
+    differences of step h (h * TAG_SIZE for dt), the step from lstsq, R orthonormalised (its nearest rotation, by SVD)."""
+    def f(d):
+        return PC.project(cam, R0 @ cayley(d[:3]), t0 + d[3:], P).ravel()
+
+    J = np.empty((obs.size, 6))
+    for i in range(6):
+        d = np.zeros(6)
+        d[i] = h if i < 3 else h * TAG_SIZE
+        J[:, i] = (f(d) - f(-d)) / (2.0 * d[i])
+    step = np.linalg.lstsq(J, obs.ravel() - f(np.zeros(6)), rcond=None)[0]
+    U, _, Vt = np.linalg.svd(R0 @ cayley(step[:3]))
+    return U @ Vt, t0 + step[3:]
+
+
+@functools.lru_cache(maxsize=None)
+def stepped(cam, p):
+    """-> (distance of the library's iterate 1 to the reference's, distance of the reference at STEP_H to itself at STEP_H / 2),
+    both the largest distance in px between the two poses' projections of the board's 144 corners."""
+    c = CAMERAS[cam]
+    R, t = PC.pose(p, 6, 6)
+    table = PC.exact_table(6, 6, range(36), c, R, t, s=STEP_S, noise=0.1, seed=STEP_NOISE_SEED)
+    seed = A.board_pose(table, 6, 6, c, tag_size=TAG_SIZE, spacing_ratio=STEP_S, iterations=0, max_err_sq=1e30)
+    got = A.board_pose(table, 6, 6, c, tag_size=TAG_SIZE, spacing_ratio=STEP_S, iterations=1, max_err_sq=1e30)
+    assert seed["status"] == OK and seed["best_iter"] == 0 and got["status"] == OK
+    assert got["best_iter"] == 1, (cam, p)  # (holds for all six cases at noise seed STEP_NOISE_SEED)
+    P = PC.board_points(6, 6, STEP_S, TAG_SIZE)
+    obs = table["xy"].astype(np.float64).reshape(36, 4, 2)
+    uv = [PC.project(c, Rr, tr, P) for Rr, tr in (reference_step(c, seed["R"], seed["t"], P, obs, STEP_H),
+                                                  reference_step(c, seed["R"], seed["t"], P, obs, STEP_H / 2.0))]
+    mine = PC.project(c, got["R"], got["t"], P)
+    moved = np.linalg.norm(mine - PC.project(c, seed["R"], seed["t"], P), axis=-1).max()
+    assert moved > 0.01, (cam, p, moved)  # the step is there to be compared: the seed is not the minimum
+    return np.linalg.norm(mine - uv[0], axis=-1).max(), np.linalg.norm(uv[0] - uv[1], axis=-1).max(), moved
+
+
+def test_the_finite_difference_reference_agrees_with_itself_as_measured():
+    worst = max(stepped(cam, p)[1] for cam, p in STEP_CASES)
+    print("step: the finite-difference reference at h = %g against h / 2: %.3g px at worst (recorded %.3g, bound 10 x = %.3g px)"
+          % (STEP_H, worst, STEP_SELF_MEASURED, STEP_BOUND))
+    assert worst <= STEP_SELF_MEASURED
+
+
+@pytest.mark.parametrize("cam,p", STEP_CASES)
+def test_one_gauss_newton_step_is_the_finite_difference_step(cam, p):
+    """The analytic Jacobian of pose_accumulate, compared step for step and not through convergence: iterate 1 from the seed
+    (iterations = 0 returns it) against the step of a Jacobian taken by central differences of the numpy projection."""
+    d, self_d, moved = stepped(cam, p)
+    print("step %s / %s: the library's iterate 1 is %.3g px from the reference's (the step moved the corners %.3g px; bound %.3g px)"
+          % (cam, p, d, moved, STEP_BOUND))
+    assert d <= STEP_BOUND
+
+
+@pytest.mark.parametrize("s", (0.0, -0.5, 1.0))
+def test_spacing_ratios_with_an_id_window_that_passes_2_to_the_32(s):
+    """Camera "full", the 40 degree tilt, the 6 x 6 layout from 0xFFFFFFF0 (its ids run through 0xFFFFFFFF to 19) at the spacing
+    ratios 0, -0.5 and 1, t scaled with the board's extent at that ratio: pitch, bx, by, sb, the seed's q and the wrapping id
+    arithmetic, against the yardstick on exact data under the exact-data bound."""
+    cam, first = CAMERAS["full"], PC.WRAP_FIRST_ID
+    R, t = PC.pose("tilt40", 6, 6, s=s)
+    assert np.allclose(t, np.array(POSES["tilt40"][1]) * PC.extent(6, 6, s))
+    table = PC.exact_table(6, 6, range(36), cam, R, t, first_id=first, s=s)
+    layout = [(first + k) % (1 << 32) for k in range(36)]
+    assert table["id"].tolist() == layout and layout[15:17] == [0xFFFFFFFF, 0]
+    got = A.board_pose(table, 6, 6, cam, tag_size=TAG_SIZE, first_id=first, spacing_ratio=s)
+    Ry, ty, _ = PC.yardstick(table, 6, 6, cam, R, t, first_id=first, s=s)
+    P = PC.board_points(6, 6, s, TAG_SIZE)
+    d = np.linalg.norm(PC.project(cam, got["R"], got["t"], P) - PC.project(cam, Ry, ty, P), axis=-1).max()
+    print("spacing %g, first_id 0x%X: largest corner distance to the yardstick %.3g px (bound %.3g)" % (s, first, d, EXACT_BOUND))
+    assert got["status"] == OK and got["n_inliers"] == 36 and d <= EXACT_BOUND
+    is_rotation(got["R"])
+    assert np.abs(got["R"] - R).max() < 1e-4 and np.abs(got["t"] - t).max() < 1e-4 * PC.extent(6, 6, s)
+    # the ids survive the Python wrapper as unsigned values, in layout order; the rows are the pose's reprojection
+    assert got["pred"]["id"].dtype == np.uint32 and got["pred"]["id"].tolist() == layout
+    assert np.abs(got["pred"]["xy"].reshape(-1, 4, 2) - PC.project(cam, got["R"], got["t"], P)).max() < 1e-4
+    gone = [3, 15, 16, 30]  # on either side of the wrap
+    less = A.board_pose(np.delete(table, gone), 6, 6, cam, tag_size=TAG_SIZE, first_id=first, spacing_ratio=s, predict_missing=True)
+    assert less["status"] == OK and less["pred"]["id"].tolist() == [layout[k] for k in gone]
+    assert np.abs(less["pred"]["xy"].reshape(-1, 4, 2) - PC.project(cam, R, t, P[gone])).max() < 1e-3
+    off = table[:2].copy()
+    off["id"] = [first - 1, (first + 36) % (1 << 32)]  # next to the window on either side
+    mixed = A.board_pose(np.concatenate([off[:1], table, off[1:]]), 6, 6, cam, tag_size=TAG_SIZE, first_id=first, spacing_ratio=s)
+    assert mixed["row_status"].tolist() == [PC.OFF_BOARD] + [PC.INLIER] * 36 + [PC.OFF_BOARD] and mixed["n_inliers"] == 36
+
+
+def test_the_unit_of_tag_size_only_scales_t():
+    """The same pixels at tag_size 1e-3, 0.05 and 1e3: R and t / tag_size agree to 1e-9, rms and the predicted rows to one
+    binary32 ulp.  Observed: not bit-equal -- q = sb / tag_size and X = (...) tag_size round differently at each tag_size (0.05 and
+    1e-3 are no powers of two), so the doubles differ in their last bits; the binary32 results are the same bits at all but
+    the few values where that falls on a rounding boundary (printed)."""
+    cam = CAMERAS["full"]
+    R, t = PC.pose("tilt40", 6, 6)
+    table = PC.exact_table(6, 6, range(36), cam, R, t, noise=0.1, seed=11)
+    got = {ts: A.board_pose(table, 6, 6, cam, tag_size=ts) for ts in (1e-3, TAG_SIZE, 1e3)}
+    ref = got[TAG_SIZE]
+    assert ref["status"] == OK and np.abs(ref["t"] - t).max() < 1e-2 * PC.extent(6, 6)
+    for ts, g in got.items():
+        assert g["status"] == OK
+        dR = np.abs(g["R"] - ref["R"]).max()
+        dt = (np.abs(g["t"] / ts - ref["t"] / TAG_SIZE) / np.abs(ref["t"] / TAG_SIZE)).max()
+        a, b = g["pred"]["xy"].view(np.int32).astype(np.int64), ref["pred"]["xy"].view(np.int32).astype(np.int64)
+        ulp_pred = int(np.abs(a - b).max())
+        ulp_rms = abs(int(np.float32(g["rms"]).view(np.int32)) - int(np.float32(ref["rms"]).view(np.int32)))
+        print("tag_size %g against %g: R differs by %.3g, t / tag_size by %.3g relative, pred by %d ulp (%d of %d values), rms by %d ulp, pose bytes %s"
+              % (ts, TAG_SIZE, dR, dt, ulp_pred, int((a != b).sum()), a.size, ulp_rms, "equal" if g["pose"][:9].tobytes() == ref["pose"][:9].tobytes() else "differ"))
+        assert dR <= 1e-9 and dt <= 1e-9 and ulp_pred <= 1 and ulp_rms <= 1
+        assert g["pred"]["id"].tolist() == ref["pred"]["id"].tolist() and g["row_status"].tolist() == ref["row_status"].tolist()
 
 
 def outer_ring(cols, rows):
@@ -144,6 +297,23 @@ def test_on_a_warped_frame_the_camera_recovers_strictly_more_tags():
     assert len(with_cam) == 36 and len(plain) == 34 and pose["rms"] < 0.1 < fit["rms"]
     for t in PC.WARP_MISSING:  # and they come back where the oracle found them
         assert np.array_equal(with_cam[t].view(np.uint32), np.asarray(tags[t], np.float32).view(np.uint32))
+
+
+def test_on_a_rendered_board_whose_ids_start_at_100_the_missing_tags_come_back():
+    """first_id through the recovery restated over the host forms, with and without a camera: the renderer prints ids 100 .. 135,
+    the oracle detects all of them, three leave the table and return with the oracle's corners bit for bit."""
+    luma, saddles, tags, cam = PC.frame_from_100()
+    assert sorted(tags) == list(range(100, 136))
+    gone = (100, 114, 135)
+    less = {t: xy for t, xy in tags.items() if t not in gone}
+    for camera in (None, cam):
+        got, fit = PC.recovered_host(luma, saddles, less, 6, 6, camera=camera, first_id=PC.FRAME_FIRST_ID)
+        assert fit["status"] == OK and fit["n_inliers"] == 33 and fit["pred"]["id"].tolist() == list(gone)
+        assert list(got) == list(less) + list(gone)
+        for t in tags:
+            assert np.array_equal(got[t].view(np.uint32), np.asarray(tags[t], np.float32).view(np.uint32)), t
+    # under first_id = 0 only the ids 100 .. 135 that a 6 x 6 layout from 0 holds are on the board: none
+    assert PC.recovered_host(luma, saddles, less, 6, 6, camera=cam)[1]["status"] == FEW
 
 
 def base36(cam="mild", noise=0.1):

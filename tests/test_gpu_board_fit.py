@@ -80,13 +80,13 @@ def test_one_launch_with_all_five_frame_statuses(det):
             assert all(BC.untouched(want[k][f]) for k in ("h", "err_sq", "row_status", "rms", "pred"))
 
 
-def big_table(n_on, n_off, cols=24, rows=24, size=(1280, 800)):
+def big_table(n_on, n_off, cols=24, rows=24, size=(1280, 800), first_id=3, s=0.3):
     """n_on tags of the 24 x 24 layout under a tilted pose with 0.05 px of noise, n_off rows with ids beyond it in between."""
     rng = np.random.RandomState(5)
     ids = rng.permutation(cols * rows)[:n_on]
-    t = BC.exact_table(cols, rows, ids, BC.pose(cols, rows, size, tilt=0.01), first_id=3, noise=0.05)
-    off = BC.exact_table(cols, rows, range(n_off), BC.pose(cols, rows, size), first_id=3)
-    off["id"] = 3 + cols * rows + np.arange(n_off)
+    t = BC.exact_table(cols, rows, ids, BC.pose(cols, rows, size, s=s, tilt=0.01), first_id=first_id, s=s, noise=0.05)
+    off = BC.exact_table(cols, rows, range(n_off), BC.pose(cols, rows, size, s=s), first_id=first_id, s=s)
+    off["id"] = BC.wrapped_ids(first_id, cols * rows + np.arange(n_off))
     out = np.concatenate([t, off])
     return out[rng.permutation(len(out))]
 
@@ -98,6 +98,23 @@ def test_rows_per_frame_around_the_lane_stride_and_at_the_largest_family(det, tp
     tables = [full, full[:tpf // 2], full[:max(tpf - 1, 0)]]
     want = same_bytes(det, Batch("tpf%d" % tpf, tables, 24, 24, (1280, 800), first_id=3, max_drop=2, flags=MISSING, tpf=tpf))
     assert want["status"][0] == OK and want["n_inliers"][0] == min(tpf, 576) and want["n_pred"][0] == 576 - min(tpf, 576)
+
+
+@pytest.mark.parametrize("tpf", (65, 587))
+def test_a_wrapping_id_window_across_several_passes_of_64_tags(det, tpf):
+    """The 24 x 24 layout from 0xFFFFFF00 at spacing ratio 1: its 576 ids pass 2^32 after 256 tags, so the member bitmap in LDS
+    and the ballot compaction of pred run on wrapped ids over nine passes of 64 tags; at 587 rows the 11 off-board ids follow the
+    window's wrapped end."""
+    first = 0xFFFFFF00
+    full = big_table(min(tpf, 576), max(tpf - 576, 0), first_id=first, s=1.0)
+    assert len(full) == tpf and full["id"].max() >= first and full["id"].min() < 576 - 256
+    tables = [full, full[:tpf // 2], full[:tpf - 1]]
+    want = same_bytes(det, Batch("wrap_tpf%d" % tpf, tables, 24, 24, (1280, 800), first_id=first, s=1.0, max_drop=2, flags=MISSING, tpf=tpf))
+    n_on = min(tpf, 576)
+    assert want["status"][0] == OK and want["n_inliers"][0] == n_on and want["n_pred"][0] == 576 - n_on
+    assert (want["row_status"][0] == BC.OFF_BOARD).sum() == tpf - n_on
+    have = set(full["id"].tolist())
+    assert want["pred"][0, :576 - n_on]["id"].tolist() == [i for i in BC.wrapped_ids(first, np.arange(576)).tolist() if i not in have]
 
 
 @pytest.mark.parametrize("n", (1, 3, 2 * FRAMES_PER_WG + 1))

@@ -3,7 +3,9 @@ FILL bytes beyond and between what a frame may write included (tests/test_board_
 least-squares pose).  This is also the test that decides whether the binary64 square root of the two compilers agrees
 (csrc/board_pose_math.h: pose_sqrt).  The layout, the camera, iterations, max_drop and the flag are scalars of a call, so their
 combinations are a handful of launches of at most 16 frames, each with every frame status (tests/board_pose_cases.py:
-gpu_batches).  Then the pose's predicted rows snapped on the caller's stream, the refused arguments, the recovery without a
+gpu_batches); the launches under the cameras "full" and "k3" decide the same for the k3 and tangential products, which under the
+other cameras are products with 0 or 1e-3, and the _wrap launches run spacing ratios 1, -0.5 and 0 on an id window that passes
+2^32.  Then the pose's predicted rows snapped on the caller's stream, the refused arguments, the recovery without a
 camera pinned to the bytes of board_fit's path, and the recovery with a camera on a frame seen through a barrel lens."""
 import numpy as np
 import pytest
@@ -78,12 +80,24 @@ def test_the_kernel_gives_the_host_forms_bytes(det, name):
 
 def test_predicted_rows_feed_the_snap_on_the_callers_stream(det):
     """A second launch, on the caller's stream: the pose's rows of the missing tags go to snap_points_enqueue as they stand."""
+    pose_then_snap(det, "barrel", 0)
+
+
+def test_predicted_rows_with_wrapped_ids_feed_the_snap(det):
+    """The same chain under camera "full" with the layout from 0xFFFFFFF0: the missing tags 0, 5, 17, 30, 35 have the ids
+    0xFFFFFFF0, 0xFFFFFFF5, 1, 14, 19, which a second kernel reads in place."""
+    want = pose_then_snap(det, "full", PC.WRAP_FIRST_ID)
+    for f in range(2):
+        assert want["pred"][f, :5]["id"].tolist() == [0xFFFFFFF0, 0xFFFFFFF5, 1, 14, 19]
+
+
+def pose_then_snap(det, camera, first_id):
     import torch
-    cam = PC.CAMERAS["barrel"]
+    cam = PC.CAMERAS[camera]
     R, t = PC.pose("near", 6, 6)
-    full = PC.exact_table(6, 6, range(36), cam, R, t, noise=0.1)
+    full = PC.exact_table(6, 6, range(36), cam, R, t, first_id=first_id, noise=0.1)
     keep = np.array([i for i in range(36) if i not in (0, 5, 17, 30, 35)])
-    b = PC.PoseBatch("snap", [full[keep], full[keep][::-1]], 6, 6, cam, max_drop=1, flags=PC.MISSING, tpf=36)
+    b = PC.PoseBatch("snap", [full[keep], full[keep][::-1]], 6, 6, cam, first_id=first_id, max_drop=1, flags=PC.MISSING, tpf=36)
     want = b.host()
     saddles = np.zeros((2, 144, 5), np.float32)  # the true corners of every tag as the frame's saddle list
     saddles[:, :, :2] = full["xy"].reshape(144, 2)
@@ -108,6 +122,7 @@ def test_predicted_rows_feed_the_snap_on_the_callers_stream(det):
         assert s_st == _ffi.AGX_SNAP_OK and int(sst[f]) == _ffi.AGX_SNAP_OK and int(nkept[f]) == len(s_rows) == 5
         assert np.array_equal(slots[f, :k].cpu().numpy().view(np.uint32), s_slots)
         assert np.array_equal(kept[f, :5].cpu().numpy().view(np.uint32), s_rows)
+    return want
 
 
 def test_refused_arguments_leave_the_batch_in_flight(det):
@@ -166,6 +181,21 @@ def test_recovery_without_a_camera_returns_todays_bytes(det):
     assert list(got[0]) == list(want) and fits[0]["H"].tobytes() == hfit["H"].tobytes() and "pose" not in fits[0]
     for t in want:
         assert np.array_equal(np.asarray(got[0][t], np.float32).view(np.uint32), want[t].view(np.uint32))
+
+
+def test_detect_recovered_on_a_board_whose_ids_start_at_100(det):
+    """first_id through detect_recovered, with and without a camera, on a rendered 6 x 6 frame printed with the ids 100 .. 135:
+    the tags and the fit equal the restatement over the host forms bit for bit."""
+    luma, saddles, tags, cam = PC.frame_from_100()
+    for camera in (None, cam):
+        got, fits = det.detect_recovered(dev(luma[None]), 6, 6, first_id=PC.FRAME_FIRST_ID, camera=camera, return_fit=True)
+        want, hfit = PC.recovered_host(luma, saddles, tags, 6, 6, camera=camera, first_id=PC.FRAME_FIRST_ID)
+        assert list(got[0]) == list(want) and sorted(want) == list(range(100, 136))
+        for t in want:
+            assert np.array_equal(np.asarray(got[0][t], np.float32).view(np.uint32), want[t].view(np.uint32)), t
+        assert fits[0]["status"] == hfit["status"] == OK and fits[0]["n_inliers"] == 36
+        key = "H" if camera is None else "pose"
+        assert fits[0][key].tobytes() == hfit[key].tobytes() and fits[0]["err_sq"].tobytes() == hfit["err_sq"].tobytes()
 
 
 def test_on_a_warped_frame_the_camera_recovers_strictly_more_tags(det):
