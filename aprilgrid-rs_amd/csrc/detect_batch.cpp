@@ -4,6 +4,12 @@
 // The host tail is the reference's exhaustive search (about a millisecond per frame and thread), so the
 // end-to-end rate is set by the number of host threads the process is granted; the pool keeps them busy
 // and the device work disappears behind them.
+//
+// The entry points -- agx_detect_batch with the host tail (detect_batch_impl) or the device tail (detect_batch_device_tail),
+// agx_detect_batch_enqueue[_to] / _fetch and a group's per-rank fetch (both through resolve_on_host) -- are each a chunk or
+// group loop over one set of pieces: choose_tail, device_luma, FrameResults (every per-frame rule and the call's return code),
+// HostTail (a frame's host tail as a pool task), SlotRing, read_tail_table and take_host_frames.  The two upload schedulers
+// stay inside their functions: they were measured separately (profiles/r6_upload_scheduling_ab.txt) and differ on purpose.
 #include <hip/hip_runtime_api.h>
 
 #include <sched.h>
@@ -330,6 +336,266 @@ static int fetch_tail(agx_detector *det, const agx_tag **tags, const uint32_t **
     return AGX_OK;
 }
 
+// ---- the pieces every detect-over-a-batch entry point is put together from ---------------------------------------------------
+// Which tail a call takes: 1 the device tail, 0 the host tail, < 0 the call's error.  Asked for (option "device_tail" 1): the
+// one-time set-up's failure (code list, 155 KB of LDS for the kernel) is the call's; left to choose: `by_size` decides, and a
+// failed set-up means the host tail, which needs nothing from the device.
+static int choose_tail(agx_detector *det, bool by_size)
+{
+    const int mode = device_tail_mode(det);
+    if (mode != 1 && !(mode == 2 && by_size)) return 0;
+    const int prc = tail_prepare(det);
+    if (prc && mode == 1) return prc;
+    return prc ? 0 : 1;
+}
+
+// The frames' u8 luma in device memory, as the kernels that decode from it read it (detector.rs:507): L8 frames are their own;
+// anything else is converted behind whatever is on the detector's stream (chunk_luma8, one slot of `capacity_frames`)
+struct DeviceLuma {
+    const uint8_t *d = nullptr;
+    size_t row = 0, frame = 0;
+};
+static int device_luma(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride, size_t frame_stride,
+                       int format, size_t capacity_frames, DeviceLuma &l)
+{
+    l.d = static_cast<const uint8_t *>(d_frames);
+    l.row = row_stride;
+    l.frame = frame_stride;
+    if (format == AGX_L8) return AGX_OK;
+    l.row = (size_t)width;
+    l.frame = (size_t)width * (size_t)height;
+    return chunk_luma8(det, d_frames, n_frames, width, height, row_stride, frame_stride, format, 0, 1, capacity_frames, nullptr, &l.d);
+}
+
+// The per-frame outcome of one call: where a frame's rows go, its count, its status, and what the call's return code is derived
+// from.  The calling thread and the pool's tasks write to it, each frame by one of them.
+class FrameResults {
+public:
+    // Rows at out + f * cap; counts and statuses straight into the caller's arrays (agx_detect_batch; status may be null) ...
+    FrameResults(agx_tag *out, uint32_t cap, uint32_t *counts, int *status) : out_(out), cap_(cap), counts_(counts), status_(status) {}
+    // ... or held here (the fetches: 0 and AGX_OK until a frame is stored, handed over once the call is known to have succeeded),
+    // and with `rows` the rows as well (_enqueue_to: bound for the caller's device arrays)
+    void hold(int n_frames, bool rows)
+    {
+        cnt_.assign((size_t)n_frames, 0u);
+        st_.assign((size_t)n_frames, AGX_OK);
+        if (rows) rows_.resize((size_t)n_frames);
+        counts_ = cnt_.data();
+        status_ = st_.data();
+    }
+    // Frame f has these tags.  More than cap: AGX_ERR_CAPACITY with the true count, and no row is written -- reported, never
+    // truncated.  tags == nullptr: the rows are where they belong already (_enqueue_to: k_publish_tags has put them there).
+    void store(int f, const agx_tag *tags, size_t n)
+    {
+        counts_[f] = (uint32_t)n;
+        int s = AGX_OK;
+        if (n > cap_) s = record(AGX_ERR_CAPACITY);
+        else if (tags && n && !rows_.empty()) rows_[(size_t)f].assign(tags, tags + n);
+        else if (tags && n) std::memcpy(out_ + (size_t)f * cap_, tags, n * sizeof(agx_tag));
+        if (status_) status_[f] = s;
+    }
+    // A list of frame f's chain overflowed with status s: no tags, that status -- reported, never truncated
+    void chain_overflowed(int f, int s)
+    {
+        counts_[f] = 0;
+        if (status_) status_[f] = record(s);
+    }
+    // Host memory ran out inside frame f's search: the call fails as a whole
+    void out_of_memory(int f)
+    {
+        counts_[f] = 0;
+        if (status_) status_[f] = AGX_ERR_NOMEM;
+        nomem_.store(true);
+    }
+    bool out_of_memory() const { return nomem_.load(); }
+    // The call's return code once every frame is in.  agx_detect_batch: the first status other than AGX_OK that was recorded ...
+    int first_recorded() const { return nomem_.load() ? AGX_ERR_NOMEM : first_bad_.load(); }
+    // ... the fetches: that of the lowest frame, as the held counts and statuses (those of the frames `only` marks; nullptr:
+    // all) go to the caller's arrays (either may be null)
+    int hand_over(uint32_t *counts, int *status, int n_frames, const char *only) const
+    {
+        int rc = AGX_OK;
+        for (int f = 0; f < n_frames; ++f) {
+            if (only && !only[f]) continue;
+            if (counts) counts[f] = cnt_[(size_t)f];
+            if (status) status[f] = st_[(size_t)f];
+            if (rc == AGX_OK) rc = st_[(size_t)f];
+        }
+        return rc;
+    }
+    // The call failed as a whole (not a frame's own status): no frame's result is valid -- every frame's slot says so, so that a
+    // caller who looks at the per-frame arrays only cannot mistake an untouched slot for "no tags"
+    static void fail_all(int rc, uint32_t *counts, int *status, int n_frames)
+    {
+        for (int f = 0; f < n_frames; ++f) {
+            if (counts) counts[f] = 0;
+            if (status) status[f] = rc;
+        }
+    }
+    uint32_t cap() const { return cap_; }
+    const uint32_t *counts() const { return counts_; }
+    const int *statuses() const { return status_; }
+    const std::vector<agx_tag> &held_rows(int f) const { return rows_[(size_t)f]; }
+
+private:
+    int record(int s)
+    {
+        int exp = AGX_OK;
+        first_bad_.compare_exchange_strong(exp, s);
+        return s;
+    }
+    agx_tag *out_;
+    uint32_t cap_;
+    uint32_t *counts_;
+    int *status_;
+    std::vector<uint32_t> cnt_;
+    std::vector<int> st_;
+    std::vector<std::vector<agx_tag>> rows_;
+    std::atomic<int> first_bad_{AGX_OK};
+    std::atomic<bool> nomem_{false};
+};
+
+// Buffers that pool tasks read, reused in turn: a slot is refilled when ITS tasks are done (a counter per slot) -- no barrier
+// over the pool between refills.
+class SlotRing {
+public:
+    static constexpr int kSlots = 4;
+    void wait_free(int r)
+    {
+        std::unique_lock<std::mutex> lk(m_);
+        cv_.wait(lk, [&] { return left_[r] == 0; });
+    }
+    // make(0) .. make(n - 1) onto the pool, each of which calls done(r) as its last act
+    template <class Make>
+    void submit(WorkerPool &pool, int r, int n, Make make)
+    {
+        {
+            std::lock_guard<std::mutex> lk(m_);
+            left_[r] = n;
+        }
+        int submitted = 0;
+        try {
+            for (; submitted < n; ++submitted) pool.submit(make(submitted));
+        } catch (...) {  // a task could not be queued: the slot's counter must not wait for tasks that will never run
+            std::lock_guard<std::mutex> lk(m_);
+            left_[r] -= n - submitted;
+            throw;
+        }
+    }
+    void done(int r)
+    {
+        bool last;
+        {
+            std::lock_guard<std::mutex> lk(m_);
+            last = --left_[r] == 0;
+        }
+        if (last) cv_.notify_all();
+    }
+
+private:
+    std::mutex m_;
+    std::condition_variable cv_;
+    int left_[kSlots] = {0, 0, 0, 0};  // tasks of the slot not finished yet (guarded by m_)
+};
+
+// The host tail of one frame as a pool task: board search + decode of its saddle list over its u8 luma -- `px` at `pitch`, which
+// is that luma (format AGX_L8: an L8 frame itself, or a plane converted on the device) or the caller's host frame in `format`,
+// run through the host's own to_luma8 first.  Nothing unwinds out of a worker thread: host memory exhaustion becomes the
+// frame's status.
+struct HostTail {
+    const FamilyInfo *fam;
+    int max_boards, f;
+    const agx_saddle *saddles;
+    uint32_t n_saddles;
+    const uint8_t *px;
+    size_t pitch;
+    int width, height, format;
+    FrameResults *res;
+    SlotRing *ring;  // with a ring: the slot whose buffers this task reads
+    int slot;
+    void operator()() const
+    {
+        try {
+            std::vector<uint8_t> grey;
+            const uint8_t *g = px;
+            size_t gstride = pitch;
+            if (format != AGX_L8) {
+                grey.resize((size_t)width * (size_t)height);
+                (void)luma8(px, width, height, pitch, format, grey.data());
+                g = grey.data();
+                gstride = (size_t)width;
+            }
+            const std::vector<agx_tag> &tags = detect_tail_scratch(*fam, max_boards, saddles, n_saddles, g, width, height, gstride);
+            res->store(f, tags.data(), tags.size());
+        } catch (...) {
+            res->out_of_memory(f);
+        }
+        if (ring) ring->done(slot);
+    }
+};
+
+// The device tail's table of n frames (table[4 f] count, table[4 f + 1] TAIL_* status), the first of which is the call's frame
+// f0: TAIL_OK frames are stored from `rows` (`stride` apart; nullptr: counts only); the others are the host tail's --
+// back[f] = 1, or 2 where the kernel handed the frame back as uncertain.  True if any frame was handed back.
+static bool read_tail_table(const uint32_t *table, const agx_tag *rows, uint32_t stride, int f0, int n, FrameResults &res, char *back)
+{
+    bool any = false;
+    for (int f = 0; f < n; ++f) {
+        const uint32_t st = table[4 * f + 1], nt = table[4 * f];
+        back[f] = st == TAIL_OK ? 0 : (st & TAIL_UNCERTAIN) ? 2 : 1;
+        // (the kernel was given min(cap, 128) as its limit and hands frames beyond it back; never truncated either way)
+        if (!back[f]) res.store(f0 + f, rows ? rows + (size_t)f * stride : nullptr, nt);
+        else any = true;
+    }
+    return any;
+}
+// AGX_TAIL_DEBUG: the table's status bits and the kernel's ticks per frame, to stderr
+static void print_tail_table(const uint32_t *table, int nf, int c0)
+{
+    int h[32] = {0};
+    for (int f = 0; f < nf; ++f)
+        for (int b = 0; b < 32; ++b) h[b] += (table[4 * f + 1] >> b) & 1u;
+    for (int b = 0; b < 32; ++b)
+        if (h[b]) std::fprintf(stderr, "tail status bit %d: %d frames\n", b, h[b]);
+    std::vector<std::pair<uint32_t, int>> tk;
+    double sum = 0;
+    for (int f = 0; f < nf; ++f) {
+        tk.push_back({table[4 * f + 2], f});
+        sum += table[4 * f + 2];
+    }
+    std::sort(tk.begin(), tk.end());
+    std::fprintf(stderr, "tail ticks per frame (100 MHz): mean %.0f median %u p90 %u max %u; slowest:", sum / nf, tk[(size_t)nf / 2].first,
+                 tk[(size_t)nf * 9 / 10].first, tk.back().first);
+    for (int i = 0; i < 5 && i < nf; ++i) {
+        const int f = tk[(size_t)(nf - 1 - i)].second;
+        std::fprintf(stderr, " [frame %d: %u ticks, %u saddles, %u seeds, %u tags]", c0 + f, table[4 * f + 2], table[4 * f + 3] & 0xffff, table[4 * f + 3] >> 16, table[4 * f]);
+    }
+    std::fprintf(stderr, "\n");
+}
+
+// Of the n frames from the call's frame f0 on that `back` marks (nullptr: every frame), given their chain statuses: a frame
+// whose list overflowed is reported; the others are the host tail's -- appended to host_frames (counted from f0) and, with
+// `stats` (the device tail handed them back), counted as fallbacks, those marked 2 as uncertain.
+struct TailStats {
+    int fallback = 0, uncertain = 0;
+};
+static void take_host_frames(const char *back, const int *chain_status, int f0, int n, FrameResults &res, std::vector<int> &host_frames,
+                             TailStats *stats)
+{
+    for (int f = 0; f < n; ++f) {
+        if (back && !back[f]) continue;
+        if (chain_status[f] != AGX_OK) {
+            res.chain_overflowed(f0 + f, chain_status[f]);
+            continue;
+        }
+        if (stats) {
+            ++stats->fallback;
+            stats->uncertain += back && back[f] == 2;
+        }
+        host_frames.push_back(f);
+    }
+}
+
 }  // namespace agx
 
 using namespace agx;
@@ -417,29 +683,23 @@ extern "C" int agx_host_parallelism(void)
     }
 }
 
-static int detect_batch_impl(agx_detector *det, const void *frames, const void *d_frames, int n_frames, int width,
-                             int height, size_t row_stride_bytes, size_t frame_stride_bytes, int format, agx_tag *out,
-                             uint32_t cap_per_frame, uint32_t *counts, int *frame_status, int n_threads);
+static int detect_batch_impl(agx_detector *det, const void *frames, const void *d_frames, int n_frames, int width, int height,
+                             size_t row_stride_bytes, size_t frame_stride_bytes, int format, FrameResults &res, int n_threads);
 
 extern "C" int agx_detect_batch(agx_detector *det, const void *frames, const void *d_frames, int n_frames, int width,
                                 int height, size_t row_stride_bytes, size_t frame_stride_bytes, int format, agx_tag *out,
                                 uint32_t cap_per_frame, uint32_t *counts, int *frame_status, int n_threads)
 {
-    int rc;
+    int rc = AGX_ERR_ARG;
     try {
-        rc = detect_batch_impl(det, frames, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, out,
-                               cap_per_frame, counts, frame_status, n_threads);
+        FrameResults res(out, cap_per_frame, counts, frame_status);
+        if (counts && (out || !cap_per_frame))
+            rc = detect_batch_impl(det, frames, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, res, n_threads);
     } catch (...) {  // (the worker pool could not be created: nothing has run)
         rc = AGX_ERR_NOMEM;
     }
-    // A failure of the call as a whole (not a frame's own capacity status): no frame's result is valid -- say so in every
-    // frame's slot, so that a caller who looks at the per-frame arrays only cannot mistake an untouched slot for "no tags"
-    if (rc != AGX_OK && rc != AGX_ERR_CAPACITY && counts && n_frames > 0) {
-        for (int f = 0; f < n_frames; ++f) {
-            counts[f] = 0;
-            if (frame_status) frame_status[f] = rc;
-        }
-    }
+    // (AGX_ERR_CAPACITY is a frame's own status: the other frames' results stand)
+    if (rc != AGX_OK && rc != AGX_ERR_CAPACITY && counts && n_frames > 0) FrameResults::fail_all(rc, counts, frame_status, n_frames);
     return rc;
 }
 
@@ -448,11 +708,8 @@ extern "C" int agx_detect_batch(agx_detector *det, const void *frames, const voi
 // hands back -- an angle comparison inside its guard band, a list beyond its fixed sizes -- take the host tail on the
 // pool, as every frame does without the option: the results are the host tail's either way.
 static int detect_batch_device_tail(agx_detector *det, const void *frames, const void *d_frames, int n_frames, int width, int height,
-                                    size_t row_stride_bytes, size_t frame_stride_bytes, int format, agx_tag *out,
-                                    uint32_t cap_per_frame, uint32_t *counts, int *frame_status, WorkerPool *pool)
+                                    size_t row_stride_bytes, size_t frame_stride_bytes, int format, FrameResults &res, WorkerPool *pool)
 {
-    const FamilyInfo *fam = &det->fam;
-    const int max_boards = det->params.max_num_of_boards;
     const int device = det->device;
     constexpr int S = AGX_UPLOAD_STREAMS;
     // A frame's search occupies a workgroup of eight waves for two to five milliseconds (frames whose first seed does not
@@ -472,10 +729,9 @@ static int detect_batch_device_tail(agx_detector *det, const void *frames, const
     std::mutex m;
     std::condition_variable cv;
     std::vector<int> uploaded;  // per chunk: 0 pending, 1 on the device, -1 failed   (guarded by m)
-    std::atomic<int> first_bad{AGX_OK};
-    std::atomic<bool> nomem{false};
     std::deque<std::vector<agx_saddle>> handed_back;  // saddle lists of frames for the host tail (alive until the pool is drained)
-    int rc = AGX_OK, n_fallback = 0, n_uncertain = 0;
+    TailStats stats;
+    int rc = AGX_OK;
     bool pending_batch = false;
     // A chunk goes up in P parts on P workers at once (a copy from pageable memory is staged by the calling thread at 10 .. 15 GB/s:
     // it takes four to six of them to fill the link), the chunks one after the other (three large chunks side by side would
@@ -550,7 +806,8 @@ static int detect_batch_device_tail(agx_detector *det, const void *frames, const
     if (!d_frames) release_chunks(std::min(S, n_chunks));
     const int tail_debug = tuning_env("AGX_TAIL_DEBUG", 0);  // (as read when the handle was created)
     std::vector<uint32_t> ns, offs;
-    std::vector<int> fst;
+    std::vector<int> fst, host_frames;
+    std::vector<char> back;
     for (int ci = 0; ci < n_chunks; ++ci) {
         const int c0 = ci * chunk, nf = std::min(chunk, n_frames - c0);
         const uint8_t *h_chunk = (const uint8_t *)frames + (size_t)c0 * frame_stride_bytes;
@@ -566,62 +823,19 @@ static int detect_batch_device_tail(agx_detector *det, const void *frames, const
         rc = agx_saddles_batch_enqueue(det, d_chunk, nf, width, height, row_stride_bytes, frame_stride_bytes, format);
         if (rc) break;
         pending_batch = true;
-        const uint8_t *d_luma = static_cast<const uint8_t *>(d_chunk);  // detector.rs:507: L8 frames are their own u8 luma
-        size_t luma_row = row_stride_bytes, luma_frame = frame_stride_bytes;
-        if (format != AGX_L8) {
-            rc = chunk_luma8(det, d_chunk, nf, width, height, row_stride_bytes, frame_stride_bytes, format, 0, 1, (size_t)chunk, nullptr, &d_luma);
-            if (rc) break;
-            luma_row = (size_t)width;
-            luma_frame = (size_t)width * (size_t)height;
-        }
-        rc = enqueue_tail(det, d_luma, luma_row, luma_frame, std::max(cap_per_frame, 1u), false);
+        DeviceLuma luma;
+        rc = device_luma(det, d_chunk, nf, width, height, row_stride_bytes, frame_stride_bytes, format, (size_t)chunk, luma);
+        if (rc) break;
+        rc = enqueue_tail(det, luma.d, luma.row, luma.frame, std::max(res.cap(), 1u), false);
         if (rc) break;
         const agx_tag *tags = nullptr;
         const uint32_t *table = nullptr;
         uint32_t tag_cap = 0;
         rc = fetch_tail(det, &tags, &table, &tag_cap);  // waits for the device
         if (rc) break;
-        bool any_back = false;
-        if (tail_debug) {
-            int h[32] = {0};
-            for (int f = 0; f < nf; ++f)
-                for (int b = 0; b < 32; ++b) h[b] += (table[4 * f + 1] >> b) & 1u;
-            for (int b = 0; b < 32; ++b)
-                if (h[b]) std::fprintf(stderr, "tail status bit %d: %d frames\n", b, h[b]);
-            std::vector<std::pair<uint32_t, int>> tk;
-            double sum = 0;
-            for (int f = 0; f < nf; ++f) {
-                tk.push_back({table[4 * f + 2], f});
-                sum += table[4 * f + 2];
-            }
-            std::sort(tk.begin(), tk.end());
-            std::fprintf(stderr, "tail ticks per frame (100 MHz): mean %.0f median %u p90 %u max %u; slowest:", sum / nf, tk[(size_t)nf / 2].first,
-                         tk[(size_t)nf * 9 / 10].first, tk.back().first);
-            for (int i = 0; i < 5 && i < nf; ++i) {
-                const int f = tk[(size_t)(nf - 1 - i)].second;
-                std::fprintf(stderr, " [frame %d: %u ticks, %u saddles, %u seeds, %u tags]", c0 + f, table[4 * f + 2], table[4 * f + 3] & 0xffff, table[4 * f + 3] >> 16, table[4 * f]);
-            }
-            std::fprintf(stderr, "\n");
-        }
-        for (int f = 0; f < nf; ++f) {
-            const int gf = c0 + f;
-            const uint32_t st = table[4 * f + 1], nt = table[4 * f];
-            if (st != TAIL_OK) {
-                any_back = true;
-                continue;
-            }
-            counts[gf] = nt;
-            int stf = AGX_OK;
-            if (nt > cap_per_frame) {  // (the kernel was given min(cap_per_frame, 128) as its limit and hands frames beyond it back)
-                stf = AGX_ERR_CAPACITY;
-                int exp = AGX_OK;
-                first_bad.compare_exchange_strong(exp, stf);
-            } else if (nt) {
-                std::memcpy(out + (size_t)gf * cap_per_frame, tags + (size_t)f * tag_cap, (size_t)nt * sizeof(agx_tag));
-            }
-            if (frame_status) frame_status[gf] = stf;
-        }
-        if (any_back) {
+        if (tail_debug) print_tail_table(table, nf, c0);
+        back.resize((size_t)nf);
+        if (read_tail_table(table, tags, tag_cap, c0, nf, res, back.data())) {
             // the saddle lists of the frames handed back (and the status of frames whose chain overflowed)
             ns.resize((size_t)nf);
             offs.resize((size_t)nf);
@@ -630,49 +844,13 @@ static int detect_batch_device_tail(agx_detector *det, const void *frames, const
             rc = fetch_compact(det, &records, ns.data(), offs.data(), fst.data());
             pending_batch = false;
             if (rc) break;
-            for (int f = 0; f < nf; ++f) {
-                if (table[4 * f + 1] == TAIL_OK) continue;
-                const int gf = c0 + f;
-                if (fst[(size_t)f] != AGX_OK) {  // reported, never truncated
-                    counts[gf] = 0;
-                    if (frame_status) frame_status[gf] = fst[(size_t)f];
-                    int exp = AGX_OK;
-                    first_bad.compare_exchange_strong(exp, fst[(size_t)f]);
-                    continue;
-                }
-                ++n_fallback;
-                n_uncertain += (table[4 * f + 1] & TAIL_UNCERTAIN) != 0;
+            host_frames.clear();
+            take_host_frames(back.data(), fst.data(), c0, nf, res, host_frames, &stats);
+            for (const int f : host_frames) {  // (an L16 / colour frame: to_luma8 of the caller's frame, on the host this time)
                 handed_back.emplace_back(records + offs[(size_t)f], records + offs[(size_t)f] + ns[(size_t)f]);
-                const std::vector<agx_saddle> *list = &handed_back.back();
-                const uint8_t *img = h_chunk + (size_t)f * frame_stride_bytes;
-                pool->submit([=, &first_bad, &nomem] {
-                    try {
-                        std::vector<uint8_t> grey;  // to_luma8 of an L16 / RGB8 frame, on the host this time
-                        const uint8_t *g = img;
-                        size_t gstride = row_stride_bytes;
-                        if (format != AGX_L8) {
-                            grey.resize((size_t)width * (size_t)height);
-                            (void)luma8(img, width, height, row_stride_bytes, format, grey.data());
-                            g = grey.data();
-                            gstride = (size_t)width;
-                        }
-                        const std::vector<agx_tag> &tg = detect_tail_scratch(*fam, max_boards, list->data(), list->size(), g, width, height, gstride);
-                        int stf = AGX_OK;
-                        counts[gf] = (uint32_t)tg.size();
-                        if (tg.size() > cap_per_frame) {
-                            stf = AGX_ERR_CAPACITY;
-                            int exp = AGX_OK;
-                            first_bad.compare_exchange_strong(exp, stf);
-                        } else if (!tg.empty()) {
-                            std::memcpy(out + (size_t)gf * cap_per_frame, tg.data(), tg.size() * sizeof(agx_tag));
-                        }
-                        if (frame_status) frame_status[gf] = stf;
-                    } catch (...) {
-                        counts[gf] = 0;
-                        if (frame_status) frame_status[gf] = AGX_ERR_NOMEM;
-                        nomem.store(true);
-                    }
-                });
+                const std::vector<agx_saddle> &list = handed_back.back();
+                pool->submit(HostTail{&det->fam, det->params.max_num_of_boards, c0 + f, list.data(), (uint32_t)list.size(),
+                                      h_chunk + (size_t)f * frame_stride_bytes, row_stride_bytes, width, height, format, &res, nullptr, 0});
             }
         } else {
             abandon_batch(det);  // (the stream is idle: the batch is done with)
@@ -690,17 +868,14 @@ static int detect_batch_device_tail(agx_detector *det, const void *frames, const
     }
     (void)pool->wait();
     if (pending_batch) abandon_batch(det);
-    set_tail_stats(det, n_frames, n_fallback, n_uncertain);
-    if (rc) return rc;
-    if (nomem.load()) return AGX_ERR_NOMEM;
-    return first_bad.load();
+    set_tail_stats(det, n_frames, stats.fallback, stats.uncertain);
+    return rc ? rc : res.first_recorded();
 }
 
-static int detect_batch_impl(agx_detector *det, const void *frames, const void *d_frames, int n_frames, int width,
-                             int height, size_t row_stride_bytes, size_t frame_stride_bytes, int format, agx_tag *out,
-                             uint32_t cap_per_frame, uint32_t *counts, int *frame_status, int n_threads)
+static int detect_batch_impl(agx_detector *det, const void *frames, const void *d_frames, int n_frames, int width, int height,
+                             size_t row_stride_bytes, size_t frame_stride_bytes, int format, FrameResults &res, int n_threads)
 {
-    if (!det || !frames || !counts || n_frames <= 0 || (!out && cap_per_frame)) return AGX_ERR_ARG;
+    if (!det || !frames || n_frames <= 0) return AGX_ERR_ARG;  // (agx_detect_batch has looked at the result arrays)
     const size_t bpp = (size_t)format_px_bytes(format);
     if (!bpp || format == AGX_LF32) return AGX_ERR_FORMAT;  // the tail derives to_luma8 itself: every integer format
     if (width < 2 || height < 2) return AGX_ERR_ARG;
@@ -715,24 +890,16 @@ static int detect_batch_impl(agx_detector *det, const void *frames, const void *
     if (n_threads <= 0) n_threads = agx_host_parallelism();
     WorkerPool *pool = worker_pool(det, n_threads);
     if (!pool) return AGX_ERR_ARG;
-    const FamilyInfo *fam = &det->fam;
-    const int max_boards = det->params.max_num_of_boards;
     if (hipSetDevice(det->device) != hipSuccess) return AGX_ERR_HIP;
     const int device = det->device;
     // The device tail costs a launch whose length is its slowest frame's (1.5 .. 3.5 ms) whatever the batch; the host tail costs
     // ~0.9 ms per frame and thread.  Measured on 16 threads the two meet at ~60 frames (1: 1.0 / 1.7 ms, 16: 2.1 / 3.6,
     // 48: 4.3 / 4.4, 64: 4.6 / 4.7, 96: 6.8 / 5.3, 128: 8.9 / 6.0, 256: 15.7 / 8.5): left to choose, a call of fewer than four
     // frames per host thread keeps the host tail.
-    const int tail_mode = device_tail_mode(det);
-    bool on_device = tail_mode == 1 || (tail_mode == 2 && n_frames >= 4 * pool->size());
-    if (on_device) {  // the one-time set-up (code list, 155 KB of LDS for the kernel): asked for -> its failure is the call's;
-        const int prc = tail_prepare(det);  // left to choose -> the host tail, which needs nothing from the device
-        if (prc && tail_mode == 1) return prc;
-        if (prc) on_device = false;
-    }
+    const int on_device = choose_tail(det, n_frames >= 4 * pool->size());
+    if (on_device < 0) return on_device;
     if (on_device)
-        return detect_batch_device_tail(det, frames, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, out,
-                                        cap_per_frame, counts, frame_status, pool);
+        return detect_batch_device_tail(det, frames, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, res, pool);
     set_tail_stats(det, 0, 0, 0);  // ("last_device_tail_frames" 0: this call's tails run on the host)
 
     // Chunks of about one frame per worker (8 .. 64): the chain of a chunk takes 0.1 ms on the device, a frame's board
@@ -760,13 +927,13 @@ static int detect_batch_impl(agx_detector *det, const void *frames, const void *
         std::vector<uint32_t> ns, offs;
         std::vector<int> fst;
     };
+    static_assert(R <= SlotRing::kSlots, "a counter per slot");
     std::vector<Slot> slots((size_t)R);
+    SlotRing ring;
+    std::vector<int> host_frames;
     std::mutex m;
     std::condition_variable cv;
     std::vector<int> uploaded;   // per chunk: 0 pending, 1 on the device, -1 failed        (guarded by m)
-    int outstanding[R] = {0, 0, 0, 0};  // tails of the slot's chunk not finished yet        (guarded by m)
-    std::atomic<int> first_bad{AGX_OK};
-    std::atomic<bool> nomem{false};
     int rc = AGX_OK;
     bool pending_batch = false;  // a chunk is enqueued on the detector and not fetched yet
     auto upload_task = [&, device](int ci) {
@@ -792,10 +959,11 @@ static int detect_batch_impl(agx_detector *det, const void *frames, const void *
         const int c0 = ci * chunk, nf = std::min(chunk, n_frames - c0), r = ci % R;
         const uint8_t *h_chunk = (const uint8_t *)frames + (size_t)c0 * frame_stride_bytes;
         const void *d_chunk;
-        {
+        ring.wait_free(r);
+        if (!d_frames) {
             std::unique_lock<std::mutex> lk(m);
-            cv.wait(lk, [&] { return outstanding[r] == 0 && (d_frames || uploaded[(size_t)ci] != 0); });
-            if (!d_frames && uploaded[(size_t)ci] < 0) { rc = AGX_ERR_HIP; break; }
+            cv.wait(lk, [&] { return uploaded[(size_t)ci] != 0; });
+            if (uploaded[(size_t)ci] < 0) { rc = AGX_ERR_HIP; break; }
         }
         if (d_frames) d_chunk = (const uint8_t *)d_frames + (size_t)c0 * frame_stride_bytes;
         else d_chunk = d_stage + (size_t)(ci % S) * chunk_bytes;
@@ -823,70 +991,25 @@ static int detect_batch_impl(agx_detector *det, const void *frames, const void *
         for (int f = 0; f < nf; ++f)
             if (sl.fst[(size_t)f] == AGX_OK) total = std::max(total, (size_t)sl.offs[(size_t)f] + sl.ns[(size_t)f]);
         sl.saddles.assign(records, records + total);  // (the detector's mirror is overwritten by the next chunk)
-        int n_tasks = 0;
-        for (int f = 0; f < nf; ++f) n_tasks += sl.fst[(size_t)f] == AGX_OK;
-        {
-            std::lock_guard<std::mutex> lk(m);
-            outstanding[r] = n_tasks;
-        }
-        int submitted = 0;
-        try {
-        for (int f = 0; f < nf; ++f) {
-            const int gf = c0 + f;
-            if (sl.fst[(size_t)f] != AGX_OK) {  // reported, never truncated
-                counts[gf] = 0;
-                if (frame_status) frame_status[gf] = sl.fst[(size_t)f];
-                int exp = AGX_OK;
-                first_bad.compare_exchange_strong(exp, sl.fst[(size_t)f]);
-                continue;
+        host_frames.clear();
+        take_host_frames(nullptr, sl.fst.data(), c0, nf, res, host_frames, nullptr);
+        ring.submit(*pool, r, (int)host_frames.size(), [&](int i) {
+            const int f = host_frames[(size_t)i];
+            HostTail t{&det->fam, det->params.max_num_of_boards, c0 + f, sl.saddles.data() + sl.offs[(size_t)f], sl.ns[(size_t)f],
+                       h_chunk + (size_t)f * frame_stride_bytes, row_stride_bytes, width, height, AGX_L8, &res, &ring, r};  // L8: the frame itself, at its own pitch
+            if (h_luma) {
+                t.px = h_luma + (size_t)f * (size_t)width * (size_t)height;
+                t.pitch = (size_t)width;
             }
-            const agx_saddle *sp = sl.saddles.data() + sl.offs[(size_t)f];
-            const uint32_t n_s = sl.ns[(size_t)f];
-            const uint8_t *img = h_chunk + (size_t)f * frame_stride_bytes;
-            const uint8_t *dev_grey = h_luma ? h_luma + (size_t)f * (size_t)width * (size_t)height : nullptr;
-            pool->submit([=, &first_bad, &nomem, &m, &cv, &outstanding] {
-              try {  // nothing unwinds out of a worker thread: host memory exhaustion becomes the frame's status
-                const uint8_t *g = dev_grey ? dev_grey : img;  // L8: the frame itself, read at its own pitch
-                const size_t gstride = dev_grey ? (size_t)width : row_stride_bytes;
-                const std::vector<agx_tag> &tags = detect_tail_scratch(*fam, max_boards, sp, n_s, g, width, height, gstride);
-                int stf = AGX_OK;
-                counts[gf] = (uint32_t)tags.size();
-                if (tags.size() > cap_per_frame) {
-                    stf = AGX_ERR_CAPACITY;
-                    int exp = AGX_OK;
-                    first_bad.compare_exchange_strong(exp, stf);
-                } else if (!tags.empty()) {
-                    std::memcpy(out + (size_t)gf * cap_per_frame, tags.data(), tags.size() * sizeof(agx_tag));
-                }
-                if (frame_status) frame_status[gf] = stf;
-              } catch (...) {  // host memory exhausted inside this frame's search: the call fails as a whole
-                counts[gf] = 0;
-                if (frame_status) frame_status[gf] = AGX_ERR_NOMEM;
-                nomem.store(true);
-              }
-              bool last;
-              {
-                  std::lock_guard<std::mutex> lk(m);
-                  last = --outstanding[r] == 0;
-              }
-              if (last) cv.notify_all();
-            });
-            ++submitted;
-        }
-        } catch (...) {  // a task could not be queued: the slot's counter must not wait for tails that will never run
-            std::lock_guard<std::mutex> lk(m);
-            outstanding[r] -= n_tasks - submitted;
-            throw;
-        }
+            return t;
+        });
     }
     } catch (...) {
         rc = AGX_ERR_NOMEM;  // host memory exhausted on this thread
     }
     (void)pool->wait();  // every tail and every upload still queued (an upload may be reading the caller's frames)
     if (pending_batch) abandon_batch(det);  // an error between enqueue and fetch: no stale batch is left to be fetched later
-    if (rc) return rc;
-    if (nomem.load()) return AGX_ERR_NOMEM;
-    return first_bad.load();
+    return rc ? rc : res.first_recorded();
 }
 
 // ---- agx_detect_batch_enqueue / _enqueue_to / agx_detect_batch_fetch: detect over a batch resident in device memory ---------
@@ -901,23 +1024,13 @@ int agx::detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_fram
     const bool to_device = results != RESULTS_HOST;  // the tail's rows and table stay in device memory (SB_DTAGS + SB_DTABLE)
     // option "device_tail" -1 (default) or 1: the device tail wherever this process may use it (no batch-size rule: with the frames
     // on the device there is no upload for the host tail to hide behind); 0, or a tail this process may not use: the host tail
-    const int tail_mode = device_tail_mode(det);
-    bool on_device = tail_mode != 0;
-    if (on_device) {
-        const int prc = tail_prepare(det);
-        if (prc && tail_mode == 1) return prc;
-        if (prc) on_device = false;
-    }
+    const int on_device = choose_tail(det, true);
+    if (on_device < 0) return on_device;
     int rc = agx_saddles_batch_enqueue(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format);
     if (rc) return rc;
-    const uint8_t *d_luma = static_cast<const uint8_t *>(d_frames);  // detector.rs:507: L8 frames are their own u8 luma
-    size_t luma_row = row_stride_bytes, luma_frame = frame_stride_bytes;
-    if (format != AGX_L8) {
-        rc = chunk_luma8(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, 0, 1, (size_t)n_frames, nullptr, &d_luma);
-        luma_row = (size_t)width;
-        luma_frame = (size_t)width * (size_t)height;
-    }
-    if (!rc && on_device) rc = enqueue_tail(det, d_luma, luma_row, luma_frame, std::max(cap_per_frame, 1u), to_device);
+    DeviceLuma luma;
+    rc = device_luma(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, (size_t)n_frames, luma);
+    if (!rc && on_device) rc = enqueue_tail(det, luma.d, luma.row, luma.frame, std::max(cap_per_frame, 1u), to_device);
     if (!rc && results == RESULTS_GROUP) {
         // a group's batch: d_counts = the packed frame table [n_frames][4], d_tags = the slab (group.cpp owns both).  Without
         // the device tail no pack kernel runs: the group fills the table with "handed back" itself
@@ -938,14 +1051,14 @@ int agx::detect_enqueue_impl(agx_detector *det, const void *d_frames, int n_fram
     det->batch = BATCH_DETECT;  // (over the chain's BATCH_SADDLES)
     DetectPending &p = det->detect;
     p.results = results;
-    p.device_tail = on_device;
+    p.device_tail = on_device != 0;
     p.n_frames = n_frames;
     p.width = width;
     p.height = height;
     p.cap = cap_per_frame;
-    p.d_luma = d_luma;
-    p.luma_row = luma_row;
-    p.luma_frame = luma_frame;
+    p.d_luma = luma.d;
+    p.luma_row = luma.row;
+    p.luma_frame = luma.frame;
     p.d_tags = d_tags;
     p.d_counts = d_counts;
     p.d_status = d_status;
@@ -978,14 +1091,9 @@ int agx::decode_quads_enqueue_impl(agx_detector *det, const void *d_frames, int 
     HIP_TRY(det, hipSetDevice(det->device));
     begin_batch(det);  // (SB_LUMA_D may grow below: nothing points into it any more)
     if (tail_prepare(det)) return fail(det, AGX_ERR_HIP, "hipMalloc / hipMemcpy: the family's code list");
-    const uint8_t *d_luma = static_cast<const uint8_t *>(d_frames);  // detector.rs:507: L8 frames are their own u8 luma
-    size_t luma_row = row_stride_bytes, luma_frame = frame_stride_bytes;
-    if (format != AGX_L8) {
-        if (chunk_luma8(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, 0, 1, (size_t)n_frames, nullptr, &d_luma))
-            return fail(det, AGX_ERR_HIP, "to_luma8 of the frames on the device");
-        luma_row = (size_t)width;
-        luma_frame = (size_t)width * (size_t)height;
-    }
+    DeviceLuma luma;
+    if (device_luma(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, (size_t)n_frames, luma))
+        return fail(det, AGX_ERR_HIP, "to_luma8 of the frames on the device");
     int results = RESULTS_CALLER;
     if (!d_tags) {
         d_tags = static_cast<agx_tag *>(side_ensure(det, SB_DECODE_TAGS, slots * sizeof(agx_tag), 0));
@@ -995,9 +1103,9 @@ int agx::decode_quads_enqueue_impl(agx_detector *det, const void *d_frames, int 
         results = RESULTS_HOST;
     }
     DecodeQuadsArgs q{};
-    q.luma = d_luma;
-    q.luma_frame_stride = (long long)luma_frame;
-    q.luma_row_stride = (int)luma_row;
+    q.luma = luma.d;
+    q.luma_frame_stride = (long long)luma.frame;
+    q.luma_row_stride = (int)luma.row;
     q.W = width;
     q.H = height;
     q.n_frames = n_frames;
@@ -1178,18 +1286,13 @@ int agx::bit_code_enqueue_impl(agx_detector *det, const void *d_frames, int n_fr
     if ((size_t)n_frames * quads_per_frame >= ((size_t)1 << 29)) return fail(det, AGX_ERR_ARG, "at most 2^29 - 1 slots per batch");
     HIP_TRY(det, hipSetDevice(det->device));
     begin_batch(det);  // (SB_LUMA_D may grow below: nothing points into it any more)
-    const uint8_t *d_luma = static_cast<const uint8_t *>(d_frames);  // detector.rs:507: L8 frames are their own u8 luma
-    size_t luma_row = row_stride_bytes, luma_frame = frame_stride_bytes;
-    if (format != AGX_L8) {
-        if (chunk_luma8(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, 0, 1, (size_t)n_frames, nullptr, &d_luma))
-            return fail(det, AGX_ERR_HIP, "to_luma8 of the frames on the device");
-        luma_row = (size_t)width;
-        luma_frame = (size_t)width * (size_t)height;
-    }
+    DeviceLuma luma;
+    if (device_luma(det, d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, (size_t)n_frames, luma))
+        return fail(det, AGX_ERR_HIP, "to_luma8 of the frames on the device");
     BitCodeArgs b{};
-    b.luma = d_luma;
-    b.luma_frame_stride = (long long)luma_frame;
-    b.luma_row_stride = (int)luma_row;
+    b.luma = luma.d;
+    b.luma_frame_stride = (long long)luma.frame;
+    b.luma_row_stride = (int)luma.row;
     b.W = width;
     b.H = height;
     b.n_frames = n_frames;
@@ -1780,23 +1883,16 @@ int agx::snap_points_enqueue_impl(agx_detector *det, const void *d_saddles, size
 
 // The host tail of the frames `back` marks (1 handed back, 2 handed back as uncertain; without the device tail: every frame) of
 // the batch `b` in flight on `det`, on the pool: from the chain's compact saddle lists and those frames' u8 luma, copied down
-// from the device a group at a time.  cnt / st [n] get those frames' counts and statuses (a list of the chain overflowed: 0,
-// AGX_ERR_CAPACITY -- reported, never truncated); their rows go to out + f * cap or, with `rows` (results bound for device
-// arrays), into (*rows)[k] for host_frames[k].  Every tail has finished when this returns, whatever it returns.
-static int resolve_on_host(agx_detector *det, const DetectPending &b, const std::vector<char> &back, WorkerPool *pool, agx_tag *out,
-                           std::vector<uint32_t> &cnt, std::vector<int> &st, std::vector<int> &host_frames,
-                           std::vector<std::vector<agx_tag>> *rows, int &n_fallback, int &n_uncertain)
+// from the device a group at a time.  `res` gets those frames' results (a list of the chain overflowed: reported, never truncated
+// -- _enqueue_to: k_publish_tags has said so already), host_frames the frames whose tail ran here.  Every tail has finished when
+// this returns, whatever it returns.
+static int resolve_on_host(agx_detector *det, const DetectPending &b, const std::vector<char> &back, WorkerPool *pool, FrameResults &res,
+                           std::vector<int> &host_frames, TailStats &stats)
 {
     const int n = b.n_frames, W = b.width, H = b.height;
-    const uint32_t cap = b.cap;
     const size_t plane = (size_t)W * (size_t)H;
     hipStream_t stream = det->stream;
-    const FamilyInfo *fam = &det->fam;
-    const int max_boards = det->params.max_num_of_boards;
-    std::mutex m;
-    std::condition_variable cv;
-    int outstanding[2] = {0, 0};  // host tails of the frames in luma slot r not finished yet (guarded by m)
-    std::atomic<bool> nomem{false};
+    SlotRing ring;  // (two slots of luma)
     int rc = AGX_OK;
     try {
         do {
@@ -1807,22 +1903,9 @@ static int resolve_on_host(agx_detector *det, const DetectPending &b, const std:
             const agx_saddle *records = nullptr;
             rc = fetch_compact(det, &records, ns.data(), offs.data(), fst.data());
             if (rc) break;
-            for (int f = 0; f < n; ++f) {
-                if (!back[(size_t)f]) continue;
-                if (fst[(size_t)f] != AGX_OK) {  // reported, never truncated (_enqueue_to: k_publish_tags has said so already)
-                    cnt[(size_t)f] = 0;
-                    st[(size_t)f] = fst[(size_t)f];
-                    continue;
-                }
-                if (b.device_tail) {
-                    ++n_fallback;
-                    n_uncertain += back[(size_t)f] == 2;
-                }
-                host_frames.push_back(f);
-            }
+            take_host_frames(back.data(), fst.data(), 0, n, res, host_frames, b.device_tail ? &stats : nullptr);
             const int n_host = (int)host_frames.size();
             if (!n_host) break;
-            if (rows) rows->resize((size_t)n_host);
             // their u8 luma, copied down a group at a time into one of two pinned slots while the previous group's tails run
             const int G = std::min(n_host, std::max(8, std::min(32, 2 * pool->size())));
             const int n_slots = n_host > G ? 2 : 1;
@@ -1831,59 +1914,25 @@ static int resolve_on_host(agx_detector *det, const DetectPending &b, const std:
             if (!h_luma) { rc = AGX_ERR_HIP; break; }
             for (int c0 = 0, ci = 0; c0 < n_host && !rc; c0 += G, ++ci) {
                 const int nc = std::min(G, n_host - c0), r = ci % n_slots;
-                {
-                    std::unique_lock<std::mutex> lk(m);
-                    cv.wait(lk, [&] { return outstanding[r] == 0; });
-                }
+                ring.wait_free(r);
                 uint8_t *slot = h_luma + (size_t)r * (size_t)G * plane;
                 bool ok = true;
                 for (int i = 0; i < nc && ok; ++i)
                     ok = hipMemcpy2DAsync(slot + (size_t)i * plane, (size_t)W, b.d_luma + (size_t)host_frames[(size_t)(c0 + i)] * b.luma_frame,
                                           b.luma_row, (size_t)W, (size_t)H, hipMemcpyDeviceToHost, stream) == hipSuccess;
                 if (!ok || hipStreamSynchronize(stream) != hipSuccess) { rc = AGX_ERR_HIP; break; }
-                {
-                    std::lock_guard<std::mutex> lk(m);
-                    outstanding[r] = nc;
-                }
-                int submitted = 0;
-                try {
-                    for (int i = 0; i < nc; ++i, ++submitted) {
-                        const int k = c0 + i, f = host_frames[(size_t)k];
-                        const uint8_t *g = slot + (size_t)i * plane;
-                        const agx_saddle *sp = records + offs[(size_t)f];
-                        const uint32_t n_s = ns[(size_t)f];
-                        pool->submit([=, &cnt, &st, &nomem, &m, &cv, &outstanding] {
-                            try {  // nothing unwinds out of a worker thread: host memory exhaustion becomes the frame's status
-                                const std::vector<agx_tag> &tg = detect_tail_scratch(*fam, max_boards, sp, n_s, g, W, H, (size_t)W);
-                                cnt[(size_t)f] = (uint32_t)tg.size();
-                                if (tg.size() > cap) st[(size_t)f] = AGX_ERR_CAPACITY;
-                                else if (rows) (*rows)[(size_t)k].assign(tg.begin(), tg.end());
-                                else if (!tg.empty()) std::memcpy(out + (size_t)f * cap, tg.data(), tg.size() * sizeof(agx_tag));
-                            } catch (...) {
-                                cnt[(size_t)f] = 0;
-                                st[(size_t)f] = AGX_ERR_NOMEM;
-                                nomem.store(true);
-                            }
-                            bool last;
-                            {
-                                std::lock_guard<std::mutex> lk(m);
-                                last = --outstanding[r] == 0;
-                            }
-                            if (last) cv.notify_all();
-                        });
-                    }
-                } catch (...) {  // a task could not be queued: the slot's counter must not wait for tails that will never run
-                    std::lock_guard<std::mutex> lk(m);
-                    outstanding[r] -= nc - submitted;
-                    throw;
-                }
+                ring.submit(*pool, r, nc, [&](int i) {
+                    const int f = host_frames[(size_t)(c0 + i)];
+                    return HostTail{&det->fam, det->params.max_num_of_boards, f, records + offs[(size_t)f], ns[(size_t)f], slot + (size_t)i * plane,
+                                    (size_t)W, W, H, AGX_L8, &res, &ring, r};
+                });
             }
         } while (false);
     } catch (...) {
         rc = AGX_ERR_NOMEM;
     }
-    (void)pool->wait();  // every tail (they read the luma slots and the compact list, and write cnt / st / rows)
-    if (!rc && nomem.load()) rc = AGX_ERR_NOMEM;
+    (void)pool->wait();  // every tail (they read the luma slots and the compact list, and write to res)
+    if (!rc && res.out_of_memory()) rc = AGX_ERR_NOMEM;
     return rc;
 }
 
@@ -1898,20 +1947,18 @@ int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, in
     const bool to_dev = b.results == RESULTS_CALLER;
     hipStream_t stream = det->stream;
     if (n_threads <= 0) n_threads = agx_host_parallelism();
-    // every frame's result as the host knows it (the device arrays of _enqueue_to get the same), the frames the host tail takes,
-    // and (_enqueue_to) their tag rows until they are copied to the caller's device arrays
-    std::vector<uint32_t> cnt;
-    std::vector<int> st;
+    // every frame's result as the host knows it (the device arrays of _enqueue_to get the same) and (_enqueue_to) the host tail's
+    // tag rows until they are copied to the caller's device arrays; the frames the host tail takes
+    FrameResults res(out, cap, nullptr, nullptr);
     std::vector<int> host_frames;
-    std::vector<std::vector<agx_tag>> rows;
-    int rc = AGX_OK, n_fallback = 0, n_uncertain = 0;
+    TailStats stats;
+    int rc = AGX_OK;
     try {
         do {
             if (hipSetDevice(det->device) != hipSuccess) { rc = AGX_ERR_HIP; break; }
             WorkerPool *pool = worker_pool(det, n_threads);
             if (!pool) { rc = AGX_ERR_ARG; break; }
-            cnt.assign((size_t)n, 0u);
-            st.assign((size_t)n, AGX_OK);
+            res.hold(n, to_dev);
             std::vector<char> back((size_t)n, b.device_tail ? 0 : 1);  // 1 handed back, 2 handed back as uncertain
             if (b.device_tail) {
                 const uint32_t *table = nullptr;
@@ -1927,22 +1974,15 @@ int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, in
                     rc = fetch_tail(det, &tags, &table, &tag_stride);  // waits for the device
                     if (rc) break;
                 }
-                for (int f = 0; f < n; ++f) {
-                    const uint32_t ts = table[4 * f + 1], nt = table[4 * f];
-                    if (ts != TAIL_OK) {
-                        back[(size_t)f] = (ts & TAIL_UNCERTAIN) ? 2 : 1;
-                        continue;
-                    }
-                    cnt[(size_t)f] = nt;
-                    if (nt > cap) st[(size_t)f] = AGX_ERR_CAPACITY;  // (the kernel hands such frames back; never truncated either way)
-                    else if (!to_dev && nt) std::memcpy(out + (size_t)f * cap, tags + (size_t)f * tag_stride, (size_t)nt * sizeof(agx_tag));
-                }
+                (void)read_tail_table(table, tags, tag_stride, 0, n, res, back.data());
             }
-            rc = resolve_on_host(det, b, back, pool, out, cnt, st, host_frames, to_dev ? &rows : nullptr, n_fallback, n_uncertain);
+            rc = resolve_on_host(det, b, back, pool, res, host_frames, stats);
         } while (false);
     } catch (...) {
         rc = AGX_ERR_NOMEM;
     }
+    const uint32_t *cnt = res.counts();
+    const int *st = res.statuses();
     if (!rc && to_dev) {
         // the host tail's frames into the caller's device arrays, on the detector's stream: rows, count, status (all frames at once
         // where the host tail took every frame)
@@ -1950,36 +1990,27 @@ int agx::detect_fetch_impl(agx_detector *det, agx_tag *out, uint32_t *counts, in
         for (size_t k = 0; k < host_frames.size() && ok; ++k) {
             const int f = host_frames[k];
             if (st[(size_t)f] == AGX_OK && cnt[(size_t)f])
-                ok = hipMemcpyAsync(b.d_tags + (size_t)f * cap, rows[k].data(), (size_t)cnt[(size_t)f] * sizeof(agx_tag), hipMemcpyHostToDevice,
-                                    stream) == hipSuccess;
+                ok = hipMemcpyAsync(b.d_tags + (size_t)f * cap, res.held_rows(f).data(), (size_t)cnt[(size_t)f] * sizeof(agx_tag),
+                                    hipMemcpyHostToDevice, stream) == hipSuccess;
             if (ok && b.device_tail)
                 ok = hipMemcpyAsync(b.d_counts + f, &cnt[(size_t)f], sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess &&
                      hipMemcpyAsync(b.d_status + f, &st[(size_t)f], sizeof(int), hipMemcpyHostToDevice, stream) == hipSuccess;
         }
         if (ok && !b.device_tail)
-            ok = hipMemcpyAsync(b.d_counts, cnt.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess &&
-                 hipMemcpyAsync(b.d_status, st.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream) == hipSuccess;
+            ok = hipMemcpyAsync(b.d_counts, cnt, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, stream) == hipSuccess &&
+                 hipMemcpyAsync(b.d_status, st, (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream) == hipSuccess;
         // the caller's host arrays as well, if it passed any: the rows from the device arrays, counts and status as known here
         if (ok && out && cap)
             ok = hipMemcpyAsync(out, b.d_tags, (size_t)n * cap * sizeof(agx_tag), hipMemcpyDeviceToHost, stream) == hipSuccess;
         if (!ok || hipStreamSynchronize(stream) != hipSuccess) rc = AGX_ERR_HIP;
     }
     abandon_batch(det);  // (waits for the stream; nothing of the batch is left to be fetched)
-    set_tail_stats(det, b.device_tail ? n : 0, n_fallback, n_uncertain);
-    if (rc) {  // the call failed as a whole: no frame's result is valid (as agx_detect_batch)
-        if (counts)
-            for (int f = 0; f < n; ++f) counts[f] = 0;
-        if (frame_status)
-            for (int f = 0; f < n; ++f) frame_status[f] = rc;
+    set_tail_stats(det, b.device_tail ? n : 0, stats.fallback, stats.uncertain);
+    if (rc) {
+        FrameResults::fail_all(rc, counts, frame_status, n);
         return rc;
     }
-    int first_bad = AGX_OK;
-    for (int f = 0; f < n; ++f) {
-        if (counts) counts[f] = cnt[(size_t)f];
-        if (frame_status) frame_status[f] = st[(size_t)f];
-        if (first_bad == AGX_OK) first_bad = st[(size_t)f];
-    }
-    return first_bad;
+    return res.hand_over(counts, frame_status, n, nullptr);
 }
 
 // agx_group_detect_fetch, rank by rank: the group has read this rank's packed frame table; back[f] != 0 marks the frames the
@@ -1992,26 +2023,22 @@ int agx::group_detect_fetch_impl(agx_detector *det, const char *back_in, agx_tag
     det->batch = BATCH_SADDLES;  // (as detect_fetch_impl)
     const int n = b.n_frames;
     if (n_threads <= 0) n_threads = agx_host_parallelism();
-    std::vector<uint32_t> cnt;
-    std::vector<int> st, host_frames;
-    int rc = AGX_OK, n_fallback = 0, n_uncertain = 0;
+    FrameResults res(out, b.cap, nullptr, nullptr);
+    std::vector<int> host_frames;
+    TailStats stats;
+    int rc = AGX_OK;
     try {
         const std::vector<char> back(back_in, back_in + n);
-        cnt.assign((size_t)n, 0u);
-        st.assign((size_t)n, AGX_OK);
+        res.hold(n, false);
         if (std::any_of(back.begin(), back.end(), [](char c) { return c != 0; })) {
             WorkerPool *pool = hipSetDevice(det->device) == hipSuccess ? worker_pool(det, n_threads) : nullptr;
-            rc = pool ? resolve_on_host(det, b, back, pool, out, cnt, st, host_frames, nullptr, n_fallback, n_uncertain) : AGX_ERR_HIP;
+            rc = pool ? resolve_on_host(det, b, back, pool, res, host_frames, stats) : AGX_ERR_HIP;
         }
-        for (int f = 0; f < n && !rc; ++f)
-            if (back[(size_t)f]) {
-                counts[f] = cnt[(size_t)f];
-                frame_status[f] = st[(size_t)f];
-            }
+        if (!rc) (void)res.hand_over(counts, frame_status, n, back.data());  // (a frame's own status is not the rank's)
     } catch (...) {
         rc = AGX_ERR_NOMEM;
     }
     abandon_batch(det);
-    set_tail_stats(det, b.device_tail ? n : 0, n_fallback, n_uncertain);
+    set_tail_stats(det, b.device_tail ? n : 0, stats.fallback, stats.uncertain);
     return rc;
 }
