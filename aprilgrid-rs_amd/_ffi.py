@@ -41,6 +41,8 @@ AGX_TAGS_OK, AGX_TAGS_CAPACITY, AGX_TAGS_INPUT, AGX_TAGS_PENDING = 0, 1, 2, 3
 AGX_FIT_PREDICT_MISSING = 1
 AGX_FIT_OK, AGX_FIT_LOOSE, AGX_FIT_FEW, AGX_FIT_SINGULAR, AGX_FIT_INPUT = 0, 1, 2, 3, 4
 AGX_FIT_ROW_INLIER, AGX_FIT_ROW_OUTLIER, AGX_FIT_ROW_OFF_BOARD = 0, 1, 2
+# the lens model of agx_board_pose_enqueue_m / _tail_m: pinhole + radial-tangential, pinhole-equidistant (fisheye)
+AGX_LENS_RADTAN, AGX_LENS_EQUIDISTANT = 0, 1
 AGX_DBG_BLUR, AGX_DBG_RESP, AGX_DBG_MIN, AGX_DBG_CENTERS, AGX_DBG_REFINED = 0, 1, 2, 3, 4
 AGX_N_KERNELS = 5
 
@@ -174,6 +176,18 @@ SYMBOLS = {
                                       C.POINTER(C.c_uint32)]),
     "agx_debug_board_pose_sums": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_double,
                                             C.POINTER(C.c_double), C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), _P]),
+    "agx_board_pose_enqueue_m": (C.c_int, [_P, C.c_int, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_double, C.c_int,
+                                           C.POINTER(C.c_double), C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, _P]),
+    "agx_board_pose_tail_m": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_double, C.c_int,
+                                        C.POINTER(C.c_double), C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P,
+                                        C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_uint32), _P, C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_uint32)]),
+    "agx_debug_board_pose_sums_m": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_double,
+                                              C.c_int, C.POINTER(C.c_double), C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                              C.POINTER(C.c_uint32), _P]),
+    "agx_debug_pose_atan": (C.c_int, [_P, C.c_uint32, _P]),
+    "agx_debug_pose_project": (C.c_int, [C.c_int, C.POINTER(C.c_double), _P, C.c_uint32, _P]),
     "agx_group_create": (C.c_int, [C.c_int, C.POINTER(Params), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "agx_group_destroy": (None, [_P]),
     "agx_group_size": (C.c_int, [_P]),

@@ -22,7 +22,7 @@ struct BoardPoseArgs {
     uint32_t cols, rows, first_id;  // rows * cols in 1 .. 4096
     float spacing_ratio;            // finite, > -1
     double tag_size;                // finite, > 0
-    agx_camera camera;              // every field finite, fx and fy > 0
+    agx_camera camera;              // every field finite, fx and fy > 0; under AGX_LENS_EQUIDISTANT fx fy cx cy k1 k2 k3 k4 0
     float max_err_sq;               // >= 0
     uint32_t max_drop, min_tags;    // min_tags >= 1
     uint32_t iterations;            // 0 .. 64
@@ -37,7 +37,8 @@ struct BoardPoseArgs {
     uint32_t *n_pred;      // [n_frames]
     uint32_t *status;      // [n_frames]: AGX_FIT_*
 };
-// one wave per frame, POSE_FRAMES_PER_WG frames per workgroup; n_frames * tags_per_frame < 2^27; hipError_t
-int launch_board_pose(const BoardPoseArgs &b, void *stream);
+// one wave per frame, POSE_FRAMES_PER_WG frames per workgroup; n_frames * tags_per_frame < 2^27; lens: AGX_LENS_*, which picks the
+// kernel's instantiation; hipError_t
+int launch_board_pose(const BoardPoseArgs &b, int lens, void *stream);
 
 }  // namespace agx

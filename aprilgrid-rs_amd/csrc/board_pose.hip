@@ -12,6 +12,8 @@
 // lane per row, a (residual, lowest row) key folded by shuffles.  The frame's verdict is known before its first store.
 // Prediction: one lane per tag of the layout, 64 at a time, compacted by ballot under AGX_FIT_PREDICT_MISSING against a bitmap of
 // the inlier rows' ids.  No floating-point atomics.
+// The kernel is a template on the lens model (AGX_LENS_*): the projection, the lens's Jacobian and the seed's undistortion are
+// board_pose_math.h's for that model, everything else is one text.  Neither instantiation uses scratch.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -48,6 +50,7 @@ __device__ __forceinline__ void pose_row_xy(const uint32_t *row, float xy[8])
     for (int j = 0; j < 8; ++j) xy[j] = f32_from_bits(row[1 + j]);
 }
 
+template <int LENS>
 __global__ void __launch_bounds__(64 * POSE_FRAMES_PER_WG) k_board_pose(BoardPoseArgs b)
 {
     __shared__ PoseFrameLds lds[POSE_FRAMES_PER_WG];
@@ -98,7 +101,7 @@ __global__ void __launch_bounds__(64 * POSE_FRAMES_PER_WG) k_board_pose(BoardPos
             if (s.st[r] != AGX_FIT_ROW_INLIER) continue;
             float xy[8];
             pose_row_xy(s.rows + 9u * r, xy);
-            pose_seed_accumulate_row(g, cam, acc, s.rows[9u * r], xy);
+            pose_seed_accumulate_row<LENS>(g, cam, acc, s.rows[9u * r], xy);
         }
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1)
@@ -133,7 +136,7 @@ __global__ void __launch_bounds__(64 * POSE_FRAMES_PER_WG) k_board_pose(BoardPos
                 if (s.st[r] != AGX_FIT_ROW_INLIER) continue;
                 float xy[8];
                 pose_row_xy(s.rows + 9u * r, xy);
-                pose_accumulate_row(g, b.tag_size, cam, cur, acc, s.rows[9u * r], xy);
+                pose_accumulate_row<LENS>(g, b.tag_size, cam, cur, acc, s.rows[9u * r], xy);
             }
 #pragma unroll
             for (int m = 32; m >= 1; m >>= 1)
@@ -173,7 +176,7 @@ __global__ void __launch_bounds__(64 * POSE_FRAMES_PER_WG) k_board_pose(BoardPos
             float xy[8];
             double sum;
             pose_row_xy(s.rows + 9u * r, xy);
-            const float e = pose_row_residual(g, b.tag_size, cam, pose, s.rows[9u * r], xy, &sum);
+            const float e = pose_row_residual<LENS>(g, b.tag_size, cam, pose, s.rows[9u * r], xy, &sum);
             part += sum;
             const u64 k = ((u64)f32_bits(e) << 32) | (u64)(0xffffffffu - r);
             key = k > key ? k : key;
@@ -215,7 +218,7 @@ __global__ void __launch_bounds__(64 * POSE_FRAMES_PER_WG) k_board_pose(BoardPos
         float xy[8];
         double sum;
         pose_row_xy(s.rows + 9u * r, xy);
-        b.err_sq[row0 + r] = pose_row_residual(g, b.tag_size, cam, pose, s.rows[9u * r], xy, &sum);
+        b.err_sq[row0 + r] = pose_row_residual<LENS>(g, b.tag_size, cam, pose, s.rows[9u * r], xy, &sum);
     }
     if (lane == 0) {
 #pragma unroll
@@ -247,7 +250,7 @@ __global__ void __launch_bounds__(64 * POSE_FRAMES_PER_WG) k_board_pose(BoardPos
         if (want) {
             uint32_t *row = pred + 9u * (u64)(base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull)));
             float xy[8];
-            pose_predict(g, b.tag_size, cam, pose, t, xy);
+            pose_predict<LENS>(g, b.tag_size, cam, pose, t, xy);
             row[0] = g.first_id + t;
 #pragma unroll
             for (int j = 0; j < 8; ++j) row[1 + j] = f32_bits(xy[j]);
@@ -259,16 +262,17 @@ __global__ void __launch_bounds__(64 * POSE_FRAMES_PER_WG) k_board_pose(BoardPos
 
 }  // namespace
 
-int launch_board_pose(const BoardPoseArgs &b, void *stream)
+int launch_board_pose(const BoardPoseArgs &b, int lens, void *stream)
 {
     if (b.n_frames <= 0 || !b.tags || !b.tags_per_frame || !b.n_tags || !b.cols || !b.rows ||
         (unsigned long long)b.cols * b.rows > FIT_MAX_BOARD || !__builtin_isfinite(b.spacing_ratio) || !(b.spacing_ratio > -1.0f) ||
-        !pose_args_ok(b.camera, b.tag_size, b.iterations) || !(b.max_err_sq >= 0.0f) || !b.min_tags || (b.flags & ~AGX_FIT_PREDICT_MISSING) ||
+        !pose_args_ok(lens, b.camera, b.tag_size, b.iterations) || !(b.max_err_sq >= 0.0f) || !b.min_tags || (b.flags & ~AGX_FIT_PREDICT_MISSING) ||
         (unsigned long long)b.n_frames * b.tags_per_frame >= (1ull << 27) || !b.pose || !b.err_sq || !b.row_status || !b.n_inliers || !b.rms ||
         !b.best_iter || !b.pred || !b.n_pred || !b.status)
         return (int)hipErrorInvalidValue;
     const unsigned grid = ((unsigned)b.n_frames + POSE_FRAMES_PER_WG - 1) / POSE_FRAMES_PER_WG;
-    hipLaunchKernelGGL(k_board_pose, dim3(grid), dim3(64 * POSE_FRAMES_PER_WG), 0, (hipStream_t)stream, b);
+    if (lens == AGX_LENS_EQUIDISTANT) hipLaunchKernelGGL(k_board_pose<AGX_LENS_EQUIDISTANT>, dim3(grid), dim3(64 * POSE_FRAMES_PER_WG), 0, (hipStream_t)stream, b);
+    else hipLaunchKernelGGL(k_board_pose<AGX_LENS_RADTAN>, dim3(grid), dim3(64 * POSE_FRAMES_PER_WG), 0, (hipStream_t)stream, b);
     return (int)hipGetLastError();
 }
 

@@ -33,8 +33,29 @@
 // iterate i + 1 is iterate i updated.  A singular system ends the round at the iterates so far; at iterate 0 (iterations > 0)
 // it is AGX_FIT_SINGULAR.  The round's answer is the iterate with the lowest finite sum of |e|^2, the earliest at equal bits
 // (iterate 0 if none is finite); the sum of the last iterate is one more pass.  The answer's R goes through the Gram-Schmidt once.
+//
+// The second lens model, AGX_LENS_EQUIDISTANT (Kalibr's pinhole-equi, OpenCV's fisheye, Kannala-Brandt with four coefficients).
+// Every function that reads the camera is a template on LENS; AGX_LENS_RADTAN is the statements above, unchanged.  The nine
+// doubles are then fx, fy, cx, cy, k1, k2, k3, k4, 0: agx_camera's p1 holds k3, its p2 holds k4, its k3 must be 0.
+//   x, y, r2 as above;  r = pose_sqrt(r2);  r2 < POSE_EQUI_SMALL_R2 (2^-13):  q = 1 - r2 (1/3 - r2 (1/5 - r2 (1/7 - r2 / 9))),
+//   theta = r q;  else theta = pose_atan(r), q = theta / r;   t2 = theta theta, t4 = t2 t2, t6 = t4 t2, t8 = t4 t4,
+//   D = 1 + k1 t2 + k2 t4 + k3 t6 + k4 t8  (left to right),  s = q D,  u = fx (s x) + cx,  v = fy (s y) + cy.
+// The series' first dropped term is r2^5 / 11 < 3e-21 below the threshold; on the optical axis q = D = s = 1 and the pixel is
+// (cx, cy) exactly, with no division.  Zc not > 0: no projection, as above (the model is not carried behind the camera).
+// pose_atan(r), r >= 0 finite: + - * / only.  t = r, or 1 / r above 1;  k = (int)(8 t + 1/2), the nearest break point k / 8 of
+// 0 .. 8 (0 where 8 t + 1/2 is not in [0, 9): r not a number);  z = (t - k/8) / (1 + t k/8), |z| <= 1/16;  p = z - z z2 (1/3 - z2 (1/5 - z2 (1/7 - z2 (1/9 - z2 (1/11 - z2 / 13)))));
+// a = POSE_ATAN_TABLE[k] + p;  above 1 the answer is (pi/2 high - a) + pi/2 low.  Not correctly rounded: within 1e-14 of atan.
+// Jacobian of (s x, s y) by (x, y):  D' = 1 + 3 k1 t2 + 5 k2 t4 + 7 k3 t6 + 9 k4 t8,  g = (ds/dr) / r = (D' / (1 + r2) - s) / r2,
+// below the threshold its limit 2 (k1 - 1/3) + 4 (k2 - k1 + 1/5) r2;  d00 = s + x x g, d01 = d10 = x y g, d11 = s + y y g.  The
+// chain from there to (R, t), the sums, the solve, the iterates and the rounds are the ones above.
+// Seed's undistortion: x0, y0 as above, theta_d = pose_sqrt(x0 x0 + y0 y0);  theta = theta_d, then POSE_EQUI_THETA_STEPS (8)
+// times, no early exit:  theta = theta - (theta D(theta) - theta_d) / D'(theta);  theta >= POSE_EQUI_THETA_MAX (1.5 rad, for
+// the seed only: a pinhole ray must exist) becomes POSE_EQUI_THETA_MAX;  tan(theta) from a = theta / 8 by the series of the
+// tangent through a^15 and POSE_EQUI_TAN_DOUBLINGS (3) times t = 2 t / (1 - t t);  (x, y) = (x0, y0) tan(theta) / theta_d
+// (theta_d = 0: (x0, y0)).  A value that is not finite reaches the seed's norm checks: AGX_FIT_SINGULAR.
 #pragma once
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/aprilgrid_amd.h"
 #include "board_fit_math.h"
@@ -44,6 +65,21 @@ namespace agx {
 constexpr int POSE_SUMS = 28;  // 21 of J^T J (i <= j) + 6 of J^T e + the sum of |e|^2
 constexpr uint32_t POSE_MAX_ITERATIONS = 64;
 constexpr int POSE_UNDISTORT_STEPS = 8;
+constexpr int POSE_EQUI_THETA_STEPS = 8;        // Newton steps on theta D(theta) = theta_d, from theta = theta_d
+constexpr int POSE_EQUI_TAN_DOUBLINGS = 3;      // tan(theta) from the series of tan(theta / 8)
+constexpr double POSE_EQUI_THETA_MAX = 1.5;     // the seed's clamp on theta, radians
+constexpr double POSE_EQUI_SMALL_R2 = 0x1p-13;  // below it theta / r and (ds/dr) / r come from their series
+// atan(k / 8), k = 0 .. 8, to the nearest binary64
+constexpr double POSE_ATAN_TABLE[9] = {0.0,
+                                       0.12435499454676144,
+                                       0.24497866312686414,
+                                       0.35877067027057225,
+                                       0.4636476090008061,
+                                       0.5585993153435624,
+                                       0.6435011087932844,
+                                       0.7188299996216245,
+                                       0.7853981633974483};
+constexpr double POSE_PIO2_HI = 1.5707963267948966, POSE_PIO2_LO = 6.123233995736766e-17;
 
 struct Pose {
     double R[9];  // row major, board -> camera
@@ -58,6 +94,28 @@ AGX_HD FitGeom pose_geom(uint32_t cols, uint32_t rows, uint32_t first_id, float 
 
 AGX_HD double pose_sqrt(double v) { return __builtin_sqrt(v); }
 
+// atan(r) for r >= 0, finite: + - * / only, the same statements for both compilers (within 1e-14 of atan, not correctly rounded)
+AGX_HD double pose_atan(double r)
+{
+    const bool above = r > 1.0;
+    const double t = above ? 1.0 / r : r;
+    const double kf = t * 8.0 + 0.5;
+    const int k = kf >= 0.0 && kf < 9.0 ? (int)kf : 0;  // (an r that is not a number reads entry 0 and stays not a number)
+    const double b = (double)k * 0.125;
+    const double z = (t - b) / (1.0 + t * b), z2 = z * z;
+    const double p = z - z * z2 * (1.0 / 3.0 - z2 * (1.0 / 5.0 - z2 * (1.0 / 7.0 - z2 * (1.0 / 9.0 - z2 * (1.0 / 11.0 - z2 / 13.0)))));
+    const double a = POSE_ATAN_TABLE[k] + p;
+    return above ? (POSE_PIO2_HI - a) + POSE_PIO2_LO : a;
+}
+
+// D(theta) and D'(theta) of the equidistant model from theta^2 (agx_camera's p1 holds k3, its p2 holds k4)
+AGX_HD void pose_equi_poly(const agx_camera &c, double t2, double &D, double &Dp)
+{
+    const double t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4;
+    D = 1.0 + c.k1 * t2 + c.k2 * t4 + c.p1 * t6 + c.p2 * t8;
+    Dp = 1.0 + 3.0 * c.k1 * t2 + 5.0 * c.k2 * t4 + 7.0 * c.p1 * t6 + 9.0 * c.p2 * t8;
+}
+
 // corner j of the layout's tag t (0 .. n_board - 1) in the board's frame, in tag_size's unit
 AGX_HD void pose_board_point(const FitGeom &g, double tag_size, uint32_t t, int j, double &X, double &Y)
 {
@@ -71,42 +129,101 @@ AGX_HD void pose_board_point(const FitGeom &g, double tag_size, uint32_t t, int 
 struct PosePoint {
     double x, y, zc, r2, r4, rad, u, v;
 };
+struct PosePointEqui {
+    double x, y, zc, s, g, u, v;  // s = theta_d / r, g = (ds/dr) / r
+};
+template <int LENS>
+using PosePointOf = std::conditional_t<LENS == AGX_LENS_EQUIDISTANT, PosePointEqui, PosePoint>;
 
 // false: Zc is not > 0 (q untouched beyond zc)
-AGX_HD bool pose_project(const agx_camera &c, const Pose &p, double X, double Y, PosePoint &q)
+template <int LENS = AGX_LENS_RADTAN>
+AGX_HD bool pose_project(const agx_camera &c, const Pose &p, double X, double Y, PosePointOf<LENS> &q)
 {
     const double xc = p.R[0] * X + p.R[1] * Y + p.t[0];
     const double yc = p.R[3] * X + p.R[4] * Y + p.t[1];
     q.zc = p.R[6] * X + p.R[7] * Y + p.t[2];
     if (!(q.zc > 0.0)) return false;
     const double x = xc / q.zc, y = yc / q.zc;
-    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
-    const double rad = 1.0 + c.k1 * r2 + c.k2 * r4 + c.k3 * r6;
-    const double xd = x * rad + 2.0 * c.p1 * x * y + c.p2 * (r2 + 2.0 * x * x);
-    const double yd = y * rad + c.p1 * (r2 + 2.0 * y * y) + 2.0 * c.p2 * x * y;
-    q.x = x;
-    q.y = y;
-    q.r2 = r2;
-    q.r4 = r4;
-    q.rad = rad;
-    q.u = c.fx * xd + c.cx;
-    q.v = c.fy * yd + c.cy;
+    if constexpr (LENS == AGX_LENS_EQUIDISTANT) {
+        const double r2 = x * x + y * y, r = pose_sqrt(r2);
+        const bool small = r2 < POSE_EQUI_SMALL_R2;
+        double th, tr;  // theta, theta / r
+        if (small) {
+            tr = 1.0 - r2 * (1.0 / 3.0 - r2 * (1.0 / 5.0 - r2 * (1.0 / 7.0 - r2 / 9.0)));
+            th = r * tr;
+        } else {
+            th = pose_atan(r);
+            tr = th / r;
+        }
+        double D, Dp;
+        pose_equi_poly(c, th * th, D, Dp);
+        const double s = tr * D;
+        q.x = x;
+        q.y = y;
+        q.s = s;
+        q.g = small ? 2.0 * (c.k1 - 1.0 / 3.0) + 4.0 * (c.k2 - c.k1 + 1.0 / 5.0) * r2 : (Dp / (1.0 + r2) - s) / r2;
+        q.u = c.fx * (s * x) + c.cx;
+        q.v = c.fy * (s * y) + c.cy;
+    } else {
+        const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+        const double rad = 1.0 + c.k1 * r2 + c.k2 * r4 + c.k3 * r6;
+        const double xd = x * rad + 2.0 * c.p1 * x * y + c.p2 * (r2 + 2.0 * x * x);
+        const double yd = y * rad + c.p1 * (r2 + 2.0 * y * y) + 2.0 * c.p2 * x * y;
+        q.x = x;
+        q.y = y;
+        q.r2 = r2;
+        q.r4 = r4;
+        q.rad = rad;
+        q.u = c.fx * xd + c.cx;
+        q.v = c.fy * yd + c.cy;
+    }
     return true;
 }
 
 // |e|^2 of one correspondence: +inf without a projection or where the value is not below +inf
-AGX_HD double pose_error(const agx_camera &c, const Pose &p, double X, double Y, double uo, double vo, PosePoint &q, double &eu, double &ev)
+template <int LENS = AGX_LENS_RADTAN>
+AGX_HD double pose_error(const agx_camera &c, const Pose &p, double X, double Y, double uo, double vo, PosePointOf<LENS> &q, double &eu, double &ev)
 {
-    if (!pose_project(c, p, X, Y, q)) return __builtin_inf();
+    if (!pose_project<LENS>(c, p, X, Y, q)) return __builtin_inf();
     eu = uo - q.u;
     ev = vo - q.v;
     const double e = eu * eu + ev * ev;
     return e < __builtin_inf() ? e : __builtin_inf();
 }
 
+// tan(theta) for |theta| <= POSE_EQUI_THETA_MAX: the series of tan(theta / 8) through a^15, then three doublings
+AGX_HD double pose_tan(double theta)
+{
+    const double a = theta / 8.0, a2 = a * a;
+    double t = a + a * a2 * (1.0 / 3.0 + a2 * (2.0 / 15.0 + a2 * (17.0 / 315.0 + a2 * (62.0 / 2835.0 + a2 * (1382.0 / 155925.0 +
+               a2 * (21844.0 / 6081075.0 + a2 * (929569.0 / 638512875.0)))))));
+#pragma unroll
+    for (int i = 0; i < POSE_EQUI_TAN_DOUBLINGS; ++i) t = 2.0 * t / (1.0 - t * t);
+    return t;
+}
+
+// a pixel to normalised coordinates under the equidistant model: theta from theta_d by Newton, its tangent, the ray
+AGX_HD void pose_undistort_equi(const agx_camera &c, double u, double v, double &x, double &y)
+{
+    const double x0 = (u - c.cx) / c.fx, y0 = (v - c.cy) / c.fy;
+    const double td = pose_sqrt(x0 * x0 + y0 * y0);
+    double th = td;
+    for (int i = 0; i < POSE_EQUI_THETA_STEPS; ++i) {
+        double D, Dp;
+        pose_equi_poly(c, th * th, D, Dp);
+        th = th - (th * D - td) / Dp;
+    }
+    if (th >= POSE_EQUI_THETA_MAX) th = POSE_EQUI_THETA_MAX;
+    const double k = td > 0.0 ? pose_tan(th) / td : 1.0;
+    x = x0 * k;
+    y = y0 * k;
+}
+
 // a pixel to normalised coordinates: POSE_UNDISTORT_STEPS steps of the fixed-point iteration
+template <int LENS = AGX_LENS_RADTAN>
 AGX_HD void pose_undistort(const agx_camera &c, double u, double v, double &x, double &y)
 {
+    if constexpr (LENS == AGX_LENS_EQUIDISTANT) return pose_undistort_equi(c, u, v, x, y);
     const double x0 = (u - c.cx) / c.fx, y0 = (v - c.cy) / c.fy;
     x = x0;
     y = y0;
@@ -121,13 +238,14 @@ AGX_HD void pose_undistort(const agx_camera &c, double u, double v, double &x, d
 }
 
 // the seed's sums: the four correspondences of one table row (id on the board, corners finite) into a lane's FIT_SUMS
+template <int LENS = AGX_LENS_RADTAN>
 AGX_HD void pose_seed_accumulate_row(const FitGeom &g, const agx_camera &c, double acc[FIT_SUMS], uint32_t id, const float xy[8])
 {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         double xn, yn, x, y;
         fit_board_point(g, id - g.first_id, j, xn, yn);
-        pose_undistort(c, (double)xy[2 * j], (double)xy[2 * j + 1], x, y);
+        pose_undistort<LENS>(c, (double)xy[2 * j], (double)xy[2 * j + 1], x, y);
         fit_accumulate(acc, xn, yn, x, y);
     }
 }
@@ -184,19 +302,36 @@ AGX_HD bool pose_from_homography(const FitGeom &g, double tag_size, const double
 }
 
 // one correspondence into a lane's sums
+// the 2 x 2 derivative of the distorted point by (x, y)
+AGX_HD void pose_lens_jacobian(const agx_camera &c, const PosePoint &q, double &d00, double &d01, double &d10, double &d11)
+{
+    const double x = q.x, y = q.y;
+    const double drad = c.k1 + 2.0 * c.k2 * q.r2 + 3.0 * c.k3 * q.r4;
+    d00 = q.rad + 2.0 * x * x * drad + 2.0 * c.p1 * y + 6.0 * c.p2 * x;
+    d01 = 2.0 * x * y * drad + 2.0 * c.p1 * x + 2.0 * c.p2 * y;
+    d10 = 2.0 * x * y * drad + 2.0 * c.p1 * x + 2.0 * c.p2 * y;
+    d11 = q.rad + 2.0 * y * y * drad + 6.0 * c.p1 * y + 2.0 * c.p2 * x;
+}
+AGX_HD void pose_lens_jacobian(const agx_camera &, const PosePointEqui &q, double &d00, double &d01, double &d10, double &d11)
+{
+    const double x = q.x, y = q.y;
+    d00 = q.s + x * x * q.g;
+    d01 = x * y * q.g;
+    d10 = x * y * q.g;
+    d11 = q.s + y * y * q.g;
+}
+
+template <int LENS = AGX_LENS_RADTAN>
 AGX_HD void pose_accumulate(const agx_camera &c, const Pose &p, double acc[POSE_SUMS], double X, double Y, double uo, double vo)
 {
-    PosePoint q;
+    PosePointOf<LENS> q;
     double eu = 0.0, ev = 0.0;
-    const double e = pose_error(c, p, X, Y, uo, vo, q, eu, ev);
+    const double e = pose_error<LENS>(c, p, X, Y, uo, vo, q, eu, ev);
     acc[27] += e;
     if (!(e < __builtin_inf())) return;
     const double x = q.x, y = q.y;
-    const double drad = c.k1 + 2.0 * c.k2 * q.r2 + 3.0 * c.k3 * q.r4;
-    const double d00 = q.rad + 2.0 * x * x * drad + 2.0 * c.p1 * y + 6.0 * c.p2 * x;
-    const double d01 = 2.0 * x * y * drad + 2.0 * c.p1 * x + 2.0 * c.p2 * y;
-    const double d10 = 2.0 * x * y * drad + 2.0 * c.p1 * x + 2.0 * c.p2 * y;
-    const double d11 = q.rad + 2.0 * y * y * drad + 6.0 * c.p1 * y + 2.0 * c.p2 * x;
+    double d00, d01, d10, d11;
+    pose_lens_jacobian(c, q, d00, d01, d10, d11);
     const double m00 = c.fx * d00 / q.zc, m01 = c.fx * d01 / q.zc, m02 = -(m00 * x + m01 * y);
     const double m10 = c.fy * d10 / q.zc, m11 = c.fy * d11 / q.zc, m12 = -(m10 * x + m11 * y);
     // G = -R [P]x for P = (X, Y, 0): columns Y c3, -X c3, X c2 - Y c1
@@ -215,6 +350,7 @@ AGX_HD void pose_accumulate(const agx_camera &c, const Pose &p, double acc[POSE_
 }
 
 // the four correspondences of one inlier row into a lane's sums
+template <int LENS = AGX_LENS_RADTAN>
 AGX_HD void pose_accumulate_row(const FitGeom &g, double tag_size, const agx_camera &c, const Pose &p, double acc[POSE_SUMS], uint32_t id,
                                 const float xy[8])
 {
@@ -222,7 +358,7 @@ AGX_HD void pose_accumulate_row(const FitGeom &g, double tag_size, const agx_cam
     for (int j = 0; j < 4; ++j) {
         double X, Y;
         pose_board_point(g, tag_size, id - g.first_id, j, X, Y);
-        pose_accumulate(c, p, acc, X, Y, (double)xy[2 * j], (double)xy[2 * j + 1]);
+        pose_accumulate<LENS>(c, p, acc, X, Y, (double)xy[2 * j], (double)xy[2 * j + 1]);
     }
 }
 
@@ -262,15 +398,16 @@ AGX_HD void pose_update(Pose &p, const double d[6])
 
 // the residual of one table row under the pose: the largest of its four corners' |e|^2 in pixels, binary64 rounded to binary32;
 // *sum gets the four corners' sum in corner order
+template <int LENS = AGX_LENS_RADTAN>
 AGX_HD float pose_row_residual(const FitGeom &g, double tag_size, const agx_camera &c, const Pose &p, uint32_t id, const float xy[8], double *sum)
 {
     double worst = 0.0, total = 0.0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         double X, Y, eu, ev;
-        PosePoint q;
+        PosePointOf<LENS> q;
         pose_board_point(g, tag_size, id - g.first_id, j, X, Y);
-        const double e = pose_error(c, p, X, Y, (double)xy[2 * j], (double)xy[2 * j + 1], q, eu, ev);
+        const double e = pose_error<LENS>(c, p, X, Y, (double)xy[2 * j], (double)xy[2 * j + 1], q, eu, ev);
         total += e;
         if (e > worst) worst = e;
     }
@@ -279,14 +416,15 @@ AGX_HD float pose_row_residual(const FitGeom &g, double tag_size, const agx_came
 }
 
 // the predicted corners of the layout's tag t, rounded to binary32; NaN, NaN where Zc is not > 0
+template <int LENS = AGX_LENS_RADTAN>
 AGX_HD void pose_predict(const FitGeom &g, double tag_size, const agx_camera &c, const Pose &p, uint32_t t, float xy[8])
 {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         double X, Y;
-        PosePoint q;
+        PosePointOf<LENS> q;
         pose_board_point(g, tag_size, t, j, X, Y);
-        if (pose_project(c, p, X, Y, q)) {
+        if (pose_project<LENS>(c, p, X, Y, q)) {
             xy[2 * j] = (float)q.u;
             xy[2 * j + 1] = (float)q.v;
         } else {
@@ -298,9 +436,10 @@ AGX_HD void pose_predict(const FitGeom &g, double tag_size, const agx_camera &c,
 // the best-iterate rule: does an iterate whose sum of |e|^2 is `cost` replace the best so far
 AGX_HD bool pose_better(double cost, bool have, double best_cost) { return f64_finite(cost) && (!have || cost < best_cost); }
 
-// what both forms refuse in the camera and the pose's own scalars
-AGX_HD bool pose_args_ok(const agx_camera &c, double tag_size, uint32_t iterations)
+// what both forms refuse in the camera and the pose's own scalars (under AGX_LENS_EQUIDISTANT the ninth double is 0)
+AGX_HD bool pose_args_ok(int lens, const agx_camera &c, double tag_size, uint32_t iterations)
 {
+    if (lens != AGX_LENS_RADTAN && !(lens == AGX_LENS_EQUIDISTANT && c.k3 == 0.0)) return false;
     const double v[9] = {c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2, c.k3};
     for (int i = 0; i < 9; ++i)
         if (!f64_finite(v[i])) return false;

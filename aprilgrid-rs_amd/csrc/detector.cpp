@@ -2350,6 +2350,17 @@ int agx_board_pose_enqueue(agx_detector *det, int n_frames, const agx_tag *d_tag
                            double *d_pose, float *d_err_sq, uint32_t *d_row_status, uint32_t *d_n_inliers, float *d_rms, uint32_t *d_best_iter,
                            agx_tag *d_pred, uint32_t *d_n_pred, uint32_t *d_status)
 {
+    return agx_board_pose_enqueue_m(det, n_frames, d_tags, tags_per_frame, d_n_tags, d_tag_status, cols, rows, first_id, spacing_ratio, tag_size,
+                                    AGX_LENS_RADTAN, camera, max_err_sq, max_drop, min_tags, iterations, flags, d_pose, d_err_sq, d_row_status,
+                                    d_n_inliers, d_rms, d_best_iter, d_pred, d_n_pred, d_status);
+}
+
+int agx_board_pose_enqueue_m(agx_detector *det, int n_frames, const agx_tag *d_tags, uint32_t tags_per_frame, const uint32_t *d_n_tags,
+                             const uint32_t *d_tag_status, uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
+                             int lens_model, const double *camera, float max_err_sq, uint32_t max_drop, uint32_t min_tags, uint32_t iterations,
+                             int flags, double *d_pose, float *d_err_sq, uint32_t *d_row_status, uint32_t *d_n_inliers, float *d_rms,
+                             uint32_t *d_best_iter, agx_tag *d_pred, uint32_t *d_n_pred, uint32_t *d_status)
+{
     return agx_guard(det, [&]() -> int {
     if (!det) return AGX_ERR_ARG;
     if (!d_tags || !d_n_tags || !d_pose || !d_err_sq || !d_row_status || !d_n_inliers || !d_rms || !d_best_iter || !d_pred || !d_n_pred || !d_status ||
@@ -2359,8 +2370,8 @@ int agx_board_pose_enqueue(agx_detector *det, int n_frames, const agx_tag *d_tag
         return fail(det, AGX_ERR_ARG, "rows * cols in 1 .. 4096, spacing_ratio finite and > -1, max_err_sq >= 0, min_tags >= 1, flags AGX_FIT_PREDICT_MISSING or 0");
     agx_camera cam;
     std::memcpy(&cam, camera, sizeof cam);
-    if (!pose_args_ok(cam, tag_size, iterations))
-        return fail(det, AGX_ERR_ARG, "every camera field finite with fx and fy > 0, tag_size finite and > 0, iterations <= 64");
+    if (!pose_args_ok(lens_model, cam, tag_size, iterations))
+        return fail(det, AGX_ERR_ARG, "lens_model AGX_LENS_RADTAN or AGX_LENS_EQUIDISTANT (its ninth double 0), every camera field finite with fx and fy > 0, tag_size finite and > 0, iterations <= 64");
     if ((((uintptr_t)d_tags | (uintptr_t)d_n_tags | (uintptr_t)d_tag_status | (uintptr_t)d_err_sq | (uintptr_t)d_row_status | (uintptr_t)d_n_inliers |
           (uintptr_t)d_rms | (uintptr_t)d_best_iter | (uintptr_t)d_pred | (uintptr_t)d_n_pred | (uintptr_t)d_status) & 3) || ((uintptr_t)d_pose & 7))
         return fail(det, AGX_ERR_ARG, "d_pose must be 8-byte aligned, every other array 4-byte aligned");
@@ -2393,7 +2404,7 @@ int agx_board_pose_enqueue(agx_detector *det, int n_frames, const agx_tag *d_tag
     b.pred = d_pred;
     b.n_pred = d_n_pred;
     b.status = d_status;
-    const hipError_t e = (hipError_t)launch_board_pose(b, det->stream);
+    const hipError_t e = (hipError_t)launch_board_pose(b, lens_model, det->stream);
     if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_board_pose: ") + hipGetErrorString(e));
     return AGX_OK;
     });
@@ -2404,17 +2415,27 @@ int agx_board_pose_tail(const agx_tag *tags, uint32_t tags_per_frame, uint32_t n
                         uint32_t min_tags, uint32_t iterations, int flags, double *pose, float *err_sq, uint32_t *row_status, uint32_t *n_inliers,
                         float *rms, uint32_t *best_iter, agx_tag *pred, uint32_t *n_pred, uint32_t *status)
 {
+    return agx_board_pose_tail_m(tags, tags_per_frame, n_tags, tag_status, cols, rows, first_id, spacing_ratio, tag_size, AGX_LENS_RADTAN, camera,
+                                 max_err_sq, max_drop, min_tags, iterations, flags, pose, err_sq, row_status, n_inliers, rms, best_iter, pred, n_pred,
+                                 status);
+}
+
+int agx_board_pose_tail_m(const agx_tag *tags, uint32_t tags_per_frame, uint32_t n_tags, uint32_t tag_status, uint32_t cols, uint32_t rows,
+                          uint32_t first_id, float spacing_ratio, double tag_size, int lens_model, const double *camera, float max_err_sq,
+                          uint32_t max_drop, uint32_t min_tags, uint32_t iterations, int flags, double *pose, float *err_sq, uint32_t *row_status,
+                          uint32_t *n_inliers, float *rms, uint32_t *best_iter, agx_tag *pred, uint32_t *n_pred, uint32_t *status)
+{
     return agx_guard(nullptr, [&]() -> int {
     if (!pose || !n_inliers || !rms || !best_iter || !pred || !n_pred || !status || !camera || (n_tags && (!tags || !err_sq || !row_status)))
         return AGX_ERR_ARG;
     agx_camera cam;
     std::memcpy(&cam, camera, sizeof cam);
-    if (!board_fit_args_ok(cols, rows, spacing_ratio, 1, 1, max_err_sq, min_tags, flags) || !pose_args_ok(cam, tag_size, iterations)) return AGX_ERR_ARG;
+    if (!board_fit_args_ok(cols, rows, spacing_ratio, 1, 1, max_err_sq, min_tags, flags) || !pose_args_ok(lens_model, cam, tag_size, iterations)) return AGX_ERR_ARG;
     if ((((uintptr_t)tags | (uintptr_t)err_sq | (uintptr_t)row_status | (uintptr_t)n_inliers | (uintptr_t)rms | (uintptr_t)best_iter | (uintptr_t)pred |
           (uintptr_t)n_pred | (uintptr_t)status) & 3) || ((uintptr_t)pose & 7))
         return AGX_ERR_ARG;
     if (tags_per_frame >= (1u << 27)) return AGX_ERR_ARG;
-    *status = board_pose(tags, tags_per_frame, n_tags, tag_status, cols, rows, first_id, spacing_ratio, tag_size, cam, max_err_sq, max_drop,
+    *status = board_pose(lens_model, tags, tags_per_frame, n_tags, tag_status, cols, rows, first_id, spacing_ratio, tag_size, cam, max_err_sq, max_drop,
                          min_tags, iterations, flags, pose, err_sq, row_status, n_inliers, rms, best_iter, pred, n_pred, nullptr);
     return AGX_OK;
     });
@@ -2424,11 +2445,19 @@ int agx_debug_board_pose_sums(const agx_tag *tags, uint32_t tags_per_frame, uint
                               uint32_t first_id, float spacing_ratio, double tag_size, const double *camera, float max_err_sq, uint32_t max_drop,
                               uint32_t min_tags, uint32_t iterations, int flags, uint32_t *status, double *iter_sums)
 {
+    return agx_debug_board_pose_sums_m(tags, tags_per_frame, n_tags, tag_status, cols, rows, first_id, spacing_ratio, tag_size, AGX_LENS_RADTAN,
+                                       camera, max_err_sq, max_drop, min_tags, iterations, flags, status, iter_sums);
+}
+
+int agx_debug_board_pose_sums_m(const agx_tag *tags, uint32_t tags_per_frame, uint32_t n_tags, uint32_t tag_status, uint32_t cols, uint32_t rows,
+                                uint32_t first_id, float spacing_ratio, double tag_size, int lens_model, const double *camera, float max_err_sq,
+                                uint32_t max_drop, uint32_t min_tags, uint32_t iterations, int flags, uint32_t *status, double *iter_sums)
+{
     return agx_guard(nullptr, [&]() -> int {
     if (!status || !iter_sums || !camera || (n_tags && !tags)) return AGX_ERR_ARG;
     agx_camera cam;
     std::memcpy(&cam, camera, sizeof cam);
-    if (!board_fit_args_ok(cols, rows, spacing_ratio, 1, 1, max_err_sq, min_tags, flags) || !pose_args_ok(cam, tag_size, iterations)) return AGX_ERR_ARG;
+    if (!board_fit_args_ok(cols, rows, spacing_ratio, 1, 1, max_err_sq, min_tags, flags) || !pose_args_ok(lens_model, cam, tag_size, iterations)) return AGX_ERR_ARG;
     if ((((uintptr_t)tags | (uintptr_t)status) & 3) || ((uintptr_t)iter_sums & 7) || tags_per_frame >= (1u << 27)) return AGX_ERR_ARG;
     double pose[12];
     std::vector<float> err_sq(n_tags + 1);
@@ -2436,9 +2465,32 @@ int agx_debug_board_pose_sums(const agx_tag *tags, uint32_t tags_per_frame, uint
     std::vector<agx_tag> pred((size_t)cols * rows);
     uint32_t n_inliers = 0, n_pred = 0, best_iter = 0;
     float rms = 0.0f;
-    *status = board_pose(tags, tags_per_frame, n_tags, tag_status, cols, rows, first_id, spacing_ratio, tag_size, cam, max_err_sq, max_drop,
+    *status = board_pose(lens_model, tags, tags_per_frame, n_tags, tag_status, cols, rows, first_id, spacing_ratio, tag_size, cam, max_err_sq, max_drop,
                          min_tags, iterations, flags, pose, err_sq.data(), row_status.data(), &n_inliers, &rms, &best_iter, pred.data(), &n_pred,
                          iter_sums);
+    return AGX_OK;
+    });
+}
+
+int agx_debug_pose_atan(const double *r, uint32_t n, double *out)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (n && (!r || !out)) return AGX_ERR_ARG;
+    for (uint32_t i = 0; i < n; ++i)
+        if (!f64_finite(r[i]) || !(r[i] >= 0.0)) return AGX_ERR_ARG;
+    pose_atan_host(r, n, out);
+    return AGX_OK;
+    });
+}
+
+int agx_debug_pose_project(int lens_model, const double *camera, const double *xyz, uint32_t n, double *uv)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (!camera || (n && (!xyz || !uv))) return AGX_ERR_ARG;
+    agx_camera cam;
+    std::memcpy(&cam, camera, sizeof cam);
+    if (!pose_args_ok(lens_model, cam, 1.0, 0)) return AGX_ERR_ARG;
+    pose_project_host(lens_model, cam, xyz, n, uv);
     return AGX_OK;
     });
 }

@@ -1772,10 +1772,12 @@ uint32_t board_fit(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint3
     return status;
 }
 
-uint32_t board_pose(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint32_t tag_status, uint32_t cols, uint32_t rows, uint32_t first_id,
-                    float spacing_ratio, double tag_size, const agx_camera &cam, float max_err_sq, uint32_t max_drop, uint32_t min_tags,
-                    uint32_t iterations, int flags, double *pose_out, float *err_sq, uint32_t *row_status, uint32_t *n_inliers, float *rms,
-                    uint32_t *best_iter, agx_tag *pred, uint32_t *n_pred, double *iter_sums)
+// (one text for both lens models, as the kernel's)
+template <int LENS>
+static uint32_t board_pose_lens(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint32_t tag_status, uint32_t cols, uint32_t rows,
+                                uint32_t first_id, float spacing_ratio, double tag_size, const agx_camera &cam, float max_err_sq, uint32_t max_drop,
+                                uint32_t min_tags, uint32_t iterations, int flags, double *pose_out, float *err_sq, uint32_t *row_status,
+                                uint32_t *n_inliers, float *rms, uint32_t *best_iter, agx_tag *pred, uint32_t *n_pred, double *iter_sums)
 {
     const FitGeom g = pose_geom(cols, rows, first_id, spacing_ratio);
     const auto refuse = [&](uint32_t status) {
@@ -1808,7 +1810,7 @@ uint32_t board_pose(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint
         for (int l = 0; l < 64; ++l) {
             for (int k = 0; k < FIT_SUMS; ++k) lanes[l][k] = 0.0;
             for (uint32_t r = (uint32_t)l; r < n_tags; r += 64u)
-                if (st[r] == AGX_FIT_ROW_INLIER) pose_seed_accumulate_row(g, cam, lanes[l], tags[r].id, tags[r].xy);
+                if (st[r] == AGX_FIT_ROW_INLIER) pose_seed_accumulate_row<LENS>(g, cam, lanes[l], tags[r].id, tags[r].xy);
         }
         fold(lanes.get(), FIT_SUMS);
         double m[72], h[8];
@@ -1829,7 +1831,7 @@ uint32_t board_pose(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint
             for (int l = 0; l < 64; ++l) {
                 for (int k = 0; k < POSE_SUMS; ++k) lanes[l][k] = 0.0;
                 for (uint32_t r = (uint32_t)l; r < n_tags; r += 64u)
-                    if (st[r] == AGX_FIT_ROW_INLIER) pose_accumulate_row(g, tag_size, cam, cur, lanes[l], tags[r].id, tags[r].xy);
+                    if (st[r] == AGX_FIT_ROW_INLIER) pose_accumulate_row<LENS>(g, tag_size, cam, cur, lanes[l], tags[r].id, tags[r].xy);
             }
             fold(lanes.get(), POSE_SUMS);
             const double cost = lanes[0][27];
@@ -1857,7 +1859,7 @@ uint32_t board_pose(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint
             for (uint32_t r = (uint32_t)l; r < n_tags; r += 64u) {
                 if (st[r] != AGX_FIT_ROW_INLIER) continue;
                 double sum;
-                const float e = pose_row_residual(g, tag_size, cam, pose, tags[r].id, tags[r].xy, &sum);
+                const float e = pose_row_residual<LENS>(g, tag_size, cam, pose, tags[r].id, tags[r].xy, &sum);
                 lanes[l][0] += sum;
                 if (worst_row == 0xffffffffu || e > worst || (e == worst && r < worst_row)) {  // the lowest row at equal residual
                     worst = e;
@@ -1881,7 +1883,7 @@ uint32_t board_pose(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint
     for (uint32_t r = 0; r < n_tags; ++r) {
         row_status[r] = st[r];
         double sum;
-        if (st[r] != AGX_FIT_ROW_OFF_BOARD) err_sq[r] = pose_row_residual(g, tag_size, cam, pose, tags[r].id, tags[r].xy, &sum);
+        if (st[r] != AGX_FIT_ROW_OFF_BOARD) err_sq[r] = pose_row_residual<LENS>(g, tag_size, cam, pose, tags[r].id, tags[r].xy, &sum);
     }
     for (int i = 0; i < 9; ++i) pose_out[i] = pose.R[i];
     for (int i = 0; i < 3; ++i) pose_out[9 + i] = pose.t[i];
@@ -1896,11 +1898,42 @@ uint32_t board_pose(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint
     for (uint32_t t = 0; t < g.n_board; ++t) {
         if (member[t]) continue;
         pred[kept].id = first_id + t;
-        pose_predict(g, tag_size, cam, pose, t, pred[kept].xy);
+        pose_predict<LENS>(g, tag_size, cam, pose, t, pred[kept].xy);
         ++kept;
     }
     *n_pred = kept;
     return status;
+}
+
+uint32_t board_pose(int lens, const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint32_t tag_status, uint32_t cols, uint32_t rows,
+                    uint32_t first_id, float spacing_ratio, double tag_size, const agx_camera &cam, float max_err_sq, uint32_t max_drop,
+                    uint32_t min_tags, uint32_t iterations, int flags, double *pose_out, float *err_sq, uint32_t *row_status, uint32_t *n_inliers,
+                    float *rms, uint32_t *best_iter, agx_tag *pred, uint32_t *n_pred, double *iter_sums)
+{
+    const auto run = lens == AGX_LENS_EQUIDISTANT ? board_pose_lens<AGX_LENS_EQUIDISTANT> : board_pose_lens<AGX_LENS_RADTAN>;
+    return run(tags, tag_cap, n_tags, tag_status, cols, rows, first_id, spacing_ratio, tag_size, cam, max_err_sq, max_drop, min_tags, iterations,
+               flags, pose_out, err_sq, row_status, n_inliers, rms, best_iter, pred, n_pred, iter_sums);
+}
+
+void pose_atan_host(const double *r, uint32_t n, double *out)
+{
+    for (uint32_t i = 0; i < n; ++i) out[i] = pose_atan(r[i]);
+}
+
+void pose_project_host(int lens, const agx_camera &cam, const double *xyz, uint32_t n, double *uv)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        const Pose p = {{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, {0.0, 0.0, xyz[3 * i + 2]}};
+        bool ok;
+        if (lens == AGX_LENS_EQUIDISTANT) {
+            PosePointEqui q;
+            if ((ok = pose_project<AGX_LENS_EQUIDISTANT>(cam, p, xyz[3 * i], xyz[3 * i + 1], q))) uv[2 * i] = q.u, uv[2 * i + 1] = q.v;
+        } else {
+            PosePoint q;
+            if ((ok = pose_project<AGX_LENS_RADTAN>(cam, p, xyz[3 * i], xyz[3 * i + 1], q))) uv[2 * i] = q.u, uv[2 * i + 1] = q.v;
+        }
+        if (!ok) uv[2 * i] = uv[2 * i + 1] = std::numeric_limits<double>::quiet_NaN();
+    }
 }
 
 }  // namespace agx

@@ -1189,7 +1189,8 @@ class TagDetector:
     def board_pose_enqueue(self, tags, n_tags, cols, rows, camera, pose, err_sq, row_status, n_inliers, rms, best_iter, pred, n_pred, status,
                            tag_size=1.0, first_id=0, spacing_ratio=0.3, max_err_sq=4.0, max_drop=0, min_tags=1, iterations=10,
                            predict_missing=False, tag_status=None):
-        """Per frame the pose of the printed board in the camera frame under `camera` (a Camera: pinhole + radial-tangential)
+        """Per frame the pose of the printed board in the camera frame under `camera` (a Camera: pinhole + radial-tangential, or
+        Camera.equidistant's fisheye model -- the camera's model attribute picks the kernel)
         through every corner of the frame's tag table, its outlier rounds and the predicted corners of the layout's tags through
         the lens model (board_pose, the host form, says what is computed), in device tensors and stream-ordered behind torch's
         current stream; nothing to fetch.  tags, n_tags, tag_status and err_sq, row_status, n_inliers, rms, pred, n_pred, status
@@ -1214,11 +1215,14 @@ class TagDetector:
                 tensor(rms, torch.float32, (n,), "rms"), tensor(best_iter, torch.int32, (n,), "best_iter"),
                 tensor(pred, torch.int32, (n, n_board, 9), "pred"), tensor(n_pred, torch.int32, (n,), "n_pred"),
                 tensor(status, torch.int32, (n,), "status"))
-        cam = _camera(camera)
+        model, cam = _camera(camera)
         self._follow_torch_stream(tags)
-        rc = self._lib.agx_board_pose_enqueue(self._h, n, tags.data_ptr(), tpf, *ins, int(cols), int(rows), int(first_id), float(spacing_ratio),
-                                              float(tag_size), cam, float(max_err_sq), int(max_drop), int(min_tags), int(iterations),
-                                              _ffi.AGX_FIT_PREDICT_MISSING if predict_missing else 0, *outs)
+        head = (self._h, n, tags.data_ptr(), tpf, *ins, int(cols), int(rows), int(first_id), float(spacing_ratio), float(tag_size))
+        rest = (cam, float(max_err_sq), int(max_drop), int(min_tags), int(iterations), _ffi.AGX_FIT_PREDICT_MISSING if predict_missing else 0, *outs)
+        if model == _ffi.AGX_LENS_RADTAN:  # (the call of a radial-tangential camera is the one it was)
+            rc = self._lib.agx_board_pose_enqueue(*head, *rest)
+        else:
+            rc = self._lib.agx_board_pose_enqueue_m(*head, model, *rest)
         if rc == _ffi.AGX_OK:  # (a refused argument leaves the batch in flight where it is)
             self._replaces_batch()
         self._check(rc)
@@ -2089,18 +2093,41 @@ def board_fit(tags, cols, rows, img_size, first_id=0, spacing_ratio=0.3, max_err
 
 class Camera(namedtuple("Camera", "fx fy cx cy k1 k2 p1 p2 k3", defaults=(0.0, 0.0, 0.0, 0.0, 0.0))):
     """agx_camera: the pinhole + radial-tangential model (OpenCV's; Kalibr's pinhole-radtan with k3 = 0).  Camera(fx, fy, cx, cy)
-    is a pinhole."""
+    is a pinhole.  model is the lens model the nine numbers are read under (AGX_LENS_*): AGX_LENS_RADTAN here,
+    AGX_LENS_EQUIDISTANT for a camera made by Camera.equidistant."""
     __slots__ = ()
+    model = _ffi.AGX_LENS_RADTAN
 
     def as_doubles(self):
         """The nine doubles agx_board_pose_enqueue / _tail read."""
         return (C.c_double * 9)(*[float(v) for v in self])
 
+    @staticmethod
+    def equidistant(fx, fy, cx, cy, k1=0.0, k2=0.0, k3=0.0, k4=0.0):
+        """The pinhole-equidistant model (Kalibr's pinhole-equi, OpenCV's fisheye, Kannala-Brandt with four coefficients):
+        theta = atan(r), theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8), (u, v) = (fx, fy) theta_d (x, y) / r
+        + (cx, cy).  A Camera whose model is AGX_LENS_EQUIDISTANT and whose nine numbers are fx, fy, cx, cy, k1, k2, k3, k4, 0."""
+        return _EquidistantCamera(fx, fy, cx, cy, k1, k2, k3, k4, 0.0)
+
+
+class _EquidistantCamera(Camera):
+    """Camera.equidistant's: the same nine numbers in the order the equidistant model reads them (k3, k4 by name; p1, p2 are the
+    tuple's sixth and seventh fields, which hold k3 and k4)."""
+    __slots__ = ()
+    model = _ffi.AGX_LENS_EQUIDISTANT
+    k3 = property(lambda self: self[6])
+    k4 = property(lambda self: self[7])
+
+    def __repr__(self):
+        return "Camera.equidistant(fx=%r, fy=%r, cx=%r, cy=%r, k1=%r, k2=%r, k3=%r, k4=%r)" % tuple(self[:8])
+
 
 def _camera(camera):
+    """-> (AGX_LENS_*, the nine doubles) of a Camera or of nine numbers (radial-tangential)."""
     if camera is None:
         raise AgxError(_ffi.AGX_ERR_ARG, "camera must be given")
-    return (camera if isinstance(camera, Camera) else Camera(*camera)).as_doubles()
+    camera = camera if isinstance(camera, Camera) else Camera(*camera)
+    return camera.model, camera.as_doubles()
 
 
 def board_pose(tags, cols, rows, camera, tag_size=1.0, first_id=0, spacing_ratio=0.3, max_err_sq=4.0, max_drop=0, min_tags=1, iterations=10,
@@ -2123,12 +2150,19 @@ def board_pose(tags, cols, rows, camera, tag_size=1.0, first_id=0, spacing_ratio
     err, rst = np.full(max(n, 1), np.nan, np.float32), np.zeros(max(n, 1), np.uint32)
     pred = np.zeros(n_board, TagDetector.TAG_DTYPE)
     n_inl, n_pred, status, rms, best = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_float(0), C.c_uint32(0)
-    head = (t.ctypes.data if n else None, cap, n, int(tag_status), int(cols), int(rows), int(first_id), float(spacing_ratio), float(tag_size),
-            _camera(camera), float(max_err_sq), int(max_drop), int(min_tags), int(iterations), _ffi.AGX_FIT_PREDICT_MISSING if predict_missing else 0)
-    st = _ffi.lib().agx_board_pose_tail(*head, pose.ctypes.data, err.ctypes.data, rst.ctypes.data, C.byref(n_inl), C.byref(rms), C.byref(best),
-                                        pred.ctypes.data, C.byref(n_pred), C.byref(status))
-    if st == _ffi.AGX_OK and return_iter_sums:
-        st = _ffi.lib().agx_debug_board_pose_sums(*head, C.byref(C.c_uint32(0)), sums.ctypes.data)
+    model, cam = _camera(camera)
+    head = (t.ctypes.data if n else None, cap, n, int(tag_status), int(cols), int(rows), int(first_id), float(spacing_ratio), float(tag_size))
+    rest = (cam, float(max_err_sq), int(max_drop), int(min_tags), int(iterations), _ffi.AGX_FIT_PREDICT_MISSING if predict_missing else 0)
+    outs = (pose.ctypes.data, err.ctypes.data, rst.ctypes.data, C.byref(n_inl), C.byref(rms), C.byref(best), pred.ctypes.data, C.byref(n_pred),
+            C.byref(status))
+    if model == _ffi.AGX_LENS_RADTAN:  # (the calls of a radial-tangential camera are the ones they were)
+        st = _ffi.lib().agx_board_pose_tail(*head, *rest, *outs)
+        if st == _ffi.AGX_OK and return_iter_sums:
+            st = _ffi.lib().agx_debug_board_pose_sums(*head, *rest, C.byref(C.c_uint32(0)), sums.ctypes.data)
+    else:
+        st = _ffi.lib().agx_board_pose_tail_m(*head, model, *rest, *outs)
+        if st == _ffi.AGX_OK and return_iter_sums:
+            st = _ffi.lib().agx_debug_board_pose_sums_m(*head, model, *rest, C.byref(C.c_uint32(0)), sums.ctypes.data)
     if st != _ffi.AGX_OK:
         raise AgxError(st)
     out = {"status": status.value, "n_inliers": n_inl.value, "n_pred": n_pred.value}

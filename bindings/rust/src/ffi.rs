@@ -165,6 +165,8 @@ pub const AGX_FIT_INPUT: c_int = 4;
 pub const AGX_FIT_ROW_INLIER: c_int = 0;
 pub const AGX_FIT_ROW_OUTLIER: c_int = 1;
 pub const AGX_FIT_ROW_OFF_BOARD: c_int = 2;
+pub const AGX_LENS_RADTAN: c_int = 0;
+pub const AGX_LENS_EQUIDISTANT: c_int = 1;
 // agx_debug_fetch items
 pub const AGX_DBG_BLUR: c_int = 0;
 pub const AGX_DBG_RESP: c_int = 1;
@@ -383,6 +385,24 @@ extern "C" {
                                      first_id: u32, spacing_ratio: c_float, tag_size: c_double, camera: *const c_double,
                                      max_err_sq: c_float, max_drop: u32, min_tags: u32, iterations: u32, flags: c_int,
                                      status: *mut u32, iter_sums: *mut c_double) -> c_int;
+    // lens_model: AGX_LENS_*; under AGX_LENS_EQUIDISTANT camera is fx, fy, cx, cy, k1, k2, k3, k4, 0
+    pub fn agx_board_pose_enqueue_m(det: *mut agx_detector, n_frames: c_int, d_tags: *const agx_tag, tags_per_frame: u32, d_n_tags: *const u32,
+                                    d_tag_status: *const u32, cols: u32, rows: u32, first_id: u32, spacing_ratio: c_float, tag_size: c_double,
+                                    lens_model: c_int, camera: *const c_double, max_err_sq: c_float, max_drop: u32, min_tags: u32,
+                                    iterations: u32, flags: c_int, d_pose: *mut c_double, d_err_sq: *mut c_float, d_row_status: *mut u32,
+                                    d_n_inliers: *mut u32, d_rms: *mut c_float, d_best_iter: *mut u32, d_pred: *mut agx_tag,
+                                    d_n_pred: *mut u32, d_status: *mut u32) -> c_int;
+    pub fn agx_board_pose_tail_m(tags: *const agx_tag, tags_per_frame: u32, n_tags: u32, tag_status: u32, cols: u32, rows: u32, first_id: u32,
+                                 spacing_ratio: c_float, tag_size: c_double, lens_model: c_int, camera: *const c_double, max_err_sq: c_float,
+                                 max_drop: u32, min_tags: u32, iterations: u32, flags: c_int, pose: *mut c_double, err_sq: *mut c_float,
+                                 row_status: *mut u32, n_inliers: *mut u32, rms: *mut c_float, best_iter: *mut u32, pred: *mut agx_tag,
+                                 n_pred: *mut u32, status: *mut u32) -> c_int;
+    pub fn agx_debug_board_pose_sums_m(tags: *const agx_tag, tags_per_frame: u32, n_tags: u32, tag_status: u32, cols: u32, rows: u32,
+                                       first_id: u32, spacing_ratio: c_float, tag_size: c_double, lens_model: c_int, camera: *const c_double,
+                                       max_err_sq: c_float, max_drop: u32, min_tags: u32, iterations: u32, flags: c_int,
+                                       status: *mut u32, iter_sums: *mut c_double) -> c_int;
+    pub fn agx_debug_pose_atan(r: *const c_double, n: u32, out: *mut c_double) -> c_int;
+    pub fn agx_debug_pose_project(lens_model: c_int, camera: *const c_double, xyz: *const c_double, n: u32, uv: *mut c_double) -> c_int;
     pub fn agx_debug_blur_weights(sigma: c_float, weights: *mut c_float, cap: c_int, radius: *mut c_int) -> c_int;
     pub fn agx_debug_refine_constants(half_size_patch: c_int, cone: *mut c_float, pmat: *mut c_float, cap_points: c_int,
                                       n_points: *mut c_int) -> c_int;

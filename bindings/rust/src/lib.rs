@@ -808,6 +808,25 @@ pub struct Camera {
     pub k3: f64,
 }
 
+/// The lens model `board_pose_tail_m` reads a `Camera` under (`AGX_LENS_*`).
+#[repr(i32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq, Default)]
+pub enum LensModel {
+    /// pinhole + radial-tangential: `Camera`'s fields as they are named
+    #[default]
+    Radtan = 0,
+    /// pinhole-equidistant (Kalibr's pinhole-equi, OpenCV's fisheye): `Camera::equidistant`
+    Equidistant = 1,
+}
+
+impl Camera {
+    /// The nine doubles of the pinhole-equidistant model, `fx, fy, cx, cy, k1, k2, k3, k4, 0`: `p1` holds `k3`, `p2` holds `k4`,
+    /// `k3` is 0.  To be passed with `LensModel::Equidistant`.
+    pub fn equidistant(fx: f64, fy: f64, cx: f64, cy: f64, k1: f64, k2: f64, k3: f64, k4: f64) -> Camera {
+        Camera { fx, fy, cx, cy, k1, k2, p1: k3, p2: k4, k3: 0.0 }
+    }
+}
+
 /// What `board_pose_tail` found for one frame.
 #[derive(Clone, Debug)]
 pub struct BoardPose {
@@ -834,6 +853,14 @@ pub struct BoardPose {
 /// `AGX_FIT_FEW`, `AGX_FIT_SINGULAR` or `AGX_FIT_INPUT`.  Panics where the library refuses the arguments.
 pub fn board_pose_tail(tags: &[(u32, [(f32, f32); 4])], layout: &BoardLayout, camera: &Camera, tag_size: f64, max_err_sq: f32, max_drop: u32,
                        min_tags: u32, iterations: u32, predict_missing: bool) -> Result<BoardPose, u32> {
+    board_pose_tail_m(tags, layout, LensModel::Radtan, camera, tag_size, max_err_sq, max_drop, min_tags, iterations, predict_missing)
+}
+
+/// `board_pose_tail` under the lens model `model`: with `LensModel::Equidistant` and a `Camera::equidistant` the projection is
+/// `theta = atan(r)`, `theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8)`, `(u, v) = (fx, fy) theta_d (x, y) / r + (cx, cy)`;
+/// everything else is `board_pose_tail`'s.  `LensModel::Radtan` is that call, and its bytes.
+pub fn board_pose_tail_m(tags: &[(u32, [(f32, f32); 4])], layout: &BoardLayout, model: LensModel, camera: &Camera, tag_size: f64, max_err_sq: f32,
+                         max_drop: u32, min_tags: u32, iterations: u32, predict_missing: bool) -> Result<BoardPose, u32> {
     let table: Vec<ffi::agx_tag> = tags.iter().map(|t| ffi::agx_tag {
         id: t.0,
         xy: [t.1[0].0, t.1[0].1, t.1[1].0, t.1[1].1, t.1[2].0, t.1[2].1, t.1[3].0, t.1[3].1],
@@ -847,13 +874,13 @@ pub fn board_pose_tail(tags: &[(u32, [(f32, f32); 4])], layout: &BoardLayout, ca
     let mut pred = vec![ffi::agx_tag { id: 0, xy: [0.0; 8] }; n_board];
     let (mut n_inliers, mut n_pred, mut status, mut best_iter, mut rms) = (0u32, 0u32, 0u32, 0u32, 0f32);
     let st = unsafe {
-        ffi::agx_board_pose_tail(table.as_ptr(), table.len() as u32, table.len() as u32, ffi::AGX_TAGS_OK as u32, layout.cols, layout.rows,
-                                 layout.first_id, layout.spacing_ratio, tag_size, cam.as_ptr(), max_err_sq, max_drop, min_tags, iterations,
-                                 if predict_missing { ffi::AGX_FIT_PREDICT_MISSING } else { 0 }, pose.as_mut_ptr(), err.as_mut_ptr(),
-                                 row_status.as_mut_ptr(), &mut n_inliers, &mut rms, &mut best_iter, pred.as_mut_ptr(), &mut n_pred,
-                                 &mut status)
+        ffi::agx_board_pose_tail_m(table.as_ptr(), table.len() as u32, table.len() as u32, ffi::AGX_TAGS_OK as u32, layout.cols, layout.rows,
+                                   layout.first_id, layout.spacing_ratio, tag_size, model as c_int, cam.as_ptr(), max_err_sq, max_drop, min_tags,
+                                   iterations, if predict_missing { ffi::AGX_FIT_PREDICT_MISSING } else { 0 }, pose.as_mut_ptr(),
+                                   err.as_mut_ptr(), row_status.as_mut_ptr(), &mut n_inliers, &mut rms, &mut best_iter, pred.as_mut_ptr(),
+                                   &mut n_pred, &mut status)
     };
-    assert_eq!(st, ffi::AGX_OK, "agx_board_pose_tail failed: {}", st);
+    assert_eq!(st, ffi::AGX_OK, "agx_board_pose_tail_m failed: {}", st);
     if status as c_int != ffi::AGX_FIT_OK && status as c_int != ffi::AGX_FIT_LOOSE {
         return Err(status);
     }

@@ -1182,6 +1182,54 @@ int agx_debug_board_pose_sums(const agx_tag *tags, uint32_t tags_per_frame, uint
                               float max_err_sq, uint32_t max_drop, uint32_t min_tags, uint32_t iterations, int flags,
                               uint32_t *status, double *iter_sums);
 
+/* The same three calls under a lens model of the caller's choice: int lens_model in front of camera, everything else -- tables,
+ * layout, seed, rounds, statuses, results, contract -- as above.  AGX_LENS_RADTAN: the calls above, and their bytes.
+ * AGX_LENS_EQUIDISTANT: the pinhole-equidistant model of wide-angle and fisheye lenses (Kalibr's pinhole-equi, OpenCV's fisheye,
+ * Kannala-Brandt with four coefficients), which no radial-tangential polynomial follows beyond a field angle of about 45 degrees.
+ * For a point (X, Y, Z) in the camera frame with Z > 0: x = X/Z, y = Y/Z, r = sqrt(x^2 + y^2), theta = atan(r),
+ * theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8), s = theta_d / r, u = fx s x + cx, v = fy s y + cy.
+ * A point whose Z is not > 0 has no projection, as above: the model is not carried behind the camera.
+ * camera: nine doubles in the order fx, fy, cx, cy, k1, k2, k3, k4, 0, HOST memory, copied by the call; the ninth must be 0
+ * (struct agx_camera names the radial-tangential order only: its p1 and p2 hold k3 and k4 here).
+ * Arithmetic (csrc/board_pose_math.h, for both forms): the square root of r as above; atan by + - * / alone (1 / r above 1, a
+ * subtraction formula against the break points k / 8, an odd polynomial through z^13), within 1e-14 of the correctly rounded
+ * value (agx_debug_pose_atan hands it out).  Small-r rule: for x^2 + y^2 < 2^-13, theta / r is the series
+ * 1 - r^2/3 + r^4/5 - r^6/7 + r^8/9 and the Jacobian's (ds/dr) / r is its limit 2 (k1 - 1/3) + 4 (k2 - k1 + 1/5) r^2: a point on
+ * the optical axis projects to (cx, cy) exactly and nothing is divided by zero.  Jacobian: analytic, d theta / d r = 1 / (1 + r^2),
+ * no further transcendental.  Seed: an observed pixel goes to theta_d = |((u - cx) / fx, (v - cy) / fy)|, to theta by 8 Newton
+ * steps on theta D(theta) = theta_d from theta = theta_d (no early exit), theta >= 1.5 rad is clamped to 1.5 rad (the seed only: a
+ * pinhole ray must exist; the refinement runs through the forward model and has no such limit), and to r = tan(theta) by the
+ * series of tan(theta / 8) through its 15th power and 3 doublings t <- 2 t / (1 - t^2); then the homography and its
+ * decomposition as above.  A value that is not finite ends as AGX_FIT_SINGULAR.
+ * AGX_ERR_ARG (a batch in flight stays where it is): the calls' own list, a lens_model that is neither, and under
+ * AGX_LENS_EQUIDISTANT a ninth double that is not 0. */
+enum { AGX_LENS_RADTAN = 0, AGX_LENS_EQUIDISTANT = 1 };
+int agx_board_pose_enqueue_m(agx_detector *det, int n_frames,
+                             const agx_tag *d_tags, uint32_t tags_per_frame, const uint32_t *d_n_tags, const uint32_t *d_tag_status,
+                             uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
+                             int lens_model, const double *camera,
+                             float max_err_sq, uint32_t max_drop, uint32_t min_tags, uint32_t iterations, int flags,
+                             double *d_pose, float *d_err_sq, uint32_t *d_row_status,
+                             uint32_t *d_n_inliers, float *d_rms, uint32_t *d_best_iter,
+                             agx_tag *d_pred, uint32_t *d_n_pred, uint32_t *d_status);
+int agx_board_pose_tail_m(const agx_tag *tags, uint32_t tags_per_frame, uint32_t n_tags, uint32_t tag_status,
+                          uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
+                          int lens_model, const double *camera,
+                          float max_err_sq, uint32_t max_drop, uint32_t min_tags, uint32_t iterations, int flags,
+                          double *pose, float *err_sq, uint32_t *row_status, uint32_t *n_inliers, float *rms, uint32_t *best_iter,
+                          agx_tag *pred, uint32_t *n_pred, uint32_t *status);
+int agx_debug_board_pose_sums_m(const agx_tag *tags, uint32_t tags_per_frame, uint32_t n_tags, uint32_t tag_status,
+                                uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
+                                int lens_model, const double *camera,
+                                float max_err_sq, uint32_t max_drop, uint32_t min_tags, uint32_t iterations, int flags,
+                                uint32_t *status, double *iter_sums);
+/* For tests of the arithmetic, no handle and no device: the host form's atan of r [n] (each >= 0 and finite) into out [n]; and
+ * its projection of n points (X, Y, Z) of the camera frame, xyz [n][3], into uv [n][2] under lens_model and camera ((NaN, NaN)
+ * where Z is not > 0).  AGX_ERR_ARG: a NULL array with n > 0, an r that is negative or not finite; agx_board_pose_tail_m's
+ * rules on lens_model and camera. */
+int agx_debug_pose_atan(const double *r, uint32_t n, double *out);
+int agx_debug_pose_project(int lens_model, const double *camera, const double *xyz, uint32_t n, double *uv);
+
 /* ---- detector groups: several GPUs of one node driven from ONE process ----------------- */
 
 /* The reference's detect(&self) is stateless, so a batch shards by frame:
