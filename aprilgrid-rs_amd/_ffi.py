@@ -43,6 +43,7 @@ AGX_FIT_OK, AGX_FIT_LOOSE, AGX_FIT_FEW, AGX_FIT_SINGULAR, AGX_FIT_INPUT = 0, 1, 
 AGX_FIT_ROW_INLIER, AGX_FIT_ROW_OUTLIER, AGX_FIT_ROW_OFF_BOARD = 0, 1, 2
 # the lens model of agx_board_pose_enqueue_m / _tail_m: pinhole + radial-tangential, pinhole-equidistant (fisheye)
 AGX_LENS_RADTAN, AGX_LENS_EQUIDISTANT = 0, 1
+AGX_MAP_NONE = -2 ** 31  # both words of a rectification map's entry without a source pixel (agx_rectify_map_enqueue / _tail)
 AGX_DBG_BLUR, AGX_DBG_RESP, AGX_DBG_MIN, AGX_DBG_CENTERS, AGX_DBG_REFINED = 0, 1, 2, 3, 4
 AGX_N_KERNELS = 5
 
@@ -188,6 +189,14 @@ SYMBOLS = {
                                               C.POINTER(C.c_uint32), _P]),
     "agx_debug_pose_atan": (C.c_int, [_P, C.c_uint32, _P]),
     "agx_debug_pose_project": (C.c_int, [C.c_int, C.POINTER(C.c_double), _P, C.c_uint32, _P]),
+    "agx_rectify_map_enqueue": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t]),
+    "agx_rectify_map_tail": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t]),
+    "agx_remap_enqueue": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, _P, C.c_size_t, C.c_int, C.c_int, _P,
+                                    C.c_size_t, C.c_size_t, C.c_uint32]),
+    "agx_remap_tail": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, _P, C.c_size_t, C.c_int, C.c_int, _P, C.c_size_t,
+                                 C.c_size_t, C.c_uint32]),
+    "agx_rectified_points_enqueue": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, C.c_size_t]),
+    "agx_rectified_points_tail": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, C.c_size_t]),
     "agx_group_create": (C.c_int, [C.c_int, C.POINTER(Params), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "agx_group_destroy": (None, [_P]),
     "agx_group_size": (C.c_int, [_P]),

@@ -24,6 +24,7 @@
 #include "decode_stages.h"
 #include "detector_internal.h"
 #include "host_tail.hpp"
+#include "rectify.h"
 #include "tail_kernels.h"
 
 using namespace agx;
@@ -2491,6 +2492,153 @@ int agx_debug_pose_project(int lens_model, const double *camera, const double *x
     std::memcpy(&cam, camera, sizeof cam);
     if (!pose_args_ok(lens_model, cam, 1.0, 0)) return AGX_ERR_ARG;
     pose_project_host(lens_model, cam, xyz, n, uv);
+    return AGX_OK;
+    });
+}
+
+// ---- rectified batches (rectify.hip: k_rectify_map, k_remap, k_rectified_points and the host forms) -------------------------------
+static const char *kRectifyGeomRule =
+    "lens_model AGX_LENS_RADTAN or AGX_LENS_EQUIDISTANT (its ninth double 0), every camera field finite with fx and fy > 0, new_camera "
+    "finite with fx' and fy' > 0, rotation NULL or finite";
+
+static bool rectify_map_args(int lens_model, const double *camera, const double *new_camera, const double *rotation, int src_width,
+                             int src_height, int dst_width, int dst_height, int *map, size_t map_row_stride_bytes, RectifyMapArgs &a,
+                             const char **why)
+{
+    a.lens = lens_model;
+    if (!rectify_geom(lens_model, camera, new_camera, rotation, a.g)) return *why = kRectifyGeomRule, false;
+    a.src_w = src_width;
+    a.src_h = src_height;
+    a.dst_w = dst_width;
+    a.dst_h = dst_height;
+    a.map = map;
+    a.map_stride = map_row_stride_bytes;
+    return !(*why = rectify_map_args_bad(a));
+}
+
+int agx_rectify_map_enqueue(agx_detector *det, int lens_model, const double *camera, const double *new_camera, const double *rotation,
+                            int src_width, int src_height, int dst_width, int dst_height, int *d_map, size_t map_row_stride_bytes)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    RectifyMapArgs a{};
+    const char *why = nullptr;
+    if (!rectify_map_args(lens_model, camera, new_camera, rotation, src_width, src_height, dst_width, dst_height, d_map, map_row_stride_bytes, a, &why))
+        return fail(det, AGX_ERR_ARG, why);
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // and there is nothing of this one to be fetched
+    const hipError_t e = (hipError_t)launch_rectify_map(a, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_rectify_map: ") + hipGetErrorString(e));
+    return AGX_OK;
+    });
+}
+
+int agx_rectify_map_tail(int lens_model, const double *camera, const double *new_camera, const double *rotation, int src_width, int src_height,
+                         int dst_width, int dst_height, int *map, size_t map_row_stride_bytes)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    RectifyMapArgs a{};
+    const char *why = nullptr;
+    if (!rectify_map_args(lens_model, camera, new_camera, rotation, src_width, src_height, dst_width, dst_height, map, map_row_stride_bytes, a, &why))
+        return AGX_ERR_ARG;
+    rectify_map_host(a);
+    return AGX_OK;
+    });
+}
+
+static RemapArgs remap_args(const void *src, int n_frames, int src_width, int src_height, size_t src_row_stride_bytes, size_t src_frame_stride_bytes,
+                            int format, const int *map, size_t map_row_stride_bytes, int dst_width, int dst_height, void *dst,
+                            size_t dst_row_stride_bytes, size_t dst_frame_stride_bytes, uint32_t border)
+{
+    RemapArgs a{};
+    a.src = src;
+    a.n_frames = n_frames;
+    a.src_w = src_width;
+    a.src_h = src_height;
+    a.src_row_stride = src_row_stride_bytes;
+    a.src_frame_stride = src_frame_stride_bytes;
+    a.format = format;
+    a.map = map;
+    a.map_stride = map_row_stride_bytes;
+    a.dst_w = dst_width;
+    a.dst_h = dst_height;
+    a.dst = dst;
+    a.dst_row_stride = dst_row_stride_bytes;
+    a.dst_frame_stride = dst_frame_stride_bytes;
+    a.border = border;
+    return a;
+}
+
+int agx_remap_enqueue(agx_detector *det, const void *d_src, int n_frames, int src_width, int src_height, size_t src_row_stride_bytes,
+                      size_t src_frame_stride_bytes, int format, const int *d_map, size_t map_row_stride_bytes, int dst_width, int dst_height,
+                      void *d_dst, size_t dst_row_stride_bytes, size_t dst_frame_stride_bytes, uint32_t border)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    const RemapArgs a = remap_args(d_src, n_frames, src_width, src_height, src_row_stride_bytes, src_frame_stride_bytes, format, d_map,
+                                   map_row_stride_bytes, dst_width, dst_height, d_dst, dst_row_stride_bytes, dst_frame_stride_bytes, border);
+    if (const char *why = remap_args_bad(a)) return fail(det, AGX_ERR_ARG, why);
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // and there is nothing of this one to be fetched
+    const hipError_t e = (hipError_t)launch_remap(a, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_remap: ") + hipGetErrorString(e));
+    return AGX_OK;
+    });
+}
+
+int agx_remap_tail(const void *src, int n_frames, int src_width, int src_height, size_t src_row_stride_bytes, size_t src_frame_stride_bytes,
+                   int format, const int *map, size_t map_row_stride_bytes, int dst_width, int dst_height, void *dst, size_t dst_row_stride_bytes,
+                   size_t dst_frame_stride_bytes, uint32_t border)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    const RemapArgs a = remap_args(src, n_frames, src_width, src_height, src_row_stride_bytes, src_frame_stride_bytes, format, map,
+                                   map_row_stride_bytes, dst_width, dst_height, dst, dst_row_stride_bytes, dst_frame_stride_bytes, border);
+    if (remap_args_bad(a)) return AGX_ERR_ARG;
+    remap_host(a);
+    return AGX_OK;
+    });
+}
+
+static bool rectified_points_args(int lens_model, const double *camera, const double *new_camera, const double *rotation, const void *points,
+                                  size_t point_stride_bytes, uint32_t n_points, void *out, size_t out_stride_bytes, RectifiedPointsArgs &a,
+                                  const char **why)
+{
+    a.lens = lens_model;
+    if (!rectify_geom(lens_model, camera, new_camera, rotation, a.g)) return *why = kRectifyGeomRule, false;
+    a.points = points;
+    a.stride = point_stride_bytes;
+    a.n = n_points;
+    a.out = out;
+    a.out_stride = out_stride_bytes;
+    return !(*why = rectified_points_args_bad(a));
+}
+
+int agx_rectified_points_enqueue(agx_detector *det, int lens_model, const double *camera, const double *new_camera, const double *rotation,
+                                 const void *d_points, size_t point_stride_bytes, uint32_t n_points, void *d_out, size_t out_stride_bytes)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    RectifiedPointsArgs a{};
+    const char *why = nullptr;
+    if (!rectified_points_args(lens_model, camera, new_camera, rotation, d_points, point_stride_bytes, n_points, d_out, out_stride_bytes, a, &why))
+        return fail(det, AGX_ERR_ARG, why);
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // and there is nothing of this one to be fetched
+    const hipError_t e = (hipError_t)launch_rectified_points(a, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_rectified_points: ") + hipGetErrorString(e));
+    return AGX_OK;
+    });
+}
+
+int agx_rectified_points_tail(int lens_model, const double *camera, const double *new_camera, const double *rotation, const void *points,
+                              size_t point_stride_bytes, uint32_t n_points, void *out, size_t out_stride_bytes)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    RectifiedPointsArgs a{};
+    const char *why = nullptr;
+    if (!rectified_points_args(lens_model, camera, new_camera, rotation, points, point_stride_bytes, n_points, out, out_stride_bytes, a, &why))
+        return AGX_ERR_ARG;
+    rectified_points_host(a);
     return AGX_OK;
     });
 }

@@ -1227,6 +1227,115 @@ class TagDetector:
             self._replaces_batch()
         self._check(rc)
 
+    # ---- rectified batches: the lens model applied to the pixels (csrc/rectify.hip) ------------------------------------------
+    def _enqueued(self, rc):
+        if rc == _ffi.AGX_OK:  # (a refused argument leaves the batch in flight where it is)
+            self._replaces_batch()
+        self._check(rc)
+
+    def rectify_map_enqueue(self, camera, src_size, dst_size=None, new_camera=None, rotation=None, out=None):
+        """rectify_map (the host form says what is computed) on the device, stream-ordered behind torch's current stream; nothing
+        to fetch.  -> the map, an int32 device tensor [dst_h, dst_w, 2]; out: the caller's (rows may be padded: stride(0) even,
+        stride(1) = 2, stride(2) = 1)."""
+        import torch
+        model, cam, ncam, rot, (sw, sh), (dw, dh) = _rectify_args(camera, src_size, dst_size, new_camera, rotation)
+        if out is None:
+            if not (1 <= dw <= 16384 and 1 <= dh <= 16384):
+                raise AgxError(_ffi.AGX_ERR_ARG, "dst_size must be in 1 .. 16384")
+            out = torch.empty((dh, dw, 2), dtype=torch.int32, device="cuda:%d" % self.device)
+        elif not (getattr(out, "is_cuda", False) and out.dtype == torch.int32 and tuple(out.shape) == (dh, dw, 2) and out.stride(2) == 1
+                  and out.stride(1) == 2 and out.device.index == self.device):
+            raise AgxError(_ffi.AGX_ERR_ARG, "out must be an int32 tensor [dst_h, dst_w, 2] on the detector's device whose rows are packed")
+        self._follow_torch_stream(out)
+        self._enqueued(self._lib.agx_rectify_map_enqueue(self._h, model, cam, ncam, rot, sw, sh, dw, dh, out.data_ptr(),
+                                                         (out.stride(0) if dh > 1 else 2 * dw) * 4))
+        return out
+
+    @staticmethod
+    def _gray_batch(t, what):
+        """-> (agx_format, pixel bytes) of a device tensor [N, H, W] uint8 / int16 / uint16 whose pixels of a row are adjacent."""
+        import torch
+        if not (getattr(t, "is_cuda", False) and t.dim() == 3 and t.stride(2) == 1 and min(t.shape) > 0):
+            raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a device tensor [N, H, W] with adjacent pixels in a row" % what)
+        if t.dtype == torch.uint8:
+            return _ffi.AGX_L8, 1
+        if t.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)):
+            return _ffi.AGX_L16, 2
+        raise AgxError(_ffi.AGX_ERR_ARG, "%s must be uint8 (AGX_L8) or 16-bit (AGX_L16)" % what)
+
+    def remap_enqueue(self, frames, map, out=None, border=0):
+        """remap (the host form says what is computed) of a device batch [N, H, W] uint8 / 16-bit through `map` (an int32 device
+        tensor [dst_h, dst_w, 2]: rectify_map_enqueue's, or the caller's own) into out [N, dst_h, dst_w] of the same dtype (made if
+        None), stream-ordered behind torch's current stream; nothing to fetch.  frames, map and out may be views with padded rows
+        and frames.  -> out."""
+        import torch
+        fmt, px = self._gray_batch(frames, "frames")
+        if not (getattr(map, "is_cuda", False) and map.dtype == torch.int32 and map.dim() == 3 and map.shape[2] == 2 and map.stride(2) == 1
+                and map.stride(1) == 2 and map.device == frames.device):
+            raise AgxError(_ffi.AGX_ERR_ARG, "map must be an int32 tensor [dst_h, dst_w, 2] on the frames' device whose rows are packed")
+        n, dh, dw = int(frames.shape[0]), int(map.shape[0]), int(map.shape[1])
+        if out is None:
+            out = torch.empty((n, dh, dw), dtype=frames.dtype, device=frames.device)
+        elif self._gray_batch(out, "out")[0] != fmt or tuple(out.shape) != (n, dh, dw) or out.device != frames.device:
+            raise AgxError(_ffi.AGX_ERR_ARG, "out must be a tensor [N, dst_h, dst_w] of the frames' dtype on their device")
+        self._follow_torch_stream(frames)
+        rs = lambda t: (t.stride(1) if t.shape[1] > 1 else t.shape[2]) * px  # (a lone row or frame has no stride of its own)
+        fs = lambda t: (t.stride(0) * px if t.shape[0] > 1 else rs(t) * t.shape[1])
+        self._enqueued(self._lib.agx_remap_enqueue(self._h, frames.data_ptr(), n, int(frames.shape[2]), int(frames.shape[1]), rs(frames), fs(frames), fmt,
+                                                   map.data_ptr(), (map.stride(0) if dh > 1 else 2 * dw) * 4, dw, dh, out.data_ptr(), rs(out), fs(out),
+                                                   int(border)))
+        return out
+
+    def rectified_points_enqueue(self, points, camera, new_camera, rotation=None, out=None):
+        """rectified_points (the host form says what is computed) on the device, stream-ordered behind torch's current stream;
+        nothing to fetch.  points: a contiguous float32 device tensor [..., 2] -> out of the same shape (made if None; out = points
+        is in place); or an int32 tag table [..., 9] of detect_batch_enqueue(out=) / collect_tags_enqueue, whose corners are
+        replaced in place (four launches, one per corner; the ids stay).  -> the tensor written."""
+        import torch
+        model, cam, ncam, rot, _, _ = _rectify_args(camera, (1, 1), None, new_camera, rotation)
+        if not (getattr(points, "is_cuda", False) and points.is_contiguous() and points.dim() >= 1):
+            raise AgxError(_ffi.AGX_ERR_ARG, "points must be a contiguous device tensor")
+        self._follow_torch_stream(points)
+        if points.dtype == torch.int32 and points.shape[-1] == 9:
+            if out is not None and out is not points:
+                raise AgxError(_ffi.AGX_ERR_ARG, "a tag table is converted in place")
+            rows = points.numel() // 9
+            for j in range(4 if rows else 0):
+                p = points.data_ptr() + 4 + 8 * j
+                self._enqueued(self._lib.agx_rectified_points_enqueue(self._h, model, cam, ncam, rot, p, 36, rows, p, 36))
+            return points
+        if points.dtype != torch.float32 or points.shape[-1] != 2:
+            raise AgxError(_ffi.AGX_ERR_ARG, "points must be float32 [..., 2] or an int32 tag table [..., 9]")
+        if out is None:
+            out = torch.empty_like(points)
+        elif not (getattr(out, "is_cuda", False) and out.is_contiguous() and out.dtype == torch.float32 and out.shape == points.shape
+                  and out.device == points.device):
+            raise AgxError(_ffi.AGX_ERR_ARG, "out must be a contiguous float32 tensor of the points' shape on their device")
+        self._enqueued(self._lib.agx_rectified_points_enqueue(self._h, model, cam, ncam, rot, points.data_ptr(), 8, points.numel() // 2,
+                                                              out.data_ptr(), 8))
+        return out
+
+    def detect_rectified(self, frames, camera, new_camera=None, dst_size=None, rotation=None, to_source=False, border=0, **detect_kw):
+        """detect_batch on the frames as the ideal pinhole `new_camera` (default: the camera's own fx fy cx cy) would have seen
+        them: frames, a device tensor [N, H, W] uint8 / 16-bit of `camera` (a Camera of either lens model), go through remap_enqueue
+        into a batch of dst_size (w, h; default the frames' size) on the device and detect_batch_device runs on that batch
+        (detect_kw: its keywords).  The map is computed on the device once and kept on the detector, keyed by the arguments.
+        -> detect_batch's structure, the corners in rectified pixels or, with to_source=True, in the sensor's (rectified_points of
+        every corner)."""
+        src_size = (int(frames.shape[2]), int(frames.shape[1]))
+        model, cam, ncam, rot, _, dst = _rectify_args(camera, src_size, dst_size, new_camera, rotation)
+        key = (model, tuple(cam), tuple(ncam), None if rot is None else tuple(rot), src_size, dst, frames.device.index)
+        cache = self.__dict__.setdefault("_rectify_maps", {})
+        if key not in cache:
+            cache[key] = self.rectify_map_enqueue(camera, src_size, dst, new_camera, rotation)
+        rect = self.remap_enqueue(frames, cache[key], border=border)
+        res = self.detect_batch_device(rect, **detect_kw)
+        if to_source:
+            for frame in (res[0] if isinstance(res, tuple) else res):
+                for t in (frame or ()):
+                    frame[t] = rectified_points(frame[t], camera, ncam, rotation)
+        return res
+
     def find_boards_staged(self, saddles, spacing_ratio=0.3, counts=None, point_status=None, quads_per_frame=128, candidates_per_frame=1024,
                            n_nearest=50):
         """try_find_best_board (src/detector.rs:588-639) as its stages on device tensors, at ANY spacing_ratio: the reference's seeds
@@ -2171,6 +2280,99 @@ def board_pose(tags, cols, rows, camera, tag_size=1.0, first_id=0, spacing_ratio
                    pred=pred[:n_pred.value].copy())
         if return_iter_sums:
             out["iter_sums"] = sums
+    return out
+
+
+def _rectify_args(camera, src_size, dst_size, new_camera, rotation):
+    """-> (AGX_LENS_*, camera's nine doubles, new_camera's four, rotation's nine or None, (src_w, src_h), (dst_w, dst_h)).
+    Defaults: the source size, the camera's own fx fy cx cy, no rotation."""
+    model, cam = _camera(camera)
+    nc = [float(v) for v in (cam[:4] if new_camera is None else new_camera)][:9]
+    if len(nc) not in (4, 9):
+        raise AgxError(_ffi.AGX_ERR_ARG, "new_camera must be fx, fy, cx, cy (or a Camera, whose first four numbers are read)")
+    rot = None
+    if rotation is not None:
+        r = np.asarray(rotation, np.float64)
+        if r.size != 9:
+            raise AgxError(_ffi.AGX_ERR_ARG, "rotation must be a 3 x 3 matrix")
+        rot = (C.c_double * 9)(*r.ravel())
+    src = (int(src_size[0]), int(src_size[1]))
+    dst = src if dst_size is None else (int(dst_size[0]), int(dst_size[1]))
+    return model, cam, (C.c_double * 4)(*nc[:4]), rot, src, dst
+
+
+def rectify_map(camera, src_size, dst_size=None, new_camera=None, rotation=None, row_stride=None):
+    """The rectification map of `camera` (a Camera of either lens model) without a device (agx_rectify_map_tail): for every pixel
+    (i, j) of the ideal pinhole new_camera = (fx', fy', cx', cy') of dst_size = (w, h) the sensor pixel it comes from -- the ray
+    ((i - cx') / fx', (j - cy') / fy', 1), turned by rotation (3 x 3, rectified frame -> camera frame), projected through the
+    lens model -- in units of 1/32 px of the src_size = (w, h) sensor image, rounded to nearest.
+    -> int32 [dst_h, dst_w, 2]: (mx, my), or (AGX_MAP_NONE, AGX_MAP_NONE) where the ray has no pixel in the source.  Defaults: the
+    source's size, the camera's own fx fy cx cy, no rotation.  row_stride: bytes between the rows of the array the map is a view
+    of (padding bytes keep 0x5a).  Choosing a new_camera inside the radius where a radial-tangential polynomial is monotone is
+    the caller's job: beyond it far rays fold back into the image."""
+    model, cam, ncam, rot, (sw, sh), (dw, dh) = _rectify_args(camera, src_size, dst_size, new_camera, rotation)
+    stride = 8 * max(dw, 0) if row_stride is None else int(row_stride)
+    buf = None
+    if 1 <= dw <= 16384 and 1 <= dh <= 16384 and stride >= 8 * dw and stride % 8 == 0:
+        buf = np.full((dh, stride // 4), 0x5a5a5a5a, np.int32)
+    st = _ffi.lib().agx_rectify_map_tail(model, cam, ncam, rot, sw, sh, dw, dh, None if buf is None else buf.ctypes.data, stride)
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    return buf[:, :2 * dw].reshape(dh, dw, 2)
+
+
+def _gray_host(a, what):
+    """-> (array [N, H, W], agx_format, pixel bytes, had no frame axis) of a host image or batch, uint8 or uint16, rows may be padded"""
+    a = np.asarray(a)
+    lone = a.ndim == 2
+    a = a[None] if lone else a
+    if a.ndim != 3 or a.dtype not in (np.uint8, np.uint16) or 0 in a.shape or a.strides[2] != a.itemsize or a.strides[1] < 0 or a.strides[0] < 0:
+        raise AgxError(_ffi.AGX_ERR_ARG, "%s must be uint8 or uint16, [H, W] or [N, H, W], with adjacent pixels in a row" % what)
+    return a, (_ffi.AGX_L8 if a.dtype == np.uint8 else _ffi.AGX_L16), a.itemsize, lone
+
+
+def remap(image, map, border=0, out=None):
+    """image ([H, W] or [N, H, W], uint8 or uint16; rows and frames may be padded views) through a rectification map (int32
+    [dst_h, dst_w, 2] in 1/32 px: rectify_map's, or the caller's own) without a device (agx_remap_tail): per destination pixel with
+    entry (mx, my), x0 = mx >> 5, ax = mx & 31, x1 = min(x0 + 1, W - 1), the same in y, and
+    ((32 - ax)(32 - ay) p00 + ax (32 - ay) p10 + (32 - ax) ay p01 + ax ay p11 + 512) >> 10 -- integers only; `border` where the
+    entry is AGX_MAP_NONE or otherwise not inside the source.  -> [dst_h, dst_w] or [N, dst_h, dst_w] of the image's dtype (out:
+    the caller's array of that shape, rows and frames may be padded)."""
+    a, fmt, px, lone = _gray_host(image, "image")
+    m = np.asarray(map)
+    if m.dtype != np.int32 or m.ndim != 3 or m.shape[2] != 2 or 0 in m.shape or m.strides[2] != 4 or m.strides[1] != 8 or m.strides[0] < 0:
+        raise AgxError(_ffi.AGX_ERR_ARG, "map must be int32 [dst_h, dst_w, 2] whose rows are packed")
+    n, dh, dw = a.shape[0], m.shape[0], m.shape[1]
+    if out is None:
+        res = np.empty((n, dh, dw), a.dtype)
+    else:
+        res = _gray_host(out, "out")[0]
+        if res.dtype != a.dtype or res.shape != (n, dh, dw):
+            raise AgxError(_ffi.AGX_ERR_ARG, "out must have the image's dtype and the shape [N, dst_h, dst_w]")
+    rs = lambda t: t.strides[1] if t.shape[1] > 1 else t.shape[2] * px  # (a lone row or frame has no stride of its own)
+    fs = lambda t: t.strides[0] if t.shape[0] > 1 else rs(t) * t.shape[1]
+    st = _ffi.lib().agx_remap_tail(a.ctypes.data, n, a.shape[2], a.shape[1], rs(a), fs(a), fmt, m.ctypes.data, m.strides[0] if dh > 1 else 8 * dw, dw, dh,
+                                   res.ctypes.data, rs(res), fs(res), int(border))
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    if out is not None:
+        return out
+    return res[0] if lone else res
+
+
+def rectified_points(points, camera, new_camera, rotation=None):
+    """Points (x, y) of the rectified image, float32 [..., 2], to the sensor pixels they come from, without a device
+    (agx_rectified_points_tail): rectify_map's ray, rotation and projection in binary64 (the map's entry is this function at integer
+    positions), rounded to float32; (NaN, NaN) where the ray has no projection.  new_camera None: the camera's own fx fy cx cy."""
+    model, cam, ncam, rot, _, _ = _rectify_args(camera, (1, 1), None, new_camera, rotation)
+    p = np.ascontiguousarray(points, np.float32)
+    if p.ndim < 1 or p.shape[-1] != 2:
+        raise AgxError(_ffi.AGX_ERR_ARG, "points must be [..., 2]")
+    out = np.empty_like(p)
+    st = _ffi.lib().agx_rectified_points_tail(model, cam, ncam, rot, p.ctypes.data if p.size else None, 8, p.size // 2,
+                                              out.ctypes.data if p.size else None, 8)
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
     return out
 
 

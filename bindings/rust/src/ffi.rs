@@ -167,6 +167,8 @@ pub const AGX_FIT_ROW_OUTLIER: c_int = 1;
 pub const AGX_FIT_ROW_OFF_BOARD: c_int = 2;
 pub const AGX_LENS_RADTAN: c_int = 0;
 pub const AGX_LENS_EQUIDISTANT: c_int = 1;
+/// both words of a rectification map's entry that has no source pixel (the header's `#define AGX_MAP_NONE`, INT32_MIN)
+pub const AGX_MAP_NONE: i32 = i32::MIN;
 // agx_debug_fetch items
 pub const AGX_DBG_BLUR: c_int = 0;
 pub const AGX_DBG_RESP: c_int = 1;
@@ -403,6 +405,26 @@ extern "C" {
                                        status: *mut u32, iter_sums: *mut c_double) -> c_int;
     pub fn agx_debug_pose_atan(r: *const c_double, n: u32, out: *mut c_double) -> c_int;
     pub fn agx_debug_pose_project(lens_model: c_int, camera: *const c_double, xyz: *const c_double, n: u32, uv: *mut c_double) -> c_int;
+    // rectified batches: the map (two 32-bit words per destination pixel in 1/32 source px, or AGX_MAP_NONE), the remap, points back
+    pub fn agx_rectify_map_enqueue(det: *mut agx_detector, lens_model: c_int, camera: *const c_double, new_camera: *const c_double,
+                                   rotation: *const c_double, src_width: c_int, src_height: c_int, dst_width: c_int, dst_height: c_int,
+                                   d_map: *mut c_int, map_row_stride_bytes: usize) -> c_int;
+    pub fn agx_rectify_map_tail(lens_model: c_int, camera: *const c_double, new_camera: *const c_double, rotation: *const c_double,
+                                src_width: c_int, src_height: c_int, dst_width: c_int, dst_height: c_int, map: *mut c_int,
+                                map_row_stride_bytes: usize) -> c_int;
+    pub fn agx_remap_enqueue(det: *mut agx_detector, d_src: *const c_void, n_frames: c_int, src_width: c_int, src_height: c_int,
+                             src_row_stride_bytes: usize, src_frame_stride_bytes: usize, format: c_int, d_map: *const c_int,
+                             map_row_stride_bytes: usize, dst_width: c_int, dst_height: c_int, d_dst: *mut c_void,
+                             dst_row_stride_bytes: usize, dst_frame_stride_bytes: usize, border: u32) -> c_int;
+    pub fn agx_remap_tail(src: *const c_void, n_frames: c_int, src_width: c_int, src_height: c_int, src_row_stride_bytes: usize,
+                          src_frame_stride_bytes: usize, format: c_int, map: *const c_int, map_row_stride_bytes: usize, dst_width: c_int,
+                          dst_height: c_int, dst: *mut c_void, dst_row_stride_bytes: usize, dst_frame_stride_bytes: usize, border: u32) -> c_int;
+    pub fn agx_rectified_points_enqueue(det: *mut agx_detector, lens_model: c_int, camera: *const c_double, new_camera: *const c_double,
+                                        rotation: *const c_double, d_points: *const c_void, point_stride_bytes: usize, n_points: u32,
+                                        d_out: *mut c_void, out_stride_bytes: usize) -> c_int;
+    pub fn agx_rectified_points_tail(lens_model: c_int, camera: *const c_double, new_camera: *const c_double, rotation: *const c_double,
+                                     points: *const c_void, point_stride_bytes: usize, n_points: u32, out: *mut c_void,
+                                     out_stride_bytes: usize) -> c_int;
     pub fn agx_debug_blur_weights(sigma: c_float, weights: *mut c_float, cap: c_int, radius: *mut c_int) -> c_int;
     pub fn agx_debug_refine_constants(half_size_patch: c_int, cone: *mut c_float, pmat: *mut c_float, cap_points: c_int,
                                       n_points: *mut c_int) -> c_int;

@@ -900,6 +900,63 @@ pub fn board_pose_tail_m(tags: &[(u32, [(f32, f32); 4])], layout: &BoardLayout, 
     })
 }
 
+/// The ideal pinhole a batch is rectified to, and the rotation from its frame to the camera's (`None`: the identity).
+#[derive(Clone, Copy, Debug)]
+pub struct Rectification {
+    /// `fx', fy', cx', cy'`
+    pub new_camera: [f64; 4],
+    /// row major, rectified frame -> camera frame
+    pub rotation: Option<[f64; 9]>,
+}
+
+fn camera_doubles(camera: &Camera) -> [f64; 9] {
+    [camera.fx, camera.fy, camera.cx, camera.cy, camera.k1, camera.k2, camera.p1, camera.p2, camera.k3]
+}
+
+/// The rectification map of `camera` under `model`, the host form (no device is used): for every pixel of the `dst` = (w, h)
+/// pinhole of `rect` the pixel of the `src` = (w, h) sensor image it comes from, `[mx, my]` in 1/32 px, row major, or
+/// `[AGX_MAP_NONE; 2]` where the ray has no pixel there.  Panics where the library refuses the arguments.
+pub fn rectify_map_tail(model: LensModel, camera: &Camera, rect: &Rectification, src: (u32, u32), dst: (u32, u32)) -> Vec<[i32; 2]> {
+    let cam = camera_doubles(camera);
+    let mut map = vec![[ffi::AGX_MAP_NONE; 2]; dst.0 as usize * dst.1 as usize];
+    let st = unsafe {
+        ffi::agx_rectify_map_tail(model as c_int, cam.as_ptr(), rect.new_camera.as_ptr(), rect.rotation.as_ref().map_or(std::ptr::null(), |r| r.as_ptr()),
+                                  src.0 as c_int, src.1 as c_int, dst.0 as c_int, dst.1 as c_int, map.as_mut_ptr() as *mut c_int, 8 * dst.0 as usize)
+    };
+    assert_eq!(st, ffi::AGX_OK, "agx_rectify_map_tail failed: {}", st);
+    map
+}
+
+/// One tightly packed L8 frame of `src` = (w, h) through a map of `dst` = (w, h) entries, the host form: bilinear with 5-bit
+/// weights in integers, `border` where the entry has no source pixel.  Panics where the library refuses the arguments.
+pub fn remap_tail(frame: &[u8], src: (u32, u32), map: &[[i32; 2]], dst: (u32, u32), border: u8) -> Vec<u8> {
+    assert_eq!(frame.len(), src.0 as usize * src.1 as usize, "remap_tail: frame is not w * h bytes");
+    assert_eq!(map.len(), dst.0 as usize * dst.1 as usize, "remap_tail: map is not w * h entries");
+    let mut out = vec![0u8; map.len()];
+    let st = unsafe {
+        ffi::agx_remap_tail(frame.as_ptr() as *const std::os::raw::c_void, 1, src.0 as c_int, src.1 as c_int, src.0 as usize, frame.len(), ffi::AGX_L8,
+                            map.as_ptr() as *const c_int, 8 * dst.0 as usize, dst.0 as c_int, dst.1 as c_int,
+                            out.as_mut_ptr() as *mut std::os::raw::c_void, dst.0 as usize, out.len(), border as u32)
+    };
+    assert_eq!(st, ffi::AGX_OK, "agx_remap_tail failed: {}", st);
+    out
+}
+
+/// Points of the rectified image to the sensor pixels they come from, the host form: the map's ray, rotation and projection in
+/// binary64, rounded to `f32`; `(NaN, NaN)` where the ray has no projection.  Panics where the library refuses the arguments.
+pub fn rectified_points_tail(model: LensModel, camera: &Camera, rect: &Rectification, points: &[(f32, f32)]) -> Vec<(f32, f32)> {
+    let cam = camera_doubles(camera);
+    let flat: Vec<f32> = points.iter().flat_map(|p| [p.0, p.1]).collect();
+    let mut out = vec![0f32; flat.len()];
+    let st = unsafe {
+        ffi::agx_rectified_points_tail(model as c_int, cam.as_ptr(), rect.new_camera.as_ptr(),
+                                       rect.rotation.as_ref().map_or(std::ptr::null(), |r| r.as_ptr()), flat.as_ptr() as *const std::os::raw::c_void, 8,
+                                       points.len() as u32, out.as_mut_ptr() as *mut std::os::raw::c_void, 8)
+    };
+    assert_eq!(st, ffi::AGX_OK, "agx_rectified_points_tail failed: {}", st);
+    out.chunks(2).map(|c| (c[0], c[1])).collect()
+}
+
 fn last_error(det: *const ffi::agx_detector) -> String {
     unsafe {
         let p = ffi::agx_last_error(det);

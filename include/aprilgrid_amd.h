@@ -1230,6 +1230,80 @@ int agx_debug_board_pose_sums_m(const agx_tag *tags, uint32_t tags_per_frame, ui
 int agx_debug_pose_atan(const double *r, uint32_t n, double *out);
 int agx_debug_pose_project(int lens_model, const double *camera, const double *xyz, uint32_t n, double *uv);
 
+/* ---- rectified batches: the lens model applied to the pixels (csrc/rectify.hip; the arithmetic once, in csrc/rectify_math.h) ---- */
+
+/* Everything above works on the tag table, behind the detection; these three work in front of it.  The board search assumes a
+ * straight lattice and the decode samples through an affine or projective map: neither knows about the lens, and on a strong
+ * fisheye tags are lost.  A rectified batch -- the frames as the ideal pinhole `new_camera` would have seen them -- is also what
+ * stereo matching, the straight-lattice agx_board_fit_enqueue and consumers outside this library expect of a calibrated camera.
+ *
+ * THE MAP, once per camera (k_rectify_map; one lane per destination pixel; not the hot path).  For destination pixel (i, j) of a
+ * dst_width x dst_height pinhole new_camera = fx' fy' cx' cy' (four doubles, HOST memory, copied by the call): the ray
+ * d = ((i - cx') / fx', (j - cy') / fy', 1); (X, Y, Z) = R d with rotation = R, nine doubles, row major, rectified frame ->
+ * camera frame, HOST memory (NULL: the identity); (u, v) = the projection of (X, Y, Z) under lens_model and camera -- the one of
+ * agx_board_pose_enqueue_m, the function agx_debug_pose_project hands out, binary64 in its order of operations.  The entry is two
+ * int (32-bit) words in units of 1/32 source pixel, mx = floor(32 u + 1/2), my = floor(32 v + 1/2) in binary64, valid if the
+ * projection exists (Z > 0, u and v finite) and 0 <= mx <= 32 (src_width - 1), 0 <= my <= 32 (src_height - 1); otherwise both
+ * words are AGX_MAP_NONE.  d_map [dst_height][dst_width][2] with map_row_stride_bytes between rows (a multiple of 8, at least
+ * 8 dst_width; padding bytes are not written), caller-owned device memory, 8-byte aligned; stream-ordered, nothing to fetch; a
+ * batch in flight is replaced as by agx_board_fit_enqueue.
+ * The caller's responsibility: the radial-tangential polynomial is applied as it stands.  Beyond the radius where it stops being
+ * monotone, far rays fold back into the image (as in OpenCV's initUndistortRectifyMap); choosing new_camera and the target size
+ * inside that radius is the caller's job.  The equidistant model has no such radius below Z = 0.
+ * AGX_ERR_ARG (a batch in flight stays where it is): agx_board_pose_enqueue_m's rules on lens_model and camera; a NULL or
+ * non-finite new_camera, or fx' or fy' not > 0; a non-finite rotation; a size below 1 or above 16384; a NULL or misaligned d_map,
+ * a stride that is no multiple of 8 or below 8 dst_width.
+ * agx_rectify_map_tail: the host form -- no handle, no device, the same bytes. */
+#define AGX_MAP_NONE (-2147483647 - 1)
+int agx_rectify_map_enqueue(agx_detector *det, int lens_model, const double *camera, const double *new_camera, const double *rotation,
+                            int src_width, int src_height, int dst_width, int dst_height,
+                            int *d_map, size_t map_row_stride_bytes);
+int agx_rectify_map_tail(int lens_model, const double *camera, const double *new_camera, const double *rotation,
+                         int src_width, int src_height, int dst_width, int dst_height,
+                         int *map, size_t map_row_stride_bytes);
+
+/* THE REMAP, once per batch (k_remap; the hot path).  d_src: n_frames frames of src_width x src_height, AGX_L8 or AGX_L16, row and
+ * frame strides as in every batch entry; d_dst: n_frames frames of dst_width x dst_height in the same format with their own
+ * strides; d_map as above (the caller's own map is as good).  Per destination pixel with entry (mx, my): AGX_MAP_NONE, or any
+ * entry that is not inside the source (0 <= mx <= 32 (src_width - 1), 0 <= my <= 32 (src_height - 1)), gives `border`; otherwise
+ * x0 = mx >> 5, ax = mx & 31, x1 = min(x0 + 1, src_width - 1), the same in y, and
+ *   value = ((32 - ax)(32 - ay) p00 + ax (32 - ay) p10 + (32 - ax) ay p01 + ax ay p11 + 512) >> 10     in uint32
+ * -- bilinear with 5-bit weights, round half up.  No floating-point operation in the kernel or in the host form; nothing outside
+ * the source frames is read, nothing outside the destination rows' dst_width pixels is written.  Caller-owned device memory,
+ * stream-ordered, nothing to fetch; a batch in flight is replaced as by agx_board_fit_enqueue.  Source and destination must not
+ * overlap.
+ * AGX_ERR_ARG (a batch in flight stays where it is): a NULL array; n_frames outside 1 .. 65535; a format other than AGX_L8 and
+ * AGX_L16 (the luma front is not part of this); a source side outside 1 .. 65000 or a source frame of 2^30 px or more; a
+ * destination side outside 1 .. 16384; a row stride that does not cover a row, a frame stride (n_frames > 1) that does not cover
+ * a frame, a frame (row stride x height) of 2^31 bytes or more; AGX_L16 pointers or strides that are odd; the map's rules above;
+ * border above 255 (AGX_L8) or 65535 (AGX_L16).
+ * agx_remap_tail: the host form -- no handle, no device, the same bytes. */
+int agx_remap_enqueue(agx_detector *det, const void *d_src, int n_frames, int src_width, int src_height,
+                      size_t src_row_stride_bytes, size_t src_frame_stride_bytes, int format,
+                      const int *d_map, size_t map_row_stride_bytes, int dst_width, int dst_height,
+                      void *d_dst, size_t dst_row_stride_bytes, size_t dst_frame_stride_bytes, uint32_t border);
+int agx_remap_tail(const void *src, int n_frames, int src_width, int src_height,
+                   size_t src_row_stride_bytes, size_t src_frame_stride_bytes, int format,
+                   const int *map, size_t map_row_stride_bytes, int dst_width, int dst_height,
+                   void *dst, size_t dst_row_stride_bytes, size_t dst_frame_stride_bytes, uint32_t border);
+
+/* POINTS BACK TO THE SENSOR (k_rectified_points).  Point i of n_points is two floats (x, y), rectified pixels, at
+ * d_points + i * point_stride_bytes; it goes through the map's ray, rotation and projection (binary64; the map's entry is this
+ * function at integer positions) and (u, v), sensor pixels, rounded to binary32, is written at d_out + i * out_stride_bytes;
+ * (NaN, NaN) for a point with no projection (a point that is not finite among them).  In place (d_out = d_points, the same
+ * stride) is allowed.  Corner j of an agx_tag table is read in place at (char *)d_tags + 4 + 8 j with a stride of 36: four calls
+ * put a table detected in the rectified batch into sensor pixels, which is what agx_board_pose_enqueue_m wants for residuals in
+ * sensor pixels.  Caller-owned device memory, stream-ordered, nothing to fetch; a batch in flight is replaced as above.
+ * AGX_ERR_ARG: the map's rules on lens_model, camera, new_camera and rotation; a NULL list with n_points > 0; 2^30 points or
+ * more; a pointer or stride that is no multiple of 4, a stride below 8.
+ * agx_rectified_points_tail: the host form. */
+int agx_rectified_points_enqueue(agx_detector *det, int lens_model, const double *camera, const double *new_camera,
+                                 const double *rotation, const void *d_points, size_t point_stride_bytes, uint32_t n_points,
+                                 void *d_out, size_t out_stride_bytes);
+int agx_rectified_points_tail(int lens_model, const double *camera, const double *new_camera, const double *rotation,
+                              const void *points, size_t point_stride_bytes, uint32_t n_points,
+                              void *out, size_t out_stride_bytes);
+
 /* ---- detector groups: several GPUs of one node driven from ONE process ----------------- */
 
 /* The reference's detect(&self) is stateless, so a batch shards by frame:
