@@ -41,8 +41,8 @@ AGX_TAGS_OK, AGX_TAGS_CAPACITY, AGX_TAGS_INPUT, AGX_TAGS_PENDING = 0, 1, 2, 3
 AGX_FIT_PREDICT_MISSING = 1
 AGX_FIT_OK, AGX_FIT_LOOSE, AGX_FIT_FEW, AGX_FIT_SINGULAR, AGX_FIT_INPUT = 0, 1, 2, 3, 4
 AGX_FIT_ROW_INLIER, AGX_FIT_ROW_OUTLIER, AGX_FIT_ROW_OFF_BOARD = 0, 1, 2
-# the lens model of agx_board_pose_enqueue_m / _tail_m: pinhole + radial-tangential, pinhole-equidistant (fisheye)
-AGX_LENS_RADTAN, AGX_LENS_EQUIDISTANT = 0, 1
+# the lens model of agx_board_pose_enqueue_m / _tail_m: pinhole + radial-tangential, pinhole-equidistant (fisheye), double sphere
+AGX_LENS_RADTAN, AGX_LENS_EQUIDISTANT, AGX_LENS_DOUBLE_SPHERE = 0, 1, 2
 AGX_MAP_NONE = -2 ** 31  # both words of a rectification map's entry without a source pixel (agx_rectify_map_enqueue / _tail)
 AGX_DBG_BLUR, AGX_DBG_RESP, AGX_DBG_MIN, AGX_DBG_CENTERS, AGX_DBG_REFINED = 0, 1, 2, 3, 4
 AGX_N_KERNELS = 5

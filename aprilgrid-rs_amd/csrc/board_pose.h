@@ -22,7 +22,8 @@ struct BoardPoseArgs {
     uint32_t cols, rows, first_id;  // rows * cols in 1 .. 4096
     float spacing_ratio;            // finite, > -1
     double tag_size;                // finite, > 0
-    agx_camera camera;              // every field finite, fx and fy > 0; under AGX_LENS_EQUIDISTANT fx fy cx cy k1 k2 k3 k4 0
+    agx_camera camera;              // every field finite, fx and fy > 0; under AGX_LENS_EQUIDISTANT fx fy cx cy k1 k2 k3 k4 0,
+                                    // under AGX_LENS_DOUBLE_SPHERE fx fy cx cy xi alpha 0 0 0 (the launch puts w2 into the ninth)
     float max_err_sq;               // >= 0
     uint32_t max_drop, min_tags;    // min_tags >= 1
     uint32_t iterations;            // 0 .. 64

@@ -13,7 +13,8 @@
 // Prediction: one lane per tag of the layout, 64 at a time, compacted by ballot under AGX_FIT_PREDICT_MISSING against a bitmap of
 // the inlier rows' ids.  No floating-point atomics.
 // The kernel is a template on the lens model (AGX_LENS_*): the projection, the lens's Jacobian and the seed's undistortion are
-// board_pose_math.h's for that model, everything else is one text.  Neither instantiation uses scratch.
+// board_pose_math.h's for that model, everything else is one text.  No instantiation uses scratch.  Under
+// AGX_LENS_DOUBLE_SPHERE the camera in the arguments is pose_camera()'s, which the launch makes on the host.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -271,7 +272,11 @@ int launch_board_pose(const BoardPoseArgs &b, int lens, void *stream)
         !b.best_iter || !b.pred || !b.n_pred || !b.status)
         return (int)hipErrorInvalidValue;
     const unsigned grid = ((unsigned)b.n_frames + POSE_FRAMES_PER_WG - 1) / POSE_FRAMES_PER_WG;
-    if (lens == AGX_LENS_EQUIDISTANT) hipLaunchKernelGGL(k_board_pose<AGX_LENS_EQUIDISTANT>, dim3(grid), dim3(64 * POSE_FRAMES_PER_WG), 0, (hipStream_t)stream, b);
+    if (lens == AGX_LENS_DOUBLE_SPHERE) {
+        BoardPoseArgs d = b;
+        d.camera = pose_camera(lens, b.camera);  // (w2 once per call, by the host form's statements)
+        hipLaunchKernelGGL(k_board_pose<AGX_LENS_DOUBLE_SPHERE>, dim3(grid), dim3(64 * POSE_FRAMES_PER_WG), 0, (hipStream_t)stream, d);
+    } else if (lens == AGX_LENS_EQUIDISTANT) hipLaunchKernelGGL(k_board_pose<AGX_LENS_EQUIDISTANT>, dim3(grid), dim3(64 * POSE_FRAMES_PER_WG), 0, (hipStream_t)stream, b);
     else hipLaunchKernelGGL(k_board_pose<AGX_LENS_RADTAN>, dim3(grid), dim3(64 * POSE_FRAMES_PER_WG), 0, (hipStream_t)stream, b);
     return (int)hipGetLastError();
 }

@@ -53,6 +53,32 @@
 // the seed only: a pinhole ray must exist) becomes POSE_EQUI_THETA_MAX;  tan(theta) from a = theta / 8 by the series of the
 // tangent through a^15 and POSE_EQUI_TAN_DOUBLINGS (3) times t = 2 t / (1 - t t);  (x, y) = (x0, y0) tan(theta) / theta_d
 // (theta_d = 0: (x0, y0)).  A value that is not finite reaches the seed's norm checks: AGX_FIT_SINGULAR.
+//
+// The third lens model, AGX_LENS_DOUBLE_SPHERE (Usenko, Demmel, Cremers 2018; Kalibr's ds, Basalt's default).  The nine doubles
+// are fx, fy, cx, cy, xi, alpha, 0, 0, 0: agx_camera's k1 holds xi, its k2 holds alpha; -1 < xi <= 1, 0 <= alpha <= 1, the last
+// three exactly 0.  + - * / and pose_sqrt only: no atan, no series, no iteration.  THE ORDER OF OPERATIONS:
+//   Xc, Yc, Zc as above;  r2 = Xc Xc + Yc Yc,  d1 = pose_sqrt(r2 + Zc Zc);  no projection unless d1 > 0 and Zc > -(w2 d1);
+//   k = xi d1 + Zc,  d2 = pose_sqrt(r2 + k k),  den = alpha d2 + (1 - alpha) k,  mx = Xc / den,  my = Yc / den,
+//   u = fx mx + cx,  v = fy my + cy.
+// Zc <= 0 is no refusal: the model is carried behind the image plane, out to the cone Zc = -w2 d1 (inside it den > 0).
+//   w1 = alpha / (1 - alpha) for alpha <= 0.5, else (1 - alpha) / alpha;   w2 = (w1 + xi) / pose_sqrt(2 w1 xi + xi xi + 1).
+// w2 depends on the camera only.  pose_camera() computes it once per call, on the host, for the kernel and the host form alike,
+// and hands the functions below a camera whose k3 (the ninth double, 0 in the caller's) holds it: no function below is given a
+// double-sphere camera that did not come through pose_camera().
+// Jacobian m = d(u, v) / d(Xc, Yc, Zc), in closed form (x = Xc / Zc does not exist where Zc <= 0):  a = xi / d1,  b = alpha / d2,
+//   s = b (1 + k a) + (1 - alpha) a  (d den / d Xc = Xc s, d den / d Yc = Yc s),  dz = (a Zc + 1) (b k + (1 - alpha))  (d den / d Zc),
+//   id = 1 / den;   m00 = fx id (1 - mx (Xc s)),  m01 = -(fx id (mx (Yc s))),  m02 = -(fx id (mx dz)),
+//                   m10 = -(fy id (my (Xc s))),  m11 = fy id (1 - my (Yc s)),  m12 = -(fy id (my dz)).
+// The chain from m to (R, t), the sums, the solve, the iterates and the rounds are the ones above.
+// Seed's unprojection, closed form:  x0 = (u - cx) / fx,  y0 = (v - cy) / fy,  r2 = x0 x0 + y0 y0,  t = 1 - (2 alpha - 1) r2
+//   (t < 0: the pixel is outside the unprojection's domain, which happens for alpha > 0.5 only),
+//   mz = (1 - alpha alpha r2) / (alpha pose_sqrt(t) + (1 - alpha)),  n = mz mz + r2,
+//   sc = (mz xi + pose_sqrt(mz mz + (1 - xi xi) r2)) / n,   ray = (sc x0, sc y0, sc mz - xi),   (x, y) = (ray_x, ray_y) / ray_z.
+// The seed needs a pinhole ray, so it clamps (the seed only; the refinement runs through the forward model and has no such
+// limit): unless t >= 0 and ray_z > 0 and x x + y y < POSE_TAN_THETA_MAX^2 (the ray is less than POSE_EQUI_THETA_MAX = 1.5 rad
+// off the axis; a value that is not a number fails the tests too), (x, y) = (x0, y0) (POSE_TAN_THETA_MAX / pose_sqrt(r2)),
+// (0, 0) where r2 is not > 0.  On the principal point r2 = 0, mz = 1, ray = ((1 + xi) 0, (1 + xi) 0, (1 + xi) - xi): (0, 0) with
+// no division by r.
 #pragma once
 #include <cstdint>
 #include <type_traits>
@@ -80,6 +106,7 @@ constexpr double POSE_ATAN_TABLE[9] = {0.0,
                                        0.7188299996216245,
                                        0.7853981633974483};
 constexpr double POSE_PIO2_HI = 1.5707963267948966, POSE_PIO2_LO = 6.123233995736766e-17;
+constexpr double POSE_TAN_THETA_MAX = 14.101419947171719;  // tan(POSE_EQUI_THETA_MAX) to the nearest binary64: the double-sphere seed's clamp
 
 struct Pose {
     double R[9];  // row major, board -> camera
@@ -132,52 +159,86 @@ struct PosePoint {
 struct PosePointEqui {
     double x, y, zc, s, g, u, v;  // s = theta_d / r, g = (ds/dr) / r
 };
+struct PosePointDs {
+    double xc, yc, zc, d1, k, d2, den, mx, my, u, v;
+};
 template <int LENS>
-using PosePointOf = std::conditional_t<LENS == AGX_LENS_EQUIDISTANT, PosePointEqui, PosePoint>;
+using PosePointOf = std::conditional_t<LENS == AGX_LENS_DOUBLE_SPHERE, PosePointDs, std::conditional_t<LENS == AGX_LENS_EQUIDISTANT, PosePointEqui, PosePoint>>;
 
-// false: Zc is not > 0 (q untouched beyond zc)
+// the camera as the functions below read it: the caller's, and under AGX_LENS_DOUBLE_SPHERE its k3 holds w2, the valid cone's
+// Zc / d1 (once per call, on the host, for both forms; the caller's camera has passed pose_args_ok)
+inline agx_camera pose_camera(int lens, const agx_camera &c)
+{
+    agx_camera o = c;
+    if (lens == AGX_LENS_DOUBLE_SPHERE) {
+        const double xi = c.k1, al = c.k2;
+        const double w1 = al <= 0.5 ? al / (1.0 - al) : (1.0 - al) / al;
+        o.k3 = (w1 + xi) / pose_sqrt(2.0 * w1 * xi + xi * xi + 1.0);
+    }
+    return o;
+}
+
+// false: no projection -- Zc is not > 0, or under AGX_LENS_DOUBLE_SPHERE the point is not inside the valid cone (q untouched beyond zc)
 template <int LENS = AGX_LENS_RADTAN>
 AGX_HD bool pose_project(const agx_camera &c, const Pose &p, double X, double Y, PosePointOf<LENS> &q)
 {
     const double xc = p.R[0] * X + p.R[1] * Y + p.t[0];
     const double yc = p.R[3] * X + p.R[4] * Y + p.t[1];
     q.zc = p.R[6] * X + p.R[7] * Y + p.t[2];
-    if (!(q.zc > 0.0)) return false;
-    const double x = xc / q.zc, y = yc / q.zc;
-    if constexpr (LENS == AGX_LENS_EQUIDISTANT) {
-        const double r2 = x * x + y * y, r = pose_sqrt(r2);
-        const bool small = r2 < POSE_EQUI_SMALL_R2;
-        double th, tr;  // theta, theta / r
-        if (small) {
-            tr = 1.0 - r2 * (1.0 / 3.0 - r2 * (1.0 / 5.0 - r2 * (1.0 / 7.0 - r2 / 9.0)));
-            th = r * tr;
-        } else {
-            th = pose_atan(r);
-            tr = th / r;
-        }
-        double D, Dp;
-        pose_equi_poly(c, th * th, D, Dp);
-        const double s = tr * D;
-        q.x = x;
-        q.y = y;
-        q.s = s;
-        q.g = small ? 2.0 * (c.k1 - 1.0 / 3.0) + 4.0 * (c.k2 - c.k1 + 1.0 / 5.0) * r2 : (Dp / (1.0 + r2) - s) / r2;
-        q.u = c.fx * (s * x) + c.cx;
-        q.v = c.fy * (s * y) + c.cy;
+    if constexpr (LENS == AGX_LENS_DOUBLE_SPHERE) {  // (k1 holds xi, k2 alpha, k3 pose_camera's w2)
+        const double r2 = xc * xc + yc * yc, d1 = pose_sqrt(r2 + q.zc * q.zc);
+        if (!(d1 > 0.0) || !(q.zc > -(c.k3 * d1))) return false;
+        const double k = c.k1 * d1 + q.zc, d2 = pose_sqrt(r2 + k * k);
+        const double den = c.k2 * d2 + (1.0 - c.k2) * k;
+        q.xc = xc;
+        q.yc = yc;
+        q.d1 = d1;
+        q.k = k;
+        q.d2 = d2;
+        q.den = den;
+        q.mx = xc / den;
+        q.my = yc / den;
+        q.u = c.fx * q.mx + c.cx;
+        q.v = c.fy * q.my + c.cy;
+        return true;
     } else {
-        const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
-        const double rad = 1.0 + c.k1 * r2 + c.k2 * r4 + c.k3 * r6;
-        const double xd = x * rad + 2.0 * c.p1 * x * y + c.p2 * (r2 + 2.0 * x * x);
-        const double yd = y * rad + c.p1 * (r2 + 2.0 * y * y) + 2.0 * c.p2 * x * y;
-        q.x = x;
-        q.y = y;
-        q.r2 = r2;
-        q.r4 = r4;
-        q.rad = rad;
-        q.u = c.fx * xd + c.cx;
-        q.v = c.fy * yd + c.cy;
+        if (!(q.zc > 0.0)) return false;
+        const double x = xc / q.zc, y = yc / q.zc;
+        if constexpr (LENS == AGX_LENS_EQUIDISTANT) {
+            const double r2 = x * x + y * y, r = pose_sqrt(r2);
+            const bool small = r2 < POSE_EQUI_SMALL_R2;
+            double th, tr;  // theta, theta / r
+            if (small) {
+                tr = 1.0 - r2 * (1.0 / 3.0 - r2 * (1.0 / 5.0 - r2 * (1.0 / 7.0 - r2 / 9.0)));
+                th = r * tr;
+            } else {
+                th = pose_atan(r);
+                tr = th / r;
+            }
+            double D, Dp;
+            pose_equi_poly(c, th * th, D, Dp);
+            const double s = tr * D;
+            q.x = x;
+            q.y = y;
+            q.s = s;
+            q.g = small ? 2.0 * (c.k1 - 1.0 / 3.0) + 4.0 * (c.k2 - c.k1 + 1.0 / 5.0) * r2 : (Dp / (1.0 + r2) - s) / r2;
+            q.u = c.fx * (s * x) + c.cx;
+            q.v = c.fy * (s * y) + c.cy;
+        } else {
+            const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+            const double rad = 1.0 + c.k1 * r2 + c.k2 * r4 + c.k3 * r6;
+            const double xd = x * rad + 2.0 * c.p1 * x * y + c.p2 * (r2 + 2.0 * x * x);
+            const double yd = y * rad + c.p1 * (r2 + 2.0 * y * y) + 2.0 * c.p2 * x * y;
+            q.x = x;
+            q.y = y;
+            q.r2 = r2;
+            q.r4 = r4;
+            q.rad = rad;
+            q.u = c.fx * xd + c.cx;
+            q.v = c.fy * yd + c.cy;
+        }
+        return true;
     }
-    return true;
 }
 
 // |e|^2 of one correspondence: +inf without a projection or where the value is not below +inf
@@ -219,10 +280,30 @@ AGX_HD void pose_undistort_equi(const agx_camera &c, double u, double v, double 
     y = y0 * k;
 }
 
+// a pixel to normalised coordinates under the double-sphere model: the closed-form unprojection, its pinhole ray, the seed's clamp
+AGX_HD void pose_undistort_ds(const agx_camera &c, double u, double v, double &x, double &y)
+{
+    const double xi = c.k1, al = c.k2;
+    const double x0 = (u - c.cx) / c.fx, y0 = (v - c.cy) / c.fy;
+    const double r2 = x0 * x0 + y0 * y0;
+    const double t = 1.0 - (2.0 * al - 1.0) * r2;
+    const double mz = (1.0 - al * al * r2) / (al * pose_sqrt(t) + (1.0 - al));
+    const double n = mz * mz + r2;
+    const double sc = (mz * xi + pose_sqrt(mz * mz + (1.0 - xi * xi) * r2)) / n;
+    const double rz = sc * mz - xi;
+    x = sc * x0 / rz;
+    y = sc * y0 / rz;
+    if (t >= 0.0 && rz > 0.0 && x * x + y * y < POSE_TAN_THETA_MAX * POSE_TAN_THETA_MAX) return;
+    const double k = r2 > 0.0 ? POSE_TAN_THETA_MAX / pose_sqrt(r2) : 0.0;
+    x = x0 * k;
+    y = y0 * k;
+}
+
 // a pixel to normalised coordinates: POSE_UNDISTORT_STEPS steps of the fixed-point iteration
 template <int LENS = AGX_LENS_RADTAN>
 AGX_HD void pose_undistort(const agx_camera &c, double u, double v, double &x, double &y)
 {
+    if constexpr (LENS == AGX_LENS_DOUBLE_SPHERE) return pose_undistort_ds(c, u, v, x, y);
     if constexpr (LENS == AGX_LENS_EQUIDISTANT) return pose_undistort_equi(c, u, v, x, y);
     const double x0 = (u - c.cx) / c.fx, y0 = (v - c.cy) / c.fy;
     x = x0;
@@ -320,6 +401,21 @@ AGX_HD void pose_lens_jacobian(const agx_camera &, const PosePointEqui &q, doubl
     d10 = x * y * q.g;
     d11 = q.s + y * y * q.g;
 }
+// the double-sphere model's d(u, v) / d(Xc, Yc, Zc), directly (no x = Xc / Zc: Zc may be <= 0)
+AGX_HD void pose_ds_jacobian(const agx_camera &c, const PosePointDs &q, double &m00, double &m01, double &m02, double &m10, double &m11, double &m12)
+{
+    const double a = c.k1 / q.d1, b = c.k2 / q.d2, c1 = 1.0 - c.k2;
+    const double s = b * (1.0 + q.k * a) + c1 * a;
+    const double dz = (a * q.zc + 1.0) * (b * q.k + c1);
+    const double id = 1.0 / q.den, fi = c.fx * id, gi = c.fy * id;
+    const double sx = q.xc * s, sy = q.yc * s;
+    m00 = fi * (1.0 - q.mx * sx);
+    m01 = -(fi * (q.mx * sy));
+    m02 = -(fi * (q.mx * dz));
+    m10 = -(gi * (q.my * sx));
+    m11 = gi * (1.0 - q.my * sy);
+    m12 = -(gi * (q.my * dz));
+}
 
 template <int LENS = AGX_LENS_RADTAN>
 AGX_HD void pose_accumulate(const agx_camera &c, const Pose &p, double acc[POSE_SUMS], double X, double Y, double uo, double vo)
@@ -329,11 +425,16 @@ AGX_HD void pose_accumulate(const agx_camera &c, const Pose &p, double acc[POSE_
     const double e = pose_error<LENS>(c, p, X, Y, uo, vo, q, eu, ev);
     acc[27] += e;
     if (!(e < __builtin_inf())) return;
-    const double x = q.x, y = q.y;
-    double d00, d01, d10, d11;
-    pose_lens_jacobian(c, q, d00, d01, d10, d11);
-    const double m00 = c.fx * d00 / q.zc, m01 = c.fx * d01 / q.zc, m02 = -(m00 * x + m01 * y);
-    const double m10 = c.fy * d10 / q.zc, m11 = c.fy * d11 / q.zc, m12 = -(m10 * x + m11 * y);
+    double m00, m01, m02, m10, m11, m12;  // d(u, v) / d(Xc, Yc, Zc)
+    if constexpr (LENS == AGX_LENS_DOUBLE_SPHERE) {
+        pose_ds_jacobian(c, q, m00, m01, m02, m10, m11, m12);
+    } else {
+        const double x = q.x, y = q.y;
+        double d00, d01, d10, d11;
+        pose_lens_jacobian(c, q, d00, d01, d10, d11);
+        m00 = c.fx * d00 / q.zc, m01 = c.fx * d01 / q.zc, m02 = -(m00 * x + m01 * y);
+        m10 = c.fy * d10 / q.zc, m11 = c.fy * d11 / q.zc, m12 = -(m10 * x + m11 * y);
+    }
     // G = -R [P]x for P = (X, Y, 0): columns Y c3, -X c3, X c2 - Y c1
     const double g00 = Y * p.R[2], g10 = Y * p.R[5], g20 = Y * p.R[8];
     const double g01 = -(X * p.R[2]), g11 = -(X * p.R[5]), g21 = -(X * p.R[8]);
@@ -415,7 +516,7 @@ AGX_HD float pose_row_residual(const FitGeom &g, double tag_size, const agx_came
     return (float)worst;
 }
 
-// the predicted corners of the layout's tag t, rounded to binary32; NaN, NaN where Zc is not > 0
+// the predicted corners of the layout's tag t, rounded to binary32; NaN, NaN without a projection
 template <int LENS = AGX_LENS_RADTAN>
 AGX_HD void pose_predict(const FitGeom &g, double tag_size, const agx_camera &c, const Pose &p, uint32_t t, float xy[8])
 {
@@ -436,10 +537,12 @@ AGX_HD void pose_predict(const FitGeom &g, double tag_size, const agx_camera &c,
 // the best-iterate rule: does an iterate whose sum of |e|^2 is `cost` replace the best so far
 AGX_HD bool pose_better(double cost, bool have, double best_cost) { return f64_finite(cost) && (!have || cost < best_cost); }
 
-// what both forms refuse in the camera and the pose's own scalars (under AGX_LENS_EQUIDISTANT the ninth double is 0)
+// what both forms refuse in the camera and the pose's own scalars (under AGX_LENS_EQUIDISTANT the ninth double is 0; under
+// AGX_LENS_DOUBLE_SPHERE the seventh, eighth and ninth are exactly 0, -1 < xi <= 1 and 0 <= alpha <= 1)
 AGX_HD bool pose_args_ok(int lens, const agx_camera &c, double tag_size, uint32_t iterations)
 {
-    if (lens != AGX_LENS_RADTAN && !(lens == AGX_LENS_EQUIDISTANT && c.k3 == 0.0)) return false;
+    const bool ds = lens == AGX_LENS_DOUBLE_SPHERE && c.p1 == 0.0 && c.p2 == 0.0 && c.k3 == 0.0 && c.k1 > -1.0 && c.k1 <= 1.0 && c.k2 >= 0.0 && c.k2 <= 1.0;
+    if (lens != AGX_LENS_RADTAN && !(lens == AGX_LENS_EQUIDISTANT && c.k3 == 0.0) && !ds) return false;
     const double v[9] = {c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2, c.k3};
     for (int i = 0; i < 9; ++i)
         if (!f64_finite(v[i])) return false;

@@ -2372,7 +2372,7 @@ int agx_board_pose_enqueue_m(agx_detector *det, int n_frames, const agx_tag *d_t
     agx_camera cam;
     std::memcpy(&cam, camera, sizeof cam);
     if (!pose_args_ok(lens_model, cam, tag_size, iterations))
-        return fail(det, AGX_ERR_ARG, "lens_model AGX_LENS_RADTAN or AGX_LENS_EQUIDISTANT (its ninth double 0), every camera field finite with fx and fy > 0, tag_size finite and > 0, iterations <= 64");
+        return fail(det, AGX_ERR_ARG, "lens_model AGX_LENS_RADTAN, AGX_LENS_EQUIDISTANT (its ninth double 0) or AGX_LENS_DOUBLE_SPHERE (xi in (-1, 1], alpha in [0, 1], its last three doubles 0), every camera field finite with fx and fy > 0, tag_size finite and > 0, iterations <= 64");
     if ((((uintptr_t)d_tags | (uintptr_t)d_n_tags | (uintptr_t)d_tag_status | (uintptr_t)d_err_sq | (uintptr_t)d_row_status | (uintptr_t)d_n_inliers |
           (uintptr_t)d_rms | (uintptr_t)d_best_iter | (uintptr_t)d_pred | (uintptr_t)d_n_pred | (uintptr_t)d_status) & 3) || ((uintptr_t)d_pose & 7))
         return fail(det, AGX_ERR_ARG, "d_pose must be 8-byte aligned, every other array 4-byte aligned");
@@ -2498,7 +2498,7 @@ int agx_debug_pose_project(int lens_model, const double *camera, const double *x
 
 // ---- rectified batches (rectify.hip: k_rectify_map, k_remap, k_rectified_points and the host forms) -------------------------------
 static const char *kRectifyGeomRule =
-    "lens_model AGX_LENS_RADTAN or AGX_LENS_EQUIDISTANT (its ninth double 0), every camera field finite with fx and fy > 0, new_camera "
+    "lens_model AGX_LENS_RADTAN, AGX_LENS_EQUIDISTANT (its ninth double 0) or AGX_LENS_DOUBLE_SPHERE (xi in (-1, 1], alpha in [0, 1], its last three doubles 0), every camera field finite with fx and fy > 0, new_camera "
     "finite with fx' and fy' > 0, rotation NULL or finite";
 
 static bool rectify_map_args(int lens_model, const double *camera, const double *new_camera, const double *rotation, int src_width,

@@ -1772,7 +1772,7 @@ uint32_t board_fit(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint3
     return status;
 }
 
-// (one text for both lens models, as the kernel's)
+// (one text for every lens model, as the kernel's; cam is pose_camera()'s)
 template <int LENS>
 static uint32_t board_pose_lens(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint32_t tag_status, uint32_t cols, uint32_t rows,
                                 uint32_t first_id, float spacing_ratio, double tag_size, const agx_camera &cam, float max_err_sq, uint32_t max_drop,
@@ -1910,8 +1910,10 @@ uint32_t board_pose(int lens, const agx_tag *tags, uint32_t tag_cap, uint32_t n_
                     uint32_t min_tags, uint32_t iterations, int flags, double *pose_out, float *err_sq, uint32_t *row_status, uint32_t *n_inliers,
                     float *rms, uint32_t *best_iter, agx_tag *pred, uint32_t *n_pred, double *iter_sums)
 {
-    const auto run = lens == AGX_LENS_EQUIDISTANT ? board_pose_lens<AGX_LENS_EQUIDISTANT> : board_pose_lens<AGX_LENS_RADTAN>;
-    return run(tags, tag_cap, n_tags, tag_status, cols, rows, first_id, spacing_ratio, tag_size, cam, max_err_sq, max_drop, min_tags, iterations,
+    const auto run = lens == AGX_LENS_DOUBLE_SPHERE ? board_pose_lens<AGX_LENS_DOUBLE_SPHERE>
+                     : lens == AGX_LENS_EQUIDISTANT ? board_pose_lens<AGX_LENS_EQUIDISTANT>
+                                                    : board_pose_lens<AGX_LENS_RADTAN>;
+    return run(tags, tag_cap, n_tags, tag_status, cols, rows, first_id, spacing_ratio, tag_size, pose_camera(lens, cam), max_err_sq, max_drop, min_tags, iterations,
                flags, pose_out, err_sq, row_status, n_inliers, rms, best_iter, pred, n_pred, iter_sums);
 }
 
@@ -1920,12 +1922,16 @@ void pose_atan_host(const double *r, uint32_t n, double *out)
     for (uint32_t i = 0; i < n; ++i) out[i] = pose_atan(r[i]);
 }
 
-void pose_project_host(int lens, const agx_camera &cam, const double *xyz, uint32_t n, double *uv)
+void pose_project_host(int lens, const agx_camera &camera, const double *xyz, uint32_t n, double *uv)
 {
+    const agx_camera cam = pose_camera(lens, camera);
     for (uint32_t i = 0; i < n; ++i) {
         const Pose p = {{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, {0.0, 0.0, xyz[3 * i + 2]}};
         bool ok;
-        if (lens == AGX_LENS_EQUIDISTANT) {
+        if (lens == AGX_LENS_DOUBLE_SPHERE) {
+            PosePointDs q;
+            if ((ok = pose_project<AGX_LENS_DOUBLE_SPHERE>(cam, p, xyz[3 * i], xyz[3 * i + 1], q))) uv[2 * i] = q.u, uv[2 * i + 1] = q.v;
+        } else if (lens == AGX_LENS_EQUIDISTANT) {
             PosePointEqui q;
             if ((ok = pose_project<AGX_LENS_EQUIDISTANT>(cam, p, xyz[3 * i], xyz[3 * i + 1], q))) uv[2 * i] = q.u, uv[2 * i + 1] = q.v;
         } else {

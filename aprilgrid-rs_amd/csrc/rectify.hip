@@ -149,7 +149,9 @@ int launch_rectify_map(const RectifyMapArgs &a, void *stream)
 {
     if (rectify_map_args_bad(a)) return (int)hipErrorInvalidValue;
     const unsigned grid = (unsigned)(((size_t)a.dst_w * a.dst_h + RECT_BLOCK - 1) / RECT_BLOCK);
-    if (a.lens == AGX_LENS_EQUIDISTANT)
+    if (a.lens == AGX_LENS_DOUBLE_SPHERE)
+        hipLaunchKernelGGL(k_rectify_map<AGX_LENS_DOUBLE_SPHERE>, dim3(grid), dim3(RECT_BLOCK), 0, (hipStream_t)stream, a);
+    else if (a.lens == AGX_LENS_EQUIDISTANT)
         hipLaunchKernelGGL(k_rectify_map<AGX_LENS_EQUIDISTANT>, dim3(grid), dim3(RECT_BLOCK), 0, (hipStream_t)stream, a);
     else
         hipLaunchKernelGGL(k_rectify_map<AGX_LENS_RADTAN>, dim3(grid), dim3(RECT_BLOCK), 0, (hipStream_t)stream, a);
@@ -161,7 +163,9 @@ int launch_rectified_points(const RectifiedPointsArgs &a, void *stream)
     if (rectified_points_args_bad(a)) return (int)hipErrorInvalidValue;
     if (!a.n) return (int)hipSuccess;
     const unsigned grid = (a.n + RECT_BLOCK - 1) / RECT_BLOCK;
-    if (a.lens == AGX_LENS_EQUIDISTANT)
+    if (a.lens == AGX_LENS_DOUBLE_SPHERE)
+        hipLaunchKernelGGL(k_rectified_points<AGX_LENS_DOUBLE_SPHERE>, dim3(grid), dim3(RECT_BLOCK), 0, (hipStream_t)stream, a);
+    else if (a.lens == AGX_LENS_EQUIDISTANT)
         hipLaunchKernelGGL(k_rectified_points<AGX_LENS_EQUIDISTANT>, dim3(grid), dim3(RECT_BLOCK), 0, (hipStream_t)stream, a);
     else
         hipLaunchKernelGGL(k_rectified_points<AGX_LENS_RADTAN>, dim3(grid), dim3(RECT_BLOCK), 0, (hipStream_t)stream, a);
@@ -232,13 +236,15 @@ void remap_host_t(const RemapArgs &a)
 
 void rectify_map_host(const RectifyMapArgs &a)
 {
-    if (a.lens == AGX_LENS_EQUIDISTANT) rectify_map_host_t<AGX_LENS_EQUIDISTANT>(a);
+    if (a.lens == AGX_LENS_DOUBLE_SPHERE) rectify_map_host_t<AGX_LENS_DOUBLE_SPHERE>(a);
+    else if (a.lens == AGX_LENS_EQUIDISTANT) rectify_map_host_t<AGX_LENS_EQUIDISTANT>(a);
     else rectify_map_host_t<AGX_LENS_RADTAN>(a);
 }
 
 void rectified_points_host(const RectifiedPointsArgs &a)
 {
-    if (a.lens == AGX_LENS_EQUIDISTANT) rectified_points_host_t<AGX_LENS_EQUIDISTANT>(a);
+    if (a.lens == AGX_LENS_DOUBLE_SPHERE) rectified_points_host_t<AGX_LENS_DOUBLE_SPHERE>(a);
+    else if (a.lens == AGX_LENS_EQUIDISTANT) rectified_points_host_t<AGX_LENS_EQUIDISTANT>(a);
     else rectified_points_host_t<AGX_LENS_RADTAN>(a);
 }
 

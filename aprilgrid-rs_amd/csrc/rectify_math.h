@@ -6,7 +6,8 @@
 //   dx = (x - cx') / fx',  dy = (y - cy') / fy';   X = R0 dx + R1 dy + R2,  Y = R3 dx + R4 dy + R5,  Z = R6 dx + R7 dy + R8
 //   (left to right; R row major, rectified frame -> camera frame; no rotation is the identity matrix through the same statements);
 //   (u, v) = board_pose_math.h's pose_project<LENS> of the point (X, Y) under the identity pose moved to Z -- the call behind
-//   agx_debug_pose_project, not restated here.  No projection: Z not > 0, or u or v not finite.
+//   agx_debug_pose_project, not restated here.  No projection: Z not > 0 (under AGX_LENS_DOUBLE_SPHERE: (X, Y, Z) outside the
+//   model's valid cone, which reaches past Z = 0), or u or v not finite.
 // rectified_points rounds (u, v) to binary32, (NaN, NaN) without a projection.  The map's entry at the integer position (i, j) is
 //   mx = floor(u 32 + 1/2),  my = floor(v 32 + 1/2)  in binary64, kept if 0 <= mx <= 32 (src_w - 1) and 0 <= my <= 32 (src_h - 1);
 //   else, and without a projection, both words are RECT_NONE (AGX_MAP_NONE).
@@ -115,6 +116,7 @@ inline bool rectify_geom(int lens, const double *camera, const double *new_camer
     const double *c = camera;
     g.cam = agx_camera{c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8]};
     if (!pose_args_ok(lens, g.cam, 1.0, 0)) return false;
+    g.cam = pose_camera(lens, g.cam);  // (the double-sphere model's w2: once per call, for the kernel and the host form)
     for (int i = 0; i < 4; ++i)
         if (!f64_finite(new_camera[i])) return false;
     if (!(new_camera[0] > 0.0) || !(new_camera[1] > 0.0)) return false;

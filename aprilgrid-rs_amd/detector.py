@@ -1190,7 +1190,7 @@ class TagDetector:
                            tag_size=1.0, first_id=0, spacing_ratio=0.3, max_err_sq=4.0, max_drop=0, min_tags=1, iterations=10,
                            predict_missing=False, tag_status=None):
         """Per frame the pose of the printed board in the camera frame under `camera` (a Camera: pinhole + radial-tangential, or
-        Camera.equidistant's fisheye model -- the camera's model attribute picks the kernel)
+        Camera.equidistant's fisheye or Camera.double_sphere's model -- the camera's model attribute picks the kernel)
         through every corner of the frame's tag table, its outlier rounds and the predicted corners of the layout's tags through
         the lens model (board_pose, the host form, says what is computed), in device tensors and stream-ordered behind torch's
         current stream; nothing to fetch.  tags, n_tags, tag_status and err_sq, row_status, n_inliers, rms, pred, n_pred, status
@@ -1317,7 +1317,7 @@ class TagDetector:
 
     def detect_rectified(self, frames, camera, new_camera=None, dst_size=None, rotation=None, to_source=False, border=0, **detect_kw):
         """detect_batch on the frames as the ideal pinhole `new_camera` (default: the camera's own fx fy cx cy) would have seen
-        them: frames, a device tensor [N, H, W] uint8 / 16-bit of `camera` (a Camera of either lens model), go through remap_enqueue
+        them: frames, a device tensor [N, H, W] uint8 / 16-bit of `camera` (a Camera of any lens model), go through remap_enqueue
         into a batch of dst_size (w, h; default the frames' size) on the device and detect_batch_device runs on that batch
         (detect_kw: its keywords).  The map is computed on the device once and kept on the detector, keyed by the arguments.
         -> detect_batch's structure, the corners in rectified pixels or, with to_source=True, in the sensor's (rectified_points of
@@ -2203,7 +2203,7 @@ def board_fit(tags, cols, rows, img_size, first_id=0, spacing_ratio=0.3, max_err
 class Camera(namedtuple("Camera", "fx fy cx cy k1 k2 p1 p2 k3", defaults=(0.0, 0.0, 0.0, 0.0, 0.0))):
     """agx_camera: the pinhole + radial-tangential model (OpenCV's; Kalibr's pinhole-radtan with k3 = 0).  Camera(fx, fy, cx, cy)
     is a pinhole.  model is the lens model the nine numbers are read under (AGX_LENS_*): AGX_LENS_RADTAN here,
-    AGX_LENS_EQUIDISTANT for a camera made by Camera.equidistant."""
+    AGX_LENS_EQUIDISTANT for a camera made by Camera.equidistant, AGX_LENS_DOUBLE_SPHERE for one made by Camera.double_sphere."""
     __slots__ = ()
     model = _ffi.AGX_LENS_RADTAN
 
@@ -2218,6 +2218,14 @@ class Camera(namedtuple("Camera", "fx fy cx cy k1 k2 p1 p2 k3", defaults=(0.0, 0
         + (cx, cy).  A Camera whose model is AGX_LENS_EQUIDISTANT and whose nine numbers are fx, fy, cx, cy, k1, k2, k3, k4, 0."""
         return _EquidistantCamera(fx, fy, cx, cy, k1, k2, k3, k4, 0.0)
 
+    @staticmethod
+    def double_sphere(fx, fy, cx, cy, xi, alpha):
+        """The double-sphere model (Usenko, Demmel, Cremers 2018; Kalibr's ds, Basalt's default): d1 = |(X, Y, Z)|, k = xi d1 + Z,
+        d2 = |(X, Y, k)|, (u, v) = (fx X, fy Y) / (alpha d2 + (1 - alpha) k) + (cx, cy), for every point inside the model's valid
+        cone, points with Z <= 0 among them.  -1 < xi <= 1, 0 <= alpha <= 1.  A Camera whose model is AGX_LENS_DOUBLE_SPHERE and
+        whose nine numbers are fx, fy, cx, cy, xi, alpha, 0, 0, 0."""
+        return _DoubleSphereCamera(fx, fy, cx, cy, xi, alpha, 0.0, 0.0, 0.0)
+
 
 class _EquidistantCamera(Camera):
     """Camera.equidistant's: the same nine numbers in the order the equidistant model reads them (k3, k4 by name; p1, p2 are the
@@ -2229,6 +2237,17 @@ class _EquidistantCamera(Camera):
 
     def __repr__(self):
         return "Camera.equidistant(fx=%r, fy=%r, cx=%r, cy=%r, k1=%r, k2=%r, k3=%r, k4=%r)" % tuple(self[:8])
+
+
+class _DoubleSphereCamera(Camera):
+    """Camera.double_sphere's: xi and alpha by name (the tuple's fourth and fifth fields, k1 and k2); the last three numbers are 0."""
+    __slots__ = ()
+    model = _ffi.AGX_LENS_DOUBLE_SPHERE
+    xi = property(lambda self: self[4])
+    alpha = property(lambda self: self[5])
+
+    def __repr__(self):
+        return "Camera.double_sphere(fx=%r, fy=%r, cx=%r, cy=%r, xi=%r, alpha=%r)" % tuple(self[:6])
 
 
 def _camera(camera):
@@ -2302,7 +2321,7 @@ def _rectify_args(camera, src_size, dst_size, new_camera, rotation):
 
 
 def rectify_map(camera, src_size, dst_size=None, new_camera=None, rotation=None, row_stride=None):
-    """The rectification map of `camera` (a Camera of either lens model) without a device (agx_rectify_map_tail): for every pixel
+    """The rectification map of `camera` (a Camera of any lens model) without a device (agx_rectify_map_tail): for every pixel
     (i, j) of the ideal pinhole new_camera = (fx', fy', cx', cy') of dst_size = (w, h) the sensor pixel it comes from -- the ray
     ((i - cx') / fx', (j - cy') / fy', 1), turned by rotation (3 x 3, rectified frame -> camera frame), projected through the
     lens model -- in units of 1/32 px of the src_size = (w, h) sensor image, rounded to nearest.

@@ -167,6 +167,7 @@ pub const AGX_FIT_ROW_OUTLIER: c_int = 1;
 pub const AGX_FIT_ROW_OFF_BOARD: c_int = 2;
 pub const AGX_LENS_RADTAN: c_int = 0;
 pub const AGX_LENS_EQUIDISTANT: c_int = 1;
+pub const AGX_LENS_DOUBLE_SPHERE: c_int = 2;
 /// both words of a rectification map's entry that has no source pixel (the header's `#define AGX_MAP_NONE`, INT32_MIN)
 pub const AGX_MAP_NONE: i32 = i32::MIN;
 // agx_debug_fetch items
@@ -387,7 +388,8 @@ extern "C" {
                                      first_id: u32, spacing_ratio: c_float, tag_size: c_double, camera: *const c_double,
                                      max_err_sq: c_float, max_drop: u32, min_tags: u32, iterations: u32, flags: c_int,
                                      status: *mut u32, iter_sums: *mut c_double) -> c_int;
-    // lens_model: AGX_LENS_*; under AGX_LENS_EQUIDISTANT camera is fx, fy, cx, cy, k1, k2, k3, k4, 0
+    // lens_model: AGX_LENS_*; under AGX_LENS_EQUIDISTANT camera is fx, fy, cx, cy, k1, k2, k3, k4, 0; under
+    // AGX_LENS_DOUBLE_SPHERE fx, fy, cx, cy, xi, alpha, 0, 0, 0
     pub fn agx_board_pose_enqueue_m(det: *mut agx_detector, n_frames: c_int, d_tags: *const agx_tag, tags_per_frame: u32, d_n_tags: *const u32,
                                     d_tag_status: *const u32, cols: u32, rows: u32, first_id: u32, spacing_ratio: c_float, tag_size: c_double,
                                     lens_model: c_int, camera: *const c_double, max_err_sq: c_float, max_drop: u32, min_tags: u32,

@@ -817,6 +817,8 @@ pub enum LensModel {
     Radtan = 0,
     /// pinhole-equidistant (Kalibr's pinhole-equi, OpenCV's fisheye): `Camera::equidistant`
     Equidistant = 1,
+    /// double sphere (Usenko, Demmel, Cremers 2018; Kalibr's ds, Basalt's default): `Camera::double_sphere`
+    DoubleSphere = 2,
 }
 
 impl Camera {
@@ -824,6 +826,12 @@ impl Camera {
     /// `k3` is 0.  To be passed with `LensModel::Equidistant`.
     pub fn equidistant(fx: f64, fy: f64, cx: f64, cy: f64, k1: f64, k2: f64, k3: f64, k4: f64) -> Camera {
         Camera { fx, fy, cx, cy, k1, k2, p1: k3, p2: k4, k3: 0.0 }
+    }
+
+    /// The nine doubles of the double-sphere model, `fx, fy, cx, cy, xi, alpha, 0, 0, 0`: `k1` holds `xi` (in `(-1, 1]`), `k2` holds
+    /// `alpha` (in `[0, 1]`).  To be passed with `LensModel::DoubleSphere`.  Points with `Z <= 0` inside the model's valid cone project.
+    pub fn double_sphere(fx: f64, fy: f64, cx: f64, cy: f64, xi: f64, alpha: f64) -> Camera {
+        Camera { fx, fy, cx, cy, k1: xi, k2: alpha, p1: 0.0, p2: 0.0, k3: 0.0 }
     }
 }
 

@@ -1201,9 +1201,25 @@ int agx_debug_board_pose_sums(const agx_tag *tags, uint32_t tags_per_frame, uint
  * pinhole ray must exist; the refinement runs through the forward model and has no such limit), and to r = tan(theta) by the
  * series of tan(theta / 8) through its 15th power and 3 doublings t <- 2 t / (1 - t^2); then the homography and its
  * decomposition as above.  A value that is not finite ends as AGX_FIT_SINGULAR.
- * AGX_ERR_ARG (a batch in flight stays where it is): the calls' own list, a lens_model that is neither, and under
- * AGX_LENS_EQUIDISTANT a ninth double that is not 0. */
+ * AGX_LENS_DOUBLE_SPHERE: the double-sphere model (Usenko, Demmel, Cremers 2018; Kalibr's ds, Basalt's default) of lenses of
+ * 180 degrees and more.  camera: nine doubles in the order fx, fy, cx, cy, xi, alpha, 0, 0, 0 (agx_camera's k1 and k2 hold xi and
+ * alpha here).  For a point (X, Y, Z) in the camera frame: d1 = sqrt(X^2 + Y^2 + Z^2), k = xi d1 + Z, d2 = sqrt(X^2 + Y^2 + k^2),
+ * den = alpha d2 + (1 - alpha) k, u = fx (X / den) + cx, v = fy (Y / den) + cy.  Validity: with w1 = alpha / (1 - alpha) for
+ * alpha <= 0.5, else (1 - alpha) / alpha, and w2 = (w1 + xi) / sqrt(2 w1 xi + xi^2 + 1), the point has a projection iff d1 > 0 and
+ * Z > -w2 d1.  Nothing else refuses it: Z <= 0 is NO refusal under this model -- a corner more than 90 degrees off the axis inside
+ * that cone is fitted and predicted like any other.  w2 is computed once per call, on the host, for both forms.
+ * Arithmetic: + - * / and the correctly rounded square root only -- no atan, no series, no iteration.  Jacobian: d(u, v) /
+ * d(X, Y, Z) directly in closed form (not through x = X / Z).  Seed: an observed pixel goes through the closed-form unprojection
+ * mx = (u - cx) / fx, my = (v - cy) / fy, r2 = mx^2 + my^2, mz = (1 - alpha^2 r2) / (alpha sqrt(1 - (2 alpha - 1) r2) + 1 - alpha),
+ * ray = (mz xi + sqrt(mz^2 + (1 - xi^2) r2)) / (mz^2 + r2) (mx, my, mz) - (0, 0, xi), and (ray_x, ray_y) / ray_z enters the
+ * homography.  The seed, and only the seed, clamps (a pinhole ray must exist): a pixel whose ray lies 1.5 rad or more off the axis,
+ * or has ray_z <= 0, or that is outside the unprojection's domain (1 - (2 alpha - 1) r2 < 0, for alpha > 0.5 only), takes the
+ * direction (mx, my) at the radius tan(1.5).  A pixel on the principal point gives (0, 0) with no division by r.
+ * AGX_ERR_ARG (a batch in flight stays where it is): the calls' own list, a lens_model that is none of the three, under
+ * AGX_LENS_EQUIDISTANT a ninth double that is not 0, and under AGX_LENS_DOUBLE_SPHERE an alpha outside [0, 1], a xi outside
+ * (-1, 1], or a seventh, eighth or ninth double that is not exactly 0. */
 enum { AGX_LENS_RADTAN = 0, AGX_LENS_EQUIDISTANT = 1 };
+enum { AGX_LENS_DOUBLE_SPHERE = 2 };
 int agx_board_pose_enqueue_m(agx_detector *det, int n_frames,
                              const agx_tag *d_tags, uint32_t tags_per_frame, const uint32_t *d_n_tags, const uint32_t *d_tag_status,
                              uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
@@ -1225,7 +1241,7 @@ int agx_debug_board_pose_sums_m(const agx_tag *tags, uint32_t tags_per_frame, ui
                                 uint32_t *status, double *iter_sums);
 /* For tests of the arithmetic, no handle and no device: the host form's atan of r [n] (each >= 0 and finite) into out [n]; and
  * its projection of n points (X, Y, Z) of the camera frame, xyz [n][3], into uv [n][2] under lens_model and camera ((NaN, NaN)
- * where Z is not > 0).  AGX_ERR_ARG: a NULL array with n > 0, an r that is negative or not finite; agx_board_pose_tail_m's
+ * where Z is not > 0; under AGX_LENS_DOUBLE_SPHERE where the point is outside the valid cone instead).  AGX_ERR_ARG: a NULL array with n > 0, an r that is negative or not finite; agx_board_pose_tail_m's
  * rules on lens_model and camera. */
 int agx_debug_pose_atan(const double *r, uint32_t n, double *out);
 int agx_debug_pose_project(int lens_model, const double *camera, const double *xyz, uint32_t n, double *uv);
@@ -1243,13 +1259,14 @@ int agx_debug_pose_project(int lens_model, const double *camera, const double *x
  * camera frame, HOST memory (NULL: the identity); (u, v) = the projection of (X, Y, Z) under lens_model and camera -- the one of
  * agx_board_pose_enqueue_m, the function agx_debug_pose_project hands out, binary64 in its order of operations.  The entry is two
  * int (32-bit) words in units of 1/32 source pixel, mx = floor(32 u + 1/2), my = floor(32 v + 1/2) in binary64, valid if the
- * projection exists (Z > 0, u and v finite) and 0 <= mx <= 32 (src_width - 1), 0 <= my <= 32 (src_height - 1); otherwise both
+ * projection exists (Z > 0, under AGX_LENS_DOUBLE_SPHERE Z > -w2 d1 instead; u and v finite) and 0 <= mx <= 32 (src_width - 1), 0 <= my <= 32 (src_height - 1); otherwise both
  * words are AGX_MAP_NONE.  d_map [dst_height][dst_width][2] with map_row_stride_bytes between rows (a multiple of 8, at least
  * 8 dst_width; padding bytes are not written), caller-owned device memory, 8-byte aligned; stream-ordered, nothing to fetch; a
  * batch in flight is replaced as by agx_board_fit_enqueue.
  * The caller's responsibility: the radial-tangential polynomial is applied as it stands.  Beyond the radius where it stops being
  * monotone, far rays fold back into the image (as in OpenCV's initUndistortRectifyMap); choosing new_camera and the target size
- * inside that radius is the caller's job.  The equidistant model has no such radius below Z = 0.
+ * inside that radius is the caller's job.  The equidistant model has no such radius below Z = 0.  The double-sphere model
+ * is carried past Z = 0: a rotated ray with Z <= 0 inside the valid cone has a map entry and a rectified point.
  * AGX_ERR_ARG (a batch in flight stays where it is): agx_board_pose_enqueue_m's rules on lens_model and camera; a NULL or
  * non-finite new_camera, or fx' or fy' not > 0; a non-finite rotation; a size below 1 or above 16384; a NULL or misaligned d_map,
  * a stride that is no multiple of 8 or below 8 dst_width.

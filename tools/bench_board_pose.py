@@ -4,7 +4,9 @@ on the same tables in the same run.  One GPU, one process.
 The tables: the 36 tags of a 6 x 6 board (tag side 0.05, spacing 0.3) under one tilted pose per frame, projected in numpy float64
 through the model -- once through a pinhole (fx = fy = 400 on 800 x 600), once through the same camera with k1 = -0.3, k2 = 0.1,
 once through the same pinhole under the equidistant model with Kalibr-sized coefficients (Camera.equidistant: the kernel's
-AGX_LENS_EQUIDISTANT instantiation; profiles/board_pose_equi.json holds three readings of this run beside the parent's figures)
+AGX_LENS_EQUIDISTANT instantiation; profiles/board_pose_equi.json holds three readings of this run beside the parent's figures),
+once through a double-sphere camera of the same focal length near the axis (Camera.double_sphere, xi = 0.6, alpha = 0.45: the
+AGX_LENS_DOUBLE_SPHERE instantiation; profiles/board_pose_ds.json)
 -- moved by +-0.1 px and rounded to binary32; resident on the device.  k_board_pose is taken at iterations 0, 5 and 10 on
 both, and at 10 with one row per frame stored under a wrong id and max_drop 1, which costs a second round; k_board_fit on the
 pinhole tables with every tag predicted.
@@ -51,7 +53,12 @@ def tables(n, cam, rng):
         Q = np.stack([X, Y, np.zeros_like(X)], -1) @ R.T + tr
         x, y = Q[..., 0] / Q[..., 2], Q[..., 1] / Q[..., 2]
         r2 = x * x + y * y
-        if getattr(cam, "model", 0):  # Camera.equidistant: theta_d / r in rad's place
+        if getattr(cam, "model", 0) == 2:  # Camera.double_sphere: the model's own denominator in Z's place
+            d1 = np.sqrt((Q ** 2).sum(-1))
+            kk = cam[4] * d1 + Q[..., 2]
+            den = cam[5] * np.sqrt(Q[..., 0] ** 2 + Q[..., 1] ** 2 + kk ** 2) + (1 - cam[5]) * kk
+            x, y, rad = Q[..., 0] / den, Q[..., 1] / den, 1.0
+        elif getattr(cam, "model", 0):  # Camera.equidistant: theta_d / r in rad's place
             th = np.arctan(np.sqrt(r2))
             rad = th * (1 + k1 * th ** 2 + k2 * th ** 4 + cam[6] * th ** 6 + cam[7] * th ** 8) / np.sqrt(r2)
         else:
@@ -78,7 +85,8 @@ def main():
     dev = torch.device("cuda", 0)
     F = args.frames
     cams = {"pinhole": A.Camera(400.0, 400.0, 400.0, 300.0), "barrel": A.Camera(400.0, 400.0, 400.0, 300.0, -0.3, 0.1),
-            "equidistant": A.Camera.equidistant(400.0, 400.0, 400.0, 300.0, -0.013, 0.021, -0.013, 0.0026)}
+            "equidistant": A.Camera.equidistant(400.0, 400.0, 400.0, 300.0, -0.013, 0.021, -0.013, 0.0026),
+            "double_sphere": A.Camera.double_sphere(640.0, 640.0, 400.0, 300.0, 0.6, 0.45)}
     det = A.TagDetector("t36h11", None, device=0)
     i32 = dict(dtype=torch.int32, device=dev)
     f32 = dict(dtype=torch.float32, device=dev)

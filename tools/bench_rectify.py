@@ -1,6 +1,8 @@
 """Device time per batch of k_remap (agx_remap_enqueue) at 256 frames of 1280 x 800 through the map of an equidistant camera into a
 target of the same size, beside a device-to-device copy of the same batch in the same run -- the floor for one byte in and one
-byte out per pixel -- for AGX_L8 and AGX_L16, and k_rectify_map once.  One GPU, one process.
+byte out per pixel -- for AGX_L8 and AGX_L16, and k_rectify_map once; then k_rectify_map under a double-sphere camera of the same
+focal length near the axis (fx = 420 (1 + xi), xi = 0.6, alpha = 0.45) and k_rectified_points under both over one point per pixel
+(profiles/rectify_ds.json).  One GPU, one process.
 
 The camera: pinhole-equidistant, fx = fy = 420 on 1280 x 800 with Kalibr-sized coefficients, rectified to the pinhole of the same
 fx fy cx cy (every target pixel has a source pixel there; the share of entries without one is reported).  The frames
@@ -75,6 +77,18 @@ def main():
     host = m.cpu().numpy()
     assert host.tobytes() == A.rectify_map(cam, (W, H)).tobytes(), "the device's map is not the host form's"
     result["map_entries_without_a_source_pixel"] = round(float((host[..., 0] == _ffi.AGX_MAP_NONE).mean()), 4)
+    # the double-sphere rows: k_rectify_map and k_rectified_points (one point per pixel of the target) beside the equidistant camera's
+    ds = A.Camera.double_sphere(672.0, 672.0, 640.0, 400.0, 0.6, 0.45)
+    m_ds = torch.empty((H, W, 2), dtype=torch.int32, device=dev)
+    result["k_rectify_map_double_sphere"] = med(timed(lambda: det.rectify_map_enqueue(ds, (W, H), out=m_ds)))
+    assert m_ds.cpu().numpy().tobytes() == A.rectify_map(ds, (W, H)).tobytes(), "the device's double-sphere map is not the host form's"
+    result["map_entries_without_a_source_pixel_double_sphere"] = round(float((m_ds[..., 0] == _ffi.AGX_MAP_NONE).float().mean().item()), 4)
+    jj, ii = torch.meshgrid(torch.arange(H, device=dev, dtype=torch.float32), torch.arange(W, device=dev, dtype=torch.float32), indexing="ij")
+    pts = torch.stack([ii, jj], dim=-1).contiguous()
+    out = torch.empty_like(pts)
+    for name, c in (("equidistant", cam), ("double_sphere", ds)):
+        result["k_rectified_points_%s_%d_points" % (name, W * H)] = med(timed(lambda: det.rectified_points_enqueue(pts, c, c[:4], out=out)))
+    del m_ds, pts, out
     groups = (F + FRAMES_PER_GROUP - 1) // FRAMES_PER_GROUP
     for name, dtype, px in (("l8", torch.uint8, 1), ("l16", torch.int16, 2)):
         src = torch.randint(0, 256, (F, H, W), dtype=torch.uint8, device=dev)
