@@ -1,7 +1,7 @@
 // board_fit.h -- host-visible interface of k_board_fit (board_fit.hip): the board-to-image homography through every frame's tag
 // table, its outlier rounds and the predicted corners of the layout's tags (agx_board_fit_enqueue).  The arithmetic is
-// board_fit_math.h's; host_tail.cpp's board_fit is the same on the host.  Internal to the library; the public boundary is
-// include/aprilgrid_amd.h.
+// board_fit_math.h's, the rounds are board_rounds.h's; host_tail.cpp's board_fit is the same on the host.  Internal to the
+// library; the public boundary is include/aprilgrid_amd.h.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -12,7 +12,7 @@ namespace agx {
 
 constexpr int FIT_FRAMES_PER_WG = 2;  // one wave per frame; two frames' staged rows fit the 64 KiB of static LDS
 
-// All pointers are device pointers.
+// All pointers are device pointers for the kernel; the host form (board_fit) reads frame 0 of a record of host pointers.
 struct BoardFitArgs {
     int n_frames;
     const agx_tag *tags;         // [n_frames][tags_per_frame]
@@ -34,7 +34,11 @@ struct BoardFitArgs {
     uint32_t *n_pred;      // [n_frames]
     uint32_t *status;      // [n_frames]: AGX_FIT_*
 };
-// one wave per frame, FIT_FRAMES_PER_WG frames per workgroup; n_frames * tags_per_frame < 2^27; hipError_t
+// The rule that the record breaks, or null: every entry point's check and the launch's.  device: the kernel's record (n_frames and
+// tags_per_frame > 0, tag_status may be null); else the host form's, whose tags, err_sq and row_status may be null while
+// n_tags[0] == 0.  Arrays 4-byte aligned, h 8-byte; n_frames * tags_per_frame < 2^27.
+const char *board_fit_args_bad(const BoardFitArgs &b, bool device);
+// one wave per frame, FIT_FRAMES_PER_WG frames per workgroup; hipError_t
 int launch_board_fit(const BoardFitArgs &b, void *stream);
 
 }  // namespace agx

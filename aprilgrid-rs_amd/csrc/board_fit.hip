@@ -16,6 +16,7 @@
 
 #include "board_fit.h"
 #include "board_fit_math.h"
+#include "board_rounds.h"
 
 namespace agx {
 namespace {
@@ -204,14 +205,14 @@ __global__ void __launch_bounds__(64 * FIT_FRAMES_PER_WG) k_board_fit(BoardFitAr
 
 }  // namespace
 
+const char *board_fit_args_bad(const BoardFitArgs &b, bool device)
+{
+    return rounds_args_bad(b, device, b.h, b.h, b.img_w > 0 && b.img_h > 0 ? nullptr : "img_w and img_h > 0");
+}
+
 int launch_board_fit(const BoardFitArgs &b, void *stream)
 {
-    if (b.n_frames <= 0 || !b.tags || !b.tags_per_frame || !b.n_tags || !b.cols || !b.rows ||
-        (unsigned long long)b.cols * b.rows > FIT_MAX_BOARD || !__builtin_isfinite(b.spacing_ratio) || !(b.spacing_ratio > -1.0f) ||
-        b.img_w <= 0 || b.img_h <= 0 || !(b.max_err_sq >= 0.0f) || !b.min_tags || (b.flags & ~AGX_FIT_PREDICT_MISSING) ||
-        (unsigned long long)b.n_frames * b.tags_per_frame >= (1ull << 27) || !b.h || !b.err_sq || !b.row_status || !b.n_inliers || !b.rms ||
-        !b.pred || !b.n_pred || !b.status)
-        return (int)hipErrorInvalidValue;
+    if (board_fit_args_bad(b, true)) return (int)hipErrorInvalidValue;
     const unsigned grid = ((unsigned)b.n_frames + FIT_FRAMES_PER_WG - 1) / FIT_FRAMES_PER_WG;
     hipLaunchKernelGGL(k_board_fit, dim3(grid), dim3(64 * FIT_FRAMES_PER_WG), 0, (hipStream_t)stream, b);
     return (int)hipGetLastError();

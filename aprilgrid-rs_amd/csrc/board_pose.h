@@ -1,7 +1,7 @@
 // board_pose.h -- host-visible interface of k_board_pose (board_pose.hip): the board's pose under a lens model through every
 // frame's tag table, its outlier rounds and the predicted corners of the layout's tags (agx_board_pose_enqueue).  The arithmetic
-// is board_pose_math.h's; host_tail.cpp's board_pose is the same on the host.  Internal to the library; the public boundary is
-// include/aprilgrid_amd.h.
+// is board_pose_math.h's, the rounds are board_rounds.h's; host_tail.cpp's board_pose is the same on the host.  Internal to the
+// library; the public boundary is include/aprilgrid_amd.h.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -12,7 +12,7 @@ namespace agx {
 
 constexpr int POSE_FRAMES_PER_WG = 2;  // one wave per frame; two frames' staged rows fit the 64 KiB of static LDS
 
-// All pointers are device pointers.
+// All pointers are device pointers for the kernel; the host form (board_pose) reads frame 0 of a record of host pointers.
 struct BoardPoseArgs {
     int n_frames;
     const agx_tag *tags;         // [n_frames][tags_per_frame]
@@ -38,8 +38,11 @@ struct BoardPoseArgs {
     uint32_t *n_pred;      // [n_frames]
     uint32_t *status;      // [n_frames]: AGX_FIT_*
 };
-// one wave per frame, POSE_FRAMES_PER_WG frames per workgroup; n_frames * tags_per_frame < 2^27; lens: AGX_LENS_*, which picks the
-// kernel's instantiation; hipError_t
+// The rule that the record breaks under the lens model `lens`, or null: board_fit_args_bad's rules with pose and best_iter for h,
+// and pose_args_ok (board_pose_math.h) for the camera (the caller's, before pose_camera()), tag_size and iterations.
+const char *board_pose_args_bad(const BoardPoseArgs &b, int lens, bool device);
+// one wave per frame, POSE_FRAMES_PER_WG frames per workgroup; lens: AGX_LENS_*, which picks the kernel's
+// instantiation; b.camera is the caller's; hipError_t
 int launch_board_pose(const BoardPoseArgs &b, int lens, void *stream);
 
 }  // namespace agx

@@ -21,6 +21,7 @@
 
 #include "board_pose.h"
 #include "board_pose_math.h"
+#include "board_rounds.h"
 
 namespace agx {
 namespace {
@@ -263,21 +264,21 @@ __global__ void __launch_bounds__(64 * POSE_FRAMES_PER_WG) k_board_pose(BoardPos
 
 }  // namespace
 
+const char *board_pose_args_bad(const BoardPoseArgs &b, int lens, bool device)
+{
+    return rounds_args_bad(b, device, b.pose, b.best_iter,
+                           pose_args_ok(lens, b.camera, b.tag_size, b.iterations) ? nullptr : AGX_LENS_CAMERA_RULE ", tag_size finite and > 0, iterations <= 64");
+}
+
 int launch_board_pose(const BoardPoseArgs &b, int lens, void *stream)
 {
-    if (b.n_frames <= 0 || !b.tags || !b.tags_per_frame || !b.n_tags || !b.cols || !b.rows ||
-        (unsigned long long)b.cols * b.rows > FIT_MAX_BOARD || !__builtin_isfinite(b.spacing_ratio) || !(b.spacing_ratio > -1.0f) ||
-        !pose_args_ok(lens, b.camera, b.tag_size, b.iterations) || !(b.max_err_sq >= 0.0f) || !b.min_tags || (b.flags & ~AGX_FIT_PREDICT_MISSING) ||
-        (unsigned long long)b.n_frames * b.tags_per_frame >= (1ull << 27) || !b.pose || !b.err_sq || !b.row_status || !b.n_inliers || !b.rms ||
-        !b.best_iter || !b.pred || !b.n_pred || !b.status)
-        return (int)hipErrorInvalidValue;
+    if (board_pose_args_bad(b, lens, true)) return (int)hipErrorInvalidValue;
     const unsigned grid = ((unsigned)b.n_frames + POSE_FRAMES_PER_WG - 1) / POSE_FRAMES_PER_WG;
-    if (lens == AGX_LENS_DOUBLE_SPHERE) {
-        BoardPoseArgs d = b;
-        d.camera = pose_camera(lens, b.camera);  // (w2 once per call, by the host form's statements)
-        hipLaunchKernelGGL(k_board_pose<AGX_LENS_DOUBLE_SPHERE>, dim3(grid), dim3(64 * POSE_FRAMES_PER_WG), 0, (hipStream_t)stream, d);
-    } else if (lens == AGX_LENS_EQUIDISTANT) hipLaunchKernelGGL(k_board_pose<AGX_LENS_EQUIDISTANT>, dim3(grid), dim3(64 * POSE_FRAMES_PER_WG), 0, (hipStream_t)stream, b);
-    else hipLaunchKernelGGL(k_board_pose<AGX_LENS_RADTAN>, dim3(grid), dim3(64 * POSE_FRAMES_PER_WG), 0, (hipStream_t)stream, b);
+    BoardPoseArgs d = b;
+    d.camera = pose_camera(lens, b.camera);  // (w2 once per call, by the host form's statements; the caller's camera under the other two)
+    with_lens(lens, [&](auto L) {
+        hipLaunchKernelGGL(k_board_pose<decltype(L)::value>, dim3(grid), dim3(64 * POSE_FRAMES_PER_WG), 0, (hipStream_t)stream, d);
+    });
     return (int)hipGetLastError();
 }
 

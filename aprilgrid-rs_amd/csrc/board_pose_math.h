@@ -539,6 +539,9 @@ AGX_HD bool pose_better(double cost, bool have, double best_cost) { return f64_f
 
 // what both forms refuse in the camera and the pose's own scalars (under AGX_LENS_EQUIDISTANT the ninth double is 0; under
 // AGX_LENS_DOUBLE_SPHERE the seventh, eighth and ninth are exactly 0, -1 < xi <= 1 and 0 <= alpha <= 1)
+#define AGX_LENS_CAMERA_RULE /* the lens and camera half of it, for every entry point's message */                                            \
+    "lens_model AGX_LENS_RADTAN, AGX_LENS_EQUIDISTANT (its ninth double 0) or AGX_LENS_DOUBLE_SPHERE (xi in (-1, 1], alpha in [0, 1], its last " \
+    "three doubles 0), every camera field finite with fx and fy > 0"
 AGX_HD bool pose_args_ok(int lens, const agx_camera &c, double tag_size, uint32_t iterations)
 {
     const bool ds = lens == AGX_LENS_DOUBLE_SPHERE && c.p1 == 0.0 && c.p2 == 0.0 && c.k3 == 0.0 && c.k1 > -1.0 && c.k1 <= 1.0 && c.k2 >= 0.0 && c.k2 <= 1.0;
@@ -547,6 +550,16 @@ AGX_HD bool pose_args_ok(int lens, const agx_camera &c, double tag_size, uint32_
     for (int i = 0; i < 9; ++i)
         if (!f64_finite(v[i])) return false;
     return c.fx > 0.0 && c.fy > 0.0 && f64_finite(tag_size) && tag_size > 0.0 && iterations <= POSE_MAX_ITERATIONS;
+}
+
+// The one place where a lens model that is known at run time picks a template argument: f(std::integral_constant<int, AGX_LENS_*>{}).
+// A value that is neither of the other two is AGX_LENS_RADTAN (the entry points have refused everything else).
+template <class F>
+inline auto with_lens(int lens, F f)
+{
+    if (lens == AGX_LENS_DOUBLE_SPHERE) return f(std::integral_constant<int, AGX_LENS_DOUBLE_SPHERE>{});
+    if (lens == AGX_LENS_EQUIDISTANT) return f(std::integral_constant<int, AGX_LENS_EQUIDISTANT>{});
+    return f(std::integral_constant<int, AGX_LENS_RADTAN>{});
 }
 
 }  // namespace agx

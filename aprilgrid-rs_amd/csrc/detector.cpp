@@ -2268,15 +2268,8 @@ int agx_collect_tags_tail(int family, uint32_t n_quads, const uint32_t *quads, u
 }
 
 // ---- the board's homography from the tag table (board_fit.hip: k_board_fit; host_tail.cpp: board_fit) ---------------------------
-// what both forms refuse in their scalar arguments
-static bool board_fit_args_ok(uint32_t cols, uint32_t rows, float spacing_ratio, int img_w, int img_h, float max_err_sq, uint32_t min_tags,
-                              int flags)
-{
-    if (!cols || !rows || (uint64_t)cols * rows > FIT_MAX_BOARD) return false;
-    if (!std::isfinite(spacing_ratio) || !(spacing_ratio > -1.0f) || img_w <= 0 || img_h <= 0) return false;
-    return max_err_sq >= 0.0f && min_tags != 0 && !(flags & ~AGX_FIT_PREDICT_MISSING);  // (a NaN fails the comparison)
-}
-
+// Every form builds the kernel's record from its C arguments, which come in the record's order, and board_fit_args_bad checks it:
+// the enqueue's with device pointers, the tail's for its one frame, whose n_tags and tag_status are words of the call.
 int agx_board_fit_enqueue(agx_detector *det, int n_frames, const agx_tag *d_tags, uint32_t tags_per_frame, const uint32_t *d_n_tags,
                           const uint32_t *d_tag_status, uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, int img_w,
                           int img_h, float max_err_sq, uint32_t max_drop, uint32_t min_tags, int flags, double *d_h, float *d_err_sq,
@@ -2284,41 +2277,11 @@ int agx_board_fit_enqueue(agx_detector *det, int n_frames, const agx_tag *d_tags
 {
     return agx_guard(det, [&]() -> int {
     if (!det) return AGX_ERR_ARG;
-    if (!d_tags || !d_n_tags || !d_h || !d_err_sq || !d_row_status || !d_n_inliers || !d_rms || !d_pred || !d_n_pred || !d_status || n_frames <= 0 ||
-        !tags_per_frame)
-        return fail(det, AGX_ERR_ARG, "a null array, n_frames <= 0 or tags_per_frame == 0");
-    if (!board_fit_args_ok(cols, rows, spacing_ratio, img_w, img_h, max_err_sq, min_tags, flags))
-        return fail(det, AGX_ERR_ARG, "rows * cols in 1 .. 4096, spacing_ratio finite and > -1, img_w and img_h > 0, max_err_sq >= 0, min_tags >= 1, flags AGX_FIT_PREDICT_MISSING or 0");
-    if ((((uintptr_t)d_tags | (uintptr_t)d_n_tags | (uintptr_t)d_tag_status | (uintptr_t)d_err_sq | (uintptr_t)d_row_status | (uintptr_t)d_n_inliers |
-          (uintptr_t)d_rms | (uintptr_t)d_pred | (uintptr_t)d_n_pred | (uintptr_t)d_status) & 3) || ((uintptr_t)d_h & 7))
-        return fail(det, AGX_ERR_ARG, "d_h must be 8-byte aligned, every other array 4-byte aligned");
-    if ((size_t)n_frames * tags_per_frame >= ((size_t)1 << 27)) return fail(det, AGX_ERR_ARG, "at most 2^27 - 1 tag rows per batch");
+    const BoardFitArgs b{n_frames, d_tags, tags_per_frame, d_n_tags, d_tag_status, cols, rows, first_id, spacing_ratio, img_w, img_h, max_err_sq,
+                         max_drop, min_tags, flags, d_h, d_err_sq, d_row_status, d_n_inliers, d_rms, d_pred, d_n_pred, d_status};
+    if (const char *why = board_fit_args_bad(b, true)) return fail(det, AGX_ERR_ARG, why);
     HIP_TRY(det, hipSetDevice(det->device));
     begin_batch(det);  // and there is nothing of this one to be fetched
-    BoardFitArgs b{};
-    b.n_frames = n_frames;
-    b.tags = d_tags;
-    b.tags_per_frame = tags_per_frame;
-    b.n_tags = d_n_tags;
-    b.tag_status = d_tag_status;
-    b.cols = cols;
-    b.rows = rows;
-    b.first_id = first_id;
-    b.spacing_ratio = spacing_ratio;
-    b.img_w = img_w;
-    b.img_h = img_h;
-    b.max_err_sq = max_err_sq;
-    b.max_drop = max_drop;
-    b.min_tags = min_tags;
-    b.flags = flags;
-    b.h = d_h;
-    b.err_sq = d_err_sq;
-    b.row_status = d_row_status;
-    b.n_inliers = d_n_inliers;
-    b.rms = d_rms;
-    b.pred = d_pred;
-    b.n_pred = d_n_pred;
-    b.status = d_status;
     const hipError_t e = (hipError_t)launch_board_fit(b, det->stream);
     if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_board_fit: ") + hipGetErrorString(e));
     return AGX_OK;
@@ -2331,20 +2294,29 @@ int agx_board_fit_tail(const agx_tag *tags, uint32_t tags_per_frame, uint32_t n_
                        uint32_t *n_pred, uint32_t *status)
 {
     return agx_guard(nullptr, [&]() -> int {
-    if (!h || !n_inliers || !rms || !pred || !n_pred || !status || (n_tags && (!tags || !err_sq || !row_status))) return AGX_ERR_ARG;
-    if (!board_fit_args_ok(cols, rows, spacing_ratio, img_w, img_h, max_err_sq, min_tags, flags)) return AGX_ERR_ARG;
-    if ((((uintptr_t)tags | (uintptr_t)err_sq | (uintptr_t)row_status | (uintptr_t)n_inliers | (uintptr_t)rms | (uintptr_t)pred | (uintptr_t)n_pred |
-          (uintptr_t)status) & 3) || ((uintptr_t)h & 7))
-        return AGX_ERR_ARG;
-    if (tags_per_frame >= (1u << 27)) return AGX_ERR_ARG;
-    *status = board_fit(tags, tags_per_frame, n_tags, tag_status, cols, rows, first_id, spacing_ratio, img_w, img_h, max_err_sq, max_drop, min_tags,
-                        flags, h, err_sq, row_status, n_inliers, rms, pred, n_pred);
+    const BoardFitArgs b{1, tags, tags_per_frame, &n_tags, &tag_status, cols, rows, first_id, spacing_ratio, img_w, img_h, max_err_sq,
+                         max_drop, min_tags, flags, h, err_sq, row_status, n_inliers, rms, pred, n_pred, status};
+    if (board_fit_args_bad(b, false)) return AGX_ERR_ARG;
+    *status = board_fit(b);
     return AGX_OK;
     });
 }
 
 // ---- the board's pose under a lens model (board_pose.hip: k_board_pose; host_tail.cpp: board_pose) ------------------------------
 static_assert(sizeof(agx_camera) == 9 * sizeof(double), "agx_camera is nine doubles: the calls take it as const double *");
+// the record likewise; camera is not null
+static BoardPoseArgs board_pose_record(int n_frames, const agx_tag *tags, uint32_t tags_per_frame, const uint32_t *n_tags, const uint32_t *tag_status,
+                                       uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size, const double *camera,
+                                       float max_err_sq, uint32_t max_drop, uint32_t min_tags, uint32_t iterations, int flags, double *pose,
+                                       float *err_sq, uint32_t *row_status, uint32_t *n_inliers, float *rms, uint32_t *best_iter, agx_tag *pred,
+                                       uint32_t *n_pred, uint32_t *status)
+{
+    agx_camera cam;
+    std::memcpy(&cam, camera, sizeof cam);
+    return BoardPoseArgs{n_frames, tags, tags_per_frame, n_tags, tag_status, cols, rows, first_id, spacing_ratio, tag_size, cam, max_err_sq, max_drop,
+                         min_tags, iterations, flags, pose, err_sq, row_status, n_inliers, rms, best_iter, pred, n_pred, status};
+}
+
 int agx_board_pose_enqueue(agx_detector *det, int n_frames, const agx_tag *d_tags, uint32_t tags_per_frame, const uint32_t *d_n_tags,
                            const uint32_t *d_tag_status, uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
                            const double *camera, float max_err_sq, uint32_t max_drop, uint32_t min_tags, uint32_t iterations, int flags,
@@ -2364,47 +2336,13 @@ int agx_board_pose_enqueue_m(agx_detector *det, int n_frames, const agx_tag *d_t
 {
     return agx_guard(det, [&]() -> int {
     if (!det) return AGX_ERR_ARG;
-    if (!d_tags || !d_n_tags || !d_pose || !d_err_sq || !d_row_status || !d_n_inliers || !d_rms || !d_best_iter || !d_pred || !d_n_pred || !d_status ||
-        !camera || n_frames <= 0 || !tags_per_frame)
-        return fail(det, AGX_ERR_ARG, "a null array or camera, n_frames <= 0 or tags_per_frame == 0");
-    if (!board_fit_args_ok(cols, rows, spacing_ratio, 1, 1, max_err_sq, min_tags, flags))
-        return fail(det, AGX_ERR_ARG, "rows * cols in 1 .. 4096, spacing_ratio finite and > -1, max_err_sq >= 0, min_tags >= 1, flags AGX_FIT_PREDICT_MISSING or 0");
-    agx_camera cam;
-    std::memcpy(&cam, camera, sizeof cam);
-    if (!pose_args_ok(lens_model, cam, tag_size, iterations))
-        return fail(det, AGX_ERR_ARG, "lens_model AGX_LENS_RADTAN, AGX_LENS_EQUIDISTANT (its ninth double 0) or AGX_LENS_DOUBLE_SPHERE (xi in (-1, 1], alpha in [0, 1], its last three doubles 0), every camera field finite with fx and fy > 0, tag_size finite and > 0, iterations <= 64");
-    if ((((uintptr_t)d_tags | (uintptr_t)d_n_tags | (uintptr_t)d_tag_status | (uintptr_t)d_err_sq | (uintptr_t)d_row_status | (uintptr_t)d_n_inliers |
-          (uintptr_t)d_rms | (uintptr_t)d_best_iter | (uintptr_t)d_pred | (uintptr_t)d_n_pred | (uintptr_t)d_status) & 3) || ((uintptr_t)d_pose & 7))
-        return fail(det, AGX_ERR_ARG, "d_pose must be 8-byte aligned, every other array 4-byte aligned");
-    if ((size_t)n_frames * tags_per_frame >= ((size_t)1 << 27)) return fail(det, AGX_ERR_ARG, "at most 2^27 - 1 tag rows per batch");
+    if (!camera) return fail(det, AGX_ERR_ARG, "a null camera");
+    const BoardPoseArgs b = board_pose_record(n_frames, d_tags, tags_per_frame, d_n_tags, d_tag_status, cols, rows, first_id, spacing_ratio, tag_size,
+                                              camera, max_err_sq, max_drop, min_tags, iterations, flags, d_pose, d_err_sq, d_row_status, d_n_inliers,
+                                              d_rms, d_best_iter, d_pred, d_n_pred, d_status);
+    if (const char *why = board_pose_args_bad(b, lens_model, true)) return fail(det, AGX_ERR_ARG, why);
     HIP_TRY(det, hipSetDevice(det->device));
     begin_batch(det);  // and there is nothing of this one to be fetched
-    BoardPoseArgs b{};
-    b.n_frames = n_frames;
-    b.tags = d_tags;
-    b.tags_per_frame = tags_per_frame;
-    b.n_tags = d_n_tags;
-    b.tag_status = d_tag_status;
-    b.cols = cols;
-    b.rows = rows;
-    b.first_id = first_id;
-    b.spacing_ratio = spacing_ratio;
-    b.tag_size = tag_size;
-    b.camera = cam;
-    b.max_err_sq = max_err_sq;
-    b.max_drop = max_drop;
-    b.min_tags = min_tags;
-    b.iterations = iterations;
-    b.flags = flags;
-    b.pose = d_pose;
-    b.err_sq = d_err_sq;
-    b.row_status = d_row_status;
-    b.n_inliers = d_n_inliers;
-    b.rms = d_rms;
-    b.best_iter = d_best_iter;
-    b.pred = d_pred;
-    b.n_pred = d_n_pred;
-    b.status = d_status;
     const hipError_t e = (hipError_t)launch_board_pose(b, lens_model, det->stream);
     if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_board_pose: ") + hipGetErrorString(e));
     return AGX_OK;
@@ -2427,17 +2365,12 @@ int agx_board_pose_tail_m(const agx_tag *tags, uint32_t tags_per_frame, uint32_t
                           uint32_t *n_inliers, float *rms, uint32_t *best_iter, agx_tag *pred, uint32_t *n_pred, uint32_t *status)
 {
     return agx_guard(nullptr, [&]() -> int {
-    if (!pose || !n_inliers || !rms || !best_iter || !pred || !n_pred || !status || !camera || (n_tags && (!tags || !err_sq || !row_status)))
-        return AGX_ERR_ARG;
-    agx_camera cam;
-    std::memcpy(&cam, camera, sizeof cam);
-    if (!board_fit_args_ok(cols, rows, spacing_ratio, 1, 1, max_err_sq, min_tags, flags) || !pose_args_ok(lens_model, cam, tag_size, iterations)) return AGX_ERR_ARG;
-    if ((((uintptr_t)tags | (uintptr_t)err_sq | (uintptr_t)row_status | (uintptr_t)n_inliers | (uintptr_t)rms | (uintptr_t)best_iter | (uintptr_t)pred |
-          (uintptr_t)n_pred | (uintptr_t)status) & 3) || ((uintptr_t)pose & 7))
-        return AGX_ERR_ARG;
-    if (tags_per_frame >= (1u << 27)) return AGX_ERR_ARG;
-    *status = board_pose(lens_model, tags, tags_per_frame, n_tags, tag_status, cols, rows, first_id, spacing_ratio, tag_size, cam, max_err_sq, max_drop,
-                         min_tags, iterations, flags, pose, err_sq, row_status, n_inliers, rms, best_iter, pred, n_pred, nullptr);
+    if (!camera) return AGX_ERR_ARG;
+    const BoardPoseArgs b = board_pose_record(1, tags, tags_per_frame, &n_tags, &tag_status, cols, rows, first_id, spacing_ratio, tag_size, camera,
+                                              max_err_sq, max_drop, min_tags, iterations, flags, pose, err_sq, row_status, n_inliers, rms, best_iter,
+                                              pred, n_pred, status);
+    if (board_pose_args_bad(b, lens_model, false)) return AGX_ERR_ARG;
+    *status = board_pose(b, lens_model, nullptr);
     return AGX_OK;
     });
 }
@@ -2455,20 +2388,22 @@ int agx_debug_board_pose_sums_m(const agx_tag *tags, uint32_t tags_per_frame, ui
                                 uint32_t max_drop, uint32_t min_tags, uint32_t iterations, int flags, uint32_t *status, double *iter_sums)
 {
     return agx_guard(nullptr, [&]() -> int {
-    if (!status || !iter_sums || !camera || (n_tags && !tags)) return AGX_ERR_ARG;
-    agx_camera cam;
-    std::memcpy(&cam, camera, sizeof cam);
-    if (!board_fit_args_ok(cols, rows, spacing_ratio, 1, 1, max_err_sq, min_tags, flags) || !pose_args_ok(lens_model, cam, tag_size, iterations)) return AGX_ERR_ARG;
-    if ((((uintptr_t)tags | (uintptr_t)status) & 3) || ((uintptr_t)iter_sums & 7) || tags_per_frame >= (1u << 27)) return AGX_ERR_ARG;
+    if (!iter_sums || ((uintptr_t)iter_sums & 7) || !camera) return AGX_ERR_ARG;
     double pose[12];
+    uint32_t n_inliers = 0, n_pred = 0, best_iter = 0, word = 0;
+    float rms = 0.0f;
+    agx_tag none;
+    // the tail's outputs are this call's own; its three arrays stand on one element each until the record has passed and gives their sizes
+    BoardPoseArgs b = board_pose_record(1, tags, tags_per_frame, &n_tags, &tag_status, cols, rows, first_id, spacing_ratio, tag_size, camera, max_err_sq,
+                                        max_drop, min_tags, iterations, flags, pose, &rms, &word, &n_inliers, &rms, &best_iter, &none, &n_pred, status);
+    if (board_pose_args_bad(b, lens_model, false)) return AGX_ERR_ARG;
     std::vector<float> err_sq(n_tags + 1);
     std::vector<uint32_t> row_status(n_tags + 1);
     std::vector<agx_tag> pred((size_t)cols * rows);
-    uint32_t n_inliers = 0, n_pred = 0, best_iter = 0;
-    float rms = 0.0f;
-    *status = board_pose(lens_model, tags, tags_per_frame, n_tags, tag_status, cols, rows, first_id, spacing_ratio, tag_size, cam, max_err_sq, max_drop,
-                         min_tags, iterations, flags, pose, err_sq.data(), row_status.data(), &n_inliers, &rms, &best_iter, pred.data(), &n_pred,
-                         iter_sums);
+    b.err_sq = err_sq.data();
+    b.row_status = row_status.data();
+    b.pred = pred.data();
+    *status = board_pose(b, lens_model, iter_sums);
     return AGX_OK;
     });
 }
@@ -2498,7 +2433,7 @@ int agx_debug_pose_project(int lens_model, const double *camera, const double *x
 
 // ---- rectified batches (rectify.hip: k_rectify_map, k_remap, k_rectified_points and the host forms) -------------------------------
 static const char *kRectifyGeomRule =
-    "lens_model AGX_LENS_RADTAN, AGX_LENS_EQUIDISTANT (its ninth double 0) or AGX_LENS_DOUBLE_SPHERE (xi in (-1, 1], alpha in [0, 1], its last three doubles 0), every camera field finite with fx and fy > 0, new_camera "
+    AGX_LENS_CAMERA_RULE ", new_camera "
     "finite with fx' and fy' > 0, rotation NULL or finite";
 
 static bool rectify_map_args(int lens_model, const double *camera, const double *new_camera, const double *rotation, int src_width,

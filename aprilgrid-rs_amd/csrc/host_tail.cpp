@@ -7,6 +7,7 @@
 #include "decode_math.h"  // round_half_away, f32_as_u32, tag_affine: the decode kernels' own definitions
 #include "board_fit_math.h"  // the board fit's arithmetic and order of summation: k_board_fit's own definitions
 #include "board_pose_math.h"  // the board pose's: k_board_pose's own definitions
+#include "board_rounds.h"  // the outlier rounds of both and their two models
 
 #ifdef AGX_TAIL_PROFILE
 #include <chrono>
@@ -1679,242 +1680,23 @@ uint32_t snap_points(const void *slots, size_t stride, uint32_t n_slots, const u
     return AGX_SNAP_OK;
 }
 
-uint32_t board_fit(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint32_t tag_status, uint32_t cols, uint32_t rows, uint32_t first_id,
-                   float spacing_ratio, int img_w, int img_h, float max_err_sq, uint32_t max_drop, uint32_t min_tags, int flags, double *h_out,
-                   float *err_sq, uint32_t *row_status, uint32_t *n_inliers, float *rms, agx_tag *pred, uint32_t *n_pred)
+// the two fitters over one frame's tag table: the rounds and the models are board_rounds.h's
+uint32_t board_fit(const BoardFitArgs &b)
 {
-    const FitGeom g = fit_geom(cols, rows, first_id, spacing_ratio, img_w, img_h);
-    const auto refuse = [&](uint32_t status) {
-        *n_inliers = 0;
-        *n_pred = 0;
-        return status;
-    };
-    if (n_tags > tag_cap || n_tags > FIT_MAX_ROWS || tag_status != AGX_TAGS_OK) return refuse(AGX_FIT_INPUT);
-    std::vector<uint8_t> st(n_tags);
-    uint32_t n_inl = 0;
-    for (uint32_t r = 0; r < n_tags; ++r) {
-        st[r] = AGX_FIT_ROW_OFF_BOARD;
-        if (!fit_on_board(g, tags[r].id)) continue;
-        for (int j = 0; j < 8; ++j)
-            if (!f32_finite(tags[r].xy[j])) return refuse(AGX_FIT_INPUT);
-        st[r] = AGX_FIT_ROW_INLIER;
-        ++n_inl;
-    }
-    // the kernel's 64 lanes one after the other: lane l takes the rows l, l + 64, ...; the fold is p[l] + p[l ^ m] over m = 32 .. 1,
-    // of which lane 0's value needs p[l] += p[l + m] for l < m only
-    const auto fold = [](double (*p)[FIT_SUMS], int n) {
-        for (int m = 32; m >= 1; m >>= 1)
-            for (int l = 0; l < m; ++l)
-                for (int k = 0; k < n; ++k) p[l][k] = p[l][k] + p[l + m][k];
-    };
-    uint32_t status = AGX_FIT_OK, drops = 0;
-    double h[8] = {0}, sum_sq = 0.0;
-    std::unique_ptr<double[][FIT_SUMS]> lanes(new double[64][FIT_SUMS]);
-    for (;;) {
-        if (n_inl < min_tags) return refuse(AGX_FIT_FEW);
-        for (int l = 0; l < 64; ++l) {
-            for (int k = 0; k < FIT_SUMS; ++k) lanes[l][k] = 0.0;
-            for (uint32_t r = (uint32_t)l; r < n_tags; r += 64u)
-                if (st[r] == AGX_FIT_ROW_INLIER) fit_accumulate_row(g, lanes[l], tags[r].id, tags[r].xy);
-        }
-        fold(lanes.get(), FIT_SUMS);
-        double m[72];
-        fit_system(lanes[0], m);
-        if (!fit_solve(m, h)) return refuse(AGX_FIT_SINGULAR);
-        float worst = 0.0f;
-        uint32_t worst_row = 0xffffffffu;
-        for (int l = 0; l < 64; ++l) {
-            lanes[l][0] = 0.0;
-            for (uint32_t r = (uint32_t)l; r < n_tags; r += 64u) {
-                if (st[r] != AGX_FIT_ROW_INLIER) continue;
-                double sum;
-                const float e = fit_row_residual(g, h, tags[r].id, tags[r].xy, &sum);
-                lanes[l][0] += sum;
-                if (worst_row == 0xffffffffu || e > worst || (e == worst && r < worst_row)) {  // the lowest row at equal residual
-                    worst = e;
-                    worst_row = r;
-                }
-            }
-        }
-        if (worst > max_err_sq) {
-            if (drops < max_drop) {
-                st[worst_row] = AGX_FIT_ROW_OUTLIER;
-                ++drops;
-                --n_inl;
-                continue;
-            }
-            status = AGX_FIT_LOOSE;
-        }
-        fold(lanes.get(), 1);
-        sum_sq = lanes[0][0];
-        break;
-    }
-    for (uint32_t r = 0; r < n_tags; ++r) {
-        row_status[r] = st[r];
-        double sum;
-        if (st[r] != AGX_FIT_ROW_OFF_BOARD) err_sq[r] = fit_row_residual(g, h, tags[r].id, tags[r].xy, &sum);
-    }
-    fit_h_matrix(g, h, h_out);
-    *n_inliers = n_inl;
-    *rms = fit_rms(sum_sq, n_inl);
-    std::vector<bool> member(g.n_board, false);
-    if (flags & AGX_FIT_PREDICT_MISSING)
-        for (uint32_t r = 0; r < n_tags; ++r)
-            if (st[r] == AGX_FIT_ROW_INLIER) member[tags[r].id - first_id] = true;
-    uint32_t kept = 0;
-    for (uint32_t t = 0; t < g.n_board; ++t) {
-        if (member[t]) continue;
-        pred[kept].id = first_id + t;
-        fit_predict(g, h, t, pred[kept].xy);
-        ++kept;
-    }
-    *n_pred = kept;
-    return status;
+    const FitGeom g = fit_geom(b.cols, b.rows, b.first_id, b.spacing_ratio, b.img_w, b.img_h);
+    FitModel m{g};
+    return board_rounds_host(b, g, m);
 }
 
-// (one text for every lens model, as the kernel's; cam is pose_camera()'s)
-template <int LENS>
-static uint32_t board_pose_lens(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint32_t tag_status, uint32_t cols, uint32_t rows,
-                                uint32_t first_id, float spacing_ratio, double tag_size, const agx_camera &cam, float max_err_sq, uint32_t max_drop,
-                                uint32_t min_tags, uint32_t iterations, int flags, double *pose_out, float *err_sq, uint32_t *row_status,
-                                uint32_t *n_inliers, float *rms, uint32_t *best_iter, agx_tag *pred, uint32_t *n_pred, double *iter_sums)
+uint32_t board_pose(const BoardPoseArgs &b, int lens, double *iter_sums)
 {
-    const FitGeom g = pose_geom(cols, rows, first_id, spacing_ratio);
-    const auto refuse = [&](uint32_t status) {
-        *n_inliers = 0;
-        *n_pred = 0;
-        return status;
-    };
-    if (n_tags > tag_cap || n_tags > FIT_MAX_ROWS || tag_status != AGX_TAGS_OK) return refuse(AGX_FIT_INPUT);
-    std::vector<uint8_t> st(n_tags);
-    uint32_t n_inl = 0;
-    for (uint32_t r = 0; r < n_tags; ++r) {
-        st[r] = AGX_FIT_ROW_OFF_BOARD;
-        if (!fit_on_board(g, tags[r].id)) continue;
-        for (int j = 0; j < 8; ++j)
-            if (!f32_finite(tags[r].xy[j])) return refuse(AGX_FIT_INPUT);
-        st[r] = AGX_FIT_ROW_INLIER;
-        ++n_inl;
-    }
-    // the kernel's 64 lanes one after the other, as in board_fit
-    const auto fold = [](double (*p)[FIT_SUMS], int n) {
-        for (int m = 32; m >= 1; m >>= 1)
-            for (int l = 0; l < m; ++l)
-                for (int k = 0; k < n; ++k) p[l][k] = p[l][k] + p[l + m][k];
-    };
-    static_assert(POSE_SUMS <= FIT_SUMS, "board_pose: the lanes' sums share board_fit's rows");
-    std::unique_ptr<double[][FIT_SUMS]> lanes(new double[64][FIT_SUMS]);
-    if (n_inl < min_tags) return refuse(AGX_FIT_FEW);
-    Pose pose;
-    {  // the seed
-        for (int l = 0; l < 64; ++l) {
-            for (int k = 0; k < FIT_SUMS; ++k) lanes[l][k] = 0.0;
-            for (uint32_t r = (uint32_t)l; r < n_tags; r += 64u)
-                if (st[r] == AGX_FIT_ROW_INLIER) pose_seed_accumulate_row<LENS>(g, cam, lanes[l], tags[r].id, tags[r].xy);
-        }
-        fold(lanes.get(), FIT_SUMS);
-        double m[72], h[8];
-        fit_system(lanes[0], m);
-        if (!fit_solve(m, h) || !pose_from_homography(g, tag_size, h, pose)) return refuse(AGX_FIT_SINGULAR);
-    }
-    uint32_t status = AGX_FIT_OK, drops = 0, best_it = 0;
-    double sum_sq = 0.0;
-    for (;;) {  // a round
-        if (n_inl < min_tags) return refuse(AGX_FIT_FEW);
-        Pose cur = pose;
-        double best_cost = 0.0;
-        bool have = false;
-        best_it = 0;
-        if (iter_sums)
-            for (uint32_t i = 0; i <= iterations; ++i) iter_sums[i] = std::numeric_limits<double>::quiet_NaN();
-        for (uint32_t it = 0;; ++it) {
-            for (int l = 0; l < 64; ++l) {
-                for (int k = 0; k < POSE_SUMS; ++k) lanes[l][k] = 0.0;
-                for (uint32_t r = (uint32_t)l; r < n_tags; r += 64u)
-                    if (st[r] == AGX_FIT_ROW_INLIER) pose_accumulate_row<LENS>(g, tag_size, cam, cur, lanes[l], tags[r].id, tags[r].xy);
-            }
-            fold(lanes.get(), POSE_SUMS);
-            const double cost = lanes[0][27];
-            if (iter_sums) iter_sums[it] = cost;
-            if (pose_better(cost, have, best_cost)) {
-                pose = cur;
-                best_cost = cost;
-                best_it = it;
-                have = true;
-            }
-            if (it == iterations) break;
-            double m[42], d[6];
-            pose_system(lanes[0], m);
-            if (!fit_solve_n<6>(m, d)) {
-                if (it == 0) return refuse(AGX_FIT_SINGULAR);
-                break;
-            }
-            pose_update(cur, d);
-        }
-        if (!pose_gram_schmidt(pose.R)) return refuse(AGX_FIT_SINGULAR);
-        float worst = 0.0f;
-        uint32_t worst_row = 0xffffffffu;
-        for (int l = 0; l < 64; ++l) {
-            lanes[l][0] = 0.0;
-            for (uint32_t r = (uint32_t)l; r < n_tags; r += 64u) {
-                if (st[r] != AGX_FIT_ROW_INLIER) continue;
-                double sum;
-                const float e = pose_row_residual<LENS>(g, tag_size, cam, pose, tags[r].id, tags[r].xy, &sum);
-                lanes[l][0] += sum;
-                if (worst_row == 0xffffffffu || e > worst || (e == worst && r < worst_row)) {  // the lowest row at equal residual
-                    worst = e;
-                    worst_row = r;
-                }
-            }
-        }
-        if (worst > max_err_sq) {
-            if (drops < max_drop) {
-                st[worst_row] = AGX_FIT_ROW_OUTLIER;
-                ++drops;
-                --n_inl;
-                continue;
-            }
-            status = AGX_FIT_LOOSE;
-        }
-        fold(lanes.get(), 1);
-        sum_sq = lanes[0][0];
-        break;
-    }
-    for (uint32_t r = 0; r < n_tags; ++r) {
-        row_status[r] = st[r];
-        double sum;
-        if (st[r] != AGX_FIT_ROW_OFF_BOARD) err_sq[r] = pose_row_residual<LENS>(g, tag_size, cam, pose, tags[r].id, tags[r].xy, &sum);
-    }
-    for (int i = 0; i < 9; ++i) pose_out[i] = pose.R[i];
-    for (int i = 0; i < 3; ++i) pose_out[9 + i] = pose.t[i];
-    *n_inliers = n_inl;
-    *rms = fit_rms(sum_sq, n_inl);
-    *best_iter = best_it;
-    std::vector<bool> member(g.n_board, false);
-    if (flags & AGX_FIT_PREDICT_MISSING)
-        for (uint32_t r = 0; r < n_tags; ++r)
-            if (st[r] == AGX_FIT_ROW_INLIER) member[tags[r].id - first_id] = true;
-    uint32_t kept = 0;
-    for (uint32_t t = 0; t < g.n_board; ++t) {
-        if (member[t]) continue;
-        pred[kept].id = first_id + t;
-        pose_predict<LENS>(g, tag_size, cam, pose, t, pred[kept].xy);
-        ++kept;
-    }
-    *n_pred = kept;
-    return status;
-}
-
-uint32_t board_pose(int lens, const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint32_t tag_status, uint32_t cols, uint32_t rows,
-                    uint32_t first_id, float spacing_ratio, double tag_size, const agx_camera &cam, float max_err_sq, uint32_t max_drop,
-                    uint32_t min_tags, uint32_t iterations, int flags, double *pose_out, float *err_sq, uint32_t *row_status, uint32_t *n_inliers,
-                    float *rms, uint32_t *best_iter, agx_tag *pred, uint32_t *n_pred, double *iter_sums)
-{
-    const auto run = lens == AGX_LENS_DOUBLE_SPHERE ? board_pose_lens<AGX_LENS_DOUBLE_SPHERE>
-                     : lens == AGX_LENS_EQUIDISTANT ? board_pose_lens<AGX_LENS_EQUIDISTANT>
-                                                    : board_pose_lens<AGX_LENS_RADTAN>;
-    return run(tags, tag_cap, n_tags, tag_status, cols, rows, first_id, spacing_ratio, tag_size, pose_camera(lens, cam), max_err_sq, max_drop, min_tags, iterations,
-               flags, pose_out, err_sq, row_status, n_inliers, rms, best_iter, pred, n_pred, iter_sums);
+    BoardPoseArgs d = b;
+    d.camera = pose_camera(lens, b.camera);
+    const FitGeom g = pose_geom(b.cols, b.rows, b.first_id, b.spacing_ratio);
+    return with_lens(lens, [&](auto L) {
+        PoseModel<decltype(L)::value> m{d, g, iter_sums};
+        return board_rounds_host(d, g, m);
+    });
 }
 
 void pose_atan_host(const double *r, uint32_t n, double *out)
@@ -1925,21 +1707,15 @@ void pose_atan_host(const double *r, uint32_t n, double *out)
 void pose_project_host(int lens, const agx_camera &camera, const double *xyz, uint32_t n, double *uv)
 {
     const agx_camera cam = pose_camera(lens, camera);
-    for (uint32_t i = 0; i < n; ++i) {
-        const Pose p = {{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, {0.0, 0.0, xyz[3 * i + 2]}};
-        bool ok;
-        if (lens == AGX_LENS_DOUBLE_SPHERE) {
-            PosePointDs q;
-            if ((ok = pose_project<AGX_LENS_DOUBLE_SPHERE>(cam, p, xyz[3 * i], xyz[3 * i + 1], q))) uv[2 * i] = q.u, uv[2 * i + 1] = q.v;
-        } else if (lens == AGX_LENS_EQUIDISTANT) {
-            PosePointEqui q;
-            if ((ok = pose_project<AGX_LENS_EQUIDISTANT>(cam, p, xyz[3 * i], xyz[3 * i + 1], q))) uv[2 * i] = q.u, uv[2 * i + 1] = q.v;
-        } else {
-            PosePoint q;
-            if ((ok = pose_project<AGX_LENS_RADTAN>(cam, p, xyz[3 * i], xyz[3 * i + 1], q))) uv[2 * i] = q.u, uv[2 * i + 1] = q.v;
+    with_lens(lens, [&](auto L) {
+        constexpr int LENS = decltype(L)::value;
+        for (uint32_t i = 0; i < n; ++i) {
+            const Pose p = {{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, {0.0, 0.0, xyz[3 * i + 2]}};
+            PosePointOf<LENS> q;
+            if (pose_project<LENS>(cam, p, xyz[3 * i], xyz[3 * i + 1], q)) uv[2 * i] = q.u, uv[2 * i + 1] = q.v;
+            else uv[2 * i] = uv[2 * i + 1] = std::numeric_limits<double>::quiet_NaN();
         }
-        if (!ok) uv[2 * i] = uv[2 * i + 1] = std::numeric_limits<double>::quiet_NaN();
-    }
+    });
 }
 
 }  // namespace agx

@@ -8,6 +8,8 @@
 #include <vector>
 
 #include "../../include/aprilgrid_amd.h"
+#include "board_fit.h"
+#include "board_pose.h"
 
 namespace agx {
 
@@ -143,22 +145,16 @@ uint32_t snap_points(const void *slots, size_t stride, uint32_t n_slots, const u
                      float *dist_sq, uint32_t *rows, uint32_t *n_rows_out, uint32_t *row_index);
 
 // The board-to-image homography through one frame's tag table, its outlier rounds and the predicted corners of the layout's tags
-// (agx_board_fit_tail; k_board_fit is the device form, board_fit_math.h the arithmetic and the order of summation of both).
-// tags [n_tags] of a table of tag_cap rows whose status word is tag_status.  -> AGX_FIT_*; for AGX_FIT_FEW, _SINGULAR and _INPUT
-// only *n_inliers = *n_pred = 0 is written.  h [9], err_sq / row_status [n_tags], pred [rows * cols].
-uint32_t board_fit(const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint32_t tag_status, uint32_t cols, uint32_t rows, uint32_t first_id,
-                   float spacing_ratio, int img_w, int img_h, float max_err_sq, uint32_t max_drop, uint32_t min_tags, int flags, double *h,
-                   float *err_sq, uint32_t *row_status, uint32_t *n_inliers, float *rms, agx_tag *pred, uint32_t *n_pred);
+// (agx_board_fit_tail; k_board_fit is the device form, board_fit_math.h the arithmetic and the order of summation of both,
+// board_rounds.h the rounds).  b is the kernel's record with host pointers, of which frame 0 is read and written (n_frames is 1;
+// a null tag_status is AGX_TAGS_OK).  -> AGX_FIT_*, which is not stored; for AGX_FIT_FEW, _SINGULAR and _INPUT only
+// n_inliers[0] = n_pred[0] = 0 is written.
+uint32_t board_fit(const BoardFitArgs &b);
 
-// The board's pose under the lens model `lens` (AGX_LENS_*, checked by the caller) through one frame's tag table, its outlier rounds and the
-// predicted corners of the layout's tags (agx_board_pose_tail; k_board_pose is the device form, board_pose_math.h the arithmetic
-// and the order of summation of both).  Arguments and the refusal rule as board_fit's; pose [12] (R row major, then t),
-// *best_iter the chosen iterate of the last round; iter_sums [iterations + 1] or null: the sum of |e|^2 of every iterate of the
-// last round, NaN for an iterate that was not reached (agx_debug_board_pose_sums).
-uint32_t board_pose(int lens, const agx_tag *tags, uint32_t tag_cap, uint32_t n_tags, uint32_t tag_status, uint32_t cols, uint32_t rows,
-                    uint32_t first_id, float spacing_ratio, double tag_size, const agx_camera &cam, float max_err_sq, uint32_t max_drop,
-                    uint32_t min_tags, uint32_t iterations, int flags, double *pose, float *err_sq, uint32_t *row_status, uint32_t *n_inliers,
-                    float *rms, uint32_t *best_iter, agx_tag *pred, uint32_t *n_pred, double *iter_sums);
+// The board's pose under the lens model `lens` (AGX_LENS_*, checked by the caller) likewise (agx_board_pose_tail; k_board_pose is
+// the device form, board_pose_math.h the arithmetic).  b.camera is the caller's.  iter_sums [iterations + 1] or null: the sum of
+// |e|^2 of every iterate of the last round, NaN for an iterate that was not reached (agx_debug_board_pose_sums).
+uint32_t board_pose(const BoardPoseArgs &b, int lens, double *iter_sums);
 // board_pose_math.h's pose_atan of r [n] as this compiler gives it (agx_debug_pose_atan), and its pose_project of n camera-frame
 // points xyz [n][3] under the identity pose moved to each point's Z (agx_debug_pose_project): uv [n][2], NaN where Z is not > 0.
 void pose_atan_host(const double *r, uint32_t n, double *out);

@@ -149,12 +149,7 @@ int launch_rectify_map(const RectifyMapArgs &a, void *stream)
 {
     if (rectify_map_args_bad(a)) return (int)hipErrorInvalidValue;
     const unsigned grid = (unsigned)(((size_t)a.dst_w * a.dst_h + RECT_BLOCK - 1) / RECT_BLOCK);
-    if (a.lens == AGX_LENS_DOUBLE_SPHERE)
-        hipLaunchKernelGGL(k_rectify_map<AGX_LENS_DOUBLE_SPHERE>, dim3(grid), dim3(RECT_BLOCK), 0, (hipStream_t)stream, a);
-    else if (a.lens == AGX_LENS_EQUIDISTANT)
-        hipLaunchKernelGGL(k_rectify_map<AGX_LENS_EQUIDISTANT>, dim3(grid), dim3(RECT_BLOCK), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(k_rectify_map<AGX_LENS_RADTAN>, dim3(grid), dim3(RECT_BLOCK), 0, (hipStream_t)stream, a);
+    with_lens(a.lens, [&](auto L) { hipLaunchKernelGGL(k_rectify_map<decltype(L)::value>, dim3(grid), dim3(RECT_BLOCK), 0, (hipStream_t)stream, a); });
     return (int)hipGetLastError();
 }
 
@@ -163,12 +158,7 @@ int launch_rectified_points(const RectifiedPointsArgs &a, void *stream)
     if (rectified_points_args_bad(a)) return (int)hipErrorInvalidValue;
     if (!a.n) return (int)hipSuccess;
     const unsigned grid = (a.n + RECT_BLOCK - 1) / RECT_BLOCK;
-    if (a.lens == AGX_LENS_DOUBLE_SPHERE)
-        hipLaunchKernelGGL(k_rectified_points<AGX_LENS_DOUBLE_SPHERE>, dim3(grid), dim3(RECT_BLOCK), 0, (hipStream_t)stream, a);
-    else if (a.lens == AGX_LENS_EQUIDISTANT)
-        hipLaunchKernelGGL(k_rectified_points<AGX_LENS_EQUIDISTANT>, dim3(grid), dim3(RECT_BLOCK), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(k_rectified_points<AGX_LENS_RADTAN>, dim3(grid), dim3(RECT_BLOCK), 0, (hipStream_t)stream, a);
+    with_lens(a.lens, [&](auto L) { hipLaunchKernelGGL(k_rectified_points<decltype(L)::value>, dim3(grid), dim3(RECT_BLOCK), 0, (hipStream_t)stream, a); });
     return (int)hipGetLastError();
 }
 
@@ -236,16 +226,12 @@ void remap_host_t(const RemapArgs &a)
 
 void rectify_map_host(const RectifyMapArgs &a)
 {
-    if (a.lens == AGX_LENS_DOUBLE_SPHERE) rectify_map_host_t<AGX_LENS_DOUBLE_SPHERE>(a);
-    else if (a.lens == AGX_LENS_EQUIDISTANT) rectify_map_host_t<AGX_LENS_EQUIDISTANT>(a);
-    else rectify_map_host_t<AGX_LENS_RADTAN>(a);
+    with_lens(a.lens, [&](auto L) { rectify_map_host_t<decltype(L)::value>(a); });
 }
 
 void rectified_points_host(const RectifiedPointsArgs &a)
 {
-    if (a.lens == AGX_LENS_DOUBLE_SPHERE) rectified_points_host_t<AGX_LENS_DOUBLE_SPHERE>(a);
-    else if (a.lens == AGX_LENS_EQUIDISTANT) rectified_points_host_t<AGX_LENS_EQUIDISTANT>(a);
-    else rectified_points_host_t<AGX_LENS_RADTAN>(a);
+    with_lens(a.lens, [&](auto L) { rectified_points_host_t<decltype(L)::value>(a); });
 }
 
 void remap_host(const RemapArgs &a)
