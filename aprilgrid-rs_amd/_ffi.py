@@ -44,6 +44,9 @@ AGX_FIT_ROW_INLIER, AGX_FIT_ROW_OUTLIER, AGX_FIT_ROW_OFF_BOARD = 0, 1, 2
 # the lens model of agx_board_pose_enqueue_m / _tail_m: pinhole + radial-tangential, pinhole-equidistant (fisheye), double sphere
 AGX_LENS_RADTAN, AGX_LENS_EQUIDISTANT, AGX_LENS_DOUBLE_SPHERE = 0, 1, 2
 AGX_MAP_NONE = -2 ** 31  # both words of a rectification map's entry without a source pixel (agx_rectify_map_enqueue / _tail)
+# agx_render_boards_enqueue / _tail: what became of a frame; the flag under which the destination's pixels are the background
+AGX_RENDER_OK, AGX_RENDER_EMPTY, AGX_RENDER_INPUT = 0, 1, 2
+AGX_RENDER_KEEP_BACKGROUND = 1
 AGX_DBG_BLUR, AGX_DBG_RESP, AGX_DBG_MIN, AGX_DBG_CENTERS, AGX_DBG_REFINED = 0, 1, 2, 3, 4
 AGX_N_KERNELS = 5
 
@@ -67,6 +70,11 @@ POINT_DTYPE = [("x", "f4"), ("y", "f4")]  # numpy dtype of agx_point
 
 class TagC(C.Structure):
     _fields_ = [("id", C.c_uint32), ("xy", C.c_float * 8)]
+
+
+class RenderParams(C.Structure):  # agx_render_params: six 32-bit fields, handed over as const void *
+    _fields_ = [("black", C.c_uint32), ("white", C.c_uint32), ("background", C.c_uint32), ("page_margin", C.c_float),
+                ("supersample", C.c_uint32), ("flags", C.c_uint32)]
 
 
 # every symbol include/aprilgrid_amd.h declares: name -> (restype, argtypes)
@@ -197,6 +205,10 @@ SYMBOLS = {
                                  C.c_size_t, C.c_uint32]),
     "agx_rectified_points_enqueue": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, C.c_size_t]),
     "agx_rectified_points_tail": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, C.c_size_t]),
+    "agx_render_boards_enqueue": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_uint32, C.c_uint32,
+                                            C.c_uint32, C.c_float, C.c_double, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "agx_render_boards_tail": (C.c_int, [C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
+                                         C.c_double, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "agx_group_create": (C.c_int, [C.c_int, C.POINTER(Params), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "agx_group_destroy": (None, [_P]),
     "agx_group_size": (C.c_int, [_P]),

@@ -25,6 +25,7 @@
 #include "detector_internal.h"
 #include "host_tail.hpp"
 #include "rectify.h"
+#include "render.h"
 #include "tail_kernels.h"
 
 using namespace agx;
@@ -2574,6 +2575,75 @@ int agx_rectified_points_tail(int lens_model, const double *camera, const double
     if (!rectified_points_args(lens_model, camera, new_camera, rotation, points, point_stride_bytes, n_points, out, out_stride_bytes, a, &why))
         return AGX_ERR_ARG;
     rectified_points_host(a);
+    return AGX_OK;
+    });
+}
+
+// ---- the board through pose and lens model (render.hip: k_render_boards and the host form) -----------------------------------------
+static_assert(sizeof(agx_render_params) == 24, "agx_render_params is six 32-bit fields: the calls take it as const void *");
+// the kernel's record from the C arguments; AGX_OK, or the status with *why the text of an AGX_ERR_ARG
+static int render_record(int n_frames, int width, int height, size_t row_stride_bytes, size_t frame_stride_bytes, int format, int family,
+                         uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size, int lens_model, const double *camera,
+                         const double *poses, const void *params, void *frames, agx_tag *truth, uint32_t *n_truth, uint32_t *status, bool device,
+                         RenderArgs &a, const char **why)
+{
+    if (!camera || !params) return *why = "a null camera or params", AGX_ERR_ARG;
+    agx_camera cam;
+    agx_render_params p;
+    std::memcpy(&cam, camera, sizeof cam);
+    std::memcpy(&p, params, sizeof p);
+    int edge = 0, border = 0;
+    uint32_t n_codes = 0;
+    if (!render_family(family, edge, border, n_codes)) return *why = "an unknown family", AGX_ERR_FAMILY;
+    a.lens = lens_model;
+    a.n_frames = n_frames;
+    a.width = width;
+    a.height = height;
+    a.row_stride = row_stride_bytes;
+    a.frame_stride = frame_stride_bytes;
+    a.format = format;
+    a.family = family;
+    a.poses = poses;
+    a.frames = frames;
+    a.truth = truth;
+    a.n_truth = n_truth;
+    a.status = status;
+    // (the geometry of a layout that is refused is not used: cols = 0 must not divide)
+    a.g = render_geom(lens_model, cam, cols, (uint64_t)cols * rows <= FIT_MAX_BOARD ? rows : 0, first_id, spacing_ratio, tag_size, edge, border, p);
+    return (*why = render_args_bad(a, cam, p, device)) ? AGX_ERR_ARG : AGX_OK;
+}
+
+int agx_render_boards_enqueue(agx_detector *det, int n_frames, int width, int height, size_t row_stride_bytes, size_t frame_stride_bytes,
+                              int format, int family, uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
+                              int lens_model, const double *camera, const double *d_poses, const void *params, void *d_frames, agx_tag *d_truth,
+                              uint32_t *d_n_truth, uint32_t *d_status)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    RenderArgs a{};
+    const char *why = nullptr;
+    if (const int st = render_record(n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, family, cols, rows, first_id, spacing_ratio,
+                                     tag_size, lens_model, camera, d_poses, params, d_frames, d_truth, d_n_truth, d_status, true, a, &why))
+        return fail(det, st, why);
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // and there is nothing of this one to be fetched
+    const hipError_t e = (hipError_t)launch_render_boards(a, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_render_boards: ") + hipGetErrorString(e));
+    return AGX_OK;
+    });
+}
+
+int agx_render_boards_tail(int width, int height, size_t row_stride_bytes, int format, int family, uint32_t cols, uint32_t rows, uint32_t first_id,
+                           float spacing_ratio, double tag_size, int lens_model, const double *camera, const double *pose, const void *params,
+                           void *frame, agx_tag *truth, uint32_t *n_truth, uint32_t *status)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    RenderArgs a{};
+    const char *why = nullptr;
+    if (const int st = render_record(1, width, height, row_stride_bytes, row_stride_bytes * (size_t)(height > 0 ? height : 0), format, family, cols, rows,
+                                     first_id, spacing_ratio, tag_size, lens_model, camera, pose, params, frame, truth, n_truth, status, false, a, &why))
+        return st;
+    render_boards_host(a);
     return AGX_OK;
     });
 }

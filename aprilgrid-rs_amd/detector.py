@@ -1315,6 +1315,37 @@ class TagDetector:
                                                               out.data_ptr(), 8))
         return out
 
+    def render_boards_enqueue(self, frames, cols, rows, camera, poses, truth, n_truth, status, family=None, first_id=0, spacing_ratio=0.3,
+                              tag_size=1.0, black=0, white=None, background=None, page_margin=0.5, supersample=3, keep_background=False):
+        """render_boards (the host form says what is drawn) into a device batch, stream-ordered behind torch's current stream;
+        nothing to fetch.  frames: a device tensor [N, H, W] uint8 / 16-bit whose pixels of a row are adjacent (rows and frames may
+        be padded views); poses: float64 [N, 12] on the frames' device, R row major then t -- board_pose_enqueue's `pose`, read
+        in place; truth int32 [N, rows * cols, 9], n_truth and status int32 [N] take the projected corners of every tag (the
+        rows board_pose_enqueue's `pred` would hold), their count and AGX_RENDER_*.  family: a TagFamily (default: the
+        detector's).  white defaults to the format's largest value, background to half of it.  -> frames."""
+        import torch
+        fmt, px = self._gray_batch(frames, "frames")
+        n, h, w, dev = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2]), frames.device
+        n_board = int(cols) * int(rows)
+
+        def tensor(t, dtype, shape, what):
+            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == shape and t.device == dev):
+                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s tensor %s on the frames' device" % (what, dtype, shape))
+            return t.data_ptr()
+
+        ptrs = (tensor(truth, torch.int32, (n, n_board, 9), "truth"), tensor(n_truth, torch.int32, (n,), "n_truth"),
+                tensor(status, torch.int32, (n,), "status"))
+        d_poses = tensor(poses, torch.float64, (n, 12), "poses")
+        model, cam = _camera(camera)
+        params = _render_params(fmt, black, white, background, page_margin, supersample, keep_background)
+        fam = int(self.tag_family if family is None else (TagFamily.from_str(family) if isinstance(family, str) else family))
+        self._follow_torch_stream(frames)
+        rs = (frames.stride(1) if h > 1 else w) * px  # (a lone row or frame has no stride of its own)
+        fs = frames.stride(0) * px if n > 1 else rs * h
+        self._enqueued(self._lib.agx_render_boards_enqueue(self._h, n, w, h, rs, fs, fmt, fam, int(cols), int(rows), int(first_id), float(spacing_ratio),
+                                                           float(tag_size), model, cam, d_poses, C.addressof(params), frames.data_ptr(), *ptrs))
+        return frames
+
     def detect_rectified(self, frames, camera, new_camera=None, dst_size=None, rotation=None, to_source=False, border=0, **detect_kw):
         """detect_batch on the frames as the ideal pinhole `new_camera` (default: the camera's own fx fy cx cy) would have seen
         them: frames, a device tensor [N, H, W] uint8 / 16-bit of `camera` (a Camera of any lens model), go through remap_enqueue
@@ -2393,6 +2424,90 @@ def rectified_points(points, camera, new_camera, rotation=None):
     if st != _ffi.AGX_OK:
         raise AgxError(st)
     return out
+
+
+def _render_params(fmt, black, white, background, page_margin, supersample, keep_background):
+    """-> the agx_render_params of the keywords (white None: the format's largest value; background None: half of it)"""
+    top = 65535 if fmt == _ffi.AGX_L16 else 255
+    white = top if white is None else white
+    background = top // 2 + 1 if background is None else background
+    for v in (black, white, background, supersample):
+        if not 0 <= int(v) < 2 ** 32:
+            raise AgxError(_ffi.AGX_ERR_ARG, "black, white, background and supersample must be unsigned 32-bit numbers")
+    return _ffi.RenderParams(int(black), int(white), int(background), float(page_margin), int(supersample),
+                             _ffi.AGX_RENDER_KEEP_BACKGROUND if keep_background else 0)
+
+
+def board_pose_looking_at(distance, tilt_x=0.0, tilt_y=0.0, roll=0.0, offset=(0.0, 0.0)):
+    """The pose (R [3, 3], t [3], float64; Xc = R X + t) of a board that faces the camera `distance` (in tag_size's unit) down the
+    optical axis, its centre moved by `offset` (x, y) in the camera frame.  At zero angles the board's X is the image's right and
+    its Y the image's up -- tag first_id sits at the bottom left, as Kalibr prints it -- so R = diag(1, -1, -1).  tilt_x, tilt_y and
+    roll (degrees) then turn the board about the camera's x, y and z axes through the board's centre: R = Rz(roll) Ry(tilt_y)
+    Rx(tilt_x) diag(1, -1, -1)."""
+    ax, ay, az = (float(np.deg2rad(v)) for v in (tilt_x, tilt_y, roll))
+    cx, sx, cy, sy, cz, sz = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
+    rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]], np.float64)
+    ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]], np.float64)
+    rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]], np.float64)
+    return rz @ ry @ rx @ np.diag([1.0, -1.0, -1.0]), np.array([float(offset[0]), float(offset[1]), float(distance)], np.float64)
+
+
+def pose_rows(poses):
+    """(R, t), a list of them, or an array [12] / [N, 12] -> contiguous float64 [N, 12]: R row major, then t"""
+    if isinstance(poses, tuple) and len(poses) == 2 and np.ndim(poses[0]) == 2:
+        poses = [poses]
+    if isinstance(poses, (list, tuple)) and len(poses) and isinstance(poses[0], (list, tuple)) and len(poses[0]) == 2 and np.ndim(poses[0][0]) == 2:
+        poses = [np.concatenate([np.asarray(r, np.float64).reshape(9), np.asarray(t, np.float64).reshape(3)]) for r, t in poses]
+    a = np.ascontiguousarray(poses, np.float64)
+    if a.ndim == 1:
+        a = a[None]
+    if a.ndim != 2 or a.shape[1] != 12:
+        raise AgxError(_ffi.AGX_ERR_ARG, "poses must be (R, t), a list of them, or an array [N, 12]")
+    return a
+
+
+def render_boards(size, cols, rows, camera, poses, family="T36H11", first_id=0, spacing_ratio=0.3, tag_size=1.0, black=0, white=None,
+                  background=None, page_margin=0.5, supersample=3, keep_background=False, dtype=np.uint8, out=None):
+    """The printed board (Kalibr's AprilGrid layout of board_fit: tag first_id + r*cols + c at column c, row r; black squares of
+    side spacing_ratio at the lattice points; the tags of `family` with their borders and code bits) as `camera` (a Camera of any
+    lens model) sees it from each of `poses` ((R, t), a list of them or [N, 12]; Xc = R X + t with the board in the plane Z = 0,
+    centred, in tag_size's unit: board_pose's pose) without a device (agx_render_boards_tail, once per frame).  A pixel takes
+    supersample x supersample samples; each is taken back to the board through the inverse of board_pose's forward projection
+    (a seed from the lens's unprojection, 4 Newton steps, accepted within 2^-20 px) and the pixel is the rounded mean of white,
+    black and background over its samples, in integers.  page_margin: the white border around the board, in tag sides.
+    keep_background: the frame's own pixels are the background (an overlay on `out`); a pixel with no sample on the page is not
+    written.  size (w, h); dtype uint8 or uint16; out: the caller's array [N, H, W] (or [H, W] for one pose), rows and frames may
+    be padded.
+    -> (frames [N, H, W], truth [N, rows * cols] rows of TagDetector.TAG_DTYPE -- the projected corners of every tag in id order,
+    NaN without a projection --, n_truth uint32 [N], status uint32 [N] AGX_RENDER_*)."""
+    p = pose_rows(poses)
+    n, (w, h) = p.shape[0], (int(size[0]), int(size[1]))
+    if out is None:
+        dt = np.dtype(dtype)
+        if dt not in (np.uint8, np.uint16) or keep_background:
+            raise AgxError(_ffi.AGX_ERR_ARG, "dtype must be uint8 or uint16; keep_background needs out")
+        res = np.zeros((n, max(h, 0), max(w, 0)), dt)
+        fmt, px = (_ffi.AGX_L8 if dt == np.uint8 else _ffi.AGX_L16), dt.itemsize
+        if res.size == 0:
+            res = np.zeros((n, 1, 1), dt)  # (the library refuses the size)
+    else:
+        res, fmt, px, _ = _gray_host(out, "out")
+        if res.shape != (n, h, w):
+            raise AgxError(_ffi.AGX_ERR_ARG, "out must have the shape [N, H, W] of the poses and size")
+    model, cam = _camera(camera)
+    params = _render_params(fmt, black, white, background, page_margin, supersample, keep_background)
+    fam = int(TagFamily.from_str(family) if isinstance(family, str) else family)
+    n_board = int(cols) * int(rows) if 0 < int(cols) * int(rows) <= 4096 else 1
+    truth = np.zeros((n, n_board), TagDetector.TAG_DTYPE)
+    n_truth, status = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    rs = res.strides[1] if res.shape[1] > 1 else res.shape[2] * px
+    for f in range(n):
+        st = _ffi.lib().agx_render_boards_tail(w, h, rs, fmt, fam, int(cols), int(rows), int(first_id), float(spacing_ratio), float(tag_size), model, cam,
+                                               p[f].ctypes.data, C.addressof(params), res[f].ctypes.data, truth[f].ctypes.data,
+                                               n_truth[f:].ctypes.data, status[f:].ctypes.data)
+        if st != _ffi.AGX_OK:
+            raise AgxError(st)
+    return (res if out is None else out), truth, n_truth, status
 
 
 def _find_board_call(call, saddles, cap, keep=None):

@@ -168,6 +168,21 @@ pub const AGX_FIT_ROW_OFF_BOARD: c_int = 2;
 pub const AGX_LENS_RADTAN: c_int = 0;
 pub const AGX_LENS_EQUIDISTANT: c_int = 1;
 pub const AGX_LENS_DOUBLE_SPHERE: c_int = 2;
+pub const AGX_RENDER_OK: c_int = 0;
+pub const AGX_RENDER_EMPTY: c_int = 1;
+pub const AGX_RENDER_INPUT: c_int = 2;
+pub const AGX_RENDER_KEEP_BACKGROUND: c_int = 1;
+/// `params` of `agx_render_boards_enqueue` / `_tail` (the header's `struct agx_render_params`; the prototypes take it as `const void *`)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct agx_render_params {
+    pub black: u32,
+    pub white: u32,
+    pub background: u32,
+    pub page_margin: c_float,
+    pub supersample: u32,
+    pub flags: u32,
+}
 /// both words of a rectification map's entry that has no source pixel (the header's `#define AGX_MAP_NONE`, INT32_MIN)
 pub const AGX_MAP_NONE: i32 = i32::MIN;
 // agx_debug_fetch items
@@ -427,6 +442,17 @@ extern "C" {
     pub fn agx_rectified_points_tail(lens_model: c_int, camera: *const c_double, new_camera: *const c_double, rotation: *const c_double,
                                      points: *const c_void, point_stride_bytes: usize, n_points: u32, out: *mut c_void,
                                      out_stride_bytes: usize) -> c_int;
+    // the board through pose and lens model; params: an agx_render_params (six 32-bit fields: black, white, background as u32,
+    // page_margin as f32, supersample and flags as u32), handed over as const void *
+    pub fn agx_render_boards_enqueue(det: *mut agx_detector, n_frames: c_int, width: c_int, height: c_int, row_stride_bytes: usize,
+                                     frame_stride_bytes: usize, format: c_int, family: c_int, cols: u32, rows: u32, first_id: u32,
+                                     spacing_ratio: c_float, tag_size: c_double, lens_model: c_int, camera: *const c_double,
+                                     d_poses: *const c_double, params: *const c_void, d_frames: *mut c_void, d_truth: *mut agx_tag,
+                                     d_n_truth: *mut u32, d_status: *mut u32) -> c_int;
+    pub fn agx_render_boards_tail(width: c_int, height: c_int, row_stride_bytes: usize, format: c_int, family: c_int, cols: u32, rows: u32,
+                                  first_id: u32, spacing_ratio: c_float, tag_size: c_double, lens_model: c_int, camera: *const c_double,
+                                  pose: *const c_double, params: *const c_void, frame: *mut c_void, truth: *mut agx_tag, n_truth: *mut u32,
+                                  status: *mut u32) -> c_int;
     pub fn agx_debug_blur_weights(sigma: c_float, weights: *mut c_float, cap: c_int, radius: *mut c_int) -> c_int;
     pub fn agx_debug_refine_constants(half_size_patch: c_int, cone: *mut c_float, pmat: *mut c_float, cap_points: c_int,
                                       n_points: *mut c_int) -> c_int;

@@ -965,6 +965,49 @@ pub fn rectified_points_tail(model: LensModel, camera: &Camera, rect: &Rectifica
     out.chunks(2).map(|c| (c[0], c[1])).collect()
 }
 
+/// What `render_boards_tail` drew: the L8 frame, row major, and the projected corners of every tag of the layout in id order.
+#[derive(Clone, Debug)]
+pub struct RenderedBoard {
+    /// `AGX_RENDER_OK` or `AGX_RENDER_EMPTY`
+    pub status: u32,
+    pub frame: Vec<u8>,
+    /// `(id, corners)`; `(NaN, NaN)` for a corner without a projection; empty unless `status` is `AGX_RENDER_OK`
+    pub truth: Vec<(u32, [(f32, f32); 4])>,
+}
+
+/// The printed board of `layout` (tags of `family`) as `camera` under `model` sees it from the pose `r` (row major, board ->
+/// camera), `t` in `tag_size`'s unit, the host form (no device is used): one tightly packed L8 frame of `size` = (w, h) drawn over
+/// `background`, `supersample` x `supersample` samples a pixel, a white `page_margin` (tag sides) around the board.
+/// `Err(AGX_RENDER_INPUT)`: a pose that is not finite or not a rotation.  Panics where the library refuses the arguments.
+pub fn render_boards_tail(family: TagFamily, layout: &BoardLayout, model: LensModel, camera: &Camera, tag_size: f64, r: &[f64; 9], t: &[f64; 3],
+                          size: (u32, u32), black: u8, white: u8, background: u8, page_margin: f32, supersample: u32) -> Result<RenderedBoard, u32> {
+    let cam = camera_doubles(camera);
+    let mut pose = [0f64; 12];
+    pose[..9].copy_from_slice(r);
+    pose[9..].copy_from_slice(t);
+    let params = ffi::agx_render_params { black: black as u32, white: white as u32, background: background as u32, page_margin, supersample, flags: 0 };
+    let n_board = layout.cols as usize * layout.rows as usize;
+    let mut frame = vec![background; size.0 as usize * size.1 as usize];
+    let mut truth = vec![ffi::agx_tag { id: 0, xy: [0.0; 8] }; n_board.max(1)];
+    let (mut n_truth, mut status) = (0u32, 0u32);
+    let st = unsafe {
+        ffi::agx_render_boards_tail(size.0 as c_int, size.1 as c_int, size.0 as usize, ffi::AGX_L8, family as c_int, layout.cols, layout.rows,
+                                    layout.first_id, layout.spacing_ratio, tag_size, model as c_int, cam.as_ptr(), pose.as_ptr(),
+                                    &params as *const ffi::agx_render_params as *const std::os::raw::c_void,
+                                    frame.as_mut_ptr() as *mut std::os::raw::c_void, truth.as_mut_ptr(), &mut n_truth, &mut status)
+    };
+    assert_eq!(st, ffi::AGX_OK, "agx_render_boards_tail failed: {}", st);
+    if status as c_int == ffi::AGX_RENDER_INPUT {
+        return Err(status);
+    }
+    Ok(RenderedBoard {
+        status,
+        frame,
+        truth: truth[..n_truth as usize].iter()
+            .map(|q| (q.id, [(q.xy[0], q.xy[1]), (q.xy[2], q.xy[3]), (q.xy[4], q.xy[5]), (q.xy[6], q.xy[7])])).collect(),
+    })
+}
+
 fn last_error(det: *const ffi::agx_detector) -> String {
     unsafe {
         let p = ffi::agx_last_error(det);

@@ -1321,6 +1321,65 @@ int agx_rectified_points_tail(int lens_model, const double *camera, const double
                               const void *points, size_t point_stride_bytes, uint32_t n_points,
                               void *out, size_t out_stride_bytes);
 
+/* ---- the board through the lens: a pose and a camera to the pixels the sensor sees (csrc/render.hip; csrc/render_math.h) ---- */
+
+/* The forward model of agx_board_pose_enqueue_m, applied to the printed board itself: for every frame f of a device batch the
+ * board of the layout (cols, rows, first_id, spacing_ratio; tag first_id + r cols + c at column c, row r; the plane Z = 0 centred on
+ * the board's centre, in tag_size's unit -- agx_board_pose_enqueue's board frame) as the camera (lens_model, camera: nine HOST
+ * doubles, agx_board_pose_enqueue_m's rules) sees it from the pose d_poses[f] = 12 doubles, R row major then t: exactly
+ * agx_board_pose_enqueue_m's d_pose, readable in place.  For overlays of the board at an estimated pose, synthetic batches under
+ * any lens without a host round trip, and ground truth that is the forward model itself (k_render_boards<LENS>).
+ * d_frames: n_frames frames of width x height, AGX_L8 or AGX_L16, row and frame strides as in every batch entry.  `family`'s code
+ * table (agx_family) gives the tags' bits.  params: HOST memory, copied by the call -- struct agx_render_params below names its
+ * six 32-bit fields (the prototypes take it as const void *): black, white, background in the format's range; page_margin, the
+ * white border around the board in tag sides; supersample S in 1 .. 4; flags.
+ * A pixel (i, j) takes S x S samples at (i + (a + 1/2) / S - 1/2, j + (b + 1/2) / S - 1/2).  A sample (u, v) is inverted to the
+ * board point (X, Y) whose FORWARD projection -- the one of agx_debug_pose_project -- is (u, v): a seed from the lens's
+ * unprojection and the ray's intersection with the board's plane, then 4 Newton steps on the 2 x 2 system with the pose's own
+ * analytic Jacobian (no early exit).  The sample is on the page iff that point projects, its projection lies within 2^-20 px of
+ * (u, v), and (X, Y) lies on the page; any other sample -- outside the double-sphere cone, or with Z not > 0 under the other two
+ * models, among them -- is background.  No clamp of the seed decides by itself.  The board: a black square of side spacing_ratio
+ * at every lattice point (the outer ring included), every tag with its black border and the family's code bits, rows printed
+ * from the high end of Y (Kalibr's board, y up), white elsewhere on the page: the tag's corners in the order (0,0), (1,0),
+ * (1,1), (0,1) of its board square decode to its own id at quarter turn 0.  Shading is integer only:
+ *   value = (n_white white + n_black black + n_bg bg + S S / 2) / (S S)      in uint32,
+ * bg = background, or under AGX_RENDER_KEEP_BACKGROUND the pixel's current value (an overlay on a real frame; a pixel with no
+ * sample on the page is then not written at all).  Binary64 with + - * / and correctly rounded square roots up to the
+ * classification, nothing floating after it.  Never a byte beyond `width` pixels of a row is written.
+ * Ground truth: d_truth [n_frames][rows cols] agx_tag rows {id, xy} of every tag of the layout in id order with d_n_truth[f] =
+ * rows cols -- the bytes agx_board_pose_enqueue_m's d_pred has for the same pose, (NaN, NaN) for a corner without a projection;
+ * the rows feed agx_snap_points_enqueue and agx_decode_quads_enqueue in place.
+ * d_status[f], decided before the frame's first store: AGX_RENDER_OK; AGX_RENDER_EMPTY, none of the board's four outer corners
+ * projects (the frame is all background, or under AGX_RENDER_KEEP_BACKGROUND untouched; d_n_truth[f] = 0); AGX_RENDER_INPUT, a
+ * pose entry that is not finite or two columns of R whose dot product is further than 2^-20 from 1 (with itself) or 0 (nothing of
+ * the frame is written; d_n_truth[f] = 0).  Caller-owned device memory, stream-ordered, nothing to fetch; a batch in flight is
+ * replaced as by agx_board_fit_enqueue.
+ * AGX_ERR_FAMILY: an unknown family.  AGX_ERR_ARG (a batch in flight stays where it is): a NULL array; n_frames outside
+ * 1 .. 65535; a format other than AGX_L8 and AGX_L16; a side outside 1 .. 16384; agx_remap_enqueue's rules on strides and 16-bit
+ * alignment; rows cols outside 1 .. 4096, a spacing_ratio that is negative or not finite; agx_board_pose_enqueue_m's rules on
+ * lens_model, camera and tag_size; first_id + rows cols beyond the family's code table; S outside 1 .. 4; a colour above 255
+ * (AGX_L8) or 65535 (AGX_L16); a page_margin that is negative or not finite; an unknown flag; d_poses not 8-byte aligned, another
+ * array not 4-byte aligned.
+ * agx_render_boards_tail: the host form -- ONE frame in host memory, no handle, no device, the same bytes. */
+enum { AGX_RENDER_OK = 0, AGX_RENDER_EMPTY = 1, AGX_RENDER_INPUT = 2 };
+enum { AGX_RENDER_KEEP_BACKGROUND = 1 };
+struct agx_render_params { uint32_t black, white, background; float page_margin; uint32_t supersample, flags; };
+typedef struct agx_render_params agx_render_params;
+#ifdef __cplusplus
+static_assert(sizeof(agx_render_params) == 24, "agx_render_params: six 32-bit fields");
+#else
+_Static_assert(sizeof(agx_render_params) == 24, "agx_render_params: six 32-bit fields");
+#endif
+int agx_render_boards_enqueue(agx_detector *det, int n_frames, int width, int height,
+                              size_t row_stride_bytes, size_t frame_stride_bytes, int format, int family,
+                              uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
+                              int lens_model, const double *camera, const double *d_poses, const void *params,
+                              void *d_frames, agx_tag *d_truth, uint32_t *d_n_truth, uint32_t *d_status);
+int agx_render_boards_tail(int width, int height, size_t row_stride_bytes, int format, int family,
+                           uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
+                           int lens_model, const double *camera, const double *pose, const void *params,
+                           void *frame, agx_tag *truth, uint32_t *n_truth, uint32_t *status);
+
 /* ---- detector groups: several GPUs of one node driven from ONE process ----------------- */
 
 /* The reference's detect(&self) is stateless, so a batch shards by frame:
