@@ -124,6 +124,10 @@ SYMBOLS = {
                                      C.POINTER(C.c_uint32)]),
     "agx_rochade_refine_h": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, _P, C.c_uint32, _P, _P,
                                        C.POINTER(C.c_uint32), C.c_int]),
+    "agx_refine_windows_enqueue": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, _P, C.c_size_t, C.c_uint32,
+                                             _P, _P, _P, _P, C.c_int, C.c_int]),
+    "agx_decimate_enqueue": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _P, C.c_size_t, C.c_size_t]),
+    "agx_decimate_tail": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _P, C.c_size_t, C.c_size_t]),
     "agx_decode_quads_enqueue": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, _P, C.c_size_t, C.c_uint32,
                                            _P, _P, _P, _P, _P]),
     "agx_decode_quads_fetch": (C.c_int, [_P, _P, _P, _P]),

@@ -180,6 +180,33 @@ struct RefinePatchConsts {
 // a point's own (4*half+1)^2 window, whatever p.padded says.  hipError_t
 int launch_refine_patch(const RefinePointsArgs &p, const RefinePatchConsts *consts, int half, int n_frames, void *stream);
 
+// k_refine_windows<HALF> (agx_refine_windows_enqueue): the same rochade_refine on the frames' blur at the taps `w`, with the blur
+// window of every point computed from the input in LDS: no plane is read or written.  All pointers are device pointers.
+struct RefineWindowsArgs {
+    const uint8_t *frames;   // frames of format `fmt`: 0 AGX_L8, 1 AGX_L16, 3 AGX_LF32
+    long long frame_stride;  // bytes
+    int row_stride;          // bytes
+    int fmt;
+    int W, H;
+    const void *points;      // slot s: two floats (x, y) at points + s * point_stride, s = f * points_per_frame + i
+    size_t point_stride;     // bytes, a multiple of 4, >= 8
+    uint32_t points_per_frame;
+    const uint32_t *counts;     // as RefinePointsArgs
+    const uint32_t *status_in;  // [n_frames][points_per_frame], or null: a slot whose word is non-zero is handed on, not refined
+    float *out;                 // as RefinePointsArgs
+    uint32_t *status;
+    int factor;           // 1: the point as it is; else x * scale + offset, two rounded operations
+    float scale, offset;  // (float)factor, 0.5f * (factor - 1)
+    int radius;           // 1 .. GB_MAX_RADIUS
+    float w[2 * 16 + 1];  // the blur taps (GaussBlurArgs::w)
+    int points_per_group;  // set by the launch: points of a workgroup, and the floats of LDS between two of them
+    uint32_t lds_stride;
+};
+// the points a workgroup takes at this half size and radius: whole waves (multiples of 4), at most 16, within 64 KB of LDS
+int refine_windows_points_per_group(int half, int radius);
+// grid (ceil(points_per_frame / points per group), n_frames <= 65535); `consts` is the device record of `half`.  hipError_t
+int launch_refine_windows(const RefineWindowsArgs &p, const RefinePatchConsts *consts, int half, int n_frames, void *stream);
+
 // The chain's deferred refinement, between launch_kernel(K_FLOOD_REFINE, .., true) and launch_kernel(K_RARE, .., true):
 // k_generic_cluster (a.n_frames workgroups; generic_frame for the frames that need it) and k_refine_clusters<half>, rochade_refine
 // at half_size_patch `half` in 1 .. 4 of every frame's cluster table on its blur plane (a fixed number of one-wave workgroups per

@@ -3482,11 +3482,15 @@ __device__ __forceinline__ uint32_t refine_point(const RefineConsts &rc, const f
 }
 
 // A point's slot: its record -- five zeros unless it refined -- and its status.
-__device__ __forceinline__ void write_point_slot(const RefinePointsArgs &p, size_t slot, uint32_t st, const float (&rec)[5])
+__device__ __forceinline__ void write_point_slot(float *out, uint32_t *status, size_t slot, uint32_t st, const float (&rec)[5])
 {
 #pragma unroll
-    for (int q = 0; q < 5; ++q) p.out[slot * 5 + q] = st == POINT_REFINED ? rec[q] : 0.0f;
-    p.status[slot] = st;
+    for (int q = 0; q < 5; ++q) out[slot * 5 + q] = st == POINT_REFINED ? rec[q] : 0.0f;
+    status[slot] = st;
+}
+__device__ __forceinline__ void write_point_slot(const RefinePointsArgs &p, size_t slot, uint32_t st, const float (&rec)[5])
+{
+    write_point_slot(p.out, p.status, slot, st, rec);
 }
 
 // grid (ceil(points_per_frame / 64), n_frames): point i of frame f reads points[f * ppf + i] and writes record and status
@@ -3546,14 +3550,14 @@ struct RefinePatchLds {
     float smooth[REFINE_PATCH_POINTS][SMOOTH_STRIDE];
     float prm[REFINE_PATCH_POINTS][8];
 };
-template <int HALF>
-__device__ __forceinline__ void refine_patch_body(RefinePatchLds<HALF> &s, uint32_t g, uint32_t l, bool inside, const float *win,
-                                                  size_t pitch, const RefinePatchConsts *__restrict__ rc)
+// Steps 2 and 3 for point g, whose window lies in LDS at s.win[g] (WIN floats a row): s.smooth[g] and the six sums s.prm[g][0 .. 5].
+// The one statement of these sums: refine_patch_body below and k_refine_windows, whose window is a blur it computed itself
+// and whose LDS (RefineWindowsLds: any number of points) is laid out at launch, both come through here.  Every lane of the
+// workgroup calls it: the first barrier is the one behind the window's writes.
+template <int HALF, typename LDS>
+__device__ __forceinline__ void refine_patch_sums(LDS &s, uint32_t g, uint32_t l, bool inside, const RefinePatchConsts *__restrict__ rc)
 {
-    constexpr int KS = RefinePatchLds<HALF>::KS, N = RefinePatchLds<HALF>::N, WIN = RefinePatchLds<HALF>::WIN, NWIN = RefinePatchLds<HALF>::NWIN;
-    if (inside) {
-        for (int e = (int)l; e < NWIN; e += REFINE_PATCH_LANES) s.win[g][e] = win[(size_t)(e / WIN) * pitch + (e % WIN)];
-    }
+    constexpr int KS = RefinePatchLds<HALF>::KS, N = RefinePatchLds<HALF>::N, WIN = RefinePatchLds<HALF>::WIN;
     __syncthreads();
     if (inside) {
         for (int o = (int)l; o < N; o += REFINE_PATCH_LANES) {
@@ -3574,6 +3578,17 @@ __device__ __forceinline__ void refine_patch_body(RefinePatchLds<HALF> &s, uint3
         s.prm[g][l] = sum;
     }
     __syncthreads();
+}
+
+template <int HALF>
+__device__ __forceinline__ void refine_patch_body(RefinePatchLds<HALF> &s, uint32_t g, uint32_t l, bool inside, const float *win,
+                                                  size_t pitch, const RefinePatchConsts *__restrict__ rc)
+{
+    constexpr int WIN = RefinePatchLds<HALF>::WIN, NWIN = RefinePatchLds<HALF>::NWIN;
+    if (inside) {
+        for (int e = (int)l; e < NWIN; e += REFINE_PATCH_LANES) s.win[g][e] = win[(size_t)(e / WIN) * pitch + (e % WIN)];
+    }
+    refine_patch_sums<HALF>(s, g, l, inside, rc);
 }
 
 template <int HALF>
@@ -3613,6 +3628,146 @@ int launch_refine_patch(const RefinePointsArgs &p, const RefinePatchConsts *cons
     case 3: hipLaunchKernelGGL((k_refine_patch<3>), grid, block, 0, s, p, consts); break;
     case 4: hipLaunchKernelGGL((k_refine_patch<4>), grid, block, 0, s, p, consts); break;
     default: return (int)hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// k_refine_windows<HALF>: rochade_refine of caller-given points on the frames' blur WITHOUT a blur plane --
+// agx_refine_windows_enqueue.  Every pixel of gaussian_blur_f32 (image_util.rs:110-206) is a function of the input alone, so
+// the (4*HALF+1)^2 blur window of a point is computed from the (4*HALF+1+2r)^2 input pixels around it, r = ceil(2 sigma),
+// in LDS, and nothing else of the frame is touched.  Sixteen lanes serve one point, as in k_refine_patch:
+//   0. the slot's word of status_in, if non-zero, is handed on and the point is not looked at; else the point, read in place
+//      (rows of any stride), goes to full resolution (factor > 1: one rounded multiply and one rounded add) and
+//      refine_window_inside decides AGX_POINT_OUTSIDE in float before anything is read;
+//   1. the input window goes to LDS as luma through luma32f_at, the conversion k_gauss_blur uses, coordinates clamped to the frame
+//      (the reference's border rule of both passes: a clamped row of the staged tile is the clamped row's horizontal pass);
+//   2. the horizontal pass, (4*HALF+1+2r) rows x (4*HALF+1) columns, each value ONE running sum from 0.0f over the taps ascending;
+//   3. the vertical pass writes the (4*HALF+1)^2 blur window over the staged tile, the same way;
+//   4. refine_patch_sums -- k_refine_patch's own conv and parameter sums -- then lane 0 runs refine_tail and writes the slot.
+// A blur pixel computed this way has the bytes k_gauss_blur (and K1 at sigma 1.5) stores for it, so every record and status
+// word equals agx_refine_points_enqueue_h's on the blur plane.  The workgroup holds p.points_per_group points, chosen by the
+// launch from HALF and r so that the windows fit 64 KB of LDS; p.lds_stride floats apart.
+// ------------------------------------------------------------------------------------------
+template <int FMT>
+__device__ __forceinline__ float luma32f_at(const uint8_t *__restrict__ rowp, int x);
+
+constexpr int REFINE_WINDOWS_MAX_POINTS = 16;
+static_assert(sizeof(RefineWindowsArgs::w) == sizeof(GaussBlurArgs::w), "the taps of k_gauss_blur");
+
+// refine_patch_sums' view of k_refine_windows' LDS: point g's arrays at base + g * stride
+struct RefineWindowsLds {
+    struct PerPoint {
+        float *base;
+        uint32_t stride;
+        __device__ __forceinline__ float *operator[](uint32_t g) const { return base + (size_t)g * stride; }
+    };
+    PerPoint win, smooth, prm;
+};
+
+template <int HALF>
+__global__ void __launch_bounds__(REFINE_WINDOWS_MAX_POINTS *REFINE_PATCH_LANES) k_refine_windows(RefineWindowsArgs p, const RefinePatchConsts *__restrict__ rc)
+{
+    extern __shared__ float rw_lds[];
+    constexpr int WIN = RefinePatchLds<HALF>::WIN, N = RefinePatchLds<HALF>::N;
+    const int r = p.radius, taps = 2 * r + 1, T = WIN + 2 * r;
+    const uint32_t g = threadIdx.x / REFINE_PATCH_LANES, l = threadIdx.x % REFINE_PATCH_LANES;
+    // a point's floats: the staged tile (T x T; the blur window, WIN x WIN, lies in it later), the horizontal pass (T x WIN), smooth[N], prm[8]
+    const RefineWindowsLds s{{rw_lds, p.lds_stride}, {rw_lds + T * T + T * WIN, p.lds_stride}, {rw_lds + T * T + T * WIN + N, p.lds_stride}};
+    float *tile = s.win[g], *hbuf = tile + T * T;
+    const float *prm = s.prm[g];
+    const uint32_t f = blockIdx.y, i = blockIdx.x * (uint32_t)p.points_per_group + g;
+    uint32_t n = p.points_per_frame;
+    if (p.counts) n = min(p.counts[f], n);
+    const bool live = i < n;  // (no lane leaves before the last barrier)
+    const size_t slot = (size_t)f * p.points_per_frame + (live ? i : 0u);
+    uint32_t handed = 0u;
+    if (live && p.status_in) handed = p.status_in[slot];
+    float rxf = 0.0f, ryf = 0.0f;
+    bool inside = false;
+    if (live && !handed) {
+        const float *pt = reinterpret_cast<const float *>(static_cast<const unsigned char *>(p.points) + slot * p.point_stride);
+        float x = pt[0], y = pt[1];
+        if (p.factor != 1) {
+            x = x * p.scale + p.offset;
+            y = y * p.scale + p.offset;
+        }
+        inside = refine_window_inside<HALF>(x, y, p.W, p.H, rxf, ryf);
+    }
+    if (inside) {
+        const uint8_t *frame = p.frames + (size_t)f * (size_t)p.frame_stride;
+        const int x0 = (int)rxf - 2 * HALF - r, y0 = (int)ryf - 2 * HALF - r;
+        for (int e = (int)l; e < T * T; e += REFINE_PATCH_LANES) {
+            const int ry = e / T, rx = e - ry * T;
+            const int y = min(max(y0 + ry, 0), p.H - 1), x = min(max(x0 + rx, 0), p.W - 1);
+            const uint8_t *rowp = frame + (size_t)y * (size_t)p.row_stride;
+            tile[e] = p.fmt == 0 ? luma32f_at<0>(rowp, x) : p.fmt == 1 ? luma32f_at<1>(rowp, x) : luma32f_at<3>(rowp, x);
+        }
+    }
+    __syncthreads();
+    if (inside) {
+        for (int e = (int)l; e < T * WIN; e += REFINE_PATCH_LANES) {
+            const int ry = e / WIN, c = e - ry * WIN;
+            const float *t = tile + ry * T + c;
+            float sum = 0.0f;
+#pragma unroll 4
+            for (int k = 0; k < taps; ++k) sum = sum + t[k] * p.w[k];
+            hbuf[e] = sum;
+        }
+    }
+    __syncthreads();
+    if (inside) {
+        for (int e = (int)l; e < WIN * WIN; e += REFINE_PATCH_LANES) {
+            const float *h = hbuf + e;  // row e / WIN, column e % WIN: tap k is k rows below
+            float sum = 0.0f;
+#pragma unroll 4
+            for (int k = 0; k < taps; ++k) sum = sum + h[k * WIN] * p.w[k];
+            tile[e] = sum;
+        }
+    }
+    refine_patch_sums<HALF>(s, g, l, inside, rc);
+    if (!live || l != 0) return;
+    float rec[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    uint32_t st = handed ? handed : POINT_OUTSIDE;
+    if (inside) {
+        const float sums[6] = {prm[0], prm[1], prm[2], prm[3], prm[4], prm[5]};
+        st = refine_tail(sums, rxf, ryf, rec);
+    }
+    write_point_slot(p.out, p.status, slot, st, rec);
+}
+
+// floats of LDS per point: the staged tile (the blur window later lies in it), the horizontal pass, smooth[], six sums; points of a
+// workgroup start 16 banks apart
+static uint32_t refine_windows_lds_stride(int half, int radius)
+{
+    const int win = 4 * half + 1, ks = 2 * half + 1, t = win + 2 * radius;
+    return (uint32_t)((t * t + t * win + ks * ks + 8 + 31) / 32 * 32 + 16);
+}
+
+int refine_windows_points_per_group(int half, int radius)
+{
+    const size_t bytes = (size_t)refine_windows_lds_stride(half, radius) * sizeof(float);
+    const size_t fit = ((size_t)64 * 1024) / bytes / REFINE_PATCH_POINTS * REFINE_PATCH_POINTS;  // whole waves
+    return (int)std::min<size_t>(fit, REFINE_WINDOWS_MAX_POINTS);  // (half 4 at radius 16: 13 376 bytes a point, four of them)
+}
+
+int launch_refine_windows(const RefineWindowsArgs &args, const RefinePatchConsts *consts, int half, int n_frames, void *stream)
+{
+    if (n_frames <= 0 || n_frames > 65535 || !args.points_per_frame || !consts || half < 1 || half > REFINE_PATCH_MAX_HALF ||
+        args.radius < 1 || args.radius > GB_MAX_RADIUS || (args.fmt != 0 && args.fmt != 1 && args.fmt != 3))
+        return (int)hipErrorInvalidValue;
+    RefineWindowsArgs p = args;
+    p.lds_stride = refine_windows_lds_stride(half, p.radius);
+    p.points_per_group = refine_windows_points_per_group(half, p.radius);
+    const size_t lds = (size_t)p.points_per_group * p.lds_stride * sizeof(float);
+    const uint32_t ppg = (uint32_t)p.points_per_group;
+    const dim3 grid((p.points_per_frame + ppg - 1) / ppg, (unsigned)n_frames), block(ppg * REFINE_PATCH_LANES);
+    hipStream_t s = (hipStream_t)stream;
+    switch (half) {
+    case 1: hipLaunchKernelGGL((k_refine_windows<1>), grid, block, lds, s, p, consts); break;
+    case 2: hipLaunchKernelGGL((k_refine_windows<2>), grid, block, lds, s, p, consts); break;
+    case 3: hipLaunchKernelGGL((k_refine_windows<3>), grid, block, lds, s, p, consts); break;
+    default: hipLaunchKernelGGL((k_refine_windows<4>), grid, block, lds, s, p, consts); break;
     }
     return hipGetLastError();
 }

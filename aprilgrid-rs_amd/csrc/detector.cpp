@@ -20,6 +20,7 @@
 #include "board_pose.h"
 #include "board_pose_math.h"
 #include "chain_kernels.h"
+#include "decimate.h"
 #include "decode_math.h"
 #include "decode_stages.h"
 #include "detector_internal.h"
@@ -1379,6 +1380,57 @@ int agx_refine_points_fetch(agx_detector *det, agx_saddle *out, uint32_t *status
     return agx_guard(det, [&]() -> int { return refine_points_fetch_impl(det, out, status); });
 }
 
+// rochade_refine on the frames' blur with no blur plane: k_refine_windows computes every point's blur window from the input
+int agx_refine_windows_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height, size_t row_stride_bytes,
+                               size_t frame_stride_bytes, int format, const void *d_points, size_t point_stride_bytes,
+                               uint32_t points_per_frame, const uint32_t *d_counts, const uint32_t *d_status_in, agx_saddle *d_out,
+                               uint32_t *d_status, int factor, int half_size_patch)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    if (format != AGX_L8 && format != AGX_L16 && format != AGX_LF32) return fail(det, AGX_ERR_FORMAT, "format must be AGX_L8, AGX_L16 or AGX_LF32");
+    if (half_size_patch < 1 || half_size_patch > REFINE_PATCH_MAX_HALF) return fail(det, AGX_ERR_ARG, "half_size_patch must be in 1 .. 4");
+    if (factor < 1 || factor > 4) return fail(det, AGX_ERR_ARG, "factor must be in 1 .. 4");
+    if (!d_frames || !d_points || n_frames <= 0) return fail(det, AGX_ERR_ARG, "null frames, null points or n_frames <= 0");
+    if (!points_per_frame) return fail(det, AGX_ERR_ARG, "points_per_frame must be > 0");
+    if (!d_out || !d_status) return fail(det, AGX_ERR_ARG, "d_out and d_status are the caller's: both are required");
+    if (point_stride_bytes < 8 || (point_stride_bytes & 3)) return fail(det, AGX_ERR_ARG, "point_stride_bytes must be a multiple of 4 and at least 8");
+    if ((((uintptr_t)d_points | (uintptr_t)d_counts | (uintptr_t)d_status_in | (uintptr_t)d_out | (uintptr_t)d_status) & 3))
+        return fail(det, AGX_ERR_ARG, "points, counts, status and result buffers must be 4-byte aligned");
+    if (const int rc = check_frame_batch(det, {d_frames, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format},
+                                         {/*min_side*/ 1, /*lf32*/ true, /*lone_frame_stride*/ false, /*align16*/ true, /*front_rows*/ false}))
+        return rc;
+    if ((size_t)n_frames * points_per_frame >= ((size_t)1 << 31)) return fail(det, AGX_ERR_ARG, "at most 2^31 - 1 points per batch");
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // and there is nothing of this one to be fetched
+    const RefinePatchConsts *d_consts = nullptr;
+    if (const int rc = ensure_patch_consts(det, &d_consts)) return rc;
+    RefineWindowsArgs p{};
+    p.frames = static_cast<const uint8_t *>(d_frames);
+    p.frame_stride = (long long)frame_stride_bytes;
+    p.row_stride = (int)row_stride_bytes;
+    p.fmt = format;
+    p.W = width;
+    p.H = height;
+    p.points = d_points;
+    p.point_stride = point_stride_bytes;
+    p.points_per_frame = points_per_frame;
+    p.counts = d_counts;
+    p.status_in = d_status_in;
+    p.out = reinterpret_cast<float *>(d_out);
+    p.status = d_status;
+    p.factor = factor;
+    p.scale = (float)factor;
+    p.offset = 0.5f * (float)(factor - 1);
+    p.radius = det->front_radius;  // the handle's sigma, as the chain's front has it
+    static_assert(sizeof(p.w) == sizeof(det->front_w), "the taps of k_gauss_blur");
+    std::memcpy(p.w, det->front_w, sizeof(p.w));
+    const hipError_t e = (hipError_t)launch_refine_windows(p, d_consts + (half_size_patch - 1), half_size_patch, n_frames, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_refine_windows: ") + hipGetErrorString(e));
+    return AGX_OK;
+    });
+}
+
 int agx_rochade_refine_h(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes, int format, int image,
                          const void *points, uint32_t n_points, agx_saddle *out, uint32_t *status, uint32_t *n_refined, int half_size_patch)
 {
@@ -2531,6 +2583,56 @@ int agx_remap_tail(const void *src, int n_frames, int src_width, int src_height,
                                    map_row_stride_bytes, dst_width, dst_height, dst, dst_row_stride_bytes, dst_frame_stride_bytes, border);
     if (remap_args_bad(a)) return AGX_ERR_ARG;
     remap_host(a);
+    return AGX_OK;
+    });
+}
+
+// ---- decimated batches (decimate.hip: k_decimate and the host form) ---------------------------------------------------------------
+static DecimateArgs decimate_args(const void *src, int n_frames, int width, int height, size_t row_stride_bytes, size_t frame_stride_bytes,
+                                  int format, int factor, void *dst, size_t dst_row_stride_bytes, size_t dst_frame_stride_bytes)
+{
+    DecimateArgs a{};
+    a.src = src;
+    a.n_frames = n_frames;
+    a.src_w = width;
+    a.src_h = height;
+    a.src_row_stride = row_stride_bytes;
+    a.src_frame_stride = frame_stride_bytes;
+    a.format = format;
+    a.factor = factor;
+    a.dst = dst;
+    a.dst_row_stride = dst_row_stride_bytes;
+    a.dst_frame_stride = dst_frame_stride_bytes;
+    return a;
+}
+
+int agx_decimate_enqueue(agx_detector *det, const void *d_src, int n_frames, int width, int height, size_t row_stride_bytes,
+                         size_t frame_stride_bytes, int format, int factor, void *d_dst, size_t dst_row_stride_bytes,
+                         size_t dst_frame_stride_bytes)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    if (format != AGX_L8 && format != AGX_L16) return fail(det, AGX_ERR_FORMAT, "format must be AGX_L8 or AGX_L16");
+    const DecimateArgs a = decimate_args(d_src, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, factor, d_dst,
+                                         dst_row_stride_bytes, dst_frame_stride_bytes);
+    if (const char *why = decimate_args_bad(a)) return fail(det, AGX_ERR_ARG, why);
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // and there is nothing of this one to be fetched
+    const hipError_t e = (hipError_t)launch_decimate(a, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_decimate: ") + hipGetErrorString(e));
+    return AGX_OK;
+    });
+}
+
+int agx_decimate_tail(const void *src, int n_frames, int width, int height, size_t row_stride_bytes, size_t frame_stride_bytes, int format,
+                      int factor, void *dst, size_t dst_row_stride_bytes, size_t dst_frame_stride_bytes)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (format != AGX_L8 && format != AGX_L16) return AGX_ERR_FORMAT;
+    const DecimateArgs a = decimate_args(src, n_frames, width, height, row_stride_bytes, frame_stride_bytes, format, factor, dst,
+                                         dst_row_stride_bytes, dst_frame_stride_bytes);
+    if (decimate_args_bad(a)) return AGX_ERR_ARG;
+    decimate_host(a);
     return AGX_OK;
     });
 }

@@ -676,6 +676,37 @@ class TagDetector:
         self._check(self._lib.agx_refine_points_fetch(self._h, out.ctypes.data, status.ctypes.data))
         return out, status
 
+    def refine_windows_enqueue(self, frames, points, out, status, counts=None, status_in=None, factor=1, half_size_patch=2, format=None):
+        """refine_points_enqueue(.., image="blurred") without its blur plane (agx_refine_windows_enqueue): every point's blur window
+        is computed from the input pixels around it, so the cost follows the points, not the pixels, and the records and status
+        words are the same bytes.  Stream-ordered behind torch's current stream; nothing to fetch.  frames: [N,H,W] uint8 / 16-bit /
+        float32 on this detector's GPU, rows and frames may be padded (a view).  points: a float32 device tensor [N,P,K], K >= 2,
+        whose rows start with (x, y) -- [N,P,2] points and [N,P,5] records are both read in place.  out float32 [N,P,5] and
+        status int32 [N,P]: the results, required.  counts: optional int32 [N].  status_in: optional int32 [N,P]; a slot whose word
+        is non-zero is not refined: zero record, the word handed on.  factor 1 .. 4: the points are those of decimate_enqueue(frames,
+        factor) and go to full resolution as x * factor + (factor - 1) / 2 in float32 first."""
+        import torch
+        fmt, n, w, h, rs, fs = self._strided_frames(frames, format)
+        dev = frames.device
+
+        def tensor(t, dtype, shape, what):
+            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == shape and t.device == dev):
+                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s tensor %s on the frames' device" % (what, dtype, shape))
+            return t.data_ptr()
+
+        if not (getattr(points, "is_cuda", False) and points.dtype == torch.float32 and points.dim() == 3 and points.shape[0] == n
+                and points.shape[1] > 0 and points.shape[2] >= 2 and points.stride(2) == 1 and points.stride(1) >= 2
+                and (n == 1 or points.stride(0) == points.shape[1] * points.stride(1)) and points.device == dev):
+            raise AgxError(_ffi.AGX_ERR_ARG, "points must be a float32 device tensor [N, P, K >= 2] whose rows are evenly spaced")
+        ppf = int(points.shape[1])
+        p_counts = tensor(counts, torch.int32, (n,), "counts") if counts is not None else None
+        p_in = tensor(status_in, torch.int32, (n, ppf), "status_in") if status_in is not None else None
+        p_out, p_status = tensor(out, torch.float32, (n, ppf, 5), "out"), tensor(status, torch.int32, (n, ppf), "status")
+        self._follow_torch_stream(frames)
+        self._enqueued(self._lib.agx_refine_windows_enqueue(self._h, frames.data_ptr(), n, w, h, rs, fs, fmt, points.data_ptr(),
+                                                            points.stride(1) * 4, ppf, p_counts, p_in, p_out, p_status, int(factor),
+                                                            int(half_size_patch)))
+
     # ---- try_decode_quad of caller-given quads (src/detector.rs:448-476) --------------------
     def decode_quads(self, image, quads, format=None, with_bits=False):
         """try_decode_quad of every quad of `quads` (n x 4 corners (x, y), any array that reshapes to [n, 8]) on a host image
@@ -1286,6 +1317,25 @@ class TagDetector:
                                                    int(border)))
         return out
 
+    def decimate_enqueue(self, frames, factor, out=None):
+        """decimate (the host form says what is computed) of a device batch [N, H, W] uint8 / 16-bit by `factor` in 2 .. 4 into out
+        [N, H // factor, W // factor] of the same dtype (made if None), stream-ordered behind torch's current stream; nothing to
+        fetch.  frames and out may be views with padded rows and frames.  -> out."""
+        import torch
+        fmt, px = self._gray_batch(frames, "frames")
+        f = int(factor)
+        n, dh, dw = int(frames.shape[0]), int(frames.shape[1]) // max(f, 1), int(frames.shape[2]) // max(f, 1)
+        if out is None:
+            out = torch.empty((n, max(dh, 1), max(dw, 1)), dtype=frames.dtype, device=frames.device)  # (a side of 0: the library refuses)
+        elif self._gray_batch(out, "out")[0] != fmt or tuple(out.shape) != (n, dh, dw) or out.device != frames.device:
+            raise AgxError(_ffi.AGX_ERR_ARG, "out must be a tensor [N, H // factor, W // factor] of the frames' dtype on their device")
+        self._follow_torch_stream(frames)
+        rs = lambda t: (t.stride(1) if t.shape[1] > 1 else t.shape[2]) * px  # (a lone row or frame has no stride of its own)
+        fs = lambda t: (t.stride(0) * px if t.shape[0] > 1 else rs(t) * t.shape[1])
+        self._enqueued(self._lib.agx_decimate_enqueue(self._h, frames.data_ptr(), n, int(frames.shape[2]), int(frames.shape[1]), rs(frames), fs(frames),
+                                                      fmt, f, out.data_ptr(), rs(out), fs(out)))
+        return out
+
     def rectified_points_enqueue(self, points, camera, new_camera, rotation=None, out=None):
         """rectified_points (the host form says what is computed) on the device, stream-ordered behind torch's current stream;
         nothing to fetch.  points: a contiguous float32 device tensor [..., 2] -> out of the same shape (made if None; out = points
@@ -1648,6 +1698,45 @@ class TagDetector:
         self.sync()
         return self._staged_result("detect_staged", cstatus, int(clusters_per_frame), tags, ntags, tst)
 
+    def detect_decimated(self, frames, factor=2, fine_half_size_patch=None, clusters_per_frame=4096, quads_per_frame=128, tags_per_frame=None,
+                         format=None, decode_model="affine", return_saddles=False):
+        """detect, coarse to fine (AprilTag's quad_decimate with a refine at full resolution): the frames -- a device tensor [N,H,W]
+        uint8 / 16-bit -- are averaged down by `factor` in 2 .. 4 (decimate_enqueue); detect_staged's planes, clusters and refine
+        run on that coarse batch, 1 / factor^2 of the pixels and of the workspace; refine_windows_enqueue then refines every coarse
+        saddle on the FULL frames at fine_half_size_patch (None: the handle's half_size_patch), reading the coarse records in place
+        with the coarse point status handed on and the points taken to full resolution by its factor=; the k / phi filter and
+        detect_staged's rounds -- find boards, decode on the full-resolution frames, collect -- follow.  No plane of the full size
+        is made.  The remaining keywords are detect_staged's.  factor=1 is detect_staged itself.
+        -> detect_staged's structure, the corners in full-resolution pixels; with return_saddles also (records, counts, status),
+        the fine saddle lists as device tensors."""
+        import torch
+        if int(factor) == 1:
+            if return_saddles:
+                raise AgxError(_ffi.AGX_ERR_ARG, "factor=1 is detect_staged, which returns no saddle lists")
+            return self.detect_staged(frames, clusters_per_frame, quads_per_frame, tags_per_frame, format, decode_model)
+        if format is not None and format != self._gray_batch(frames, "frames")[0]:
+            raise AgxError(_ffi.AGX_ERR_FORMAT, "detect_decimated at factor > 1 takes AGX_L8 / AGX_L16 frames [N, H, W]")
+        self._gray_batch(frames, "frames")
+        if not frames.is_contiguous():
+            raise AgxError(_ffi.AGX_ERR_ARG, "frames must be a contiguous device tensor")
+        n, h, w = (int(v) for v in frames.shape)
+        cpf, qpf = int(clusters_per_frame), int(quads_per_frame)
+        if tags_per_frame is None:
+            n_codes = C.c_int(0)
+            self._check(self._lib.agx_detector_family_info(self._h, None, None, None, None, C.byref(n_codes)))
+            tags_per_frame = n_codes.value
+        half = self.half_size_patch if fine_half_size_patch is None else int(fine_half_size_patch)
+        coarse = self.decimate_enqueue(frames, factor)
+        crec, counts, cpst, cstatus = self._staged_saddles(coarse, n, int(coarse.shape[2]), int(coarse.shape[1]), cpf, None, filtered=False)
+        records, pstatus = torch.zeros_like(crec), torch.zeros_like(cpst)
+        self.refine_windows_enqueue(frames, crec, records, pstatus, counts=counts, status_in=cpst, factor=factor, half_size_patch=half)
+        self.filter_saddles_enqueue(records, pstatus, counts=counts)
+        listed = pstatus.clone() if return_saddles else None
+        tags, ntags, tst = self._staged_rounds(frames, n, w, h, records, counts, pstatus, cpf, qpf, int(tags_per_frame), None, decode_model)
+        self.sync()
+        out = self._staged_result("detect_decimated", cstatus, cpf, tags, ntags, tst)
+        return (out, (records, counts, listed)) if return_saddles else out
+
     def _staged_tables(self, frames, clusters_per_frame, quads_per_frame, tags_per_frame, format, decode_model, keep_listed=False):
         """detect_staged's chain and rounds, enqueued -> ((records, counts, listed point status), cluster status, tags, n_tags,
         tag_status): device tensors, complete in stream order.  keep_listed: the point status words as the k / phi filter left
@@ -1666,6 +1755,15 @@ class TagDetector:
         i32 = dict(dtype=torch.int32, device=dev)
         records, counts, pstatus, cstatus = self._staged_saddles(frames, n, w, h, cpf, format)
         listed = pstatus.clone() if keep_listed else None
+        tags, ntags, tst = self._staged_rounds(frames, n, w, h, records, counts, pstatus, cpf, qpf, tpf, format, decode_model)
+        return (records, counts, listed), cstatus, tags, ntags, tst
+
+    def _staged_rounds(self, frames, n, w, h, records, counts, pstatus, cpf, qpf, tpf, format, decode_model):
+        """max_num_of_boards rounds of find boards -> decode on `frames` -> collect over the saddle lists (records, counts, pstatus:
+        _staged_saddles'), enqueued -> (tags, n_tags, tag_status), device tensors."""
+        import torch
+        dev = frames.device
+        i32 = dict(dtype=torch.int32, device=dev)
         quads, qpts = torch.zeros((n, qpf, 4), **i32), torch.zeros((n, qpf, 4, 2), dtype=torch.float32, device=dev)
         nq, bst = torch.zeros(n, **i32), torch.zeros(n, **i32)
         qtags, qst = torch.zeros((n, qpf, 9), **i32), torch.zeros((n, qpf), **i32)
@@ -1688,7 +1786,7 @@ class TagDetector:
                 self.best_tag_enqueue(sbits, sids, srots, qst, counts=nq, status_in=qst, quads=qpts, tags=qtags)
             self.collect_tags_enqueue(quads, nq, bst, qtags, qst, pstatus if r + 1 < rounds else None, tags, ntags, tst, reset=r == 0,
                                       saddles_per_frame=cpf)
-        return (records, counts, listed), cstatus, tags, ntags, tst
+        return tags, ntags, tst
 
     def recover_tags_enqueue(self, frames, saddles, counts, point_status, tags, n_tags, tag_status, cols, rows, first_id=0, spacing_ratio=0.3,
                              max_dist=3.0, max_err=2.0, max_drop=4, min_tags=2, format=None, camera=None, tag_size=1.0, iterations=10):
@@ -1783,9 +1881,9 @@ class TagDetector:
                          "err_sq": host["err_sq"][f, :k].copy() if good else None})
         return out, fits
 
-    def _staged_saddles(self, frames, n, w, h, cpf, format):
+    def _staged_saddles(self, frames, n, w, h, cpf, format, filtered=True):
         """The staged chain up to the saddle lists: planes at the handle's sigma, clusters, refine on the blur plane at the
-        handle's half_size_patch, the k / phi filter -> (records float32 [N, cpf, 5], counts int32 [N], point status int32 [N, cpf],
+        handle's half_size_patch, the k / phi filter (filtered=False: not that) -> (records float32 [N, cpf, 5], counts int32 [N], point status int32 [N, cpf],
         cluster status int32 [N]), device tensors as find_boards_enqueue reads them."""
         import torch
         dev = frames.device
@@ -1798,7 +1896,8 @@ class TagDetector:
         self.planes_enqueue(frames, self.blur_sigma, blur=blur, response=resp, format=format)
         self.clusters_enqueue(resp, clusters=rows, points=pts, counts=counts, status=cstatus)
         self.refine_points_enqueue(blur, pts, counts=counts, out=records, status=pstatus, image="plane", half_size_patch=self.half_size_patch)
-        self.filter_saddles_enqueue(records, pstatus, counts=counts)
+        if filtered:
+            self.filter_saddles_enqueue(records, pstatus, counts=counts)
         return records, counts, pstatus, cstatus
 
     def _staged_result(self, who, cstatus, cpf, tags, ntags, tst, skip=None):
@@ -2403,6 +2502,32 @@ def remap(image, map, border=0, out=None):
     fs = lambda t: t.strides[0] if t.shape[0] > 1 else rs(t) * t.shape[1]
     st = _ffi.lib().agx_remap_tail(a.ctypes.data, n, a.shape[2], a.shape[1], rs(a), fs(a), fmt, m.ctypes.data, m.strides[0] if dh > 1 else 8 * dw, dw, dh,
                                    res.ctypes.data, rs(res), fs(res), int(border))
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    if out is not None:
+        return out
+    return res[0] if lone else res
+
+
+def decimate(image, factor, out=None):
+    """image ([H, W] or [N, H, W], uint8 or uint16; rows and frames may be padded views) averaged down by `factor` in 2 .. 4 without
+    a device (agx_decimate_tail): out(X, Y) = (sum of the factor x factor pixels at (factor X + dx, factor Y + dy) + factor^2 // 2)
+    // factor^2 -- integers only, round half up; trailing columns and rows are dropped.  The centre of out(X, Y) is the image
+    position (factor X + (factor - 1) / 2, factor Y + (factor - 1) / 2): what refine_windows_enqueue's factor= undoes.
+    -> [H // factor, W // factor] or [N, H // factor, W // factor] of the image's dtype (out: the caller's array of that shape, rows
+    and frames may be padded)."""
+    a, fmt, px, lone = _gray_host(image, "image")
+    f = int(factor)
+    n, dh, dw = a.shape[0], a.shape[1] // max(f, 1), a.shape[2] // max(f, 1)
+    if out is None:
+        res = np.empty((n, max(dh, 1), max(dw, 1)), a.dtype)  # (an output side of 0 is the library's to refuse)
+    else:
+        res = _gray_host(out, "out")[0]
+        if res.dtype != a.dtype or res.shape != (n, dh, dw):
+            raise AgxError(_ffi.AGX_ERR_ARG, "out must have the image's dtype and the shape [N, H // factor, W // factor]")
+    rs = lambda t: t.strides[1] if t.shape[1] > 1 else t.shape[2] * px  # (a lone row or frame has no stride of its own)
+    fs = lambda t: t.strides[0] if t.shape[0] > 1 else rs(t) * t.shape[1]
+    st = _ffi.lib().agx_decimate_tail(a.ctypes.data, n, a.shape[2], a.shape[1], rs(a), fs(a), fmt, f, res.ctypes.data, rs(res), fs(res))
     if st != _ffi.AGX_OK:
         raise AgxError(st)
     if out is not None:

@@ -453,6 +453,18 @@ extern "C" {
                                   first_id: u32, spacing_ratio: c_float, tag_size: c_double, lens_model: c_int, camera: *const c_double,
                                   pose: *const c_double, params: *const c_void, frame: *mut c_void, truth: *mut agx_tag, n_truth: *mut u32,
                                   status: *mut u32) -> c_int;
+    // coarse to fine: the batch averaged down by `factor`, and rochade_refine on the blur of the full frames with every point's blur
+    // window computed from the input (no blur plane); its `factor` takes a point of the decimated frame to full resolution
+    pub fn agx_decimate_enqueue(det: *mut agx_detector, d_src: *const c_void, n_frames: c_int, width: c_int, height: c_int,
+                                row_stride_bytes: usize, frame_stride_bytes: usize, format: c_int, factor: c_int, d_dst: *mut c_void,
+                                dst_row_stride_bytes: usize, dst_frame_stride_bytes: usize) -> c_int;
+    pub fn agx_decimate_tail(src: *const c_void, n_frames: c_int, width: c_int, height: c_int, row_stride_bytes: usize,
+                             frame_stride_bytes: usize, format: c_int, factor: c_int, dst: *mut c_void, dst_row_stride_bytes: usize,
+                             dst_frame_stride_bytes: usize) -> c_int;
+    pub fn agx_refine_windows_enqueue(det: *mut agx_detector, d_frames: *const c_void, n_frames: c_int, width: c_int, height: c_int,
+                                      row_stride_bytes: usize, frame_stride_bytes: usize, format: c_int, d_points: *const c_void,
+                                      point_stride_bytes: usize, points_per_frame: u32, d_counts: *const u32, d_status_in: *const u32,
+                                      d_out: *mut agx_saddle, d_status: *mut u32, factor: c_int, half_size_patch: c_int) -> c_int;
     pub fn agx_debug_blur_weights(sigma: c_float, weights: *mut c_float, cap: c_int, radius: *mut c_int) -> c_int;
     pub fn agx_debug_refine_constants(half_size_patch: c_int, cone: *mut c_float, pmat: *mut c_float, cap_points: c_int,
                                       n_points: *mut c_int) -> c_int;

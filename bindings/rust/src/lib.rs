@@ -950,6 +950,23 @@ pub fn remap_tail(frame: &[u8], src: (u32, u32), map: &[[i32; 2]], dst: (u32, u3
     out
 }
 
+/// One tightly packed L8 frame of `src` = (w, h) averaged down by `factor` in 2 .. 4, the host form: every output pixel the mean
+/// of its `factor` x `factor` source pixels in integers, round half up; `(w / factor, h / factor)` pixels, row major.  The centre of
+/// output pixel `(X, Y)` is the source position `(factor X + (factor - 1) / 2, factor Y + (factor - 1) / 2)`.  Panics where the
+/// library refuses the arguments.
+pub fn decimate_tail(frame: &[u8], src: (u32, u32), factor: u32) -> Vec<u8> {
+    assert_eq!(frame.len(), src.0 as usize * src.1 as usize, "decimate_tail: frame is not w * h bytes");
+    assert!((2..=4).contains(&factor) && src.0 >= factor && src.1 >= factor, "decimate_tail: factor must be in 2 .. 4 and no larger than a side");
+    let (dw, dh) = ((src.0 / factor) as usize, (src.1 / factor) as usize);
+    let mut out = vec![0u8; dw * dh];
+    let st = unsafe {
+        ffi::agx_decimate_tail(frame.as_ptr() as *const std::os::raw::c_void, 1, src.0 as c_int, src.1 as c_int, src.0 as usize, frame.len(), ffi::AGX_L8,
+                               factor as c_int, out.as_mut_ptr() as *mut std::os::raw::c_void, dw, out.len())
+    };
+    assert_eq!(st, ffi::AGX_OK, "agx_decimate_tail failed: {}", st);
+    out
+}
+
 /// Points of the rectified image to the sensor pixels they come from, the host form: the map's ray, rotation and projection in
 /// binary64, rounded to `f32`; `(NaN, NaN)` where the ray has no projection.  Panics where the library refuses the arguments.
 pub fn rectified_points_tail(model: LensModel, camera: &Camera, rect: &Rectification, points: &[(f32, f32)]) -> Vec<(f32, f32)> {

@@ -438,6 +438,52 @@ int agx_rochade_refine(agx_detector *det, const void *pixels, int width, int hei
 int agx_rochade_refine_h(agx_detector *det, const void *pixels, int width, int height, size_t row_stride_bytes, int format,
                          int image, const void *points, uint32_t n_points, agx_saddle *out, uint32_t *status,
                          uint32_t *n_refined, int half_size_patch);
+/* THE WINDOWED REFINE (k_refine_windows): agx_refine_points_enqueue_h(.., AGX_REFINE_BLURRED, ..) without its blur plane.  Every
+ * pixel of gaussian_blur_f32 (src/image_util.rs:110-206) is a function of the input alone, so the (4h+1)^2 blur window of a point
+ * is computed from the (4h+1+2r)^2 input pixels around it, r = ceil(2 sigma) at the handle's sigma, clamped to the frame: no
+ * plane is allocated, written or read, and the cost follows the points, not the pixels.  Every record and status word equals,
+ * byte for byte, what agx_refine_points_enqueue_h writes for the same full-resolution points on the same frames.
+ * d_frames / n_frames / width / height / strides as agx_refine_points_enqueue; format AGX_L8, AGX_L16 (pointer and strides 2-byte
+ * aligned) or AGX_LF32 (refined on its blur, unlike AGX_REFINE_PLANE); any other is AGX_ERR_FORMAT.  Slot s = f points_per_frame
+ * + i reads two floats (x, y) at (char *)d_points + s point_stride_bytes: agx_point rows (8) and agx_saddle records (20) are
+ * both read in place.  d_counts as agx_refine_points_enqueue.  d_status_in (optional, [n_frames points_per_frame]): a slot whose
+ * word is non-zero is not refined -- its record is five zero floats and its status the word handed on, as the decode stages hand
+ * status on.  factor in 1 .. 4: the point (x, y) of a frame decimated by `factor` (agx_decimate_enqueue) is taken to full
+ * resolution as x * (float)factor + 0.5f * (factor - 1), one rounded multiply and one rounded add in binary32, the same for y;
+ * at 1 the point is taken as it is.  AGX_POINT_OUTSIDE is decided in float before anything is read, by agx_refine_points_enqueue's
+ * rule.  d_out and d_status: caller-owned device memory, required.  In place (d_out = d_points at a stride of 20, d_status =
+ * d_status_in) is allowed: a slot is read before it is written and by no other slot.  Stream-ordered, nothing to fetch; a batch
+ * in flight is replaced as by agx_board_fit_enqueue.
+ * AGX_ERR_ARG (a batch in flight stays where it is): a NULL d_frames, d_points, d_out or d_status; points_per_frame == 0;
+ * half_size_patch outside 1 .. 4; factor outside 1 .. 4; point_stride_bytes below 8 or no multiple of 4; a misaligned array;
+ * agx_refine_points_enqueue's rules on the frames. */
+int agx_refine_windows_enqueue(agx_detector *det, const void *d_frames, int n_frames, int width, int height,
+                               size_t row_stride_bytes, size_t frame_stride_bytes, int format,
+                               const void *d_points, size_t point_stride_bytes, uint32_t points_per_frame,
+                               const uint32_t *d_counts, const uint32_t *d_status_in,
+                               agx_saddle *d_out, uint32_t *d_status, int factor, int half_size_patch);
+
+/* ---- decimated batches (csrc/decimate.hip; csrc/decimate_math.h) ------------------------- */
+
+/* A batch of AGX_L8 or AGX_L16 frames averaged down by an integer factor f in 2 .. 4 (k_decimate): AprilTag's quad_decimate, the
+ * first half of a coarse-to-fine detect (agx_refine_windows_enqueue's `factor` is the second).  d_dst: n_frames frames of
+ * floor(width / f) x floor(height / f) in the same format with their own strides; trailing source columns and rows are dropped.
+ *   out(X, Y) = (sum of the f x f source pixels at (f X + dx, f Y + dy) + f f / 2) / (f f)      in uint32
+ * -- the mean, round half up.  No floating-point operation in the kernel or in the host form.  The centre of output pixel (X, Y)
+ * is the source position (f X + (f - 1) / 2, f Y + (f - 1) / 2).  Nothing outside the source rows' width pixels is read, nothing
+ * outside the destination rows' floor(width / f) pixels is written.  Caller-owned device memory, stream-ordered, nothing to
+ * fetch; a batch in flight is replaced as by agx_board_fit_enqueue.  Source and destination must not overlap.
+ * AGX_ERR_FORMAT: a format other than AGX_L8 and AGX_L16 (the luma front is not part of this).  AGX_ERR_ARG (a batch in flight
+ * stays where it is): a NULL array; n_frames outside 1 .. 65535; f outside 2 .. 4; width or height below f (an output side of
+ * 0) or above 65000, or a frame of 2^30 px or more; a row stride that does not cover a row or is 2^31 or more, a frame stride
+ * (n_frames > 1) that does not cover a frame; AGX_L16 pointers or strides that are odd.
+ * agx_decimate_tail: the host form -- no handle, no device, the same bytes. */
+int agx_decimate_enqueue(agx_detector *det, const void *d_src, int n_frames, int width, int height,
+                         size_t row_stride_bytes, size_t frame_stride_bytes, int format, int factor,
+                         void *d_dst, size_t dst_row_stride_bytes, size_t dst_frame_stride_bytes);
+int agx_decimate_tail(const void *src, int n_frames, int width, int height,
+                      size_t row_stride_bytes, size_t frame_stride_bytes, int format, int factor,
+                      void *dst, size_t dst_row_stride_bytes, size_t dst_frame_stride_bytes);
 
 /* ---- decode of caller-given quads -------------------------------------------------------- */
 
