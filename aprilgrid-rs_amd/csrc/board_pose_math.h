@@ -64,7 +64,8 @@
 //   w1 = alpha / (1 - alpha) for alpha <= 0.5, else (1 - alpha) / alpha;   w2 = (w1 + xi) / pose_sqrt(2 w1 xi + xi xi + 1).
 // w2 depends on the camera only.  pose_camera() computes it once per call, on the host, for the kernel and the host form alike,
 // and hands the functions below a camera whose k3 (the ninth double, 0 in the caller's) holds it: no function below is given a
-// double-sphere camera that did not come through pose_camera().
+// double-sphere camera that did not come through pose_camera().  (The calibration, calib_math.h, moves the camera on the device:
+// pose_camera() is callable there, and every iterate's camera goes through it.)
 // Jacobian m = d(u, v) / d(Xc, Yc, Zc), in closed form (x = Xc / Zc does not exist where Zc <= 0):  a = xi / d1,  b = alpha / d2,
 //   s = b (1 + k a) + (1 - alpha) a  (d den / d Xc = Xc s, d den / d Yc = Yc s),  dz = (a Zc + 1) (b k + (1 - alpha))  (d den / d Zc),
 //   id = 1 / den;   m00 = fx id (1 - mx (Xc s)),  m01 = -(fx id (mx (Yc s))),  m02 = -(fx id (mx dz)),
@@ -167,7 +168,7 @@ using PosePointOf = std::conditional_t<LENS == AGX_LENS_DOUBLE_SPHERE, PosePoint
 
 // the camera as the functions below read it: the caller's, and under AGX_LENS_DOUBLE_SPHERE its k3 holds w2, the valid cone's
 // Zc / d1 (once per call, on the host, for both forms; the caller's camera has passed pose_args_ok)
-inline agx_camera pose_camera(int lens, const agx_camera &c)
+AGX_HD agx_camera pose_camera(int lens, const agx_camera &c)
 {
     agx_camera o = c;
     if (lens == AGX_LENS_DOUBLE_SPHERE) {
@@ -417,14 +418,11 @@ AGX_HD void pose_ds_jacobian(const agx_camera &c, const PosePointDs &q, double &
     m12 = -(gi * (q.my * dz));
 }
 
+// the 2 x 6 Jacobian of a projected correspondence by (w, dt): ja[0 .. 6) the row of u, jb[0 .. 6) the row of v (one text for
+// pose_accumulate and calib_math.h's calib_row)
 template <int LENS = AGX_LENS_RADTAN>
-AGX_HD void pose_accumulate(const agx_camera &c, const Pose &p, double acc[POSE_SUMS], double X, double Y, double uo, double vo)
+AGX_HD void pose_jacobian_rows(const agx_camera &c, const Pose &p, const PosePointOf<LENS> &q, double X, double Y, double *ja, double *jb)
 {
-    PosePointOf<LENS> q;
-    double eu = 0.0, ev = 0.0;
-    const double e = pose_error<LENS>(c, p, X, Y, uo, vo, q, eu, ev);
-    acc[27] += e;
-    if (!(e < __builtin_inf())) return;
     double m00, m01, m02, m10, m11, m12;  // d(u, v) / d(Xc, Yc, Zc)
     if constexpr (LENS == AGX_LENS_DOUBLE_SPHERE) {
         pose_ds_jacobian(c, q, m00, m01, m02, m10, m11, m12);
@@ -439,8 +437,24 @@ AGX_HD void pose_accumulate(const agx_camera &c, const Pose &p, double acc[POSE_
     const double g00 = Y * p.R[2], g10 = Y * p.R[5], g20 = Y * p.R[8];
     const double g01 = -(X * p.R[2]), g11 = -(X * p.R[5]), g21 = -(X * p.R[8]);
     const double g02 = X * p.R[1] - Y * p.R[0], g12 = X * p.R[4] - Y * p.R[3], g22 = X * p.R[7] - Y * p.R[6];
-    const double ja[7] = {m00 * g00 + m01 * g10 + m02 * g20, m00 * g01 + m01 * g11 + m02 * g21, m00 * g02 + m01 * g12 + m02 * g22, m00, m01, m02, eu};
-    const double jb[7] = {m10 * g00 + m11 * g10 + m12 * g20, m10 * g01 + m11 * g11 + m12 * g21, m10 * g02 + m11 * g12 + m12 * g22, m10, m11, m12, ev};
+    ja[0] = m00 * g00 + m01 * g10 + m02 * g20, ja[1] = m00 * g01 + m01 * g11 + m02 * g21, ja[2] = m00 * g02 + m01 * g12 + m02 * g22;
+    ja[3] = m00, ja[4] = m01, ja[5] = m02;
+    jb[0] = m10 * g00 + m11 * g10 + m12 * g20, jb[1] = m10 * g01 + m11 * g11 + m12 * g21, jb[2] = m10 * g02 + m11 * g12 + m12 * g22;
+    jb[3] = m10, jb[4] = m11, jb[5] = m12;
+}
+
+template <int LENS = AGX_LENS_RADTAN>
+AGX_HD void pose_accumulate(const agx_camera &c, const Pose &p, double acc[POSE_SUMS], double X, double Y, double uo, double vo)
+{
+    PosePointOf<LENS> q;
+    double eu = 0.0, ev = 0.0;
+    const double e = pose_error<LENS>(c, p, X, Y, uo, vo, q, eu, ev);
+    acc[27] += e;
+    if (!(e < __builtin_inf())) return;
+    double ja[7], jb[7];
+    pose_jacobian_rows<LENS>(c, p, q, X, Y, ja, jb);
+    ja[6] = eu;
+    jb[6] = ev;
     int k = 0;
 #pragma unroll
     for (int i = 0; i < 6; ++i)

@@ -19,6 +19,7 @@
 #include "board_fit_math.h"
 #include "board_pose.h"
 #include "board_pose_math.h"
+#include "calibrate.h"
 #include "chain_kernels.h"
 #include "decimate.h"
 #include "decode_math.h"
@@ -2480,6 +2481,81 @@ int agx_debug_pose_project(int lens_model, const double *camera, const double *x
     std::memcpy(&cam, camera, sizeof cam);
     if (!pose_args_ok(lens_model, cam, 1.0, 0)) return AGX_ERR_ARG;
     pose_project_host(lens_model, cam, xyz, n, uv);
+    return AGX_OK;
+    });
+}
+
+// ---- the camera from the batch (calibrate.hip: k_calib_blocks, k_calib_solve; calibrate_host.cpp) -------------------------------
+static CalibArgs calib_record(int n_frames, const agx_tag *tags, uint32_t tags_per_frame, const uint32_t *n_tags, const uint32_t *tag_status, uint32_t cols,
+                              uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size, const double *camera, uint32_t fixed_mask,
+                              double damping, uint32_t iterations, uint32_t min_tags, uint32_t min_frames, int flags, const double *pose_in,
+                              const uint32_t *row_status, const uint32_t *fit_status, double *camera_out, double *pose, float *frame_cost,
+                              uint32_t *frame_n, void *report)
+{
+    agx_camera cam;
+    std::memcpy(&cam, camera, sizeof cam);
+    return CalibArgs{n_frames, tags, tags_per_frame, n_tags, tag_status, cols, rows, first_id, spacing_ratio, tag_size, cam, fixed_mask, damping,
+                     iterations, min_tags, min_frames, flags, pose_in, row_status, fit_status, camera_out, pose, frame_cost, frame_n,
+                     static_cast<agx_calib_report *>(report)};
+}
+
+int agx_calibrate_enqueue(agx_detector *det, int n_frames, const agx_tag *d_tags, uint32_t tags_per_frame, const uint32_t *d_n_tags,
+                          const uint32_t *d_tag_status, uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
+                          int lens_model, const double *camera, uint32_t fixed_mask, double damping, uint32_t iterations, uint32_t min_tags,
+                          uint32_t min_frames, int flags, const double *d_pose_in, const uint32_t *d_row_status, const uint32_t *d_fit_status,
+                          double *d_camera, double *d_pose, float *d_frame_cost, uint32_t *d_frame_n, void *d_report)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    if (!camera) return fail(det, AGX_ERR_ARG, "a null camera");
+    const CalibArgs a = calib_record(n_frames, d_tags, tags_per_frame, d_n_tags, d_tag_status, cols, rows, first_id, spacing_ratio, tag_size, camera,
+                                     fixed_mask, damping, iterations, min_tags, min_frames, flags, d_pose_in, d_row_status, d_fit_status, d_camera,
+                                     d_pose, d_frame_cost, d_frame_n, d_report);
+    if (const char *why = calib_args_bad(a, lens_model)) return fail(det, AGX_ERR_ARG, why);
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // and there is nothing of this one to be fetched
+    void *work = side_ensure(det, SB_CALIB_WORK, calib_work_bytes(n_frames), 0);
+    if (!work) return fail(det, AGX_ERR_NOMEM, "the calibration's workspace");
+    const hipError_t e = (hipError_t)launch_calibrate(a, lens_model, work, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_calib_blocks / k_calib_solve: ") + hipGetErrorString(e));
+    return AGX_OK;
+    });
+}
+
+int agx_calibrate_tail(int n_frames, const agx_tag *tags, uint32_t tags_per_frame, const uint32_t *n_tags, const uint32_t *tag_status, uint32_t cols,
+                       uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size, int lens_model, const double *camera,
+                       uint32_t fixed_mask, double damping, uint32_t iterations, uint32_t min_tags, uint32_t min_frames, int flags,
+                       const double *pose_in, const uint32_t *row_status, const uint32_t *fit_status, double *camera_out, double *pose,
+                       float *frame_cost, uint32_t *frame_n, void *report)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (!camera) return AGX_ERR_ARG;
+    const CalibArgs a = calib_record(n_frames, tags, tags_per_frame, n_tags, tag_status, cols, rows, first_id, spacing_ratio, tag_size, camera, fixed_mask,
+                                     damping, iterations, min_tags, min_frames, flags, pose_in, row_status, fit_status, camera_out, pose, frame_cost,
+                                     frame_n, report);
+    if (calib_args_bad(a, lens_model)) return AGX_ERR_ARG;
+    calibrate_host(a, lens_model);
+    return AGX_OK;
+    });
+}
+
+int agx_calibrate_seed_tail(const double *h, const uint32_t *fit_status, uint32_t n, int img_w, int img_h, double *camera_out, uint32_t *status)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (!h || !fit_status || !camera_out || !status || !n || img_w < 1 || img_h < 1) return AGX_ERR_ARG;
+    *status = calibrate_seed_host(h, fit_status, n, img_w, img_h, camera_out);
+    return AGX_OK;
+    });
+}
+
+int agx_debug_calib_param_jacobian(int lens_model, const double *camera, const double *xyz, uint32_t n, double *out)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (!camera || (n && (!xyz || !out))) return AGX_ERR_ARG;
+    agx_camera cam;
+    std::memcpy(&cam, camera, sizeof cam);
+    if (!pose_args_ok(lens_model, cam, 1.0, 0)) return AGX_ERR_ARG;
+    calib_param_jacobian_host(lens_model, cam, xyz, n, out);
     return AGX_OK;
     });
 }

@@ -201,6 +201,7 @@ enum {
     SB_CLUSTERS_COUNTS,  // ... [n_frames] uint32 ...
     SB_CLUSTERS_STATUS,  // ... and [n_frames] uint32 (AGX_CLUSTERS_*)
     SB_CLUSTERS_PLANE,   // agx_cluster_centers: the host's plane on the device
+    SB_CALIB_WORK,       // agx_calibrate_enqueue: the state, the frames' blocks and poses between its launches (calibrate.h: CalibWork)
     SB_COUNT
 };
 }  // namespace agx

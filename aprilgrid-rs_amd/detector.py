@@ -1258,6 +1258,105 @@ class TagDetector:
             self._replaces_batch()
         self._check(rc)
 
+    # ---- the camera from the batch (agx_calibrate_enqueue) ---------------------------------------------------------------------
+    @staticmethod
+    def calibrate(tags, n_tags, cols, rows, camera, poses, row_status, fit_status, **kw):
+        """The host form, no device needed: the module's calibrate."""
+        return calibrate(tags, n_tags, cols, rows, camera, poses, row_status, fit_status, **kw)
+
+    @staticmethod
+    def calibrate_seed(h, fit_status, img_size):
+        """The closed-form seed, host only: the module's calibrate_seed."""
+        return calibrate_seed(h, fit_status, img_size)
+
+    def calibrate_enqueue(self, tags, n_tags, cols, rows, camera, pose_in, row_status, fit_status, camera_out, pose, frame_cost, frame_n, report,
+                          tag_size=1.0, first_id=0, spacing_ratio=0.3, fixed=0, damping=0.0, iterations=10, min_tags=1, min_frames=1,
+                          accept_loose=False, tag_status=None):
+        """The camera's nine doubles and every usable frame's pose from a batch of tag tables (calibrate, the host form, says what
+        is computed), in device tensors and stream-ordered behind torch's current stream; nothing to fetch.  tags, n_tags,
+        tag_status as board_pose_enqueue's; pose_in float64 [N, 12], row_status int32 [N, T] and fit_status int32 [N] are its pose,
+        row_status and status, read in place.  camera: the seed (host).  camera_out float64 [9]; pose float64 [N, 12] (may be
+        pose_in); frame_cost float32 [N]; frame_n int32 [N]; report float64 [69], read with calib_report()."""
+        import torch
+        if not (getattr(tags, "is_cuda", False) and tags.dtype == torch.int32 and tags.is_contiguous() and tags.dim() == 3 and tags.shape[2] == 9
+                and tags.shape[1] > 0):
+            raise AgxError(_ffi.AGX_ERR_ARG, "tags must be a contiguous int32 device tensor [N, T, 9]")
+        n, tpf, dev = int(tags.shape[0]), int(tags.shape[1]), tags.device
+
+        def tensor(t, dtype, shape, what, optional=False):
+            if t is None and optional:
+                return None
+            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == shape and t.device == dev):
+                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s tensor %s on the tags' device" % (what, dtype, shape))
+            return t.data_ptr()
+
+        ins = (tensor(n_tags, torch.int32, (n,), "n_tags"), tensor(tag_status, torch.int32, (n,), "tag_status", optional=True))
+        state = (tensor(pose_in, torch.float64, (n, 12), "pose_in"), tensor(row_status, torch.int32, (n, tpf), "row_status"),
+                 tensor(fit_status, torch.int32, (n,), "fit_status"))
+        outs = (tensor(camera_out, torch.float64, (9,), "camera_out"), tensor(pose, torch.float64, (n, 12), "pose"),
+                tensor(frame_cost, torch.float32, (n,), "frame_cost"), tensor(frame_n, torch.int32, (n,), "frame_n"),
+                tensor(report, torch.float64, (69,), "report"))
+        model, cam = _camera(camera)
+        self._follow_torch_stream(tags)
+        rc = self._lib.agx_calibrate_enqueue(self._h, n, tags.data_ptr(), tpf, *ins, int(cols), int(rows), int(first_id), float(spacing_ratio),
+                                             float(tag_size), model, cam, _fixed_mask(fixed), float(damping), int(iterations), int(min_tags),
+                                             int(min_frames), _ffi.AGX_CALIB_ACCEPT_LOOSE if accept_loose else 0, *state, *outs)
+        self._enqueued(rc)
+
+    def calibrate_batch(self, frames, cols, rows, tag_size=1.0, lens="radtan", camera=None, fixed=0, rounds=3, iterations=10, damping=None,
+                        first_id=0, spacing_ratio=0.3, cap=None, max_err_sq=4.0, max_drop=0, min_tags=1, min_frames=1, accept_loose=True,
+                        pose_iterations=10, format=None):
+        """A camera from a batch of frames resident on this detector's GPU, every stage on the device: detect_batch_enqueue(out=)
+        -> board_fit_enqueue -> calibrate_seed -> `rounds` x (board_pose_enqueue with its outlier rounds -> calibrate_enqueue).
+        camera: the seed; None: calibrate_seed's pinhole under the model `lens` names ("radtan", "equidistant" or "double_sphere";
+        a double-sphere seed is that pinhole at xi = 0, alpha = 0.5).  With a camera given, its own model counts and `lens` is
+        not read.  damping: None is 0, and 1e-6 under the double-sphere model (_seed_damping says why).
+        The frames' tables, poses and masks stay on the device.  Read back between the stages: the seed's homographies and status
+        words once; per round the nine doubles and the 552-byte report; at the end the pose call's status words and the frames'
+        corner counts for the report.
+        -> (Camera, poses float64 [N, 12] on the device (frames that were not usable keep the pose call's rows), report: the last
+        round's calib_report() with pose_status, the pose call's status words, and frame_n)."""
+        import torch
+        n, h, w = int(frames.shape[0]), int(frames.shape[-2] if frames.dim() == 3 else frames.shape[1]), int(frames.shape[-1] if frames.dim() == 3 else frames.shape[2])
+        n_board = int(cols) * int(rows)
+        cap = n_board if cap is None else int(cap)
+        dev = frames.device
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+        tags, counts, status = i32(n, cap, 9), i32(n), i32(n)
+        self.detect_batch_enqueue(frames, cap, out=(tags, counts, status), format=format)
+        self.detect_batch_fetch(raise_on_overflow=False)
+        err, rst, n_inl, rms, pred, n_pred, fst = f32(n, cap), i32(n, cap), i32(n), f32(n), i32(n, n_board, 9), i32(n), i32(n)
+        layout = dict(first_id=first_id, spacing_ratio=spacing_ratio)
+        if camera is None:
+            hs = f64(n, 9)
+            self.board_fit_enqueue(tags, counts, cols, rows, (w, h), hs, err, rst, n_inl, rms, pred, n_pred, fst, max_err_sq=max_err_sq,
+                                   max_drop=max_drop, min_tags=min_tags, tag_status=status, **layout)
+            torch.cuda.current_stream(dev).synchronize()
+            seed = calibrate_seed(hs.cpu().numpy(), fst.cpu().numpy().astype(np.uint32), (w, h))
+            if seed["status"] != _ffi.AGX_CALIB_OK:
+                raise AgxError(_ffi.AGX_ERR_STATE, "calibrate_batch: the seed is AGX_CALIB_%s" % ("FEW" if seed["status"] == _ffi.AGX_CALIB_FEW else "SINGULAR"))
+            camera = _lens_seed(lens, seed["camera"])
+        pose, best, cam_out, fcost, fn, rep = f64(n, 12), i32(n), f64(9), f32(n), i32(n), f64(69)
+        report, damping = None, _seed_damping(camera, damping)
+        for _ in range(int(rounds)):
+            self.board_pose_enqueue(tags, counts, cols, rows, camera, pose, err, rst, n_inl, rms, best, pred, n_pred, fst, tag_size=tag_size,
+                                    max_err_sq=max_err_sq, max_drop=max_drop, min_tags=min_tags, iterations=pose_iterations, tag_status=status,
+                                    **layout)
+            self.calibrate_enqueue(tags, counts, cols, rows, camera, pose, rst, fst, cam_out, pose, fcost, fn, rep, tag_size=tag_size, fixed=fixed,
+                                   damping=damping, iterations=iterations, min_tags=min_tags, min_frames=min_frames, accept_loose=accept_loose,
+                                   tag_status=status, **layout)
+            torch.cuda.current_stream(dev).synchronize()
+            report = calib_report(rep.cpu().numpy())
+            if report["status"] != _ffi.AGX_CALIB_OK:
+                break
+            camera = type(camera)(*cam_out.cpu().numpy().tolist()) if isinstance(camera, Camera) else Camera(*cam_out.cpu().numpy().tolist())
+        if report is not None:
+            report["pose_status"] = fst.cpu().numpy()
+            report["frame_n"] = fn.cpu().numpy()
+        return camera, pose, report
+
     # ---- rectified batches: the lens model applied to the pixels (csrc/rectify.hip) ------------------------------------------
     def _enqueued(self, rc):
         if rc == _ffi.AGX_OK:  # (a refused argument leaves the batch in flight where it is)
@@ -2429,6 +2528,133 @@ def board_pose(tags, cols, rows, camera, tag_size=1.0, first_id=0, spacing_ratio
                    pred=pred[:n_pred.value].copy())
         if return_iter_sums:
             out["iter_sums"] = sums
+    return out
+
+
+def _fixed_mask(fixed):
+    """fixed: the mask itself, or the held doubles by position 0 .. 8 or by Camera's field names -> the mask"""
+    if isinstance(fixed, (int, np.integer)):
+        mask = int(fixed)
+    else:
+        mask = 0
+        for f in fixed:
+            i = Camera._fields.index(f) if isinstance(f, str) and f in Camera._fields else f
+            if isinstance(i, str) or not 0 <= int(i) < 9:
+                raise AgxError(_ffi.AGX_ERR_ARG, "fixed names one of %s or a position 0 .. 8, got %r" % (", ".join(Camera._fields), f))
+            mask |= 1 << int(i)
+    if not 0 <= mask < 512:
+        raise AgxError(_ffi.AGX_ERR_ARG, "fixed must be a mask below 512")
+    return mask
+
+
+def _lens_seed(lens, pinhole):
+    """calibrate_seed's pinhole as the seed of the lens model `lens`"""
+    fx, fy, cx, cy = pinhole[:4]
+    if lens in ("radtan", _ffi.AGX_LENS_RADTAN):
+        return Camera(fx, fy, cx, cy)
+    if lens in ("equidistant", _ffi.AGX_LENS_EQUIDISTANT):
+        return Camera.equidistant(fx, fy, cx, cy)
+    if lens in ("double_sphere", _ffi.AGX_LENS_DOUBLE_SPHERE):
+        # near the axis den = (1 + xi) Z: at xi = 0 the focal length is fx itself, whatever alpha is.  At xi = 0 the undamped system
+        # of iterate 0 is refused (AGX_CALIB_SINGULAR): calibrate_batch steps from this seed under _seed_damping
+        return Camera.double_sphere(fx, fy, cx, cy, 0.0, 0.5)
+    raise AgxError(_ffi.AGX_ERR_ARG, "lens must be 'radtan', 'equidistant' or 'double_sphere', got %r" % (lens,))
+
+
+def _seed_damping(camera, damping):
+    """calibrate_batch's damping: the caller's, or by default 0 -- under the double-sphere model 1e-6, which carries the first step
+    off the set xi = 0 where the undamped reduced system is singular (Levenberg's factor 1 + 1e-6 on the diagonals slows the last
+    steps, it does not move the minimum: tests/test_calibrate_cpu.py measures the answer against scipy's)"""
+    if damping is not None:
+        return float(damping)
+    return 1e-6 if _camera(camera)[0] == _ffi.AGX_LENS_DOUBLE_SPHERE else 0.0
+
+
+def calib_report(report):
+    """agx_calib_report's 552 bytes (calibrate_enqueue's report tensor on the host) -> dict: status AGX_CALIB_*, best_iter,
+    iterations_run, n_frames_used, n_corners, rms, cost float64 [65] (NaN: an iterate that was not reached)."""
+    r = np.ascontiguousarray(report).view(np.uint8).reshape(-1)
+    if r.size != 552:
+        raise AgxError(_ffi.AGX_ERR_ARG, "a report is 552 bytes")
+    r = r.view(np.dtype(_ffi.CALIB_REPORT_DTYPE))[0]
+    return {"status": int(r["status"]), "best_iter": int(r["best_iter"]), "iterations_run": int(r["iterations_run"]),
+            "n_frames_used": int(r["n_frames_used"]), "n_corners": int(r["n_corners"]), "rms": float(r["rms"]), "cost": r["cost"].copy()}
+
+
+def calibrate(tags, n_tags, cols, rows, camera, poses, row_status, fit_status, tag_size=1.0, first_id=0, spacing_ratio=0.3, fixed=0, damping=0.0,
+              iterations=10, min_tags=1, min_frames=1, accept_loose=False, tag_status=None, raw=False):
+    """The host form of calibrate_enqueue (agx_calibrate_tail) without a device: the camera's nine doubles, under `camera`'s lens
+    model from `camera` as the seed, and every usable frame's pose, by `iterations` damped Gauss-Newton steps on the pixel residual
+    of all inlier corners with the poses eliminated frame by frame; the iterate of the lowest cost is the answer (iterate 0 is the
+    inputs).  tags: rows of TagDetector.TAG_DTYPE [N, T]; n_tags [N]; poses float64 [N, 12], row_status uint32 [N, T] and
+    fit_status uint32 [N]: board_pose's pose, row_status and status per frame.  A frame is usable iff its status is AGX_FIT_OK
+    (accept_loose: AGX_FIT_LOOSE too) and min_tags of its rows are AGX_FIT_ROW_INLIER.  fixed: a mask (bit i holds the i-th
+    double), or the held doubles by Camera's field names or positions.
+    -> dict: status AGX_CALIB_* and calib_report's fields; for AGX_CALIB_OK also camera (a Camera of the seed's model), pose
+    float64 [N, 12] (the input's rows where a frame was not usable), frame_cost float32 [N], frame_n uint32 [N].  raw: also the
+    output arrays as the call left them over guard values (camera_raw, pose_raw, ..., report_raw), for parity tests."""
+    t = np.ascontiguousarray(tags)
+    if t.dtype != TagDetector.TAG_DTYPE or t.ndim != 2:
+        raise AgxError(_ffi.AGX_ERR_ARG, "tags must be rows of TAG_DTYPE [N, T]")
+    n, tpf = int(t.shape[0]), int(t.shape[1])
+    cnt = np.ascontiguousarray(n_tags, np.uint32).reshape(-1)
+    pin = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+    rst = np.ascontiguousarray(row_status, np.uint32).reshape(n, -1)
+    fst = np.ascontiguousarray(fit_status, np.uint32).reshape(-1)
+    tst = None if tag_status is None else np.ascontiguousarray(tag_status, np.uint32).reshape(-1)
+    if not (cnt.shape[0] == n and pin.shape[0] == n and rst.shape[1] == tpf and fst.shape[0] == n and (tst is None or tst.shape[0] == n)):
+        raise AgxError(_ffi.AGX_ERR_ARG, "n_tags, poses, row_status, fit_status (and tag_status) must have one entry per frame of tags")
+    model, cam = _camera(camera)
+    cam_out = np.full(9, np.nan, np.float64)
+    pose = pin.copy()
+    cost, fn = np.full(max(n, 1), np.nan, np.float32), np.full(max(n, 1), 0xFFFFFFFF, np.uint32)
+    rep = np.zeros(1, np.dtype(_ffi.CALIB_REPORT_DTYPE))
+    st = _ffi.lib().agx_calibrate_tail(n, t.ctypes.data if t.size else None, tpf, cnt.ctypes.data, None if tst is None else tst.ctypes.data,
+                                       int(cols), int(rows), int(first_id), float(spacing_ratio), float(tag_size), model, cam, _fixed_mask(fixed),
+                                       float(damping), int(iterations), int(min_tags), int(min_frames),
+                                       _ffi.AGX_CALIB_ACCEPT_LOOSE if accept_loose else 0, pin.ctypes.data, rst.ctypes.data, fst.ctypes.data,
+                                       cam_out.ctypes.data, pose.ctypes.data, cost.ctypes.data, fn.ctypes.data, rep.ctypes.data)
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    out = calib_report(rep)
+    if out["status"] == _ffi.AGX_CALIB_OK:
+        seed = camera if isinstance(camera, Camera) else Camera(*camera)
+        out.update(camera=type(seed)(*cam_out.tolist()), pose=pose, frame_cost=cost[:n], frame_n=fn[:n])
+    if raw:
+        out.update(camera_raw=cam_out, pose_raw=pose, frame_cost_raw=cost[:n], frame_n_raw=fn[:n], report_raw=rep)
+    return out
+
+
+def calibrate_seed(h, fit_status, img_size):
+    """The closed-form seed of a calibration (agx_calibrate_seed_tail; OpenCV's initCameraMatrix2D), host only: from the
+    homographies h [N, 9] or [N, 3, 3] of board_fit (board units -> pixels) whose status word is AGX_FIT_OK or AGX_FIT_LOOSE, the
+    principal point ((w - 1) / 2, (h - 1) / 2) and fx, fy from the two orthogonality constraints per homography (Zhang 2000);
+    zero distortion.  -> dict: status AGX_CALIB_OK with camera (a pinhole Camera), or AGX_CALIB_FEW / AGX_CALIB_SINGULAR."""
+    hs = np.ascontiguousarray(h, np.float64).reshape(-1, 9)
+    fst = np.ascontiguousarray(fit_status, np.uint32).reshape(-1)
+    if hs.shape[0] != fst.shape[0]:
+        raise AgxError(_ffi.AGX_ERR_ARG, "one status word per homography")
+    cam = np.zeros(9, np.float64)
+    status = C.c_uint32(0)
+    st = _ffi.lib().agx_calibrate_seed_tail(hs.ctypes.data if hs.size else None, fst.ctypes.data if fst.size else None, int(hs.shape[0]),
+                                            int(img_size[0]), int(img_size[1]), cam.ctypes.data, C.byref(status))
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    out = {"status": status.value}
+    if status.value == _ffi.AGX_CALIB_OK:
+        out["camera"] = Camera(*cam.tolist())
+    return out
+
+
+def calib_param_jacobian(camera, xyz):
+    """For tests of the arithmetic (agx_debug_calib_param_jacobian): the derivative of the projected pixel by the camera's nine
+    doubles at points xyz [N, 3] of the camera frame -> float64 [N, 2, 9] (NaN where the point has no projection)."""
+    p = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+    out = np.zeros((p.shape[0], 2, 9), np.float64)
+    model, cam = _camera(camera)
+    st = _ffi.lib().agx_debug_calib_param_jacobian(model, cam, p.ctypes.data if p.size else None, int(p.shape[0]), out.ctypes.data if p.size else None)
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
     return out
 
 

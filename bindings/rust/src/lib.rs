@@ -908,6 +908,87 @@ pub fn board_pose_tail_m(tags: &[(u32, [(f32, f32); 4])], layout: &BoardLayout, 
     })
 }
 
+/// `agx_calib_report`: what `calibrate_tail` says about the call.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct CalibReport {
+    /// `AGX_CALIB_OK`, `AGX_CALIB_FEW` or `AGX_CALIB_SINGULAR`
+    pub status: u32,
+    /// the iterate that became the answer (0 = the inputs)
+    pub best_iter: u32,
+    /// the last iterate that was evaluated
+    pub iterations_run: u32,
+    pub n_frames_used: u32,
+    pub n_corners: u32,
+    pub reserved: u32,
+    /// the answer's RMS reprojection error in pixels
+    pub rms: f64,
+    /// the total squared residual of every iterate (NaN: not reached)
+    pub cost: [f64; 65],
+}
+
+/// One frame of `calibrate_tail`: its tag table and what `board_pose_tail_m` found for it under the seed camera.
+pub struct CalibFrame<'a> {
+    pub tags: &'a [(u32, [(f32, f32); 4])],
+    pub pose: &'a BoardPose,
+}
+
+/// The camera's nine doubles and every usable frame's pose from a batch of tag tables (`agx_calibrate_tail`, the host form: no
+/// device is used): `iterations` (0..=64) damped Gauss-Newton steps over the camera's free doubles (`fixed_mask` bit i holds
+/// double i) and all poses, the best iterate kept.  A frame is usable iff its pose's status is `AGX_FIT_OK` (`accept_loose`:
+/// `AGX_FIT_LOOSE` too) and it has `min_tags` inlier rows.  -> the camera, the poses (12 doubles: R row major, then t; `None` for
+/// a frame that was not usable) and the report; `Err(report)` under `AGX_CALIB_FEW` / `AGX_CALIB_SINGULAR`.  Panics where the
+/// library refuses the arguments.
+pub fn calibrate_tail(frames: &[CalibFrame], layout: &BoardLayout, model: LensModel, camera: &Camera, tag_size: f64, fixed_mask: u32, damping: f64,
+                      iterations: u32, min_tags: u32, min_frames: u32, accept_loose: bool) -> Result<(Camera, Vec<Option<[f64; 12]>>, CalibReport), CalibReport> {
+    let n = frames.len();
+    let tpf = frames.iter().map(|f| f.tags.len()).max().unwrap_or(0).max(1);
+    let mut table = vec![ffi::agx_tag { id: 0, xy: [0.0; 8] }; n * tpf];
+    let mut row_status = vec![ffi::AGX_FIT_ROW_OFF_BOARD as u32; n * tpf];
+    let (mut n_tags, mut fit_status, mut pose_in) = (vec![0u32; n], vec![0u32; n], vec![0f64; 12 * n]);
+    for (f, fr) in frames.iter().enumerate() {
+        for (k, t) in fr.tags.iter().enumerate() {
+            table[f * tpf + k] = ffi::agx_tag { id: t.0, xy: [t.1[0].0, t.1[0].1, t.1[1].0, t.1[1].1, t.1[2].0, t.1[2].1, t.1[3].0, t.1[3].1] };
+            row_status[f * tpf + k] = fr.pose.rows[k].0;
+        }
+        n_tags[f] = fr.tags.len() as u32;
+        fit_status[f] = fr.pose.status;
+        pose_in[12 * f..12 * f + 9].copy_from_slice(&fr.pose.r);
+        pose_in[12 * f + 9..12 * f + 12].copy_from_slice(&fr.pose.t);
+    }
+    let cam = [camera.fx, camera.fy, camera.cx, camera.cy, camera.k1, camera.k2, camera.p1, camera.p2, camera.k3];
+    let (mut cam_out, mut pose, mut cost, mut frame_n) = ([0f64; 9], vec![0f64; 12 * n], vec![0f32; n], vec![0u32; n]);
+    let mut report = CalibReport { status: 0, best_iter: 0, iterations_run: 0, n_frames_used: 0, n_corners: 0, reserved: 0, rms: 0.0, cost: [0.0; 65] };
+    let st = unsafe {
+        ffi::agx_calibrate_tail(n as c_int, table.as_ptr(), tpf as u32, n_tags.as_ptr(), std::ptr::null(), layout.cols, layout.rows, layout.first_id,
+                                layout.spacing_ratio, tag_size, model as c_int, cam.as_ptr(), fixed_mask, damping, iterations, min_tags, min_frames,
+                                if accept_loose { ffi::AGX_CALIB_ACCEPT_LOOSE } else { 0 }, pose_in.as_ptr(), row_status.as_ptr(), fit_status.as_ptr(),
+                                cam_out.as_mut_ptr(), pose.as_mut_ptr(), cost.as_mut_ptr(), frame_n.as_mut_ptr(),
+                                &mut report as *mut CalibReport as *mut std::os::raw::c_void)
+    };
+    assert_eq!(st, ffi::AGX_OK, "agx_calibrate_tail failed: {}", st);
+    if report.status as c_int != ffi::AGX_CALIB_OK {
+        return Err(report);
+    }
+    let c = Camera { fx: cam_out[0], fy: cam_out[1], cx: cam_out[2], cy: cam_out[3], k1: cam_out[4], k2: cam_out[5], p1: cam_out[6], p2: cam_out[7], k3: cam_out[8] };
+    let poses = (0..n).map(|f| if frame_n[f] > 0 { let mut p = [0f64; 12]; p.copy_from_slice(&pose[12 * f..12 * f + 12]); Some(p) } else { None }).collect();
+    Ok((c, poses, report))
+}
+
+/// The closed-form seed of a calibration (`agx_calibrate_seed_tail`, OpenCV's `initCameraMatrix2D`): a pinhole `Camera` with the
+/// principal point at the image's centre and `fx`, `fy` from the homographies `h` (row major, board units -> pixels, `board_fit_tail`'s)
+/// whose status word is `AGX_FIT_OK` or `AGX_FIT_LOOSE`.  `Err(AGX_CALIB_FEW | AGX_CALIB_SINGULAR)`.
+pub fn calibrate_seed_tail(h: &[[f64; 9]], fit_status: &[u32], img_w: i32, img_h: i32) -> Result<Camera, u32> {
+    assert!(!h.is_empty() && h.len() == fit_status.len(), "calibrate_seed_tail: one status word per homography");
+    let (mut cam, mut status) = ([0f64; 9], 0u32);
+    let st = unsafe { ffi::agx_calibrate_seed_tail(h.as_ptr() as *const f64, fit_status.as_ptr(), h.len() as u32, img_w, img_h, cam.as_mut_ptr(), &mut status) };
+    assert_eq!(st, ffi::AGX_OK, "agx_calibrate_seed_tail failed: {}", st);
+    if status as c_int != ffi::AGX_CALIB_OK {
+        return Err(status);
+    }
+    Ok(Camera { fx: cam[0], fy: cam[1], cx: cam[2], cy: cam[3], k1: 0.0, k2: 0.0, p1: 0.0, p2: 0.0, k3: 0.0 })
+}
+
 /// The ideal pinhole a batch is rectified to, and the rotation from its frame to the camera's (`None`: the identity).
 #[derive(Clone, Copy, Debug)]
 pub struct Rectification {

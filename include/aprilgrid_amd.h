@@ -1292,6 +1292,82 @@ int agx_debug_board_pose_sums_m(const agx_tag *tags, uint32_t tags_per_frame, ui
 int agx_debug_pose_atan(const double *r, uint32_t n, double *out);
 int agx_debug_pose_project(int lens_model, const double *camera, const double *xyz, uint32_t n, double *uv);
 
+/* ---- the camera from the batch: nine doubles and every frame's pose from a batch of tag tables ------------------------------- */
+
+/* What a calibration pipeline is for.  Every call above that takes a camera takes nine doubles under a lens model; this call
+ * produces them.  Inputs: the tag tables of n_frames frames (agx_collect_tags_enqueue / agx_detect_batch_enqueue_to), and what
+ * agx_board_pose_enqueue_m wrote for them under the seed camera -- d_pose_in [n_frames][12], d_row_status, d_fit_status (its
+ * d_pose, d_row_status, d_status), read in place.  A frame is usable iff its d_fit_status word is AGX_FIT_OK (AGX_FIT_LOOSE too
+ * under AGX_CALIB_ACCEPT_LOOSE), its table is within tags_per_frame and 640 rows, its d_tag_status word (when given) is
+ * AGX_TAGS_OK, and at least min_tags of its rows are marked AGX_FIT_ROW_INLIER with an id on the board; those rows' 4 corners
+ * are its correspondences.  This is fixed for the whole call: there are no outlier rounds here -- alternate this call with the
+ * pose call, whose rounds do that.
+ * Minimised: the sum of squared pixel residuals over the camera's free doubles and the 6 pose unknowns of every usable frame, by
+ * `iterations` Levenberg-damped Gauss-Newton steps with the poses eliminated frame by frame (the Schur complement): per frame the
+ * 136 sums of J^T J, J^T e and |e|^2 in agx_board_fit_enqueue's fixed order of summation, diagonals times (1 + damping), the
+ * 6 x 16 elimination; the frames' reduced 9 x 9 blocks folded in frame order by the same lane / tree rule, scaled symmetrically by
+ * their diagonal, and solved under the 2^-40 pivot rule.  csrc/calib_math.h states it once for both forms: binary64, + - * / and
+ * the correctly rounded square root, no contraction.  The parameter Jacobian is analytic for all three lens models.
+ * camera: the seed, nine HOST doubles under lens_model (agx_board_pose_enqueue_m's rules).  fixed_mask: bit i holds camera double
+ * i at the seed's bits; the slots a lens model defines as 0 are always held.  Iterate 0 is the inputs; the outputs are the
+ * iterate with the lowest finite total cost, the lowest iterate at equal cost (iterate 0 while none is finite), so the result is
+ * never worse than the inputs.  An iterate whose camera leaves the model's domain (fx <= 0, alpha outside [0, 1], ...) has cost
+ * +inf; it, an iterate with a corner that has no projection, and a refused system end the steps at the iterates so far.
+ * Results, caller-owned device memory, all required:
+ *   d_camera [9];  d_pose [n_frames][12], written for usable frames only, may be d_pose_in itself;
+ *   d_frame_n [n_frames]: the frame's correspondences (0: not usable);  d_frame_cost [n_frames]: its sum of |e|^2 at the answer;
+ *   d_report: one struct agx_calib_report (8-byte aligned) -- status AGX_CALIB_*, the answer's iterate, the last iterate
+ *     evaluated, the usable frames, their correspondences, the answer's RMS in pixels, and cost[i], the total |e|^2 of iterate i
+ *     (NaN: not reached).
+ * AGX_CALIB_FEW: fewer usable frames than min_frames, or fewer correspondences (corners) than free unknowns (free camera doubles
+ * + 6 per usable frame).  The count is of corners, not of equations, although a corner gives two: the rule is stricter than the
+ * problem needs and refuses some batches that are determined -- three frames of one tag each with eight doubles free, say (12
+ * corners, 24 equations, 26 unknowns is refused rightly; with the camera held, 12 against 18 is refused although 24 equations
+ * determine it) -- and never one that is not.  AGX_CALIB_SINGULAR: iterate 0's system is refused by the pivot rule (the frames do not determine the free
+ * doubles: fx against the distance of fronto-parallel boards, say).  Under both only d_report is written.
+ * 2 (iterations + 1) + 1 launches, stream-ordered; the state stays in a workspace on the handle and nothing returns to the host.
+ * The call replaces the batch in flight without waiting.  AGX_ERR_ARG (a batch in flight stays where it is): a NULL array
+ * (d_tag_status may be NULL), n_frames outside 1 .. 65535, tags_per_frame == 0, rows * cols outside 1 .. 4096, a spacing_ratio
+ * that is not finite or not > -1, agx_board_pose_enqueue_m's rules on lens_model, camera and tag_size, a damping that is negative
+ * or not finite, iterations > 64, min_tags or min_frames == 0, fixed_mask >= 512, an unknown flag, a binary64 array or the report
+ * not 8-byte aligned, another array not 4-byte aligned, 2^27 tag rows or more. */
+enum { AGX_CALIB_OK = 0, AGX_CALIB_FEW = 1, AGX_CALIB_SINGULAR = 2 };
+enum { AGX_CALIB_ACCEPT_LOOSE = 1 };
+struct agx_calib_report {
+    uint32_t status, best_iter, iterations_run, n_frames_used, n_corners, reserved;
+    double rms;
+    double cost[65];
+};
+typedef struct agx_calib_report agx_calib_report;
+int agx_calibrate_enqueue(agx_detector *det, int n_frames,
+                          const agx_tag *d_tags, uint32_t tags_per_frame, const uint32_t *d_n_tags, const uint32_t *d_tag_status,
+                          uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
+                          int lens_model, const double *camera,
+                          uint32_t fixed_mask, double damping, uint32_t iterations, uint32_t min_tags, uint32_t min_frames, int flags,
+                          const double *d_pose_in, const uint32_t *d_row_status, const uint32_t *d_fit_status,
+                          double *d_camera, double *d_pose, float *d_frame_cost, uint32_t *d_frame_n, void *d_report);
+/* The host form without a detector handle (no device needed): n_frames frames in host memory, the same arithmetic, order of
+ * summation and bytes.  AGX_ERR_ARG as the batch call's. */
+int agx_calibrate_tail(int n_frames,
+                       const agx_tag *tags, uint32_t tags_per_frame, const uint32_t *n_tags, const uint32_t *tag_status,
+                       uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
+                       int lens_model, const double *camera,
+                       uint32_t fixed_mask, double damping, uint32_t iterations, uint32_t min_tags, uint32_t min_frames, int flags,
+                       const double *pose_in, const uint32_t *row_status, const uint32_t *fit_status,
+                       double *camera_out, double *pose, float *frame_cost, uint32_t *frame_n, void *report);
+/* The closed-form seed, host only (OpenCV's initCameraMatrix2D): from the homographies h [n][9] of agx_board_fit_enqueue /
+ * _tail (board units -> pixels) whose fit_status word is AGX_FIT_OK or AGX_FIT_LOOSE, the principal point ((img_w - 1) / 2,
+ * (img_h - 1) / 2) and fx, fy from the 2 x 2 normal equations of the two orthogonality constraints per homography (Zhang 2000);
+ * zero distortion: camera_out [9] = fx, fy, cx, cy, 0, 0, 0, 0, 0.  *status: AGX_CALIB_OK; AGX_CALIB_FEW (no usable homography)
+ * or AGX_CALIB_SINGULAR (1 / fx^2 and 1 / fy^2 are not determined -- fronto-parallel boards -- or not positive), camera_out
+ * untouched.  AGX_ERR_ARG: a NULL array, n == 0, img_w or img_h < 1. */
+int agx_calibrate_seed_tail(const double *h, const uint32_t *fit_status, uint32_t n, int img_w, int img_h,
+                            double *camera_out, uint32_t *status);
+/* For tests of the arithmetic, no handle and no device: the 2 x 9 derivative of agx_debug_pose_project's (u, v) by the nine
+ * camera doubles at n points of the camera frame, xyz [n][3], into out [n][2][9] (NaN where the point has no projection).
+ * AGX_ERR_ARG as agx_debug_pose_project's. */
+int agx_debug_calib_param_jacobian(int lens_model, const double *camera, const double *xyz, uint32_t n, double *out);
+
 /* ---- rectified batches: the lens model applied to the pixels (csrc/rectify.hip; the arithmetic once, in csrc/rectify_math.h) ---- */
 
 /* Everything above works on the tag table, behind the detection; these three work in front of it.  The board search assumes a
