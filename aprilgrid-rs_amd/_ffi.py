@@ -48,6 +48,11 @@ AGX_CALIB_OK, AGX_CALIB_FEW, AGX_CALIB_SINGULAR = 0, 1, 2
 AGX_CALIB_ACCEPT_LOOSE = 1
 CALIB_REPORT_DTYPE = [("status", "u4"), ("best_iter", "u4"), ("iterations_run", "u4"), ("n_frames_used", "u4"), ("n_corners", "u4"),
                       ("reserved", "u4"), ("rms", "f8"), ("cost", "f8", (65,))]
+# agx_rig_calibrate_enqueue / _tail: the call's status; agx_rig_seed_tail's word per camera; agx_rig_report as a numpy dtype
+AGX_RIG_OK, AGX_RIG_FEW, AGX_RIG_SINGULAR = 0, 1, 2
+AGX_RIG_CAM_ATTACHED, AGX_RIG_CAM_DETACHED = 0, 1
+RIG_REPORT_DTYPE = [("status", "u4"), ("best_iter", "u4"), ("iterations_run", "u4"), ("n_instants_used", "u4"), ("n_frames_used", "u4"),
+                    ("n_corners", "u4"), ("n_cams_free", "u4"), ("reserved", "u4"), ("rms", "f8"), ("cost", "f8", (65,))]
 AGX_MAP_NONE = -2 ** 31  # both words of a rectification map's entry without a source pixel (agx_rectify_map_enqueue / _tail)
 # agx_render_boards_enqueue / _tail: what became of a frame; the flag under which the destination's pixels are the background
 AGX_RENDER_OK, AGX_RENDER_EMPTY, AGX_RENDER_INPUT = 0, 1, 2
@@ -214,6 +219,14 @@ SYMBOLS = {
                                      _P, _P]),
     "agx_calibrate_seed_tail": (C.c_int, [_P, _P, C.c_uint32, C.c_int, C.c_int, _P, C.POINTER(C.c_uint32)]),
     "agx_debug_calib_param_jacobian": (C.c_int, [C.c_int, C.POINTER(C.c_double), _P, C.c_uint32, _P]),
+    "agx_rig_calibrate_enqueue": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_double,
+                                            C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                            _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "agx_rig_calibrate_tail": (C.c_int, [C.c_int, C.c_int, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_double,
+                                         C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                         _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "agx_rig_seed_tail": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "agx_debug_rig_jacobian": (C.c_int, [C.c_int, C.POINTER(C.c_double), _P, _P, _P, C.c_uint32, _P]),
     "agx_rectify_map_enqueue": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t]),
     "agx_rectify_map_tail": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t]),
     "agx_remap_enqueue": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, _P, C.c_size_t, C.c_int, C.c_int, _P,

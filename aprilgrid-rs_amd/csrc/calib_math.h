@@ -351,33 +351,48 @@ AGX_HD bool calib_few(uint32_t n_usable, uint32_t n_corners, uint32_t min_frames
     return n_usable < min_frames || n_usable == 0u || (uint64_t)n_corners < (uint64_t)n_free + 6ull * n_usable;
 }
 
-// One lane, after iterate `it`'s blocks were folded (fold [CALIB_FOLD]): the best rule, the reduced solve, the next camera.
-// fold and m (CALIB_SCRATCH doubles) are indexed at run time: LDS in the kernel.
-AGX_HD void calib_step(CalibCtl &t, uint32_t it, uint32_t iterations, int lens, uint32_t held, const double *fold, double *m)
+// The best-iterate and freeze core of a call's control block, one text for calib_step here and rig_math.h's rig_step.  Ctl has
+// cost[], best_cost, frozen, have, mark_best, apply, best_it, it_run and status; *cost is iterate `it`'s folded |e|^2 (read only
+// while the state is not frozen); keep() copies the current iterate's unknowns to the best's.  -> true: a step is to be solved for.
+template <class Ctl, class Keep>
+AGX_HD bool ctl_iterate(Ctl &t, uint32_t it, uint32_t iterations, const double *cost_at, Keep keep)
 {
     t.mark_best = 0u;
     t.apply = 0u;
-    if (t.frozen) return;
-    const double cost = fold[54];
+    if (t.frozen) return false;
+    const double cost = *cost_at;
     t.cost[it] = cost;
     t.it_run = it;
     if (it == 0u || pose_better(cost, t.have != 0u, t.best_cost)) {  // (iterate 0 stands while no cost is finite)
         if (f64_finite(cost)) t.have = 1u, t.best_cost = cost;
         t.best_it = it;
         t.mark_best = 1u;
-        for (int i = 0; i < 9; ++i) t.cam_best[i] = t.cam[i];
+        keep();
     }
     if (!f64_finite(cost)) {
         t.frozen = 1u;
-        return;
+        return false;
     }
-    if (it == iterations) return;  // (the last pair gave the final iterate's cost only)
+    return it != iterations;  // (the last launches gave the final iterate's cost only)
+}
+// a refused system ends the steps; at iterate 0 it is the call's `singular` status
+template <class Ctl>
+AGX_HD void ctl_refused(Ctl &t, uint32_t it, uint32_t singular)
+{
+    if (it == 0u) t.status = singular;
+    t.frozen = 1u;
+}
+
+// One lane, after iterate `it`'s blocks were folded (fold [CALIB_FOLD]): the best rule, the reduced solve, the next camera.
+// fold and m (CALIB_SCRATCH doubles) are indexed at run time: LDS in the kernel.
+AGX_HD void calib_step(CalibCtl &t, uint32_t it, uint32_t iterations, int lens, uint32_t held, const double *fold, double *m)
+{
+    if (!ctl_iterate(t, it, iterations, fold + 54, [&]() {
+            for (int i = 0; i < 9; ++i) t.cam_best[i] = t.cam[i];
+        }))
+        return;
     double *dc = t.dc;  // (read by the next blocks launch only under apply)
-    if (fold[55] != 0.0 || !calib_reduced_solve(fold, m, dc)) {
-        if (it == 0u) t.status = AGX_CALIB_SINGULAR;
-        t.frozen = 1u;
-        return;
-    }
+    if (fold[55] != 0.0 || !calib_reduced_solve(fold, m, dc)) return ctl_refused(t, it, AGX_CALIB_SINGULAR);
     double *next = m;  // (the system is spent)
     for (int i = 0; i < 9; ++i) next[i] = (held >> i) & 1u ? t.cam[i] : t.cam[i] + dc[i];
     if (!pose_args_ok(lens, calib_camera(next), 1.0, 0u)) {  // the step leaves the model's domain: that iterate's cost is +inf
@@ -402,7 +417,16 @@ AGX_HD bool calib_args_ok(double damping, uint32_t iterations, uint32_t min_tags
 AGX_HD bool calib_frame_ok(uint32_t fit_status, int flags) { return fit_status == AGX_FIT_OK || ((flags & AGX_CALIB_ACCEPT_LOOSE) && fit_status == AGX_FIT_LOOSE); }
 AGX_HD bool calib_row_counts(const FitGeom &g, uint32_t id, uint32_t row_status) { return row_status == AGX_FIT_ROW_INLIER && fit_on_board(g, id); }
 
-// the call's report from its final state: the RMS is pose_sqrt(best cost / corners), not a number under AGX_CALIB_FEW
+// what every call's report says of its iterates, one text for calib_report here and rig_math.h's rig_report: the RMS is
+// pose_sqrt(best cost / corners), not a number under the call's `few` status
+template <class Ctl, class Rep>
+AGX_HD void ctl_report_iterates(const Ctl &t, Rep *r, uint32_t few)
+{
+    r->rms = t.status == few ? calib_nan() : pose_sqrt(t.cost[t.best_it] / (double)t.n_corners);
+    for (uint32_t i = 0; i <= CALIB_MAX_ITERATIONS; ++i) r->cost[i] = t.cost[i];
+}
+
+// the call's report from its final state
 AGX_HD void calib_report(const CalibCtl &t, agx_calib_report *r)
 {
     r->status = t.status;
@@ -411,8 +435,7 @@ AGX_HD void calib_report(const CalibCtl &t, agx_calib_report *r)
     r->n_frames_used = t.n_usable;
     r->n_corners = t.n_corners;
     r->reserved = 0u;
-    r->rms = t.status == AGX_CALIB_FEW ? calib_nan() : pose_sqrt(t.cost[t.best_it] / (double)t.n_corners);
-    for (uint32_t i = 0; i <= CALIB_MAX_ITERATIONS; ++i) r->cost[i] = t.cost[i];
+    ctl_report_iterates(t, r, AGX_CALIB_FEW);
 }
 
 }  // namespace agx

@@ -20,6 +20,8 @@
 #include "board_pose.h"
 #include "board_pose_math.h"
 #include "calibrate.h"
+#include "rig.h"
+#include "rig_math.h"
 #include "chain_kernels.h"
 #include "decimate.h"
 #include "decode_math.h"
@@ -2556,6 +2558,95 @@ int agx_debug_calib_param_jacobian(int lens_model, const double *camera, const d
     std::memcpy(&cam, camera, sizeof cam);
     if (!pose_args_ok(lens_model, cam, 1.0, 0)) return AGX_ERR_ARG;
     calib_param_jacobian_host(lens_model, cam, xyz, n, out);
+    return AGX_OK;
+    });
+}
+
+// ---- the rig from the batch (rig.hip: k_rig_blocks, k_rig_instants, k_rig_solve; rig_host.cpp) ---------------------------------
+static bool rig_record(RigArgs &a, int n_cams, int n_instants, const agx_tag *tags, uint32_t tags_per_frame, const uint32_t *n_tags, const uint32_t *tag_status,
+                       uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size, const int *lens_models, const double *cameras,
+                       double damping, uint32_t iterations, uint32_t min_tags, uint32_t min_cams, uint32_t min_instants, int flags, const double *pose_in,
+                       const uint32_t *row_status, const uint32_t *fit_status, const double *extrinsics_in, double *extrinsics, double *rig_pose,
+                       float *frame_cost, uint32_t *frame_n, uint32_t *cam_n, void *report)
+{
+    if (!lens_models || !cameras || n_cams < RIG_MIN_CAMS || n_cams > RIG_MAX_CAMS) return false;
+    a = RigArgs{};
+    a.n_cams = n_cams, a.n_instants = n_instants;
+    a.tags = tags, a.tags_per_frame = tags_per_frame, a.n_tags = n_tags, a.tag_status = tag_status;
+    a.cols = cols, a.rows = rows, a.first_id = first_id, a.spacing_ratio = spacing_ratio, a.tag_size = tag_size;
+    for (int c = 0; c < n_cams; ++c) {
+        a.lens[c] = lens_models[c];
+        std::memcpy(&a.camera[c], cameras + 9 * c, sizeof(agx_camera));
+    }
+    a.damping = damping, a.iterations = iterations, a.min_tags = min_tags, a.min_cams = min_cams, a.min_instants = min_instants, a.flags = flags;
+    a.pose_in = pose_in, a.row_status = row_status, a.fit_status = fit_status, a.ext_in = extrinsics_in, a.ext = extrinsics, a.rig_pose = rig_pose;
+    a.frame_cost = frame_cost, a.frame_n = frame_n, a.cam_n = cam_n, a.report = static_cast<agx_rig_report *>(report);
+    return true;
+}
+
+int agx_rig_calibrate_enqueue(agx_detector *det, int n_cams, int n_instants, const agx_tag *d_tags, uint32_t tags_per_frame, const uint32_t *d_n_tags,
+                              const uint32_t *d_tag_status, uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
+                              const int *lens_models, const double *cameras, double damping, uint32_t iterations, uint32_t min_tags, uint32_t min_cams,
+                              uint32_t min_instants, int flags, const double *d_pose_in, const uint32_t *d_row_status, const uint32_t *d_fit_status,
+                              const double *d_extrinsics_in, double *d_extrinsics, double *d_rig_pose, float *d_frame_cost, uint32_t *d_frame_n,
+                              uint32_t *d_cam_n, void *d_report)
+{
+    return agx_guard(det, [&]() -> int {
+    if (!det) return AGX_ERR_ARG;
+    RigArgs a;
+    if (!rig_record(a, n_cams, n_instants, d_tags, tags_per_frame, d_n_tags, d_tag_status, cols, rows, first_id, spacing_ratio, tag_size, lens_models, cameras,
+                    damping, iterations, min_tags, min_cams, min_instants, flags, d_pose_in, d_row_status, d_fit_status, d_extrinsics_in, d_extrinsics,
+                    d_rig_pose, d_frame_cost, d_frame_n, d_cam_n, d_report))
+        return fail(det, AGX_ERR_ARG, "n_cams in 2 .. 8, lens_models and cameras not null");
+    if (const char *why = rig_args_bad(a, false)) return fail(det, AGX_ERR_ARG, why);
+    HIP_TRY(det, hipSetDevice(det->device));
+    begin_batch(det);  // and there is nothing of this one to be fetched
+    void *work = side_ensure(det, SB_RIG_WORK, rig_work_bytes(n_cams, n_instants), 0);
+    if (!work) return fail(det, AGX_ERR_NOMEM, "the rig calibration's workspace");
+    const hipError_t e = (hipError_t)launch_rig_calibrate(a, work, det->stream);
+    if (e != hipSuccess) return fail(det, AGX_ERR_HIP, std::string("k_rig_blocks / k_rig_instants / k_rig_solve: ") + hipGetErrorString(e));
+    return AGX_OK;
+    });
+}
+
+int agx_rig_calibrate_tail(int n_cams, int n_instants, const agx_tag *tags, uint32_t tags_per_frame, const uint32_t *n_tags, const uint32_t *tag_status,
+                           uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size, const int *lens_models,
+                           const double *cameras, double damping, uint32_t iterations, uint32_t min_tags, uint32_t min_cams, uint32_t min_instants,
+                           int flags, const double *pose_in, const uint32_t *row_status, const uint32_t *fit_status, const double *extrinsics_in,
+                           double *extrinsics, double *rig_pose, float *frame_cost, uint32_t *frame_n, uint32_t *cam_n, void *report)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    RigArgs a;
+    if (!rig_record(a, n_cams, n_instants, tags, tags_per_frame, n_tags, tag_status, cols, rows, first_id, spacing_ratio, tag_size, lens_models, cameras,
+                    damping, iterations, min_tags, min_cams, min_instants, flags, pose_in, row_status, fit_status, extrinsics_in, extrinsics, rig_pose,
+                    frame_cost, frame_n, cam_n, report))
+        return AGX_ERR_ARG;
+    if (rig_args_bad(a, true)) return AGX_ERR_ARG;
+    rig_calibrate_host(a);
+    return AGX_OK;
+    });
+}
+
+int agx_rig_seed_tail(int n_cams, int n_instants, const double *pose, const uint32_t *fit_status, const uint32_t *frame_n, double *extrinsics_out,
+                      uint32_t *cam_status)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (!pose || !fit_status || !extrinsics_out || !cam_status || n_cams < RIG_MIN_CAMS || n_cams > RIG_MAX_CAMS || n_instants < 1 ||
+        (uint64_t)n_cams * (uint64_t)n_instants > CALIB_MAX_FRAMES)
+        return AGX_ERR_ARG;
+    rig_seed_host(n_cams, n_instants, pose, fit_status, frame_n, extrinsics_out, cam_status);
+    return AGX_OK;
+    });
+}
+
+int agx_debug_rig_jacobian(int lens_model, const double *camera, const double *extrinsic, const double *rig_pose, const double *XY, uint32_t n, double *out)
+{
+    return agx_guard(nullptr, [&]() -> int {
+    if (!camera || !rig_pose || (n && (!XY || !out))) return AGX_ERR_ARG;
+    agx_camera cam;
+    std::memcpy(&cam, camera, sizeof cam);
+    if (!pose_args_ok(lens_model, cam, 1.0, 0)) return AGX_ERR_ARG;
+    rig_jacobian_host(lens_model, cam, extrinsic, rig_pose, XY, n, out);
     return AGX_OK;
     });
 }

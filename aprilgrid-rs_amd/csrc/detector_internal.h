@@ -202,6 +202,7 @@ enum {
     SB_CLUSTERS_STATUS,  // ... and [n_frames] uint32 (AGX_CLUSTERS_*)
     SB_CLUSTERS_PLANE,   // agx_cluster_centers: the host's plane on the device
     SB_CALIB_WORK,       // agx_calibrate_enqueue: the state, the frames' blocks and poses between its launches (calibrate.h: CalibWork)
+    SB_RIG_WORK,         // agx_rig_calibrate_enqueue: the state, the frames' sums and the instants' blocks between its launches (rig.h: RigWork)
     SB_COUNT
 };
 }  // namespace agx

@@ -1357,6 +1357,103 @@ class TagDetector:
             report["frame_n"] = fn.cpu().numpy()
         return camera, pose, report
 
+    # ---- the rig from the batch (agx_rig_calibrate_enqueue) -------------------------------------------------------------------
+    @staticmethod
+    def rig_calibrate(tags, n_tags, cols, rows, cameras, poses, row_status, fit_status, extrinsics, **kw):
+        """The host form, no device needed: the module's rig_calibrate."""
+        return rig_calibrate(tags, n_tags, cols, rows, cameras, poses, row_status, fit_status, extrinsics, **kw)
+
+    @staticmethod
+    def rig_seed(poses, fit_status, frame_n=None):
+        """The closed-form seed, host only: the module's rig_seed."""
+        return rig_seed(poses, fit_status, frame_n)
+
+    def rig_calibrate_enqueue(self, tags, n_tags, cols, rows, cameras, pose_in, row_status, fit_status, extrinsics_in, extrinsics, rig_pose,
+                              frame_cost, frame_n, cam_n, report, tag_size=1.0, first_id=0, spacing_ratio=0.3, damping=0.0, iterations=10,
+                              min_tags=1, min_cams=2, min_instants=1, accept_loose=False, tag_status=None):
+        """The extrinsics of a rig's cameras and the board's pose at every usable instant from synchronised tag tables
+        (rig_calibrate, the host form, says what is computed), in device tensors and stream-ordered behind torch's current stream;
+        nothing to fetch.  tags int32 [C, S, T, 9] (camera c at instant s), n_tags and fit_status int32 [C, S], row_status int32
+        [C, S, T], pose_in float64 [C, S, 12]: the pose call's tables and answers per camera, read in place (tag_status int32
+        [C, S] or None).  cameras: C Cameras (host), held.  extrinsics_in float64 [C, 12]: the seed (rig_seed), may be
+        extrinsics itself.  extrinsics float64 [C, 12]; rig_pose float64 [S, 12]; frame_cost float32 [C, S]; frame_n int32
+        [C, S]; cam_n int32 [C]; report float64 [70], read with rig_report()."""
+        import torch
+        if not (getattr(tags, "is_cuda", False) and tags.dtype == torch.int32 and tags.is_contiguous() and tags.dim() == 4 and tags.shape[3] == 9
+                and tags.shape[2] > 0):
+            raise AgxError(_ffi.AGX_ERR_ARG, "tags must be a contiguous int32 device tensor [C, S, T, 9]")
+        nc, ns, tpf, dev = int(tags.shape[0]), int(tags.shape[1]), int(tags.shape[2]), tags.device
+
+        def tensor(t, dtype, shape, what, optional=False):
+            if t is None and optional:
+                return None
+            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == shape and t.device == dev):
+                raise AgxError(_ffi.AGX_ERR_ARG, "%s must be a contiguous %s tensor %s on the tags' device" % (what, dtype, shape))
+            return t.data_ptr()
+
+        ins = (tensor(n_tags, torch.int32, (nc, ns), "n_tags"), tensor(tag_status, torch.int32, (nc, ns), "tag_status", optional=True))
+        state = (tensor(pose_in, torch.float64, (nc, ns, 12), "pose_in"), tensor(row_status, torch.int32, (nc, ns, tpf), "row_status"),
+                 tensor(fit_status, torch.int32, (nc, ns), "fit_status"), tensor(extrinsics_in, torch.float64, (nc, 12), "extrinsics_in"))
+        outs = (tensor(extrinsics, torch.float64, (nc, 12), "extrinsics"), tensor(rig_pose, torch.float64, (ns, 12), "rig_pose"),
+                tensor(frame_cost, torch.float32, (nc, ns), "frame_cost"), tensor(frame_n, torch.int32, (nc, ns), "frame_n"),
+                tensor(cam_n, torch.int32, (nc,), "cam_n"), tensor(report, torch.float64, (70,), "report"))
+        models, cams = _rig_cameras(cameras, nc)
+        self._follow_torch_stream(tags)
+        rc = self._lib.agx_rig_calibrate_enqueue(self._h, nc, ns, tags.data_ptr(), tpf, *ins, int(cols), int(rows), int(first_id), float(spacing_ratio),
+                                                 float(tag_size), models, cams, float(damping), int(iterations), int(min_tags), int(min_cams),
+                                                 int(min_instants), _ffi.AGX_CALIB_ACCEPT_LOOSE if accept_loose else 0, *state, *outs)
+        self._enqueued(rc)
+
+    def rig_calibrate_batch(self, frames, cols, rows, cameras, tag_size=1.0, rounds=2, iterations=10, damping=0.0, first_id=0, spacing_ratio=0.3,
+                            cap=None, max_err_sq=4.0, max_drop=0, min_tags=1, min_cams=2, min_instants=1, accept_loose=True, pose_iterations=10,
+                            format=None):
+        """A rig's extrinsics from frames [C, S, H, W] resident on this detector's GPU (camera c at instant s), every stage on the
+        device: detect_batch_enqueue(out=) on the stacked batch -> `rounds` x (one board_pose_enqueue per camera on its slice, whose
+        rounds mark the outliers -> rig_calibrate_enqueue).  cameras: C calibrated Cameras, held.  Read back: the poses and status
+        words for rig_seed in the first round only, and the 560-byte report per round.  Each round's extrinsics seed the next.
+        -> (extrinsics float64 [C, 12] and rig poses float64 [S, 12] on the device, report: the last round's rig_report() with
+        cam_status (rig_seed's), cam_n, frame_n and pose_status)."""
+        import torch
+        if frames.dim() != 4:
+            raise AgxError(_ffi.AGX_ERR_ARG, "frames must be [C, S, H, W]")
+        nc, ns = int(frames.shape[0]), int(frames.shape[1])
+        n, n_board = nc * ns, int(cols) * int(rows)
+        cap = n_board if cap is None else int(cap)
+        dev = frames.device
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+        tags, counts, status = i32(n, cap, 9), i32(n), i32(n)
+        self.detect_batch_enqueue(frames.reshape(n, int(frames.shape[2]), int(frames.shape[3])), cap, out=(tags, counts, status), format=format)
+        self.detect_batch_fetch(raise_on_overflow=False)
+        err, rst, n_inl, rms, best, pred, n_pred, fst = f32(n, cap), i32(n, cap), i32(n), f32(n), i32(n), i32(n, n_board, 9), i32(n), i32(n)
+        pose, ext, rig_pose, fcost, fn, cam_n, rep = f64(n, 12), f64(nc, 12), f64(ns, 12), f32(nc, ns), i32(nc, ns), i32(nc), f64(70)
+        layout = dict(first_id=first_id, spacing_ratio=spacing_ratio)
+        report, cam_status = None, None
+        for rnd in range(int(rounds)):
+            for c in range(nc):
+                k = slice(c * ns, (c + 1) * ns)
+                self.board_pose_enqueue(tags[k], counts[k], cols, rows, cameras[c], pose[k], err[k], rst[k], n_inl[k], rms[k], best[k], pred[k],
+                                        n_pred[k], fst[k], tag_size=tag_size, max_err_sq=max_err_sq, max_drop=max_drop, min_tags=min_tags,
+                                        iterations=pose_iterations, tag_status=status[k], **layout)
+            if rnd == 0:
+                torch.cuda.current_stream(dev).synchronize()
+                seed = rig_seed(pose.cpu().numpy().reshape(nc, ns, 12), fst.cpu().numpy().astype(np.uint32).reshape(nc, ns),
+                                n_inl.cpu().numpy().astype(np.uint32).reshape(nc, ns))
+                cam_status = seed["cam_status"]
+                ext.copy_(torch.from_numpy(seed["extrinsics"]))
+            self.rig_calibrate_enqueue(tags.view(nc, ns, cap, 9), counts.view(nc, ns), cols, rows, cameras, pose.view(nc, ns, 12), rst.view(nc, ns, cap),
+                                       fst.view(nc, ns), ext, ext, rig_pose, fcost, fn, cam_n, rep, tag_size=tag_size, damping=damping,
+                                       iterations=iterations, min_tags=min_tags, min_cams=min_cams, min_instants=min_instants,
+                                       accept_loose=accept_loose, tag_status=status.view(nc, ns), **layout)
+            torch.cuda.current_stream(dev).synchronize()
+            report = rig_report(rep.cpu().numpy())
+            if report["status"] != _ffi.AGX_RIG_OK:
+                break
+        if report is not None:
+            report.update(cam_status=cam_status, cam_n=cam_n.cpu().numpy(), frame_n=fn.cpu().numpy(), pose_status=fst.cpu().numpy().reshape(nc, ns))
+        return ext, rig_pose, report
+
     # ---- rectified batches: the lens model applied to the pixels (csrc/rectify.hip) ------------------------------------------
     def _enqueued(self, rc):
         if rc == _ffi.AGX_OK:  # (a refused argument leaves the batch in flight where it is)
@@ -2653,6 +2750,115 @@ def calib_param_jacobian(camera, xyz):
     out = np.zeros((p.shape[0], 2, 9), np.float64)
     model, cam = _camera(camera)
     st = _ffi.lib().agx_debug_calib_param_jacobian(model, cam, p.ctypes.data if p.size else None, int(p.shape[0]), out.ctypes.data if p.size else None)
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    return out
+
+
+def _rig_cameras(cameras, n_cams):
+    """-> (int [C] of AGX_LENS_*, double [C * 9]) as ctypes arrays, from C Cameras (or nine numbers each)"""
+    cameras = list(cameras)
+    if len(cameras) != n_cams or not 2 <= n_cams <= 8:
+        raise AgxError(_ffi.AGX_ERR_ARG, "one camera per camera of the rig, 2 .. 8 of them")
+    pairs = [_camera(c) for c in cameras]
+    models = (C.c_int * n_cams)(*[m for m, _ in pairs])
+    nine = (C.c_double * (9 * n_cams))(*[float(v) for _, d in pairs for v in d])
+    return models, nine
+
+
+def rig_report(report):
+    """agx_rig_report's 560 bytes (rig_calibrate_enqueue's report tensor on the host) -> dict: status AGX_RIG_*, best_iter,
+    iterations_run, n_instants_used, n_frames_used, n_corners, n_cams_free, rms, cost float64 [65] (NaN: an iterate that was not
+    reached)."""
+    r = np.ascontiguousarray(report).view(np.uint8).reshape(-1)
+    if r.size != 560:
+        raise AgxError(_ffi.AGX_ERR_ARG, "a report is 560 bytes")
+    r = r.view(np.dtype(_ffi.RIG_REPORT_DTYPE))[0]
+    out = {k: int(r[k]) for k in ("status", "best_iter", "iterations_run", "n_instants_used", "n_frames_used", "n_corners", "n_cams_free")}
+    out.update(rms=float(r["rms"]), cost=r["cost"].copy())
+    return out
+
+
+def rig_calibrate(tags, n_tags, cols, rows, cameras, poses, row_status, fit_status, extrinsics, tag_size=1.0, first_id=0, spacing_ratio=0.3,
+                  damping=0.0, iterations=10, min_tags=1, min_cams=2, min_instants=1, accept_loose=False, tag_status=None, raw=False, in_place=False):
+    """The host form of rig_calibrate_enqueue (agx_rig_calibrate_tail) without a device: the extrinsics E_c (camera from rig,
+    E_0 the identity) of C = 2 .. 8 cameras and the board's pose T_s (rig from board) at every usable instant, by `iterations`
+    damped Gauss-Newton steps on the pixel residual of all inlier corners under E_c o T_s with the T_s eliminated instant by
+    instant; the iterate of the lowest cost is the answer (iterate 0 is the inputs).  tags: rows of TagDetector.TAG_DTYPE
+    [C, S, T] (camera c at instant s); n_tags [C, S]; poses float64 [C, S, 12], row_status uint32 [C, S, T] and fit_status uint32
+    [C, S]: board_pose's answers per frame under cameras[c]; extrinsics float64 [C, 12]: the seed (rig_seed).  A frame is usable
+    as calibrate's; an instant iff min_cams of its frames are; a camera without a counted frame keeps its seed.
+    -> dict: status AGX_RIG_* and rig_report's fields; for AGX_RIG_OK also extrinsics [C, 12], rig_pose [S, 12] (NaN rows for
+    unusable instants), frame_cost float32 [C, S], frame_n uint32 [C, S], cam_n uint32 [C].  raw: also the output arrays as the
+    call left them over guard values (extrinsics_raw, ...).  in_place: the seed array is the output array (the aliased call)."""
+    t = np.ascontiguousarray(tags)
+    if t.dtype != TagDetector.TAG_DTYPE or t.ndim != 3:
+        raise AgxError(_ffi.AGX_ERR_ARG, "tags must be rows of TAG_DTYPE [C, S, T]")
+    nc, ns, tpf = int(t.shape[0]), int(t.shape[1]), int(t.shape[2])
+    n = nc * ns
+    cnt = np.ascontiguousarray(n_tags, np.uint32).reshape(-1)
+    pin = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+    rst = np.ascontiguousarray(row_status, np.uint32).reshape(-1, max(tpf, 1))
+    fst = np.ascontiguousarray(fit_status, np.uint32).reshape(-1)
+    tst = None if tag_status is None else np.ascontiguousarray(tag_status, np.uint32).reshape(-1)
+    ein = np.array(extrinsics, np.float64).reshape(-1, 12)
+    if not (cnt.shape[0] == n and pin.shape[0] == n and rst.shape[0] == n and fst.shape[0] == n and (tst is None or tst.shape[0] == n) and ein.shape[0] == nc):
+        raise AgxError(_ffi.AGX_ERR_ARG, "n_tags, poses, row_status, fit_status (and tag_status) must have one entry per frame of tags, extrinsics one per camera")
+    models, cams = _rig_cameras(cameras, nc)
+    ext = ein if in_place else np.full((nc, 12), np.nan, np.float64)
+    rig_pose = np.full((max(ns, 1), 12), np.nan, np.float64)
+    cost, fn = np.full(max(n, 1), np.nan, np.float32), np.full(max(n, 1), 0xFFFFFFFF, np.uint32)
+    cam_n = np.full(nc, 0xFFFFFFFF, np.uint32)
+    rep = np.zeros(1, np.dtype(_ffi.RIG_REPORT_DTYPE))
+    st = _ffi.lib().agx_rig_calibrate_tail(nc, ns, t.ctypes.data if t.size else None, tpf, cnt.ctypes.data, None if tst is None else tst.ctypes.data,
+                                           int(cols), int(rows), int(first_id), float(spacing_ratio), float(tag_size), models, cams, float(damping),
+                                           int(iterations), int(min_tags), int(min_cams), int(min_instants),
+                                           _ffi.AGX_CALIB_ACCEPT_LOOSE if accept_loose else 0, pin.ctypes.data, rst.ctypes.data, fst.ctypes.data,
+                                           ein.ctypes.data, ext.ctypes.data, rig_pose.ctypes.data, cost.ctypes.data, fn.ctypes.data, cam_n.ctypes.data,
+                                           rep.ctypes.data)
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    out = rig_report(rep)
+    if out["status"] == _ffi.AGX_RIG_OK:
+        out.update(extrinsics=ext, rig_pose=rig_pose[:ns], frame_cost=cost[:n].reshape(nc, ns), frame_n=fn[:n].reshape(nc, ns), cam_n=cam_n)
+    if raw:
+        out.update(extrinsics_raw=ext, rig_pose_raw=rig_pose[:ns], frame_cost_raw=cost[:n], frame_n_raw=fn[:n], cam_n_raw=cam_n, report_raw=rep)
+    return out
+
+
+def rig_seed(poses, fit_status, frame_n=None):
+    """The closed-form seed of a rig calibration (agx_rig_seed_tail), host only: poses float64 [C, S, 12] and fit_status [C, S] of
+    board_pose per frame, frame_n [C, S] (correspondences per frame) or None.  Cameras attach level by level from camera 0, each
+    through the lowest-numbered camera attached earlier with which it shares an instant where both poses are AGX_FIT_OK, at the
+    shared instant with the most correspondences (the lowest at ties): E_c = pose[c, s] o pose[r, s]^-1 o E_r.
+    -> dict: extrinsics float64 [C, 12], cam_status uint32 [C] (AGX_RIG_CAM_ATTACHED, or AGX_RIG_CAM_DETACHED with the identity)."""
+    p = np.ascontiguousarray(poses, np.float64)
+    if p.ndim != 3 or p.shape[2] != 12:
+        raise AgxError(_ffi.AGX_ERR_ARG, "poses must be [C, S, 12]")
+    nc, ns = int(p.shape[0]), int(p.shape[1])
+    fst = np.ascontiguousarray(fit_status, np.uint32).reshape(-1)
+    fn = None if frame_n is None else np.ascontiguousarray(frame_n, np.uint32).reshape(-1)
+    if fst.shape[0] != nc * ns or (fn is not None and fn.shape[0] != nc * ns):
+        raise AgxError(_ffi.AGX_ERR_ARG, "one status word (and one count) per pose")
+    ext, cst = np.zeros((nc, 12), np.float64), np.zeros(nc, np.uint32)
+    st = _ffi.lib().agx_rig_seed_tail(nc, ns, p.ctypes.data if p.size else None, fst.ctypes.data if fst.size else None,
+                                      None if fn is None else fn.ctypes.data, ext.ctypes.data, cst.ctypes.data)
+    if st != _ffi.AGX_OK:
+        raise AgxError(st)
+    return {"extrinsics": ext, "cam_status": cst}
+
+
+def rig_jacobian(camera, extrinsic, rig_pose, XY):
+    """For tests of the arithmetic (agx_debug_rig_jacobian): the derivative of the projected pixel of board points XY [N, 2] under
+    camera, extrinsic [12] (None: camera 0) and rig_pose [12] by the 6 + 6 update unknowns -> float64 [N, 2, 12] (NaN where the
+    point has no projection)."""
+    p = np.ascontiguousarray(XY, np.float64).reshape(-1, 2)
+    out = np.zeros((p.shape[0], 2, 12), np.float64)
+    model, cam = _camera(camera)
+    e = None if extrinsic is None else np.ascontiguousarray(extrinsic, np.float64).reshape(12)
+    t = np.ascontiguousarray(rig_pose, np.float64).reshape(12)
+    st = _ffi.lib().agx_debug_rig_jacobian(model, cam, None if e is None else e.ctypes.data, t.ctypes.data, p.ctypes.data if p.size else None,
+                                           int(p.shape[0]), out.ctypes.data if p.size else None)
     if st != _ffi.AGX_OK:
         raise AgxError(st)
     return out

@@ -173,6 +173,12 @@ pub const AGX_CALIB_OK: c_int = 0;
 pub const AGX_CALIB_FEW: c_int = 1;
 pub const AGX_CALIB_SINGULAR: c_int = 2;
 pub const AGX_CALIB_ACCEPT_LOOSE: c_int = 1;
+// agx_rig_calibrate_enqueue / _tail: the call's status; agx_rig_seed_tail's word per camera
+pub const AGX_RIG_OK: c_int = 0;
+pub const AGX_RIG_FEW: c_int = 1;
+pub const AGX_RIG_SINGULAR: c_int = 2;
+pub const AGX_RIG_CAM_ATTACHED: c_int = 0;
+pub const AGX_RIG_CAM_DETACHED: c_int = 1;
 pub const AGX_RENDER_OK: c_int = 0;
 pub const AGX_RENDER_EMPTY: c_int = 1;
 pub const AGX_RENDER_INPUT: c_int = 2;
@@ -442,6 +448,24 @@ extern "C" {
     pub fn agx_calibrate_seed_tail(h: *const c_double, fit_status: *const u32, n: u32, img_w: c_int, img_h: c_int, camera_out: *mut c_double,
                                    status: *mut u32) -> c_int;
     pub fn agx_debug_calib_param_jacobian(lens_model: c_int, camera: *const c_double, xyz: *const c_double, n: u32, out: *mut c_double) -> c_int;
+    // the rig from the batch; d_report / report: one agx_rig_report (lib.rs: RigReport), 8-byte aligned
+    pub fn agx_rig_calibrate_enqueue(det: *mut agx_detector, n_cams: c_int, n_instants: c_int, d_tags: *const agx_tag, tags_per_frame: u32,
+                                     d_n_tags: *const u32, d_tag_status: *const u32, cols: u32, rows: u32, first_id: u32, spacing_ratio: c_float,
+                                     tag_size: c_double, lens_models: *const c_int, cameras: *const c_double, damping: c_double, iterations: u32,
+                                     min_tags: u32, min_cams: u32, min_instants: u32, flags: c_int, d_pose_in: *const c_double,
+                                     d_row_status: *const u32, d_fit_status: *const u32, d_extrinsics_in: *const c_double,
+                                     d_extrinsics: *mut c_double, d_rig_pose: *mut c_double, d_frame_cost: *mut c_float, d_frame_n: *mut u32,
+                                     d_cam_n: *mut u32, d_report: *mut c_void) -> c_int;
+    pub fn agx_rig_calibrate_tail(n_cams: c_int, n_instants: c_int, tags: *const agx_tag, tags_per_frame: u32, n_tags: *const u32,
+                                  tag_status: *const u32, cols: u32, rows: u32, first_id: u32, spacing_ratio: c_float, tag_size: c_double,
+                                  lens_models: *const c_int, cameras: *const c_double, damping: c_double, iterations: u32, min_tags: u32,
+                                  min_cams: u32, min_instants: u32, flags: c_int, pose_in: *const c_double, row_status: *const u32,
+                                  fit_status: *const u32, extrinsics_in: *const c_double, extrinsics: *mut c_double, rig_pose: *mut c_double,
+                                  frame_cost: *mut c_float, frame_n: *mut u32, cam_n: *mut u32, report: *mut c_void) -> c_int;
+    pub fn agx_rig_seed_tail(n_cams: c_int, n_instants: c_int, pose: *const c_double, fit_status: *const u32, frame_n: *const u32,
+                             extrinsics_out: *mut c_double, cam_status: *mut u32) -> c_int;
+    pub fn agx_debug_rig_jacobian(lens_model: c_int, camera: *const c_double, extrinsic: *const c_double, rig_pose: *const c_double,
+                                  XY: *const c_double, n: u32, out: *mut c_double) -> c_int;
     // rectified batches: the map (two 32-bit words per destination pixel in 1/32 source px, or AGX_MAP_NONE), the remap, points back
     pub fn agx_rectify_map_enqueue(det: *mut agx_detector, lens_model: c_int, camera: *const c_double, new_camera: *const c_double,
                                    rotation: *const c_double, src_width: c_int, src_height: c_int, dst_width: c_int, dst_height: c_int,

@@ -989,6 +989,100 @@ pub fn calibrate_seed_tail(h: &[[f64; 9]], fit_status: &[u32], img_w: i32, img_h
     Ok(Camera { fx: cam[0], fy: cam[1], cx: cam[2], cy: cam[3], k1: 0.0, k2: 0.0, p1: 0.0, p2: 0.0, k3: 0.0 })
 }
 
+/// `agx_rig_report`: what `rig_calibrate_tail` says about the call.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct RigReport {
+    /// `AGX_RIG_OK`, `AGX_RIG_FEW` or `AGX_RIG_SINGULAR`
+    pub status: u32,
+    /// the iterate that became the answer (0 = the inputs)
+    pub best_iter: u32,
+    /// the last iterate that was evaluated
+    pub iterations_run: u32,
+    pub n_instants_used: u32,
+    pub n_frames_used: u32,
+    pub n_corners: u32,
+    /// the cameras c >= 1 with a counted frame
+    pub n_cams_free: u32,
+    pub reserved: u32,
+    /// the answer's RMS reprojection error in pixels
+    pub rms: f64,
+    /// the total squared residual of every iterate (NaN: not reached)
+    pub cost: [f64; 65],
+}
+
+/// One camera of a rig for `rig_calibrate_tail`: its lens model and nine doubles (held), and its frames, one per instant.
+pub struct RigCamera<'a> {
+    pub model: LensModel,
+    pub camera: Camera,
+    pub frames: &'a [CalibFrame<'a>],
+}
+
+/// The extrinsics of a rig's cameras and the board's pose at every usable instant (`agx_rig_calibrate_tail`, the host form: no
+/// device is used).  `cams`: 2..=8 cameras with one frame per instant each; `seed`: camera-from-rig per camera, 12 doubles (R row
+/// major, then t; entry 0 is not read), `rig_seed_tail`'s.  An instant is usable iff `min_cams` of its frames are.  -> the
+/// extrinsics (entry 0 the identity), the rig-from-board pose per instant (`None`: not usable) and the report; `Err(report)` under
+/// `AGX_RIG_FEW` / `AGX_RIG_SINGULAR`.  Panics where the library refuses the arguments.
+pub fn rig_calibrate_tail(cams: &[RigCamera], layout: &BoardLayout, tag_size: f64, seed: &[[f64; 12]], damping: f64, iterations: u32, min_tags: u32,
+                          min_cams: u32, min_instants: u32, accept_loose: bool) -> Result<(Vec<[f64; 12]>, Vec<Option<[f64; 12]>>, RigReport), RigReport> {
+    let (nc, ns) = (cams.len(), cams.first().map(|c| c.frames.len()).unwrap_or(0));
+    assert!(seed.len() == nc && cams.iter().all(|c| c.frames.len() == ns), "rig_calibrate_tail: one seed per camera, one frame per camera and instant");
+    let n = nc * ns;
+    let tpf = cams.iter().flat_map(|c| c.frames.iter()).map(|f| f.tags.len()).max().unwrap_or(0).max(1);
+    let mut table = vec![ffi::agx_tag { id: 0, xy: [0.0; 8] }; n * tpf];
+    let mut row_status = vec![ffi::AGX_FIT_ROW_OFF_BOARD as u32; n * tpf];
+    let (mut n_tags, mut fit_status, mut pose_in) = (vec![0u32; n], vec![0u32; n], vec![0f64; 12 * n]);
+    let (mut models, mut cameras) = (vec![0 as c_int; nc], vec![0f64; 9 * nc]);
+    for (c, cam) in cams.iter().enumerate() {
+        models[c] = cam.model as c_int;
+        let k = &cam.camera;
+        cameras[9 * c..9 * c + 9].copy_from_slice(&[k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2, k.k3]);
+        for (s, fr) in cam.frames.iter().enumerate() {
+            let f = c * ns + s;
+            for (i, t) in fr.tags.iter().enumerate() {
+                table[f * tpf + i] = ffi::agx_tag { id: t.0, xy: [t.1[0].0, t.1[0].1, t.1[1].0, t.1[1].1, t.1[2].0, t.1[2].1, t.1[3].0, t.1[3].1] };
+                row_status[f * tpf + i] = fr.pose.rows[i].0;
+            }
+            n_tags[f] = fr.tags.len() as u32;
+            fit_status[f] = fr.pose.status;
+            pose_in[12 * f..12 * f + 9].copy_from_slice(&fr.pose.r);
+            pose_in[12 * f + 9..12 * f + 12].copy_from_slice(&fr.pose.t);
+        }
+    }
+    let ext_in: Vec<f64> = seed.iter().flat_map(|e| e.iter().copied()).collect();
+    let (mut ext, mut rig_pose, mut cost, mut frame_n, mut cam_n) = (vec![0f64; 12 * nc], vec![0f64; 12 * ns], vec![0f32; n], vec![0u32; n], vec![0u32; nc]);
+    let mut report = RigReport { status: 0, best_iter: 0, iterations_run: 0, n_instants_used: 0, n_frames_used: 0, n_corners: 0, n_cams_free: 0, reserved: 0,
+                                 rms: 0.0, cost: [0.0; 65] };
+    let st = unsafe {
+        ffi::agx_rig_calibrate_tail(nc as c_int, ns as c_int, table.as_ptr(), tpf as u32, n_tags.as_ptr(), std::ptr::null(), layout.cols, layout.rows,
+                                    layout.first_id, layout.spacing_ratio, tag_size, models.as_ptr(), cameras.as_ptr(), damping, iterations, min_tags,
+                                    min_cams, min_instants, if accept_loose { ffi::AGX_CALIB_ACCEPT_LOOSE } else { 0 }, pose_in.as_ptr(),
+                                    row_status.as_ptr(), fit_status.as_ptr(), ext_in.as_ptr(), ext.as_mut_ptr(), rig_pose.as_mut_ptr(), cost.as_mut_ptr(),
+                                    frame_n.as_mut_ptr(), cam_n.as_mut_ptr(), &mut report as *mut RigReport as *mut std::os::raw::c_void)
+    };
+    assert_eq!(st, ffi::AGX_OK, "agx_rig_calibrate_tail failed: {}", st);
+    if report.status as c_int != ffi::AGX_RIG_OK {
+        return Err(report);
+    }
+    let twelve = |v: &[f64], i: usize| { let mut p = [0f64; 12]; p.copy_from_slice(&v[12 * i..12 * i + 12]); p };
+    let extrinsics = (0..nc).map(|c| twelve(&ext, c)).collect();
+    let poses = (0..ns).map(|s| if (0..nc).any(|c| frame_n[c * ns + s] > 0) { Some(twelve(&rig_pose, s)) } else { None }).collect();
+    Ok((extrinsics, poses, report))
+}
+
+/// The closed-form seed of a rig calibration (`agx_rig_seed_tail`): `pose[c][s]` (12 doubles) and `fit_status[c][s]` of
+/// `board_pose_tail_m` per frame.  -> per camera its extrinsic, `None` for a camera that could not be attached.
+pub fn rig_seed_tail(pose: &[Vec<[f64; 12]>], fit_status: &[Vec<u32>]) -> Vec<Option<[f64; 12]>> {
+    let (nc, ns) = (pose.len(), pose.first().map(|p| p.len()).unwrap_or(0));
+    assert!(fit_status.len() == nc && pose.iter().zip(fit_status).all(|(p, f)| p.len() == ns && f.len() == ns), "rig_seed_tail: one status word per pose");
+    let flat: Vec<f64> = pose.iter().flat_map(|p| p.iter().flat_map(|e| e.iter().copied())).collect();
+    let fst: Vec<u32> = fit_status.iter().flat_map(|f| f.iter().copied()).collect();
+    let (mut ext, mut status) = (vec![0f64; 12 * nc], vec![0u32; nc]);
+    let st = unsafe { ffi::agx_rig_seed_tail(nc as c_int, ns as c_int, flat.as_ptr(), fst.as_ptr(), std::ptr::null(), ext.as_mut_ptr(), status.as_mut_ptr()) };
+    assert_eq!(st, ffi::AGX_OK, "agx_rig_seed_tail failed: {}", st);
+    (0..nc).map(|c| if status[c] as c_int == ffi::AGX_RIG_CAM_ATTACHED { let mut p = [0f64; 12]; p.copy_from_slice(&ext[12 * c..12 * c + 12]); Some(p) } else { None }).collect()
+}
+
 /// The ideal pinhole a batch is rectified to, and the rotation from its frame to the camera's (`None`: the identity).
 #[derive(Clone, Copy, Debug)]
 pub struct Rectification {

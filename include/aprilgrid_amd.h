@@ -1368,6 +1368,89 @@ int agx_calibrate_seed_tail(const double *h, const uint32_t *fit_status, uint32_
  * AGX_ERR_ARG as agx_debug_pose_project's. */
 int agx_debug_calib_param_jacobian(int lens_model, const double *camera, const double *xyz, uint32_t n, double *out);
 
+/* ---- the rig from the batch: the cameras' extrinsics and the board's pose at every instant from synchronised tag tables ------- */
+
+/* What the people who print AprilGrids calibrate with them: stereo pairs, multi-camera heads, a fisheye next to a pinhole.
+ * n_cams cameras (2 .. 8) look at one board at n_instants synchronised instants; frame f = c * n_instants + s is camera c at
+ * instant s, n_cams * n_instants in 1 .. 65535; every array "per frame" is in that order.  Each camera has its own lens model
+ * and nine doubles (lens_models [n_cams], cameras [n_cams][9]: HOST memory, copied by the call; held here -- alternate with
+ * agx_calibrate_enqueue per camera to move them).
+ * Unknowns: E_c, camera from rig, for c = 1 .. n_cams - 1 (E_0 is the identity and is never written differently: that fixes the
+ * gauge), and T_s, rig from board, for every usable instant; both 12 doubles, R row major then t, d_pose's layout.  Minimised: the
+ * sum over the counted frames' inlier corners of | project<lens_c>(camera_c, E_c o T_s o X) - observed |^2.
+ * A frame is usable by agx_calibrate_enqueue's rule, word for word (d_fit_status, AGX_CALIB_ACCEPT_LOOSE, d_tag_status, the 640
+ * rows, min_tags inlier rows on the board).  An instant is usable iff at least min_cams (>= 1; 2 is the usual choice) of its
+ * frames are; the frames of an unusable instant do not count.  A camera c >= 1 without a counted frame is held: d_extrinsics[c]
+ * keeps the seed's bits and d_cam_n[c] = 0.
+ * Inputs read in place: d_pose_in [frames][12], d_row_status, d_fit_status as agx_board_pose_enqueue_m wrote them under each
+ * camera; d_extrinsics_in [n_cams][12], the seed (agx_rig_seed_tail), which may be d_extrinsics itself; entry 0 is not read.
+ * T_s's seed is made on the device: E_c^-1 o pose_in[c, s] for the lowest usable c of the instant.
+ * The arithmetic (csrc/rig_math.h, once for both forms; binary64, + - * / and the correctly rounded square root, no
+ * contraction): the update is agx_board_pose_enqueue's local Cayley update (R <- R C(w), t <- t + dt) on E_c and on T_s; per
+ * counted frame the 91 sums of the 12 x 12 J^T J over [dE_c | dT_s], J^T e and |e|^2 in agx_board_fit_enqueue's fixed order
+ * (camera 0's frames the T_s part alone, 28); per instant V_s and its gradient summed in camera order, diagonals times
+ * (1 + damping), the 6 x 6 elimination, and the instant's contribution to the reduced 6 (n_cams - 1) square system, dense across
+ * the cameras that share the instant; the contributions folded in instant order by agx_calibrate_enqueue's lane / tree rule,
+ * scaled symmetrically by the diagonal and solved with partial pivoting under the 2^-40 rule; back-substitution gives dT_s.
+ * Iterate 0 is the inputs; the answer is the iterate with the lowest finite total cost, the lowest iterate at ties, so it is
+ * never worse than the inputs; a corner without a projection or a refused system ends the steps at the iterates so far.  A seed
+ * extrinsic that is not finite cannot be refused here (it is device memory): it makes iterate 0's cost not finite, the call
+ * ends at iterate 0 and the seed is the answer.
+ * Results, caller-owned device memory, all required: d_extrinsics [n_cams][12] (entry 0 the identity); d_rig_pose
+ * [n_instants][12], written for usable instants only; d_frame_n [frames]: the frame's correspondences (0: not counted);
+ * d_frame_cost [frames]: its sum of |e|^2 at the answer; d_cam_n [n_cams]: the camera's counted frames; d_report: one struct
+ * agx_rig_report (8-byte aligned).
+ * AGX_RIG_FEW: fewer usable instants than min_instants, no free camera, or fewer corners than 6 * n_cams_free + 6 *
+ * n_instants_used.  AGX_RIG_SINGULAR: iterate 0's reduced system is refused by the pivot rule -- undamped, two groups of cameras
+ * that never share an instant (cameras 0, 1 at some instants, 2, 3 at others, min_cams = 2: nothing ties the second group to the
+ * first).  Under both only d_report is written.
+ * 3 (iterations + 1) launches (k_rig_blocks, k_rig_instants, k_rig_solve per iterate), stream-ordered; the state stays in a
+ * workspace on the handle and nothing returns to the host.  The call replaces the batch in flight without waiting.
+ * AGX_ERR_ARG (a batch in flight stays where it is): a NULL array (d_tag_status may be NULL), n_cams outside 2 .. 8, a frame
+ * count outside 1 .. 65535, agx_board_pose_enqueue_m's rules on any camera and on tag_size, agx_calibrate_enqueue's rules on
+ * the layout, damping, iterations, min_tags, min_instants (as its min_frames), flags and alignment, min_cams == 0. */
+enum { AGX_RIG_OK = 0, AGX_RIG_FEW = 1, AGX_RIG_SINGULAR = 2 };
+enum { AGX_RIG_CAM_ATTACHED = 0, AGX_RIG_CAM_DETACHED = 1 };
+struct agx_rig_report {
+    uint32_t status, best_iter, iterations_run, n_instants_used, n_frames_used, n_corners, n_cams_free, reserved;
+    double rms;
+    double cost[65];
+};
+typedef struct agx_rig_report agx_rig_report;
+int agx_rig_calibrate_enqueue(agx_detector *det, int n_cams, int n_instants,
+                              const agx_tag *d_tags, uint32_t tags_per_frame, const uint32_t *d_n_tags, const uint32_t *d_tag_status,
+                              uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
+                              const int *lens_models, const double *cameras,
+                              double damping, uint32_t iterations, uint32_t min_tags, uint32_t min_cams, uint32_t min_instants, int flags,
+                              const double *d_pose_in, const uint32_t *d_row_status, const uint32_t *d_fit_status,
+                              const double *d_extrinsics_in, double *d_extrinsics, double *d_rig_pose,
+                              float *d_frame_cost, uint32_t *d_frame_n, uint32_t *d_cam_n, void *d_report);
+/* The host form without a detector handle (no device needed): the same arithmetic, order of summation and bytes.  AGX_ERR_ARG
+ * as the batch call's, and a seed extrinsic that is not finite (readable here). */
+int agx_rig_calibrate_tail(int n_cams, int n_instants,
+                           const agx_tag *tags, uint32_t tags_per_frame, const uint32_t *n_tags, const uint32_t *tag_status,
+                           uint32_t cols, uint32_t rows, uint32_t first_id, float spacing_ratio, double tag_size,
+                           const int *lens_models, const double *cameras,
+                           double damping, uint32_t iterations, uint32_t min_tags, uint32_t min_cams, uint32_t min_instants, int flags,
+                           const double *pose_in, const uint32_t *row_status, const uint32_t *fit_status,
+                           const double *extrinsics_in, double *extrinsics, double *rig_pose,
+                           float *frame_cost, uint32_t *frame_n, uint32_t *cam_n, void *report);
+/* The closed-form seed, host only: pose [frames][12] and fit_status [frames] of agx_board_pose_enqueue_m per camera; frame_n
+ * [frames] (correspondences per frame) or NULL.  Cameras are attached level by level from camera 0: a camera c that is not
+ * attached yet attaches through the lowest-numbered camera r attached in an earlier level with which it shares an instant where
+ * both status words are AGX_FIT_OK (and, with frame_n, both counts are > 0); among those instants the one with the largest
+ * frame_n[c, s] + frame_n[r, s], the lowest s at ties (and with frame_n NULL);  E_c = pose[c, s] o pose[r, s]^-1 o E_r.
+ * extrinsics_out [n_cams][12]; cam_status [n_cams]: AGX_RIG_CAM_ATTACHED, or AGX_RIG_CAM_DETACHED with the identity.
+ * AGX_ERR_ARG: a NULL array (frame_n may be NULL), n_cams outside 2 .. 8, a frame count outside 1 .. 65535. */
+int agx_rig_seed_tail(int n_cams, int n_instants, const double *pose, const uint32_t *fit_status, const uint32_t *frame_n,
+                      double *extrinsics_out, uint32_t *cam_status);
+/* For tests of the arithmetic, no handle and no device: the derivative of the projected pixel of the board points XY [n][2]
+ * (Z = 0) under camera, extrinsic [12] and rig_pose [12] by the 6 + 6 update unknowns (w, dt of E_c, then of T_s; the residual
+ * observed - projected has the opposite sign), out [n][2][12]; NaN where the point has no projection.  extrinsic NULL: camera
+ * 0, whose first six columns are 0.  AGX_ERR_ARG as agx_debug_pose_project's. */
+int agx_debug_rig_jacobian(int lens_model, const double *camera, const double *extrinsic, const double *rig_pose, const double *XY,
+                           uint32_t n, double *out);
+
 /* ---- rectified batches: the lens model applied to the pixels (csrc/rectify.hip; the arithmetic once, in csrc/rectify_math.h) ---- */
 
 /* Everything above works on the tag table, behind the detection; these three work in front of it.  The board search assumes a
